@@ -291,6 +291,36 @@ def sharded_step_fn(job, ctx, engine, fetch, nt_total, warm_up, window, mode, bo
     return step
 
 
+DUMP_SAMPLE = 1 << 22    # payload elements written by --dump-outputs (16 MB as float32)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, state, dev):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files (< 64 MB in all).
+    The int16 payload (80 x 512 x 512 x 3 elements) is too large to write whole: payload_sample.npy holds the elements at
+    DUMP_SAMPLE fixed, seeded, sorted positions, and payload_frame_sum.npy / payload_frame_sumsq.npy sum every element of
+    each frame (exact in float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    key = np.asarray(state["key"])
+    pl = state["payload"]
+    pl = torch.from_numpy(pl).to(dev) if isinstance(pl, np.ndarray) else pl
+    pl = pl.reshape(-1)
+    n = pl.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+        sample = pl[torch.from_numpy(idx).to(dev)]
+    else:
+        sample = pl
+    per_frame = pl.to(torch.int64).reshape(key.size, -1)
+    out = {"key": key.astype(np.float32),
+           "table": np.asarray(state["table"]).astype(np.float32),
+           "payload_sample": sample.float().cpu().numpy(),
+           "payload_frame_sum": per_frame.sum(1).cpu().numpy().astype(np.float64),
+           "payload_frame_sumsq": (per_frame * per_frame).sum(1).cpu().numpy().astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def verify_against_one_gpu(ctx, frames_full, warm_up, window, mode, bound, state, max_batch, hp, wp):
     """Rank 0, untimed: the sharded payload / table / key mask must equal a single-GPU run."""
     ctx.prepare(hp, wp, max_batch)
@@ -321,6 +351,9 @@ def main():
     ap.add_argument("--profile-legs", action="store_true",
                     help="with --no-extras: still run ONE untimed `abs 2` encode and ONE decode of the job, so that a rocprofv3 "
                          "trace of this command also holds the lossy-tail and the decoder kernels (profiles/collect.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: "
+                         "key, table, a fixed sample of the payload and per-frame sums of the whole payload")
     ap.add_argument("--frames", type=int, default=NT,
                     help="frames per GPU (default 80 = the BASELINE.json configuration; other values are "
                          "exploration only and are labelled as such in config.workload)")
@@ -395,6 +428,8 @@ def main():
     elapsed = job.timed(step, args.steps, args.warmup, drain=getattr(step, "drain", None))
     total_frames = (nt_total if sharded else nt_rank * world) * args.steps
     value = total_frames / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state, dev)
 
     check = None
     if sharded and world > 1 and rank == 0:

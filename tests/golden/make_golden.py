@@ -21,14 +21,20 @@ What it does:
   * (round 5) instantiates the reference's own `PredNet` class (prednet.py) over numpy stand-ins for the Keras surface it
     touches (tests/golden/keras_standin.py) and runs its build / get_initial_state / step -> ref_prednet.npz.
 
+  * records which directory-listing calls and which file names the reference's decompress.py mentions (counts of
+    fixed words in its text, and the text's sha256) -> ref_decoder_io.json, read by tests/test_sidecar.py.
+
 Every file regenerates bit for bit except ref_train.npz, whose folder order inside a split follows the reference's `set()`
 iteration (string hashing: PYTHONHASHSEED); the tests compare it per folder.
 
-Run:  /opt/conda/bin/python3.9 tests/golden/make_golden.py      (--train-only: just ref_train.npz; --prednet-only: just ref_prednet.npz; --runs4-only: just ref_runs4.npz)
+Run:  /opt/conda/bin/python3.9 tests/golden/make_golden.py      (--train-only: just ref_train.npz; --prednet-only: just ref_prednet.npz; --runs4-only: just ref_runs4.npz;
+      --decoder-io-only: just ref_decoder_io.json)
 (python3.9 + numpy 1.26 because the reference calls ndarray.tostring(), removed in numpy 2.)
-Nothing from the reference's source text is written to the fixtures: only arrays.
+Nothing from the reference's source text is written to the fixtures: only arrays, and word counts.
 """
+import hashlib
 import io
+import json
 import os
 import shutil
 import sys
@@ -602,7 +608,26 @@ def _prednet_fixture(out):
             name, len(layer.trainable_weights), X_hat.shape, float(np.abs(X_hat[0, 1] - X[0, 0]).mean())))
 
 
+DECODER_WORDS = ("listdir", "glob", "scandir", "walk", "filename.txt", "key_frame.dat", "entropy.dat")
+
+
+def _decoder_io_fixture():
+    """How the reference's decoder finds its inputs: occurrences of the directory-listing calls and of the three file
+    names in the text of decompress.py.  Words and counts only."""
+    src = open(os.path.join(REF, "decompress.py"), "rb").read()
+    text = src.decode("utf-8")
+    doc = {"file": "src/decompress.py", "sha256": hashlib.sha256(src).hexdigest(),
+           "occurrences": {w: text.count(w) for w in DECODER_WORDS}}
+    with open(os.path.join(HERE, "ref_decoder_io.json"), "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return doc
+
+
 def main():
+    if "--decoder-io-only" in sys.argv:
+        print("ref_decoder_io.json:", _decoder_io_fixture())
+        return
     _install_stubs()
     if "--prednet-only" in sys.argv:
         pn = {}
@@ -662,6 +687,7 @@ def main():
     _prednet_fixture(pn)
     np.savez_compressed(os.path.join(HERE, "ref_prednet.npz"), **pn)
     print("ref_prednet.npz:", len(pn), "arrays")
+    print("ref_decoder_io.json:", _decoder_io_fixture())
 
 
 if __name__ == "__main__":

@@ -5,7 +5,9 @@ spawn again."""
 import os
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 from conftest import ROOT
 
@@ -127,3 +129,36 @@ def test_stage_log_collects_without_printing(monkeypatch, capsys):
     compress._Stages().mark("c")
     out = capsys.readouterr()
     assert out.out == "" and out.err == ""
+
+
+def test_timed_runs_exactly_the_requested_steps(bench, monkeypatch):
+    """`--steps K --warmup W`: W untimed calls, then exactly K timed ones (checked on the CPU: synchronize is a no-op)."""
+    monkeypatch.setattr(bench.torch.cuda, "synchronize", lambda *a: None)
+    calls = []
+    job = bench.Job(0, 1, None, "cpu")
+    job.timed(lambda: calls.append(1), 7, 2, drain=lambda: calls.append("d"))
+    assert calls == [1, 1, "d"] + [1] * 7 + ["d"]
+
+
+def test_dump_outputs_writes_the_step_result_as_float_arrays(bench, tmp_path):
+    """--dump-outputs: key, table, a seeded sample of the payload and exact per-frame sums, float32 / float64, under 64 MB;
+    the same state gives the same files."""
+    nt, per = 6, 512 * 512 * 3
+    rng = np.random.default_rng(1)
+    payload = torch.from_numpy(rng.integers(-300, 300, nt * per).astype(np.int16))
+    state = {"payload": payload, "key": np.array([1, 0, 0, 1, 0, 0], bool), "table": np.array([0, -1, 1, 5], np.int16)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), state, "cpu")
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["key.npy", "payload_frame_sum.npy", "payload_frame_sumsq.npy", "payload_sample.npy", "table.npy"]
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        np.testing.assert_array_equal(got[f[:-4]], np.load(tmp_path / "b" / f))
+    p = payload.numpy().reshape(nt, per).astype(np.int64)
+    np.testing.assert_array_equal(got["payload_frame_sum"], p.sum(1))
+    np.testing.assert_array_equal(got["payload_frame_sumsq"], (p * p).sum(1))
+    np.testing.assert_array_equal(got["key"], [1, 0, 0, 1, 0, 0])
+    np.testing.assert_array_equal(got["table"], [0, -1, 1, 5])
+    assert got["payload_sample"].size == bench.DUMP_SAMPLE and set(np.unique(got["payload_sample"])) <= set(range(-300, 300))
