@@ -223,6 +223,45 @@ int tz_decoded_get(tz_ctx* ctx, int first, int count, uint8_t* out);
  * int16 delta stack (sharded decoding: the inverse scan carry comes from the previous shard). */
 int tz_decode_delta(tz_ctx* ctx, const int16_t* delta, uint8_t* frames_out);
 
+/* ---- range decode (no reference counterpart: decompress.py:39 always writes every frame) -------------------
+ * Frames [first, first + count) of a stream without the whole-sequence work.  The predictor restarts at every key frame
+ * (decompress.py:143-175) and the inverse spatial delta (decompress.py:22-29) needs only the decoded element in front of
+ * the range, so a range costs one read of the payload prefix (tz_undelta_carry), the predictor steps from the range's
+ * restart frame to its last frame, and the scan + reconstruct of the range alone.
+ * tz_range_restart (host only, like tz_build_table): the frame at which a decoder must start its rollout to reproduce
+ * frame `first` bit for bit.  key_mask[nt]: the key frames key discovery finds (decompress.py:123-129: any non-zero
+ * sample).  Rule: the largest key frame k with warm_up < k <= first, else 0.  A rollout from such a k is the sub-stack
+ * [k, end) replayed with warm_up = 0: its predictions depend on frame k alone and frame k is its own base, as in the
+ * whole-stack replay.  A rollout from 0 is the sub-stack [0, end) with the job's warm_up; it must reach frame warm_up
+ * (the replay's key-interval walk starts there), so tz_rollout_decode_range extends it to max(end, warm_up + 1) frames
+ * and returns nothing of the extension.  A sub-stack needs no other minimum length (a lone key frame is a 1-frame
+ * replay); the length conditions of the sharded decoder's cuts (tezip_amd/dist.py) concern the shard in FRONT of a cut,
+ * which a range never decodes.  Key frames k in (0, warm_up] are not restarts: frames below warm_up are C0 copies in the
+ * replay, and from k = warm_up the predictor does exactly the steps a restart at 0 does.  Any earlier valid restart is
+ * also correct, only slower. */
+int tz_range_restart(const uint8_t* key_mask, int nt, int warm_up, int first, int* restart);
+/* tz_rollout_decode_range: tz_rollout_decode for frames [first, first + count) only.  Key discovery runs over the whole
+ * stack (key_mask[nt], host, receives it); the predictor runs over [restart, first + count) (plus the extension above)
+ * of the resident stack, and the prediction stack holds those frames only.  key_frames == NULL: the stack staged with
+ * tz_frames_begin / tz_frames_put, whose nt, H, W must be the call's (else TZ_ERR_INVALID).  The short stack serves
+ * tz_decode_range only: tz_decode / tz_get_predictions / tz_decode_delta report TZ_ERR_STATE until the next whole
+ * rollout.  TZ_ERR_INVALID for first / count outside [0, nt). */
+int tz_rollout_decode_range(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, int first, int count,
+                            uint8_t* key_mask);
+/* tz_undelta_carry: the decoded element x[n0-1] of the inverse spatial delta over payload[0, n0), i.e.
+ * -(sum of s'[0..n0)) mod 2^16 with s'[0] = -s[0] (k_undelta_carry: one read of the prefix, 2 B/element).
+ * payload == NULL: the payload staged with tz_payload_begin / tz_payload_put.  table_len == -1: the payload holds the
+ * symbols as they are (no remap), else the inverse rank remap and 1600 - x of decompress.py:31-36,236 apply first, as in
+ * tz_decode.  n0 == 0 is TZ_ERR_INVALID: the stream start has no carry.  *carry (host) receives the element. */
+int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, const int16_t* table, int table_len, int16_t* carry);
+/* tz_decode_range: tz_decode for frames [first, first + count), on the prediction stack of the last
+ * tz_rollout_decode_range (the range must lie inside the frames that call covered).  payload_len is the WHOLE stream,
+ * nt*H*W*3, checked as tz_decode checks it; elements behind the range are not read.  For first > 0 the scan starts from
+ * tz_undelta_carry's element over [0, first*H*W*3).  frames_out: count*H*W*3 uint8, or NULL to keep the frames in the
+ * context for tz_decoded_get, whose frame indices are then sequence indices inside [first, first + count). */
+int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len, int first,
+                    int count, uint8_t* frames_out);
+
 /* ---- operator seams, usable stand-alone (each mirrors one reference helper) -----------------
  * tz_delta_encode: compress.py:292-314.  pred: nframes padded f32 frames; orig: nframes
  * unpadded u8 frames; zero_mask[nframes] (host): 1 => that frame's delta is forced to 0. */

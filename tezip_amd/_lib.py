@@ -48,6 +48,11 @@ _SIGS = {
     "tz_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                              C.c_void_p, C.c_void_p]),
     "tz_rollout_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_range_restart": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "tz_rollout_decode_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p]),
+    "tz_undelta_carry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_int16)]),
+    "tz_decode_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tz_frames_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "tz_frames_put": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_frames_fence": (C.c_int, [C.c_void_p]),
@@ -132,6 +137,16 @@ def diagnostic_defines(lib=None):
 
 def pad8(v):
     return (v + 7) // 8 * 8
+
+
+def range_restart(key_mask, warm_up, first):
+    """tz_range_restart (host only): the frame a decoder restarts its rollout at to reproduce frame `first`."""
+    km = np.ascontiguousarray(key_mask, np.uint8)
+    r = C.c_int(0)
+    rc = load().tz_range_restart(km.ctypes.data, int(km.size), int(warm_up), int(first), C.byref(r))
+    if rc != TZ_OK:
+        raise TezipError(rc, "tz_range_restart: first=%d outside a %d-frame mask, or warm_up=%d < 0" % (first, km.size, warm_up))
+    return r.value
 
 
 def _numel(x):
@@ -415,6 +430,20 @@ class Context:
         self._shape = (nt, h, w)
         return key.astype(bool)
 
+    def rollout_decode_range(self, key_frames, warm_up, first, count):
+        """tz_rollout_decode for frames [first, first + count) only; key_frames as for rollout_decode.  Returns the key mask
+        of the whole stack."""
+        if key_frames is None:
+            nt, h, w = self._staged
+        else:
+            self._check_stack(key_frames, "key_frames")
+            nt, h, w = key_frames.shape[:3]
+        key = np.zeros(nt, np.uint8)
+        self._ck(self.lib.tz_rollout_decode_range(self.h, None if key_frames is None else _ptr(key_frames, np.uint8), nt, h, w,
+                                                  warm_up, int(first), int(count), key.ctypes.data))
+        self._shape = (nt, h, w)
+        return key.astype(bool)
+
     def get_predictions(self, out=None):
         """out: a host or device buffer of nt*Hp*Wp*3 float32 (default: a new numpy array)."""
         nt, h, w = self._shape
@@ -532,6 +561,24 @@ class Context:
         self._ck(self.lib.tz_decode(self.h, None if payload is None else _ptr(payload), n, _ptr(tb), tl, _ptr(out)))
         return out
 
+    def decode_range(self, payload, table, first, count, out=None):
+        """tz_decode_range: frames [first, first + count) after rollout_decode_range.  payload: the WHOLE stream (or None
+        after payload_begin / payload_put); out="resident" keeps the frames for decoded_get (sequence indices)."""
+        nt, h, w = self._shape
+        n = nt * h * w * 3
+        if payload is not None and _numel(payload) != n:  # decompress.py:240: the reference's reshape raises
+            raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
+        resident = isinstance(out, str) and out == "resident"
+        if resident:
+            out = None
+        elif out is None:
+            out = np.empty((int(count), h, w, 3), np.uint8)
+        tl = -1 if table is None else len(table)
+        tb = None if table is None else np.ascontiguousarray(table, np.int16)
+        self._ck(self.lib.tz_decode_range(self.h, None if payload is None else _ptr(payload), n, _ptr(tb), tl, int(first),
+                                          int(count), _ptr(out)))
+        return out
+
     # ---- operator seams
     def delta_encode(self, pred, orig, zero_mask=None, out=None):
         n, h, w = orig.shape[:3]
@@ -578,6 +625,15 @@ class Context:
         tb = np.ascontiguousarray(table, np.int16)
         self._ck(self.lib.tz_unmap(self.h, _ptr(x), n, tb.ctypes.data, len(tb), int(offset), _ptr(out)))
         return out
+
+    def undelta_carry(self, payload, n0, table=None, staged=False):
+        """tz_undelta_carry: the decoded element in front of payload[n0] (table None: no remap).  staged=True: the payload
+        staged with payload_begin / payload_put."""
+        tl = -1 if table is None else len(table)
+        tb = None if table is None else np.ascontiguousarray(table, np.int16)
+        c = C.c_int16(0)
+        self._ck(self.lib.tz_undelta_carry(self.h, None if staged else _ptr(payload), int(n0), _ptr(tb), tl, C.byref(c)))
+        return int(c.value)
 
     def spatial_undelta(self, x, carry=None, out=None):
         n = int(np.prod(x.shape))

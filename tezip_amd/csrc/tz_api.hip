@@ -100,7 +100,7 @@ int tz_check_pred_contract(tz_ctx* ctx, const char* who) {
 
 extern "C" int tz_rollout_contract(tz_ctx* ctx) {
     if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->have_rollout) return tz_fail(ctx, TZ_ERR_STATE, "no rollout in this context");
+    if (!ctx->have_rollout && !ctx->have_range) return tz_fail(ctx, TZ_ERR_STATE, "no rollout in this context");
     return ctx->pred_contract;
 }
 
@@ -532,7 +532,8 @@ int tz_dev_out_finish(tz_ctx* ctx, std::vector<tz_out>& outs) {
 static const char* kProfNames[TZP_COUNT] = {"conv3x3_mfma", "err0", "delta", "quant", "spatial_delta_hist",
                                             "lut_remap", "undelta_scan", "reconstruct", "sse",
                                             "conv16_lds_dma", "conv16b_level0", "conv_small_valu", "conv3x3_general",
-                                            "convlat_small_grid", "wino_pa2", "table_create", "quant_serial_chains"};
+                                            "convlat_small_grid", "wino_pa2", "table_create", "quant_serial_chains",
+                                            "undelta_carry"};
 
 namespace {
 struct RoctxApi {
@@ -795,7 +796,7 @@ __global__ void k_bcast_frames_flagged(const float* __restrict__ src, size_t fe,
 }
 
 static int rollout_setup(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up,
-                         const std::vector<int>* first = nullptr) {
+                         const std::vector<int>* first = nullptr, int pred_frames = -1) {
     if (!ctx->model) return tz_fail(ctx, TZ_ERR_STATE, "no model loaded");
     if (nt < 1 || H < 1 || W < 1 || warm_up < 0 || nt > 32767 || H > 32767 || W > 32767)
         return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d warm_up=%d (int16 trailer limits)", nt, H, W, warm_up);
@@ -814,10 +815,11 @@ static int rollout_setup(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int 
     ctx->Wp = Wp;
     ctx->warm_up = warm_up;
     ctx->have_rollout = false;
+    ctx->have_range = false;
     ctx->pending_src = nullptr;
     ctx->pending_sent.clear();
     const size_t fsz = (size_t)H * W * 3;
-    size_t fb = (size_t)nt * fsz, pb = (size_t)nt * Hp * Wp * 3 * 4;
+    size_t fb = (size_t)nt * fsz, pb = (size_t)(pred_frames < 0 ? nt : pred_frames) * Hp * Wp * 3 * 4;
     if (frames) ctx->staged = false;
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_frames, &ctx->cap_frames, fb));
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_pred, &ctx->cap_pred, pb));
@@ -919,7 +921,8 @@ struct PredItem {
 // predictor call over all windows (launch-only, no per-step copies).  Capturing this sequence
 // into a hipGraph was measured and brings nothing (cfg1/cfg2 are bound by the latency of their
 // tiny grids, not by launch overhead; cfg3+ are GPU-bound), so the launches stay plain.
-static int run_schedule(tz_ctx* ctx, std::vector<PredItem>& items) {
+// frames: the stack the items' frame indices refer to (NULL = the context's whole stack; a range rollout passes a sub-stack)
+static int run_schedule(tz_ctx* ctx, std::vector<PredItem>& items, const uint8_t* frames = nullptr) {
     int Hp, Wp, maxB;
     TZ_TRY(tz_model_dims(ctx, &Hp, &Wp, &maxB));
     if (items.empty()) return TZ_OK;
@@ -1018,7 +1021,7 @@ static int run_schedule(tz_ctx* ctx, std::vector<PredItem>& items) {
             // the slot numbers of the table are positions in the batch: the activation slots of a group start at slot0
             const bool skip = fused[g] && all_fed[g][b];
             if (g == 1) ctx->stream = ctx->stream2;   // the launchers take the context's stream
-            rc = tz_model_predict_batch_dev(ctx, counts[g][b], tab, maxB, ctx->d_frames, ctx->H, ctx->W, ctx->d_pred, ctx->d_pred, slot0,
+            rc = tz_model_predict_batch_dev(ctx, counts[g][b], tab, maxB, frames ? frames : ctx->d_frames, ctx->H, ctx->W, ctx->d_pred, ctx->d_pred, slot0,
                                             tab + 3 * (size_t)maxB, skip, &fused[g]);
             ctx->stream = main_stream;
         }
@@ -1039,6 +1042,7 @@ extern "C" int tz_frames_begin(tz_ctx* ctx, int nt, int H, int W) {
     if (nt < 1 || H < 1 || W < 1 || nt > 32767 || H > 32767 || W > 32767)
         return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d (int16 trailer limits)", nt, H, W);
     ctx->have_rollout = false;
+    ctx->have_range = false;
     ctx->staged = false;
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_frames, &ctx->cap_frames, (size_t)nt * H * W * 3));
     // earlier work queued on the compute stream may still read d_frames
@@ -1094,10 +1098,10 @@ extern "C" int tz_payload_put(tz_ctx* ctx, size_t offset, size_t count, const in
 
 extern "C" int tz_decoded_get(tz_ctx* ctx, int first, int count, uint8_t* out) {
     if (!ctx || !out) return TZ_ERR_INVALID;
-    if (!ctx->d_out || !ctx->have_decoded || first < 0 || count < 0 || first + count > ctx->nt)
+    if (!ctx->d_out || !ctx->have_decoded || first < ctx->dec_first || count < 0 || first + count > ctx->dec_first + ctx->dec_count)
         return tz_fail(ctx, TZ_ERR_INVALID, "frames [%d, %d) outside the resident decoded stack", first, first + count);
     const size_t fsz = (size_t)ctx->H * ctx->W * 3;
-    TZ_TRY(tz_d2h(ctx, out, ctx->d_out + (size_t)first * fsz, (size_t)count * fsz, ctx->stream));
+    TZ_TRY(tz_d2h(ctx, out, ctx->d_out + (size_t)(first - ctx->dec_first) * fsz, (size_t)count * fsz, ctx->stream));
     return tz_stream_sync(ctx);
 }
 
@@ -1283,6 +1287,20 @@ extern "C" int tz_rollout(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int
     return rc;
 }
 
+// decompress.py:123-129: a frame of the resident stack is a key frame iff it has a non-zero sample (flags back on the host)
+static int discover_keys(tz_ctx* ctx, int nt, int H, int W, std::vector<int>* flags) {
+    void* d_flags;
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(int) * nt, &d_flags));
+    size_t fb = (size_t)H * W * 3;
+    hipError_t e = hipMemsetAsync(d_flags, 0, sizeof(int) * nt, ctx->stream);
+    int gx = (int)std::min<size_t>((fb + 255) / 256, 64);
+    hipLaunchKernelGGL(k_any_nonzero, dim3(gx, nt), dim3(256), 0, ctx->stream, ctx->d_frames, fb, (int*)d_flags);
+    if (e == hipSuccess) e = hipMemcpyAsync(flags->data(), d_flags, sizeof(int) * nt, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "key discovery failed: %s", hipGetErrorString(e));
+    return TZ_OK;
+}
+
 extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up,
                                  uint8_t* key_mask) {
     tz_roctx_range roctx_("tz_rollout_decode");
@@ -1290,19 +1308,8 @@ extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt,
     ctx->enc_pending = false;
     int rc = rollout_setup(ctx, key_frames, nt, H, W, warm_up);
     if (rc != TZ_OK) return rc;
-    // decompress.py:123-129: a frame is a key frame iff it has a non-zero sample
     std::vector<int> flags(nt, 0);
-    void* d_flags;
-    rc = tz_pool_alloc(ctx, sizeof(int) * nt, &d_flags);
-    if (rc == TZ_OK) {
-        size_t fb = (size_t)H * W * 3;
-        hipError_t e = hipMemsetAsync(d_flags, 0, sizeof(int) * nt, ctx->stream);
-        int gx = (int)std::min<size_t>((fb + 255) / 256, 64);
-        hipLaunchKernelGGL(k_any_nonzero, dim3(gx, nt), dim3(256), 0, ctx->stream, ctx->d_frames, fb, (int*)d_flags);
-        if (e == hipSuccess) e = hipMemcpyAsync(flags.data(), d_flags, sizeof(int) * nt, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "key discovery failed: %s", hipGetErrorString(e));
-    }
+    rc = discover_keys(ctx, nt, H, W, &flags);
     if (rc != TZ_OK) {
         tz_pool_release_all(ctx);
         return rc;
@@ -1349,6 +1356,88 @@ extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt,
         ctx->rollout_is_decode = true;
         if (key_mask)
             for (int i = 0; i < nt; ++i) key_mask[i] = flags[i] ? 1 : 0;
+    }
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_range_restart(const uint8_t* key_mask, int nt, int warm_up, int first, int* restart) {
+    if (!key_mask || !restart || nt < 1 || warm_up < 0 || first < 0 || first >= nt) return TZ_ERR_INVALID;
+    int r = 0;
+    for (int k = first; k > warm_up; --k)
+        if (key_mask[k]) {
+            r = k;
+            break;
+        }
+    *restart = r;
+    return TZ_OK;
+}
+
+extern "C" int tz_rollout_decode_range(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, int first,
+                                       int count, uint8_t* key_mask) {
+    tz_roctx_range roctx_("tz_rollout_decode_range");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (nt < 1 || first < 0 || count < 1 || first >= nt || count > nt - first)
+        return tz_fail(ctx, TZ_ERR_INVALID, "frame range [%d, %d + %d) outside the %d-frame sequence", first, first, count, nt);
+    if (!key_frames && ctx->staged && (ctx->nt != nt || ctx->H != H || ctx->W != W))
+        return tz_fail(ctx, TZ_ERR_INVALID, "range decode of a %d x %d x %d stack, the staged stack is %d x %d x %d", nt, H, W,
+                       ctx->nt, ctx->H, ctx->W);
+    ctx->enc_pending = false;
+    // the whole key stack is staged (key discovery looks at every frame); the prediction stack is sized below
+    int rc = rollout_setup(ctx, key_frames, nt, H, W, warm_up, nullptr, 1);
+    if (rc != TZ_OK) return rc;
+    std::vector<int> flags(nt, 0);
+    rc = discover_keys(ctx, nt, H, W, &flags);
+    // the whole-stack replay (tz_rollout_decode) needs frames 0..warm_up to be key frames; refuse what it refuses
+    for (int i = 0; rc == TZ_OK && i <= warm_up; ++i)
+        if (i >= nt || !flags[i]) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", i);
+    std::vector<uint8_t> mask(nt);
+    for (int i = 0; i < nt; ++i) mask[i] = flags[i] ? 1 : 0;
+    int r = 0;
+    if (rc == TZ_OK) rc = tz_range_restart(mask.data(), nt, warm_up, first, &r);
+    if (rc != TZ_OK) {
+        tz_pool_release_all(ctx);
+        return rc;
+    }
+    // sub-stack [r, end): from a key frame r > warm_up with warm_up 0, from frame 0 with the job's warm_up -- and then
+    // reaching frame warm_up, which the replay's key-interval walk starts from
+    const int end = r == 0 ? std::max(first + count, warm_up + 1) : first + count;
+    const int ns = end - r, sw = r == 0 ? warm_up : 0;
+    std::vector<int> kfc;
+    for (int i = r; i < end; ++i)
+        if (flags[i]) kfc.push_back(i - r);
+    kfc.push_back(ns);
+    // the schedule of tz_rollout_decode (decompress.py:138-179) on the sub-stack
+    std::vector<uint8_t> recon_key(ns, 0);
+    std::vector<int> c0_slots;
+    std::vector<PredItem> items;
+    for (int i = 0; i < sw; ++i) c0_slots.push_back(i);
+    for (int k = sw; k + 1 < (int)kfc.size(); ++k)
+        for (int pi = kfc[k]; pi < kfc[k + 1]; ++pi) {
+            if (pi == kfc[k]) {
+                recon_key[pi] = 1;
+                c0_slots.push_back(pi);
+            } else {
+                items.push_back(PredItem{pi, pi == kfc[k] + 1 ? 1 : 0, pi - 1, pi - kfc[k]});
+            }
+        }
+    recon_key[0] = 1;  // decompress.py:186 (frame 0, or the key frame r)
+    const size_t fsz = (size_t)H * W * 3;
+    rc = tz_ensure(ctx, (void**)&ctx->d_pred, &ctx->cap_pred, (size_t)ns * ctx->Hp * ctx->Wp * 3 * 4);
+    if (rc == TZ_OK) rc = fill_c0(ctx, c0_slots);
+    if (rc == TZ_OK) rc = run_schedule(ctx, items, ctx->d_frames + (size_t)r * fsz);
+    if (rc == TZ_OK) {
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "range decode rollout failed: %s", hipGetErrorString(e));
+    }
+    if (rc == TZ_OK) {
+        ctx->key_mask = recon_key;
+        ctx->have_range = true;
+        ctx->range_restart = r;
+        ctx->range_end = end;
+        ctx->pred_contract = tz_get_contract(ctx);
+        ctx->rollout_is_decode = true;
+        if (key_mask) memcpy(key_mask, mask.data(), nt);
     }
     tz_pool_release_all(ctx);
     return rc;
@@ -1769,7 +1858,97 @@ extern "C" int tz_decode(tz_ctx* ctx, const int16_t* payload, size_t payload_len
                                  ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
     }
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && resident) ctx->have_decoded = true;   // only a decode whose work is queued leaves frames to fetch
+    if (rc == TZ_OK && resident) {   // only a decode whose work is queued leaves frames to fetch
+        ctx->have_decoded = true;
+        ctx->dec_first = 0;
+        ctx->dec_count = nt;
+    }
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// the decoded element in front of payload[n0] (k_undelta_carry): enqueued, then read back
+static int undelta_carry(tz_ctx* ctx, const int16_t* d_pay, size_t n0, const int16_t* h_lut, int16_t* carry) {
+    void* d_word;
+    unsigned w = 0;
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(unsigned), &d_word));
+    TZ_TRY(tzk_undelta_carry(ctx, d_pay, n0, h_lut, 1, (unsigned*)d_word));
+    TZ_TRY(tz_d2h(ctx, &w, d_word, sizeof(unsigned), ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
+    *carry = (int16_t)(w & 0xFFFFu);
+    return TZ_OK;
+}
+
+// payload == NULL: the payload staged with tz_payload_begin / tz_payload_put, which must hold `need` elements
+static int staged_payload(tz_ctx* ctx, size_t need, const int16_t** payload) {
+    if (!ctx->d_payload || ctx->payload_len < need) return tz_fail(ctx, TZ_ERR_STATE, "no staged payload of %zu elements", need);
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
+    *payload = ctx->d_payload;
+    return TZ_OK;
+}
+
+extern "C" int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, const int16_t* table, int table_len,
+                                int16_t* carry) {
+    tz_roctx_range roctx_("tz_undelta_carry");
+    if (!ctx || !carry) return TZ_ERR_INVALID;
+    if (n0 == 0) return tz_fail(ctx, TZ_ERR_INVALID, "tz_undelta_carry: n0 = 0, the stream start has no carry");
+    if (table_len < -1 || table_len > TZ_NBINS || (table_len > 0 && !table)) return tz_fail(ctx, TZ_ERR_INVALID, "bad table");
+    if (!payload) TZ_TRY(staged_payload(ctx, n0, &payload));
+    std::vector<int16_t> lut;
+    if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
+    const void* d_pay = nullptr;
+    int rc = tz_dev_in(ctx, payload, n0 * 2, &d_pay);
+    if (rc == TZ_OK) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, table_len >= 0 ? lut.data() : nullptr, carry);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                               int first, int count, uint8_t* frames_out) {
+    tz_roctx_range roctx_("tz_decode_range");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (!ctx->have_range) return tz_fail(ctx, TZ_ERR_STATE, "tz_decode_range needs a tz_rollout_decode_range first");
+    TZ_TRY(tz_check_pred_contract(ctx, "tz_decode_range"));
+    if (table_len < -1 || table_len > TZ_NBINS || (table_len > 0 && !table)) return tz_fail(ctx, TZ_ERR_INVALID, "bad table");
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W, r = ctx->range_restart;
+    if (first < r || count < 1 || first >= ctx->range_end || count > ctx->range_end - first)
+        return tz_fail(ctx, TZ_ERR_INVALID, "frame range [%d, %d + %d) outside the frames [%d, %d) the range rollout covered", first,
+                       first, count, r, ctx->range_end);
+    const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe, n0 = (size_t)first * fe, nr = (size_t)count * fe;
+    if (!payload) TZ_TRY(staged_payload(ctx, N, &payload));
+    ctx->have_decoded = false;
+    if (payload_len != N)  // decompress.py:240: the reshape raises
+        return tz_fail(ctx, TZ_ERR_INVALID, "payload holds %zu elements, the key-frame stack implies %zu", payload_len, N);
+    const bool resident = frames_out == nullptr;
+    if (resident) {  // keep the frames in the context: tz_decoded_get (sequence coordinates)
+        TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_out, &ctx->cap_out, nr));
+        frames_out = ctx->d_out;
+    }
+    std::vector<tz_out> outs;
+    tz_out o;
+    const void* d_pay = nullptr;
+    void* d_mask = nullptr;
+    int16_t carry = 0;
+    int rc = tz_dev_in(ctx, payload, n0 * 2 + nr * 2, &d_pay);   // (nothing behind the range is read)
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, frames_out, nr, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, count, &d_mask);
+    if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, ctx->key_mask.data() + (first - r), count);
+    std::vector<int16_t> lut;
+    if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
+    const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
+    if (rc == TZ_OK && first > 0) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, h_lut, &carry);
+    if (rc == TZ_OK)
+        rc = tzk_decode_tail_range(ctx, (const int16_t*)d_pay + n0, h_lut, 1, first > 0, carry,
+                                   ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + n0,
+                                   (const uint8_t*)d_mask, count, H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK && resident) {
+        ctx->have_decoded = true;
+        ctx->dec_first = first;
+        ctx->dec_count = count;
+    }
     tz_pool_release_all(ctx);
     return rc;
 }

@@ -2150,6 +2150,108 @@ int tzk_decode_tail_fused(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut21
     return TZ_OK;
 }
 
+// the decoder's tail over frames [first, first + nframes) of a stream (tz_decode_range): `in`, pred, key and d_key_mask
+// point at the range's first frame and `carry` is the decoded element in front of it (has_carry = 0 at the stream start).
+// The fused launch where tzk_decode_tail_fused's layout conditions hold, else a scan into a temporary and k_recon*.
+int tzk_decode_tail_range(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry,
+                          int16_t carry, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H,
+                          int W, int Hp, int Wp, uint8_t* out) {
+    const size_t fe = (size_t)H * W * 3, n = (size_t)nframes * fe;
+    if (n == 0) return TZ_OK;
+    if (H == Hp && W == Wp && fe % SCAN_EPT == 0 && key && !ctx->decode_unfused &&
+        ((((uintptr_t)in | (uintptr_t)pred | (uintptr_t)key | (uintptr_t)out) & 15) == 0)) {
+        const ScanRecon rc = {(const float4*)pred, key, d_key_mask, (unsigned long long)fe, out};
+        return scan_launch(ctx, in, n, has_carry, carry, h_lut2112, post_offset, nullptr, &rc);
+    }
+    void* d_diff;
+    TZ_TRY(tz_pool_alloc(ctx, n * 2, &d_diff));
+    TZ_TRY(scan_launch(ctx, in, n, has_carry, carry, h_lut2112, post_offset, (int16_t*)d_diff));
+    return tzk_reconstruct(ctx, pred, key, d_key_mask, (const int16_t*)d_diff, nframes, H, W, Hp, Wp, out);
+}
+
+// ------------------------------------------------------------------------ prefix carry of the inverse scan
+// A decoder that starts the inverse spatial delta at element n0 (tz_decode_range) needs the decoded element in front of
+// it: x[n0-1] = -(sum_{j<n0} s'[j]) mod 2^16 (the scan above with c0 = 0, s'[0] = -s[0]; with LUT the symbols are the
+// ones scan_load16<LUT> produces).  One read-only pass over the prefix, 2 B/element: 16-byte loads, a scalar head up to
+// the first 16-byte boundary and a scalar tail; per-wave shuffle sums, then LDS, then ONE agent-scope atomic add per
+// workgroup into a word the host clears with hipMemsetAsync in front of the launch.  The word sums the NEGATED symbols
+// mod 2^32, so its low 16 bits are x[n0-1].  No hand-off between workgroups inside the launch: the consumer is the next
+// launch on the stream, or a 4-byte read.
+static constexpr int CARRY_UNROLL = 8;   // 16-byte loads in flight per thread and iteration (predicated: no serial tail)
+
+template <bool LUT>
+__device__ __forceinline__ unsigned carry_sym(int x, const int16_t* sl, int post_offset) {
+    if (LUT) x = (x >= 0 && x <= TZ_NBINS) ? (int)sl[x] : (int)(short)(post_offset ? TZ_OFFSET - x : x);
+    return (unsigned)x;
+}
+
+template <bool LUT>
+__device__ __forceinline__ unsigned carry_sum8(short8 v, const int16_t* sl, int post_offset) {
+    unsigned s = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += carry_sym<LUT>(v[k], sl, post_offset);
+    return s;
+}
+
+// head: elements in front of the first 16-byte boundary (0..7); the vectors start at in + head
+template <bool LUT>
+__global__ __launch_bounds__(256) void k_undelta_carry(const int16_t* __restrict__ in, size_t n, unsigned head,
+                                                       const int16_t* __restrict__ lut, int post_offset,
+                                                       unsigned* __restrict__ word) {
+    __shared__ int16_t sl[LUT ? TZ_NBINS + 1 : 1];
+    __shared__ unsigned wsum[4];
+    if (LUT) {
+        for (int k = threadIdx.x; k < TZ_NBINS + 1; k += 256) sl[k] = lut[k];
+        __syncthreads();
+    }
+    const size_t n8 = (n - head) / 8, nthr = (size_t)gridDim.x * 256;
+    const short8* in8 = (const short8*)(in + head);
+    unsigned s = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += CARRY_UNROLL * nthr) {
+        short8 v[CARRY_UNROLL];
+#pragma unroll
+        for (int u = 0; u < CARRY_UNROLL; ++u)
+            if (i + u * nthr < n8) v[u] = in8[i + u * nthr];
+#pragma unroll
+        for (int u = 0; u < CARRY_UNROLL; ++u)
+            if (i + u * nthr < n8) s += carry_sum8<LUT>(v[u], sl, post_offset);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 8) {
+        const size_t t = head + n8 * 8 + threadIdx.x;                  // ragged tail
+        if (threadIdx.x < head) s += carry_sym<LUT>(in[threadIdx.x], sl, post_offset);
+        if (t < n) s += carry_sym<LUT>(in[t], sl, post_offset);
+        if (threadIdx.x == 0) s -= 2u * carry_sym<LUT>(in[0], sl, post_offset);   // s'[0] = -s[0]
+    }
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        __hip_atomic_fetch_add(word, 0u - (wsum[0] + wsum[1] + wsum[2] + wsum[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// enqueue the carry of payload[0, n0) into *d_word (device); h_lut2112 NULL = symbols as stored
+int tzk_undelta_carry(tz_ctx* ctx, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_word) {
+    if (n0 == 0) return tz_fail(ctx, TZ_ERR_INVALID, "undelta carry: the stream start has no carry");
+    void* d_lut = nullptr;
+    if (h_lut2112) {
+        TZ_TRY(tz_pool_alloc(ctx, (TZ_NBINS + 1) * 2, &d_lut));
+        TZ_TRY(tz_upload(ctx, d_lut, h_lut2112, (TZ_NBINS + 1) * 2));
+    }
+    const unsigned head = (unsigned)std::min<size_t>(n0, ((16 - ((uintptr_t)in & 15)) & 15) / 2);
+    if (((uintptr_t)in & 1) != 0) return tz_fail(ctx, TZ_ERR_INVALID, "undelta carry: payload not 2-byte aligned");
+    TZ_HIP(ctx, hipMemsetAsync(d_word, 0, sizeof(unsigned), ctx->stream));
+    const int G = grid_for((n0 - head) / 8 / CARRY_UNROLL + 1, 256);
+    tz_prof_scope ps(ctx, TZP_CARRY);
+    if (h_lut2112)
+        hipLaunchKernelGGL(k_undelta_carry<true>, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)d_lut,
+                           post_offset, d_word);
+    else
+        hipLaunchKernelGGL(k_undelta_carry<false>, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)nullptr,
+                           post_offset, d_word);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // ----------------------------------------------------------------------------- reconstruct
 // decompress.py:252-256,269: pred*255 - diff, clip [0,255], truncate.  pred*255 in float64
 // minus an integer, clipped and truncated equals clamp(trunc(f32(pred*255)) - diff, 0, 255)

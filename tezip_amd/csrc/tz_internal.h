@@ -31,6 +31,7 @@ enum tz_prof_class {
     TZP_WINO,       // k_wino: TZ-PA2 form (Winograd F(2x2, 3x3) on the same-resolution source) of the k_conv16 convolutions
     TZP_TABLE,      // HOST time: rank table + LUT from the downloaded histogram (compress.py:356-361)
     TZP_QSERIAL,    // not a time: `launches` counts the chains the quantiser sent through its serial fallback (k_q_serial)
+    TZP_CARRY,      // prefix carry of the inverse scan (k_undelta_carry, tz_decode_range)
     TZP_COUNT
 };
 
@@ -67,6 +68,11 @@ struct tz_ctx {
     std::vector<uint8_t> group_first; // nt: 1 where a group starts (delta slot 0 -> 0)
     std::vector<uint8_t> quant_skip;  // nt: 1 where error_bound is not applied
     bool have_rollout = false, rollout_is_decode = false;
+    // tz_rollout_decode_range: the prediction stack holds frames [range_restart, range_end) of the nt-frame key stack
+    // (slot i = frame range_restart + i) and key_mask is indexed the same way; have_rollout stays false meanwhile, so that
+    // no whole-stack entry reads the short stack
+    bool have_range = false;
+    int range_restart = 0, range_end = 0;
     int pred_contract = 0;            // the arithmetic contract that produced the resident prediction stack (stamped by
                                       // tz_rollout / tz_rollout_decode; tz_encode* / tz_decode* refuse a flip in between)
     // pinned staging ring for small host->device uploads (index arrays, masks, LUTs): the copy
@@ -114,6 +120,7 @@ struct tz_ctx {
     uint8_t* d_out = nullptr;               // resident decoded frames of a tz_decode(frames_out = NULL)
     size_t cap_out = 0;
     bool have_decoded = false;
+    int dec_first = 0, dec_count = 0;       // frames of the sequence that d_out holds (tz_decode: all, tz_decode_range: its range)
     bool enc_pending = false, enc_entropy = false;  // tz_encode_begin done, symbols resident in d_payload
     int16_t enc_first = 0;                          // first element of the shard's quantised delta stack
     const uint8_t* pending_src = nullptr;  // host frame stack whose non-key frames are still to be sent
@@ -272,6 +279,10 @@ int tzk_unmap_undelta(tz_ctx*, const int16_t* in, size_t n, const int16_t* h_lut
 int tzk_decode_tail_fused(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, const float* pred,
                           const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
                           uint8_t* out, bool* done);
+int tzk_decode_tail_range(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry,
+                          int16_t carry, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H,
+                          int W, int Hp, int Wp, uint8_t* out);
+int tzk_undelta_carry(tz_ctx*, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_word);
 int tzk_reconstruct(tz_ctx*, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
                     int nframes, int H, int W, int Hp, int Wp, uint8_t* out);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,

@@ -120,7 +120,8 @@ class _Prefetch:
         self.t.join(timeout=5.0)
 
 
-def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shape, VERBOSE, device, contract=None, stack=None):
+def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shape, VERBOSE, device, contract=None, stack=None,
+                   frames=None):
     """decompress.py:87-279 with nothing of size nt*H*W on the host: entropy.dat is decompressed
     piece by piece straight into HBM (the trailer is read from the last piece), key_frame.dat
     likewise, the decoded frames come back window by window and are PNG-encoded on a thread pool
@@ -129,7 +130,9 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
     `stack` = (nt, H, W) from tezip_amd.json (round 6), or None: the reference keeps the shape in the LAST values of
     entropy.dat (compress.py:390-394), so without it nothing can start before the whole payload is decompressed; with it
     the key frames are staged and the decoder's rollout is queued FIRST, entropy.dat being decompressed on a worker
-    thread meanwhile, and the trailer is checked against it when it arrives."""
+    thread meanwhile, and the trailer is checked against it when it arrives.
+    `frames` = (A, B): only frames [A, B) are rolled out, decoded and written (tz_rollout_decode_range / tz_decode_range);
+    the whole stream is still staged, because its trailer holds the table and the shape."""
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
     from .compress import _Stages, io_threads
@@ -185,7 +188,10 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
-            ctx.rollout_decode(None, warm_up)     # (key discovery, then the predictor launches are queued)
+            if frames is None:
+                ctx.rollout_decode(None, warm_up)     # (key discovery, then the predictor launches are queued)
+            else:
+                ctx.rollout_decode_range(None, warm_up, frames[0], frames[1] - frames[0])
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
 
@@ -238,13 +244,19 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
         if early is not None and (nt, H, W, warm_up) != tuple(early):
             raise ValueError("tezip_amd.json describes the stack as %r (frames, height, width, warm-up), entropy.dat's trailer as %r"
                              % (tuple(early), (nt, H, W, warm_up)))
+        if frames is not None:
+            check_frames(frames, nt)
         if early is None:
             hp, wp = checks(nt, H, W)
             per = stage_keys(nt, H, W, hp, wp)
             rollout(warm_up)
         fb = H * W * C
         stages.mark("rollout (decoder)", ctx)
-        ctx.decode(None, table, out="resident")
+        lo, hi = (0, nt) if frames is None else frames
+        if frames is None:
+            ctx.decode(None, table, out="resident")
+        else:
+            ctx.decode_range(None, table, lo, hi - lo, out="resident")
         stages.mark("decode tail (frames resident)", ctx)
         if VERBOSE:
             prof = ctx.prof_get()
@@ -260,8 +272,8 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             Image.fromarray(buf[j]).save(os.path.join(OUTPUT_DIR, name))
 
         with ThreadPoolExecutor(max_workers=io_threads()) as pool:  # PIL's encoder releases the GIL
-            for ci, f0 in enumerate(range(0, nt, per)):
-                k = min(per, nt - f0)
+            for ci, f0 in enumerate(range(lo, hi, per)):
+                k = min(per, hi - f0)
                 slot = ci % 3
                 for ft in busy[slot]:
                     ft.result()           # the encoders of the window that used this buffer are done
@@ -276,11 +288,24 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
     return True
 
 
-def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0):
+def check_frames(frames, nt):
+    """A frame range (A, B) must satisfy 0 <= A < B <= nt (filename.txt's length, then entropy.dat's trailer)."""
+    a, b = frames
+    if not 0 <= a < b <= nt:
+        raise ValueError("frame range %d:%d is outside the %d frames of this sequence (0 <= A < B <= %d)" % (a, b, nt, nt))
+
+
+def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=None):
+    """frames: None = every frame (the reference's behaviour), or (A, B) = write file_names[A:B] only, byte-identical to
+    what a whole decode writes for those names (B None = to the end).  Not in the reference."""
     if not GPU_FLAG:
         print("ERROR: this build runs the decompression path on an AMD MI355X only (no CPU path).")
         exit()
     job = tzdist.active()
+    if frames is not None and job is not None:
+        # same error class as adopt_contract: a launcher must not see success when no frame was written
+        print("ERROR: a frame range (--frames) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
+        sys.exit(2)
     rank0 = job is None or job[0] == 0
     # every rank of a sharded job writes the images of its own windows: each makes the directory (on one node they race for
     # the same one, hence exist_ok; on node-local paths each node gets its share -- INTEGRATION.md section 3)
@@ -295,13 +320,21 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0):
     # decompress.py:55: `isdigit` is not called there, so any 1-character first line is the flag
     if file_names and len(file_names[0]) == 1:
         isRGB = bool(int(file_names.pop(0)))
+    if frames is not None:
+        frames = (int(frames[0]), len(file_names) if frames[1] is None else int(frames[1]))
+        try:
+            check_frames(frames, len(file_names))
+        except ValueError as e:
+            print("ERROR:", e)
+            sys.exit(2)
 
     cfg, wts, model_shape = open_model(WEIGHTS_DIR)
     contract = adopt_contract(DATA_DIR, wts, VERBOSE)
     if job is None and not os.environ.get("TEZIP_NO_STREAMING"):
         # (the sidecar passed adopt_contract: it is readable or absent)
         stack = None if os.environ.get("TEZIP_NO_EARLY_ROLLOUT") else sidecar.stack_of(sidecar.read(DATA_DIR))
-        done = _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shape, VERBOSE, device, contract, stack)
+        done = _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shape, VERBOSE, device, contract, stack,
+                              frames)
         if done:
             return
 
@@ -329,6 +362,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0):
         print("filename.txt：", len(file_names))
         print("number of images", nt)
         exit()
+    if frames is not None:
+        check_frames(frames, nt)
 
     if job:
         device = tzdist.init_from_env()
@@ -347,10 +382,18 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0):
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
-            ctx.rollout_decode(np.ascontiguousarray(key_frames), warm_up)
+            tb = None if table is None else np.ascontiguousarray(table)
+            if frames is None:
+                ctx.rollout_decode(np.ascontiguousarray(key_frames), warm_up)
+            else:
+                first, count = frames[0], frames[1] - frames[0]
+                ctx.rollout_decode_range(np.ascontiguousarray(key_frames), warm_up, first, count)
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
-            frames = ctx.decode(np.ascontiguousarray(payload), None if table is None else np.ascontiguousarray(table))
+            if frames is None:
+                frames = ctx.decode(np.ascontiguousarray(payload), tb)
+            else:
+                frames = ctx.decode_range(np.ascontiguousarray(payload), tb, first, count)
             if VERBOSE:
                 prof = ctx.prof_get()
                 if table is not None:
@@ -388,4 +431,4 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0):
             raise
         return
     with ThreadPoolExecutor(max_workers=io_threads()) as pool:  # PIL's encoder releases the GIL
-        list(pool.map(save, range(nt)))
+        list(pool.map(save, range(len(frames))))

@@ -39,6 +39,9 @@ FLAG_TABLE = (
     # 256x256 pixels on), 1 = TZ-PA1 (what files compressed by builds before round 4 need for -u), 2 = TZ-PA2.  The same
     # value must be given to -c and -u: the reference's file format has no field for it.
     (None, "--pa", dict(type=int, choices=(0, 1, 2), default=None, dest="pa")),
+    # not in the reference: with -u, write only frames A:B (half-open, either end may be omitted) or the one frame N of
+    # the sequence, decoded without rolling out, scanning and saving the others (decompress.run(frames=...))
+    (None, "--frames", dict(type=str, default=None, metavar="A:B", dest="frames")),
 )
 
 TEXT = {
@@ -64,6 +67,40 @@ def build_parser():
     for short, long_, kw in FLAG_TABLE:
         parser.add_argument(*([short, long_] if short else [long_]), **kw)
     return parser
+
+
+def parse_frames(spec):
+    """--frames SPEC -> (A, B) with B None for "to the end"; "N" is N:N+1.  Raises ValueError for a malformed spec or
+    negative indices (the bound against the sequence length is checked once filename.txt is read)."""
+    spec = spec.strip()
+    try:
+        if ":" in spec:
+            a, b = spec.split(":")
+            a = int(a) if a.strip() else 0
+            b = int(b) if b.strip() else None
+        else:
+            a = int(spec)
+            b = a + 1
+    except ValueError:
+        raise ValueError("--frames takes A:B (either end may be omitted) or N, got %r" % spec) from None
+    if a < 0 or (b is not None and b < 0):
+        raise ValueError("--frames indices must be non-negative, got %r" % spec)
+    if b is not None and b <= a:
+        raise ValueError("--frames %r is an empty range" % spec)
+    return a, b
+
+
+def check_frames_flag(arg):
+    """--frames is valid with -u only.  Returns (frames, None), or (None, message) for a refusal."""
+    spec = getattr(arg, "frames", None)
+    if spec is None:
+        return None, None
+    if arg.uncompress is None or arg.learn is not None or arg.compress is not None:
+        return None, "--frames is valid with -u (--uncompress) only"
+    try:
+        return parse_frames(spec), None
+    except ValueError as e:
+        return None, str(e)
 
 
 def probe_gpu(force_cpu):
@@ -108,6 +145,10 @@ def check_compress(arg):
 
 
 def _main(arg):
+    frames, problem = check_frames_flag(arg)
+    if problem:   # exit status 2, as decompress.adopt_contract's errors: nothing was written
+        print("ERROR:", problem)
+        sys.exit(2)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # launched by torch.distributed.run: one rank per GPU
         from . import dist as tzdist
         tzdist.init_from_env()
@@ -124,6 +165,8 @@ def _main(arg):
     if chosen[0] == "uncompress":
         print("uncompress mode")
         model, src, dst = arg.uncompress
+        if frames is not None:
+            return decompress.run(model, src, dst, gpu, arg.verbose, frames=frames)
         return decompress.run(model, src, dst, gpu, arg.verbose)
     print("compress mode")
     problem = check_compress(arg)
