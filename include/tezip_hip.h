@@ -28,6 +28,13 @@ extern "C" {
 
 typedef struct tz_ctx tz_ctx;
 
+/* tz_encode_quality: one record per frame (16 bytes) */
+typedef struct {
+    unsigned long long sse;   /* sum over the frame of (decoded - original)^2 */
+    unsigned max_abs;         /* max |decoded - original| */
+    unsigned n_changed;       /* samples with decoded != original */
+} tz_frame_quality;
+
 typedef enum {
     TZ_OK = 0,
     TZ_ERR_INVALID = -1,     /* bad argument (the reference prints + exit()s or raises) */
@@ -261,6 +268,26 @@ int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, const int16
  * context for tz_decoded_get, whose frame indices are then sequence indices inside [first, first + count). */
 int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len, int first,
                     int count, uint8_t* frames_out);
+
+/* tz_encode_quality: what the stored payload of an encode decodes to, compared with the originals (no reference
+ * counterpart; `tezip.py -c --report`).  On the context's ENCODER rollout (tz_rollout, SWP or DWP; anything else, a
+ * tz_rollout_decode included, is TZ_ERR_STATE) the decoder's tail -- inverse remap, inverse spatial delta, reconstruct,
+ * the launches tz_decode makes -- runs over `payload` with the encoder's own predictions and frames, under the mask the
+ * decoder's rollout would reconstruct with (frame 0 and every key frame from the warm_up-th on; warm-up frames 1..p-1
+ * take their C0 slot), and k_quality compares the frames it yields with the originals.  The decoder's rollout
+ * regenerates the encoder's predictions bit for bit, so out[f] describes frame f exactly as
+ * `-u` writes it; zstd and the decoder's own rollout are not exercised.
+ *  payload: nt*H*W*3 int16 (host or device), or NULL = the resident payload of the last tz_encode(payload = NULL) on the
+ *           current rollout (TZ_ERR_STATE when there is none).  payload_len must be nt*H*W*3 (else TZ_ERR_INVALID).
+ *  table / table_len: as tz_decode (table_len == -1: no rank table).  shuffled: the payload holds byte planes
+ *           (tz_encode's opt-in shuffle); they are undone into scratch first.
+ *  out:     nt records, host or device.  The call returns once they are complete.
+ * Nothing of the context changes: payload, predictions, frames and rollout state are as they were.
+ * Limitation: a key frame whose samples are all zero is not found again by the decoder's key discovery
+ * (decompress.py:123-129) and `-u` fails on such a stream; the records describe the stream the
+ * encoder meant to write. */
+int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                      int shuffled, tz_frame_quality* out);
 
 /* ---- operator seams, usable stand-alone (each mirrors one reference helper) -----------------
  * tz_delta_encode: compress.py:292-314.  pred: nframes padded f32 frames; orig: nframes

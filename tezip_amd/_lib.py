@@ -53,6 +53,7 @@ _SIGS = {
                                           C.c_void_p]),
     "tz_undelta_carry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_int16)]),
     "tz_decode_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_encode_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_frames_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "tz_frames_put": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_frames_fence": (C.c_int, [C.c_void_p]),
@@ -95,6 +96,14 @@ _SIGS = {
     "tz_prof_reset": (C.c_int, [C.c_void_p]),
 }
 EXPORTS = sorted(_SIGS)
+
+
+class FrameQuality(C.Structure):
+    """tz_frame_quality: one record of tz_encode_quality (16 bytes)."""
+    _fields_ = [("sse", C.c_ulonglong), ("max_abs", C.c_uint), ("n_changed", C.c_uint)]
+
+
+QUALITY_DTYPE = np.dtype([("sse", "<u8"), ("max_abs", "<u4"), ("n_changed", "<u4")])   # the same layout as a numpy record
 
 _LIB = None
 
@@ -577,6 +586,23 @@ class Context:
         tb = None if table is None else np.ascontiguousarray(table, np.int16)
         self._ck(self.lib.tz_decode_range(self.h, None if payload is None else _ptr(payload), n, _ptr(tb), tl, int(first),
                                           int(count), _ptr(out)))
+        return out
+
+    def encode_quality(self, payload="resident", table=None, shuffle=False):
+        """tz_encode_quality after rollout + encode: per frame (sse, max_abs, n_changed) of what the payload decodes to
+        against the originals, as a QUALITY_DTYPE record array of nt entries.  payload: "resident" (the payload of
+        encode(..., payload="resident")) or a host / device buffer of nt*H*W*3 int16; table: the encode's table (None:
+        no remap); shuffle: the payload holds byte planes."""
+        nt, h, w = self._shape
+        n = nt * h * w * 3
+        resident = isinstance(payload, str) and payload == "resident"
+        if not resident and _numel(payload) != n:
+            raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
+        out = np.zeros(nt, QUALITY_DTYPE)
+        tl = -1 if table is None else len(table)
+        tb = None if table is None else np.ascontiguousarray(table, np.int16)
+        self._ck(self.lib.tz_encode_quality(self.h, None if resident else _ptr(payload), n, _ptr(tb), tl, int(bool(shuffle)),
+                                            out.ctypes.data))
         return out
 
     # ---- operator seams

@@ -10,12 +10,13 @@ Output directory:
 """
 import glob
 import os
+import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, sidecar, weights, zstd
+from . import _lib, quality, sidecar, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -281,9 +282,12 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
 
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
-        ENTROPY_RUN, device=0, SHUFFLE=False):
+        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
+    REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
+    bound introduced, from the stored payload decoded on the device (tz_encode_quality) -- and print the worst error,
+    the PSNR and the compression ratio.  Single-GPU jobs only.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -293,6 +297,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
         print("ERROR: this build runs the compression path on an AMD MI355X only (no CPU path).")
         exit()
     if tzdist.active() is not None:
+        if REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
+            print("ERROR: --report is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU")
+            sys.exit(2)
         return _run_sharded(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE,
                             VERBOSE, ENTROPY_RUN, device, SHUFFLE)
     if not os.path.exists(OUTPUT_DIR):
@@ -348,6 +355,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             stages.mark("rollout", ctx)
             _, table, _ = ctx.encode(MODE, BOUND_VALUE, ENTROPY_RUN, payload="resident", shuffle=SHUFFLE)
             stages.mark("encode (payload resident)", ctx)
+            if REPORT:   # stream-ordered before _stream_outputs fetches the payload; changes nothing it reads
+                t0 = time.time()
+                stats = ctx.encode_quality("resident", table if ENTROPY_RUN else None, shuffle=SHUFFLE)
+                if VERBOSE:
+                    print("quality:{0}".format(time.time() - t0) + "[sec]")
+                stages.mark("quality report (device)")
             if VERBOSE:
                 prof = ctx.prof_get()
                 print("error_bound:{0}".format(prof["quant"][0] / 1e3) + "[sec]")
@@ -362,6 +375,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             if VERBOSE:
                 print("arithmetic contract:", doc["arithmetic_contract"])
             stages.mark("key_frame.dat + entropy.dat")
+            if REPORT:   # the three files exist: the ratio is known
+                report = quality.summarize(stats, src.files, H, W, MODE, BOUND_VALUE, quality.file_sizes(OUTPUT_DIR),
+                                           window=WINDOW_SIZE, threshold=THRESHOLD, warm_up=PREPROCESS)
+                quality.write(OUTPUT_DIR, report)
+                for line in quality.stdout_lines(report):
+                    print(line)
         finally:
             ctx.close()
 

@@ -137,6 +137,8 @@ extern "C" int tz_ctx_create(int device, void* hip_stream, tz_ctx** out) {
         if (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ctx->contract = e[0] - '0';
         e = getenv("TEZIP_WINO_IPW");            // measurements: column blocks per k_wino workgroup (0 = per launch)
         if (e) ctx->wino_ipw = atoi(e);
+        e = getenv("TEZIP_QUALITY_GRID");        // diagnostic: workgroups of k_quality (0 = per launch; tests of launch-shape invariance)
+        if (e) ctx->quality_grid = atoi(e);
     }
     ctx->device = device;
     {
@@ -533,7 +535,7 @@ static const char* kProfNames[TZP_COUNT] = {"conv3x3_mfma", "err0", "delta", "qu
                                             "lut_remap", "undelta_scan", "reconstruct", "sse",
                                             "conv16_lds_dma", "conv16b_level0", "conv_small_valu", "conv3x3_general",
                                             "convlat_small_grid", "wino_pa2", "table_create", "quant_serial_chains",
-                                            "undelta_carry"};
+                                            "undelta_carry", "quality"};
 
 namespace {
 struct RoctxApi {
@@ -1083,6 +1085,7 @@ extern "C" int tz_frames_get(tz_ctx* ctx, int first, int count, uint8_t* out) {
 extern "C" int tz_payload_begin(tz_ctx* ctx, size_t count) {
     if (!ctx) return TZ_ERR_INVALID;
     ctx->enc_pending = false;   // the resident symbols of a tz_encode_begin are about to be overwritten
+    ctx->enc_resident = false;  // and so is the payload of a tz_encode(payload = NULL)
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, std::max<size_t>(count, 8) * 2));
     ctx->payload_len = count;
     TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old payload
@@ -1118,6 +1121,7 @@ extern "C" int tz_rollout(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int
     tz_roctx_range roctx_("tz_rollout");
     if (!ctx) return TZ_ERR_INVALID;
     ctx->enc_pending = false;   // a tz_encode_begin belongs to the rollout before it
+    ctx->enc_resident = false;  // so does a resident payload
     if (window < 0) return tz_fail(ctx, TZ_ERR_INVALID, "window must be >= 0");
     if (nt < warm_up + 2)  // the reference breaks here
         return tz_fail(ctx, TZ_ERR_INVALID, "need at least warm_up+2 frames (nt=%d, warm_up=%d)", nt, warm_up);
@@ -1287,6 +1291,18 @@ extern "C" int tz_rollout(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int
     return rc;
 }
 
+// decompress.py:138-186: the frames the decoder reconstructs from their key-frame bytes rather than from a prediction slot
+// -- frame 0 and every key frame from the warm_up-th on; the warm-up frames 1..warm_up-1 reconstruct from their C0 slot.
+// key: the key mask of an n-frame stack.  The decoder's rollouts leave this in ctx->key_mask; tz_encode_quality derives
+// it from the encoder's key mask, so that its tail reconstructs what -u does.
+static std::vector<uint8_t> recon_key_mask(const uint8_t* key, int n, int warm_up) {
+    std::vector<uint8_t> r(n, 0);
+    for (int i = 0, k = 0; i < n; ++i)
+        if (key[i]) r[i] = k++ >= warm_up;
+    if (n > 0) r[0] = 1;   // decompress.py:186
+    return r;
+}
+
 // decompress.py:123-129: a frame of the resident stack is a key frame iff it has a non-zero sample (flags back on the host)
 static int discover_keys(tz_ctx* ctx, int nt, int H, int W, std::vector<int>* flags) {
     void* d_flags;
@@ -1306,6 +1322,7 @@ extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt,
     tz_roctx_range roctx_("tz_rollout_decode");
     if (!ctx) return TZ_ERR_INVALID;
     ctx->enc_pending = false;
+    ctx->enc_resident = false;
     int rc = rollout_setup(ctx, key_frames, nt, H, W, warm_up);
     if (rc != TZ_OK) return rc;
     std::vector<int> flags(nt, 0);
@@ -1320,7 +1337,6 @@ extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt,
     kfc.push_back(nt);
     // decompress.py:138-179: warm_up copies of C0, then for every key interval: the key frame
     // itself, one prediction from the key frame, then recursion on the previous prediction.
-    std::vector<uint8_t> recon_key(nt, 0);
     std::vector<int> c0_slots;
     std::vector<PredItem> items;
     int produced = warm_up;
@@ -1332,7 +1348,6 @@ extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt,
                 return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", pi);
             }
             if (pi == kfc[k]) {
-                recon_key[pi] = 1;
                 c0_slots.push_back(pi);  // slot content is never used for reconstruction
             } else {
                 items.push_back(PredItem{pi, pi == kfc[k] + 1 ? 1 : 0, pi - 1, pi - kfc[k]});
@@ -1342,7 +1357,6 @@ extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt,
         tz_pool_release_all(ctx);
         return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (%d of %d frames)", produced, nt);
     }
-    recon_key[0] = 1;  // decompress.py:186
     rc = fill_c0(ctx, c0_slots);
     if (rc == TZ_OK) rc = run_schedule(ctx, items);
     if (rc == TZ_OK) {
@@ -1350,7 +1364,9 @@ extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt,
         if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "decode rollout failed: %s", hipGetErrorString(e));
     }
     if (rc == TZ_OK) {
-        ctx->key_mask = recon_key;
+        std::vector<uint8_t> km(nt);
+        for (int i = 0; i < nt; ++i) km[i] = flags[i] ? 1 : 0;
+        ctx->key_mask = recon_key_mask(km.data(), nt, warm_up);
         ctx->have_rollout = true;
         ctx->pred_contract = tz_get_contract(ctx);
         ctx->rollout_is_decode = true;
@@ -1383,6 +1399,7 @@ extern "C" int tz_rollout_decode_range(tz_ctx* ctx, const uint8_t* key_frames, i
         return tz_fail(ctx, TZ_ERR_INVALID, "range decode of a %d x %d x %d stack, the staged stack is %d x %d x %d", nt, H, W,
                        ctx->nt, ctx->H, ctx->W);
     ctx->enc_pending = false;
+    ctx->enc_resident = false;
     // the whole key stack is staged (key discovery looks at every frame); the prediction stack is sized below
     int rc = rollout_setup(ctx, key_frames, nt, H, W, warm_up, nullptr, 1);
     if (rc != TZ_OK) return rc;
@@ -1408,20 +1425,18 @@ extern "C" int tz_rollout_decode_range(tz_ctx* ctx, const uint8_t* key_frames, i
         if (flags[i]) kfc.push_back(i - r);
     kfc.push_back(ns);
     // the schedule of tz_rollout_decode (decompress.py:138-179) on the sub-stack
-    std::vector<uint8_t> recon_key(ns, 0);
     std::vector<int> c0_slots;
     std::vector<PredItem> items;
     for (int i = 0; i < sw; ++i) c0_slots.push_back(i);
     for (int k = sw; k + 1 < (int)kfc.size(); ++k)
         for (int pi = kfc[k]; pi < kfc[k + 1]; ++pi) {
             if (pi == kfc[k]) {
-                recon_key[pi] = 1;
                 c0_slots.push_back(pi);
             } else {
                 items.push_back(PredItem{pi, pi == kfc[k] + 1 ? 1 : 0, pi - 1, pi - kfc[k]});
             }
         }
-    recon_key[0] = 1;  // decompress.py:186 (frame 0, or the key frame r)
+    const std::vector<uint8_t> recon_key = recon_key_mask(mask.data() + r, ns, sw);   // (frame 0 of it: 0, or the key frame r)
     const size_t fsz = (size_t)H * W * 3;
     rc = tz_ensure(ctx, (void**)&ctx->d_pred, &ctx->cap_pred, (size_t)ns * ctx->Hp * ctx->Wp * 3 * 4);
     if (rc == TZ_OK) rc = fill_c0(ctx, c0_slots);
@@ -1577,6 +1592,8 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
     if (!ctx->have_rollout || ctx->rollout_is_decode) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode needs a tz_rollout first");
     TZ_TRY(tz_check_pred_contract(ctx, "tz_encode"));
     ctx->enc_pending = false;
+    ctx->enc_resident = false;
+    const bool to_resident = payload == nullptr;
     if (!payload) {  // keep the payload in the context: it leaves through tz_payload_get
         const size_t n = (size_t)ctx->nt * ctx->H * ctx->W * 3;
         TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, n * 2));
@@ -1653,6 +1670,7 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
     }
     outs.push_back(o_pay);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK && to_resident) ctx->enc_resident = true;   // (tz_encode_quality's payload == NULL)
     tz_pool_release_all(ctx);
     return rc;
 }
@@ -1671,6 +1689,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
     TZ_TRY(tz_check_pred_contract(ctx, "tz_encode_begin"));
     if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
     ctx->enc_pending = false;
+    ctx->enc_resident = false;   // d_payload now receives a shard's symbols
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, N * 2));
     ctx->payload_len = N;
@@ -1949,6 +1968,65 @@ extern "C" int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t paylo
         ctx->dec_first = first;
         ctx->dec_count = count;
     }
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// The report of `-c --report` (include/tezip_hip.h): the decoder's tail over the payload on the ENCODER's predictions and
+// frames -- the reconstruct reads frames only where the mask says "key", and there the encoder's originals are the bytes
+// key_frame.dat stores -- into pool scratch, then k_quality against the originals.  Only scratch is written.
+extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                                 int shuffled, tz_frame_quality* out) {
+    tz_roctx_range roctx_("tz_encode_quality");
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    if (!ctx->have_rollout || ctx->rollout_is_decode)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_quality needs the encoder rollout of a tz_rollout");
+    TZ_TRY(tz_check_pred_contract(ctx, "tz_encode_quality"));
+    if (table_len < -1 || table_len > TZ_NBINS || (table_len > 0 && !table)) return tz_fail(ctx, TZ_ERR_INVALID, "bad table");
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
+    const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe;
+    if (!payload) {
+        if (!ctx->enc_resident || !ctx->d_payload || ctx->payload_len != N)
+            return tz_fail(ctx, TZ_ERR_STATE, "no resident payload of a tz_encode on this rollout");
+        payload = ctx->d_payload;
+    }
+    if (payload_len != N)
+        return tz_fail(ctx, TZ_ERR_INVALID, "payload holds %zu elements, the encoded stack %zu", payload_len, N);
+    if (shuffled && (N & 7)) return tz_fail(ctx, TZ_ERR_INVALID, "byte shuffle needs a multiple of 8 elements");
+    std::vector<tz_out> outs;
+    tz_out o;
+    const void* d_pay = nullptr;
+    void *d_plain = nullptr, *d_mask = nullptr, *d_dec = nullptr, *d_diff = nullptr;
+    int rc = tz_dev_in(ctx, payload, N * 2, &d_pay);
+    if (rc == TZ_OK && shuffled) {   // byte planes -> int16 in scratch (the caller's payload stays as it is)
+        rc = tz_pool_alloc(ctx, N * 2, &d_plain);
+        if (rc == TZ_OK) rc = tzk_shuffle(ctx, (const int16_t*)d_pay, N, (uint8_t*)d_plain, 1);
+        d_pay = d_plain;
+    }
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_quality) * nt, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    const std::vector<uint8_t> recon = recon_key_mask(ctx->key_mask.data(), nt, ctx->warm_up);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_mask);
+    if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, recon.data(), nt);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N, &d_dec);
+    std::vector<int16_t> lut;
+    if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
+    const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
+    bool fused = false;   // the launches of tz_decode
+    if (rc == TZ_OK && !ctx->decode_unfused)
+        rc = tzk_decode_tail_fused(ctx, (const int16_t*)d_pay, h_lut, 1, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt,
+                                   H, W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec, &fused);
+    if (rc == TZ_OK && !fused) {
+        rc = tz_pool_alloc(ctx, N * 2, &d_diff);
+        if (rc == TZ_OK && h_lut) rc = tzk_unmap_undelta(ctx, (const int16_t*)d_pay, N, h_lut, 1, (int16_t*)d_diff);
+        else if (rc == TZ_OK) rc = tzk_undelta(ctx, (const int16_t*)d_pay, N, 0, 0, (int16_t*)d_diff);
+        if (rc == TZ_OK)
+            rc = tzk_reconstruct(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, (const int16_t*)d_diff, nt, H, W,
+                                 ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
+    }
+    if (rc == TZ_OK) rc = tzk_quality(ctx, ctx->d_frames, (const uint8_t*)d_dec, nt, fe, (tz_frame_quality*)o.dev);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device records too: complete on return)
     tz_pool_release_all(ctx);
     return rc;
 }

@@ -2338,6 +2338,168 @@ int tzk_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key, const ui
     return TZ_OK;
 }
 
+// ------------------------------------------------------------------------ reconstruction statistics
+// tz_encode_quality: per frame f of two unpadded uint8 stacks (the originals and what the decoder's tail makes of the
+// stored payload) sse = sum (dec - orig)^2, max |dec - orig| and #(dec != orig), as exact integers.  Streaming, 2 B read
+// per element: a workgroup owns a contiguous range of whole tiles (256 lanes x one 16-byte load of each stack), cut
+// without regard to frame boundaries so that small frames still fill the chip.  The running sums belong to one frame;
+// where a tile crosses the frame's end the lanes add the part in front of the boundary, the workgroup flushes (shuffle
+// reduction per wave, LDS across the four waves, then ONE u64 add, u32 max and u32 add per frame it touched, agent
+// scope) and carries on with the next frame.  A lane's loads of the next tile are issued before the current one is
+// summed (two 16-byte loads of each stack in flight per lane).  Integer reductions: the records do not depend on the grid.  The elements
+// in front of the first 16-byte boundary of `orig` (0..15) are added one by one by workgroup 0; stacks whose addresses
+// differ modulo 16 take byte loads throughout (VEC = false).
+static constexpr int QY_TILE = 256 * 16;   // elements per workgroup and step
+
+struct QyPart {
+    unsigned long long sse;
+    unsigned mx, cnt;
+};
+
+__device__ __forceinline__ void qy_add(unsigned long long* sse, unsigned* mx, unsigned* cnt, tz_frame_quality* q) {
+    __hip_atomic_fetch_add(&q->sse, *sse, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_max(&q->max_abs, *mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&q->n_changed, *cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// every thread of the workgroup calls this (block-uniform control flow); q = the frame's record
+__device__ __forceinline__ void qy_flush(unsigned long long sse, unsigned mx, unsigned cnt, QyPart* red, tz_frame_quality* q) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sse += __shfl_xor(sse, off, 64);
+        mx = max(mx, (unsigned)__shfl_xor((int)mx, off, 64));
+        cnt += (unsigned)__shfl_xor((int)cnt, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = QyPart{sse, mx, cnt};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sse = red[0].sse + red[1].sse + red[2].sse + red[3].sse;
+        mx = max(max(red[0].mx, red[1].mx), max(red[2].mx, red[3].mx));
+        cnt = red[0].cnt + red[1].cnt + red[2].cnt + red[3].cnt;
+        if (sse != 0) qy_add(&sse, &mx, &cnt, q);   // (sse == 0: nothing changed, the record stays as cleared)
+    }
+    __syncthreads();   // red is written again by the next flush
+}
+
+// elements e .. e+15 of both stacks, packed 4 per word; 0 in both for those at or behind `end`
+struct QyRaw {
+    uint4 a, b;
+};
+
+template <bool VEC>
+__device__ __forceinline__ QyRaw qy_fetch(const uint8_t* __restrict__ orig, const uint8_t* __restrict__ dec, size_t e, size_t end) {
+    QyRaw r;
+    if (VEC && e + 16 <= end) {
+        r.a = *(const uint4*)(orig + e);
+        r.b = *(const uint4*)(dec + e);
+    } else {
+        unsigned aw[4] = {0, 0, 0, 0}, bw[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (e + j < end) {
+                aw[j >> 2] |= (unsigned)orig[e + j] << (8 * (j & 3));
+                bw[j >> 2] |= (unsigned)dec[e + j] << (8 * (j & 3));
+            }
+        r.a = make_uint4(aw[0], aw[1], aw[2], aw[3]);
+        r.b = make_uint4(bw[0], bw[1], bw[2], bw[3]);
+    }
+    return r;
+}
+
+// |dec - orig| per element
+__device__ __forceinline__ void qy_absdiff(const QyRaw& r, unsigned ad[16]) {
+    const unsigned aw[4] = {r.a.x, r.a.y, r.a.z, r.a.w}, bw[4] = {r.b.x, r.b.y, r.b.z, r.b.w};
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int d = (int)((bw[w] >> (8 * k)) & 0xffu) - (int)((aw[w] >> (8 * k)) & 0xffu);
+            ad[4 * w + k] = (unsigned)(d < 0 ? -d : d);
+        }
+}
+
+// per_block: elements per workgroup, a multiple of QY_TILE; tiles start at `head`
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_quality(const uint8_t* __restrict__ orig, const uint8_t* __restrict__ dec, size_t n,
+                                                 size_t fe, unsigned head, size_t per_block, tz_frame_quality* __restrict__ out) {
+    __shared__ QyPart red[4];
+    if (blockIdx.x == 0 && threadIdx.x < head) {   // in front of the first 16-byte boundary: element by element
+        const size_t i = threadIdx.x;
+        const int d = (int)dec[i] - (int)orig[i];
+        if (d != 0) {
+            unsigned long long s = (unsigned long long)(d * d);
+            unsigned m = (unsigned)(d < 0 ? -d : d), c = 1;
+            qy_add(&s, &m, &c, out + i / fe);
+        }
+    }
+    const size_t b0 = head + (size_t)blockIdx.x * per_block;
+    if (b0 >= n) return;   // (workgroup-uniform)
+    const size_t b1 = min(n, b0 + per_block);
+    size_t f = b0 / fe;                          // the frame the running sums belong to
+    unsigned long long sse = 0;
+    unsigned mx = 0, cnt = 0;
+    QyRaw cur = qy_fetch<VEC>(orig, dec, b0 + (size_t)threadIdx.x * 16, min(b1, b0 + (size_t)QY_TILE));
+    for (size_t t = b0; t < b1; t += QY_TILE) {
+        const size_t tend = min(b1, t + (size_t)QY_TILE), e = t + (size_t)threadIdx.x * 16;
+        QyRaw nxt{};   // the next tile's loads are in flight while this one is summed
+        if (tend < b1) nxt = qy_fetch<VEC>(orig, dec, e + QY_TILE, min(b1, tend + (size_t)QY_TILE));
+        unsigned ad[16];
+        qy_absdiff(cur, ad);
+        cur = nxt;
+        for (size_t lo = t;;) {                  // segments [lo, lim) of the tile inside frame f
+            const size_t bnd = (f + 1) * fe, lim = min(bnd, tend);
+            unsigned s = 0, m = 0, c = 0;        // (16 x 255^2 fits)
+            if (lo == t && lim == tend) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    s += ad[j] * ad[j];
+                    m = max(m, ad[j]);
+                    c += ad[j] != 0;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const unsigned v = (e + j >= lo && e + j < lim) ? ad[j] : 0u;
+                    s += v * v;
+                    m = max(m, v);
+                    c += v != 0;
+                }
+            }
+            sse += s;
+            mx = max(mx, m);
+            cnt += c;
+            if (lim < bnd) break;                // frame f goes on behind this tile
+            qy_flush(sse, mx, cnt, red, out + f);
+            sse = 0;
+            mx = cnt = 0;
+            ++f;
+            lo = lim;
+            if (lo >= tend) break;
+        }
+    }
+    if (f * fe < n) qy_flush(sse, mx, cnt, red, out + f);
+}
+
+int tzk_quality(tz_ctx* ctx, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out) {
+    if (nframes <= 0 || fe == 0) return TZ_OK;
+    const size_t n = (size_t)nframes * fe;
+    TZ_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(tz_frame_quality) * nframes, ctx->stream));
+    const bool vec = (((uintptr_t)orig ^ (uintptr_t)dec) & 15) == 0;
+    const unsigned head = vec ? (unsigned)std::min<size_t>(n, (16 - ((uintptr_t)orig & 15)) & 15) : 0u;
+    const size_t tiles = std::max<size_t>(1, (n - head + QY_TILE - 1) / QY_TILE);
+    size_t G = ctx->quality_grid > 0 ? (size_t)ctx->quality_grid : (size_t)grid_for(tiles, 1);
+    G = std::max<size_t>(1, std::min(G, tiles));
+    const size_t per_block = (tiles + G - 1) / G * QY_TILE;
+    G = std::max<size_t>(1, (n - head + per_block - 1) / per_block);   // (no workgroup without a tile)
+    tz_prof_scope ps(ctx, TZP_QUALITY);
+    if (vec)
+        hipLaunchKernelGGL(k_quality<true>, dim3((unsigned)G), dim3(256), 0, ctx->stream, orig, dec, n, fe, head, per_block, d_out);
+    else
+        hipLaunchKernelGGL(k_quality<false>, dim3((unsigned)G), dim3(256), 0, ctx->stream, orig, dec, n, fe, head, per_block, d_out);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // ------------------------------------------------------------------------------ window SSE
 // compress.py:246: mean((X_test_pad - pred)^2) in float64 over PADDED frames.  Per frame the
 // sum is taken in a fixed order so that it is reproducible: 4096-element blocks; thread t sums

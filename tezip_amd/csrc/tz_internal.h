@@ -32,6 +32,7 @@ enum tz_prof_class {
     TZP_TABLE,      // HOST time: rank table + LUT from the downloaded histogram (compress.py:356-361)
     TZP_QSERIAL,    // not a time: `launches` counts the chains the quantiser sent through its serial fallback (k_q_serial)
     TZP_CARRY,      // prefix carry of the inverse scan (k_undelta_carry, tz_decode_range)
+    TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality)
     TZP_COUNT
 };
 
@@ -59,6 +60,7 @@ struct tz_ctx {
     int contract = 0;                 // arithmetic contract of the predictor: 0 = by frame size, 1 = TZ-PA1, 2 = TZ-PA2 (tz_set_contract, TEZIP_PA)
     int num_cus = 256;                // compute units of the device (k_wino: column blocks per workgroup)
     int wino_ipw = 0;                 // TEZIP_WINO_IPW (measurements): column blocks per k_wino workgroup, 0 = chosen per launch
+    int quality_grid = 0;             // TEZIP_QUALITY_GRID (diagnostic): workgroups of k_quality, 0 = chosen per launch
     // rollout-resident data
     int nt = 0, H = 0, W = 0, Hp = 0, Wp = 0, warm_up = 0;
     uint8_t* d_frames = nullptr;      // nt*H*W*3 (encoder: originals; decoder: key stack)
@@ -109,6 +111,7 @@ struct tz_ctx {
     bool staged = false;                    // d_frames was filled by tz_frames_begin / tz_frames_put
     int16_t* d_payload = nullptr;           // resident payload of a tz_encode(payload = NULL)
     size_t cap_payload = 0, payload_len = 0;
+    bool enc_resident = false;              // d_payload holds what tz_encode(payload = NULL) wrote on the current rollout
     unsigned* d_scan_status = nullptr;      // inverse scan: one word per resident block, tagged with the launch's epoch
     unsigned scan_epoch = 0;
     unsigned scan_dbg_skew = 0, scan_dbg_limit = 0;   // tz_scan_fault_inject: poll for another epoch / give up sooner
@@ -285,6 +288,8 @@ int tzk_decode_tail_range(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, 
 int tzk_undelta_carry(tz_ctx*, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_word);
 int tzk_reconstruct(tz_ctx*, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
                     int nframes, int H, int W, int Hp, int Wp, uint8_t* out);
+// per-frame (sse, max |dec - orig|, #changed) of two unpadded nframes x fe uint8 stacks; d_out (device) is cleared here
+int tzk_quality(tz_ctx*, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,
             double* h_sse);
 int tzk_sse_blocks(int Hp, int Wp);

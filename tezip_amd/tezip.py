@@ -42,6 +42,9 @@ FLAG_TABLE = (
     # not in the reference: with -u, write only frames A:B (half-open, either end may be omitted) or the one frame N of
     # the sequence, decoded without rolling out, scanning and saving the others (decompress.run(frames=...))
     (None, "--frames", dict(type=str, default=None, metavar="A:B", dest="frames")),
+    # not in the reference: with -c, also write quality.json (the error the bound introduced, per frame and for the
+    # sequence, from the stored payload decoded on the GPU) and print max_abs_err / PSNR / ratio (compress.run(REPORT=...))
+    (None, "--report", dict(action="store_true", dest="report")),
 )
 
 TEXT = {
@@ -103,6 +106,19 @@ def check_frames_flag(arg):
         return None, str(e)
 
 
+def check_report_flag(arg):
+    """--report is valid with -c of one single-GPU job only.  Returns None, or the message of a refusal."""
+    if not getattr(arg, "report", False):
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--report is valid with -c (--compress) only"
+    if getattr(arg, "sweep", None) is not None:
+        return "--report cannot be combined with --sweep"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--report is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+    return None
+
+
 def probe_gpu(force_cpu):
     """tezip.py:12-21 asked TensorFlow for a GPU; here a context on device 0 must open."""
     if force_cpu:
@@ -149,6 +165,10 @@ def _main(arg):
     if problem:   # exit status 2, as decompress.adopt_contract's errors: nothing was written
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_report_flag(arg)
+    if problem:   # likewise, before any GPU is touched
+        print("ERROR:", problem)
+        sys.exit(2)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # launched by torch.distributed.run: one rank per GPU
         from . import dist as tzdist
         tzdist.init_from_env()
@@ -179,6 +199,9 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if getattr(arg, "report", False):
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=True)
     return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                         arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle)
 
