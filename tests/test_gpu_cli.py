@@ -83,6 +83,25 @@ def test_wrong_model_size_is_reported_like_the_reference(tmp_path, capsys):
     assert "ERROR:Image size is out of scope for this model." in capsys.readouterr().out
 
 
+def test_cli_refuses_a_nan_tolerance(tmp_path):
+    """`-c ... -m absrel -b 0.3 nan`: the reference raises (E = NaN, compress.py:61,67).  The CLI must exit non-zero with a
+    message, and write no payload -- not a lossless job under the name of a lossy one."""
+    import subprocess
+    import sys
+    cfg = PredNetConfig(stack_sizes=(3, 16, 32))
+    mdir = str(tmp_path / "model")
+    weights.save_model(mdir, cfg, cfg.init_weights(seed=2, bias_scale=0.2), 16, 24)
+    ddir = _write(tmp_path, synth.translating_scene(6, 16, 24, seed=2), False)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for mode, bound in (("absrel", ["0.3", "nan"]), ("abs", ["nan"])):
+        cdir = str(tmp_path / ("c_" + mode))
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-m", "tezip_amd.tezip", "-c", mdir, ddir, cdir,
+                            "-p", "0", "-w", "3", "-m", mode, "-b"] + bound, cwd=root, capture_output=True, text=True, timeout=330)
+        assert r.returncode not in (0, 124, 137) and r.returncode > 0, (mode, r.returncode, r.stdout + r.stderr)
+        assert "NaN" in r.stdout + r.stderr, r.stdout + r.stderr
+        assert not os.path.exists(os.path.join(cdir, "entropy.dat")) and not os.path.exists(os.path.join(cdir, "key_frame.dat"))
+
+
 def test_cli_with_the_reference_model_files(tmp_path):
     """Model directory exactly as the reference leaves it: prednet_model.json + Keras
     prednet_weights.hdf5 (fixture written by real h5py, read by the built-in reader)."""

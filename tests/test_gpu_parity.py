@@ -186,6 +186,33 @@ def test_error_bound_rejects_negative_pwrel(ctx):
     ctx.error_bound(o, d, "abs", [-3.0])   # abs takes |b| (compress.py:29)
 
 
+def test_encode_rejects_a_nan_tolerance(ctx):
+    """A NaN tolerance makes every run's value (u + l) / 2 NaN, and the reference raises assigning it into its int array
+    (compress.py:61,67).  absrel 0.3 nan used to pass for the identity (min(0.3, NaN) = 0.3) and was encoded lossless.
+    absrel NaN 0 is lossless in the reference (compress.py:35 returns before E is formed) and stays so."""
+    from tezip_amd._lib import TezipError
+    nan = float("nan")
+    rng = np.random.default_rng(4)
+    nt, h, w = 6, 16, 24                       # unpadded: the fused lossy encode is the path taken
+    frames = _frames(rng, nt, h, w)
+    ctx.load_model(SMALL, SMALL.init_weights(seed=3, bias_scale=0.2))
+    ctx.prepare(h, w, max_batch=2)
+    ctx.rollout(frames, 0, 3)
+    for mode, bound in (("absrel", [0.3, nan]), ("absrel", [nan, 0.01]), ("abs", [nan]), ("rel", [nan]), ("pwrel", [nan])):
+        for entropy in (True, False):
+            with pytest.raises(TezipError) as e:
+                ctx.encode(mode, bound, entropy)
+            assert e.value.status == -1 and "NaN" in str(e.value), (mode, bound, entropy)
+        with pytest.raises(TezipError):        # the delta tap takes the unfused quantiser
+            ctx.encode(mode, bound, True, want_delta=True)
+        with pytest.raises(TezipError):
+            ctx.error_bound(frames[:1], np.zeros((1, h, w, 3), np.int16), mode, bound)
+    lossless, table, _ = ctx.encode("absrel", [nan, 0.0], True)
+    want, want_table, _ = ctx.encode("abs", [0.0], True)
+    np.testing.assert_array_equal(lossless, want)
+    np.testing.assert_array_equal(table, want_table)
+
+
 @pytest.mark.parametrize("n", [1, 7, 8, 4099, 3 * 64 * 64 * 5 + 3])
 @pytest.mark.parametrize("offset", [0, 1])
 def test_spatial_delta_histogram_and_inverse(ctx, n, offset):

@@ -68,3 +68,24 @@ def test_the_reference_itself_is_lossless_at_these_tolerances(name):
     mode, bound = str(R4[pre + "mode"]), R4[pre + "bound"].tolist()
     worst = {"abs": lambda b: abs(b[0]), "rel": lambda b: 255.0 * b[0], "absrel": lambda b: min(abs(b[0]), 255.0 * b[1])}[mode](bound)
     assert 0.0 < worst <= 0.499
+
+
+def test_a_nan_tolerance_is_never_the_identity():
+    """absrel 0.3 nan: std::min(|b0|, 255 * NaN) is |b0| = 0.3, which looked like the identity, so the job was encoded
+    lossless.  The reference raises on it (E = NaN, so (u + l) / 2 is NaN and cannot be assigned into its int array).  A NaN
+    tolerance must reach the general path, which refuses it (GPU half: tests/test_gpu_parity.py)."""
+    import ctypes
+    from tezip_amd import _lib
+    lib = _lib.load()
+    is_identity = getattr(lib, "_Z20tz_quant_is_identityidd")   # bool tz_quant_is_identity(int, double, double): host only
+    is_identity.restype, is_identity.argtypes = ctypes.c_bool, [ctypes.c_int, ctypes.c_double, ctypes.c_double]
+    nan = float("nan")
+    absrel = _lib.MODES["absrel"]
+    assert is_identity(absrel, 0.3, 0.9)              # the shortcut itself is still taken
+    assert not is_identity(absrel, 0.3, nan)
+    assert not is_identity(absrel, nan, 0.001)
+    assert not is_identity(absrel, nan, nan)
+    for mode in ("abs", "rel", "pwrel"):
+        assert not is_identity(_lib.MODES[mode], nan, 0.0), mode
+        assert not is_identity(_lib.MODES[mode], nan, nan), mode
+    assert is_identity(_lib.MODES["abs"], 0.3, nan)   # b1 is not read outside absrel

@@ -554,9 +554,11 @@ struct RoctxApi {
             pop = (int (*)())dlsym(h, "roctxRangePop");
         }
         if (!push || !pop) {
+            const char* why = dlerror();         // (once: a second call returns NULL)
+            fprintf(stderr, "[tezip] TEZIP_ROCTX is set but no ROCTx library could be opened (%s): no ranges\n", why ? why : "symbols missing");
             push = nullptr;
             pop = nullptr;
-            fprintf(stderr, "[tezip] TEZIP_ROCTX is set but no ROCTx library could be opened (%s): no ranges\n", dlerror() ? dlerror() : "symbols missing");
+            if (h) dlclose(h);
         }
     }
 };

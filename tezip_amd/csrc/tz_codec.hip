@@ -1505,6 +1505,9 @@ int tzk_error_bound(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8
         return tz_fail(ctx, TZ_ERR_INVALID, "%s bound must be >= 0 (the reference raises on a negative one)", mode == TZ_MODE_REL ? "rel" : "pwrel");
     if (mode == TZ_MODE_ABSREL && b1 < 0.0)
         return tz_fail(ctx, TZ_ERR_INVALID, "the rel bound of absrel must be >= 0 (the reference raises on a negative one)");
+    // a NaN tolerance makes every run's value (u + l) / 2 NaN: the reference raises assigning it into its int array
+    if (std::isnan(b0) || (mode == TZ_MODE_ABSREL && std::isnan(b1)))
+        return tz_fail(ctx, TZ_ERR_INVALID, "error bound is NaN (the reference raises on a NaN tolerance)");
     if (nframes <= 0 || H <= 0 || W <= 0) return TZ_OK;
     return quant_run(ctx, orig, diff, nullptr, h_skip, nframes, H, W, mode, b0, b1);
 }
@@ -1521,6 +1524,9 @@ int tzk_quant_sd_fused(tz_ctx* ctx, const float* pred, const uint8_t* orig, cons
         return tz_fail(ctx, TZ_ERR_INVALID, "%s bound must be >= 0 (the reference raises on a negative one)", mode == TZ_MODE_REL ? "rel" : "pwrel");
     if (mode == TZ_MODE_ABSREL && b1 < 0.0)
         return tz_fail(ctx, TZ_ERR_INVALID, "the rel bound of absrel must be >= 0 (the reference raises on a negative one)");
+    // a NaN tolerance makes every run's value (u + l) / 2 NaN: the reference raises assigning it into its int array
+    if (std::isnan(b0) || (mode == TZ_MODE_ABSREL && std::isnan(b1)))
+        return tz_fail(ctx, TZ_ERR_INVALID, "error bound is NaN (the reference raises on a NaN tolerance)");
     if (H != Hp || W != Wp || ((size_t)H * W) % 8 || nframes <= 0 || (((uintptr_t)sym) & 15)) return TZ_OK;
     QFused fu{pred, d_zero_mask, apply_offset, sym, d_hist, d_edge};
     TZ_TRY(quant_run(ctx, orig, nullptr, &fu, h_skip, nframes, H, W, mode, b0, b1));
@@ -1671,6 +1677,9 @@ static constexpr double kQIdentityMaxE = 0.499;
 
 bool tz_quant_is_identity(int mode, double b0, double b1) {
     static const bool enabled = !getenv("TEZIP_QMAP") || atoi(getenv("TEZIP_QMAP")) != 0;   // (0: A/B against the general quantiser)
+    // a NaN tolerance goes to the general path, which refuses it (std::min(|b0|, NaN) would be |b0|: absrel 0.3 nan looked
+    // like the identity and was encoded lossless)
+    if (std::isnan(b0) || (mode == TZ_MODE_ABSREL && std::isnan(b1))) return false;
     double worst;
     if (mode == TZ_MODE_ABS) worst = fabs(b0);
     else if (mode == TZ_MODE_REL) worst = 255.0 * b0;

@@ -886,9 +886,15 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
 // slower) or no level can split.
 static int epart_measure(tz_ctx* ctx, int n, const int* d_idx, int stride, const uint8_t* d_frames_u8, int H, int W,
                          const float* d_in_stack, float* d_out_stack, int slot0, const int* d_next_slot, int* choice) {
-    if (!ctx->ev_cal[0]) {
+    if (!ctx->ev_cal[0]) {                       // both events or neither: a later call never records on a null event
         TZ_HIP(ctx, hipEventCreate(&ctx->ev_cal[0]));
-        TZ_HIP(ctx, hipEventCreate(&ctx->ev_cal[1]));
+        hipError_t e = hipEventCreate(&ctx->ev_cal[1]);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(ctx->ev_cal[0]);
+            ctx->ev_cal[0] = nullptr;
+            ctx->ev_cal[1] = nullptr;
+            TZ_HIP(ctx, e);
+        }
     }
     const bool prof = ctx->prof_on;
     ctx->prof_on = false;                        // (the measurement's launches are not the caller's)
