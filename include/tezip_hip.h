@@ -214,8 +214,9 @@ int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int entropy, un
 int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const int16_t* table, int table_len,
                      int16_t* payload);
 /* ---- decoder back half (decompress.py:203-256): payload (+table) -> nt*H*W*3 uint8 frames,
- * using the prediction stack of the last tz_rollout_decode.  payload_len (elements) must be
- * nt*H*W*3 of that rollout: the reference fails at its reshape otherwise (decompress.py:240). */
+ * using the prediction stack of the last tz_rollout_decode (or tz_rollout_decode_range of [0, nt)).  payload_len
+ * (elements) must be nt*H*W*3 of that rollout: the reference fails at its reshape otherwise (decompress.py:240).
+ * table_len: -1 = no table, else 0..TZ_NBINS (anything else is TZ_ERR_INVALID). */
 int tz_decode(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
               uint8_t* frames_out);
 /* Streaming decode (decompress.py:87-113 decompresses and holds both files whole): stage the
@@ -250,9 +251,10 @@ int tz_range_restart(const uint8_t* key_mask, int nt, int warm_up, int first, in
 /* tz_rollout_decode_range: tz_rollout_decode for frames [first, first + count) only.  Key discovery runs over the whole
  * stack (key_mask[nt], host, receives it); the predictor runs over [restart, first + count) (plus the extension above)
  * of the resident stack, and the prediction stack holds those frames only.  key_frames == NULL: the stack staged with
- * tz_frames_begin / tz_frames_put, whose nt, H, W must be the call's (else TZ_ERR_INVALID).  The short stack serves
- * tz_decode_range only: tz_decode / tz_get_predictions / tz_decode_delta report TZ_ERR_STATE until the next whole
- * rollout.  TZ_ERR_INVALID for first / count outside [0, nt). */
+ * tz_frames_begin / tz_frames_put, whose nt, H, W must be the call's (else TZ_ERR_INVALID).  A stack short of [0, nt)
+ * serves tz_decode_range only: tz_decode / tz_get_predictions / tz_decode_delta report TZ_ERR_STATE until the next whole
+ * rollout; a range of [0, nt) is the whole rollout and serves them all.  TZ_ERR_INVALID for first / count outside
+ * [0, nt). */
 int tz_rollout_decode_range(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, int first, int count,
                             uint8_t* key_mask);
 /* tz_undelta_carry: the decoded element x[n0-1] of the inverse spatial delta over payload[0, n0), i.e.
@@ -262,7 +264,7 @@ int tz_rollout_decode_range(tz_ctx* ctx, const uint8_t* key_frames, int nt, int 
  * tz_decode.  n0 == 0 is TZ_ERR_INVALID: the stream start has no carry.  *carry (host) receives the element. */
 int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, const int16_t* table, int table_len, int16_t* carry);
 /* tz_decode_range: tz_decode for frames [first, first + count), on the prediction stack of the last
- * tz_rollout_decode_range (the range must lie inside the frames that call covered).  payload_len is the WHOLE stream,
+ * tz_rollout_decode_range or tz_rollout_decode (the range must lie inside the frames that call covered).  payload_len is the WHOLE stream,
  * nt*H*W*3, checked as tz_decode checks it; elements behind the range are not read.  For first > 0 the scan starts from
  * tz_undelta_carry's element over [0, first*H*W*3).  frames_out: count*H*W*3 uint8, or NULL to keep the frames in the
  * context for tz_decoded_get, whose frame indices are then sequence indices inside [first, first + count). */

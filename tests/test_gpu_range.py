@@ -292,6 +292,63 @@ def test_range_errors(ctx):
     np.testing.assert_array_equal(ctx.decode_range(payload, table, 5, 2), full[5:7])
 
 
+def test_whole_rollout_decode_at_the_warm_up_edge(ctx):
+    """What tz_rollout_decode accepts and refuses where the warm-up reaches the end of the stack or a key frame is missing
+    inside it (the range entry refuses warm_up >= nt; the whole one accepts warm_up == nt: every frame a C0 copy)."""
+    from tezip_amd import _lib
+    nt, h, w, p = 8, 24, 32, 1
+    keys, kd, payload, table, full = _job(ctx, nt, h, w, p, 3, None, "abs", [2.0], True)
+    c0 = ctx.get_predictions()[0].copy()                      # warm-up slot 0 of the p = 1 rollout: C0
+    km = ctx.rollout_decode(keys, nt)
+    np.testing.assert_array_equal(km, kd)
+    pred = ctx.get_predictions()
+    for i in range(nt):
+        np.testing.assert_array_equal(pred[i], c0)
+    got = ctx.decode(payload, table)                          # only frame 0 reconstructs from its key bytes
+    np.testing.assert_array_equal(got[0], full[0])
+    with pytest.raises(_lib.TezipError) as e:
+        ctx.rollout_decode(keys, nt + 1)
+    assert e.value.status == -1
+    assert "key frames do not cover the sequence (%d of %d frames)" % (nt + 1, nt) in str(e.value)
+    holed = keys.copy()
+    holed[1] = 0                                              # frames 0..2 must be key frames for warm_up 2
+    ks = [i for i in range(nt) if holed[i].any()]
+    with pytest.raises(_lib.TezipError) as e:
+        ctx.rollout_decode(holed, 2)
+    assert e.value.status == -1
+    assert "key frames do not cover the sequence (frame %d)" % ks[2] in str(e.value)
+    with pytest.raises(_lib.TezipError) as e:                 # the refused rollout leaves no prediction stack behind
+        ctx.get_predictions()
+    assert e.value.status == -4
+
+
+def test_whole_and_range_rollouts_serve_each_others_decodes(ctx):
+    """A whole decoder rollout and a range rollout of [0, nt) leave the same prediction stack, so each serves the other's
+    decode entry points with the same bytes."""
+    nt, h, w, p = 12, 24, 32, 1
+    keys, kd, payload, table, full = _job(ctx, nt, h, w, p, 4, None, "abs", [2.0], True)
+    pred = ctx.get_predictions().copy()
+    ks = [k for k in range(nt) if kd[k] and k > p]
+    for a, b in ((0, nt), (0, 3), (ks[0], nt), (ks[0] + 1, ks[0] + 3)):   # a whole rollout, then range decodes
+        np.testing.assert_array_equal(ctx.decode_range(payload, table, a, b - a), full[a:b], err_msg="frames [%d, %d)" % (a, b))
+    np.testing.assert_array_equal(ctx.rollout_decode_range(keys, p, 0, nt), kd)
+    np.testing.assert_array_equal(ctx.get_predictions(), pred)
+    np.testing.assert_array_equal(ctx.decode(payload, table), full)
+    ctx.decode(payload, table, out="resident")
+    np.testing.assert_array_equal(ctx.decoded_get(0, nt), full)
+
+
+def test_decode_refuses_a_table_length_below_minus_one(ctx):
+    nt, h, w, p = 6, 24, 32, 1
+    keys, kd, payload, table, full = _job(ctx, nt, h, w, p, 3, None, "abs", [2.0], True)
+    out = np.zeros_like(full)
+    assert ctx.lib.tz_decode(ctx.h, payload.ctypes.data, payload.size, None, -7, out.ctypes.data) == -1
+    assert b"bad table" in ctx.lib.tz_last_error(ctx.h)
+    assert ctx.lib.tz_decode_range(ctx.h, payload.ctypes.data, payload.size, None, -7, 0, nt, out.ctypes.data) == -1
+    assert not out.any()
+    np.testing.assert_array_equal(ctx.decode(payload, table), full)   # the context still decodes
+
+
 # --------------------------------------------------------------------------------------------------- 4. work proof
 def test_range_runs_only_the_predictor_steps_from_its_restart(ctx):
     from tezip_amd import _lib

@@ -581,7 +581,7 @@ class Context:
         if resident:
             out = None
         elif out is None:
-            out = np.empty((int(count), h, w, 3), np.uint8)
+            out = _RESULTS.empty((int(count), h, w, 3), np.uint8)
         tl = -1 if table is None else len(table)
         tb = None if table is None else np.ascontiguousarray(table, np.int16)
         self._ck(self.lib.tz_decode_range(self.h, None if payload is None else _ptr(payload), n, _ptr(tb), tl, int(first),

@@ -100,7 +100,7 @@ int tz_check_pred_contract(tz_ctx* ctx, const char* who) {
 
 extern "C" int tz_rollout_contract(tz_ctx* ctx) {
     if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->have_rollout && !ctx->have_range) return tz_fail(ctx, TZ_ERR_STATE, "no rollout in this context");
+    if (ctx->rollout_kind == tz_ctx::ROLLOUT_NONE) return tz_fail(ctx, TZ_ERR_STATE, "no rollout in this context");
     return ctx->pred_contract;
 }
 
@@ -661,6 +661,19 @@ extern "C" int tz_timer_stop(tz_ctx* ctx, float* ms) {
 
 // ------------------------------------------------------------------------------ rollout
 static int pad8(int v) { return (v + 7) / 8 * 8; }  // data_utils.py:103-107
+// frames of a sequence: the trailer stores nt as int16 (compress.py:390-394)
+constexpr int kMaxFrames = 32767;
+
+static void set_rollout(tz_ctx* ctx, tz_ctx::tz_rollout_kind kind, int pred_first, int pred_end) {
+    ctx->rollout_kind = kind;
+    ctx->pred_first = pred_first;
+    ctx->pred_end = pred_end;
+}
+
+// the prediction stack is one of `kind` and holds every frame of the sequence
+static bool whole_stack(const tz_ctx* ctx, tz_ctx::tz_rollout_kind kind) {
+    return ctx->rollout_kind == kind && ctx->pred_first == 0 && ctx->pred_end == ctx->nt;
+}
 
 // decompress.py:123-129: is there a non-zero sample in frame f?  16 bytes per lane where the frame allows it.
 // Key frames of a PINNED host stack, fetched by the compute stream itself (zero-copy reads over PCIe: page-locked host
@@ -802,7 +815,7 @@ __global__ void k_bcast_frames_flagged(const float* __restrict__ src, size_t fe,
 static int rollout_setup(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up,
                          const std::vector<int>* first = nullptr, int pred_frames = -1) {
     if (!ctx->model) return tz_fail(ctx, TZ_ERR_STATE, "no model loaded");
-    if (nt < 1 || H < 1 || W < 1 || warm_up < 0 || nt > 32767 || H > 32767 || W > 32767)
+    if (nt < 1 || H < 1 || W < 1 || warm_up < 0 || nt > kMaxFrames || H > 32767 || W > 32767)
         return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d warm_up=%d (int16 trailer limits)", nt, H, W, warm_up);
     int Hp, Wp, maxB;
     TZ_TRY(tz_model_dims(ctx, &Hp, &Wp, &maxB));
@@ -818,8 +831,7 @@ static int rollout_setup(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int 
     ctx->Hp = Hp;
     ctx->Wp = Wp;
     ctx->warm_up = warm_up;
-    ctx->have_rollout = false;
-    ctx->have_range = false;
+    set_rollout(ctx, tz_ctx::ROLLOUT_NONE, 0, 0);
     ctx->pending_src = nullptr;
     ctx->pending_sent.clear();
     const size_t fsz = (size_t)H * W * 3;
@@ -1043,10 +1055,9 @@ static int run_schedule(tz_ctx* ctx, std::vector<PredItem>& items, const uint8_t
 // the reference keeps everything in RAM, compress.py:116-122,329-333).
 extern "C" int tz_frames_begin(tz_ctx* ctx, int nt, int H, int W) {
     if (!ctx) return TZ_ERR_INVALID;
-    if (nt < 1 || H < 1 || W < 1 || nt > 32767 || H > 32767 || W > 32767)
+    if (nt < 1 || H < 1 || W < 1 || nt > kMaxFrames || H > 32767 || W > 32767)
         return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d (int16 trailer limits)", nt, H, W);
-    ctx->have_rollout = false;
-    ctx->have_range = false;
+    set_rollout(ctx, tz_ctx::ROLLOUT_NONE, 0, 0);
     ctx->staged = false;
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_frames, &ctx->cap_frames, (size_t)nt * H * W * 3));
     // earlier work queued on the compute stream may still read d_frames
@@ -1257,9 +1268,7 @@ extern "C" int tz_rollout(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int
         // slot 0 of every group opened on the way holds C0 (258); the last frame keeps its prediction (260-262: k_sse_decide
         // does not flag it)
         if (rc == TZ_OK && nt > 1) {
-            // (gridDim.y = nt: rollout_setup refuses nt > 32767 -- the trailer stores it as int16, compress.py:390-394 -- so
-            // the 65535 limit of a grid's y dimension is never reached)
-            static_assert(32767 <= 65535, "nt limit vs gridDim.y");
+            static_assert(kMaxFrames <= 65535, "gridDim.y = nt");   // (rollout_setup refuses nt > kMaxFrames)
             hipLaunchKernelGGL(k_bcast_frames_flagged, dim3(std::min(gx, 128), nt), dim3(256), 0, ctx->stream, c0, fe_pad, (const int*)d_flag, ctx->d_pred);
             if (hipGetLastError() != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "DWP launch failed");
         }
@@ -1281,9 +1290,8 @@ extern "C" int tz_rollout(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int
         ctx->key_mask = key;
         ctx->group_first = gfirst;
         ctx->quant_skip = qskip;
-        ctx->have_rollout = true;
+        set_rollout(ctx, tz_ctx::ROLLOUT_ENCODE, 0, nt);
         ctx->pred_contract = tz_get_contract(ctx);
-        ctx->rollout_is_decode = false;
         if (key_mask) memcpy(key_mask, key.data(), nt);
         if (mse_log) memcpy(mse_log, mse.data(), sizeof(double) * nt);
         hipError_t e = hipStreamSynchronize(ctx->stream);
@@ -1312,6 +1320,7 @@ static int discover_keys(tz_ctx* ctx, int nt, int H, int W, std::vector<int>* fl
     size_t fb = (size_t)H * W * 3;
     hipError_t e = hipMemsetAsync(d_flags, 0, sizeof(int) * nt, ctx->stream);
     int gx = (int)std::min<size_t>((fb + 255) / 256, 64);
+    static_assert(kMaxFrames <= 65535, "gridDim.y = nt");   // (rollout_setup refuses nt > kMaxFrames)
     hipLaunchKernelGGL(k_any_nonzero, dim3(gx, nt), dim3(256), 0, ctx->stream, ctx->d_frames, fb, (int*)d_flags);
     if (e == hipSuccess) e = hipMemcpyAsync(flags->data(), d_flags, sizeof(int) * nt, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1319,64 +1328,85 @@ static int discover_keys(tz_ctx* ctx, int nt, int H, int W, std::vector<int>* fl
     return TZ_OK;
 }
 
-extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up,
-                                 uint8_t* key_mask) {
-    tz_roctx_range roctx_("tz_rollout_decode");
-    if (!ctx) return TZ_ERR_INVALID;
+// The decoder's rollout (decompress.py:138-179) of frames [first, first + count) of the nt-frame key stack: the whole key
+// stack is staged (key discovery looks at every frame), the predictor runs from the range's restart frame r
+// (tz_range_restart) to the range's end, and slot i of the prediction stack holds frame r + i.  [0, nt) is the whole
+// decode.  range: tz_rollout_decode_range's refusals -- frames 0..warm_up must be key frames -- ahead of the walk's own.
+static int rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, int first, int count,
+                          uint8_t* key_mask, bool range) {
     ctx->enc_pending = false;
     ctx->enc_resident = false;
-    int rc = rollout_setup(ctx, key_frames, nt, H, W, warm_up);
+    // (a range sizes its prediction stack once it knows its restart frame)
+    int rc = rollout_setup(ctx, key_frames, nt, H, W, warm_up, nullptr, first == 0 && count == nt ? nt : 1);
     if (rc != TZ_OK) return rc;
     std::vector<int> flags(nt, 0);
     rc = discover_keys(ctx, nt, H, W, &flags);
+    for (int i = 0; range && rc == TZ_OK && i <= warm_up; ++i)
+        if (i >= nt || !flags[i]) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", i);
+    std::vector<uint8_t> mask(nt);
+    for (int i = 0; i < nt; ++i) mask[i] = flags[i] ? 1 : 0;
+    int r = 0;
+    if (rc == TZ_OK) rc = tz_range_restart(mask.data(), nt, warm_up, first, &r);
     if (rc != TZ_OK) {
         tz_pool_release_all(ctx);
         return rc;
     }
+    // sub-stack [r, end): from a key frame r > warm_up with warm_up 0, or from frame 0 with the job's warm_up -- and then
+    // reaching frame warm_up, which the key-interval walk starts from (the whole decode of warm_up == nt: all C0 copies)
+    const int end = r == 0 ? std::min(nt, std::max(first + count, warm_up + 1)) : first + count;
+    const int ns = end - r, sw = r == 0 ? warm_up : 0;
     std::vector<int> kfc;
     for (int i = 0; i < nt; ++i)
         if (flags[i]) kfc.push_back(i);
     kfc.push_back(nt);
-    // decompress.py:138-179: warm_up copies of C0, then for every key interval: the key frame
-    // itself, one prediction from the key frame, then recursion on the previous prediction.
+    // warm_up copies of C0, then for every key interval: the key frame itself, one prediction from the key frame, then
+    // recursion on the previous prediction.  The walk checks the whole stack and keeps the frames of [r, end).
     std::vector<int> c0_slots;
     std::vector<PredItem> items;
+    for (int i = 0; i < std::min(sw, ns); ++i) c0_slots.push_back(i);
     int produced = warm_up;
-    for (int i = 0; i < warm_up && i < nt; ++i) c0_slots.push_back(i);
     for (int k = warm_up; k + 1 < (int)kfc.size(); ++k)
         for (int pi = kfc[k]; pi < kfc[k + 1]; ++pi, ++produced) {
-            if (produced != pi || pi >= nt) {
+            if (produced != pi) {
                 tz_pool_release_all(ctx);
                 return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", pi);
             }
+            if (pi < r || pi >= end) continue;
             if (pi == kfc[k]) {
-                c0_slots.push_back(pi);  // slot content is never used for reconstruction
+                c0_slots.push_back(pi - r);  // slot content is never used for reconstruction
             } else {
-                items.push_back(PredItem{pi, pi == kfc[k] + 1 ? 1 : 0, pi - 1, pi - kfc[k]});
+                items.push_back(PredItem{pi - r, pi == kfc[k] + 1 ? 1 : 0, pi - 1 - r, pi - kfc[k]});
             }
         }
     if (produced != nt) {
         tz_pool_release_all(ctx);
         return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (%d of %d frames)", produced, nt);
     }
-    rc = fill_c0(ctx, c0_slots);
-    if (rc == TZ_OK) rc = run_schedule(ctx, items);
+    const std::vector<uint8_t> recon_key = recon_key_mask(mask.data() + r, ns, sw);   // (frame 0 of it: 0, or the key frame r)
+    const size_t fsz = (size_t)H * W * 3;
+    rc = tz_ensure(ctx, (void**)&ctx->d_pred, &ctx->cap_pred, (size_t)ns * ctx->Hp * ctx->Wp * 3 * 4);
+    if (rc == TZ_OK) rc = fill_c0(ctx, c0_slots);
+    if (rc == TZ_OK) rc = run_schedule(ctx, items, ctx->d_frames + (size_t)r * fsz);
     if (rc == TZ_OK) {
         hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "decode rollout failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess)
+            rc = tz_fail(ctx, TZ_ERR_HIP, "%sdecode rollout failed: %s", range ? "range " : "", hipGetErrorString(e));
     }
     if (rc == TZ_OK) {
-        std::vector<uint8_t> km(nt);
-        for (int i = 0; i < nt; ++i) km[i] = flags[i] ? 1 : 0;
-        ctx->key_mask = recon_key_mask(km.data(), nt, warm_up);
-        ctx->have_rollout = true;
+        ctx->key_mask = recon_key;
+        set_rollout(ctx, tz_ctx::ROLLOUT_DECODE, r, end);
         ctx->pred_contract = tz_get_contract(ctx);
-        ctx->rollout_is_decode = true;
-        if (key_mask)
-            for (int i = 0; i < nt; ++i) key_mask[i] = flags[i] ? 1 : 0;
+        if (key_mask) memcpy(key_mask, mask.data(), nt);
     }
     tz_pool_release_all(ctx);
     return rc;
+}
+
+extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up,
+                                 uint8_t* key_mask) {
+    tz_roctx_range roctx_("tz_rollout_decode");
+    if (!ctx) return TZ_ERR_INVALID;
+    return rollout_decode(ctx, key_frames, nt, H, W, warm_up, 0, nt, key_mask, false);
 }
 
 extern "C" int tz_range_restart(const uint8_t* key_mask, int nt, int warm_up, int first, int* restart) {
@@ -1400,69 +1430,13 @@ extern "C" int tz_rollout_decode_range(tz_ctx* ctx, const uint8_t* key_frames, i
     if (!key_frames && ctx->staged && (ctx->nt != nt || ctx->H != H || ctx->W != W))
         return tz_fail(ctx, TZ_ERR_INVALID, "range decode of a %d x %d x %d stack, the staged stack is %d x %d x %d", nt, H, W,
                        ctx->nt, ctx->H, ctx->W);
-    ctx->enc_pending = false;
-    ctx->enc_resident = false;
-    // the whole key stack is staged (key discovery looks at every frame); the prediction stack is sized below
-    int rc = rollout_setup(ctx, key_frames, nt, H, W, warm_up, nullptr, 1);
-    if (rc != TZ_OK) return rc;
-    std::vector<int> flags(nt, 0);
-    rc = discover_keys(ctx, nt, H, W, &flags);
-    // the whole-stack replay (tz_rollout_decode) needs frames 0..warm_up to be key frames; refuse what it refuses
-    for (int i = 0; rc == TZ_OK && i <= warm_up; ++i)
-        if (i >= nt || !flags[i]) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", i);
-    std::vector<uint8_t> mask(nt);
-    for (int i = 0; i < nt; ++i) mask[i] = flags[i] ? 1 : 0;
-    int r = 0;
-    if (rc == TZ_OK) rc = tz_range_restart(mask.data(), nt, warm_up, first, &r);
-    if (rc != TZ_OK) {
-        tz_pool_release_all(ctx);
-        return rc;
-    }
-    // sub-stack [r, end): from a key frame r > warm_up with warm_up 0, from frame 0 with the job's warm_up -- and then
-    // reaching frame warm_up, which the replay's key-interval walk starts from
-    const int end = r == 0 ? std::max(first + count, warm_up + 1) : first + count;
-    const int ns = end - r, sw = r == 0 ? warm_up : 0;
-    std::vector<int> kfc;
-    for (int i = r; i < end; ++i)
-        if (flags[i]) kfc.push_back(i - r);
-    kfc.push_back(ns);
-    // the schedule of tz_rollout_decode (decompress.py:138-179) on the sub-stack
-    std::vector<int> c0_slots;
-    std::vector<PredItem> items;
-    for (int i = 0; i < sw; ++i) c0_slots.push_back(i);
-    for (int k = sw; k + 1 < (int)kfc.size(); ++k)
-        for (int pi = kfc[k]; pi < kfc[k + 1]; ++pi) {
-            if (pi == kfc[k]) {
-                c0_slots.push_back(pi);
-            } else {
-                items.push_back(PredItem{pi, pi == kfc[k] + 1 ? 1 : 0, pi - 1, pi - kfc[k]});
-            }
-        }
-    const std::vector<uint8_t> recon_key = recon_key_mask(mask.data() + r, ns, sw);   // (frame 0 of it: 0, or the key frame r)
-    const size_t fsz = (size_t)H * W * 3;
-    rc = tz_ensure(ctx, (void**)&ctx->d_pred, &ctx->cap_pred, (size_t)ns * ctx->Hp * ctx->Wp * 3 * 4);
-    if (rc == TZ_OK) rc = fill_c0(ctx, c0_slots);
-    if (rc == TZ_OK) rc = run_schedule(ctx, items, ctx->d_frames + (size_t)r * fsz);
-    if (rc == TZ_OK) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "range decode rollout failed: %s", hipGetErrorString(e));
-    }
-    if (rc == TZ_OK) {
-        ctx->key_mask = recon_key;
-        ctx->have_range = true;
-        ctx->range_restart = r;
-        ctx->range_end = end;
-        ctx->pred_contract = tz_get_contract(ctx);
-        ctx->rollout_is_decode = true;
-        if (key_mask) memcpy(key_mask, mask.data(), nt);
-    }
-    tz_pool_release_all(ctx);
-    return rc;
+    return rollout_decode(ctx, key_frames, nt, H, W, warm_up, first, count, key_mask, true);
 }
 
 extern "C" int tz_get_predictions(tz_ctx* ctx, float* out) {
     if (!ctx || !out) return TZ_ERR_INVALID;
-    if (!ctx->have_rollout) return tz_fail(ctx, TZ_ERR_STATE, "no rollout in this context");
+    if (ctx->rollout_kind == tz_ctx::ROLLOUT_NONE || !whole_stack(ctx, ctx->rollout_kind))
+        return tz_fail(ctx, TZ_ERR_STATE, "no rollout in this context");
     size_t bytes = (size_t)ctx->nt * ctx->Hp * ctx->Wp * 3 * 4;
     TZ_HIP(ctx, hipMemcpyAsync(out, ctx->d_pred, bytes, hipMemcpyDefault, ctx->stream));
     TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1591,7 +1565,7 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
                          int* table_len, int16_t* delta_out) {
     tz_roctx_range roctx_("tz_encode");
     if (!ctx || !table_len || ((entropy & 1) && !table)) return TZ_ERR_INVALID;
-    if (!ctx->have_rollout || ctx->rollout_is_decode) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode needs a tz_rollout first");
+    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode needs a tz_rollout first");
     TZ_TRY(tz_check_pred_contract(ctx, "tz_encode"));
     ctx->enc_pending = false;
     ctx->enc_resident = false;
@@ -1687,7 +1661,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
                                int16_t* edge) {
     tz_roctx_range roctx_("tz_encode_begin");
     if (!ctx || !edge || (entropy && !hist)) return TZ_ERR_INVALID;
-    if (!ctx->have_rollout || ctx->rollout_is_decode) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_begin needs a tz_rollout first");
+    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_begin needs a tz_rollout first");
     TZ_TRY(tz_check_pred_contract(ctx, "tz_encode_begin"));
     if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
     ctx->enc_pending = false;
@@ -1724,7 +1698,7 @@ extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const
     if (ctx->enc_entropy != (table_len >= 0) || (table_len > 0 && !table) || table_len > TZ_MAX_TABLE)
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode_finish: table does not match the entropy flag of tz_encode_begin");
     const size_t N = ctx->payload_len;
-    if (!ctx->have_rollout || ctx->rollout_is_decode || N != (size_t)ctx->nt * ctx->H * ctx->W * 3) {
+    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE) || N != (size_t)ctx->nt * ctx->H * ctx->W * 3) {
         ctx->enc_pending = false;
         return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish: the resident symbols (%zu) are not those of the current rollout", N);
     }
@@ -1790,7 +1764,7 @@ extern "C" int tz_byte_unshuffle(tz_ctx* ctx, const uint8_t* in, size_t n, int16
 
 extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int16_t* delta_out) {
     if (!ctx || !delta_out) return TZ_ERR_INVALID;
-    if (!ctx->have_rollout || ctx->rollout_is_decode) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_delta needs a tz_rollout first");
+    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_delta needs a tz_rollout first");
     TZ_TRY(tz_check_pred_contract(ctx, "tz_encode_delta"));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
     const size_t N = (size_t)nt * H * W * 3;
@@ -1810,7 +1784,7 @@ extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int1
 
 extern "C" int tz_decode_delta(tz_ctx* ctx, const int16_t* delta, uint8_t* frames_out) {
     if (!ctx || !delta || !frames_out) return TZ_ERR_INVALID;
-    if (!ctx->have_rollout || !ctx->rollout_is_decode) return tz_fail(ctx, TZ_ERR_STATE, "tz_decode_delta needs a tz_rollout_decode first");
+    if (!whole_stack(ctx, tz_ctx::ROLLOUT_DECODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_decode_delta needs a tz_rollout_decode first");
     TZ_TRY(tz_check_pred_contract(ctx, "tz_decode_delta"));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
     const size_t N = (size_t)nt * H * W * 3;
@@ -1827,63 +1801,6 @@ extern "C" int tz_decode_delta(tz_ctx* ctx, const int16_t* delta, uint8_t* frame
         rc = tzk_reconstruct(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, (const int16_t*)d_diff, nt, H, W,
                              ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
-}
-
-extern "C" int tz_decode(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
-                         uint8_t* frames_out) {
-    tz_roctx_range roctx_("tz_decode");
-    if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->have_rollout || !ctx->rollout_is_decode) return tz_fail(ctx, TZ_ERR_STATE, "tz_decode needs a tz_rollout_decode first");
-    TZ_TRY(tz_check_pred_contract(ctx, "tz_decode"));
-    if (table_len > TZ_NBINS || (table_len >= 0 && !table && table_len > 0)) return tz_fail(ctx, TZ_ERR_INVALID, "bad table");
-    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
-    const size_t N = (size_t)nt * H * W * 3;
-    if (!payload) {  // staged with tz_payload_begin / tz_payload_put (on the copy stream)
-        if (!ctx->d_payload || ctx->payload_len < N) return tz_fail(ctx, TZ_ERR_STATE, "no staged payload of %zu elements", N);
-        TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));
-        TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
-        payload = ctx->d_payload;
-    }
-    ctx->have_decoded = false;
-    if (payload_len != N)  // decompress.py:240: the reshape raises
-        return tz_fail(ctx, TZ_ERR_INVALID, "payload holds %zu elements, the key-frame stack implies %zu", payload_len, N);
-    const bool resident = frames_out == nullptr;
-    if (resident) {  // keep the frames in the context: tz_decoded_get
-        TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_out, &ctx->cap_out, N));
-        frames_out = ctx->d_out;
-    }
-    std::vector<tz_out> outs;
-    tz_out o;
-    const void* d_pay = nullptr;
-    void *d_diff = nullptr, *d_mask = nullptr;
-    int rc = tz_dev_in(ctx, payload, N * 2, &d_pay);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, frames_out, N, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_mask);
-    if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, ctx->key_mask.data(), nt);
-    std::vector<int16_t> lut;
-    if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);  // decompress.py:203-236 rides on the scan of 240-245
-    const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    bool fused = false;
-    if (rc == TZ_OK && !ctx->decode_unfused)   // one launch: inverse remap + inverse spatial delta + reconstruct
-        rc = tzk_decode_tail_fused(ctx, (const int16_t*)d_pay, h_lut, 1, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt,
-                                   H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev, &fused);
-    if (rc == TZ_OK && !fused) {
-        rc = tz_pool_alloc(ctx, N * 2, &d_diff);
-        if (rc == TZ_OK && h_lut) rc = tzk_unmap_undelta(ctx, (const int16_t*)d_pay, N, h_lut, 1, (int16_t*)d_diff);
-        else if (rc == TZ_OK) rc = tzk_undelta(ctx, (const int16_t*)d_pay, N, 0, 0, (int16_t*)d_diff);  // decompress.py:240-245
-        if (rc == TZ_OK)                                                    // decompress.py:252-256,269
-            rc = tzk_reconstruct(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, (const int16_t*)d_diff, nt, H, W,
-                                 ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && resident) {   // only a decode whose work is queued leaves frames to fetch
-        ctx->have_decoded = true;
-        ctx->dec_first = 0;
-        ctx->dec_count = nt;
-    }
     tz_pool_release_all(ctx);
     return rc;
 }
@@ -1909,12 +1826,18 @@ static int staged_payload(tz_ctx* ctx, size_t need, const int16_t** payload) {
     return TZ_OK;
 }
 
+// table_len: -1 = no table (entropy remap off), else the length of the rank table
+static int check_table(tz_ctx* ctx, const int16_t* table, int table_len) {
+    if (table_len < -1 || table_len > TZ_NBINS || (table_len > 0 && !table)) return tz_fail(ctx, TZ_ERR_INVALID, "bad table");
+    return TZ_OK;
+}
+
 extern "C" int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, const int16_t* table, int table_len,
                                 int16_t* carry) {
     tz_roctx_range roctx_("tz_undelta_carry");
     if (!ctx || !carry) return TZ_ERR_INVALID;
     if (n0 == 0) return tz_fail(ctx, TZ_ERR_INVALID, "tz_undelta_carry: n0 = 0, the stream start has no carry");
-    if (table_len < -1 || table_len > TZ_NBINS || (table_len > 0 && !table)) return tz_fail(ctx, TZ_ERR_INVALID, "bad table");
+    TZ_TRY(check_table(ctx, table, table_len));
     if (!payload) TZ_TRY(staged_payload(ctx, n0, &payload));
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
@@ -1925,17 +1848,17 @@ extern "C" int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, 
     return rc;
 }
 
-extern "C" int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
-                               int first, int count, uint8_t* frames_out) {
-    tz_roctx_range roctx_("tz_decode_range");
-    if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->have_range) return tz_fail(ctx, TZ_ERR_STATE, "tz_decode_range needs a tz_rollout_decode_range first");
-    TZ_TRY(tz_check_pred_contract(ctx, "tz_decode_range"));
-    if (table_len < -1 || table_len > TZ_NBINS || (table_len > 0 && !table)) return tz_fail(ctx, TZ_ERR_INVALID, "bad table");
-    const int nt = ctx->nt, H = ctx->H, W = ctx->W, r = ctx->range_restart;
-    if (first < r || count < 1 || first >= ctx->range_end || count > ctx->range_end - first)
+// Frames [first, first + count) of the stream (decompress.py:203-256): the carry of the inverse scan in front of the range
+// when it does not start the stream, then the decoder's tail over the range.  The range lies inside the resident prediction
+// stack; payload is the WHOLE stream, of which nothing behind the range is read.
+static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, size_t payload_len, const int16_t* table,
+                         int table_len, int first, int count, uint8_t* frames_out) {
+    TZ_TRY(tz_check_pred_contract(ctx, who));
+    TZ_TRY(check_table(ctx, table, table_len));
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W, r = ctx->pred_first;
+    if (first < r || count < 1 || first >= ctx->pred_end || count > ctx->pred_end - first)
         return tz_fail(ctx, TZ_ERR_INVALID, "frame range [%d, %d + %d) outside the frames [%d, %d) the range rollout covered", first,
-                       first, count, r, ctx->range_end);
+                       first, count, r, ctx->pred_end);
     const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe, n0 = (size_t)first * fe, nr = (size_t)count * fe;
     if (!payload) TZ_TRY(staged_payload(ctx, N, &payload));
     ctx->have_decoded = false;
@@ -1951,7 +1874,7 @@ extern "C" int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t paylo
     const void* d_pay = nullptr;
     void* d_mask = nullptr;
     int16_t carry = 0;
-    int rc = tz_dev_in(ctx, payload, n0 * 2 + nr * 2, &d_pay);   // (nothing behind the range is read)
+    int rc = tz_dev_in(ctx, payload, n0 * 2 + nr * 2, &d_pay);
     if (rc == TZ_OK) rc = tz_dev_out(ctx, frames_out, nr, &o);
     if (rc == TZ_OK) outs.push_back(o);
     if (rc == TZ_OK) rc = tz_pool_alloc(ctx, count, &d_mask);
@@ -1961,17 +1884,34 @@ extern "C" int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t paylo
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
     if (rc == TZ_OK && first > 0) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, h_lut, &carry);
     if (rc == TZ_OK)
-        rc = tzk_decode_tail_range(ctx, (const int16_t*)d_pay + n0, h_lut, 1, first > 0, carry,
-                                   ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + n0,
-                                   (const uint8_t*)d_mask, count, H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
+        rc = tzk_decode_tail(ctx, (const int16_t*)d_pay + n0, h_lut, 1, first > 0, carry,
+                             ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + n0,
+                             (const uint8_t*)d_mask, count, H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && resident) {
+    if (rc == TZ_OK && resident) {   // only a decode whose work is queued leaves frames to fetch
         ctx->have_decoded = true;
         ctx->dec_first = first;
         ctx->dec_count = count;
     }
     tz_pool_release_all(ctx);
     return rc;
+}
+
+extern "C" int tz_decode(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                         uint8_t* frames_out) {
+    tz_roctx_range roctx_("tz_decode");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (!whole_stack(ctx, tz_ctx::ROLLOUT_DECODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_decode needs a tz_rollout_decode first");
+    return decode_frames(ctx, "tz_decode", payload, payload_len, table, table_len, 0, ctx->nt, frames_out);
+}
+
+extern "C" int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                               int first, int count, uint8_t* frames_out) {
+    tz_roctx_range roctx_("tz_decode_range");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (ctx->rollout_kind != tz_ctx::ROLLOUT_DECODE)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_decode_range needs a tz_rollout_decode_range first");
+    return decode_frames(ctx, "tz_decode_range", payload, payload_len, table, table_len, first, count, frames_out);
 }
 
 // The report of `-c --report` (include/tezip_hip.h): the decoder's tail over the payload on the ENCODER's predictions and
@@ -1981,10 +1921,10 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
                                  int shuffled, tz_frame_quality* out) {
     tz_roctx_range roctx_("tz_encode_quality");
     if (!ctx || !out) return TZ_ERR_INVALID;
-    if (!ctx->have_rollout || ctx->rollout_is_decode)
+    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE))
         return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_quality needs the encoder rollout of a tz_rollout");
     TZ_TRY(tz_check_pred_contract(ctx, "tz_encode_quality"));
-    if (table_len < -1 || table_len > TZ_NBINS || (table_len > 0 && !table)) return tz_fail(ctx, TZ_ERR_INVALID, "bad table");
+    TZ_TRY(check_table(ctx, table, table_len));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
     const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe;
     if (!payload) {
@@ -1998,7 +1938,7 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
     std::vector<tz_out> outs;
     tz_out o;
     const void* d_pay = nullptr;
-    void *d_plain = nullptr, *d_mask = nullptr, *d_dec = nullptr, *d_diff = nullptr;
+    void *d_plain = nullptr, *d_mask = nullptr, *d_dec = nullptr;
     int rc = tz_dev_in(ctx, payload, N * 2, &d_pay);
     if (rc == TZ_OK && shuffled) {   // byte planes -> int16 in scratch (the caller's payload stays as it is)
         rc = tz_pool_alloc(ctx, N * 2, &d_plain);
@@ -2014,18 +1954,9 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    bool fused = false;   // the launches of tz_decode
-    if (rc == TZ_OK && !ctx->decode_unfused)
-        rc = tzk_decode_tail_fused(ctx, (const int16_t*)d_pay, h_lut, 1, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt,
-                                   H, W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec, &fused);
-    if (rc == TZ_OK && !fused) {
-        rc = tz_pool_alloc(ctx, N * 2, &d_diff);
-        if (rc == TZ_OK && h_lut) rc = tzk_unmap_undelta(ctx, (const int16_t*)d_pay, N, h_lut, 1, (int16_t*)d_diff);
-        else if (rc == TZ_OK) rc = tzk_undelta(ctx, (const int16_t*)d_pay, N, 0, 0, (int16_t*)d_diff);
-        if (rc == TZ_OK)
-            rc = tzk_reconstruct(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, (const int16_t*)d_diff, nt, H, W,
-                                 ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
-    }
+    if (rc == TZ_OK)   // the launches of tz_decode
+        rc = tzk_decode_tail(ctx, (const int16_t*)d_pay, h_lut, 1, 0, 0, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H,
+                             W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
     if (rc == TZ_OK) rc = tzk_quality(ctx, ctx->d_frames, (const uint8_t*)d_dec, nt, fe, (tz_frame_quality*)o.dev);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device records too: complete on return)

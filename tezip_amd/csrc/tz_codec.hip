@@ -2137,34 +2137,14 @@ int tzk_undelta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t
     return scan_launch(ctx, in, n, has_carry, carry, nullptr, 0, out);
 }
 
-// decoder: inverse rank remap (+ 1600 - x) and inverse spatial delta in one pass over the payload
-int tzk_unmap_undelta(tz_ctx* ctx, const int16_t* in, size_t n, const int16_t* h_lut2112, int post_offset, int16_t* out) {
-    return scan_launch(ctx, in, n, 0, 0, h_lut2112, post_offset, out);
-}
-
-// the decoder's tail in one launch (inverse remap when there is a table, inverse spatial delta, reconstruct) where the
-// layout allows it: unpadded frames of a multiple of 16 elements, 16-byte aligned buffers.  *done = false: the caller
-// runs the two separate launches.
-int tzk_decode_tail_fused(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut2112, int post_offset, const float* pred,
-                          const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
-                          uint8_t* out, bool* done) {
-    *done = false;
-    const size_t fe = (size_t)H * W * 3, n = (size_t)nframes * fe;
-    if (n == 0 || H != Hp || W != Wp || fe % SCAN_EPT != 0 || !key ||
-        ((((uintptr_t)in | (uintptr_t)pred | (uintptr_t)key | (uintptr_t)out) & 15) != 0))
-        return TZ_OK;
-    const ScanRecon rc = {(const float4*)pred, key, d_key_mask, (unsigned long long)fe, out};
-    TZ_TRY(scan_launch(ctx, in, n, 0, 0, h_lut2112, post_offset, nullptr, &rc));
-    *done = true;
-    return TZ_OK;
-}
-
-// the decoder's tail over frames [first, first + nframes) of a stream (tz_decode_range): `in`, pred, key and d_key_mask
-// point at the range's first frame and `carry` is the decoded element in front of it (has_carry = 0 at the stream start).
-// The fused launch where tzk_decode_tail_fused's layout conditions hold, else a scan into a temporary and k_recon*.
-int tzk_decode_tail_range(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry,
-                          int16_t carry, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H,
-                          int W, int Hp, int Wp, uint8_t* out) {
+// the decoder's tail over frames [first, first + nframes) of a stream (tz_decode, tz_decode_range, tz_encode_quality): `in`,
+// pred, key and d_key_mask point at the range's first frame and `carry` is the decoded element in front of it (has_carry = 0
+// at the stream start).  One launch (inverse remap when there is a table, inverse spatial delta, reconstruct) where the
+// layout allows it: unpadded frames of a multiple of 16 elements, 16-byte aligned buffers, and no TEZIP_DECODE_UNFUSED.
+// Else a scan into a temporary and k_recon*.
+int tzk_decode_tail(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry, int16_t carry,
+                    const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
+                    uint8_t* out) {
     const size_t fe = (size_t)H * W * 3, n = (size_t)nframes * fe;
     if (n == 0) return TZ_OK;
     if (H == Hp && W == Wp && fe % SCAN_EPT == 0 && key && !ctx->decode_unfused &&

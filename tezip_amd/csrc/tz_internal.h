@@ -69,14 +69,13 @@ struct tz_ctx {
     std::vector<uint8_t> key_mask;    // nt
     std::vector<uint8_t> group_first; // nt: 1 where a group starts (delta slot 0 -> 0)
     std::vector<uint8_t> quant_skip;  // nt: 1 where error_bound is not applied
-    bool have_rollout = false, rollout_is_decode = false;
-    // tz_rollout_decode_range: the prediction stack holds frames [range_restart, range_end) of the nt-frame key stack
-    // (slot i = frame range_restart + i) and key_mask is indexed the same way; have_rollout stays false meanwhile, so that
-    // no whole-stack entry reads the short stack
-    bool have_range = false;
-    int range_restart = 0, range_end = 0;
+    // the resident prediction stack: made by which rollout, and holding frames [pred_first, pred_end) of the nt-frame
+    // sequence (slot i = frame pred_first + i; key_mask is indexed the same way).  tz_rollout and tz_rollout_decode leave
+    // the whole stack [0, nt); tz_rollout_decode_range a sub-stack, which only tz_decode_range reads.
+    enum tz_rollout_kind { ROLLOUT_NONE = 0, ROLLOUT_ENCODE, ROLLOUT_DECODE } rollout_kind = ROLLOUT_NONE;
+    int pred_first = 0, pred_end = 0;
     int pred_contract = 0;            // the arithmetic contract that produced the resident prediction stack (stamped by
-                                      // tz_rollout / tz_rollout_decode; tz_encode* / tz_decode* refuse a flip in between)
+                                      // tz_rollout / tz_rollout_decode*; tz_encode* / tz_decode* refuse a flip in between)
     // pinned staging ring for small host->device uploads (index arrays, masks, LUTs): the copy
     // out of it is truly asynchronous and the memory outlives the caller's locals
     uint8_t* ring = nullptr;
@@ -278,13 +277,9 @@ int tzk_lut(tz_ctx*, const int16_t* in, size_t n, const int16_t* h_lut2112, int 
 // forward: int16[n] -> low-byte plane | high-byte plane (2n bytes); inverse: planes (passed as `in`) -> int16[n] at `out`
 int tzk_shuffle(tz_ctx*, const int16_t* in, size_t n, uint8_t* out, int inverse);
 int tzk_undelta(tz_ctx*, const int16_t* in, size_t n, int has_carry, int16_t carry, int16_t* out);
-int tzk_unmap_undelta(tz_ctx*, const int16_t* in, size_t n, const int16_t* h_lut2112, int post_offset, int16_t* out);
-int tzk_decode_tail_fused(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, const float* pred,
-                          const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
-                          uint8_t* out, bool* done);
-int tzk_decode_tail_range(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry,
-                          int16_t carry, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H,
-                          int W, int Hp, int Wp, uint8_t* out);
+int tzk_decode_tail(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry, int16_t carry,
+                    const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
+                    uint8_t* out);
 int tzk_undelta_carry(tz_ctx*, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_word);
 int tzk_reconstruct(tz_ctx*, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
                     int nframes, int H, int W, int Hp, int Wp, uint8_t* out);

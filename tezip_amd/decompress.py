@@ -184,14 +184,12 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             stages.mark("zstd-d key_frame.dat + stage to HBM", ctx)
             return per
 
-        def rollout(warm_up):
+        def rollout(nt, warm_up):
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
-            if frames is None:
-                ctx.rollout_decode(None, warm_up)     # (key discovery, then the predictor launches are queued)
-            else:
-                ctx.rollout_decode_range(None, warm_up, frames[0], frames[1] - frames[0])
+            lo, hi = frames or (0, nt)
+            ctx.rollout_decode_range(None, warm_up, lo, hi - lo)   # (key discovery, then the predictor launches are queued)
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
 
@@ -216,7 +214,7 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
                 nt, H, W, warm_early = early
                 hp, wp = checks(nt, H, W)
                 per = stage_keys(nt, H, W, hp, wp)
-                rollout(warm_early)
+                rollout(nt, warm_early)
                 stages.mark("rollout (decoder) queued")
             tail = np.zeros(0, np.int16)
             off = 0
@@ -249,14 +247,11 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
         if early is None:
             hp, wp = checks(nt, H, W)
             per = stage_keys(nt, H, W, hp, wp)
-            rollout(warm_up)
+            rollout(nt, warm_up)
         fb = H * W * C
         stages.mark("rollout (decoder)", ctx)
-        lo, hi = (0, nt) if frames is None else frames
-        if frames is None:
-            ctx.decode(None, table, out="resident")
-        else:
-            ctx.decode_range(None, table, lo, hi - lo, out="resident")
+        lo, hi = frames or (0, nt)
+        ctx.decode_range(None, table, lo, hi - lo, out="resident")
         stages.mark("decode tail (frames resident)", ctx)
         if VERBOSE:
             prof = ctx.prof_get()
@@ -383,17 +378,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
                 ctx.prof_enable(True)
             t0 = time.time()
             tb = None if table is None else np.ascontiguousarray(table)
-            if frames is None:
-                ctx.rollout_decode(np.ascontiguousarray(key_frames), warm_up)
-            else:
-                first, count = frames[0], frames[1] - frames[0]
-                ctx.rollout_decode_range(np.ascontiguousarray(key_frames), warm_up, first, count)
+            first, end = frames or (0, nt)
+            ctx.rollout_decode_range(np.ascontiguousarray(key_frames), warm_up, first, end - first)
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
-            if frames is None:
-                frames = ctx.decode(np.ascontiguousarray(payload), tb)
-            else:
-                frames = ctx.decode_range(np.ascontiguousarray(payload), tb, first, count)
+            frames = ctx.decode_range(np.ascontiguousarray(payload), tb, first, end - first)
             if VERBOSE:
                 prof = ctx.prof_get()
                 if table is not None:
