@@ -89,8 +89,10 @@ int tz_model_load(tz_ctx* ctx, int nb_layers, const int* stack_sizes, const int*
  * TZ_ERR_UNSUPPORTED when a level's widest per-frame plane (gate columns / error maps) would
  * reach 2^30 floats: the kernels address inside one frame's plane with 32-bit offsets (frames and
  * batch items are 64-bit strides).  Which level binds depends on the model: for the reference's
- * (3,48,96,192) it is level 1's 192 gate columns, i.e. frames up to ~22.3 M pixels (4096 x 4096
- * passes, 8192 x 8192 does not); the error text names the model's limit.  A deviation: the
+ * (3,48,96,192) it is level 1's 192 gate columns: the largest square frame is exactly 4728 x 4728
+ * (4736 x 4736 is refused), the largest one-tile strip 8 x 2,796,200, ~22.3 M pixels in all;
+ * models with R_l < S_l bind on their error maps instead (2 S_l floats per pixel).  The error text
+ * names the model's limit; tests/test_gpu_frame_limit.py holds these edges.  A deviation: the
  * reference's frame size is bounded by memory only. */
 int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch);
 /* X_hat[0,0] of predict((1,2,Hp,Wp,3)) (compress.py:197): input independent. out: Hp*Wp*3 f32 */
