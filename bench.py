@@ -15,11 +15,17 @@ N>1    : one process per GPU.  `python bench.py --gpus N` starts the N ranks its
          all_gather for the shard-boundary carries, an all-reduce of 2111 histogram counters, and
          the payload shards sent point to point to rank 0, in flight while the next step rolls out; the
          clock stops only after the last shards have landed) => weak scaling, 4 windows per GPU.
-         The sharded result is checked byte-identical to a single-GPU run of the same sequence
-         (untimed).  `--mode replicas` (every rank its own 80-frame sequence, nothing exchanged)
+         With --full the sharded result is checked byte-identical to a single-GPU run of the same
+         sequence (untimed).  `--mode replicas` (every rank its own 80-frame sequence, nothing exchanged)
          is kept and is reported as an extra key of the same line.
 
-Extra objects on the JSON line: "roofline" (dominant kernel = MFMA convolution),
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it sets up,
+runs the W + K steps, writes --dump-outputs if asked, and prints the line with `metric`, `value`, `unit`,
+`ms_per_step`, `higher_is_better`, `dtype` and the workload's description.  Everything else takes runs of its
+own and comes with `--full` (the --no-* options trim a --full run): the N > 1 check against a single-GPU run
+and the extra objects below.
+
+Extra objects on the JSON line (`--full`): "roofline" (dominant kernel = MFMA convolution),
 "roofline_delta" (the HBM-bound delta kernel named by the north star), "cpu_baseline"
 (the C oracle = a port of the same path, timed on this box's host cores, rank 0, N=1 only),
 "host_to_host" (SURVEY.md §8d's wall-clock definition: uint8 stack in host memory -> int16
@@ -344,13 +350,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mode", choices=["sharded", "replicas"], default="sharded",
                     help="N>1: shard the windows of ONE 80*N-frame sequence (default) or one 80-frame sequence per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip host_to_host / lossy_abs2 / cfg4_sharded / the other mode")
-    ap.add_argument("--no-host-pipeline", action="store_true", help="skip the PNG -> compress.run -> decompress.run -> PNG leg")
-    ap.add_argument("--no-trained-ratio", action="store_true", help="skip training a model for compression_ratio_trained")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: the N > 1 check against one GPU, per-kernel "
+                         "times and rooflines, compression ratios, host to host, the other precisions, modes and "
+                         "configurations, decode, the host pipeline and the CPU baseline (the --no-* options trim it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip host_to_host / lossy_abs2 / cfg4_sharded / the other mode and the other extras")
+    ap.add_argument("--no-host-pipeline", action="store_true", help="with --full: skip the PNG -> compress.run -> decompress.run -> PNG leg")
+    ap.add_argument("--no-trained-ratio", action="store_true", help="with --full: skip training a model for compression_ratio_trained")
     ap.add_argument("--profile-legs", action="store_true",
-                    help="with --no-extras: still run ONE untimed `abs 2` encode and ONE decode of the job, so that a rocprofv3 "
-                         "trace of this command also holds the lossy-tail and the decoder kernels (profiles/collect.sh)")
+                    help="with --full --no-extras: still run ONE untimed `abs 2` encode and ONE decode of the job, so that a "
+                         "rocprofv3 trace of this command also holds the lossy-tail and the decoder kernels (profiles/collect.sh)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: "
                          "key, table, a fixed sample of the payload and per-frame sums of the whole payload")
@@ -431,6 +442,49 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, state, dev)
 
+    line = {
+        "metric": "frames/sec (predict+delta-encode), 512x512 seq",
+        "value": value,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "value_definition": "device-resident: frames already in HBM when the clock starts, payload left in HBM, table on the "
+                            "host.  The bench contract fixes this definition (inputs resident in HBM when the timed region "
+                            "starts; a PCIe-inclusive rate is never `value`).  SURVEY.md 8d / BASELINE.md 4 define the "
+                            "BASELINE metric host to host: THAT number is value_host_to_host (pinned buffers, PCIe both ways "
+                            "inside the clock), measured by `--full` in the same run -- quote it when comparing with the 50 "
+                            "frames/s target",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": ("512x512x3 synthetic turbulence stack, %d frames per GPU (ONE %d-frame sequence), SWP 20-frame "
+                                "windows, warm_up 0, lossy rel 1e-3, entropy remap on; PredNet (3,48,96,192) glorot seed 123"
+                                % (nt_rank, nt_total))
+                   + (" [EXPLORATION: not the BASELINE.json sequence length]" if explore else ""),
+                   "frames_per_step": nt_total if sharded else nt_rank * world,
+                   "sharding": ("windows of one sequence over the ranks (dist.compress_sharded), payload gathered on rank 0"
+                                if sharded else "replicas: one sequence per GPU"),
+                   "backend": backend, "ranks_share_one_gpu": single_dev if world > 1 else False},
+    }
+
+    def finish():
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(real_stdout, (json.dumps(line) + "\n").encode())
+        ctx.close()
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
+    # ==================================================================== --full: everything beyond the headline
     check = None
     if sharded and world > 1 and rank == 0:
         full = turbulence_cuda(nt_total, 0, nt_total, H, W, 3, dev)
@@ -719,35 +773,10 @@ def main():
         extras["compression_ratio_trained"].pop("_weights", None)
 
     if rank == 0:
-        line = {
-            "metric": "frames/sec (predict+delta-encode), 512x512 seq",
-            "value": value,
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "value_definition": "device-resident: frames already in HBM when the clock starts, payload left in HBM, table on the "
-                                "host.  The bench contract fixes this definition (inputs resident in HBM when the timed region "
-                                "starts; a PCIe-inclusive rate is never `value`).  SURVEY.md 8d / BASELINE.md 4 define the "
-                                "BASELINE metric host to host: THAT number is value_host_to_host (pinned buffers, PCIe both ways "
-                                "inside the clock), measured in this same run -- quote it when comparing with the 50 frames/s target",
+        line["config"]["predicted_frames_per_step_rank0"] = n_pred
+        line.update({
             "value_host_to_host": (extras.get("host_to_host") or {}).get("pinned_frames_per_s"),
             "value_host_to_host_pipelined": (extras.get("host_to_host") or {}).get("pinned_pipelined_frames_per_s"),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": ("512x512x3 synthetic turbulence stack, %d frames per GPU (ONE %d-frame sequence), SWP 20-frame "
-                                    "windows, warm_up 0, lossy rel 1e-3, entropy remap on; PredNet (3,48,96,192) glorot seed 123"
-                                    % (nt_rank, nt_total))
-                       + (" [EXPLORATION: not the BASELINE.json sequence length]" if explore else ""),
-                       "frames_per_step": nt_total if sharded else nt_rank * world,
-                       "predicted_frames_per_step_rank0": n_pred,
-                       "sharding": ("windows of one sequence over the ranks (dist.compress_sharded), payload gathered on rank 0"
-                                    if sharded else "replicas: one sequence per GPU"),
-                       "backend": backend, "ranks_share_one_gpu": single_dev if world > 1 else False},
             "sharded_check": check,
             "compression_ratio": ratio,
             "arithmetic_contract": "TZ-PA%d" % contract,
@@ -797,14 +826,9 @@ def main():
                                      "share_of_step_device_time": tail_ms / max(step_dev_ms, 1e-9)},
             "kernel_ms_per_step": {k: v[0] for k, v in prof.items()},
             "cpu_baseline": cpu,
-        }
+        })
         line.update(extras)
-        sys.stdout.flush()
-        os.write(real_stdout, (json.dumps(line) + "\n").encode())
-    ctx.close()
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 def decode_leg(job, ctx, frames, own_state, args):

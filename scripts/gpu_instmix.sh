@@ -3,10 +3,11 @@
 # SALU, LDS, VMEM instructions per wave.  VALU instructions that are not MFMAs take 4 cycles of their SIMD each, which the
 # matrix pipe of that SIMD does not get (scripts/microbench/coexec.hip): this is the budget to watch.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --kernel-trace --output-format csv -d gpurun_out/imix -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras > /dev/null 2> gpurun_out/imix.err
+export OUT="${OUT:?set OUT to the directory the results go to}" && mkdir -p "$OUT"
+timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --kernel-trace --output-format csv -d $OUT/imix -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/imix.err
 python - <<'PY'
-import csv, glob, collections
-f = glob.glob("gpurun_out/imix/*/*_counter_collection.csv")[0]
+import csv, glob, collections, os
+f = glob.glob(os.environ["OUT"] + "/imix/*/*_counter_collection.csv")[0]
 agg = collections.defaultdict(lambda: collections.defaultdict(float))
 n = collections.Counter()
 seen = set()
@@ -27,4 +28,4 @@ for k, c in sorted(agg.items(), key=lambda kv: -kv[1].get("SQ_INSTS_MFMA", 0)):
     print("%-46s %6d %9.0f %8.0f %8.0f %8.0f %8.0f %8.0f %10.3f" % (k[:46], n[k], w / n[k], valu / w, mf / w, c.get("SQ_INSTS_SALU", 0) / w,
           c.get("SQ_INSTS_LDS", 0) / w, (c.get("SQ_INSTS_VMEM_RD", 0) + c.get("SQ_INSTS_VMEM_WR", 0)) / w, (valu * 4) / (mf * 32) if mf else float("nan")))
 PY
-rm -rf gpurun_out/imix
+rm -rf $OUT/imix

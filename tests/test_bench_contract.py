@@ -162,3 +162,20 @@ def test_dump_outputs_writes_the_step_result_as_float_arrays(bench, tmp_path):
     np.testing.assert_array_equal(got["key"], [1, 0, 0, 1, 0, 0])
     np.testing.assert_array_equal(got["table"], [0, -1, 1, 5])
     assert got["payload_sample"].size == bench.DUMP_SAMPLE and set(np.unique(got["payload_sample"])) <= set(range(-300, 300))
+
+
+def test_plain_run_stops_after_the_headline(bench):
+    """A plain run sets up, runs the W + K steps, writes --dump-outputs and prints the line; everything that takes runs of its
+    own (the N > 1 check against one GPU, per-kernel times, rooflines, extras, CPU baseline) comes only with --full
+    (checked on the source: the run itself needs a GPU; tests/test_gpu_bench.py runs it)."""
+    import inspect
+    src = inspect.getsource(bench.main)
+    assert 'ap.add_argument("--full", action="store_true"' in src
+    plain_end = src.index("if not args.full:")
+    assert src.index("elapsed = job.timed(step, args.steps, args.warmup") < src.index("dump_outputs(args.dump_outputs") < plain_end
+    for full_only in ("verify_against_one_gpu(", "ctx.prof_enable(True)", "ctx.delta_encode(", "decode_leg(", "configs_leg(",
+                      "cfg5_sweep(", "trained_ratio(", "cfg4_sharded(", "host_pipeline_leg(", "cpu_baseline(", "zstd.compress_array("):
+        assert src.index(full_only) > plain_end, full_only
+    head = src[src.index("    line = {"):plain_end]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert '"%s":' % key in head, key
