@@ -194,16 +194,15 @@ int tz_payload_get(tz_ctx* ctx, size_t offset, size_t count, int16_t* out);
 int tz_set_payload_deferred(tz_ctx* ctx, int on);
 int tz_payload_wait(tz_ctx* ctx);
 /* First stage of tz_encode only (compress.py:292-319): delta + error-bound quantisation of the
- * context-resident rollout -> int16 delta stack nt*H*W*3.  Used when frame windows are sharded
- * over GPUs: the spatial delta and the histogram then need a carry / a sum across shards
- * (tz_spatial_delta with has_carry, tz_build_table, tz_remap). */
+ * context-resident rollout -> int16 delta stack nt*H*W*3, the stack tz_encode's delta_out receives.
+ * (The sharded encoder does not need it: it runs tz_encode_begin / tz_encode_finish.) */
 int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int16_t* delta_out);
 /* tz_encode in two phases, for jobs whose frame windows are sharded over GPUs (the
  * reference is single-process).  The spatial delta runs over the whole flattened stack
  * (compress.py:339) and the rank table comes from the global histogram (compress.py:354-361), so a
  * shard runs compress.py:292-355 on its own frames (begin), the ranks exchange one carry element
  * and sum the 2111 counters, and the shard finishes compress.py:356-373 with the global table
- * (finish).  Same kernels as tz_encode.
+ * (finish).  tz_encode is the one-shard case: the same code runs both.
  * begin: hist (host, TZ_NBINS counters, may be NULL when entropy == 0) receives this shard's counts
  * taken WITHOUT a carry; edge[0], edge[1] (host) the first and the last element of the shard's
  * quantised delta stack.  edge[1] is the carry of the next shard; with its own carry c a shard moves

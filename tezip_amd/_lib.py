@@ -269,6 +269,19 @@ def _ptr(x, dtype=None):
     raise TypeError("unsupported buffer type %r" % type(x))
 
 
+def _bounds(bound):
+    """-b values -> (b0, b1) of the C ABI (b1 is absrel's rel bound, 0 for the other modes)."""
+    return float(bound[0]), float(bound[1]) if len(bound) > 1 else 0.0
+
+
+def _payload_out(out, n):
+    """An encoder's payload output -> the buffer passed on and returned: "resident" keeps the payload in the context
+    (payload_get) and is None, None is a new host array of n int16, anything else a host or device buffer."""
+    if isinstance(out, str) and out == "resident":
+        return None
+    return _RESULTS.empty(n, np.int16) if out is None else out
+
+
 class Context:
     """One context per GPU/process (tz_ctx)."""
 
@@ -482,13 +495,8 @@ class Context:
         int16 payload (same buffer size), see tz_byte_shuffle.  want_delta / delta_out (a host or
         device buffer of nt*H*W*3 int16): also return the quantised delta stack."""
         nt, h, w = self._shape
-        b0 = float(bound[0])
-        b1 = float(bound[1]) if len(bound) > 1 else 0.0
-        resident = isinstance(payload, str) and payload == "resident"  # stays in the context: payload_get
-        if resident:
-            payload = None
-        elif payload is None:
-            payload = _RESULTS.empty(nt * h * w * 3, np.int16)
+        b0, b1 = _bounds(bound)
+        payload = _payload_out(payload, nt * h * w * 3)
         table = np.zeros(TZ_MAX_TABLE, np.int16)
         tlen = C.c_int(0)
         delta = delta_out if delta_out is not None else (np.empty((nt, h, w, 3), np.int16) if want_delta else None)
@@ -511,10 +519,10 @@ class Context:
         """First phase of a window-sharded encode (tz_encode_begin): -> (hist uint64[2111] | None,
         first, last) where hist counts this shard's symbols taken without a carry and first / last
         are the edge elements of its quantised delta stack.  The symbols stay in the context."""
-        b1 = float(bound[1]) if len(bound) > 1 else 0.0
+        b0, b1 = _bounds(bound)
         hist = np.zeros(TZ_NBINS, np.uint64) if entropy else None
         edge = np.zeros(2, np.int16)
-        self._ck(self.lib.tz_encode_begin(self.h, MODES[mode], float(bound[0]), b1, int(bool(entropy)),
+        self._ck(self.lib.tz_encode_begin(self.h, MODES[mode], b0, b1, int(bool(entropy)),
                                           None if hist is None else hist.ctypes.data, edge.ctypes.data))
         return hist, int(edge[0]), int(edge[1])
 
@@ -523,11 +531,7 @@ class Context:
         the first shard), table = the table of the summed histogram (None: no remap).  out: host or
         device buffer, "resident" keeps the payload in the context (payload_get)."""
         nt, h, w = self._shape
-        resident = isinstance(out, str) and out == "resident"
-        if resident:
-            out = None
-        elif out is None:
-            out = _RESULTS.empty(nt * h * w * 3, np.int16)
+        out = _payload_out(out, nt * h * w * 3)
         tb = None if table is None else np.ascontiguousarray(table, np.int16)
         self._ck(self.lib.tz_encode_finish(self.h, int(carry is not None), int(carry or 0), _ptr(tb),
                                            -1 if tb is None else len(tb), _ptr(out)))
@@ -540,8 +544,8 @@ class Context:
         nt, h, w = self._shape
         if out is None:
             out = np.empty((nt, h, w, 3), np.int16)
-        b1 = float(bound[1]) if len(bound) > 1 else 0.0
-        self._ck(self.lib.tz_encode_delta(self.h, MODES[mode], float(bound[0]), b1, _ptr(out)))
+        b0, b1 = _bounds(bound)
+        self._ck(self.lib.tz_encode_delta(self.h, MODES[mode], b0, b1, _ptr(out)))
         return out
 
     def decode_delta(self, delta, out=None):
@@ -616,9 +620,9 @@ class Context:
 
     def error_bound(self, orig, diff, mode, bound, skip_mask=None):
         n, h, w = orig.shape[:3]
-        b1 = float(bound[1]) if len(bound) > 1 else 0.0
+        b0, b1 = _bounds(bound)
         sk = None if skip_mask is None else np.ascontiguousarray(skip_mask, np.uint8)
-        self._ck(self.lib.tz_error_bound(self.h, _ptr(orig), _ptr(diff), _ptr(sk), n, h, w, MODES[mode], float(bound[0]), b1))
+        self._ck(self.lib.tz_error_bound(self.h, _ptr(orig), _ptr(diff), _ptr(sk), n, h, w, MODES[mode], b0, b1))
         return diff
 
     def spatial_delta(self, x, offset, carry=None, hist=None, out=None):

@@ -281,6 +281,32 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
     return kf.result(), esize
 
 
+def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
+    """The checks of a compression job, in this order, each refusal with its message and exit(): the frame size against
+    the model's, the number of frames, --shuffle's multiple of 8.  The accepted job then writes filename.txt into
+    out_dir (None: not this process): compress.py:133-136 writes it after the images are loaded, and a rejected job
+    must not leave a partial directory behind.  Returns the padded frame size."""
+    nt, H, W = src.nt, src.H, src.W
+    hp, wp = padding_shape(H, W)
+    if model_shape is not None and (model_shape[0] != hp or model_shape[1] != wp):
+        print("ERROR:Image size is out of scope for this model.")
+        print("Compatible sizes for this model are height", model_shape[0] - 7, "to", model_shape[0], "and width",
+              model_shape[1] - 7, "to", model_shape[1])
+        exit()
+    if nt < warm_up + 2:
+        print("ERROR: need at least warm_up+2 images (%d given, warm_up %d)." % (nt, warm_up))
+        exit()
+    if shuffle and (nt * H * W * 3) % 8:
+        print("ERROR: --shuffle needs nt*H*W*3 to be a multiple of 8 (%d x %d x %d x 3 is not)." % (nt, H, W))
+        exit()
+    if out_dir is not None:
+        with open(os.path.join(out_dir, 'filename.txt'), 'w', encoding='UTF-8') as f:
+            f.write(f"{int(src.is_rgb)}\n")
+            for file_name in src.files:
+                f.write("%s\n" % file_name)
+    return hp, wp
+
+
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
@@ -315,24 +341,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
         stages.mark("first window decoded")
         cfg, wts, model_shape = open_model(WEIGHTS_DIR)
         stages.mark("model directory read")
-        hp, wp = padding_shape(H, W)
-        if model_shape is not None and (model_shape[0] != hp or model_shape[1] != wp):
-            print("ERROR:Image size is out of scope for this model.")
-            print("Compatible sizes for this model are height", model_shape[0] - 7, "to", model_shape[0], "and width",
-                  model_shape[1] - 7, "to", model_shape[1])
-            exit()
-        if nt < PREPROCESS + 2:
-            print("ERROR: need at least warm_up+2 images (%d given, warm_up %d)." % (nt, PREPROCESS))
-            exit()
-        if SHUFFLE and (nt * H * W * 3) % 8:
-            print("ERROR: --shuffle needs nt*H*W*3 to be a multiple of 8 (%d x %d x %d x 3 is not)." % (nt, H, W))
-            exit()
-        # the job is accepted: only now does the output directory receive its first file (compress.py:133-136
-        # writes it after the images are loaded; a rejected job must not leave a partial directory behind)
-        with open(os.path.join(OUTPUT_DIR, 'filename.txt'), 'w', encoding='UTF-8') as f:
-            f.write(f"{int(src.is_rgb)}\n")
-            for file_name in src.files:
-                f.write("%s\n" % file_name)
+        hp, wp = _accept_job(src, model_shape, PREPROCESS, SHUFFLE, OUTPUT_DIR)
         nwin = 1 if WINDOW_SIZE is None else max(1, (nt - PREPROCESS + WINDOW_SIZE - 1) // WINDOW_SIZE)
         ctx = make_context(cfg, wts, hp, wp, min(nwin, 64), device)
         stages.mark("context + model prepare")
@@ -423,25 +432,9 @@ def _run_sharded(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THR
     if rank0 and not os.path.exists(OUTPUT_DIR):
         os.mkdir(OUTPUT_DIR)
     src = FrameSource(DATA_DIR)          # lists, probes the first image (mode, size): same messages as load_images
-    nt, H, W, files, isRGB = src.nt, src.H, src.W, src.files, src.is_rgb
+    nt, H, W = src.nt, src.H, src.W
     cfg, wts, model_shape = open_model(WEIGHTS_DIR)
-    hp, wp = padding_shape(H, W)
-    if model_shape is not None and (model_shape[0] != hp or model_shape[1] != wp):
-        print("ERROR:Image size is out of scope for this model.")
-        print("Compatible sizes for this model are height", model_shape[0] - 7, "to", model_shape[0], "and width",
-              model_shape[1] - 7, "to", model_shape[1])
-        exit()
-    if nt < PREPROCESS + 2:
-        print("ERROR: need at least warm_up+2 images (%d given, warm_up %d)." % (nt, PREPROCESS))
-        exit()
-    if SHUFFLE and (nt * H * W * 3) % 8:
-        print("ERROR: --shuffle needs nt*H*W*3 to be a multiple of 8 (%d x %d x %d x 3 is not)." % (nt, H, W))
-        exit()
-    if rank0:
-        with open(os.path.join(OUTPUT_DIR, 'filename.txt'), 'w', encoding='UTF-8') as f:
-            f.write(f"{int(isRGB)}\n")
-            for file_name in files:
-                f.write("%s\n" % file_name)
+    hp, wp = _accept_job(src, model_shape, PREPROCESS, SHUFFLE, OUTPUT_DIR if rank0 else None)
     if WINDOW_SIZE is None:
         if rank0:
             print("NOTE: DWP (-t) finds its windows sequentially and does not shard: running on rank 0 only.")

@@ -1097,8 +1097,7 @@ extern "C" int tz_frames_get(tz_ctx* ctx, int first, int count, uint8_t* out) {
 
 extern "C" int tz_payload_begin(tz_ctx* ctx, size_t count) {
     if (!ctx) return TZ_ERR_INVALID;
-    ctx->enc_pending = false;   // the resident symbols of a tz_encode_begin are about to be overwritten
-    ctx->enc_resident = false;  // and so is the payload of a tz_encode(payload = NULL)
+    ctx->enc_kind = tz_ctx::ENC_NONE;   // whatever the encoder left in d_payload is about to be overwritten
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, std::max<size_t>(count, 8) * 2));
     ctx->payload_len = count;
     TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old payload
@@ -1133,8 +1132,7 @@ extern "C" int tz_rollout(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int
                           double threshold, uint8_t* key_mask, double* mse_log) {
     tz_roctx_range roctx_("tz_rollout");
     if (!ctx) return TZ_ERR_INVALID;
-    ctx->enc_pending = false;   // a tz_encode_begin belongs to the rollout before it
-    ctx->enc_resident = false;  // so does a resident payload
+    ctx->enc_kind = tz_ctx::ENC_NONE;   // the symbols of a tz_encode_begin or a resident payload belong to the rollout before it
     if (window < 0) return tz_fail(ctx, TZ_ERR_INVALID, "window must be >= 0");
     if (nt < warm_up + 2)  // the reference breaks here
         return tz_fail(ctx, TZ_ERR_INVALID, "need at least warm_up+2 frames (nt=%d, warm_up=%d)", nt, warm_up);
@@ -1334,8 +1332,7 @@ static int discover_keys(tz_ctx* ctx, int nt, int H, int W, std::vector<int>* fl
 // decode.  range: tz_rollout_decode_range's refusals -- frames 0..warm_up must be key frames -- ahead of the walk's own.
 static int rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, int first, int count,
                           uint8_t* key_mask, bool range) {
-    ctx->enc_pending = false;
-    ctx->enc_resident = false;
+    ctx->enc_kind = tz_ctx::ENC_NONE;
     // (a range sizes its prediction stack once it knows its restart frame)
     int rc = rollout_setup(ctx, key_frames, nt, H, W, warm_up, nullptr, first == 0 && count == nt ? nt : 1);
     if (rc != TZ_OK) return rc;
@@ -1519,11 +1516,19 @@ static int remap_out(tz_ctx* ctx, const int16_t* d_sd, size_t N, const int16_t* 
     return TZ_OK;
 }
 
-// compress.py:292-355 on the context-resident rollout: delta, quantiser, spatial delta over the whole
-// flattened stack (no carry), 1600 offset + bincount when `entropy`.  d_sym receives the symbols (or
-// the raw spatial delta), d_hist the counters (zeroed here), d_edge[0..1] the first and the last
-// element of the quantised delta stack (what a shard boundary needs).  d_delta_tap
-// (may be NULL): the quantised delta stack is also wanted there.
+// What every encode entry checks before it touches a buffer (a NaN bound is refused by the quantiser's own launches).
+static int encode_check(tz_ctx* ctx, const char* who, int mode) {
+    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "%s needs a tz_rollout first", who);
+    TZ_TRY(tz_check_pred_contract(ctx, who));
+    if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
+    return TZ_OK;
+}
+
+// compress.py:292-355 on the context-resident rollout: delta, quantiser, spatial delta over the whole flattened stack
+// (no carry), 1600 offset + bincount when `entropy`.  d_sym receives the symbols (or the raw spatial delta), d_hist the
+// counters (zeroed here), d_edge[0..1] the first and the last element of the quantised delta stack (what a shard
+// boundary needs).  d_delta_tap (may be NULL): the quantised delta stack is also wanted there.  d_sym
+// NULL: stop after the quantiser (compress.py:292-319), the delta stack in d_delta_tap is all that is wanted.
 static int encode_front(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* d_delta_tap, int16_t* d_sym,
                         unsigned long long* d_hist, int16_t* d_edge) {
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
@@ -1554,6 +1559,7 @@ static int encode_front(tz_ctx* ctx, int mode, double b0, double b1, int entropy
     TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta));
     // compress.py:315-319
     TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_delta, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
+    if (!d_sym) return TZ_OK;
     // compress.py:339-355
     TZ_TRY(tzk_spatial_delta(ctx, (const int16_t*)d_delta, N, 0, 0, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr));
     TZ_HIP(ctx, hipMemcpyAsync(d_edge, d_delta, 2, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1561,28 +1567,50 @@ static int encode_front(tz_ctx* ctx, int mode, double b0, double b1, int entropy
     return TZ_OK;
 }
 
+// compress.py:356-373 from the N symbols of encode_front to the payload `o`, which joins `outs` to leave.  carry (may be
+// NULL): the previous shard's last delta element, with which the first symbol of a tz_encode_begin is made again.  lut
+// (NULL: none): the rank remap, by remap_out (in place when o is d_sym itself); else the symbols are copied unless
+// they are already in o.  o_shuffled (may be NULL): the payload leaves from there, as the byte planes of o.
+static int encode_tail(tz_ctx* ctx, int16_t* d_sym, size_t N, const int16_t* carry, const int16_t* lut, tz_out* o,
+                       tz_out* o_shuffled, bool defer, std::vector<tz_out>& outs) {
+    if (carry) {   // sd = carry - x[0] instead of x[0] (compress.py:73-77 across the boundary)
+        const int16_t sd = (int16_t)(*carry - ctx->enc_first);
+        const int16_t y = ctx->enc_entropy ? (int16_t)(TZ_OFFSET - sd) : sd;
+        TZ_TRY(tz_upload(ctx, d_sym, &y, 2));
+    }
+    if (lut) {
+        TZ_TRY(remap_out(ctx, d_sym, N, lut, o, defer));  // compress.py:369
+    } else if (o->dev != d_sym) {
+        hipError_t e = hipMemcpyAsync(o->dev, d_sym, N * 2, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "payload copy: %s", hipGetErrorString(e));
+    }
+    if (o_shuffled) {
+        TZ_TRY(tzk_shuffle(ctx, (const int16_t*)o->dev, N, (uint8_t*)o_shuffled->dev, 0));
+        o = o_shuffled;
+    }
+    outs.push_back(*o);
+    return tz_dev_out_finish(ctx, outs);
+}
+
 extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* payload, int16_t* table,
                          int* table_len, int16_t* delta_out) {
     tz_roctx_range roctx_("tz_encode");
     if (!ctx || !table_len || ((entropy & 1) && !table)) return TZ_ERR_INVALID;
-    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode needs a tz_rollout first");
-    TZ_TRY(tz_check_pred_contract(ctx, "tz_encode"));
-    ctx->enc_pending = false;
-    ctx->enc_resident = false;
-    const bool to_resident = payload == nullptr;
-    if (!payload) {  // keep the payload in the context: it leaves through tz_payload_get
-        const size_t n = (size_t)ctx->nt * ctx->H * ctx->W * 3;
-        TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, n * 2));
-        ctx->payload_len = n;
-        payload = ctx->d_payload;
-    }
-    if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
+    TZ_TRY(encode_check(ctx, "tz_encode", mode));
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
     const bool shuffle = (entropy & 2) != 0;  // opt-in byte planes (not a reference format)
     entropy &= 1;
     if (shuffle && (N & 7)) return tz_fail(ctx, TZ_ERR_INVALID, "byte shuffle needs a multiple of 8 elements");
+    ctx->enc_kind = tz_ctx::ENC_NONE;
+    const bool to_resident = payload == nullptr;
+    if (to_resident) {  // keep the payload in the context: it leaves through tz_payload_get
+        TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, N * 2));
+        ctx->payload_len = N;
+        payload = ctx->d_payload;
+    }
     std::vector<tz_out> outs;
-    tz_out o_pay, o_delta, o_final;
+    tz_out o_pay, o_plain{nullptr, nullptr, N * 2}, o_delta;
+    tz_out* o = shuffle ? &o_plain : &o_pay;   // where the plain payload goes (scratch when it is shuffled into o_pay)
     void *d_hist = nullptr, *d_sd = nullptr, *d_edge = nullptr;
     // a transfer of the call before may still be reading the staging buffer (and writing the caller's previous host
     // buffer): it has ~a rollout's time to finish, and must have before this call's remap writes the buffer again
@@ -1599,18 +1627,11 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
     if (rc == TZ_OK && defer) {
         if (ctx->cap_payload_stage < N * 2) rc = tz_payload_settle(ctx);   // (growing frees the old buffer)
         if (rc == TZ_OK) rc = tz_ensure(ctx, (void**)&ctx->d_payload_stage, &ctx->cap_payload_stage, N * 2);
-        o_pay.bytes = N * 2;
-        o_pay.host = payload;
-        o_pay.dev = ctx->d_payload_stage;
+        o_pay = tz_out{payload, ctx->d_payload_stage, N * 2};
     } else if (rc == TZ_OK) {
         rc = tz_dev_out(ctx, payload, N * 2, &o_pay);
     }
-    if (rc == TZ_OK && shuffle) {  // the stages below write the plain payload to a scratch buffer instead
-        o_final = o_pay;
-        o_pay = tz_out();
-        o_pay.bytes = N * 2;
-        rc = tz_pool_alloc(ctx, N * 2, &o_pay.dev);
-    }
+    if (rc == TZ_OK && shuffle) rc = tz_pool_alloc(ctx, N * 2, &o_plain.dev);
     if (rc == TZ_OK && delta_out) {
         rc = tz_dev_out(ctx, delta_out, N * 2, &o_delta);
         if (rc == TZ_OK) outs.push_back(o_delta);
@@ -1620,9 +1641,11 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
         rc = tz_pool_alloc(ctx, TZ_NBINS * sizeof(unsigned long long), &d_hist);
         if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N * 2, &d_sd);
     }
+    int16_t* d_sym = entropy ? (int16_t*)d_sd : (int16_t*)o->dev;   // without a table the symbols are the payload
     if (rc == TZ_OK)
-        rc = encode_front(ctx, mode, b0, b1, entropy, delta_out ? (int16_t*)o_delta.dev : nullptr,
-                          entropy ? (int16_t*)d_sd : (int16_t*)o_pay.dev, (unsigned long long*)d_hist, (int16_t*)d_edge);
+        rc = encode_front(ctx, mode, b0, b1, entropy, delta_out ? (int16_t*)o_delta.dev : nullptr, d_sym,
+                          (unsigned long long*)d_hist, (int16_t*)d_edge);
+    std::vector<int16_t> lut;
     if (rc == TZ_OK && !entropy) {
         *table_len = -1;
     } else if (rc == TZ_OK) {
@@ -1630,7 +1653,6 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
         hipError_t e = hipMemcpyAsync(hist.data(), d_hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "hist download: %s", hipGetErrorString(e));
-        std::vector<int16_t> lut;
         const auto t0 = std::chrono::steady_clock::now();
         if (rc == TZ_OK) rc = tz_build_table(hist.data(), TZ_NBINS, table, table_len);  // 356-361
         if (rc == TZ_OK) rc = build_enc_lut(ctx, table, *table_len, &lut);
@@ -1638,34 +1660,25 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
             ctx->prof[TZP_TABLE].total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             ctx->prof[TZP_TABLE].launches += 1;
         }
-        if (rc == TZ_OK) rc = remap_out(ctx, (const int16_t*)d_sd, N, lut.data(), &o_pay, defer);  // 369
     }
-    if (rc == TZ_OK && shuffle) {
-        rc = tzk_shuffle(ctx, (const int16_t*)o_pay.dev, N, (uint8_t*)o_final.dev, 0);
-        o_pay = o_final;
-    }
-    outs.push_back(o_pay);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && to_resident) ctx->enc_resident = true;   // (tz_encode_quality's payload == NULL)
+    if (rc == TZ_OK)
+        rc = encode_tail(ctx, d_sym, N, nullptr, entropy ? lut.data() : nullptr, o, shuffle ? &o_pay : nullptr, defer, outs);
+    if (rc == TZ_OK && to_resident) ctx->enc_kind = tz_ctx::ENC_PAYLOAD;   // (tz_encode_quality's payload == NULL)
     tz_pool_release_all(ctx);
     return rc;
 }
 
-// ---- tz_encode in two phases, for jobs whose frame windows are sharded over GPUs.
-// The spatial delta runs over the WHOLE flattened stack (compress.py:339) and the rank table comes
-// from the GLOBAL histogram (compress.py:354-361): a shard therefore runs everything up to its own
-// symbols and counters (begin), the ranks exchange one carry element and sum 2111 counters, and
-// the shard finishes with the global table (finish).  Same kernels as tz_encode; the symbols stay in
-// the context's resident payload buffer between the two calls and are remapped in place.
+// ---- tz_encode in two phases, for jobs whose frame windows are sharded over GPUs.  The spatial delta
+// runs over the WHOLE flattened stack (compress.py:339) and the rank table comes from the GLOBAL histogram
+// (compress.py:354-361): a shard runs encode_front into the context's resident payload buffer (begin), the ranks exchange
+// one carry element and sum 2111 counters, and the shard runs encode_tail with the global table (finish).  tz_encode is
+// the one-shard case.
 extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int entropy, unsigned long long* hist,
                                int16_t* edge) {
     tz_roctx_range roctx_("tz_encode_begin");
     if (!ctx || !edge || (entropy && !hist)) return TZ_ERR_INVALID;
-    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_begin needs a tz_rollout first");
-    TZ_TRY(tz_check_pred_contract(ctx, "tz_encode_begin"));
-    if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
-    ctx->enc_pending = false;
-    ctx->enc_resident = false;   // d_payload now receives a shard's symbols
+    TZ_TRY(encode_check(ctx, "tz_encode_begin", mode));
+    ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload now receives a shard's symbols
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, N * 2));
     ctx->payload_len = N;
@@ -1682,7 +1695,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
         if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "tz_encode_begin: %s", hipGetErrorString(e));
     }
     if (rc == TZ_OK) {
-        ctx->enc_pending = true;
+        ctx->enc_kind = tz_ctx::ENC_SYMBOLS;
         ctx->enc_entropy = entropy != 0;
         ctx->enc_first = edge[0];
     }
@@ -1694,36 +1707,23 @@ extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const
                                 int16_t* payload) {
     tz_roctx_range roctx_("tz_encode_finish");
     if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->enc_pending) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish needs a tz_encode_begin first");
+    if (ctx->enc_kind != tz_ctx::ENC_SYMBOLS) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish needs a tz_encode_begin first");
     if (ctx->enc_entropy != (table_len >= 0) || (table_len > 0 && !table) || table_len > TZ_MAX_TABLE)
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode_finish: table does not match the entropy flag of tz_encode_begin");
     const size_t N = ctx->payload_len;
     if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE) || N != (size_t)ctx->nt * ctx->H * ctx->W * 3) {
-        ctx->enc_pending = false;
+        ctx->enc_kind = tz_ctx::ENC_NONE;
         return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish: the resident symbols (%zu) are not those of the current rollout", N);
     }
-    int rc = TZ_OK;
-    if (has_carry) {
-        // the first element of the shard: sd = carry - x[0] instead of x[0] (compress.py:73-77 across the boundary)
-        const int16_t sd = (int16_t)(carry - ctx->enc_first);
-        const int16_t y = ctx->enc_entropy ? (int16_t)(TZ_OFFSET - sd) : sd;
-        rc = tz_upload(ctx, ctx->d_payload, &y, 2);
-    }
+    std::vector<int16_t> lut;
     std::vector<tz_out> outs;
-    tz_out o;
+    tz_out o{nullptr, ctx->d_payload};   // payload NULL: the symbols become the payload in place and stay resident
+    int rc = ctx->enc_entropy ? build_enc_lut(ctx, table, table_len, &lut) : TZ_OK;
     if (rc == TZ_OK && payload) rc = tz_dev_out(ctx, payload, N * 2, &o);
-    if (rc == TZ_OK && ctx->enc_entropy) {
-        std::vector<int16_t> lut;
-        rc = build_enc_lut(ctx, table, table_len, &lut);
-        if (rc == TZ_OK && payload) rc = remap_out(ctx, ctx->d_payload, N, lut.data(), &o);                 // compress.py:369
-        else if (rc == TZ_OK) rc = tzk_lut(ctx, ctx->d_payload, N, lut.data(), 0, ctx->d_payload);           // in place: stays resident
-    } else if (rc == TZ_OK && payload) {
-        hipError_t e = hipMemcpyAsync(o.dev, ctx->d_payload, N * 2, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "payload copy: %s", hipGetErrorString(e));
-    }
-    if (payload) outs.push_back(o);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) ctx->enc_pending = false;
+    if (rc == TZ_OK)
+        rc = encode_tail(ctx, ctx->d_payload, N, has_carry ? &carry : nullptr, ctx->enc_entropy ? lut.data() : nullptr, &o,
+                         nullptr, false, outs);
+    if (rc == TZ_OK) ctx->enc_kind = tz_ctx::ENC_NONE;
     tz_pool_release_all(ctx);
     return rc;
 }
@@ -1764,19 +1764,13 @@ extern "C" int tz_byte_unshuffle(tz_ctx* ctx, const uint8_t* in, size_t n, int16
 
 extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int16_t* delta_out) {
     if (!ctx || !delta_out) return TZ_ERR_INVALID;
-    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_delta needs a tz_rollout first");
-    TZ_TRY(tz_check_pred_contract(ctx, "tz_encode_delta"));
-    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
-    const size_t N = (size_t)nt * H * W * 3;
+    TZ_TRY(encode_check(ctx, "tz_encode_delta", mode));
+    const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
     std::vector<tz_out> outs;
     tz_out o;
-    void* d_mask = nullptr;
     int rc = tz_dev_out(ctx, delta_out, N * 2, &o);
     if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_mask);
-    if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, ctx->group_first.data(), nt);
-    if (rc == TZ_OK) rc = tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)o.dev);
-    if (rc == TZ_OK) rc = tzk_error_bound(ctx, ctx->d_frames, (int16_t*)o.dev, ctx->quant_skip.data(), nt, H, W, mode, b0, b1);
+    if (rc == TZ_OK) rc = encode_front(ctx, mode, b0, b1, 0, (int16_t*)o.dev, nullptr, nullptr, nullptr);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     tz_pool_release_all(ctx);
     return rc;
@@ -1928,7 +1922,7 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
     const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe;
     if (!payload) {
-        if (!ctx->enc_resident || !ctx->d_payload || ctx->payload_len != N)
+        if (ctx->enc_kind != tz_ctx::ENC_PAYLOAD || !ctx->d_payload || ctx->payload_len != N)
             return tz_fail(ctx, TZ_ERR_STATE, "no resident payload of a tz_encode on this rollout");
         payload = ctx->d_payload;
     }

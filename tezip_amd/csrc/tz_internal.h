@@ -110,7 +110,11 @@ struct tz_ctx {
     bool staged = false;                    // d_frames was filled by tz_frames_begin / tz_frames_put
     int16_t* d_payload = nullptr;           // resident payload of a tz_encode(payload = NULL)
     size_t cap_payload = 0, payload_len = 0;
-    bool enc_resident = false;              // d_payload holds what tz_encode(payload = NULL) wrote on the current rollout
+    // what d_payload holds for the encoder on the current rollout: nothing, the symbols of a tz_encode_begin (before
+    // the carry and the remap of tz_encode_finish) or the payload of a tz_encode(payload = NULL)
+    enum tz_enc_kind { ENC_NONE = 0, ENC_SYMBOLS, ENC_PAYLOAD } enc_kind = ENC_NONE;
+    bool enc_entropy = false;               // ENC_SYMBOLS: they are 1600 - sd (tz_encode_begin's entropy flag)
+    int16_t enc_first = 0;                  // ENC_SYMBOLS: first element of the shard's quantised delta stack
     unsigned* d_scan_status = nullptr;      // inverse scan: one word per resident block, tagged with the launch's epoch
     unsigned scan_epoch = 0;
     unsigned scan_dbg_skew = 0, scan_dbg_limit = 0;   // tz_scan_fault_inject: poll for another epoch / give up sooner
@@ -123,8 +127,6 @@ struct tz_ctx {
     size_t cap_out = 0;
     bool have_decoded = false;
     int dec_first = 0, dec_count = 0;       // frames of the sequence that d_out holds (tz_decode: all, tz_decode_range: its range)
-    bool enc_pending = false, enc_entropy = false;  // tz_encode_begin done, symbols resident in d_payload
-    int16_t enc_first = 0;                          // first element of the shard's quantised delta stack
     const uint8_t* pending_src = nullptr;  // host frame stack whose non-key frames are still to be sent
     std::vector<uint8_t> pending_sent;     // nt: 1 = already on its way
     std::vector<hipEvent_t> chunk_ev;  // payload chunk hand-over events (compute -> copy stream)

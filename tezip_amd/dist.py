@@ -12,11 +12,11 @@ windows with NO data-path collective.  Only three things cross shard boundaries
   3. rank 0 receives the payload shards point to point, straight into their place in the
      full payload buffer (peers `send`, rank 0 `irecv`s into slices: nothing lands on a rank
      that does not use it).
-A rank runs the SAME fused kernels as a single GPU does (round 3): tz_rollout, then tz_encode_begin
-(delta, quantiser, spatial delta without a carry, histogram -- the symbols stay in its HBM), the two
-small collectives, then tz_encode_finish (patches the shard's first symbol for the carry, remaps
-with the global table).  Until round 2 a rank went through the unfused stand-alone operators with a
-host round trip for the carry.
+A rank runs the SAME code as a single GPU does (round 3; tz_encode is the one-shard case): tz_rollout,
+then tz_encode_begin (delta, quantiser, spatial delta without a carry, histogram -- the symbols stay
+in its HBM), the two small collectives, then tz_encode_finish (patches the shard's first symbol for
+the carry, remaps with the global table).  Until round 2 a rank went through the unfused stand-alone
+operators with a host round trip for the carry.
 The decoder shards the same way; its inverse scan needs the prefix of per-shard sums.
 
 Failure handling: every compute stage that sits in front of a collective reports its outcome THROUGH
