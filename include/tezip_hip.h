@@ -335,6 +335,40 @@ int tz_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key_frames, co
  * (x/255 - pred)^2 in float64, fixed summation order). sse: nframes doubles (host). */
 int tz_window_sse(tz_ctx* ctx, const uint8_t* orig, const float* pred, int nframes, int H, int W, double* sse);
 
+/* ---- opt-in Huffman coder of the payload (no reference counterpart: compress.py:375-400 hands the int16 payload to zstd;
+ * `tezip.py -c --coder huff`, format in DESIGN.md section 9, slow statement of it in tezip_amd/huff.py) ---------------------
+ * An order-0 canonical Huffman code over the payload's 16-bit values: symbol = value - base, alphabet A <= TZ_NBINS, code
+ * lengths <= 12, codes canonical (shorter first, then by symbol), so `lengths` (A bytes, 0 = absent) is the whole code.
+ * The coded stream is index | bits: one u32 word offset per chunk (64 runs), one u16 size in bits per run (256 symbols),
+ * padded to 4 bytes, then the 32-bit words of the bit stream.
+ * tz_huff_lengths (host only, like tz_build_table): optimal lengths under the limit max_len (package-merge) from A counts;
+ * deterministic, Kraft sum exactly 1 with two or more symbols present, one present symbol gets length 1, zero counts get 0.
+ * TZ_ERR_INVALID: no symbol present, more than 2^max_len present, A outside [1, TZ_NBINS], max_len outside [1, 15]. */
+int tz_huff_lengths(const unsigned long long* counts, int A, int max_len, uint8_t* lengths);
+/* Counts of the context-resident payload (tz_encode / tz_encode_finish with payload == NULL) in symbol order:
+ * counts[TZ_NBINS] (host) receives them, *base the smallest value present, *A the span up to the largest.  One read of the
+ * payload (k_huff_count).  TZ_ERR_INVALID when the values span more than TZ_NBINS symbols. */
+int tz_huff_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base);
+/* Codes the context-resident payload into a context-resident stream; *bytes receives its size, tz_huff_get fetches it in
+ * pieces like tz_payload_get.  The payload stays as it is.  TZ_ERR_INVALID before any launch for a bad code (A, base, a
+ * length above 12, Kraft sum > 1), and after the size pass for a payload value the code has no symbol for. */
+int tz_huff_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes);
+int tz_huff_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out);
+/* Decoder: stage a coded stream of `bytes` bytes for n elements in pieces on the copy stream (begin, then put for any
+ * partition of [0, bytes)), then expand it into the context's payload buffer exactly as if tz_payload_begin /
+ * tz_payload_put had staged n elements: tz_decode (payload == NULL), tz_decode_range, tz_undelta_carry run unchanged on it.
+ * R must be 256.  The caller validates the index (tezip_amd/huff.py: parse); the kernel itself clamps every offset and read
+ * to the stream, so a corrupt body gives wrong symbols, never an access outside the buffers. */
+int tz_huff_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R);
+int tz_huff_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src);
+int tz_huff_decode(tz_ctx* ctx);
+/* Stand-alone forms on host or device arrays (they use, and overwrite, the context's resident stream buffer).
+ * capacity: bytes `out` holds; a larger stream is TZ_ERR_INVALID with *bytes set to what it needs. */
+int tz_huff_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
+                       size_t capacity, size_t* bytes);
+int tz_huff_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base,
+                       int R, int16_t* out);
+
 /* ---- timing helper: HIP events on the context's stream (bench.py) -------------------------- */
 int tz_timer_start(tz_ctx* ctx);
 int tz_timer_stop(tz_ctx* ctx, float* ms);

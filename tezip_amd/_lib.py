@@ -87,6 +87,17 @@ _SIGS = {
     "tz_reconstruct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                  C.c_void_p]),
     "tz_window_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_huff_lengths": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "tz_huff_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tz_huff_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "tz_huff_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_huff_begin": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "tz_huff_put": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_huff_decode": (C.c_int, [C.c_void_p]),
+    "tz_huff_encode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                     C.POINTER(C.c_size_t)]),
+    "tz_huff_decode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p]),
     "tz_timer_start": (C.c_int, [C.c_void_p]),
     "tz_timer_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "tz_prof_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -607,6 +618,56 @@ class Context:
         tb = None if table is None else np.ascontiguousarray(table, np.int16)
         self._ck(self.lib.tz_encode_quality(self.h, None if resident else _ptr(payload), n, _ptr(tb), tl, int(bool(shuffle)),
                                             out.ctypes.data))
+        return out
+
+    # ---- opt-in Huffman coder (tz_huff_*; format: tezip_amd/huff.py)
+    def huff_counts(self):
+        """Counts of the resident payload -> (uint64[A], base): counts[s] of the value s + base."""
+        counts = np.zeros(TZ_NBINS, np.uint64)
+        a, base = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.tz_huff_counts(self.h, counts.ctypes.data, C.byref(a), C.byref(base)))
+        return counts[: a.value].copy(), base.value
+
+    def huff_encode(self, lengths, base):
+        """Code the resident payload into the resident stream (index | bits); returns its size in bytes."""
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        nbytes = C.c_size_t(0)
+        self._ck(self.lib.tz_huff_encode(self.h, ln.ctypes.data, int(ln.size), int(base), C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def huff_get(self, offset, count, out=None):
+        if out is None:
+            out = np.empty(count, np.uint8)
+        self._ck(self.lib.tz_huff_get(self.h, int(offset), int(count), _ptr(out, np.uint8)))
+        return out
+
+    def huff_begin(self, nbytes, n, lengths, base, run=256):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        self._ck(self.lib.tz_huff_begin(self.h, int(nbytes), int(n), ln.ctypes.data, int(ln.size), int(base), int(run)))
+
+    def huff_put(self, offset, piece):
+        self._ck(self.lib.tz_huff_put(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
+
+    def huff_decode(self):
+        self._ck(self.lib.tz_huff_decode(self.h))
+
+    def huff_encode_buf(self, x, lengths, base, out=None):
+        """Stand-alone: int16 values (host or device) -> the coded stream (index | bits) as a uint8 array."""
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        n = _numel(x)
+        if out is None:   # the most a stream can need: 12 bits per symbol, a pad word per chunk, the index
+            out = np.empty(n * 3 // 2 + (n // 16384 + 1) * 8 + (n // 256 + 1) * 2 + 64, np.uint8)
+        nbytes = C.c_size_t(0)
+        self._ck(self.lib.tz_huff_encode_buf(self.h, _ptr(x), n, ln.ctypes.data, int(ln.size), int(base), _ptr(out), _numel(out),
+                                             C.byref(nbytes)))
+        return out[: nbytes.value]
+
+    def huff_decode_buf(self, stream, n, lengths, base, run=256, out=None):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        if out is None:
+            out = np.empty(n, np.int16)
+        self._ck(self.lib.tz_huff_decode_buf(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size), int(base),
+                                             int(run), _ptr(out)))
         return out
 
     # ---- operator seams

@@ -7,6 +7,8 @@ Output directory:
   key_frame.dat  zstd-9 of uint8[nt*H*W*3], zero except key frames           (compress.py:271-278)
   entropy.dat    zstd-9 of int16: payload | table | T  (or | -1) | 1,nt,H,W,3 | warm_up
                                                                               (compress.py:381-400)
+                 with CODER="huff" (--coder huff; not a reference format): "TZH1" header | that trailer | code lengths |
+                 index | bit stream, written by the GPU (tezip_amd/huff.py)
 """
 import glob
 import os
@@ -16,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, quality, sidecar, weights, zstd
+from . import _lib, huff, quality, sidecar, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -224,7 +226,42 @@ class _Stages:
             self.last = now
 
 
-def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None):
+CODERS = ("zstd", "huff")
+HUFF_PIECE = 16 << 20   # bytes of the coded stream fetched and written at a time
+
+
+def check_coder(coder, shuffle=False, sharded=False):
+    """The refusals of --coder, for tezip.py and for a direct caller of run(): None, or the message."""
+    if coder not in CODERS:
+        return "--coder takes one of %s, got %r" % (", ".join(CODERS), coder)
+    if coder == "huff" and shuffle:
+        return "--coder huff cannot be combined with --shuffle (byte planes help zstd; a symbol coder codes whole symbols)"
+    if coder == "huff" and sharded:
+        return "--coder huff is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+    return None
+
+
+def _huff_entropy_file(ctx, path, n, trailer, verbose):
+    """entropy.dat of CODER="huff": the resident payload is coded on the device (tz_huff_encode) and only the coded
+    stream crosses to the host; the header, the reference trailer and the code lengths go in front of it."""
+    t0 = time.perf_counter()
+    counts, base = ctx.huff_counts()
+    lengths = huff.code_lengths(counts)
+    nbytes = ctx.huff_encode(lengths, base)
+    nruns, nchunks = huff.geometry(n)
+    front = huff.pack_front(trailer, lengths, base, n, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4)
+    bufs = [np.empty(min(HUFF_PIECE, nbytes), np.uint8) for _ in range(2)]
+    with open(path, mode='wb') as f:
+        f.write(front)
+        for k, off in enumerate(range(0, nbytes, HUFF_PIECE)):
+            cnt = min(HUFF_PIECE, nbytes - off)
+            f.write(ctx.huff_get(off, cnt, out=bufs[k % 2][:cnt]))
+    if verbose:
+        print("huffman_coding:{0}".format(time.perf_counter() - t0) + "[sec]")
+    return len(front) + nbytes
+
+
+def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False):
     """key_frame.dat and entropy.dat (compress.py:271-278, 375-400) from the context-resident frames
     and payload, piece by piece: nothing of size nt*H*W lives on the host."""
     n = nt * H * W * 3
@@ -266,8 +303,13 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
     else:
         tail = np.array([-1], dtype=np.int64)
     trailer = np.concatenate([tail, [SHUFFLE_MARK if shuffled else 1, nt, H, W, 3], [warm_up]]).astype(np.int16)
-    bufs = [np.empty(min(PAYLOAD_CHUNK, n), np.int16) for _ in range(2)]
     t_e = time.perf_counter()
+    if coder == "huff":
+        esize = _huff_entropy_file(ctx, os.path.join(out_dir, "entropy.dat"), n, trailer, verbose)
+        if stages:
+            stages.add("huffman coding + fetch entropy.dat", time.perf_counter() - t_e)
+        return kf.result(), esize
+    bufs = [np.empty(min(PAYLOAD_CHUNK, n), np.int16) for _ in range(2)]
     with open(os.path.join(out_dir, "entropy.dat"), mode='wb') as f:
         sc = zstd.StreamCompressor(f, n * 2 + trailer.nbytes, 9, zstd.default_threads())
         for k, off in enumerate(range(0, n, PAYLOAD_CHUNK)):
@@ -308,12 +350,15 @@ def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
 
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
-        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False):
+        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd"):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
     bound introduced, from the stored payload decoded on the device (tz_encode_quality) -- and print the worst error,
     the PSNR and the compression ratio.  Single-GPU jobs only.
+    CODER (--coder; NOT in the reference): "zstd" writes the reference's entropy.dat; "huff" has the GPU Huffman-code the
+    payload (tezip_amd/huff.py) -- such a file is not readable by the reference; `-u` recognises it by its magic.
+    Single-GPU jobs only, not with SHUFFLE.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -322,12 +367,16 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if not GPU_FLAG:
         print("ERROR: this build runs the compression path on an AMD MI355X only (no CPU path).")
         exit()
+    problem = check_coder(CODER, SHUFFLE, tzdist.active() is not None)
+    if problem:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
+        print("ERROR:", problem)
+        sys.exit(2)
     if tzdist.active() is not None:
         if REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
             print("ERROR: --report is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU")
             sys.exit(2)
         return _run_sharded(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE,
-                            VERBOSE, ENTROPY_RUN, device, SHUFFLE)
+                            VERBOSE, ENTROPY_RUN, device, SHUFFLE, CODER)
     if not os.path.exists(OUTPUT_DIR):
         os.mkdir(OUTPUT_DIR)
     stages = _Stages()
@@ -379,7 +428,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     # the spatial-delta kernel here (timed above), what is left is the host-side sort
                     print("table_create:{0}".format(prof["table_create"][0] / 1e3) + "[sec]")
                     print("replacing_based_on_frequency:{0}".format(prof["lut_remap"][0] / 1e3) + "[sec]")
-            _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages)
+            _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
+                            coder=CODER, verbose=VERBOSE)
             doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS))   # the contract the predictions were made under
             if VERBOSE:
                 print("arithmetic contract:", doc["arithmetic_contract"])
@@ -422,11 +472,15 @@ def pack_outputs_from_keys(nt, H, W, key, key_frames, payload, table, warm_up, s
 
 
 def _run_sharded(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, VERBOSE,
-                 ENTROPY_RUN, device, SHUFFLE):
+                 ENTROPY_RUN, device, SHUFFLE, CODER="zstd"):
     """Under torch.distributed.run.  SWP: the windows are sharded over the ranks and so is the image I/O -- every rank
     lists the directory (names only) and decodes the files of ITS frame range, nothing else (compress.py:97-122 decodes
     every file in one loop); rank 0 additionally reads the few key frames key_frame.dat needs and writes the files.
     DWP does not shard (its windows are found sequentially): rank 0 runs it alone."""
+    problem = check_coder(CODER, SHUFFLE, sharded=True)
+    if problem:
+        print("ERROR:", problem)
+        sys.exit(2)
     job = tzdist.active()
     rank0 = job[0] == 0
     if rank0 and not os.path.exists(OUTPUT_DIR):

@@ -218,6 +218,7 @@ extern "C" int tz_ctx_destroy(tz_ctx* ctx) {
     if (ctx->d_payload_stage) (void)hipFree(ctx->d_payload_stage);
     if (ctx->ev_payload) (void)hipEventDestroy(ctx->ev_payload);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
+    if (ctx->d_huff) (void)hipFree(ctx->d_huff);
     if (ctx->d_scan_status) (void)hipFree(ctx->d_scan_status);
     if (ctx->h_fault) (void)hipHostFree((void*)ctx->h_fault);
     for (auto& s : ctx->prof)
@@ -535,7 +536,7 @@ static const char* kProfNames[TZP_COUNT] = {"conv3x3_mfma", "err0", "delta", "qu
                                             "lut_remap", "undelta_scan", "reconstruct", "sse",
                                             "conv16_lds_dma", "conv16b_level0", "conv_small_valu", "conv3x3_general",
                                             "convlat_small_grid", "wino_pa2", "table_create", "quant_serial_chains",
-                                            "undelta_carry", "quality"};
+                                            "undelta_carry", "quality", "huffman"};
 
 namespace {
 struct RoctxApi {
@@ -2115,6 +2116,290 @@ extern "C" int tz_window_sse(tz_ctx* ctx, const uint8_t* orig, const float* pred
     int rc = tz_dev_in(ctx, orig, (size_t)nframes * H * W * 3, &dor);
     if (rc == TZ_OK) rc = tz_dev_in(ctx, pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp);
     if (rc == TZ_OK) rc = tzk_sse(ctx, (const uint8_t*)dor, (const float*)dp, nframes, H, W, Hp, Wp, sse);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// --------------------------------------------------------------------------- Huffman coder
+// Opt-in entropy coder of the payload (`--coder huff`; NOT a reference feature: compress.py:375-400 hands the int16 payload
+// to zstd).  Format and geometry: DESIGN.md section 9; kernels: tz_codec.hip.
+//
+// tz_huff_lengths: optimal code lengths under the limit max_len by PACKAGE-MERGE (Larmore & Hirschberg 1990), the plain
+// list form: level j holds the leaves merged by weight with the pairs ("packages") of level j - 1; the first 2m - 2 items
+// of the last level are taken, a taken package takes its two items one level down, and a symbol's length is the number of
+// levels on which its leaf is taken.  Leaves are merged in ascending (count, then descending symbol) order and a leaf goes
+// before a package of equal weight, so the result is a function of the counts alone, the taken leaves of a level are a
+// prefix of that order (lengths never increase with the count), and the code is complete (Kraft sum exactly 1).
+extern "C" int tz_huff_lengths(const unsigned long long* counts, int A, int max_len, uint8_t* lengths) {
+    if (!counts || !lengths || A < 1 || A > TZ_NBINS || max_len < 1 || max_len > 15) return TZ_ERR_INVALID;
+    std::vector<int> sym;
+    unsigned long long total = 0;
+    for (int s = 0; s < A; ++s) {
+        lengths[s] = 0;
+        if (!counts[s]) continue;
+        if (counts[s] >= (1ull << 58) || total + counts[s] >= (1ull << 58)) return TZ_ERR_INVALID;   // (weights are summed over <= 15 levels)
+        total += counts[s];
+        sym.push_back(s);
+    }
+    const size_t m = sym.size();
+    if (m == 0 || m > ((size_t)1 << max_len)) return TZ_ERR_INVALID;
+    if (m == 1) {
+        lengths[sym[0]] = 1;
+        return TZ_OK;
+    }
+    std::sort(sym.begin(), sym.end(), [&](int a, int b) { return counts[a] != counts[b] ? counts[a] < counts[b] : a > b; });
+    std::vector<std::vector<unsigned long long>> w(max_len);
+    std::vector<std::vector<uint8_t>> leaf(max_len);
+    for (int j = 0; j < max_len; ++j) {
+        const size_t npk = j ? w[j - 1].size() / 2 : 0;
+        size_t a = 0, b = 0;
+        while (a < m || b < npk) {
+            const unsigned long long wp = b < npk ? w[j - 1][2 * b] + w[j - 1][2 * b + 1] : 0;
+            if (a < m && (b >= npk || counts[sym[a]] <= wp)) {
+                w[j].push_back(counts[sym[a++]]);
+                leaf[j].push_back(1);
+            } else {
+                w[j].push_back(wp);
+                leaf[j].push_back(0);
+                ++b;
+            }
+        }
+    }
+    size_t take = 2 * m - 2;
+    for (int j = max_len - 1; j >= 0 && take; --j) {
+        if (take > w[j].size()) return TZ_ERR_INVALID;   // (cannot happen for m <= 2^max_len)
+        size_t q = 0;
+        for (size_t i = 0; i < take; ++i) q += leaf[j][i];
+        for (size_t i = 0; i < q; ++i) lengths[sym[i]] += 1;
+        take = 2 * (take - q);
+    }
+    return TZ_OK;
+}
+
+// The two tables of a code given by its lengths (canonical: shorter first, then by symbol; stored bit-reversed):
+// enc[s] = stored code | length << 12 (0: absent), dec[next 12 bits] = symbol | length << 12.  Checks everything a launch
+// depends on: A, base, lengths <= 12, at least one symbol, Kraft sum <= 1.
+static int huff_tables(tz_ctx* ctx, const uint8_t* lengths, int A, int base, std::vector<uint16_t>* enc, std::vector<uint16_t>* dec) {
+    if (!lengths || A < 1 || A > TZ_NBINS) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: alphabet size %d outside [1, %d]", A, TZ_NBINS);
+    if (base < -32768 || base + A - 1 > 32767) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: base %d with %d symbols leaves int16", base, A);
+    unsigned long long kraft = 0;
+    int first = -1;
+    for (int s = 0; s < A; ++s) {
+        if (lengths[s] > TZ_HUFF_L) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: code length %d of symbol %d exceeds %d", lengths[s], s, TZ_HUFF_L);
+        if (lengths[s]) {
+            kraft += 1ull << (TZ_HUFF_L - lengths[s]);
+            if (first < 0) first = s;
+        }
+    }
+    if (first < 0) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: the code lengths name no symbol");
+    if (kraft > (1ull << TZ_HUFF_L)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: Kraft sum of the code lengths exceeds 1");
+    if (enc) enc->assign(A, 0);
+    if (dec) dec->assign((size_t)1 << TZ_HUFF_L, (uint16_t)(first | (1 << 12)));   // unreachable entries: a valid symbol, length 1
+    unsigned code = 0;
+    for (int l = 1; l <= TZ_HUFF_L; ++l) {
+        for (int s = 0; s < A; ++s) {
+            if (lengths[s] != l) continue;
+            unsigned rev = 0;
+            for (int b = 0; b < l; ++b) rev |= ((code >> b) & 1u) << (l - 1 - b);
+            ++code;
+            if (enc) (*enc)[s] = (uint16_t)(rev | (l << 12));
+            if (dec)
+                for (unsigned k = 0; k < (1u << (TZ_HUFF_L - l)); ++k) (*dec)[rev | (k << l)] = (uint16_t)(s | (l << 12));
+        }
+        code <<= 1;
+    }
+    return TZ_OK;
+}
+
+static void huff_geometry(size_t n, size_t* nruns, size_t* nchunks, size_t* index_bytes) {
+    *nruns = (n + TZ_HUFF_RUN - 1) / TZ_HUFF_RUN;
+    *nchunks = (*nruns + TZ_HUFF_CHUNK_RUNS - 1) / TZ_HUFF_CHUNK_RUNS;
+    *index_bytes = *nchunks * 4 + ((*nruns * 2 + 3) & ~(size_t)3);
+}
+
+// d_in (device, n int16) -> ctx->d_huff = index | bits; *bytes its size.  Waits once, for the size of the bit stream.
+static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uint8_t* lengths, int A, int base, size_t* bytes) {
+    if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    std::vector<uint16_t> enc;
+    TZ_TRY(huff_tables(ctx, lengths, A, base, &enc, nullptr));
+    size_t nruns, nchunks, index_bytes;
+    huff_geometry(n, &nruns, &nchunks, &index_bytes);
+    void *d_enc, *d_idx, *d_meta;
+    TZ_TRY(tz_pool_alloc(ctx, (size_t)A * 2, &d_enc));
+    TZ_TRY(tz_pool_alloc(ctx, index_bytes, &d_idx));
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta));
+    TZ_TRY(tz_upload(ctx, d_enc, enc.data(), (size_t)A * 2));
+    TZ_HIP(ctx, hipMemsetAsync(d_idx, 0, index_bytes, ctx->stream));   // (the padding behind an odd number of run sizes is part of the file)
+    unsigned* d_chunk_off = (unsigned*)d_idx;
+    uint16_t* d_run_bits = (uint16_t*)((uint8_t*)d_idx + nchunks * 4);
+    TZ_TRY(tzk_huff_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta));
+    tz_huff_meta meta;
+    TZ_TRY(tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
+    if (meta.bad) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: the payload holds a value the code lengths give no code");
+    if (meta.total_words >= (1ull << 32)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: a bit stream of %llu words does not fit the format", meta.total_words);
+    const size_t total = index_bytes + (size_t)meta.total_words * 4;
+    ctx->huff_n = 0;   // (a staged decoder stream, if any, is gone)
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, total));
+    ctx->huff_bytes = total;
+    TZ_HIP(ctx, hipMemcpyAsync(ctx->d_huff, d_idx, index_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(ctx->d_huff + index_bytes),
+                        (size_t)meta.total_words));
+    *bytes = total;
+    return TZ_OK;
+}
+
+extern "C" int tz_huff_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
+    tz_roctx_range roctx_("tz_huff_counts");
+    if (!ctx || !counts || !A || !base) return TZ_ERR_INVALID;
+    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huff_counts needs a resident payload (tz_encode with payload == NULL)");
+    void *d_hist, *d_meta;
+    std::vector<unsigned long long> h(TZ_HUFF_COUNT_BINS);
+    tz_huff_meta meta;
+    int rc = tz_pool_alloc(ctx, TZ_HUFF_COUNT_BINS * sizeof(unsigned long long), &d_hist);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta);
+    if (rc == TZ_OK) rc = tzk_huff_count(ctx, ctx->d_payload, ctx->payload_len, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
+    if (rc == TZ_OK) rc = tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream);
+    if (rc == TZ_OK) rc = tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    TZ_TRY(rc);
+    int lo = -1, hi = -1;
+    for (int b = 0; b < TZ_HUFF_COUNT_BINS; ++b)
+        if (h[b]) {
+            if (lo < 0) lo = b;
+            hi = b;
+        }
+    if (meta.bad || lo < 0 || hi - lo + 1 > TZ_NBINS)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_huff_counts: the payload's values span more than %d symbols", TZ_NBINS);
+    for (int s = 0; s < TZ_NBINS; ++s) counts[s] = lo + s <= hi ? h[lo + s] : 0;
+    *A = hi - lo + 1;
+    *base = lo - TZ_HUFF_COUNT_BIAS;
+    return TZ_OK;
+}
+
+extern "C" int tz_huff_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes) {
+    tz_roctx_range roctx_("tz_huff_encode");
+    if (!ctx || !bytes) return TZ_ERR_INVALID;
+    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huff_encode needs a resident payload (tz_encode with payload == NULL)");
+    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_huff_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    if (!ctx->d_huff || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the resident Huffman stream");
+    TZ_TRY(tz_d2h(ctx, out, ctx->d_huff + offset, count, ctx->stream));
+    return tz_stream_sync(ctx);
+}
+
+// what a stream of `bytes` bytes must satisfy to be the index | bits of n elements; *stream_words its bit stream
+static int huff_check_stream(tz_ctx* ctx, size_t bytes, size_t n, int R, size_t* stream_words) {
+    if (R != TZ_HUFF_RUN) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: run length %d, this build codes runs of %d", R, TZ_HUFF_RUN);
+    if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    size_t nruns, nchunks, index_bytes;
+    huff_geometry(n, &nruns, &nchunks, &index_bytes);
+    if (bytes < index_bytes || ((bytes - index_bytes) & 3) || (bytes - index_bytes) / 4 >= ((size_t)1 << 32))
+        return tz_fail(ctx, TZ_ERR_INVALID, "huffman: a stream of %zu bytes cannot hold the %zu-byte index of %zu elements and whole words", bytes,
+                       index_bytes, n);
+    *stream_words = (bytes - index_bytes) / 4;
+    return TZ_OK;
+}
+
+extern "C" int tz_huff_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
+    if (!ctx) return TZ_ERR_INVALID;
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
+    std::vector<uint16_t> dec;
+    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec));
+    ctx->huff_n = 0;
+    ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload is about to receive the expanded stream
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, std::max<size_t>(bytes, 16)));
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, std::max<size_t>(n, 8) * 2));
+    ctx->payload_len = 0;
+    ctx->huff_bytes = bytes;
+    ctx->huff_dec_tab.swap(dec);
+    ctx->huff_base = base;
+    ctx->huff_n = n;
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
+    return TZ_OK;
+}
+
+extern "C" int tz_huff_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
+    if (!ctx || !src) return TZ_ERR_INVALID;
+    if (!ctx->d_huff || !ctx->huff_n || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged Huffman stream");
+    return tz_h2d(ctx, ctx->d_huff + offset, src, count, ctx->copy_stream);
+}
+
+static int huff_decode_dev(tz_ctx* ctx, const uint8_t* d_stream, size_t stream_words, size_t n, const std::vector<uint16_t>& dec, int base,
+                           int16_t* d_out) {
+    size_t nruns, nchunks, index_bytes;
+    huff_geometry(n, &nruns, &nchunks, &index_bytes);
+    void* d_dec;
+    TZ_TRY(tz_pool_alloc(ctx, dec.size() * 2, &d_dec));
+    TZ_TRY(tz_upload(ctx, d_dec, dec.data(), dec.size() * 2));
+    return tzk_huff_dec(ctx, (const unsigned*)d_stream, (const uint16_t*)(d_stream + nchunks * 4), (const unsigned*)(d_stream + index_bytes),
+                        stream_words, (const uint16_t*)d_dec, base, n, d_out);
+}
+
+extern "C" int tz_huff_decode(tz_ctx* ctx) {
+    tz_roctx_range roctx_("tz_huff_decode");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (!ctx->huff_n || !ctx->d_huff || !ctx->d_payload || ctx->cap_payload < ctx->huff_n * 2)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_huff_decode needs a stream staged with tz_huff_begin / tz_huff_put");
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, ctx->huff_bytes, ctx->huff_n, TZ_HUFF_RUN, &sw));
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of tz_huff_put
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
+    const int rc = huff_decode_dev(ctx, ctx->d_huff, sw, ctx->huff_n, ctx->huff_dec_tab, ctx->huff_base, ctx->d_payload);
+    if (rc == TZ_OK) ctx->payload_len = ctx->huff_n;   // exactly as if tz_payload_begin / tz_payload_put had staged them
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_huff_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
+                                  size_t capacity, size_t* bytes) {
+    if (!ctx || !in || !out || !bytes) return TZ_ERR_INVALID;
+    const void* din = nullptr;
+    int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes);
+    if (rc == TZ_OK && *bytes > capacity) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: the stream needs %zu bytes, the buffer holds %zu", *bytes, capacity);
+    if (rc == TZ_OK) {
+        if (tz_is_device_ptr(out)) {
+            hipError_t e = hipMemcpyAsync(out, ctx->d_huff, *bytes, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "stream copy: %s", hipGetErrorString(e));
+        } else {
+            rc = tz_d2h(ctx, out, ctx->d_huff, *bytes, ctx->stream);
+        }
+    }
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_huff_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
+                                  int16_t* out) {
+    if (!ctx || !stream || !out) return TZ_ERR_INVALID;
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
+    std::vector<uint16_t> dec;
+    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec));
+    const void* din = nullptr;
+    tz_out o;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, stream, bytes, &din);
+    if (rc == TZ_OK && ((uintptr_t)din & 3)) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: a device stream must be 4-byte aligned");
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
+    if (rc == TZ_OK) {
+        outs.push_back(o);
+        rc = huff_decode_dev(ctx, (const uint8_t*)din, sw, n, dec, base, (int16_t*)o.dev);
+    }
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
     tz_pool_release_all(ctx);
     return rc;
 }

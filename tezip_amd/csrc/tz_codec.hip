@@ -2532,3 +2532,300 @@ int tzk_sse(tz_ctx* ctx, const uint8_t* orig, const float* pred, int nframes, in
     }
     return TZ_OK;
 }
+
+// ---------------------------------------------------------------------------- Huffman coder
+// Opt-in stage that is NOT in the reference (`--coder huff`; format: DESIGN.md section 9, tezip_amd/huff.py is the slow
+// statement of it): an order-0 canonical Huffman code over the 16-bit payload symbols, lengths <= 12.  A RUN is 256
+// consecutive symbols coded back to back by one lane, a CHUNK is 64 runs = one wave and starts on a 32-bit word, so no two
+// waves ever write the same word of global memory.  Codes are stored bit-reversed from the least significant end, so the
+// decoder looks up the next 12 bits of the stream in a 4096-entry table of symbol | length << 12.
+static constexpr int HF_L = TZ_HUFF_L, HF_R = TZ_HUFF_RUN, HF_CR = TZ_HUFF_CHUNK_RUNS;
+static constexpr int HF_CHUNK = HF_R * HF_CR;                  // symbols per chunk
+static constexpr int HF_CHUNK_WORDS = HF_CHUNK * HF_L / 32;    // the most words a chunk can need (6144 = 24 KB of LDS)
+static constexpr int HF_ENC_PAD = (TZ_NBINS + 7) & ~7;
+
+// 8 consecutive payload elements from element e0 (elements at or behind n read as `fill`); VEC: in + e0 is 16-byte aligned
+template <bool VEC>
+__device__ __forceinline__ short8 hf_load8(const int16_t* __restrict__ in, size_t e0, size_t n, short fill) {
+    short8 v;
+    if (VEC && e0 + 8 <= n) return *(const short8*)(in + e0);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = e0 + k < n ? in[e0 + k] : fill;
+    return v;
+}
+
+// exclusive prefix sum over the 64 lanes of a wave; *total = the wave's sum
+__device__ __forceinline__ unsigned hf_wave_excl(unsigned v, unsigned* total) {
+    const int lane = threadIdx.x & 63;
+    unsigned inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    *total = __shfl(inc, 63, 64);
+    return inc - v;
+}
+
+// Counts of the payload values (bin = value + TZ_HUFF_COUNT_BIAS; anything outside the 4096 bins sets meta->bad): the
+// histogram a payload has when no earlier pass left one (a payload without a rank table, a tz_encode_finish).  One read
+// of the payload, 2 B/element; equal neighbours are merged in the thread before they reach the LDS counters.
+__global__ __launch_bounds__(256) void k_huff_count(const int16_t* __restrict__ in, size_t n, unsigned long long* __restrict__ hist,
+                                                    tz_huff_meta* __restrict__ meta) {
+    __shared__ unsigned h[TZ_HUFF_COUNT_BINS];
+    for (int k = threadIdx.x; k < TZ_HUFF_COUNT_BINS; k += 256) h[k] = 0;
+    __syncthreads();
+    const size_t n8 = (n + 7) / 8, stride = (size_t)gridDim.x * 256;
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride) {
+        const short8 v = hf_load8<true>(in, i * 8, n, (short)0);
+        const int valid = (int)std::min((size_t)8, n - i * 8);
+        int prev = v[0], cnt = 1;
+#pragma unroll
+        for (int k = 1; k <= 8; ++k) {
+            const bool more = k < valid;
+            if (more && v[k < 8 ? k : 7] == prev) {
+                ++cnt;
+                continue;
+            }
+            const int b = prev + TZ_HUFF_COUNT_BIAS;
+            if (b >= 0 && b < TZ_HUFF_COUNT_BINS) atomicAdd(&h[b], (unsigned)cnt);
+            else bad = true;
+            if (!more) break;
+            prev = v[k < 8 ? k : 7];
+            cnt = 1;
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < TZ_HUFF_COUNT_BINS; k += 256)
+        if (h[k]) atomicAdd(&hist[k], (unsigned long long)h[k]);
+    if (bad) atomicOr(&meta->bad, 1u);
+}
+
+int tzk_huff_count(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* d_hist, tz_huff_meta* d_meta) {
+    if ((uintptr_t)in & 15) return tz_fail(ctx, TZ_ERR_INVALID, "k_huff_count needs a 16-byte aligned payload");
+    TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, TZ_HUFF_COUNT_BINS * sizeof(unsigned long long), ctx->stream));
+    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    hipLaunchKernelGGL(k_huff_count, dim3(grid_for((n + 7) / 8, 256)), dim3(256), 0, ctx->stream, in, n, d_hist, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// Size pass: one wave per chunk, four chunks per workgroup.  A 16-byte load per lane covers two runs per step (32 lanes x
+// 8 symbols = one run), so the loads are fully coalesced; the 32 partial sums of a run meet in a butterfly.  run_bits[r]
+// is the index's 16-bit entry of run r; chunk_bits[c] feeds k_huff_scan.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_huff_size(const int16_t* __restrict__ in, size_t n, const uint16_t* __restrict__ enc, int A,
+                                                   int base, size_t nruns, size_t nchunks, uint16_t* __restrict__ run_bits,
+                                                   unsigned* __restrict__ chunk_bits, tz_huff_meta* __restrict__ meta) {
+    __shared__ uint8_t len[HF_ENC_PAD];
+    for (int k = threadIdx.x; k < HF_ENC_PAD; k += 256) len[k] = k < A ? (uint8_t)(enc[k] >> 12) : 0;
+    __syncthreads();
+    const size_t chunk = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (chunk >= nchunks) return;
+    const int lane = threadIdx.x & 63;
+    const size_t c0 = chunk * HF_CHUNK;
+    unsigned mine = 0;
+    bool bad = false;
+    for (int j = 0; j < HF_CR / 2; ++j) {
+        const size_t e0 = c0 + (size_t)j * 512 + (size_t)lane * 8;
+        unsigned s = 0;
+        if (e0 < n) {
+            const short8 v = hf_load8<VEC>(in, e0, n, (short)0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const unsigned sym = (unsigned)((int)v[k] - base);
+                const unsigned l = sym < (unsigned)A ? len[sym] : 0u;
+                if (e0 + k < n) {
+                    s += l;
+                    bad |= l == 0;
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+        const size_t run = chunk * HF_CR + 2 * j + (lane >> 5);
+        if ((lane & 31) == 0 && run < nruns) {
+            run_bits[run] = (uint16_t)s;
+            mine += s;
+        }
+    }
+    mine += __shfl_xor(mine, 32, 64);
+    if (lane == 0) chunk_bits[chunk] = mine;
+    if (bad) atomicOr(&meta->bad, 1u);
+}
+
+// Chunk word offsets: exclusive scan of ceil(bits / 32) over the chunks (a few 10^4 values: one workgroup, each thread a
+// contiguous slice, the 1024 slice sums scanned in LDS).
+__global__ __launch_bounds__(1024) void k_huff_scan(const unsigned* __restrict__ chunk_bits, size_t nchunks, unsigned* __restrict__ chunk_off,
+                                                    tz_huff_meta* __restrict__ meta) {
+    __shared__ unsigned long long part[1024];
+    const size_t per = (nchunks + 1023) / 1024, a = std::min(nchunks, (size_t)threadIdx.x * per), b = std::min(nchunks, a + per);
+    unsigned long long s = 0;
+    for (size_t c = a; c < b; ++c) s += (chunk_bits[c] + 31u) >> 5;
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const unsigned long long t = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+        __syncthreads();
+        part[threadIdx.x] += t;
+        __syncthreads();
+    }
+    unsigned long long off = part[threadIdx.x] - s;
+    for (size_t c = a; c < b; ++c) {
+        chunk_off[c] = (unsigned)off;   // (the host refuses a stream of 2^32 words or more before anything reads these)
+        off += (chunk_bits[c] + 31u) >> 5;
+    }
+    if (threadIdx.x == 1023) meta->total_words = part[1023];
+}
+
+int tzk_huff_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
+                  unsigned* d_chunk_off, tz_huff_meta* d_meta) {
+    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
+    void* d_cbits;
+    TZ_TRY(tz_pool_alloc(ctx, nchunks * sizeof(unsigned), &d_cbits));
+    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    const dim3 grid((unsigned)((nchunks + 3) / 4));
+    if ((uintptr_t)in & 15)
+        hipLaunchKernelGGL(k_huff_size<false>, grid, dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
+                           (unsigned*)d_cbits, d_meta);
+    else
+        hipLaunchKernelGGL(k_huff_size<true>, grid, dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
+                           (unsigned*)d_cbits, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_huff_scan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)d_cbits, nchunks, d_chunk_off, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// Pack pass: one wave (= one workgroup) per chunk.  Every lane packs its run into a 64-bit accumulator and ORs whole
+// 32-bit words into the chunk's image in LDS (the first and the last word of a run are shared with the neighbouring
+// lanes: ds_or, no return value); the image then leaves with coalesced stores.  No global atomics.
+template <bool VEC>
+__global__ __launch_bounds__(64) void k_huff_enc(const int16_t* __restrict__ in, size_t n, const uint16_t* __restrict__ enc, int A, int base,
+                                                 size_t nruns, const uint16_t* __restrict__ run_bits, const unsigned* __restrict__ chunk_off,
+                                                 unsigned* __restrict__ words, size_t stream_words) {
+    __shared__ uint16_t tab[HF_ENC_PAD];
+    __shared__ unsigned img[HF_CHUNK_WORDS];
+    const int lane = threadIdx.x;
+    const size_t chunk = blockIdx.x, run = chunk * HF_CR + lane;
+    for (int k = lane; k < HF_ENC_PAD; k += 64) tab[k] = k < A ? enc[k] : (uint16_t)0;
+    unsigned tot;
+    const unsigned pos = hf_wave_excl(run < nruns ? (unsigned)run_bits[run] : 0u, &tot);
+    const unsigned cw = std::min((tot + 31u) >> 5, (unsigned)HF_CHUNK_WORDS);
+    for (unsigned k = lane; k < cw; k += 64) img[k] = 0;
+    __syncthreads();
+    const size_t r0 = run * HF_R;
+    const int cnt = r0 < n ? (int)std::min((size_t)HF_R, n - r0) : 0;
+    unsigned long long acc = 0;
+    unsigned nb = pos & 31u, wi = pos >> 5;
+    for (int j = 0; j < cnt; j += 8) {
+        const short8 v = hf_load8<VEC>(in, r0 + j, n, (short)0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const unsigned sym = (unsigned)((int)v[k] - base);
+            const unsigned e = (sym < (unsigned)A && j + k < cnt) ? tab[sym] : 0u;   // (no code: nothing is written; k_huff_size said so)
+            acc |= (unsigned long long)(e & 0xFFFu) << nb;
+            nb += e >> 12;
+            if (nb >= 32) {
+                if (wi < cw) atomicOr(&img[wi], (unsigned)acc);
+                ++wi;
+                acc >>= 32;
+                nb -= 32;
+            }
+        }
+    }
+    if (nb > 0 && wi < cw) atomicOr(&img[wi], (unsigned)acc);
+    __syncthreads();
+    const size_t w0 = chunk_off[chunk];
+    for (unsigned k = lane; k < cw; k += 64)
+        if (w0 + k < stream_words) words[w0 + k] = img[k];
+}
+
+int tzk_huff_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
+                 const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words) {
+    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    if ((uintptr_t)in & 15)
+        hipLaunchKernelGGL(k_huff_enc<false>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits,
+                           d_chunk_off, d_words, stream_words);
+    else
+        hipLaunchKernelGGL(k_huff_enc<true>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits,
+                           d_chunk_off, d_words, stream_words);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// Expand pass: one wave (= one workgroup) per chunk.  The chunk's words are staged in LDS behind the decode table; every
+// lane decodes its run from its own bit offset (exclusive wave scan of the run sizes) and writes 16-byte pieces of its 512
+// output bytes.  Nothing taken from the stream becomes an address unchecked: chunk offsets are clamped to the stream, a
+// chunk's staged words to the LDS image, every read of the image to its end (a zero word stands behind it), run sizes to
+// R * L, and a lane stops after its run's symbol count, which comes from n alone.  Every table entry has a length >= 1
+// and a symbol inside the alphabet (the host builds it from validated lengths), so a corrupt body yields wrong symbols,
+// never an access outside the buffers.
+template <bool VEC>
+__global__ __launch_bounds__(64) void k_huff_dec(const unsigned* __restrict__ chunk_off, const uint16_t* __restrict__ run_bits,
+                                                 const unsigned* __restrict__ words, size_t stream_words, size_t nruns, size_t nchunks,
+                                                 const uint16_t* __restrict__ dec, int base, size_t n, int16_t* __restrict__ out) {
+    __shared__ uint16_t tab[1 << HF_L];
+    __shared__ unsigned img[HF_CHUNK_WORDS + 1];
+    const int lane = threadIdx.x;
+    const size_t chunk = blockIdx.x, run = chunk * HF_CR + lane;
+    for (int k = lane; k < (1 << HF_L) / 8; k += 64) ((uint4*)tab)[k] = ((const uint4*)dec)[k];
+    const size_t w0 = std::min((size_t)chunk_off[chunk], stream_words);
+    const size_t w1 = chunk + 1 < nchunks ? std::min((size_t)chunk_off[chunk + 1], stream_words) : stream_words;
+    const unsigned cw = w1 > w0 ? (unsigned)std::min(w1 - w0, (size_t)HF_CHUNK_WORDS) : 0u;
+    for (unsigned k = lane; k < cw; k += 64) img[k] = words[w0 + k];
+    if (lane == 0) img[cw] = 0;
+    unsigned tot;
+    const unsigned pos = hf_wave_excl(run < nruns ? std::min((unsigned)run_bits[run], (unsigned)(HF_R * HF_L)) : 0u, &tot);
+    __syncthreads();
+    const size_t r0 = run * HF_R;
+    const int cnt = r0 < n ? (int)std::min((size_t)HF_R, n - r0) : 0;
+    unsigned wi = pos >> 5;
+    unsigned long long acc = (unsigned long long)img[std::min(wi, cw)] >> (pos & 31u);
+    unsigned nb = 32u - (pos & 31u);
+    ++wi;
+    acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
+    nb += 32;
+    ++wi;
+    for (int j = 0; j < cnt; j += 8) {
+        short8 v;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const unsigned e = tab[(unsigned)acc & 0xFFFu];
+            const unsigned l = e >> 12;
+            v[k] = (short)((int)(e & 0xFFFu) + base);
+            acc >>= l;
+            nb -= l;
+            if (nb <= 32) {
+                acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
+                nb += 32;
+                ++wi;
+            }
+        }
+        if (VEC && j + 8 <= cnt) {
+            *(short8*)(out + r0 + j) = v;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (j + k < cnt) out[r0 + j + k] = v[k];
+        }
+    }
+}
+
+int tzk_huff_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
+                 const uint16_t* d_dec, int base, size_t n, int16_t* out) {
+    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    if ((uintptr_t)out & 15)
+        hipLaunchKernelGGL(k_huff_dec<false>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words,
+                           nruns, nchunks, d_dec, base, n, out);
+    else
+        hipLaunchKernelGGL(k_huff_dec<true>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words,
+                           nruns, nchunks, d_dec, base, n, out);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}

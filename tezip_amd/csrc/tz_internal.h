@@ -33,6 +33,7 @@ enum tz_prof_class {
     TZP_QSERIAL,    // not a time: `launches` counts the chains the quantiser sent through its serial fallback (k_q_serial)
     TZP_CARRY,      // prefix carry of the inverse scan (k_undelta_carry, tz_decode_range)
     TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality)
+    TZP_HUFF,       // opt-in Huffman coder: k_huff_count / k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec
     TZP_COUNT
 };
 
@@ -123,6 +124,13 @@ struct tz_ctx {
     volatile unsigned* h_fault = nullptr;
     unsigned* d_fault = nullptr;
     int decode_unfused = 0;                 // TEZIP_DECODE_UNFUSED=1: tz_decode as scan + reconstruct launches (cross-check)
+    // opt-in Huffman coder (tz_huff_*): the coded stream (index | bits) of the resident payload, or the stream a decoder
+    // stages with tz_huff_begin / tz_huff_put together with what tz_huff_decode needs to expand it
+    uint8_t* d_huff = nullptr;
+    size_t cap_huff = 0, huff_bytes = 0;
+    size_t huff_n = 0;                      // tz_huff_begin: elements the staged stream decodes to (0: nothing staged)
+    int huff_base = 0;
+    std::vector<uint16_t> huff_dec_tab;     // tz_huff_begin: the 2^12-entry decode table of the staged stream's lengths
     uint8_t* d_out = nullptr;               // resident decoded frames of a tz_decode(frames_out = NULL)
     size_t cap_out = 0;
     bool have_decoded = false;
@@ -287,6 +295,22 @@ int tzk_reconstruct(tz_ctx*, const float* pred, const uint8_t* key, const uint8_
                     int nframes, int H, int W, int Hp, int Wp, uint8_t* out);
 // per-frame (sse, max |dec - orig|, #changed) of two unpadded nframes x fe uint8 stacks; d_out (device) is cleared here
 int tzk_quality(tz_ctx*, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out);
+// Huffman coder.  Geometry: runs of TZ_HUFF_RUN symbols, chunks of TZ_HUFF_CHUNK_RUNS runs.
+static constexpr int TZ_HUFF_L = 12, TZ_HUFF_RUN = 256, TZ_HUFF_CHUNK_RUNS = 64;
+static constexpr int TZ_HUFF_COUNT_BINS = 4096, TZ_HUFF_COUNT_BIAS = 1024;   // k_huff_count: bin = value + bias
+struct tz_huff_meta {            // device words the size / scan launches leave for the host
+    unsigned long long total_words;
+    unsigned bad;                // a payload value without a code (k_huff_size) or outside the counted range (k_huff_count)
+    unsigned pad;
+};
+int tzk_huff_count(tz_ctx*, const int16_t* in, size_t n, unsigned long long* d_hist4096, tz_huff_meta* d_meta);
+// run sizes (u16, bits) and chunk word offsets (u32) of the payload under the code `h_enc` (u16[A]: stored code | length << 12)
+int tzk_huff_size(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
+                  unsigned* d_chunk_off, tz_huff_meta* d_meta);
+int tzk_huff_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
+                 const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words);
+int tzk_huff_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
+                 const uint16_t* d_dec_tab4096, int base, size_t n, int16_t* out);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,
             double* h_sse);
 int tzk_sse_blocks(int Hp, int Wp);

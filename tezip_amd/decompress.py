@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from . import _lib, sidecar, zstd
+from . import _lib, huff, sidecar, zstd
 from . import dist as tzdist
 from .compress import SHUFFLE_MARK, make_context, open_model
 from .data_utils import padding_shape
@@ -194,60 +194,84 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
 
         with open(paths["entropy.dat"], "rb") as f:
-            ent_size = zstd.content_size(f.read(64))
-        if ent_size % 2 or ent_size < 16:
-            raise ValueError("entropy.dat is too short")
-        total = ent_size // 2
-        # the stack is known up front only from this build's sidecar -- a HINT: it is used when it agrees with everything
-        # that can be checked now (key_frame.dat's size, the model's frame size, filename.txt), and the trailer has the last
-        # word; a hint that does not fit is dropped and the late path below reports whatever is really wrong
-        early = None
-        if stack is not None and key_len == stack[0] * stack[1] * stack[2] * 3 and len(file_names) == stack[0]:
-            hp_e, wp_e = padding_shape(stack[1], stack[2])
-            if model_shape is None or (model_shape[0] == hp_e and model_shape[1] == wp_e):
-                early = stack
-        pre = _Prefetch(paths["entropy.dat"])      # entropy.dat is being decompressed from here on
-        try:
-            per = None
-            ctx.payload_begin(total)               # (in front of the rollout: the copy stream need not wait for it)
-            if early is not None:
-                nt, H, W, warm_early = early
-                hp, wp = checks(nt, H, W)
-                per = stage_keys(nt, H, W, hp, wp)
-                rollout(nt, warm_early)
-                stages.mark("rollout (decoder) queued")
-            tail = np.zeros(0, np.int16)
-            off = 0
-            for size, piece in pre:
-                if size != ent_size or piece.size % 2 or off * 2 + piece.size > ent_size:
-                    raise ValueError("entropy.dat: inconsistent stream")
-                p16 = piece.view(np.int16)
-                ctx.payload_put(off, p16)       # staged on the copy stream; the piece buffer is free on return
-                off += p16.size
-                tail = np.concatenate([tail, p16[-TAIL_ELEMS:]])[-TAIL_ELEMS:]
-        finally:
-            pre.close()
-        if off != total:
-            raise ValueError("entropy.dat: truncated stream")
-        stages.mark("zstd-d entropy.dat + stage to HBM", ctx)
-        warm_up, shape, tlen = int(tail[-1]), tuple(int(v) for v in tail[-6:-1]), int(tail[-7])
-        if tlen < -1 or tlen > tail.size - 7:
-            raise ValueError("corrupt table length %d" % tlen)
-        table = None if tlen == -1 else np.ascontiguousarray(tail[tail.size - 7 - tlen: tail.size - 7])
-        payload_len = total - 7 - max(tlen, 0)
-        check_stream(shape, warm_up, payload_len, key_len)
-        if shape[0] == SHUFFLE_MARK:
-            return False
-        _, nt, H, W, C = shape
-        if early is not None and (nt, H, W, warm_up) != tuple(early):
-            raise ValueError("tezip_amd.json describes the stack as %r (frames, height, width, warm-up), entropy.dat's trailer as %r"
-                             % (tuple(early), (nt, H, W, warm_up)))
-        if frames is not None:
-            check_frames(frames, nt)
-        if early is None:
+            ent_head = f.read(64)
+        if huff.is_huff(ent_head):
+            # this build's opt-in Huffman file: everything the decoder needs stands in FRONT of the bit stream, so the
+            # whole file is validated on the CPU (huff.parse) before anything is staged, and the rollout is queued first
+            coded = huff.parse(np.fromfile(paths["entropy.dat"], np.uint8), key_len)
+            table, warm_up = coded.table, coded.warm_up
+            _, nt, H, W, C = coded.shape
+            if stack is not None and key_len == stack[0] * stack[1] * stack[2] * 3 and len(file_names) == stack[0] \
+                    and (nt, H, W, warm_up) != tuple(stack):
+                raise ValueError("tezip_amd.json describes the stack as %r (frames, height, width, warm-up), entropy.dat's trailer as %r"
+                                 % (tuple(stack), (nt, H, W, warm_up)))
+            if frames is not None:
+                check_frames(frames, nt)
             hp, wp = checks(nt, H, W)
+            ctx.huff_begin(coded.body.size, coded.n, coded.lengths, coded.base, coded.run)
             per = stage_keys(nt, H, W, hp, wp)
             rollout(nt, warm_up)
+            stages.mark("rollout (decoder) queued")
+            for off in range(0, coded.body.size, 16 << 20):
+                ctx.huff_put(off, coded.body[off: off + (16 << 20)])   # pageable: the piece is free again on return
+            ctx.huff_decode()                                           # -> the payload buffer, as payload_put leaves it
+            stages.mark("stage entropy.dat + huffman decode", ctx)
+        else:
+            with open(paths["entropy.dat"], "rb") as f:
+                ent_size = zstd.content_size(f.read(64))
+            if ent_size % 2 or ent_size < 16:
+                raise ValueError("entropy.dat is too short")
+            total = ent_size // 2
+            # the stack is known up front only from this build's sidecar -- a HINT: it is used when it agrees with everything
+            # that can be checked now (key_frame.dat's size, the model's frame size, filename.txt), and the trailer has the last
+            # word; a hint that does not fit is dropped and the late path below reports whatever is really wrong
+            early = None
+            if stack is not None and key_len == stack[0] * stack[1] * stack[2] * 3 and len(file_names) == stack[0]:
+                hp_e, wp_e = padding_shape(stack[1], stack[2])
+                if model_shape is None or (model_shape[0] == hp_e and model_shape[1] == wp_e):
+                    early = stack
+            pre = _Prefetch(paths["entropy.dat"])      # entropy.dat is being decompressed from here on
+            try:
+                per = None
+                ctx.payload_begin(total)               # (in front of the rollout: the copy stream need not wait for it)
+                if early is not None:
+                    nt, H, W, warm_early = early
+                    hp, wp = checks(nt, H, W)
+                    per = stage_keys(nt, H, W, hp, wp)
+                    rollout(nt, warm_early)
+                    stages.mark("rollout (decoder) queued")
+                tail = np.zeros(0, np.int16)
+                off = 0
+                for size, piece in pre:
+                    if size != ent_size or piece.size % 2 or off * 2 + piece.size > ent_size:
+                        raise ValueError("entropy.dat: inconsistent stream")
+                    p16 = piece.view(np.int16)
+                    ctx.payload_put(off, p16)       # staged on the copy stream; the piece buffer is free on return
+                    off += p16.size
+                    tail = np.concatenate([tail, p16[-TAIL_ELEMS:]])[-TAIL_ELEMS:]
+            finally:
+                pre.close()
+            if off != total:
+                raise ValueError("entropy.dat: truncated stream")
+            stages.mark("zstd-d entropy.dat + stage to HBM", ctx)
+            warm_up, shape, tlen = int(tail[-1]), tuple(int(v) for v in tail[-6:-1]), int(tail[-7])
+            if tlen < -1 or tlen > tail.size - 7:
+                raise ValueError("corrupt table length %d" % tlen)
+            table = None if tlen == -1 else np.ascontiguousarray(tail[tail.size - 7 - tlen: tail.size - 7])
+            payload_len = total - 7 - max(tlen, 0)
+            check_stream(shape, warm_up, payload_len, key_len)
+            if shape[0] == SHUFFLE_MARK:
+                return False
+            _, nt, H, W, C = shape
+            if early is not None and (nt, H, W, warm_up) != tuple(early):
+                raise ValueError("tezip_amd.json describes the stack as %r (frames, height, width, warm-up), entropy.dat's trailer as %r"
+                                 % (tuple(early), (nt, H, W, warm_up)))
+            if frames is not None:
+                check_frames(frames, nt)
+            if early is None:
+                hp, wp = checks(nt, H, W)
+                per = stage_keys(nt, H, W, hp, wp)
+                rollout(nt, warm_up)
         fb = H * W * C
         stages.mark("rollout (decoder)", ctx)
         lo, hi = frames or (0, nt)
@@ -342,8 +366,21 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
             exit()
 
     key_bytes = read("key_frame.dat")
-    payload, table, shape, warm_up = parse_stream(read("entropy.dat"))
-    check_stream(shape, warm_up, payload.size, len(key_bytes))
+    coded = None
+    try:
+        with open(os.path.join(DATA_DIR, "entropy.dat"), mode='rb') as f:
+            if huff.is_huff(f.read(4)):   # this build's opt-in Huffman file: validated here, expanded on the device below
+                coded = huff.parse(np.fromfile(os.path.join(DATA_DIR, "entropy.dat"), np.uint8), len(key_bytes))
+    except FileNotFoundError:
+        pass   # (read() below prints the reference's message)
+    if coded is not None:
+        if job is not None:
+            print("ERROR: a Huffman-coded entropy.dat cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
+            sys.exit(2)
+        payload, table, shape, warm_up = None, coded.table, coded.shape, coded.warm_up
+    else:
+        payload, table, shape, warm_up = parse_stream(read("entropy.dat"))
+        check_stream(shape, warm_up, payload.size, len(key_bytes))
     _, nt, H, W, C = shape
     key_frames = np.frombuffer(key_bytes, dtype=np.uint8).reshape(nt, H, W, C)
     hp, wp = padding_shape(H, W)
@@ -382,7 +419,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
             ctx.rollout_decode_range(np.ascontiguousarray(key_frames), warm_up, first, end - first)
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
-            frames = ctx.decode_range(np.ascontiguousarray(payload), tb, first, end - first)
+            if coded is not None:
+                ctx.huff_begin(coded.body.size, coded.n, coded.lengths, coded.base, coded.run)
+                ctx.huff_put(0, np.ascontiguousarray(coded.body))
+                ctx.huff_decode()
+            frames = ctx.decode_range(None if coded is not None else np.ascontiguousarray(payload), tb, first, end - first)
             if VERBOSE:
                 prof = ctx.prof_get()
                 if table is not None:

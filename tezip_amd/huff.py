@@ -1,0 +1,299 @@
+"""The Huffman-coded entropy.dat (`--coder huff`; NOT a reference format): container, validation and a plain numpy
+encoder / decoder of the stream the GPU kernels write (k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec in
+csrc/tz_codec.hip).  The slow pair here is the specification the kernels are tested against (tests/test_huff.py,
+tests/test_gpu_huff.py); the product never calls it on the hot path.  DESIGN.md section 9 holds the format as prose.
+
+File layout, little-endian, every section padded with zero bytes to a multiple of 4:
+  header   48 bytes: "TZH1" | u16 version = 1 | u16 L = 12 | u64 n | i32 base | u32 A | u32 R | u32 chunk_runs |
+           u32 nchunks | u32 stream_words | u32 trailer_len | u32 0
+  trailer  trailer_len int16: the reference trailer verbatim (table | T  or  -1, then 1, nt, H, W, 3, then warm_up)
+  lengths  A bytes: code length of symbol s (payload value = s + base), 0 = absent, else 1..L; codes are canonical
+  index    nchunks u32 word offsets of the chunks in the bit stream, then nruns = ceil(n / R) u16 run sizes in bits
+  bits     stream_words u32
+A run is R consecutive symbols coded back to back; a chunk is chunk_runs runs and starts on a word boundary.  A code of
+length l and canonical value c (MSB first) is stored bit-reversed, first code bit in the lowest free bit of the stream.
+"""
+import struct
+
+import numpy as np
+
+MAGIC = b"TZH1"
+VERSION = 1
+MAX_LEN = 12            # L: a decode table entry is symbol (12 bits) | length (4 bits)
+RUN = 256               # R: symbols per run (one lane of the kernels)
+CHUNK_RUNS = 64         # runs per chunk (one wave)
+NBINS = 2111            # TZ_NBINS: the largest alphabet
+HEADER = struct.Struct("<4sHHQiIIIIIII")   # 48 bytes
+
+
+def is_huff(head):
+    """The first bytes of an entropy.dat: this project's magic (a zstd frame starts 28 B5 2F FD)."""
+    return bytes(head[:4]) == MAGIC
+
+
+def _pad4(nbytes):
+    return (nbytes + 3) & ~3
+
+
+def code_lengths(counts, max_len=MAX_LEN):
+    """tz_huff_lengths (host only): optimal length-limited code lengths from counts; uint8[A], 0 = absent."""
+    import ctypes as C
+    from . import _lib
+    counts = np.ascontiguousarray(counts, np.uint64)
+    out = np.zeros(counts.size, np.uint8)
+    rc = _lib.load().tz_huff_lengths(counts.ctypes.data, int(counts.size), int(max_len), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError("tz_huff_lengths refused the counts (status %d): no symbol present, more symbols than 2^max_len "
+                         "codes, or an alphabet outside [1, %d]" % (rc, NBINS))
+    return out
+
+
+def kraft_sum(lengths, max_len=MAX_LEN):
+    """Sum of 2^(max_len - l) over the present symbols: a prefix code has at most 2^max_len."""
+    ln = np.asarray(lengths, np.int64)
+    ln = ln[ln > 0]
+    return int(np.sum(np.int64(1) << (max_len - ln)))
+
+
+def check_lengths(lengths, max_len=MAX_LEN):
+    ln = np.asarray(lengths)
+    if ln.ndim != 1 or not 1 <= ln.size <= NBINS:
+        raise ValueError("entropy.dat (huff): alphabet size A = %d outside [1, %d]" % (ln.size, NBINS))
+    if ln.size and int(ln.max()) > max_len:
+        raise ValueError("entropy.dat (huff): code lengths hold %d, the limit L is %d" % (int(ln.max()), max_len))
+    if not (ln > 0).any():
+        raise ValueError("entropy.dat (huff): code lengths name no symbol")
+    if kraft_sum(ln, max_len) > (1 << max_len):
+        raise ValueError("entropy.dat (huff): Kraft sum of the code lengths exceeds 1 (not a prefix code)")
+
+
+def canonical_codes(lengths):
+    """-> uint16[A] stored (bit-reversed) codes; canonical order: shorter first, then by symbol."""
+    ln = np.asarray(lengths, np.int64)
+    order = [s for s in np.lexsort((np.arange(ln.size), ln)) if ln[s] > 0]
+    codes = np.zeros(ln.size, np.uint32)
+    code, prev = 0, 0
+    for s in order:
+        code <<= int(ln[s]) - prev
+        prev = int(ln[s])
+        codes[s] = code
+        code += 1
+    rev = np.zeros(ln.size, np.uint32)
+    for s in order:
+        c, l, r = int(codes[s]), int(ln[s]), 0
+        for b in range(l):
+            r |= ((c >> b) & 1) << (l - 1 - b)
+        rev[s] = r
+    return rev.astype(np.uint16)
+
+
+def encode_table(lengths):
+    """uint16[A]: stored code | length << 12 (0 for an absent symbol) -- what k_huff_enc holds in LDS."""
+    return (canonical_codes(lengths) | (np.asarray(lengths, np.uint16) << 12)).astype(np.uint16)
+
+
+def decode_table(lengths, max_len=MAX_LEN):
+    """uint16[2^L]: symbol | length << 12 for the next L bits of the stream.  Entries no code reaches (a one-symbol
+    alphabet) hold the lowest present symbol with length 1, so that a decoder always advances."""
+    ln = np.asarray(lengths, np.int64)
+    rev = canonical_codes(ln)
+    present = np.nonzero(ln > 0)[0]
+    tab = np.full(1 << max_len, int(present[0]) | (1 << 12), np.uint16)
+    for s in present:
+        l = int(ln[s])
+        tab[int(rev[s]) + (np.arange(1 << (max_len - l)) << l)] = int(s) | (l << 12)
+    return tab
+
+
+def geometry(n, run=RUN, chunk_runs=CHUNK_RUNS):
+    nruns = (n + run - 1) // run
+    return nruns, (nruns + chunk_runs - 1) // chunk_runs
+
+
+def encode_body(payload, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
+    """int16 payload -> (chunk_off uint32[nchunks], run_bits uint16[nruns], words uint32[stream_words])."""
+    sym = np.asarray(payload, np.int64).reshape(-1) - int(base)
+    n = sym.size
+    ln = np.asarray(lengths, np.int64)
+    if n < 1:
+        raise ValueError("huff: an empty payload cannot be coded")
+    if sym.min() < 0 or sym.max() >= ln.size or (ln[sym] == 0).any():
+        raise ValueError("huff: the payload holds a value without a code")
+    nruns, nchunks = geometry(n, run, chunk_runs)
+    sl = ln[sym]
+    cum = np.concatenate([[0], np.cumsum(sl)])                      # bits in front of symbol i, chunks unpadded
+    run_start = np.arange(nruns, dtype=np.int64) * run
+    run_bits = cum[np.minimum(run_start + run, n)] - cum[run_start]
+    chunk_first = np.arange(nchunks, dtype=np.int64) * run * chunk_runs
+    chunk_bits = cum[np.minimum(chunk_first + run * chunk_runs, n)] - cum[chunk_first]
+    chunk_words = (chunk_bits + 31) >> 5
+    chunk_off = np.concatenate([[0], np.cumsum(chunk_words)])
+    total = int(chunk_off[-1])
+    if total >= 1 << 32:
+        raise ValueError("huff: the bit stream needs %d words, the format holds 2^32 - 1" % total)
+    ci = np.arange(n, dtype=np.int64) // (run * chunk_runs)
+    pos = chunk_off[ci] * 32 + (cum[:-1] - cum[chunk_first][ci])   # stream bit of every symbol's first code bit
+    val = canonical_codes(ln).astype(np.uint64)[sym] << (pos & 31).astype(np.uint64)
+    words = np.zeros(total + 1, np.uint64)
+    w = pos >> 5                                                    # ascending: codes never overlap, so OR is a sum
+    first = np.nonzero(np.concatenate([[True], w[1:] != w[:-1]]))[0]
+    words[w[first]] += np.add.reduceat(val & np.uint64(0xFFFFFFFF), first)
+    words[w[first] + 1] += np.add.reduceat(val >> np.uint64(32), first)
+    return chunk_off[:-1].astype(np.uint32), run_bits.astype(np.uint16), words[:total].astype(np.uint32)
+
+
+def decode_body(chunk_off, run_bits, words, n, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
+    """The inverse of encode_body: every run is decoded from its own bit offset (chunk offset + the run sizes in front of
+    it inside the chunk), all runs in lockstep as the lanes of k_huff_dec do.  Reads past the stream's end see zeros."""
+    nruns, nchunks = geometry(n, run, chunk_runs)
+    tab = decode_table(lengths)
+    rb = np.zeros(nchunks * chunk_runs, np.int64)
+    rb[:nruns] = np.asarray(run_bits, np.int64)
+    rb = rb.reshape(nchunks, chunk_runs)
+    pos = (np.asarray(chunk_off, np.int64)[:, None] * 32 + np.cumsum(rb, 1) - rb).reshape(-1)[:nruns]
+    w = np.concatenate([np.asarray(words, np.uint64), np.zeros(2, np.uint64)])
+    last = w.size - 2
+    out = np.zeros(nruns * run, np.int16)
+    for k in range(run):
+        i = np.minimum(pos >> 5, last)
+        bits = ((w[i] | (w[i + 1] << np.uint64(32))) >> (pos & 31).astype(np.uint64)) & np.uint64(0xFFF)
+        e = tab[bits.astype(np.int64)]
+        out[k::run] = (e & 0xFFF).astype(np.int64) + int(base)
+        pos = pos + (e >> 12)
+    return out[:n]
+
+
+def reference_trailer(table, shape5, warm_up):
+    """compress.py:381-394 without the payload: table | T (or -1) | shape | warm_up as int16."""
+    if table is not None:
+        tail = np.concatenate([np.asarray(table, np.int64), [len(table)]])
+    else:
+        tail = np.array([-1], dtype=np.int64)
+    return np.concatenate([tail, list(shape5), [warm_up]]).astype("<i2")
+
+
+def parse_trailer(tr):
+    """-> (table | None, shape5, warm_up) of the reference trailer held in the header."""
+    tr = np.asarray(tr, np.int16)
+    if tr.size < 7:
+        raise ValueError("entropy.dat (huff): trailer holds %d values, at least 7 are needed" % tr.size)
+    warm_up, shape, tlen = int(tr[-1]), tuple(int(v) for v in tr[-6:-1]), int(tr[-7])
+    if tlen == -1:
+        if tr.size != 7:
+            raise ValueError("entropy.dat (huff): trailer without a table holds %d values, not 7" % tr.size)
+        return None, shape, warm_up
+    if tlen < 0 or tlen != tr.size - 7:
+        raise ValueError("entropy.dat (huff): trailer table length %d does not fit its %d values" % (tlen, tr.size))
+    return np.ascontiguousarray(tr[:tlen]), shape, warm_up
+
+
+def pack_front(trailer, lengths, base, n, nchunks, stream_words, run=RUN, chunk_runs=CHUNK_RUNS):
+    """Header | trailer | lengths: everything of the file in front of the index."""
+    trailer = np.ascontiguousarray(trailer, "<i2")
+    lengths = np.ascontiguousarray(lengths, np.uint8)
+    head = HEADER.pack(MAGIC, VERSION, MAX_LEN, int(n), int(base), int(lengths.size), int(run), int(chunk_runs), int(nchunks),
+                       int(stream_words), int(trailer.size), 0)
+    tb, lb = trailer.tobytes(), lengths.tobytes()
+    return head + tb + b"\0" * (_pad4(len(tb)) - len(tb)) + lb + b"\0" * (_pad4(len(lb)) - len(lb))
+
+
+def pack_body(chunk_off, run_bits, words):
+    """Index | bits: the part of the file the device writes (tz_huff_encode's stream)."""
+    rb = np.ascontiguousarray(run_bits, "<u2").tobytes()
+    return (np.ascontiguousarray(chunk_off, "<u4").tobytes() + rb + b"\0" * (_pad4(len(rb)) - len(rb))
+            + np.ascontiguousarray(words, "<u4").tobytes())
+
+
+def body_bytes(n, stream_words, run=RUN, chunk_runs=CHUNK_RUNS):
+    nruns, nchunks = geometry(n, run, chunk_runs)
+    return nchunks * 4 + _pad4(nruns * 2) + stream_words * 4
+
+
+def encode_file(payload, table, shape5, warm_up, lengths=None, base=None):
+    """The whole entropy.dat of a payload, on the CPU (tests, and the specification of compress.run's output)."""
+    payload = np.asarray(payload, np.int16).reshape(-1)
+    if base is None:
+        base = int(payload.min())
+    if lengths is None:
+        lengths = code_lengths(np.bincount(payload.astype(np.int64) - base))
+    co, rb, words = encode_body(payload, lengths, base)
+    return pack_front(reference_trailer(table, shape5, warm_up), lengths, base, payload.size, co.size, words.size) + pack_body(co, rb, words)
+
+
+class Parsed:
+    """A validated Huffman entropy.dat: header fields, the reference trailer's content, and views of the sections."""
+
+
+def parse(data, key_len=None):
+    """Validate a Huffman-coded entropy.dat (bytes / uint8 array) -> Parsed.  Everything a pointer or a launch will be
+    derived from is checked here, on the CPU; a failure is a ValueError that names the field."""
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1)
+    if buf.size < HEADER.size:
+        raise ValueError("entropy.dat (huff): file size %d is shorter than the %d-byte header (truncated)" % (buf.size, HEADER.size))
+    magic, version, max_len, n, base, A, run, chunk_runs, nchunks, stream_words, trailer_len, _ = HEADER.unpack(buf[:HEADER.size].tobytes())
+    if magic != MAGIC:
+        raise ValueError("entropy.dat (huff): magic %r is not %r" % (magic, MAGIC))
+    if version != VERSION:
+        raise ValueError("entropy.dat (huff): format version %d, this build reads version %d" % (version, VERSION))
+    if max_len != MAX_LEN:
+        raise ValueError("entropy.dat (huff): code length limit L = %d, this build reads L = %d" % (max_len, MAX_LEN))
+    if not 1 <= A <= NBINS:
+        raise ValueError("entropy.dat (huff): alphabet size A = %d outside [1, TZ_NBINS = %d]" % (A, NBINS))
+    if base < -32768 or base + A - 1 > 32767:
+        raise ValueError("entropy.dat (huff): symbol base %d with A = %d leaves int16" % (base, A))
+    if run != RUN or chunk_runs != CHUNK_RUNS:
+        raise ValueError("entropy.dat (huff): run length R = %d / chunk of %d runs, this build reads R = %d / %d"
+                         % (run, chunk_runs, RUN, CHUNK_RUNS))
+    if n < 1 or n >= 1 << 40:
+        raise ValueError("entropy.dat (huff): element count n = %d outside [1, 2^40)" % n)
+    nruns, want_chunks = geometry(n, run, chunk_runs)
+    if nchunks != want_chunks:
+        raise ValueError("entropy.dat (huff): nchunks = %d, n = %d elements make %d chunks" % (nchunks, n, want_chunks))
+    if not 7 <= trailer_len <= NBINS + 7:
+        raise ValueError("entropy.dat (huff): trailer length %d outside [7, %d]" % (trailer_len, NBINS + 7))
+    o_tr = HEADER.size
+    o_len = o_tr + _pad4(trailer_len * 2)
+    o_idx = o_len + _pad4(A)
+    o_runs = o_idx + nchunks * 4
+    o_bits = o_runs + _pad4(nruns * 2)
+    total = o_bits + stream_words * 4
+    if buf.size != total:
+        raise ValueError("entropy.dat (huff): file size %d, the header describes %d bytes (truncated or corrupt file)" % (buf.size, total))
+    p = Parsed()
+    p.n, p.base, p.A, p.run, p.chunk_runs, p.nchunks, p.nruns, p.stream_words = n, base, A, run, chunk_runs, nchunks, nruns, stream_words
+    p.table, p.shape, p.warm_up = parse_trailer(buf[o_tr: o_tr + trailer_len * 2].view("<i2"))
+    p.lengths = buf[o_len: o_len + A]
+    check_lengths(p.lengths)
+    one, nt, H, W, C = p.shape
+    if one != 1 or C != 3 or nt < 1 or H < 1 or W < 1:
+        raise ValueError("entropy.dat (huff): unsupported stack shape %r (expected (1, nt, H, W, 3))" % (tuple(p.shape),))
+    if n != nt * H * W * C:
+        raise ValueError("entropy.dat (huff): element count n = %d, the trailer's shape says %d" % (n, nt * H * W * C))
+    if key_len is not None and key_len != n:
+        raise ValueError("key_frame.dat holds %d bytes, entropy.dat's trailer implies %d" % (key_len, n))
+    if not 0 <= p.warm_up < nt:
+        raise ValueError("entropy.dat: warm-up count %d outside [0, %d)" % (p.warm_up, nt))
+    if p.table is not None and (base != 0 or A > max(len(p.table), 1)):
+        raise ValueError("entropy.dat (huff): alphabet A = %d / base %d does not fit the %d ranks of the table" % (A, base, len(p.table)))
+    p.chunk_off = buf[o_idx: o_runs].view("<u4")
+    p.run_bits = buf[o_runs: o_runs + nruns * 2].view("<u2")
+    p.words = buf[o_bits: total].view("<u4")
+    p.body = buf[o_idx: total]                      # index | bits: what tz_huff_put stages
+    co = p.chunk_off.astype(np.int64)
+    if co[0] != 0 or (np.diff(co) < 0).any() or co[-1] > stream_words:
+        raise ValueError("entropy.dat (huff): chunk offset table is not ascending inside the %d words of the bit stream" % stream_words)
+    rb = p.run_bits.astype(np.int64)
+    if (rb > run * MAX_LEN).any():
+        raise ValueError("entropy.dat (huff): a run length of %d bits exceeds R * L = %d" % (int(rb.max()), run * MAX_LEN))
+    per_chunk = np.add.reduceat(rb, np.arange(0, nruns, chunk_runs))
+    room = (np.concatenate([co[1:], [stream_words]]) - co) * 32
+    if (per_chunk > room).any():
+        c = int(np.nonzero(per_chunk > room)[0][0])
+        raise ValueError("entropy.dat (huff): the run lengths of chunk %d sum to %d bits, the chunk has %d" % (c, int(per_chunk[c]), int(room[c])))
+    return p
+
+
+def decode_file(data, key_len=None):
+    """-> (payload int16[n], Parsed) on the CPU."""
+    p = parse(data, key_len)
+    return decode_body(p.chunk_off, p.run_bits, p.words, p.n, p.lengths, p.base), p

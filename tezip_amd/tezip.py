@@ -45,6 +45,9 @@ FLAG_TABLE = (
     # not in the reference: with -c, also write quality.json (the error the bound introduced, per frame and for the
     # sequence, from the stored payload decoded on the GPU) and print max_abs_err / PSNR / ratio (compress.run(REPORT=...))
     (None, "--report", dict(action="store_true", dest="report")),
+    # not in the reference: with -c, the coder of entropy.dat.  zstd = the reference's file; huff = canonical Huffman codes
+    # written by the GPU (tezip_amd/huff.py; the reference cannot read such a file, -u recognises it by its magic)
+    (None, "--coder", dict(type=str, choices=("zstd", "huff"), default="zstd", dest="coder")),
 )
 
 TEXT = {
@@ -119,6 +122,18 @@ def check_report_flag(arg):
     return None
 
 
+def check_coder_flag(arg):
+    """--coder huff is valid with -c of one single-GPU job, without --shuffle and --sweep.  Returns None, or the message
+    of a refusal."""
+    if getattr(arg, "coder", "zstd") == "zstd":
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--coder is valid with -c (--compress) only (-u recognises the coder of a file by itself)"
+    if getattr(arg, "sweep", None) is not None:
+        return "--coder huff cannot be combined with --sweep"
+    return compress.check_coder(arg.coder, arg.shuffle, int(os.environ.get("WORLD_SIZE", "1")) > 1)
+
+
 def probe_gpu(force_cpu):
     """tezip.py:12-21 asked TensorFlow for a GPU; here a context on device 0 must open."""
     if force_cpu:
@@ -169,6 +184,10 @@ def _main(arg):
     if problem:   # likewise, before any GPU is touched
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_coder_flag(arg)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # launched by torch.distributed.run: one rank per GPU
         from . import dist as tzdist
         tzdist.init_from_env()
@@ -199,6 +218,10 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if getattr(arg, "coder", "zstd") != "zstd":
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=arg.coder)
     if getattr(arg, "report", False):
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=True)
