@@ -369,6 +369,30 @@ int tz_huff_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* 
 int tz_huff_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base,
                        int R, int16_t* out);
 
+/* ---- opt-in Huffman coder with repeat tokens (`tezip.py -c --coder huffr`, format TZR1 in DESIGN.md section 9, slow
+ * statement of it in tezip_amd/huffr.py) ---------------------------------------------------------------------------------
+ * The coder above with a tokeniser in front: the payload interleaves three channels, so a quantiser run repeats with
+ * period 3.  Element j of a run of R = 256 elements is a match when j >= 3 and equals element j - 3; a maximal stretch of
+ * m matches is coded as the token T_k, k = floor(log2 m), plus k raw bits, every other element as a literal.  A code has
+ * the A <= TZ_NBINS literals (symbol = value - base) and then the TZ_HUFFR_NTOK tokens: `lengths` holds A + 8 bytes and
+ * `counts` TZ_NBINS + 8 entries in every call below, while A and base keep describing the literals.  Index, bit stream,
+ * refusals and clamps are tz_huff_*'s; the resident stream buffer is shared with them (a tz_huffr_begin replaces a stream
+ * tz_huff_begin staged and the other way round, and each decoder refuses the other's stream with TZ_ERR_STATE). */
+#define TZ_HUFFR_NTOK 8
+int tz_huffr_lengths(const unsigned long long* counts, int total, int max_len, uint8_t* lengths);   /* total = A + 8 */
+/* counts[0 .. A) the literals, counts[A .. A + 8) the tokens T_0..T_7 of the resident payload (k_huffr_count) */
+int tz_huffr_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base);
+int tz_huffr_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* counts, int* A, int* base);
+int tz_huffr_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes);
+int tz_huffr_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out);
+int tz_huffr_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R);
+int tz_huffr_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src);
+int tz_huffr_decode(tz_ctx* ctx);
+int tz_huffr_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
+                        size_t capacity, size_t* bytes);
+int tz_huffr_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base,
+                        int R, int16_t* out);
+
 /* ---- timing helper: HIP events on the context's stream (bench.py) -------------------------- */
 int tz_timer_start(tz_ctx* ctx);
 int tz_timer_stop(tz_ctx* ctx, float* ms);

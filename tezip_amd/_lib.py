@@ -22,6 +22,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "libtezip_hip.so")
 
 TZ_OK = 0
 TZ_NBINS = 2111
+HUFFR_NTOK = 8          # TZ_HUFFR_NTOK: repeat tokens behind the literals of a tz_huffr_* code
 TZ_MAX_TABLE = 1021
 MODES = {"abs": 0, "rel": 1, "absrel": 2, "pwrel": 3}
 
@@ -98,6 +99,18 @@ _SIGS = {
                                      C.POINTER(C.c_size_t)]),
     "tz_huff_decode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p]),
+    "tz_huffr_lengths": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "tz_huffr_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tz_huffr_counts_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tz_huffr_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "tz_huffr_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_huffr_begin": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "tz_huffr_put": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_huffr_decode": (C.c_int, [C.c_void_p]),
+    "tz_huffr_encode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
+    "tz_huffr_decode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p]),
     "tz_timer_start": (C.c_int, [C.c_void_p]),
     "tz_timer_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "tz_prof_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -668,6 +681,61 @@ class Context:
             out = np.empty(n, np.int16)
         self._ck(self.lib.tz_huff_decode_buf(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size), int(base),
                                              int(run), _ptr(out)))
+        return out
+
+    # ---- opt-in Huffman coder with repeat tokens (tz_huffr_*; format: tezip_amd/huffr.py).  `lengths` holds the A literals
+    # and then the 8 tokens; the A the library is given is the number of literals.
+    def huffr_counts(self, x=None):
+        """Token counts of the resident payload (or of the int16 array x) -> (uint64[A + 8], base): the literals s + base,
+        then the repeat tokens T_0..T_7."""
+        counts = np.zeros(TZ_NBINS + HUFFR_NTOK, np.uint64)
+        a, base = C.c_int(0), C.c_int(0)
+        if x is None:
+            self._ck(self.lib.tz_huffr_counts(self.h, counts.ctypes.data, C.byref(a), C.byref(base)))
+        else:
+            self._ck(self.lib.tz_huffr_counts_buf(self.h, _ptr(x), _numel(x), counts.ctypes.data, C.byref(a), C.byref(base)))
+        return counts[: a.value + HUFFR_NTOK].copy(), base.value
+
+    def huffr_encode(self, lengths, base):
+        """Code the resident payload into the resident stream (index | bits); returns its size in bytes."""
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        nbytes = C.c_size_t(0)
+        self._ck(self.lib.tz_huffr_encode(self.h, ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def huffr_get(self, offset, count, out=None):
+        if out is None:
+            out = np.empty(count, np.uint8)
+        self._ck(self.lib.tz_huffr_get(self.h, int(offset), int(count), _ptr(out, np.uint8)))
+        return out
+
+    def huffr_begin(self, nbytes, n, lengths, base, run=256):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        self._ck(self.lib.tz_huffr_begin(self.h, int(nbytes), int(n), ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), int(run)))
+
+    def huffr_put(self, offset, piece):
+        self._ck(self.lib.tz_huffr_put(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
+
+    def huffr_decode(self):
+        self._ck(self.lib.tz_huffr_decode(self.h))
+
+    def huffr_encode_buf(self, x, lengths, base, out=None):
+        """Stand-alone: int16 values (host or device) -> the coded stream (index | bits) as a uint8 array."""
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        n = _numel(x)
+        if out is None:   # the most a stream can need: 12 bits per element, a pad word per chunk, the index
+            out = np.empty(n * 3 // 2 + (n // 16384 + 1) * 8 + (n // 256 + 1) * 2 + 64, np.uint8)
+        nbytes = C.c_size_t(0)
+        self._ck(self.lib.tz_huffr_encode_buf(self.h, _ptr(x), n, ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), _ptr(out),
+                                              _numel(out), C.byref(nbytes)))
+        return out[: nbytes.value]
+
+    def huffr_decode_buf(self, stream, n, lengths, base, run=256, out=None):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        if out is None:
+            out = np.empty(n, np.int16)
+        self._ck(self.lib.tz_huffr_decode_buf(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size) - HUFFR_NTOK,
+                                              int(base), int(run), _ptr(out)))
         return out
 
     # ---- operator seams

@@ -8,7 +8,8 @@ Output directory:
   entropy.dat    zstd-9 of int16: payload | table | T  (or | -1) | 1,nt,H,W,3 | warm_up
                                                                               (compress.py:381-400)
                  with CODER="huff" (--coder huff; not a reference format): "TZH1" header | that trailer | code lengths |
-                 index | bit stream, written by the GPU (tezip_amd/huff.py)
+                 index | bit stream, written by the GPU (tezip_amd/huff.py); with CODER="huffr" the
+                 same under the magic "TZR1", the code being over literals and period-3 repeat tokens (tezip_amd/huffr.py)
 """
 import glob
 import os
@@ -18,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, huff, quality, sidecar, weights, zstd
+from . import _lib, huff, huffr, quality, sidecar, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -226,7 +227,7 @@ class _Stages:
             self.last = now
 
 
-CODERS = ("zstd", "huff")
+CODERS = ("zstd", "huff", "huffr")
 HUFF_PIECE = 16 << 20   # bytes of the coded stream fetched and written at a time
 
 
@@ -234,22 +235,29 @@ def check_coder(coder, shuffle=False, sharded=False):
     """The refusals of --coder, for tezip.py and for a direct caller of run(): None, or the message."""
     if coder not in CODERS:
         return "--coder takes one of %s, got %r" % (", ".join(CODERS), coder)
-    if coder == "huff" and shuffle:
-        return "--coder huff cannot be combined with --shuffle (byte planes help zstd; a symbol coder codes whole symbols)"
-    if coder == "huff" and sharded:
-        return "--coder huff is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+    if coder != "zstd" and shuffle:
+        return "--coder %s cannot be combined with --shuffle (byte planes help zstd; a symbol coder codes whole symbols)" % coder
+    if coder != "zstd" and sharded:
+        return "--coder %s is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU" % coder
     return None
 
 
-def _huff_entropy_file(ctx, path, n, trailer, verbose):
-    """entropy.dat of CODER="huff": the resident payload is coded on the device (tz_huff_encode) and only the coded
-    stream crosses to the host; the header, the reference trailer and the code lengths go in front of it."""
+def _huff_entropy_file(ctx, path, n, trailer, verbose, coder="huff"):
+    """entropy.dat of CODER="huff" / "huffr": the resident payload is coded on the device (tz_huff_encode / tz_huffr_encode)
+    and only the coded stream crosses to the host; the header, the reference trailer and the code lengths go in front of it."""
     t0 = time.perf_counter()
-    counts, base = ctx.huff_counts()
-    lengths = huff.code_lengths(counts)
-    nbytes = ctx.huff_encode(lengths, base)
+    if coder == "huffr":
+        fmt = huffr
+        counts, base = ctx.huffr_counts()
+        lengths = huffr.code_lengths(counts)
+        nbytes = ctx.huffr_encode(lengths, base)
+    else:
+        fmt = huff
+        counts, base = ctx.huff_counts()
+        lengths = huff.code_lengths(counts)
+        nbytes = ctx.huff_encode(lengths, base)
     nruns, nchunks = huff.geometry(n)
-    front = huff.pack_front(trailer, lengths, base, n, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4)
+    front = fmt.pack_front(trailer, lengths, base, n, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4)
     bufs = [np.empty(min(HUFF_PIECE, nbytes), np.uint8) for _ in range(2)]
     with open(path, mode='wb') as f:
         f.write(front)
@@ -304,8 +312,8 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
         tail = np.array([-1], dtype=np.int64)
     trailer = np.concatenate([tail, [SHUFFLE_MARK if shuffled else 1, nt, H, W, 3], [warm_up]]).astype(np.int16)
     t_e = time.perf_counter()
-    if coder == "huff":
-        esize = _huff_entropy_file(ctx, os.path.join(out_dir, "entropy.dat"), n, trailer, verbose)
+    if coder in ("huff", "huffr"):
+        esize = _huff_entropy_file(ctx, os.path.join(out_dir, "entropy.dat"), n, trailer, verbose, coder)
         if stages:
             stages.add("huffman coding + fetch entropy.dat", time.perf_counter() - t_e)
         return kf.result(), esize
@@ -357,7 +365,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     bound introduced, from the stored payload decoded on the device (tz_encode_quality) -- and print the worst error,
     the PSNR and the compression ratio.  Single-GPU jobs only.
     CODER (--coder; NOT in the reference): "zstd" writes the reference's entropy.dat; "huff" has the GPU Huffman-code the
-    payload (tezip_amd/huff.py) -- such a file is not readable by the reference; `-u` recognises it by its magic.
+    payload (tezip_amd/huff.py), "huffr" the same over literals and period-3 repeat tokens (tezip_amd/huffr.py) -- such a
+    file is not readable by the reference; `-u` recognises it by its magic.
     Single-GPU jobs only, not with SHUFFLE.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,

@@ -2130,8 +2130,8 @@ extern "C" int tz_window_sse(tz_ctx* ctx, const uint8_t* orig, const float* pred
 // levels on which its leaf is taken.  Leaves are merged in ascending (count, then descending symbol) order and a leaf goes
 // before a package of equal weight, so the result is a function of the counts alone, the taken leaves of a level are a
 // prefix of that order (lengths never increase with the count), and the code is complete (Kraft sum exactly 1).
-extern "C" int tz_huff_lengths(const unsigned long long* counts, int A, int max_len, uint8_t* lengths) {
-    if (!counts || !lengths || A < 1 || A > TZ_NBINS || max_len < 1 || max_len > 15) return TZ_ERR_INVALID;
+static int huff_package_merge(const unsigned long long* counts, int A, int max_a, int max_len, uint8_t* lengths) {
+    if (!counts || !lengths || A < 1 || A > max_a || max_len < 1 || max_len > 15) return TZ_ERR_INVALID;
     std::vector<int> sym;
     unsigned long long total = 0;
     for (int s = 0; s < A; ++s) {
@@ -2176,14 +2176,28 @@ extern "C" int tz_huff_lengths(const unsigned long long* counts, int A, int max_
     return TZ_OK;
 }
 
+extern "C" int tz_huff_lengths(const unsigned long long* counts, int A, int max_len, uint8_t* lengths) {
+    return huff_package_merge(counts, A, TZ_NBINS, max_len, lengths);
+}
+
+// the same over the symbols of a TZR1 code: `total` = literals + the TZ_HUFFR_NTOK repeat tokens behind them
+extern "C" int tz_huffr_lengths(const unsigned long long* counts, int total, int max_len, uint8_t* lengths) {
+    if (total <= TZ_HUFFR_NTOK) return TZ_ERR_INVALID;
+    return huff_package_merge(counts, total, TZ_NBINS + TZ_HUFFR_NTOK, max_len, lengths);
+}
+
 // The two tables of a code given by its lengths (canonical: shorter first, then by symbol; stored bit-reversed):
 // enc[s] = stored code | length << 12 (0: absent), dec[next 12 bits] = symbol | length << 12.  Checks everything a launch
-// depends on: A, base, lengths <= 12, at least one symbol, Kraft sum <= 1.
-static int huff_tables(tz_ctx* ctx, const uint8_t* lengths, int A, int base, std::vector<uint16_t>* enc, std::vector<uint16_t>* dec) {
+// depends on: A, base, lengths <= 12, at least one symbol, Kraft sum <= 1.  ntok > 0 (TZR1): `lengths` holds ntok more
+// symbols behind the A literals, the repeat tokens; A and base still describe the literals, one of which must be present.
+static int huff_tables(tz_ctx* ctx, const uint8_t* lengths, int A, int base, std::vector<uint16_t>* enc, std::vector<uint16_t>* dec,
+                       int ntok = 0) {
     if (!lengths || A < 1 || A > TZ_NBINS) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: alphabet size %d outside [1, %d]", A, TZ_NBINS);
     if (base < -32768 || base + A - 1 > 32767) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: base %d with %d symbols leaves int16", base, A);
     unsigned long long kraft = 0;
     int first = -1;
+    const int lits = A;
+    A += ntok;
     for (int s = 0; s < A; ++s) {
         if (lengths[s] > TZ_HUFF_L) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: code length %d of symbol %d exceeds %d", lengths[s], s, TZ_HUFF_L);
         if (lengths[s]) {
@@ -2191,7 +2205,7 @@ static int huff_tables(tz_ctx* ctx, const uint8_t* lengths, int A, int base, std
             if (first < 0) first = s;
         }
     }
-    if (first < 0) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: the code lengths name no symbol");
+    if (first < 0 || first >= lits) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: the code lengths name no symbol");
     if (kraft > (1ull << TZ_HUFF_L)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: Kraft sum of the code lengths exceeds 1");
     if (enc) enc->assign(A, 0);
     if (dec) dec->assign((size_t)1 << TZ_HUFF_L, (uint16_t)(first | (1 << 12)));   // unreachable entries: a valid symbol, length 1
@@ -2218,33 +2232,40 @@ static void huff_geometry(size_t n, size_t* nruns, size_t* nchunks, size_t* inde
 }
 
 // d_in (device, n int16) -> ctx->d_huff = index | bits; *bytes its size.  Waits once, for the size of the bit stream.
-static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uint8_t* lengths, int A, int base, size_t* bytes) {
+// tokens: the TZR1 stream (lengths holds A + TZ_HUFFR_NTOK entries, k_huffr_size / k_huffr_enc) instead of the TZH1 one.
+static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uint8_t* lengths, int A, int base, size_t* bytes,
+                           bool tokens = false) {
     if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
     std::vector<uint16_t> enc;
-    TZ_TRY(huff_tables(ctx, lengths, A, base, &enc, nullptr));
+    TZ_TRY(huff_tables(ctx, lengths, A, base, &enc, nullptr, tokens ? TZ_HUFFR_NTOK : 0));
     size_t nruns, nchunks, index_bytes;
     huff_geometry(n, &nruns, &nchunks, &index_bytes);
     void *d_enc, *d_idx, *d_meta;
-    TZ_TRY(tz_pool_alloc(ctx, (size_t)A * 2, &d_enc));
+    TZ_TRY(tz_pool_alloc(ctx, enc.size() * 2, &d_enc));
     TZ_TRY(tz_pool_alloc(ctx, index_bytes, &d_idx));
     TZ_TRY(tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta));
-    TZ_TRY(tz_upload(ctx, d_enc, enc.data(), (size_t)A * 2));
+    TZ_TRY(tz_upload(ctx, d_enc, enc.data(), enc.size() * 2));
     TZ_HIP(ctx, hipMemsetAsync(d_idx, 0, index_bytes, ctx->stream));   // (the padding behind an odd number of run sizes is part of the file)
     unsigned* d_chunk_off = (unsigned*)d_idx;
     uint16_t* d_run_bits = (uint16_t*)((uint8_t*)d_idx + nchunks * 4);
-    TZ_TRY(tzk_huff_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta));
+    if (tokens) TZ_TRY(tzk_huffr_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta));
+    else TZ_TRY(tzk_huff_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta));
     tz_huff_meta meta;
     TZ_TRY(tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream));
     TZ_TRY(tz_stream_sync(ctx));
     if (meta.bad) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: the payload holds a value the code lengths give no code");
     if (meta.total_words >= (1ull << 32)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: a bit stream of %llu words does not fit the format", meta.total_words);
     const size_t total = index_bytes + (size_t)meta.total_words * 4;
-    ctx->huff_n = 0;   // (a staged decoder stream, if any, is gone)
+    ctx->huff_n = ctx->huffr_n = 0;   // (a staged decoder stream, if any, is gone)
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, total));
     ctx->huff_bytes = total;
     TZ_HIP(ctx, hipMemcpyAsync(ctx->d_huff, d_idx, index_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(ctx->d_huff + index_bytes),
-                        (size_t)meta.total_words));
+    if (tokens)
+        TZ_TRY(tzk_huffr_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(ctx->d_huff + index_bytes),
+                             (size_t)meta.total_words));
+    else
+        TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(ctx->d_huff + index_bytes),
+                            (size_t)meta.total_words));
     *bytes = total;
     return TZ_OK;
 }
@@ -2314,7 +2335,7 @@ extern "C" int tz_huff_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t*
     TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
     std::vector<uint16_t> dec;
     TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec));
-    ctx->huff_n = 0;
+    ctx->huff_n = ctx->huffr_n = 0;
     ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload is about to receive the expanded stream
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, std::max<size_t>(bytes, 16)));
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, std::max<size_t>(n, 8) * 2));
@@ -2400,6 +2421,163 @@ extern "C" int tz_huff_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t byt
     }
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// --------------------------------------------------------------------------- Huffman coder with repeat tokens (TZR1)
+// `--coder huffr`: the entry points above, one by one, for the stream whose runs are tokenised first (tezip_amd/huffr.py,
+// k_huffr_* in tz_codec.hip).  A code has A literals and TZ_HUFFR_NTOK repeat tokens, so `lengths` holds A + 8 bytes here.
+// The resident stream buffer and the index layout are the Huffman coder's.
+static int huffr_counts_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, unsigned long long* counts, int* A, int* base) {
+    void *d_hist, *d_meta;
+    std::vector<unsigned long long> h(TZ_HUFF_COUNT_BINS + TZ_HUFFR_NTOK);
+    tz_huff_meta meta;
+    int rc = tz_pool_alloc(ctx, h.size() * sizeof(unsigned long long), &d_hist);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta);
+    if (rc == TZ_OK) rc = tzk_huffr_count(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
+    if (rc == TZ_OK) rc = tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream);
+    if (rc == TZ_OK) rc = tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
+    TZ_TRY(rc);
+    int lo = -1, hi = -1;   // (every value of a run is a literal at its first occurrence there: the literals span the values)
+    for (int b = 0; b < TZ_HUFF_COUNT_BINS; ++b)
+        if (h[b]) {
+            if (lo < 0) lo = b;
+            hi = b;
+        }
+    if (meta.bad || lo < 0 || hi - lo + 1 > TZ_NBINS)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_huffr_counts: the payload's values span more than %d symbols", TZ_NBINS);
+    const int a = hi - lo + 1;
+    for (int s = 0; s < TZ_NBINS + TZ_HUFFR_NTOK; ++s) counts[s] = s < a ? h[lo + s] : s < a + TZ_HUFFR_NTOK ? h[TZ_HUFF_COUNT_BINS + s - a] : 0;
+    *A = a;
+    *base = lo - TZ_HUFF_COUNT_BIAS;
+    return TZ_OK;
+}
+
+extern "C" int tz_huffr_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
+    tz_roctx_range roctx_("tz_huffr_counts");
+    if (!ctx || !counts || !A || !base) return TZ_ERR_INVALID;
+    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huffr_counts needs a resident payload (tz_encode with payload == NULL)");
+    const int rc = huffr_counts_dev(ctx, ctx->d_payload, ctx->payload_len, counts, A, base);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_huffr_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes) {
+    tz_roctx_range roctx_("tz_huffr_encode");
+    if (!ctx || !bytes) return TZ_ERR_INVALID;
+    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huffr_encode needs a resident payload (tz_encode with payload == NULL)");
+    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes, true);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_huffr_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) { return tz_huff_get(ctx, offset, count, out); }
+
+extern "C" int tz_huffr_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
+    if (!ctx) return TZ_ERR_INVALID;
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
+    std::vector<uint16_t> dec;
+    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, TZ_HUFFR_NTOK));
+    ctx->huff_n = ctx->huffr_n = 0;
+    ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload is about to receive the expanded stream
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, std::max<size_t>(bytes, 16)));
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, std::max<size_t>(n, 8) * 2));
+    ctx->payload_len = 0;
+    ctx->huff_bytes = bytes;
+    ctx->huff_dec_tab.swap(dec);
+    ctx->huff_base = base;
+    ctx->huffr_A = A;
+    ctx->huffr_n = n;
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
+    return TZ_OK;
+}
+
+extern "C" int tz_huffr_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
+    if (!ctx || !src) return TZ_ERR_INVALID;
+    if (!ctx->d_huff || !ctx->huffr_n || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged Huffman stream");
+    return tz_h2d(ctx, ctx->d_huff + offset, src, count, ctx->copy_stream);
+}
+
+static int huffr_decode_dev(tz_ctx* ctx, const uint8_t* d_stream, size_t stream_words, size_t n, const std::vector<uint16_t>& dec, int A,
+                            int base, int16_t* d_out) {
+    size_t nruns, nchunks, index_bytes;
+    huff_geometry(n, &nruns, &nchunks, &index_bytes);
+    void* d_dec;
+    TZ_TRY(tz_pool_alloc(ctx, dec.size() * 2, &d_dec));
+    TZ_TRY(tz_upload(ctx, d_dec, dec.data(), dec.size() * 2));
+    return tzk_huffr_dec(ctx, (const unsigned*)d_stream, (const uint16_t*)(d_stream + nchunks * 4), (const unsigned*)(d_stream + index_bytes),
+                         stream_words, (const uint16_t*)d_dec, A, base, n, d_out);
+}
+
+extern "C" int tz_huffr_decode(tz_ctx* ctx) {
+    tz_roctx_range roctx_("tz_huffr_decode");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (!ctx->huffr_n || !ctx->d_huff || !ctx->d_payload || ctx->cap_payload < ctx->huffr_n * 2)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_huffr_decode needs a stream staged with tz_huffr_begin / tz_huffr_put");
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, ctx->huff_bytes, ctx->huffr_n, TZ_HUFF_RUN, &sw));
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of tz_huffr_put
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
+    const int rc = huffr_decode_dev(ctx, ctx->d_huff, sw, ctx->huffr_n, ctx->huff_dec_tab, ctx->huffr_A, ctx->huff_base, ctx->d_payload);
+    if (rc == TZ_OK) ctx->payload_len = ctx->huffr_n;   // exactly as if tz_payload_begin / tz_payload_put had staged them
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_huffr_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
+                                   size_t capacity, size_t* bytes) {
+    if (!ctx || !in || !out || !bytes) return TZ_ERR_INVALID;
+    const void* din = nullptr;
+    int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes, true);
+    if (rc == TZ_OK && *bytes > capacity) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: the stream needs %zu bytes, the buffer holds %zu", *bytes, capacity);
+    if (rc == TZ_OK) {
+        if (tz_is_device_ptr(out)) {
+            hipError_t e = hipMemcpyAsync(out, ctx->d_huff, *bytes, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "stream copy: %s", hipGetErrorString(e));
+        } else {
+            rc = tz_d2h(ctx, out, ctx->d_huff, *bytes, ctx->stream);
+        }
+    }
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_huffr_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
+                                   int16_t* out) {
+    if (!ctx || !stream || !out) return TZ_ERR_INVALID;
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
+    std::vector<uint16_t> dec;
+    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, TZ_HUFFR_NTOK));
+    const void* din = nullptr;
+    tz_out o;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, stream, bytes, &din);
+    if (rc == TZ_OK && ((uintptr_t)din & 3)) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: a device stream must be 4-byte aligned");
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
+    if (rc == TZ_OK) {
+        outs.push_back(o);
+        rc = huffr_decode_dev(ctx, (const uint8_t*)din, sw, n, dec, A, base, (int16_t*)o.dev);
+    }
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// the counts of a stand-alone host or device array, as tz_huffr_counts gives them for the resident payload
+extern "C" int tz_huffr_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* counts, int* A, int* base) {
+    if (!ctx || !in || !counts || !A || !base) return TZ_ERR_INVALID;
+    const void* din = nullptr;
+    int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    if (rc == TZ_OK) rc = huffr_counts_dev(ctx, (const int16_t*)din, n, counts, A, base);
     tz_pool_release_all(ctx);
     return rc;
 }

@@ -2829,3 +2829,285 @@ int tzk_huff_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
+
+// ---------------------------------------------------------------------------- Huffman coder with repeat tokens
+// Opt-in stage `--coder huffr` (format TZR1: DESIGN.md section 9, tezip_amd/huffr.py is the slow statement of it).  The
+// geometry is the Huffman coder's above -- a lane owns a run of 256 payload elements, a wave a chunk of 64 runs that starts
+// on a word -- but a lane no longer codes one symbol per element: element j of a run MATCHES when j >= 3 and
+// s[j] == s[j - 3] (the payload interleaves three channels, so a quantiser run repeats with period 3), every maximal
+// stretch of m matches becomes the token T_k = symbol A + k, k = floor(log2 m), followed by k raw bits m - 2^k, and the
+// other elements are literals.  The three encoder passes share ONE walk of a run (hfr_walk), so the histogram, the sizes
+// and the packed bits cannot disagree about the tokens.  The walk is uniform over the lanes of a wave: every lane takes
+// one element per step, and what a step emits is predicated.
+static constexpr int HFR_NTOK = TZ_HUFFR_NTOK, HFR_DIST = 3;
+static constexpr int HFR_ENC_PAD = (TZ_NBINS + HFR_NTOK + 7) & ~7;
+
+// Walks the run of `cnt` elements at r0.  f(m, lit, s) is called once per element and once behind the run: m > 0 is a
+// stretch of m matches that ended in front of this point (to be coded first), lit says the element s is a literal.
+template <bool VEC, class F>
+__device__ __forceinline__ void hfr_walk(const int16_t* __restrict__ in, size_t n, size_t r0, int cnt, F&& f) {
+    int h1 = 0, h2 = 0, h3 = 0, m = 0;
+    for (int j = 0; j < cnt; j += 8) {
+        const short8 v = hf_load8<VEC>(in, r0 + j, n, (short)0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int s = v[k];
+            const bool live = j + k < cnt, match = live && j + k >= HFR_DIST && s == h3, lit = live && !match;
+            f(lit ? m : 0, lit, s);
+            m = match ? m + 1 : (lit ? 0 : m);
+            h3 = h2;
+            h2 = h1;
+            h1 = s;
+        }
+    }
+    f(m, false, 0);   // the stretch the run's end cuts
+}
+
+// Token counts of the payload: bins [0, 4096) are the literals (bin = value + TZ_HUFF_COUNT_BIAS; a literal outside sets
+// meta->bad), bins 4096 + k the tokens T_k.  One thread per run, the histogram of a workgroup in LDS.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_huffr_count(const int16_t* __restrict__ in, size_t n, size_t nruns, unsigned long long* __restrict__ hist,
+                                                     tz_huff_meta* __restrict__ meta) {
+    __shared__ unsigned h[TZ_HUFF_COUNT_BINS + HFR_NTOK];
+    for (int k = threadIdx.x; k < TZ_HUFF_COUNT_BINS + HFR_NTOK; k += 256) h[k] = 0;
+    __syncthreads();
+    bool bad = false;
+    for (size_t run = (size_t)blockIdx.x * 256 + threadIdx.x; run < nruns; run += (size_t)gridDim.x * 256) {
+        const size_t r0 = run * HF_R;
+        hfr_walk<VEC>(in, n, r0, (int)std::min((size_t)HF_R, n - r0), [&](int m, bool lit, int s) {
+            if (m) atomicAdd(&h[TZ_HUFF_COUNT_BINS + (31 - __clz(m))], 1u);
+            if (lit) {
+                const int b = s + TZ_HUFF_COUNT_BIAS;
+                if (b >= 0 && b < TZ_HUFF_COUNT_BINS) atomicAdd(&h[b], 1u);
+                else bad = true;
+            }
+        });
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < TZ_HUFF_COUNT_BINS + HFR_NTOK; k += 256)
+        if (h[k]) atomicAdd(&hist[k], (unsigned long long)h[k]);
+    if (bad) atomicOr(&meta->bad, 1u);
+}
+
+int tzk_huffr_count(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* d_hist, tz_huff_meta* d_meta) {
+    const size_t nruns = (n + HF_R - 1) / HF_R;
+    TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, (TZ_HUFF_COUNT_BINS + HFR_NTOK) * sizeof(unsigned long long), ctx->stream));
+    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    const dim3 grid((unsigned)std::min((nruns + 255) / 256, (size_t)2048));
+    if ((uintptr_t)in & 15) hipLaunchKernelGGL(k_huffr_count<false>, grid, dim3(256), 0, ctx->stream, in, n, nruns, d_hist, d_meta);
+    else hipLaunchKernelGGL(k_huffr_count<true>, grid, dim3(256), 0, ctx->stream, in, n, nruns, d_hist, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// Size pass: one wave per chunk, four chunks per workgroup; a lane sums the bits of its run (code lengths of its literals
+// and tokens plus the raw bits), run_bits[r] is the index's entry of run r, chunk_bits[c] feeds k_huff_scan.  `enc` holds
+// A + 8 entries: the literals, then T_0..T_7.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_huffr_size(const int16_t* __restrict__ in, size_t n, const uint16_t* __restrict__ enc, int A,
+                                                    int base, size_t nruns, size_t nchunks, uint16_t* __restrict__ run_bits,
+                                                    unsigned* __restrict__ chunk_bits, tz_huff_meta* __restrict__ meta) {
+    __shared__ uint8_t len[HFR_ENC_PAD];
+    for (int k = threadIdx.x; k < HFR_ENC_PAD; k += 256) len[k] = k < A + HFR_NTOK ? (uint8_t)(enc[k] >> 12) : 0;
+    __syncthreads();
+    const size_t chunk = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (chunk >= nchunks) return;
+    const int lane = threadIdx.x & 63;
+    const size_t run = chunk * HF_CR + lane, r0 = run * HF_R;
+    unsigned bits = 0;
+    bool bad = false;
+    if (run < nruns)
+        hfr_walk<VEC>(in, n, r0, (int)std::min((size_t)HF_R, n - r0), [&](int m, bool lit, int s) {
+            if (m) {
+                const int k = 31 - __clz(m);
+                const unsigned l = len[A + k];
+                bits += l + k;
+                bad |= l == 0;
+            }
+            if (lit) {
+                const unsigned sym = (unsigned)(s - base);
+                const unsigned l = sym < (unsigned)A ? len[sym] : 0u;
+                bits += l;
+                bad |= l == 0;
+            }
+        });
+    if (run < nruns) run_bits[run] = (uint16_t)bits;
+    unsigned tot = bits;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d, 64);
+    if (lane == 0) chunk_bits[chunk] = tot;
+    if (bad) atomicOr(&meta->bad, 1u);
+}
+
+int tzk_huffr_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
+                   unsigned* d_chunk_off, tz_huff_meta* d_meta) {
+    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
+    void* d_cbits;
+    TZ_TRY(tz_pool_alloc(ctx, nchunks * sizeof(unsigned), &d_cbits));
+    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    const dim3 grid((unsigned)((nchunks + 3) / 4));
+    if ((uintptr_t)in & 15)
+        hipLaunchKernelGGL(k_huffr_size<false>, grid, dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
+                           (unsigned*)d_cbits, d_meta);
+    else
+        hipLaunchKernelGGL(k_huffr_size<true>, grid, dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
+                           (unsigned*)d_cbits, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_huff_scan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)d_cbits, nchunks, d_chunk_off, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// Pack pass: k_huff_enc's scheme (one wave per chunk, 64-bit accumulator per lane, whole words ORed into the chunk's image
+// in LDS, coalesced stores of the image, no global atomics) over the tokens of hfr_walk.  A step appends at most a token
+// with its raw bits and a literal: 12 + 7 + 12 bits on top of fewer than 32, so the accumulator holds them.
+template <bool VEC>
+__global__ __launch_bounds__(64) void k_huffr_enc(const int16_t* __restrict__ in, size_t n, const uint16_t* __restrict__ enc, int A, int base,
+                                                  size_t nruns, const uint16_t* __restrict__ run_bits, const unsigned* __restrict__ chunk_off,
+                                                  unsigned* __restrict__ words, size_t stream_words) {
+    __shared__ uint16_t tab[HFR_ENC_PAD];
+    __shared__ unsigned img[HF_CHUNK_WORDS];
+    const int lane = threadIdx.x;
+    const size_t chunk = blockIdx.x, run = chunk * HF_CR + lane;
+    for (int k = lane; k < HFR_ENC_PAD; k += 64) tab[k] = k < A + HFR_NTOK ? enc[k] : (uint16_t)0;
+    unsigned tot;
+    const unsigned pos = hf_wave_excl(run < nruns ? (unsigned)run_bits[run] : 0u, &tot);
+    const unsigned cw = std::min((tot + 31u) >> 5, (unsigned)HF_CHUNK_WORDS);
+    for (unsigned k = lane; k < cw; k += 64) img[k] = 0;
+    __syncthreads();
+    const size_t r0 = run * HF_R;
+    const int cnt = r0 < n ? (int)std::min((size_t)HF_R, n - r0) : 0;
+    unsigned long long acc = 0;
+    unsigned nb = pos & 31u, wi = pos >> 5;
+    hfr_walk<VEC>(in, n, r0, cnt, [&](int m, bool lit, int s) {
+        if (m) {
+            const int k = 31 - __clz(m);
+            const unsigned e = tab[A + k];            // (no code: k_huffr_size said so, and the host launched nothing)
+            acc |= (unsigned long long)((e & 0xFFFu) | ((unsigned)(m - (1 << k)) << (e >> 12))) << nb;
+            nb += (e >> 12) + k;
+        }
+        if (lit) {
+            const unsigned sym = (unsigned)(s - base);
+            const unsigned e = sym < (unsigned)A ? tab[sym] : 0u;
+            acc |= (unsigned long long)(e & 0xFFFu) << nb;
+            nb += e >> 12;
+        }
+        if (nb >= 32) {
+            if (wi < cw) atomicOr(&img[wi], (unsigned)acc);
+            ++wi;
+            acc >>= 32;
+            nb -= 32;
+        }
+    });
+    if (nb > 0 && wi < cw) atomicOr(&img[wi], (unsigned)acc);
+    __syncthreads();
+    const size_t w0 = chunk_off[chunk];
+    for (unsigned k = lane; k < cw; k += 64)
+        if (w0 + k < stream_words) words[w0 + k] = img[k];
+}
+
+int tzk_huffr_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
+                  const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words) {
+    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    if ((uintptr_t)in & 15)
+        hipLaunchKernelGGL(k_huffr_enc<false>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits,
+                           d_chunk_off, d_words, stream_words);
+    else
+        hipLaunchKernelGGL(k_huffr_enc<true>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits,
+                           d_chunk_off, d_words, stream_words);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// Expand pass: k_huff_dec's scheme and clamps (chunk offsets to the stream, staged words to the image, reads of the image
+// to its end, run sizes to R * L, a lane stops after its run's element count, which comes from n alone).  Every lane
+// produces one element per step: inside a stretch it copies the element three back, which it holds in registers (the
+// history in front of a run is three times `base`); otherwise it looks up a symbol, and a token >= A starts a stretch of
+// 2^k + k raw bits elements whose first one is this step's.  A stretch ends with the run, whatever its token says.  After
+// a refill the accumulator holds more than 32 valid bits and a step takes at most 12 + 7, so a corrupt body yields wrong
+// elements, never an access outside the buffers.
+template <bool VEC>
+__global__ __launch_bounds__(64) void k_huffr_dec(const unsigned* __restrict__ chunk_off, const uint16_t* __restrict__ run_bits,
+                                                  const unsigned* __restrict__ words, size_t stream_words, size_t nruns, size_t nchunks,
+                                                  const uint16_t* __restrict__ dec, int A, int base, size_t n, int16_t* __restrict__ out) {
+    __shared__ uint16_t tab[1 << HF_L];
+    __shared__ unsigned img[HF_CHUNK_WORDS + 1];
+    const int lane = threadIdx.x;
+    const size_t chunk = blockIdx.x, run = chunk * HF_CR + lane;
+    for (int k = lane; k < (1 << HF_L) / 8; k += 64) ((uint4*)tab)[k] = ((const uint4*)dec)[k];
+    const size_t w0 = std::min((size_t)chunk_off[chunk], stream_words);
+    const size_t w1 = chunk + 1 < nchunks ? std::min((size_t)chunk_off[chunk + 1], stream_words) : stream_words;
+    const unsigned cw = w1 > w0 ? (unsigned)std::min(w1 - w0, (size_t)HF_CHUNK_WORDS) : 0u;
+    for (unsigned k = lane; k < cw; k += 64) img[k] = words[w0 + k];
+    if (lane == 0) img[cw] = 0;
+    unsigned tot;
+    const unsigned pos = hf_wave_excl(run < nruns ? std::min((unsigned)run_bits[run], (unsigned)(HF_R * HF_L)) : 0u, &tot);
+    __syncthreads();
+    const size_t r0 = run * HF_R;
+    const int cnt = r0 < n ? (int)std::min((size_t)HF_R, n - r0) : 0;
+    unsigned wi = pos >> 5;
+    unsigned long long acc = (unsigned long long)img[std::min(wi, cw)] >> (pos & 31u);
+    unsigned nb = 32u - (pos & 31u);
+    ++wi;
+    acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
+    nb += 32;
+    ++wi;
+    int h1 = base, h2 = base, h3 = base;
+    unsigned m = 0;
+    for (int j = 0; j < cnt; j += 8) {
+        short8 v;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            int val = h3;
+            if (m == 0) {
+                const unsigned e = tab[(unsigned)acc & 0xFFFu];
+                const unsigned l = e >> 12, sym = e & 0xFFFu;
+                acc >>= l;
+                nb -= l;
+                if (sym < (unsigned)A) {
+                    val = (int)sym + base;
+                    m = 1;
+                } else {
+                    const unsigned tk = std::min(sym - (unsigned)A, (unsigned)(HFR_NTOK - 1));
+                    m = (1u << tk) + ((unsigned)acc & ((1u << tk) - 1u));
+                    acc >>= tk;
+                    nb -= tk;
+                }
+                if (nb <= 32) {
+                    acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
+                    nb += 32;
+                    ++wi;
+                }
+            }
+            --m;
+            v[k] = (short)val;
+            h3 = h2;
+            h2 = h1;
+            h1 = val;
+        }
+        if (VEC && j + 8 <= cnt) {
+            *(short8*)(out + r0 + j) = v;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (j + k < cnt) out[r0 + j + k] = v[k];
+        }
+    }
+}
+
+int tzk_huffr_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
+                  const uint16_t* d_dec, int A, int base, size_t n, int16_t* out) {
+    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    if ((uintptr_t)out & 15)
+        hipLaunchKernelGGL(k_huffr_dec<false>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words,
+                           nruns, nchunks, d_dec, A, base, n, out);
+    else
+        hipLaunchKernelGGL(k_huffr_dec<true>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words,
+                           nruns, nchunks, d_dec, A, base, n, out);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}

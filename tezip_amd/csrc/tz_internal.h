@@ -33,7 +33,7 @@ enum tz_prof_class {
     TZP_QSERIAL,    // not a time: `launches` counts the chains the quantiser sent through its serial fallback (k_q_serial)
     TZP_CARRY,      // prefix carry of the inverse scan (k_undelta_carry, tz_decode_range)
     TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality)
-    TZP_HUFF,       // opt-in Huffman coder: k_huff_count / k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec
+    TZP_HUFF,       // opt-in Huffman coder: k_huff_count / k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec (and k_huffr_*)
     TZP_COUNT
 };
 
@@ -131,6 +131,10 @@ struct tz_ctx {
     size_t huff_n = 0;                      // tz_huff_begin: elements the staged stream decodes to (0: nothing staged)
     int huff_base = 0;
     std::vector<uint16_t> huff_dec_tab;     // tz_huff_begin: the 2^12-entry decode table of the staged stream's lengths
+    // tz_huffr_begin stages a TZR1 stream in the same buffers (d_huff, huff_bytes, huff_base, huff_dec_tab) and sets these
+    // instead of huff_n, so that neither decoder expands the other's stream
+    size_t huffr_n = 0;
+    int huffr_A = 0;                        // literals of the staged TZR1 code (symbols A..A + 7 are its repeat tokens)
     uint8_t* d_out = nullptr;               // resident decoded frames of a tz_decode(frames_out = NULL)
     size_t cap_out = 0;
     bool have_decoded = false;
@@ -311,6 +315,15 @@ int tzk_huff_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, in
                  const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words);
 int tzk_huff_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
                  const uint16_t* d_dec_tab4096, int base, size_t n, int16_t* out);
+// Huffman coder with repeat tokens (TZR1): the same geometry and index; a code has A literals and then
+// TZ_HUFFR_NTOK repeat tokens, so d_enc holds A + 8 entries and the histogram TZ_HUFF_COUNT_BINS + 8 bins.
+int tzk_huffr_count(tz_ctx*, const int16_t* in, size_t n, unsigned long long* d_hist4104, tz_huff_meta* d_meta);
+int tzk_huffr_size(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
+                   unsigned* d_chunk_off, tz_huff_meta* d_meta);
+int tzk_huffr_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
+                  const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words);
+int tzk_huffr_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
+                  const uint16_t* d_dec_tab4096, int A, int base, size_t n, int16_t* out);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,
             double* h_sse);
 int tzk_sse_blocks(int Hp, int Wp);

@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from . import _lib, huff, sidecar, zstd
+from . import _lib, huff, huffr, sidecar, zstd
 from . import dist as tzdist
 from .compress import SHUFFLE_MARK, make_context, open_model
 from .data_utils import padding_shape
@@ -47,6 +47,23 @@ def check_stream(shape, warm_up, payload_len, key_len):
 
 
 TAIL_ELEMS = _lib.TZ_NBINS + 8  # the longest trailer: table (<= 2111 symbols) + T + shape(5) + warm_up
+
+
+def coded_format(head):
+    """The module of this build's opt-in entropy.dat formats the first bytes of a file name (huff: TZH1, huffr: TZR1), or
+    None for the reference's zstd frame."""
+    if huff.is_huff(head):
+        return huff
+    if huffr.is_huffr(head):
+        return huffr
+    return None
+
+
+def coded_calls(ctx, coded):
+    """(begin, put, decode) of the context for a parsed TZH1 / TZR1 file."""
+    if isinstance(coded, huffr.Parsed):
+        return ctx.huffr_begin, ctx.huffr_put, ctx.huffr_decode
+    return ctx.huff_begin, ctx.huff_put, ctx.huff_decode
 
 
 def adopt_contract(DATA_DIR, wts, VERBOSE):
@@ -195,10 +212,12 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
 
         with open(paths["entropy.dat"], "rb") as f:
             ent_head = f.read(64)
-        if huff.is_huff(ent_head):
+        fmt = coded_format(ent_head)
+        if fmt is not None:
             # this build's opt-in Huffman file: everything the decoder needs stands in FRONT of the bit stream, so the
-            # whole file is validated on the CPU (huff.parse) before anything is staged, and the rollout is queued first
-            coded = huff.parse(np.fromfile(paths["entropy.dat"], np.uint8), key_len)
+            # whole file is validated on the CPU (huff.parse / huffr.parse) before anything is staged, and the rollout is
+            # queued first
+            coded = fmt.parse(np.fromfile(paths["entropy.dat"], np.uint8), key_len)
             table, warm_up = coded.table, coded.warm_up
             _, nt, H, W, C = coded.shape
             if stack is not None and key_len == stack[0] * stack[1] * stack[2] * 3 and len(file_names) == stack[0] \
@@ -208,13 +227,14 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             if frames is not None:
                 check_frames(frames, nt)
             hp, wp = checks(nt, H, W)
-            ctx.huff_begin(coded.body.size, coded.n, coded.lengths, coded.base, coded.run)
+            begin, put, expand = coded_calls(ctx, coded)
+            begin(coded.body.size, coded.n, coded.lengths, coded.base, coded.run)
             per = stage_keys(nt, H, W, hp, wp)
             rollout(nt, warm_up)
             stages.mark("rollout (decoder) queued")
             for off in range(0, coded.body.size, 16 << 20):
-                ctx.huff_put(off, coded.body[off: off + (16 << 20)])   # pageable: the piece is free again on return
-            ctx.huff_decode()                                           # -> the payload buffer, as payload_put leaves it
+                put(off, coded.body[off: off + (16 << 20)])             # pageable: the piece is free again on return
+            expand()                                                    # -> the payload buffer, as payload_put leaves it
             stages.mark("stage entropy.dat + huffman decode", ctx)
         else:
             with open(paths["entropy.dat"], "rb") as f:
@@ -369,8 +389,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
     coded = None
     try:
         with open(os.path.join(DATA_DIR, "entropy.dat"), mode='rb') as f:
-            if huff.is_huff(f.read(4)):   # this build's opt-in Huffman file: validated here, expanded on the device below
-                coded = huff.parse(np.fromfile(os.path.join(DATA_DIR, "entropy.dat"), np.uint8), len(key_bytes))
+            fmt = coded_format(f.read(4))
+            if fmt is not None:           # this build's opt-in Huffman file: validated here, expanded on the device below
+                coded = fmt.parse(np.fromfile(os.path.join(DATA_DIR, "entropy.dat"), np.uint8), len(key_bytes))
     except FileNotFoundError:
         pass   # (read() below prints the reference's message)
     if coded is not None:
@@ -420,9 +441,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
             if coded is not None:
-                ctx.huff_begin(coded.body.size, coded.n, coded.lengths, coded.base, coded.run)
-                ctx.huff_put(0, np.ascontiguousarray(coded.body))
-                ctx.huff_decode()
+                begin, put, expand = coded_calls(ctx, coded)
+                begin(coded.body.size, coded.n, coded.lengths, coded.base, coded.run)
+                put(0, np.ascontiguousarray(coded.body))
+                expand()
             frames = ctx.decode_range(None if coded is not None else np.ascontiguousarray(payload), tb, first, end - first)
             if VERBOSE:
                 prof = ctx.prof_get()

@@ -46,8 +46,9 @@ FLAG_TABLE = (
     # sequence, from the stored payload decoded on the GPU) and print max_abs_err / PSNR / ratio (compress.run(REPORT=...))
     (None, "--report", dict(action="store_true", dest="report")),
     # not in the reference: with -c, the coder of entropy.dat.  zstd = the reference's file; huff = canonical Huffman codes
-    # written by the GPU (tezip_amd/huff.py; the reference cannot read such a file, -u recognises it by its magic)
-    (None, "--coder", dict(type=str, choices=("zstd", "huff"), default="zstd", dest="coder")),
+    # written by the GPU (tezip_amd/huff.py; the reference cannot read such a file, -u recognises it by its magic); huffr = the
+    # same with repeat tokens for the payload's period-3 runs (tezip_amd/huffr.py), a smaller file under an error bound
+    (None, "--coder", dict(type=str, choices=("zstd", "huff", "huffr"), default="zstd", dest="coder")),
 )
 
 TEXT = {
@@ -123,14 +124,14 @@ def check_report_flag(arg):
 
 
 def check_coder_flag(arg):
-    """--coder huff is valid with -c of one single-GPU job, without --shuffle and --sweep.  Returns None, or the message
+    """--coder huff / huffr is valid with -c of one single-GPU job, without --shuffle and --sweep.  Returns None, or the message
     of a refusal."""
     if getattr(arg, "coder", "zstd") == "zstd":
         return None
     if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
         return "--coder is valid with -c (--compress) only (-u recognises the coder of a file by itself)"
     if getattr(arg, "sweep", None) is not None:
-        return "--coder huff cannot be combined with --sweep"
+        return "--coder %s cannot be combined with --sweep" % arg.coder
     return compress.check_coder(arg.coder, arg.shuffle, int(os.environ.get("WORLD_SIZE", "1")) > 1)
 
 
