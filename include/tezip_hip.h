@@ -393,6 +393,34 @@ int tz_huffr_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t*
 int tz_huffr_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base,
                         int R, int16_t* out);
 
+/* ---- opt-in key-frame coder (`tezip.py -c --key-coder huff`, format TZK1 in DESIGN.md section 9, slow statement of it in
+ * tezip_amd/keycoder.py; no reference counterpart: compress.py:271-278 hands a zero-except-keys stack to zstd) -----------------
+ * Only the key frames are stored: each as the residuals mod 256 of one of four predictors over its own samples (0: none,
+ * 1: left neighbour, 2: upper neighbour, 3: left + up - upleft; same channel, 0 outside the frame), all of them under one
+ * canonical Huffman code of 256 symbols (`lengths`, as tz_huff_*; index | bits as there).  idx: nkeys >= 1 frame indices,
+ * strictly ascending inside the stack; pred: nkeys predictor ids 0..3.  TZ_ERR_INVALID for anything else, for a bad code and
+ * for a stream size that cannot hold nkeys * H * W * 3 symbols.  The coder keeps a stream and a symbol buffer of its own:
+ * what tz_huff_* / tz_huffr_* hold or have staged is left as it is.
+ * Encoder, on the frame stack resident after tz_frames_put or tz_rollout (TZ_ERR_STATE without one):
+ * tz_keys_counts: counts[nkeys][4][256] (host) of the residual values of every key frame under every predictor, from one
+ * read of the key frames (k_key_hist); the caller chooses the predictors and the code from them. */
+int tz_keys_counts(tz_ctx* ctx, const int* idx, int nkeys, unsigned* counts);
+/* Codes the key frames into a context-resident stream; *bytes receives its size, tz_keys_get fetches it in pieces. */
+int tz_keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths, size_t* bytes);
+int tz_keys_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out);
+/* Decoder: begin, then put for any partition of [0, bytes) on the copy stream, then tz_keys_decode, which leaves the context's
+ * frame stack exactly as tz_frames_begin(nt, H, W) and tz_frames_put of the whole zero-except-keys stack leave it (the other
+ * frames are zeroed): tz_frames_get, tz_rollout_decode(NULL, ...) and tz_rollout_decode_range(NULL, ...) run unchanged.
+ * TZ_ERR_STATE when tz_keys_decode runs before every byte was put.  The caller validates the index
+ * (tezip_amd/keycoder.py: parse); the kernels clamp as tz_huff_decode's do. */
+int tz_keys_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* pred,
+                  const uint8_t* lengths);
+int tz_keys_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src);
+int tz_keys_decode(tz_ctx* ctx);
+/* Stand-alone forms on host or device arrays: frames (k, H, W, 3) <-> k * H * W * 3 int16 symbols 0..255, pred[k] per frame. */
+int tz_keys_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* pred, int16_t* sym);
+int tz_keys_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* pred, uint8_t* frames);
+
 /* ---- timing helper: HIP events on the context's stream (bench.py) -------------------------- */
 int tz_timer_start(tz_ctx* ctx);
 int tz_timer_stop(tz_ctx* ctx, float* ms);

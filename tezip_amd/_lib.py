@@ -111,6 +111,14 @@ _SIGS = {
                                       C.POINTER(C.c_size_t)]),
     "tz_huffr_decode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p]),
+    "tz_keys_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "tz_keys_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "tz_keys_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_keys_begin": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_keys_put": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_keys_decode": (C.c_int, [C.c_void_p]),
+    "tz_keys_residual_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_keys_unresidual_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tz_timer_start": (C.c_int, [C.c_void_p]),
     "tz_timer_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "tz_prof_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -681,6 +689,67 @@ class Context:
             out = np.empty(n, np.int16)
         self._ck(self.lib.tz_huff_decode_buf(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size), int(base),
                                              int(run), _ptr(out)))
+        return out
+
+    # ---- opt-in key-frame coder (tz_keys_*; format: tezip_amd/keycoder.py)
+    def keys_counts(self, idx):
+        """Counts of the residual values of the resident stack's frames `idx` under the four predictors -> uint32[k][4][256]."""
+        ix = np.ascontiguousarray(idx, np.int32)
+        counts = np.zeros((ix.size, 4, 256), np.uint32)
+        self._ck(self.lib.tz_keys_counts(self.h, ix.ctypes.data, int(ix.size), counts.ctypes.data))
+        return counts
+
+    def keys_encode(self, idx, pred, lengths):
+        """Code the frames `idx` of the resident stack into the resident key stream (index | bits); returns its size."""
+        ix, pr, ln = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(pred, np.uint8), np.ascontiguousarray(lengths, np.uint8)
+        if pr.size != ix.size or ln.size != 256:
+            raise ValueError("%d predictor ids for %d key frames, %d code lengths (256 wanted)" % (pr.size, ix.size, ln.size))
+        nbytes = C.c_size_t(0)
+        self._ck(self.lib.tz_keys_encode(self.h, ix.ctypes.data, int(ix.size), pr.ctypes.data, ln.ctypes.data, C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def keys_get(self, offset, count, out=None):
+        if out is None:
+            out = np.empty(count, np.uint8)
+        self._ck(self.lib.tz_keys_get(self.h, int(offset), int(count), _ptr(out, np.uint8)))
+        return out
+
+    def keys_begin(self, nbytes, nt, h, w, idx, pred, lengths):
+        ix, pr, ln = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(pred, np.uint8), np.ascontiguousarray(lengths, np.uint8)
+        if pr.size != ix.size or ln.size != 256:
+            raise ValueError("%d predictor ids for %d key frames, %d code lengths (256 wanted)" % (pr.size, ix.size, ln.size))
+        self._ck(self.lib.tz_keys_begin(self.h, int(nbytes), int(nt), int(h), int(w), ix.ctypes.data, int(ix.size), pr.ctypes.data,
+                                        ln.ctypes.data))
+        self._keys_shape = (int(nt), int(h), int(w))
+
+    def keys_put(self, offset, piece):
+        self._ck(self.lib.tz_keys_put(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
+
+    def keys_decode(self):
+        """-> the context's frame stack, as frames_begin + frames_put of the zero-except-keys stack leave it."""
+        self._ck(self.lib.tz_keys_decode(self.h))
+        self._staged = self._shape = self._keys_shape
+
+    def keys_residual_buf(self, frames, pred, out=None):
+        """Stand-alone: uint8 (k, H, W, 3) frames (host or device) -> their k * H * W * 3 int16 residual symbols."""
+        self._check_stack(frames, "frames")
+        k, h, w = (int(v) for v in frames.shape[:3])
+        pr = np.ascontiguousarray(pred, np.uint8)
+        if pr.size != k:
+            raise ValueError("%d predictor ids for %d frames" % (pr.size, k))
+        if out is None:
+            out = np.empty(k * h * w * 3, np.int16)
+        self._ck(self.lib.tz_keys_residual_buf(self.h, _ptr(frames), k, h, w, pr.ctypes.data, _ptr(out)))
+        return out
+
+    def keys_unresidual_buf(self, sym, pred, h, w, out=None):
+        pr = np.ascontiguousarray(pred, np.uint8)
+        k = int(pr.size)
+        if _numel(sym) != k * h * w * 3:
+            raise ValueError("%d symbols for %d frames of %d x %d x 3" % (_numel(sym), k, h, w))
+        if out is None:
+            out = np.empty((k, h, w, 3), np.uint8)
+        self._ck(self.lib.tz_keys_unresidual_buf(self.h, _ptr(sym), k, int(h), int(w), pr.ctypes.data, _ptr(out)))
         return out
 
     # ---- opt-in Huffman coder with repeat tokens (tz_huffr_*; format: tezip_amd/huffr.py).  `lengths` holds the A literals

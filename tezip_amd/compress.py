@@ -10,6 +10,10 @@ Output directory:
                  with CODER="huff" (--coder huff; not a reference format): "TZH1" header | that trailer | code lengths |
                  index | bit stream, written by the GPU (tezip_amd/huff.py); with CODER="huffr" the
                  same under the magic "TZR1", the code being over literals and period-3 repeat tokens (tezip_amd/huffr.py)
+  with KEY_CODER="huff" (--key-coder huff; not a reference format) key_frame.dat holds the key frames alone: "TZK1" header |
+                 key indices | predictor ids | code lengths | index | bit stream -- per key frame the residuals of the best
+                 of four predictors (none, left, up, left + up - upleft), Huffman-coded on the GPU (tezip_amd/keycoder.py,
+                 DESIGN.md section 9).  Smaller than zstd-9 on smooth frames, LARGER on sparse ones: hence opt-in
 """
 import glob
 import os
@@ -19,7 +23,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, huff, huffr, quality, sidecar, weights, zstd
+from . import _lib, huff, huffr, keycoder, quality, sidecar, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -242,6 +246,51 @@ def check_coder(coder, shuffle=False, sharded=False):
     return None
 
 
+KEY_CODERS = ("zstd", "huff")
+
+
+def check_key_coder(key_coder, sharded=False):
+    """The refusals of --key-coder, for tezip.py and for a direct caller of run(): None, or the message."""
+    if key_coder not in KEY_CODERS:
+        return "--key-coder takes one of %s, got %r" % (", ".join(KEY_CODERS), key_coder)
+    if key_coder != "zstd" and sharded:
+        return "--key-coder %s is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU" % key_coder
+    return None
+
+
+def _huff_key_file(ctx, path, nt, H, W, key_idx, verbose):
+    """key_frame.dat of KEY_CODER="huff": the key frames of the resident stack are counted under the four predictors, the
+    predictors and the one code are chosen here (keycoder.choose_predictors, tz_huff_lengths), the device codes them
+    (tz_keys_encode) and only the coded stream crosses to the host -- no zero frame, no raw key frame, no zstd."""
+    t0 = time.perf_counter()
+    counts = ctx.keys_counts(key_idx)
+    pred = keycoder.choose_predictors(counts)
+    lengths = huff.code_lengths(keycoder.chosen_counts(counts, pred))
+    nbytes = ctx.keys_encode(key_idx, pred, lengths)
+    n = len(key_idx) * H * W * 3
+    nruns, nchunks = huff.geometry(n)
+    front = keycoder.pack_front(nt, H, W, key_idx, pred, lengths, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4)
+    bufs = [np.empty(min(HUFF_PIECE, nbytes), np.uint8) for _ in range(2)]
+    with open(path, mode='wb') as f:
+        f.write(front)
+        for k, off in enumerate(range(0, nbytes, HUFF_PIECE)):
+            cnt = min(HUFF_PIECE, nbytes - off)
+            f.write(ctx.keys_get(off, cnt, out=bufs[k % 2][:cnt]))
+    if verbose:
+        print("key_coding:{0}".format(time.perf_counter() - t0) + "[sec]")
+    return len(front) + nbytes
+
+
+class _Done:
+    """A finished piece of work where a future is expected."""
+
+    def __init__(self, value):
+        self.value = value
+
+    def result(self):
+        return self.value
+
+
 def _huff_entropy_file(ctx, path, n, trailer, verbose, coder="huff"):
     """entropy.dat of CODER="huff" / "huffr": the resident payload is coded on the device (tz_huff_encode / tz_huffr_encode)
     and only the coded stream crosses to the host; the header, the reference trailer and the code lengths go in front of it."""
@@ -269,13 +318,20 @@ def _huff_entropy_file(ctx, path, n, trailer, verbose, coder="huff"):
     return len(front) + nbytes
 
 
-def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False):
+def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False,
+                    key_coder="zstd"):
     """key_frame.dat and entropy.dat (compress.py:271-278, 375-400) from the context-resident frames
     and payload, piece by piece: nothing of size nt*H*W lives on the host."""
     n = nt * H * W * 3
     key_idx = [int(i) for i in np.nonzero(key)[0]]
     zero = np.zeros((H, W, 3), np.uint8)
-    if len(key_idx) * H * W * 3 <= KEY_PREFETCH_BYTES:
+    if key_coder == "huff":
+        # few key frames or all of them (-w 1): one path, the stack never leaves the device
+        t_k = time.perf_counter()
+        kf = _Done(_huff_key_file(ctx, os.path.join(out_dir, "key_frame.dat"), nt, H, W, key_idx, verbose))
+        if stages:
+            stages.add("key-frame coding + fetch key_frame.dat", time.perf_counter() - t_k)
+    elif len(key_idx) * H * W * 3 <= KEY_PREFETCH_BYTES:
         # the usual case, a few key frames: fetched up front, key_frame.dat is compressed by a worker while the
         # payload is fetched and compressed here (the context is not thread-safe: the worker never touches it)
         key_frames = {i: ctx.frames_get(i, 1)[0] for i in key_idx}
@@ -301,11 +357,7 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
             for i in range(nt):
                 sc.write(ctx.frames_get(i, 1)[0] if i in is_key else zero)
             ksize = sc.close()
-
-        class _Done:
-            def result(self):
-                return ksize
-        kf = _Done()
+        kf = _Done(ksize)
     if table is not None:
         tail = np.concatenate([table.astype(np.int64), [len(table)]])
     else:
@@ -358,7 +410,7 @@ def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
 
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
-        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd"):
+        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd"):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -368,6 +420,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     payload (tezip_amd/huff.py), "huffr" the same over literals and period-3 repeat tokens (tezip_amd/huffr.py) -- such a
     file is not readable by the reference; `-u` recognises it by its magic.
     Single-GPU jobs only, not with SHUFFLE.
+    KEY_CODER (--key-coder; NOT in the reference): "zstd" writes the reference's key_frame.dat; "huff" has the GPU code the
+    key frames alone as predictor residuals under a Huffman code (tezip_amd/keycoder.py) -- not readable by the reference,
+    `-u` recognises it by its magic; smaller than zstd-9 on smooth frames and larger on sparse ones.  Independent of CODER
+    and SHUFFLE.  Single-GPU jobs only.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -376,7 +432,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if not GPU_FLAG:
         print("ERROR: this build runs the compression path on an AMD MI355X only (no CPU path).")
         exit()
-    problem = check_coder(CODER, SHUFFLE, tzdist.active() is not None)
+    problem = check_coder(CODER, SHUFFLE, tzdist.active() is not None) or check_key_coder(KEY_CODER, tzdist.active() is not None)
     if problem:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         print("ERROR:", problem)
         sys.exit(2)
@@ -438,7 +494,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     print("table_create:{0}".format(prof["table_create"][0] / 1e3) + "[sec]")
                     print("replacing_based_on_frequency:{0}".format(prof["lut_remap"][0] / 1e3) + "[sec]")
             _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
-                            coder=CODER, verbose=VERBOSE)
+                            coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER)
             doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS))   # the contract the predictions were made under
             if VERBOSE:
                 print("arithmetic contract:", doc["arithmetic_contract"])

@@ -219,6 +219,8 @@ extern "C" int tz_ctx_destroy(tz_ctx* ctx) {
     if (ctx->ev_payload) (void)hipEventDestroy(ctx->ev_payload);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
     if (ctx->d_huff) (void)hipFree(ctx->d_huff);
+    if (ctx->d_keys) (void)hipFree(ctx->d_keys);
+    if (ctx->d_keysym) (void)hipFree(ctx->d_keysym);
     if (ctx->d_scan_status) (void)hipFree(ctx->d_scan_status);
     if (ctx->h_fault) (void)hipHostFree((void*)ctx->h_fault);
     for (auto& s : ctx->prof)
@@ -2233,8 +2235,9 @@ static void huff_geometry(size_t n, size_t* nruns, size_t* nchunks, size_t* inde
 
 // d_in (device, n int16) -> ctx->d_huff = index | bits; *bytes its size.  Waits once, for the size of the bit stream.
 // tokens: the TZR1 stream (lengths holds A + TZ_HUFFR_NTOK entries, k_huffr_size / k_huffr_enc) instead of the TZH1 one.
+// keys: the stream goes to the key-frame coder's buffer ctx->d_keys instead, and what the entropy coders hold stays.
 static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uint8_t* lengths, int A, int base, size_t* bytes,
-                           bool tokens = false) {
+                           bool tokens = false, bool keys = false) {
     if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
     std::vector<uint16_t> enc;
     TZ_TRY(huff_tables(ctx, lengths, A, base, &enc, nullptr, tokens ? TZ_HUFFR_NTOK : 0));
@@ -2256,15 +2259,24 @@ static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uin
     if (meta.bad) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: the payload holds a value the code lengths give no code");
     if (meta.total_words >= (1ull << 32)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: a bit stream of %llu words does not fit the format", meta.total_words);
     const size_t total = index_bytes + (size_t)meta.total_words * 4;
-    ctx->huff_n = ctx->huffr_n = 0;   // (a staged decoder stream, if any, is gone)
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, total));
-    ctx->huff_bytes = total;
-    TZ_HIP(ctx, hipMemcpyAsync(ctx->d_huff, d_idx, index_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    uint8_t* d_stream;
+    if (keys) {
+        ctx->keys_n = 0;              // (a staged decoder stream, if any, is gone)
+        TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, total));
+        ctx->keys_bytes = total;
+        d_stream = ctx->d_keys;
+    } else {
+        ctx->huff_n = ctx->huffr_n = 0;
+        TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, total));
+        ctx->huff_bytes = total;
+        d_stream = ctx->d_huff;
+    }
+    TZ_HIP(ctx, hipMemcpyAsync(d_stream, d_idx, index_bytes, hipMemcpyDeviceToDevice, ctx->stream));
     if (tokens)
-        TZ_TRY(tzk_huffr_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(ctx->d_huff + index_bytes),
+        TZ_TRY(tzk_huffr_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(d_stream + index_bytes),
                              (size_t)meta.total_words));
     else
-        TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(ctx->d_huff + index_bytes),
+        TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(d_stream + index_bytes),
                             (size_t)meta.total_words));
     *bytes = total;
     return TZ_OK;
@@ -2578,6 +2590,229 @@ extern "C" int tz_huffr_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, uns
     const void* din = nullptr;
     int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
     if (rc == TZ_OK) rc = huffr_counts_dev(ctx, (const int16_t*)din, n, counts, A, base);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// --------------------------------------------------------------------------- key-frame coder (TZK1)
+// `--key-coder huff` (NOT a reference feature: compress.py:271-278 hands a zero-except-keys stack of the whole sequence to
+// zstd): the key frames alone, as predictor residuals under one TZH1 code (tezip_amd/keycoder.py, k_key_* in tz_codec.hip).
+// The coder has buffers of its own (d_keys, d_keysym): what tz_huff_* / tz_huffr_* hold or have staged is left alone.
+static constexpr int TZ_KEYS_A = 256;
+
+// the key list of a stack of nt frames: at least one index, strictly ascending, inside [0, nt); predictor ids 0..3
+static int keys_check(tz_ctx* ctx, int nt, const int* idx, int nkeys, const uint8_t* pred) {
+    if (!idx || nkeys < 1 || nkeys > nt) return tz_fail(ctx, TZ_ERR_INVALID, "key frames: %d indices for a stack of %d frames", nkeys, nt);
+    for (int k = 0; k < nkeys; ++k) {
+        if (idx[k] < 0 || idx[k] >= nt || (k && idx[k] <= idx[k - 1]))
+            return tz_fail(ctx, TZ_ERR_INVALID, "key frames: index %d (entry %d) is not ascending inside [0, %d)", idx[k], k, nt);
+        if (pred && pred[k] > 3) return tz_fail(ctx, TZ_ERR_INVALID, "key frames: predictor id %d (entry %d) outside [0, 3]", pred[k], k);
+    }
+    return TZ_OK;
+}
+
+static int keys_upload(tz_ctx* ctx, const int* idx, const uint8_t* pred, int nkeys, const int** d_idx, const uint8_t** d_pred) {
+    void *di, *dp;
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(int) * nkeys, &di));
+    TZ_TRY(tz_upload(ctx, di, idx, sizeof(int) * nkeys));
+    *d_idx = (const int*)di;
+    if (pred) {
+        TZ_TRY(tz_pool_alloc(ctx, nkeys, &dp));
+        TZ_TRY(tz_upload(ctx, dp, pred, nkeys));
+        *d_pred = (const uint8_t*)dp;
+    }
+    return TZ_OK;
+}
+
+// the encoder's precondition: a frame stack in the context (tz_frames_put or a rollout), everything of it arrived
+static int keys_resident(tz_ctx* ctx, const char* who) {
+    if (!ctx->d_frames || ctx->nt < 1 || !(ctx->staged || ctx->rollout_kind != tz_ctx::ROLLOUT_NONE))
+        return tz_fail(ctx, TZ_ERR_STATE, "%s needs a resident frame stack (tz_frames_begin / tz_frames_put, or a rollout)", who);
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
+    return TZ_OK;
+}
+
+static int keys_counts(tz_ctx* ctx, const int* idx, int nkeys, unsigned* counts) {
+    const int* d_idx = nullptr;
+    const uint8_t* d_pred = nullptr;
+    void* d_counts;
+    const size_t cb = (size_t)nkeys * 4 * TZ_KEYS_A * sizeof(unsigned);
+    TZ_TRY(keys_upload(ctx, idx, nullptr, nkeys, &d_idx, &d_pred));
+    TZ_TRY(tz_pool_alloc(ctx, cb, &d_counts));
+    TZ_TRY(tzk_key_hist(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, nkeys, (unsigned*)d_counts));
+    TZ_TRY(tz_d2h(ctx, counts, d_counts, cb, ctx->stream));
+    return tz_stream_sync(ctx);
+}
+
+extern "C" int tz_keys_counts(tz_ctx* ctx, const int* idx, int nkeys, unsigned* counts) {
+    tz_roctx_range roctx_("tz_keys_counts");
+    if (!ctx || !counts) return TZ_ERR_INVALID;
+    TZ_TRY(keys_resident(ctx, "tz_keys_counts"));
+    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys, nullptr));
+    const int rc = keys_counts(ctx, idx, nkeys, counts);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+static int keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths, size_t* bytes) {
+    const size_t n = (size_t)nkeys * ctx->H * ctx->W * 3;
+    const int* d_idx = nullptr;
+    const uint8_t* d_pred = nullptr;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
+    TZ_TRY(keys_upload(ctx, idx, pred, nkeys, &d_idx, &d_pred));
+    TZ_TRY(tzk_key_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, d_pred, nkeys, ctx->d_keysym));
+    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, false, true);
+}
+
+extern "C" int tz_keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths, size_t* bytes) {
+    tz_roctx_range roctx_("tz_keys_encode");
+    if (!ctx || !pred || !lengths || !bytes) return TZ_ERR_INVALID;
+    TZ_TRY(keys_resident(ctx, "tz_keys_encode"));
+    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys, pred));
+    const int rc = keys_encode(ctx, idx, nkeys, pred, lengths, bytes);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_keys_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    if (!ctx->d_keys || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the resident key-frame stream");
+    TZ_TRY(tz_d2h(ctx, out, ctx->d_keys + offset, count, ctx->stream));
+    return tz_stream_sync(ctx);
+}
+
+extern "C" int tz_keys_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* pred,
+                             const uint8_t* lengths) {
+    if (!ctx || !pred) return TZ_ERR_INVALID;
+    if (nt < 1 || H < 1 || W < 1 || nt > kMaxFrames || H > 32767 || W > 32767)
+        return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d (int16 trailer limits)", nt, H, W);
+    TZ_TRY(keys_check(ctx, nt, idx, nkeys, pred));
+    const size_t n = (size_t)nkeys * H * W * 3;
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, bytes, n, TZ_HUFF_RUN, &sw));
+    std::vector<uint16_t> dec;
+    TZ_TRY(huff_tables(ctx, lengths, TZ_KEYS_A, 0, nullptr, &dec));
+    ctx->keys_n = 0;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, std::max<size_t>(bytes, 16)));
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, std::max<size_t>(n, 8) * 2));
+    ctx->keys_bytes = bytes;
+    ctx->keys_put = 0;
+    ctx->keys_nt = nt;
+    ctx->keys_H = H;
+    ctx->keys_W = W;
+    ctx->keys_idx.assign(idx, idx + nkeys);
+    ctx->keys_pred.assign(pred, pred + nkeys);
+    ctx->keys_dec_tab.swap(dec);
+    ctx->keys_n = n;
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
+    return TZ_OK;
+}
+
+extern "C" int tz_keys_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
+    if (!ctx || !src) return TZ_ERR_INVALID;
+    if (!ctx->d_keys || !ctx->keys_n || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged key-frame stream");
+    TZ_TRY(tz_h2d(ctx, ctx->d_keys + offset, src, count, ctx->copy_stream));
+    ctx->keys_put += count;
+    return TZ_OK;
+}
+
+// symbols (device) -> the frames idx[k] of a stack at d_frames; the other frames of the stack are not touched
+static int keys_unresidual(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* idx, const uint8_t* pred, int nkeys, uint8_t* d_frames) {
+    const int* d_idx = nullptr;
+    const uint8_t* d_pred = nullptr;
+    TZ_TRY(keys_upload(ctx, idx, pred, nkeys, &d_idx, &d_pred));
+    return tzk_key_unresid(ctx, d_sym, H, W, d_idx, d_pred, nkeys, d_frames);
+}
+
+static int keys_decode(tz_ctx* ctx) {
+    const int nt = ctx->keys_nt, H = ctx->keys_H, W = ctx->keys_W;
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, ctx->keys_bytes, ctx->keys_n, TZ_HUFF_RUN, &sw));
+    // what tz_frames_begin does: the stack's buffer and shape; whatever rollout was resident is gone
+    set_rollout(ctx, tz_ctx::ROLLOUT_NONE, 0, 0);
+    ctx->staged = false;
+    const size_t fb = (size_t)nt * H * W * 3;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_frames, &ctx->cap_frames, fb));
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of tz_keys_put (and older copies into d_frames)
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
+    TZ_TRY(huff_decode_dev(ctx, ctx->d_keys, sw, ctx->keys_n, ctx->keys_dec_tab, 0, ctx->d_keysym));
+    TZ_HIP(ctx, hipMemsetAsync(ctx->d_frames, 0, fb, ctx->stream));   // the frames that are no key frames (a fresh buffer holds anything)
+    TZ_TRY(keys_unresidual(ctx, ctx->d_keysym, H, W, ctx->keys_idx.data(), ctx->keys_pred.data(), (int)ctx->keys_idx.size(), ctx->d_frames));
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));       // a later tz_frames_put waits for the frames written here
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
+    ctx->nt = nt;
+    ctx->H = H;
+    ctx->W = W;
+    ctx->staged = true;
+    return TZ_OK;
+}
+
+extern "C" int tz_keys_decode(tz_ctx* ctx) {
+    tz_roctx_range roctx_("tz_keys_decode");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (!ctx->keys_n || !ctx->d_keys || !ctx->d_keysym)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_keys_decode needs a stream staged with tz_keys_begin / tz_keys_put");
+    if (ctx->keys_put != ctx->keys_bytes)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_keys_decode: %zu of the stream's %zu bytes were put", ctx->keys_put, ctx->keys_bytes);
+    const int rc = keys_decode(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// stand-alone forms on host or device arrays: frames (k, H, W, 3) <-> k * H * W * 3 int16 symbols, pred[k] per frame
+static int keys_buf_check(tz_ctx* ctx, int k, int H, int W, const uint8_t* pred, std::vector<int>* idx) {
+    if (k < 1 || H < 1 || W < 1 || k > kMaxFrames || H > 32767 || W > 32767)
+        return tz_fail(ctx, TZ_ERR_INVALID, "bad key-frame stack k=%d H=%d W=%d", k, H, W);
+    idx->resize(k);
+    for (int i = 0; i < k; ++i) (*idx)[i] = i;
+    return keys_check(ctx, k, idx->data(), k, pred);
+}
+
+extern "C" int tz_keys_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* pred, int16_t* sym) {
+    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
+    std::vector<int> idx;
+    TZ_TRY(keys_buf_check(ctx, k, H, W, pred, &idx));
+    const size_t n = (size_t)k * H * W * 3;
+    const void* din = nullptr;
+    const int* d_idx = nullptr;
+    const uint8_t* d_pred = nullptr;
+    tz_out o;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, frames, n, &din);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, sym, n * 2, &o);
+    if (rc == TZ_OK && ((uintptr_t)o.dev & 1)) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames: a device symbol array must be 2-byte aligned");
+    if (rc == TZ_OK) rc = keys_upload(ctx, idx.data(), pred, k, &d_idx, &d_pred);
+    if (rc == TZ_OK) {
+        outs.push_back(o);
+        rc = tzk_key_resid(ctx, (const uint8_t*)din, H, W, d_idx, d_pred, k, (int16_t*)o.dev);
+    }
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_keys_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* pred, uint8_t* frames) {
+    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
+    std::vector<int> idx;
+    TZ_TRY(keys_buf_check(ctx, k, H, W, pred, &idx));
+    const size_t n = (size_t)k * H * W * 3;
+    const void* din = nullptr;
+    tz_out o;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, sym, n * 2, &din);
+    if (rc == TZ_OK && ((uintptr_t)din & 1)) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames: a device symbol array must be 2-byte aligned");
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, frames, n, &o);
+    if (rc == TZ_OK) {
+        outs.push_back(o);
+        rc = keys_unresidual(ctx, (const int16_t*)din, H, W, idx.data(), pred, k, (uint8_t*)o.dev);
+    }
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
     tz_pool_release_all(ctx);
     return rc;
 }

@@ -3111,3 +3111,224 @@ int tzk_huffr_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_ru
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
+
+// ---------------------------------------------------------------------------- key-frame coder
+// Opt-in stage `--key-coder huff` (format TZK1: DESIGN.md section 9, tezip_amd/keycoder.py is the slow statement of it).
+// A key frame is turned into the residuals of one of four predictors over its own samples -- 0: none, 1: the left
+// neighbour a, 2: the upper neighbour b, 3: a + b - c with c the upper-left one, always of the same channel and 0 outside
+// the frame, everything mod 256 -- and the residuals of all key frames are coded by the k_huff_* kernels above as int16
+// symbols 0..255.  The inverses are prefix sums mod 256 along the rows (1), the columns (2) or both (3).
+// A frame is fe = H * W3 bytes, W3 = 3 W; a thread takes a UNIT of it: unit 0 is the head in front of the first 16-byte
+// boundary of the frame's address (fewer than 16 samples, possibly none), unit u >= 1 the 16 samples from there on.
+struct KeyWin {
+    unsigned x[16], a[16], b[16], c[16];   // the samples and their left, upper and upper-left neighbours (0 outside the frame)
+};
+
+__device__ __forceinline__ unsigned key_head(const uint8_t* f, size_t fe) {
+    return (unsigned)min(fe, (size_t)((16 - ((uintptr_t)f & 15)) & 15));
+}
+
+// *e / *cnt: first sample and number of samples of unit u (cnt 0: nothing to do)
+__device__ __forceinline__ void key_unit(size_t u, unsigned head, size_t fe, size_t* e, int* cnt) {
+    if (u == 0) {
+        *e = 0;
+        *cnt = (int)head;
+    } else {
+        *e = head + (u - 1) * 16;
+        *cnt = *e < fe ? (int)min((size_t)16, fe - *e) : 0;
+    }
+}
+
+__device__ __forceinline__ void key_window(const uint8_t* __restrict__ f, size_t fe, unsigned W3, size_t e, int cnt, KeyWin& w) {
+    unsigned cw[19], uw[19];   // samples e - 3 .. e + 15 and the 19 one row above them
+    if (cnt == 16 && e >= (size_t)W3 + 4) {   // a whole unit with every neighbour inside the frame; f + e is 16-byte aligned
+        const uint4 cur = *(const uint4*)(f + e);
+        const unsigned left = *(const unsigned*)(f + e - 4);
+        uint8_t up[19];
+        __builtin_memcpy(up, f + e - W3 - 3, 19);   // (no alignment: W3 is any multiple of 3)
+        const unsigned cq[4] = {cur.x, cur.y, cur.z, cur.w};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cw[j] = (left >> (8 * (j + 1))) & 0xffu;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) cw[j + 3] = (cq[j >> 2] >> (8 * (j & 3))) & 0xffu;
+#pragma unroll
+        for (int j = 0; j < 19; ++j) uw[j] = up[j];
+    } else {                                   // the head, the tail and the first row: sample by sample, each index checked
+#pragma unroll
+        for (int j = 0; j < 19; ++j) {
+            const long long i = (long long)e - 3 + j, iu = i - (long long)W3;
+            cw[j] = (i >= 0 && i < (long long)fe && j < cnt + 3) ? f[i] : 0u;
+            uw[j] = (iu >= 0 && iu < (long long)fe && j < cnt + 3) ? f[iu] : 0u;
+        }
+    }
+    unsigned y = (unsigned)(e / W3), r = (unsigned)(e - (size_t)y * W3);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const bool hl = r >= 3, hu = y > 0;
+        w.x[j] = cw[j + 3];
+        w.a[j] = hl ? cw[j] : 0u;
+        w.b[j] = hu ? uw[j + 3] : 0u;
+        w.c[j] = (hl && hu) ? uw[j] : 0u;
+        if (++r == W3) {
+            r = 0;
+            ++y;
+        }
+    }
+}
+
+// Counts of the residual values of key frame idx[k] under all four predictors, from ONE read of the frame:
+// counts[k][p][256].  Every wave of a workgroup has its own 4 x 256 counters in LDS (the residuals of a smooth frame crowd
+// into a few bins); a workgroup adds each (predictor, bin) it touched to the global counters once.
+__global__ __launch_bounds__(256) void k_key_hist(const uint8_t* __restrict__ frames, size_t fe, unsigned W3, const int* __restrict__ idx,
+                                                  unsigned* __restrict__ counts) {
+    __shared__ unsigned h[4][1024];
+    for (int k = threadIdx.x; k < 4096; k += 256) (&h[0][0])[k] = 0;
+    __syncthreads();
+    const int key = blockIdx.y;
+    const uint8_t* f = frames + (size_t)idx[key] * fe;
+    const unsigned head = key_head(f, fe);
+    const size_t nunits = 1 + (fe - head + 15) / 16, stride = (size_t)gridDim.x * 256;
+    unsigned* hw = h[threadIdx.x >> 6];
+    for (size_t u = (size_t)blockIdx.x * 256 + threadIdx.x; u < nunits; u += stride) {
+        size_t e;
+        int cnt;
+        key_unit(u, head, fe, &e, &cnt);
+        if (cnt <= 0) continue;
+        KeyWin w;
+        key_window(f, fe, W3, e, cnt, w);
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (j < cnt) {
+                atomicAdd(&hw[w.x[j]], 1u);
+                atomicAdd(&hw[256 + ((w.x[j] - w.a[j]) & 255u)], 1u);
+                atomicAdd(&hw[512 + ((w.x[j] - w.b[j]) & 255u)], 1u);
+                atomicAdd(&hw[768 + ((w.x[j] - w.a[j] - w.b[j] + w.c[j]) & 255u)], 1u);
+            }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < 1024; k += 256) {
+        const unsigned s = h[0][k] + h[1][k] + h[2][k] + h[3][k];
+        if (s) atomicAdd(&counts[(size_t)key * 1024 + k], s);
+    }
+}
+
+static dim3 key_grid(size_t fe, int nkeys) {
+    return dim3((unsigned)std::min<size_t>((fe / 16 + 2 + 255) / 256, 256), (unsigned)nkeys);
+}
+
+int tzk_key_hist(tz_ctx* ctx, const uint8_t* d_frames, int H, int W, const int* d_idx, int nkeys, unsigned* d_counts) {
+    const size_t fe = (size_t)H * W * 3;
+    TZ_HIP(ctx, hipMemsetAsync(d_counts, 0, (size_t)nkeys * 1024 * sizeof(unsigned), ctx->stream));
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    hipLaunchKernelGGL(k_key_hist, key_grid(fe, nkeys), dim3(256), 0, ctx->stream, d_frames, fe, (unsigned)W * 3u, d_idx, d_counts);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// Residuals of key frame idx[k] under predictor pred[k] as int16 symbols 0..255 at sym[k * fe ...]: what k_huff_size /
+// k_huff_enc code.  16-byte loads of the samples; 16-byte stores where the output's address allows them.
+__global__ __launch_bounds__(256) void k_key_resid(const uint8_t* __restrict__ frames, size_t fe, unsigned W3, const int* __restrict__ idx,
+                                                   const uint8_t* __restrict__ pred, int16_t* __restrict__ sym) {
+    const int key = blockIdx.y;
+    const uint8_t* f = frames + (size_t)idx[key] * fe;
+    int16_t* out = sym + (size_t)key * fe;
+    const unsigned p = pred[key];
+    const unsigned head = key_head(f, fe);
+    const size_t nunits = 1 + (fe - head + 15) / 16, stride = (size_t)gridDim.x * 256;
+    for (size_t u = (size_t)blockIdx.x * 256 + threadIdx.x; u < nunits; u += stride) {
+        size_t e;
+        int cnt;
+        key_unit(u, head, fe, &e, &cnt);
+        if (cnt <= 0) continue;
+        KeyWin w;
+        key_window(f, fe, W3, e, cnt, w);
+        short8 lo, hi;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const unsigned q = (p & 1u ? w.a[j] : 0u) + (p & 2u ? w.b[j] : 0u) - (p == 3u ? w.c[j] : 0u);
+            const short v = (short)((w.x[j] - q) & 255u);
+            if (j < 8) lo[j] = v;
+            else hi[j - 8] = v;
+        }
+        if (cnt == 16 && ((uintptr_t)(out + e) & 15) == 0) {
+            *(short8*)(out + e) = lo;
+            *(short8*)(out + e + 8) = hi;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (j < cnt) out[e + j] = j < 8 ? lo[j] : hi[j - 8];
+        }
+    }
+}
+
+int tzk_key_resid(tz_ctx* ctx, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, int16_t* d_sym) {
+    const size_t fe = (size_t)H * W * 3;
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    hipLaunchKernelGGL(k_key_resid, key_grid(fe, nkeys), dim3(256), 0, ctx->stream, d_frames, fe, (unsigned)W * 3u, d_idx, d_pred, d_sym);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// The inverse, first pass: one wave per (key frame, row) turns the row's symbols into bytes of frame idx[k] -- under
+// predictors 1 and 3 as the inclusive prefix sum mod 256 along the row, per channel: 64 columns at a time, a shuffle scan
+// over the lanes, the carry into the next 64 columns in a register.  Only the low byte of a symbol counts.
+__global__ __launch_bounds__(256) void k_key_unresid_row(const int16_t* __restrict__ sym, int H, int W, const int* __restrict__ idx,
+                                                         const uint8_t* __restrict__ pred, uint8_t* __restrict__ frames) {
+    const int key = blockIdx.y, y = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (y >= H) return;   // (wave-uniform)
+    const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3;
+    const int16_t* s = sym + (size_t)key * fe + (size_t)y * W3;
+    uint8_t* o = frames + (size_t)idx[key] * fe + (size_t)y * W3;
+    const bool scan = (pred[key] & 1u) != 0;
+    unsigned carry[3] = {0u, 0u, 0u};
+    for (int c0 = 0; c0 < W; c0 += 64) {
+        const int col = c0 + lane;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            unsigned v = col < W ? (unsigned)s[(size_t)col * 3 + ch] & 255u : 0u;
+            if (scan) {
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const unsigned t = __shfl_up(v, d, 64);
+                    if (lane >= d) v += t;
+                }
+                v += carry[ch];
+                carry[ch] = __shfl(v, 63, 64) & 255u;
+            }
+            if (col < W) o[(size_t)col * 3 + ch] = (uint8_t)v;
+        }
+    }
+}
+
+// Second pass, predictors 2 and 3: a thread per (key frame, sample of a row) walks down its column and replaces every byte
+// by the running sum mod 256; neighbouring threads touch neighbouring bytes.  Eight rows are loaded before they are summed.
+__global__ __launch_bounds__(256) void k_key_unresid_col(int H, int W, const int* __restrict__ idx, const uint8_t* __restrict__ pred,
+                                                         uint8_t* __restrict__ frames) {
+    const int key = blockIdx.y;
+    if (!(pred[key] & 2u)) return;   // (workgroup-uniform)
+    const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3, j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= W3) return;
+    uint8_t* o = frames + (size_t)idx[key] * fe + j;
+    unsigned acc = 0;
+    for (int y0 = 0; y0 < H; y0 += 8) {
+        unsigned v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = y0 + i < H ? o[(size_t)(y0 + i) * W3] : 0u;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            acc += v[i];
+            if (y0 + i < H) o[(size_t)(y0 + i) * W3] = (uint8_t)acc;
+        }
+    }
+}
+
+int tzk_key_unresid(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, uint8_t* d_frames) {
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    hipLaunchKernelGGL(k_key_unresid_row, dim3((unsigned)((H + 3) / 4), (unsigned)nkeys), dim3(256), 0, ctx->stream, d_sym, H, W, d_idx, d_pred,
+                       d_frames);
+    TZ_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_key_unresid_col, dim3((unsigned)(((size_t)W * 3 + 255) / 256), (unsigned)nkeys), dim3(256), 0, ctx->stream, H, W, d_idx,
+                       d_pred, d_frames);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}

@@ -33,7 +33,8 @@ enum tz_prof_class {
     TZP_QSERIAL,    // not a time: `launches` counts the chains the quantiser sent through its serial fallback (k_q_serial)
     TZP_CARRY,      // prefix carry of the inverse scan (k_undelta_carry, tz_decode_range)
     TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality)
-    TZP_HUFF,       // opt-in Huffman coder: k_huff_count / k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec (and k_huffr_*)
+    TZP_HUFF,       // opt-in Huffman coder: k_huff_count / k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec (and k_huffr_*),
+                    // and the key-frame coder in front of it: k_key_hist / k_key_resid / k_key_unresid_*
     TZP_COUNT
 };
 
@@ -135,6 +136,18 @@ struct tz_ctx {
     // instead of huff_n, so that neither decoder expands the other's stream
     size_t huffr_n = 0;
     int huffr_A = 0;                        // literals of the staged TZR1 code (symbols A..A + 7 are its repeat tokens)
+    // opt-in key-frame coder (tz_keys_*): buffers of its own, so that an entropy stream staged with tz_huff_begin /
+    // tz_huffr_begin survives it.  d_keys: the coded stream (index | bits) tz_keys_encode left or tz_keys_begin / tz_keys_put
+    // stage; d_keysym: the int16 residual symbols between the predictor kernels and the Huffman kernels
+    uint8_t* d_keys = nullptr;
+    int16_t* d_keysym = nullptr;
+    size_t cap_keys = 0, cap_keysym = 0, keys_bytes = 0;
+    size_t keys_n = 0;                      // tz_keys_begin: symbols the staged stream decodes to (0: nothing staged)
+    size_t keys_put = 0;                    // bytes tz_keys_put has staged since tz_keys_begin
+    int keys_nt = 0, keys_H = 0, keys_W = 0;
+    std::vector<int> keys_idx;              // tz_keys_begin: the key frames' indices ...
+    std::vector<uint8_t> keys_pred;         // ... and predictor ids
+    std::vector<uint16_t> keys_dec_tab;     // tz_keys_begin: the 2^12-entry decode table of the staged stream's lengths
     uint8_t* d_out = nullptr;               // resident decoded frames of a tz_decode(frames_out = NULL)
     size_t cap_out = 0;
     bool have_decoded = false;
@@ -324,6 +337,11 @@ int tzk_huffr_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, i
                   const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words);
 int tzk_huffr_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
                   const uint16_t* d_dec_tab4096, int A, int base, size_t n, int16_t* out);
+// key-frame coder (TZK1).  d_frames: a stack of H x W x 3 frames of which frame d_idx[k] is key frame k;
+// d_pred[k] its predictor id 0..3; d_sym: nkeys * H * W * 3 int16 symbols 0..255, key after key.
+int tzk_key_hist(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, int nkeys, unsigned* d_counts /* [nkeys][4][256] */);
+int tzk_key_resid(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, int16_t* d_sym);
+int tzk_key_unresid(tz_ctx*, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, uint8_t* d_frames);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,
             double* h_sse);
 int tzk_sse_blocks(int Hp, int Wp);

@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from . import _lib, huff, huffr, sidecar, zstd
+from . import _lib, huff, huffr, keycoder, sidecar, zstd
 from . import dist as tzdist
 from .compress import SHUFFLE_MARK, make_context, open_model
 from .data_utils import padding_shape
@@ -64,6 +64,18 @@ def coded_calls(ctx, coded):
     if isinstance(coded, huffr.Parsed):
         return ctx.huffr_begin, ctx.huffr_put, ctx.huffr_decode
     return ctx.huff_begin, ctx.huff_put, ctx.huff_decode
+
+
+def stage_coded_keys(ctx, keys, stack):
+    """A parsed TZK1 key_frame.dat -> the context's frame stack, as frames_begin + frames_put of the zero-except-keys stack
+    leave it (tz_keys_begin / tz_keys_put / tz_keys_decode).  stack: the (nt, H, W) entropy.dat describes."""
+    if (keys.nt, keys.H, keys.W) != tuple(stack):
+        raise ValueError("key_frame.dat describes the stack as %r (frames, height, width), entropy.dat's trailer as %r"
+                         % ((keys.nt, keys.H, keys.W), tuple(stack)))
+    ctx.keys_begin(keys.body.size, keys.nt, keys.H, keys.W, keys.idx, keys.pred, keys.lengths)
+    for off in range(0, keys.body.size, 16 << 20):
+        ctx.keys_put(off, keys.body[off: off + (16 << 20)])                 # pageable: the piece is free again on return
+    ctx.keys_decode()
 
 
 def adopt_contract(DATA_DIR, wts, VERBOSE):
@@ -167,7 +179,10 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
         stages.mark("context + model load")
         with open(paths["key_frame.dat"], "rb") as f:
             head = f.read(64)
-        key_len = zstd.content_size(head)
+        # this build's opt-in key-frame file (TZK1): validated whole on the CPU; the length the zero-except-keys stack
+        # would have stands in its header, so the cross-checks below see what they see for the reference's file
+        keys = keycoder.parse(np.fromfile(paths["key_frame.dat"], np.uint8)) if keycoder.is_keycoded(head) else None
+        key_len = keys.nt * keys.H * keys.W * 3 if keys is not None else zstd.content_size(head)
 
         def checks(nt, H, W):
             hp, wp = padding_shape(H, W)
@@ -189,6 +204,10 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             stages.mark("model prepare")
             fb = H * W * 3
             per = max(1, (16 << 20) // fb)
+            if keys is not None:
+                stage_coded_keys(ctx, keys, (nt, H, W))
+                stages.mark("stage key_frame.dat + key-frame decode", ctx)
+                return per
             ctx.frames_begin(nt, H, W)
             first = 0
             with open(paths["key_frame.dat"], "rb") as f:
@@ -385,13 +404,24 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
             print("ERROR: No such file or directory:", os.path.join(DATA_DIR, name))
             exit()
 
-    key_bytes = read("key_frame.dat")
+    keys = None
+    try:
+        with open(os.path.join(DATA_DIR, "key_frame.dat"), mode='rb') as f:
+            if keycoder.is_keycoded(f.read(4)):   # this build's opt-in key-frame file: validated here, expanded on the device below
+                keys = keycoder.parse(np.fromfile(os.path.join(DATA_DIR, "key_frame.dat"), np.uint8))
+    except FileNotFoundError:
+        pass   # (read() below prints the reference's message)
+    if keys is not None and job is not None:
+        print("ERROR: a GPU-coded key_frame.dat (--key-coder huff) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
+        sys.exit(2)
+    key_bytes = None if keys is not None else read("key_frame.dat")
+    key_len = keys.nt * keys.H * keys.W * 3 if keys is not None else len(key_bytes)   # (the zero-except-keys stack's size)
     coded = None
     try:
         with open(os.path.join(DATA_DIR, "entropy.dat"), mode='rb') as f:
             fmt = coded_format(f.read(4))
             if fmt is not None:           # this build's opt-in Huffman file: validated here, expanded on the device below
-                coded = fmt.parse(np.fromfile(os.path.join(DATA_DIR, "entropy.dat"), np.uint8), len(key_bytes))
+                coded = fmt.parse(np.fromfile(os.path.join(DATA_DIR, "entropy.dat"), np.uint8), key_len)
     except FileNotFoundError:
         pass   # (read() below prints the reference's message)
     if coded is not None:
@@ -401,9 +431,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
         payload, table, shape, warm_up = None, coded.table, coded.shape, coded.warm_up
     else:
         payload, table, shape, warm_up = parse_stream(read("entropy.dat"))
-        check_stream(shape, warm_up, payload.size, len(key_bytes))
+        check_stream(shape, warm_up, payload.size, key_len)
     _, nt, H, W, C = shape
-    key_frames = np.frombuffer(key_bytes, dtype=np.uint8).reshape(nt, H, W, C)
+    key_frames = None if keys is not None else np.frombuffer(key_bytes, dtype=np.uint8).reshape(nt, H, W, C)
     hp, wp = padding_shape(H, W)
     if model_shape is not None and (model_shape[0] != hp or model_shape[1] != wp):
         print("ERROR:keyframe size and model size do not match.")
@@ -437,7 +467,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
             t0 = time.time()
             tb = None if table is None else np.ascontiguousarray(table)
             first, end = frames or (0, nt)
-            ctx.rollout_decode_range(np.ascontiguousarray(key_frames), warm_up, first, end - first)
+            if keys is not None:    # the same C calls as the streaming path; the stack stays on the device
+                stage_coded_keys(ctx, keys, (nt, H, W))
+                ctx.rollout_decode_range(None, warm_up, first, end - first)
+            else:
+                ctx.rollout_decode_range(np.ascontiguousarray(key_frames), warm_up, first, end - first)
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
             if coded is not None:

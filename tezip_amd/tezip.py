@@ -49,6 +49,10 @@ FLAG_TABLE = (
     # written by the GPU (tezip_amd/huff.py; the reference cannot read such a file, -u recognises it by its magic); huffr = the
     # same with repeat tokens for the payload's period-3 runs (tezip_amd/huffr.py), a smaller file under an error bound
     (None, "--coder", dict(type=str, choices=("zstd", "huff", "huffr"), default="zstd", dest="coder")),
+    # not in the reference: with -c, the coder of key_frame.dat.  zstd = the reference's file; huff = the key frames alone, as
+    # predictor residuals Huffman-coded by the GPU (tezip_amd/keycoder.py; the reference cannot read such a file, -u recognises
+    # it by its magic).  Much smaller on smooth frames, LARGER than zstd on sparse ones (README): check with --report's ratio
+    (None, "--key-coder", dict(type=str, choices=("zstd", "huff"), default="zstd", dest="key_coder")),
 )
 
 TEXT = {
@@ -135,6 +139,17 @@ def check_coder_flag(arg):
     return compress.check_coder(arg.coder, arg.shuffle, int(os.environ.get("WORLD_SIZE", "1")) > 1)
 
 
+def check_key_coder_flag(arg):
+    """--key-coder huff is valid with -c of one single-GPU job, without --sweep.  Returns None, or the message of a refusal."""
+    if getattr(arg, "key_coder", "zstd") == "zstd":
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--key-coder is valid with -c (--compress) only (-u recognises the coder of a file by itself)"
+    if getattr(arg, "sweep", None) is not None:
+        return "--key-coder %s cannot be combined with --sweep" % arg.key_coder
+    return compress.check_key_coder(arg.key_coder, int(os.environ.get("WORLD_SIZE", "1")) > 1)
+
+
 def probe_gpu(force_cpu):
     """tezip.py:12-21 asked TensorFlow for a GPU; here a context on device 0 must open."""
     if force_cpu:
@@ -189,6 +204,10 @@ def _main(arg):
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_key_coder_flag(arg)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # launched by torch.distributed.run: one rank per GPU
         from . import dist as tzdist
         tzdist.init_from_env()
@@ -219,6 +238,10 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if getattr(arg, "key_coder", "zstd") != "zstd":
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=arg.key_coder)
     if getattr(arg, "coder", "zstd") != "zstd":
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
