@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_huff import golden_payloads, synthetic_payloads
+from test_huff import assert_fills_the_image, filling_payloads, golden_payloads, synthetic_payloads
 
 pytestmark = pytest.mark.gpu
 
@@ -25,11 +25,12 @@ def ctx():
 
 
 def _inputs():
+    """(name, payload, lengths): lengths None = the optimal code of the payload's own counts."""
     from tezip_amd import huff
-    out = [(name, pay) for name, pay, _, _, _ in golden_payloads()] + synthetic_payloads(huff)
+    out = [(name, pay, None) for name, pay, _, _, _ in golden_payloads()] + [(name, pay, None) for name, pay in synthetic_payloads(huff)]
     rng = np.random.default_rng(11)
-    out.append(("geometric_8M", np.minimum(rng.geometric(0.25, 8 << 20) - 1, 1020).astype(np.int16)))
-    return out
+    out.append(("geometric_8M", np.minimum(rng.geometric(0.25, 8 << 20) - 1, 1020).astype(np.int16), None))
+    return out + filling_payloads(huff)      # given codes: chunks that fill the LDS image, runs that end on words, an incomplete code
 
 
 def _code(pay):
@@ -38,9 +39,11 @@ def _code(pay):
     return huff.code_lengths(np.bincount(pay.astype(np.int64) - base)), base
 
 
-def _check_pair(ctx, name, pay):
+def _check_pair(ctx, name, pay, ln=None):
     from tezip_amd import huff
-    ln, base = _code(pay)
+    base = int(pay.min())
+    if ln is None:
+        ln, base = _code(pay)
     want = np.frombuffer(huff.pack_body(*huff.encode_body(pay, ln, base)), np.uint8)
     got = ctx.huff_encode_buf(pay, ln, base)
     assert got.size == want.size and (got == want).all(), "%s: the GPU stream differs from the numpy encoder's" % name
@@ -50,11 +53,21 @@ def _check_pair(ctx, name, pay):
     co, rb = got[: nchunks * 4].view("<u4"), got[nchunks * 4: nchunks * 4 + nruns * 2].view("<u2")
     words = got[huff.body_bytes(pay.size, 0):].view("<u4")
     assert (huff.decode_body(co, rb, words, pay.size, ln, base) == pay).all(), "%s: numpy decode of the GPU stream" % name
+    return co, rb
 
 
 def test_gpu_stream_is_the_numpy_stream(ctx):
-    for name, pay in _inputs():
-        _check_pair(ctx, name, pay)
+    from tezip_amd import huff
+    seen = set()
+    for name, pay, ln in _inputs():
+        co, rb = _check_pair(ctx, name, pay, ln)
+        if name.startswith("all12"):                                    # or the test is not testing the bound
+            assert_fills_the_image(huff, name, pay.size, co, rb)
+            seen.add("all12")
+        if name.startswith("all1_"):
+            assert (rb[:-1] == 256).all() and rb[-1] == 1
+            seen.add("all1")
+    assert seen == {"all12", "all1"}
 
 
 def test_device_buffers_two_bytes_off_alignment(ctx):

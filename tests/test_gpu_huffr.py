@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
-from test_huff import golden_payloads, synthetic_payloads
+from test_huff import assert_fills_the_image, golden_payloads, synthetic_payloads
 
 pytestmark = pytest.mark.gpu
 
@@ -26,14 +26,20 @@ def ctx():
 
 
 def _inputs():
+    """(name, payload, lengths): lengths None = the optimal code of the payload's own token counts."""
     from tezip_amd import huff
-    out = [(name, pay) for name, pay, _, _, _ in golden_payloads()] + synthetic_payloads(huff)
+    out = [(name, pay, None) for name, pay, _, _, _ in golden_payloads()] + [(name, pay, None) for name, pay in synthetic_payloads(huff)]
     rng = np.random.default_rng(11)
-    out.append(("all_equal", np.full(5 * 16384 + 300, -7, np.int16)))
-    out.append(("no_match", (np.arange(3 * 16384 + 1234) % 7).astype(np.int16)))            # s[j] != s[j - 3] everywhere
+    out.append(("all_equal", np.full(5 * 16384 + 300, -7, np.int16), None))
+    out.append(("no_match", (np.arange(3 * 16384 + 1234) % 7).astype(np.int16), None))      # s[j] != s[j - 3] everywhere
     runs = np.repeat(rng.integers(0, 50, (40000, 3)), rng.geometric(0.05, 40000), 0).reshape(-1).astype(np.int16)    # pixels repeat
-    out.append(("pixel_runs_n%d" % (runs.size - 5), runs[: runs.size - 5]))                 # long stretches, n % 8 != 0
-    out.append(("geometric_8M", np.minimum(rng.geometric(0.25, 8 << 20) - 1, 1020).astype(np.int16)))
+    out.append(("pixel_runs_n%d" % (runs.size - 5), runs[: runs.size - 5], None))           # long stretches, n % 8 != 0
+    out.append(("geometric_8M", np.minimum(rng.geometric(0.25, 8 << 20) - 1, 1020).astype(np.int16), None))
+    # a given code of 2111 + 8 lengths of 12: without a match every run is R * L bits and every chunk fills the LDS image
+    all12 = np.full(2111 + 8, 12, np.uint8)
+    out.append(("all12_no_match", (np.arange(2 * 16384 + 300) % 2111).astype(np.int16), all12))
+    assert int(runs.min()) == 0
+    out.append(("all12_pixel_runs", runs[: runs.size - 5], all12))
     return out
 
 
@@ -43,14 +49,15 @@ def _code(pay):
     return huffr.code_lengths(huffr.token_counts(pay, base, int(pay.max()) - base + 1)), base
 
 
-def _check_pair(ctx, name, pay):
+def _check_pair(ctx, name, pay, ln=None):
     from tezip_amd import huffr
     base = int(pay.min())
     A = int(pay.max()) - base + 1
     want_counts = huffr.token_counts(pay, base, A)
     counts, gbase = ctx.huffr_counts(pay)
     assert gbase == base and counts.size == A + 8 and (counts == want_counts).all(), "%s: k_huffr_count against the numpy tokeniser" % name
-    ln = huffr.code_lengths(counts)
+    if ln is None:
+        ln = huffr.code_lengths(counts)
     want = np.frombuffer(huffr.pack_body(*huffr.encode_body(pay, ln, base)), np.uint8)
     got = ctx.huffr_encode_buf(pay, ln, base)
     assert got.size == want.size and (got == want).all(), "%s: the GPU stream differs from the numpy encoder's" % name
@@ -60,12 +67,19 @@ def _check_pair(ctx, name, pay):
     co, rb = got[: nchunks * 4].view("<u4"), got[nchunks * 4: nchunks * 4 + nruns * 2].view("<u2")
     words = got[huffr.body_bytes(pay.size, 0):].view("<u4")
     assert (huffr.decode_body(co, rb, words, pay.size, ln, base) == pay).all(), "%s: numpy decode of the GPU stream" % name
+    return co, rb
 
 
 def test_gpu_stream_is_the_numpy_stream(ctx):
-    for name, pay in _inputs():
-        assert name != "no_match" or huffr_tokens(pay) == 0
-        _check_pair(ctx, name, pay)
+    from tezip_amd import huffr
+    filled = 0
+    for name, pay, ln in _inputs():
+        assert not name.endswith("no_match") or huffr_tokens(pay) == 0
+        co, rb = _check_pair(ctx, name, pay, ln)
+        if name == "all12_no_match":                                    # or the test is not testing the bound
+            assert_fills_the_image(huffr, name, pay.size, co, rb)
+            filled += 1
+    assert filled == 1
 
 
 def huffr_tokens(pay):

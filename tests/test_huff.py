@@ -50,6 +50,33 @@ def synthetic_payloads(H):
     return out
 
 
+def filling_payloads(H):
+    """(name, payload, lengths) under GIVEN codes, none of them code_lengths' choice -- huff_tables accepts any code with
+    Kraft sum <= 1.  all12: 2111 symbols of 12 bits (Kraft 2111/4096), so every full run is R * L = 3072 bits and every full
+    chunk 6144 words, the whole LDS image of the kernels; all1: two symbols of one bit, every run exactly 8 words (no lane
+    shares a word with its neighbour) and a last run of one bit; incomplete: three symbols of 2 bits, a quarter of the decode
+    table reached by no code."""
+    rng = np.random.default_rng(13)
+    chunk = H.RUN * H.CHUNK_RUNS
+    out = [("all12_n%d" % (2 * chunk + 300), np.concatenate([np.arange(2111), rng.integers(0, 2111, 2 * chunk + 300 - 2111)]).astype(np.int16),
+            np.full(2111, 12, np.uint8))]
+    pay = rng.integers(0, 2, chunk + 256 + 1).astype(np.int16)
+    pay[0] = 0
+    out.append(("all1_n%d" % pay.size, pay, np.array([1, 1], np.uint8)))
+    pay = rng.integers(0, 3, chunk + 777).astype(np.int16)
+    pay[0] = 0
+    out.append(("incomplete_222_n%d" % pay.size, pay, np.array([2, 2, 2], np.uint8)))
+    return out
+
+
+def assert_fills_the_image(H, name, n, chunk_off, run_bits):
+    """The index of an all-12 stream: every full run is R * L bits, the first chunk takes all 6144 words."""
+    full = n // H.RUN
+    assert full >= 2 * H.CHUNK_RUNS and (np.asarray(run_bits[:full], np.int64) == H.RUN * H.MAX_LEN).all(), name
+    assert int(chunk_off[1]) - int(chunk_off[0]) == H.RUN * H.CHUNK_RUNS * H.MAX_LEN // 32 == 6144, name
+    assert int(chunk_off[2]) - int(chunk_off[1]) == 6144, name
+
+
 def _cost(counts, lengths):
     return int(np.sum(np.asarray(counts, np.int64) * np.asarray(lengths, np.int64)))
 
@@ -198,6 +225,23 @@ def test_numpy_pair_is_the_identity(huff):
         assert int(rb.astype(np.int64).sum()) == int(ln[pay.astype(np.int64) - base].astype(np.int64).sum()), name
         assert (huff.decode_body(co, rb, words, pay.size, ln, base) == pay).all(), name
         assert len(huff.pack_body(co, rb, words)) == huff.body_bytes(pay.size, words.size), name
+
+
+def test_numpy_pair_is_the_identity_under_given_codes(huff):
+    """So far the pair was the identity under optimal codes only; the kernels are held to it under any valid code."""
+    for name, pay, ln in filling_payloads(huff):
+        huff.check_lengths(ln)
+        assert huff.kraft_sum(ln) < 1 << 12 or ln.size == 2, name
+        co, rb, words = huff.encode_body(pay, ln, 0)
+        nruns, nchunks = huff.geometry(pay.size)
+        assert co.size == nchunks and rb.size == nruns and words.size == (int(ln[0]) * pay.size + 31) // 32, name
+        assert (huff.decode_body(co, rb, words, pay.size, ln, 0) == pay).all(), name
+        if name.startswith("all12"):
+            assert_fills_the_image(huff, name, pay.size, co, rb)
+        if name.startswith("all1_"):
+            assert (rb[:-1] == 256).all() and rb[-1] == 1 and co.tolist() == [0, 64 * 8], name
+    tab = huff.decode_table(np.array([2, 2, 2], np.uint8))
+    assert (tab[3::4] == (0 | (1 << 12))).all()                         # the unreachable quarter still advances a decoder
 
 
 def _file(huff, n=3 * 8 * 8 * 3, table=True, seed=0):

@@ -68,6 +68,37 @@ def test_numpy_pair_is_the_identity(mods):
         assert (R.decode_file(data, key_len=pay.size)[0] == pay).all()
 
 
+def filling_payloads(R):
+    """(name, payload, lengths) under a GIVEN code of 2111 + 8 lengths of 12 (Kraft 2119/4096): on a payload without any match
+    every full run is R * L = 3072 bits and every full chunk 6144 words, the whole LDS image of the kernels; on pixel runs the
+    tokens and their raw bits are coded under it too."""
+    rng = np.random.default_rng(11)
+    chunk = R.RUN * R.CHUNK_RUNS
+    ln = np.full(2111 + R.NTOK, 12, np.uint8)
+    out = [("all12_no_match", (np.arange(2 * chunk + 300) % 2111).astype(np.int16), ln)]           # s[j] != s[j - 3] everywhere
+    runs = np.repeat(rng.integers(0, 50, (4000, 3)), rng.geometric(0.05, 4000), 0).reshape(-1).astype(np.int16)
+    runs[:3] = 0
+    out.append(("all12_pixel_runs_n%d" % (runs.size - 5), runs[: runs.size - 5], ln))
+    return out
+
+
+def test_numpy_pair_is_the_identity_under_a_given_code(mods):
+    from test_huff import assert_fills_the_image
+    huff, R = mods
+    for name, pay, ln in filling_payloads(R):
+        R.check_lengths(ln)
+        assert int(pay.min()) == 0
+        co, rb, words = R.encode_body(pay, ln, 0)
+        nruns, nchunks = R.geometry(pay.size)
+        assert co.size == nchunks and rb.size == nruns and int(rb.astype(np.int64).max()) <= R.RUN * R.MAX_LEN, name
+        assert (R.decode_body(co, rb, words, pay.size, ln, 0) == pay).all(), name
+        if name == "all12_no_match":
+            assert int(R.token_counts(pay, 0, 2111)[2111:].sum()) == 0
+            assert_fills_the_image(R, name, pay.size, co, rb)
+        else:
+            assert int(R.token_counts(pay, 0, 2111)[2111:].sum()) > 1000 and pay.size > 2 * R.RUN * R.CHUNK_RUNS, name
+
+
 def test_vector_tokeniser_is_the_loop(mods):
     """tokenise (what encode_body uses) against tokenise_run, the plain loop over one run."""
     huff, R = mods

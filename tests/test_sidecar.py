@@ -140,3 +140,27 @@ def test_prefetch_hands_over_the_stream_in_order_and_raises_where_the_consumer_i
     next(it)
     pre.close()
     assert not pre.t.is_alive()
+
+
+def test_prefetch_defaults_are_the_module_constants_when_it_is_made(tmp_path, monkeypatch):
+    """piece_bytes / depth None = decompress.PREFETCH_PIECE_BYTES / PREFETCH_DEPTH as they are NOW (16 MB and 8 untouched), so a
+    test can make the ring of decompress.run turn over on a small stream."""
+    from tezip_amd import decompress, zstd
+    assert (decompress.PREFETCH_PIECE_BYTES, decompress.PREFETCH_DEPTH) == (16 << 20, 8)
+    assert (decompress.PUT_PIECE, decompress.FETCH_WINDOW_BYTES) == (16 << 20, 16 << 20)
+    data = np.arange(10_001, dtype=np.uint16).view(np.uint8)
+    path = tmp_path / "x.zst"
+    path.write_bytes(zstd.compress_array(data, 3, 0))
+    pre = decompress._Prefetch(str(path))
+    assert (pre.piece_bytes, pre.nbuf, pre.q.maxsize) == (16 << 20, 10, 8)
+    got = [p.copy() for _, p in pre]
+    pre.close()
+    assert len(got) == 1 and (got[0] == data).all()
+    monkeypatch.setattr(decompress, "PREFETCH_PIECE_BYTES", 2048)
+    monkeypatch.setattr(decompress, "PREFETCH_DEPTH", 1)
+    pre = decompress._Prefetch(str(path))
+    assert (pre.piece_bytes, pre.nbuf, pre.q.maxsize) == (2048, 3, 1)
+    got = [p.copy() for _, p in pre]                                  # 20 002 bytes: 9 pieces of 2 048 and one of 1 570
+    pre.close()
+    assert [g.size for g in got] == [2048] * 9 + [1570]
+    np.testing.assert_array_equal(np.concatenate(got), data)

@@ -47,6 +47,11 @@ def check_stream(shape, warm_up, payload_len, key_len):
 
 
 TAIL_ELEMS = _lib.TZ_NBINS + 8  # the longest trailer: table (<= 2111 symbols) + T + shape(5) + warm_up
+# piece sizes of the streaming paths, read when a run starts (tests/test_gpu_pieces.py shrinks them to make every loop iterate)
+PUT_PIECE = 16 << 20            # bytes of a coded body (TZH1 / TZR1 / TZK1) staged per huff_put / huffr_put / keys_put
+FETCH_WINDOW_BYTES = 16 << 20   # a fetch window holds the frames that fit in this many bytes (at least one)
+PREFETCH_PIECE_BYTES = 16 << 20  # _Prefetch: bytes of entropy.dat decompressed per piece
+PREFETCH_DEPTH = 8              # _Prefetch: pieces queued ahead of the consumer
 
 
 def coded_format(head):
@@ -73,8 +78,9 @@ def stage_coded_keys(ctx, keys, stack):
         raise ValueError("key_frame.dat describes the stack as %r (frames, height, width), entropy.dat's trailer as %r"
                          % ((keys.nt, keys.H, keys.W), tuple(stack)))
     ctx.keys_begin(keys.body.size, keys.nt, keys.H, keys.W, keys.idx, keys.pred, keys.lengths)
-    for off in range(0, keys.body.size, 16 << 20):
-        ctx.keys_put(off, keys.body[off: off + (16 << 20)])                 # pageable: the piece is free again on return
+    piece = PUT_PIECE
+    for off in range(0, keys.body.size, piece):
+        ctx.keys_put(off, keys.body[off: off + piece])                      # pageable: the piece is free again on return
     ctx.keys_decode()
 
 
@@ -100,9 +106,11 @@ class _Prefetch:
     queue the decoder's rollout first and collect the payload afterwards.  At most `depth` + 2 pieces exist at a time,
     whatever the length of the stream.  An error on the worker is raised where the caller iterates."""
 
-    def __init__(self, path, piece_bytes=16 << 20, depth=8):
+    def __init__(self, path, piece_bytes=None, depth=None):
         import queue
         import threading
+        piece_bytes = PREFETCH_PIECE_BYTES if piece_bytes is None else piece_bytes    # (None: the module constant now)
+        depth = PREFETCH_DEPTH if depth is None else depth
         self.path, self.piece_bytes = path, piece_bytes
         self.q = queue.Queue(maxsize=depth)
         self.nbuf = depth + 2     # `depth` queued + the one the caller holds + the one being filled
@@ -203,7 +211,7 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             ctx.prepare(hp, wp, 64 if nt > 64 else max(1, nt))
             stages.mark("model prepare")
             fb = H * W * 3
-            per = max(1, (16 << 20) // fb)
+            per = max(1, FETCH_WINDOW_BYTES // fb)
             if keys is not None:
                 stage_coded_keys(ctx, keys, (nt, H, W))
                 stages.mark("stage key_frame.dat + key-frame decode", ctx)
@@ -251,8 +259,9 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             per = stage_keys(nt, H, W, hp, wp)
             rollout(nt, warm_up)
             stages.mark("rollout (decoder) queued")
-            for off in range(0, coded.body.size, 16 << 20):
-                put(off, coded.body[off: off + (16 << 20)])             # pageable: the piece is free again on return
+            piece = PUT_PIECE
+            for off in range(0, coded.body.size, piece):
+                put(off, coded.body[off: off + piece])                  # pageable: the piece is free again on return
             expand()                                                    # -> the payload buffer, as payload_put leaves it
             stages.mark("stage entropy.dat + huffman decode", ctx)
         else:
