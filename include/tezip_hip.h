@@ -292,6 +292,29 @@ int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t payload_len, con
 int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
                       int shuffled, tz_frame_quality* out);
 
+/* ---- per-frame digests (no reference counterpart; `tezip.py -c --digests`, `-u --verify`; format TZD64 version 1 in
+ * DESIGN.md section 9, slow statement of it in tezip_amd/digest.py) ------------------------------------------------------
+ * For a frame of n bytes x[0..n) in (H, W, 3) memory order, all arithmetic mod 2^64:
+ *   digest = sum over i of mix(256 * i + x[i]),  mix = splitmix64's output function
+ *   (z = k + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31).
+ * mix is a bijection and the keys of a frame are distinct, so a change of one sample always changes the digest; the sum is
+ * commutative, so the value does not depend on how k_digest cuts a frame over lanes and workgroups (TEZIP_DIGEST_GRID
+ * forces the number of workgroups, a diagnostic).  An error-detection code, NOT a cryptographic hash: it guards against
+ * damage and against decoders that stopped agreeing with the encoder, not against an adversary.
+ * tz_frame_digests: the stand-alone form, nframes frames of frame_bytes bytes each, frames and out (nframes words) host or
+ * device.  frame_bytes >= 2^32 is TZ_ERR_INVALID before any launch; an empty frame has the digest 0. */
+int tz_frame_digests(tz_ctx* ctx, const uint8_t* frames, int nframes, size_t frame_bytes, unsigned long long* out);
+/* The digests of the decoded frames [first, first + count) that tz_decode / tz_decode_range left in the context with
+ * frames_out == NULL, taken where they lie, before any of them is fetched; frame indices follow tz_decoded_get's rule
+ * (sequence indices inside the decoded range).  TZ_ERR_STATE without such frames, TZ_ERR_INVALID for a range outside them. */
+int tz_decoded_digests(tz_ctx* ctx, int first, int count, unsigned long long* out);
+/* tz_encode_quality's twin: arguments, state rules and errors are exactly its own, and both run the same front (checks,
+ * unshuffle, mask, the decoder's tail into scratch), so they cannot disagree about what "decoded" means.  decoded[nt]: the
+ * digests of what the stored payload decodes to, i.e. of the images `-u` writes; original[nt] (may be NULL): those of the
+ * resident source frames.  Host or device; complete on return.  Nothing of the context changes. */
+int tz_encode_digests(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                      int shuffled, unsigned long long* decoded, unsigned long long* original);
+
 /* ---- operator seams, usable stand-alone (each mirrors one reference helper) -----------------
  * tz_delta_encode: compress.py:292-314.  pred: nframes padded f32 frames; orig: nframes
  * unpadded u8 frames; zero_mask[nframes] (host): 1 => that frame's delta is forced to 0. */

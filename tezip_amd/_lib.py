@@ -55,6 +55,9 @@ _SIGS = {
     "tz_undelta_carry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_int16)]),
     "tz_decode_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tz_encode_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "tz_encode_digests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_frame_digests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "tz_decoded_digests": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_frames_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "tz_frames_put": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_frames_fence": (C.c_int, [C.c_void_p]),
@@ -639,6 +642,43 @@ class Context:
         tb = None if table is None else np.ascontiguousarray(table, np.int16)
         self._ck(self.lib.tz_encode_quality(self.h, None if resident else _ptr(payload), n, _ptr(tb), tl, int(bool(shuffle)),
                                             out.ctypes.data))
+        return out
+
+    # ---- per-frame digests (tz_*_digests; format TZD64: tezip_amd/digest.py)
+    def encode_digests(self, payload="resident", table=None, shuffle=False, original=True):
+        """tz_encode_digests after rollout + encode, arguments as encode_quality's -> (decoded, original): uint64[nt] each,
+        the digests of what the payload decodes to and of the resident source frames (None with original=False)."""
+        nt, h, w = self._shape
+        n = nt * h * w * 3
+        resident = isinstance(payload, str) and payload == "resident"
+        if not resident and _numel(payload) != n:
+            raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
+        dec = np.zeros(nt, np.uint64)
+        org = np.zeros(nt, np.uint64) if original else None
+        tl = -1 if table is None else len(table)
+        tb = None if table is None else np.ascontiguousarray(table, np.int16)
+        self._ck(self.lib.tz_encode_digests(self.h, None if resident else _ptr(payload), n, _ptr(tb), tl, int(bool(shuffle)),
+                                            dec.ctypes.data, None if org is None else org.ctypes.data))
+        return dec, org
+
+    def frame_digests(self, frames, nframes=None, frame_bytes=None, out=None):
+        """tz_frame_digests of a host array or device tensor of uint8: frames[0] is one frame, or give nframes and frame_bytes
+        for a flat buffer.  out: uint64 host array or device tensor of int64 (the same 64 bits), default a new host array."""
+        if nframes is None:
+            nframes = int(frames.shape[0])
+            frame_bytes = _numel(frames) // nframes if nframes else 0
+        if _numel(frames) != int(nframes) * int(frame_bytes):
+            raise ValueError("buffer holds %d bytes, expected %d frames of %d" % (_numel(frames), nframes, frame_bytes))
+        if out is None:
+            out = np.zeros(int(nframes), np.uint64)
+        self._ck(self.lib.tz_frame_digests(self.h, _ptr(frames), int(nframes), int(frame_bytes), _ptr(out)))
+        return out
+
+    def decoded_digests(self, first, count):
+        """tz_decoded_digests: uint64[count] of the frames decode(..., out="resident") / decode_range(..., out="resident")
+        left in the context (sequence indices, as decoded_get)."""
+        out = np.zeros(int(count), np.uint64)
+        self._ck(self.lib.tz_decoded_digests(self.h, int(first), int(count), out.ctypes.data))
         return out
 
     # ---- opt-in Huffman coder (tz_huff_*; format: tezip_amd/huff.py)

@@ -23,7 +23,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, huff, huffr, keycoder, quality, sidecar, weights, zstd
+from . import _lib, digest, huff, huffr, keycoder, quality, sidecar, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -410,7 +410,7 @@ def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
 
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
-        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd"):
+        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -424,6 +424,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     key frames alone as predictor residuals under a Huffman code (tezip_amd/keycoder.py) -- not readable by the reference,
     `-u` recognises it by its magic; smaller than zstd-9 on smooth frames and larger on sparse ones.  Independent of CODER
     and SHUFFLE.  Single-GPU jobs only.
+    DIGESTS (--digests; NOT in the reference): also write frame_digests.json (tezip_amd/digest.py) -- per frame the digest
+    of what the stored payload decodes to and of the source frame, both taken on the device (tz_encode_digests); `-u`
+    verifies its frames against them before it writes an image.  The other files are byte for byte what they are without
+    it; the file is written last.  Single-GPU jobs only.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -439,6 +443,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if tzdist.active() is not None:
         if REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
             print("ERROR: --report is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU")
+            sys.exit(2)
+        if DIGESTS:  # likewise
+            print("ERROR: --digests is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU")
             sys.exit(2)
         return _run_sharded(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE,
                             VERBOSE, ENTROPY_RUN, device, SHUFFLE, CODER)
@@ -484,6 +491,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 if VERBOSE:
                     print("quality:{0}".format(time.time() - t0) + "[sec]")
                 stages.mark("quality report (device)")
+            if DIGESTS:  # likewise: the decoder's tail into scratch, one pass over what it yields and one over the originals
+                t0 = time.time()
+                dig = ctx.encode_digests("resident", table if ENTROPY_RUN else None, shuffle=SHUFFLE)
+                if VERBOSE:
+                    print("digests:{0}".format(time.time() - t0) + "[sec]")
+                stages.mark("frame digests (device)")
             if VERBOSE:
                 prof = ctx.prof_get()
                 print("error_bound:{0}".format(prof["quant"][0] / 1e3) + "[sec]")
@@ -505,6 +518,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 quality.write(OUTPUT_DIR, report)
                 for line in quality.stdout_lines(report):
                     print(line)
+            if DIGESTS:  # last: every other file is what it is without the flag
+                digest.write(OUTPUT_DIR, digest.make(dig[0], dig[1], (H, W, 3)))
         finally:
             ctx.close()
 

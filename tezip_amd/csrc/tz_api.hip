@@ -139,6 +139,8 @@ extern "C" int tz_ctx_create(int device, void* hip_stream, tz_ctx** out) {
         if (e) ctx->wino_ipw = atoi(e);
         e = getenv("TEZIP_QUALITY_GRID");        // diagnostic: workgroups of k_quality (0 = per launch; tests of launch-shape invariance)
         if (e) ctx->quality_grid = atoi(e);
+        e = getenv("TEZIP_DIGEST_GRID");         // diagnostic: workgroups of k_digest (0 = per launch; tests of launch-shape invariance)
+        if (e) ctx->digest_grid = atoi(e);
     }
     ctx->device = device;
     {
@@ -538,7 +540,7 @@ static const char* kProfNames[TZP_COUNT] = {"conv3x3_mfma", "err0", "delta", "qu
                                             "lut_remap", "undelta_scan", "reconstruct", "sse",
                                             "conv16_lds_dma", "conv16b_level0", "conv_small_valu", "conv3x3_general",
                                             "convlat_small_grid", "wino_pa2", "table_create", "quant_serial_chains",
-                                            "undelta_carry", "quality", "huffman"};
+                                            "undelta_carry", "quality", "huffman", "digest"};
 
 namespace {
 struct RoctxApi {
@@ -1911,16 +1913,15 @@ extern "C" int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t paylo
     return decode_frames(ctx, "tz_decode_range", payload, payload_len, table, table_len, first, count, frames_out);
 }
 
-// The report of `-c --report` (include/tezip_hip.h): the decoder's tail over the payload on the ENCODER's predictions and
-// frames -- the reconstruct reads frames only where the mask says "key", and there the encoder's originals are the bytes
-// key_frame.dat stores -- into pool scratch, then k_quality against the originals.  Only scratch is written.
-extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
-                                 int shuffled, tz_frame_quality* out) {
-    tz_roctx_range roctx_("tz_encode_quality");
-    if (!ctx || !out) return TZ_ERR_INVALID;
-    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE))
-        return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_quality needs the encoder rollout of a tz_rollout");
-    TZ_TRY(tz_check_pred_contract(ctx, "tz_encode_quality"));
+// What the stored payload of an encode decodes to (include/tezip_hip.h: tz_encode_quality, tz_encode_digests): the decoder's
+// tail over the payload on the ENCODER's predictions and frames -- the reconstruct reads frames only where the mask says
+// "key", and there the encoder's originals are the bytes key_frame.dat stores -- into pool scratch (*d_dec, nt*H*W*3
+// bytes, queued on the context's stream).  Only scratch is written; the caller releases the pool.  One statement of
+// "decoded" for every entry point that describes it.
+static int encode_decoded(tz_ctx* ctx, const char* who, const int16_t* payload, size_t payload_len, const int16_t* table,
+                          int table_len, int shuffled, const uint8_t** d_dec_out) {
+    if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "%s needs the encoder rollout of a tz_rollout", who);
+    TZ_TRY(tz_check_pred_contract(ctx, who));
     TZ_TRY(check_table(ctx, table, table_len));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
     const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe;
@@ -1932,8 +1933,6 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
     if (payload_len != N)
         return tz_fail(ctx, TZ_ERR_INVALID, "payload holds %zu elements, the encoded stack %zu", payload_len, N);
     if (shuffled && (N & 7)) return tz_fail(ctx, TZ_ERR_INVALID, "byte shuffle needs a multiple of 8 elements");
-    std::vector<tz_out> outs;
-    tz_out o;
     const void* d_pay = nullptr;
     void *d_plain = nullptr, *d_mask = nullptr, *d_dec = nullptr;
     int rc = tz_dev_in(ctx, payload, N * 2, &d_pay);
@@ -1942,8 +1941,6 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
         if (rc == TZ_OK) rc = tzk_shuffle(ctx, (const int16_t*)d_pay, N, (uint8_t*)d_plain, 1);
         d_pay = d_plain;
     }
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_quality) * nt, &o);
-    if (rc == TZ_OK) outs.push_back(o);
     const std::vector<uint8_t> recon = recon_key_mask(ctx->key_mask.data(), nt, ctx->warm_up);
     if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_mask);
     if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, recon.data(), nt);
@@ -1954,9 +1951,89 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
     if (rc == TZ_OK)   // the launches of tz_decode
         rc = tzk_decode_tail(ctx, (const int16_t*)d_pay, h_lut, 1, 0, 0, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H,
                              W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
-    if (rc == TZ_OK) rc = tzk_quality(ctx, ctx->d_frames, (const uint8_t*)d_dec, nt, fe, (tz_frame_quality*)o.dev);
+    *d_dec_out = (const uint8_t*)d_dec;
+    return rc;
+}
+
+// The report of `-c --report`: k_quality of the decoded stack against the originals.
+extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                                 int shuffled, tz_frame_quality* out) {
+    tz_roctx_range roctx_("tz_encode_quality");
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    std::vector<tz_out> outs;
+    tz_out o;
+    const uint8_t* d_dec = nullptr;
+    int rc = encode_decoded(ctx, "tz_encode_quality", payload, payload_len, table, table_len, shuffled, &d_dec);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_quality) * ctx->nt, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    if (rc == TZ_OK) rc = tzk_quality(ctx, ctx->d_frames, d_dec, ctx->nt, (size_t)ctx->H * ctx->W * 3, (tz_frame_quality*)o.dev);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device records too: complete on return)
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// The records of `-c --digests`: k_digest of the decoded stack, and of the resident originals when asked for.
+extern "C" int tz_encode_digests(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                                 int shuffled, unsigned long long* decoded, unsigned long long* original) {
+    tz_roctx_range roctx_("tz_encode_digests");
+    if (!ctx || !decoded) return TZ_ERR_INVALID;
+    std::vector<tz_out> outs;
+    tz_out o;
+    const uint8_t* d_dec = nullptr;
+    int rc = encode_decoded(ctx, "tz_encode_digests", payload, payload_len, table, table_len, shuffled, &d_dec);
+    const int nt = ctx->nt;
+    const size_t fe = (size_t)ctx->H * ctx->W * 3;
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, decoded, sizeof(unsigned long long) * nt, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    if (rc == TZ_OK) rc = tzk_digest(ctx, d_dec, nt, fe, (unsigned long long*)o.dev);
+    if (rc == TZ_OK && original) {
+        rc = tz_dev_out(ctx, original, sizeof(unsigned long long) * nt, &o);
+        if (rc == TZ_OK) outs.push_back(o);
+        if (rc == TZ_OK) rc = tzk_digest(ctx, ctx->d_frames, nt, fe, (unsigned long long*)o.dev);
+    }
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device words too: complete on return)
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// TZD64 digests of any unpadded uint8 stack (`-u --verify` on the whole-array path; tests against tezip_amd/digest.py).
+extern "C" int tz_frame_digests(tz_ctx* ctx, const uint8_t* frames, int nframes, size_t frame_bytes, unsigned long long* out) {
+    tz_roctx_range roctx_("tz_frame_digests");
+    if (!ctx || nframes < 0 || (nframes > 0 && (!out || (!frames && frame_bytes)))) return TZ_ERR_INVALID;
+    if (frame_bytes >> 32) return tz_fail(ctx, TZ_ERR_INVALID, "frames of %zu bytes: a digest covers fewer than 2^32", frame_bytes);
+    if (nframes == 0) return TZ_OK;
+    std::vector<tz_out> outs;
+    tz_out o;
+    const void* d_in = nullptr;
+    int rc = tz_dev_in(ctx, frames, (size_t)nframes * frame_bytes, &d_in);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(unsigned long long) * nframes, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    if (rc == TZ_OK) rc = tzk_digest(ctx, (const uint8_t*)d_in, nframes, frame_bytes, (unsigned long long*)o.dev);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// The same over the decoded frames a tz_decode / tz_decode_range with frames_out == NULL left in the context (`-u --verify`
+// on the streaming path, before any frame is fetched); frame indices as tz_decoded_get's.
+extern "C" int tz_decoded_digests(tz_ctx* ctx, int first, int count, unsigned long long* out) {
+    tz_roctx_range roctx_("tz_decoded_digests");
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    if (!ctx->d_out || !ctx->have_decoded) return tz_fail(ctx, TZ_ERR_STATE, "tz_decoded_digests needs the resident frames of a tz_decode / tz_decode_range");
+    if (first < ctx->dec_first || count < 0 || first > ctx->dec_first + ctx->dec_count || count > ctx->dec_first + ctx->dec_count - first)
+        return tz_fail(ctx, TZ_ERR_INVALID, "frames [%d, %d + %d) outside the resident decoded stack", first, first, count);
+    if (count == 0) return TZ_OK;
+    const size_t fsz = (size_t)ctx->H * ctx->W * 3;
+    std::vector<tz_out> outs;
+    tz_out o;
+    int rc = tz_dev_out(ctx, out, sizeof(unsigned long long) * count, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    if (rc == TZ_OK) rc = tzk_digest(ctx, ctx->d_out + (size_t)(first - ctx->dec_first) * fsz, count, fsz, (unsigned long long*)o.dev);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
     tz_pool_release_all(ctx);
     return rc;
 }

@@ -2489,6 +2489,109 @@ int tzk_quality(tz_ctx* ctx, const uint8_t* orig, const uint8_t* dec, int nframe
     return TZ_OK;
 }
 
+// ------------------------------------------------------------------------------ frame digests
+// TZD64 version 1 (slow statement in tezip_amd/digest.py): per frame of an unpadded uint8 stack the
+// sum mod 2^64 over its bytes of mix(256 * i + x[i]), i the byte's position inside ITS frame and mix splitmix64's output
+// function.  An error-detection code, not a cryptographic hash.  The sum is commutative, so any cut of a frame over lanes,
+// waves and workgroups gives the same 64 bits.  Streaming, 1 B read per element, shaped like k_quality: a workgroup owns a
+// contiguous run of whole tiles (256 lanes x one 16-byte load), cut without regard to frame boundaries; the running sum
+// belongs to one frame, and where a tile crosses the frame's end the workgroup flushes (shuffle reduction per wave, LDS
+// across the four waves, then ONE relaxed u64 add per frame it touched, agent scope -- the kernel's only global atomic) and
+// carries on with the next frame.  Tiles are laid over the stack from the 16-byte boundary at or in front of its first
+// byte: positions are v = element index + pre (pre = address mod 16), so every full lane is an aligned 16-byte load, and
+// the lane that holds the bytes in front of the first boundary, like the one that holds the tail, loads byte by byte with
+// every index checked against [pre, n + pre): nothing outside the stack is read.  frame_bytes < 2^32, so a position is
+// 32 bits and a key 40; the 64-bit multiplies are what the compiler builds from 32-bit ones.
+static constexpr int DG_TILE = 256 * 16;   // elements per workgroup and step
+
+__device__ __forceinline__ unsigned long long dg_mix(unsigned long long k) {
+    unsigned long long z = k + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// every thread of the workgroup calls this (block-uniform control flow); word = the frame's digest
+__device__ __forceinline__ void dg_flush(unsigned long long sum, unsigned long long* red, unsigned long long* word) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sum = red[0] + red[1] + red[2] + red[3];
+        __hip_atomic_fetch_add(word, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();   // red is written again by the next flush
+}
+
+// positions v .. v+15, packed 4 per word; bytes outside [pre, end) are not read (and 0 here)
+__device__ __forceinline__ uint4 dg_fetch(const uint8_t* __restrict__ x, unsigned pre, size_t v, size_t end) {
+    if (v >= pre && v + 16 <= end) return *(const uint4*)(x + (v - pre));
+    unsigned w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (v + j >= pre && v + j < end) w[j >> 2] |= (unsigned)x[v + j - pre] << (8 * (j & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// nv = n + pre positions; per_block: positions per workgroup, a multiple of DG_TILE
+__global__ __launch_bounds__(256) void k_digest(const uint8_t* __restrict__ x, size_t nv, size_t fe, unsigned pre, size_t per_block,
+                                                unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long red[4];
+    const size_t b0 = (size_t)blockIdx.x * per_block;
+    if (b0 >= nv) return;   // (workgroup-uniform)
+    const size_t b1 = min(nv, b0 + per_block);
+    size_t f = (max(b0, (size_t)pre) - pre) / fe;   // the frame the running sum belongs to
+    unsigned long long sum = 0;
+    uint4 cur = dg_fetch(x, pre, b0 + (size_t)threadIdx.x * 16, min(b1, b0 + (size_t)DG_TILE));
+    for (size_t t = b0; t < b1; t += DG_TILE) {
+        const size_t tend = min(b1, t + (size_t)DG_TILE), e = t + (size_t)threadIdx.x * 16;
+        uint4 nxt = make_uint4(0, 0, 0, 0);   // the next tile's load is in flight while this one is mixed
+        if (tend < b1) nxt = dg_fetch(x, pre, e + DG_TILE, min(b1, tend + (size_t)DG_TILE));
+        const unsigned w[4] = {cur.x, cur.y, cur.z, cur.w};
+        cur = nxt;
+        for (size_t lo = max(t, (size_t)pre);;) {   // segments [lo, lim) of the tile inside frame f
+            const size_t fs = f * fe + pre, bnd = fs + fe, lim = min(bnd, tend);
+            if (e >= lo && e + 16 <= lim) {          // the lane's 16 bytes lie inside the segment
+                const unsigned p0 = (unsigned)(e - fs);
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    sum += dg_mix(((unsigned long long)(p0 + j) << 8) | ((w[j >> 2] >> (8 * (j & 3))) & 0xffu));
+            } else if (e + 16 > lo && e < lim) {     // some of them do
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (e + j >= lo && e + j < lim)
+                        sum += dg_mix(((unsigned long long)(unsigned)(e + j - fs) << 8) | ((w[j >> 2] >> (8 * (j & 3))) & 0xffu));
+            }
+            if (lim < bnd) break;                    // frame f goes on behind this tile
+            dg_flush(sum, red, out + f);
+            sum = 0;
+            ++f;
+            lo = lim;
+            if (lo >= tend) break;
+        }
+    }
+    if (f * fe + pre < b1) dg_flush(sum, red, out + f);   // (the frame began inside this run and goes on behind it)
+}
+
+int tzk_digest(tz_ctx* ctx, const uint8_t* x, int nframes, size_t fe, unsigned long long* d_out) {
+    if (nframes <= 0) return TZ_OK;
+    if (fe >> 32) return tz_fail(ctx, TZ_ERR_INVALID, "frames of %zu bytes: a digest covers fewer than 2^32", fe);
+    TZ_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * nframes, ctx->stream));
+    if (fe == 0) return TZ_OK;   // (the digest of no bytes)
+    const unsigned pre = (unsigned)((uintptr_t)x & 15);
+    const size_t nv = (size_t)nframes * fe + pre;
+    const size_t tiles = (nv + DG_TILE - 1) / DG_TILE;
+    size_t G = ctx->digest_grid > 0 ? (size_t)ctx->digest_grid : (size_t)grid_for(tiles, 1);
+    G = std::max<size_t>(1, std::min(G, tiles));
+    const size_t per_block = (tiles + G - 1) / G * DG_TILE;
+    G = (nv + per_block - 1) / per_block;   // (no workgroup without a tile)
+    tz_prof_scope ps(ctx, TZP_DIGEST);
+    hipLaunchKernelGGL(k_digest, dim3((unsigned)G), dim3(256), 0, ctx->stream, x, nv, fe, pre, per_block, d_out);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // ------------------------------------------------------------------------------ window SSE
 // compress.py:246: mean((X_test_pad - pred)^2) in float64 over PADDED frames.  Per frame the
 // sum is taken in a fixed order so that it is reproducible: 4096-element blocks; thread t sums

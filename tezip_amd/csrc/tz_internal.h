@@ -35,6 +35,7 @@ enum tz_prof_class {
     TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality)
     TZP_HUFF,       // opt-in Huffman coder: k_huff_count / k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec (and k_huffr_*),
                     // and the key-frame coder in front of it: k_key_hist / k_key_resid / k_key_unresid_*
+    TZP_DIGEST,     // per-frame digests TZD64 (k_digest: tz_frame_digests, tz_decoded_digests, tz_encode_digests)
     TZP_COUNT
 };
 
@@ -63,6 +64,7 @@ struct tz_ctx {
     int num_cus = 256;                // compute units of the device (k_wino: column blocks per workgroup)
     int wino_ipw = 0;                 // TEZIP_WINO_IPW (measurements): column blocks per k_wino workgroup, 0 = chosen per launch
     int quality_grid = 0;             // TEZIP_QUALITY_GRID (diagnostic): workgroups of k_quality, 0 = chosen per launch
+    int digest_grid = 0;              // TEZIP_DIGEST_GRID (diagnostic): workgroups of k_digest, 0 = chosen per launch
     // rollout-resident data
     int nt = 0, H = 0, W = 0, Hp = 0, Wp = 0, warm_up = 0;
     uint8_t* d_frames = nullptr;      // nt*H*W*3 (encoder: originals; decoder: key stack)
@@ -312,6 +314,8 @@ int tzk_reconstruct(tz_ctx*, const float* pred, const uint8_t* key, const uint8_
                     int nframes, int H, int W, int Hp, int Wp, uint8_t* out);
 // per-frame (sse, max |dec - orig|, #changed) of two unpadded nframes x fe uint8 stacks; d_out (device) is cleared here
 int tzk_quality(tz_ctx*, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out);
+// TZD64 digests of nframes frames of fe bytes (fe < 2^32, else TZ_ERR_INVALID before any launch); d_out: nframes words, cleared here
+int tzk_digest(tz_ctx*, const uint8_t* x, int nframes, size_t fe, unsigned long long* d_out);
 // Huffman coder.  Geometry: runs of TZ_HUFF_RUN symbols, chunks of TZ_HUFF_CHUNK_RUNS runs.
 static constexpr int TZ_HUFF_L = 12, TZ_HUFF_RUN = 256, TZ_HUFF_CHUNK_RUNS = 64;
 static constexpr int TZ_HUFF_COUNT_BINS = 4096, TZ_HUFF_COUNT_BIAS = 1024;   // k_huff_count: bin = value + bias

@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from . import _lib, huff, huffr, keycoder, sidecar, zstd
+from . import _lib, digest, huff, huffr, keycoder, sidecar, zstd
 from . import dist as tzdist
 from .compress import SHUFFLE_MARK, make_context, open_model
 from .data_utils import padding_shape
@@ -100,6 +100,41 @@ def adopt_contract(DATA_DIR, wts, VERBOSE):
     return contract
 
 
+VERIFY_MODES = ("auto", "require", "off")
+
+
+def check_verify(mode, data_dir, sharded=False):
+    """The refusals of --verify that need no GPU, for tezip.py and for a direct caller of run(): None, or the message."""
+    if mode not in VERIFY_MODES:
+        return "--verify takes one of %s, got %r" % (", ".join(VERIFY_MODES), mode)
+    if mode == "require" and sharded:
+        return "--verify require is not available for a sharded job (WORLD_SIZE > 1), which does not verify: run it on one GPU"
+    if mode == "require" and not digest.present(data_dir):
+        return "--verify require: %s holds no %s (compress with --digests)" % (data_dir, digest.NAME)
+    return None
+
+
+def check_records(records, nt, H, W):
+    """frame_digests.json against the stack the stream describes; a contradiction ends the run with EXIT STATUS 2 (the error
+    class of adopt_contract: nothing was written)."""
+    try:
+        digest.validate(records, nt, (H, W, 3))
+    except ValueError as e:
+        print("ERROR:", e)
+        sys.exit(2)
+
+
+def verify_frames(records, got, first, file_names):
+    """The digests `got` of the decoded frames first, first + 1, ... against the recorded ones, before any image is written:
+    a mismatch names the frames (ten at the most, the rest counted) and ends the run with EXIT STATUS 3."""
+    bad = digest.mismatches(records, got, first)
+    if bad:
+        for line in digest.mismatch_lines(bad, file_names):
+            print(line)
+        sys.exit(3)
+    print("verified: %d frames" % len(got))
+
+
 class _Prefetch:
     """zstd.stream_decompress of one file on a worker thread (libzstd releases the GIL), its pieces copied into a ring of
     host buffers and handed over through a bounded queue: the caller -- the only thread that touches the context -- can
@@ -158,7 +193,7 @@ class _Prefetch:
 
 
 def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shape, VERBOSE, device, contract=None, stack=None,
-                   frames=None):
+                   frames=None, records=None):
     """decompress.py:87-279 with nothing of size nt*H*W on the host: entropy.dat is decompressed
     piece by piece straight into HBM (the trailer is read from the last piece), key_frame.dat
     likewise, the decoded frames come back window by window and are PNG-encoded on a thread pool
@@ -169,7 +204,9 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
     the key frames are staged and the decoder's rollout is queued FIRST, entropy.dat being decompressed on a worker
     thread meanwhile, and the trailer is checked against it when it arrives.
     `frames` = (A, B): only frames [A, B) are rolled out, decoded and written (tz_rollout_decode_range / tz_decode_range);
-    the whole stream is still staged, because its trailer holds the table and the shape."""
+    the whole stream is still staged, because its trailer holds the table and the shape.
+    `records` = the validated frame_digests.json, or None: the decoded frames are checked against it where they lie in HBM
+    (tz_decoded_digests), before the first of them is fetched."""
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
     from .compress import _Stages, io_threads
@@ -321,10 +358,15 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
                 per = stage_keys(nt, H, W, hp, wp)
                 rollout(nt, warm_up)
         fb = H * W * C
+        if records is not None:
+            check_records(records, nt, H, W)
         stages.mark("rollout (decoder)", ctx)
         lo, hi = frames or (0, nt)
         ctx.decode_range(None, table, lo, hi - lo, out="resident")
         stages.mark("decode tail (frames resident)", ctx)
+        if records is not None:
+            verify_frames(records, ctx.decoded_digests(lo, hi - lo), lo, file_names)
+            stages.mark("verify frame digests")
         if VERBOSE:
             prof = ctx.prof_get()
             if table is not None:
@@ -362,9 +404,15 @@ def check_frames(frames, nt):
         raise ValueError("frame range %d:%d is outside the %d frames of this sequence (0 <= A < B <= %d)" % (a, b, nt, nt))
 
 
-def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=None):
+def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=None, verify="auto"):
     """frames: None = every frame (the reference's behaviour), or (A, B) = write file_names[A:B] only, byte-identical to
-    what a whole decode writes for those names (B None = to the end).  Not in the reference."""
+    what a whole decode writes for those names (B None = to the end).  Not in the reference.
+    verify (--verify; not in the reference): "auto" = when the directory holds frame_digests.json (`-c --digests`,
+    tezip_amd/digest.py) the decoded frames -- those of `frames` only -- are checked against it on the device before an
+    image is written: a mismatch names the frames, writes nothing and exits with status 3, a match prints
+    "verified: <count> frames"; a directory without the file decodes as ever.  "require" = the same, and a missing file
+    is exit status 2 before a GPU is touched.  "off" = never check: the way to salvage a damaged directory.  A sharded
+    job does not verify (auto: rank 0 says so; require: refused)."""
     if not GPU_FLAG:
         print("ERROR: this build runs the decompression path on an AMD MI355X only (no CPU path).")
         exit()
@@ -374,6 +422,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
         print("ERROR: a frame range (--frames) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
         sys.exit(2)
     rank0 = job is None or job[0] == 0
+    problem = check_verify(verify, DATA_DIR, job is not None)
+    if problem:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
+        print("ERROR:", problem)
+        sys.exit(2)
     # every rank of a sharded job writes the images of its own windows: each makes the directory (on one node they race for
     # the same one, hence exist_ok; on node-local paths each node gets its share -- INTEGRATION.md section 3)
     os.makedirs(OUTPUT_DIR, exist_ok=True)
@@ -395,13 +447,29 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
             print("ERROR:", e)
             sys.exit(2)
 
+    records = None
+    if verify != "off" and digest.present(DATA_DIR):
+        if job is not None:
+            if rank0:
+                print("NOTE: a sharded job (WORLD_SIZE > 1) does not verify %s: run -u on one GPU to check the frames" % digest.NAME)
+        else:
+            try:   # a damaged file is an error, not 'absent': same class and exit status as adopt_contract's
+                records = digest.read(DATA_DIR, frames=len(file_names))
+            except ValueError as e:
+                print("ERROR:", e)
+                sys.exit(2)
+
     cfg, wts, model_shape = open_model(WEIGHTS_DIR)
     contract = adopt_contract(DATA_DIR, wts, VERBOSE)
     if job is None and not os.environ.get("TEZIP_NO_STREAMING"):
         # (the sidecar passed adopt_contract: it is readable or absent)
         stack = None if os.environ.get("TEZIP_NO_EARLY_ROLLOUT") else sidecar.stack_of(sidecar.read(DATA_DIR))
-        done = _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shape, VERBOSE, device, contract, stack,
-                              frames)
+        if records is not None:
+            done = _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shape, VERBOSE, device, contract, stack,
+                                  frames, records)
+        else:
+            done = _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shape, VERBOSE, device, contract, stack,
+                                  frames)
         if done:
             return
 
@@ -456,6 +524,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
         exit()
     if frames is not None:
         check_frames(frames, nt)
+    if records is not None:
+        check_records(records, nt, H, W)
 
     if job:
         device = tzdist.init_from_env()
@@ -494,6 +564,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
                 if table is not None:
                     print("replacing_based_on_frequency:{0}".format(prof["lut_remap"][0] / 1e3) + "[sec]")
                 print("finding_difference:{0}".format(prof["undelta_scan"][0] / 1e3) + "[sec]")
+            if records is not None:   # the whole-array path: the digests of what it decoded (tz_frame_digests), before any image
+                verify_frames(records, ctx.frame_digests(frames), first, file_names)
     finally:
         ctx.close()
 

@@ -53,6 +53,13 @@ FLAG_TABLE = (
     # predictor residuals Huffman-coded by the GPU (tezip_amd/keycoder.py; the reference cannot read such a file, -u recognises
     # it by its magic).  Much smaller on smooth frames, LARGER than zstd on sparse ones (README): check with --report's ratio
     (None, "--key-coder", dict(type=str, choices=("zstd", "huff"), default="zstd", dest="key_coder")),
+    # not in the reference: with -c, also write frame_digests.json (tezip_amd/digest.py): per frame the digest of what the stored
+    # payload decodes to and of the source frame, taken on the GPU (compress.run(DIGESTS=True)).  The other files do not change
+    (None, "--digests", dict(action="store_true", dest="digests")),
+    # not in the reference: with -u, what to do about frame_digests.json.  auto (also when the flag is absent) = when the file
+    # is there, the decoded frames are checked against it on the GPU before an image is written (a mismatch: exit status 3, no
+    # image); require = the same, and a directory without the file is refused; off = never check (salvage a damaged directory)
+    (None, "--verify", dict(type=str, choices=decompress.VERIFY_MODES, default=None, dest="verify")),
 )
 
 TEXT = {
@@ -150,6 +157,30 @@ def check_key_coder_flag(arg):
     return compress.check_key_coder(arg.key_coder, int(os.environ.get("WORLD_SIZE", "1")) > 1)
 
 
+def check_digests_flag(arg):
+    """--digests is valid with -c of one single-GPU job, without --sweep.  Returns None, or the message of a refusal."""
+    if not getattr(arg, "digests", False):
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--digests is valid with -c (--compress) only"
+    if getattr(arg, "sweep", None) is not None:
+        return "--digests cannot be combined with --sweep"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--digests is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+    return None
+
+
+def check_verify_flag(arg):
+    """--verify is valid with -u only; `require` needs frame_digests.json in the directory and one GPU.  Returns None, or the
+    message of a refusal."""
+    mode = getattr(arg, "verify", None)
+    if mode is None:
+        return None
+    if arg.uncompress is None or arg.learn is not None or arg.compress is not None:
+        return "--verify is valid with -u (--uncompress) only"
+    return decompress.check_verify(mode, arg.uncompress[1], int(os.environ.get("WORLD_SIZE", "1")) > 1)
+
+
 def probe_gpu(force_cpu):
     """tezip.py:12-21 asked TensorFlow for a GPU; here a context on device 0 must open."""
     if force_cpu:
@@ -208,6 +239,14 @@ def _main(arg):
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_digests_flag(arg)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
+    problem = check_verify_flag(arg)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # launched by torch.distributed.run: one rank per GPU
         from . import dist as tzdist
         tzdist.init_from_env()
@@ -224,6 +263,8 @@ def _main(arg):
     if chosen[0] == "uncompress":
         print("uncompress mode")
         model, src, dst = arg.uncompress
+        if getattr(arg, "verify", None) is not None:
+            return decompress.run(model, src, dst, gpu, arg.verbose, frames=frames, verify=arg.verify)
         if frames is not None:
             return decompress.run(model, src, dst, gpu, arg.verbose, frames=frames)
         return decompress.run(model, src, dst, gpu, arg.verbose)
@@ -238,6 +279,10 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if getattr(arg, "digests", False):
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"), DIGESTS=True)
     if getattr(arg, "key_coder", "zstd") != "zstd":
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
