@@ -444,6 +444,26 @@ int tz_keys_decode(tz_ctx* ctx);
 int tz_keys_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* pred, int16_t* sym);
 int tz_keys_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* pred, uint8_t* frames);
 
+/* ---- the same with gray key frames stored once (`--key-coder huffg`, format TZK2 in DESIGN.md section 9, slow statement of it
+ * in tezip_amd/keycoderg.py) ---------------------------------------------------------------------------------------------------
+ * A key frame whose three channels are equal at every pixel is GRAY: it contributes the H * W residuals of channel 0, and the
+ * decoder writes each sample to all three channels.  predg: nkeys pred bytes, bits 0-1 the predictor id, bit 2 (value 4) GRAY;
+ * TZ_ERR_INVALID above 7.  The symbols of frame k start at the sum of the counts of the frames before it.  The tz_keysg_*
+ * calls share the buffers of tz_keys_*; a stream staged by tz_keysg_begin is refused by tz_keys_put / tz_keys_decode and the
+ * other way round (TZ_ERR_INVALID / TZ_ERR_STATE), and each begin discards what the other had staged.
+ * tz_keys_gray: gray[k] = 1 iff frame idx[k] of the resident stack is GRAY (k_key_gray, one read of the key frames). */
+int tz_keys_gray(tz_ctx* ctx, const int* idx, int nkeys, uint8_t* gray);
+int tz_keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* predg, const uint8_t* lengths, size_t* bytes);
+int tz_keysg_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out);
+int tz_keysg_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* predg,
+                   const uint8_t* lengths);
+int tz_keysg_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src);
+int tz_keysg_decode(tz_ctx* ctx);
+/* Stand-alone forms: frames (k, H, W, 3) <-> the sum over k of H * W (GRAY) or H * W * 3 int16 symbols.  The GRAY bit is taken
+ * as given: tz_keysg_residual_buf codes channel 0 of such a frame whatever the other channels hold. */
+int tz_keysg_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* predg, int16_t* sym);
+int tz_keysg_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* predg, uint8_t* frames);
+
 /* ---- timing helper: HIP events on the context's stream (bench.py) -------------------------- */
 int tz_timer_start(tz_ctx* ctx);
 int tz_timer_stop(tz_ctx* ctx, float* ms);

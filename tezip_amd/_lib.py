@@ -122,6 +122,14 @@ _SIGS = {
     "tz_keys_decode": (C.c_int, [C.c_void_p]),
     "tz_keys_residual_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tz_keys_unresidual_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_keys_gray": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "tz_keysg_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "tz_keysg_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_keysg_begin": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_keysg_put": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_keysg_decode": (C.c_int, [C.c_void_p]),
+    "tz_keysg_residual_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_keysg_unresidual_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tz_timer_start": (C.c_int, [C.c_void_p]),
     "tz_timer_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "tz_prof_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -790,6 +798,75 @@ class Context:
         if out is None:
             out = np.empty((k, h, w, 3), np.uint8)
         self._ck(self.lib.tz_keys_unresidual_buf(self.h, _ptr(sym), k, int(h), int(w), pr.ctypes.data, _ptr(out)))
+        return out
+
+    # ---- the same with gray key frames stored once (tz_keys_gray, tz_keysg_*; format: tezip_amd/keycoderg.py).  predg: pred
+    # bytes, predictor id | 4 for a GRAY frame, which has h * w symbols instead of h * w * 3
+    def keys_gray(self, idx):
+        """bool[k]: the three channels of frame idx[k] of the resident stack are equal at every pixel."""
+        ix = np.ascontiguousarray(idx, np.int32)
+        gray = np.zeros(ix.size, np.uint8)
+        self._ck(self.lib.tz_keys_gray(self.h, ix.ctypes.data, int(ix.size), gray.ctypes.data))
+        return gray.astype(bool)
+
+    def keysg_encode(self, idx, predg, lengths):
+        """Code the frames `idx` of the resident stack into the resident key stream (index | bits); returns its size."""
+        ix, pr, ln = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(predg, np.uint8), np.ascontiguousarray(lengths, np.uint8)
+        if pr.size != ix.size or ln.size != 256:
+            raise ValueError("%d pred bytes for %d key frames, %d code lengths (256 wanted)" % (pr.size, ix.size, ln.size))
+        nbytes = C.c_size_t(0)
+        self._ck(self.lib.tz_keysg_encode(self.h, ix.ctypes.data, int(ix.size), pr.ctypes.data, ln.ctypes.data, C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def keysg_get(self, offset, count, out=None):
+        if out is None:
+            out = np.empty(count, np.uint8)
+        self._ck(self.lib.tz_keysg_get(self.h, int(offset), int(count), _ptr(out, np.uint8)))
+        return out
+
+    def keysg_begin(self, nbytes, nt, h, w, idx, predg, lengths):
+        ix, pr, ln = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(predg, np.uint8), np.ascontiguousarray(lengths, np.uint8)
+        if pr.size != ix.size or ln.size != 256:
+            raise ValueError("%d pred bytes for %d key frames, %d code lengths (256 wanted)" % (pr.size, ix.size, ln.size))
+        self._ck(self.lib.tz_keysg_begin(self.h, int(nbytes), int(nt), int(h), int(w), ix.ctypes.data, int(ix.size), pr.ctypes.data,
+                                         ln.ctypes.data))
+        self._keys_shape = (int(nt), int(h), int(w))
+
+    def keysg_put(self, offset, piece):
+        self._ck(self.lib.tz_keysg_put(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
+
+    def keysg_decode(self):
+        """-> the context's frame stack, as frames_begin + frames_put of the zero-except-keys stack leave it."""
+        self._ck(self.lib.tz_keysg_decode(self.h))
+        self._staged = self._shape = self._keys_shape
+
+    @staticmethod
+    def _keysg_symbols(predg, h, w):
+        pr = np.ascontiguousarray(predg, np.uint8)
+        return pr, int(np.where(pr & 4, h * w, h * w * 3).sum())
+
+    def keysg_residual_buf(self, frames, predg, out=None):
+        """Stand-alone: uint8 (k, H, W, 3) frames (host or device) -> their int16 residual symbols, H * W for a GRAY frame."""
+        self._check_stack(frames, "frames")
+        k, h, w = (int(v) for v in frames.shape[:3])
+        pr, n = self._keysg_symbols(predg, h, w)
+        if pr.size != k:
+            raise ValueError("%d pred bytes for %d frames" % (pr.size, k))
+        if out is None:
+            out = np.empty(n, np.int16)
+        elif _numel(out) != n:
+            raise ValueError("%d symbols of room, %d wanted" % (_numel(out), n))
+        self._ck(self.lib.tz_keysg_residual_buf(self.h, _ptr(frames), k, h, w, pr.ctypes.data, _ptr(out)))
+        return out
+
+    def keysg_unresidual_buf(self, sym, predg, h, w, out=None):
+        pr, n = self._keysg_symbols(predg, int(h), int(w))
+        k = int(pr.size)
+        if _numel(sym) != n:
+            raise ValueError("%d symbols for %d frames of %d x %d, %d wanted" % (_numel(sym), k, h, w, n))
+        if out is None:
+            out = np.empty((k, h, w, 3), np.uint8)
+        self._ck(self.lib.tz_keysg_unresidual_buf(self.h, _ptr(sym), k, int(h), int(w), pr.ctypes.data, _ptr(out)))
         return out
 
     # ---- opt-in Huffman coder with repeat tokens (tz_huffr_*; format: tezip_amd/huffr.py).  `lengths` holds the A literals

@@ -14,6 +14,8 @@ Output directory:
                  key indices | predictor ids | code lengths | index | bit stream -- per key frame the residuals of the best
                  of four predictors (none, left, up, left + up - upleft), Huffman-coded on the GPU (tezip_amd/keycoder.py,
                  DESIGN.md section 9).  Smaller than zstd-9 on smooth frames, LARGER on sparse ones: hence opt-in
+  with KEY_CODER="huffg" (--key-coder huffg) the same under the magic "TZK2": a key frame whose three channels are equal at
+                 every pixel (a gray source, widened to RGB) is coded as one channel (tezip_amd/keycoderg.py)
 """
 import glob
 import os
@@ -23,7 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, digest, huff, huffr, keycoder, quality, sidecar, weights, zstd
+from . import _lib, digest, huff, huffr, keycoder, keycoderg, quality, sidecar, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -246,7 +248,7 @@ def check_coder(coder, shuffle=False, sharded=False):
     return None
 
 
-KEY_CODERS = ("zstd", "huff")
+KEY_CODERS = ("zstd", "huff", "huffg")
 
 
 def check_key_coder(key_coder, sharded=False):
@@ -276,6 +278,30 @@ def _huff_key_file(ctx, path, nt, H, W, key_idx, verbose):
         for k, off in enumerate(range(0, nbytes, HUFF_PIECE)):
             cnt = min(HUFF_PIECE, nbytes - off)
             f.write(ctx.keys_get(off, cnt, out=bufs[k % 2][:cnt]))
+    if verbose:
+        print("key_coding:{0}".format(time.perf_counter() - t0) + "[sec]")
+    return len(front) + nbytes
+
+
+def _huffg_key_file(ctx, path, nt, H, W, key_idx, verbose):
+    """key_frame.dat of KEY_CODER="huffg" (TZK2): as _huff_key_file, and one more read of the key frames says which of them
+    are gray (tz_keys_gray); those are counted, coded and stored as one channel (keycoderg.gray_counts: the three-channel
+    counts divided by 3, the same integers keycoderg.encode_file uses)."""
+    t0 = time.perf_counter()
+    gray = ctx.keys_gray(key_idx)
+    counts = keycoderg.gray_counts(ctx.keys_counts(key_idx), gray)
+    predg = keycoderg.pred_bytes(counts, gray)
+    lengths = huff.code_lengths(keycoderg.chosen_counts(counts, predg))
+    nbytes = ctx.keysg_encode(key_idx, predg, lengths)
+    n = keycoderg.offsets(gray, H, W)[1]
+    nruns, nchunks = huff.geometry(n)
+    front = keycoderg.pack_front(nt, H, W, key_idx, predg, lengths, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4)
+    bufs = [np.empty(min(HUFF_PIECE, nbytes), np.uint8) for _ in range(2)]
+    with open(path, mode='wb') as f:
+        f.write(front)
+        for k, off in enumerate(range(0, nbytes, HUFF_PIECE)):
+            cnt = min(HUFF_PIECE, nbytes - off)
+            f.write(ctx.keysg_get(off, cnt, out=bufs[k % 2][:cnt]))
     if verbose:
         print("key_coding:{0}".format(time.perf_counter() - t0) + "[sec]")
     return len(front) + nbytes
@@ -325,10 +351,11 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
     n = nt * H * W * 3
     key_idx = [int(i) for i in np.nonzero(key)[0]]
     zero = np.zeros((H, W, 3), np.uint8)
-    if key_coder == "huff":
+    if key_coder in ("huff", "huffg"):
         # few key frames or all of them (-w 1): one path, the stack never leaves the device
         t_k = time.perf_counter()
-        kf = _Done(_huff_key_file(ctx, os.path.join(out_dir, "key_frame.dat"), nt, H, W, key_idx, verbose))
+        key_file_of = _huffg_key_file if key_coder == "huffg" else _huff_key_file
+        kf = _Done(key_file_of(ctx, os.path.join(out_dir, "key_frame.dat"), nt, H, W, key_idx, verbose))
         if stages:
             stages.add("key-frame coding + fetch key_frame.dat", time.perf_counter() - t_k)
     elif len(key_idx) * H * W * 3 <= KEY_PREFETCH_BYTES:
@@ -422,8 +449,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     Single-GPU jobs only, not with SHUFFLE.
     KEY_CODER (--key-coder; NOT in the reference): "zstd" writes the reference's key_frame.dat; "huff" has the GPU code the
     key frames alone as predictor residuals under a Huffman code (tezip_amd/keycoder.py) -- not readable by the reference,
-    `-u` recognises it by its magic; smaller than zstd-9 on smooth frames and larger on sparse ones.  Independent of CODER
-    and SHUFFLE.  Single-GPU jobs only.
+    `-u` recognises it by its magic; smaller than zstd-9 on smooth frames and larger on sparse ones.  "huffg" is "huff"
+    with every gray key frame (three equal channels: a single-channel source) coded as one channel
+    (tezip_amd/keycoderg.py).  Independent of CODER and SHUFFLE.  Single-GPU jobs only.
     DIGESTS (--digests; NOT in the reference): also write frame_digests.json (tezip_amd/digest.py) -- per frame the digest
     of what the stored payload decodes to and of the source frame, both taken on the device (tz_encode_digests); `-u`
     verifies its frames against them before it writes an image.  The other files are byte for byte what they are without

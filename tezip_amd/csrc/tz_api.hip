@@ -2338,7 +2338,7 @@ static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uin
     const size_t total = index_bytes + (size_t)meta.total_words * 4;
     uint8_t* d_stream;
     if (keys) {
-        ctx->keys_n = 0;              // (a staged decoder stream, if any, is gone)
+        ctx->keys_n = ctx->keysg_n = 0;   // (a staged decoder stream, if any, is gone)
         TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, total));
         ctx->keys_bytes = total;
         d_stream = ctx->d_keys;
@@ -2771,7 +2771,7 @@ extern "C" int tz_keys_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, co
     TZ_TRY(huff_check_stream(ctx, bytes, n, TZ_HUFF_RUN, &sw));
     std::vector<uint16_t> dec;
     TZ_TRY(huff_tables(ctx, lengths, TZ_KEYS_A, 0, nullptr, &dec));
-    ctx->keys_n = 0;
+    ctx->keys_n = ctx->keysg_n = 0;
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, std::max<size_t>(bytes, 16)));
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, std::max<size_t>(n, 8) * 2));
     ctx->keys_bytes = bytes;
@@ -2887,6 +2887,236 @@ extern "C" int tz_keys_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, in
     if (rc == TZ_OK) {
         outs.push_back(o);
         rc = keys_unresidual(ctx, (const int16_t*)din, H, W, idx.data(), pred, k, (uint8_t*)o.dev);
+    }
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// --------------------------------------------------------------------------- key-frame coder, gray frames once (TZK2)
+// `--key-coder huffg`: TZK1 with a GRAY bit per key frame (tezip_amd/keycoderg.py, k_key_gray / k_keyg_* in tz_codec.hip).
+// The stream, the symbols and the staged decoder's fields are those of tz_keys_*; ctx->keysg_n instead of ctx->keys_n says
+// that what is staged is a TZK2 stream, so each decoder refuses a body staged for the other format.
+
+// pred bytes 0..7 -> off[k], the exclusive prefix of the frames' symbol counts, and their sum
+static int keysg_layout(tz_ctx* ctx, const uint8_t* predg, int nkeys, int H, int W, std::vector<unsigned long long>* off, size_t* n) {
+    off->resize(nkeys);
+    unsigned long long at = 0;
+    for (int k = 0; k < nkeys; ++k) {
+        if (predg[k] > 7) return tz_fail(ctx, TZ_ERR_INVALID, "key frames: pred byte %d (entry %d) outside [0, 7]", predg[k], k);
+        (*off)[k] = at;
+        at += (unsigned long long)H * W * ((predg[k] & 4) ? 1 : 3);
+    }
+    *n = (size_t)at;
+    return TZ_OK;
+}
+
+static int keysg_upload(tz_ctx* ctx, const int* idx, const uint8_t* predg, const std::vector<unsigned long long>& off, int nkeys,
+                        const int** d_idx, const uint8_t** d_predg, const unsigned long long** d_off) {
+    void* d;
+    TZ_TRY(keys_upload(ctx, idx, predg, nkeys, d_idx, d_predg));
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(unsigned long long) * nkeys, &d));
+    TZ_TRY(tz_upload(ctx, d, off.data(), sizeof(unsigned long long) * nkeys));
+    *d_off = (const unsigned long long*)d;
+    return TZ_OK;
+}
+
+static int keys_gray(tz_ctx* ctx, const int* idx, int nkeys, uint8_t* gray) {
+    const int* d_idx = nullptr;
+    const uint8_t* d_pred = nullptr;
+    void* d_flags;
+    std::vector<unsigned> flags(nkeys);
+    TZ_TRY(keys_upload(ctx, idx, nullptr, nkeys, &d_idx, &d_pred));
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(unsigned) * nkeys, &d_flags));
+    TZ_TRY(tzk_key_gray(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, nkeys, (unsigned*)d_flags));
+    TZ_TRY(tz_d2h(ctx, flags.data(), d_flags, sizeof(unsigned) * nkeys, ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
+    for (int k = 0; k < nkeys; ++k) gray[k] = flags[k] ? 0 : 1;
+    return TZ_OK;
+}
+
+extern "C" int tz_keys_gray(tz_ctx* ctx, const int* idx, int nkeys, uint8_t* gray) {
+    tz_roctx_range roctx_("tz_keys_gray");
+    if (!ctx || !gray) return TZ_ERR_INVALID;
+    TZ_TRY(keys_resident(ctx, "tz_keys_gray"));
+    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys, nullptr));
+    const int rc = keys_gray(ctx, idx, nkeys, gray);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+static int keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* predg, const uint8_t* lengths, size_t* bytes) {
+    std::vector<unsigned long long> off;
+    size_t n;
+    TZ_TRY(keysg_layout(ctx, predg, nkeys, ctx->H, ctx->W, &off, &n));
+    const int* d_idx = nullptr;
+    const uint8_t* d_predg = nullptr;
+    const unsigned long long* d_off = nullptr;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
+    TZ_TRY(keysg_upload(ctx, idx, predg, off, nkeys, &d_idx, &d_predg, &d_off));
+    TZ_TRY(tzk_keyg_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, d_predg, d_off, nkeys, ctx->d_keysym));
+    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, false, true);
+}
+
+extern "C" int tz_keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* predg, const uint8_t* lengths, size_t* bytes) {
+    tz_roctx_range roctx_("tz_keysg_encode");
+    if (!ctx || !predg || !lengths || !bytes) return TZ_ERR_INVALID;
+    TZ_TRY(keys_resident(ctx, "tz_keysg_encode"));
+    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys, nullptr));
+    const int rc = keysg_encode(ctx, idx, nkeys, predg, lengths, bytes);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_keysg_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
+    return tz_keys_get(ctx, offset, count, out);   // (an encoder's stream carries no format of its own: index | bits)
+}
+
+extern "C" int tz_keysg_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* predg,
+                              const uint8_t* lengths) {
+    if (!ctx || !predg) return TZ_ERR_INVALID;
+    if (nt < 1 || H < 1 || W < 1 || nt > kMaxFrames || H > 32767 || W > 32767)
+        return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d (int16 trailer limits)", nt, H, W);
+    TZ_TRY(keys_check(ctx, nt, idx, nkeys, nullptr));
+    std::vector<unsigned long long> off;
+    size_t n, sw;
+    TZ_TRY(keysg_layout(ctx, predg, nkeys, H, W, &off, &n));
+    TZ_TRY(huff_check_stream(ctx, bytes, n, TZ_HUFF_RUN, &sw));
+    std::vector<uint16_t> dec;
+    TZ_TRY(huff_tables(ctx, lengths, TZ_KEYS_A, 0, nullptr, &dec));
+    ctx->keys_n = ctx->keysg_n = 0;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, std::max<size_t>(bytes, 16)));
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, std::max<size_t>(n, 8) * 2));
+    ctx->keys_bytes = bytes;
+    ctx->keys_put = 0;
+    ctx->keys_nt = nt;
+    ctx->keys_H = H;
+    ctx->keys_W = W;
+    ctx->keys_idx.assign(idx, idx + nkeys);
+    ctx->keys_pred.assign(predg, predg + nkeys);
+    ctx->keys_dec_tab.swap(dec);
+    ctx->keysg_n = n;
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
+    return TZ_OK;
+}
+
+extern "C" int tz_keysg_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
+    if (!ctx || !src) return TZ_ERR_INVALID;
+    if (!ctx->d_keys || !ctx->keysg_n || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged key-frame stream (TZK2)");
+    TZ_TRY(tz_h2d(ctx, ctx->d_keys + offset, src, count, ctx->copy_stream));
+    ctx->keys_put += count;
+    return TZ_OK;
+}
+
+// symbols (device) -> the frames idx[k] of a stack at d_frames; the other frames of the stack are not touched
+static int keysg_unresidual(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* idx, const uint8_t* predg, int nkeys, uint8_t* d_frames) {
+    std::vector<unsigned long long> off;
+    size_t n;
+    TZ_TRY(keysg_layout(ctx, predg, nkeys, H, W, &off, &n));
+    std::vector<uint8_t> pred3(predg, predg + nkeys);
+    for (auto& p : pred3)
+        if (p & 4) p = 0;
+    const int* d_idx = nullptr;
+    const uint8_t* d_predg = nullptr;
+    const unsigned long long* d_off = nullptr;
+    void *d_pred3, *d_tmp;
+    TZ_TRY(keysg_upload(ctx, idx, predg, off, nkeys, &d_idx, &d_predg, &d_off));
+    TZ_TRY(tz_pool_alloc(ctx, nkeys, &d_pred3));
+    TZ_TRY(tz_upload(ctx, d_pred3, pred3.data(), nkeys));
+    TZ_TRY(tz_pool_alloc(ctx, n, &d_tmp));
+    return tzk_keyg_unresid(ctx, d_sym, H, W, d_idx, d_predg, (const uint8_t*)d_pred3, d_off, nkeys, (uint8_t*)d_tmp, d_frames);
+}
+
+static int keysg_decode(tz_ctx* ctx) {
+    const int nt = ctx->keys_nt, H = ctx->keys_H, W = ctx->keys_W;
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, ctx->keys_bytes, ctx->keysg_n, TZ_HUFF_RUN, &sw));
+    // what tz_frames_begin does: the stack's buffer and shape; whatever rollout was resident is gone
+    set_rollout(ctx, tz_ctx::ROLLOUT_NONE, 0, 0);
+    ctx->staged = false;
+    const size_t fb = (size_t)nt * H * W * 3;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_frames, &ctx->cap_frames, fb));
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of tz_keysg_put (and older copies into d_frames)
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
+    TZ_TRY(huff_decode_dev(ctx, ctx->d_keys, sw, ctx->keysg_n, ctx->keys_dec_tab, 0, ctx->d_keysym));
+    TZ_HIP(ctx, hipMemsetAsync(ctx->d_frames, 0, fb, ctx->stream));   // the frames that are no key frames (a fresh buffer holds anything)
+    TZ_TRY(keysg_unresidual(ctx, ctx->d_keysym, H, W, ctx->keys_idx.data(), ctx->keys_pred.data(), (int)ctx->keys_idx.size(), ctx->d_frames));
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));       // a later tz_frames_put waits for the frames written here
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
+    ctx->nt = nt;
+    ctx->H = H;
+    ctx->W = W;
+    ctx->staged = true;
+    return TZ_OK;
+}
+
+extern "C" int tz_keysg_decode(tz_ctx* ctx) {
+    tz_roctx_range roctx_("tz_keysg_decode");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (!ctx->keysg_n || !ctx->d_keys || !ctx->d_keysym)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_keysg_decode needs a stream staged with tz_keysg_begin / tz_keysg_put");
+    if (ctx->keys_put != ctx->keys_bytes)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_keysg_decode: %zu of the stream's %zu bytes were put", ctx->keys_put, ctx->keys_bytes);
+    const int rc = keysg_decode(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// stand-alone forms on host or device arrays: frames (k, H, W, 3) <-> the symbols keysg_layout counts, predg[k] per frame
+static int keysg_buf_check(tz_ctx* ctx, int k, int H, int W, std::vector<int>* idx) {
+    if (k < 1 || H < 1 || W < 1 || k > kMaxFrames || H > 32767 || W > 32767)
+        return tz_fail(ctx, TZ_ERR_INVALID, "bad key-frame stack k=%d H=%d W=%d", k, H, W);
+    idx->resize(k);
+    for (int i = 0; i < k; ++i) (*idx)[i] = i;
+    return TZ_OK;
+}
+
+extern "C" int tz_keysg_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* predg, int16_t* sym) {
+    if (!ctx || !frames || !predg || !sym) return TZ_ERR_INVALID;
+    std::vector<int> idx;
+    std::vector<unsigned long long> off;
+    size_t n;
+    TZ_TRY(keysg_buf_check(ctx, k, H, W, &idx));
+    TZ_TRY(keysg_layout(ctx, predg, k, H, W, &off, &n));
+    const void* din = nullptr;
+    const int* d_idx = nullptr;
+    const uint8_t* d_predg = nullptr;
+    const unsigned long long* d_off = nullptr;
+    tz_out o;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, frames, (size_t)k * H * W * 3, &din);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, sym, n * 2, &o);
+    if (rc == TZ_OK && ((uintptr_t)o.dev & 1)) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames: a device symbol array must be 2-byte aligned");
+    if (rc == TZ_OK) rc = keysg_upload(ctx, idx.data(), predg, off, k, &d_idx, &d_predg, &d_off);
+    if (rc == TZ_OK) {
+        outs.push_back(o);
+        rc = tzk_keyg_resid(ctx, (const uint8_t*)din, H, W, d_idx, d_predg, d_off, k, (int16_t*)o.dev);
+    }
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_keysg_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* predg, uint8_t* frames) {
+    if (!ctx || !frames || !predg || !sym) return TZ_ERR_INVALID;
+    std::vector<int> idx;
+    std::vector<unsigned long long> off;
+    size_t n;
+    TZ_TRY(keysg_buf_check(ctx, k, H, W, &idx));
+    TZ_TRY(keysg_layout(ctx, predg, k, H, W, &off, &n));
+    const void* din = nullptr;
+    tz_out o;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, sym, n * 2, &din);
+    if (rc == TZ_OK && ((uintptr_t)din & 1)) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames: a device symbol array must be 2-byte aligned");
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, frames, (size_t)k * H * W * 3, &o);
+    if (rc == TZ_OK) {
+        outs.push_back(o);
+        rc = keysg_unresidual(ctx, (const int16_t*)din, H, W, idx.data(), predg, k, (uint8_t*)o.dev);
     }
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);

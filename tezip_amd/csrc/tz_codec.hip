@@ -3435,3 +3435,244 @@ int tzk_key_unresid(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* 
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
+
+// ---------------------------------------------------------------------------- key-frame coder, gray frames once (TZK2)
+// Opt-in stage `--key-coder huffg` (format TZK2: DESIGN.md section 9, tezip_amd/keycoderg.py is the slow statement of it).
+// A key frame whose three channels are equal at every pixel is GRAY (bit 2 of its pred byte): it contributes the H * W
+// residuals of channel 0 alone, and the inverse writes each sample to all three channels.  Frames therefore differ in size:
+// frame k's symbols start at off[k], the u64 exclusive prefix of the per-frame symbol counts the host passes in.
+
+// flags[k] becomes non-zero iff key frame idx[k] has a pixel with unequal channels.  The frame is gray iff f[i] == f[i + 1] for
+// every byte index i with i % 3 != 2 (fe is a multiple of 3, so i + 1 < fe for those).  Unit 0 is the head in front of the first
+// 16-byte boundary, unit u >= 1 the 48 bytes from there on: three 16-byte loads, every byte compared with its successor through
+// a funnel shift (the successor of the 48th byte is loaded by itself), the comparisons at i % 3 == 2 masked out.  48 is a
+// multiple of 3, so the mask depends on the frame alone.  One OR per workgroup that saw an unequal pixel.
+__global__ __launch_bounds__(256) void k_key_gray(const uint8_t* __restrict__ frames, size_t fe, const int* __restrict__ idx,
+                                                  unsigned* __restrict__ flags) {
+    const int key = blockIdx.y;
+    const uint8_t* f = frames + (size_t)idx[key] * fe;
+    const unsigned head = key_head(f, fe);
+    const size_t nunits = 1 + (fe - head + 47) / 48, stride = (size_t)gridDim.x * 256;
+    unsigned mask[3];   // byte k of mask[d]: 0xff where (head + 4 d + k) % 3 != 2
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        mask[d] = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((head + 4u * d + k) % 3u != 2u) mask[d] |= 0xffu << (8 * k);
+    }
+    unsigned bad = 0;
+    for (size_t u = (size_t)blockIdx.x * 256 + threadIdx.x; u < nunits; u += stride) {
+        if (u == 0) {
+            for (unsigned i = 0; i < head; ++i)
+                if (i % 3u != 2u) bad |= (unsigned)(f[i] ^ f[i + 1]);     // i + 1 < fe: i is not the last byte of its pixel
+            continue;
+        }
+        const size_t e = head + (u - 1) * 48;
+        if (e >= fe) continue;
+        if (fe - e >= 48) {   // a whole unit; f + e is 16-byte aligned
+            const uint4 q0 = *(const uint4*)(f + e), q1 = *(const uint4*)(f + e + 16), q2 = *(const uint4*)(f + e + 32);
+            const unsigned next = e + 48 < fe ? f[e + 48] : 0u;            // (when e + 48 == fe, byte 47 ends a pixel: masked)
+            const unsigned w[13] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, next};
+#pragma unroll
+            for (int j = 0; j < 12; ++j) bad |= (w[j] ^ ((w[j] >> 8) | (w[j + 1] << 24))) & mask[j % 3];
+        } else {              // the tail: byte by byte
+            for (size_t i = e; i < fe; ++i)
+                if (i % 3 != 2) bad |= (unsigned)(f[i] ^ f[i + 1]);
+        }
+    }
+    if (__syncthreads_or(bad != 0) && threadIdx.x == 0) atomicOr(&flags[key], 1u);
+}
+
+int tzk_key_gray(tz_ctx* ctx, const uint8_t* d_frames, int H, int W, const int* d_idx, int nkeys, unsigned* d_flags) {
+    const size_t fe = (size_t)H * W * 3;
+    TZ_HIP(ctx, hipMemsetAsync(d_flags, 0, (size_t)nkeys * sizeof(unsigned), ctx->stream));
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    hipLaunchKernelGGL(k_key_gray, dim3((unsigned)std::min<size_t>((fe / 48 + 2 + 255) / 256, 256), (unsigned)nkeys), dim3(256), 0, ctx->stream,
+                       d_frames, fe, d_idx, d_flags);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// Residuals of key frame idx[k] under pred byte predg[k] at sym[off[k] ...].  GRAY: a thread per pixel reads channel 0 of the
+// pixel and of its three neighbours at stride 3 (a wave covers 192 contiguous bytes of a row) and writes one symbol, so a
+// wave stores 128 contiguous bytes.  Any other frame: k_key_resid's units, at the frame's own offset.
+__global__ __launch_bounds__(256) void k_keyg_resid(const uint8_t* __restrict__ frames, int H, int W, const int* __restrict__ idx,
+                                                    const uint8_t* __restrict__ predg, const unsigned long long* __restrict__ off,
+                                                    int16_t* __restrict__ sym) {
+    const int key = blockIdx.y;
+    const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3, stride = (size_t)gridDim.x * 256;
+    const uint8_t* f = frames + (size_t)idx[key] * fe;
+    int16_t* out = sym + off[key];
+    const unsigned p = predg[key] & 3u;
+    if (predg[key] & 4u) {   // (workgroup-uniform)
+        const size_t np = (size_t)H * W;
+        for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < np; q += stride) {
+            const size_t y = q / (size_t)W, col = q - y * (size_t)W;
+            const bool hl = col > 0, hu = y > 0;
+            const unsigned x = f[q * 3];
+            const unsigned a = hl ? f[(q - 1) * 3] : 0u, b = hu ? f[(q - W) * 3] : 0u, c = (hl && hu) ? f[(q - W - 1) * 3] : 0u;
+            const unsigned pr = (p & 1u ? a : 0u) + (p & 2u ? b : 0u) - (p == 3u ? c : 0u);
+            out[q] = (int16_t)((x - pr) & 255u);
+        }
+        return;
+    }
+    const unsigned head = key_head(f, fe);
+    const size_t nunits = 1 + (fe - head + 15) / 16;
+    for (size_t u = (size_t)blockIdx.x * 256 + threadIdx.x; u < nunits; u += stride) {
+        size_t e;
+        int cnt;
+        key_unit(u, head, fe, &e, &cnt);
+        if (cnt <= 0) continue;
+        KeyWin w;
+        key_window(f, fe, (unsigned)W3, e, cnt, w);
+        short8 lo, hi;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const unsigned q = (p & 1u ? w.a[j] : 0u) + (p & 2u ? w.b[j] : 0u) - (p == 3u ? w.c[j] : 0u);
+            const short v = (short)((w.x[j] - q) & 255u);
+            if (j < 8) lo[j] = v;
+            else hi[j - 8] = v;
+        }
+        if (cnt == 16 && ((uintptr_t)(out + e) & 15) == 0) {
+            *(short8*)(out + e) = lo;
+            *(short8*)(out + e + 8) = hi;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (j < cnt) out[e + j] = j < 8 ? lo[j] : hi[j - 8];
+        }
+    }
+}
+
+int tzk_keyg_resid(tz_ctx* ctx, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_predg,
+                   const unsigned long long* d_off, int nkeys, int16_t* d_sym) {
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    hipLaunchKernelGGL(k_keyg_resid, key_grid((size_t)H * W * 3, nkeys), dim3(256), 0, ctx->stream, d_frames, H, W, d_idx, d_predg, d_off, d_sym);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// A wave holds one sample per lane, those of ncols (1..64) neighbouring pixels; their 3 * ncols bytes -- every sample three
+// times -- go to g as aligned dwords: lane d builds the d-th aligned dword at or below g from the samples of the (at most two)
+// pixels it covers, fetched by shuffles, and stores it whole where all four bytes belong to the chunk, byte by byte at the two
+// ends.  g has any alignment; 3 * 64 bytes and up to 3 bytes of misalignment touch at most 49 dwords.  Every lane of the wave
+// must call this.
+__device__ __forceinline__ void keyg_store3(unsigned v, int lane, int ncols, uint8_t* g) {
+    const int n = ncols * 3, t0 = lane * 4 - (int)((uintptr_t)g & 3);   // t0: this lane's dword, as a byte offset from g
+    unsigned w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = min(max(t0 + j, 0), 191);
+        w |= (__shfl(v, t / 3, 64) & 255u) << (8 * j);
+    }
+    if (t0 >= n) return;
+    if (t0 >= 0 && t0 + 4 <= n) {
+        *(unsigned*)(g + t0) = w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (t0 + j >= 0 && t0 + j < n) g[t0 + j] = (uint8_t)(w >> (8 * j));
+    }
+}
+
+// The inverse, first pass: one wave per (key frame, row).  GRAY: the row's W symbols, scanned along the row under predictors 1
+// and 3 (k_key_unresid_row's shuffle scan, one channel), go replicated into the frame (keyg_store3) -- or, when a column
+// pass follows (predictors 2 and 3), as single bytes to tmp[off[k] + y * W + col], from where k_keyg_unresid_col finishes
+// them.  Any other frame: k_key_unresid_row's work at the frame's own offset.  Only the low byte of a symbol counts.
+__global__ __launch_bounds__(256) void k_keyg_unresid_row(const int16_t* __restrict__ sym, int H, int W, const int* __restrict__ idx,
+                                                          const uint8_t* __restrict__ predg, const unsigned long long* __restrict__ off,
+                                                          uint8_t* __restrict__ tmp, uint8_t* __restrict__ frames) {
+    const int key = blockIdx.y, y = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (y >= H) return;   // (wave-uniform)
+    const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3;
+    const unsigned pb = predg[key];
+    const bool scan = (pb & 1u) != 0;
+    uint8_t* o = frames + (size_t)idx[key] * fe + (size_t)y * W3;
+    if (pb & 4u) {   // (workgroup-uniform)
+        const int16_t* s = sym + off[key] + (size_t)y * W;
+        uint8_t* t = tmp + off[key] + (size_t)y * W;
+        unsigned carry = 0;
+        for (int c0 = 0; c0 < W; c0 += 64) {
+            const int col = c0 + lane;
+            unsigned v = col < W ? (unsigned)s[col] & 255u : 0u;
+            if (scan) {
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const unsigned u = __shfl_up(v, d, 64);
+                    if (lane >= d) v += u;
+                }
+                v += carry;
+                carry = __shfl(v, 63, 64) & 255u;
+            }
+            if (pb & 2u) {
+                if (col < W) t[col] = (uint8_t)v;
+            } else {
+                keyg_store3(v, lane, min(64, W - c0), o + (size_t)c0 * 3);
+            }
+        }
+        return;
+    }
+    const int16_t* s = sym + off[key] + (size_t)y * W3;
+    unsigned carry[3] = {0u, 0u, 0u};
+    for (int c0 = 0; c0 < W; c0 += 64) {
+        const int col = c0 + lane;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            unsigned v = col < W ? (unsigned)s[(size_t)col * 3 + ch] & 255u : 0u;
+            if (scan) {
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const unsigned u = __shfl_up(v, d, 64);
+                    if (lane >= d) v += u;
+                }
+                v += carry[ch];
+                carry[ch] = __shfl(v, 63, 64) & 255u;
+            }
+            if (col < W) o[(size_t)col * 3 + ch] = (uint8_t)v;
+        }
+    }
+}
+
+// Second pass of a GRAY frame under predictors 2 and 3: a thread per (key frame, column) walks down its column of tmp, eight
+// rows loaded ahead, and every wave writes the running sums mod 256 of its 64 columns replicated into the frame (keyg_store3).
+// The other frames' column pass is k_key_unresid_col itself, given predictor ids in which the GRAY frames carry 0.
+__global__ __launch_bounds__(256) void k_keyg_unresid_col(int H, int W, const int* __restrict__ idx, const uint8_t* __restrict__ predg,
+                                                          const unsigned long long* __restrict__ off, const uint8_t* __restrict__ tmp,
+                                                          uint8_t* __restrict__ frames) {
+    const int key = blockIdx.y, lane = threadIdx.x & 63;
+    if ((predg[key] & 6u) != 6u) return;   // (workgroup-uniform)
+    const int c0 = (int)(blockIdx.x * 256 + (threadIdx.x & ~63u));   // the wave's first column
+    if (c0 >= W) return;                   // (wave-uniform)
+    const int col = c0 + lane, ncols = min(64, W - c0);
+    const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3;
+    const uint8_t* t = tmp + off[key] + col;
+    uint8_t* o = frames + (size_t)idx[key] * fe + (size_t)c0 * 3;
+    unsigned acc = 0;
+    for (int y0 = 0; y0 < H; y0 += 8) {
+        unsigned v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (y0 + i < H && col < W) ? t[(size_t)(y0 + i) * W] : 0u;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            acc += v[i];
+            if (y0 + i < H) keyg_store3(acc, lane, ncols, o + (size_t)(y0 + i) * W3);   // (the condition is wave-uniform)
+        }
+    }
+}
+
+// d_pred3: the predictor ids with 0 for every GRAY frame (k_key_unresid_col skips those); d_tmp: one byte per symbol
+int tzk_keyg_unresid(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_predg, const uint8_t* d_pred3,
+                     const unsigned long long* d_off, int nkeys, uint8_t* d_tmp, uint8_t* d_frames) {
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    hipLaunchKernelGGL(k_keyg_unresid_row, dim3((unsigned)((H + 3) / 4), (unsigned)nkeys), dim3(256), 0, ctx->stream, d_sym, H, W, d_idx, d_predg,
+                       d_off, d_tmp, d_frames);
+    TZ_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_keyg_unresid_col, dim3((unsigned)((W + 255) / 256), (unsigned)nkeys), dim3(256), 0, ctx->stream, H, W, d_idx, d_predg,
+                       d_off, d_tmp, d_frames);
+    TZ_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_key_unresid_col, dim3((unsigned)(((size_t)W * 3 + 255) / 256), (unsigned)nkeys), dim3(256), 0, ctx->stream, H, W, d_idx,
+                       d_pred3, d_frames);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}

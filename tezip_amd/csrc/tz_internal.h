@@ -150,6 +150,8 @@ struct tz_ctx {
     std::vector<int> keys_idx;              // tz_keys_begin: the key frames' indices ...
     std::vector<uint8_t> keys_pred;         // ... and predictor ids
     std::vector<uint16_t> keys_dec_tab;     // tz_keys_begin: the 2^12-entry decode table of the staged stream's lengths
+    size_t keysg_n = 0;                     // tz_keysg_begin: the same for a TZK2 stream, which shares the buffers and the fields
+                                            // above (keys_pred then holds pred bytes); at most one of keys_n, keysg_n is non-zero
     uint8_t* d_out = nullptr;               // resident decoded frames of a tz_decode(frames_out = NULL)
     size_t cap_out = 0;
     bool have_decoded = false;
@@ -346,6 +348,14 @@ int tzk_huffr_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bi
 int tzk_key_hist(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, int nkeys, unsigned* d_counts /* [nkeys][4][256] */);
 int tzk_key_resid(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, int16_t* d_sym);
 int tzk_key_unresid(tz_ctx*, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, uint8_t* d_frames);
+// the same with gray key frames stored once (TZK2).  d_predg[k]: predictor id | 4 for a GRAY frame, which has H * W symbols;
+// d_off[k]: where frame k's symbols start in d_sym (u64 exclusive prefix of the per-frame counts); d_flags[k] != 0: not gray;
+// d_pred3: d_predg with 0 for every GRAY frame; d_tmp: scratch of one byte per symbol
+int tzk_key_gray(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, int nkeys, unsigned* d_flags);
+int tzk_keyg_resid(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_predg,
+                   const unsigned long long* d_off, int nkeys, int16_t* d_sym);
+int tzk_keyg_unresid(tz_ctx*, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_predg, const uint8_t* d_pred3,
+                     const unsigned long long* d_off, int nkeys, uint8_t* d_tmp, uint8_t* d_frames);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,
             double* h_sse);
 int tzk_sse_blocks(int Hp, int Wp);

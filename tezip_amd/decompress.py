@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from . import _lib, digest, huff, huffr, keycoder, sidecar, zstd
+from . import _lib, digest, huff, huffr, keycoder, keycoderg, sidecar, zstd
 from . import dist as tzdist
 from .compress import SHUFFLE_MARK, make_context, open_model
 from .data_utils import padding_shape
@@ -48,7 +48,7 @@ def check_stream(shape, warm_up, payload_len, key_len):
 
 TAIL_ELEMS = _lib.TZ_NBINS + 8  # the longest trailer: table (<= 2111 symbols) + T + shape(5) + warm_up
 # piece sizes of the streaming paths, read when a run starts (tests/test_gpu_pieces.py shrinks them to make every loop iterate)
-PUT_PIECE = 16 << 20            # bytes of a coded body (TZH1 / TZR1 / TZK1) staged per huff_put / huffr_put / keys_put
+PUT_PIECE = 16 << 20            # bytes of a coded body (TZH1 / TZR1 / TZK1 / TZK2) staged per huff_put / huffr_put / keys_put
 FETCH_WINDOW_BYTES = 16 << 20   # a fetch window holds the frames that fit in this many bytes (at least one)
 PREFETCH_PIECE_BYTES = 16 << 20  # _Prefetch: bytes of entropy.dat decompressed per piece
 PREFETCH_DEPTH = 8              # _Prefetch: pieces queued ahead of the consumer
@@ -71,17 +71,29 @@ def coded_calls(ctx, coded):
     return ctx.huff_begin, ctx.huff_put, ctx.huff_decode
 
 
+def parse_coded_keys(head, path):
+    """The key_frame.dat at `path`, of which `head` holds the first bytes: this build's opt-in formats (TZK1, TZK2) validated
+    whole on the CPU -> keycoder.Parsed / keycoderg.Parsed; None for the reference's zstd frame."""
+    for fmt in (keycoder, keycoderg):
+        if fmt.is_keycoded(head):
+            return fmt.parse(np.fromfile(path, np.uint8))
+    return None
+
+
 def stage_coded_keys(ctx, keys, stack):
-    """A parsed TZK1 key_frame.dat -> the context's frame stack, as frames_begin + frames_put of the zero-except-keys stack
-    leave it (tz_keys_begin / tz_keys_put / tz_keys_decode).  stack: the (nt, H, W) entropy.dat describes."""
+    """A parsed TZK1 / TZK2 key_frame.dat -> the context's frame stack, as frames_begin + frames_put of the zero-except-keys
+    stack leave it (tz_keys_begin / tz_keys_put / tz_keys_decode, or their tz_keysg_* forms).  stack: the (nt, H, W)
+    entropy.dat describes."""
     if (keys.nt, keys.H, keys.W) != tuple(stack):
         raise ValueError("key_frame.dat describes the stack as %r (frames, height, width), entropy.dat's trailer as %r"
                          % ((keys.nt, keys.H, keys.W), tuple(stack)))
-    ctx.keys_begin(keys.body.size, keys.nt, keys.H, keys.W, keys.idx, keys.pred, keys.lengths)
+    begin, put, decode = ((ctx.keysg_begin, ctx.keysg_put, ctx.keysg_decode) if isinstance(keys, keycoderg.Parsed) else
+                          (ctx.keys_begin, ctx.keys_put, ctx.keys_decode))
+    begin(keys.body.size, keys.nt, keys.H, keys.W, keys.idx, keys.pred, keys.lengths)
     piece = PUT_PIECE
     for off in range(0, keys.body.size, piece):
-        ctx.keys_put(off, keys.body[off: off + piece])                      # pageable: the piece is free again on return
-    ctx.keys_decode()
+        put(off, keys.body[off: off + piece])                               # pageable: the piece is free again on return
+    decode()
 
 
 def adopt_contract(DATA_DIR, wts, VERBOSE):
@@ -224,9 +236,9 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
         stages.mark("context + model load")
         with open(paths["key_frame.dat"], "rb") as f:
             head = f.read(64)
-        # this build's opt-in key-frame file (TZK1): validated whole on the CPU; the length the zero-except-keys stack
+        # this build's opt-in key-frame file (TZK1 / TZK2): validated whole on the CPU; the length the zero-except-keys stack
         # would have stands in its header, so the cross-checks below see what they see for the reference's file
-        keys = keycoder.parse(np.fromfile(paths["key_frame.dat"], np.uint8)) if keycoder.is_keycoded(head) else None
+        keys = parse_coded_keys(head, paths["key_frame.dat"])
         key_len = keys.nt * keys.H * keys.W * 3 if keys is not None else zstd.content_size(head)
 
         def checks(nt, H, W):
@@ -484,12 +496,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
     keys = None
     try:
         with open(os.path.join(DATA_DIR, "key_frame.dat"), mode='rb') as f:
-            if keycoder.is_keycoded(f.read(4)):   # this build's opt-in key-frame file: validated here, expanded on the device below
-                keys = keycoder.parse(np.fromfile(os.path.join(DATA_DIR, "key_frame.dat"), np.uint8))
+            # this build's opt-in key-frame file: validated here, expanded on the device below
+            keys = parse_coded_keys(f.read(4), os.path.join(DATA_DIR, "key_frame.dat"))
     except FileNotFoundError:
         pass   # (read() below prints the reference's message)
     if keys is not None and job is not None:
-        print("ERROR: a GPU-coded key_frame.dat (--key-coder huff) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
+        print("ERROR: a GPU-coded key_frame.dat (--key-coder huff / huffg) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
         sys.exit(2)
     key_bytes = None if keys is not None else read("key_frame.dat")
     key_len = keys.nt * keys.H * keys.W * 3 if keys is not None else len(key_bytes)   # (the zero-except-keys stack's size)

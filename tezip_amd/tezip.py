@@ -51,8 +51,9 @@ FLAG_TABLE = (
     (None, "--coder", dict(type=str, choices=("zstd", "huff", "huffr"), default="zstd", dest="coder")),
     # not in the reference: with -c, the coder of key_frame.dat.  zstd = the reference's file; huff = the key frames alone, as
     # predictor residuals Huffman-coded by the GPU (tezip_amd/keycoder.py; the reference cannot read such a file, -u recognises
-    # it by its magic).  Much smaller on smooth frames, LARGER than zstd on sparse ones (README): check with --report's ratio
-    (None, "--key-coder", dict(type=str, choices=("zstd", "huff"), default="zstd", dest="key_coder")),
+    # it by its magic).  Much smaller on smooth frames, LARGER than zstd on sparse ones (README): check with --report's ratio.
+    # huffg = huff with every gray key frame (a single-channel source, widened to RGB) coded as one channel (tezip_amd/keycoderg.py)
+    (None, "--key-coder", dict(type=str, choices=("zstd", "huff", "huffg"), default="zstd", dest="key_coder")),
     # not in the reference: with -c, also write frame_digests.json (tezip_amd/digest.py): per frame the digest of what the stored
     # payload decodes to and of the source frame, taken on the GPU (compress.run(DIGESTS=True)).  The other files do not change
     (None, "--digests", dict(action="store_true", dest="digests")),
@@ -147,7 +148,7 @@ def check_coder_flag(arg):
 
 
 def check_key_coder_flag(arg):
-    """--key-coder huff is valid with -c of one single-GPU job, without --sweep.  Returns None, or the message of a refusal."""
+    """--key-coder huff / huffg is valid with -c of one single-GPU job, without --sweep.  Returns None, or the message of a refusal."""
     if getattr(arg, "key_coder", "zstd") == "zstd":
         return None
     if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
