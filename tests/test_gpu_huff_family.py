@@ -1,0 +1,116 @@
+"""The staged decoders of the four coded formats (tz_huff_*, tz_huffr_*, tz_keys_*, tz_keysg_*) share their host code; each
+must still refuse what it refused before, in the same words, and work after a refusal.  The expected texts are typed in
+from the source of the commit before the entry points were put on common code."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+INVALID, STATE = -1, -4                      # TZ_ERR_INVALID, TZ_ERR_STATE
+N = 16384 + 257                              # a chunk, a run and one element
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from tezip_amd import _lib
+    c = _lib.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def streams(ctx):
+    """{family: (body, the arguments of begin behind the byte count, check(context) of what it decoded)}: one valid stream per format."""
+    from tezip_amd import huff, huffr, keycoder, keycoderg
+    rng = np.random.default_rng(5)
+    pay = np.where(rng.random(N) < 0.1, rng.integers(-9, 10, N), np.array([3, -2, 7])[np.arange(N) % 3]).astype(np.int16)
+    base = int(pay.min())
+    out = {}
+    for name, M, ntok in (("huff", huff, 0), ("huffr", huffr, 8)):
+        ln = M.code_lengths(np.bincount(pay.astype(np.int64) - base) if not ntok else huffr.token_counts(pay, base, int(pay.max()) - base + 1))
+        body = getattr(ctx, name + "_encode_buf")(pay, ln, base).copy()
+
+        def check(c, pay=pay):
+            assert (c.payload_get(0, N) == pay).all()
+        out[name] = (body, (N, ln, base), check)
+    stack = np.zeros((2, 8, 8, 3), np.uint8)
+    stack[0] = rng.integers(0, 256, (8, 8, 3))
+    stack[1] = rng.integers(0, 256, (8, 8, 1))      # gray
+    for name, M in (("keys", keycoder), ("keysg", keycoderg)):
+        p = M.parse(M.encode_file(stack, [0, 1], 2))
+
+        def check(c, stack=stack):
+            assert (c.frames_get(0, 2) == stack).all()
+        out[name] = (p.body.copy(), (2, 8, 8, [0, 1], p.pred.copy(), p.lengths.copy()), check)
+    return out
+
+
+def refused(status, text, fn, *args, **kw):
+    from tezip_amd import _lib
+    with pytest.raises(_lib.TezipError) as e:
+        fn(*args, **kw)
+    assert e.value.status == status and str(e.value) == "tezip_hip status %d: %s" % (status, text)
+
+
+def works(ctx, streams, name):
+    body, args, check = streams[name]
+    getattr(ctx, name + "_begin")(body.size, *args)
+    getattr(ctx, name + "_put")(0, body)
+    getattr(ctx, name + "_decode")()
+    check(ctx)                               # (of the context that decoded)
+
+
+PUT_TEXT = {"huff": "byte range outside the staged Huffman stream", "huffr": "byte range outside the staged Huffman stream",
+            "keys": "byte range outside the staged key-frame stream", "keysg": "byte range outside the staged key-frame stream (TZK2)"}
+SIBLING = {"huff": "huffr", "huffr": "huff", "keys": "keysg", "keysg": "keys"}
+
+
+@pytest.mark.parametrize("name", ["huff", "huffr", "keys", "keysg"])
+def test_refusals_keep_their_words_and_leave_the_decoder_working(name, streams):
+    from tezip_amd import _lib
+    ctx = _lib.Context(0)                    # a context of its own: nothing is staged in it
+    try:
+        body, args, _ = streams[name]
+        begin, put, decode = (getattr(ctx, name + s) for s in ("_begin", "_put", "_decode"))
+        nothing = "tz_%s_decode needs a stream staged with tz_%s_begin / tz_%s_put" % (name, name, name)
+        refused(STATE, nothing, decode)
+        refused(INVALID, PUT_TEXT[name], put, 0, body[:4])                      # (nothing staged: no range is inside)
+        works(ctx, streams, name)
+        begin(body.size, *args)
+        refused(INVALID, PUT_TEXT[name], put, body.size - 3, body[:4])          # ends one byte behind the stream
+        works(ctx, streams, name)
+        sib = SIBLING[name]
+        getattr(ctx, sib + "_begin")(streams[sib][0].size, *streams[sib][1])    # the sibling format's begin
+        refused(INVALID, PUT_TEXT[name], put, 0, body[:4])
+        refused(STATE, nothing, decode)
+        works(ctx, streams, sib)
+        works(ctx, streams, name)
+        if name in ("huff", "huffr"):
+            n, ln, base = args
+            refused(INVALID, "huffman: run length 128, this build codes runs of 256", begin, body.size, n, ln, base, run=128)
+            index = 2 * 4 + 66 * 2            # two chunk offsets, ceil(N / 256) = 66 run sizes
+            for nbytes in (body.size + 1, index - 4):
+                refused(INVALID, "huffman: a stream of %d bytes cannot hold the %d-byte index of %d elements and whole words" % (nbytes, index, N),
+                        begin, nbytes, n, ln, base)
+        else:
+            n = 2 * 8 * 8 * 3 if name == "keys" else 8 * 8 * 3 + 8 * 8
+            index = 4 + 4                     # one chunk offset; 2 (keys: 384 symbols) or 1 (keysg: 256) run sizes, padded
+            refused(INVALID, "huffman: a stream of %d bytes cannot hold the %d-byte index of %d elements and whole words" % (body.size + 2, index, n),
+                    begin, body.size + 2, *args)
+        works(ctx, streams, name)
+    finally:
+        ctx.close()
+
+
+def test_key_decoders_refuse_a_stream_put_in_part(streams):
+    from tezip_amd import _lib
+    ctx = _lib.Context(0)
+    try:
+        for name in ("keys", "keysg"):
+            body, args, _ = streams[name]
+            getattr(ctx, name + "_begin")(body.size, *args)
+            getattr(ctx, name + "_put")(0, body[:8])
+            refused(STATE, "tz_%s_decode: 8 of the stream's %d bytes were put" % (name, body.size), getattr(ctx, name + "_decode"))
+            works(ctx, streams, name)
+    finally:
+        ctx.close()

@@ -689,6 +689,66 @@ class Context:
         self._ck(self.lib.tz_decoded_digests(self.h, int(first), int(count), out.ctypes.data))
         return out
 
+    # ---- the opt-in coded streams.  Private helpers behind the four families below: `fn` is the library's entry point, `ntok` the
+    # repeat tokens behind the literals of `lengths` (the A the library is given is the number of literals), `what` names a
+    # pred array in a message.
+    def _stream_encode(self, fn, lengths, base, ntok):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        nbytes = C.c_size_t(0)
+        self._ck(fn(self.h, ln.ctypes.data, int(ln.size) - ntok, int(base), C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def _stream_get(self, fn, offset, count, out):
+        if out is None:
+            out = np.empty(count, np.uint8)
+        self._ck(fn(self.h, int(offset), int(count), _ptr(out, np.uint8)))
+        return out
+
+    def _stream_begin(self, fn, nbytes, n, lengths, base, run, ntok):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        self._ck(fn(self.h, int(nbytes), int(n), ln.ctypes.data, int(ln.size) - ntok, int(base), int(run)))
+
+    def _stream_put(self, fn, offset, piece):
+        self._ck(fn(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
+
+    def _stream_encode_buf(self, fn, x, lengths, base, out, ntok):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        n = _numel(x)
+        if out is None:   # the most a stream can need: 12 bits per element, a pad word per chunk, the index
+            out = np.empty(n * 3 // 2 + (n // 16384 + 1) * 8 + (n // 256 + 1) * 2 + 64, np.uint8)
+        nbytes = C.c_size_t(0)
+        self._ck(fn(self.h, _ptr(x), n, ln.ctypes.data, int(ln.size) - ntok, int(base), _ptr(out), _numel(out), C.byref(nbytes)))
+        return out[: nbytes.value]
+
+    def _stream_decode_buf(self, fn, stream, n, lengths, base, run, out, ntok):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        if out is None:
+            out = np.empty(n, np.int16)
+        self._ck(fn(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size) - ntok, int(base), int(run), _ptr(out)))
+        return out
+
+    @staticmethod
+    def _key_args(idx, pred, lengths, what):
+        ix, pr, ln = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(pred, np.uint8), np.ascontiguousarray(lengths, np.uint8)
+        if pr.size != ix.size or ln.size != 256:
+            raise ValueError("%d %s for %d key frames, %d code lengths (256 wanted)" % (pr.size, what, ix.size, ln.size))
+        return ix, pr, ln
+
+    def _keys_encode(self, fn, idx, pred, lengths, what):
+        ix, pr, ln = self._key_args(idx, pred, lengths, what)
+        nbytes = C.c_size_t(0)
+        self._ck(fn(self.h, ix.ctypes.data, int(ix.size), pr.ctypes.data, ln.ctypes.data, C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def _keys_begin(self, fn, nbytes, nt, h, w, idx, pred, lengths, what):
+        ix, pr, ln = self._key_args(idx, pred, lengths, what)
+        self._ck(fn(self.h, int(nbytes), int(nt), int(h), int(w), ix.ctypes.data, int(ix.size), pr.ctypes.data, ln.ctypes.data))
+        self._keys_shape = (int(nt), int(h), int(w))
+
+    def _keys_decode(self, fn):
+        self._ck(fn(self.h))
+        self._staged = self._shape = self._keys_shape
+
     # ---- opt-in Huffman coder (tz_huff_*; format: tezip_amd/huff.py)
     def huff_counts(self):
         """Counts of the resident payload -> (uint64[A], base): counts[s] of the value s + base."""
@@ -699,45 +759,26 @@ class Context:
 
     def huff_encode(self, lengths, base):
         """Code the resident payload into the resident stream (index | bits); returns its size in bytes."""
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        nbytes = C.c_size_t(0)
-        self._ck(self.lib.tz_huff_encode(self.h, ln.ctypes.data, int(ln.size), int(base), C.byref(nbytes)))
-        return int(nbytes.value)
+        return self._stream_encode(self.lib.tz_huff_encode, lengths, base, 0)
 
     def huff_get(self, offset, count, out=None):
-        if out is None:
-            out = np.empty(count, np.uint8)
-        self._ck(self.lib.tz_huff_get(self.h, int(offset), int(count), _ptr(out, np.uint8)))
-        return out
+        return self._stream_get(self.lib.tz_huff_get, offset, count, out)
 
     def huff_begin(self, nbytes, n, lengths, base, run=256):
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        self._ck(self.lib.tz_huff_begin(self.h, int(nbytes), int(n), ln.ctypes.data, int(ln.size), int(base), int(run)))
+        self._stream_begin(self.lib.tz_huff_begin, nbytes, n, lengths, base, run, 0)
 
     def huff_put(self, offset, piece):
-        self._ck(self.lib.tz_huff_put(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
+        self._stream_put(self.lib.tz_huff_put, offset, piece)
 
     def huff_decode(self):
         self._ck(self.lib.tz_huff_decode(self.h))
 
     def huff_encode_buf(self, x, lengths, base, out=None):
         """Stand-alone: int16 values (host or device) -> the coded stream (index | bits) as a uint8 array."""
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        n = _numel(x)
-        if out is None:   # the most a stream can need: 12 bits per symbol, a pad word per chunk, the index
-            out = np.empty(n * 3 // 2 + (n // 16384 + 1) * 8 + (n // 256 + 1) * 2 + 64, np.uint8)
-        nbytes = C.c_size_t(0)
-        self._ck(self.lib.tz_huff_encode_buf(self.h, _ptr(x), n, ln.ctypes.data, int(ln.size), int(base), _ptr(out), _numel(out),
-                                             C.byref(nbytes)))
-        return out[: nbytes.value]
+        return self._stream_encode_buf(self.lib.tz_huff_encode_buf, x, lengths, base, out, 0)
 
     def huff_decode_buf(self, stream, n, lengths, base, run=256, out=None):
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        if out is None:
-            out = np.empty(n, np.int16)
-        self._ck(self.lib.tz_huff_decode_buf(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size), int(base),
-                                             int(run), _ptr(out)))
-        return out
+        return self._stream_decode_buf(self.lib.tz_huff_decode_buf, stream, n, lengths, base, run, out, 0)
 
     # ---- opt-in key-frame coder (tz_keys_*; format: tezip_amd/keycoder.py)
     def keys_counts(self, idx):
@@ -749,34 +790,20 @@ class Context:
 
     def keys_encode(self, idx, pred, lengths):
         """Code the frames `idx` of the resident stack into the resident key stream (index | bits); returns its size."""
-        ix, pr, ln = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(pred, np.uint8), np.ascontiguousarray(lengths, np.uint8)
-        if pr.size != ix.size or ln.size != 256:
-            raise ValueError("%d predictor ids for %d key frames, %d code lengths (256 wanted)" % (pr.size, ix.size, ln.size))
-        nbytes = C.c_size_t(0)
-        self._ck(self.lib.tz_keys_encode(self.h, ix.ctypes.data, int(ix.size), pr.ctypes.data, ln.ctypes.data, C.byref(nbytes)))
-        return int(nbytes.value)
+        return self._keys_encode(self.lib.tz_keys_encode, idx, pred, lengths, "predictor ids")
 
     def keys_get(self, offset, count, out=None):
-        if out is None:
-            out = np.empty(count, np.uint8)
-        self._ck(self.lib.tz_keys_get(self.h, int(offset), int(count), _ptr(out, np.uint8)))
-        return out
+        return self._stream_get(self.lib.tz_keys_get, offset, count, out)
 
     def keys_begin(self, nbytes, nt, h, w, idx, pred, lengths):
-        ix, pr, ln = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(pred, np.uint8), np.ascontiguousarray(lengths, np.uint8)
-        if pr.size != ix.size or ln.size != 256:
-            raise ValueError("%d predictor ids for %d key frames, %d code lengths (256 wanted)" % (pr.size, ix.size, ln.size))
-        self._ck(self.lib.tz_keys_begin(self.h, int(nbytes), int(nt), int(h), int(w), ix.ctypes.data, int(ix.size), pr.ctypes.data,
-                                        ln.ctypes.data))
-        self._keys_shape = (int(nt), int(h), int(w))
+        self._keys_begin(self.lib.tz_keys_begin, nbytes, nt, h, w, idx, pred, lengths, "predictor ids")
 
     def keys_put(self, offset, piece):
-        self._ck(self.lib.tz_keys_put(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
+        self._stream_put(self.lib.tz_keys_put, offset, piece)
 
     def keys_decode(self):
         """-> the context's frame stack, as frames_begin + frames_put of the zero-except-keys stack leave it."""
-        self._ck(self.lib.tz_keys_decode(self.h))
-        self._staged = self._shape = self._keys_shape
+        self._keys_decode(self.lib.tz_keys_decode)
 
     def keys_residual_buf(self, frames, pred, out=None):
         """Stand-alone: uint8 (k, H, W, 3) frames (host or device) -> their k * H * W * 3 int16 residual symbols."""
@@ -811,34 +838,20 @@ class Context:
 
     def keysg_encode(self, idx, predg, lengths):
         """Code the frames `idx` of the resident stack into the resident key stream (index | bits); returns its size."""
-        ix, pr, ln = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(predg, np.uint8), np.ascontiguousarray(lengths, np.uint8)
-        if pr.size != ix.size or ln.size != 256:
-            raise ValueError("%d pred bytes for %d key frames, %d code lengths (256 wanted)" % (pr.size, ix.size, ln.size))
-        nbytes = C.c_size_t(0)
-        self._ck(self.lib.tz_keysg_encode(self.h, ix.ctypes.data, int(ix.size), pr.ctypes.data, ln.ctypes.data, C.byref(nbytes)))
-        return int(nbytes.value)
+        return self._keys_encode(self.lib.tz_keysg_encode, idx, predg, lengths, "pred bytes")
 
     def keysg_get(self, offset, count, out=None):
-        if out is None:
-            out = np.empty(count, np.uint8)
-        self._ck(self.lib.tz_keysg_get(self.h, int(offset), int(count), _ptr(out, np.uint8)))
-        return out
+        return self._stream_get(self.lib.tz_keysg_get, offset, count, out)
 
     def keysg_begin(self, nbytes, nt, h, w, idx, predg, lengths):
-        ix, pr, ln = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(predg, np.uint8), np.ascontiguousarray(lengths, np.uint8)
-        if pr.size != ix.size or ln.size != 256:
-            raise ValueError("%d pred bytes for %d key frames, %d code lengths (256 wanted)" % (pr.size, ix.size, ln.size))
-        self._ck(self.lib.tz_keysg_begin(self.h, int(nbytes), int(nt), int(h), int(w), ix.ctypes.data, int(ix.size), pr.ctypes.data,
-                                         ln.ctypes.data))
-        self._keys_shape = (int(nt), int(h), int(w))
+        self._keys_begin(self.lib.tz_keysg_begin, nbytes, nt, h, w, idx, predg, lengths, "pred bytes")
 
     def keysg_put(self, offset, piece):
-        self._ck(self.lib.tz_keysg_put(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
+        self._stream_put(self.lib.tz_keysg_put, offset, piece)
 
     def keysg_decode(self):
         """-> the context's frame stack, as frames_begin + frames_put of the zero-except-keys stack leave it."""
-        self._ck(self.lib.tz_keysg_decode(self.h))
-        self._staged = self._shape = self._keys_shape
+        self._keys_decode(self.lib.tz_keysg_decode)
 
     @staticmethod
     def _keysg_symbols(predg, h, w):
@@ -870,7 +883,7 @@ class Context:
         return out
 
     # ---- opt-in Huffman coder with repeat tokens (tz_huffr_*; format: tezip_amd/huffr.py).  `lengths` holds the A literals
-    # and then the 8 tokens; the A the library is given is the number of literals.
+    # and then the 8 tokens.
     def huffr_counts(self, x=None):
         """Token counts of the resident payload (or of the int16 array x) -> (uint64[A + 8], base): the literals s + base,
         then the repeat tokens T_0..T_7."""
@@ -884,45 +897,26 @@ class Context:
 
     def huffr_encode(self, lengths, base):
         """Code the resident payload into the resident stream (index | bits); returns its size in bytes."""
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        nbytes = C.c_size_t(0)
-        self._ck(self.lib.tz_huffr_encode(self.h, ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), C.byref(nbytes)))
-        return int(nbytes.value)
+        return self._stream_encode(self.lib.tz_huffr_encode, lengths, base, HUFFR_NTOK)
 
     def huffr_get(self, offset, count, out=None):
-        if out is None:
-            out = np.empty(count, np.uint8)
-        self._ck(self.lib.tz_huffr_get(self.h, int(offset), int(count), _ptr(out, np.uint8)))
-        return out
+        return self._stream_get(self.lib.tz_huffr_get, offset, count, out)
 
     def huffr_begin(self, nbytes, n, lengths, base, run=256):
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        self._ck(self.lib.tz_huffr_begin(self.h, int(nbytes), int(n), ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), int(run)))
+        self._stream_begin(self.lib.tz_huffr_begin, nbytes, n, lengths, base, run, HUFFR_NTOK)
 
     def huffr_put(self, offset, piece):
-        self._ck(self.lib.tz_huffr_put(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
+        self._stream_put(self.lib.tz_huffr_put, offset, piece)
 
     def huffr_decode(self):
         self._ck(self.lib.tz_huffr_decode(self.h))
 
     def huffr_encode_buf(self, x, lengths, base, out=None):
         """Stand-alone: int16 values (host or device) -> the coded stream (index | bits) as a uint8 array."""
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        n = _numel(x)
-        if out is None:   # the most a stream can need: 12 bits per element, a pad word per chunk, the index
-            out = np.empty(n * 3 // 2 + (n // 16384 + 1) * 8 + (n // 256 + 1) * 2 + 64, np.uint8)
-        nbytes = C.c_size_t(0)
-        self._ck(self.lib.tz_huffr_encode_buf(self.h, _ptr(x), n, ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), _ptr(out),
-                                              _numel(out), C.byref(nbytes)))
-        return out[: nbytes.value]
+        return self._stream_encode_buf(self.lib.tz_huffr_encode_buf, x, lengths, base, out, HUFFR_NTOK)
 
     def huffr_decode_buf(self, stream, n, lengths, base, run=256, out=None):
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        if out is None:
-            out = np.empty(n, np.int16)
-        self._ck(self.lib.tz_huffr_decode_buf(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size) - HUFFR_NTOK,
-                                              int(base), int(run), _ptr(out)))
-        return out
+        return self._stream_decode_buf(self.lib.tz_huffr_decode_buf, stream, n, lengths, base, run, out, HUFFR_NTOK)
 
     # ---- operator seams
     def delta_encode(self, pred, orig, zero_mask=None, out=None):

@@ -260,6 +260,20 @@ def check_key_coder(key_coder, sharded=False):
     return None
 
 
+def _write_coded(path, front, nbytes, get, label, t0):
+    """The file of a coder whose stream is resident on the device: `front`, then the nbytes of the stream, fetched by
+    get(offset, count, out=) piece by piece into two buffers in turn.  label: what to print the time since t0 under."""
+    bufs = [np.empty(min(HUFF_PIECE, nbytes), np.uint8) for _ in range(2)]
+    with open(path, mode='wb') as f:
+        f.write(front)
+        for k, off in enumerate(range(0, nbytes, HUFF_PIECE)):
+            cnt = min(HUFF_PIECE, nbytes - off)
+            f.write(get(off, cnt, out=bufs[k % 2][:cnt]))
+    if label:
+        print("{0}:{1}".format(label, time.perf_counter() - t0) + "[sec]")
+    return len(front) + nbytes
+
+
 def _huff_key_file(ctx, path, nt, H, W, key_idx, verbose):
     """key_frame.dat of KEY_CODER="huff": the key frames of the resident stack are counted under the four predictors, the
     predictors and the one code are chosen here (keycoder.choose_predictors, tz_huff_lengths), the device codes them
@@ -272,15 +286,7 @@ def _huff_key_file(ctx, path, nt, H, W, key_idx, verbose):
     n = len(key_idx) * H * W * 3
     nruns, nchunks = huff.geometry(n)
     front = keycoder.pack_front(nt, H, W, key_idx, pred, lengths, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4)
-    bufs = [np.empty(min(HUFF_PIECE, nbytes), np.uint8) for _ in range(2)]
-    with open(path, mode='wb') as f:
-        f.write(front)
-        for k, off in enumerate(range(0, nbytes, HUFF_PIECE)):
-            cnt = min(HUFF_PIECE, nbytes - off)
-            f.write(ctx.keys_get(off, cnt, out=bufs[k % 2][:cnt]))
-    if verbose:
-        print("key_coding:{0}".format(time.perf_counter() - t0) + "[sec]")
-    return len(front) + nbytes
+    return _write_coded(path, front, nbytes, ctx.keys_get, "key_coding" if verbose else None, t0)
 
 
 def _huffg_key_file(ctx, path, nt, H, W, key_idx, verbose):
@@ -296,15 +302,7 @@ def _huffg_key_file(ctx, path, nt, H, W, key_idx, verbose):
     n = keycoderg.offsets(gray, H, W)[1]
     nruns, nchunks = huff.geometry(n)
     front = keycoderg.pack_front(nt, H, W, key_idx, predg, lengths, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4)
-    bufs = [np.empty(min(HUFF_PIECE, nbytes), np.uint8) for _ in range(2)]
-    with open(path, mode='wb') as f:
-        f.write(front)
-        for k, off in enumerate(range(0, nbytes, HUFF_PIECE)):
-            cnt = min(HUFF_PIECE, nbytes - off)
-            f.write(ctx.keysg_get(off, cnt, out=bufs[k % 2][:cnt]))
-    if verbose:
-        print("key_coding:{0}".format(time.perf_counter() - t0) + "[sec]")
-    return len(front) + nbytes
+    return _write_coded(path, front, nbytes, ctx.keysg_get, "key_coding" if verbose else None, t0)
 
 
 class _Done:
@@ -333,15 +331,7 @@ def _huff_entropy_file(ctx, path, n, trailer, verbose, coder="huff"):
         nbytes = ctx.huff_encode(lengths, base)
     nruns, nchunks = huff.geometry(n)
     front = fmt.pack_front(trailer, lengths, base, n, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4)
-    bufs = [np.empty(min(HUFF_PIECE, nbytes), np.uint8) for _ in range(2)]
-    with open(path, mode='wb') as f:
-        f.write(front)
-        for k, off in enumerate(range(0, nbytes, HUFF_PIECE)):
-            cnt = min(HUFF_PIECE, nbytes - off)
-            f.write(ctx.huff_get(off, cnt, out=bufs[k % 2][:cnt]))
-    if verbose:
-        print("huffman_coding:{0}".format(time.perf_counter() - t0) + "[sec]")
-    return len(front) + nbytes
+    return _write_coded(path, front, nbytes, ctx.huff_get, "huffman_coding" if verbose else None, t0)
 
 
 def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False,

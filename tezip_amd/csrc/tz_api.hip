@@ -2311,13 +2311,13 @@ static void huff_geometry(size_t n, size_t* nruns, size_t* nchunks, size_t* inde
 }
 
 // d_in (device, n int16) -> ctx->d_huff = index | bits; *bytes its size.  Waits once, for the size of the bit stream.
-// tokens: the TZR1 stream (lengths holds A + TZ_HUFFR_NTOK entries, k_huffr_size / k_huffr_enc) instead of the TZH1 one.
+// ntok: TZ_HUFFR_NTOK for the TZR1 stream (lengths then holds A + ntok entries, k_huffr_size / k_huffr_enc), 0 for TZH1.
 // keys: the stream goes to the key-frame coder's buffer ctx->d_keys instead, and what the entropy coders hold stays.
-static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uint8_t* lengths, int A, int base, size_t* bytes,
-                           bool tokens = false, bool keys = false) {
+static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uint8_t* lengths, int A, int base, size_t* bytes, int ntok,
+                           bool keys = false) {
     if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
     std::vector<uint16_t> enc;
-    TZ_TRY(huff_tables(ctx, lengths, A, base, &enc, nullptr, tokens ? TZ_HUFFR_NTOK : 0));
+    TZ_TRY(huff_tables(ctx, lengths, A, base, &enc, nullptr, ntok));
     size_t nruns, nchunks, index_bytes;
     huff_geometry(n, &nruns, &nchunks, &index_bytes);
     void *d_enc, *d_idx, *d_meta;
@@ -2328,8 +2328,7 @@ static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uin
     TZ_HIP(ctx, hipMemsetAsync(d_idx, 0, index_bytes, ctx->stream));   // (the padding behind an odd number of run sizes is part of the file)
     unsigned* d_chunk_off = (unsigned*)d_idx;
     uint16_t* d_run_bits = (uint16_t*)((uint8_t*)d_idx + nchunks * 4);
-    if (tokens) TZ_TRY(tzk_huffr_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta));
-    else TZ_TRY(tzk_huff_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta));
+    TZ_TRY(tzk_huff_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, ntok, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta));
     tz_huff_meta meta;
     TZ_TRY(tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream));
     TZ_TRY(tz_stream_sync(ctx));
@@ -2338,71 +2337,21 @@ static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uin
     const size_t total = index_bytes + (size_t)meta.total_words * 4;
     uint8_t* d_stream;
     if (keys) {
-        ctx->keys_n = ctx->keysg_n = 0;   // (a staged decoder stream, if any, is gone)
+        ctx->keys_kind = tz_ctx::KEYS_NONE;   // (a staged decoder stream, if any, is gone)
         TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, total));
         ctx->keys_bytes = total;
         d_stream = ctx->d_keys;
     } else {
-        ctx->huff_n = ctx->huffr_n = 0;
+        ctx->huff_kind = tz_ctx::HUFF_NONE;
         TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, total));
         ctx->huff_bytes = total;
         d_stream = ctx->d_huff;
     }
     TZ_HIP(ctx, hipMemcpyAsync(d_stream, d_idx, index_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    if (tokens)
-        TZ_TRY(tzk_huffr_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(d_stream + index_bytes),
-                             (size_t)meta.total_words));
-    else
-        TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(d_stream + index_bytes),
-                            (size_t)meta.total_words));
+    TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, ntok, d_run_bits, d_chunk_off, (unsigned*)(d_stream + index_bytes),
+                        (size_t)meta.total_words));
     *bytes = total;
     return TZ_OK;
-}
-
-extern "C" int tz_huff_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
-    tz_roctx_range roctx_("tz_huff_counts");
-    if (!ctx || !counts || !A || !base) return TZ_ERR_INVALID;
-    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huff_counts needs a resident payload (tz_encode with payload == NULL)");
-    void *d_hist, *d_meta;
-    std::vector<unsigned long long> h(TZ_HUFF_COUNT_BINS);
-    tz_huff_meta meta;
-    int rc = tz_pool_alloc(ctx, TZ_HUFF_COUNT_BINS * sizeof(unsigned long long), &d_hist);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta);
-    if (rc == TZ_OK) rc = tzk_huff_count(ctx, ctx->d_payload, ctx->payload_len, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
-    if (rc == TZ_OK) rc = tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream);
-    if (rc == TZ_OK) rc = tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    TZ_TRY(rc);
-    int lo = -1, hi = -1;
-    for (int b = 0; b < TZ_HUFF_COUNT_BINS; ++b)
-        if (h[b]) {
-            if (lo < 0) lo = b;
-            hi = b;
-        }
-    if (meta.bad || lo < 0 || hi - lo + 1 > TZ_NBINS)
-        return tz_fail(ctx, TZ_ERR_INVALID, "tz_huff_counts: the payload's values span more than %d symbols", TZ_NBINS);
-    for (int s = 0; s < TZ_NBINS; ++s) counts[s] = lo + s <= hi ? h[lo + s] : 0;
-    *A = hi - lo + 1;
-    *base = lo - TZ_HUFF_COUNT_BIAS;
-    return TZ_OK;
-}
-
-extern "C" int tz_huff_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes) {
-    tz_roctx_range roctx_("tz_huff_encode");
-    if (!ctx || !bytes) return TZ_ERR_INVALID;
-    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huff_encode needs a resident payload (tz_encode with payload == NULL)");
-    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes);
-    tz_pool_release_all(ctx);
-    return rc;
-}
-
-extern "C" int tz_huff_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
-    if (!ctx || !out) return TZ_ERR_INVALID;
-    if (!ctx->d_huff || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
-        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the resident Huffman stream");
-    TZ_TRY(tz_d2h(ctx, out, ctx->d_huff + offset, count, ctx->stream));
-    return tz_stream_sync(ctx);
 }
 
 // what a stream of `bytes` bytes must satisfy to be the index | bits of n elements; *stream_words its bit stream
@@ -2418,113 +2367,33 @@ static int huff_check_stream(tz_ctx* ctx, size_t bytes, size_t n, int R, size_t*
     return TZ_OK;
 }
 
-extern "C" int tz_huff_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
-    if (!ctx) return TZ_ERR_INVALID;
-    size_t sw;
-    TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
-    std::vector<uint16_t> dec;
-    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec));
-    ctx->huff_n = ctx->huffr_n = 0;
-    ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload is about to receive the expanded stream
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, std::max<size_t>(bytes, 16)));
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, std::max<size_t>(n, 8) * 2));
-    ctx->payload_len = 0;
-    ctx->huff_bytes = bytes;
-    ctx->huff_dec_tab.swap(dec);
-    ctx->huff_base = base;
-    ctx->huff_n = n;
-    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
-    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
-    return TZ_OK;
-}
-
-extern "C" int tz_huff_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
-    if (!ctx || !src) return TZ_ERR_INVALID;
-    if (!ctx->d_huff || !ctx->huff_n || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
-        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged Huffman stream");
-    return tz_h2d(ctx, ctx->d_huff + offset, src, count, ctx->copy_stream);
-}
-
-static int huff_decode_dev(tz_ctx* ctx, const uint8_t* d_stream, size_t stream_words, size_t n, const std::vector<uint16_t>& dec, int base,
-                           int16_t* d_out) {
+static int huff_decode_dev(tz_ctx* ctx, const uint8_t* d_stream, size_t stream_words, size_t n, const std::vector<uint16_t>& dec, int A, int base,
+                           int ntok, int16_t* d_out) {
     size_t nruns, nchunks, index_bytes;
     huff_geometry(n, &nruns, &nchunks, &index_bytes);
     void* d_dec;
     TZ_TRY(tz_pool_alloc(ctx, dec.size() * 2, &d_dec));
     TZ_TRY(tz_upload(ctx, d_dec, dec.data(), dec.size() * 2));
     return tzk_huff_dec(ctx, (const unsigned*)d_stream, (const uint16_t*)(d_stream + nchunks * 4), (const unsigned*)(d_stream + index_bytes),
-                        stream_words, (const uint16_t*)d_dec, base, n, d_out);
+                        stream_words, (const uint16_t*)d_dec, A, base, ntok, n, d_out);
 }
 
-extern "C" int tz_huff_decode(tz_ctx* ctx) {
-    tz_roctx_range roctx_("tz_huff_decode");
-    if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->huff_n || !ctx->d_huff || !ctx->d_payload || ctx->cap_payload < ctx->huff_n * 2)
-        return tz_fail(ctx, TZ_ERR_STATE, "tz_huff_decode needs a stream staged with tz_huff_begin / tz_huff_put");
-    size_t sw;
-    TZ_TRY(huff_check_stream(ctx, ctx->huff_bytes, ctx->huff_n, TZ_HUFF_RUN, &sw));
-    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of tz_huff_put
-    TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
-    const int rc = huff_decode_dev(ctx, ctx->d_huff, sw, ctx->huff_n, ctx->huff_dec_tab, ctx->huff_base, ctx->d_payload);
-    if (rc == TZ_OK) ctx->payload_len = ctx->huff_n;   // exactly as if tz_payload_begin / tz_payload_put had staged them
-    tz_pool_release_all(ctx);
-    return rc;
-}
+// One body per entry point of the two entropy coders, `--coder huff` (TZH1, ntok == 0) and `--coder huffr` (TZR1, ntok ==
+// TZ_HUFFR_NTOK: the runs are tokenised first, tezip_amd/huffr.py, and `lengths` holds A + 8 bytes).  `who` is the entry
+// point's family, "tz_huff" or "tz_huffr", for the messages.  Both stage into the same buffers; ctx->huff_kind says which
+// format's begin did, so each put and decode refuses the other's stream.
+static tz_ctx::tz_huff_kind huff_kind_of(int ntok) { return ntok ? tz_ctx::HUFF_TZR1 : tz_ctx::HUFF_TZH1; }
 
-extern "C" int tz_huff_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
-                                  size_t capacity, size_t* bytes) {
-    if (!ctx || !in || !out || !bytes) return TZ_ERR_INVALID;
-    const void* din = nullptr;
-    int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
-    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes);
-    if (rc == TZ_OK && *bytes > capacity) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: the stream needs %zu bytes, the buffer holds %zu", *bytes, capacity);
-    if (rc == TZ_OK) {
-        if (tz_is_device_ptr(out)) {
-            hipError_t e = hipMemcpyAsync(out, ctx->d_huff, *bytes, hipMemcpyDeviceToDevice, ctx->stream);
-            if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "stream copy: %s", hipGetErrorString(e));
-        } else {
-            rc = tz_d2h(ctx, out, ctx->d_huff, *bytes, ctx->stream);
-        }
-    }
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
-}
-
-extern "C" int tz_huff_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
-                                  int16_t* out) {
-    if (!ctx || !stream || !out) return TZ_ERR_INVALID;
-    size_t sw;
-    TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
-    std::vector<uint16_t> dec;
-    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec));
-    const void* din = nullptr;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, stream, bytes, &din);
-    if (rc == TZ_OK && ((uintptr_t)din & 3)) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: a device stream must be 4-byte aligned");
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = huff_decode_dev(ctx, (const uint8_t*)din, sw, n, dec, base, (int16_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
-}
-
-// --------------------------------------------------------------------------- Huffman coder with repeat tokens (TZR1)
-// `--coder huffr`: the entry points above, one by one, for the stream whose runs are tokenised first (tezip_amd/huffr.py,
-// k_huffr_* in tz_codec.hip).  A code has A literals and TZ_HUFFR_NTOK repeat tokens, so `lengths` holds A + 8 bytes here.
-// The resident stream buffer and the index layout are the Huffman coder's.
-static int huffr_counts_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, unsigned long long* counts, int* A, int* base) {
+// the counts of n device elements: the A literals from the lowest to the highest value present, then the ntok tokens
+static int huff_counts_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, int ntok, const char* who, unsigned long long* counts, int* A, int* base) {
     void *d_hist, *d_meta;
-    std::vector<unsigned long long> h(TZ_HUFF_COUNT_BINS + TZ_HUFFR_NTOK);
+    std::vector<unsigned long long> h(TZ_HUFF_COUNT_BINS + ntok);
     tz_huff_meta meta;
     int rc = tz_pool_alloc(ctx, h.size() * sizeof(unsigned long long), &d_hist);
     if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta);
-    if (rc == TZ_OK) rc = tzk_huffr_count(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
+    if (rc == TZ_OK)
+        rc = ntok ? tzk_huffr_count(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta)
+                  : tzk_huff_count(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
     if (rc == TZ_OK) rc = tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream);
     if (rc == TZ_OK) rc = tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream);
     if (rc == TZ_OK) rc = tz_stream_sync(ctx);
@@ -2536,41 +2405,37 @@ static int huffr_counts_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, unsigned
             hi = b;
         }
     if (meta.bad || lo < 0 || hi - lo + 1 > TZ_NBINS)
-        return tz_fail(ctx, TZ_ERR_INVALID, "tz_huffr_counts: the payload's values span more than %d symbols", TZ_NBINS);
+        return tz_fail(ctx, TZ_ERR_INVALID, "%s_counts: the payload's values span more than %d symbols", who, TZ_NBINS);
     const int a = hi - lo + 1;
-    for (int s = 0; s < TZ_NBINS + TZ_HUFFR_NTOK; ++s) counts[s] = s < a ? h[lo + s] : s < a + TZ_HUFFR_NTOK ? h[TZ_HUFF_COUNT_BINS + s - a] : 0;
+    for (int s = 0; s < TZ_NBINS + ntok; ++s) counts[s] = s < a ? h[lo + s] : s < a + ntok ? h[TZ_HUFF_COUNT_BINS + s - a] : 0;
     *A = a;
     *base = lo - TZ_HUFF_COUNT_BIAS;
     return TZ_OK;
 }
 
-extern "C" int tz_huffr_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
-    tz_roctx_range roctx_("tz_huffr_counts");
+static int huff_counts(tz_ctx* ctx, int ntok, const char* who, unsigned long long* counts, int* A, int* base) {
     if (!ctx || !counts || !A || !base) return TZ_ERR_INVALID;
-    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huffr_counts needs a resident payload (tz_encode with payload == NULL)");
-    const int rc = huffr_counts_dev(ctx, ctx->d_payload, ctx->payload_len, counts, A, base);
+    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "%s_counts needs a resident payload (tz_encode with payload == NULL)", who);
+    const int rc = huff_counts_dev(ctx, ctx->d_payload, ctx->payload_len, ntok, who, counts, A, base);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-extern "C" int tz_huffr_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes) {
-    tz_roctx_range roctx_("tz_huffr_encode");
+static int huff_encode(tz_ctx* ctx, int ntok, const char* who, const uint8_t* lengths, int A, int base, size_t* bytes) {
     if (!ctx || !bytes) return TZ_ERR_INVALID;
-    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huffr_encode needs a resident payload (tz_encode with payload == NULL)");
-    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes, true);
+    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "%s_encode needs a resident payload (tz_encode with payload == NULL)", who);
+    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes, ntok);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-extern "C" int tz_huffr_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) { return tz_huff_get(ctx, offset, count, out); }
-
-extern "C" int tz_huffr_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
+static int huff_begin(tz_ctx* ctx, int ntok, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
     if (!ctx) return TZ_ERR_INVALID;
     size_t sw;
     TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
     std::vector<uint16_t> dec;
-    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, TZ_HUFFR_NTOK));
-    ctx->huff_n = ctx->huffr_n = 0;
+    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, ntok));
+    ctx->huff_kind = tz_ctx::HUFF_NONE;
     ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload is about to receive the expanded stream
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, std::max<size_t>(bytes, 16)));
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, std::max<size_t>(n, 8) * 2));
@@ -2578,52 +2443,41 @@ extern "C" int tz_huffr_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t
     ctx->huff_bytes = bytes;
     ctx->huff_dec_tab.swap(dec);
     ctx->huff_base = base;
-    ctx->huffr_A = A;
-    ctx->huffr_n = n;
+    ctx->huff_A = A;
+    ctx->huff_n = n;
+    ctx->huff_kind = huff_kind_of(ntok);
     TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
     return TZ_OK;
 }
 
-extern "C" int tz_huffr_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
+static int huff_put(tz_ctx* ctx, int ntok, size_t offset, size_t count, const uint8_t* src) {
     if (!ctx || !src) return TZ_ERR_INVALID;
-    if (!ctx->d_huff || !ctx->huffr_n || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
+    if (!ctx->d_huff || ctx->huff_kind != huff_kind_of(ntok) || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
         return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged Huffman stream");
     return tz_h2d(ctx, ctx->d_huff + offset, src, count, ctx->copy_stream);
 }
 
-static int huffr_decode_dev(tz_ctx* ctx, const uint8_t* d_stream, size_t stream_words, size_t n, const std::vector<uint16_t>& dec, int A,
-                            int base, int16_t* d_out) {
-    size_t nruns, nchunks, index_bytes;
-    huff_geometry(n, &nruns, &nchunks, &index_bytes);
-    void* d_dec;
-    TZ_TRY(tz_pool_alloc(ctx, dec.size() * 2, &d_dec));
-    TZ_TRY(tz_upload(ctx, d_dec, dec.data(), dec.size() * 2));
-    return tzk_huffr_dec(ctx, (const unsigned*)d_stream, (const uint16_t*)(d_stream + nchunks * 4), (const unsigned*)(d_stream + index_bytes),
-                         stream_words, (const uint16_t*)d_dec, A, base, n, d_out);
-}
-
-extern "C" int tz_huffr_decode(tz_ctx* ctx) {
-    tz_roctx_range roctx_("tz_huffr_decode");
+static int huff_decode(tz_ctx* ctx, int ntok, const char* who) {
     if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->huffr_n || !ctx->d_huff || !ctx->d_payload || ctx->cap_payload < ctx->huffr_n * 2)
-        return tz_fail(ctx, TZ_ERR_STATE, "tz_huffr_decode needs a stream staged with tz_huffr_begin / tz_huffr_put");
+    if (ctx->huff_kind != huff_kind_of(ntok) || !ctx->d_huff || !ctx->d_payload || ctx->cap_payload < ctx->huff_n * 2)
+        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode needs a stream staged with %s_begin / %s_put", who, who, who);
     size_t sw;
-    TZ_TRY(huff_check_stream(ctx, ctx->huff_bytes, ctx->huffr_n, TZ_HUFF_RUN, &sw));
-    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of tz_huffr_put
+    TZ_TRY(huff_check_stream(ctx, ctx->huff_bytes, ctx->huff_n, TZ_HUFF_RUN, &sw));
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of the puts
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
-    const int rc = huffr_decode_dev(ctx, ctx->d_huff, sw, ctx->huffr_n, ctx->huff_dec_tab, ctx->huffr_A, ctx->huff_base, ctx->d_payload);
-    if (rc == TZ_OK) ctx->payload_len = ctx->huffr_n;   // exactly as if tz_payload_begin / tz_payload_put had staged them
+    const int rc = huff_decode_dev(ctx, ctx->d_huff, sw, ctx->huff_n, ctx->huff_dec_tab, ctx->huff_A, ctx->huff_base, ntok, ctx->d_payload);
+    if (rc == TZ_OK) ctx->payload_len = ctx->huff_n;   // exactly as if tz_payload_begin / tz_payload_put had staged them
     tz_pool_release_all(ctx);
     return rc;
 }
 
-extern "C" int tz_huffr_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
-                                   size_t capacity, size_t* bytes) {
+static int huff_encode_buf(tz_ctx* ctx, int ntok, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
+                           size_t capacity, size_t* bytes) {
     if (!ctx || !in || !out || !bytes) return TZ_ERR_INVALID;
     const void* din = nullptr;
     int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
-    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes, true);
+    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes, ntok);
     if (rc == TZ_OK && *bytes > capacity) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: the stream needs %zu bytes, the buffer holds %zu", *bytes, capacity);
     if (rc == TZ_OK) {
         if (tz_is_device_ptr(out)) {
@@ -2638,22 +2492,22 @@ extern "C" int tz_huffr_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, con
     return rc;
 }
 
-extern "C" int tz_huffr_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
-                                   int16_t* out) {
-    if (!ctx || !stream || !out) return TZ_ERR_INVALID;
-    size_t sw;
-    TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
-    std::vector<uint16_t> dec;
-    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, TZ_HUFFR_NTOK));
+// The stand-alone forms that turn one host or device array into another: `in` is made a device array, `out` one to be copied
+// back if it is none, run(device in, device out) launches, the copy back and the stream are awaited, the pool is released.
+// A device array whose address has a bit of in_mask / out_mask set is refused with `misaligned`.
+template <class F>
+static int buf_op(tz_ctx* ctx, const void* in, size_t in_bytes, unsigned in_mask, void* out, size_t out_bytes, unsigned out_mask,
+                  const char* misaligned, F&& run) {
     const void* din = nullptr;
     tz_out o;
     std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, stream, bytes, &din);
-    if (rc == TZ_OK && ((uintptr_t)din & 3)) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: a device stream must be 4-byte aligned");
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
+    int rc = tz_dev_in(ctx, in, in_bytes, &din);
+    if (rc == TZ_OK && ((uintptr_t)din & in_mask)) rc = tz_fail(ctx, TZ_ERR_INVALID, "%s", misaligned);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, out_bytes, &o);
+    if (rc == TZ_OK && ((uintptr_t)o.dev & out_mask)) rc = tz_fail(ctx, TZ_ERR_INVALID, "%s", misaligned);
     if (rc == TZ_OK) {
         outs.push_back(o);
-        rc = huffr_decode_dev(ctx, (const uint8_t*)din, sw, n, dec, A, base, (int16_t*)o.dev);
+        rc = run(din, o.dev);
     }
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
@@ -2661,12 +2515,98 @@ extern "C" int tz_huffr_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t by
     return rc;
 }
 
+static int huff_decode_buf(tz_ctx* ctx, int ntok, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
+                           int16_t* out) {
+    if (!ctx || !stream || !out) return TZ_ERR_INVALID;
+    size_t sw;
+    TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
+    std::vector<uint16_t> dec;
+    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, ntok));
+    return buf_op(ctx, stream, bytes, 3, out, n * 2, 0, "huffman: a device stream must be 4-byte aligned", [&](const void* din, void* dout) {
+        return huff_decode_dev(ctx, (const uint8_t*)din, sw, n, dec, A, base, ntok, (int16_t*)dout);
+    });
+}
+
+extern "C" int tz_huff_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
+    tz_roctx_range roctx_("tz_huff_counts");
+    return huff_counts(ctx, 0, "tz_huff", counts, A, base);
+}
+
+extern "C" int tz_huff_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes) {
+    tz_roctx_range roctx_("tz_huff_encode");
+    return huff_encode(ctx, 0, "tz_huff", lengths, A, base, bytes);
+}
+
+extern "C" int tz_huff_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    if (!ctx->d_huff || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the resident Huffman stream");
+    TZ_TRY(tz_d2h(ctx, out, ctx->d_huff + offset, count, ctx->stream));
+    return tz_stream_sync(ctx);
+}
+
+extern "C" int tz_huff_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
+    return huff_begin(ctx, 0, bytes, n, lengths, A, base, R);
+}
+
+extern "C" int tz_huff_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) { return huff_put(ctx, 0, offset, count, src); }
+
+extern "C" int tz_huff_decode(tz_ctx* ctx) {
+    tz_roctx_range roctx_("tz_huff_decode");
+    return huff_decode(ctx, 0, "tz_huff");
+}
+
+extern "C" int tz_huff_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
+                                  size_t capacity, size_t* bytes) {
+    return huff_encode_buf(ctx, 0, in, n, lengths, A, base, out, capacity, bytes);
+}
+
+extern "C" int tz_huff_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
+                                  int16_t* out) {
+    return huff_decode_buf(ctx, 0, stream, bytes, n, lengths, A, base, R, out);
+}
+
+extern "C" int tz_huffr_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
+    tz_roctx_range roctx_("tz_huffr_counts");
+    return huff_counts(ctx, TZ_HUFFR_NTOK, "tz_huffr", counts, A, base);
+}
+
+extern "C" int tz_huffr_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes) {
+    tz_roctx_range roctx_("tz_huffr_encode");
+    return huff_encode(ctx, TZ_HUFFR_NTOK, "tz_huffr", lengths, A, base, bytes);
+}
+
+extern "C" int tz_huffr_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) { return tz_huff_get(ctx, offset, count, out); }
+
+extern "C" int tz_huffr_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
+    return huff_begin(ctx, TZ_HUFFR_NTOK, bytes, n, lengths, A, base, R);
+}
+
+extern "C" int tz_huffr_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
+    return huff_put(ctx, TZ_HUFFR_NTOK, offset, count, src);
+}
+
+extern "C" int tz_huffr_decode(tz_ctx* ctx) {
+    tz_roctx_range roctx_("tz_huffr_decode");
+    return huff_decode(ctx, TZ_HUFFR_NTOK, "tz_huffr");
+}
+
+extern "C" int tz_huffr_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
+                                   size_t capacity, size_t* bytes) {
+    return huff_encode_buf(ctx, TZ_HUFFR_NTOK, in, n, lengths, A, base, out, capacity, bytes);
+}
+
+extern "C" int tz_huffr_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
+                                   int16_t* out) {
+    return huff_decode_buf(ctx, TZ_HUFFR_NTOK, stream, bytes, n, lengths, A, base, R, out);
+}
+
 // the counts of a stand-alone host or device array, as tz_huffr_counts gives them for the resident payload
 extern "C" int tz_huffr_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* counts, int* A, int* base) {
     if (!ctx || !in || !counts || !A || !base) return TZ_ERR_INVALID;
     const void* din = nullptr;
     int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
-    if (rc == TZ_OK) rc = huffr_counts_dev(ctx, (const int16_t*)din, n, counts, A, base);
+    if (rc == TZ_OK) rc = huff_counts_dev(ctx, (const int16_t*)din, n, TZ_HUFFR_NTOK, "tz_huffr", counts, A, base);
     tz_pool_release_all(ctx);
     return rc;
 }
@@ -2675,6 +2615,9 @@ extern "C" int tz_huffr_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, uns
 // `--key-coder huff` (NOT a reference feature: compress.py:271-278 hands a zero-except-keys stack of the whole sequence to
 // zstd): the key frames alone, as predictor residuals under one TZH1 code (tezip_amd/keycoder.py, k_key_* in tz_codec.hip).
 // The coder has buffers of its own (d_keys, d_keysym): what tz_huff_* / tz_huffr_* hold or have staged is left alone.
+// `--key-coder huffg` (TZK2) is TZK1 with a GRAY bit per key frame (tezip_amd/keycoderg.py, k_key_gray / k_keyg_* in tz_codec.hip):
+// its stream, symbols and staged decoder's fields are the same, and ctx->keys_kind says which format's begin staged them, so
+// each put and decode refuses a body staged for the other format.
 static constexpr int TZ_KEYS_A = 256;
 
 // the key list of a stack of nt frames: at least one index, strictly ascending, inside [0, nt); predictor ids 0..3
@@ -2739,7 +2682,7 @@ static int keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pr
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
     TZ_TRY(keys_upload(ctx, idx, pred, nkeys, &d_idx, &d_pred));
     TZ_TRY(tzk_key_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, d_pred, nkeys, ctx->d_keysym));
-    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, false, true);
+    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);
 }
 
 extern "C" int tz_keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths, size_t* bytes) {
@@ -2760,43 +2703,6 @@ extern "C" int tz_keys_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* ou
     return tz_stream_sync(ctx);
 }
 
-extern "C" int tz_keys_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* pred,
-                             const uint8_t* lengths) {
-    if (!ctx || !pred) return TZ_ERR_INVALID;
-    if (nt < 1 || H < 1 || W < 1 || nt > kMaxFrames || H > 32767 || W > 32767)
-        return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d (int16 trailer limits)", nt, H, W);
-    TZ_TRY(keys_check(ctx, nt, idx, nkeys, pred));
-    const size_t n = (size_t)nkeys * H * W * 3;
-    size_t sw;
-    TZ_TRY(huff_check_stream(ctx, bytes, n, TZ_HUFF_RUN, &sw));
-    std::vector<uint16_t> dec;
-    TZ_TRY(huff_tables(ctx, lengths, TZ_KEYS_A, 0, nullptr, &dec));
-    ctx->keys_n = ctx->keysg_n = 0;
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, std::max<size_t>(bytes, 16)));
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, std::max<size_t>(n, 8) * 2));
-    ctx->keys_bytes = bytes;
-    ctx->keys_put = 0;
-    ctx->keys_nt = nt;
-    ctx->keys_H = H;
-    ctx->keys_W = W;
-    ctx->keys_idx.assign(idx, idx + nkeys);
-    ctx->keys_pred.assign(pred, pred + nkeys);
-    ctx->keys_dec_tab.swap(dec);
-    ctx->keys_n = n;
-    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
-    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
-    return TZ_OK;
-}
-
-extern "C" int tz_keys_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
-    if (!ctx || !src) return TZ_ERR_INVALID;
-    if (!ctx->d_keys || !ctx->keys_n || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
-        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged key-frame stream");
-    TZ_TRY(tz_h2d(ctx, ctx->d_keys + offset, src, count, ctx->copy_stream));
-    ctx->keys_put += count;
-    return TZ_OK;
-}
-
 // symbols (device) -> the frames idx[k] of a stack at d_frames; the other frames of the stack are not touched
 static int keys_unresidual(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* idx, const uint8_t* pred, int nkeys, uint8_t* d_frames) {
     const int* d_idx = nullptr;
@@ -2804,100 +2710,6 @@ static int keys_unresidual(tz_ctx* ctx, const int16_t* d_sym, int H, int W, cons
     TZ_TRY(keys_upload(ctx, idx, pred, nkeys, &d_idx, &d_pred));
     return tzk_key_unresid(ctx, d_sym, H, W, d_idx, d_pred, nkeys, d_frames);
 }
-
-static int keys_decode(tz_ctx* ctx) {
-    const int nt = ctx->keys_nt, H = ctx->keys_H, W = ctx->keys_W;
-    size_t sw;
-    TZ_TRY(huff_check_stream(ctx, ctx->keys_bytes, ctx->keys_n, TZ_HUFF_RUN, &sw));
-    // what tz_frames_begin does: the stack's buffer and shape; whatever rollout was resident is gone
-    set_rollout(ctx, tz_ctx::ROLLOUT_NONE, 0, 0);
-    ctx->staged = false;
-    const size_t fb = (size_t)nt * H * W * 3;
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_frames, &ctx->cap_frames, fb));
-    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of tz_keys_put (and older copies into d_frames)
-    TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
-    TZ_TRY(huff_decode_dev(ctx, ctx->d_keys, sw, ctx->keys_n, ctx->keys_dec_tab, 0, ctx->d_keysym));
-    TZ_HIP(ctx, hipMemsetAsync(ctx->d_frames, 0, fb, ctx->stream));   // the frames that are no key frames (a fresh buffer holds anything)
-    TZ_TRY(keys_unresidual(ctx, ctx->d_keysym, H, W, ctx->keys_idx.data(), ctx->keys_pred.data(), (int)ctx->keys_idx.size(), ctx->d_frames));
-    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));       // a later tz_frames_put waits for the frames written here
-    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
-    ctx->nt = nt;
-    ctx->H = H;
-    ctx->W = W;
-    ctx->staged = true;
-    return TZ_OK;
-}
-
-extern "C" int tz_keys_decode(tz_ctx* ctx) {
-    tz_roctx_range roctx_("tz_keys_decode");
-    if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->keys_n || !ctx->d_keys || !ctx->d_keysym)
-        return tz_fail(ctx, TZ_ERR_STATE, "tz_keys_decode needs a stream staged with tz_keys_begin / tz_keys_put");
-    if (ctx->keys_put != ctx->keys_bytes)
-        return tz_fail(ctx, TZ_ERR_STATE, "tz_keys_decode: %zu of the stream's %zu bytes were put", ctx->keys_put, ctx->keys_bytes);
-    const int rc = keys_decode(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
-}
-
-// stand-alone forms on host or device arrays: frames (k, H, W, 3) <-> k * H * W * 3 int16 symbols, pred[k] per frame
-static int keys_buf_check(tz_ctx* ctx, int k, int H, int W, const uint8_t* pred, std::vector<int>* idx) {
-    if (k < 1 || H < 1 || W < 1 || k > kMaxFrames || H > 32767 || W > 32767)
-        return tz_fail(ctx, TZ_ERR_INVALID, "bad key-frame stack k=%d H=%d W=%d", k, H, W);
-    idx->resize(k);
-    for (int i = 0; i < k; ++i) (*idx)[i] = i;
-    return keys_check(ctx, k, idx->data(), k, pred);
-}
-
-extern "C" int tz_keys_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* pred, int16_t* sym) {
-    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
-    std::vector<int> idx;
-    TZ_TRY(keys_buf_check(ctx, k, H, W, pred, &idx));
-    const size_t n = (size_t)k * H * W * 3;
-    const void* din = nullptr;
-    const int* d_idx = nullptr;
-    const uint8_t* d_pred = nullptr;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, frames, n, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, sym, n * 2, &o);
-    if (rc == TZ_OK && ((uintptr_t)o.dev & 1)) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames: a device symbol array must be 2-byte aligned");
-    if (rc == TZ_OK) rc = keys_upload(ctx, idx.data(), pred, k, &d_idx, &d_pred);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_key_resid(ctx, (const uint8_t*)din, H, W, d_idx, d_pred, k, (int16_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
-}
-
-extern "C" int tz_keys_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* pred, uint8_t* frames) {
-    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
-    std::vector<int> idx;
-    TZ_TRY(keys_buf_check(ctx, k, H, W, pred, &idx));
-    const size_t n = (size_t)k * H * W * 3;
-    const void* din = nullptr;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, sym, n * 2, &din);
-    if (rc == TZ_OK && ((uintptr_t)din & 1)) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames: a device symbol array must be 2-byte aligned");
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, frames, n, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = keys_unresidual(ctx, (const int16_t*)din, H, W, idx.data(), pred, k, (uint8_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
-}
-
-// --------------------------------------------------------------------------- key-frame coder, gray frames once (TZK2)
-// `--key-coder huffg`: TZK1 with a GRAY bit per key frame (tezip_amd/keycoderg.py, k_key_gray / k_keyg_* in tz_codec.hip).
-// The stream, the symbols and the staged decoder's fields are those of tz_keys_*; ctx->keysg_n instead of ctx->keys_n says
-// that what is staged is a TZK2 stream, so each decoder refuses a body staged for the other format.
 
 // pred bytes 0..7 -> off[k], the exclusive prefix of the frames' symbol counts, and their sum
 static int keysg_layout(tz_ctx* ctx, const uint8_t* predg, int nkeys, int H, int W, std::vector<unsigned long long>* off, size_t* n) {
@@ -2956,7 +2768,7 @@ static int keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* p
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
     TZ_TRY(keysg_upload(ctx, idx, predg, off, nkeys, &d_idx, &d_predg, &d_off));
     TZ_TRY(tzk_keyg_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, d_predg, d_off, nkeys, ctx->d_keysym));
-    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, false, true);
+    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);
 }
 
 extern "C" int tz_keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* predg, const uint8_t* lengths, size_t* bytes) {
@@ -2971,44 +2783,6 @@ extern "C" int tz_keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uin
 
 extern "C" int tz_keysg_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
     return tz_keys_get(ctx, offset, count, out);   // (an encoder's stream carries no format of its own: index | bits)
-}
-
-extern "C" int tz_keysg_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* predg,
-                              const uint8_t* lengths) {
-    if (!ctx || !predg) return TZ_ERR_INVALID;
-    if (nt < 1 || H < 1 || W < 1 || nt > kMaxFrames || H > 32767 || W > 32767)
-        return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d (int16 trailer limits)", nt, H, W);
-    TZ_TRY(keys_check(ctx, nt, idx, nkeys, nullptr));
-    std::vector<unsigned long long> off;
-    size_t n, sw;
-    TZ_TRY(keysg_layout(ctx, predg, nkeys, H, W, &off, &n));
-    TZ_TRY(huff_check_stream(ctx, bytes, n, TZ_HUFF_RUN, &sw));
-    std::vector<uint16_t> dec;
-    TZ_TRY(huff_tables(ctx, lengths, TZ_KEYS_A, 0, nullptr, &dec));
-    ctx->keys_n = ctx->keysg_n = 0;
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, std::max<size_t>(bytes, 16)));
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, std::max<size_t>(n, 8) * 2));
-    ctx->keys_bytes = bytes;
-    ctx->keys_put = 0;
-    ctx->keys_nt = nt;
-    ctx->keys_H = H;
-    ctx->keys_W = W;
-    ctx->keys_idx.assign(idx, idx + nkeys);
-    ctx->keys_pred.assign(predg, predg + nkeys);
-    ctx->keys_dec_tab.swap(dec);
-    ctx->keysg_n = n;
-    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
-    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
-    return TZ_OK;
-}
-
-extern "C" int tz_keysg_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
-    if (!ctx || !src) return TZ_ERR_INVALID;
-    if (!ctx->d_keys || !ctx->keysg_n || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
-        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged key-frame stream (TZK2)");
-    TZ_TRY(tz_h2d(ctx, ctx->d_keys + offset, src, count, ctx->copy_stream));
-    ctx->keys_put += count;
-    return TZ_OK;
 }
 
 // symbols (device) -> the frames idx[k] of a stack at d_frames; the other frames of the stack are not touched
@@ -3030,20 +2804,62 @@ static int keysg_unresidual(tz_ctx* ctx, const int16_t* d_sym, int H, int W, con
     return tzk_keyg_unresid(ctx, d_sym, H, W, d_idx, d_predg, (const uint8_t*)d_pred3, d_off, nkeys, (uint8_t*)d_tmp, d_frames);
 }
 
-static int keysg_decode(tz_ctx* ctx) {
+// One body for tz_keys_begin / tz_keysg_begin: the key list and the pred array are checked as the format says -- predictor
+// ids 0..3 (TZK1) or pred bytes 0..7, whose GRAY bits give the symbol count (TZK2) -- the rest is the same.
+static int keys_begin(tz_ctx* ctx, tz_ctx::tz_keys_kind kind, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* pred,
+                      const uint8_t* lengths) {
+    if (!ctx || !pred) return TZ_ERR_INVALID;
+    if (nt < 1 || H < 1 || W < 1 || nt > kMaxFrames || H > 32767 || W > 32767)
+        return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d (int16 trailer limits)", nt, H, W);
+    TZ_TRY(keys_check(ctx, nt, idx, nkeys, kind == tz_ctx::KEYS_TZK1 ? pred : nullptr));
+    std::vector<unsigned long long> off;
+    size_t n = (size_t)nkeys * H * W * 3, sw;
+    if (kind == tz_ctx::KEYS_TZK2) TZ_TRY(keysg_layout(ctx, pred, nkeys, H, W, &off, &n));
+    TZ_TRY(huff_check_stream(ctx, bytes, n, TZ_HUFF_RUN, &sw));
+    std::vector<uint16_t> dec;
+    TZ_TRY(huff_tables(ctx, lengths, TZ_KEYS_A, 0, nullptr, &dec));
+    ctx->keys_kind = tz_ctx::KEYS_NONE;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, std::max<size_t>(bytes, 16)));
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, std::max<size_t>(n, 8) * 2));
+    ctx->keys_bytes = bytes;
+    ctx->keys_put = 0;
+    ctx->keys_nt = nt;
+    ctx->keys_H = H;
+    ctx->keys_W = W;
+    ctx->keys_idx.assign(idx, idx + nkeys);
+    ctx->keys_pred.assign(pred, pred + nkeys);
+    ctx->keys_dec_tab.swap(dec);
+    ctx->keys_n = n;
+    ctx->keys_kind = kind;
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
+    TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
+    return TZ_OK;
+}
+
+static int keys_put(tz_ctx* ctx, tz_ctx::tz_keys_kind kind, size_t offset, size_t count, const uint8_t* src) {
+    if (!ctx || !src) return TZ_ERR_INVALID;
+    if (!ctx->d_keys || ctx->keys_kind != kind || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged key-frame stream%s", kind == tz_ctx::KEYS_TZK2 ? " (TZK2)" : "");
+    TZ_TRY(tz_h2d(ctx, ctx->d_keys + offset, src, count, ctx->copy_stream));
+    ctx->keys_put += count;
+    return TZ_OK;
+}
+
+static int keys_decode_dev(tz_ctx* ctx) {
     const int nt = ctx->keys_nt, H = ctx->keys_H, W = ctx->keys_W;
     size_t sw;
-    TZ_TRY(huff_check_stream(ctx, ctx->keys_bytes, ctx->keysg_n, TZ_HUFF_RUN, &sw));
+    TZ_TRY(huff_check_stream(ctx, ctx->keys_bytes, ctx->keys_n, TZ_HUFF_RUN, &sw));
     // what tz_frames_begin does: the stack's buffer and shape; whatever rollout was resident is gone
     set_rollout(ctx, tz_ctx::ROLLOUT_NONE, 0, 0);
     ctx->staged = false;
     const size_t fb = (size_t)nt * H * W * 3;
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_frames, &ctx->cap_frames, fb));
-    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of tz_keysg_put (and older copies into d_frames)
+    TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of the puts (and older copies into d_frames)
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
-    TZ_TRY(huff_decode_dev(ctx, ctx->d_keys, sw, ctx->keysg_n, ctx->keys_dec_tab, 0, ctx->d_keysym));
+    TZ_TRY(huff_decode_dev(ctx, ctx->d_keys, sw, ctx->keys_n, ctx->keys_dec_tab, TZ_KEYS_A, 0, 0, ctx->d_keysym));
     TZ_HIP(ctx, hipMemsetAsync(ctx->d_frames, 0, fb, ctx->stream));   // the frames that are no key frames (a fresh buffer holds anything)
-    TZ_TRY(keysg_unresidual(ctx, ctx->d_keysym, H, W, ctx->keys_idx.data(), ctx->keys_pred.data(), (int)ctx->keys_idx.size(), ctx->d_frames));
+    TZ_TRY((ctx->keys_kind == tz_ctx::KEYS_TZK2 ? keysg_unresidual : keys_unresidual)(ctx, ctx->d_keysym, H, W, ctx->keys_idx.data(),
+                                                                                    ctx->keys_pred.data(), (int)ctx->keys_idx.size(), ctx->d_frames));
     TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));       // a later tz_frames_put waits for the frames written here
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
     ctx->nt = nt;
@@ -3053,20 +2869,50 @@ static int keysg_decode(tz_ctx* ctx) {
     return TZ_OK;
 }
 
-extern "C" int tz_keysg_decode(tz_ctx* ctx) {
-    tz_roctx_range roctx_("tz_keysg_decode");
+static int keys_decode(tz_ctx* ctx, tz_ctx::tz_keys_kind kind, const char* who) {
     if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->keysg_n || !ctx->d_keys || !ctx->d_keysym)
-        return tz_fail(ctx, TZ_ERR_STATE, "tz_keysg_decode needs a stream staged with tz_keysg_begin / tz_keysg_put");
+    if (ctx->keys_kind != kind || !ctx->d_keys || !ctx->d_keysym)
+        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode needs a stream staged with %s_begin / %s_put", who, who, who);
     if (ctx->keys_put != ctx->keys_bytes)
-        return tz_fail(ctx, TZ_ERR_STATE, "tz_keysg_decode: %zu of the stream's %zu bytes were put", ctx->keys_put, ctx->keys_bytes);
-    const int rc = keysg_decode(ctx);
+        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode: %zu of the stream's %zu bytes were put", who, ctx->keys_put, ctx->keys_bytes);
+    const int rc = keys_decode_dev(ctx);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-// stand-alone forms on host or device arrays: frames (k, H, W, 3) <-> the symbols keysg_layout counts, predg[k] per frame
-static int keysg_buf_check(tz_ctx* ctx, int k, int H, int W, std::vector<int>* idx) {
+extern "C" int tz_keys_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* pred,
+                             const uint8_t* lengths) {
+    return keys_begin(ctx, tz_ctx::KEYS_TZK1, bytes, nt, H, W, idx, nkeys, pred, lengths);
+}
+
+extern "C" int tz_keys_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
+    return keys_put(ctx, tz_ctx::KEYS_TZK1, offset, count, src);
+}
+
+extern "C" int tz_keys_decode(tz_ctx* ctx) {
+    tz_roctx_range roctx_("tz_keys_decode");
+    return keys_decode(ctx, tz_ctx::KEYS_TZK1, "tz_keys");
+}
+
+extern "C" int tz_keysg_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* predg,
+                              const uint8_t* lengths) {
+    return keys_begin(ctx, tz_ctx::KEYS_TZK2, bytes, nt, H, W, idx, nkeys, predg, lengths);
+}
+
+extern "C" int tz_keysg_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
+    return keys_put(ctx, tz_ctx::KEYS_TZK2, offset, count, src);
+}
+
+extern "C" int tz_keysg_decode(tz_ctx* ctx) {
+    tz_roctx_range roctx_("tz_keysg_decode");
+    return keys_decode(ctx, tz_ctx::KEYS_TZK2, "tz_keysg");
+}
+
+// stand-alone forms on host or device arrays: frames (k, H, W, 3) <-> int16 symbols, k * H * W * 3 of them under pred[k] per
+// frame (TZK1), or those keysg_layout counts under predg[k] (TZK2)
+static const char* const kKeySymAlign = "key frames: a device symbol array must be 2-byte aligned";
+
+static int keys_buf_check(tz_ctx* ctx, int k, int H, int W, std::vector<int>* idx) {
     if (k < 1 || H < 1 || W < 1 || k > kMaxFrames || H > 32767 || W > 32767)
         return tz_fail(ctx, TZ_ERR_INVALID, "bad key-frame stack k=%d H=%d W=%d", k, H, W);
     idx->resize(k);
@@ -3074,31 +2920,45 @@ static int keysg_buf_check(tz_ctx* ctx, int k, int H, int W, std::vector<int>* i
     return TZ_OK;
 }
 
+extern "C" int tz_keys_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* pred, int16_t* sym) {
+    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
+    std::vector<int> idx;
+    TZ_TRY(keys_buf_check(ctx, k, H, W, &idx));
+    TZ_TRY(keys_check(ctx, k, idx.data(), k, pred));
+    const size_t n = (size_t)k * H * W * 3;
+    return buf_op(ctx, frames, n, 0, sym, n * 2, 1, kKeySymAlign, [&](const void* din, void* dout) {
+        const int* d_idx = nullptr;
+        const uint8_t* d_pred = nullptr;
+        TZ_TRY(keys_upload(ctx, idx.data(), pred, k, &d_idx, &d_pred));
+        return tzk_key_resid(ctx, (const uint8_t*)din, H, W, d_idx, d_pred, k, (int16_t*)dout);
+    });
+}
+
+extern "C" int tz_keys_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* pred, uint8_t* frames) {
+    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
+    std::vector<int> idx;
+    TZ_TRY(keys_buf_check(ctx, k, H, W, &idx));
+    TZ_TRY(keys_check(ctx, k, idx.data(), k, pred));
+    const size_t n = (size_t)k * H * W * 3;
+    return buf_op(ctx, sym, n * 2, 1, frames, n, 0, kKeySymAlign, [&](const void* din, void* dout) {
+        return keys_unresidual(ctx, (const int16_t*)din, H, W, idx.data(), pred, k, (uint8_t*)dout);
+    });
+}
+
 extern "C" int tz_keysg_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* predg, int16_t* sym) {
     if (!ctx || !frames || !predg || !sym) return TZ_ERR_INVALID;
     std::vector<int> idx;
     std::vector<unsigned long long> off;
     size_t n;
-    TZ_TRY(keysg_buf_check(ctx, k, H, W, &idx));
+    TZ_TRY(keys_buf_check(ctx, k, H, W, &idx));
     TZ_TRY(keysg_layout(ctx, predg, k, H, W, &off, &n));
-    const void* din = nullptr;
-    const int* d_idx = nullptr;
-    const uint8_t* d_predg = nullptr;
-    const unsigned long long* d_off = nullptr;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, frames, (size_t)k * H * W * 3, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, sym, n * 2, &o);
-    if (rc == TZ_OK && ((uintptr_t)o.dev & 1)) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames: a device symbol array must be 2-byte aligned");
-    if (rc == TZ_OK) rc = keysg_upload(ctx, idx.data(), predg, off, k, &d_idx, &d_predg, &d_off);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_keyg_resid(ctx, (const uint8_t*)din, H, W, d_idx, d_predg, d_off, k, (int16_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
+    return buf_op(ctx, frames, (size_t)k * H * W * 3, 0, sym, n * 2, 1, kKeySymAlign, [&](const void* din, void* dout) {
+        const int* d_idx = nullptr;
+        const uint8_t* d_predg = nullptr;
+        const unsigned long long* d_off = nullptr;
+        TZ_TRY(keysg_upload(ctx, idx.data(), predg, off, k, &d_idx, &d_predg, &d_off));
+        return tzk_keyg_resid(ctx, (const uint8_t*)din, H, W, d_idx, d_predg, d_off, k, (int16_t*)dout);
+    });
 }
 
 extern "C" int tz_keysg_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* predg, uint8_t* frames) {
@@ -3106,20 +2966,9 @@ extern "C" int tz_keysg_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, i
     std::vector<int> idx;
     std::vector<unsigned long long> off;
     size_t n;
-    TZ_TRY(keysg_buf_check(ctx, k, H, W, &idx));
+    TZ_TRY(keys_buf_check(ctx, k, H, W, &idx));
     TZ_TRY(keysg_layout(ctx, predg, k, H, W, &off, &n));
-    const void* din = nullptr;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, sym, n * 2, &din);
-    if (rc == TZ_OK && ((uintptr_t)din & 1)) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames: a device symbol array must be 2-byte aligned");
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, frames, (size_t)k * H * W * 3, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = keysg_unresidual(ctx, (const int16_t*)din, H, W, idx.data(), predg, k, (uint8_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
+    return buf_op(ctx, sym, n * 2, 1, frames, (size_t)k * H * W * 3, 0, kKeySymAlign, [&](const void* din, void* dout) {
+        return keysg_unresidual(ctx, (const int16_t*)din, H, W, idx.data(), predg, k, (uint8_t*)dout);
+    });
 }

@@ -2670,6 +2670,96 @@ __device__ __forceinline__ unsigned hf_wave_excl(unsigned v, unsigned* total) {
     return inc - v;
 }
 
+// What the pack kernels (k_huff_enc, k_huffr_enc) share.  hf_enc_begin: the code table `enc` of nsym entries into tab[PAD],
+// the bit offset of this lane's run inside the chunk (returned) and the chunk's size in words *cw, clamped to the image,
+// whose first *cw words are cleared.  Ends with a barrier.
+template <int PAD>
+__device__ __forceinline__ unsigned hf_enc_begin(uint16_t* tab, unsigned* img, const uint16_t* __restrict__ enc, int nsym, size_t run, size_t nruns,
+                                                 const uint16_t* __restrict__ run_bits, unsigned* cw) {
+    const int lane = threadIdx.x;
+    for (int k = lane; k < PAD; k += 64) tab[k] = k < nsym ? enc[k] : (uint16_t)0;
+    unsigned tot;
+    const unsigned pos = hf_wave_excl(run < nruns ? (unsigned)run_bits[run] : 0u, &tot);
+    *cw = std::min((tot + 31u) >> 5, (unsigned)HF_CHUNK_WORDS);
+    for (unsigned k = lane; k < *cw; k += 64) img[k] = 0;
+    __syncthreads();
+    return pos;
+}
+
+// a full word of the accumulator leaves for the image (the first and the last word of a run are shared with the
+// neighbouring lanes: ds_or, no return value)
+__device__ __forceinline__ void hf_flush(unsigned long long& acc, unsigned& nb, unsigned& wi, unsigned cw, unsigned* img) {
+    if (nb >= 32) {
+        if (wi < cw) atomicOr(&img[wi], (unsigned)acc);
+        ++wi;
+        acc >>= 32;
+        nb -= 32;
+    }
+}
+
+// the last, partial word of the run, then the image leaves with coalesced stores, clamped to the stream
+__device__ __forceinline__ void hf_enc_end(unsigned long long acc, unsigned nb, unsigned wi, unsigned cw, unsigned* img,
+                                           const unsigned* __restrict__ chunk_off, size_t chunk, unsigned* __restrict__ words, size_t stream_words) {
+    if (nb > 0 && wi < cw) atomicOr(&img[wi], (unsigned)acc);
+    __syncthreads();
+    const size_t w0 = chunk_off[chunk];
+    for (unsigned k = threadIdx.x; k < cw; k += 64)
+        if (w0 + k < stream_words) words[w0 + k] = img[k];
+}
+
+// What the expand kernels (k_huff_dec, k_huffr_dec) share, and with it every clamp that makes a corrupt body harmless.
+// hf_dec_begin: the decode table into tab, the chunk's words into img -- chunk offsets clamped to the stream, the staged
+// words to the image, a zero word behind them at img[*cw] -- and this lane's bit offset from the run sizes, each clamped to
+// R * L (returned).  Ends with a barrier.
+__device__ __forceinline__ unsigned hf_dec_begin(uint16_t* tab, unsigned* img, const uint16_t* __restrict__ dec, const unsigned* __restrict__ chunk_off,
+                                                 const uint16_t* __restrict__ run_bits, const unsigned* __restrict__ words, size_t stream_words,
+                                                 size_t nruns, size_t nchunks, size_t chunk, size_t run, unsigned* cw_out) {
+    const int lane = threadIdx.x;
+    for (int k = lane; k < (1 << HF_L) / 8; k += 64) ((uint4*)tab)[k] = ((const uint4*)dec)[k];
+    const size_t w0 = std::min((size_t)chunk_off[chunk], stream_words);
+    const size_t w1 = chunk + 1 < nchunks ? std::min((size_t)chunk_off[chunk + 1], stream_words) : stream_words;
+    const unsigned cw = w1 > w0 ? (unsigned)std::min(w1 - w0, (size_t)HF_CHUNK_WORDS) : 0u;
+    for (unsigned k = lane; k < cw; k += 64) img[k] = words[w0 + k];
+    if (lane == 0) img[cw] = 0;
+    unsigned tot;
+    const unsigned pos = hf_wave_excl(run < nruns ? std::min((unsigned)run_bits[run], (unsigned)(HF_R * HF_L)) : 0u, &tot);
+    __syncthreads();
+    *cw_out = cw;
+    return pos;
+}
+
+// the first two words of the run that starts at bit `pos` of the image: nb valid bits in acc, more than 32; wi: the next word
+__device__ __forceinline__ void hf_dec_first(const unsigned* img, unsigned pos, unsigned cw, unsigned long long& acc, unsigned& nb, unsigned& wi) {
+    wi = pos >> 5;
+    acc = (unsigned long long)img[std::min(wi, cw)] >> (pos & 31u);
+    nb = 32u - (pos & 31u);
+    ++wi;
+    acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
+    nb += 32;
+    ++wi;
+}
+
+// the next word of the image joins the accumulator once 32 bits or fewer are left; reads are clamped to the zero word
+__device__ __forceinline__ void hf_refill(unsigned long long& acc, unsigned& nb, unsigned& wi, unsigned cw, const unsigned* img) {
+    if (nb <= 32) {
+        acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
+        nb += 32;
+        ++wi;
+    }
+}
+
+// elements j .. j + 7 of the run at r0 leave (those in front of cnt); VEC: out + r0 is 16-byte aligned
+template <bool VEC>
+__device__ __forceinline__ void hf_store8(int16_t* __restrict__ out, size_t r0, int j, int cnt, short8 v) {
+    if (VEC && j + 8 <= cnt) {
+        *(short8*)(out + r0 + j) = v;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (j + k < cnt) out[r0 + j + k] = v[k];
+    }
+}
+
 // Counts of the payload values (bin = value + TZ_HUFF_COUNT_BIAS; anything outside the 4096 bins sets meta->bad): the
 // histogram a payload has when no earlier pass left one (a payload without a rank table, a tz_encode_finish).  One read
 // of the payload, 2 B/element; equal neighbours are merged in the thread before they reach the LDS counters.
@@ -2783,26 +2873,6 @@ __global__ __launch_bounds__(1024) void k_huff_scan(const unsigned* __restrict__
     if (threadIdx.x == 1023) meta->total_words = part[1023];
 }
 
-int tzk_huff_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
-                  unsigned* d_chunk_off, tz_huff_meta* d_meta) {
-    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
-    void* d_cbits;
-    TZ_TRY(tz_pool_alloc(ctx, nchunks * sizeof(unsigned), &d_cbits));
-    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
-    tz_prof_scope ps(ctx, TZP_HUFF);
-    const dim3 grid((unsigned)((nchunks + 3) / 4));
-    if ((uintptr_t)in & 15)
-        hipLaunchKernelGGL(k_huff_size<false>, grid, dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
-                           (unsigned*)d_cbits, d_meta);
-    else
-        hipLaunchKernelGGL(k_huff_size<true>, grid, dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
-                           (unsigned*)d_cbits, d_meta);
-    TZ_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_huff_scan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)d_cbits, nchunks, d_chunk_off, d_meta);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
-}
-
 // Pack pass: one wave (= one workgroup) per chunk.  Every lane packs its run into a 64-bit accumulator and ORs whole
 // 32-bit words into the chunk's image in LDS (the first and the last word of a run are shared with the neighbouring
 // lanes: ds_or, no return value); the image then leaves with coalesced stores.  No global atomics.
@@ -2812,14 +2882,9 @@ __global__ __launch_bounds__(64) void k_huff_enc(const int16_t* __restrict__ in,
                                                  unsigned* __restrict__ words, size_t stream_words) {
     __shared__ uint16_t tab[HF_ENC_PAD];
     __shared__ unsigned img[HF_CHUNK_WORDS];
-    const int lane = threadIdx.x;
-    const size_t chunk = blockIdx.x, run = chunk * HF_CR + lane;
-    for (int k = lane; k < HF_ENC_PAD; k += 64) tab[k] = k < A ? enc[k] : (uint16_t)0;
-    unsigned tot;
-    const unsigned pos = hf_wave_excl(run < nruns ? (unsigned)run_bits[run] : 0u, &tot);
-    const unsigned cw = std::min((tot + 31u) >> 5, (unsigned)HF_CHUNK_WORDS);
-    for (unsigned k = lane; k < cw; k += 64) img[k] = 0;
-    __syncthreads();
+    const size_t chunk = blockIdx.x, run = chunk * HF_CR + threadIdx.x;
+    unsigned cw;
+    const unsigned pos = hf_enc_begin<HF_ENC_PAD>(tab, img, enc, A, run, nruns, run_bits, &cw);
     const size_t r0 = run * HF_R;
     const int cnt = r0 < n ? (int)std::min((size_t)HF_R, n - r0) : 0;
     unsigned long long acc = 0;
@@ -2832,33 +2897,10 @@ __global__ __launch_bounds__(64) void k_huff_enc(const int16_t* __restrict__ in,
             const unsigned e = (sym < (unsigned)A && j + k < cnt) ? tab[sym] : 0u;   // (no code: nothing is written; k_huff_size said so)
             acc |= (unsigned long long)(e & 0xFFFu) << nb;
             nb += e >> 12;
-            if (nb >= 32) {
-                if (wi < cw) atomicOr(&img[wi], (unsigned)acc);
-                ++wi;
-                acc >>= 32;
-                nb -= 32;
-            }
+            hf_flush(acc, nb, wi, cw, img);
         }
     }
-    if (nb > 0 && wi < cw) atomicOr(&img[wi], (unsigned)acc);
-    __syncthreads();
-    const size_t w0 = chunk_off[chunk];
-    for (unsigned k = lane; k < cw; k += 64)
-        if (w0 + k < stream_words) words[w0 + k] = img[k];
-}
-
-int tzk_huff_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
-                 const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words) {
-    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
-    tz_prof_scope ps(ctx, TZP_HUFF);
-    if ((uintptr_t)in & 15)
-        hipLaunchKernelGGL(k_huff_enc<false>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits,
-                           d_chunk_off, d_words, stream_words);
-    else
-        hipLaunchKernelGGL(k_huff_enc<true>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits,
-                           d_chunk_off, d_words, stream_words);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
+    hf_enc_end(acc, nb, wi, cw, img, chunk_off, chunk, words, stream_words);
 }
 
 // Expand pass: one wave (= one workgroup) per chunk.  The chunk's words are staged in LDS behind the decode table; every
@@ -2874,26 +2916,13 @@ __global__ __launch_bounds__(64) void k_huff_dec(const unsigned* __restrict__ ch
                                                  const uint16_t* __restrict__ dec, int base, size_t n, int16_t* __restrict__ out) {
     __shared__ uint16_t tab[1 << HF_L];
     __shared__ unsigned img[HF_CHUNK_WORDS + 1];
-    const int lane = threadIdx.x;
-    const size_t chunk = blockIdx.x, run = chunk * HF_CR + lane;
-    for (int k = lane; k < (1 << HF_L) / 8; k += 64) ((uint4*)tab)[k] = ((const uint4*)dec)[k];
-    const size_t w0 = std::min((size_t)chunk_off[chunk], stream_words);
-    const size_t w1 = chunk + 1 < nchunks ? std::min((size_t)chunk_off[chunk + 1], stream_words) : stream_words;
-    const unsigned cw = w1 > w0 ? (unsigned)std::min(w1 - w0, (size_t)HF_CHUNK_WORDS) : 0u;
-    for (unsigned k = lane; k < cw; k += 64) img[k] = words[w0 + k];
-    if (lane == 0) img[cw] = 0;
-    unsigned tot;
-    const unsigned pos = hf_wave_excl(run < nruns ? std::min((unsigned)run_bits[run], (unsigned)(HF_R * HF_L)) : 0u, &tot);
-    __syncthreads();
+    const size_t chunk = blockIdx.x, run = chunk * HF_CR + threadIdx.x;
+    unsigned cw, nb, wi;
+    unsigned long long acc;
+    const unsigned pos = hf_dec_begin(tab, img, dec, chunk_off, run_bits, words, stream_words, nruns, nchunks, chunk, run, &cw);
     const size_t r0 = run * HF_R;
     const int cnt = r0 < n ? (int)std::min((size_t)HF_R, n - r0) : 0;
-    unsigned wi = pos >> 5;
-    unsigned long long acc = (unsigned long long)img[std::min(wi, cw)] >> (pos & 31u);
-    unsigned nb = 32u - (pos & 31u);
-    ++wi;
-    acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
-    nb += 32;
-    ++wi;
+    hf_dec_first(img, pos, cw, acc, nb, wi);
     for (int j = 0; j < cnt; j += 8) {
         short8 v;
 #pragma unroll
@@ -2903,34 +2932,10 @@ __global__ __launch_bounds__(64) void k_huff_dec(const unsigned* __restrict__ ch
             v[k] = (short)((int)(e & 0xFFFu) + base);
             acc >>= l;
             nb -= l;
-            if (nb <= 32) {
-                acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
-                nb += 32;
-                ++wi;
-            }
+            hf_refill(acc, nb, wi, cw, img);
         }
-        if (VEC && j + 8 <= cnt) {
-            *(short8*)(out + r0 + j) = v;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (j + k < cnt) out[r0 + j + k] = v[k];
-        }
+        hf_store8<VEC>(out, r0, j, cnt, v);
     }
-}
-
-int tzk_huff_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
-                 const uint16_t* d_dec, int base, size_t n, int16_t* out) {
-    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
-    tz_prof_scope ps(ctx, TZP_HUFF);
-    if ((uintptr_t)out & 15)
-        hipLaunchKernelGGL(k_huff_dec<false>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words,
-                           nruns, nchunks, d_dec, base, n, out);
-    else
-        hipLaunchKernelGGL(k_huff_dec<true>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words,
-                           nruns, nchunks, d_dec, base, n, out);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
 }
 
 // ---------------------------------------------------------------------------- Huffman coder with repeat tokens
@@ -3043,26 +3048,6 @@ __global__ __launch_bounds__(256) void k_huffr_size(const int16_t* __restrict__ 
     if (bad) atomicOr(&meta->bad, 1u);
 }
 
-int tzk_huffr_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
-                   unsigned* d_chunk_off, tz_huff_meta* d_meta) {
-    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
-    void* d_cbits;
-    TZ_TRY(tz_pool_alloc(ctx, nchunks * sizeof(unsigned), &d_cbits));
-    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
-    tz_prof_scope ps(ctx, TZP_HUFF);
-    const dim3 grid((unsigned)((nchunks + 3) / 4));
-    if ((uintptr_t)in & 15)
-        hipLaunchKernelGGL(k_huffr_size<false>, grid, dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
-                           (unsigned*)d_cbits, d_meta);
-    else
-        hipLaunchKernelGGL(k_huffr_size<true>, grid, dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
-                           (unsigned*)d_cbits, d_meta);
-    TZ_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_huff_scan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)d_cbits, nchunks, d_chunk_off, d_meta);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
-}
-
 // Pack pass: k_huff_enc's scheme (one wave per chunk, 64-bit accumulator per lane, whole words ORed into the chunk's image
 // in LDS, coalesced stores of the image, no global atomics) over the tokens of hfr_walk.  A step appends at most a token
 // with its raw bits and a literal: 12 + 7 + 12 bits on top of fewer than 32, so the accumulator holds them.
@@ -3072,14 +3057,9 @@ __global__ __launch_bounds__(64) void k_huffr_enc(const int16_t* __restrict__ in
                                                   unsigned* __restrict__ words, size_t stream_words) {
     __shared__ uint16_t tab[HFR_ENC_PAD];
     __shared__ unsigned img[HF_CHUNK_WORDS];
-    const int lane = threadIdx.x;
-    const size_t chunk = blockIdx.x, run = chunk * HF_CR + lane;
-    for (int k = lane; k < HFR_ENC_PAD; k += 64) tab[k] = k < A + HFR_NTOK ? enc[k] : (uint16_t)0;
-    unsigned tot;
-    const unsigned pos = hf_wave_excl(run < nruns ? (unsigned)run_bits[run] : 0u, &tot);
-    const unsigned cw = std::min((tot + 31u) >> 5, (unsigned)HF_CHUNK_WORDS);
-    for (unsigned k = lane; k < cw; k += 64) img[k] = 0;
-    __syncthreads();
+    const size_t chunk = blockIdx.x, run = chunk * HF_CR + threadIdx.x;
+    unsigned cw;
+    const unsigned pos = hf_enc_begin<HFR_ENC_PAD>(tab, img, enc, A + HFR_NTOK, run, nruns, run_bits, &cw);
     const size_t r0 = run * HF_R;
     const int cnt = r0 < n ? (int)std::min((size_t)HF_R, n - r0) : 0;
     unsigned long long acc = 0;
@@ -3097,32 +3077,9 @@ __global__ __launch_bounds__(64) void k_huffr_enc(const int16_t* __restrict__ in
             acc |= (unsigned long long)(e & 0xFFFu) << nb;
             nb += e >> 12;
         }
-        if (nb >= 32) {
-            if (wi < cw) atomicOr(&img[wi], (unsigned)acc);
-            ++wi;
-            acc >>= 32;
-            nb -= 32;
-        }
+        hf_flush(acc, nb, wi, cw, img);
     });
-    if (nb > 0 && wi < cw) atomicOr(&img[wi], (unsigned)acc);
-    __syncthreads();
-    const size_t w0 = chunk_off[chunk];
-    for (unsigned k = lane; k < cw; k += 64)
-        if (w0 + k < stream_words) words[w0 + k] = img[k];
-}
-
-int tzk_huffr_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
-                  const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words) {
-    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
-    tz_prof_scope ps(ctx, TZP_HUFF);
-    if ((uintptr_t)in & 15)
-        hipLaunchKernelGGL(k_huffr_enc<false>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits,
-                           d_chunk_off, d_words, stream_words);
-    else
-        hipLaunchKernelGGL(k_huffr_enc<true>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits,
-                           d_chunk_off, d_words, stream_words);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
+    hf_enc_end(acc, nb, wi, cw, img, chunk_off, chunk, words, stream_words);
 }
 
 // Expand pass: k_huff_dec's scheme and clamps (chunk offsets to the stream, staged words to the image, reads of the image
@@ -3138,26 +3095,13 @@ __global__ __launch_bounds__(64) void k_huffr_dec(const unsigned* __restrict__ c
                                                   const uint16_t* __restrict__ dec, int A, int base, size_t n, int16_t* __restrict__ out) {
     __shared__ uint16_t tab[1 << HF_L];
     __shared__ unsigned img[HF_CHUNK_WORDS + 1];
-    const int lane = threadIdx.x;
-    const size_t chunk = blockIdx.x, run = chunk * HF_CR + lane;
-    for (int k = lane; k < (1 << HF_L) / 8; k += 64) ((uint4*)tab)[k] = ((const uint4*)dec)[k];
-    const size_t w0 = std::min((size_t)chunk_off[chunk], stream_words);
-    const size_t w1 = chunk + 1 < nchunks ? std::min((size_t)chunk_off[chunk + 1], stream_words) : stream_words;
-    const unsigned cw = w1 > w0 ? (unsigned)std::min(w1 - w0, (size_t)HF_CHUNK_WORDS) : 0u;
-    for (unsigned k = lane; k < cw; k += 64) img[k] = words[w0 + k];
-    if (lane == 0) img[cw] = 0;
-    unsigned tot;
-    const unsigned pos = hf_wave_excl(run < nruns ? std::min((unsigned)run_bits[run], (unsigned)(HF_R * HF_L)) : 0u, &tot);
-    __syncthreads();
+    const size_t chunk = blockIdx.x, run = chunk * HF_CR + threadIdx.x;
+    unsigned cw, nb, wi;
+    unsigned long long acc;
+    const unsigned pos = hf_dec_begin(tab, img, dec, chunk_off, run_bits, words, stream_words, nruns, nchunks, chunk, run, &cw);
     const size_t r0 = run * HF_R;
     const int cnt = r0 < n ? (int)std::min((size_t)HF_R, n - r0) : 0;
-    unsigned wi = pos >> 5;
-    unsigned long long acc = (unsigned long long)img[std::min(wi, cw)] >> (pos & 31u);
-    unsigned nb = 32u - (pos & 31u);
-    ++wi;
-    acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
-    nb += 32;
-    ++wi;
+    hf_dec_first(img, pos, cw, acc, nb, wi);
     int h1 = base, h2 = base, h3 = base;
     unsigned m = 0;
     for (int j = 0; j < cnt; j += 8) {
@@ -3179,11 +3123,7 @@ __global__ __launch_bounds__(64) void k_huffr_dec(const unsigned* __restrict__ c
                     acc >>= tk;
                     nb -= tk;
                 }
-                if (nb <= 32) {
-                    acc |= (unsigned long long)img[std::min(wi, cw)] << nb;
-                    nb += 32;
-                    ++wi;
-                }
+                hf_refill(acc, nb, wi, cw, img);
             }
             --m;
             v[k] = (short)val;
@@ -3191,26 +3131,53 @@ __global__ __launch_bounds__(64) void k_huffr_dec(const unsigned* __restrict__ c
             h2 = h1;
             h1 = val;
         }
-        if (VEC && j + 8 <= cnt) {
-            *(short8*)(out + r0 + j) = v;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (j + k < cnt) out[r0 + j + k] = v[k];
-        }
+        hf_store8<VEC>(out, r0, j, cnt, v);
     }
 }
 
-int tzk_huffr_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
-                  const uint16_t* d_dec, int A, int base, size_t n, int16_t* out) {
+// The launchers of the size, pack and expand passes of both coders: ntok == 0 runs the k_huff_* kernels, ntok ==
+// TZ_HUFFR_NTOK the k_huffr_* ones (d_enc then holds A + ntok entries); VEC says that the payload is 16-byte aligned.
+int tzk_huff_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, uint16_t* d_run_bits,
+                  unsigned* d_chunk_off, tz_huff_meta* d_meta) {
+    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
+    void* d_cbits;
+    TZ_TRY(tz_pool_alloc(ctx, nchunks * sizeof(unsigned), &d_cbits));
+    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    const bool vec = !((uintptr_t)in & 15);
+    const auto k = ntok ? (vec ? k_huffr_size<true> : k_huffr_size<false>) : (vec ? k_huff_size<true> : k_huff_size<false>);
+    hipLaunchKernelGGL(k, dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
+                       (unsigned*)d_cbits, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_huff_scan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)d_cbits, nchunks, d_chunk_off, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+int tzk_huff_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, const uint16_t* d_run_bits,
+                 const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words) {
     const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
     tz_prof_scope ps(ctx, TZP_HUFF);
-    if ((uintptr_t)out & 15)
-        hipLaunchKernelGGL(k_huffr_dec<false>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words,
-                           nruns, nchunks, d_dec, A, base, n, out);
+    const bool vec = !((uintptr_t)in & 15);
+    const auto k = ntok ? (vec ? k_huffr_enc<true> : k_huffr_enc<false>) : (vec ? k_huff_enc<true> : k_huff_enc<false>);
+    hipLaunchKernelGGL(k, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits, d_chunk_off, d_words,
+                       stream_words);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+int tzk_huff_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
+                 const uint16_t* d_dec, int A, int base, int ntok, size_t n, int16_t* out) {
+    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    const bool vec = !((uintptr_t)out & 15);
+    const dim3 grid((unsigned)nchunks);
+    if (ntok)   // (the literal count A tells k_huffr_dec the tokens from the literals; k_huff_dec has no use for it)
+        hipLaunchKernelGGL(vec ? k_huffr_dec<true> : k_huffr_dec<false>, grid, dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words,
+                           stream_words, nruns, nchunks, d_dec, A, base, n, out);
     else
-        hipLaunchKernelGGL(k_huffr_dec<true>, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words,
-                           nruns, nchunks, d_dec, A, base, n, out);
+        hipLaunchKernelGGL(vec ? k_huff_dec<true> : k_huff_dec<false>, grid, dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words,
+                           stream_words, nruns, nchunks, d_dec, base, n, out);
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }

@@ -131,27 +131,25 @@ struct tz_ctx {
     // stages with tz_huff_begin / tz_huff_put together with what tz_huff_decode needs to expand it
     uint8_t* d_huff = nullptr;
     size_t cap_huff = 0, huff_bytes = 0;
-    size_t huff_n = 0;                      // tz_huff_begin: elements the staged stream decodes to (0: nothing staged)
-    int huff_base = 0;
-    std::vector<uint16_t> huff_dec_tab;     // tz_huff_begin: the 2^12-entry decode table of the staged stream's lengths
-    // tz_huffr_begin stages a TZR1 stream in the same buffers (d_huff, huff_bytes, huff_base, huff_dec_tab) and sets these
-    // instead of huff_n, so that neither decoder expands the other's stream
-    size_t huffr_n = 0;
-    int huffr_A = 0;                        // literals of the staged TZR1 code (symbols A..A + 7 are its repeat tokens)
+    // what tz_huff_begin / tz_huffr_begin staged in d_huff, so that neither decoder expands the other's stream
+    enum tz_huff_kind { HUFF_NONE, HUFF_TZH1, HUFF_TZR1 } huff_kind = HUFF_NONE;
+    size_t huff_n = 0;                      // elements the staged stream decodes to
+    int huff_A = 0, huff_base = 0;          // literals of the staged code (a TZR1 code has its repeat tokens behind them)
+    std::vector<uint16_t> huff_dec_tab;     // the 2^12-entry decode table of the staged stream's lengths
     // opt-in key-frame coder (tz_keys_*): buffers of its own, so that an entropy stream staged with tz_huff_begin /
     // tz_huffr_begin survives it.  d_keys: the coded stream (index | bits) tz_keys_encode left or tz_keys_begin / tz_keys_put
     // stage; d_keysym: the int16 residual symbols between the predictor kernels and the Huffman kernels
     uint8_t* d_keys = nullptr;
     int16_t* d_keysym = nullptr;
     size_t cap_keys = 0, cap_keysym = 0, keys_bytes = 0;
-    size_t keys_n = 0;                      // tz_keys_begin: symbols the staged stream decodes to (0: nothing staged)
-    size_t keys_put = 0;                    // bytes tz_keys_put has staged since tz_keys_begin
+    // what tz_keys_begin / tz_keysg_begin staged in d_keys, so that neither decoder expands the other's stream
+    enum tz_keys_kind { KEYS_NONE, KEYS_TZK1, KEYS_TZK2 } keys_kind = KEYS_NONE;
+    size_t keys_n = 0;                      // symbols the staged stream decodes to
+    size_t keys_put = 0;                    // bytes tz_keys_put / tz_keysg_put have staged since the begin
     int keys_nt = 0, keys_H = 0, keys_W = 0;
-    std::vector<int> keys_idx;              // tz_keys_begin: the key frames' indices ...
-    std::vector<uint8_t> keys_pred;         // ... and predictor ids
-    std::vector<uint16_t> keys_dec_tab;     // tz_keys_begin: the 2^12-entry decode table of the staged stream's lengths
-    size_t keysg_n = 0;                     // tz_keysg_begin: the same for a TZK2 stream, which shares the buffers and the fields
-                                            // above (keys_pred then holds pred bytes); at most one of keys_n, keysg_n is non-zero
+    std::vector<int> keys_idx;              // the key frames' indices ...
+    std::vector<uint8_t> keys_pred;         // ... and predictor ids (TZK1) or pred bytes (TZK2)
+    std::vector<uint16_t> keys_dec_tab;     // the 2^12-entry decode table of the staged stream's lengths
     uint8_t* d_out = nullptr;               // resident decoded frames of a tz_decode(frames_out = NULL)
     size_t cap_out = 0;
     bool have_decoded = false;
@@ -327,22 +325,17 @@ struct tz_huff_meta {            // device words the size / scan launches leave 
     unsigned pad;
 };
 int tzk_huff_count(tz_ctx*, const int16_t* in, size_t n, unsigned long long* d_hist4096, tz_huff_meta* d_meta);
-// run sizes (u16, bits) and chunk word offsets (u32) of the payload under the code `h_enc` (u16[A]: stored code | length << 12)
-int tzk_huff_size(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
+// Huffman coder with repeat tokens (TZR1, DESIGN.md section 9): the same geometry and index; a code has A literals and then
+// TZ_HUFFR_NTOK repeat tokens, so the histogram holds TZ_HUFF_COUNT_BINS + 8 bins.
+int tzk_huffr_count(tz_ctx*, const int16_t* in, size_t n, unsigned long long* d_hist4104, tz_huff_meta* d_meta);
+// The passes of both coders; ntok: 0 (TZH1) or TZ_HUFFR_NTOK (TZR1, d_enc then holds A + ntok entries behind the A literals).
+// run sizes (u16, bits) and chunk word offsets (u32) of the payload under the code `d_enc` (u16: stored code | length << 12)
+int tzk_huff_size(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, uint16_t* d_run_bits,
                   unsigned* d_chunk_off, tz_huff_meta* d_meta);
-int tzk_huff_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
+int tzk_huff_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, const uint16_t* d_run_bits,
                  const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words);
 int tzk_huff_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
-                 const uint16_t* d_dec_tab4096, int base, size_t n, int16_t* out);
-// Huffman coder with repeat tokens (TZR1, DESIGN.md section 9): the same geometry and index; a code has A literals and then
-// TZ_HUFFR_NTOK repeat tokens, so d_enc holds A + 8 entries and the histogram TZ_HUFF_COUNT_BINS + 8 bins.
-int tzk_huffr_count(tz_ctx*, const int16_t* in, size_t n, unsigned long long* d_hist4104, tz_huff_meta* d_meta);
-int tzk_huffr_size(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
-                   unsigned* d_chunk_off, tz_huff_meta* d_meta);
-int tzk_huffr_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
-                  const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words);
-int tzk_huffr_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
-                  const uint16_t* d_dec_tab4096, int A, int base, size_t n, int16_t* out);
+                 const uint16_t* d_dec_tab4096, int A, int base, int ntok, size_t n, int16_t* out);
 // key-frame coder (TZK1).  d_frames: a stack of H x W x 3 frames of which frame d_idx[k] is key frame k;
 // d_pred[k] its predictor id 0..3; d_sym: nkeys * H * W * 3 int16 symbols 0..255, key after key.
 int tzk_key_hist(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, int nkeys, unsigned* d_counts /* [nkeys][4][256] */);

@@ -13,6 +13,7 @@ File layout, little-endian, every section padded with zero bytes to a multiple o
 A run is R consecutive symbols coded back to back; a chunk is chunk_runs runs and starts on a word boundary.  A code of
 length l and canonical value c (MSB first) is stored bit-reversed, first code bit in the lowest free bit of the stream.
 """
+import collections
 import struct
 
 import numpy as np
@@ -24,6 +25,9 @@ RUN = 256               # R: symbols per run (one lane of the kernels)
 CHUNK_RUNS = 64         # runs per chunk (one wave)
 NBINS = 2111            # TZ_NBINS: the largest alphabet
 HEADER = struct.Struct("<4sHHQiIIIIIII")   # 48 bytes
+# What tells the entropy.dat formats apart: the magic, the tag of the messages, and the repeat tokens behind the A literals.
+Format = collections.namedtuple("Format", "magic tag ntok")
+TZH1 = Format(MAGIC, "huff", 0)
 
 
 def is_huff(head):
@@ -110,50 +114,66 @@ def geometry(n, run=RUN, chunk_runs=CHUNK_RUNS):
     return nruns, (nruns + chunk_runs - 1) // chunk_runs
 
 
-def encode_body(payload, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
-    """int16 payload -> (chunk_off uint32[nchunks], run_bits uint16[nruns], words uint32[stream_words])."""
-    sym = np.asarray(payload, np.int64).reshape(-1) - int(base)
-    n = sym.size
-    ln = np.asarray(lengths, np.int64)
-    if n < 1:
-        raise ValueError("huff: an empty payload cannot be coded")
-    if sym.min() < 0 or sym.max() >= ln.size or (ln[sym] == 0).any():
-        raise ValueError("huff: the payload holds a value without a code")
+def layout(tag, bits, at, run=RUN, chunk_runs=CHUNK_RUNS):
+    """bits int64[n]: the bits coded AT every element -> (chunk_off uint32[nchunks], run_bits uint16[nruns], stream_words,
+    pos): pos is the stream bit at which the code of each element of `at` starts."""
+    n = bits.size
     nruns, nchunks = geometry(n, run, chunk_runs)
-    sl = ln[sym]
-    cum = np.concatenate([[0], np.cumsum(sl)])                      # bits in front of symbol i, chunks unpadded
+    cum = np.concatenate([[0], np.cumsum(bits)])                    # bits in front of element i, chunks unpadded
     run_start = np.arange(nruns, dtype=np.int64) * run
     run_bits = cum[np.minimum(run_start + run, n)] - cum[run_start]
     chunk_first = np.arange(nchunks, dtype=np.int64) * run * chunk_runs
     chunk_bits = cum[np.minimum(chunk_first + run * chunk_runs, n)] - cum[chunk_first]
-    chunk_words = (chunk_bits + 31) >> 5
-    chunk_off = np.concatenate([[0], np.cumsum(chunk_words)])
+    chunk_off = np.concatenate([[0], np.cumsum((chunk_bits + 31) >> 5)])
     total = int(chunk_off[-1])
     if total >= 1 << 32:
-        raise ValueError("huff: the bit stream needs %d words, the format holds 2^32 - 1" % total)
-    ci = np.arange(n, dtype=np.int64) // (run * chunk_runs)
-    pos = chunk_off[ci] * 32 + (cum[:-1] - cum[chunk_first][ci])   # stream bit of every symbol's first code bit
-    val = canonical_codes(ln).astype(np.uint64)[sym] << (pos & 31).astype(np.uint64)
+        raise ValueError("%s: the bit stream needs %d words, the format holds 2^32 - 1" % (tag, total))
+    ci = at // (run * chunk_runs)
+    pos = chunk_off[ci] * 32 + (cum[at] - cum[chunk_first][ci])
+    return chunk_off[:-1].astype(np.uint32), run_bits.astype(np.uint16), total, pos
+
+
+def scatter(code, pos, total):
+    """Codes (fewer than 32 bits each) at ascending, non-overlapping stream bits `pos` -> uint32[total] words."""
+    val = code.astype(np.uint64) << (pos & 31).astype(np.uint64)
     words = np.zeros(total + 1, np.uint64)
     w = pos >> 5                                                    # ascending: codes never overlap, so OR is a sum
     first = np.nonzero(np.concatenate([[True], w[1:] != w[:-1]]))[0]
     words[w[first]] += np.add.reduceat(val & np.uint64(0xFFFFFFFF), first)
     words[w[first] + 1] += np.add.reduceat(val >> np.uint64(32), first)
-    return chunk_off[:-1].astype(np.uint32), run_bits.astype(np.uint16), words[:total].astype(np.uint32)
+    return words[:total].astype(np.uint32)
 
 
-def decode_body(chunk_off, run_bits, words, n, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
-    """The inverse of encode_body: every run is decoded from its own bit offset (chunk offset + the run sizes in front of
-    it inside the chunk), all runs in lockstep as the lanes of k_huff_dec do.  Reads past the stream's end see zeros."""
+def encode_body(payload, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
+    """int16 payload -> (chunk_off uint32[nchunks], run_bits uint16[nruns], words uint32[stream_words])."""
+    sym = np.asarray(payload, np.int64).reshape(-1) - int(base)
+    ln = np.asarray(lengths, np.int64)
+    if sym.size < 1:
+        raise ValueError("huff: an empty payload cannot be coded")
+    if sym.min() < 0 or sym.max() >= ln.size or (ln[sym] == 0).any():
+        raise ValueError("huff: the payload holds a value without a code")
+    chunk_off, run_bits, total, pos = layout("huff", ln[sym], np.arange(sym.size, dtype=np.int64), run, chunk_runs)
+    return chunk_off, run_bits, scatter(canonical_codes(ln)[sym], pos, total)
+
+
+def run_positions(chunk_off, run_bits, words, n, run=RUN, chunk_runs=CHUNK_RUNS):
+    """-> (pos int64[nruns]: the stream bit at which every run starts (chunk offset + the run sizes in front of it inside the
+    chunk), w: the words as uint64 with two zero words behind them, last: the highest index a 64-bit window may start at)."""
     nruns, nchunks = geometry(n, run, chunk_runs)
-    tab = decode_table(lengths)
     rb = np.zeros(nchunks * chunk_runs, np.int64)
     rb[:nruns] = np.asarray(run_bits, np.int64)
     rb = rb.reshape(nchunks, chunk_runs)
     pos = (np.asarray(chunk_off, np.int64)[:, None] * 32 + np.cumsum(rb, 1) - rb).reshape(-1)[:nruns]
     w = np.concatenate([np.asarray(words, np.uint64), np.zeros(2, np.uint64)])
-    last = w.size - 2
-    out = np.zeros(nruns * run, np.int16)
+    return pos, w, w.size - 2
+
+
+def decode_body(chunk_off, run_bits, words, n, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
+    """The inverse of encode_body: every run is decoded from its own bit offset, all runs in lockstep as the lanes of
+    k_huff_dec do.  Reads past the stream's end see zeros."""
+    tab = decode_table(lengths)
+    pos, w, last = run_positions(chunk_off, run_bits, words, n, run, chunk_runs)
+    out = np.zeros(pos.size * run, np.int16)
     for k in range(run):
         i = np.minimum(pos >> 5, last)
         bits = ((w[i] | (w[i + 1] << np.uint64(32))) >> (pos & 31).astype(np.uint64)) & np.uint64(0xFFF)
@@ -187,14 +207,19 @@ def parse_trailer(tr):
     return np.ascontiguousarray(tr[:tlen]), shape, warm_up
 
 
-def pack_front(trailer, lengths, base, n, nchunks, stream_words, run=RUN, chunk_runs=CHUNK_RUNS):
-    """Header | trailer | lengths: everything of the file in front of the index."""
+def pack_front_of(fmt, trailer, lengths, base, n, nchunks, stream_words, run=RUN, chunk_runs=CHUNK_RUNS):
+    """Header | trailer | lengths of the format `fmt`: everything of the file in front of the index."""
     trailer = np.ascontiguousarray(trailer, "<i2")
     lengths = np.ascontiguousarray(lengths, np.uint8)
-    head = HEADER.pack(MAGIC, VERSION, MAX_LEN, int(n), int(base), int(lengths.size), int(run), int(chunk_runs), int(nchunks),
-                       int(stream_words), int(trailer.size), 0)
+    head = HEADER.pack(fmt.magic, VERSION, MAX_LEN, int(n), int(base), int(lengths.size) - fmt.ntok, int(run), int(chunk_runs),
+                       int(nchunks), int(stream_words), int(trailer.size), 0)
     tb, lb = trailer.tobytes(), lengths.tobytes()
     return head + tb + b"\0" * (_pad4(len(tb)) - len(tb)) + lb + b"\0" * (_pad4(len(lb)) - len(lb))
+
+
+def pack_front(trailer, lengths, base, n, nchunks, stream_words, run=RUN, chunk_runs=CHUNK_RUNS):
+    """Header | trailer | lengths: everything of the file in front of the index."""
+    return pack_front_of(TZH1, trailer, lengths, base, n, nchunks, stream_words, run, chunk_runs)
 
 
 def pack_body(chunk_off, run_bits, words):
@@ -224,73 +249,89 @@ class Parsed:
     """A validated Huffman entropy.dat: header fields, the reference trailer's content, and views of the sections."""
 
 
-def parse(data, key_len=None):
-    """Validate a Huffman-coded entropy.dat (bytes / uint8 array) -> Parsed.  Everything a pointer or a launch will be
-    derived from is checked here, on the CPU; a failure is a ValueError that names the field."""
-    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1)
+def check_index(what, chunk_off, run_bits, stream_words, run=RUN, chunk_runs=CHUNK_RUNS, ascending="ascending"):
+    """The index of a stream whose file is `what` (the prefix of the messages): offsets ascending from 0 inside the stream,
+    run sizes <= R * L, and the run sizes of a chunk fit the chunk."""
+    co = chunk_off.astype(np.int64)
+    if co[0] != 0 or (np.diff(co) < 0).any() or co[-1] > stream_words:
+        raise ValueError("%s: chunk offset table is not %s inside the %d words of the bit stream" % (what, ascending, stream_words))
+    rb = run_bits.astype(np.int64)
+    if (rb > run * MAX_LEN).any():
+        raise ValueError("%s: a run length of %d bits exceeds R * L = %d" % (what, int(rb.max()), run * MAX_LEN))
+    per_chunk = np.add.reduceat(rb, np.arange(0, rb.size, chunk_runs))
+    room = (np.concatenate([co[1:], [stream_words]]) - co) * 32
+    if (per_chunk > room).any():
+        c = int(np.nonzero(per_chunk > room)[0][0])
+        raise ValueError("%s: the run lengths of chunk %d sum to %d bits, the chunk has %d" % (what, c, int(per_chunk[c]), int(room[c])))
+
+
+def as_bytes(data):
+    """bytes / any array -> a flat uint8 view"""
+    return np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1)
+
+
+def parse_of(fmt, p, check, data, key_len=None):
+    """Validate an entropy.dat of the format `fmt` (bytes / uint8 array) into the empty Parsed `p`; `check` is the format's
+    check_lengths.  Everything a pointer or a launch will be derived from is checked here, on the CPU; a failure is a
+    ValueError that names the field."""
+    what = "entropy.dat (%s)" % fmt.tag
+    buf = as_bytes(data)
     if buf.size < HEADER.size:
-        raise ValueError("entropy.dat (huff): file size %d is shorter than the %d-byte header (truncated)" % (buf.size, HEADER.size))
+        raise ValueError("%s: file size %d is shorter than the %d-byte header (truncated)" % (what, buf.size, HEADER.size))
     magic, version, max_len, n, base, A, run, chunk_runs, nchunks, stream_words, trailer_len, _ = HEADER.unpack(buf[:HEADER.size].tobytes())
-    if magic != MAGIC:
-        raise ValueError("entropy.dat (huff): magic %r is not %r" % (magic, MAGIC))
+    if magic != fmt.magic:
+        raise ValueError("%s: magic %r is not %r" % (what, magic, fmt.magic))
     if version != VERSION:
-        raise ValueError("entropy.dat (huff): format version %d, this build reads version %d" % (version, VERSION))
+        raise ValueError("%s: format version %d, this build reads version %d" % (what, version, VERSION))
     if max_len != MAX_LEN:
-        raise ValueError("entropy.dat (huff): code length limit L = %d, this build reads L = %d" % (max_len, MAX_LEN))
+        raise ValueError("%s: code length limit L = %d, this build reads L = %d" % (what, max_len, MAX_LEN))
     if not 1 <= A <= NBINS:
-        raise ValueError("entropy.dat (huff): alphabet size A = %d outside [1, TZ_NBINS = %d]" % (A, NBINS))
+        raise ValueError("%s: %s A = %d outside [1, TZ_NBINS = %d]" % (what, "literal alphabet" if fmt.ntok else "alphabet size", A, NBINS))
     if base < -32768 or base + A - 1 > 32767:
-        raise ValueError("entropy.dat (huff): symbol base %d with A = %d leaves int16" % (base, A))
+        raise ValueError("%s: symbol base %d with A = %d leaves int16" % (what, base, A))
     if run != RUN or chunk_runs != CHUNK_RUNS:
-        raise ValueError("entropy.dat (huff): run length R = %d / chunk of %d runs, this build reads R = %d / %d"
-                         % (run, chunk_runs, RUN, CHUNK_RUNS))
+        raise ValueError("%s: run length R = %d / chunk of %d runs, this build reads R = %d / %d" % (what, run, chunk_runs, RUN, CHUNK_RUNS))
     if n < 1 or n >= 1 << 40:
-        raise ValueError("entropy.dat (huff): element count n = %d outside [1, 2^40)" % n)
+        raise ValueError("%s: element count n = %d outside [1, 2^40)" % (what, n))
     nruns, want_chunks = geometry(n, run, chunk_runs)
     if nchunks != want_chunks:
-        raise ValueError("entropy.dat (huff): nchunks = %d, n = %d elements make %d chunks" % (nchunks, n, want_chunks))
+        raise ValueError("%s: nchunks = %d, n = %d elements make %d chunks" % (what, nchunks, n, want_chunks))
     if not 7 <= trailer_len <= NBINS + 7:
-        raise ValueError("entropy.dat (huff): trailer length %d outside [7, %d]" % (trailer_len, NBINS + 7))
+        raise ValueError("%s: trailer length %d outside [7, %d]" % (what, trailer_len, NBINS + 7))
     o_tr = HEADER.size
     o_len = o_tr + _pad4(trailer_len * 2)
-    o_idx = o_len + _pad4(A)
+    o_idx = o_len + _pad4(A + fmt.ntok)
     o_runs = o_idx + nchunks * 4
     o_bits = o_runs + _pad4(nruns * 2)
     total = o_bits + stream_words * 4
     if buf.size != total:
-        raise ValueError("entropy.dat (huff): file size %d, the header describes %d bytes (truncated or corrupt file)" % (buf.size, total))
-    p = Parsed()
+        raise ValueError("%s: file size %d, the header describes %d bytes (truncated or corrupt file)" % (what, buf.size, total))
     p.n, p.base, p.A, p.run, p.chunk_runs, p.nchunks, p.nruns, p.stream_words = n, base, A, run, chunk_runs, nchunks, nruns, stream_words
     p.table, p.shape, p.warm_up = parse_trailer(buf[o_tr: o_tr + trailer_len * 2].view("<i2"))
-    p.lengths = buf[o_len: o_len + A]
-    check_lengths(p.lengths)
+    p.lengths = buf[o_len: o_len + A + fmt.ntok]                     # the literals, then the repeat tokens
+    check(p.lengths)
     one, nt, H, W, C = p.shape
     if one != 1 or C != 3 or nt < 1 or H < 1 or W < 1:
-        raise ValueError("entropy.dat (huff): unsupported stack shape %r (expected (1, nt, H, W, 3))" % (tuple(p.shape),))
+        raise ValueError("%s: unsupported stack shape %r (expected (1, nt, H, W, 3))" % (what, tuple(p.shape)))
     if n != nt * H * W * C:
-        raise ValueError("entropy.dat (huff): element count n = %d, the trailer's shape says %d" % (n, nt * H * W * C))
+        raise ValueError("%s: element count n = %d, the trailer's shape says %d" % (what, n, nt * H * W * C))
     if key_len is not None and key_len != n:
         raise ValueError("key_frame.dat holds %d bytes, entropy.dat's trailer implies %d" % (key_len, n))
     if not 0 <= p.warm_up < nt:
         raise ValueError("entropy.dat: warm-up count %d outside [0, %d)" % (p.warm_up, nt))
     if p.table is not None and (base != 0 or A > max(len(p.table), 1)):
-        raise ValueError("entropy.dat (huff): alphabet A = %d / base %d does not fit the %d ranks of the table" % (A, base, len(p.table)))
+        raise ValueError("%s: alphabet A = %d / base %d does not fit the %d ranks of the table" % (what, A, base, len(p.table)))
     p.chunk_off = buf[o_idx: o_runs].view("<u4")
     p.run_bits = buf[o_runs: o_runs + nruns * 2].view("<u2")
     p.words = buf[o_bits: total].view("<u4")
-    p.body = buf[o_idx: total]                      # index | bits: what tz_huff_put stages
-    co = p.chunk_off.astype(np.int64)
-    if co[0] != 0 or (np.diff(co) < 0).any() or co[-1] > stream_words:
-        raise ValueError("entropy.dat (huff): chunk offset table is not ascending inside the %d words of the bit stream" % stream_words)
-    rb = p.run_bits.astype(np.int64)
-    if (rb > run * MAX_LEN).any():
-        raise ValueError("entropy.dat (huff): a run length of %d bits exceeds R * L = %d" % (int(rb.max()), run * MAX_LEN))
-    per_chunk = np.add.reduceat(rb, np.arange(0, nruns, chunk_runs))
-    room = (np.concatenate([co[1:], [stream_words]]) - co) * 32
-    if (per_chunk > room).any():
-        c = int(np.nonzero(per_chunk > room)[0][0])
-        raise ValueError("entropy.dat (huff): the run lengths of chunk %d sum to %d bits, the chunk has %d" % (c, int(per_chunk[c]), int(room[c])))
+    p.body = buf[o_idx: total]                      # index | bits: what tz_huff_put / tz_huffr_put stages
+    check_index(what, p.chunk_off, p.run_bits, stream_words, run, chunk_runs)
     return p
+
+
+def parse(data, key_len=None):
+    """Validate a Huffman-coded entropy.dat (bytes / uint8 array) -> Parsed."""
+    return parse_of(TZH1, Parsed(), check_lengths, data, key_len)
 
 
 def decode_file(data, key_len=None):

@@ -21,6 +21,7 @@ of three elements equal to `base` where a token stands at j < 3, so every bit pa
 """
 import numpy as np
 
+from . import huff
 from .huff import (CHUNK_RUNS, HEADER, MAX_LEN, NBINS, RUN, _pad4, body_bytes, canonical_codes, decode_table,  # noqa: F401
                    geometry, kraft_sum, pack_body, parse_trailer, reference_trailer)   # (index | bits are laid out as in TZH1)
 
@@ -28,6 +29,7 @@ MAGIC = b"TZR1"
 VERSION = 1
 NTOK = 8                # repeat tokens T_0..T_7: stretches of 2^k .. 2^(k+1) - 1 matches
 DIST = 3                # the match distance: one pixel of the interleaved (H, W, 3) payload
+TZR1 = huff.Format(MAGIC, "huffr", NTOK)
 
 
 def is_huffr(head):
@@ -120,42 +122,20 @@ def encode_body(payload, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
         raise ValueError("huffr: the payload needs a literal or a token without a code")
     bits = np.zeros(n, np.int64)
     bits[at] = tl + nextra[at]
-    cum = np.concatenate([[0], np.cumsum(bits)])                     # bits in front of element i, chunks unpadded
-    nruns, nchunks = geometry(n, run, chunk_runs)
-    run_start = np.arange(nruns, dtype=np.int64) * run
-    run_bits = cum[np.minimum(run_start + run, n)] - cum[run_start]
-    chunk_first = np.arange(nchunks, dtype=np.int64) * run * chunk_runs
-    chunk_bits = cum[np.minimum(chunk_first + run * chunk_runs, n)] - cum[chunk_first]
-    chunk_off = np.concatenate([[0], np.cumsum((chunk_bits + 31) >> 5)])
-    total = int(chunk_off[-1])
-    if total >= 1 << 32:
-        raise ValueError("huffr: the bit stream needs %d words, the format holds 2^32 - 1" % total)
-    ci = at // (run * chunk_runs)
-    pos = chunk_off[ci] * 32 + (cum[at] - cum[chunk_first][ci])      # stream bit of every token's first code bit
+    chunk_off, run_bits, total, pos = huff.layout("huffr", bits, at, run, chunk_runs)
     code = canonical_codes(ln).astype(np.int64)[tok[at]] | (extra[at] << tl)          # <= 12 + 7 bits
-    val = code.astype(np.uint64) << (pos & 31).astype(np.uint64)
-    words = np.zeros(total + 1, np.uint64)
-    w = pos >> 5                                                     # ascending: codes never overlap, so OR is a sum
-    first = np.nonzero(np.concatenate([[True], w[1:] != w[:-1]]))[0]
-    words[w[first]] += np.add.reduceat(val & np.uint64(0xFFFFFFFF), first)
-    words[w[first] + 1] += np.add.reduceat(val >> np.uint64(32), first)
-    return chunk_off[:-1].astype(np.uint32), run_bits.astype(np.uint16), words[:total].astype(np.uint32)
+    return chunk_off, run_bits, huff.scatter(code, pos, total)
 
 
 def decode_body(chunk_off, run_bits, words, n, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
     """The inverse of encode_body for ANY bits: every run is decoded from its own bit offset, all runs in lockstep as the
     lanes of k_huffr_dec do, one element per step -- a lane inside a stretch copies the element three back, any other lane
     reads a symbol.  Reads past the stream's end see zeros; a stretch ends with its run."""
-    nruns, nchunks = geometry(n, run, chunk_runs)
     ln = np.asarray(lengths, np.int64)
     A = ln.size - NTOK
     tab = decode_table(ln)
-    rb = np.zeros(nchunks * chunk_runs, np.int64)
-    rb[:nruns] = np.asarray(run_bits, np.int64)
-    rb = rb.reshape(nchunks, chunk_runs)
-    pos = (np.asarray(chunk_off, np.int64)[:, None] * 32 + np.cumsum(rb, 1) - rb).reshape(-1)[:nruns]
-    w = np.concatenate([np.asarray(words, np.uint64), np.zeros(2, np.uint64)])
-    last = w.size - 2
+    pos, w, last = huff.run_positions(chunk_off, run_bits, words, n, run, chunk_runs)
+    nruns = pos.size
     out = np.zeros(nruns * run, np.int16)
     h1 = h2 = h3 = np.full(nruns, int(base), np.int64)               # the imaginary history in front of a run
     m = np.zeros(nruns, np.int64)                                    # elements the current stretch still has to copy
@@ -178,12 +158,7 @@ def decode_body(chunk_off, run_bits, words, n, lengths, base, run=RUN, chunk_run
 
 def pack_front(trailer, lengths, base, n, nchunks, stream_words, run=RUN, chunk_runs=CHUNK_RUNS):
     """Header | trailer | lengths: everything of the file in front of the index."""
-    trailer = np.ascontiguousarray(trailer, "<i2")
-    lengths = np.ascontiguousarray(lengths, np.uint8)
-    head = HEADER.pack(MAGIC, VERSION, MAX_LEN, int(n), int(base), int(lengths.size) - NTOK, int(run), int(chunk_runs),
-                       int(nchunks), int(stream_words), int(trailer.size), 0)
-    tb, lb = trailer.tobytes(), lengths.tobytes()
-    return head + tb + b"\0" * (_pad4(len(tb)) - len(tb)) + lb + b"\0" * (_pad4(len(lb)) - len(lb))
+    return huff.pack_front_of(TZR1, trailer, lengths, base, n, nchunks, stream_words, run, chunk_runs)
 
 
 def encode_file(payload, table, shape5, warm_up, lengths=None, base=None):
@@ -203,72 +178,8 @@ class Parsed:
 
 
 def parse(data, key_len=None):
-    """Validate a TZR1 entropy.dat (bytes / uint8 array) -> Parsed.  Everything a pointer or a launch will be derived from
-    is checked here, on the CPU; a failure is a ValueError that names the field."""
-    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1)
-    if buf.size < HEADER.size:
-        raise ValueError("entropy.dat (huffr): file size %d is shorter than the %d-byte header (truncated)" % (buf.size, HEADER.size))
-    magic, version, max_len, n, base, A, run, chunk_runs, nchunks, stream_words, trailer_len, _ = HEADER.unpack(buf[:HEADER.size].tobytes())
-    if magic != MAGIC:
-        raise ValueError("entropy.dat (huffr): magic %r is not %r" % (magic, MAGIC))
-    if version != VERSION:
-        raise ValueError("entropy.dat (huffr): format version %d, this build reads version %d" % (version, VERSION))
-    if max_len != MAX_LEN:
-        raise ValueError("entropy.dat (huffr): code length limit L = %d, this build reads L = %d" % (max_len, MAX_LEN))
-    if not 1 <= A <= NBINS:
-        raise ValueError("entropy.dat (huffr): literal alphabet A = %d outside [1, TZ_NBINS = %d]" % (A, NBINS))
-    if base < -32768 or base + A - 1 > 32767:
-        raise ValueError("entropy.dat (huffr): symbol base %d with A = %d leaves int16" % (base, A))
-    if run != RUN or chunk_runs != CHUNK_RUNS:
-        raise ValueError("entropy.dat (huffr): run length R = %d / chunk of %d runs, this build reads R = %d / %d"
-                         % (run, chunk_runs, RUN, CHUNK_RUNS))
-    if n < 1 or n >= 1 << 40:
-        raise ValueError("entropy.dat (huffr): element count n = %d outside [1, 2^40)" % n)
-    nruns, want_chunks = geometry(n, run, chunk_runs)
-    if nchunks != want_chunks:
-        raise ValueError("entropy.dat (huffr): nchunks = %d, n = %d elements make %d chunks" % (nchunks, n, want_chunks))
-    if not 7 <= trailer_len <= NBINS + 7:
-        raise ValueError("entropy.dat (huffr): trailer length %d outside [7, %d]" % (trailer_len, NBINS + 7))
-    o_tr = HEADER.size
-    o_len = o_tr + _pad4(trailer_len * 2)
-    o_idx = o_len + _pad4(A + NTOK)
-    o_runs = o_idx + nchunks * 4
-    o_bits = o_runs + _pad4(nruns * 2)
-    total = o_bits + stream_words * 4
-    if buf.size != total:
-        raise ValueError("entropy.dat (huffr): file size %d, the header describes %d bytes (truncated or corrupt file)" % (buf.size, total))
-    p = Parsed()
-    p.n, p.base, p.A, p.run, p.chunk_runs, p.nchunks, p.nruns, p.stream_words = n, base, A, run, chunk_runs, nchunks, nruns, stream_words
-    p.table, p.shape, p.warm_up = parse_trailer(buf[o_tr: o_tr + trailer_len * 2].view("<i2"))
-    p.lengths = buf[o_len: o_len + A + NTOK]                         # literals, then T_0..T_7
-    check_lengths(p.lengths)
-    one, nt, H, W, C = p.shape
-    if one != 1 or C != 3 or nt < 1 or H < 1 or W < 1:
-        raise ValueError("entropy.dat (huffr): unsupported stack shape %r (expected (1, nt, H, W, 3))" % (tuple(p.shape),))
-    if n != nt * H * W * C:
-        raise ValueError("entropy.dat (huffr): element count n = %d, the trailer's shape says %d" % (n, nt * H * W * C))
-    if key_len is not None and key_len != n:
-        raise ValueError("key_frame.dat holds %d bytes, entropy.dat's trailer implies %d" % (key_len, n))
-    if not 0 <= p.warm_up < nt:
-        raise ValueError("entropy.dat: warm-up count %d outside [0, %d)" % (p.warm_up, nt))
-    if p.table is not None and (base != 0 or A > max(len(p.table), 1)):
-        raise ValueError("entropy.dat (huffr): alphabet A = %d / base %d does not fit the %d ranks of the table" % (A, base, len(p.table)))
-    p.chunk_off = buf[o_idx: o_runs].view("<u4")
-    p.run_bits = buf[o_runs: o_runs + nruns * 2].view("<u2")
-    p.words = buf[o_bits: total].view("<u4")
-    p.body = buf[o_idx: total]                      # index | bits: what tz_huffr_put stages
-    co = p.chunk_off.astype(np.int64)
-    if co[0] != 0 or (np.diff(co) < 0).any() or co[-1] > stream_words:
-        raise ValueError("entropy.dat (huffr): chunk offset table is not ascending inside the %d words of the bit stream" % stream_words)
-    rb = p.run_bits.astype(np.int64)
-    if (rb > run * MAX_LEN).any():
-        raise ValueError("entropy.dat (huffr): a run length of %d bits exceeds R * L = %d" % (int(rb.max()), run * MAX_LEN))
-    per_chunk = np.add.reduceat(rb, np.arange(0, nruns, chunk_runs))
-    room = (np.concatenate([co[1:], [stream_words]]) - co) * 32
-    if (per_chunk > room).any():
-        c = int(np.nonzero(per_chunk > room)[0][0])
-        raise ValueError("entropy.dat (huffr): the run lengths of chunk %d sum to %d bits, the chunk has %d" % (c, int(per_chunk[c]), int(room[c])))
-    return p
+    """Validate a TZR1 entropy.dat (bytes / uint8 array) -> Parsed: huff.parse's checks over A + 8 code lengths."""
+    return huff.parse_of(TZR1, Parsed(), check_lengths, data, key_len)
 
 
 def decode_file(data, key_len=None):

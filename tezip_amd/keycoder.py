@@ -121,21 +121,25 @@ def symbols(key_frames, pred):
     return np.concatenate([residual(f, p) for f, p in zip(key_frames, pred)])
 
 
-def encode_file(stack_or_keyframes, idx, nt):
-    """The whole key_frame.dat on the CPU (tests, and the specification of compress.run's output).  The first argument is
-    the (nt, H, W, 3) stack, of which the frames `idx` are coded, or the (len(idx), H, W, 3) key frames themselves."""
+def key_frames_of(what, stack_or_keyframes, idx, nt):
+    """encode_file's arguments -> (uint8 (k, H, W, 3) key frames, int64[k] indices); `what` is the prefix of the messages."""
     x = np.asarray(stack_or_keyframes, np.uint8)
     idx = np.asarray(idx, np.int64).reshape(-1)
     if x.ndim != 4 or x.shape[3] != 3:
         raise ValueError("key frames must be a (k, H, W, 3) uint8 stack, got shape %r" % (tuple(x.shape),))
     if idx.size < 1 or (np.diff(idx) <= 0).any() or idx[0] < 0 or idx[-1] >= nt:
-        raise ValueError("key_frame.dat (huff): key indices must be strictly ascending inside [0, %d)" % nt)
+        raise ValueError("%s: key indices must be strictly ascending inside [0, %d)" % (what, nt))
     if x.shape[0] == nt:
-        kf = x[idx]
-    elif x.shape[0] == idx.size:
-        kf = x
-    else:
-        raise ValueError("%d frames given for %d key indices of a %d-frame sequence" % (x.shape[0], idx.size, nt))
+        return x[idx], idx
+    if x.shape[0] == idx.size:
+        return x, idx
+    raise ValueError("%d frames given for %d key indices of a %d-frame sequence" % (x.shape[0], idx.size, nt))
+
+
+def encode_file(stack_or_keyframes, idx, nt):
+    """The whole key_frame.dat on the CPU (tests, and the specification of compress.run's output).  The first argument is
+    the (nt, H, W, 3) stack, of which the frames `idx` are coded, or the (len(idx), H, W, 3) key frames themselves."""
+    kf, idx = key_frames_of("key_frame.dat (huff)", stack_or_keyframes, idx, nt)
     H, W = kf.shape[1:3]
     counts = predictor_counts(kf)
     pred = choose_predictors(counts)
@@ -148,70 +152,82 @@ class Parsed:
     """A validated TZK1 key_frame.dat: the stack's shape, the key indices, their predictors, and views of the sections."""
 
 
-def parse(data):
-    """Validate a TZK1 key_frame.dat (bytes / uint8 array) -> Parsed.  Everything a pointer or a launch will be derived
-    from is checked here, on the CPU; a failure is a ValueError that names the field."""
-    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1)
+def parse_header(what, magic_want, data):
+    """The header of a TZK1 / TZK2 file (`what` is the prefix of the messages) -> (buf, nt, H, W, nkeys, run, chunk_runs,
+    nchunks, stream_words, o_pred, o_len, o_co): the fields and where the pred bytes, the lengths and the index start."""
+    buf = huff.as_bytes(data)
     if buf.size < HEADER.size:
-        raise ValueError("key_frame.dat (huff): file size %d is shorter than the %d-byte header (truncated)" % (buf.size, HEADER.size))
+        raise ValueError("%s: file size %d is shorter than the %d-byte header (truncated)" % (what, buf.size, HEADER.size))
     magic, version, max_len, nt, H, W, C, nkeys, run, chunk_runs, nchunks, stream_words, _ = HEADER.unpack(buf[:HEADER.size].tobytes())
-    if magic != MAGIC:
-        raise ValueError("key_frame.dat (huff): magic %r is not %r" % (magic, MAGIC))
+    if magic != magic_want:
+        raise ValueError("%s: magic %r is not %r" % (what, magic, magic_want))
     if version != VERSION:
-        raise ValueError("key_frame.dat (huff): format version %d, this build reads version %d" % (version, VERSION))
+        raise ValueError("%s: format version %d, this build reads version %d" % (what, version, VERSION))
     if max_len != huff.MAX_LEN:
-        raise ValueError("key_frame.dat (huff): code length limit L = %d, this build reads L = %d" % (max_len, huff.MAX_LEN))
+        raise ValueError("%s: code length limit L = %d, this build reads L = %d" % (what, max_len, huff.MAX_LEN))
     if run != huff.RUN or chunk_runs != huff.CHUNK_RUNS:
-        raise ValueError("key_frame.dat (huff): run length R = %d / chunk of %d runs, this build reads R = %d / %d"
-                         % (run, chunk_runs, huff.RUN, huff.CHUNK_RUNS))
+        raise ValueError("%s: run length R = %d / chunk of %d runs, this build reads R = %d / %d"
+                         % (what, run, chunk_runs, huff.RUN, huff.CHUNK_RUNS))
     if C != 3:
-        raise ValueError("key_frame.dat (huff): channel count C = %d, this build reads C = 3" % C)
+        raise ValueError("%s: channel count C = %d, this build reads C = 3" % (what, C))
     if not (1 <= nt <= MAX_FRAMES and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise ValueError("key_frame.dat (huff): stack shape nt = %d, H = %d, W = %d outside [1, %d] x [1, %d]^2" % (nt, H, W, MAX_FRAMES, MAX_SIDE))
+        raise ValueError("%s: stack shape nt = %d, H = %d, W = %d outside [1, %d] x [1, %d]^2" % (what, nt, H, W, MAX_FRAMES, MAX_SIDE))
     if not 1 <= nkeys <= nt:
-        raise ValueError("key_frame.dat (huff): nkeys = %d outside [1, nt = %d]" % (nkeys, nt))
-    n = nkeys * H * W * 3
+        raise ValueError("%s: nkeys = %d outside [1, nt = %d]" % (what, nkeys, nt))
+    o_pred = HEADER.size + nkeys * 4
+    o_len = o_pred + _pad4(nkeys)
+    return buf, nt, H, W, nkeys, run, chunk_runs, nchunks, stream_words, o_pred, o_len, o_len + 256
+
+
+def parse_keys(what, p, buf, nt, nkeys, o_pred):
+    """p.idx and p.pred: the key indices, strictly ascending inside [0, nt), and the bytes behind them (not yet checked)."""
+    p.idx = buf[HEADER.size: o_pred].view("<u4")
+    ix = p.idx.astype(np.int64)
+    if (np.diff(ix) <= 0).any() or ix[-1] >= nt:
+        raise ValueError("%s: key indices are not strictly ascending inside [0, nt = %d)" % (what, nt))
+    p.pred = buf[o_pred: o_pred + nkeys]
+
+
+def parse_stream(what, p, buf, o_co, n, run, chunk_runs, nchunks, stream_words, frames):
+    """Everything that depends on the symbol count n: the chunk count (`frames` words the message), the file's size, the code
+    lengths in front of o_co, and the index | bits from there on."""
     nruns, want_chunks = huff.geometry(n, run, chunk_runs)
     if nchunks != want_chunks:
-        raise ValueError("key_frame.dat (huff): nchunks = %d, %d key frames of %d x %d make %d chunks" % (nchunks, nkeys, H, W, want_chunks))
-    o_idx = HEADER.size
-    o_pred = o_idx + nkeys * 4
-    o_len = o_pred + _pad4(nkeys)
-    o_co = o_len + 256
+        raise ValueError("%s: nchunks = %d, %s make %d chunks" % (what, nchunks, frames, want_chunks))
     o_runs = o_co + nchunks * 4
     o_bits = o_runs + _pad4(nruns * 2)
     total = o_bits + stream_words * 4
     if buf.size != total:
-        raise ValueError("key_frame.dat (huff): file size %d, the header describes %d bytes (truncated or corrupt file)" % (buf.size, total))
-    p = Parsed()
-    p.nt, p.H, p.W, p.nkeys, p.n, p.run, p.nchunks, p.nruns, p.stream_words = nt, H, W, nkeys, n, run, nchunks, nruns, stream_words
-    p.idx = buf[o_idx: o_pred].view("<u4")
-    ix = p.idx.astype(np.int64)
-    if (np.diff(ix) <= 0).any() or ix[-1] >= nt:
-        raise ValueError("key_frame.dat (huff): key indices are not strictly ascending inside [0, nt = %d)" % nt)
-    p.pred = buf[o_pred: o_pred + nkeys]
-    if int(p.pred.max()) >= NPRED:
-        raise ValueError("key_frame.dat (huff): predictor id %d outside [0, 3]" % int(p.pred.max()))
-    p.lengths = buf[o_len: o_co]
+        raise ValueError("%s: file size %d, the header describes %d bytes (truncated or corrupt file)" % (what, buf.size, total))
+    p.n, p.run, p.nchunks, p.nruns, p.stream_words = n, run, nchunks, nruns, stream_words
+    p.lengths = buf[o_co - 256: o_co]
+    p.chunk_off = buf[o_co: o_runs].view("<u4")
+    p.run_bits = buf[o_runs: o_runs + nruns * 2].view("<u2")
+    p.words = buf[o_bits: total].view("<u4")
+    p.body = buf[o_co: total]                       # index | bits: what tz_keys_put / tz_keysg_put stages
+
+
+def check_stream(what, p):
+    """The code lengths and the index of a parsed file."""
     try:
         huff.check_lengths(p.lengths)
     except ValueError as e:
         raise ValueError(str(e).replace("entropy.dat", "key_frame.dat")) from None
-    p.chunk_off = buf[o_co: o_runs].view("<u4")
-    p.run_bits = buf[o_runs: o_runs + nruns * 2].view("<u2")
-    p.words = buf[o_bits: total].view("<u4")
-    p.body = buf[o_co: total]                       # index | bits: what tz_keys_put stages
-    co = p.chunk_off.astype(np.int64)
-    if co[0] != 0 or (np.diff(co) < 0).any() or co[-1] > stream_words:
-        raise ValueError("key_frame.dat (huff): chunk offset table is not ascending from 0 inside the %d words of the bit stream" % stream_words)
-    rb = p.run_bits.astype(np.int64)
-    if (rb > run * huff.MAX_LEN).any():
-        raise ValueError("key_frame.dat (huff): a run length of %d bits exceeds R * L = %d" % (int(rb.max()), run * huff.MAX_LEN))
-    per_chunk = np.add.reduceat(rb, np.arange(0, nruns, chunk_runs))
-    room = (np.concatenate([co[1:], [stream_words]]) - co) * 32
-    if (per_chunk > room).any():
-        c = int(np.nonzero(per_chunk > room)[0][0])
-        raise ValueError("key_frame.dat (huff): the run lengths of chunk %d sum to %d bits, the chunk has %d" % (c, int(per_chunk[c]), int(room[c])))
+    huff.check_index(what, p.chunk_off, p.run_bits, p.stream_words, p.run, huff.CHUNK_RUNS, "ascending from 0")
+
+
+def parse(data):
+    """Validate a TZK1 key_frame.dat (bytes / uint8 array) -> Parsed.  Everything a pointer or a launch will be derived
+    from is checked here, on the CPU; a failure is a ValueError that names the field."""
+    what = "key_frame.dat (huff)"
+    buf, nt, H, W, nkeys, run, chunk_runs, nchunks, stream_words, o_pred, o_len, o_co = parse_header(what, MAGIC, data)
+    p = Parsed()
+    p.nt, p.H, p.W, p.nkeys = nt, H, W, nkeys
+    parse_stream(what, p, buf, o_co, nkeys * H * W * 3, run, chunk_runs, nchunks, stream_words, "%d key frames of %d x %d" % (nkeys, H, W))
+    parse_keys(what, p, buf, nt, nkeys, o_pred)
+    if int(p.pred.max()) >= NPRED:
+        raise ValueError("%s: predictor id %d outside [0, 3]" % (what, int(p.pred.max())))
+    check_stream(what, p)
     return p
 
 

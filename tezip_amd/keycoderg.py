@@ -130,18 +130,7 @@ def pack_front(nt, H, W, idx, predg, lengths, nchunks, stream_words):
 def encode_file(stack_or_keyframes, idx, nt):
     """The whole key_frame.dat on the CPU (tests, and the specification of compress.run's output).  The first argument is
     the (nt, H, W, 3) stack, of which the frames `idx` are coded, or the (len(idx), H, W, 3) key frames themselves."""
-    x = np.asarray(stack_or_keyframes, np.uint8)
-    idx = np.asarray(idx, np.int64).reshape(-1)
-    if x.ndim != 4 or x.shape[3] != 3:
-        raise ValueError("key frames must be a (k, H, W, 3) uint8 stack, got shape %r" % (tuple(x.shape),))
-    if idx.size < 1 or (np.diff(idx) <= 0).any() or idx[0] < 0 or idx[-1] >= nt:
-        raise ValueError("key_frame.dat (huffg): key indices must be strictly ascending inside [0, %d)" % nt)
-    if x.shape[0] == nt:
-        kf = x[idx]
-    elif x.shape[0] == idx.size:
-        kf = x
-    else:
-        raise ValueError("%d frames given for %d key indices of a %d-frame sequence" % (x.shape[0], idx.size, nt))
+    kf, idx = keycoder.key_frames_of("key_frame.dat (huffg)", stack_or_keyframes, idx, nt)
     H, W = kf.shape[1:3]
     gray = gray_flags(kf)
     counts = gray_counts(keycoder.predictor_counts(kf), gray)
@@ -158,72 +147,21 @@ class Parsed:
 def parse(data):
     """Validate a TZK2 key_frame.dat (bytes / uint8 array) -> Parsed.  Everything a pointer or a launch will be derived
     from is checked here, on the CPU; a failure is a ValueError that names the field."""
-    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1)
-    if buf.size < HEADER.size:
-        raise ValueError("key_frame.dat (huffg): file size %d is shorter than the %d-byte header (truncated)" % (buf.size, HEADER.size))
-    magic, version, max_len, nt, H, W, C, nkeys, run, chunk_runs, nchunks, stream_words, _ = HEADER.unpack(buf[:HEADER.size].tobytes())
-    if magic != MAGIC:
-        raise ValueError("key_frame.dat (huffg): magic %r is not %r" % (magic, MAGIC))
-    if version != VERSION:
-        raise ValueError("key_frame.dat (huffg): format version %d, this build reads version %d" % (version, VERSION))
-    if max_len != huff.MAX_LEN:
-        raise ValueError("key_frame.dat (huffg): code length limit L = %d, this build reads L = %d" % (max_len, huff.MAX_LEN))
-    if run != huff.RUN or chunk_runs != huff.CHUNK_RUNS:
-        raise ValueError("key_frame.dat (huffg): run length R = %d / chunk of %d runs, this build reads R = %d / %d"
-                         % (run, chunk_runs, huff.RUN, huff.CHUNK_RUNS))
-    if C != 3:
-        raise ValueError("key_frame.dat (huffg): channel count C = %d, this build reads C = 3" % C)
-    if not (1 <= nt <= MAX_FRAMES and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise ValueError("key_frame.dat (huffg): stack shape nt = %d, H = %d, W = %d outside [1, %d] x [1, %d]^2" % (nt, H, W, MAX_FRAMES, MAX_SIDE))
-    if not 1 <= nkeys <= nt:
-        raise ValueError("key_frame.dat (huffg): nkeys = %d outside [1, nt = %d]" % (nkeys, nt))
+    what = "key_frame.dat (huffg)"
+    buf, nt, H, W, nkeys, run, chunk_runs, nchunks, stream_words, o_pred, o_len, o_co = keycoder.parse_header(what, MAGIC, data)
     # the pred bytes come before anything that depends on n: n is a function of their GRAY bits
-    o_idx = HEADER.size
-    o_pred = o_idx + nkeys * 4
-    o_len = o_pred + _pad4(nkeys)
-    o_co = o_len + 256
     if buf.size < o_co:
-        raise ValueError("key_frame.dat (huffg): file size %d is shorter than the %d bytes in front of the index (truncated)" % (buf.size, o_co))
+        raise ValueError("%s: file size %d is shorter than the %d bytes in front of the index (truncated)" % (what, buf.size, o_co))
     p = Parsed()
-    p.idx = buf[o_idx: o_pred].view("<u4")
-    ix = p.idx.astype(np.int64)
-    if (np.diff(ix) <= 0).any() or ix[-1] >= nt:
-        raise ValueError("key_frame.dat (huffg): key indices are not strictly ascending inside [0, nt = %d)" % nt)
-    p.pred = buf[o_pred: o_pred + nkeys]
+    p.nt, p.H, p.W, p.nkeys = nt, H, W, nkeys
+    keycoder.parse_keys(what, p, buf, nt, nkeys, o_pred)
     if int(p.pred.max()) >= 2 * GRAY:
-        raise ValueError("key_frame.dat (huffg): pred byte %d outside [0, 7]" % int(p.pred.max()))
+        raise ValueError("%s: pred byte %d outside [0, 7]" % (what, int(p.pred.max())))
     p.gray = (p.pred & GRAY) != 0
     p.offsets, n = offsets(p.gray, H, W)
-    nruns, want_chunks = huff.geometry(n, run, chunk_runs)
-    if nchunks != want_chunks:
-        raise ValueError("key_frame.dat (huffg): nchunks = %d, %d key frames of %d x %d (%d of them gray) make %d chunks"
-                         % (nchunks, nkeys, H, W, int(p.gray.sum()), want_chunks))
-    o_runs = o_co + nchunks * 4
-    o_bits = o_runs + _pad4(nruns * 2)
-    total = o_bits + stream_words * 4
-    if buf.size != total:
-        raise ValueError("key_frame.dat (huffg): file size %d, the header describes %d bytes (truncated or corrupt file)" % (buf.size, total))
-    p.nt, p.H, p.W, p.nkeys, p.n, p.run, p.nchunks, p.nruns, p.stream_words = nt, H, W, nkeys, n, run, nchunks, nruns, stream_words
-    p.lengths = buf[o_len: o_co]
-    try:
-        huff.check_lengths(p.lengths)
-    except ValueError as e:
-        raise ValueError(str(e).replace("entropy.dat", "key_frame.dat")) from None
-    p.chunk_off = buf[o_co: o_runs].view("<u4")
-    p.run_bits = buf[o_runs: o_runs + nruns * 2].view("<u2")
-    p.words = buf[o_bits: total].view("<u4")
-    p.body = buf[o_co: total]                       # index | bits: what tz_keysg_put stages
-    co = p.chunk_off.astype(np.int64)
-    if co[0] != 0 or (np.diff(co) < 0).any() or co[-1] > stream_words:
-        raise ValueError("key_frame.dat (huffg): chunk offset table is not ascending from 0 inside the %d words of the bit stream" % stream_words)
-    rb = p.run_bits.astype(np.int64)
-    if (rb > run * huff.MAX_LEN).any():
-        raise ValueError("key_frame.dat (huffg): a run length of %d bits exceeds R * L = %d" % (int(rb.max()), run * huff.MAX_LEN))
-    per_chunk = np.add.reduceat(rb, np.arange(0, nruns, chunk_runs))
-    room = (np.concatenate([co[1:], [stream_words]]) - co) * 32
-    if (per_chunk > room).any():
-        c = int(np.nonzero(per_chunk > room)[0][0])
-        raise ValueError("key_frame.dat (huffg): the run lengths of chunk %d sum to %d bits, the chunk has %d" % (c, int(per_chunk[c]), int(room[c])))
+    keycoder.parse_stream(what, p, buf, o_co, n, run, chunk_runs, nchunks, stream_words,
+                          "%d key frames of %d x %d (%d of them gray)" % (nkeys, H, W, int(p.gray.sum())))
+    keycoder.check_stream(what, p)
     return p
 
 
