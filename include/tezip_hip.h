@@ -15,7 +15,9 @@
  *  - One context per GPU/process; a context is not thread-safe; contexts are independent.
  *  - Frames are HWC, 3 channels; "padded" means H,W rounded up to a multiple of 8
  *    (data_utils.py:77-107) with pitch Wp*3.
- *  - All integer streams are int16, C-order over (frame, y, x, channel) (compress.py:329-340).
+ *  - All integer streams are int16, C-order over (frame, y, x, channel) (compress.py:329-340).  The one exception is opt-in:
+ *    under tz_set_payload_channels(ctx, 1) the PAYLOAD holds channel 0 alone, nt*H*W elements over (frame, y, x), wherever
+ *    a comment below says nt*H*W*3 of it; frames keep three channels.
  */
 #ifndef TEZIP_HIP_H
 #define TEZIP_HIP_H
@@ -179,6 +181,24 @@ int tz_get_predictions(tz_ctx* ctx, float* out);
  * that instead. */
 int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* payload,
               int16_t* table, int* table_len, int16_t* delta_out);
+/* Opt-in one-channel payload of a gray job (no reference counterpart: compress.py:114 widens a single-channel source to RGB and
+ * the payload carries every delta three times; `tezip.py -c --gray`, format in DESIGN.md section 9, slow statement of it in
+ * tezip_amd/graypayload.py).  channels: 3 (the default: every entry point does exactly what it does without this call) or 1;
+ * anything else is TZ_ERR_INVALID.  tz_get_payload_channels returns the value in force.  With 1:
+ *  - tz_encode first checks that EVERY frame of the resident stack is gray (three equal channels at every pixel, k_key_gray)
+ *    and returns TZ_ERR_INVALID naming the first frame that is not: the library never drops colour.  The quantiser runs per
+ *    frame and channel (compress.py:316-319) and the decoder's predictions depend on the key frames alone
+ *    (decompress.py:143-175), so channel 0 of the quantised delta stack reconstructs channel 0 within the bound, and the
+ *    other two channels, whose originals equal channel 0, get the same sample and the same error.  The payload holds the
+ *    nt*H*W elements of finding_difference (compress.py:73-77) over channel 0 alone, the rank table is built from their
+ *    histogram; payload == NULL, the deferred hand-over and the shuffle bit (nt*H*W a multiple of 8) work as with 3.  A
+ *    non-NULL delta_out is TZ_ERR_INVALID.
+ *  - tz_decode, tz_decode_range, tz_encode_quality and tz_encode_digests take payload_len == nt*H*W and still yield frames of
+ *    H*W*3 bytes, the decoded sample written to all three channels; tz_undelta_carry serves a range with n0 = first*H*W.
+ *  - tz_encode_begin, tz_encode_finish, tz_encode_delta and tz_decode_delta return TZ_ERR_UNSUPPORTED (sharded gray jobs are
+ *    out of scope).  tz_huff_* / tz_huffr_* code whatever the resident payload holds. */
+int tz_set_payload_channels(tz_ctx* ctx, int channels);
+int tz_get_payload_channels(tz_ctx* ctx);
 /* Streaming delivery: tz_encode with payload == NULL keeps the payload in the context; it is then
  * fetched in pieces of `count` int16 elements starting at `offset` (compress.py:375-400 appends and
  * compresses one monolithic array). */
@@ -354,6 +374,18 @@ int tz_spatial_undelta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, 
  * the key byte (key_frames), else trunc(pred*255). */
 int tz_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key_frames, const uint8_t* key_mask,
                    const int16_t* diff, int nframes, int H, int W, uint8_t* out);
+/* The two kernels of the one-channel payload (tz_set_payload_channels), stand-alone.
+ * tz_spatial_delta_gray: tz_spatial_delta over channel 0 of an interleaved 3-channel int16 stack.  in3: npix*3 elements in
+ * (frame, y, x, 3) order; out: npix elements, out[0] = in3[0] (or carry - in3[0]), out[i] = in3[3(i-1)] - in3[3i], then
+ * 1600 - x when apply_offset; channels 1 and 2 are never read.  hist as tz_spatial_delta's (symbols outside [0, TZ_NBINS)
+ * are not counted). */
+int tz_spatial_delta_gray(tz_ctx* ctx, const int16_t* in3, size_t npix, int has_carry, int16_t carry, int apply_offset,
+                          int16_t* out, unsigned long long* hist);
+/* tz_reconstruct_gray: tz_reconstruct from ONE int16 delta per pixel (diff1: nframes*H*W): base = the key byte of channel 0
+ * where key_mask says so, else trunc(pred channel 0 * 255); v = clamp(base - d, 0, 255) goes to all three channels of out
+ * (nframes*H*W*3).  pred, key_frames: the 3-channel stacks tz_reconstruct takes. */
+int tz_reconstruct_gray(tz_ctx* ctx, const float* pred, const uint8_t* key_frames, const uint8_t* key_mask,
+                        const int16_t* diff1, int nframes, int H, int W, uint8_t* out);
 /* tz_window_sse: the inner sum of compress.py:246 for nframes (sum over the padded frame of
  * (x/255 - pred)^2 in float64, fixed summation order). sse: nframes doubles (host). */
 int tz_window_sse(tz_ctx* ctx, const uint8_t* orig, const float* pred, int nframes, int H, int W, double* sse);

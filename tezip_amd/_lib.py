@@ -67,6 +67,11 @@ _SIGS = {
     "tz_decoded_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_payload_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
     "tz_set_payload_deferred": (C.c_int, [C.c_void_p, C.c_int]),
+    "tz_set_payload_channels": (C.c_int, [C.c_void_p, C.c_int]),
+    "tz_get_payload_channels": (C.c_int, [C.c_void_p]),
+    "tz_spatial_delta_gray": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int16, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_reconstruct_gray": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p]),
     "tz_payload_wait": (C.c_int, [C.c_void_p]),
     "tz_get_predictions": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tz_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
@@ -337,6 +342,7 @@ class Context:
         if rc != TZ_OK:
             raise TezipError(rc, self.lib.tz_strerror(rc).decode() + " (tz_ctx_create; a MI355X is required)")
         self.h = h
+        self.channels = 3
 
     def close(self):
         if getattr(self, "h", None):
@@ -539,7 +545,7 @@ class Context:
         device buffer of nt*H*W*3 int16): also return the quantised delta stack."""
         nt, h, w = self._shape
         b0, b1 = _bounds(bound)
-        payload = _payload_out(payload, nt * h * w * 3)
+        payload = _payload_out(payload, nt * h * w * self.channels)
         table = np.zeros(TZ_MAX_TABLE, np.int16)
         tlen = C.c_int(0)
         delta = delta_out if delta_out is not None else (np.empty((nt, h, w, 3), np.int16) if want_delta else None)
@@ -549,6 +555,16 @@ class Context:
                                     C.byref(tlen), _ptr(delta)))
         t = table[: tlen.value].copy() if tlen.value >= 0 else None
         return payload, t, delta
+
+    def set_payload_channels(self, channels):
+        """tz_set_payload_channels: 3 (the default) or 1 = the one-channel payload of a gray job (tezip_amd/graypayload.py):
+        encode then refuses a stack with colour and yields nt*H*W elements, decode / decode_range / encode_quality /
+        encode_digests take as many and still yield 3-channel frames."""
+        self._ck(self.lib.tz_set_payload_channels(self.h, int(channels)))
+        self.channels = int(channels)
+
+    def get_payload_channels(self):
+        return int(self.lib.tz_get_payload_channels(self.h))
 
     def set_payload_deferred(self, on=True):
         """tz_set_payload_deferred: encode(payload=<pinned host buffer>) returns with the device -> host transfer of
@@ -604,7 +620,7 @@ class Context:
         """payload None: the pieces staged with payload_begin / payload_put.  out="resident": the
         frames stay in the context (decoded_get)."""
         nt, h, w = self._shape
-        n = nt * h * w * 3
+        n = nt * h * w * self.channels
         if payload is not None and _numel(payload) != n:  # decompress.py:240: the reference's reshape raises
             raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
         resident = isinstance(out, str) and out == "resident"
@@ -621,7 +637,7 @@ class Context:
         """tz_decode_range: frames [first, first + count) after rollout_decode_range.  payload: the WHOLE stream (or None
         after payload_begin / payload_put); out="resident" keeps the frames for decoded_get (sequence indices)."""
         nt, h, w = self._shape
-        n = nt * h * w * 3
+        n = nt * h * w * self.channels
         if payload is not None and _numel(payload) != n:  # decompress.py:240: the reference's reshape raises
             raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
         resident = isinstance(out, str) and out == "resident"
@@ -641,7 +657,7 @@ class Context:
         encode(..., payload="resident")) or a host / device buffer of nt*H*W*3 int16; table: the encode's table (None:
         no remap); shuffle: the payload holds byte planes."""
         nt, h, w = self._shape
-        n = nt * h * w * 3
+        n = nt * h * w * self.channels
         resident = isinstance(payload, str) and payload == "resident"
         if not resident and _numel(payload) != n:
             raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
@@ -657,7 +673,7 @@ class Context:
         """tz_encode_digests after rollout + encode, arguments as encode_quality's -> (decoded, original): uint64[nt] each,
         the digests of what the payload decodes to and of the resident source frames (None with original=False)."""
         nt, h, w = self._shape
-        n = nt * h * w * 3
+        n = nt * h * w * self.channels
         resident = isinstance(payload, str) and payload == "resident"
         if not resident and _numel(payload) != n:
             raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
@@ -979,6 +995,27 @@ class Context:
         if out is None:
             out = np.empty(n, np.int16)
         self._ck(self.lib.tz_spatial_undelta(self.h, _ptr(x), n, int(carry is not None), int(carry or 0), _ptr(out)))
+        return out
+
+    def spatial_delta_gray(self, x3, offset, carry=None, hist=None, out=None):
+        """tz_spatial_delta_gray: spatial_delta over channel 0 of the interleaved int16 stack x3 (npix * 3 elements, host or
+        device) -> npix elements."""
+        npix = _numel(x3) // 3
+        if _numel(x3) != npix * 3:
+            raise ValueError("%d elements are not whole 3-channel pixels" % _numel(x3))
+        if out is None:
+            out = np.empty(npix, np.int16)
+        self._ck(self.lib.tz_spatial_delta_gray(self.h, _ptr(x3), npix, int(carry is not None), int(carry or 0), int(offset),
+                                                _ptr(out), _ptr(hist)))
+        return out
+
+    def reconstruct_gray(self, pred, key_frames, key_mask, diff1, out=None):
+        """tz_reconstruct_gray: diff1 (n, H, W) holds one int16 delta per pixel; -> (n, H, W, 3) uint8, three equal channels."""
+        n, h, w = diff1.shape[:3]
+        if out is None:
+            out = np.empty((n, h, w, 3), np.uint8)
+        km = None if key_mask is None else np.ascontiguousarray(key_mask, np.uint8)
+        self._ck(self.lib.tz_reconstruct_gray(self.h, _ptr(pred), _ptr(key_frames), _ptr(km), _ptr(diff1), n, h, w, _ptr(out)))
         return out
 
     def reconstruct(self, pred, key_frames, key_mask, diff, out=None):

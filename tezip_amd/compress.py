@@ -7,6 +7,8 @@ Output directory:
   key_frame.dat  zstd-9 of uint8[nt*H*W*3], zero except key frames           (compress.py:271-278)
   entropy.dat    zstd-9 of int16: payload | table | T  (or | -1) | 1,nt,H,W,3 | warm_up
                                                                               (compress.py:381-400)
+                 with GRAY (--gray; not a reference format) on a job whose frames are all gray: the payload holds channel 0
+                 alone, nt*H*W elements, and the shape in the trailer ends in 1 (tezip_amd/graypayload.py)
                  with CODER="huff" (--coder huff; not a reference format): "TZH1" header | that trailer | code lengths |
                  index | bit stream, written by the GPU (tezip_amd/huff.py); with CODER="huffr" the
                  same under the magic "TZR1", the code being over literals and period-3 repeat tokens (tezip_amd/huffr.py)
@@ -248,6 +250,27 @@ def check_coder(coder, shuffle=False, sharded=False):
     return None
 
 
+def check_gray(gray, sharded=False):
+    """The refusal of --gray that a direct caller of run() can meet (tezip.py knows the others): None, or the message."""
+    if gray and sharded:
+        return "--gray is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+    return None
+
+
+def decide_gray(ctx, nt, files):
+    """--gray after the frames are staged: one read of the resident stack says whether every frame is gray (tz_keys_gray over all
+    of them).  Yes: the context is set to the one-channel payload and 1 is returned.  No: 3, and nothing changes -- the flag
+    never fails a job and never loses information."""
+    gray = ctx.keys_gray(range(nt))
+    if gray.all():
+        ctx.set_payload_channels(1)
+        print("gray: yes, payload stores 1 of 3 channels")
+        return 1
+    i = int(np.nonzero(~gray)[0][0])
+    print("gray: no (frame %d %s has colour), payload keeps three channels" % (i, files[i]))
+    return 3
+
+
 KEY_CODERS = ("zstd", "huff", "huffg")
 
 
@@ -335,10 +358,12 @@ def _huff_entropy_file(ctx, path, n, trailer, verbose, coder="huff"):
 
 
 def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False,
-                    key_coder="zstd"):
+                    key_coder="zstd", channels=3):
     """key_frame.dat and entropy.dat (compress.py:271-278, 375-400) from the context-resident frames
-    and payload, piece by piece: nothing of size nt*H*W lives on the host."""
-    n = nt * H * W * 3
+    and payload, piece by piece: nothing of size nt*H*W lives on the host.  channels: what the resident payload stores per
+    pixel (1: a gray job, tezip_amd/graypayload.py); key_frame.dat has three either way."""
+    n_key = nt * H * W * 3
+    n = nt * H * W * channels
     key_idx = [int(i) for i in np.nonzero(key)[0]]
     zero = np.zeros((H, W, 3), np.uint8)
     if key_coder in ("huff", "huffg"):
@@ -356,7 +381,7 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
         def key_file():
             t0 = time.perf_counter()
             with open(os.path.join(out_dir, "key_frame.dat"), mode='wb') as f:
-                sc = zstd.StreamCompressor(f, n, 9, max(1, zstd.default_threads() // 4))
+                sc = zstd.StreamCompressor(f, n_key, 9, max(1, zstd.default_threads() // 4))
                 for i in range(nt):
                     sc.write(key_frames.get(i, zero))
                 size = sc.close()
@@ -370,7 +395,7 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
         # frames_get, written before entropy.dat -- host memory stays independent of the number of frames
         is_key = set(key_idx)
         with open(os.path.join(out_dir, "key_frame.dat"), mode='wb') as f:
-            sc = zstd.StreamCompressor(f, n, 9, zstd.default_threads())
+            sc = zstd.StreamCompressor(f, n_key, 9, zstd.default_threads())
             for i in range(nt):
                 sc.write(ctx.frames_get(i, 1)[0] if i in is_key else zero)
             ksize = sc.close()
@@ -379,7 +404,7 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
         tail = np.concatenate([table.astype(np.int64), [len(table)]])
     else:
         tail = np.array([-1], dtype=np.int64)
-    trailer = np.concatenate([tail, [SHUFFLE_MARK if shuffled else 1, nt, H, W, 3], [warm_up]]).astype(np.int16)
+    trailer = np.concatenate([tail, [SHUFFLE_MARK if shuffled else 1, nt, H, W, channels], [warm_up]]).astype(np.int16)
     t_e = time.perf_counter()
     if coder in ("huff", "huffr"):
         esize = _huff_entropy_file(ctx, os.path.join(out_dir, "entropy.dat"), n, trailer, verbose, coder)
@@ -427,7 +452,7 @@ def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
 
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
-        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False):
+        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -446,6 +471,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     of what the stored payload decodes to and of the source frame, both taken on the device (tz_encode_digests); `-u`
     verifies its frames against them before it writes an image.  The other files are byte for byte what they are without
     it; the file is written last.  Single-GPU jobs only.
+    GRAY (--gray; NOT in the reference): when every frame of the job is gray (three equal channels: a single-channel source
+    widened to RGB), entropy.dat stores one payload channel instead of three (tezip_amd/graypayload.py) -- such a file is
+    not readable by the reference, `-u` recognises it by the shape in its trailer.  Decided after the frames are staged; a job
+    with colour writes exactly the files it writes without the flag.  Works with every CODER, KEY_CODER, SHUFFLE, REPORT and
+    DIGESTS.  Single-GPU jobs only.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -454,7 +484,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if not GPU_FLAG:
         print("ERROR: this build runs the compression path on an AMD MI355X only (no CPU path).")
         exit()
-    problem = check_coder(CODER, SHUFFLE, tzdist.active() is not None) or check_key_coder(KEY_CODER, tzdist.active() is not None)
+    problem = (check_coder(CODER, SHUFFLE, tzdist.active() is not None) or check_key_coder(KEY_CODER, tzdist.active() is not None)
+               or check_gray(GRAY, tzdist.active() is not None))
     if problem:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         print("ERROR:", problem)
         sys.exit(2)
@@ -490,6 +521,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             for f0, view in chunks:
                 ctx.frames_put(f0, view)   # pageable ring buffer: free again when the call returns
             stages.mark("remaining windows decoded + staged", ctx)
+            channels = 3
+            if GRAY:
+                channels = decide_gray(ctx, nt, src.files)
+                stages.mark("gray check (device)")
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
@@ -525,8 +560,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     print("table_create:{0}".format(prof["table_create"][0] / 1e3) + "[sec]")
                     print("replacing_based_on_frequency:{0}".format(prof["lut_remap"][0] / 1e3) + "[sec]")
             _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
-                            coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER)
-            doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS))   # the contract the predictions were made under
+                            coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels)
+            doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),   # the contract the predictions were made under
+                                payload_channels=channels)
             if VERBOSE:
                 print("arithmetic contract:", doc["arithmetic_contract"])
             stages.mark("key_frame.dat + entropy.dat")

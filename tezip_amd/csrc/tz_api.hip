@@ -1597,12 +1597,74 @@ static int encode_tail(tz_ctx* ctx, int16_t* d_sym, size_t N, const int16_t* car
     return tz_dev_out_finish(ctx, outs);
 }
 
+// ---- one-channel payload of a gray job (include/tezip_hip.h: tz_set_payload_channels)
+extern "C" int tz_set_payload_channels(tz_ctx* ctx, int channels) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (channels != 1 && channels != 3) return tz_fail(ctx, TZ_ERR_INVALID, "payload channels must be 3 or 1, not %d", channels);
+    if (channels != ctx->payload_channels) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made for the other count
+    ctx->payload_channels = channels;
+    return TZ_OK;
+}
+
+extern "C" int tz_get_payload_channels(tz_ctx* ctx) { return ctx ? ctx->payload_channels : TZ_ERR_INVALID; }
+
+// the entry points of the sharded encoder / decoder do not serve a one-channel payload
+static int gray_unsupported(tz_ctx* ctx, const char* who) {
+    if (ctx->payload_channels == 1)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve a one-channel payload (tz_set_payload_channels(1)): sharded gray jobs are not supported", who);
+    return TZ_OK;
+}
+
+static int keys_upload(tz_ctx* ctx, const int* idx, const uint8_t* pred, int nkeys, const int** d_idx, const uint8_t** d_pred);
+
+// TZ_ERR_INVALID naming the first frame of the resident stack that has a pixel with unequal channels (k_key_gray over all frames)
+static int encode_all_gray(tz_ctx* ctx) {
+    const int nt = ctx->nt;
+    std::vector<int> idx(nt);
+    for (int i = 0; i < nt; ++i) idx[i] = i;
+    std::vector<unsigned> flags(nt);
+    const int* d_idx = nullptr;
+    const uint8_t* d_pred = nullptr;
+    void* d_flags;
+    TZ_TRY(keys_upload(ctx, idx.data(), nullptr, nt, &d_idx, &d_pred));
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(unsigned) * nt, &d_flags));
+    TZ_TRY(tzk_key_gray(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, nt, (unsigned*)d_flags));
+    TZ_TRY(tz_d2h(ctx, flags.data(), d_flags, sizeof(unsigned) * nt, ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
+    for (int i = 0; i < nt; ++i)
+        if (flags[i]) return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode: frame %d has colour, a one-channel payload would drop it", i);
+    return TZ_OK;
+}
+
+// encode_front for a one-channel payload: the unfused path over the three-channel stack (delta, quantiser -- which also walks
+// channels 1 and 2, whose output is dropped), then the spatial delta of channel 0 alone; d_sym receives nt*H*W elements.
+static int encode_front_gray(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* d_sym, unsigned long long* d_hist,
+                             int16_t* d_edge) {
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
+    const size_t n1 = (size_t)nt * H * W;
+    void *d_mask = nullptr, *d_delta = nullptr;
+    TZ_TRY(tz_pool_alloc(ctx, nt, &d_mask));
+    TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
+    if (entropy) TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, TZ_NBINS * sizeof(unsigned long long), ctx->stream));
+    TZ_TRY(tz_pool_alloc(ctx, n1 * 3 * 2, &d_delta));
+    TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta));
+    TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_delta, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
+    return tzk_spatial_delta_gray(ctx, (const int16_t*)d_delta, n1, 0, 0, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge);
+}
+
 extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* payload, int16_t* table,
                          int* table_len, int16_t* delta_out) {
     tz_roctx_range roctx_("tz_encode");
     if (!ctx || !table_len || ((entropy & 1) && !table)) return TZ_ERR_INVALID;
     TZ_TRY(encode_check(ctx, "tz_encode", mode));
-    const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
+    const bool gray = ctx->payload_channels == 1;
+    if (gray) {
+        if (delta_out) return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode: no delta_out with a one-channel payload");
+        const int rc_gray = encode_all_gray(ctx);
+        tz_pool_release_all(ctx);
+        TZ_TRY(rc_gray);
+    }
+    const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * ctx->payload_channels;
     const bool shuffle = (entropy & 2) != 0;  // opt-in byte planes (not a reference format)
     entropy &= 1;
     if (shuffle && (N & 7)) return tz_fail(ctx, TZ_ERR_INVALID, "byte shuffle needs a multiple of 8 elements");
@@ -1647,7 +1709,9 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
         if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N * 2, &d_sd);
     }
     int16_t* d_sym = entropy ? (int16_t*)d_sd : (int16_t*)o->dev;   // without a table the symbols are the payload
-    if (rc == TZ_OK)
+    if (rc == TZ_OK && gray)
+        rc = encode_front_gray(ctx, mode, b0, b1, entropy, d_sym, (unsigned long long*)d_hist, (int16_t*)d_edge);
+    else if (rc == TZ_OK)
         rc = encode_front(ctx, mode, b0, b1, entropy, delta_out ? (int16_t*)o_delta.dev : nullptr, d_sym,
                           (unsigned long long*)d_hist, (int16_t*)d_edge);
     std::vector<int16_t> lut;
@@ -1682,6 +1746,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
                                int16_t* edge) {
     tz_roctx_range roctx_("tz_encode_begin");
     if (!ctx || !edge || (entropy && !hist)) return TZ_ERR_INVALID;
+    TZ_TRY(gray_unsupported(ctx, "tz_encode_begin"));
     TZ_TRY(encode_check(ctx, "tz_encode_begin", mode));
     ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload now receives a shard's symbols
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
@@ -1712,6 +1777,7 @@ extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const
                                 int16_t* payload) {
     tz_roctx_range roctx_("tz_encode_finish");
     if (!ctx) return TZ_ERR_INVALID;
+    TZ_TRY(gray_unsupported(ctx, "tz_encode_finish"));
     if (ctx->enc_kind != tz_ctx::ENC_SYMBOLS) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish needs a tz_encode_begin first");
     if (ctx->enc_entropy != (table_len >= 0) || (table_len > 0 && !table) || table_len > TZ_MAX_TABLE)
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode_finish: table does not match the entropy flag of tz_encode_begin");
@@ -1769,6 +1835,7 @@ extern "C" int tz_byte_unshuffle(tz_ctx* ctx, const uint8_t* in, size_t n, int16
 
 extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int16_t* delta_out) {
     if (!ctx || !delta_out) return TZ_ERR_INVALID;
+    TZ_TRY(gray_unsupported(ctx, "tz_encode_delta"));
     TZ_TRY(encode_check(ctx, "tz_encode_delta", mode));
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
     std::vector<tz_out> outs;
@@ -1783,6 +1850,7 @@ extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int1
 
 extern "C" int tz_decode_delta(tz_ctx* ctx, const int16_t* delta, uint8_t* frames_out) {
     if (!ctx || !delta || !frames_out) return TZ_ERR_INVALID;
+    TZ_TRY(gray_unsupported(ctx, "tz_decode_delta"));
     if (!whole_stack(ctx, tz_ctx::ROLLOUT_DECODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_decode_delta needs a tz_rollout_decode first");
     TZ_TRY(tz_check_pred_contract(ctx, "tz_decode_delta"));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
@@ -1858,7 +1926,10 @@ static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, s
     if (first < r || count < 1 || first >= ctx->pred_end || count > ctx->pred_end - first)
         return tz_fail(ctx, TZ_ERR_INVALID, "frame range [%d, %d + %d) outside the frames [%d, %d) the range rollout covered", first,
                        first, count, r, ctx->pred_end);
-    const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe, n0 = (size_t)first * fe, nr = (size_t)count * fe;
+    // fe: bytes of a decoded frame; pe: payload elements of a frame (H*W of them under tz_set_payload_channels(1))
+    const bool gray = ctx->payload_channels == 1;
+    const size_t fe = (size_t)H * W * 3, pe = gray ? (size_t)H * W : fe, N = (size_t)nt * pe, n0 = (size_t)first * pe,
+                 np = (size_t)count * pe, nr = (size_t)count * fe;
     if (!payload) TZ_TRY(staged_payload(ctx, N, &payload));
     ctx->have_decoded = false;
     if (payload_len != N)  // decompress.py:240: the reshape raises
@@ -1873,7 +1944,7 @@ static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, s
     const void* d_pay = nullptr;
     void* d_mask = nullptr;
     int16_t carry = 0;
-    int rc = tz_dev_in(ctx, payload, n0 * 2 + nr * 2, &d_pay);
+    int rc = tz_dev_in(ctx, payload, n0 * 2 + np * 2, &d_pay);
     if (rc == TZ_OK) rc = tz_dev_out(ctx, frames_out, nr, &o);
     if (rc == TZ_OK) outs.push_back(o);
     if (rc == TZ_OK) rc = tz_pool_alloc(ctx, count, &d_mask);
@@ -1883,8 +1954,8 @@ static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, s
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
     if (rc == TZ_OK && first > 0) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, h_lut, &carry);
     if (rc == TZ_OK)
-        rc = tzk_decode_tail(ctx, (const int16_t*)d_pay + n0, h_lut, 1, first > 0, carry,
-                             ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + n0,
+        rc = (gray ? tzk_decode_tail_gray : tzk_decode_tail)(ctx, (const int16_t*)d_pay + n0, h_lut, 1, first > 0, carry,
+                             ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + (size_t)first * fe,
                              (const uint8_t*)d_mask, count, H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     if (rc == TZ_OK && resident) {   // only a decode whose work is queued leaves frames to fetch
@@ -1924,7 +1995,8 @@ static int encode_decoded(tz_ctx* ctx, const char* who, const int16_t* payload, 
     TZ_TRY(tz_check_pred_contract(ctx, who));
     TZ_TRY(check_table(ctx, table, table_len));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
-    const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe;
+    const bool gray = ctx->payload_channels == 1;
+    const size_t fe = (size_t)H * W * 3, N = (size_t)nt * (gray ? (size_t)H * W : fe);   // N: payload elements
     if (!payload) {
         if (ctx->enc_kind != tz_ctx::ENC_PAYLOAD || !ctx->d_payload || ctx->payload_len != N)
             return tz_fail(ctx, TZ_ERR_STATE, "no resident payload of a tz_encode on this rollout");
@@ -1944,13 +2016,13 @@ static int encode_decoded(tz_ctx* ctx, const char* who, const int16_t* payload, 
     const std::vector<uint8_t> recon = recon_key_mask(ctx->key_mask.data(), nt, ctx->warm_up);
     if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_mask);
     if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, recon.data(), nt);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N, &d_dec);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, (size_t)nt * fe, &d_dec);
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
     if (rc == TZ_OK)   // the launches of tz_decode
-        rc = tzk_decode_tail(ctx, (const int16_t*)d_pay, h_lut, 1, 0, 0, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H,
-                             W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
+        rc = (gray ? tzk_decode_tail_gray : tzk_decode_tail)(ctx, (const int16_t*)d_pay, h_lut, 1, 0, 0, ctx->d_pred, ctx->d_frames,
+                                                             (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
     *d_dec_out = (const uint8_t*)d_dec;
     return rc;
 }
@@ -2182,6 +2254,62 @@ extern "C" int tz_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key
         outs.push_back(o);
         rc = tzk_reconstruct(ctx, (const float*)dp, (const uint8_t*)dk, (const uint8_t*)dm, (const int16_t*)dd, nframes, H,
                              W, Hp, Wp, (uint8_t*)o.dev);
+    }
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_spatial_delta_gray(tz_ctx* ctx, const int16_t* in3, size_t npix, int has_carry, int16_t carry, int apply_offset,
+                                     int16_t* out, unsigned long long* hist) {
+    if (!ctx || !in3 || !out) return TZ_ERR_INVALID;
+    const void* din;
+    tz_out o, oh;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, in3, npix * 3 * 2, &din);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, npix * 2, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    void* dh = nullptr;
+    if (rc == TZ_OK && hist) {
+        rc = tz_dev_out(ctx, hist, TZ_NBINS * sizeof(unsigned long long), &oh);
+        if (rc == TZ_OK) {
+            dh = oh.dev;
+            if (oh.host) {  // counts are ADDED to what the caller holds
+                hipError_t e = hipMemcpyAsync(dh, hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream);
+                if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "hist upload: %s", hipGetErrorString(e));
+            }
+            outs.push_back(oh);
+        }
+    }
+    if (rc == TZ_OK)
+        rc = tzk_spatial_delta_gray(ctx, (const int16_t*)din, npix, has_carry, carry, apply_offset, (int16_t*)o.dev,
+                                    (unsigned long long*)dh, nullptr);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_reconstruct_gray(tz_ctx* ctx, const float* pred, const uint8_t* key_frames, const uint8_t* key_mask,
+                                   const int16_t* diff1, int nframes, int H, int W, uint8_t* out) {
+    if (!ctx || !pred || !diff1 || !out || nframes < 0 || H < 1 || W < 1) return TZ_ERR_INVALID;
+    int Hp = pad8(H), Wp = pad8(W);
+    size_t n1 = (size_t)nframes * H * W;
+    std::vector<uint8_t> km(nframes, 0);
+    if (key_mask && key_frames) memcpy(km.data(), key_mask, nframes);
+    const void *dp, *dk = nullptr, *dd;
+    void* dm;
+    tz_out o;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp);
+    if (rc == TZ_OK && key_frames) rc = tz_dev_in(ctx, key_frames, n1 * 3, &dk);
+    if (rc == TZ_OK) rc = tz_dev_in(ctx, diff1, n1 * 2, &dd);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nframes, &dm);
+    if (rc == TZ_OK && nframes) rc = tz_upload(ctx, dm, km.data(), nframes);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n1 * 3, &o);
+    if (rc == TZ_OK) {
+        outs.push_back(o);
+        rc = tzk_reconstruct_gray(ctx, (const float*)dp, (const uint8_t*)dk, (const uint8_t*)dm, (const int16_t*)dd, nframes, H,
+                                  W, Hp, Wp, (uint8_t*)o.dev);
     }
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     tz_pool_release_all(ctx);

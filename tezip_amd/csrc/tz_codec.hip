@@ -1705,6 +1705,87 @@ int tzk_spatial_delta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, i
     return TZ_OK;
 }
 
+// ------------------------------------------------- spatial delta of channel 0 alone (one-channel payload of a gray job)
+// tz_set_payload_channels(1): finding_difference (compress.py:73-77) over channel 0 of the interleaved (frame, y, x, 3) stack,
+// out[0] = x[0] (or carry - x[0]), out[p] = x[3(p-1)] - x[3p]; then 1600 - y and the histogram as k_sdelta.  Channels 1 and 2
+// are fetched with the cache lines they share with channel 0 and never looked at.
+// Fast form: a lane takes 8 pixels, i.e. 24 elements as three 16-byte loads, picks the 8 channel-0 halves out of the 12
+// dwords, and writes one 16-byte store; the channel-0 element in front of its first pixel is one extra 2-byte load (the cache
+// line of the neighbouring lane).  `head` pixels in front (those up to the first pixel at which in3 AND out are 16-byte
+// aligned; all npix when there is no such pixel) and the npix - head - 8 n8 pixels behind go one by one.
+// edge (may be NULL): edge[0], edge[1] = the first and the last channel-0 element, as encode_front leaves them.
+__device__ __forceinline__ void sdelta_gray1(const int16_t* __restrict__ in, size_t p, int has_carry, int16_t carry, int apply_offset,
+                                             int16_t* __restrict__ out, HistLds* hl) {
+    const short cur = in[3 * p];
+    const short sd = p ? (short)(in[3 * (p - 1)] - cur) : (has_carry ? (short)(carry - cur) : cur);
+    const short y = apply_offset ? (short)(TZ_OFFSET - sd) : sd;
+    out[p] = y;
+    if (hl && y >= 0 && y < TZ_NBINS) atomicAdd(&hl->w[HL_FULL + y], 1u);
+}
+
+template <bool HIST>
+__global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_sdelta_gray(const int16_t* __restrict__ in, size_t npix, size_t head, size_t n8,
+                                                     int has_carry, int16_t carry, int apply_offset, int16_t* __restrict__ out,
+                                                     unsigned long long* __restrict__ hist, int16_t* __restrict__ edge) {
+    __shared__ unsigned hraw[HIST ? HL_WORDS : 1];
+    HistLds& hl = *(HistLds*)hraw;
+    if (HIST) hist_clear(hl);
+    const int centre = apply_offset ? TZ_OFFSET : 0;
+    HistAcc acc;
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint4* in8 = (const uint4*)(in + 3 * head);   // 16-byte aligned when n8 > 0 (tzk_spatial_delta_gray)
+    uint4* out8 = (uint4*)(out + head);
+    const unsigned short* inu = (const unsigned short*)in;
+    for (size_t i = t0; i < n8; i += stride) {
+        const uint4 a = in8[3 * i], b = in8[3 * i + 1], c = in8[3 * i + 2];
+        // elements 0, 3, 6, .. 21 of the 24: the low half of dwords 0, 3, 6, 9 and the high half of dwords 1, 4, 7, 10
+        const uint4 v = make_uint4((a.x & 0xFFFFu) | (a.y & 0xFFFF0000u), (a.w & 0xFFFFu) | (b.x & 0xFFFF0000u),
+                                   (b.z & 0xFFFFu) | (b.w & 0xFFFF0000u), (c.y & 0xFFFFu) | (c.z & 0xFFFF0000u));
+        const size_t p0 = head + 8 * i;   // the lane's first pixel
+        // the channel-0 element in front; without one (start of the stream, no carry) sd[0] = x[0], i.e. "prev" = 2 x[0]
+        const unsigned prev = p0 ? (unsigned)inu[3 * (p0 - 1)] : (has_carry ? (unsigned)(unsigned short)carry : ((v.x << 1) & 0xFFFFu));
+        unsigned Y[4];
+        sdelta8(v, prev, apply_offset != 0, Y);
+        out8[i] = make_uint4(Y[0], Y[1], Y[2], Y[3]);
+        if (HIST) hist_add8(hl, acc, Y, centre);
+    }
+    // the pixels in front of and behind the vector groups
+    const size_t v_end = head + 8 * n8, nscalar = head + (npix - v_end);
+    for (size_t j = t0; j < nscalar; j += stride)
+        sdelta_gray1(in, j < head ? j : v_end + (j - head), has_carry, carry, apply_offset, out, HIST ? &hl : nullptr);
+    if (edge && t0 == 0) {
+        edge[0] = in[0];
+        edge[1] = in[3 * (npix - 1)];
+    }
+    if (HIST) hist_flush(hl, acc, centre, hist);
+}
+
+int tzk_spatial_delta_gray(tz_ctx* ctx, const int16_t* in3, size_t npix, int has_carry, int16_t carry, int apply_offset,
+                           int16_t* out, unsigned long long* d_hist, int16_t* d_edge) {
+    if (npix == 0) return TZ_OK;
+    if (((uintptr_t)in3 | (uintptr_t)out) & 1) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_gray buffers must be 2-byte aligned");
+    // the first pixel h at which both in3 + 3 h and out + h sit on a 16-byte boundary: 6 h = -in3 (mod 16) has one solution
+    // in [0, 8) and so has 2 h = -out; when the two differ nothing can be vectorised
+    size_t head = npix;
+    for (size_t h = 0; h < 8 && h < npix; ++h)
+        if ((((uintptr_t)in3 + 6 * h) & 15) == 0 && (((uintptr_t)out + 2 * h) & 15) == 0) {
+            head = h;
+            break;
+        }
+    const size_t n8 = (npix - head) / 8;
+    if (n8 == 0) head = npix;
+    tz_prof_scope ps(ctx, TZP_SDELTA);
+    const size_t items = std::max(n8, head + (npix - head - 8 * n8));
+    if (d_hist)
+        hipLaunchKernelGGL(k_sdelta_gray<true>, dim3(std::min(HB_GRID, grid_for(items, HB_THREADS))), dim3(HB_THREADS), 0, ctx->stream,
+                           in3, npix, head, n8, has_carry, carry, apply_offset, out, d_hist, d_edge);
+    else
+        hipLaunchKernelGGL(k_sdelta_gray<false>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, in3, npix, head, n8,
+                           has_carry, carry, apply_offset, out, d_hist, d_edge);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // ----------------------------------------------------------------------- rank remap / unmap
 // compress.py:84-90 and decompress.py:31-36 are T sequential `where` passes (O(N*T)); here
 // one pass through a 2112-entry LUT held in LDS.  Values outside [0, 2112) pass through
@@ -2325,6 +2406,115 @@ int tzk_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key, const ui
     }
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
+}
+
+// ---------------------------------------------------------- reconstruct from a one-channel payload (gray job)
+// tz_set_payload_channels(1): diff holds ONE delta per pixel; base = the key byte of channel 0 (key slots) or
+// trunc(pred channel 0 * 255), v = clamp(base - d, 0, 255) is written to all three channels.  General form: crop of a padded
+// prediction as k_recon; a thread takes 4 pixels and writes their 12 bytes as three dwords when `out` allows it.
+__global__ __launch_bounds__(256) void k_recon_gray(const float* __restrict__ pred, const uint8_t* __restrict__ key,
+                                                    const uint8_t* __restrict__ key_mask, const int16_t* __restrict__ diff,
+                                                    size_t n1, int H, int W, int Hp, int Wp, int out_dwords, uint8_t* __restrict__ out) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t fpix = (size_t)H * W, fp = (size_t)Hp * Wp * 3;
+    const size_t n4 = n1 / 4;
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4 + (n1 & 3 ? 1 : 0); q += stride) {
+        unsigned v4[4] = {0, 0, 0, 0};
+        const int cnt = q < n4 ? 4 : (int)(n1 & 3);
+        for (int k = 0; k < cnt; ++k) {
+            const size_t p = q * 4 + k;
+            const size_t f = p / fpix, r = p - f * fpix;
+            int base;
+            if (key_mask[f]) {
+                base = key[3 * p];
+            } else {
+                const size_t y = r / (size_t)W, x = r - y * (size_t)W;
+                base = (int)(pred[f * fp + (y * (size_t)Wp + x) * 3] * 255.0f);
+            }
+            int v = base - (int)diff[p];
+            v4[k] = (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
+        }
+        if (cnt == 4 && out_dwords) {   // bytes v0 v0 v0 v1 | v1 v1 v2 v2 | v2 v3 v3 v3
+            unsigned* o = (unsigned*)(out + 12 * q);
+            o[0] = v4[0] * 0x010101u | (v4[1] << 24);
+            o[1] = v4[1] * 0x0101u | (v4[2] * 0x0101u << 16);
+            o[2] = v4[2] | (v4[3] * 0x010101u << 8);
+        } else {
+            for (int k = 0; k < cnt; ++k) {
+                uint8_t* o = out + 3 * (q * 4 + k);
+                o[0] = o[1] = o[2] = (uint8_t)v4[k];
+            }
+        }
+    }
+}
+
+// Flat form: unpadded frames of a multiple of 8 pixels, 8 pixels per lane: 16 B of deltas, the 96 B of prediction (or the
+// 24 B of key bytes) that hold their channel 0, 24 B out as three aligned 8-byte stores.
+__global__ __launch_bounds__(256) void k_recon_gray_flat(const float4* __restrict__ pred, const uint2* __restrict__ key,
+                                                         const uint8_t* __restrict__ key_mask, const short8* __restrict__ diff,
+                                                         size_t n8, unsigned frame_pix8, uint2* __restrict__ out) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
+        const short8 d = diff[i];
+        int base[8];
+        if (key_mask[i / frame_pix8]) {
+            const uint2 k0 = key[3 * i], k1 = key[3 * i + 1], k2 = key[3 * i + 2];
+            // channel 0 of pixel k is byte 3 k of the 24
+            base[0] = k0.x & 0xff;          base[1] = k0.x >> 24;
+            base[2] = (k0.y >> 16) & 0xff;  base[3] = (k1.x >> 8) & 0xff;
+            base[4] = k1.y & 0xff;          base[5] = k1.y >> 24;
+            base[6] = (k2.x >> 16) & 0xff;  base[7] = (k2.y >> 8) & 0xff;
+        } else {
+            // channel 0 of pixel k is float 3 k of the 24
+            const float4 p0 = pred[6 * i], p1 = pred[6 * i + 1], p2 = pred[6 * i + 2], p3 = pred[6 * i + 3], p4 = pred[6 * i + 4],
+                         p5 = pred[6 * i + 5];
+            base[0] = (int)(p0.x * 255.0f); base[1] = (int)(p0.w * 255.0f);
+            base[2] = (int)(p1.z * 255.0f); base[3] = (int)(p2.y * 255.0f);
+            base[4] = (int)(p3.x * 255.0f); base[5] = (int)(p3.w * 255.0f);
+            base[6] = (int)(p4.z * 255.0f); base[7] = (int)(p5.y * 255.0f);
+        }
+        unsigned v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int a = base[j] - (int)d[j];
+            v[j] = (unsigned)(a < 0 ? 0 : (a > 255 ? 255 : a));
+        }
+        // bytes v0 v0 v0 v1 | v1 v1 v2 v2 | v2 v3 v3 v3, twice
+        out[3 * i] = make_uint2(v[0] * 0x010101u | (v[1] << 24), v[1] * 0x0101u | (v[2] * 0x0101u << 16));
+        out[3 * i + 1] = make_uint2(v[2] | (v[3] * 0x010101u << 8), v[4] * 0x010101u | (v[5] << 24));
+        out[3 * i + 2] = make_uint2(v[5] * 0x0101u | (v[6] * 0x0101u << 16), v[6] | (v[7] * 0x010101u << 8));
+    }
+}
+
+int tzk_reconstruct_gray(tz_ctx* ctx, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
+                         int nframes, int H, int W, int Hp, int Wp, uint8_t* out) {
+    const size_t fpix = (size_t)H * W, n1 = (size_t)nframes * fpix;
+    if (n1 == 0) return TZ_OK;
+    tz_prof_scope ps(ctx, TZP_RECON);
+    if (H == Hp && W == Wp && fpix % 8 == 0 && key && ((((uintptr_t)diff | (uintptr_t)pred) & 15) == 0) &&
+        ((((uintptr_t)key | (uintptr_t)out) & 7) == 0)) {
+        hipLaunchKernelGGL(k_recon_gray_flat, dim3(grid_for(n1 / 8, 256)), dim3(256), 0, ctx->stream, (const float4*)pred,
+                           (const uint2*)key, d_key_mask, (const short8*)diff, n1 / 8, (unsigned)(fpix / 8), (uint2*)out);
+    } else {
+        hipLaunchKernelGGL(k_recon_gray, dim3(grid_for(n1 / 4 + 1, 256)), dim3(256), 0, ctx->stream, pred, key, d_key_mask, diff,
+                           n1, H, W, Hp, Wp, (int)(((uintptr_t)out & 3) == 0), out);
+    }
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// The decoder's tail over a one-channel payload: the inverse remap and the inverse spatial delta of the nframes * H * W
+// elements (scan_launch, the launch tzk_decode_tail's unfused path makes) into a temporary, then k_recon_gray*.  The fused
+// walk of k_scan2p is left to the three-channel payload.
+int tzk_decode_tail_gray(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry, int16_t carry,
+                         const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp,
+                         int Wp, uint8_t* out) {
+    const size_t n1 = (size_t)nframes * H * W;
+    if (n1 == 0) return TZ_OK;
+    void* d_diff;
+    TZ_TRY(tz_pool_alloc(ctx, n1 * 2, &d_diff));
+    TZ_TRY(scan_launch(ctx, in, n1, has_carry, carry, h_lut2112, post_offset, (int16_t*)d_diff));
+    return tzk_reconstruct_gray(ctx, pred, key, d_key_mask, (const int16_t*)d_diff, nframes, H, W, Hp, Wp, out);
 }
 
 // ------------------------------------------------------------------------ reconstruction statistics

@@ -127,6 +127,7 @@ struct tz_ctx {
     volatile unsigned* h_fault = nullptr;
     unsigned* d_fault = nullptr;
     int decode_unfused = 0;                 // TEZIP_DECODE_UNFUSED=1: tz_decode as scan + reconstruct launches (cross-check)
+    int payload_channels = 3;               // tz_set_payload_channels: 1 = the payload of a gray job holds channel 0 alone
     // opt-in Huffman coder (tz_huff_*): the coded stream (index | bits) of the resident payload, or the stream a decoder
     // stages with tz_huff_begin / tz_huff_put together with what tz_huff_decode needs to expand it
     uint8_t* d_huff = nullptr;
@@ -312,6 +313,17 @@ int tzk_decode_tail(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int po
 int tzk_undelta_carry(tz_ctx*, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_word);
 int tzk_reconstruct(tz_ctx*, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
                     int nframes, int H, int W, int Hp, int Wp, uint8_t* out);
+// one-channel payload of a gray job (tz_set_payload_channels(1)).  tzk_spatial_delta_gray: tzk_spatial_delta over channel 0 of
+// the interleaved stack in3 (npix * 3 elements) -> npix elements; d_edge (may be NULL) receives the first and the last
+// channel-0 element.  tzk_reconstruct_gray: diff holds ONE delta per pixel, the sample goes to all three channels of out.
+// tzk_decode_tail_gray: tzk_decode_tail for such a payload, `in` holding nframes * H * W elements (scan, then reconstruct).
+int tzk_spatial_delta_gray(tz_ctx*, const int16_t* in3, size_t npix, int has_carry, int16_t carry, int apply_offset,
+                           int16_t* out, unsigned long long* d_hist, int16_t* d_edge);
+int tzk_reconstruct_gray(tz_ctx*, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
+                         int nframes, int H, int W, int Hp, int Wp, uint8_t* out);
+int tzk_decode_tail_gray(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry, int16_t carry,
+                         const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp,
+                         int Wp, uint8_t* out);
 // per-frame (sse, max |dec - orig|, #changed) of two unpadded nframes x fe uint8 stacks; d_out (device) is cleared here
 int tzk_quality(tz_ctx*, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out);
 // TZD64 digests of nframes frames of fe bytes (fe < 2^32, else TZ_ERR_INVALID before any launch); d_out: nframes words, cleared here

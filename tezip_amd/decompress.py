@@ -34,16 +34,28 @@ def check_stream(shape, warm_up, payload_len, key_len):
     the native library.  The reference fails with a ValueError at its reshapes
     (decompress.py:115,240) for the same inconsistencies."""
     one, nt, H, W, C = shape
-    if one not in (1, SHUFFLE_MARK) or C != 3 or nt < 1 or H < 1 or W < 1:
-        raise ValueError("entropy.dat: unsupported stack shape %r (expected (1, nt, H, W, 3))" % (tuple(shape),))
+    # C: the channels the PAYLOAD stores per pixel -- 3, or 1 for this build's opt-in payload of a gray job (--gray,
+    # tezip_amd/graypayload.py); the frames and key_frame.dat have three channels either way
+    if one not in (1, SHUFFLE_MARK) or C not in (1, 3) or nt < 1 or H < 1 or W < 1:
+        raise ValueError("entropy.dat: unsupported stack shape %r (expected (1, nt, H, W, 3), or (1, nt, H, W, 1) for a gray job)"
+                         % (tuple(shape),))
     n = nt * H * W * C
     if payload_len != n:
         raise ValueError("entropy.dat: payload holds %d elements, the trailer says %d (truncated or corrupt file)"
                          % (payload_len, n))
-    if key_len != n:
-        raise ValueError("key_frame.dat holds %d bytes, entropy.dat's trailer implies %d" % (key_len, n))
+    if key_len != nt * H * W * 3:
+        raise ValueError("key_frame.dat holds %d bytes, the stack shape %r of entropy.dat's trailer implies %d"
+                         % (key_len, tuple(shape), nt * H * W * 3))
     if not 0 <= warm_up < nt:
         raise ValueError("entropy.dat: warm-up count %d outside [0, %d)" % (warm_up, nt))
+
+
+def check_channels(data_dir, C):
+    """The payload channels entropy.dat's trailer states (3, or 1 for a --gray job) against tezip_amd.json, which records 1
+    and says nothing for 3.  The trailer is authoritative; a sidecar that contradicts it belongs to another stream."""
+    want = sidecar.channels_of(sidecar.read(data_dir))
+    if want is not None and want != C:
+        raise ValueError("tezip_amd.json describes the payload as %d-channel, entropy.dat's trailer as %d-channel" % (want, C))
 
 
 TAIL_ELEMS = _lib.TZ_NBINS + 8  # the longest trailer: table (<= 2111 symbols) + T + shape(5) + warm_up
@@ -369,7 +381,8 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
                 hp, wp = checks(nt, H, W)
                 per = stage_keys(nt, H, W, hp, wp)
                 rollout(nt, warm_up)
-        fb = H * W * C
+        check_channels(DATA_DIR, C)
+        ctx.set_payload_channels(C)         # 1: the one-channel payload of a gray job; the frames keep three channels
         if records is not None:
             check_records(records, nt, H, W)
         stages.mark("rollout (decoder)", ctx)
@@ -385,7 +398,7 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
                 print("replacing_based_on_frequency:{0}".format(prof["lut_remap"][0] / 1e3) + "[sec]")
             print("finding_difference:{0}".format(prof["undelta_scan"][0] / 1e3) + "[sec]")
         print("save as RGB" if isRGB else "save as gray")
-        ring = [np.empty((per, H, W, C), np.uint8) for _ in range(3)]
+        ring = [np.empty((per, H, W, 3), np.uint8) for _ in range(3)]
         busy = [[], [], []]
 
         def save(buf, j, name):
@@ -522,7 +535,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
         payload, table, shape, warm_up = parse_stream(read("entropy.dat"))
         check_stream(shape, warm_up, payload.size, key_len)
     _, nt, H, W, C = shape
-    key_frames = None if keys is not None else np.frombuffer(key_bytes, dtype=np.uint8).reshape(nt, H, W, C)
+    check_channels(DATA_DIR, C)
+    if C == 1 and job is not None:
+        print("ERROR: a one-channel payload (--gray) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
+        sys.exit(2)
+    key_frames = None if keys is not None else np.frombuffer(key_bytes, dtype=np.uint8).reshape(nt, H, W, 3)
     hp, wp = padding_shape(H, W)
     if model_shape is not None and (model_shape[0] != hp or model_shape[1] != wp):
         print("ERROR:keyframe size and model size do not match.")
@@ -546,6 +563,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
     try:
         if contract:
             ctx.set_contract(contract)
+        ctx.set_payload_channels(C)
         if shape[0] == SHUFFLE_MARK:  # this build's opt-in byte planes -> the int16 payload
             payload = ctx.byte_unshuffle(np.ascontiguousarray(payload).view(np.uint8))
         if job:

@@ -311,12 +311,14 @@ def parse_of(fmt, p, check, data, key_len=None):
     p.lengths = buf[o_len: o_len + A + fmt.ntok]                     # the literals, then the repeat tokens
     check(p.lengths)
     one, nt, H, W, C = p.shape
-    if one != 1 or C != 3 or nt < 1 or H < 1 or W < 1:
-        raise ValueError("%s: unsupported stack shape %r (expected (1, nt, H, W, 3))" % (what, tuple(p.shape)))
+    # C: the channels the payload stores per pixel, 3 or -- the opt-in payload of a gray job, tezip_amd/graypayload.py -- 1
+    if one != 1 or C not in (1, 3) or nt < 1 or H < 1 or W < 1:
+        raise ValueError("%s: unsupported stack shape %r (expected (1, nt, H, W, 3), or (1, nt, H, W, 1) for a gray job)"
+                         % (what, tuple(p.shape)))
     if n != nt * H * W * C:
         raise ValueError("%s: element count n = %d, the trailer's shape says %d" % (what, n, nt * H * W * C))
-    if key_len is not None and key_len != n:
-        raise ValueError("key_frame.dat holds %d bytes, entropy.dat's trailer implies %d" % (key_len, n))
+    if key_len is not None and key_len != nt * H * W * 3:
+        raise ValueError("key_frame.dat holds %d bytes, entropy.dat's trailer implies %d" % (key_len, nt * H * W * 3))
     if not 0 <= p.warm_up < nt:
         raise ValueError("entropy.dat: warm-up count %d outside [0, %d)" % (p.warm_up, nt))
     if p.table is not None and (base != 0 or A > max(len(p.table), 1)):

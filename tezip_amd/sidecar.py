@@ -11,6 +11,10 @@ it; `-c` writes this one, `-u` adopts it:
   {"format": 1, "arithmetic_contract": "TZ-PA2", "contract": 2, "tz_version": 101,
    "arch": "gfx950", "padded_frame": [512, 512], "weights_sha256": "...", "stack": [80, 512, 512, 0]}
 
+`payload_channels` = 1 (optional): the payload of entropy.dat stores one channel per pixel (`-c --gray` on a job whose frames
+are all gray, tezip_amd/graypayload.py); a job with the three-channel payload has no such key.  The trailer of entropy.dat
+states the same and is authoritative: a sidecar that contradicts it is an error.
+
 `stack` = [frames, height, width, warm_up] (round 6, optional): the reference stores these in the LAST seven
 values of entropy.dat (compress.py:390-394), so a decoder learns it only when the whole payload is decompressed; with
 it here the decoder runs its rollout WHILE entropy.dat is being decompressed (decompress._run_streaming) and checks the
@@ -47,7 +51,7 @@ def requested_contract():
     return int(v) if v in ("1", "2") else None
 
 
-def write(out_dir, contract, wts, hp, wp, stack=None):
+def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3):
     from . import _lib
     if contract not in (1, 2):
         raise ValueError("contract must be 1 or 2, not %r" % (contract,))
@@ -56,6 +60,8 @@ def write(out_dir, contract, wts, hp, wp, stack=None):
            "weights_sha256": weights_sha256(wts)}
     if stack is not None:
         doc["stack"] = [int(v) for v in stack]
+    if payload_channels == 1:   # a --gray job; every other job has no such key
+        doc["payload_channels"] = 1
     with open(os.path.join(out_dir, NAME), "w", encoding="UTF-8") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
@@ -86,6 +92,17 @@ def stack_of(doc):
             and 0 <= st[3] < st[0]):
         return tuple(st)
     return None
+
+
+def channels_of(doc):
+    """The payload channels the sidecar states: 1 for a --gray job (tezip_amd/graypayload.py), 3 for a sidecar without the key,
+    None without a sidecar.  Anything else in the key is a damaged file."""
+    if doc is None:
+        return None
+    ch = doc.get("payload_channels", 3)
+    if ch not in (1, 3) or isinstance(ch, bool):
+        raise SidecarMismatch("%s states payload_channels %r (1 is the only value ever written)" % (NAME, ch))
+    return ch
 
 
 def resolve(doc, wts=None):

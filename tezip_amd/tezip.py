@@ -57,6 +57,10 @@ FLAG_TABLE = (
     # not in the reference: with -c, also write frame_digests.json (tezip_amd/digest.py): per frame the digest of what the stored
     # payload decodes to and of the source frame, taken on the GPU (compress.run(DIGESTS=True)).  The other files do not change
     (None, "--digests", dict(action="store_true", dest="digests")),
+    # not in the reference: with -c, store ONE payload channel in entropy.dat when every frame of the job is gray (a
+    # single-channel source, widened to RGB: tezip_amd/graypayload.py; the reference cannot read such a file, -u recognises it by
+    # the shape in its trailer).  A job with colour writes exactly the files it writes without the flag
+    (None, "--gray", dict(action="store_true", dest="gray")),
     # not in the reference: with -u, what to do about frame_digests.json.  auto (also when the flag is absent) = when the file
     # is there, the decoded frames are checked against it on the GPU before an image is written (a mismatch: exit status 3, no
     # image); require = the same, and a directory without the file is refused; off = never check (salvage a damaged directory)
@@ -171,6 +175,17 @@ def check_digests_flag(arg):
     return None
 
 
+def check_gray_flag(arg):
+    """--gray is valid with -c of one single-GPU job, without --sweep.  Returns None, or the message of a refusal."""
+    if not getattr(arg, "gray", False):
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--gray is valid with -c (--compress) only (-u recognises a one-channel payload by itself)"
+    if getattr(arg, "sweep", None) is not None:
+        return "--gray cannot be combined with --sweep"
+    return compress.check_gray(True, int(os.environ.get("WORLD_SIZE", "1")) > 1)
+
+
 def check_verify_flag(arg):
     """--verify is valid with -u only; `require` needs frame_digests.json in the directory and one GPU.  Returns None, or the
     message of a refusal."""
@@ -248,6 +263,10 @@ def _main(arg):
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_gray_flag(arg)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # launched by torch.distributed.run: one rank per GPU
         from . import dist as tzdist
         tzdist.init_from_env()
@@ -280,6 +299,11 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if getattr(arg, "gray", False):
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), GRAY=True)
     if getattr(arg, "digests", False):
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
