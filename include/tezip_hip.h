@@ -37,6 +37,14 @@ typedef struct {
     unsigned n_changed;       /* samples with decoded != original */
 } tz_frame_quality;
 
+/* tz_ssim_frames / tz_encode_ssim: one record per frame (24 bytes), definition TZ-SSIM-1 below */
+typedef struct {
+    long long sum_q32;        /* sum of Q over the frame's windows; frame SSIM = sum_q32 / (windows * 2^32) */
+    long long min_q32;        /* the smallest Q of the frame (its worst window = min_q32 / 2^32), 0 when there is no window */
+    unsigned windows;         /* windows of the frame, three channels together */
+    unsigned reserved;        /* 0 */
+} tz_frame_ssim;
+
 typedef enum {
     TZ_OK = 0,
     TZ_ERR_INVALID = -1,     /* bad argument (the reference prints + exit()s or raises) */
@@ -334,6 +342,38 @@ int tz_decoded_digests(tz_ctx* ctx, int first, int count, unsigned long long* ou
  * resident source frames.  Host or device; complete on return.  Nothing of the context changes. */
 int tz_encode_digests(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
                       int shuffled, unsigned long long* decoded, unsigned long long* original);
+
+/* ---- structural similarity (no reference counterpart; `tezip.py -c --report --ssim`; definition TZ-SSIM-1, also in DESIGN.md
+ * section 9, slow statement of it in tezip_amd/ssim.py) ---------------------------------------------------------------------
+ * For two uint8 frames a, b of shape (H, W, 3), each channel on its own:
+ *   windows  8 x 8 pixels at every origin (y, x) with y % 4 == 0, x % 4 == 0, y + 8 <= H, x + 8 <= W: per channel
+ *            ((H-8)/4 + 1) * ((W-8)/4 + 1) windows when H, W >= 8, else none; a frame has three times as many.  Up to 3 rows at
+ *            the bottom and 3 columns at the right edge (H % 4, W % 4) lie in no window and are not compared.
+ *   moments  exact integers over the window's 64 samples: s1 = sum a, s2 = sum b, sa = sum a^2, sb = sum b^2, s12 = sum ab.
+ *   factors  the usual SSIM with C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2 and the population variance, multiplied through by
+ *            64^2 and by 100 so that the constants are integers; int64, all four below 2^53 in magnitude, d1, d2 > 0:
+ *              n1 = 200 * s1 * s2 + 2663424                     d1 = 100 * (s1^2 + s2^2) + 2663424
+ *              n2 = 200 * (64 * s12 - s1 * s2) + 23970816       d2 = 100 * (64 * (sa + sb) - s1^2 - s2^2) + 23970816
+ *   value    in float64, in exactly this order: p = double(n1) * double(n2), q = double(d1) * double(d2), r = p / q,
+ *            Q = llrint(r * 4294967296.0), round half to even.  There is no other floating-point operation; the library is
+ *            built with -ffp-contract=off -fno-fast-math and the device's fp64 division is the correctly rounded one, so Q is
+ *            the integer numpy computes (tests/test_gpu_ssim.py compares every field as integers, with no tolerance).
+ *   record   sum_q32 = sum of Q, min_q32 = the smallest Q over the frame's windows (0 without a window), windows, reserved = 0.
+ *            Sum and minimum of integers do not depend on how k_ssim cuts a frame over lanes and workgroups
+ *            (TEZIP_SSIM_GRID forces the number of workgroups, a diagnostic): the record is a function of the two frames.
+ * Figures (host, tezip_amd/ssim.py): frame SSIM = sum_q32 / (windows * 2^32); sequence SSIM = sum of sums / (sum of windows *
+ * 2^32), not a mean of frame values; none where windows == 0.
+ * tz_ssim_frames: the stand-alone form over two stacks of nframes frames, a, b and out (nframes records) host or device;
+ * complete on return.  TZ_ERR_INVALID for nframes < 0, H or W <= 0 or a frame of 2^32 bytes or more, before any launch;
+ * nframes == 0 launches nothing. */
+int tz_ssim_frames(tz_ctx* ctx, const uint8_t* a, const uint8_t* b, int nframes, int H, int W, tz_frame_ssim* out);
+/* tz_encode_quality's third twin: arguments, state rules and errors are exactly its own (a resident payload, the shuffle and
+ * tz_set_payload_channels(ctx, 1) with payload_len == nt*H*W included) and it runs the same front, then k_ssim over the
+ * decoded scratch frames and the resident originals: out[f] is the SSIM record of frame f as `-u` writes it against its
+ * source.  out: nt records, host or device; complete on return.  Nothing of the context changes.  The launches are counted
+ * in the profiling class "quality". */
+int tz_encode_ssim(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                   int shuffled, tz_frame_ssim* out);
 
 /* ---- operator seams, usable stand-alone (each mirrors one reference helper) -----------------
  * tz_delta_encode: compress.py:292-314.  pred: nframes padded f32 frames; orig: nframes

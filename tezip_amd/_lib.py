@@ -17,6 +17,8 @@ import threading
 
 import numpy as np
 
+from .ssim import SSIM_DTYPE   # tz_frame_ssim as a numpy record (24 bytes)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libtezip_hip.so")
 
@@ -57,6 +59,8 @@ _SIGS = {
     "tz_encode_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_encode_digests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tz_frame_digests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "tz_ssim_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_encode_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_decoded_digests": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_frames_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "tz_frames_put": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -666,6 +670,35 @@ class Context:
         tb = None if table is None else np.ascontiguousarray(table, np.int16)
         self._ck(self.lib.tz_encode_quality(self.h, None if resident else _ptr(payload), n, _ptr(tb), tl, int(bool(shuffle)),
                                             out.ctypes.data))
+        return out
+
+    # ---- structural similarity (definition TZ-SSIM-1: tezip_amd/ssim.py)
+    def encode_ssim(self, payload="resident", table=None, shuffle=False):
+        """tz_encode_ssim after rollout + encode, arguments as encode_quality's: per frame (sum_q32, min_q32, windows,
+        reserved) of what the payload decodes to against the originals, as a SSIM_DTYPE record array of nt entries."""
+        nt, h, w = self._shape
+        n = nt * h * w * self.channels
+        resident = isinstance(payload, str) and payload == "resident"
+        if not resident and _numel(payload) != n:
+            raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
+        out = np.zeros(nt, SSIM_DTYPE)
+        tl = -1 if table is None else len(table)
+        tb = None if table is None else np.ascontiguousarray(table, np.int16)
+        self._ck(self.lib.tz_encode_ssim(self.h, None if resident else _ptr(payload), n, _ptr(tb), tl, int(bool(shuffle)),
+                                         out.ctypes.data))
+        return out
+
+    def ssim_frames(self, a, b):
+        """tz_ssim_frames of two uint8 stacks (nt, H, W, 3), host arrays or device tensors: SSIM_DTYPE[nt]."""
+        if tuple(a.shape) != tuple(b.shape) or len(a.shape) != 4 or a.shape[3] != 3:
+            raise ValueError("two stacks of one shape (nt, H, W, 3), got %r and %r" % (tuple(a.shape), tuple(b.shape)))
+        nt, h, w = int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a, np.uint8)
+        if isinstance(b, np.ndarray):
+            b = np.ascontiguousarray(b, np.uint8)
+        out = np.zeros(nt, SSIM_DTYPE)
+        self._ck(self.lib.tz_ssim_frames(self.h, _ptr(a), _ptr(b), nt, h, w, out.ctypes.data))
         return out
 
     # ---- per-frame digests (tz_*_digests; format TZD64: tezip_amd/digest.py)

@@ -451,8 +451,12 @@ def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
     return hp, wp
 
 
+SSIM_NEEDS_REPORT = "--ssim extends the compression report: add --report"
+
+
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
-        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False):
+        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False,
+        SSIM=False):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -476,6 +480,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     not readable by the reference, `-u` recognises it by the shape in its trailer.  Decided after the frames are staged; a job
     with colour writes exactly the files it writes without the flag.  Works with every CODER, KEY_CODER, SHUFFLE, REPORT and
     DIGESTS.  Single-GPU jobs only.
+    SSIM (--ssim; NOT in the reference; with REPORT only): the report also carries the structural similarity of what the
+    stored payload decodes to against the sources (definition TZ-SSIM-1: tezip_amd/ssim.py), from one tz_encode_ssim call on
+    the same resident payload; a fourth line is printed.  Every other file is what it is without it.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -488,6 +495,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                or check_gray(GRAY, tzdist.active() is not None))
     if problem:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         print("ERROR:", problem)
+        sys.exit(2)
+    if SSIM and not REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
+        print("ERROR:", SSIM_NEEDS_REPORT)
         sys.exit(2)
     if tzdist.active() is not None:
         if REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
@@ -544,6 +554,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 if VERBOSE:
                     print("quality:{0}".format(time.time() - t0) + "[sec]")
                 stages.mark("quality report (device)")
+                if SSIM:   # likewise, on the same resident payload
+                    t0 = time.time()
+                    ssim_rec = ctx.encode_ssim("resident", table if ENTROPY_RUN else None, shuffle=SHUFFLE)
+                    if VERBOSE:
+                        print("ssim:{0}".format(time.time() - t0) + "[sec]")
+                    stages.mark("ssim (device)")
             if DIGESTS:  # likewise: the decoder's tail into scratch, one pass over what it yields and one over the originals
                 t0 = time.time()
                 dig = ctx.encode_digests("resident", table if ENTROPY_RUN else None, shuffle=SHUFFLE)
@@ -568,7 +584,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             stages.mark("key_frame.dat + entropy.dat")
             if REPORT:   # the three files exist: the ratio is known
                 report = quality.summarize(stats, src.files, H, W, MODE, BOUND_VALUE, quality.file_sizes(OUTPUT_DIR),
-                                           window=WINDOW_SIZE, threshold=THRESHOLD, warm_up=PREPROCESS)
+                                           window=WINDOW_SIZE, threshold=THRESHOLD, warm_up=PREPROCESS,
+                                           **({"ssim": ssim_rec} if SSIM else {}))
                 quality.write(OUTPUT_DIR, report)
                 for line in quality.stdout_lines(report):
                     print(line)

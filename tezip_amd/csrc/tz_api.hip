@@ -141,6 +141,8 @@ extern "C" int tz_ctx_create(int device, void* hip_stream, tz_ctx** out) {
         if (e) ctx->quality_grid = atoi(e);
         e = getenv("TEZIP_DIGEST_GRID");         // diagnostic: workgroups of k_digest (0 = per launch; tests of launch-shape invariance)
         if (e) ctx->digest_grid = atoi(e);
+        e = getenv("TEZIP_SSIM_GRID");           // diagnostic: workgroups of k_ssim (0 = per launch; tests of launch-shape invariance)
+        if (e) ctx->ssim_grid = atoi(e);
     }
     ctx->device = device;
     {
@@ -2066,6 +2068,46 @@ extern "C" int tz_encode_digests(tz_ctx* ctx, const int16_t* payload, size_t pay
     }
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device words too: complete on return)
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// The records of `-c --report --ssim`: k_ssim of the decoded stack against the originals.
+extern "C" int tz_encode_ssim(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                              int shuffled, tz_frame_ssim* out) {
+    tz_roctx_range roctx_("tz_encode_ssim");
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    std::vector<tz_out> outs;
+    tz_out o;
+    const uint8_t* d_dec = nullptr;
+    int rc = encode_decoded(ctx, "tz_encode_ssim", payload, payload_len, table, table_len, shuffled, &d_dec);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_ssim) * ctx->nt, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    if (rc == TZ_OK) rc = tzk_ssim(ctx, d_dec, ctx->d_frames, ctx->nt, ctx->H, ctx->W, (tz_frame_ssim*)o.dev);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device records too: complete on return)
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// TZ-SSIM-1 records of any two unpadded uint8 stacks (tests against tezip_amd/ssim.py).
+extern "C" int tz_ssim_frames(tz_ctx* ctx, const uint8_t* a, const uint8_t* b, int nframes, int H, int W, tz_frame_ssim* out) {
+    tz_roctx_range roctx_("tz_ssim_frames");
+    if (!ctx || nframes < 0 || (nframes > 0 && (!out || !a || !b))) return TZ_ERR_INVALID;
+    if (H <= 0 || W <= 0) return tz_fail(ctx, TZ_ERR_INVALID, "frames of %d x %d", H, W);
+    const size_t fe = (size_t)H * W * 3;
+    if (fe >> 32) return tz_fail(ctx, TZ_ERR_INVALID, "frames of %zu bytes: SSIM covers frames of fewer than 2^32", fe);
+    if (nframes == 0) return TZ_OK;
+    std::vector<tz_out> outs;
+    tz_out o;
+    const void *d_a = nullptr, *d_b = nullptr;
+    int rc = tz_dev_in(ctx, a, (size_t)nframes * fe, &d_a);
+    if (rc == TZ_OK) rc = tz_dev_in(ctx, b, (size_t)nframes * fe, &d_b);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_ssim) * nframes, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    if (rc == TZ_OK) rc = tzk_ssim(ctx, (const uint8_t*)d_a, (const uint8_t*)d_b, nframes, H, W, (tz_frame_ssim*)o.dev);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
     tz_pool_release_all(ctx);
     return rc;
 }

@@ -2782,6 +2782,180 @@ int tzk_digest(tz_ctx* ctx, const uint8_t* x, int nframes, size_t fe, unsigned l
     return TZ_OK;
 }
 
+// ------------------------------------------------------------------------------ structural similarity
+// TZ-SSIM-1 (include/tezip_hip.h, DESIGN.md section 9, slow statement in tezip_amd/ssim.py): per frame of two unpadded uint8
+// stacks the sum and the minimum of the integer Q of every 8 x 8 window (stride 4, per channel).  A window is 2 x 2 CELLS of
+// 4 x 4 pixels, so the five moments are formed once per cell and summed four at a time.
+// A workgroup walks a contiguous run of TILES; a tile is SS_T x SS_T window origins of one frame, i.e. (SS_T + 1)^2 = 256 cells,
+// one per lane: 64 x 64 pixels, of which the last 4 columns and rows are the apron that the neighbouring tiles read again
+// (a 16 x 16 tile of origins has 289 cells and a second, nearly empty pass over them: measured 79 us against 65 us on cfg3's job).
+//   phase 1: a lane forms one cell: 4 rows of 12 bytes of each stack (ss_row12), 15 integer moments, one 16-byte record per
+//            channel into LDS: {s1 | s2 << 16, sa, sb, s12} (s1, s2 <= 16 * 255; the others < 2^21).
+//   phase 2: a lane per window origin (225 of the 256) reads the four records of each channel (consecutive lanes read
+//            consecutive 16-byte records, a row of 15 lanes skips one record of the 16-record pitch), forms
+//            the four int64 factors and evaluates Q: two fp64 multiplies, ONE correctly rounded fp64 division, a multiply
+//            by 2^32 (exact) and rint (half to even) -- no other floating-point operation, -ffp-contract=off.
+// The running sum and minimum belong to one frame; where the run of tiles moves on to the next frame, and at its end, the
+// workgroup flushes: shuffle reduction per wave, LDS across the four waves, then ONE 64-bit add and ONE signed 64-bit min per
+// frame it touched (relaxed, agent scope).  Integer reductions: the records do not depend on the grid (TEZIP_SSIM_GRID).
+// k_ssim_init writes the records first: sum 0, min INT64_MAX (0 for frames without a window), the window count, reserved 0.
+static constexpr int SS_T = 15;                       // window origins per tile side
+static constexpr int SS_C = SS_T + 1;                 // cells per tile side
+static constexpr int SS_CELLS = SS_C * SS_C;
+
+struct SsPart {
+    long long sum, mn;
+};
+
+__device__ __forceinline__ long long ss_min(long long x, long long y) { return y < x ? y : x; }
+
+// the 12 bytes at stack offset `off` (one cell row: 4 pixels x 3 channels), packed 4 per word.  Aligned dword loads -- three
+// where the address is a multiple of 4, else four and a funnel shift -- wherever those dwords lie inside the stack
+// [x, x + total); the rows at the stack's two ends that they would leave take byte loads.  Nothing outside the stack is read.
+__device__ __forceinline__ void ss_row12(const uint8_t* __restrict__ x, size_t off, size_t total, unsigned w[3]) {
+    const uintptr_t addr = (uintptr_t)x + off, m = addr & 3, p0 = addr - m;
+    if (p0 >= (uintptr_t)x && p0 + (m ? 16 : 12) <= (uintptr_t)x + total) {
+        const unsigned* p = (const unsigned*)p0;
+        const unsigned d0 = p[0], d1 = p[1], d2 = p[2], d3 = m ? p[3] : 0u;
+        const unsigned sh = 8u * (unsigned)m;
+        w[0] = (unsigned)((((unsigned long long)d1 << 32) | d0) >> sh);
+        w[1] = (unsigned)((((unsigned long long)d2 << 32) | d1) >> sh);
+        w[2] = (unsigned)((((unsigned long long)d3 << 32) | d2) >> sh);
+    } else {
+        w[0] = w[1] = w[2] = 0;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) w[j >> 2] |= (unsigned)x[off + j] << (8 * (j & 3));
+    }
+}
+
+// Q of one window from its five moments (exact integers; every factor below 2^53 in magnitude, d1, d2 > 0)
+__device__ __forceinline__ long long ss_q(long long s1, long long s2, long long sa, long long sb, long long s12) {
+    const long long n1 = 200 * s1 * s2 + 2663424;
+    const long long n2 = 200 * (64 * s12 - s1 * s2) + 23970816;
+    const long long d1 = 100 * (s1 * s1 + s2 * s2) + 2663424;
+    const long long d2 = 100 * (64 * (sa + sb) - s1 * s1 - s2 * s2) + 23970816;
+    const double p = (double)n1 * (double)n2;
+    const double q = (double)d1 * (double)d2;
+    const double r = p / q;
+    return (long long)__builtin_rint(r * 4294967296.0);   // |r * 2^32| < 2^34: the conversion is exact
+}
+
+// every thread of the workgroup calls this (block-uniform control flow); rec = the frame's record
+__device__ __forceinline__ void ss_flush(long long sum, long long mn, SsPart* red, tz_frame_ssim* rec) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off, 64);
+        mn = ss_min(mn, __shfl_xor(mn, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = SsPart{sum, mn};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sum = red[0].sum + red[1].sum + red[2].sum + red[3].sum;
+        mn = ss_min(ss_min(red[0].mn, red[1].mn), ss_min(red[2].mn, red[3].mn));
+        __hip_atomic_fetch_add(&rec->sum_q32, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_min(&rec->min_q32, mn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();   // red is written again by the next flush
+}
+
+__global__ __launch_bounds__(256) void k_ssim_init(tz_frame_ssim* __restrict__ out, int nframes, unsigned windows) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f < nframes) out[f] = tz_frame_ssim{0, windows ? INT64_MAX : 0, windows, 0u};
+}
+
+// CH x CW cells and (CH - 1) x (CW - 1) window origins per channel (CH = H / 4, CW = W / 4, both >= 2); TY x TX tiles per
+// frame, ntiles in all; workgroup b walks tiles [b * per_block, (b + 1) * per_block)
+__global__ __launch_bounds__(256) void k_ssim(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, size_t total, size_t fe,
+                                              int W, int CH, int CW, int TY, int TX, size_t ntiles, size_t per_block,
+                                              tz_frame_ssim* __restrict__ out) {
+    __shared__ uint4 cell[3][SS_CELLS];
+    __shared__ SsPart red[4];
+    const size_t t0 = (size_t)blockIdx.x * per_block;
+    if (t0 >= ntiles) return;   // (workgroup-uniform)
+    const size_t t1 = min(ntiles, t0 + per_block), per_frame = (size_t)TY * TX;
+    size_t f = t0 / per_frame;                    // the frame the running sum and minimum belong to
+    long long sum = 0, mn = INT64_MAX;
+    for (size_t t = t0; t < t1; ++t) {
+        const size_t tf = t / per_frame;
+        if (tf != f) {
+            ss_flush(sum, mn, red, out + f);
+            sum = 0;
+            mn = INT64_MAX;
+            f = tf;
+        }
+        const int rem = (int)(t - tf * per_frame), ty = rem / TX, tx = rem - ty * TX;
+        // phase 1: the cells of the tile that lie inside the frame's cell grid
+        for (int ci = threadIdx.x; ci < SS_CELLS; ci += 256) {
+            const int ly = ci / SS_C, lx = ci - ly * SS_C, cy = ty * SS_T + ly, cx = tx * SS_T + lx;
+            if (cy >= CH || cx >= CW) continue;
+            unsigned s1[3] = {0, 0, 0}, s2[3] = {0, 0, 0}, sa[3] = {0, 0, 0}, sb[3] = {0, 0, 0}, s12[3] = {0, 0, 0};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const size_t off = tf * fe + ((size_t)(cy * 4 + r) * W + (size_t)cx * 4) * 3;   // (< total: the cell lies inside the frame)
+                unsigned wa[3], wb[3];
+                ss_row12(a, off, total, wa);
+                ss_row12(b, off, total, wb);
+#pragma unroll
+                for (int j = 0; j < 12; ++j) {
+                    const unsigned av = (wa[j >> 2] >> (8 * (j & 3))) & 0xffu, bv = (wb[j >> 2] >> (8 * (j & 3))) & 0xffu;
+                    const int c = j % 3;
+                    s1[c] += av;
+                    s2[c] += bv;
+                    sa[c] += av * av;
+                    sb[c] += bv * bv;
+                    s12[c] += av * bv;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cell[c][ci] = make_uint4(s1[c] | (s2[c] << 16), sa[c], sb[c], s12[c]);
+        }
+        __syncthreads();
+        // phase 2: one window origin per lane, three channels
+        {
+            const int ly = threadIdx.x / SS_T, lx = threadIdx.x % SS_T, wy = ty * SS_T + ly, wx = tx * SS_T + lx;
+            if (threadIdx.x < SS_T * SS_T && wy < CH - 1 && wx < CW - 1) {
+                const int i00 = ly * SS_C + lx;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const uint4 q0 = cell[c][i00], q1 = cell[c][i00 + 1], q2 = cell[c][i00 + SS_C], q3 = cell[c][i00 + SS_C + 1];
+                    const unsigned m1 = (q0.x & 0xffffu) + (q1.x & 0xffffu) + (q2.x & 0xffffu) + (q3.x & 0xffffu);
+                    const unsigned m2 = (q0.x >> 16) + (q1.x >> 16) + (q2.x >> 16) + (q3.x >> 16);
+                    const long long Q = ss_q((long long)m1, (long long)m2, (long long)(q0.y + q1.y + q2.y + q3.y),
+                                             (long long)(q0.z + q1.z + q2.z + q3.z), (long long)(q0.w + q1.w + q2.w + q3.w));
+                    sum += Q;
+                    mn = ss_min(mn, Q);
+                }
+            }
+        }
+        __syncthreads();   // the cells are written again by the next tile
+    }
+    ss_flush(sum, mn, red, out + f);
+}
+
+// per-frame TZ-SSIM-1 records of two unpadded nframes x H x W x 3 uint8 stacks; d_out (device) is written whole here
+int tzk_ssim(tz_ctx* ctx, const uint8_t* a, const uint8_t* b, int nframes, int H, int W, tz_frame_ssim* d_out) {
+    if (nframes <= 0) return TZ_OK;
+    const size_t fe = (size_t)H * W * 3;
+    if (H <= 0 || W <= 0 || (fe >> 32)) return tz_fail(ctx, TZ_ERR_INVALID, "frames of %d x %d: SSIM covers frames of fewer than 2^32 bytes", H, W);
+    const int CH = H / 4, CW = W / 4;
+    const bool any = CH >= 2 && CW >= 2;
+    const unsigned windows = any ? 3u * (unsigned)(CH - 1) * (unsigned)(CW - 1) : 0u;
+    tz_prof_scope ps(ctx, TZP_QUALITY);
+    hipLaunchKernelGGL(k_ssim_init, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, ctx->stream, d_out, nframes, windows);
+    TZ_HIP(ctx, hipGetLastError());
+    if (!any) return TZ_OK;
+    const int TY = (CH - 1 + SS_T - 1) / SS_T, TX = (CW - 1 + SS_T - 1) / SS_T;
+    const size_t ntiles = (size_t)nframes * TY * TX;
+    size_t G = ctx->ssim_grid > 0 ? (size_t)ctx->ssim_grid : (size_t)grid_for(ntiles, 1);
+    G = std::max<size_t>(1, std::min(G, ntiles));
+    const size_t per_block = (ntiles + G - 1) / G;
+    G = (ntiles + per_block - 1) / per_block;   // (no workgroup without a tile)
+    hipLaunchKernelGGL(k_ssim, dim3((unsigned)G), dim3(256), 0, ctx->stream, a, b, (size_t)nframes * fe, fe, W, CH, CW, TY, TX,
+                       ntiles, per_block, d_out);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // ------------------------------------------------------------------------------ window SSE
 // compress.py:246: mean((X_test_pad - pred)^2) in float64 over PADDED frames.  Per frame the
 // sum is taken in a fixed order so that it is reproducible: 4096-element blocks; thread t sums

@@ -32,7 +32,7 @@ enum tz_prof_class {
     TZP_TABLE,      // HOST time: rank table + LUT from the downloaded histogram (compress.py:356-361)
     TZP_QSERIAL,    // not a time: `launches` counts the chains the quantiser sent through its serial fallback (k_q_serial)
     TZP_CARRY,      // prefix carry of the inverse scan (k_undelta_carry, tz_decode_range)
-    TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality)
+    TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality; k_ssim, tz_encode_ssim / tz_ssim_frames)
     TZP_HUFF,       // opt-in Huffman coder: k_huff_count / k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec (and k_huffr_*),
                     // and the key-frame coder in front of it: k_key_hist / k_key_resid / k_key_unresid_*
     TZP_DIGEST,     // per-frame digests TZD64 (k_digest: tz_frame_digests, tz_decoded_digests, tz_encode_digests)
@@ -65,6 +65,7 @@ struct tz_ctx {
     int wino_ipw = 0;                 // TEZIP_WINO_IPW (measurements): column blocks per k_wino workgroup, 0 = chosen per launch
     int quality_grid = 0;             // TEZIP_QUALITY_GRID (diagnostic): workgroups of k_quality, 0 = chosen per launch
     int digest_grid = 0;              // TEZIP_DIGEST_GRID (diagnostic): workgroups of k_digest, 0 = chosen per launch
+    int ssim_grid = 0;                // TEZIP_SSIM_GRID (diagnostic): workgroups of k_ssim, 0 = chosen per launch
     // rollout-resident data
     int nt = 0, H = 0, W = 0, Hp = 0, Wp = 0, warm_up = 0;
     uint8_t* d_frames = nullptr;      // nt*H*W*3 (encoder: originals; decoder: key stack)
@@ -328,6 +329,9 @@ int tzk_decode_tail_gray(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, i
 int tzk_quality(tz_ctx*, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out);
 // TZD64 digests of nframes frames of fe bytes (fe < 2^32, else TZ_ERR_INVALID before any launch); d_out: nframes words, cleared here
 int tzk_digest(tz_ctx*, const uint8_t* x, int nframes, size_t fe, unsigned long long* d_out);
+// TZ-SSIM-1 records of two unpadded nframes x H x W x 3 uint8 stacks (a frame of 2^32 bytes or more: TZ_ERR_INVALID before any
+// launch); d_out: nframes records, written whole here
+int tzk_ssim(tz_ctx*, const uint8_t* a, const uint8_t* b, int nframes, int H, int W, tz_frame_ssim* d_out);
 // Huffman coder.  Geometry: runs of TZ_HUFF_RUN symbols, chunks of TZ_HUFF_CHUNK_RUNS runs.
 static constexpr int TZ_HUFF_L = 12, TZ_HUFF_RUN = 256, TZ_HUFF_CHUNK_RUNS = 64;
 static constexpr int TZ_HUFF_COUNT_BINS = 4096, TZ_HUFF_COUNT_BIAS = 1024;   // k_huff_count: bin = value + bias

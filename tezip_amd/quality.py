@@ -41,12 +41,15 @@ def _sizes(sizes):
     return sizes
 
 
-def summarize(stats, names, H, W, mode, bound, sizes, window=None, threshold=None, warm_up=None):
+def summarize(stats, names, H, W, mode, bound, sizes, window=None, threshold=None, warm_up=None, ssim=None):
     """The report of one job as a JSON-ready dict.
     stats: the per-frame records in frame order; names: the frames' file names (filename.txt order); sizes: the byte
     sizes of filename.txt, key_frame.dat and entropy.dat (a dict by name or a sequence in that order).  PSNR per frame
     uses the frame's H*W*3 samples, the sequence's PSNR the sum of sse over all nt*H*W*3 samples (not a mean of frame
-    PSNRs).  ratio = nt*H*W*3 / (sum of the three sizes)."""
+    PSNRs).  ratio = nt*H*W*3 / (sum of the three sizes).
+    ssim (--ssim): the per-frame tz_frame_ssim records (tezip_amd/ssim.py) -- the document then gains "ssim" and "ssim_min" (the
+    worst window of the job) at the top and in every per_frame entry, null where a frame has no window; None: exactly the
+    document without them."""
     rec = _records(stats)
     nt = len(rec)
     if len(names) != nt:
@@ -57,7 +60,7 @@ def summarize(stats, names, H, W, mode, bound, sizes, window=None, threshold=Non
     stored = sum(_sizes(sizes))
     per_frame = [{"name": str(n), "max_abs_err": int(r[1]), "sse": int(r[0]), "n_changed": int(r[2]),
                   "psnr_db": psnr_db(int(r[0]), fe)} for n, r in zip(names, rec)]
-    return {
+    doc = {
         "mode": mode,
         "bound": [float(b) for b in bound],
         "window": None if window is None else int(window),
@@ -76,6 +79,15 @@ def summarize(stats, names, H, W, mode, bound, sizes, window=None, threshold=Non
         "ratio": float(total) / float(stored) if stored else None,
         "per_frame": per_frame,
     }
+    if ssim is not None:
+        from . import ssim as tzssim
+        fig = tzssim.figures(ssim)
+        if len(fig["per_frame"]) != nt:
+            raise ValueError("%d ssim records for %d frames" % (len(fig["per_frame"]), nt))
+        doc["ssim"], doc["ssim_min"] = fig["ssim"], fig["ssim_min"]
+        for entry, f in zip(per_frame, fig["per_frame"]):
+            entry["ssim"], entry["ssim_min"] = f["ssim"], f["ssim_min"]
+    return doc
 
 
 def file_sizes(out_dir):
@@ -92,6 +104,10 @@ def write(out_dir, doc):
 
 
 def stdout_lines(doc):
-    """The three lines -c --report prints."""
+    """The three lines -c --report prints, and the SSIM line behind them when the document has the key (--ssim)."""
     psnr = "inf" if doc["psnr_db"] is None else "%.4f" % doc["psnr_db"]
-    return ["max_abs_err: %d" % doc["max_abs_err"], "PSNR: %s [dB]" % psnr, "ratio: %.4f" % doc["ratio"]]
+    lines = ["max_abs_err: %d" % doc["max_abs_err"], "PSNR: %s [dB]" % psnr, "ratio: %.4f" % doc["ratio"]]
+    if "ssim" in doc:
+        from . import ssim as tzssim
+        lines.append(tzssim.stdout_line(doc["ssim"], doc["ssim_min"]))
+    return lines

@@ -45,6 +45,10 @@ FLAG_TABLE = (
     # not in the reference: with -c, also write quality.json (the error the bound introduced, per frame and for the
     # sequence, from the stored payload decoded on the GPU) and print max_abs_err / PSNR / ratio (compress.run(REPORT=...))
     (None, "--report", dict(action="store_true", dest="report")),
+    # not in the reference: with -c --report, the report also carries the structural similarity (SSIM, definition TZ-SSIM-1 in
+    # tezip_amd/ssim.py) of what the stored payload decodes to against the sources, per frame and for the sequence, computed on
+    # the GPU (compress.run(SSIM=True)); `python -m tezip_amd.ssim IMAGES RESTORED` gives the same figures after a -u
+    (None, "--ssim", dict(action="store_true", dest="ssim")),
     # not in the reference: with -c, the coder of entropy.dat.  zstd = the reference's file; huff = canonical Huffman codes
     # written by the GPU (tezip_amd/huff.py; the reference cannot read such a file, -u recognises it by its magic); huffr = the
     # same with repeat tokens for the payload's period-3 runs (tezip_amd/huffr.py), a smaller file under an error bound
@@ -175,6 +179,21 @@ def check_digests_flag(arg):
     return None
 
 
+def check_ssim_flag(arg):
+    """--ssim is valid with -c --report of one single-GPU job only.  Returns None, or the message of a refusal."""
+    if not getattr(arg, "ssim", False):
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--ssim is valid with -c (--compress) --report only"
+    if getattr(arg, "sweep", None) is not None:
+        return "--ssim cannot be combined with --sweep"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--ssim is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+    if not getattr(arg, "report", False):
+        return compress.SSIM_NEEDS_REPORT
+    return None
+
+
 def check_gray_flag(arg):
     """--gray is valid with -c of one single-GPU job, without --sweep.  Returns None, or the message of a refusal."""
     if not getattr(arg, "gray", False):
@@ -259,6 +278,10 @@ def _main(arg):
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_ssim_flag(arg)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
     problem = check_verify_flag(arg)
     if problem:   # likewise
         print("ERROR:", problem)
@@ -299,6 +322,11 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if getattr(arg, "ssim", False):
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=True,
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), GRAY=bool(getattr(arg, "gray", False)), SSIM=True)
     if getattr(arg, "gray", False):
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
