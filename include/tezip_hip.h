@@ -488,6 +488,29 @@ int tz_huffr_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t*
 int tz_huffr_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base,
                         int R, int16_t* out);
 
+/* ---- opt-in Huffman coder that picks its match distance (`tezip.py -c --coder huffd`, format TZR2 in DESIGN.md section 9,
+ * slow statement of it in tezip_amd/huffd.py) ----------------------------------------------------------------------------
+ * One coder over the two above: a file names its match distance D.  D = 0: no repeat tokens, the stream is tz_huff_*'s for
+ * the same literal lengths.  D = 1 or 3: tz_huffr_*'s tokeniser with "three" replaced by D (element j of a run matches when
+ * j >= D and equals element j - D; the history in front of a run is D elements equal to base); for D = 3 the stream is
+ * tz_huffr_*'s byte for byte.  `lengths` holds A + 8 bytes for every D, and with D = 0 the eight token lengths must be 0.
+ * tz_huffd_counts fills THREE histograms from one read of the payload (k_huffd_count): `counts` holds 3 rows of TZ_NBINS + 8
+ * entries, row 0 for D = 0, row 1 for D = 1, row 2 for D = 3, each the A literals, then T_0..T_7 (all 0 in row 0), then
+ * zeros; the host chooses D from them (tezip_amd/huffd.py: choose).  TZ_ERR_INVALID for a D outside {0, 1, 3}; every other
+ * refusal and clamp is tz_huffr_*'s.  The resident stream buffer is the one tz_huff_* / tz_huffr_* use: a tz_huffd_begin
+ * replaces what they staged and the other way round, and each decoder refuses the others' streams with TZ_ERR_STATE. */
+int tz_huffd_counts(tz_ctx* ctx, unsigned long long* counts /* [3][TZ_NBINS + 8] */, int* A, int* base);
+int tz_huffd_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* counts, int* A, int* base);
+int tz_huffd_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, int D, size_t* bytes);
+int tz_huffd_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out);
+int tz_huffd_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R, int D);
+int tz_huffd_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src);
+int tz_huffd_decode(tz_ctx* ctx);
+int tz_huffd_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, int D, uint8_t* out,
+                        size_t capacity, size_t* bytes);
+int tz_huffd_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base,
+                        int R, int D, int16_t* out);
+
 /* ---- opt-in key-frame coder (`tezip.py -c --key-coder huff`, format TZK1 in DESIGN.md section 9, slow statement of it in
  * tezip_amd/keycoder.py; no reference counterpart: compress.py:271-278 hands a zero-except-keys stack to zstd) -----------------
  * Only the key frames are stored: each as the residuals mod 256 of one of four predictors over its own samples (0: none,

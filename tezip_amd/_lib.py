@@ -121,6 +121,17 @@ _SIGS = {
     "tz_huffr_decode": (C.c_int, [C.c_void_p]),
     "tz_huffr_encode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]),
+    "tz_huffd_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tz_huffd_counts_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tz_huffd_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "tz_huffd_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_huffd_begin": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tz_huffd_put": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "tz_huffd_decode": (C.c_int, [C.c_void_p]),
+    "tz_huffd_encode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
+    "tz_huffd_decode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p]),
     "tz_huffr_decode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p]),
     "tz_keys_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -966,6 +977,58 @@ class Context:
 
     def huffr_decode_buf(self, stream, n, lengths, base, run=256, out=None):
         return self._stream_decode_buf(self.lib.tz_huffr_decode_buf, stream, n, lengths, base, run, out, HUFFR_NTOK)
+
+    # ---- opt-in Huffman coder that picks its match distance (tz_huffd_*; format: tezip_amd/huffd.py).  `lengths` holds the A
+    # literals and then the 8 tokens for every distance; dist is 0 (no tokens), 1 or 3.
+    def huffd_counts(self, x=None):
+        """The three token histograms of the resident payload (or of the int16 array x), from one read of it ->
+        (uint64[3][A + 8], base): row 0 without tokens, row 1 at match distance 1, row 2 at distance 3."""
+        counts = np.zeros((3, TZ_NBINS + HUFFR_NTOK), np.uint64)
+        a, base = C.c_int(0), C.c_int(0)
+        if x is None:
+            self._ck(self.lib.tz_huffd_counts(self.h, counts.ctypes.data, C.byref(a), C.byref(base)))
+        else:
+            self._ck(self.lib.tz_huffd_counts_buf(self.h, _ptr(x), _numel(x), counts.ctypes.data, C.byref(a), C.byref(base)))
+        return counts[:, : a.value + HUFFR_NTOK].copy(), base.value
+
+    def huffd_encode(self, lengths, base, dist):
+        """Code the resident payload into the resident stream (index | bits) at the match distance dist; returns its size."""
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        nbytes = C.c_size_t(0)
+        self._ck(self.lib.tz_huffd_encode(self.h, ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), int(dist), C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def huffd_get(self, offset, count, out=None):
+        return self._stream_get(self.lib.tz_huffd_get, offset, count, out)
+
+    def huffd_begin(self, nbytes, n, lengths, base, dist, run=256):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        self._ck(self.lib.tz_huffd_begin(self.h, int(nbytes), int(n), ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), int(run), int(dist)))
+
+    def huffd_put(self, offset, piece):
+        self._stream_put(self.lib.tz_huffd_put, offset, piece)
+
+    def huffd_decode(self):
+        self._ck(self.lib.tz_huffd_decode(self.h))
+
+    def huffd_encode_buf(self, x, lengths, base, dist, out=None):
+        """Stand-alone: int16 values (host or device) -> the coded stream (index | bits) as a uint8 array."""
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        n = _numel(x)
+        if out is None:   # the most a stream can need: 12 bits per element, a pad word per chunk, the index
+            out = np.empty(n * 3 // 2 + (n // 16384 + 1) * 8 + (n // 256 + 1) * 2 + 64, np.uint8)
+        nbytes = C.c_size_t(0)
+        self._ck(self.lib.tz_huffd_encode_buf(self.h, _ptr(x), n, ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), int(dist), _ptr(out),
+                                              _numel(out), C.byref(nbytes)))
+        return out[: nbytes.value]
+
+    def huffd_decode_buf(self, stream, n, lengths, base, dist, run=256, out=None):
+        ln = np.ascontiguousarray(lengths, np.uint8)
+        if out is None:
+            out = np.empty(n, np.int16)
+        self._ck(self.lib.tz_huffd_decode_buf(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base),
+                                              int(run), int(dist), _ptr(out)))
+        return out
 
     # ---- operator seams
     def delta_encode(self, pred, orig, zero_mask=None, out=None):

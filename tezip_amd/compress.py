@@ -11,7 +11,8 @@ Output directory:
                  alone, nt*H*W elements, and the shape in the trailer ends in 1 (tezip_amd/graypayload.py)
                  with CODER="huff" (--coder huff; not a reference format): "TZH1" header | that trailer | code lengths |
                  index | bit stream, written by the GPU (tezip_amd/huff.py); with CODER="huffr" the
-                 same under the magic "TZR1", the code being over literals and period-3 repeat tokens (tezip_amd/huffr.py)
+                 same under the magic "TZR1", the code being over literals and period-3 repeat tokens (tezip_amd/huffr.py);
+                 with CODER="huffd" under the magic "TZR2", the match distance 0 / 1 / 3 chosen per file (tezip_amd/huffd.py)
   with KEY_CODER="huff" (--key-coder huff; not a reference format) key_frame.dat holds the key frames alone: "TZK1" header |
                  key indices | predictor ids | code lengths | index | bit stream -- per key frame the residuals of the best
                  of four predictors (none, left, up, left + up - upleft), Huffman-coded on the GPU (tezip_amd/keycoder.py,
@@ -27,7 +28,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, digest, huff, huffr, keycoder, keycoderg, quality, sidecar, weights, zstd
+from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, quality, sidecar, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -235,7 +236,7 @@ class _Stages:
             self.last = now
 
 
-CODERS = ("zstd", "huff", "huffr")
+CODERS = ("zstd", "huff", "huffr", "huffd")
 HUFF_PIECE = 16 << 20   # bytes of the coded stream fetched and written at a time
 
 
@@ -339,9 +340,19 @@ class _Done:
 
 
 def _huff_entropy_file(ctx, path, n, trailer, verbose, coder="huff"):
-    """entropy.dat of CODER="huff" / "huffr": the resident payload is coded on the device (tz_huff_encode / tz_huffr_encode)
-    and only the coded stream crosses to the host; the header, the reference trailer and the code lengths go in front of it."""
+    """entropy.dat of CODER="huff" / "huffr" / "huffd": the resident payload is coded on the device (tz_huff_encode /
+    tz_huffr_encode / tz_huffd_encode) and only the coded stream crosses to the host; the header, the reference trailer and the
+    code lengths go in front of it.  huffd: one read of the payload counts it under the three match distances, the distance
+    and its code are chosen here from those counts (huffd.choose), and one line says which."""
     t0 = time.perf_counter()
+    if coder == "huffd":
+        counts3, base = ctx.huffd_counts()
+        dist, lengths, costs = huffd.choose(counts3)
+        print("coder: huffd, match distance %d (bits: none %d, 1: %d, 3: %d)" % ((dist,) + tuple(costs)))
+        nbytes = ctx.huffd_encode(lengths, base, dist)
+        nruns, nchunks = huff.geometry(n)
+        front = huffd.pack_front(trailer, lengths, base, n, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4, dist)
+        return _write_coded(path, front, nbytes, ctx.huffd_get, "huffman_coding" if verbose else None, t0)
     if coder == "huffr":
         fmt = huffr
         counts, base = ctx.huffr_counts()
@@ -406,7 +417,7 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
         tail = np.array([-1], dtype=np.int64)
     trailer = np.concatenate([tail, [SHUFFLE_MARK if shuffled else 1, nt, H, W, channels], [warm_up]]).astype(np.int16)
     t_e = time.perf_counter()
-    if coder in ("huff", "huffr"):
+    if coder in ("huff", "huffr", "huffd"):
         esize = _huff_entropy_file(ctx, os.path.join(out_dir, "entropy.dat"), n, trailer, verbose, coder)
         if stages:
             stages.add("huffman coding + fetch entropy.dat", time.perf_counter() - t_e)
@@ -463,7 +474,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     bound introduced, from the stored payload decoded on the device (tz_encode_quality) -- and print the worst error,
     the PSNR and the compression ratio.  Single-GPU jobs only.
     CODER (--coder; NOT in the reference): "zstd" writes the reference's entropy.dat; "huff" has the GPU Huffman-code the
-    payload (tezip_amd/huff.py), "huffr" the same over literals and period-3 repeat tokens (tezip_amd/huffr.py) -- such a
+    payload (tezip_amd/huff.py), "huffr" the same over literals and period-3 repeat tokens (tezip_amd/huffr.py), "huffd" the same
+    with the match distance (none, 1 or 3) chosen per file from exact counts (tezip_amd/huffd.py) -- such a
     file is not readable by the reference; `-u` recognises it by its magic.
     Single-GPU jobs only, not with SHUFFLE.
     KEY_CODER (--key-coder; NOT in the reference): "zstd" writes the reference's key_frame.dat; "huff" has the GPU code the

@@ -2483,8 +2483,9 @@ static void huff_geometry(size_t n, size_t* nruns, size_t* nchunks, size_t* inde
 // d_in (device, n int16) -> ctx->d_huff = index | bits; *bytes its size.  Waits once, for the size of the bit stream.
 // ntok: TZ_HUFFR_NTOK for the TZR1 stream (lengths then holds A + ntok entries, k_huffr_size / k_huffr_enc), 0 for TZH1.
 // keys: the stream goes to the key-frame coder's buffer ctx->d_keys instead, and what the entropy coders hold stays.
+// dist: the match distance of a tokenised stream (3: TZR1; a TZR2 stream names 1 or 3).
 static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uint8_t* lengths, int A, int base, size_t* bytes, int ntok,
-                           bool keys = false) {
+                           bool keys = false, int dist = 3) {
     if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
     std::vector<uint16_t> enc;
     TZ_TRY(huff_tables(ctx, lengths, A, base, &enc, nullptr, ntok));
@@ -2498,7 +2499,7 @@ static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uin
     TZ_HIP(ctx, hipMemsetAsync(d_idx, 0, index_bytes, ctx->stream));   // (the padding behind an odd number of run sizes is part of the file)
     unsigned* d_chunk_off = (unsigned*)d_idx;
     uint16_t* d_run_bits = (uint16_t*)((uint8_t*)d_idx + nchunks * 4);
-    TZ_TRY(tzk_huff_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, ntok, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta));
+    TZ_TRY(tzk_huff_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, ntok, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta, dist));
     tz_huff_meta meta;
     TZ_TRY(tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream));
     TZ_TRY(tz_stream_sync(ctx));
@@ -2519,7 +2520,7 @@ static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uin
     }
     TZ_HIP(ctx, hipMemcpyAsync(d_stream, d_idx, index_bytes, hipMemcpyDeviceToDevice, ctx->stream));
     TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, ntok, d_run_bits, d_chunk_off, (unsigned*)(d_stream + index_bytes),
-                        (size_t)meta.total_words));
+                        (size_t)meta.total_words, dist));
     *bytes = total;
     return TZ_OK;
 }
@@ -2538,20 +2539,22 @@ static int huff_check_stream(tz_ctx* ctx, size_t bytes, size_t n, int R, size_t*
 }
 
 static int huff_decode_dev(tz_ctx* ctx, const uint8_t* d_stream, size_t stream_words, size_t n, const std::vector<uint16_t>& dec, int A, int base,
-                           int ntok, int16_t* d_out) {
+                           int ntok, int16_t* d_out, int dist = 3) {
     size_t nruns, nchunks, index_bytes;
     huff_geometry(n, &nruns, &nchunks, &index_bytes);
     void* d_dec;
     TZ_TRY(tz_pool_alloc(ctx, dec.size() * 2, &d_dec));
     TZ_TRY(tz_upload(ctx, d_dec, dec.data(), dec.size() * 2));
     return tzk_huff_dec(ctx, (const unsigned*)d_stream, (const uint16_t*)(d_stream + nchunks * 4), (const unsigned*)(d_stream + index_bytes),
-                        stream_words, (const uint16_t*)d_dec, A, base, ntok, n, d_out);
+                        stream_words, (const uint16_t*)d_dec, A, base, ntok, n, d_out, dist);
 }
 
 // One body per entry point of the two entropy coders, `--coder huff` (TZH1, ntok == 0) and `--coder huffr` (TZR1, ntok ==
 // TZ_HUFFR_NTOK: the runs are tokenised first, tezip_amd/huffr.py, and `lengths` holds A + 8 bytes).  `who` is the entry
 // point's family, "tz_huff" or "tz_huffr", for the messages.  Both stage into the same buffers; ctx->huff_kind says which
-// format's begin did, so each put and decode refuses the other's stream.
+// format's begin did, so each put and decode refuses the other's stream.  `--coder huffd` (TZR2, tezip_amd/huffd.py) runs the
+// same bodies: its match distance D says which of the two kernel families codes the stream (0: TZH1's, 1 or 3: TZR1's at that
+// distance), `lengths` always holds A + 8 bytes, and its streams are of a third kind.
 static tz_ctx::tz_huff_kind huff_kind_of(int ntok) { return ntok ? tz_ctx::HUFF_TZR1 : tz_ctx::HUFF_TZH1; }
 
 // the counts of n device elements: the A literals from the lowest to the highest value present, then the ntok tokens
@@ -2591,15 +2594,16 @@ static int huff_counts(tz_ctx* ctx, int ntok, const char* who, unsigned long lon
     return rc;
 }
 
-static int huff_encode(tz_ctx* ctx, int ntok, const char* who, const uint8_t* lengths, int A, int base, size_t* bytes) {
+static int huff_encode(tz_ctx* ctx, int ntok, const char* who, const uint8_t* lengths, int A, int base, size_t* bytes, int dist = 3) {
     if (!ctx || !bytes) return TZ_ERR_INVALID;
     if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "%s_encode needs a resident payload (tz_encode with payload == NULL)", who);
-    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes, ntok);
+    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes, ntok, false, dist);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-static int huff_begin(tz_ctx* ctx, int ntok, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
+static int huff_begin(tz_ctx* ctx, int ntok, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
+                      tz_ctx::tz_huff_kind kind = tz_ctx::HUFF_NONE, int dist = 3) {
     if (!ctx) return TZ_ERR_INVALID;
     size_t sw;
     TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
@@ -2615,39 +2619,42 @@ static int huff_begin(tz_ctx* ctx, int ntok, size_t bytes, size_t n, const uint8
     ctx->huff_base = base;
     ctx->huff_A = A;
     ctx->huff_n = n;
-    ctx->huff_kind = huff_kind_of(ntok);
+    ctx->huff_dist = dist;
+    ctx->huff_kind = kind != tz_ctx::HUFF_NONE ? kind : huff_kind_of(ntok);
     TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
     return TZ_OK;
 }
 
-static int huff_put(tz_ctx* ctx, int ntok, size_t offset, size_t count, const uint8_t* src) {
+static int huff_put(tz_ctx* ctx, tz_ctx::tz_huff_kind kind, size_t offset, size_t count, const uint8_t* src) {
     if (!ctx || !src) return TZ_ERR_INVALID;
-    if (!ctx->d_huff || ctx->huff_kind != huff_kind_of(ntok) || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
+    if (!ctx->d_huff || ctx->huff_kind != kind || offset > ctx->huff_bytes || count > ctx->huff_bytes - offset)
         return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged Huffman stream");
     return tz_h2d(ctx, ctx->d_huff + offset, src, count, ctx->copy_stream);
 }
 
-static int huff_decode(tz_ctx* ctx, int ntok, const char* who) {
+static int huff_decode(tz_ctx* ctx, tz_ctx::tz_huff_kind kind, const char* who) {
     if (!ctx) return TZ_ERR_INVALID;
-    if (ctx->huff_kind != huff_kind_of(ntok) || !ctx->d_huff || !ctx->d_payload || ctx->cap_payload < ctx->huff_n * 2)
+    // (a staged TZR2 stream carries its match distance: none = the TZH1 kernels, else the tokenised ones at that distance)
+    const int dist = kind == tz_ctx::HUFF_TZR2 ? ctx->huff_dist : 3, ntok = kind == tz_ctx::HUFF_TZH1 || dist == 0 ? 0 : TZ_HUFFR_NTOK;
+    if (ctx->huff_kind != kind || !ctx->d_huff || !ctx->d_payload || ctx->cap_payload < ctx->huff_n * 2)
         return tz_fail(ctx, TZ_ERR_STATE, "%s_decode needs a stream staged with %s_begin / %s_put", who, who, who);
     size_t sw;
     TZ_TRY(huff_check_stream(ctx, ctx->huff_bytes, ctx->huff_n, TZ_HUFF_RUN, &sw));
     TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of the puts
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
-    const int rc = huff_decode_dev(ctx, ctx->d_huff, sw, ctx->huff_n, ctx->huff_dec_tab, ctx->huff_A, ctx->huff_base, ntok, ctx->d_payload);
+    const int rc = huff_decode_dev(ctx, ctx->d_huff, sw, ctx->huff_n, ctx->huff_dec_tab, ctx->huff_A, ctx->huff_base, ntok, ctx->d_payload, dist);
     if (rc == TZ_OK) ctx->payload_len = ctx->huff_n;   // exactly as if tz_payload_begin / tz_payload_put had staged them
     tz_pool_release_all(ctx);
     return rc;
 }
 
 static int huff_encode_buf(tz_ctx* ctx, int ntok, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
-                           size_t capacity, size_t* bytes) {
+                           size_t capacity, size_t* bytes, int dist = 3) {
     if (!ctx || !in || !out || !bytes) return TZ_ERR_INVALID;
     const void* din = nullptr;
     int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
-    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes, ntok);
+    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes, ntok, false, dist);
     if (rc == TZ_OK && *bytes > capacity) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: the stream needs %zu bytes, the buffer holds %zu", *bytes, capacity);
     if (rc == TZ_OK) {
         if (tz_is_device_ptr(out)) {
@@ -2686,14 +2693,14 @@ static int buf_op(tz_ctx* ctx, const void* in, size_t in_bytes, unsigned in_mask
 }
 
 static int huff_decode_buf(tz_ctx* ctx, int ntok, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
-                           int16_t* out) {
+                           int16_t* out, int dist = 3) {
     if (!ctx || !stream || !out) return TZ_ERR_INVALID;
     size_t sw;
     TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
     std::vector<uint16_t> dec;
     TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, ntok));
     return buf_op(ctx, stream, bytes, 3, out, n * 2, 0, "huffman: a device stream must be 4-byte aligned", [&](const void* din, void* dout) {
-        return huff_decode_dev(ctx, (const uint8_t*)din, sw, n, dec, A, base, ntok, (int16_t*)dout);
+        return huff_decode_dev(ctx, (const uint8_t*)din, sw, n, dec, A, base, ntok, (int16_t*)dout, dist);
     });
 }
 
@@ -2719,11 +2726,11 @@ extern "C" int tz_huff_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t*
     return huff_begin(ctx, 0, bytes, n, lengths, A, base, R);
 }
 
-extern "C" int tz_huff_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) { return huff_put(ctx, 0, offset, count, src); }
+extern "C" int tz_huff_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) { return huff_put(ctx, tz_ctx::HUFF_TZH1, offset, count, src); }
 
 extern "C" int tz_huff_decode(tz_ctx* ctx) {
     tz_roctx_range roctx_("tz_huff_decode");
-    return huff_decode(ctx, 0, "tz_huff");
+    return huff_decode(ctx, tz_ctx::HUFF_TZH1, "tz_huff");
 }
 
 extern "C" int tz_huff_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
@@ -2753,12 +2760,12 @@ extern "C" int tz_huffr_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t
 }
 
 extern "C" int tz_huffr_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
-    return huff_put(ctx, TZ_HUFFR_NTOK, offset, count, src);
+    return huff_put(ctx, tz_ctx::HUFF_TZR1, offset, count, src);
 }
 
 extern "C" int tz_huffr_decode(tz_ctx* ctx) {
     tz_roctx_range roctx_("tz_huffr_decode");
-    return huff_decode(ctx, TZ_HUFFR_NTOK, "tz_huffr");
+    return huff_decode(ctx, tz_ctx::HUFF_TZR1, "tz_huffr");
 }
 
 extern "C" int tz_huffr_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
@@ -2779,6 +2786,107 @@ extern "C" int tz_huffr_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, uns
     if (rc == TZ_OK) rc = huff_counts_dev(ctx, (const int16_t*)din, n, TZ_HUFFR_NTOK, "tz_huffr", counts, A, base);
     tz_pool_release_all(ctx);
     return rc;
+}
+
+// ---- `--coder huffd` (TZR2): the coder that picks its match distance
+// D must be 0, 1 or 3; *ntok = the tokens the kernels code with (none for D = 0, whose eight token lengths must be 0)
+static int huffd_family(tz_ctx* ctx, int D, const uint8_t* lengths, int A, int* ntok) {
+    if (D != 0 && D != 1 && D != 3) return tz_fail(ctx, TZ_ERR_INVALID, "tz_huffd: match distance %d, the format knows 0 (no tokens), 1 and 3", D);
+    *ntok = D ? TZ_HUFFR_NTOK : 0;
+    if (D == 0 && lengths && A >= 1 && A <= TZ_NBINS)
+        for (int k = 0; k < TZ_HUFFR_NTOK; ++k)
+            if (lengths[A + k]) return tz_fail(ctx, TZ_ERR_INVALID, "tz_huffd: match distance 0 with a code length %d for the token T_%d", lengths[A + k], k);
+    return TZ_OK;
+}
+
+// counts: three rows of TZ_NBINS + 8 entries (match distance 0 | 1 | 3), each the A literals, then T_0..T_7, then zeros
+static int huffd_counts_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, unsigned long long* counts, int* A, int* base) {
+    constexpr int BINS = TZ_HUFF_COUNT_BINS + TZ_HUFFR_NTOK, ROW = TZ_NBINS + TZ_HUFFR_NTOK;
+    void *d_hist, *d_meta;
+    std::vector<unsigned long long> h(3 * BINS);
+    tz_huff_meta meta;
+    int rc = tz_pool_alloc(ctx, h.size() * sizeof(unsigned long long), &d_hist);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta);
+    if (rc == TZ_OK) rc = tzk_huffd_count(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
+    if (rc == TZ_OK) rc = tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream);
+    if (rc == TZ_OK) rc = tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
+    TZ_TRY(rc);
+    int lo = -1, hi = -1;   // (row 0 counts every element; the other rows' literals span the same values)
+    for (int b = 0; b < TZ_HUFF_COUNT_BINS; ++b)
+        if (h[b]) {
+            if (lo < 0) lo = b;
+            hi = b;
+        }
+    if (meta.bad || lo < 0 || hi - lo + 1 > TZ_NBINS)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_huffd_counts: the payload's values span more than %d symbols", TZ_NBINS);
+    const int a = hi - lo + 1;
+    for (int d = 0; d < 3; ++d)
+        for (int s = 0; s < ROW; ++s)
+            counts[d * ROW + s] = s < a ? h[d * BINS + lo + s] : s < a + TZ_HUFFR_NTOK ? h[d * BINS + TZ_HUFF_COUNT_BINS + s - a] : 0;
+    *A = a;
+    *base = lo - TZ_HUFF_COUNT_BIAS;
+    return TZ_OK;
+}
+
+extern "C" int tz_huffd_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
+    tz_roctx_range roctx_("tz_huffd_counts");
+    if (!ctx || !counts || !A || !base) return TZ_ERR_INVALID;
+    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huffd_counts needs a resident payload (tz_encode with payload == NULL)");
+    const int rc = huffd_counts_dev(ctx, ctx->d_payload, ctx->payload_len, counts, A, base);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_huffd_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* counts, int* A, int* base) {
+    if (!ctx || !in || !counts || !A || !base) return TZ_ERR_INVALID;
+    const void* din = nullptr;
+    int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    if (rc == TZ_OK) rc = huffd_counts_dev(ctx, (const int16_t*)din, n, counts, A, base);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_huffd_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, int D, size_t* bytes) {
+    tz_roctx_range roctx_("tz_huffd_encode");
+    if (!ctx || !bytes) return TZ_ERR_INVALID;
+    int ntok;
+    TZ_TRY(huffd_family(ctx, D, lengths, A, &ntok));
+    return huff_encode(ctx, ntok, "tz_huffd", lengths, A, base, bytes, D);
+}
+
+extern "C" int tz_huffd_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) { return tz_huff_get(ctx, offset, count, out); }
+
+extern "C" int tz_huffd_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R, int D) {
+    if (!ctx) return TZ_ERR_INVALID;
+    int ntok;
+    TZ_TRY(huffd_family(ctx, D, lengths, A, &ntok));
+    return huff_begin(ctx, ntok, bytes, n, lengths, A, base, R, tz_ctx::HUFF_TZR2, D);
+}
+
+extern "C" int tz_huffd_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
+    return huff_put(ctx, tz_ctx::HUFF_TZR2, offset, count, src);
+}
+
+extern "C" int tz_huffd_decode(tz_ctx* ctx) {
+    tz_roctx_range roctx_("tz_huffd_decode");
+    return huff_decode(ctx, tz_ctx::HUFF_TZR2, "tz_huffd");
+}
+
+extern "C" int tz_huffd_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, int D, uint8_t* out,
+                                   size_t capacity, size_t* bytes) {
+    if (!ctx) return TZ_ERR_INVALID;
+    int ntok;
+    TZ_TRY(huffd_family(ctx, D, lengths, A, &ntok));
+    return huff_encode_buf(ctx, ntok, in, n, lengths, A, base, out, capacity, bytes, D);
+}
+
+extern "C" int tz_huffd_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
+                                   int D, int16_t* out) {
+    if (!ctx) return TZ_ERR_INVALID;
+    int ntok;
+    TZ_TRY(huffd_family(ctx, D, lengths, A, &ntok));
+    return huff_decode_buf(ctx, ntok, stream, bytes, n, lengths, A, base, R, out, D);
 }
 
 // --------------------------------------------------------------------------- key-frame coder (TZK1)

@@ -3316,15 +3316,17 @@ static constexpr int HFR_ENC_PAD = (TZ_NBINS + HFR_NTOK + 7) & ~7;
 
 // Walks the run of `cnt` elements at r0.  f(m, lit, s) is called once per element and once behind the run: m > 0 is a
 // stretch of m matches that ended in front of this point (to be coded first), lit says the element s is a literal.
-template <bool VEC, class F>
+// DIST is the match distance: 3 (TZR1, and TZR2 with D = 3) or 1 (TZR2 with D = 1: the neighbour in front).
+template <bool VEC, int DIST, class F>
 __device__ __forceinline__ void hfr_walk(const int16_t* __restrict__ in, size_t n, size_t r0, int cnt, F&& f) {
+    static_assert(DIST == 1 || DIST == 3, "match distances of the formats: 1 and 3");
     int h1 = 0, h2 = 0, h3 = 0, m = 0;
     for (int j = 0; j < cnt; j += 8) {
         const short8 v = hf_load8<VEC>(in, r0 + j, n, (short)0);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int s = v[k];
-            const bool live = j + k < cnt, match = live && j + k >= HFR_DIST && s == h3, lit = live && !match;
+            const bool live = j + k < cnt, match = live && j + k >= DIST && s == (DIST == 1 ? h1 : h3), lit = live && !match;
             f(lit ? m : 0, lit, s);
             m = match ? m + 1 : (lit ? 0 : m);
             h3 = h2;
@@ -3346,7 +3348,7 @@ __global__ __launch_bounds__(256) void k_huffr_count(const int16_t* __restrict__
     bool bad = false;
     for (size_t run = (size_t)blockIdx.x * 256 + threadIdx.x; run < nruns; run += (size_t)gridDim.x * 256) {
         const size_t r0 = run * HF_R;
-        hfr_walk<VEC>(in, n, r0, (int)std::min((size_t)HF_R, n - r0), [&](int m, bool lit, int s) {
+        hfr_walk<VEC, HFR_DIST>(in, n, r0, (int)std::min((size_t)HF_R, n - r0), [&](int m, bool lit, int s) {
             if (m) atomicAdd(&h[TZ_HUFF_COUNT_BINS + (31 - __clz(m))], 1u);
             if (lit) {
                 const int b = s + TZ_HUFF_COUNT_BIAS;
@@ -3373,10 +3375,90 @@ int tzk_huffr_count(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long
     return TZ_OK;
 }
 
+// Opt-in stage `--coder huffd` (format TZR2: DESIGN.md section 9, tezip_amd/huffd.py): the coder picks its match distance
+// D in {0: no tokens, 1, 3} from exact counts, so ONE read of the payload fills the three histograms the choice needs, each of
+// k_huffr_count's layout (4096 literal bins, then T_0..T_7): hist[0] the plain literals, hist[1] the tokens at distance 1,
+// hist[2] those at distance 3.  One thread per run as there; a lane carries both match states (the neighbour h1 with its
+// stretch m1, the element three back h3 with m3) through the same uniform steps.  A stretch at distance 1 is a run of equal
+// values, so the plain histogram takes such a stretch with one add when it ends, not one per element.  A value outside the
+// 4096 bins sets meta->bad (it is a literal at its first place in a run under every distance).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_huffd_count(const int16_t* __restrict__ in, size_t n, size_t nruns, unsigned long long* __restrict__ hist,
+                                                     tz_huff_meta* __restrict__ meta) {
+    constexpr int BINS = TZ_HUFF_COUNT_BINS + HFR_NTOK;
+    __shared__ unsigned h[3 * BINS];
+    for (int k = threadIdx.x; k < 3 * BINS; k += 256) h[k] = 0;
+    __syncthreads();
+    bool bad = false;
+    for (size_t run = (size_t)blockIdx.x * 256 + threadIdx.x; run < nruns; run += (size_t)gridDim.x * 256) {
+        const size_t r0 = run * HF_R;
+        const int cnt = (int)std::min((size_t)HF_R, n - r0);
+        int h1 = 0, h2 = 0, h3 = 0, m1 = 0, m3 = 0;
+        for (int j = 0; j < cnt; j += 8) {
+            const short8 v = hf_load8<VEC>(in, r0 + j, n, (short)0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int s = v[k];
+                if (j + k >= cnt) continue;   // (uniform but for the last run of the payload)
+                const int b = s + TZ_HUFF_COUNT_BIAS, b1 = h1 + TZ_HUFF_COUNT_BIAS;
+                const bool ok = b >= 0 && b < TZ_HUFF_COUNT_BINS;
+                const bool match1 = j + k >= 1 && s == h1, match3 = j + k >= HFR_DIST && s == h3;
+                bad |= !ok;
+                if (match1) {
+                    ++m1;
+                } else {
+                    if (m1) {   // the stretch in front: its token, and its elements as plain literals (h1 was counted in range)
+                        atomicAdd(&h[BINS + TZ_HUFF_COUNT_BINS + (31 - __clz(m1))], 1u);
+                        if (b1 >= 0 && b1 < TZ_HUFF_COUNT_BINS) atomicAdd(&h[b1], (unsigned)m1);
+                        m1 = 0;
+                    }
+                    if (ok) {
+                        atomicAdd(&h[b], 1u);
+                        atomicAdd(&h[BINS + b], 1u);
+                    }
+                }
+                if (match3) {
+                    ++m3;
+                } else {
+                    if (m3) atomicAdd(&h[2 * BINS + TZ_HUFF_COUNT_BINS + (31 - __clz(m3))], 1u);
+                    m3 = 0;
+                    if (ok) atomicAdd(&h[2 * BINS + b], 1u);
+                }
+                h3 = h2;
+                h2 = h1;
+                h1 = s;
+            }
+        }
+        const int b1 = h1 + TZ_HUFF_COUNT_BIAS;   // the stretches the run's end cuts
+        if (m1) {
+            atomicAdd(&h[BINS + TZ_HUFF_COUNT_BINS + (31 - __clz(m1))], 1u);
+            if (b1 >= 0 && b1 < TZ_HUFF_COUNT_BINS) atomicAdd(&h[b1], (unsigned)m1);
+        }
+        if (m3) atomicAdd(&h[2 * BINS + TZ_HUFF_COUNT_BINS + (31 - __clz(m3))], 1u);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < 3 * BINS; k += 256)
+        if (h[k]) atomicAdd(&hist[k], (unsigned long long)h[k]);
+    if (bad) atomicOr(&meta->bad, 1u);
+}
+
+// d_hist: 3 x (TZ_HUFF_COUNT_BINS + 8) counts, distance 0 | 1 | 3
+int tzk_huffd_count(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* d_hist, tz_huff_meta* d_meta) {
+    const size_t nruns = (n + HF_R - 1) / HF_R;
+    TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, 3 * (TZ_HUFF_COUNT_BINS + HFR_NTOK) * sizeof(unsigned long long), ctx->stream));
+    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    const dim3 grid((unsigned)std::min((nruns + 255) / 256, (size_t)2048));
+    if ((uintptr_t)in & 15) hipLaunchKernelGGL(k_huffd_count<false>, grid, dim3(256), 0, ctx->stream, in, n, nruns, d_hist, d_meta);
+    else hipLaunchKernelGGL(k_huffd_count<true>, grid, dim3(256), 0, ctx->stream, in, n, nruns, d_hist, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // Size pass: one wave per chunk, four chunks per workgroup; a lane sums the bits of its run (code lengths of its literals
 // and tokens plus the raw bits), run_bits[r] is the index's entry of run r, chunk_bits[c] feeds k_huff_scan.  `enc` holds
 // A + 8 entries: the literals, then T_0..T_7.
-template <bool VEC>
+template <bool VEC, int DIST>
 __global__ __launch_bounds__(256) void k_huffr_size(const int16_t* __restrict__ in, size_t n, const uint16_t* __restrict__ enc, int A,
                                                     int base, size_t nruns, size_t nchunks, uint16_t* __restrict__ run_bits,
                                                     unsigned* __restrict__ chunk_bits, tz_huff_meta* __restrict__ meta) {
@@ -3390,7 +3472,7 @@ __global__ __launch_bounds__(256) void k_huffr_size(const int16_t* __restrict__ 
     unsigned bits = 0;
     bool bad = false;
     if (run < nruns)
-        hfr_walk<VEC>(in, n, r0, (int)std::min((size_t)HF_R, n - r0), [&](int m, bool lit, int s) {
+        hfr_walk<VEC, DIST>(in, n, r0, (int)std::min((size_t)HF_R, n - r0), [&](int m, bool lit, int s) {
             if (m) {
                 const int k = 31 - __clz(m);
                 const unsigned l = len[A + k];
@@ -3415,7 +3497,7 @@ __global__ __launch_bounds__(256) void k_huffr_size(const int16_t* __restrict__ 
 // Pack pass: k_huff_enc's scheme (one wave per chunk, 64-bit accumulator per lane, whole words ORed into the chunk's image
 // in LDS, coalesced stores of the image, no global atomics) over the tokens of hfr_walk.  A step appends at most a token
 // with its raw bits and a literal: 12 + 7 + 12 bits on top of fewer than 32, so the accumulator holds them.
-template <bool VEC>
+template <bool VEC, int DIST>
 __global__ __launch_bounds__(64) void k_huffr_enc(const int16_t* __restrict__ in, size_t n, const uint16_t* __restrict__ enc, int A, int base,
                                                   size_t nruns, const uint16_t* __restrict__ run_bits, const unsigned* __restrict__ chunk_off,
                                                   unsigned* __restrict__ words, size_t stream_words) {
@@ -3428,7 +3510,7 @@ __global__ __launch_bounds__(64) void k_huffr_enc(const int16_t* __restrict__ in
     const int cnt = r0 < n ? (int)std::min((size_t)HF_R, n - r0) : 0;
     unsigned long long acc = 0;
     unsigned nb = pos & 31u, wi = pos >> 5;
-    hfr_walk<VEC>(in, n, r0, cnt, [&](int m, bool lit, int s) {
+    hfr_walk<VEC, DIST>(in, n, r0, cnt, [&](int m, bool lit, int s) {
         if (m) {
             const int k = 31 - __clz(m);
             const unsigned e = tab[A + k];            // (no code: k_huffr_size said so, and the host launched nothing)
@@ -3448,12 +3530,12 @@ __global__ __launch_bounds__(64) void k_huffr_enc(const int16_t* __restrict__ in
 
 // Expand pass: k_huff_dec's scheme and clamps (chunk offsets to the stream, staged words to the image, reads of the image
 // to its end, run sizes to R * L, a lane stops after its run's element count, which comes from n alone).  Every lane
-// produces one element per step: inside a stretch it copies the element three back, which it holds in registers (the
-// history in front of a run is three times `base`); otherwise it looks up a symbol, and a token >= A starts a stretch of
+// produces one element per step: inside a stretch it copies the element DIST back, which it holds in registers (the
+// history in front of a run is DIST times `base`); otherwise it looks up a symbol, and a token >= A starts a stretch of
 // 2^k + k raw bits elements whose first one is this step's.  A stretch ends with the run, whatever its token says.  After
 // a refill the accumulator holds more than 32 valid bits and a step takes at most 12 + 7, so a corrupt body yields wrong
 // elements, never an access outside the buffers.
-template <bool VEC>
+template <bool VEC, int DIST>
 __global__ __launch_bounds__(64) void k_huffr_dec(const unsigned* __restrict__ chunk_off, const uint16_t* __restrict__ run_bits,
                                                   const unsigned* __restrict__ words, size_t stream_words, size_t nruns, size_t nchunks,
                                                   const uint16_t* __restrict__ dec, int A, int base, size_t n, int16_t* __restrict__ out) {
@@ -3472,7 +3554,7 @@ __global__ __launch_bounds__(64) void k_huffr_dec(const unsigned* __restrict__ c
         short8 v;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            int val = h3;
+            int val = DIST == 1 ? h1 : h3;
             if (m == 0) {
                 const unsigned e = tab[(unsigned)acc & 0xFFFu];
                 const unsigned l = e >> 12, sym = e & 0xFFFu;
@@ -3500,16 +3582,20 @@ __global__ __launch_bounds__(64) void k_huffr_dec(const unsigned* __restrict__ c
 }
 
 // The launchers of the size, pack and expand passes of both coders: ntok == 0 runs the k_huff_* kernels, ntok ==
-// TZ_HUFFR_NTOK the k_huffr_* ones (d_enc then holds A + ntok entries); VEC says that the payload is 16-byte aligned.
+// TZ_HUFFR_NTOK the k_huffr_* ones (d_enc then holds A + ntok entries) at the match distance `dist`: 3 is TZR1's, 1 the other
+// one a TZR2 file may name; VEC says that the payload is 16-byte aligned.
 int tzk_huff_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, uint16_t* d_run_bits,
-                  unsigned* d_chunk_off, tz_huff_meta* d_meta) {
+                  unsigned* d_chunk_off, tz_huff_meta* d_meta, int dist) {
+    if (ntok && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
     const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
     void* d_cbits;
     TZ_TRY(tz_pool_alloc(ctx, nchunks * sizeof(unsigned), &d_cbits));
     TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
     tz_prof_scope ps(ctx, TZP_HUFF);
     const bool vec = !((uintptr_t)in & 15);
-    const auto k = ntok ? (vec ? k_huffr_size<true> : k_huffr_size<false>) : (vec ? k_huff_size<true> : k_huff_size<false>);
+    const auto k = !ntok      ? (vec ? k_huff_size<true> : k_huff_size<false>)
+                   : dist == 1 ? (vec ? k_huffr_size<true, 1> : k_huffr_size<false, 1>)
+                               : (vec ? k_huffr_size<true, HFR_DIST> : k_huffr_size<false, HFR_DIST>);
     hipLaunchKernelGGL(k, dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
                        (unsigned*)d_cbits, d_meta);
     TZ_HIP(ctx, hipGetLastError());
@@ -3519,11 +3605,14 @@ int tzk_huff_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_en
 }
 
 int tzk_huff_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, const uint16_t* d_run_bits,
-                 const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words) {
+                 const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words, int dist) {
+    if (ntok && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
     const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
     tz_prof_scope ps(ctx, TZP_HUFF);
     const bool vec = !((uintptr_t)in & 15);
-    const auto k = ntok ? (vec ? k_huffr_enc<true> : k_huffr_enc<false>) : (vec ? k_huff_enc<true> : k_huff_enc<false>);
+    const auto k = !ntok      ? (vec ? k_huff_enc<true> : k_huff_enc<false>)
+                   : dist == 1 ? (vec ? k_huffr_enc<true, 1> : k_huffr_enc<false, 1>)
+                               : (vec ? k_huffr_enc<true, HFR_DIST> : k_huffr_enc<false, HFR_DIST>);
     hipLaunchKernelGGL(k, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits, d_chunk_off, d_words,
                        stream_words);
     TZ_HIP(ctx, hipGetLastError());
@@ -3531,14 +3620,16 @@ int tzk_huff_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc
 }
 
 int tzk_huff_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
-                 const uint16_t* d_dec, int A, int base, int ntok, size_t n, int16_t* out) {
+                 const uint16_t* d_dec, int A, int base, int ntok, size_t n, int16_t* out, int dist) {
+    if (ntok && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
     const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
     tz_prof_scope ps(ctx, TZP_HUFF);
     const bool vec = !((uintptr_t)out & 15);
     const dim3 grid((unsigned)nchunks);
     if (ntok)   // (the literal count A tells k_huffr_dec the tokens from the literals; k_huff_dec has no use for it)
-        hipLaunchKernelGGL(vec ? k_huffr_dec<true> : k_huffr_dec<false>, grid, dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words,
-                           stream_words, nruns, nchunks, d_dec, A, base, n, out);
+        hipLaunchKernelGGL(dist == 1 ? (vec ? k_huffr_dec<true, 1> : k_huffr_dec<false, 1>)
+                                     : (vec ? k_huffr_dec<true, HFR_DIST> : k_huffr_dec<false, HFR_DIST>),
+                           grid, dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words, nruns, nchunks, d_dec, A, base, n, out);
     else
         hipLaunchKernelGGL(vec ? k_huff_dec<true> : k_huff_dec<false>, grid, dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words,
                            stream_words, nruns, nchunks, d_dec, base, n, out);

@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from . import _lib, digest, huff, huffr, keycoder, keycoderg, sidecar, zstd
+from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, sidecar, zstd
 from . import dist as tzdist
 from .compress import SHUFFLE_MARK, make_context, open_model
 from .data_utils import padding_shape
@@ -60,24 +60,28 @@ def check_channels(data_dir, C):
 
 TAIL_ELEMS = _lib.TZ_NBINS + 8  # the longest trailer: table (<= 2111 symbols) + T + shape(5) + warm_up
 # piece sizes of the streaming paths, read when a run starts (tests/test_gpu_pieces.py shrinks them to make every loop iterate)
-PUT_PIECE = 16 << 20            # bytes of a coded body (TZH1 / TZR1 / TZK1 / TZK2) staged per huff_put / huffr_put / keys_put
+PUT_PIECE = 16 << 20            # bytes of a coded body (TZH1 / TZR1 / TZR2 / TZK1 / TZK2) staged per huff_put / huffr_put / keys_put
 FETCH_WINDOW_BYTES = 16 << 20   # a fetch window holds the frames that fit in this many bytes (at least one)
 PREFETCH_PIECE_BYTES = 16 << 20  # _Prefetch: bytes of entropy.dat decompressed per piece
 PREFETCH_DEPTH = 8              # _Prefetch: pieces queued ahead of the consumer
 
 
 def coded_format(head):
-    """The module of this build's opt-in entropy.dat formats the first bytes of a file name (huff: TZH1, huffr: TZR1), or
-    None for the reference's zstd frame."""
+    """The module of this build's opt-in entropy.dat formats the first bytes of a file name (huff: TZH1, huffr: TZR1,
+    huffd: TZR2), or None for the reference's zstd frame."""
     if huff.is_huff(head):
         return huff
     if huffr.is_huffr(head):
         return huffr
+    if huffd.is_huffd(head):
+        return huffd
     return None
 
 
 def coded_calls(ctx, coded):
-    """(begin, put, decode) of the context for a parsed TZH1 / TZR1 file."""
+    """(begin, put, decode) of the context for a parsed TZH1 / TZR1 / TZR2 file; begin takes (bytes, n, lengths, base, run)."""
+    if isinstance(coded, huffd.Parsed):          # (the file's match distance goes with its lengths)
+        return (lambda nbytes, n, lengths, base, run: ctx.huffd_begin(nbytes, n, lengths, base, coded.dist, run)), ctx.huffd_put, ctx.huffd_decode
     if isinstance(coded, huffr.Parsed):
         return ctx.huffr_begin, ctx.huffr_put, ctx.huffr_decode
     return ctx.huff_begin, ctx.huff_put, ctx.huff_decode
@@ -303,8 +307,8 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
         fmt = coded_format(ent_head)
         if fmt is not None:
             # this build's opt-in Huffman file: everything the decoder needs stands in FRONT of the bit stream, so the
-            # whole file is validated on the CPU (huff.parse / huffr.parse) before anything is staged, and the rollout is
-            # queued first
+            # whole file is validated on the CPU (huff.parse / huffr.parse / huffd.parse) before anything is staged, and the
+            # rollout is queued first
             coded = fmt.parse(np.fromfile(paths["entropy.dat"], np.uint8), key_len)
             table, warm_up = coded.table, coded.warm_up
             _, nt, H, W, C = coded.shape

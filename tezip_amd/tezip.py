@@ -51,8 +51,9 @@ FLAG_TABLE = (
     (None, "--ssim", dict(action="store_true", dest="ssim")),
     # not in the reference: with -c, the coder of entropy.dat.  zstd = the reference's file; huff = canonical Huffman codes
     # written by the GPU (tezip_amd/huff.py; the reference cannot read such a file, -u recognises it by its magic); huffr = the
-    # same with repeat tokens for the payload's period-3 runs (tezip_amd/huffr.py), a smaller file under an error bound
-    (None, "--coder", dict(type=str, choices=("zstd", "huff", "huffr"), default="zstd", dest="coder")),
+    # same with repeat tokens for the payload's period-3 runs (tezip_amd/huffr.py), a smaller file under an error bound; huffd =
+    # one coder over both: it counts the payload at match distance none / 1 / 3 and codes at the cheapest (tezip_amd/huffd.py)
+    (None, "--coder", dict(type=str, choices=("zstd", "huff", "huffr", "huffd"), default="zstd", dest="coder")),
     # not in the reference: with -c, the coder of key_frame.dat.  zstd = the reference's file; huff = the key frames alone, as
     # predictor residuals Huffman-coded by the GPU (tezip_amd/keycoder.py; the reference cannot read such a file, -u recognises
     # it by its magic).  Much smaller on smooth frames, LARGER than zstd on sparse ones (README): check with --report's ratio.
@@ -144,7 +145,7 @@ def check_report_flag(arg):
 
 
 def check_coder_flag(arg):
-    """--coder huff / huffr is valid with -c of one single-GPU job, without --shuffle and --sweep.  Returns None, or the message
+    """--coder huff / huffr / huffd is valid with -c of one single-GPU job, without --shuffle and --sweep.  Returns None, or the message
     of a refusal."""
     if getattr(arg, "coder", "zstd") == "zstd":
         return None
