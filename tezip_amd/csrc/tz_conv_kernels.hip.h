@@ -68,7 +68,27 @@ struct ConvArgs {
     const float* e0_ahat;   // Ahat_0 at t0 [H*W][3]
     const int* e0_slot;
     long long e0_nstride;
+    // k_wino, gate convolutions: where `init` (G0) / `aux` (the cell state C0) are ONE value per column (measured bit for
+    // bit at prepare time, tz_prednet.hip measure_uniform): every pixel at least `ring` pixels away from all four edges of
+    // the plane holds the row `*_u` ([ncols] / [R]); ring < 0 or a null row: nowhere.  A tile inside that region skips the
+    // per-pixel loads.  A model with biases has such a region at its top level only: below it the constants REPEAT (collapsed
+    // taps are a chain per output parity, a level doubles the period of the one above), so there is a second, wider region,
+    // measured the same way: every pixel at least `*_tring` away from the edges equals the pixel at the same place (y mod 16,
+    // x mod 16) of the REFERENCE tile, the 16 x 16 tile at ref_tile_origin(H), ref_tile_origin(W).  A tile inside it reads the
+    // reference tile's values in place of its own: the same loads, from a block that stays in L2.  < 0: nowhere.
+    const float* init_u;
+    const float* aux_u;
+    int init_ring, aux_ring;
+    int init_tring, aux_tring;
 };
+
+// the reference tile of a plane: the 16 x 16 tile that holds the centre pixel
+__host__ __device__ __forceinline__ int ref_tile_origin(int extent) { return (extent >> 1) & ~15; }
+
+// (wave-uniform) the 16 x 16 tile at (y0, x0) of an H x W plane lies in the region where a constant is its uniform row
+__device__ __forceinline__ bool tile_uniform(const float* u, int ring, int y0, int x0, int H, int W) {
+    return u && ring >= 0 && y0 >= ring && y0 + 16 <= H - ring && x0 >= ring && x0 + 16 <= W - ring;
+}
 
 static constexpr int SA = 18;    // LDS row stride of one patch pixel (16 channels + 2 pad floats)
 static constexpr int PW = 18;    // same-resolution halo patch: PW x PW pixels around the 16x16 tile
@@ -1555,6 +1575,36 @@ __global__ __launch_bounds__(256) void k_to_fragments(const float* __restrict__ 
         const int y = (tile / tiles_x) * 16 + py, x = (tile % tiles_x) * 16 + px;
         dst[i] = (y < H && x < W) ? src[((long long)y * W + x) * ncols + cb * NT * 16 + nt * 16 + (lane & 15)] : 0.0f;
     }
+}
+
+// Prepare-time measurement of WHERE a per-pixel constant image src[H*W][ncols] is one value per column: compares every
+// pixel's columns with the centre pixel's as 32-bit patterns (-0, denormals and NaN count by identity) and leaves in *ring
+// (zeroed by the caller) 1 + the largest distance from the nearest edge of the plane at which a pixel differs -- the
+// smallest w such that every pixel at least w away from all four edges equals the centre pixel; 0: the whole plane does.
+// H * W * ncols < 2^30 (tz_model_prepare).
+// by_tile: the pixel is compared with the one at its place (y mod 16, x mod 16) in the reference tile instead (ConvArgs).
+__global__ __launch_bounds__(256) void k_uniform_ring(const unsigned* __restrict__ src, int H, int W, int ncols, int by_tile,
+                                                      int* __restrict__ ring) {
+    const unsigned* centre = src + ((size_t)(H / 2) * W + W / 2) * ncols;
+    const int ry = ref_tile_origin(H), rx = ref_tile_origin(W);   // (by_tile: H, W >= 16, tz_prednet.hip measure_uniform)
+    const unsigned total = (unsigned)H * (unsigned)W * (unsigned)ncols;
+    int mine = 0;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned pix = i / (unsigned)ncols, col = i - pix * (unsigned)ncols;
+        const int y = (int)(pix / (unsigned)W), x = (int)(pix - (unsigned)y * (unsigned)W);
+        const unsigned want = by_tile ? src[((size_t)(ry + (y & 15)) * W + rx + (x & 15)) * ncols + col] : centre[col];
+        if (src[i] != want) {
+            const int dy = y < H - 1 - y ? y : H - 1 - y, dx = x < W - 1 - x ? x : W - 1 - x;
+            const int w = (dy < dx ? dy : dx) + 1;
+            mine = w > mine ? w : mine;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int other = __shfl_xor(mine, o);
+        mine = other > mine ? other : mine;
+    }
+    if ((threadIdx.x & 63) == 0 && mine) atomicMax(ring, mine);
 }
 
 // level-0 error unit (prednet.py:274-277 with a = input frame, Ahat = Ahat_0(t0)):

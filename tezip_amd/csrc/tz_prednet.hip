@@ -43,6 +43,11 @@ struct PackedConv {
     std::vector<Seg> segs;
 };
 
+enum { UNI_G0 = 0, UNI_C0 = 1, UNI_AHAT0 = 2 };
+// bits of TEZIP_UNIFORM (measurements: one part at a time; 0 = the per-pixel loads everywhere): k_wino's start values, its cell state
+// and whether tiles that only REPEAT (the reference tile) take theirs
+enum { UNI_USE_WINO_INIT = 1, UNI_USE_WINO_CELL = 2, UNI_USE_TILES = 4, UNI_USE_ALL = 7 };
+
 struct tz_model {
     int L = 0;
     int stack[TZ_MAX_LEVELS] = {0}, rstack[TZ_MAX_LEVELS] = {0};
@@ -52,6 +57,13 @@ struct tz_model {
     bool prepared = false;
     float *R0[TZ_MAX_LEVELS] = {0}, *C0[TZ_MAX_LEVELS] = {0}, *Ahat0[TZ_MAX_LEVELS] = {0}, *G0[TZ_MAX_LEVELS] = {0};
     float *G0f[TZ_MAX_LEVELS] = {0}, *C0f[TZ_MAX_LEVELS] = {0};  // G0 / C0 in accumulator-fragment order (k_to_fragments)
+    // Where G0 / C0 / Ahat0 are one value per column (measure_uniform, tz_model_prepare): every pixel at least ring[k][l]
+    // pixels away from all four edges of the level's plane holds the centre pixel's row uni[k][l] (a pointer into the array);
+    // -1: nowhere.  k: UNI_G0, UNI_C0, UNI_AHAT0.
+    int ring[3][TZ_MAX_LEVELS] = {{0}};
+    int tring[3][TZ_MAX_LEVELS] = {{0}};   // ... outside this ring every 16 x 16 tile equals the reference tile (ConvArgs)
+    const float* uni[3][TZ_MAX_LEVELS] = {{0}};
+    int uniform_mask = 0;   // TEZIP_UNIFORM at prepare time: which consumers take the shortcut (UNI_USE_*), default all
     float *E[TZ_MAX_LEVELS] = {0}, *R1[TZ_MAX_LEVELS] = {0};
     float* P[TZ_MAX_LEVELS] = {0};   // gate accumulators after the E_l part of the chain (split launches of small grids), or null
     int Pcap[TZ_MAX_LEVELS] = {0};   // ... how many batch slots P[l] holds (<= maxB: at most kPBytes per level)
@@ -630,6 +642,82 @@ extern "C" int tz_model_load(tz_ctx* ctx, int nb_layers, const int* stack_sizes,
     return TZ_OK;
 }
 
+// Where the per-pixel, per-model constants are uniform.  G0_l, C0_l and Ahat0_l come from the t = 0 pass, whose input is all
+// zeros.  Nothing about them is assumed: k_uniform_ring compares every pixel bit for bit and returns the width of a border ring,
+// twice per array:
+//   * ring: outside it the whole plane is the centre pixel's row.  k_wino takes that row instead of the per-pixel loads of
+//     G0_l / C0_l (levels >= 1; ConvArgs::init_u / aux_u).  Zero biases (Keras' default initialisation, the bench's model):
+//     every constant is 0, ring 0, every tile.  A model with biases: the TOP level only (ring 1 for G0 / Ahat0: the zero
+//     padding; 0 for C0) -- below it r0_{l+1} is read through the x2 upsample with weights collapsed per output parity
+//     (TZ-PA1): four different fmaf chains, so the interior of level l repeats with period 2^(L-1-l) instead of being one value.
+//   * tring: outside it every 16 x 16 tile equals the REFERENCE tile (the one that holds the centre pixel), which covers any
+//     such period up to 16.  k_wino reads the reference tile in place of a tile inside (ConvArgs::init_tring / aux_tring):
+//     as many loads, all workgroups of a launch from one block.  Valid only if the reference tile itself lies inside.
+// Ahat0_l and level 0 are measured and logged as well; their consumers (the pool / error epilogues, k_conv16b) keep the
+// per-pixel loads: the shortcut measured nothing there (profiles/uniform_constants_2026-10-18.md).
+// TEZIP_UNIFORM (read here, per prepare): 0 = never, else a mask of UNI_USE_*; TEZIP_UNIFORM_LOG=1: one line per level and array.
+static bool tile_inside(int w, int y0, int x0, int H, int W) {   // (tile_uniform of the kernels)
+    return w >= 0 && y0 >= w && y0 + 16 <= H - w && x0 >= w && x0 + 16 <= W - w;
+}
+static int measure_uniform(tz_ctx* ctx, tz_model* m) {
+    const int L = m->L;
+    const char* env = getenv("TEZIP_UNIFORM");
+    m->uniform_mask = env ? atoi(env) & UNI_USE_ALL : UNI_USE_ALL;
+    for (int k = 0; k < 3; ++k)
+        for (int l = 0; l < TZ_MAX_LEVELS; ++l) {
+            m->ring[k][l] = m->tring[k][l] = -1;
+            m->uni[k][l] = nullptr;
+        }
+    int* d_ring = nullptr;
+    int h_ring[2][3][TZ_MAX_LEVELS] = {{{0}}};   // [by_tile][array][level]
+    if (m->uniform_mask) {
+        TZ_TRY(dmalloc(ctx, m, (void**)&d_ring, sizeof(h_ring)));
+        TZ_HIP(ctx, hipMemsetAsync(d_ring, 0, sizeof(h_ring), ctx->stream));
+    }
+    const float* const* arr[3] = {m->G0, m->C0, m->Ahat0};
+    for (int l = 0; l < L && m->uniform_mask; ++l) {
+        const int H = m->Hp >> l, W = m->Wp >> l;
+        const int nc[3] = {m->gate_t1[l].ncols, m->rstack[l], m->stack[l]};
+        for (int k = 0; k < 3; ++k)
+            for (int t = 0; t < (H >= 16 && W >= 16 ? 2 : 1); ++t) {
+                const long long total = (long long)H * W * nc[k];
+                hipLaunchKernelGGL(k_uniform_ring, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                                   (const unsigned*)arr[k][l], H, W, nc[k], t, d_ring + (t * 3 + k) * TZ_MAX_LEVELS + l);
+                TZ_HIP(ctx, hipGetLastError());
+            }
+    }
+    if (m->uniform_mask) TZ_HIP(ctx, hipMemcpyAsync(h_ring, d_ring, sizeof(h_ring), hipMemcpyDeviceToHost, ctx->stream));
+    TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    static const char* const names[3] = {"G0", "C0", "Ahat0"};
+    const bool log = getenv("TEZIP_UNIFORM_LOG") && atoi(getenv("TEZIP_UNIFORM_LOG"));
+    for (int l = 0; l < L; ++l) {
+        const int H = m->Hp >> l, W = m->Wp >> l;
+        const int nc[3] = {m->gate_t1[l].ncols, m->rstack[l], m->stack[l]};
+        for (int k = 0; k < 3; ++k) {
+            // (a ring that leaves no pixel: the centre pixel, H/2 W/2, is as far from the edges as a pixel gets)
+            const int far = std::min((H - 1) / 2, (W - 1) / 2);
+            if (m->uniform_mask && h_ring[0][k][l] <= far) {
+                m->ring[k][l] = h_ring[0][k][l];
+                m->uni[k][l] = arr[k][l] + ((size_t)(H / 2) * W + W / 2) * nc[k];
+            }
+            // (the reference tile stands in for others only where it is itself what the comparison says it is)
+            if ((m->uniform_mask & UNI_USE_TILES) && H >= 16 && W >= 16 &&
+                tile_inside(h_ring[1][k][l], ref_tile_origin(H), ref_tile_origin(W), H, W))
+                m->tring[k][l] = h_ring[1][k][l];
+            if (log) {
+                // w: the ring outside which a tile takes either shortcut
+                const int w1 = m->ring[k][l], wt = m->tring[k][l], w = wt >= 0 && (w1 < 0 || wt < w1) ? wt : w1;
+                int uniform = 0, tiles = ((H + 15) / 16) * ((W + 15) / 16);
+                for (int ty0 = 0; ty0 < H; ty0 += 16)
+                    for (int tx0 = 0; tx0 < W; tx0 += 16) uniform += tile_inside(w1, ty0, tx0, H, W) || tile_inside(wt, ty0, tx0, H, W);
+                fprintf(stderr, "[tezip] uniform constants, level %d %s (%dx%d): w %d, 16x16 tiles %d uniform %d non-uniform; one value: w %d, "
+                        "repeating tiles: w %d\n", l, names[k], H, W, w, uniform, tiles - uniform, w1, wt);
+            }
+        }
+    }
+    return TZ_OK;
+}
+
 extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
     tz_roctx_range roctx_("tz_model_prepare");
     if (!ctx) return TZ_ERR_INVALID;
@@ -795,7 +883,7 @@ extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
                          &m->a_conv[l]));
         if (l >= 1) TZ_TRY(pack_wino(ctx, m, {Seg{0, 2 * m->stack[l], 0}}, plain_cols(m->a_k(l), m->a_b(l), 2 * m->stack[l], Cout), NT, &m->a_conv[l]));
     }
-    TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    TZ_TRY(measure_uniform(ctx, m));   // (synchronises the stream)
     m->prepared = true;
     return TZ_OK;
 }
@@ -979,6 +1067,13 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
     // SAME launch as A_l (both only need E_l), leaves its accumulators in P_l, and the top-down pass
     // continues the chain over up(R_{l+1}) from there -- same fmaf chain, same bits, 108 + 54 slots off
     // the critical path of a cfg1 step.
+    // the uniform row and ring of constant k at level l, for the consumers TEZIP_UNIFORM leaves on (else: nowhere uniform)
+    auto set_uniform = [&](const float*& u, int& ring, int& tring, int k, int l, int use) {
+        const bool on = (m->uniform_mask & use) && m->ring[k][l] >= 0;
+        u = on ? m->uni[k][l] : nullptr;
+        ring = on ? m->ring[k][l] : -1;
+        tring = (m->uniform_mask & use) ? m->tring[k][l] : -1;
+    };
     auto gate_args = [&](int l, ConvArgs& a) {
         const PackedConv& pc = m->gate_t1[l];
         memset(&a, 0, sizeof(a));
@@ -995,6 +1090,10 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         a.auxf = m->C0f[l];
         a.out0_nstride = npx(l) * m->rstack[l];
         a.out0 = m->R1[l] + slot0 * a.out0_nstride;
+        // (k_wino only, levels >= 1: at level 0 and in the pool / error epilogues the shortcut measured nothing,
+        // profiles/uniform_constants_2026-10-18.md)
+        set_uniform(a.init_u, a.init_ring, a.init_tring, UNI_G0, l, l >= 1 ? UNI_USE_WINO_INIT : 0);
+        set_uniform(a.aux_u, a.aux_ring, a.aux_tring, UNI_C0, l, l >= 1 ? UNI_USE_WINO_CELL : 0);
     };
     auto aconv_args = [&](int l, ConvArgs& a) {
         const PackedConv& pc = m->a_conv[l];
@@ -1006,6 +1105,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         set_geom(a, hl(l), wl(l));
         a.Cout = m->stack[l + 1];
         a.aux = m->Ahat0[l + 1];
+        a.init_tring = a.aux_tring = -1;
         a.out0_nstride = npx(l + 1) * 2 * m->stack[l + 1];
         a.out0 = m->E[l + 1] + slot0 * a.out0_nstride;
     };
@@ -1033,8 +1133,10 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         ge.wino_stride = (ge.src[0].C + ge.src[1].C) >> 2;
         ge.wino_first = 0;
         ge.nsrc = 1;                      // the chains over E_l only
-        ge.initf = nullptr;
+        ge.initf = nullptr;           // (it starts from G0_l: the uniform row where the tile allows)
         ge.aux = ge.auxf = nullptr;
+        ge.aux_u = nullptr;
+        ge.aux_ring = ge.aux_tring = -1;
         ge.out0_nstride = npx(l) * ge.ncols;
         ge.out0 = m->P[l] + slot0 * ge.out0_nstride;
         ge.ipw = 1;   // short workgroups: a CU a side workgroup holds is one the critical path may be waiting for
@@ -1107,6 +1209,8 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
             a.init_nstride = npx(l) * a.ncols;
             a.init = m->P[l] + slot0 * a.init_nstride;
             a.initf = nullptr;
+            a.init_u = nullptr;   // (per item: nothing uniform about it)
+            a.init_ring = a.init_tring = -1;
             const LatPlan pu = lat_plan(ctx, 4, EPI_LSTM, true, a.src[0].C % 16 == 0, a, n);
             tz_prof_scope ps(ctx, TZP_CONV);
             ps.sub = TZP_CONVLAT;
@@ -1121,6 +1225,8 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
             a.init_nstride = npx(l) * a.ncols;
             a.init = m->P[l] + slot0 * a.init_nstride;
             a.initf = nullptr;
+            a.init_u = nullptr;   // (start values per item; the cell state may still be uniform)
+            a.init_ring = a.init_tring = -1;
             TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_epart_done[l], 0));
             tz_prof_scope ps(ctx, TZP_CONV);
             ps.sub = TZP_WINO;

@@ -468,10 +468,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         f32x4 in0[NT], in1[NT];
         {
             const int y = ty0 + 8 * (mt >> 1) + 2 * g + ph + per_item, x0 = tx0 + 8 * (mt & 1);
-            if (a.init && !(TZW_ABL & 64)) {
+            // (uniform) away from the border of the plane G0 is one value per column (ConvArgs::init_u): NT loads and a
+            // splat, the bias branch below, instead of 8 NT scattered ones
+            const bool uni_init = tile_uniform(a.init_u, a.init_ring, ty0, tx0, a.H, a.W);
+            if (a.init && !uni_init && !(TZW_ABL & 64)) {
                 const float* initn = a.init + (long long)n * a.init_nstride;   // (0 for the per-model G0; a split launch's start values are per item)
                 if (ty0 + 16 <= a.H && tx0 + 16 <= a.W) {   // (uniform) the whole tile inside the image: one lane offset, uniform steps
-                    const float* ip = initn + (unsigned)((y * a.W + x0) * a.ncols + cb * (16 * NT) + r);
+                    // (uniform) where G0 repeats tile by tile the reference tile stands in for this one (ConvArgs::init_tring):
+                    // every workgroup of the launch then reads the same block
+                    const bool rep = tile_uniform(a.init, a.init_tring, ty0, tx0, a.H, a.W);
+                    const int yr = rep ? y - ty0 + ref_tile_origin(a.H) : y, xr = rep ? x0 - tx0 + ref_tile_origin(a.W) : x0;
+                    const float* ip = initn + (unsigned)((yr * a.W + xr) * a.ncols + cb * (16 * NT) + r);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float* ie = ip + (unsigned)(2 * e * a.ncols);
@@ -496,9 +503,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     }
                 }
             } else {
+                const float* bu = uni_init && !(TZW_ABL & 64) ? a.init_u : a.bias;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
-                    const float b = a.bias[cb * (16 * NT) + 16 * t + r];
+                    const float b = bu[cb * (16 * NT) + 16 * t + r];
                     in0[t] = in1[t] = (f32x4){b, b, b, b};
                 }
             }
@@ -653,11 +661,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             char* p0 = (char*)o0;
             char* p1 = (char*)o1;
             float cpv[2][4];
+            if (tile_uniform(a.aux_u, a.aux_ring, ty0, tx0, a.H, a.W) && !(TZW_ABL & 256)) {
+                // (uniform) away from the border of the plane the cell state is one value per channel: one load
+                const float cu = a.aux_u[ch];
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
+                for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    cpv[b][e] = a.aux && !(TZW_ABL & 256) ? *(const float*)(pc + (size_t)(2 * e + b) * R * 4 + voff) : 0.0f;
+                    for (int e = 0; e < 4; ++e) cpv[b][e] = cu;
+            } else {
+                // (uniform) where the cell state repeats tile by tile: the reference tile's values (ConvArgs::aux_tring)
+                const unsigned roff = 4u * (unsigned)(((ref_tile_origin(a.H) - ty0) * a.W + ref_tile_origin(a.W) - tx0) * R);
+                const unsigned coff = tile_uniform(a.aux, a.aux_tring, ty0, tx0, a.H, a.W) ? voff + roff : voff;
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        cpv[b][e] = a.aux && !(TZW_ABL & 256) ? *(const float*)(pc + (size_t)(2 * e + b) * R * 4 + coff) : 0.0f;
+            }
 #ifdef TZW_STAMPS
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             TZW_STAMP(6)
