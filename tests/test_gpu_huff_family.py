@@ -1,4 +1,4 @@
-"""The staged decoders of the four coded formats (tz_huff_*, tz_huffr_*, tz_keys_*, tz_keysg_*) share their host code; each
+"""The staged decoders of the five coded formats (tz_huff_*, tz_huffr_*, tz_huffd_*, tz_keys_*, tz_keysg_*) share their host code; each
 must still refuse what it refused before, in the same words, and work after a refusal.  The expected texts are typed in
 from the source of the commit before the entry points were put on common code."""
 import numpy as np
@@ -21,7 +21,7 @@ def ctx():
 @pytest.fixture(scope="module")
 def streams(ctx):
     """{family: (body, the arguments of begin behind the byte count, check(context) of what it decoded)}: one valid stream per format."""
-    from tezip_amd import huff, huffr, keycoder, keycoderg
+    from tezip_amd import huff, huffd, huffr, keycoder, keycoderg
     rng = np.random.default_rng(5)
     pay = np.where(rng.random(N) < 0.1, rng.integers(-9, 10, N), np.array([3, -2, 7])[np.arange(N) % 3]).astype(np.int16)
     base = int(pay.min())
@@ -33,6 +33,8 @@ def streams(ctx):
         def check(c, pay=pay):
             assert (c.payload_get(0, N) == pay).all()
         out[name] = (body, (N, ln, base), check)
+    ln = huffd.lengths_of(huffd.token_counts(pay, base, int(pay.max()) - base + 1)[1], 1)      # the same payload at D = 1
+    out["huffd"] = (ctx.huffd_encode_buf(pay, ln, base, 1).copy(), (N, ln, base, 1), check)
     stack = np.zeros((2, 8, 8, 3), np.uint8)
     stack[0] = rng.integers(0, 256, (8, 8, 3))
     stack[1] = rng.integers(0, 256, (8, 8, 1))      # gray
@@ -61,11 +63,12 @@ def works(ctx, streams, name):
 
 
 PUT_TEXT = {"huff": "byte range outside the staged Huffman stream", "huffr": "byte range outside the staged Huffman stream",
+            "huffd": "byte range outside the staged Huffman stream",
             "keys": "byte range outside the staged key-frame stream", "keysg": "byte range outside the staged key-frame stream (TZK2)"}
-SIBLING = {"huff": "huffr", "huffr": "huff", "keys": "keysg", "keysg": "keys"}
+SIBLINGS = {"huff": ("huffr",), "huffr": ("huff",), "huffd": ("huffr", "huff"), "keys": ("keysg",), "keysg": ("keys",)}
 
 
-@pytest.mark.parametrize("name", ["huff", "huffr", "keys", "keysg"])
+@pytest.mark.parametrize("name", ["huff", "huffr", "huffd", "keys", "keysg"])
 def test_refusals_keep_their_words_and_leave_the_decoder_working(name, streams):
     from tezip_amd import _lib
     ctx = _lib.Context(0)                    # a context of its own: nothing is staged in it
@@ -79,19 +82,21 @@ def test_refusals_keep_their_words_and_leave_the_decoder_working(name, streams):
         begin(body.size, *args)
         refused(INVALID, PUT_TEXT[name], put, body.size - 3, body[:4])          # ends one byte behind the stream
         works(ctx, streams, name)
-        sib = SIBLING[name]
-        getattr(ctx, sib + "_begin")(streams[sib][0].size, *streams[sib][1])    # the sibling format's begin
-        refused(INVALID, PUT_TEXT[name], put, 0, body[:4])
-        refused(STATE, nothing, decode)
-        works(ctx, streams, sib)
-        works(ctx, streams, name)
-        if name in ("huff", "huffr"):
-            n, ln, base = args
-            refused(INVALID, "huffman: run length 128, this build codes runs of 256", begin, body.size, n, ln, base, run=128)
+        for sib in SIBLINGS[name]:
+            getattr(ctx, sib + "_begin")(streams[sib][0].size, *streams[sib][1])    # a sibling format's begin
+            refused(INVALID, PUT_TEXT[name], put, 0, body[:4])
+            refused(STATE, nothing, decode)
+            works(ctx, streams, sib)
+            works(ctx, streams, name)
+        if name in ("huff", "huffr", "huffd"):
+            n, ln, base, *dist = args         # (dist: huffd's D = 1)
+            refused(INVALID, "huffman: run length 128, this build codes runs of 256", begin, body.size, n, ln, base, *dist, run=128)
             index = 2 * 4 + 66 * 2            # two chunk offsets, ceil(N / 256) = 66 run sizes
             for nbytes in (body.size + 1, index - 4):
                 refused(INVALID, "huffman: a stream of %d bytes cannot hold the %d-byte index of %d elements and whole words" % (nbytes, index, N),
-                        begin, nbytes, n, ln, base)
+                        begin, nbytes, n, ln, base, *dist)
+            if name == "huffd":
+                refused(INVALID, "tz_huffd: match distance 2, the format knows 0 (no tokens), 1 and 3", begin, body.size, n, ln, base, 2)
         else:
             n = 2 * 8 * 8 * 3 if name == "keys" else 8 * 8 * 3 + 8 * 8
             index = 4 + 4                     # one chunk offset; 2 (keys: 384 symbols) or 1 (keysg: 256) run sizes, padded

@@ -1,7 +1,8 @@
-"""The four coded formats that share one Huffman stream (TZH1 `huff`, TZR1 `huffr`, TZK1 `keycoder`, TZK2 `keycoderg`) against
-what the commit before their common code wrote and refused: the SHA-256 of every `encode_file` and the text of every
-`parse` refusal were recorded there (tests/golden/huff_family_parent.json, written by tests/golden/make_huff_family.py)
-and are recomputed here.  No GPU."""
+"""The five coded formats that share one Huffman stream (TZH1 `huff`, TZR1 `huffr`, TZR2 `huffd`, TZK1 `keycoder`, TZK2
+`keycoderg`) against what the commit before their common code wrote and refused: the SHA-256 of every `encode_file` and the
+text of every `parse` refusal were recorded there (tests/golden/huff_family_parent.json, written by
+tests/golden/make_huff_family.py) and are recomputed here.  The `huffd` entries were recorded at the commit before huffd.py was
+put on huffr.py's tokeniser and decode loop, while it still held its own.  No GPU."""
 import hashlib
 import json
 import os
@@ -19,8 +20,8 @@ SIZES = (1, 255, 256, 257, 16383, 16384, 16385, 3 * 16384 + 5)   # around a run 
 def mods():
     from tezip_amd import build
     build.build()
-    from tezip_amd import huff, huffr, keycoder, keycoderg
-    return {"huff": huff, "huffr": huffr, "keycoder": keycoder, "keycoderg": keycoderg}
+    from tezip_amd import huff, huffd, huffr, keycoder, keycoderg
+    return {"huff": huff, "huffr": huffr, "huffd": huffd, "keycoder": keycoder, "keycoderg": keycoderg}
 
 
 @pytest.fixture(scope="module")
@@ -49,6 +50,22 @@ def payload_cases():
     for n in SIZES:
         for repeats in (True, False):
             yield "n%d_%s" % (n, "rep" if repeats else "norep"), payload(n, repeats)
+
+
+def stretches(n):
+    """int16[n]: distance-1 stretches of 2^k - 1 and 2^k matches (the `stretches` family of tests/test_gpu_huffd.py)."""
+    m = [v for k in range(8) for v in ((1 << k) - 1, 1 << k)]
+    groups = np.repeat(np.arange(len(m)) % 5 + 3 * (np.arange(len(m)) % 2), np.array(m) + 1)
+    return np.tile(groups, n // groups.size + 1)[:n].astype(np.int16)
+
+
+def huffd_cases():
+    yield from payload_cases()
+    yield "n16385_stretches", stretches(16385)
+
+
+HUFFD_DISTS = (None, 0, 1, 3)   # None: the distance the format's rule chooses
+NCASES = {"huff": 16, "huffr": 16, "huffd": 17 * len(HUFFD_DISTS), "keycoder": 12, "keycoderg": 12}
 
 
 def key_stack(nt, H, W, ngray, seed=0):
@@ -100,6 +117,26 @@ def digests(mods):
                 dec = M.decode_body(*_sections(M, data))
             assert dec.dtype == np.int16 and (dec == pay).all(), (k, name)
             out[k][name] = hashlib.sha256(data).hexdigest()
+    chosen = set()
+    for name, pay in huffd_cases():
+        M = mods["huffd"]
+        for dist in HUFFD_DISTS:
+            data = M.encode_file(pay, None, payload_shape(pay.size), 0, dist=dist)
+            D = M.HEADER.unpack(data[:48])[11]
+            if dist is None:
+                chosen.add(D)
+            else:
+                assert D == dist
+            if pay.size % 3 == 0:
+                dec, p = M.decode_file(data, key_len=pay.size)
+                assert p.n == pay.size and type(p) is M.Parsed and p.dist == D
+            else:
+                with pytest.raises(ValueError, match=r"entropy.dat \(huffd\): element count n = %d, the trailer's shape says %d" % (pay.size, max(pay.size // 3, 1) * 3)):
+                    M.decode_file(data)
+                dec = M.decode_body(*_sections(M, data), D)
+            assert dec.dtype == np.int16 and (dec == pay).all(), ("huffd", name, dist)
+            out["huffd"]["%s_d%s" % (name, "chosen" if dist is None else dist)] = hashlib.sha256(data).hexdigest()
+    assert chosen == {0, 1, 3}                               # the rule picks every distance somewhere in the cases
     for name, stack in key_cases():
         for k in ("keycoder", "keycoderg"):
             M = mods[k]
@@ -174,7 +211,7 @@ def corruptions(M, data, key):
 def good_files(mods):
     """One valid file per format, each of three chunks."""
     pay = payload(33000, True, seed=1)                       # 129 runs
-    out = {k: mods[k].encode_file(pay, None, (1, 1, 100, 110, 3), 0) for k in ("huff", "huffr")}
+    out = {k: mods[k].encode_file(pay, None, (1, 1, 100, 110, 3), 0) for k in ("huff", "huffr", "huffd")}
     out["keycoder"] = mods["keycoder"].encode_file(key_stack(3, 64, 64, 1, seed=1), np.arange(3), 3)    # 64 * 64 * 9 symbols
     out["keycoderg"] = mods["keycoderg"].encode_file(key_stack(3, 64, 80, 1, seed=1), np.arange(3), 3)  # 64 * 80 * 7 symbols
     return out
@@ -185,13 +222,19 @@ def refusals(mods):
     out = {}
     for k, data in good_files(mods).items():
         out[k] = {name: _refusal(mods[k], bad) for name, bad in corruptions(mods[k], data, k.startswith("key"))}
+    M, data = mods["huffd"], good_files(mods)["huffd"]       # the D field, the header's last u32
+    assert M.HEADER.unpack(data[:48])[11] == 3 and M.parse(data).lengths[-M.NTOK:].any()
+    at0 = M.encode_file(payload(33000, True, seed=1), None, (1, 1, 100, 110, 3), 0, dist=0)
+    out["huffd"]["dist_2"] = _refusal(M, _with_field(M, data, 11, 2))
+    out["huffd"]["dist_0_with_token_length"] = _refusal(M, _with_field(M, data, 11, 0))
+    out["huffd"]["dist_3_coded_at_0"] = _refusal(M, _with_field(M, at0, 11, 3))   # may parse: the index still checks
     return out
 
 
 def test_coded_bytes_are_the_parents(mods, parent):
     got = digests(mods)
     for k in got:
-        assert set(got[k]) == set(parent["digests"][k]) and len(got[k]) in (16, 12)
+        assert set(got[k]) == set(parent["digests"][k]) and len(got[k]) == NCASES[k]
         for name in got[k]:
             assert got[k][name] == parent["digests"][k][name], (k, name)
 
@@ -202,4 +245,5 @@ def test_parser_refusals_are_the_parents(mods, parent):
         assert set(got[k]) == set(parent["refusals"][k])
         for name in got[k]:
             assert got[k][name] == parent["refusals"][k][name], (k, name)
-        assert sum(v is None for v in got[k].values()) == 0, k   # every corruption above is refused
+        # every corruption above is refused, but for a TZR2 file coded at D = 0 that names D = 3, where the parent says so
+        assert {n for n, v in got[k].items() if v is None} <= ({"dist_3_coded_at_0"} if k == "huffd" else set()), k

@@ -225,6 +225,11 @@ def _numel(x):
     return int(x.numel()) if hasattr(x, "numel") else int(np.asarray(x).size)
 
 
+def _dist(dist):
+    """The match-distance argument of a tz_huffd_* call; the other families' calls have none."""
+    return () if dist is None else (int(dist),)
+
+
 class _Pinned:
     """Owner of one tz_host_alloc block (freed when the last numpy view goes away)."""
 
@@ -749,13 +754,23 @@ class Context:
         self._ck(self.lib.tz_decoded_digests(self.h, int(first), int(count), out.ctypes.data))
         return out
 
-    # ---- the opt-in coded streams.  Private helpers behind the four families below: `fn` is the library's entry point, `ntok` the
-    # repeat tokens behind the literals of `lengths` (the A the library is given is the number of literals), `what` names a
-    # pred array in a message.
-    def _stream_encode(self, fn, lengths, base, ntok):
+    # ---- the opt-in coded streams.  Private helpers behind the five families below: `fn` is the library's entry point, `ntok` the
+    # repeat tokens behind the literals of `lengths` (the A the library is given is the number of literals), `dist` the match
+    # distance where the entry point takes one (tz_huffd_*), `what` names a pred array in a message.
+    def _stream_counts(self, fn, fn_buf, x, rows):
+        """-> (uint64[rows][A + 8], base) of the resident payload, or of the int16 array x"""
+        counts = np.zeros((rows, TZ_NBINS + HUFFR_NTOK), np.uint64)
+        a, base = C.c_int(0), C.c_int(0)
+        if x is None:
+            self._ck(fn(self.h, counts.ctypes.data, C.byref(a), C.byref(base)))
+        else:
+            self._ck(fn_buf(self.h, _ptr(x), _numel(x), counts.ctypes.data, C.byref(a), C.byref(base)))
+        return counts[:, : a.value + HUFFR_NTOK].copy(), base.value
+
+    def _stream_encode(self, fn, lengths, base, ntok, dist=None):
         ln = np.ascontiguousarray(lengths, np.uint8)
         nbytes = C.c_size_t(0)
-        self._ck(fn(self.h, ln.ctypes.data, int(ln.size) - ntok, int(base), C.byref(nbytes)))
+        self._ck(fn(self.h, ln.ctypes.data, int(ln.size) - ntok, int(base), *_dist(dist), C.byref(nbytes)))
         return int(nbytes.value)
 
     def _stream_get(self, fn, offset, count, out):
@@ -764,27 +779,27 @@ class Context:
         self._ck(fn(self.h, int(offset), int(count), _ptr(out, np.uint8)))
         return out
 
-    def _stream_begin(self, fn, nbytes, n, lengths, base, run, ntok):
+    def _stream_begin(self, fn, nbytes, n, lengths, base, run, ntok, dist=None):
         ln = np.ascontiguousarray(lengths, np.uint8)
-        self._ck(fn(self.h, int(nbytes), int(n), ln.ctypes.data, int(ln.size) - ntok, int(base), int(run)))
+        self._ck(fn(self.h, int(nbytes), int(n), ln.ctypes.data, int(ln.size) - ntok, int(base), int(run), *_dist(dist)))
 
     def _stream_put(self, fn, offset, piece):
         self._ck(fn(self.h, int(offset), _numel(piece), _ptr(piece, np.uint8)))
 
-    def _stream_encode_buf(self, fn, x, lengths, base, out, ntok):
+    def _stream_encode_buf(self, fn, x, lengths, base, out, ntok, dist=None):
         ln = np.ascontiguousarray(lengths, np.uint8)
         n = _numel(x)
         if out is None:   # the most a stream can need: 12 bits per element, a pad word per chunk, the index
             out = np.empty(n * 3 // 2 + (n // 16384 + 1) * 8 + (n // 256 + 1) * 2 + 64, np.uint8)
         nbytes = C.c_size_t(0)
-        self._ck(fn(self.h, _ptr(x), n, ln.ctypes.data, int(ln.size) - ntok, int(base), _ptr(out), _numel(out), C.byref(nbytes)))
+        self._ck(fn(self.h, _ptr(x), n, ln.ctypes.data, int(ln.size) - ntok, int(base), *_dist(dist), _ptr(out), _numel(out), C.byref(nbytes)))
         return out[: nbytes.value]
 
-    def _stream_decode_buf(self, fn, stream, n, lengths, base, run, out, ntok):
+    def _stream_decode_buf(self, fn, stream, n, lengths, base, run, out, ntok, dist=None):
         ln = np.ascontiguousarray(lengths, np.uint8)
         if out is None:
             out = np.empty(n, np.int16)
-        self._ck(fn(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size) - ntok, int(base), int(run), _ptr(out)))
+        self._ck(fn(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size) - ntok, int(base), int(run), *_dist(dist), _ptr(out)))
         return out
 
     @staticmethod
@@ -947,13 +962,8 @@ class Context:
     def huffr_counts(self, x=None):
         """Token counts of the resident payload (or of the int16 array x) -> (uint64[A + 8], base): the literals s + base,
         then the repeat tokens T_0..T_7."""
-        counts = np.zeros(TZ_NBINS + HUFFR_NTOK, np.uint64)
-        a, base = C.c_int(0), C.c_int(0)
-        if x is None:
-            self._ck(self.lib.tz_huffr_counts(self.h, counts.ctypes.data, C.byref(a), C.byref(base)))
-        else:
-            self._ck(self.lib.tz_huffr_counts_buf(self.h, _ptr(x), _numel(x), counts.ctypes.data, C.byref(a), C.byref(base)))
-        return counts[: a.value + HUFFR_NTOK].copy(), base.value
+        counts, base = self._stream_counts(self.lib.tz_huffr_counts, self.lib.tz_huffr_counts_buf, x, 1)
+        return counts[0], base
 
     def huffr_encode(self, lengths, base):
         """Code the resident payload into the resident stream (index | bits); returns its size in bytes."""
@@ -983,27 +993,17 @@ class Context:
     def huffd_counts(self, x=None):
         """The three token histograms of the resident payload (or of the int16 array x), from one read of it ->
         (uint64[3][A + 8], base): row 0 without tokens, row 1 at match distance 1, row 2 at distance 3."""
-        counts = np.zeros((3, TZ_NBINS + HUFFR_NTOK), np.uint64)
-        a, base = C.c_int(0), C.c_int(0)
-        if x is None:
-            self._ck(self.lib.tz_huffd_counts(self.h, counts.ctypes.data, C.byref(a), C.byref(base)))
-        else:
-            self._ck(self.lib.tz_huffd_counts_buf(self.h, _ptr(x), _numel(x), counts.ctypes.data, C.byref(a), C.byref(base)))
-        return counts[:, : a.value + HUFFR_NTOK].copy(), base.value
+        return self._stream_counts(self.lib.tz_huffd_counts, self.lib.tz_huffd_counts_buf, x, 3)
 
     def huffd_encode(self, lengths, base, dist):
         """Code the resident payload into the resident stream (index | bits) at the match distance dist; returns its size."""
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        nbytes = C.c_size_t(0)
-        self._ck(self.lib.tz_huffd_encode(self.h, ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), int(dist), C.byref(nbytes)))
-        return int(nbytes.value)
+        return self._stream_encode(self.lib.tz_huffd_encode, lengths, base, HUFFR_NTOK, dist)
 
     def huffd_get(self, offset, count, out=None):
         return self._stream_get(self.lib.tz_huffd_get, offset, count, out)
 
     def huffd_begin(self, nbytes, n, lengths, base, dist, run=256):
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        self._ck(self.lib.tz_huffd_begin(self.h, int(nbytes), int(n), ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), int(run), int(dist)))
+        self._stream_begin(self.lib.tz_huffd_begin, nbytes, n, lengths, base, run, HUFFR_NTOK, dist)
 
     def huffd_put(self, offset, piece):
         self._stream_put(self.lib.tz_huffd_put, offset, piece)
@@ -1013,22 +1013,10 @@ class Context:
 
     def huffd_encode_buf(self, x, lengths, base, dist, out=None):
         """Stand-alone: int16 values (host or device) -> the coded stream (index | bits) as a uint8 array."""
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        n = _numel(x)
-        if out is None:   # the most a stream can need: 12 bits per element, a pad word per chunk, the index
-            out = np.empty(n * 3 // 2 + (n // 16384 + 1) * 8 + (n // 256 + 1) * 2 + 64, np.uint8)
-        nbytes = C.c_size_t(0)
-        self._ck(self.lib.tz_huffd_encode_buf(self.h, _ptr(x), n, ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base), int(dist), _ptr(out),
-                                              _numel(out), C.byref(nbytes)))
-        return out[: nbytes.value]
+        return self._stream_encode_buf(self.lib.tz_huffd_encode_buf, x, lengths, base, out, HUFFR_NTOK, dist)
 
     def huffd_decode_buf(self, stream, n, lengths, base, dist, run=256, out=None):
-        ln = np.ascontiguousarray(lengths, np.uint8)
-        if out is None:
-            out = np.empty(n, np.int16)
-        self._ck(self.lib.tz_huffd_decode_buf(self.h, _ptr(stream), _numel(stream), int(n), ln.ctypes.data, int(ln.size) - HUFFR_NTOK, int(base),
-                                              int(run), int(dist), _ptr(out)))
-        return out
+        return self._stream_decode_buf(self.lib.tz_huffd_decode_buf, stream, n, lengths, base, run, out, HUFFR_NTOK, dist)
 
     # ---- operator seams
     def delta_encode(self, pred, orig, zero_mask=None, out=None):

@@ -339,32 +339,28 @@ class _Done:
         return self.value
 
 
+# CODER -> (the format's module, whether the coder chooses a match distance); the name is also the prefix of the Context's methods
+_HUFF_CODERS = {"huff": (huff, False), "huffr": (huffr, False), "huffd": (huffd, True)}
+
+
 def _huff_entropy_file(ctx, path, n, trailer, verbose, coder="huff"):
     """entropy.dat of CODER="huff" / "huffr" / "huffd": the resident payload is coded on the device (tz_huff_encode /
     tz_huffr_encode / tz_huffd_encode) and only the coded stream crosses to the host; the header, the reference trailer and the
     code lengths go in front of it.  huffd: one read of the payload counts it under the three match distances, the distance
     and its code are chosen here from those counts (huffd.choose), and one line says which."""
     t0 = time.perf_counter()
-    if coder == "huffd":
-        counts3, base = ctx.huffd_counts()
-        dist, lengths, costs = huffd.choose(counts3)
+    fmt, has_dist = _HUFF_CODERS[coder]
+    counts, base = getattr(ctx, coder + "_counts")()
+    if has_dist:
+        dist, lengths, costs = fmt.choose(counts)
         print("coder: huffd, match distance %d (bits: none %d, 1: %d, 3: %d)" % ((dist,) + tuple(costs)))
-        nbytes = ctx.huffd_encode(lengths, base, dist)
-        nruns, nchunks = huff.geometry(n)
-        front = huffd.pack_front(trailer, lengths, base, n, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4, dist)
-        return _write_coded(path, front, nbytes, ctx.huffd_get, "huffman_coding" if verbose else None, t0)
-    if coder == "huffr":
-        fmt = huffr
-        counts, base = ctx.huffr_counts()
-        lengths = huffr.code_lengths(counts)
-        nbytes = ctx.huffr_encode(lengths, base)
+        extra = (dist,)                               # (what encode and pack_front take behind the other coders' arguments)
     else:
-        fmt = huff
-        counts, base = ctx.huff_counts()
-        lengths = huff.code_lengths(counts)
-        nbytes = ctx.huff_encode(lengths, base)
+        extra, lengths = (), fmt.code_lengths(counts)
+    nbytes = getattr(ctx, coder + "_encode")(lengths, base, *extra)
     nruns, nchunks = huff.geometry(n)
-    front = fmt.pack_front(trailer, lengths, base, n, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4)
+    front = fmt.pack_front(trailer, lengths, base, n, nchunks, (nbytes - huff.body_bytes(n, 0)) // 4, *extra)
+    # (the three coders leave ONE resident stream: huffr_get and huffd_get are other names of huff_get)
     return _write_coded(path, front, nbytes, ctx.huff_get, "huffman_coding" if verbose else None, t0)
 
 

@@ -2435,18 +2435,21 @@ extern "C" int tz_huffr_lengths(const unsigned long long* counts, int total, int
     return huff_package_merge(counts, total, TZ_NBINS + TZ_HUFFR_NTOK, max_len, lengths);
 }
 
+// the repeat tokens behind the literals of a code at the match distance dist (0: a stream without tokens)
+static int huff_ntok(int dist) { return dist ? TZ_HUFFR_NTOK : 0; }
+
 // The two tables of a code given by its lengths (canonical: shorter first, then by symbol; stored bit-reversed):
 // enc[s] = stored code | length << 12 (0: absent), dec[next 12 bits] = symbol | length << 12.  Checks everything a launch
-// depends on: A, base, lengths <= 12, at least one symbol, Kraft sum <= 1.  ntok > 0 (TZR1): `lengths` holds ntok more
-// symbols behind the A literals, the repeat tokens; A and base still describe the literals, one of which must be present.
-static int huff_tables(tz_ctx* ctx, const uint8_t* lengths, int A, int base, std::vector<uint16_t>* enc, std::vector<uint16_t>* dec,
-                       int ntok = 0) {
+// depends on: A, base, lengths <= 12, at least one symbol, Kraft sum <= 1.  dist: the match distance of the stream (see HuffFmt
+// below); a tokenised one (dist != 0) has TZ_HUFFR_NTOK more symbols in `lengths` behind the A literals, the repeat tokens; A
+// and base still describe the literals, one of which must be present.
+static int huff_tables(tz_ctx* ctx, const uint8_t* lengths, int A, int base, std::vector<uint16_t>* enc, std::vector<uint16_t>* dec, int dist) {
     if (!lengths || A < 1 || A > TZ_NBINS) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: alphabet size %d outside [1, %d]", A, TZ_NBINS);
     if (base < -32768 || base + A - 1 > 32767) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: base %d with %d symbols leaves int16", base, A);
     unsigned long long kraft = 0;
     int first = -1;
     const int lits = A;
-    A += ntok;
+    A += huff_ntok(dist);
     for (int s = 0; s < A; ++s) {
         if (lengths[s] > TZ_HUFF_L) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: code length %d of symbol %d exceeds %d", lengths[s], s, TZ_HUFF_L);
         if (lengths[s]) {
@@ -2481,14 +2484,14 @@ static void huff_geometry(size_t n, size_t* nruns, size_t* nchunks, size_t* inde
 }
 
 // d_in (device, n int16) -> ctx->d_huff = index | bits; *bytes its size.  Waits once, for the size of the bit stream.
-// ntok: TZ_HUFFR_NTOK for the TZR1 stream (lengths then holds A + ntok entries, k_huffr_size / k_huffr_enc), 0 for TZH1.
+// dist: the match distance, 0 for a stream without tokens (k_huff_size / k_huff_enc), else 1 or 3 (lengths then holds A +
+// TZ_HUFFR_NTOK entries, k_huffr_size / k_huffr_enc at that distance).
 // keys: the stream goes to the key-frame coder's buffer ctx->d_keys instead, and what the entropy coders hold stays.
-// dist: the match distance of a tokenised stream (3: TZR1; a TZR2 stream names 1 or 3).
-static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uint8_t* lengths, int A, int base, size_t* bytes, int ntok,
-                           bool keys = false, int dist = 3) {
+static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uint8_t* lengths, int A, int base, size_t* bytes, int dist,
+                           bool keys) {
     if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
     std::vector<uint16_t> enc;
-    TZ_TRY(huff_tables(ctx, lengths, A, base, &enc, nullptr, ntok));
+    TZ_TRY(huff_tables(ctx, lengths, A, base, &enc, nullptr, dist));
     size_t nruns, nchunks, index_bytes;
     huff_geometry(n, &nruns, &nchunks, &index_bytes);
     void *d_enc, *d_idx, *d_meta;
@@ -2499,7 +2502,7 @@ static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uin
     TZ_HIP(ctx, hipMemsetAsync(d_idx, 0, index_bytes, ctx->stream));   // (the padding behind an odd number of run sizes is part of the file)
     unsigned* d_chunk_off = (unsigned*)d_idx;
     uint16_t* d_run_bits = (uint16_t*)((uint8_t*)d_idx + nchunks * 4);
-    TZ_TRY(tzk_huff_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, ntok, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta, dist));
+    TZ_TRY(tzk_huff_size(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (tz_huff_meta*)d_meta, dist));
     tz_huff_meta meta;
     TZ_TRY(tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream));
     TZ_TRY(tz_stream_sync(ctx));
@@ -2519,7 +2522,7 @@ static int huff_encode_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, const uin
         d_stream = ctx->d_huff;
     }
     TZ_HIP(ctx, hipMemcpyAsync(d_stream, d_idx, index_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, ntok, d_run_bits, d_chunk_off, (unsigned*)(d_stream + index_bytes),
+    TZ_TRY(tzk_huff_enc(ctx, d_in, n, (const uint16_t*)d_enc, A, base, d_run_bits, d_chunk_off, (unsigned*)(d_stream + index_bytes),
                         (size_t)meta.total_words, dist));
     *bytes = total;
     return TZ_OK;
@@ -2539,39 +2542,52 @@ static int huff_check_stream(tz_ctx* ctx, size_t bytes, size_t n, int R, size_t*
 }
 
 static int huff_decode_dev(tz_ctx* ctx, const uint8_t* d_stream, size_t stream_words, size_t n, const std::vector<uint16_t>& dec, int A, int base,
-                           int ntok, int16_t* d_out, int dist = 3) {
+                           int dist, int16_t* d_out) {
     size_t nruns, nchunks, index_bytes;
     huff_geometry(n, &nruns, &nchunks, &index_bytes);
     void* d_dec;
     TZ_TRY(tz_pool_alloc(ctx, dec.size() * 2, &d_dec));
     TZ_TRY(tz_upload(ctx, d_dec, dec.data(), dec.size() * 2));
     return tzk_huff_dec(ctx, (const unsigned*)d_stream, (const uint16_t*)(d_stream + nchunks * 4), (const unsigned*)(d_stream + index_bytes),
-                        stream_words, (const uint16_t*)d_dec, A, base, ntok, n, d_out, dist);
+                        stream_words, (const uint16_t*)d_dec, A, base, n, d_out, dist);
 }
 
-// One body per entry point of the two entropy coders, `--coder huff` (TZH1, ntok == 0) and `--coder huffr` (TZR1, ntok ==
-// TZ_HUFFR_NTOK: the runs are tokenised first, tezip_amd/huffr.py, and `lengths` holds A + 8 bytes).  `who` is the entry
-// point's family, "tz_huff" or "tz_huffr", for the messages.  Both stage into the same buffers; ctx->huff_kind says which
-// format's begin did, so each put and decode refuses the other's stream.  `--coder huffd` (TZR2, tezip_amd/huffd.py) runs the
-// same bodies: its match distance D says which of the two kernel families codes the stream (0: TZH1's, 1 or 3: TZR1's at that
-// distance), `lengths` always holds A + 8 bytes, and its streams are of a third kind.
-static tz_ctx::tz_huff_kind huff_kind_of(int ntok) { return ntok ? tz_ctx::HUFF_TZR1 : tz_ctx::HUFF_TZH1; }
+// One body per entry point of the three entropy coders, which are ONE coder at three match distances: what tells them apart
+// is a HuffFmt.  dist == 0: no element matches, the stream is the plain one of the k_huff_* kernels and `lengths` holds A
+// bytes (`--coder huff`, TZH1).  dist == 1 or 3: the runs are tokenised first (tezip_amd/huffr.py), the k_huffr_* kernels run at
+// that distance and `lengths` holds A + 8 bytes (`--coder huffr`, TZR1, is dist == 3).  `--coder huffd` (TZR2,
+// tezip_amd/huffd.py) names its distance D per stream: 0, 1 or 3, `lengths` always A + 8 bytes, the eight token lengths 0 under
+// D == 0.  `who` is the entry point's family for the messages.  All stage into the same buffers; ctx->huff_kind says which
+// format's begin did, so each put and decode refuses another's stream (a TZR1 stream and a TZR2 one at D == 3 too), and
+// ctx->huff_dist holds the staged stream's distance, which is all that decode needs to pick its kernel.
+struct HuffFmt {
+    tz_ctx::tz_huff_kind kind;
+    int dist;
+    const char* who;
+};
+static constexpr HuffFmt FMT_TZH1{tz_ctx::HUFF_TZH1, 0, "tz_huff"}, FMT_TZR1{tz_ctx::HUFF_TZR1, 3, "tz_huffr"};
+// (a TZR2 descriptor exists per stream only, huffd_family fills it: put and decode, which know no D, take the kind and the name)
 
-// the counts of n device elements: the A literals from the lowest to the highest value present, then the ntok tokens
-static int huff_counts_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, int ntok, const char* who, unsigned long long* counts, int* A, int* base) {
+typedef int (*huff_count_launch)(tz_ctx*, const int16_t*, size_t, unsigned long long*, tz_huff_meta*);
+
+// the counts of n device elements, `rows` rows (1, or huffd's 3: match distance 0 | 1 | 3) of TZ_NBINS + ntok entries as `launch`
+// leaves them: the A literals from the lowest to the highest value present, then the ntok tokens, then zeros
+static int huff_counts_dev(tz_ctx* ctx, const char* who, int ntok, int rows, huff_count_launch launch, const int16_t* d_in, size_t n,
+                           unsigned long long* counts, int* A, int* base) {
+    const int BINS = TZ_HUFF_COUNT_BINS + ntok, ROW = TZ_NBINS + ntok;
     void *d_hist, *d_meta;
-    std::vector<unsigned long long> h(TZ_HUFF_COUNT_BINS + ntok);
+    std::vector<unsigned long long> h((size_t)rows * BINS);
     tz_huff_meta meta;
     int rc = tz_pool_alloc(ctx, h.size() * sizeof(unsigned long long), &d_hist);
     if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta);
-    if (rc == TZ_OK)
-        rc = ntok ? tzk_huffr_count(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta)
-                  : tzk_huff_count(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
+    if (rc == TZ_OK) rc = launch(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
     if (rc == TZ_OK) rc = tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream);
     if (rc == TZ_OK) rc = tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream);
     if (rc == TZ_OK) rc = tz_stream_sync(ctx);
     TZ_TRY(rc);
-    int lo = -1, hi = -1;   // (every value of a run is a literal at its first occurrence there: the literals span the values)
+    // Row 0 alone gives the span.  Every value of a run is a literal at its first occurrence there, so the literals of a
+    // tokenised row span the values; huffd's row 0 counts every element, and its other rows' literals span the same values.
+    int lo = -1, hi = -1;
     for (int b = 0; b < TZ_HUFF_COUNT_BINS; ++b)
         if (h[b]) {
             if (lo < 0) lo = b;
@@ -2580,35 +2596,45 @@ static int huff_counts_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, int ntok,
     if (meta.bad || lo < 0 || hi - lo + 1 > TZ_NBINS)
         return tz_fail(ctx, TZ_ERR_INVALID, "%s_counts: the payload's values span more than %d symbols", who, TZ_NBINS);
     const int a = hi - lo + 1;
-    for (int s = 0; s < TZ_NBINS + ntok; ++s) counts[s] = s < a ? h[lo + s] : s < a + ntok ? h[TZ_HUFF_COUNT_BINS + s - a] : 0;
+    for (int d = 0; d < rows; ++d)
+        for (int s = 0; s < ROW; ++s)
+            counts[d * ROW + s] = s < a ? h[d * BINS + lo + s] : s < a + ntok ? h[d * BINS + TZ_HUFF_COUNT_BINS + s - a] : 0;
     *A = a;
     *base = lo - TZ_HUFF_COUNT_BIAS;
     return TZ_OK;
 }
 
-static int huff_counts(tz_ctx* ctx, int ntok, const char* who, unsigned long long* counts, int* A, int* base) {
+// in == NULL: the resident payload; else a stand-alone host or device array of n elements
+static int huff_counts(tz_ctx* ctx, const char* who, int ntok, int rows, huff_count_launch launch, const int16_t* in, size_t n,
+                       unsigned long long* counts, int* A, int* base) {
     if (!ctx || !counts || !A || !base) return TZ_ERR_INVALID;
-    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "%s_counts needs a resident payload (tz_encode with payload == NULL)", who);
-    const int rc = huff_counts_dev(ctx, ctx->d_payload, ctx->payload_len, ntok, who, counts, A, base);
+    const void* din = ctx->d_payload;
+    int rc = TZ_OK;
+    if (in)
+        rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    else if (!ctx->d_payload || !ctx->payload_len)
+        return tz_fail(ctx, TZ_ERR_STATE, "%s_counts needs a resident payload (tz_encode with payload == NULL)", who);
+    else
+        n = ctx->payload_len;
+    if (rc == TZ_OK) rc = huff_counts_dev(ctx, who, ntok, rows, launch, (const int16_t*)din, n, counts, A, base);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-static int huff_encode(tz_ctx* ctx, int ntok, const char* who, const uint8_t* lengths, int A, int base, size_t* bytes, int dist = 3) {
+static int huff_encode(tz_ctx* ctx, const HuffFmt& f, const uint8_t* lengths, int A, int base, size_t* bytes) {
     if (!ctx || !bytes) return TZ_ERR_INVALID;
-    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "%s_encode needs a resident payload (tz_encode with payload == NULL)", who);
-    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes, ntok, false, dist);
+    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "%s_encode needs a resident payload (tz_encode with payload == NULL)", f.who);
+    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes, f.dist, false);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-static int huff_begin(tz_ctx* ctx, int ntok, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
-                      tz_ctx::tz_huff_kind kind = tz_ctx::HUFF_NONE, int dist = 3) {
+static int huff_begin(tz_ctx* ctx, const HuffFmt& f, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
     if (!ctx) return TZ_ERR_INVALID;
     size_t sw;
     TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
     std::vector<uint16_t> dec;
-    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, ntok));
+    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, f.dist));
     ctx->huff_kind = tz_ctx::HUFF_NONE;
     ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload is about to receive the expanded stream
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_huff, &ctx->cap_huff, std::max<size_t>(bytes, 16)));
@@ -2619,8 +2645,8 @@ static int huff_begin(tz_ctx* ctx, int ntok, size_t bytes, size_t n, const uint8
     ctx->huff_base = base;
     ctx->huff_A = A;
     ctx->huff_n = n;
-    ctx->huff_dist = dist;
-    ctx->huff_kind = kind != tz_ctx::HUFF_NONE ? kind : huff_kind_of(ntok);
+    ctx->huff_dist = f.dist;
+    ctx->huff_kind = f.kind;
     TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
     return TZ_OK;
@@ -2635,26 +2661,24 @@ static int huff_put(tz_ctx* ctx, tz_ctx::tz_huff_kind kind, size_t offset, size_
 
 static int huff_decode(tz_ctx* ctx, tz_ctx::tz_huff_kind kind, const char* who) {
     if (!ctx) return TZ_ERR_INVALID;
-    // (a staged TZR2 stream carries its match distance: none = the TZH1 kernels, else the tokenised ones at that distance)
-    const int dist = kind == tz_ctx::HUFF_TZR2 ? ctx->huff_dist : 3, ntok = kind == tz_ctx::HUFF_TZH1 || dist == 0 ? 0 : TZ_HUFFR_NTOK;
     if (ctx->huff_kind != kind || !ctx->d_huff || !ctx->d_payload || ctx->cap_payload < ctx->huff_n * 2)
         return tz_fail(ctx, TZ_ERR_STATE, "%s_decode needs a stream staged with %s_begin / %s_put", who, who, who);
     size_t sw;
     TZ_TRY(huff_check_stream(ctx, ctx->huff_bytes, ctx->huff_n, TZ_HUFF_RUN, &sw));
     TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of the puts
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
-    const int rc = huff_decode_dev(ctx, ctx->d_huff, sw, ctx->huff_n, ctx->huff_dec_tab, ctx->huff_A, ctx->huff_base, ntok, ctx->d_payload, dist);
+    const int rc = huff_decode_dev(ctx, ctx->d_huff, sw, ctx->huff_n, ctx->huff_dec_tab, ctx->huff_A, ctx->huff_base, ctx->huff_dist, ctx->d_payload);
     if (rc == TZ_OK) ctx->payload_len = ctx->huff_n;   // exactly as if tz_payload_begin / tz_payload_put had staged them
     tz_pool_release_all(ctx);
     return rc;
 }
 
-static int huff_encode_buf(tz_ctx* ctx, int ntok, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
-                           size_t capacity, size_t* bytes, int dist = 3) {
+static int huff_encode_buf(tz_ctx* ctx, const HuffFmt& f, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
+                           size_t capacity, size_t* bytes) {
     if (!ctx || !in || !out || !bytes) return TZ_ERR_INVALID;
     const void* din = nullptr;
     int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
-    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes, ntok, false, dist);
+    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes, f.dist, false);
     if (rc == TZ_OK && *bytes > capacity) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: the stream needs %zu bytes, the buffer holds %zu", *bytes, capacity);
     if (rc == TZ_OK) {
         if (tz_is_device_ptr(out)) {
@@ -2692,26 +2716,26 @@ static int buf_op(tz_ctx* ctx, const void* in, size_t in_bytes, unsigned in_mask
     return rc;
 }
 
-static int huff_decode_buf(tz_ctx* ctx, int ntok, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
-                           int16_t* out, int dist = 3) {
+static int huff_decode_buf(tz_ctx* ctx, const HuffFmt& f, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base,
+                           int R, int16_t* out) {
     if (!ctx || !stream || !out) return TZ_ERR_INVALID;
     size_t sw;
     TZ_TRY(huff_check_stream(ctx, bytes, n, R, &sw));
     std::vector<uint16_t> dec;
-    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, ntok));
+    TZ_TRY(huff_tables(ctx, lengths, A, base, nullptr, &dec, f.dist));
     return buf_op(ctx, stream, bytes, 3, out, n * 2, 0, "huffman: a device stream must be 4-byte aligned", [&](const void* din, void* dout) {
-        return huff_decode_dev(ctx, (const uint8_t*)din, sw, n, dec, A, base, ntok, (int16_t*)dout, dist);
+        return huff_decode_dev(ctx, (const uint8_t*)din, sw, n, dec, A, base, f.dist, (int16_t*)dout);
     });
 }
 
 extern "C" int tz_huff_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
     tz_roctx_range roctx_("tz_huff_counts");
-    return huff_counts(ctx, 0, "tz_huff", counts, A, base);
+    return huff_counts(ctx, "tz_huff", 0, 1, tzk_huff_count, nullptr, 0, counts, A, base);
 }
 
 extern "C" int tz_huff_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes) {
     tz_roctx_range roctx_("tz_huff_encode");
-    return huff_encode(ctx, 0, "tz_huff", lengths, A, base, bytes);
+    return huff_encode(ctx, FMT_TZH1, lengths, A, base, bytes);
 }
 
 extern "C" int tz_huff_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
@@ -2723,7 +2747,7 @@ extern "C" int tz_huff_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* ou
 }
 
 extern "C" int tz_huff_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
-    return huff_begin(ctx, 0, bytes, n, lengths, A, base, R);
+    return huff_begin(ctx, FMT_TZH1, bytes, n, lengths, A, base, R);
 }
 
 extern "C" int tz_huff_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) { return huff_put(ctx, tz_ctx::HUFF_TZH1, offset, count, src); }
@@ -2735,28 +2759,28 @@ extern "C" int tz_huff_decode(tz_ctx* ctx) {
 
 extern "C" int tz_huff_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
                                   size_t capacity, size_t* bytes) {
-    return huff_encode_buf(ctx, 0, in, n, lengths, A, base, out, capacity, bytes);
+    return huff_encode_buf(ctx, FMT_TZH1, in, n, lengths, A, base, out, capacity, bytes);
 }
 
 extern "C" int tz_huff_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
                                   int16_t* out) {
-    return huff_decode_buf(ctx, 0, stream, bytes, n, lengths, A, base, R, out);
+    return huff_decode_buf(ctx, FMT_TZH1, stream, bytes, n, lengths, A, base, R, out);
 }
 
 extern "C" int tz_huffr_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
     tz_roctx_range roctx_("tz_huffr_counts");
-    return huff_counts(ctx, TZ_HUFFR_NTOK, "tz_huffr", counts, A, base);
+    return huff_counts(ctx, "tz_huffr", TZ_HUFFR_NTOK, 1, tzk_huffr_count, nullptr, 0, counts, A, base);
 }
 
 extern "C" int tz_huffr_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, size_t* bytes) {
     tz_roctx_range roctx_("tz_huffr_encode");
-    return huff_encode(ctx, TZ_HUFFR_NTOK, "tz_huffr", lengths, A, base, bytes);
+    return huff_encode(ctx, FMT_TZR1, lengths, A, base, bytes);
 }
 
 extern "C" int tz_huffr_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) { return tz_huff_get(ctx, offset, count, out); }
 
 extern "C" int tz_huffr_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
-    return huff_begin(ctx, TZ_HUFFR_NTOK, bytes, n, lengths, A, base, R);
+    return huff_begin(ctx, FMT_TZR1, bytes, n, lengths, A, base, R);
 }
 
 extern "C" int tz_huffr_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
@@ -2770,29 +2794,24 @@ extern "C" int tz_huffr_decode(tz_ctx* ctx) {
 
 extern "C" int tz_huffr_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
                                    size_t capacity, size_t* bytes) {
-    return huff_encode_buf(ctx, TZ_HUFFR_NTOK, in, n, lengths, A, base, out, capacity, bytes);
+    return huff_encode_buf(ctx, FMT_TZR1, in, n, lengths, A, base, out, capacity, bytes);
 }
 
 extern "C" int tz_huffr_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
                                    int16_t* out) {
-    return huff_decode_buf(ctx, TZ_HUFFR_NTOK, stream, bytes, n, lengths, A, base, R, out);
+    return huff_decode_buf(ctx, FMT_TZR1, stream, bytes, n, lengths, A, base, R, out);
 }
 
 // the counts of a stand-alone host or device array, as tz_huffr_counts gives them for the resident payload
 extern "C" int tz_huffr_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* counts, int* A, int* base) {
-    if (!ctx || !in || !counts || !A || !base) return TZ_ERR_INVALID;
-    const void* din = nullptr;
-    int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
-    if (rc == TZ_OK) rc = huff_counts_dev(ctx, (const int16_t*)din, n, TZ_HUFFR_NTOK, "tz_huffr", counts, A, base);
-    tz_pool_release_all(ctx);
-    return rc;
+    return in ? huff_counts(ctx, "tz_huffr", TZ_HUFFR_NTOK, 1, tzk_huffr_count, in, n, counts, A, base) : TZ_ERR_INVALID;
 }
 
 // ---- `--coder huffd` (TZR2): the coder that picks its match distance
-// D must be 0, 1 or 3; *ntok = the tokens the kernels code with (none for D = 0, whose eight token lengths must be 0)
-static int huffd_family(tz_ctx* ctx, int D, const uint8_t* lengths, int A, int* ntok) {
+// D must be 0, 1 or 3, and the eight token lengths of D = 0 must be 0; *f = the descriptor of a TZR2 stream at that distance
+static int huffd_family(tz_ctx* ctx, int D, const uint8_t* lengths, int A, HuffFmt* f) {
     if (D != 0 && D != 1 && D != 3) return tz_fail(ctx, TZ_ERR_INVALID, "tz_huffd: match distance %d, the format knows 0 (no tokens), 1 and 3", D);
-    *ntok = D ? TZ_HUFFR_NTOK : 0;
+    *f = HuffFmt{tz_ctx::HUFF_TZR2, D, "tz_huffd"};
     if (D == 0 && lengths && A >= 1 && A <= TZ_NBINS)
         for (int k = 0; k < TZ_HUFFR_NTOK; ++k)
             if (lengths[A + k]) return tz_fail(ctx, TZ_ERR_INVALID, "tz_huffd: match distance 0 with a code length %d for the token T_%d", lengths[A + k], k);
@@ -2800,68 +2819,30 @@ static int huffd_family(tz_ctx* ctx, int D, const uint8_t* lengths, int A, int* 
 }
 
 // counts: three rows of TZ_NBINS + 8 entries (match distance 0 | 1 | 3), each the A literals, then T_0..T_7, then zeros
-static int huffd_counts_dev(tz_ctx* ctx, const int16_t* d_in, size_t n, unsigned long long* counts, int* A, int* base) {
-    constexpr int BINS = TZ_HUFF_COUNT_BINS + TZ_HUFFR_NTOK, ROW = TZ_NBINS + TZ_HUFFR_NTOK;
-    void *d_hist, *d_meta;
-    std::vector<unsigned long long> h(3 * BINS);
-    tz_huff_meta meta;
-    int rc = tz_pool_alloc(ctx, h.size() * sizeof(unsigned long long), &d_hist);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta);
-    if (rc == TZ_OK) rc = tzk_huffd_count(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
-    if (rc == TZ_OK) rc = tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream);
-    if (rc == TZ_OK) rc = tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
-    TZ_TRY(rc);
-    int lo = -1, hi = -1;   // (row 0 counts every element; the other rows' literals span the same values)
-    for (int b = 0; b < TZ_HUFF_COUNT_BINS; ++b)
-        if (h[b]) {
-            if (lo < 0) lo = b;
-            hi = b;
-        }
-    if (meta.bad || lo < 0 || hi - lo + 1 > TZ_NBINS)
-        return tz_fail(ctx, TZ_ERR_INVALID, "tz_huffd_counts: the payload's values span more than %d symbols", TZ_NBINS);
-    const int a = hi - lo + 1;
-    for (int d = 0; d < 3; ++d)
-        for (int s = 0; s < ROW; ++s)
-            counts[d * ROW + s] = s < a ? h[d * BINS + lo + s] : s < a + TZ_HUFFR_NTOK ? h[d * BINS + TZ_HUFF_COUNT_BINS + s - a] : 0;
-    *A = a;
-    *base = lo - TZ_HUFF_COUNT_BIAS;
-    return TZ_OK;
-}
-
 extern "C" int tz_huffd_counts(tz_ctx* ctx, unsigned long long* counts, int* A, int* base) {
     tz_roctx_range roctx_("tz_huffd_counts");
-    if (!ctx || !counts || !A || !base) return TZ_ERR_INVALID;
-    if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "tz_huffd_counts needs a resident payload (tz_encode with payload == NULL)");
-    const int rc = huffd_counts_dev(ctx, ctx->d_payload, ctx->payload_len, counts, A, base);
-    tz_pool_release_all(ctx);
-    return rc;
+    return huff_counts(ctx, "tz_huffd", TZ_HUFFR_NTOK, 3, tzk_huffd_count, nullptr, 0, counts, A, base);
 }
 
 extern "C" int tz_huffd_counts_buf(tz_ctx* ctx, const int16_t* in, size_t n, unsigned long long* counts, int* A, int* base) {
-    if (!ctx || !in || !counts || !A || !base) return TZ_ERR_INVALID;
-    const void* din = nullptr;
-    int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
-    if (rc == TZ_OK) rc = huffd_counts_dev(ctx, (const int16_t*)din, n, counts, A, base);
-    tz_pool_release_all(ctx);
-    return rc;
+    return in ? huff_counts(ctx, "tz_huffd", TZ_HUFFR_NTOK, 3, tzk_huffd_count, in, n, counts, A, base) : TZ_ERR_INVALID;
 }
 
 extern "C" int tz_huffd_encode(tz_ctx* ctx, const uint8_t* lengths, int A, int base, int D, size_t* bytes) {
     tz_roctx_range roctx_("tz_huffd_encode");
     if (!ctx || !bytes) return TZ_ERR_INVALID;
-    int ntok;
-    TZ_TRY(huffd_family(ctx, D, lengths, A, &ntok));
-    return huff_encode(ctx, ntok, "tz_huffd", lengths, A, base, bytes, D);
+    HuffFmt f;
+    TZ_TRY(huffd_family(ctx, D, lengths, A, &f));
+    return huff_encode(ctx, f, lengths, A, base, bytes);
 }
 
 extern "C" int tz_huffd_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) { return tz_huff_get(ctx, offset, count, out); }
 
 extern "C" int tz_huffd_begin(tz_ctx* ctx, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R, int D) {
     if (!ctx) return TZ_ERR_INVALID;
-    int ntok;
-    TZ_TRY(huffd_family(ctx, D, lengths, A, &ntok));
-    return huff_begin(ctx, ntok, bytes, n, lengths, A, base, R, tz_ctx::HUFF_TZR2, D);
+    HuffFmt f;
+    TZ_TRY(huffd_family(ctx, D, lengths, A, &f));
+    return huff_begin(ctx, f, bytes, n, lengths, A, base, R);
 }
 
 extern "C" int tz_huffd_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
@@ -2876,17 +2857,17 @@ extern "C" int tz_huffd_decode(tz_ctx* ctx) {
 extern "C" int tz_huffd_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, int D, uint8_t* out,
                                    size_t capacity, size_t* bytes) {
     if (!ctx) return TZ_ERR_INVALID;
-    int ntok;
-    TZ_TRY(huffd_family(ctx, D, lengths, A, &ntok));
-    return huff_encode_buf(ctx, ntok, in, n, lengths, A, base, out, capacity, bytes, D);
+    HuffFmt f;
+    TZ_TRY(huffd_family(ctx, D, lengths, A, &f));
+    return huff_encode_buf(ctx, f, in, n, lengths, A, base, out, capacity, bytes);
 }
 
 extern "C" int tz_huffd_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R,
                                    int D, int16_t* out) {
     if (!ctx) return TZ_ERR_INVALID;
-    int ntok;
-    TZ_TRY(huffd_family(ctx, D, lengths, A, &ntok));
-    return huff_decode_buf(ctx, ntok, stream, bytes, n, lengths, A, base, R, out, D);
+    HuffFmt f;
+    TZ_TRY(huffd_family(ctx, D, lengths, A, &f));
+    return huff_decode_buf(ctx, f, stream, bytes, n, lengths, A, base, R, out);
 }
 
 // --------------------------------------------------------------------------- key-frame coder (TZK1)
@@ -2960,7 +2941,7 @@ static int keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pr
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
     TZ_TRY(keys_upload(ctx, idx, pred, nkeys, &d_idx, &d_pred));
     TZ_TRY(tzk_key_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, d_pred, nkeys, ctx->d_keysym));
-    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);
+    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);   // (dist 0: plain TZH1 codes)
 }
 
 extern "C" int tz_keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths, size_t* bytes) {
@@ -3046,7 +3027,7 @@ static int keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* p
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
     TZ_TRY(keysg_upload(ctx, idx, predg, off, nkeys, &d_idx, &d_predg, &d_off));
     TZ_TRY(tzk_keyg_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, d_predg, d_off, nkeys, ctx->d_keysym));
-    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);
+    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);   // (dist 0: plain TZH1 codes)
 }
 
 extern "C" int tz_keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* predg, const uint8_t* lengths, size_t* bytes) {
@@ -3095,7 +3076,7 @@ static int keys_begin(tz_ctx* ctx, tz_ctx::tz_keys_kind kind, size_t bytes, int 
     if (kind == tz_ctx::KEYS_TZK2) TZ_TRY(keysg_layout(ctx, pred, nkeys, H, W, &off, &n));
     TZ_TRY(huff_check_stream(ctx, bytes, n, TZ_HUFF_RUN, &sw));
     std::vector<uint16_t> dec;
-    TZ_TRY(huff_tables(ctx, lengths, TZ_KEYS_A, 0, nullptr, &dec));
+    TZ_TRY(huff_tables(ctx, lengths, TZ_KEYS_A, 0, nullptr, &dec, 0));
     ctx->keys_kind = tz_ctx::KEYS_NONE;
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keys, &ctx->cap_keys, std::max<size_t>(bytes, 16)));
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, std::max<size_t>(n, 8) * 2));

@@ -3581,19 +3581,19 @@ __global__ __launch_bounds__(64) void k_huffr_dec(const unsigned* __restrict__ c
     }
 }
 
-// The launchers of the size, pack and expand passes of both coders: ntok == 0 runs the k_huff_* kernels, ntok ==
-// TZ_HUFFR_NTOK the k_huffr_* ones (d_enc then holds A + ntok entries) at the match distance `dist`: 3 is TZR1's, 1 the other
-// one a TZR2 file may name; VEC says that the payload is 16-byte aligned.
-int tzk_huff_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, uint16_t* d_run_bits,
+// The launchers of the size, pack and expand passes of the coder at the match distance `dist`: 0 (TZH1, the key frames, a TZR2
+// file without tokens) runs the k_huff_* kernels, 3 (TZR1) and 1 (the other one a TZR2 file may name) the k_huffr_* ones at that
+// distance (d_enc then holds A + TZ_HUFFR_NTOK entries); VEC says that the payload is 16-byte aligned.
+int tzk_huff_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
                   unsigned* d_chunk_off, tz_huff_meta* d_meta, int dist) {
-    if (ntok && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
+    if (dist != 0 && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
     const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
     void* d_cbits;
     TZ_TRY(tz_pool_alloc(ctx, nchunks * sizeof(unsigned), &d_cbits));
     TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
     tz_prof_scope ps(ctx, TZP_HUFF);
     const bool vec = !((uintptr_t)in & 15);
-    const auto k = !ntok      ? (vec ? k_huff_size<true> : k_huff_size<false>)
+    const auto k = !dist      ? (vec ? k_huff_size<true> : k_huff_size<false>)
                    : dist == 1 ? (vec ? k_huffr_size<true, 1> : k_huffr_size<false, 1>)
                                : (vec ? k_huffr_size<true, HFR_DIST> : k_huffr_size<false, HFR_DIST>);
     hipLaunchKernelGGL(k, dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0, ctx->stream, in, n, d_enc, A, base, nruns, nchunks, d_run_bits,
@@ -3604,13 +3604,13 @@ int tzk_huff_size(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_en
     return TZ_OK;
 }
 
-int tzk_huff_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, const uint16_t* d_run_bits,
+int tzk_huff_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
                  const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words, int dist) {
-    if (ntok && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
+    if (dist != 0 && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
     const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
     tz_prof_scope ps(ctx, TZP_HUFF);
     const bool vec = !((uintptr_t)in & 15);
-    const auto k = !ntok      ? (vec ? k_huff_enc<true> : k_huff_enc<false>)
+    const auto k = !dist      ? (vec ? k_huff_enc<true> : k_huff_enc<false>)
                    : dist == 1 ? (vec ? k_huffr_enc<true, 1> : k_huffr_enc<false, 1>)
                                : (vec ? k_huffr_enc<true, HFR_DIST> : k_huffr_enc<false, HFR_DIST>);
     hipLaunchKernelGGL(k, dim3((unsigned)nchunks), dim3(64), 0, ctx->stream, in, n, d_enc, A, base, nruns, d_run_bits, d_chunk_off, d_words,
@@ -3620,13 +3620,13 @@ int tzk_huff_enc(tz_ctx* ctx, const int16_t* in, size_t n, const uint16_t* d_enc
 }
 
 int tzk_huff_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
-                 const uint16_t* d_dec, int A, int base, int ntok, size_t n, int16_t* out, int dist) {
-    if (ntok && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
+                 const uint16_t* d_dec, int A, int base, size_t n, int16_t* out, int dist) {
+    if (dist != 0 && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
     const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
     tz_prof_scope ps(ctx, TZP_HUFF);
     const bool vec = !((uintptr_t)out & 15);
     const dim3 grid((unsigned)nchunks);
-    if (ntok)   // (the literal count A tells k_huffr_dec the tokens from the literals; k_huff_dec has no use for it)
+    if (dist)   // (the literal count A tells k_huffr_dec the tokens from the literals; k_huff_dec has no use for it)
         hipLaunchKernelGGL(dist == 1 ? (vec ? k_huffr_dec<true, 1> : k_huffr_dec<false, 1>)
                                      : (vec ? k_huffr_dec<true, HFR_DIST> : k_huffr_dec<false, HFR_DIST>),
                            grid, dim3(64), 0, ctx->stream, d_chunk_off, d_run_bits, d_words, stream_words, nruns, nchunks, d_dec, A, base, n, out);

@@ -135,7 +135,7 @@ struct tz_ctx {
     size_t cap_huff = 0, huff_bytes = 0;
     // what tz_huff_begin / tz_huffr_begin / tz_huffd_begin staged in d_huff, so that no decoder expands another's stream
     enum tz_huff_kind { HUFF_NONE, HUFF_TZH1, HUFF_TZR1, HUFF_TZR2 } huff_kind = HUFF_NONE;
-    int huff_dist = 0;                      // HUFF_TZR2: the match distance D of the staged stream (0: no tokens, 1, 3)
+    int huff_dist = 0;                      // the match distance of the staged stream: 0 (TZH1: no tokens), 3 (TZR1), a TZR2 stream's 0, 1 or 3
     size_t huff_n = 0;                      // elements the staged stream decodes to
     int huff_A = 0, huff_base = 0;          // literals of the staged code (a TZR1 code has its repeat tokens behind them)
     std::vector<uint16_t> huff_dec_tab;     // the 2^12-entry decode table of the staged stream's lengths
@@ -347,15 +347,15 @@ int tzk_huff_count(tz_ctx*, const int16_t* in, size_t n, unsigned long long* d_h
 int tzk_huffr_count(tz_ctx*, const int16_t* in, size_t n, unsigned long long* d_hist4104, tz_huff_meta* d_meta);
 // The coder that picks its match distance (TZR2): three such histograms from one read, distance 0 (no tokens) | 1 | 3.
 int tzk_huffd_count(tz_ctx*, const int16_t* in, size_t n, unsigned long long* d_hist3x4104, tz_huff_meta* d_meta);
-// The passes of both coders; ntok: 0 (TZH1) or TZ_HUFFR_NTOK (TZR1, d_enc then holds A + ntok entries behind the A literals).
-// dist: the match distance of a tokenised stream, 3 (TZR1) or 1 (a TZR2 file names either); without tokens it is not read.
+// The passes of the coder at the match distance dist: 0 (TZH1: no tokens), or a tokenised stream's 3 (TZR1) or 1 (a TZR2 file
+// names any of the three); d_enc then holds TZ_HUFFR_NTOK entries behind the A literals.
 // run sizes (u16, bits) and chunk word offsets (u32) of the payload under the code `d_enc` (u16: stored code | length << 12)
-int tzk_huff_size(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, uint16_t* d_run_bits,
-                  unsigned* d_chunk_off, tz_huff_meta* d_meta, int dist = 3);
-int tzk_huff_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, int ntok, const uint16_t* d_run_bits,
-                 const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words, int dist = 3);
+int tzk_huff_size(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, uint16_t* d_run_bits,
+                  unsigned* d_chunk_off, tz_huff_meta* d_meta, int dist);
+int tzk_huff_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, int A, int base, const uint16_t* d_run_bits,
+                 const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words, int dist);
 int tzk_huff_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
-                 const uint16_t* d_dec_tab4096, int A, int base, int ntok, size_t n, int16_t* out, int dist = 3);
+                 const uint16_t* d_dec_tab4096, int A, int base, size_t n, int16_t* out, int dist);
 // key-frame coder (TZK1).  d_frames: a stack of H x W x 3 frames of which frame d_idx[k] is key frame k;
 // d_pred[k] its predictor id 0..3; d_sym: nkeys * H * W * 3 int16 symbols 0..255, key after key.
 int tzk_key_hist(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, int nkeys, unsigned* d_counts /* [nkeys][4][256] */);

@@ -2,6 +2,7 @@
 /root/reference/src/decompress.py:39 `run(...)`; the rollout replay, inverse remap, inverse
 spatial delta (a prefix scan on the GPU instead of the reference's Python loop) and the
 reconstruction run in libtezip_hip.so."""
+import functools
 import os
 import sys
 import time
@@ -69,22 +70,18 @@ PREFETCH_DEPTH = 8              # _Prefetch: pieces queued ahead of the consumer
 def coded_format(head):
     """The module of this build's opt-in entropy.dat formats the first bytes of a file name (huff: TZH1, huffr: TZR1,
     huffd: TZR2), or None for the reference's zstd frame."""
-    if huff.is_huff(head):
-        return huff
-    if huffr.is_huffr(head):
-        return huffr
-    if huffd.is_huffd(head):
-        return huffd
+    for fmt in (huff, huffr, huffd):
+        if bytes(head[:4]) == fmt.MAGIC:
+            return fmt
     return None
 
 
 def coded_calls(ctx, coded):
-    """(begin, put, decode) of the context for a parsed TZH1 / TZR1 / TZR2 file; begin takes (bytes, n, lengths, base, run)."""
-    if isinstance(coded, huffd.Parsed):          # (the file's match distance goes with its lengths)
-        return (lambda nbytes, n, lengths, base, run: ctx.huffd_begin(nbytes, n, lengths, base, coded.dist, run)), ctx.huffd_put, ctx.huffd_decode
-    if isinstance(coded, huffr.Parsed):
-        return ctx.huffr_begin, ctx.huffr_put, ctx.huffr_decode
-    return ctx.huff_begin, ctx.huff_put, ctx.huff_decode
+    """(begin, put, decode) of the context for a parsed TZH1 / TZR1 / TZR2 file; begin takes (bytes, n, lengths, base, run=)."""
+    begin, put, decode = (getattr(ctx, "%s_%s" % (coded.coder, op)) for op in ("begin", "put", "decode"))
+    if coded.coder == "huffd":                   # (the file's match distance goes with its lengths)
+        begin = functools.partial(begin, dist=coded.dist)
+    return begin, put, decode
 
 
 def parse_coded_keys(head, path):
@@ -320,7 +317,7 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
                 check_frames(frames, nt)
             hp, wp = checks(nt, H, W)
             begin, put, expand = coded_calls(ctx, coded)
-            begin(coded.body.size, coded.n, coded.lengths, coded.base, coded.run)
+            begin(coded.body.size, coded.n, coded.lengths, coded.base, run=coded.run)
             per = stage_keys(nt, H, W, hp, wp)
             rollout(nt, warm_up)
             stages.mark("rollout (decoder) queued")
@@ -589,7 +586,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
             if coded is not None:
                 begin, put, expand = coded_calls(ctx, coded)
-                begin(coded.body.size, coded.n, coded.lengths, coded.base, coded.run)
+                begin(coded.body.size, coded.n, coded.lengths, coded.base, run=coded.run)
                 put(0, np.ascontiguousarray(coded.body))
                 expand()
             frames = ctx.decode_range(None if coded is not None else np.ascontiguousarray(payload), tb, first, end - first)

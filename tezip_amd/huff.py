@@ -144,15 +144,16 @@ def scatter(code, pos, total):
     return words[:total].astype(np.uint32)
 
 
-def encode_body(payload, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
-    """int16 payload -> (chunk_off uint32[nchunks], run_bits uint16[nruns], words uint32[stream_words])."""
+def encode_body(payload, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS, tag="huff"):
+    """int16 payload -> (chunk_off uint32[nchunks], run_bits uint16[nruns], words uint32[stream_words]); `tag` names the coder
+    in the messages."""
     sym = np.asarray(payload, np.int64).reshape(-1) - int(base)
     ln = np.asarray(lengths, np.int64)
     if sym.size < 1:
-        raise ValueError("huff: an empty payload cannot be coded")
+        raise ValueError("%s: an empty payload cannot be coded" % tag)
     if sym.min() < 0 or sym.max() >= ln.size or (ln[sym] == 0).any():
-        raise ValueError("huff: the payload holds a value without a code")
-    chunk_off, run_bits, total, pos = layout("huff", ln[sym], np.arange(sym.size, dtype=np.int64), run, chunk_runs)
+        raise ValueError("%s: the payload holds a value without a code" % tag)
+    chunk_off, run_bits, total, pos = layout(tag, ln[sym], np.arange(sym.size, dtype=np.int64), run, chunk_runs)
     return chunk_off, run_bits, scatter(canonical_codes(ln)[sym], pos, total)
 
 
@@ -247,6 +248,7 @@ def encode_file(payload, table, shape5, warm_up, lengths=None, base=None):
 
 class Parsed:
     """A validated Huffman entropy.dat: header fields, the reference trailer's content, and views of the sections."""
+    coder = "huff"
 
 
 def check_index(what, chunk_off, run_bits, stream_words, run=RUN, chunk_runs=CHUNK_RUNS, ascending="ascending"):

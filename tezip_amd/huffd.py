@@ -1,8 +1,9 @@
 """The Huffman-coded entropy.dat whose coder picks its match distance (`--coder huffd`; NOT a reference format): container,
-validation, the choice rule and a plain numpy tokeniser / encoder / decoder of the stream the GPU kernels write (k_huffd_count,
-then k_huff_size / k_huff_enc / k_huff_dec or k_huffr_size / k_huffr_enc / k_huffr_dec at the chosen distance, csrc/tz_codec.hip).
-The slow code here is the specification the kernels are tested against (tests/test_huffd.py, tests/test_gpu_huffd.py); the
-product never calls it on the hot path.  DESIGN.md section 9 holds the format as prose.
+validation, the choice rule and the numpy encoder / decoder of the stream the GPU kernels write (k_huffd_count, then k_huff_size /
+k_huff_enc / k_huff_dec or k_huffr_size / k_huffr_enc / k_huffr_dec at the chosen distance, csrc/tz_codec.hip).  The stream has
+ONE statement: huff.py's without tokens (D = 0), huffr.py's tokeniser, encoder and decode loop at the distance D = 1 or 3; this
+module delegates to them.  The slow code is the specification the kernels are tested against (tests/test_huffd.py,
+tests/test_gpu_huffd.py); the product never calls it on the hot path.  DESIGN.md section 9 holds the format as prose.
 
 TZR2 is TZR1 (tezip_amd/huffr.py) with another magic and the match distance D in the header's last u32:
   header   48 bytes: "TZR2" | u16 version = 1 | u16 L = 12 | u64 n | i32 base | u32 A | u32 R | u32 chunk_runs |
@@ -46,26 +47,11 @@ def check_dist(dist):
 
 
 def tokenise(sym, A, dist, run=RUN):
-    """huffr.tokenise at the match distance `dist`: sym int64[n] (value - base) -> (tok, extra, nextra), int64[n] each.  tok[i]
-    is the symbol coded AT element i -- the literal sym[i], A + k at the first element of a stretch, -1 inside a stretch --
-    followed by nextra[i] raw bits `extra[i]`.  dist = 0: every element is a literal."""
-    dist = check_dist(dist)
+    """huffr.tokenise at the match distance `dist`; dist = 0: every element is a literal followed by no raw bits."""
+    if check_dist(dist):
+        return huffr.tokenise(sym, A, run, dist)
     sym = np.asarray(sym, np.int64).reshape(-1)
-    n = sym.size
-    match = np.zeros(n, bool)
-    if dist:
-        match[dist:] = sym[dist:] == sym[:-dist]
-        match &= (np.arange(n) % run) >= dist                        # (so a stretch never spans a run boundary)
-    start = np.nonzero(match & ~np.concatenate([[False], match[:-1]]))[0]
-    end = np.nonzero(match & ~np.concatenate([match[1:], [False]]))[0]
-    m = end - start + 1
-    k = np.zeros(m.size, np.int64)
-    for t in range(1, NTOK):
-        k += m >= (1 << t)
-    tok = np.where(match, -1, sym)
-    extra, nextra = np.zeros(n, np.int64), np.zeros(n, np.int64)
-    tok[start], extra[start], nextra[start] = A + k, m - (np.int64(1) << k), k
-    return tok, extra, nextra
+    return sym.copy(), np.zeros_like(sym), np.zeros_like(sym)
 
 
 def token_counts(payload, base, A):
@@ -123,61 +109,29 @@ def check_lengths_of(dist):
 
 def encode_body(payload, lengths, base, dist, run=RUN, chunk_runs=CHUNK_RUNS):
     """int16 payload -> (chunk_off uint32[nchunks], run_bits uint16[nruns], words uint32[stream_words]) at the distance `dist`;
-    lengths holds A + 8 entries."""
-    dist = check_dist(dist)
+    lengths holds A + 8 entries.  huffr.encode_body at that distance; dist = 0: huff.encode_body over the literal lengths."""
+    if check_dist(dist):
+        return huffr.encode_body(payload, lengths, base, run, chunk_runs, dist, "huffd")
     sym = np.asarray(payload, np.int64).reshape(-1) - int(base)
-    n = sym.size
     ln = np.asarray(lengths, np.int64)
     A = ln.size - NTOK
-    if n < 1:
+    if sym.size < 1:
         raise ValueError("huffd: an empty payload cannot be coded")
     if A < 1 or sym.min() < 0 or sym.max() >= A:
         raise ValueError("huffd: the payload holds a value outside the %d literals" % A)
-    if dist == 0 and ln[A:].any():
+    if ln[A:].any():
         raise ValueError("huffd: match distance 0 with a code length for a repeat token")
-    tok, extra, nextra = tokenise(sym, A, dist, run)
-    at = np.nonzero(tok >= 0)[0]                                     # the elements something is coded at
-    tl = ln[tok[at]]
-    if (tl == 0).any():
+    if (ln[sym] == 0).any():
         raise ValueError("huffd: the payload needs a literal or a token without a code")
-    bits = np.zeros(n, np.int64)
-    bits[at] = tl + nextra[at]
-    chunk_off, run_bits, total, pos = huff.layout("huffd", bits, at, run, chunk_runs)
-    codes = canonical_codes(ln if dist else ln[:A]).astype(np.int64)
-    code = codes[tok[at]] | (extra[at] << tl)                        # <= 12 + 7 bits
-    return chunk_off, run_bits, huff.scatter(code, pos, total)
+    return huff.encode_body(payload, ln[:A], base, run, chunk_runs, "huffd")
 
 
 def decode_body(chunk_off, run_bits, words, n, lengths, base, dist, run=RUN, chunk_runs=CHUNK_RUNS):
-    """The inverse of encode_body for ANY bits, huffr.decode_body at the distance `dist`: all runs in lockstep, one element per
-    step -- a lane inside a stretch copies the element `dist` back (in front of the run: `base`), any other lane reads a symbol.
-    Reads past the stream's end see zeros; a stretch ends with its run.  dist = 0: huff.decode_body over the literal lengths."""
-    dist = check_dist(dist)
-    ln = np.asarray(lengths, np.int64)
-    A = ln.size - NTOK
-    if dist == 0:
-        return huff.decode_body(chunk_off, run_bits, words, n, ln[:A], base, run, chunk_runs)
-    tab = decode_table(ln)
-    pos, w, last = huff.run_positions(chunk_off, run_bits, words, n, run, chunk_runs)
-    nruns = pos.size
-    out = np.zeros(nruns * run, np.int16)
-    hist = [np.full(nruns, int(base), np.int64) for _ in range(dist)]   # hist[-dist] is the element `dist` back
-    m = np.zeros(nruns, np.int64)                                    # elements the current stretch still has to copy
-    for j in range(run):
-        read = m == 0
-        i = np.minimum(pos >> 5, last)
-        window = ((w[i] | (w[i + 1] << np.uint64(32))) >> (pos & 31).astype(np.uint64)).astype(np.int64) & ((1 << 31) - 1)
-        e = tab[window & 0xFFF].astype(np.int64)
-        l, s = e >> 12, e & 0xFFF
-        token = read & (s >= A)
-        k = np.where(token, np.minimum(s - A, NTOK - 1), 0)
-        m = np.where(token, (np.int64(1) << k) + ((window >> l) & ((np.int64(1) << k) - 1)), m)
-        pos = pos + np.where(read, l + k, 0)
-        val = np.where(read & ~token, s + int(base), hist[-dist])
-        m = np.maximum(m - 1, 0)
-        out[j::run] = val
-        hist = hist[1:] + [val]
-    return out[:n]
+    """The inverse of encode_body for ANY bits: huffr.decode_body at the distance `dist`; dist = 0: huff.decode_body over the
+    literal lengths."""
+    if check_dist(dist):
+        return huffr.decode_body(chunk_off, run_bits, words, n, lengths, base, run, chunk_runs, dist)
+    return huff.decode_body(chunk_off, run_bits, words, n, np.asarray(lengths)[:-NTOK], base, run, chunk_runs)
 
 
 def pack_front(trailer, lengths, base, n, nchunks, stream_words, dist, run=RUN, chunk_runs=CHUNK_RUNS):

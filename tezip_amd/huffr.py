@@ -28,7 +28,7 @@ from .huff import (CHUNK_RUNS, HEADER, MAX_LEN, NBINS, RUN, _pad4, body_bytes, c
 MAGIC = b"TZR1"
 VERSION = 1
 NTOK = 8                # repeat tokens T_0..T_7: stretches of 2^k .. 2^(k+1) - 1 matches
-DIST = 3                # the match distance: one pixel of the interleaved (H, W, 3) payload
+DIST = 3                # TZR1's match distance: one pixel of the interleaved (H, W, 3) payload
 TZR1 = huff.Format(MAGIC, "huffr", NTOK)
 
 
@@ -79,14 +79,15 @@ def tokenise_run(values):
     return out
 
 
-def tokenise(sym, A, run=RUN):
+def tokenise(sym, A, run=RUN, dist=DIST):
     """sym int64[n] (value - base) -> (tok, extra, nextra), int64[n] each: tok[i] is the symbol coded AT element i -- the
-    literal sym[i], A + k at the first element of a stretch, -1 inside a stretch -- followed by nextra[i] raw bits `extra[i]`."""
+    literal sym[i], A + k at the first element of a stretch, -1 inside a stretch -- followed by nextra[i] raw bits `extra[i]`.
+    dist >= 1: the match distance (TZR1: 3; a TZR2 file, tezip_amd/huffd.py, names 1 or 3)."""
     sym = np.asarray(sym, np.int64).reshape(-1)
     n = sym.size
     match = np.zeros(n, bool)
-    match[DIST:] = sym[DIST:] == sym[:-DIST]
-    match &= (np.arange(n) % run) >= DIST                            # (so a stretch never spans a run boundary)
+    match[dist:] = sym[dist:] == sym[:-dist]
+    match &= (np.arange(n) % run) >= dist                            # (so a stretch never spans a run boundary)
     start = np.nonzero(match & ~np.concatenate([[False], match[:-1]]))[0]
     end = np.nonzero(match & ~np.concatenate([match[1:], [False]]))[0]
     m = end - start + 1
@@ -105,31 +106,32 @@ def token_counts(payload, base, A):
     return np.bincount(tok[tok >= 0], minlength=A + NTOK).astype(np.uint64)
 
 
-def encode_body(payload, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
-    """int16 payload -> (chunk_off uint32[nchunks], run_bits uint16[nruns], words uint32[stream_words])."""
+def encode_body(payload, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS, dist=DIST, tag="huffr"):
+    """int16 payload -> (chunk_off uint32[nchunks], run_bits uint16[nruns], words uint32[stream_words]) at the match distance
+    `dist` >= 1; `tag` names the coder in the messages."""
     sym = np.asarray(payload, np.int64).reshape(-1) - int(base)
     n = sym.size
     ln = np.asarray(lengths, np.int64)
     A = ln.size - NTOK
     if n < 1:
-        raise ValueError("huffr: an empty payload cannot be coded")
+        raise ValueError("%s: an empty payload cannot be coded" % tag)
     if A < 1 or sym.min() < 0 or sym.max() >= A:
-        raise ValueError("huffr: the payload holds a value outside the %d literals" % A)
-    tok, extra, nextra = tokenise(sym, A, run)
+        raise ValueError("%s: the payload holds a value outside the %d literals" % (tag, A))
+    tok, extra, nextra = tokenise(sym, A, run, dist)
     at = np.nonzero(tok >= 0)[0]                                     # the elements something is coded at
     tl = ln[tok[at]]
     if (tl == 0).any():
-        raise ValueError("huffr: the payload needs a literal or a token without a code")
+        raise ValueError("%s: the payload needs a literal or a token without a code" % tag)
     bits = np.zeros(n, np.int64)
     bits[at] = tl + nextra[at]
-    chunk_off, run_bits, total, pos = huff.layout("huffr", bits, at, run, chunk_runs)
+    chunk_off, run_bits, total, pos = huff.layout(tag, bits, at, run, chunk_runs)
     code = canonical_codes(ln).astype(np.int64)[tok[at]] | (extra[at] << tl)          # <= 12 + 7 bits
     return chunk_off, run_bits, huff.scatter(code, pos, total)
 
 
-def decode_body(chunk_off, run_bits, words, n, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS):
+def decode_body(chunk_off, run_bits, words, n, lengths, base, run=RUN, chunk_runs=CHUNK_RUNS, dist=DIST):
     """The inverse of encode_body for ANY bits: every run is decoded from its own bit offset, all runs in lockstep as the
-    lanes of k_huffr_dec do, one element per step -- a lane inside a stretch copies the element three back, any other lane
+    lanes of k_huffr_dec do, one element per step -- a lane inside a stretch copies the element `dist` back, any other lane
     reads a symbol.  Reads past the stream's end see zeros; a stretch ends with its run."""
     ln = np.asarray(lengths, np.int64)
     A = ln.size - NTOK
@@ -137,7 +139,7 @@ def decode_body(chunk_off, run_bits, words, n, lengths, base, run=RUN, chunk_run
     pos, w, last = huff.run_positions(chunk_off, run_bits, words, n, run, chunk_runs)
     nruns = pos.size
     out = np.zeros(nruns * run, np.int16)
-    h1 = h2 = h3 = np.full(nruns, int(base), np.int64)               # the imaginary history in front of a run
+    hist = [np.full(nruns, int(base), np.int64)] * dist              # the imaginary history in front of a run, oldest first
     m = np.zeros(nruns, np.int64)                                    # elements the current stretch still has to copy
     for j in range(run):
         read = m == 0
@@ -149,10 +151,10 @@ def decode_body(chunk_off, run_bits, words, n, lengths, base, run=RUN, chunk_run
         k = np.where(token, np.minimum(s - A, NTOK - 1), 0)
         m = np.where(token, (np.int64(1) << k) + ((window >> l) & ((np.int64(1) << k) - 1)), m)
         pos = pos + np.where(read, l + k, 0)
-        val = np.where(read & ~token, s + int(base), h3)
+        val = np.where(read & ~token, s + int(base), hist[0])
         m = np.maximum(m - 1, 0)
         out[j::run] = val
-        h3, h2, h1 = h2, h1, val
+        hist = hist[1:] + [val]
     return out[:n]
 
 
