@@ -207,6 +207,21 @@ int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t*
  *    out of scope).  tz_huff_* / tz_huffr_* code whatever the resident payload holds. */
 int tz_set_payload_channels(tz_ctx* ctx, int channels);
 int tz_get_payload_channels(tz_ctx* ctx);
+/* Opt-in stride of the payload's spatial delta (no reference counterpart: finding_difference, compress.py:73-77, subtracts the
+ * flat neighbour, which on a colour stack is another channel of the same pixel; `tezip.py -c --sdelta channel`, format in
+ * DESIGN.md section 9, slow statement in tezip_amd/sdelta.py).  mode 0 (the default: every entry point does exactly what it does
+ * without this call) = flat; mode 1 = the channel stride S = tz_get_payload_channels(): out[i] = in[i] for i < S, else
+ * in[i-S] - in[i] (int16 wrap), over the flattened stack across pixel, row and frame boundaries.  Anything else is
+ * TZ_ERR_INVALID.  A change drops a resident payload.  With a one-channel payload S = 1 and mode 1 is the flat delta.  Under
+ * mode 1 with three channels:
+ *  - tz_encode (payload == NULL, the deferred hand-over, the shuffle bit and delta_out included) yields the strided payload:
+ *    quantiser, 1600 offset, histogram, rank table and remap are unchanged, sd stays in [-510, 510].
+ *  - tz_decode, tz_decode_range, tz_encode_quality, tz_encode_ssim and tz_encode_digests take such a payload and yield what they
+ *    yield under mode 0 from the flat payload of the same job.
+ *  - tz_encode_begin, tz_encode_finish, tz_encode_delta, tz_decode_delta and tz_undelta_carry return TZ_ERR_UNSUPPORTED under
+ *    mode 1 (whatever the channel count): one carry element is not the carry of a strided scan, sharded jobs are out of scope. */
+int tz_set_delta_stride(tz_ctx* ctx, int mode);
+int tz_get_delta_stride(tz_ctx* ctx);
 /* Streaming delivery: tz_encode with payload == NULL keeps the payload in the context; it is then
  * fetched in pieces of `count` int16 elements starting at `offset` (compress.py:375-400 appends and
  * compresses one monolithic array). */
@@ -421,6 +436,18 @@ int tz_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key_frames, co
  * are not counted). */
 int tz_spatial_delta_gray(tz_ctx* ctx, const int16_t* in3, size_t npix, int has_carry, int16_t carry, int apply_offset,
                           int16_t* out, unsigned long long* hist);
+/* The kernels of the channel-stride spatial delta (tz_set_delta_stride), stand-alone and independent of the context's mode.
+ * stride: 1 or 3 (else TZ_ERR_INVALID); with 1 they are tz_spatial_delta / tz_spatial_undelta / tz_undelta_carry.  carry: NULL,
+ * or `stride` HOST elements, the ones in front of in[0] (carry[c] in front of in[c]).
+ * tz_spatial_delta_stride: out[i] = in[i-stride] - in[i] (in[i] itself for i < stride without a carry), then 1600 - x when
+ * apply_offset; hist as tz_spatial_delta's.  tz_spatial_undelta_stride: the inverse, x[i] = x[i-stride] - in[i].
+ * tz_undelta_carry_stride: the `stride` decoded elements in front of payload[n0] (carry_out[c] = x[n0 - stride + c]), n0 a
+ * positive multiple of stride, through the rank table as tz_undelta_carry; payload NULL = the staged payload. */
+int tz_spatial_delta_stride(tz_ctx* ctx, const int16_t* in, size_t n, int stride, const int16_t* carry, int apply_offset,
+                            int16_t* out, unsigned long long* hist);
+int tz_spatial_undelta_stride(tz_ctx* ctx, const int16_t* in, size_t n, int stride, const int16_t* carry, int16_t* out);
+int tz_undelta_carry_stride(tz_ctx* ctx, const int16_t* payload, size_t n0, int stride, const int16_t* table, int table_len,
+                            int16_t* carry_out);
 /* tz_reconstruct_gray: tz_reconstruct from ONE int16 delta per pixel (diff1: nframes*H*W): base = the key byte of channel 0
  * where key_mask says so, else trunc(pred channel 0 * 255); v = clamp(base - d, 0, 255) goes to all three channels of out
  * (nframes*H*W*3).  pred, key_frames: the 3-channel stacks tz_reconstruct takes. */

@@ -73,6 +73,11 @@ _SIGS = {
     "tz_set_payload_deferred": (C.c_int, [C.c_void_p, C.c_int]),
     "tz_set_payload_channels": (C.c_int, [C.c_void_p, C.c_int]),
     "tz_get_payload_channels": (C.c_int, [C.c_void_p]),
+    "tz_set_delta_stride": (C.c_int, [C.c_void_p, C.c_int]),
+    "tz_get_delta_stride": (C.c_int, [C.c_void_p]),
+    "tz_spatial_delta_stride": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_spatial_undelta_stride": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_undelta_carry_stride": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "tz_spatial_delta_gray": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int16, C.c_int, C.c_void_p, C.c_void_p]),
     "tz_reconstruct_gray": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p]),
@@ -342,6 +347,14 @@ def _bounds(bound):
     return float(bound[0]), float(bound[1]) if len(bound) > 1 else 0.0
 
 
+def _carry(carry, stride):
+    """The carry argument of a tz_*_stride seam: `stride` int16 elements on the host (a scalar serves stride 1)."""
+    c = np.ascontiguousarray(np.atleast_1d(np.asarray(carry)).astype(np.int16))
+    if c.size != int(stride):
+        raise ValueError("the carry holds %d elements, the stride is %d" % (c.size, int(stride)))
+    return c
+
+
 def _payload_out(out, n):
     """An encoder's payload output -> the buffer passed on and returned: "resident" keeps the payload in the context
     (payload_get) and is None, None is a new host array of n int16, anything else a host or device buffer."""
@@ -585,6 +598,15 @@ class Context:
 
     def get_payload_channels(self):
         return int(self.lib.tz_get_payload_channels(self.h))
+
+    def set_delta_stride(self, mode):
+        """tz_set_delta_stride: 0 (the default) = the reference's flat spatial delta, 1 = the spatial delta of the payload at
+        the channel stride (tezip_amd/sdelta.py): encode / decode / decode_range / encode_quality / encode_ssim /
+        encode_digests work on the strided payload; the sharded entry points and undelta_carry refuse."""
+        self._ck(self.lib.tz_set_delta_stride(self.h, int(mode)))
+
+    def get_delta_stride(self):
+        return int(self.lib.tz_get_delta_stride(self.h))
 
     def set_payload_deferred(self, on=True):
         """tz_set_payload_deferred: encode(payload=<pinned host buffer>) returns with the device -> host transfer of
@@ -1080,6 +1102,33 @@ class Context:
             out = np.empty(n, np.int16)
         self._ck(self.lib.tz_spatial_undelta(self.h, _ptr(x), n, int(carry is not None), int(carry or 0), _ptr(out)))
         return out
+
+    def spatial_delta_stride(self, x, stride, offset, carry=None, hist=None, out=None):
+        """tz_spatial_delta_stride: out[i] = x[i - stride] - x[i] (tezip_amd/sdelta.py); carry: None or `stride` elements."""
+        n = _numel(x)
+        if out is None:
+            out = np.empty(n, np.int16)
+        cy = None if carry is None else _carry(carry, stride)
+        self._ck(self.lib.tz_spatial_delta_stride(self.h, _ptr(x), n, int(stride), _ptr(cy), int(offset), _ptr(out), _ptr(hist)))
+        return out
+
+    def spatial_undelta_stride(self, x, stride, carry=None, out=None):
+        """tz_spatial_undelta_stride: the inverse, x[i] = x[i - stride] - s[i]."""
+        n = _numel(x)
+        if out is None:
+            out = np.empty(n, np.int16)
+        cy = None if carry is None else _carry(carry, stride)
+        self._ck(self.lib.tz_spatial_undelta_stride(self.h, _ptr(x), n, int(stride), _ptr(cy), _ptr(out)))
+        return out
+
+    def undelta_carry_stride(self, payload, n0, stride, table=None, staged=False):
+        """tz_undelta_carry_stride: the `stride` decoded elements in front of payload[n0] (n0 a positive multiple of stride)."""
+        tl = -1 if table is None else len(table)
+        tb = None if table is None else np.ascontiguousarray(table, np.int16)
+        c = np.zeros(max(int(stride), 1), np.int16)
+        self._ck(self.lib.tz_undelta_carry_stride(self.h, None if staged else _ptr(payload), int(n0), int(stride), _ptr(tb), tl,
+                                                  c.ctypes.data))
+        return c
 
     def spatial_delta_gray(self, x3, offset, carry=None, hist=None, out=None):
         """tz_spatial_delta_gray: spatial_delta over channel 0 of the interleaved int16 stack x3 (npix * 3 elements, host or

@@ -9,6 +9,9 @@ Output directory:
                                                                               (compress.py:381-400)
                  with GRAY (--gray; not a reference format) on a job whose frames are all gray: the payload holds channel 0
                  alone, nt*H*W elements, and the shape in the trailer ends in 1 (tezip_amd/graypayload.py)
+                 with SDELTA="channel" (--sdelta channel; not a reference format) on a three-channel payload: the spatial
+                 delta of the payload is taken three elements back (the same channel of the pixel in front) and the first
+                 entry of the shape in the trailer is 4, or 5 with byte planes (tezip_amd/sdelta.py)
                  with CODER="huff" (--coder huff; not a reference format): "TZH1" header | that trailer | code lengths |
                  index | bit stream, written by the GPU (tezip_amd/huff.py); with CODER="huffr" the
                  same under the magic "TZR1", the code being over literals and period-3 repeat tokens (tezip_amd/huffr.py);
@@ -28,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, quality, sidecar, weights, zstd
+from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, quality, sdelta, sidecar, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -258,6 +261,26 @@ def check_gray(gray, sharded=False):
     return None
 
 
+def check_sdelta(mode, sharded=False):
+    """The refusals of --sdelta that a direct caller of run() can meet (tezip.py knows the others): None, or the message."""
+    if mode not in sdelta.MODES:
+        return "--sdelta takes one of %s, got %r" % (", ".join(sdelta.MODES), mode)
+    if mode == "channel" and sharded:
+        return "--sdelta channel is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+    return None
+
+
+def decide_sdelta(ctx, channels):
+    """--sdelta channel once the payload's channel count is known: with three channels the context is set to the channel
+    stride and True is returned; a one-channel payload (--gray on an all-gray job) has stride 1, which is the flat delta."""
+    if channels == 3:
+        ctx.set_delta_stride(1)
+        print("sdelta: channel (stride 3)")
+        return True
+    print("sdelta: channel equals flat on a one-channel payload")
+    return False
+
+
 def decide_gray(ctx, nt, files):
     """--gray after the frames are staged: one read of the resident stack says whether every frame is gray (tz_keys_gray over all
     of them).  Yes: the context is set to the one-channel payload and 1 is returned.  No: 3, and nothing changes -- the flag
@@ -365,10 +388,11 @@ def _huff_entropy_file(ctx, path, n, trailer, verbose, coder="huff"):
 
 
 def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False,
-                    key_coder="zstd", channels=3):
+                    key_coder="zstd", channels=3, strided=False):
     """key_frame.dat and entropy.dat (compress.py:271-278, 375-400) from the context-resident frames
     and payload, piece by piece: nothing of size nt*H*W lives on the host.  channels: what the resident payload stores per
-    pixel (1: a gray job, tezip_amd/graypayload.py); key_frame.dat has three either way."""
+    pixel (1: a gray job, tezip_amd/graypayload.py); key_frame.dat has three either way.  strided: the payload's spatial delta
+    ran at the channel stride (tezip_amd/sdelta.py): the trailer says so in the first entry of its shape."""
     n_key = nt * H * W * 3
     n = nt * H * W * channels
     key_idx = [int(i) for i in np.nonzero(key)[0]]
@@ -411,7 +435,8 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
         tail = np.concatenate([table.astype(np.int64), [len(table)]])
     else:
         tail = np.array([-1], dtype=np.int64)
-    trailer = np.concatenate([tail, [SHUFFLE_MARK if shuffled else 1, nt, H, W, channels], [warm_up]]).astype(np.int16)
+    one = sdelta.mark(shuffled) if strided else (SHUFFLE_MARK if shuffled else 1)
+    trailer = np.concatenate([tail, [one, nt, H, W, channels], [warm_up]]).astype(np.int16)
     t_e = time.perf_counter()
     if coder in ("huff", "huffr", "huffd"):
         esize = _huff_entropy_file(ctx, os.path.join(out_dir, "entropy.dat"), n, trailer, verbose, coder)
@@ -462,7 +487,7 @@ SSIM_NEEDS_REPORT = "--ssim extends the compression report: add --report"
 
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
-        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False,
+        ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
         SSIM=False):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
@@ -488,6 +513,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     not readable by the reference, `-u` recognises it by the shape in its trailer.  Decided after the frames are staged; a job
     with colour writes exactly the files it writes without the flag.  Works with every CODER, KEY_CODER, SHUFFLE, REPORT and
     DIGESTS.  Single-GPU jobs only.
+    SDELTA (--sdelta; NOT in the reference): "flat" (the default: every file, line and launch is what it is without it) or
+    "channel": the spatial delta of a three-channel payload is taken at the channel stride (tezip_amd/sdelta.py); only the
+    lossless back half of the coder changes, so the job decodes to exactly the images it decodes to without it.  `-u`
+    recognises the stream by the mark in its trailer.  On a one-channel payload (GRAY on an all-gray job) the stride is 1 and
+    the files are those of GRAY alone.  Works with every CODER, KEY_CODER, SHUFFLE, REPORT, SSIM and DIGESTS.  Single-GPU jobs only.
     SSIM (--ssim; NOT in the reference; with REPORT only): the report also carries the structural similarity of what the
     stored payload decodes to against the sources (definition TZ-SSIM-1: tezip_amd/ssim.py), from one tz_encode_ssim call on
     the same resident payload; a fourth line is printed.  Every other file is what it is without it.
@@ -500,7 +530,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
         print("ERROR: this build runs the compression path on an AMD MI355X only (no CPU path).")
         exit()
     problem = (check_coder(CODER, SHUFFLE, tzdist.active() is not None) or check_key_coder(KEY_CODER, tzdist.active() is not None)
-               or check_gray(GRAY, tzdist.active() is not None))
+               or check_gray(GRAY, tzdist.active() is not None) or check_sdelta(SDELTA, tzdist.active() is not None))
     if problem:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         print("ERROR:", problem)
         sys.exit(2)
@@ -543,6 +573,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             if GRAY:
                 channels = decide_gray(ctx, nt, src.files)
                 stages.mark("gray check (device)")
+            strided = SDELTA == "channel" and decide_sdelta(ctx, channels)
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
@@ -584,9 +615,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     print("table_create:{0}".format(prof["table_create"][0] / 1e3) + "[sec]")
                     print("replacing_based_on_frequency:{0}".format(prof["lut_remap"][0] / 1e3) + "[sec]")
             _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
-                            coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels)
+                            coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided)
             doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),   # the contract the predictions were made under
-                                payload_channels=channels)
+                                payload_channels=channels, sdelta="channel" if strided else "flat")
             if VERBOSE:
                 print("arithmetic contract:", doc["arithmetic_contract"])
             stages.mark("key_frame.dat + entropy.dat")

@@ -226,6 +226,7 @@ extern "C" int tz_ctx_destroy(tz_ctx* ctx) {
     if (ctx->d_keys) (void)hipFree(ctx->d_keys);
     if (ctx->d_keysym) (void)hipFree(ctx->d_keysym);
     if (ctx->d_scan_status) (void)hipFree(ctx->d_scan_status);
+    if (ctx->d_scan3_status) (void)hipFree(ctx->d_scan3_status);
     if (ctx->h_fault) (void)hipHostFree((void*)ctx->h_fault);
     for (auto& s : ctx->prof)
         for (auto& e : s.pending) {
@@ -1617,6 +1618,27 @@ static int gray_unsupported(tz_ctx* ctx, const char* who) {
     return TZ_OK;
 }
 
+// ---- spatial delta at the channel stride (include/tezip_hip.h: tz_set_delta_stride)
+extern "C" int tz_set_delta_stride(tz_ctx* ctx, int mode) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (mode != 0 && mode != 1) return tz_fail(ctx, TZ_ERR_INVALID, "delta stride mode must be 0 (flat) or 1 (channel), not %d", mode);
+    if (mode != ctx->delta_stride_mode) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under the other stride
+    ctx->delta_stride_mode = mode;
+    return TZ_OK;
+}
+
+extern "C" int tz_get_delta_stride(tz_ctx* ctx) { return ctx ? ctx->delta_stride_mode : TZ_ERR_INVALID; }
+
+// the stride in force: mode 1 on a one-channel payload is the flat delta
+static bool stride3(const tz_ctx* ctx) { return ctx->delta_stride_mode == 1 && ctx->payload_channels == 3; }
+
+// one carry element is not the carry of a strided scan, and sharded jobs are out of scope
+static int stride_unsupported(tz_ctx* ctx, const char* who) {
+    if (ctx->delta_stride_mode == 1)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve the channel-stride spatial delta (tz_set_delta_stride(1)): sharded jobs and one-element carries are flat only", who);
+    return TZ_OK;
+}
+
 static int keys_upload(tz_ctx* ctx, const int* idx, const uint8_t* pred, int nkeys, const int** d_idx, const uint8_t** d_pred);
 
 // TZ_ERR_INVALID naming the first frame of the resident stack that has a pixel with unequal channels (k_key_gray over all frames)
@@ -1652,6 +1674,22 @@ static int encode_front_gray(tz_ctx* ctx, int mode, double b0, double b1, int en
     TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta));
     TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_delta, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
     return tzk_spatial_delta_gray(ctx, (const int16_t*)d_delta, n1, 0, 0, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge);
+}
+
+// encode_front under the channel stride: every job (lossless, identity shortcut, lossy) takes the unfused route -- delta and
+// quantiser into the delta stack (the caller's tap when there is one), then k_sdelta_s3; d_sym receives nt*H*W*3 elements.
+static int encode_front_s3(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* d_delta_tap, int16_t* d_sym,
+                           unsigned long long* d_hist) {
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
+    const size_t N = (size_t)nt * H * W * 3;
+    void *d_mask = nullptr, *d_delta = d_delta_tap;
+    TZ_TRY(tz_pool_alloc(ctx, nt, &d_mask));
+    TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
+    if (entropy) TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, TZ_NBINS * sizeof(unsigned long long), ctx->stream));
+    if (!d_delta) TZ_TRY(tz_pool_alloc(ctx, N * 2, &d_delta));
+    TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta));
+    TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_delta, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
+    return tzk_spatial_delta_s3(ctx, (const int16_t*)d_delta, N, nullptr, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr);
 }
 
 extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* payload, int16_t* table,
@@ -1713,6 +1751,8 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
     int16_t* d_sym = entropy ? (int16_t*)d_sd : (int16_t*)o->dev;   // without a table the symbols are the payload
     if (rc == TZ_OK && gray)
         rc = encode_front_gray(ctx, mode, b0, b1, entropy, d_sym, (unsigned long long*)d_hist, (int16_t*)d_edge);
+    else if (rc == TZ_OK && stride3(ctx))
+        rc = encode_front_s3(ctx, mode, b0, b1, entropy, delta_out ? (int16_t*)o_delta.dev : nullptr, d_sym, (unsigned long long*)d_hist);
     else if (rc == TZ_OK)
         rc = encode_front(ctx, mode, b0, b1, entropy, delta_out ? (int16_t*)o_delta.dev : nullptr, d_sym,
                           (unsigned long long*)d_hist, (int16_t*)d_edge);
@@ -1749,6 +1789,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
     tz_roctx_range roctx_("tz_encode_begin");
     if (!ctx || !edge || (entropy && !hist)) return TZ_ERR_INVALID;
     TZ_TRY(gray_unsupported(ctx, "tz_encode_begin"));
+    TZ_TRY(stride_unsupported(ctx, "tz_encode_begin"));
     TZ_TRY(encode_check(ctx, "tz_encode_begin", mode));
     ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload now receives a shard's symbols
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
@@ -1780,6 +1821,7 @@ extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const
     tz_roctx_range roctx_("tz_encode_finish");
     if (!ctx) return TZ_ERR_INVALID;
     TZ_TRY(gray_unsupported(ctx, "tz_encode_finish"));
+    TZ_TRY(stride_unsupported(ctx, "tz_encode_finish"));
     if (ctx->enc_kind != tz_ctx::ENC_SYMBOLS) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish needs a tz_encode_begin first");
     if (ctx->enc_entropy != (table_len >= 0) || (table_len > 0 && !table) || table_len > TZ_MAX_TABLE)
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode_finish: table does not match the entropy flag of tz_encode_begin");
@@ -1838,6 +1880,7 @@ extern "C" int tz_byte_unshuffle(tz_ctx* ctx, const uint8_t* in, size_t n, int16
 extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int16_t* delta_out) {
     if (!ctx || !delta_out) return TZ_ERR_INVALID;
     TZ_TRY(gray_unsupported(ctx, "tz_encode_delta"));
+    TZ_TRY(stride_unsupported(ctx, "tz_encode_delta"));
     TZ_TRY(encode_check(ctx, "tz_encode_delta", mode));
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
     std::vector<tz_out> outs;
@@ -1853,6 +1896,7 @@ extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int1
 extern "C" int tz_decode_delta(tz_ctx* ctx, const int16_t* delta, uint8_t* frames_out) {
     if (!ctx || !delta || !frames_out) return TZ_ERR_INVALID;
     TZ_TRY(gray_unsupported(ctx, "tz_decode_delta"));
+    TZ_TRY(stride_unsupported(ctx, "tz_decode_delta"));
     if (!whole_stack(ctx, tz_ctx::ROLLOUT_DECODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_decode_delta needs a tz_rollout_decode first");
     TZ_TRY(tz_check_pred_contract(ctx, "tz_decode_delta"));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
@@ -1886,6 +1930,18 @@ static int undelta_carry(tz_ctx* ctx, const int16_t* d_pay, size_t n0, const int
     return TZ_OK;
 }
 
+// the three decoded elements in front of payload[n0] under the channel stride (k_undelta_carry_s3): enqueued, then read back
+static int undelta_carry_s3(tz_ctx* ctx, const int16_t* d_pay, size_t n0, const int16_t* h_lut, int16_t* carry3) {
+    void* d_words;
+    unsigned w[3] = {0, 0, 0};
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(w), &d_words));
+    TZ_TRY(tzk_undelta_carry_s3(ctx, d_pay, n0, h_lut, 1, (unsigned*)d_words));
+    TZ_TRY(tz_d2h(ctx, w, d_words, sizeof(w), ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
+    for (int c = 0; c < 3; ++c) carry3[c] = (int16_t)(w[c] & 0xFFFFu);
+    return TZ_OK;
+}
+
 // payload == NULL: the payload staged with tz_payload_begin / tz_payload_put, which must hold `need` elements
 static int staged_payload(tz_ctx* ctx, size_t need, const int16_t** payload) {
     if (!ctx->d_payload || ctx->payload_len < need) return tz_fail(ctx, TZ_ERR_STATE, "no staged payload of %zu elements", need);
@@ -1905,6 +1961,7 @@ extern "C" int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, 
                                 int16_t* carry) {
     tz_roctx_range roctx_("tz_undelta_carry");
     if (!ctx || !carry) return TZ_ERR_INVALID;
+    TZ_TRY(stride_unsupported(ctx, "tz_undelta_carry"));
     if (n0 == 0) return tz_fail(ctx, TZ_ERR_INVALID, "tz_undelta_carry: n0 = 0, the stream start has no carry");
     TZ_TRY(check_table(ctx, table, table_len));
     if (!payload) TZ_TRY(staged_payload(ctx, n0, &payload));
@@ -1954,8 +2011,15 @@ static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, s
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    if (rc == TZ_OK && first > 0) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, h_lut, &carry);
-    if (rc == TZ_OK)
+    const bool s3 = stride3(ctx);
+    int16_t carry3[3] = {0, 0, 0};
+    if (rc == TZ_OK && first > 0 && s3) rc = undelta_carry_s3(ctx, (const int16_t*)d_pay, n0, h_lut, carry3);
+    else if (rc == TZ_OK && first > 0) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, h_lut, &carry);
+    if (rc == TZ_OK && s3)
+        rc = tzk_decode_tail_s3(ctx, (const int16_t*)d_pay + n0, h_lut, 1, first > 0 ? carry3 : nullptr,
+                                ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + (size_t)first * fe,
+                                (const uint8_t*)d_mask, count, H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
+    else if (rc == TZ_OK)
         rc = (gray ? tzk_decode_tail_gray : tzk_decode_tail)(ctx, (const int16_t*)d_pay + n0, h_lut, 1, first > 0, carry,
                              ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + (size_t)first * fe,
                              (const uint8_t*)d_mask, count, H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
@@ -2022,7 +2086,10 @@ static int encode_decoded(tz_ctx* ctx, const char* who, const int16_t* payload, 
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    if (rc == TZ_OK)   // the launches of tz_decode
+    if (rc == TZ_OK && stride3(ctx))   // the launches of tz_decode
+        rc = tzk_decode_tail_s3(ctx, (const int16_t*)d_pay, h_lut, 1, nullptr, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H,
+                                W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
+    else if (rc == TZ_OK)
         rc = (gray ? tzk_decode_tail_gray : tzk_decode_tail)(ctx, (const int16_t*)d_pay, h_lut, 1, 0, 0, ctx->d_pred, ctx->d_frames,
                                                              (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
     *d_dec_out = (const uint8_t*)d_dec;
@@ -2271,6 +2338,81 @@ extern "C" int tz_spatial_undelta(tz_ctx* ctx, const int16_t* in, size_t n, int 
         rc = tzk_undelta(ctx, (const int16_t*)din, n, has_carry, carry, (int16_t*)o.dev);
     }
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// The seams of the channel-stride spatial delta (tz_set_delta_stride): stride 3 runs the strided kernels, stride 1 the flat
+// ones, so that its bytes are tz_spatial_delta's / tz_spatial_undelta's / tz_undelta_carry's.
+static int check_stride(tz_ctx* ctx, const char* who, int stride) {
+    if (stride != 1 && stride != 3) return tz_fail(ctx, TZ_ERR_INVALID, "%s: stride must be 1 or 3, not %d", who, stride);
+    return TZ_OK;
+}
+
+extern "C" int tz_spatial_delta_stride(tz_ctx* ctx, const int16_t* in, size_t n, int stride, const int16_t* carry, int apply_offset,
+                                       int16_t* out, unsigned long long* hist) {
+    if (!ctx || !in || !out) return TZ_ERR_INVALID;
+    TZ_TRY(check_stride(ctx, "tz_spatial_delta_stride", stride));
+    if (stride == 1) return tz_spatial_delta(ctx, in, n, carry != nullptr, carry ? carry[0] : (int16_t)0, apply_offset, out, hist);
+    const void* din;
+    tz_out o, oh;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, in, n * 2, &din);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    void* dh = nullptr;
+    if (rc == TZ_OK && hist) {
+        rc = tz_dev_out(ctx, hist, TZ_NBINS * sizeof(unsigned long long), &oh);
+        if (rc == TZ_OK) {
+            dh = oh.dev;
+            if (oh.host) {  // counts are ADDED to what the caller holds
+                hipError_t e = hipMemcpyAsync(dh, hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream);
+                if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "hist upload: %s", hipGetErrorString(e));
+            }
+            outs.push_back(oh);
+        }
+    }
+    if (rc == TZ_OK) rc = tzk_spatial_delta_s3(ctx, (const int16_t*)din, n, carry, apply_offset, (int16_t*)o.dev, (unsigned long long*)dh);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_spatial_undelta_stride(tz_ctx* ctx, const int16_t* in, size_t n, int stride, const int16_t* carry, int16_t* out) {
+    if (!ctx || !in || !out) return TZ_ERR_INVALID;
+    TZ_TRY(check_stride(ctx, "tz_spatial_undelta_stride", stride));
+    if (stride == 1) return tz_spatial_undelta(ctx, in, n, carry != nullptr, carry ? carry[0] : (int16_t)0, out);
+    const void* din;
+    tz_out o;
+    std::vector<tz_out> outs;
+    int rc = tz_dev_in(ctx, in, n * 2, &din);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
+    if (rc == TZ_OK) {
+        outs.push_back(o);
+        rc = tzk_undelta_s3(ctx, (const int16_t*)din, n, carry, nullptr, 0, (int16_t*)o.dev);
+    }
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (the fault word of the bounded poll is read here)
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_undelta_carry_stride(tz_ctx* ctx, const int16_t* payload, size_t n0, int stride, const int16_t* table, int table_len,
+                                       int16_t* carry_out) {
+    tz_roctx_range roctx_("tz_undelta_carry_stride");
+    if (!ctx || !carry_out) return TZ_ERR_INVALID;
+    TZ_TRY(check_stride(ctx, "tz_undelta_carry_stride", stride));
+    if (n0 == 0 || n0 % (size_t)stride)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_undelta_carry_stride: n0 = %zu is not a positive multiple of the stride %d", n0, stride);
+    TZ_TRY(check_table(ctx, table, table_len));
+    if (!payload) TZ_TRY(staged_payload(ctx, n0, &payload));
+    std::vector<int16_t> lut;
+    if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
+    const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
+    const void* d_pay = nullptr;
+    int rc = tz_dev_in(ctx, payload, n0 * 2, &d_pay);
+    if (rc == TZ_OK && stride == 1) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, h_lut, carry_out);
+    else if (rc == TZ_OK) rc = undelta_carry_s3(ctx, (const int16_t*)d_pay, n0, h_lut, carry_out);
     tz_pool_release_all(ctx);
     return rc;
 }

@@ -1786,6 +1786,76 @@ int tzk_spatial_delta_gray(tz_ctx* ctx, const int16_t* in3, size_t npix, int has
     return TZ_OK;
 }
 
+// ------------------------------------------------- spatial delta at the channel stride (tz_set_delta_stride(1))
+// Not in the reference: out[i] = in[i-3] - in[i] (int16 wrap) over the flattened (frame, y, x, 3) stack, out[i] = in[i] (or
+// carry[i] - in[i]) for i < 3 -- the neighbour of a sample is the SAME channel of the pixel in front, not another channel of
+// its own pixel (tezip_amd/sdelta.py).  Offset and histogram as k_sdelta.  A lane takes 8 elements (16 B); the elements in
+// front of them come from one more 8-byte load (the four in front, of which three are used; same or neighbouring cache line).
+// vec = 0 (a buffer off the 16-byte grid) and the n % 8 elements behind the vectors go one by one.
+__device__ __forceinline__ void sdelta_s3_1(const int16_t* __restrict__ in, size_t i, int has_carry, short c0, short c1, short c2,
+                                            int apply_offset, int16_t* __restrict__ out, HistLds* hl) {
+    const short cur = in[i];
+    const short front = i >= 3 ? in[i - 3] : (i == 0 ? c0 : (i == 1 ? c1 : c2));
+    const short sd = (i >= 3 || has_carry) ? (short)(front - cur) : cur;
+    const short y = apply_offset ? (short)(TZ_OFFSET - sd) : sd;
+    out[i] = y;
+    if (hl && y >= 0 && y < TZ_NBINS) atomicAdd(&hl->w[HL_FULL + y], 1u);
+}
+
+template <bool HIST>
+__global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_sdelta_s3(const int16_t* __restrict__ in, size_t n, size_t n8, int has_carry,
+                                                   short c0, short c1, short c2, int apply_offset, int16_t* __restrict__ out,
+                                                   unsigned long long* __restrict__ hist) {
+    __shared__ unsigned hraw[HIST ? HL_WORDS : 1];
+    HistLds& hl = *(HistLds*)hraw;
+    if (HIST) hist_clear(hl);
+    const int centre = apply_offset ? TZ_OFFSET : 0;
+    HistAcc acc;
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint4* in8 = (const uint4*)in;   // 16-byte aligned when n8 > 0 (tzk_spatial_delta_s3)
+    uint4* out8 = (uint4*)out;
+    for (size_t i = t0; i < n8; i += stride) {
+        const uint4 v = in8[i];
+        // w = (e[-4], e[-3]), (e[-2], e[-1]): the elements in front of the lane's eight.  At the start of the stream they are
+        // the carry, or -- out[k] = x[k] for k < 3 -- "2 x[k]"
+        uint2 w;
+        if (i) w = *(const uint2*)(in + 8 * i - 4);
+        else if (has_carry) w = make_uint2((unsigned)(unsigned short)c0 << 16, (unsigned)(unsigned short)c1 | ((unsigned)(unsigned short)c2 << 16));
+        else w = make_uint2(v.x << 17, ((v.x >> 15) & 0xFFFEu) | (v.y << 17));
+        // P = the eight elements three places in front, two per dword
+        const unsigned P0 = __builtin_amdgcn_alignbit(w.y, w.x, 16), P1 = __builtin_amdgcn_alignbit(v.x, w.y, 16),
+                       P2 = __builtin_amdgcn_alignbit(v.y, v.x, 16), P3 = __builtin_amdgcn_alignbit(v.z, v.y, 16);
+        unsigned Y[4] = {pk_sub(P0, v.x), pk_sub(P1, v.y), pk_sub(P2, v.z), pk_sub(P3, v.w)};
+        if (apply_offset) {
+            const unsigned C = ((unsigned)TZ_OFFSET << 16) | (unsigned)TZ_OFFSET;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) Y[j] = pk_sub(C, Y[j]);
+        }
+        out8[i] = make_uint4(Y[0], Y[1], Y[2], Y[3]);
+        if (HIST) hist_add8(hl, acc, Y, centre);
+    }
+    for (size_t j = 8 * n8 + t0; j < n; j += stride) sdelta_s3_1(in, j, has_carry, c0, c1, c2, apply_offset, out, HIST ? &hl : nullptr);
+    if (HIST) hist_flush(hl, acc, centre, hist);
+}
+
+int tzk_spatial_delta_s3(tz_ctx* ctx, const int16_t* in, size_t n, const int16_t* carry3, int apply_offset, int16_t* out,
+                         unsigned long long* d_hist) {
+    if (n == 0) return TZ_OK;
+    if (((uintptr_t)in | (uintptr_t)out) & 1) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_s3 buffers must be 2-byte aligned");
+    const size_t n8 = ((((uintptr_t)in | (uintptr_t)out) & 15) == 0) ? n / 8 : 0;
+    const short c0 = carry3 ? carry3[0] : 0, c1 = carry3 ? carry3[1] : 0, c2 = carry3 ? carry3[2] : 0;
+    tz_prof_scope ps(ctx, TZP_SDELTA);
+    const size_t items = std::max(n8, n - 8 * n8);
+    if (d_hist)
+        hipLaunchKernelGGL(k_sdelta_s3<true>, dim3(std::min(HB_GRID, grid_for(items, HB_THREADS))), dim3(HB_THREADS), 0, ctx->stream, in,
+                           n, n8, carry3 != nullptr, c0, c1, c2, apply_offset, out, d_hist);
+    else
+        hipLaunchKernelGGL(k_sdelta_s3<false>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, in, n, n8, carry3 != nullptr, c0,
+                           c1, c2, apply_offset, out, d_hist);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // ----------------------------------------------------------------------- rank remap / unmap
 // compress.py:84-90 and decompress.py:31-36 are T sequential `where` passes (O(N*T)); here
 // one pass through a 2112-entry LUT held in LDS.  Values outside [0, 2112) pass through
@@ -2318,6 +2388,289 @@ int tzk_undelta_carry(tz_ctx* ctx, const int16_t* in, size_t n0, const int16_t* 
     else
         hipLaunchKernelGGL(k_undelta_carry<false>, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)nullptr,
                            post_offset, d_word);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// --------------------------------------------- inverse spatial delta at the channel stride (tz_set_delta_stride(1))
+// x[i] = x[i-3] - s[i]: three interleaved wrap-around scans, one per class c = i mod 3 of the element index,
+//   x[i] = c0[c] - sum_{j <= i, j = c (mod 3)} s'[j]   (mod 2^16),  s'[j] = -s[j] for j < 3 and c0 = 0 without a carry.
+// k_scan3p has the two-phase shape of k_scan2p -- a wave owns a contiguous run of wave-tiles; sum the run, publish the block's
+// sums, poll the blocks in front (bounded, fault word), walk the run again -- with THREE sums wherever k_scan2p has one.
+// A thread's 16 elements start at an index that is no multiple of 3 (16 = 1 mod 3): it sums them by the class RELATIVE to
+// its first element (k % 3, a compile-time index into three registers) and rotates the three sums into stream classes by
+// r = base % 3 with selects (rot3); prefixes go back the same way.  No register is indexed at run time.
+// status[g] = epoch << 48 | sum2 << 32 | sum1 << 16 | sum0 (each mod 2^16) is ONE naturally aligned 64-bit word, written by
+// one 64-bit atomic store and read by 64-bit atomic loads: such an access is single-copy atomic, so a reader that sees the
+// launch's epoch sees the three sums stored with it -- there is no second word whose order against the first would matter,
+// and relaxed ordering suffices because nothing else is communicated through memory.  The words have their own epoch counter
+// (1..65535) and are cleared when it wraps, as k_scan2p's.  The payload is read twice (no register-kept run) and the
+// reconstruction is a second kernel: 6 B/element here plus tzk_reconstruct.
+__device__ __forceinline__ unsigned long long st_load64(const unsigned long long* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_store64(unsigned long long* p, unsigned long long v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// g[(r + j) % 3] = a[j]: from classes relative to an element of class r to stream classes.  rot3((3 - r) % 3, ...) is the inverse.
+__device__ __forceinline__ void rot3(unsigned r, unsigned a0, unsigned a1, unsigned a2, unsigned& g0, unsigned& g1, unsigned& g2) {
+    g0 = r == 0 ? a0 : (r == 1 ? a2 : a1);
+    g1 = r == 0 ? a1 : (r == 1 ? a0 : a2);
+    g2 = r == 0 ? a2 : (r == 1 ? a1 : a0);
+}
+
+// scan_load16 for the strided scan: the first THREE elements of the stream are negated; then the thread's sums by relative class
+template <bool LUT>
+__device__ __forceinline__ void scan3_load16(const int16_t* __restrict__ in, size_t base, size_t n, bool vec, bool neg_head,
+                                             const int16_t* sl, int post_offset, int* v, unsigned* a) {
+    scan_load16<LUT>(in, base, n, vec, false, sl, post_offset, v);
+    if (base == 0 && neg_head) {   // (elements past the end are 0)
+        v[0] = -v[0];
+        v[1] = -v[1];
+        v[2] = -v[2];
+    }
+    a[0] = a[1] = a[2] = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN_EPT; ++k) a[k % 3] += (unsigned)v[k];
+}
+
+template <bool LUT>
+__global__ __launch_bounds__(256) void k_scan3p(const int16_t* __restrict__ in, size_t n, int wtiles, int has_carry, short c0, short c1,
+                                                short c2, int vec, const int16_t* __restrict__ lut, int post_offset,
+                                                unsigned long long* __restrict__ status, unsigned epoch, unsigned poll_epoch,
+                                                unsigned poll_limit, unsigned* __restrict__ fault, int16_t* __restrict__ out) {
+    __shared__ int16_t sl[LUT ? TZ_NBINS + 1 : 1];
+    __shared__ unsigned wsum[4][3], bsum[4][3];
+    if (LUT) {
+        for (int k = threadIdx.x; k < TZ_NBINS + 1; k += 256) sl[k] = lut[k];
+        __syncthreads();
+    }
+    const int g = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t chunk0 = ((size_t)g * 4 + wv) * (size_t)wtiles * SCAN_WT;   // of this wave
+    // (1) the three sums of the wave's run, then of the block's
+    unsigned s0 = 0, s1 = 0, s2 = 0;
+    for (int t = 0; t < wtiles; ++t) {
+        const size_t base = chunk0 + (size_t)t * SCAN_WT + (size_t)lane * SCAN_EPT;
+        if (base >= n) break;
+        int v[SCAN_EPT];
+        unsigned a[3], g0, g1, g2;
+        scan3_load16<LUT>(in, base, n, vec != 0, !has_carry, sl, post_offset, v, a);
+        rot3((unsigned)(base % 3), a[0], a[1], a[2], g0, g1, g2);
+        s0 += g0;
+        s1 += g1;
+        s2 += g2;
+    }
+    s0 = wave_scan_incl(s0);
+    s1 = wave_scan_incl(s1);
+    s2 = wave_scan_incl(s2);
+    if (lane == 63) {
+        wsum[wv][0] = s0;
+        wsum[wv][1] = s1;
+        wsum[wv][2] = s2;
+    }
+    __syncthreads();
+    unsigned front[3] = {0, 0, 0}, tot[3] = {0, 0, 0};   // of the waves in front of this one in the block; of the block
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (w < wv) front[c] += wsum[w][c];
+            tot[c] += wsum[w][c];
+        }
+    if (threadIdx.x == 0)
+        st_store64(&status[g], (unsigned long long)epoch << 48 | (unsigned long long)(tot[2] & 0xFFFFu) << 32 |
+                                   (unsigned long long)(tot[1] & 0xFFFFu) << 16 | (unsigned long long)(tot[0] & 0xFFFFu));
+    // (2) the sums of the blocks in front: thread t takes blocks t, t + 256, ...; the poll is bounded as k_scan2p's, and every
+    // block has published its own word BEFORE it polls, so a launch always drains
+    unsigned m0 = 0, m1 = 0, m2 = 0;
+    for (int b = threadIdx.x; b < g; b += 256) {
+        unsigned long long w = st_load64(&status[b]);
+        unsigned spins = 0;
+        while ((unsigned)(w >> 48) != poll_epoch) {
+            if (++spins > poll_limit) {
+                *(volatile unsigned*)fault = TZ_FAULT_SCAN_POLL;
+                break;
+            }
+            w = st_load64(&status[b]);
+        }
+        m0 += (unsigned)w & 0xFFFFu;
+        m1 += (unsigned)(w >> 16) & 0xFFFFu;
+        m2 += (unsigned)(w >> 32) & 0xFFFFu;
+    }
+    m0 = wave_scan_incl(m0);
+    m1 = wave_scan_incl(m1);
+    m2 = wave_scan_incl(m2);
+    if (lane == 63) {
+        bsum[wv][0] = m0;
+        bsum[wv][1] = m1;
+        bsum[wv][2] = m2;
+    }
+    __syncthreads();
+    unsigned run[3];   // per stream class: the sum of everything in front of the wave's next tile
+#pragma unroll
+    for (int c = 0; c < 3; ++c) run[c] = front[c] + bsum[0][c] + bsum[1][c] + bsum[2][c] + bsum[3][c];
+    // (3) scan the wave's run tile by tile
+    const unsigned cc0 = has_carry ? (unsigned)(int)c0 : 0u, cc1 = has_carry ? (unsigned)(int)c1 : 0u, cc2 = has_carry ? (unsigned)(int)c2 : 0u;
+    for (int t = 0; t < wtiles; ++t) {
+        if (chunk0 + (size_t)t * SCAN_WT >= n) break;   // uniform for the wave
+        const size_t base = chunk0 + (size_t)t * SCAN_WT + (size_t)lane * SCAN_EPT;
+        int v[SCAN_EPT];
+        unsigned a[3], q0, q1, q2;
+        scan3_load16<LUT>(in, base, n, vec != 0, !has_carry, sl, post_offset, v, a);   // (all 0 for a lane past the end)
+        const unsigned r = (unsigned)(base % 3), rinv = (3u - r) % 3u;
+        rot3(r, a[0], a[1], a[2], q0, q1, q2);
+        const unsigned i0 = wave_scan_incl(q0), i1 = wave_scan_incl(q1), i2 = wave_scan_incl(q2);
+        unsigned p[3], cl[3];   // by relative class: the sums in front of the thread's elements, and the carries
+        rot3(rinv, i0 - q0 + run[0], i1 - q1 + run[1], i2 - q2 + run[2], p[0], p[1], p[2]);
+        rot3(rinv, cc0, cc1, cc2, cl[0], cl[1], cl[2]);
+        run[0] += __shfl(i0, 63);
+        run[1] += __shfl(i1, 63);
+        run[2] += __shfl(i2, 63);
+        short res[SCAN_EPT];
+#pragma unroll
+        for (int k = 0; k < SCAN_EPT; ++k) {
+            p[k % 3] += (unsigned)v[k];
+            res[k] = (short)(uint16_t)(cl[k % 3] - p[k % 3]);
+        }
+        if (vec && base + SCAN_EPT <= n) {
+            short8 x, y;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                x[k] = res[k];
+                y[k] = res[8 + k];
+            }
+            *(short8*)(out + base) = x;
+            *(short8*)(out + base + 8) = y;
+        } else {
+#pragma unroll
+            for (int k = 0; k < SCAN_EPT; ++k)
+                if (base + k < n) out[base + k] = res[k];
+        }
+    }
+}
+
+int tzk_undelta_s3(tz_ctx* ctx, const int16_t* in, size_t n, const int16_t* carry3, const int16_t* h_lut2112, int post_offset,
+                   int16_t* out) {
+    if (n == 0) return TZ_OK;
+    if (((uintptr_t)in | (uintptr_t)out) & 1) return tz_fail(ctx, TZ_ERR_INVALID, "strided inverse scan: buffers must be 2-byte aligned");
+    const size_t tiles = (n + SCAN_WT - 1) / SCAN_WT;                 // wave-tiles
+    const int G = (int)std::min<size_t>(SCAN_G, (tiles + 3) / 4);
+    const size_t tpb = (tiles + (size_t)G * 4 - 1) / ((size_t)G * 4);   // per wave
+    if (tpb > 0x7FFFFFFFull) return tz_fail(ctx, TZ_ERR_INVALID, "strided inverse scan: too many elements");
+    void* d_lut = nullptr;
+    if (h_lut2112) {
+        TZ_TRY(tz_pool_alloc(ctx, (TZ_NBINS + 1) * 2, &d_lut));
+        TZ_TRY(tz_upload(ctx, d_lut, h_lut2112, (TZ_NBINS + 1) * 2));
+    }
+    if (!ctx->d_scan3_status) TZ_HIP(ctx, hipMalloc((void**)&ctx->d_scan3_status, sizeof(unsigned long long) * SCAN_G));
+    TZ_TRY(tz_fault_word(ctx));
+    tz_prof_scope ps(ctx, TZP_SCAN);
+    if (ctx->scan3_epoch == 0 || ctx->scan3_epoch == 0xFFFFu) {   // first launch, or the epochs have gone round
+        TZ_HIP(ctx, hipMemsetAsync(ctx->d_scan3_status, 0, sizeof(unsigned long long) * SCAN_G, ctx->stream));
+        ctx->scan3_epoch = 0;
+    }
+    const unsigned epoch = ++ctx->scan3_epoch;
+    const int vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+    const short c0 = carry3 ? carry3[0] : 0, c1 = carry3 ? carry3[1] : 0, c2 = carry3 ? carry3[2] : 0;
+#define TZ_SCAN3_LAUNCH(L)                                                                                                   \
+    hipLaunchKernelGGL((k_scan3p<L>), dim3(G), dim3(256), 0, ctx->stream, in, n, (int)tpb, carry3 != nullptr, c0, c1, c2, vec, \
+                       (const int16_t*)d_lut, post_offset, ctx->d_scan3_status, epoch, (epoch + ctx->scan_dbg_skew) & 0xFFFFu,  \
+                       ctx->scan_dbg_limit ? ctx->scan_dbg_limit : SCAN_POLL_LIMIT, ctx->d_fault, out)
+    if (h_lut2112) TZ_SCAN3_LAUNCH(true);
+    else TZ_SCAN3_LAUNCH(false);
+#undef TZ_SCAN3_LAUNCH
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// The decoder's tail over a channel-stride payload: inverse remap and strided inverse scan into a temporary, then k_recon*
+// (the shape of the gray tail).  carry3: NULL at the stream start, else the three decoded elements in front of the range.
+int tzk_decode_tail_s3(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut2112, int post_offset, const int16_t* carry3,
+                       const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
+                       uint8_t* out) {
+    const size_t n = (size_t)nframes * H * W * 3;
+    if (n == 0) return TZ_OK;
+    void* d_diff;
+    TZ_TRY(tz_pool_alloc(ctx, n * 2, &d_diff));
+    TZ_TRY(tzk_undelta_s3(ctx, in, n, carry3, h_lut2112, post_offset, (int16_t*)d_diff));
+    return tzk_reconstruct(ctx, pred, key, d_key_mask, (const int16_t*)d_diff, nframes, H, W, Hp, Wp, out);
+}
+
+// The three class sums of a prefix: k_undelta_carry with one sum per class of the element index mod 3.  A thread takes 24
+// elements per step (three 16-byte loads), so the class of its k-th element RELATIVE to in[head] is k % 3 in every step: three
+// registers indexed at compile time, rotated once at the end by head % 3.  The head in front of the first 16-byte boundary and
+// the (n - head) % 24 elements behind the vectors are taken one by one by the first lanes of block 0.  words[c] receives the
+// negated sum of class c: its low 16 bits are the decoded element of class c in front of in[n].
+template <bool LUT>
+__global__ __launch_bounds__(256) void k_undelta_carry_s3(const int16_t* __restrict__ in, size_t n, unsigned head,
+                                                          const int16_t* __restrict__ lut, int post_offset,
+                                                          unsigned* __restrict__ words) {
+    __shared__ int16_t sl[LUT ? TZ_NBINS + 1 : 1];
+    __shared__ unsigned wsum[4][3];
+    if (LUT) {
+        for (int k = threadIdx.x; k < TZ_NBINS + 1; k += 256) sl[k] = lut[k];
+        __syncthreads();
+    }
+    const size_t n24 = (n - head) / 24, nthr = (size_t)gridDim.x * 256;
+    const short8* in8 = (const short8*)(in + head);
+    unsigned a[3] = {0, 0, 0};
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n24; i += nthr) {
+        const short8 v0 = in8[3 * i], v1 = in8[3 * i + 1], v2 = in8[3 * i + 2];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            a[k % 3] += carry_sym<LUT>(v0[k], sl, post_offset);
+            a[(8 + k) % 3] += carry_sym<LUT>(v1[k], sl, post_offset);
+            a[(16 + k) % 3] += carry_sym<LUT>(v2[k], sl, post_offset);
+        }
+    }
+    unsigned s[3];
+    rot3(head % 3u, a[0], a[1], a[2], s[0], s[1], s[2]);
+    if (blockIdx.x == 0 && threadIdx.x < 32) {   // head < 8 and tail < 24 elements: one per lane
+        const size_t e = threadIdx.x < head ? (size_t)threadIdx.x : head + n24 * 24 + (threadIdx.x - head);
+        if (e < n) {
+            const unsigned x = carry_sym<LUT>(in[e], sl, post_offset);
+            const unsigned c = (unsigned)(e % 3);
+            s[0] += c == 0 ? x : 0u;
+            s[1] += c == 1 ? x : 0u;
+            s[2] += c == 2 ? x : 0u;
+        }
+        if (threadIdx.x < 3) {   // s'[j] = -s[j] for j < 3 (n >= 3)
+            const unsigned x = 2u * carry_sym<LUT>(in[threadIdx.x], sl, post_offset);
+            s[0] -= threadIdx.x == 0 ? x : 0u;
+            s[1] -= threadIdx.x == 1 ? x : 0u;
+            s[2] -= threadIdx.x == 2 ? x : 0u;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        for (int off = 32; off > 0; off >>= 1) s[c] += __shfl_down(s[c], off);
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][c] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        __hip_atomic_fetch_add(&words[threadIdx.x], 0u - (wsum[0][threadIdx.x] + wsum[1][threadIdx.x] + wsum[2][threadIdx.x] + wsum[3][threadIdx.x]),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+int tzk_undelta_carry_s3(tz_ctx* ctx, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_words) {
+    if (n0 == 0 || n0 % 3) return tz_fail(ctx, TZ_ERR_INVALID, "strided undelta carry: n0 = %zu is not a positive multiple of 3", n0);
+    if (((uintptr_t)in & 1) != 0) return tz_fail(ctx, TZ_ERR_INVALID, "strided undelta carry: payload not 2-byte aligned");
+    void* d_lut = nullptr;
+    if (h_lut2112) {
+        TZ_TRY(tz_pool_alloc(ctx, (TZ_NBINS + 1) * 2, &d_lut));
+        TZ_TRY(tz_upload(ctx, d_lut, h_lut2112, (TZ_NBINS + 1) * 2));
+    }
+    const unsigned head = (unsigned)std::min<size_t>(n0, ((16 - ((uintptr_t)in & 15)) & 15) / 2);
+    TZ_HIP(ctx, hipMemsetAsync(d_words, 0, 3 * sizeof(unsigned), ctx->stream));
+    const int G = grid_for((n0 - head) / 24 + 1, 256);
+    tz_prof_scope ps(ctx, TZP_CARRY);
+    if (h_lut2112)
+        hipLaunchKernelGGL(k_undelta_carry_s3<true>, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)d_lut,
+                           post_offset, d_words);
+    else
+        hipLaunchKernelGGL(k_undelta_carry_s3<false>, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)nullptr,
+                           post_offset, d_words);
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }

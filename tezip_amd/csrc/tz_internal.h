@@ -129,6 +129,9 @@ struct tz_ctx {
     unsigned* d_fault = nullptr;
     int decode_unfused = 0;                 // TEZIP_DECODE_UNFUSED=1: tz_decode as scan + reconstruct launches (cross-check)
     int payload_channels = 3;               // tz_set_payload_channels: 1 = the payload of a gray job holds channel 0 alone
+    int delta_stride_mode = 0;              // tz_set_delta_stride: 1 = the spatial delta of the payload runs at the channel stride
+    unsigned long long* d_scan3_status = nullptr;   // strided inverse scan (k_scan3p): one 64-bit word per block, own epochs
+    unsigned scan3_epoch = 0;
     // opt-in Huffman coder (tz_huff_*): the coded stream (index | bits) of the resident payload, or the stream a decoder
     // stages with tz_huff_begin / tz_huff_put together with what tz_huff_decode needs to expand it
     uint8_t* d_huff = nullptr;
@@ -326,6 +329,20 @@ int tzk_reconstruct_gray(tz_ctx*, const float* pred, const uint8_t* key, const u
 int tzk_decode_tail_gray(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry, int16_t carry,
                          const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp,
                          int Wp, uint8_t* out);
+// spatial delta at the channel stride 3 (tz_set_delta_stride(1); DESIGN.md section 9, tezip_amd/sdelta.py).  carry3: NULL or the
+// three HOST elements in front of in[0] (classes 0, 1, 2 of the element index mod 3).  tzk_spatial_delta_s3: out[i] = in[i-3] -
+// in[i], then 1600 - y and the histogram as tzk_spatial_delta; any 2-byte aligned buffers.  tzk_undelta_s3: the inverse, three
+// interleaved wrap-around scans in one launch (k_scan3p), through the decoder LUT when there is one.  tzk_undelta_carry_s3:
+// the three decoded elements in front of in[n0] into d_words[0..2] (low 16 bits), n0 a positive multiple of 3.
+// tzk_decode_tail_s3: tzk_decode_tail over such a payload (scan into a temporary, then tzk_reconstruct).
+int tzk_spatial_delta_s3(tz_ctx*, const int16_t* in, size_t n, const int16_t* carry3, int apply_offset, int16_t* out,
+                         unsigned long long* d_hist);
+int tzk_undelta_s3(tz_ctx*, const int16_t* in, size_t n, const int16_t* carry3, const int16_t* h_lut2112, int post_offset,
+                   int16_t* out);
+int tzk_undelta_carry_s3(tz_ctx*, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_words);
+int tzk_decode_tail_s3(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, const int16_t* carry3,
+                       const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
+                       uint8_t* out);
 // per-frame (sse, max |dec - orig|, #changed) of two unpadded nframes x fe uint8 stacks; d_out (device) is cleared here
 int tzk_quality(tz_ctx*, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out);
 // TZD64 digests of nframes frames of fe bytes (fe < 2^32, else TZ_ERR_INVALID before any launch); d_out: nframes words, cleared here

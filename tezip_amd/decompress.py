@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, sidecar, zstd
 from . import dist as tzdist
+from . import sdelta
 from .compress import SHUFFLE_MARK, make_context, open_model
 from .data_utils import padding_shape
 
@@ -37,9 +38,11 @@ def check_stream(shape, warm_up, payload_len, key_len):
     one, nt, H, W, C = shape
     # C: the channels the PAYLOAD stores per pixel -- 3, or 1 for this build's opt-in payload of a gray job (--gray,
     # tezip_amd/graypayload.py); the frames and key_frame.dat have three channels either way
-    if one not in (1, SHUFFLE_MARK) or C not in (1, 3) or nt < 1 or H < 1 or W < 1:
-        raise ValueError("entropy.dat: unsupported stack shape %r (expected (1, nt, H, W, 3), or (1, nt, H, W, 1) for a gray job)"
-                         % (tuple(shape),))
+    # one: 1 in the reference, SHUFFLE_MARK for byte planes; sdelta.MARK / MARK_SHUFFLE (4 / 5) say the same of a payload whose
+    # spatial delta ran at the channel stride (--sdelta channel, tezip_amd/sdelta.py), which has three channels.  3 means nothing
+    if one not in (1, SHUFFLE_MARK) + sdelta.MARKS or C not in (1, 3) or (one in sdelta.MARKS and C != 3) or nt < 1 or H < 1 or W < 1:
+        raise ValueError("entropy.dat: unsupported stack shape %r (expected (1, nt, H, W, 3), (1, nt, H, W, 1) for a gray job or "
+                         "(4, nt, H, W, 3) for a channel-stride payload)" % (tuple(shape),))
     n = nt * H * W * C
     if payload_len != n:
         raise ValueError("entropy.dat: payload holds %d elements, the trailer says %d (truncated or corrupt file)"
@@ -57,6 +60,17 @@ def check_channels(data_dir, C):
     want = sidecar.channels_of(sidecar.read(data_dir))
     if want is not None and want != C:
         raise ValueError("tezip_amd.json describes the payload as %d-channel, entropy.dat's trailer as %d-channel" % (want, C))
+
+
+def check_sdelta(data_dir, one):
+    """The stride of the payload's spatial delta that entropy.dat's trailer states (mark 4 / 5: channel) against tezip_amd.json,
+    which records "channel" and says nothing for flat.  The trailer is authoritative; a sidecar that contradicts it belongs to
+    another stream.  Returns the mode for tz_set_delta_stride."""
+    have = "channel" if sdelta.is_strided(one) else "flat"
+    want = sidecar.sdelta_of(sidecar.read(data_dir))
+    if want is not None and want != have:
+        raise ValueError("tezip_amd.json describes the payload's spatial delta as %s, entropy.dat's trailer as %s" % (want, have))
+    return 1 if have == "channel" else 0
 
 
 TAIL_ELEMS = _lib.TZ_NBINS + 8  # the longest trailer: table (<= 2111 symbols) + T + shape(5) + warm_up
@@ -308,7 +322,7 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             # rollout is queued first
             coded = fmt.parse(np.fromfile(paths["entropy.dat"], np.uint8), key_len)
             table, warm_up = coded.table, coded.warm_up
-            _, nt, H, W, C = coded.shape
+            one, nt, H, W, C = coded.shape
             if stack is not None and key_len == stack[0] * stack[1] * stack[2] * 3 and len(file_names) == stack[0] \
                     and (nt, H, W, warm_up) != tuple(stack):
                 raise ValueError("tezip_amd.json describes the stack as %r (frames, height, width, warm-up), entropy.dat's trailer as %r"
@@ -370,9 +384,9 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             table = None if tlen == -1 else np.ascontiguousarray(tail[tail.size - 7 - tlen: tail.size - 7])
             payload_len = total - 7 - max(tlen, 0)
             check_stream(shape, warm_up, payload_len, key_len)
-            if shape[0] == SHUFFLE_MARK:
+            if sdelta.is_shuffled(shape[0]):
                 return False
-            _, nt, H, W, C = shape
+            one, nt, H, W, C = shape
             if early is not None and (nt, H, W, warm_up) != tuple(early):
                 raise ValueError("tezip_amd.json describes the stack as %r (frames, height, width, warm-up), entropy.dat's trailer as %r"
                                  % (tuple(early), (nt, H, W, warm_up)))
@@ -384,6 +398,7 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
                 rollout(nt, warm_up)
         check_channels(DATA_DIR, C)
         ctx.set_payload_channels(C)         # 1: the one-channel payload of a gray job; the frames keep three channels
+        ctx.set_delta_stride(check_sdelta(DATA_DIR, one))   # 1: the payload's spatial delta ran at the channel stride
         if records is not None:
             check_records(records, nt, H, W)
         stages.mark("rollout (decoder)", ctx)
@@ -540,6 +555,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
     if C == 1 and job is not None:
         print("ERROR: a one-channel payload (--gray) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
         sys.exit(2)
+    stride_mode = check_sdelta(DATA_DIR, shape[0])
+    if stride_mode and job is not None:
+        print("ERROR: a channel-stride payload (--sdelta channel) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
+        sys.exit(2)
     key_frames = None if keys is not None else np.frombuffer(key_bytes, dtype=np.uint8).reshape(nt, H, W, 3)
     hp, wp = padding_shape(H, W)
     if model_shape is not None and (model_shape[0] != hp or model_shape[1] != wp):
@@ -565,7 +584,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
         if contract:
             ctx.set_contract(contract)
         ctx.set_payload_channels(C)
-        if shape[0] == SHUFFLE_MARK:  # this build's opt-in byte planes -> the int16 payload
+        ctx.set_delta_stride(stride_mode)
+        if sdelta.is_shuffled(shape[0]):  # this build's opt-in byte planes -> the int16 payload
             payload = ctx.byte_unshuffle(np.ascontiguousarray(payload).view(np.uint8))
         if job:
             # key intervals sharded over the ranks (tezip_amd/dist.py); no frame travels: each rank saves its own

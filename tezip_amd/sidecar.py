@@ -15,6 +15,10 @@ it; `-c` writes this one, `-u` adopts it:
 are all gray, tezip_amd/graypayload.py); a job with the three-channel payload has no such key.  The trailer of entropy.dat
 states the same and is authoritative: a sidecar that contradicts it is an error.
 
+`sdelta` = "channel" (optional): the spatial delta of the payload was taken at the channel stride (`-c --sdelta channel` on a
+three-channel payload, tezip_amd/sdelta.py); every other job has no such key.  The trailer of entropy.dat states the same (mark
+4 or 5) and is authoritative: a sidecar that contradicts it is an error.
+
 `stack` = [frames, height, width, warm_up] (round 6, optional): the reference stores these in the LAST seven
 values of entropy.dat (compress.py:390-394), so a decoder learns it only when the whole payload is decompressed; with
 it here the decoder runs its rollout WHILE entropy.dat is being decompressed (decompress._run_streaming) and checks the
@@ -51,7 +55,7 @@ def requested_contract():
     return int(v) if v in ("1", "2") else None
 
 
-def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3):
+def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta="flat"):
     from . import _lib
     if contract not in (1, 2):
         raise ValueError("contract must be 1 or 2, not %r" % (contract,))
@@ -62,6 +66,8 @@ def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3):
         doc["stack"] = [int(v) for v in stack]
     if payload_channels == 1:   # a --gray job; every other job has no such key
         doc["payload_channels"] = 1
+    if sdelta == "channel":     # a --sdelta channel job with a three-channel payload; every other job has no such key
+        doc["sdelta"] = "channel"
     with open(os.path.join(out_dir, NAME), "w", encoding="UTF-8") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
@@ -103,6 +109,17 @@ def channels_of(doc):
     if ch not in (1, 3) or isinstance(ch, bool):
         raise SidecarMismatch("%s states payload_channels %r (1 is the only value ever written)" % (NAME, ch))
     return ch
+
+
+def sdelta_of(doc):
+    """The stride mode of the payload's spatial delta the sidecar states: "channel" for a --sdelta channel job
+    (tezip_amd/sdelta.py), "flat" for a sidecar without the key, None without a sidecar.  Anything else is a damaged file."""
+    if doc is None:
+        return None
+    mode = doc.get("sdelta", "flat")
+    if mode not in ("flat", "channel") or ("sdelta" in doc and mode != "channel"):
+        raise SidecarMismatch("%s states sdelta %r (\"channel\" is the only value ever written)" % (NAME, mode))
+    return mode
 
 
 def resolve(doc, wts=None):

@@ -70,6 +70,11 @@ FLAG_TABLE = (
     # is there, the decoded frames are checked against it on the GPU before an image is written (a mismatch: exit status 3, no
     # image); require = the same, and a directory without the file is refused; off = never check (salvage a damaged directory)
     (None, "--verify", dict(type=str, choices=decompress.VERIFY_MODES, default=None, dest="verify")),
+    # not in the reference: with -c, the stride of the payload's spatial delta.  flat (also when the flag is absent) = the
+    # reference's finding_difference, whose neighbour of a sample is another channel of the same pixel; channel = the same channel
+    # of the pixel in front (tezip_amd/sdelta.py; smaller on colour jobs, LARGER on a gray source stored with three channels: use
+    # --gray there; the reference cannot read such a file, -u recognises it by the mark in its trailer)
+    (None, "--sdelta", dict(type=str, choices=("flat", "channel"), default=None, dest="sdelta")),
 )
 
 TEXT = {
@@ -206,6 +211,19 @@ def check_gray_flag(arg):
     return compress.check_gray(True, int(os.environ.get("WORLD_SIZE", "1")) > 1)
 
 
+def check_sdelta_flag(arg):
+    """--sdelta is valid with -c only; `channel` needs one single-GPU job without --sweep.  Returns None, or the message of a
+    refusal."""
+    mode = getattr(arg, "sdelta", None)
+    if mode is None:
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--sdelta is valid with -c (--compress) only (-u recognises a channel-stride payload by itself)"
+    if mode == "channel" and getattr(arg, "sweep", None) is not None:
+        return "--sdelta channel cannot be combined with --sweep"
+    return compress.check_sdelta(mode, int(os.environ.get("WORLD_SIZE", "1")) > 1)
+
+
 def check_verify_flag(arg):
     """--verify is valid with -u only; `require` needs frame_digests.json in the directory and one GPU.  Returns None, or the
     message of a refusal."""
@@ -291,6 +309,10 @@ def _main(arg):
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_sdelta_flag(arg)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # launched by torch.distributed.run: one rank per GPU
         from . import dist as tzdist
         tzdist.init_from_env()
@@ -323,6 +345,12 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if getattr(arg, "sdelta", None) == "channel":   # (flat is the job without the flag: the calls below)
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), GRAY=bool(getattr(arg, "gray", False)),
+                            SSIM=bool(getattr(arg, "ssim", False)), SDELTA="channel")
     if getattr(arg, "ssim", False):
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=True,
