@@ -4,6 +4,7 @@
 
   python scripts/dump_isa.py                       # table: kernel, instructions, MFMA, VALU, SALU, LDS, VMEM, regs
   python scripts/dump_isa.py --kernel 'k_wino<3, 4, false>' --out /tmp/a1.s
+  python scripts/dump_isa.py --obj new/tz_codec.o --against old/tz_codec.o   # exit 1 unless the device code is the same
 """
 import argparse
 import os
@@ -56,8 +57,18 @@ def main():
     ap.add_argument("--obj", default=os.path.join(ROOT, "tezip_amd", "csrc", "tz_prednet.o"))
     ap.add_argument("--kernel", help="substring of the demangled kernel name: print (or --out) its disassembly")
     ap.add_argument("--out")
+    ap.add_argument("--against", metavar="OTHER.o", help="compare the device code with that of another build of the object")
     args = ap.parse_args()
     fns = disassemble(args.obj)
+    if args.against:
+        other = disassemble(args.against)
+        for n in sorted(set(fns) ^ set(other)):
+            print("only in %s: %s" % (args.obj if n in fns else args.against, n))
+        changed = sorted(n for n in set(fns) & set(other) if fns[n] != other[n])
+        for n in changed:
+            print("differs: %s (%d against %d instructions)" % (n, len(fns[n]), len(other[n])))
+        print("%d functions in %s, %d in %s, %d differ" % (len(fns), args.obj, len(other), args.against, len(changed)))
+        sys.exit(1 if changed or set(fns) ^ set(other) else 0)
     if args.kernel:
         hits = [n for n in fns if args.kernel in n]
         if len(hits) != 1:

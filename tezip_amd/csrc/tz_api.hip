@@ -1533,45 +1533,49 @@ static int encode_check(tz_ctx* ctx, const char* who, int mode) {
 }
 
 // compress.py:292-355 on the context-resident rollout: delta, quantiser, spatial delta over the whole flattened stack
-// (no carry), 1600 offset + bincount when `entropy`.  d_sym receives the symbols (or the raw spatial delta), d_hist the
-// counters (zeroed here), d_edge[0..1] the first and the last element of the quantised delta stack (what a shard
-// boundary needs).  d_delta_tap (may be NULL): the quantised delta stack is also wanted there.  d_sym
-// NULL: stop after the quantiser (compress.py:292-319), the delta stack in d_delta_tap is all that is wanted.
-static int encode_front(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* d_delta_tap, int16_t* d_sym,
+// (no carry), 1600 offset + bincount when `entropy`.  d_sym receives the symbols (or the raw spatial delta) of the layout,
+// nt * tz_frame_elems of them, d_hist the counters (zeroed here), d_edge[0..1] the first and the last element of the quantised
+// delta stack (what a shard boundary needs; channel 0's under the gray layout, nothing under the channel
+// stride).  d_delta_tap (may be NULL): the quantised delta stack, three channels in every layout, is also wanted there.
+// d_sym NULL: stop after the quantiser (compress.py:292-319), the delta stack in d_delta_tap is all that is wanted.
+static int encode_front(tz_ctx* ctx, tz_layout layout, int mode, double b0, double b1, int entropy, int16_t* d_delta_tap, int16_t* d_sym,
                         unsigned long long* d_hist, int16_t* d_edge) {
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
     const size_t N = (size_t)nt * H * W * 3;
+    const bool flat = layout.channels == 3 && layout.stride == 1;
     void *d_mask = nullptr, *d_delta = d_delta_tap;
     TZ_TRY(tz_pool_alloc(ctx, nt, &d_mask));
     TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
     if (entropy) TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, TZ_NBINS * sizeof(unsigned long long), ctx->stream));
-    // error_bound returns its input untouched in these cases (compress.py:24,35) ...
-    bool lossless = b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0);
-    // ... and COMPUTES its input back wherever the worst-case tolerance of the job cannot merge two different deltas
-    // (E <= 0.499: tz_quant_is_identity, with the proof).  The fused pass below then serves such a job as well; a caller
-    // that taps the delta stack still gets it through the general quantiser (the parity tests compare the two).
-    if (!d_delta_tap && tz_quant_is_identity(mode, b0, b1)) lossless = true;
-    bool fused = false;
-    // lossless and nobody asked for the delta stack: one fused pass (compress.py:292-355)
-    if (lossless && !d_delta_tap)
-        TZ_TRY(tzk_delta_sd_fused(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp,
-                                  entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge, &fused));
-    // lossy and nobody asked for the delta stack: quantiser on pred / orig, fill fused with the spatial delta
-    if (!lossless && !d_delta_tap)
-        TZ_TRY(tzk_quant_sd_fused(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, ctx->quant_skip.data(), nt, H, W,
-                                  ctx->Hp, ctx->Wp, mode, b0, b1, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge,
-                                  &fused));
-    if (fused) return TZ_OK;
+    if (flat && !d_delta_tap) {   // nobody asked for the delta stack: one of the two fused passes, where its kernel applies
+        // error_bound returns its input untouched in these cases (compress.py:24,35), and COMPUTES its input back wherever
+        // the worst-case tolerance of the job cannot merge two different deltas (E <= 0.499: tz_quant_is_identity, with the
+        // proof).  A caller that taps the delta stack still gets it through the general quantiser (the parity tests compare
+        // the two).  The gray layout and the channel stride have no fused pass.
+        const bool lossless = b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0) || tz_quant_is_identity(mode, b0, b1);
+        bool fused = false;
+        if (lossless)   // delta and spatial delta in one pass (compress.py:292-355)
+            TZ_TRY(tzk_delta_sd_fused(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp,
+                                      entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge, &fused));
+        else            // quantiser on pred / orig, fill fused with the spatial delta
+            TZ_TRY(tzk_quant_sd_fused(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, ctx->quant_skip.data(), nt, H, W,
+                                      ctx->Hp, ctx->Wp, mode, b0, b1, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge,
+                                      &fused));
+        if (fused) return TZ_OK;
+    }
     if (!d_delta) TZ_TRY(tz_pool_alloc(ctx, N * 2, &d_delta));
     // compress.py:292-314
     TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta));
-    // compress.py:315-319
+    // compress.py:315-319 (under the gray layout the quantiser also walks channels 1 and 2, whose output is dropped)
     TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_delta, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
     if (!d_sym) return TZ_OK;
     // compress.py:339-355
-    TZ_TRY(tzk_spatial_delta(ctx, (const int16_t*)d_delta, N, 0, 0, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr));
-    TZ_HIP(ctx, hipMemcpyAsync(d_edge, d_delta, 2, hipMemcpyDeviceToDevice, ctx->stream));
-    TZ_HIP(ctx, hipMemcpyAsync(d_edge + 1, (const int16_t*)d_delta + (N - 1), 2, hipMemcpyDeviceToDevice, ctx->stream));
+    TZ_TRY(tzk_spatial_delta(ctx, layout, (const int16_t*)d_delta, (size_t)nt * tz_frame_elems(layout, H, W), nullptr, entropy ? 1 : 0,
+                             d_sym, entropy ? d_hist : nullptr, d_edge));
+    if (flat) {   // (k_sdelta_gray leaves the edge elements itself)
+        TZ_HIP(ctx, hipMemcpyAsync(d_edge, d_delta, 2, hipMemcpyDeviceToDevice, ctx->stream));
+        TZ_HIP(ctx, hipMemcpyAsync(d_edge + 1, (const int16_t*)d_delta + (N - 1), 2, hipMemcpyDeviceToDevice, ctx->stream));
+    }
     return TZ_OK;
 }
 
@@ -1611,13 +1615,6 @@ extern "C" int tz_set_payload_channels(tz_ctx* ctx, int channels) {
 
 extern "C" int tz_get_payload_channels(tz_ctx* ctx) { return ctx ? ctx->payload_channels : TZ_ERR_INVALID; }
 
-// the entry points of the sharded encoder / decoder do not serve a one-channel payload
-static int gray_unsupported(tz_ctx* ctx, const char* who) {
-    if (ctx->payload_channels == 1)
-        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve a one-channel payload (tz_set_payload_channels(1)): sharded gray jobs are not supported", who);
-    return TZ_OK;
-}
-
 // ---- spatial delta at the channel stride (include/tezip_hip.h: tz_set_delta_stride)
 extern "C" int tz_set_delta_stride(tz_ctx* ctx, int mode) {
     if (!ctx) return TZ_ERR_INVALID;
@@ -1629,11 +1626,17 @@ extern "C" int tz_set_delta_stride(tz_ctx* ctx, int mode) {
 
 extern "C" int tz_get_delta_stride(tz_ctx* ctx) { return ctx ? ctx->delta_stride_mode : TZ_ERR_INVALID; }
 
-// the stride in force: mode 1 on a one-channel payload is the flat delta
-static bool stride3(const tz_ctx* ctx) { return ctx->delta_stride_mode == 1 && ctx->payload_channels == 3; }
+// the layout in force (tz_internal.h): mode 1 on a one-channel payload is the flat delta
+static constexpr tz_layout kFlat = {3, 1};
+static tz_layout layout_of(const tz_ctx* ctx) {
+    return {ctx->payload_channels, ctx->delta_stride_mode == 1 && ctx->payload_channels == 3 ? 3 : 1};
+}
 
-// one carry element is not the carry of a strided scan, and sharded jobs are out of scope
-static int stride_unsupported(tz_ctx* ctx, const char* who) {
+// The entry points of the sharded encoder / decoder serve the flat layout alone: not a one-channel payload, and one carry
+// element is not the carry of a strided scan.  (tz_undelta_carry serves a gray payload: its carry is one element.)
+static int flat_only(tz_ctx* ctx, const char* who, bool serves_gray = false) {
+    if (ctx->payload_channels == 1 && !serves_gray)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve a one-channel payload (tz_set_payload_channels(1)): sharded gray jobs are not supported", who);
     if (ctx->delta_stride_mode == 1)
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve the channel-stride spatial delta (tz_set_delta_stride(1)): sharded jobs and one-element carries are flat only", who);
     return TZ_OK;
@@ -1660,51 +1663,19 @@ static int encode_all_gray(tz_ctx* ctx) {
     return TZ_OK;
 }
 
-// encode_front for a one-channel payload: the unfused path over the three-channel stack (delta, quantiser -- which also walks
-// channels 1 and 2, whose output is dropped), then the spatial delta of channel 0 alone; d_sym receives nt*H*W elements.
-static int encode_front_gray(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* d_sym, unsigned long long* d_hist,
-                             int16_t* d_edge) {
-    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
-    const size_t n1 = (size_t)nt * H * W;
-    void *d_mask = nullptr, *d_delta = nullptr;
-    TZ_TRY(tz_pool_alloc(ctx, nt, &d_mask));
-    TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
-    if (entropy) TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, TZ_NBINS * sizeof(unsigned long long), ctx->stream));
-    TZ_TRY(tz_pool_alloc(ctx, n1 * 3 * 2, &d_delta));
-    TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta));
-    TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_delta, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
-    return tzk_spatial_delta_gray(ctx, (const int16_t*)d_delta, n1, 0, 0, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge);
-}
-
-// encode_front under the channel stride: every job (lossless, identity shortcut, lossy) takes the unfused route -- delta and
-// quantiser into the delta stack (the caller's tap when there is one), then k_sdelta_s3; d_sym receives nt*H*W*3 elements.
-static int encode_front_s3(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* d_delta_tap, int16_t* d_sym,
-                           unsigned long long* d_hist) {
-    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
-    const size_t N = (size_t)nt * H * W * 3;
-    void *d_mask = nullptr, *d_delta = d_delta_tap;
-    TZ_TRY(tz_pool_alloc(ctx, nt, &d_mask));
-    TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
-    if (entropy) TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, TZ_NBINS * sizeof(unsigned long long), ctx->stream));
-    if (!d_delta) TZ_TRY(tz_pool_alloc(ctx, N * 2, &d_delta));
-    TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta));
-    TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_delta, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
-    return tzk_spatial_delta_s3(ctx, (const int16_t*)d_delta, N, nullptr, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr);
-}
-
 extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int16_t* payload, int16_t* table,
                          int* table_len, int16_t* delta_out) {
     tz_roctx_range roctx_("tz_encode");
     if (!ctx || !table_len || ((entropy & 1) && !table)) return TZ_ERR_INVALID;
     TZ_TRY(encode_check(ctx, "tz_encode", mode));
-    const bool gray = ctx->payload_channels == 1;
-    if (gray) {
+    const tz_layout layout = layout_of(ctx);
+    if (layout.channels == 1) {
         if (delta_out) return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode: no delta_out with a one-channel payload");
         const int rc_gray = encode_all_gray(ctx);
         tz_pool_release_all(ctx);
         TZ_TRY(rc_gray);
     }
-    const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * ctx->payload_channels;
+    const size_t N = (size_t)ctx->nt * tz_frame_elems(layout, ctx->H, ctx->W);
     const bool shuffle = (entropy & 2) != 0;  // opt-in byte planes (not a reference format)
     entropy &= 1;
     if (shuffle && (N & 7)) return tz_fail(ctx, TZ_ERR_INVALID, "byte shuffle needs a multiple of 8 elements");
@@ -1749,12 +1720,8 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
         if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N * 2, &d_sd);
     }
     int16_t* d_sym = entropy ? (int16_t*)d_sd : (int16_t*)o->dev;   // without a table the symbols are the payload
-    if (rc == TZ_OK && gray)
-        rc = encode_front_gray(ctx, mode, b0, b1, entropy, d_sym, (unsigned long long*)d_hist, (int16_t*)d_edge);
-    else if (rc == TZ_OK && stride3(ctx))
-        rc = encode_front_s3(ctx, mode, b0, b1, entropy, delta_out ? (int16_t*)o_delta.dev : nullptr, d_sym, (unsigned long long*)d_hist);
-    else if (rc == TZ_OK)
-        rc = encode_front(ctx, mode, b0, b1, entropy, delta_out ? (int16_t*)o_delta.dev : nullptr, d_sym,
+    if (rc == TZ_OK)
+        rc = encode_front(ctx, layout, mode, b0, b1, entropy, delta_out ? (int16_t*)o_delta.dev : nullptr, d_sym,
                           (unsigned long long*)d_hist, (int16_t*)d_edge);
     std::vector<int16_t> lut;
     if (rc == TZ_OK && !entropy) {
@@ -1788,8 +1755,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
                                int16_t* edge) {
     tz_roctx_range roctx_("tz_encode_begin");
     if (!ctx || !edge || (entropy && !hist)) return TZ_ERR_INVALID;
-    TZ_TRY(gray_unsupported(ctx, "tz_encode_begin"));
-    TZ_TRY(stride_unsupported(ctx, "tz_encode_begin"));
+    TZ_TRY(flat_only(ctx, "tz_encode_begin"));
     TZ_TRY(encode_check(ctx, "tz_encode_begin", mode));
     ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload now receives a shard's symbols
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
@@ -1799,7 +1765,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
     int rc = tz_pool_alloc(ctx, 16, &d_edge);
     if (rc == TZ_OK && entropy) rc = tz_pool_alloc(ctx, TZ_NBINS * sizeof(unsigned long long), &d_hist);
     if (rc == TZ_OK)
-        rc = encode_front(ctx, mode, b0, b1, entropy ? 1 : 0, nullptr, ctx->d_payload, (unsigned long long*)d_hist, (int16_t*)d_edge);
+        rc = encode_front(ctx, kFlat, mode, b0, b1, entropy ? 1 : 0, nullptr, ctx->d_payload, (unsigned long long*)d_hist, (int16_t*)d_edge);
     if (rc == TZ_OK) {
         hipError_t e = hipMemcpyAsync(edge, d_edge, 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess && entropy)
@@ -1820,8 +1786,7 @@ extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const
                                 int16_t* payload) {
     tz_roctx_range roctx_("tz_encode_finish");
     if (!ctx) return TZ_ERR_INVALID;
-    TZ_TRY(gray_unsupported(ctx, "tz_encode_finish"));
-    TZ_TRY(stride_unsupported(ctx, "tz_encode_finish"));
+    TZ_TRY(flat_only(ctx, "tz_encode_finish"));
     if (ctx->enc_kind != tz_ctx::ENC_SYMBOLS) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish needs a tz_encode_begin first");
     if (ctx->enc_entropy != (table_len >= 0) || (table_len > 0 && !table) || table_len > TZ_MAX_TABLE)
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode_finish: table does not match the entropy flag of tz_encode_begin");
@@ -1879,15 +1844,14 @@ extern "C" int tz_byte_unshuffle(tz_ctx* ctx, const uint8_t* in, size_t n, int16
 
 extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int16_t* delta_out) {
     if (!ctx || !delta_out) return TZ_ERR_INVALID;
-    TZ_TRY(gray_unsupported(ctx, "tz_encode_delta"));
-    TZ_TRY(stride_unsupported(ctx, "tz_encode_delta"));
+    TZ_TRY(flat_only(ctx, "tz_encode_delta"));
     TZ_TRY(encode_check(ctx, "tz_encode_delta", mode));
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
     std::vector<tz_out> outs;
     tz_out o;
     int rc = tz_dev_out(ctx, delta_out, N * 2, &o);
     if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = encode_front(ctx, mode, b0, b1, 0, (int16_t*)o.dev, nullptr, nullptr, nullptr);
+    if (rc == TZ_OK) rc = encode_front(ctx, kFlat, mode, b0, b1, 0, (int16_t*)o.dev, nullptr, nullptr, nullptr);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     tz_pool_release_all(ctx);
     return rc;
@@ -1895,8 +1859,7 @@ extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int1
 
 extern "C" int tz_decode_delta(tz_ctx* ctx, const int16_t* delta, uint8_t* frames_out) {
     if (!ctx || !delta || !frames_out) return TZ_ERR_INVALID;
-    TZ_TRY(gray_unsupported(ctx, "tz_decode_delta"));
-    TZ_TRY(stride_unsupported(ctx, "tz_decode_delta"));
+    TZ_TRY(flat_only(ctx, "tz_decode_delta"));
     if (!whole_stack(ctx, tz_ctx::ROLLOUT_DECODE)) return tz_fail(ctx, TZ_ERR_STATE, "tz_decode_delta needs a tz_rollout_decode first");
     TZ_TRY(tz_check_pred_contract(ctx, "tz_decode_delta"));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
@@ -1911,34 +1874,22 @@ extern "C" int tz_decode_delta(tz_ctx* ctx, const int16_t* delta, uint8_t* frame
     if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_mask);
     if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, ctx->key_mask.data(), nt);
     if (rc == TZ_OK)
-        rc = tzk_reconstruct(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, (const int16_t*)d_diff, nt, H, W,
+        rc = tzk_reconstruct(ctx, 3, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, (const int16_t*)d_diff, nt, H, W,
                              ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-// the decoded element in front of payload[n0] (k_undelta_carry): enqueued, then read back
-static int undelta_carry(tz_ctx* ctx, const int16_t* d_pay, size_t n0, const int16_t* h_lut, int16_t* carry) {
-    void* d_word;
-    unsigned w = 0;
-    TZ_TRY(tz_pool_alloc(ctx, sizeof(unsigned), &d_word));
-    TZ_TRY(tzk_undelta_carry(ctx, d_pay, n0, h_lut, 1, (unsigned*)d_word));
-    TZ_TRY(tz_d2h(ctx, &w, d_word, sizeof(unsigned), ctx->stream));
-    TZ_TRY(tz_stream_sync(ctx));
-    *carry = (int16_t)(w & 0xFFFFu);
-    return TZ_OK;
-}
-
-// the three decoded elements in front of payload[n0] under the channel stride (k_undelta_carry_s3): enqueued, then read back
-static int undelta_carry_s3(tz_ctx* ctx, const int16_t* d_pay, size_t n0, const int16_t* h_lut, int16_t* carry3) {
+// the `stride` decoded elements in front of payload[n0] (k_undelta_carry, k_undelta_carry_s3): enqueued, then read back
+static int undelta_carry(tz_ctx* ctx, int stride, const int16_t* d_pay, size_t n0, const int16_t* h_lut, int16_t* carry) {
     void* d_words;
     unsigned w[3] = {0, 0, 0};
-    TZ_TRY(tz_pool_alloc(ctx, sizeof(w), &d_words));
-    TZ_TRY(tzk_undelta_carry_s3(ctx, d_pay, n0, h_lut, 1, (unsigned*)d_words));
-    TZ_TRY(tz_d2h(ctx, w, d_words, sizeof(w), ctx->stream));
+    TZ_TRY(tz_pool_alloc(ctx, stride * sizeof(unsigned), &d_words));
+    TZ_TRY(tzk_undelta_carry(ctx, stride, d_pay, n0, h_lut, 1, (unsigned*)d_words));
+    TZ_TRY(tz_d2h(ctx, w, d_words, stride * sizeof(unsigned), ctx->stream));
     TZ_TRY(tz_stream_sync(ctx));
-    for (int c = 0; c < 3; ++c) carry3[c] = (int16_t)(w[c] & 0xFFFFu);
+    for (int c = 0; c < stride; ++c) carry[c] = (int16_t)(w[c] & 0xFFFFu);
     return TZ_OK;
 }
 
@@ -1957,21 +1908,27 @@ static int check_table(tz_ctx* ctx, const int16_t* table, int table_len) {
     return TZ_OK;
 }
 
-extern "C" int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, const int16_t* table, int table_len,
-                                int16_t* carry) {
-    tz_roctx_range roctx_("tz_undelta_carry");
-    if (!ctx || !carry) return TZ_ERR_INVALID;
-    TZ_TRY(stride_unsupported(ctx, "tz_undelta_carry"));
-    if (n0 == 0) return tz_fail(ctx, TZ_ERR_INVALID, "tz_undelta_carry: n0 = 0, the stream start has no carry");
+// the body of tz_undelta_carry and tz_undelta_carry_stride, behind their own checks of the mode, the stride and n0
+static int undelta_carry_seam(tz_ctx* ctx, int stride, const int16_t* payload, size_t n0, const int16_t* table, int table_len,
+                              int16_t* carry) {
     TZ_TRY(check_table(ctx, table, table_len));
     if (!payload) TZ_TRY(staged_payload(ctx, n0, &payload));
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
     const void* d_pay = nullptr;
     int rc = tz_dev_in(ctx, payload, n0 * 2, &d_pay);
-    if (rc == TZ_OK) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, table_len >= 0 ? lut.data() : nullptr, carry);
+    if (rc == TZ_OK) rc = undelta_carry(ctx, stride, (const int16_t*)d_pay, n0, table_len >= 0 ? lut.data() : nullptr, carry);
     tz_pool_release_all(ctx);
     return rc;
+}
+
+extern "C" int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, const int16_t* table, int table_len,
+                                int16_t* carry) {
+    tz_roctx_range roctx_("tz_undelta_carry");
+    if (!ctx || !carry) return TZ_ERR_INVALID;
+    TZ_TRY(flat_only(ctx, "tz_undelta_carry", true));
+    if (n0 == 0) return tz_fail(ctx, TZ_ERR_INVALID, "tz_undelta_carry: n0 = 0, the stream start has no carry");
+    return undelta_carry_seam(ctx, 1, payload, n0, table, table_len, carry);
 }
 
 // Frames [first, first + count) of the stream (decompress.py:203-256): the carry of the inverse scan in front of the range
@@ -1986,8 +1943,8 @@ static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, s
         return tz_fail(ctx, TZ_ERR_INVALID, "frame range [%d, %d + %d) outside the frames [%d, %d) the range rollout covered", first,
                        first, count, r, ctx->pred_end);
     // fe: bytes of a decoded frame; pe: payload elements of a frame (H*W of them under tz_set_payload_channels(1))
-    const bool gray = ctx->payload_channels == 1;
-    const size_t fe = (size_t)H * W * 3, pe = gray ? (size_t)H * W : fe, N = (size_t)nt * pe, n0 = (size_t)first * pe,
+    const tz_layout layout = layout_of(ctx);
+    const size_t fe = (size_t)H * W * 3, pe = tz_frame_elems(layout, H, W), N = (size_t)nt * pe, n0 = (size_t)first * pe,
                  np = (size_t)count * pe, nr = (size_t)count * fe;
     if (!payload) TZ_TRY(staged_payload(ctx, N, &payload));
     ctx->have_decoded = false;
@@ -2002,7 +1959,7 @@ static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, s
     tz_out o;
     const void* d_pay = nullptr;
     void* d_mask = nullptr;
-    int16_t carry = 0;
+    int16_t carry[3] = {0, 0, 0};   // the layout.stride decoded elements in front of the range
     int rc = tz_dev_in(ctx, payload, n0 * 2 + np * 2, &d_pay);
     if (rc == TZ_OK) rc = tz_dev_out(ctx, frames_out, nr, &o);
     if (rc == TZ_OK) outs.push_back(o);
@@ -2011,16 +1968,9 @@ static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, s
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    const bool s3 = stride3(ctx);
-    int16_t carry3[3] = {0, 0, 0};
-    if (rc == TZ_OK && first > 0 && s3) rc = undelta_carry_s3(ctx, (const int16_t*)d_pay, n0, h_lut, carry3);
-    else if (rc == TZ_OK && first > 0) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, h_lut, &carry);
-    if (rc == TZ_OK && s3)
-        rc = tzk_decode_tail_s3(ctx, (const int16_t*)d_pay + n0, h_lut, 1, first > 0 ? carry3 : nullptr,
-                                ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + (size_t)first * fe,
-                                (const uint8_t*)d_mask, count, H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
-    else if (rc == TZ_OK)
-        rc = (gray ? tzk_decode_tail_gray : tzk_decode_tail)(ctx, (const int16_t*)d_pay + n0, h_lut, 1, first > 0, carry,
+    if (rc == TZ_OK && first > 0) rc = undelta_carry(ctx, layout.stride, (const int16_t*)d_pay, n0, h_lut, carry);
+    if (rc == TZ_OK)
+        rc = tzk_decode_tail(ctx, layout, (const int16_t*)d_pay + n0, h_lut, 1, first > 0 ? carry : nullptr,
                              ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + (size_t)first * fe,
                              (const uint8_t*)d_mask, count, H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
@@ -2061,8 +2011,8 @@ static int encode_decoded(tz_ctx* ctx, const char* who, const int16_t* payload, 
     TZ_TRY(tz_check_pred_contract(ctx, who));
     TZ_TRY(check_table(ctx, table, table_len));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
-    const bool gray = ctx->payload_channels == 1;
-    const size_t fe = (size_t)H * W * 3, N = (size_t)nt * (gray ? (size_t)H * W : fe);   // N: payload elements
+    const tz_layout layout = layout_of(ctx);
+    const size_t fe = (size_t)H * W * 3, N = (size_t)nt * tz_frame_elems(layout, H, W);   // N: payload elements
     if (!payload) {
         if (ctx->enc_kind != tz_ctx::ENC_PAYLOAD || !ctx->d_payload || ctx->payload_len != N)
             return tz_fail(ctx, TZ_ERR_STATE, "no resident payload of a tz_encode on this rollout");
@@ -2086,12 +2036,9 @@ static int encode_decoded(tz_ctx* ctx, const char* who, const int16_t* payload, 
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    if (rc == TZ_OK && stride3(ctx))   // the launches of tz_decode
-        rc = tzk_decode_tail_s3(ctx, (const int16_t*)d_pay, h_lut, 1, nullptr, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H,
-                                W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
-    else if (rc == TZ_OK)
-        rc = (gray ? tzk_decode_tail_gray : tzk_decode_tail)(ctx, (const int16_t*)d_pay, h_lut, 1, 0, 0, ctx->d_pred, ctx->d_frames,
-                                                             (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
+    if (rc == TZ_OK)   // the launches of tz_decode
+        rc = tzk_decode_tail(ctx, layout, (const int16_t*)d_pay, h_lut, 1, nullptr, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt,
+                             H, W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
     *d_dec_out = (const uint8_t*)d_dec;
     return rc;
 }
@@ -2269,14 +2216,22 @@ extern "C" int tz_error_bound(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, c
     return rc;
 }
 
-extern "C" int tz_spatial_delta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, int apply_offset,
-                                int16_t* out, unsigned long long* hist) {
-    if (!ctx || !in || !out) return TZ_ERR_INVALID;
+// The seams.  Each operation has one body, which takes the layout (tz_internal.h); the exported names of the gray payload
+// (tz_set_payload_channels) and of the channel-stride spatial delta (tz_set_delta_stride) state theirs.  A seam at stride 1
+// is the flat seam, bytes and messages.
+static int check_stride(tz_ctx* ctx, const char* who, int stride) {
+    if (stride != 1 && stride != 3) return tz_fail(ctx, TZ_ERR_INVALID, "%s: stride must be 1 or 3, not %d", who, stride);
+    return TZ_OK;
+}
+
+// n_in elements at `in` -> n_out at `out` (gray: three interleaved channels in, channel 0's delta out)
+static int spatial_delta_seam(tz_ctx* ctx, tz_layout layout, const int16_t* in, size_t n_in, size_t n_out, const int16_t* carry,
+                              int apply_offset, int16_t* out, unsigned long long* hist) {
     const void* din;
     tz_out o, oh;
     std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in, n * 2, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
+    int rc = tz_dev_in(ctx, in, n_in * 2, &din);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n_out * 2, &o);
     if (rc == TZ_OK) outs.push_back(o);
     void* dh = nullptr;
     if (rc == TZ_OK && hist) {
@@ -2290,10 +2245,30 @@ extern "C" int tz_spatial_delta(tz_ctx* ctx, const int16_t* in, size_t n, int ha
             outs.push_back(oh);
         }
     }
-    if (rc == TZ_OK) rc = tzk_spatial_delta(ctx, (const int16_t*)din, n, has_carry, carry, apply_offset, (int16_t*)o.dev, (unsigned long long*)dh);
+    if (rc == TZ_OK)
+        rc = tzk_spatial_delta(ctx, layout, (const int16_t*)din, n_out, carry, apply_offset, (int16_t*)o.dev, (unsigned long long*)dh, nullptr);
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
     tz_pool_release_all(ctx);
     return rc;
+}
+
+extern "C" int tz_spatial_delta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, int apply_offset,
+                                int16_t* out, unsigned long long* hist) {
+    if (!ctx || !in || !out) return TZ_ERR_INVALID;
+    return spatial_delta_seam(ctx, kFlat, in, n, n, has_carry ? &carry : nullptr, apply_offset, out, hist);
+}
+
+extern "C" int tz_spatial_delta_gray(tz_ctx* ctx, const int16_t* in3, size_t npix, int has_carry, int16_t carry, int apply_offset,
+                                     int16_t* out, unsigned long long* hist) {
+    if (!ctx || !in3 || !out) return TZ_ERR_INVALID;
+    return spatial_delta_seam(ctx, {1, 1}, in3, npix * 3, npix, has_carry ? &carry : nullptr, apply_offset, out, hist);
+}
+
+extern "C" int tz_spatial_delta_stride(tz_ctx* ctx, const int16_t* in, size_t n, int stride, const int16_t* carry, int apply_offset,
+                                       int16_t* out, unsigned long long* hist) {
+    if (!ctx || !in || !out) return TZ_ERR_INVALID;
+    TZ_TRY(check_stride(ctx, "tz_spatial_delta_stride", stride));
+    return spatial_delta_seam(ctx, {3, stride}, in, n, n, carry, apply_offset, out, hist);
 }
 
 static int lut_op(tz_ctx* ctx, const int16_t* in, size_t n, const std::vector<int16_t>& lut, int post, int16_t* out) {
@@ -2326,8 +2301,9 @@ extern "C" int tz_unmap(tz_ctx* ctx, const int16_t* in, size_t n, const int16_t*
     return lut_op(ctx, in, n, lut, apply_offset, out);
 }
 
-extern "C" int tz_spatial_undelta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, int16_t* out) {
-    if (!ctx || !in || !out) return TZ_ERR_INVALID;
+// (stride 3 ends with a synchronisation that reads the fault word of the scan's bounded poll; the flat seam leaves that to the
+// caller's next synchronising call -- an open difference)
+static int spatial_undelta_seam(tz_ctx* ctx, int stride, const int16_t* in, size_t n, const int16_t* carry, int16_t* out) {
     const void* din;
     tz_out o;
     std::vector<tz_out> outs;
@@ -2335,66 +2311,23 @@ extern "C" int tz_spatial_undelta(tz_ctx* ctx, const int16_t* in, size_t n, int 
     if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
     if (rc == TZ_OK) {
         outs.push_back(o);
-        rc = tzk_undelta(ctx, (const int16_t*)din, n, has_carry, carry, (int16_t*)o.dev);
+        rc = tzk_undelta(ctx, stride, (const int16_t*)din, n, carry, nullptr, 0, (int16_t*)o.dev);
     }
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK && stride == 3) rc = tz_stream_sync(ctx);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-// The seams of the channel-stride spatial delta (tz_set_delta_stride): stride 3 runs the strided kernels, stride 1 the flat
-// ones, so that its bytes are tz_spatial_delta's / tz_spatial_undelta's / tz_undelta_carry's.
-static int check_stride(tz_ctx* ctx, const char* who, int stride) {
-    if (stride != 1 && stride != 3) return tz_fail(ctx, TZ_ERR_INVALID, "%s: stride must be 1 or 3, not %d", who, stride);
-    return TZ_OK;
-}
-
-extern "C" int tz_spatial_delta_stride(tz_ctx* ctx, const int16_t* in, size_t n, int stride, const int16_t* carry, int apply_offset,
-                                       int16_t* out, unsigned long long* hist) {
+extern "C" int tz_spatial_undelta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, int16_t* out) {
     if (!ctx || !in || !out) return TZ_ERR_INVALID;
-    TZ_TRY(check_stride(ctx, "tz_spatial_delta_stride", stride));
-    if (stride == 1) return tz_spatial_delta(ctx, in, n, carry != nullptr, carry ? carry[0] : (int16_t)0, apply_offset, out, hist);
-    const void* din;
-    tz_out o, oh;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in, n * 2, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    void* dh = nullptr;
-    if (rc == TZ_OK && hist) {
-        rc = tz_dev_out(ctx, hist, TZ_NBINS * sizeof(unsigned long long), &oh);
-        if (rc == TZ_OK) {
-            dh = oh.dev;
-            if (oh.host) {  // counts are ADDED to what the caller holds
-                hipError_t e = hipMemcpyAsync(dh, hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream);
-                if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "hist upload: %s", hipGetErrorString(e));
-            }
-            outs.push_back(oh);
-        }
-    }
-    if (rc == TZ_OK) rc = tzk_spatial_delta_s3(ctx, (const int16_t*)din, n, carry, apply_offset, (int16_t*)o.dev, (unsigned long long*)dh);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    return spatial_undelta_seam(ctx, 1, in, n, has_carry ? &carry : nullptr, out);
 }
 
 extern "C" int tz_spatial_undelta_stride(tz_ctx* ctx, const int16_t* in, size_t n, int stride, const int16_t* carry, int16_t* out) {
     if (!ctx || !in || !out) return TZ_ERR_INVALID;
     TZ_TRY(check_stride(ctx, "tz_spatial_undelta_stride", stride));
-    if (stride == 1) return tz_spatial_undelta(ctx, in, n, carry != nullptr, carry ? carry[0] : (int16_t)0, out);
-    const void* din;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in, n * 2, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_undelta_s3(ctx, (const int16_t*)din, n, carry, nullptr, 0, (int16_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (the fault word of the bounded poll is read here)
-    tz_pool_release_all(ctx);
-    return rc;
+    return spatial_undelta_seam(ctx, stride, in, n, carry, out);
 }
 
 extern "C" int tz_undelta_carry_stride(tz_ctx* ctx, const int16_t* payload, size_t n0, int stride, const int16_t* table, int table_len,
@@ -2404,21 +2337,12 @@ extern "C" int tz_undelta_carry_stride(tz_ctx* ctx, const int16_t* payload, size
     TZ_TRY(check_stride(ctx, "tz_undelta_carry_stride", stride));
     if (n0 == 0 || n0 % (size_t)stride)
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_undelta_carry_stride: n0 = %zu is not a positive multiple of the stride %d", n0, stride);
-    TZ_TRY(check_table(ctx, table, table_len));
-    if (!payload) TZ_TRY(staged_payload(ctx, n0, &payload));
-    std::vector<int16_t> lut;
-    if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
-    const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    const void* d_pay = nullptr;
-    int rc = tz_dev_in(ctx, payload, n0 * 2, &d_pay);
-    if (rc == TZ_OK && stride == 1) rc = undelta_carry(ctx, (const int16_t*)d_pay, n0, h_lut, carry_out);
-    else if (rc == TZ_OK) rc = undelta_carry_s3(ctx, (const int16_t*)d_pay, n0, h_lut, carry_out);
-    tz_pool_release_all(ctx);
-    return rc;
+    return undelta_carry_seam(ctx, stride, payload, n0, table, table_len, carry_out);
 }
 
-extern "C" int tz_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key_frames, const uint8_t* key_mask,
-                              const int16_t* diff, int nframes, int H, int W, uint8_t* out) {
+// diff: `channels` deltas per pixel
+static int reconstruct_seam(tz_ctx* ctx, int channels, const float* pred, const uint8_t* key_frames, const uint8_t* key_mask,
+                            const int16_t* diff, int nframes, int H, int W, uint8_t* out) {
     if (!ctx || !pred || !diff || !out || nframes < 0 || H < 1 || W < 1) return TZ_ERR_INVALID;
     int Hp = pad8(H), Wp = pad8(W);
     size_t N = (size_t)nframes * H * W * 3;
@@ -2430,13 +2354,13 @@ extern "C" int tz_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key
     std::vector<tz_out> outs;
     int rc = tz_dev_in(ctx, pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp);
     if (rc == TZ_OK && key_frames) rc = tz_dev_in(ctx, key_frames, N, &dk);
-    if (rc == TZ_OK) rc = tz_dev_in(ctx, diff, N * 2, &dd);
+    if (rc == TZ_OK) rc = tz_dev_in(ctx, diff, N / 3 * channels * 2, &dd);
     if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nframes, &dm);
     if (rc == TZ_OK && nframes) rc = tz_upload(ctx, dm, km.data(), nframes);
     if (rc == TZ_OK) rc = tz_dev_out(ctx, out, N, &o);
     if (rc == TZ_OK) {
         outs.push_back(o);
-        rc = tzk_reconstruct(ctx, (const float*)dp, (const uint8_t*)dk, (const uint8_t*)dm, (const int16_t*)dd, nframes, H,
+        rc = tzk_reconstruct(ctx, channels, (const float*)dp, (const uint8_t*)dk, (const uint8_t*)dm, (const int16_t*)dd, nframes, H,
                              W, Hp, Wp, (uint8_t*)o.dev);
     }
     if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
@@ -2444,60 +2368,14 @@ extern "C" int tz_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key
     return rc;
 }
 
-extern "C" int tz_spatial_delta_gray(tz_ctx* ctx, const int16_t* in3, size_t npix, int has_carry, int16_t carry, int apply_offset,
-                                     int16_t* out, unsigned long long* hist) {
-    if (!ctx || !in3 || !out) return TZ_ERR_INVALID;
-    const void* din;
-    tz_out o, oh;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in3, npix * 3 * 2, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, npix * 2, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    void* dh = nullptr;
-    if (rc == TZ_OK && hist) {
-        rc = tz_dev_out(ctx, hist, TZ_NBINS * sizeof(unsigned long long), &oh);
-        if (rc == TZ_OK) {
-            dh = oh.dev;
-            if (oh.host) {  // counts are ADDED to what the caller holds
-                hipError_t e = hipMemcpyAsync(dh, hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream);
-                if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "hist upload: %s", hipGetErrorString(e));
-            }
-            outs.push_back(oh);
-        }
-    }
-    if (rc == TZ_OK)
-        rc = tzk_spatial_delta_gray(ctx, (const int16_t*)din, npix, has_carry, carry, apply_offset, (int16_t*)o.dev,
-                                    (unsigned long long*)dh, nullptr);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+extern "C" int tz_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key_frames, const uint8_t* key_mask,
+                              const int16_t* diff, int nframes, int H, int W, uint8_t* out) {
+    return reconstruct_seam(ctx, 3, pred, key_frames, key_mask, diff, nframes, H, W, out);
 }
 
 extern "C" int tz_reconstruct_gray(tz_ctx* ctx, const float* pred, const uint8_t* key_frames, const uint8_t* key_mask,
                                    const int16_t* diff1, int nframes, int H, int W, uint8_t* out) {
-    if (!ctx || !pred || !diff1 || !out || nframes < 0 || H < 1 || W < 1) return TZ_ERR_INVALID;
-    int Hp = pad8(H), Wp = pad8(W);
-    size_t n1 = (size_t)nframes * H * W;
-    std::vector<uint8_t> km(nframes, 0);
-    if (key_mask && key_frames) memcpy(km.data(), key_mask, nframes);
-    const void *dp, *dk = nullptr, *dd;
-    void* dm;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp);
-    if (rc == TZ_OK && key_frames) rc = tz_dev_in(ctx, key_frames, n1 * 3, &dk);
-    if (rc == TZ_OK) rc = tz_dev_in(ctx, diff1, n1 * 2, &dd);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nframes, &dm);
-    if (rc == TZ_OK && nframes) rc = tz_upload(ctx, dm, km.data(), nframes);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n1 * 3, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_reconstruct_gray(ctx, (const float*)dp, (const uint8_t*)dk, (const uint8_t*)dm, (const int16_t*)dd, nframes, H,
-                                  W, Hp, Wp, (uint8_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    return reconstruct_seam(ctx, 1, pred, key_frames, key_mask, diff1, nframes, H, W, out);
 }
 
 extern "C" int tz_window_sse(tz_ctx* ctx, const uint8_t* orig, const float* pred, int nframes, int H, int W, double* sse) {

@@ -1689,22 +1689,6 @@ bool tz_quant_is_identity(int mode, double b0, double b1) {
     return enabled && worst >= 0.0 && worst <= kQIdentityMaxE;   // (a NaN or a negative tolerance: the general path and its errors)
 }
 
-int tzk_spatial_delta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, int apply_offset,
-                      int16_t* out, unsigned long long* d_hist) {
-    if (n == 0) return TZ_OK;
-    if (((uintptr_t)in & 15) || ((uintptr_t)out & 15))
-        return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta buffers must be 16-byte aligned");
-    tz_prof_scope ps(ctx, TZP_SDELTA);
-    if (d_hist)
-        hipLaunchKernelGGL(k_sdelta<true>, dim3(std::min(HB_GRID, grid_for(n / 8 + 1, HB_THREADS))), dim3(HB_THREADS), 0, ctx->stream,
-                           in, n, has_carry, carry, apply_offset, out, d_hist);
-    else
-        hipLaunchKernelGGL(k_sdelta<false>, dim3(grid_for(n / 8 + 1, 256)), dim3(256), 0, ctx->stream, in, n, has_carry, carry,
-                           apply_offset, out, d_hist);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
-}
-
 // ------------------------------------------------- spatial delta of channel 0 alone (one-channel payload of a gray job)
 // tz_set_payload_channels(1): finding_difference (compress.py:73-77) over channel 0 of the interleaved (frame, y, x, 3) stack,
 // out[0] = x[0] (or carry - x[0]), out[p] = x[3(p-1)] - x[3p]; then 1600 - y and the histogram as k_sdelta.  Channels 1 and 2
@@ -1760,32 +1744,6 @@ __global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_sdelta_gray(const i
     if (HIST) hist_flush(hl, acc, centre, hist);
 }
 
-int tzk_spatial_delta_gray(tz_ctx* ctx, const int16_t* in3, size_t npix, int has_carry, int16_t carry, int apply_offset,
-                           int16_t* out, unsigned long long* d_hist, int16_t* d_edge) {
-    if (npix == 0) return TZ_OK;
-    if (((uintptr_t)in3 | (uintptr_t)out) & 1) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_gray buffers must be 2-byte aligned");
-    // the first pixel h at which both in3 + 3 h and out + h sit on a 16-byte boundary: 6 h = -in3 (mod 16) has one solution
-    // in [0, 8) and so has 2 h = -out; when the two differ nothing can be vectorised
-    size_t head = npix;
-    for (size_t h = 0; h < 8 && h < npix; ++h)
-        if ((((uintptr_t)in3 + 6 * h) & 15) == 0 && (((uintptr_t)out + 2 * h) & 15) == 0) {
-            head = h;
-            break;
-        }
-    const size_t n8 = (npix - head) / 8;
-    if (n8 == 0) head = npix;
-    tz_prof_scope ps(ctx, TZP_SDELTA);
-    const size_t items = std::max(n8, head + (npix - head - 8 * n8));
-    if (d_hist)
-        hipLaunchKernelGGL(k_sdelta_gray<true>, dim3(std::min(HB_GRID, grid_for(items, HB_THREADS))), dim3(HB_THREADS), 0, ctx->stream,
-                           in3, npix, head, n8, has_carry, carry, apply_offset, out, d_hist, d_edge);
-    else
-        hipLaunchKernelGGL(k_sdelta_gray<false>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, in3, npix, head, n8,
-                           has_carry, carry, apply_offset, out, d_hist, d_edge);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
-}
-
 // ------------------------------------------------- spatial delta at the channel stride (tz_set_delta_stride(1))
 // Not in the reference: out[i] = in[i-3] - in[i] (int16 wrap) over the flattened (frame, y, x, 3) stack, out[i] = in[i] (or
 // carry[i] - in[i]) for i < 3 -- the neighbour of a sample is the SAME channel of the pixel in front, not another channel of
@@ -1838,20 +1796,47 @@ __global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_sdelta_s3(const int
     if (HIST) hist_flush(hl, acc, centre, hist);
 }
 
-int tzk_spatial_delta_s3(tz_ctx* ctx, const int16_t* in, size_t n, const int16_t* carry3, int apply_offset, int16_t* out,
-                         unsigned long long* d_hist) {
+// The spatial delta of every layout (tz_internal.h): k_sdelta (flat), k_sdelta_gray or k_sdelta_s3, each with its own alignment
+// rule and its own cut into vector groups and single elements; one grid rule over the resulting work items.
+int tzk_spatial_delta(tz_ctx* ctx, tz_layout layout, const int16_t* in, size_t n, const int16_t* carry, int apply_offset, int16_t* out,
+                      unsigned long long* d_hist, int16_t* d_edge) {
     if (n == 0) return TZ_OK;
-    if (((uintptr_t)in | (uintptr_t)out) & 1) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_s3 buffers must be 2-byte aligned");
-    const size_t n8 = ((((uintptr_t)in | (uintptr_t)out) & 15) == 0) ? n / 8 : 0;
-    const short c0 = carry3 ? carry3[0] : 0, c1 = carry3 ? carry3[1] : 0, c2 = carry3 ? carry3[2] : 0;
+    const bool gray = layout.channels == 1, s3 = layout.stride == 3;
+    const uintptr_t both = (uintptr_t)in | (uintptr_t)out;
+    if (gray && (both & 1)) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_gray buffers must be 2-byte aligned");
+    if (s3 && (both & 1)) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_s3 buffers must be 2-byte aligned");
+    if (!gray && !s3 && (both & 15)) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta buffers must be 16-byte aligned");
+    size_t head = 0, n8 = 0, items = n / 8 + 1;   // flat: the kernel cuts the stack itself
+    if (gray) {
+        // the first pixel h at which both in + 3 h and out + h sit on a 16-byte boundary: 6 h = -in (mod 16) has one solution
+        // in [0, 8) and so has 2 h = -out; when the two differ nothing can be vectorised
+        head = n;
+        for (size_t h = 0; h < 8 && h < n; ++h)
+            if ((((uintptr_t)in + 6 * h) & 15) == 0 && (((uintptr_t)out + 2 * h) & 15) == 0) {
+                head = h;
+                break;
+            }
+        n8 = (n - head) / 8;
+        if (n8 == 0) head = n;
+        items = std::max(n8, head + (n - head - 8 * n8));
+    } else if (s3) {
+        n8 = (both & 15) == 0 ? n / 8 : 0;
+        items = std::max(n8, n - 8 * n8);
+    }
+    const int has_carry = carry != nullptr;
+    const short c0 = carry ? carry[0] : 0, c1 = carry && s3 ? carry[1] : 0, c2 = carry && s3 ? carry[2] : 0;
     tz_prof_scope ps(ctx, TZP_SDELTA);
-    const size_t items = std::max(n8, n - 8 * n8);
-    if (d_hist)
-        hipLaunchKernelGGL(k_sdelta_s3<true>, dim3(std::min(HB_GRID, grid_for(items, HB_THREADS))), dim3(HB_THREADS), 0, ctx->stream, in,
-                           n, n8, carry3 != nullptr, c0, c1, c2, apply_offset, out, d_hist);
-    else
-        hipLaunchKernelGGL(k_sdelta_s3<false>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, in, n, n8, carry3 != nullptr, c0,
-                           c1, c2, apply_offset, out, d_hist);
+    const dim3 grid(d_hist ? std::min(HB_GRID, grid_for(items, HB_THREADS)) : grid_for(items, 256)), block(d_hist ? HB_THREADS : 256);
+#define TZ_SDELTA_LAUNCH(K, ...)                                                                   \
+    do {                                                                                           \
+        if (d_hist) hipLaunchKernelGGL(K<true>, grid, block, 0, ctx->stream, __VA_ARGS__);         \
+        else hipLaunchKernelGGL(K<false>, grid, block, 0, ctx->stream, __VA_ARGS__);               \
+    } while (0)
+    // (flat first: the kernels' place in the code object follows their first mention)
+    if (!gray && !s3) TZ_SDELTA_LAUNCH(k_sdelta, in, n, has_carry, c0, apply_offset, out, d_hist);
+    else if (gray) TZ_SDELTA_LAUNCH(k_sdelta_gray, in, n, head, n8, has_carry, c0, apply_offset, out, d_hist, d_edge);
+    else TZ_SDELTA_LAUNCH(k_sdelta_s3, in, n, n8, has_carry, c0, c1, c2, apply_offset, out, d_hist);
+#undef TZ_SDELTA_LAUNCH
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
@@ -2244,69 +2229,62 @@ __global__ __launch_bounds__(256) void k_scan2p(const int16_t* __restrict__ in, 
     }
 }
 
-static int scan_launch(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, const int16_t* h_lut2112,
-                       int post_offset, int16_t* out, const ScanRecon* recon = nullptr) {
+// pool memory holding the 2112+1-entry decode LUT (*d_lut = NULL without one)
+static int upload_dec_lut(tz_ctx* ctx, const int16_t* h_lut2112, void** d_lut) {
+    *d_lut = nullptr;
+    if (!h_lut2112) return TZ_OK;
+    TZ_TRY(tz_pool_alloc(ctx, (TZ_NBINS + 1) * 2, d_lut));
+    return tz_upload(ctx, *d_lut, h_lut2112, (TZ_NBINS + 1) * 2);
+}
+
+// The host steps of an inverse-scan launch, k_scan2p's and k_scan3p's alike: the geometry (wave-tiles, blocks, tiles per wave),
+// the LUT, the fault word, the status words of the kernel (its own buffer and epoch counter) tagged with a fresh epoch, the
+// vec test; then launch(G, tiles per wave, d_lut, vec, epoch, the epoch to poll for, the poll limit).
+template <class Status, class Launch>
+static int scan_run(tz_ctx* ctx, const char* what, const int16_t* in, size_t n, const int16_t* out, const int16_t* h_lut2112,
+                    Status** d_status, unsigned* epoch_counter, Launch launch) {
     if (n == 0) return TZ_OK;
     const size_t tiles = (n + SCAN_WT - 1) / SCAN_WT;                 // wave-tiles
     const int G = (int)std::min<size_t>(SCAN_G, (tiles + 3) / 4);
     const size_t tpb = (tiles + (size_t)G * 4 - 1) / ((size_t)G * 4);   // per wave
-    if (tpb > 0x7FFFFFFFull) return tz_fail(ctx, TZ_ERR_INVALID, "inverse scan: too many elements");
-    void* d_lut = nullptr;
-    if (h_lut2112) {
-        TZ_TRY(tz_pool_alloc(ctx, (TZ_NBINS + 1) * 2, &d_lut));
-        TZ_TRY(tz_upload(ctx, d_lut, h_lut2112, (TZ_NBINS + 1) * 2));
-    }
-    if (!ctx->d_scan_status) TZ_HIP(ctx, hipMalloc((void**)&ctx->d_scan_status, sizeof(unsigned) * SCAN_G));
+    if (tpb > 0x7FFFFFFFull) return tz_fail(ctx, TZ_ERR_INVALID, "%s: too many elements", what);
+    void* d_lut;
+    TZ_TRY(upload_dec_lut(ctx, h_lut2112, &d_lut));
+    if (!*d_status) TZ_HIP(ctx, hipMalloc((void**)d_status, sizeof(Status) * SCAN_G));
     TZ_TRY(tz_fault_word(ctx));
     tz_prof_scope ps(ctx, TZP_SCAN);
-    if (ctx->scan_epoch == 0 || ctx->scan_epoch == 0xFFFFu) {   // first launch, or the epochs have gone round
-        TZ_HIP(ctx, hipMemsetAsync(ctx->d_scan_status, 0, sizeof(unsigned) * SCAN_G, ctx->stream));
-        ctx->scan_epoch = 0;
+    if (*epoch_counter == 0 || *epoch_counter == 0xFFFFu) {   // first launch, or the epochs have gone round
+        TZ_HIP(ctx, hipMemsetAsync(*d_status, 0, sizeof(Status) * SCAN_G, ctx->stream));
+        *epoch_counter = 0;
     }
-    const unsigned epoch = ++ctx->scan_epoch;
+    const unsigned epoch = ++*epoch_counter;
     const int vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-    static const int keep_regs = !getenv("TEZIP_SCAN_KEEP") || atoi(getenv("TEZIP_SCAN_KEEP")) != 0;   // (0: A/B against the two reads)
-    ScanRecon rcv = recon ? *recon : ScanRecon{};
-    rcv.keep_regs = keep_regs;
-#define TZ_SCAN_LAUNCH(L, R)                                                                                              \
-    hipLaunchKernelGGL((k_scan2p<L, R>), dim3(G), dim3(256), 0, ctx->stream, in, n, (int)tpb, has_carry, carry, vec,      \
-                       (const int16_t*)d_lut, post_offset, ctx->d_scan_status, epoch, (epoch + ctx->scan_dbg_skew) & 0xFFFFu,       \
-                       ctx->scan_dbg_limit ? ctx->scan_dbg_limit : SCAN_POLL_LIMIT, ctx->d_fault, out, rcv)
-    if (recon) {
-        if (h_lut2112) TZ_SCAN_LAUNCH(true, true);
-        else TZ_SCAN_LAUNCH(false, true);
-    } else {
-        if (h_lut2112) TZ_SCAN_LAUNCH(true, false);
-        else TZ_SCAN_LAUNCH(false, false);
-    }
-#undef TZ_SCAN_LAUNCH
+    launch(G, (int)tpb, (const int16_t*)d_lut, vec, epoch, (epoch + ctx->scan_dbg_skew) & 0xFFFFu,
+           ctx->scan_dbg_limit ? ctx->scan_dbg_limit : SCAN_POLL_LIMIT);
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
 
-int tzk_undelta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, int16_t* out) {
-    return scan_launch(ctx, in, n, has_carry, carry, nullptr, 0, out);
-}
-
-// the decoder's tail over frames [first, first + nframes) of a stream (tz_decode, tz_decode_range, tz_encode_quality): `in`,
-// pred, key and d_key_mask point at the range's first frame and `carry` is the decoded element in front of it (has_carry = 0
-// at the stream start).  One launch (inverse remap when there is a table, inverse spatial delta, reconstruct) where the
-// layout allows it: unpadded frames of a multiple of 16 elements, 16-byte aligned buffers, and no TEZIP_DECODE_UNFUSED.
-// Else a scan into a temporary and k_recon*.
-int tzk_decode_tail(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry, int16_t carry,
-                    const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
-                    uint8_t* out) {
-    const size_t fe = (size_t)H * W * 3, n = (size_t)nframes * fe;
-    if (n == 0) return TZ_OK;
-    if (H == Hp && W == Wp && fe % SCAN_EPT == 0 && key && !ctx->decode_unfused &&
-        ((((uintptr_t)in | (uintptr_t)pred | (uintptr_t)key | (uintptr_t)out) & 15) == 0)) {
-        const ScanRecon rc = {(const float4*)pred, key, d_key_mask, (unsigned long long)fe, out};
-        return scan_launch(ctx, in, n, has_carry, carry, h_lut2112, post_offset, nullptr, &rc);
-    }
-    void* d_diff;
-    TZ_TRY(tz_pool_alloc(ctx, n * 2, &d_diff));
-    TZ_TRY(scan_launch(ctx, in, n, has_carry, carry, h_lut2112, post_offset, (int16_t*)d_diff));
-    return tzk_reconstruct(ctx, pred, key, d_key_mask, (const int16_t*)d_diff, nframes, H, W, Hp, Wp, out);
+// k_scan2p over n elements: into `out`, or (recon) through the reconstruct into recon->out
+static int scan_launch(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, const int16_t* h_lut2112,
+                       int post_offset, int16_t* out, const ScanRecon* recon = nullptr) {
+    static const int keep_regs = !getenv("TEZIP_SCAN_KEEP") || atoi(getenv("TEZIP_SCAN_KEEP")) != 0;   // (0: A/B against the two reads)
+    ScanRecon rcv = recon ? *recon : ScanRecon{};
+    rcv.keep_regs = keep_regs;
+    return scan_run(ctx, "inverse scan", in, n, out, h_lut2112, &ctx->d_scan_status, &ctx->scan_epoch,
+                    [&](int G, int tpb, const int16_t* d_lut, int vec, unsigned epoch, unsigned poll_epoch, unsigned limit) {
+#define TZ_SCAN_LAUNCH(L, R)                                                                                                     \
+    hipLaunchKernelGGL((k_scan2p<L, R>), dim3(G), dim3(256), 0, ctx->stream, in, n, tpb, has_carry, carry, vec, d_lut, post_offset, \
+                       ctx->d_scan_status, epoch, poll_epoch, limit, ctx->d_fault, out, rcv)
+                        if (recon) {
+                            if (h_lut2112) TZ_SCAN_LAUNCH(true, true);
+                            else TZ_SCAN_LAUNCH(false, true);
+                        } else {
+                            if (h_lut2112) TZ_SCAN_LAUNCH(true, false);
+                            else TZ_SCAN_LAUNCH(false, false);
+                        }
+#undef TZ_SCAN_LAUNCH
+                    });
 }
 
 // ------------------------------------------------------------------------ prefix carry of the inverse scan
@@ -2367,29 +2345,6 @@ __global__ __launch_bounds__(256) void k_undelta_carry(const int16_t* __restrict
     __syncthreads();
     if (threadIdx.x == 0)
         __hip_atomic_fetch_add(word, 0u - (wsum[0] + wsum[1] + wsum[2] + wsum[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// enqueue the carry of payload[0, n0) into *d_word (device); h_lut2112 NULL = symbols as stored
-int tzk_undelta_carry(tz_ctx* ctx, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_word) {
-    if (n0 == 0) return tz_fail(ctx, TZ_ERR_INVALID, "undelta carry: the stream start has no carry");
-    void* d_lut = nullptr;
-    if (h_lut2112) {
-        TZ_TRY(tz_pool_alloc(ctx, (TZ_NBINS + 1) * 2, &d_lut));
-        TZ_TRY(tz_upload(ctx, d_lut, h_lut2112, (TZ_NBINS + 1) * 2));
-    }
-    const unsigned head = (unsigned)std::min<size_t>(n0, ((16 - ((uintptr_t)in & 15)) & 15) / 2);
-    if (((uintptr_t)in & 1) != 0) return tz_fail(ctx, TZ_ERR_INVALID, "undelta carry: payload not 2-byte aligned");
-    TZ_HIP(ctx, hipMemsetAsync(d_word, 0, sizeof(unsigned), ctx->stream));
-    const int G = grid_for((n0 - head) / 8 / CARRY_UNROLL + 1, 256);
-    tz_prof_scope ps(ctx, TZP_CARRY);
-    if (h_lut2112)
-        hipLaunchKernelGGL(k_undelta_carry<true>, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)d_lut,
-                           post_offset, d_word);
-    else
-        hipLaunchKernelGGL(k_undelta_carry<false>, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)nullptr,
-                           post_offset, d_word);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
 }
 
 // --------------------------------------------- inverse spatial delta at the channel stride (tz_set_delta_stride(1))
@@ -2550,51 +2505,23 @@ __global__ __launch_bounds__(256) void k_scan3p(const int16_t* __restrict__ in, 
     }
 }
 
-int tzk_undelta_s3(tz_ctx* ctx, const int16_t* in, size_t n, const int16_t* carry3, const int16_t* h_lut2112, int post_offset,
-                   int16_t* out) {
+// The inverse spatial delta at either stride: k_scan2p, or k_scan3p over any 2-byte aligned buffers.  carry: NULL at the stream
+// start, else the `stride` HOST elements in front of in[0]; h_lut2112 NULL = symbols as stored.
+int tzk_undelta(tz_ctx* ctx, int stride, const int16_t* in, size_t n, const int16_t* carry, const int16_t* h_lut2112, int post_offset,
+                int16_t* out) {
+    if (stride != 3) return scan_launch(ctx, in, n, carry != nullptr, carry ? carry[0] : (int16_t)0, h_lut2112, post_offset, out);
     if (n == 0) return TZ_OK;
     if (((uintptr_t)in | (uintptr_t)out) & 1) return tz_fail(ctx, TZ_ERR_INVALID, "strided inverse scan: buffers must be 2-byte aligned");
-    const size_t tiles = (n + SCAN_WT - 1) / SCAN_WT;                 // wave-tiles
-    const int G = (int)std::min<size_t>(SCAN_G, (tiles + 3) / 4);
-    const size_t tpb = (tiles + (size_t)G * 4 - 1) / ((size_t)G * 4);   // per wave
-    if (tpb > 0x7FFFFFFFull) return tz_fail(ctx, TZ_ERR_INVALID, "strided inverse scan: too many elements");
-    void* d_lut = nullptr;
-    if (h_lut2112) {
-        TZ_TRY(tz_pool_alloc(ctx, (TZ_NBINS + 1) * 2, &d_lut));
-        TZ_TRY(tz_upload(ctx, d_lut, h_lut2112, (TZ_NBINS + 1) * 2));
-    }
-    if (!ctx->d_scan3_status) TZ_HIP(ctx, hipMalloc((void**)&ctx->d_scan3_status, sizeof(unsigned long long) * SCAN_G));
-    TZ_TRY(tz_fault_word(ctx));
-    tz_prof_scope ps(ctx, TZP_SCAN);
-    if (ctx->scan3_epoch == 0 || ctx->scan3_epoch == 0xFFFFu) {   // first launch, or the epochs have gone round
-        TZ_HIP(ctx, hipMemsetAsync(ctx->d_scan3_status, 0, sizeof(unsigned long long) * SCAN_G, ctx->stream));
-        ctx->scan3_epoch = 0;
-    }
-    const unsigned epoch = ++ctx->scan3_epoch;
-    const int vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-    const short c0 = carry3 ? carry3[0] : 0, c1 = carry3 ? carry3[1] : 0, c2 = carry3 ? carry3[2] : 0;
-#define TZ_SCAN3_LAUNCH(L)                                                                                                   \
-    hipLaunchKernelGGL((k_scan3p<L>), dim3(G), dim3(256), 0, ctx->stream, in, n, (int)tpb, carry3 != nullptr, c0, c1, c2, vec, \
-                       (const int16_t*)d_lut, post_offset, ctx->d_scan3_status, epoch, (epoch + ctx->scan_dbg_skew) & 0xFFFFu,  \
-                       ctx->scan_dbg_limit ? ctx->scan_dbg_limit : SCAN_POLL_LIMIT, ctx->d_fault, out)
-    if (h_lut2112) TZ_SCAN3_LAUNCH(true);
-    else TZ_SCAN3_LAUNCH(false);
+    const short c0 = carry ? carry[0] : 0, c1 = carry ? carry[1] : 0, c2 = carry ? carry[2] : 0;
+    return scan_run(ctx, "strided inverse scan", in, n, out, h_lut2112, &ctx->d_scan3_status, &ctx->scan3_epoch,
+                    [&](int G, int tpb, const int16_t* d_lut, int vec, unsigned epoch, unsigned poll_epoch, unsigned limit) {
+#define TZ_SCAN3_LAUNCH(L)                                                                                                       \
+    hipLaunchKernelGGL((k_scan3p<L>), dim3(G), dim3(256), 0, ctx->stream, in, n, tpb, carry != nullptr, c0, c1, c2, vec, d_lut,   \
+                       post_offset, ctx->d_scan3_status, epoch, poll_epoch, limit, ctx->d_fault, out)
+                        if (h_lut2112) TZ_SCAN3_LAUNCH(true);
+                        else TZ_SCAN3_LAUNCH(false);
 #undef TZ_SCAN3_LAUNCH
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
-}
-
-// The decoder's tail over a channel-stride payload: inverse remap and strided inverse scan into a temporary, then k_recon*
-// (the shape of the gray tail).  carry3: NULL at the stream start, else the three decoded elements in front of the range.
-int tzk_decode_tail_s3(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut2112, int post_offset, const int16_t* carry3,
-                       const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
-                       uint8_t* out) {
-    const size_t n = (size_t)nframes * H * W * 3;
-    if (n == 0) return TZ_OK;
-    void* d_diff;
-    TZ_TRY(tz_pool_alloc(ctx, n * 2, &d_diff));
-    TZ_TRY(tzk_undelta_s3(ctx, in, n, carry3, h_lut2112, post_offset, (int16_t*)d_diff));
-    return tzk_reconstruct(ctx, pred, key, d_key_mask, (const int16_t*)d_diff, nframes, H, W, Hp, Wp, out);
+                    });
 }
 
 // The three class sums of a prefix: k_undelta_carry with one sum per class of the element index mod 3.  A thread takes 24
@@ -2653,24 +2580,26 @@ __global__ __launch_bounds__(256) void k_undelta_carry_s3(const int16_t* __restr
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-int tzk_undelta_carry_s3(tz_ctx* ctx, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_words) {
-    if (n0 == 0 || n0 % 3) return tz_fail(ctx, TZ_ERR_INVALID, "strided undelta carry: n0 = %zu is not a positive multiple of 3", n0);
-    if (((uintptr_t)in & 1) != 0) return tz_fail(ctx, TZ_ERR_INVALID, "strided undelta carry: payload not 2-byte aligned");
-    void* d_lut = nullptr;
-    if (h_lut2112) {
-        TZ_TRY(tz_pool_alloc(ctx, (TZ_NBINS + 1) * 2, &d_lut));
-        TZ_TRY(tz_upload(ctx, d_lut, h_lut2112, (TZ_NBINS + 1) * 2));
-    }
+// enqueue the carry of payload[0, n0) into d_words[0 .. stride) (device; the low 16 bits of each word): the decoded elements in
+// front of in[n0].  h_lut2112 NULL = symbols as stored.  Stride 3: n0 a positive multiple of 3.
+int tzk_undelta_carry(tz_ctx* ctx, int stride, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_words) {
+    const bool s3 = stride == 3;
+    if (s3 && (n0 == 0 || n0 % 3)) return tz_fail(ctx, TZ_ERR_INVALID, "strided undelta carry: n0 = %zu is not a positive multiple of 3", n0);
+    if (n0 == 0) return tz_fail(ctx, TZ_ERR_INVALID, "undelta carry: the stream start has no carry");
+    if (((uintptr_t)in & 1) != 0) return tz_fail(ctx, TZ_ERR_INVALID, "%sundelta carry: payload not 2-byte aligned", s3 ? "strided " : "");
+    void* d_lut;
+    TZ_TRY(upload_dec_lut(ctx, h_lut2112, &d_lut));
     const unsigned head = (unsigned)std::min<size_t>(n0, ((16 - ((uintptr_t)in & 15)) & 15) / 2);
-    TZ_HIP(ctx, hipMemsetAsync(d_words, 0, 3 * sizeof(unsigned), ctx->stream));
-    const int G = grid_for((n0 - head) / 24 + 1, 256);
+    TZ_HIP(ctx, hipMemsetAsync(d_words, 0, (s3 ? 3 : 1) * sizeof(unsigned), ctx->stream));
+    const int G = grid_for((n0 - head) / (s3 ? 24 : 8 * CARRY_UNROLL) + 1, 256);
     tz_prof_scope ps(ctx, TZP_CARRY);
-    if (h_lut2112)
-        hipLaunchKernelGGL(k_undelta_carry_s3<true>, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)d_lut,
-                           post_offset, d_words);
-    else
-        hipLaunchKernelGGL(k_undelta_carry_s3<false>, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)nullptr,
-                           post_offset, d_words);
+#define TZ_CARRY_LAUNCH(K) \
+    hipLaunchKernelGGL(K, dim3(G), dim3(256), 0, ctx->stream, in, n0, head, (const int16_t*)d_lut, post_offset, d_words)
+    if (!s3 && h_lut2112) TZ_CARRY_LAUNCH(k_undelta_carry<true>);
+    else if (!s3) TZ_CARRY_LAUNCH(k_undelta_carry<false>);
+    else if (h_lut2112) TZ_CARRY_LAUNCH(k_undelta_carry_s3<true>);
+    else TZ_CARRY_LAUNCH(k_undelta_carry_s3<false>);
+#undef TZ_CARRY_LAUNCH
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
@@ -2741,24 +2670,6 @@ __global__ __launch_bounds__(256) void k_recon_flat(const float4* __restrict__ p
         }
         out[i] = make_uint2(lo, hi);
     }
-}
-
-int tzk_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
-                    int nframes, int H, int W, int Hp, int Wp, uint8_t* out) {
-    size_t n = (size_t)nframes * H * W * 3;
-    if (n == 0) return TZ_OK;
-    tz_prof_scope ps(ctx, TZP_RECON);
-    const size_t fe = (size_t)H * W * 3;
-    if (H == Hp && W == Wp && fe % 8 == 0 && key && ((((uintptr_t)diff | (uintptr_t)pred) & 15) == 0) &&
-        ((((uintptr_t)key | (uintptr_t)out) & 7) == 0)) {
-        hipLaunchKernelGGL(k_recon_flat, dim3(grid_for(n / 8, 256)), dim3(256), 0, ctx->stream, (const float4*)pred,
-                           (const uint2*)key, d_key_mask, (const short8*)diff, n / 8, (unsigned)(fe / 8), (uint2*)out);
-    } else {
-        hipLaunchKernelGGL(k_recon, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, ctx->stream, pred, key, d_key_mask, diff,
-                           n, H, W, Hp, Wp, out);
-    }
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
 }
 
 // ---------------------------------------------------------- reconstruct from a one-channel payload (gray job)
@@ -2839,35 +2750,48 @@ __global__ __launch_bounds__(256) void k_recon_gray_flat(const float4* __restric
     }
 }
 
-int tzk_reconstruct_gray(tz_ctx* ctx, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
-                         int nframes, int H, int W, int Hp, int Wp, uint8_t* out) {
-    const size_t fpix = (size_t)H * W, n1 = (size_t)nframes * fpix;
-    if (n1 == 0) return TZ_OK;
+// k_recon* over a diff stack of three elements per pixel, k_recon_gray* over one (channels = 1): the flat form where the frames
+// are unpadded and a frame holds whole groups of 8 elements, on aligned buffers; else the general form.
+int tzk_reconstruct(tz_ctx* ctx, int channels, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
+                    int nframes, int H, int W, int Hp, int Wp, uint8_t* out) {
+    const size_t fe = (size_t)H * W * channels, n = (size_t)nframes * fe;   // diff elements
+    if (n == 0) return TZ_OK;
+    const bool gray = channels == 1;
     tz_prof_scope ps(ctx, TZP_RECON);
-    if (H == Hp && W == Wp && fpix % 8 == 0 && key && ((((uintptr_t)diff | (uintptr_t)pred) & 15) == 0) &&
+    if (H == Hp && W == Wp && fe % 8 == 0 && key && ((((uintptr_t)diff | (uintptr_t)pred) & 15) == 0) &&
         ((((uintptr_t)key | (uintptr_t)out) & 7) == 0)) {
-        hipLaunchKernelGGL(k_recon_gray_flat, dim3(grid_for(n1 / 8, 256)), dim3(256), 0, ctx->stream, (const float4*)pred,
-                           (const uint2*)key, d_key_mask, (const short8*)diff, n1 / 8, (unsigned)(fpix / 8), (uint2*)out);
+        hipLaunchKernelGGL(gray ? k_recon_gray_flat : k_recon_flat, dim3(grid_for(n / 8, 256)), dim3(256), 0, ctx->stream,
+                           (const float4*)pred, (const uint2*)key, d_key_mask, (const short8*)diff, n / 8, (unsigned)(fe / 8), (uint2*)out);
+    } else if (gray) {
+        hipLaunchKernelGGL(k_recon_gray, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, ctx->stream, pred, key, d_key_mask, diff, n, H, W,
+                           Hp, Wp, (int)(((uintptr_t)out & 3) == 0), out);
     } else {
-        hipLaunchKernelGGL(k_recon_gray, dim3(grid_for(n1 / 4 + 1, 256)), dim3(256), 0, ctx->stream, pred, key, d_key_mask, diff,
-                           n1, H, W, Hp, Wp, (int)(((uintptr_t)out & 3) == 0), out);
+        hipLaunchKernelGGL(k_recon, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, ctx->stream, pred, key, d_key_mask, diff, n, H, W, Hp,
+                           Wp, out);
     }
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
 
-// The decoder's tail over a one-channel payload: the inverse remap and the inverse spatial delta of the nframes * H * W
-// elements (scan_launch, the launch tzk_decode_tail's unfused path makes) into a temporary, then k_recon_gray*.  The fused
-// walk of k_scan2p is left to the three-channel payload.
-int tzk_decode_tail_gray(tz_ctx* ctx, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry, int16_t carry,
-                         const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp,
-                         int Wp, uint8_t* out) {
-    const size_t n1 = (size_t)nframes * H * W;
-    if (n1 == 0) return TZ_OK;
+// the decoder's tail over frames [first, first + nframes) of a stream (tz_decode, tz_decode_range, tz_encode_quality): `in`,
+// pred, key and d_key_mask point at the range's first frame and `carry` holds the layout.stride decoded elements in front of it (NULL
+// at the stream start).  One launch (inverse remap when there is a table, inverse spatial delta, reconstruct) where the
+// layout allows it: unpadded frames of a multiple of 16 elements, 16-byte aligned buffers, and no TEZIP_DECODE_UNFUSED.
+// Else, and for the gray and the channel-stride layout always, a scan into a temporary and k_recon* / k_recon_gray*.
+int tzk_decode_tail(tz_ctx* ctx, tz_layout layout, const int16_t* in, const int16_t* h_lut2112, int post_offset, const int16_t* carry,
+                    const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
+                    uint8_t* out) {
+    const size_t fe = tz_frame_elems(layout, H, W), n = (size_t)nframes * fe;
+    if (n == 0) return TZ_OK;
+    if (layout.channels == 3 && layout.stride == 1 && H == Hp && W == Wp && fe % SCAN_EPT == 0 && key && !ctx->decode_unfused &&
+        ((((uintptr_t)in | (uintptr_t)pred | (uintptr_t)key | (uintptr_t)out) & 15) == 0)) {
+        const ScanRecon rc = {(const float4*)pred, key, d_key_mask, (unsigned long long)fe, out};
+        return scan_launch(ctx, in, n, carry != nullptr, carry ? carry[0] : (int16_t)0, h_lut2112, post_offset, nullptr, &rc);
+    }
     void* d_diff;
-    TZ_TRY(tz_pool_alloc(ctx, n1 * 2, &d_diff));
-    TZ_TRY(scan_launch(ctx, in, n1, has_carry, carry, h_lut2112, post_offset, (int16_t*)d_diff));
-    return tzk_reconstruct_gray(ctx, pred, key, d_key_mask, (const int16_t*)d_diff, nframes, H, W, Hp, Wp, out);
+    TZ_TRY(tz_pool_alloc(ctx, n * 2, &d_diff));
+    TZ_TRY(tzk_undelta(ctx, layout.stride, in, n, carry, h_lut2112, post_offset, (int16_t*)d_diff));
+    return tzk_reconstruct(ctx, layout.channels, pred, key, d_key_mask, (const int16_t*)d_diff, nframes, H, W, Hp, Wp, out);
 }
 
 // ------------------------------------------------------------------------ reconstruction statistics

@@ -306,43 +306,34 @@ bool tz_quant_is_identity(int mode, double b0, double b1);   // error_bound leav
 int tzk_quant_sd_fused(tz_ctx*, const float* pred, const uint8_t* orig, const uint8_t* d_zero_mask, const uint8_t* h_skip,
                        int nframes, int H, int W, int Hp, int Wp, int mode, double b0, double b1, int apply_offset,
                        int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done);
-int tzk_spatial_delta(tz_ctx*, const int16_t* in, size_t n, int has_carry, int16_t carry, int apply_offset,
-                      int16_t* out, unsigned long long* d_hist);
+// The layout of the payload, stated once per layer: elements per pixel, and how far in front the element
+// lies that the spatial delta subtracts.  flat {3, 1} is the reference's; gray {1, 1} stores channel 0 alone
+// (tz_set_payload_channels(1)); channel stride {3, 3} takes the same channel of the pixel in front (tz_set_delta_stride(1)).
+// A carry is `stride` HOST elements, the ones in front of the first element, or NULL at the stream start.
+struct tz_layout {
+    int channels, stride;
+};
+static inline size_t tz_frame_elems(tz_layout l, int H, int W) { return (size_t)H * W * l.channels; }   // payload elements of a frame
+// in -> n elements at out.  flat, channel stride: in holds n elements; gray: the interleaved three-channel stack of n pixels, of
+// which channel 0 is taken, and d_edge (may be NULL) receives its first and last element.  Then 1600 - y when apply_offset,
+// and the counts ADDED to d_hist (may be NULL).  Flat wants 16-byte aligned buffers, the other two 2-byte aligned ones.
+int tzk_spatial_delta(tz_ctx*, tz_layout, const int16_t* in, size_t n, const int16_t* carry, int apply_offset, int16_t* out,
+                      unsigned long long* d_hist, int16_t* d_edge);
 int tzk_lut(tz_ctx*, const int16_t* in, size_t n, const int16_t* h_lut2112, int post_offset, int16_t* out);
 // forward: int16[n] -> low-byte plane | high-byte plane (2n bytes); inverse: planes (passed as `in`) -> int16[n] at `out`
 int tzk_shuffle(tz_ctx*, const int16_t* in, size_t n, uint8_t* out, int inverse);
-int tzk_undelta(tz_ctx*, const int16_t* in, size_t n, int has_carry, int16_t carry, int16_t* out);
-int tzk_decode_tail(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry, int16_t carry,
+// the inverse: x[i] = x[i - stride] - s[i], through the decoder LUT when there is one (k_scan2p; stride 3: k_scan3p)
+int tzk_undelta(tz_ctx*, int stride, const int16_t* in, size_t n, const int16_t* carry, const int16_t* h_lut2112, int post_offset,
+                int16_t* out);
+// the `stride` decoded elements in front of in[n0] into d_words[0 .. stride) (low 16 bits); stride 3: n0 a multiple of 3
+int tzk_undelta_carry(tz_ctx*, int stride, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_words);
+// diff holds `channels` deltas per pixel; with one, the sample goes to all three channels of out
+int tzk_reconstruct(tz_ctx*, int channels, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
+                    int nframes, int H, int W, int Hp, int Wp, uint8_t* out);
+// inverse remap, inverse spatial delta and reconstruct of nframes frames of the payload `in`
+int tzk_decode_tail(tz_ctx*, tz_layout, const int16_t* in, const int16_t* h_lut2112, int post_offset, const int16_t* carry,
                     const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
                     uint8_t* out);
-int tzk_undelta_carry(tz_ctx*, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_word);
-int tzk_reconstruct(tz_ctx*, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
-                    int nframes, int H, int W, int Hp, int Wp, uint8_t* out);
-// one-channel payload of a gray job (tz_set_payload_channels(1)).  tzk_spatial_delta_gray: tzk_spatial_delta over channel 0 of
-// the interleaved stack in3 (npix * 3 elements) -> npix elements; d_edge (may be NULL) receives the first and the last
-// channel-0 element.  tzk_reconstruct_gray: diff holds ONE delta per pixel, the sample goes to all three channels of out.
-// tzk_decode_tail_gray: tzk_decode_tail for such a payload, `in` holding nframes * H * W elements (scan, then reconstruct).
-int tzk_spatial_delta_gray(tz_ctx*, const int16_t* in3, size_t npix, int has_carry, int16_t carry, int apply_offset,
-                           int16_t* out, unsigned long long* d_hist, int16_t* d_edge);
-int tzk_reconstruct_gray(tz_ctx*, const float* pred, const uint8_t* key, const uint8_t* d_key_mask, const int16_t* diff,
-                         int nframes, int H, int W, int Hp, int Wp, uint8_t* out);
-int tzk_decode_tail_gray(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, int has_carry, int16_t carry,
-                         const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp,
-                         int Wp, uint8_t* out);
-// spatial delta at the channel stride 3 (tz_set_delta_stride(1); DESIGN.md section 9, tezip_amd/sdelta.py).  carry3: NULL or the
-// three HOST elements in front of in[0] (classes 0, 1, 2 of the element index mod 3).  tzk_spatial_delta_s3: out[i] = in[i-3] -
-// in[i], then 1600 - y and the histogram as tzk_spatial_delta; any 2-byte aligned buffers.  tzk_undelta_s3: the inverse, three
-// interleaved wrap-around scans in one launch (k_scan3p), through the decoder LUT when there is one.  tzk_undelta_carry_s3:
-// the three decoded elements in front of in[n0] into d_words[0..2] (low 16 bits), n0 a positive multiple of 3.
-// tzk_decode_tail_s3: tzk_decode_tail over such a payload (scan into a temporary, then tzk_reconstruct).
-int tzk_spatial_delta_s3(tz_ctx*, const int16_t* in, size_t n, const int16_t* carry3, int apply_offset, int16_t* out,
-                         unsigned long long* d_hist);
-int tzk_undelta_s3(tz_ctx*, const int16_t* in, size_t n, const int16_t* carry3, const int16_t* h_lut2112, int post_offset,
-                   int16_t* out);
-int tzk_undelta_carry_s3(tz_ctx*, const int16_t* in, size_t n0, const int16_t* h_lut2112, int post_offset, unsigned* d_words);
-int tzk_decode_tail_s3(tz_ctx*, const int16_t* in, const int16_t* h_lut2112, int post_offset, const int16_t* carry3,
-                       const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
-                       uint8_t* out);
 // per-frame (sse, max |dec - orig|, #changed) of two unpadded nframes x fe uint8 stacks; d_out (device) is cleared here
 int tzk_quality(tz_ctx*, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out);
 // TZD64 digests of nframes frames of fe bytes (fe < 2^32, else TZ_ERR_INVALID before any launch); d_out: nframes words, cleared here
