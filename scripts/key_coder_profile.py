@@ -121,7 +121,7 @@ def main():
     print(json.dumps(doc["wall_abs2"]), flush=True)
     doc["notes"] = ("One process, one device.  Device times are HIP-event sums of the 'huffman' profiling class, 7 runs, median: encode = "
                     "k_key_hist + k_key_resid + the Huffman size / scan / pack kernels, decode = the Huffman expand kernel + "
-                    "k_key_unresid_row / _col (the memset of the other frames is not in the class).  Wall times: compress.run / "
+                    "k_key_unresid_row / k_key_unresid_col (the memset of the other frames is not in the class).  Wall times: compress.run / "
                     "decompress.run on PNG files, abs 2, the two settings alternating, first round dropped, median of 3.")
     with open(sys.argv[1], "w") as f:
         json.dump(doc, f, indent=1)

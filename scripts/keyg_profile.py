@@ -6,7 +6,7 @@ gray key frame coded once), from the same frames, random weights (seed 3), abs 2
 `zstd` and `huffg` are measured in this tree; `huff` in a build of the PARENT commit (a checkout with its library built,
 given as parent_tree), in a child process of its own, so that the comparison is with the coder as it was, not with a switch
 inside the new build.  Device times are HIP-event sums of the 'huffman' profiling class (tz_prof_get) over the key-coder
-stage -- for huffg k_key_gray + k_key_hist + k_keyg_resid + the Huffman size / scan / pack kernels -- 7 runs, median.
+stage -- for huffg k_key_gray + k_key_hist + k_key_resid + the Huffman size / scan / pack kernels -- 7 runs, median.
 File sizes are those of compress.run's directory.
 The expectation this records (no threshold anywhere): huffg's device time on a gray job does not exceed huff's on the same
 job, since it codes a third of the symbols after one extra read.
@@ -121,7 +121,7 @@ def main():
         doc["results"][job] = r
     doc["notes"] = ("One device, one process per tree: zstd and huffg from this tree, huff from a build of the parent commit.  "
                     "encode_device_ms: HIP-event sum of the 'huffman' profiling class over the key-coder stage (huff: k_key_hist + "
-                    "k_key_resid + Huffman size / scan / pack; huffg: k_key_gray + k_key_hist + k_keyg_resid + the same Huffman kernels "
+                    "k_key_resid + Huffman size / scan / pack; huffg: k_key_gray + k_key_hist + k_key_resid + the same Huffman kernels "
                     "over a third of the symbols), 7 runs, median.  bytes: the files compress.run wrote.  Expectation recorded, not "
                     "tested: huffg_device_ms_over_huff <= 1 on a gray job.")
     with open(out_path, "w") as f:

@@ -32,11 +32,12 @@ def _stack(nt=NT, h=H, w=W, seed=1):
     return (base + rng.integers(0, 2, (nt, h, w, 3)) * 200).astype(np.uint8)
 
 
-@pytest.mark.parametrize("h,w", [(1, 1), (3, 5), (21, 30), (61, 90), (64, 64)])
+@pytest.mark.parametrize("h,w", [(1, 1), (3, 5), (21, 30), (61, 90), (64, 64), (3, 300)])
 @pytest.mark.parametrize("k", [1, 3])
 def test_buffer_forms_are_the_numpy_functions(ctx, h, w, k):
     """61 x 90 x 3 = 16 470 symbols cross a chunk boundary; W * 3 is odd or no multiple of 16 in most shapes, and with
-    k = 3 the second and third frame start off a 16-byte boundary."""
+    k = 3 the second and third frame start off a 16-byte boundary.  3 x 300: a row of five 64-column steps of the row
+    kernel, more than one workgroup of columns in the column kernel."""
     from tezip_amd import keycoder
     frames = _stack(k, h, w, seed=h * 7 + w)
     for preds in [[p] * k for p in range(4)] + ([[3, 0, 2], [1, 2, 3]] if k == 3 else []):

@@ -1,7 +1,9 @@
 """The key-frame coder that stores a gray key frame once (`--key-coder huffg`, format TZK2) on the GPU: k_key_gray gives the
-numpy flag exactly, k_keyg_resid / k_keyg_unresid_* the numpy residuals and their inverses bit for bit, compress.run the
+numpy flag exactly, k_key_resid / k_key_unresid_* the numpy residuals and their inverses bit for bit, compress.run the
 bytes of keycoderg.encode_file, and `-c --key-coder huffg --digests` then `-u --verify require` the images of a
-`--key-coder zstd` job (tezip_amd/keycoderg.py is the specification).  No test feeds a kernel a corrupted body: the
+`--key-coder zstd` job (tezip_amd/keycoderg.py is the specification).  TZK1 = TZK2 with no GRAY bit: pred bytes 0..3 through
+the TZK2 entry points give what the TZK1 entry points give, and both coders' scope counts, digests and refusal texts are those
+of the commit before they shared one residual path (tests/golden/key_coder_parent.json).  No test feeds a kernel a corrupted body: the
 container's validation and the decoder's low-byte rule are tested on the CPU (tests/test_keycoderg.py)."""
 import contextlib
 import io
@@ -75,7 +77,7 @@ def test_gray_flag_at_every_sample_of_a_small_frame(ctx):
     assert ctx.keys_gray([1, 2]).tolist() == [True, False]
 
 
-# --------------------------------------------------------------------------------------- k_keyg_resid / k_keyg_unresid_*
+# ------------------------------------------------------------------- k_key_resid / k_key_unresid_* under pred bytes 0..7
 @pytest.mark.parametrize("h,w", [(5, 7), (64, 64), (1, 1), (61, 90), (3, 300)])
 def test_unresidual_buf_is_the_numpy_function(ctx, h, w):
     """Each of the 8 pred bytes alone, and stacks that mix them so that the frames' offsets differ.  3 x 300 has more than
@@ -141,12 +143,17 @@ def _file_from_context(ctx, stack, keys):
     return keycoderg.pack_front(nt, h, w, keys, predg, lengths, huff.geometry(n)[1], (nbytes - huff.body_bytes(n, 0)) // 4) + body.tobytes()
 
 
-def test_resident_forms_match_numpy_and_refuse_the_other_format(ctx):
-    from tezip_amd import _lib, keycoder, keycoderg
+def mixed_stack():
+    """7 x 21 x 30: gray frames, a colour frame (4) and a frame one bit off gray (6); the key frames are 0, 1, 4 and 6."""
     stack = gray_stack(7, 21, 30, 3)
     stack[4] = colour_stack(1, 21, 30, 4)[0]
     stack[6, 20, 29, 2] ^= 1
-    keys = [0, 1, 4, 6]
+    return stack, [0, 1, 4, 6]
+
+
+def test_resident_forms_match_numpy_and_refuse_the_other_format(ctx):
+    from tezip_amd import _lib, keycoder, keycoderg
+    stack, keys = mixed_stack()
     _resident(ctx, stack)
     data = _file_from_context(ctx, stack, keys)
     assert data == keycoderg.encode_file(stack, keys, 7), "the GPU file differs from the numpy encoder's"
@@ -191,6 +198,163 @@ def test_resident_forms_match_numpy_and_refuse_the_other_format(ctx):
     _resident(ctx, stack)
     refused(-1, lambda: ctx.keysg_encode(keys, [0, 1, 9, 2], p.lengths))
     refused(-1, lambda: ctx.keys_gray([3, 3]))
+
+
+# ------------------------------------------------------------------------------------------ TZK1 = TZK2 with no GRAY bit
+@pytest.mark.parametrize("h,w", [(1, 1), (5, 7), (3, 300), (61, 90), (64, 64)])
+def test_without_a_gray_bit_it_is_the_tzk1_coder(ctx, h, w):
+    """Pred bytes 0..3 through the TZK2 entry points give what the TZK1 entry points give, and the two files of a stack without
+    a gray frame differ in the magic alone and decode to the same frames."""
+    from tezip_amd import keycoder, keycoderg
+    stack = colour_stack(3, h, w, h * 13 + w)
+    stack[:, 0, 0, 1] = stack[:, 0, 0, 0] ^ 0x55                         # (a random 1 x 1 frame could be gray)
+    rng = np.random.default_rng(h + w)
+    for preds in [[p] * 3 for p in range(4)] + [[3, 0, 2], [1, 2, 3]]:
+        sym = ctx.keys_residual_buf(stack, preds)
+        assert (ctx.keysg_residual_buf(stack, preds) == sym).all(), "residuals %r at %dx%d" % (preds, h, w)
+        noisy = (sym | (rng.integers(0, 2, sym.size) * 0x4100).astype(np.int16)).astype(np.int16)   # the high bytes must not count
+        back = ctx.keys_unresidual_buf(noisy, preds, h, w)
+        assert (back == stack).all() and (ctx.keysg_unresidual_buf(noisy, preds, h, w) == back).all(), "inverse %r at %dx%d" % (preds, h, w)
+    keys = [0, 2]
+    k1, k2 = keycoder.encode_file(stack, keys, 3), keycoderg.encode_file(stack, keys, 3)
+    assert k1[:4] == b"TZK1" and k2[:4] == b"TZK2" and k1[4:] == k2[4:]
+    p1, p2 = keycoder.parse(k1), keycoderg.parse(k2)
+    want = np.zeros_like(stack)
+    want[keys] = stack[keys]
+    b1, b2 = np.ascontiguousarray(p1.body), np.ascontiguousarray(p2.body)
+    ctx.keys_begin(b1.size, p1.nt, p1.H, p1.W, p1.idx, p1.pred, p1.lengths)
+    ctx.keys_put(0, b1)
+    ctx.keys_decode()
+    got1 = ctx.frames_get(0, 3)
+    ctx.keysg_begin(b2.size, p2.nt, p2.H, p2.W, p2.idx, p2.pred, p2.lengths)
+    ctx.keysg_put(0, b2)
+    ctx.keysg_decode()
+    got2 = ctx.frames_get(0, 3)
+    assert (got1 == want).all() and (got2 == got1).all()
+
+
+# ------------------------------------------------------------ scope counts, digests and refusal texts of the parent
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "key_coder_parent.json")
+
+
+class _OddAddress:
+    """A device array of n int16 symbols at an odd address, as _lib takes buffers (numel / is_contiguous / data_ptr)."""
+
+    def __init__(self, n):
+        import torch
+        self.hold = torch.zeros(2 * n + 16, dtype=torch.uint8, device="cuda")
+        self.n = n
+
+    def numel(self):
+        return self.n
+
+    def is_contiguous(self):
+        return True
+
+    def data_ptr(self):
+        return self.hold.data_ptr() + 1
+
+
+def record():
+    """The job of test_resident_forms_match_numpy_and_refuse_the_other_format through a context of its own -> {"calls": {call:
+    {"scopes": scope count of the 'huffman' profiling class, "digest": TZD64 of what the call left}}, "refusals": {case: text}}."""
+    from tezip_amd import _lib, digest, huff, keycoder, keycoderg
+    stack, keys = mixed_stack()
+    nt, h, w = stack.shape[:3]
+    calls, refusals = {}, {}
+    sym3 = np.zeros(4 * h * w * 3, np.int16)
+    odd = _OddAddress(sym3.size)
+    c = _lib.Context(0)
+
+    def counted(name, call, left):
+        c.prof_reset()
+        call()
+        scopes = int(c.prof_get()["huffman"][1])
+        calls[name] = {"scopes": scopes, "digest": "%016x" % digest.frame_digest(np.ascontiguousarray(left()).reshape(-1).view(np.uint8))}
+
+    def refused(name, call):
+        with pytest.raises(_lib.TezipError) as e:
+            call()
+        refusals[name] = str(e.value)
+
+    try:
+        c.prof_enable(True)
+        _resident(c, stack)
+        state = {}
+        counted("keys_counts", lambda: state.update(counts=c.keys_counts(keys)), lambda: state["counts"])
+        counted("keys_gray", lambda: state.update(gray=c.keys_gray(keys)), lambda: state["gray"].astype(np.uint8))
+        pred = keycoder.choose_predictors(state["counts"])
+        len1 = huff.code_lengths(keycoder.chosen_counts(state["counts"], pred))
+        counted("keys_encode", lambda: state.update(n1=c.keys_encode(keys, pred, len1)), lambda: c.keys_get(0, state["n1"]))
+        body1 = c.keys_get(0, state["n1"])
+        gcounts = keycoderg.gray_counts(state["counts"], state["gray"])
+        predg = keycoderg.pred_bytes(gcounts, state["gray"])
+        len2 = huff.code_lengths(keycoderg.chosen_counts(gcounts, predg))
+        counted("keysg_encode", lambda: state.update(n2=c.keysg_encode(keys, predg, len2)), lambda: c.keysg_get(0, state["n2"]))
+        body2 = c.keysg_get(0, state["n2"])
+        # ---- refusals of the encoder's entry points (the stack is resident)
+        bad4, bad8 = [0, 1, 4, 2], [0, 1, 8, 2]
+        refused("keys_encode pred 4", lambda: c.keys_encode(keys, bad4, len1))
+        refused("keysg_encode pred 8", lambda: c.keysg_encode(keys, bad8, len2))
+        refused("keys_residual_buf pred 4", lambda: c.keys_residual_buf(stack[keys], bad4))
+        refused("keysg_residual_buf pred 8", lambda: c.keysg_residual_buf(stack[keys], bad8))
+        refused("keys_unresidual_buf pred 4", lambda: c.keys_unresidual_buf(sym3, bad4, h, w))
+        refused("keysg_unresidual_buf pred 8", lambda: c.keysg_unresidual_buf(sym3, bad8, h, w))
+        refused("keys_begin pred 4", lambda: c.keys_begin(body1.size, nt, h, w, keys, bad4, len1))
+        refused("keysg_begin pred 8", lambda: c.keysg_begin(body2.size, nt, h, w, keys, bad8, len2))
+        for name, idx in (("indices not ascending", [0, 4, 1, 6]), ("nkeys 0", [])):
+            ok = [0] * len(idx)
+            refused("keys_counts " + name, lambda: c.keys_counts(idx))
+            refused("keys_gray " + name, lambda: c.keys_gray(idx))
+            refused("keys_encode " + name, lambda: c.keys_encode(idx, ok, len1))
+            refused("keysg_encode " + name, lambda: c.keysg_encode(idx, ok, len2))
+            refused("keys_begin " + name, lambda: c.keys_begin(body1.size, nt, h, w, idx, ok, len1))
+            refused("keysg_begin " + name, lambda: c.keysg_begin(body2.size, nt, h, w, idx, ok, len2))
+        refused("keys_residual_buf misaligned symbols", lambda: c.keys_residual_buf(stack[keys], [0, 1, 2, 3], out=odd))
+        refused("keysg_residual_buf misaligned symbols", lambda: c.keysg_residual_buf(stack[keys], [0, 1, 2, 3], out=odd))
+        refused("keys_unresidual_buf misaligned symbols", lambda: c.keys_unresidual_buf(odd, [0, 1, 2, 3], h, w))
+        refused("keysg_unresidual_buf misaligned symbols", lambda: c.keysg_unresidual_buf(odd, [0, 1, 2, 3], h, w))
+        # ---- the decoders, and the refusals of a staged stream
+        for kind, body, pr, ln in (("keys", body1, pred, len1), ("keysg", body2, predg, len2)):
+            begin, put, decode = (getattr(c, "%s_%s" % (kind, f)) for f in ("begin", "put", "decode"))
+            begin(body.size, nt, h, w, keys, pr, ln)
+            put(0, body[:100])
+            refused(kind + "_put outside the stream", lambda: put(body.size - 10, body[:100]))
+            refused(kind + "_decode after an incomplete put", decode)
+            put(100, body[100:])
+            counted(kind + "_decode", decode, lambda: c.frames_get(0, nt))
+    finally:
+        c.close()
+    return {"calls": calls, "refusals": refusals}
+
+
+def test_scopes_digests_and_refusal_texts_are_the_parents():
+    """tests/golden/key_coder_parent.json holds record() as the commit before the two coders were put behind one residual
+    path gave it (tests/golden/make_key_coder_parent.py)."""
+    import json
+    with open(FIXTURE) as f:
+        want = json.load(f)
+    got = record()
+    for part in ("calls", "refusals"):
+        assert sorted(got[part]) == sorted(want[part])
+        for name in sorted(want[part]):
+            assert got[part][name] == want[part][name], "%s: %s" % (part, name)
+
+
+def test_a_bad_index_is_named_before_a_bad_pred_byte(ctx):
+    """Both formats check the whole key list, then the pred bytes: a call that is wrong in both names
+    the index, whichever entry comes first."""
+    from tezip_amd import _lib
+    stack, _ = mixed_stack()
+    _resident(ctx, stack)
+    lengths = np.full(256, 8, np.uint8)
+    want = "tezip_hip status -1: key frames: index 1 (entry 2) is not ascending inside [0, 7)"
+    for encode, begin, bad in ((ctx.keys_encode, ctx.keys_begin, 4), (ctx.keysg_encode, ctx.keysg_begin, 8)):
+        for call in (lambda: encode([0, 4, 1, 6], [bad, 0, 0, 0], lengths),
+                     lambda: begin(4096, 7, 21, 30, [0, 4, 1, 6], [bad, 0, 0, 0], lengths)):
+            with pytest.raises(_lib.TezipError) as e:
+                call()
+            assert str(e.value) == want
 
 
 # ------------------------------------------------------------------------------------------- compress.run / decompress.run

@@ -902,27 +902,42 @@ class Context:
         """-> the context's frame stack, as frames_begin + frames_put of the zero-except-keys stack leave it."""
         self._keys_decode(self.lib.tz_keys_decode)
 
-    def keys_residual_buf(self, frames, pred, out=None):
-        """Stand-alone: uint8 (k, H, W, 3) frames (host or device) -> their k * H * W * 3 int16 residual symbols."""
+    @staticmethod
+    def _keys_symbols(pred, h, w, gray):
+        """The pred array as uint8 and the symbols its frames have: h * w for a GRAY frame where `gray` says the bit counts."""
+        pr = np.ascontiguousarray(pred, np.uint8)
+        return pr, int(np.where(pr & 4, h * w, h * w * 3).sum()) if gray else int(pr.size) * h * w * 3
+
+    def _keys_residual_buf(self, fn, frames, pred, out, what, gray):
         self._check_stack(frames, "frames")
         k, h, w = (int(v) for v in frames.shape[:3])
-        pr = np.ascontiguousarray(pred, np.uint8)
+        pr, n = self._keys_symbols(pred, h, w, gray)
         if pr.size != k:
-            raise ValueError("%d predictor ids for %d frames" % (pr.size, k))
+            raise ValueError("%d %s for %d frames" % (pr.size, what, k))
         if out is None:
-            out = np.empty(k * h * w * 3, np.int16)
-        self._ck(self.lib.tz_keys_residual_buf(self.h, _ptr(frames), k, h, w, pr.ctypes.data, _ptr(out)))
+            out = np.empty(n, np.int16)
+        elif gray and _numel(out) != n:     # (the TZK1 wrapper never checked the room of `out`, and stays as it was)
+            raise ValueError("%d symbols of room, %d wanted" % (_numel(out), n))
+        self._ck(fn(self.h, _ptr(frames), k, h, w, pr.ctypes.data, _ptr(out)))
         return out
 
-    def keys_unresidual_buf(self, sym, pred, h, w, out=None):
-        pr = np.ascontiguousarray(pred, np.uint8)
+    def _keys_unresidual_buf(self, fn, sym, pred, h, w, out, gray):
+        h, w = int(h), int(w)
+        pr, n = self._keys_symbols(pred, h, w, gray)
         k = int(pr.size)
-        if _numel(sym) != k * h * w * 3:
-            raise ValueError("%d symbols for %d frames of %d x %d x 3" % (_numel(sym), k, h, w))
+        if _numel(sym) != n:
+            raise ValueError("%d symbols for %d frames of %d x %d%s" % (_numel(sym), k, h, w, ", %d wanted" % n if gray else " x 3"))
         if out is None:
             out = np.empty((k, h, w, 3), np.uint8)
-        self._ck(self.lib.tz_keys_unresidual_buf(self.h, _ptr(sym), k, int(h), int(w), pr.ctypes.data, _ptr(out)))
+        self._ck(fn(self.h, _ptr(sym), k, h, w, pr.ctypes.data, _ptr(out)))
         return out
+
+    def keys_residual_buf(self, frames, pred, out=None):
+        """Stand-alone: uint8 (k, H, W, 3) frames (host or device) -> their k * H * W * 3 int16 residual symbols."""
+        return self._keys_residual_buf(self.lib.tz_keys_residual_buf, frames, pred, out, "predictor ids", False)
+
+    def keys_unresidual_buf(self, sym, pred, h, w, out=None):
+        return self._keys_unresidual_buf(self.lib.tz_keys_unresidual_buf, sym, pred, h, w, out, False)
 
     # ---- the same with gray key frames stored once (tz_keys_gray, tz_keysg_*; format: tezip_amd/keycoderg.py).  predg: pred
     # bytes, predictor id | 4 for a GRAY frame, which has h * w symbols instead of h * w * 3
@@ -950,34 +965,12 @@ class Context:
         """-> the context's frame stack, as frames_begin + frames_put of the zero-except-keys stack leave it."""
         self._keys_decode(self.lib.tz_keysg_decode)
 
-    @staticmethod
-    def _keysg_symbols(predg, h, w):
-        pr = np.ascontiguousarray(predg, np.uint8)
-        return pr, int(np.where(pr & 4, h * w, h * w * 3).sum())
-
     def keysg_residual_buf(self, frames, predg, out=None):
         """Stand-alone: uint8 (k, H, W, 3) frames (host or device) -> their int16 residual symbols, H * W for a GRAY frame."""
-        self._check_stack(frames, "frames")
-        k, h, w = (int(v) for v in frames.shape[:3])
-        pr, n = self._keysg_symbols(predg, h, w)
-        if pr.size != k:
-            raise ValueError("%d pred bytes for %d frames" % (pr.size, k))
-        if out is None:
-            out = np.empty(n, np.int16)
-        elif _numel(out) != n:
-            raise ValueError("%d symbols of room, %d wanted" % (_numel(out), n))
-        self._ck(self.lib.tz_keysg_residual_buf(self.h, _ptr(frames), k, h, w, pr.ctypes.data, _ptr(out)))
-        return out
+        return self._keys_residual_buf(self.lib.tz_keysg_residual_buf, frames, predg, out, "pred bytes", True)
 
     def keysg_unresidual_buf(self, sym, predg, h, w, out=None):
-        pr, n = self._keysg_symbols(predg, int(h), int(w))
-        k = int(pr.size)
-        if _numel(sym) != n:
-            raise ValueError("%d symbols for %d frames of %d x %d, %d wanted" % (_numel(sym), k, h, w, n))
-        if out is None:
-            out = np.empty((k, h, w, 3), np.uint8)
-        self._ck(self.lib.tz_keysg_unresidual_buf(self.h, _ptr(sym), k, int(h), int(w), pr.ctypes.data, _ptr(out)))
-        return out
+        return self._keys_unresidual_buf(self.lib.tz_keysg_unresidual_buf, sym, predg, h, w, out, True)
 
     # ---- opt-in Huffman coder with repeat tokens (tz_huffr_*; format: tezip_amd/huffr.py).  `lengths` holds the A literals
     # and then the 8 tokens.

@@ -1642,24 +1642,17 @@ static int flat_only(tz_ctx* ctx, const char* who, bool serves_gray = false) {
     return TZ_OK;
 }
 
-static int keys_upload(tz_ctx* ctx, const int* idx, const uint8_t* pred, int nkeys, const int** d_idx, const uint8_t** d_pred);
+static int keys_gray(tz_ctx* ctx, const int* idx, int nkeys, uint8_t* gray);   // (k_key_gray: with the key-frame coders below)
 
 // TZ_ERR_INVALID naming the first frame of the resident stack that has a pixel with unequal channels (k_key_gray over all frames)
 static int encode_all_gray(tz_ctx* ctx) {
     const int nt = ctx->nt;
     std::vector<int> idx(nt);
     for (int i = 0; i < nt; ++i) idx[i] = i;
-    std::vector<unsigned> flags(nt);
-    const int* d_idx = nullptr;
-    const uint8_t* d_pred = nullptr;
-    void* d_flags;
-    TZ_TRY(keys_upload(ctx, idx.data(), nullptr, nt, &d_idx, &d_pred));
-    TZ_TRY(tz_pool_alloc(ctx, sizeof(unsigned) * nt, &d_flags));
-    TZ_TRY(tzk_key_gray(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, nt, (unsigned*)d_flags));
-    TZ_TRY(tz_d2h(ctx, flags.data(), d_flags, sizeof(unsigned) * nt, ctx->stream));
-    TZ_TRY(tz_stream_sync(ctx));
+    std::vector<uint8_t> gray(nt);
+    TZ_TRY(keys_gray(ctx, idx.data(), nt, gray.data()));
     for (int i = 0; i < nt; ++i)
-        if (flags[i]) return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode: frame %d has colour, a one-channel payload would drop it", i);
+        if (!gray[i]) return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode: frame %d has colour, a one-channel payload would drop it", i);
     return TZ_OK;
 }
 
@@ -2890,35 +2883,70 @@ extern "C" int tz_huffd_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t by
     return huff_decode_buf(ctx, f, stream, bytes, n, lengths, A, base, R, out);
 }
 
-// --------------------------------------------------------------------------- key-frame coder (TZK1)
+// --------------------------------------------------------------------------- key-frame coders (TZK1, TZK2)
 // `--key-coder huff` (NOT a reference feature: compress.py:271-278 hands a zero-except-keys stack of the whole sequence to
 // zstd): the key frames alone, as predictor residuals under one TZH1 code (tezip_amd/keycoder.py, k_key_* in tz_codec.hip).
 // The coder has buffers of its own (d_keys, d_keysym): what tz_huff_* / tz_huffr_* hold or have staged is left alone.
-// `--key-coder huffg` (TZK2) is TZK1 with a GRAY bit per key frame (tezip_amd/keycoderg.py, k_key_gray / k_keyg_* in tz_codec.hip):
-// its stream, symbols and staged decoder's fields are the same, and ctx->keys_kind says which format's begin staged them, so
-// each put and decode refuses a body staged for the other format.
+// `--key-coder huffg` (TZK2, tezip_amd/keycoderg.py) is TZK1 with a GRAY bit per key frame, and TZK1 = TZK2 with no GRAY bit:
+// one path serves both, and a format is what KeysFmt says.  ctx->keys_kind says which format's begin staged a stream, so each
+// put and decode refuses a body staged for the other format.
 static constexpr int TZ_KEYS_A = 256;
 
-// the key list of a stack of nt frames: at least one index, strictly ascending, inside [0, nt); predictor ids 0..3
-static int keys_check(tz_ctx* ctx, int nt, const int* idx, int nkeys, const uint8_t* pred) {
+struct KeysFmt {
+    tz_ctx::tz_keys_kind kind;
+    int max_pred;           // the largest pred byte: predictor ids 0..3, | 4 (GRAY) where the format has the bit
+    const char* who;        // the entry points' prefix
+    const char* bad_pred;   // the refusal of a pred byte above max_pred: its value and its entry
+    const char* put_note;   // what the refusal of a put adds to "... the staged key-frame stream"
+};
+static constexpr KeysFmt FMT_TZK1{tz_ctx::KEYS_TZK1, 3, "tz_keys", "key frames: predictor id %d (entry %d) outside [0, 3]", ""},
+    FMT_TZK2{tz_ctx::KEYS_TZK2, 7, "tz_keysg", "key frames: pred byte %d (entry %d) outside [0, 7]", " (TZK2)"};
+
+// the key list of a stack of nt frames: at least one index, strictly ascending, inside [0, nt)
+static int keys_check(tz_ctx* ctx, int nt, const int* idx, int nkeys) {
     if (!idx || nkeys < 1 || nkeys > nt) return tz_fail(ctx, TZ_ERR_INVALID, "key frames: %d indices for a stack of %d frames", nkeys, nt);
-    for (int k = 0; k < nkeys; ++k) {
+    for (int k = 0; k < nkeys; ++k)
         if (idx[k] < 0 || idx[k] >= nt || (k && idx[k] <= idx[k - 1]))
             return tz_fail(ctx, TZ_ERR_INVALID, "key frames: index %d (entry %d) is not ascending inside [0, %d)", idx[k], k, nt);
-        if (pred && pred[k] > 3) return tz_fail(ctx, TZ_ERR_INVALID, "key frames: predictor id %d (entry %d) outside [0, 3]", pred[k], k);
-    }
     return TZ_OK;
 }
 
-static int keys_upload(tz_ctx* ctx, const int* idx, const uint8_t* pred, int nkeys, const int** d_idx, const uint8_t** d_pred) {
-    void *di, *dp;
-    TZ_TRY(tz_pool_alloc(ctx, sizeof(int) * nkeys, &di));
-    TZ_TRY(tz_upload(ctx, di, idx, sizeof(int) * nkeys));
-    *d_idx = (const int*)di;
+// pred bytes the format allows -> off[k], the exclusive prefix of the frames' symbol counts (k * H * W * 3 without a GRAY
+// frame), and their sum
+static int keys_layout(tz_ctx* ctx, const KeysFmt& f, const uint8_t* pred, int nkeys, int H, int W, std::vector<unsigned long long>* off,
+                       size_t* n) {
+    off->resize(nkeys);
+    unsigned long long at = 0;
+    for (int k = 0; k < nkeys; ++k) {
+        if (pred[k] > f.max_pred) return tz_fail(ctx, TZ_ERR_INVALID, f.bad_pred, pred[k], k);
+        (*off)[k] = at;
+        at += (unsigned long long)H * W * ((pred[k] & 4) ? 1 : 3);
+    }
+    *n = (size_t)at;
+    return TZ_OK;
+}
+
+struct KeysDev {
+    const int* idx = nullptr;
+    const uint8_t* pred = nullptr;
+    const unsigned long long* off = nullptr;
+};
+
+// idx, and pred and off where given, in pool blocks
+static int keys_upload(tz_ctx* ctx, const int* idx, const uint8_t* pred, const std::vector<unsigned long long>* off, int nkeys, KeysDev* d) {
+    void* p;
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(int) * nkeys, &p));
+    TZ_TRY(tz_upload(ctx, p, idx, sizeof(int) * nkeys));
+    d->idx = (const int*)p;
     if (pred) {
-        TZ_TRY(tz_pool_alloc(ctx, nkeys, &dp));
-        TZ_TRY(tz_upload(ctx, dp, pred, nkeys));
-        *d_pred = (const uint8_t*)dp;
+        TZ_TRY(tz_pool_alloc(ctx, nkeys, &p));
+        TZ_TRY(tz_upload(ctx, p, pred, nkeys));
+        d->pred = (const uint8_t*)p;
+    }
+    if (off) {
+        TZ_TRY(tz_pool_alloc(ctx, sizeof(unsigned long long) * nkeys, &p));
+        TZ_TRY(tz_upload(ctx, p, off->data(), sizeof(unsigned long long) * nkeys));
+        d->off = (const unsigned long long*)p;
     }
     return TZ_OK;
 }
@@ -2933,13 +2961,12 @@ static int keys_resident(tz_ctx* ctx, const char* who) {
 }
 
 static int keys_counts(tz_ctx* ctx, const int* idx, int nkeys, unsigned* counts) {
-    const int* d_idx = nullptr;
-    const uint8_t* d_pred = nullptr;
+    KeysDev d;
     void* d_counts;
     const size_t cb = (size_t)nkeys * 4 * TZ_KEYS_A * sizeof(unsigned);
-    TZ_TRY(keys_upload(ctx, idx, nullptr, nkeys, &d_idx, &d_pred));
+    TZ_TRY(keys_upload(ctx, idx, nullptr, nullptr, nkeys, &d));
     TZ_TRY(tz_pool_alloc(ctx, cb, &d_counts));
-    TZ_TRY(tzk_key_hist(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, nkeys, (unsigned*)d_counts));
+    TZ_TRY(tzk_key_hist(ctx, ctx->d_frames, ctx->H, ctx->W, d.idx, nkeys, (unsigned*)d_counts));
     TZ_TRY(tz_d2h(ctx, counts, d_counts, cb, ctx->stream));
     return tz_stream_sync(ctx);
 }
@@ -2948,79 +2975,19 @@ extern "C" int tz_keys_counts(tz_ctx* ctx, const int* idx, int nkeys, unsigned* 
     tz_roctx_range roctx_("tz_keys_counts");
     if (!ctx || !counts) return TZ_ERR_INVALID;
     TZ_TRY(keys_resident(ctx, "tz_keys_counts"));
-    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys, nullptr));
+    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys));
     const int rc = keys_counts(ctx, idx, nkeys, counts);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-static int keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths, size_t* bytes) {
-    const size_t n = (size_t)nkeys * ctx->H * ctx->W * 3;
-    const int* d_idx = nullptr;
-    const uint8_t* d_pred = nullptr;
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
-    TZ_TRY(keys_upload(ctx, idx, pred, nkeys, &d_idx, &d_pred));
-    TZ_TRY(tzk_key_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, d_pred, nkeys, ctx->d_keysym));
-    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);   // (dist 0: plain TZH1 codes)
-}
-
-extern "C" int tz_keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths, size_t* bytes) {
-    tz_roctx_range roctx_("tz_keys_encode");
-    if (!ctx || !pred || !lengths || !bytes) return TZ_ERR_INVALID;
-    TZ_TRY(keys_resident(ctx, "tz_keys_encode"));
-    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys, pred));
-    const int rc = keys_encode(ctx, idx, nkeys, pred, lengths, bytes);
-    tz_pool_release_all(ctx);
-    return rc;
-}
-
-extern "C" int tz_keys_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
-    if (!ctx || !out) return TZ_ERR_INVALID;
-    if (!ctx->d_keys || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
-        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the resident key-frame stream");
-    TZ_TRY(tz_d2h(ctx, out, ctx->d_keys + offset, count, ctx->stream));
-    return tz_stream_sync(ctx);
-}
-
-// symbols (device) -> the frames idx[k] of a stack at d_frames; the other frames of the stack are not touched
-static int keys_unresidual(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* idx, const uint8_t* pred, int nkeys, uint8_t* d_frames) {
-    const int* d_idx = nullptr;
-    const uint8_t* d_pred = nullptr;
-    TZ_TRY(keys_upload(ctx, idx, pred, nkeys, &d_idx, &d_pred));
-    return tzk_key_unresid(ctx, d_sym, H, W, d_idx, d_pred, nkeys, d_frames);
-}
-
-// pred bytes 0..7 -> off[k], the exclusive prefix of the frames' symbol counts, and their sum
-static int keysg_layout(tz_ctx* ctx, const uint8_t* predg, int nkeys, int H, int W, std::vector<unsigned long long>* off, size_t* n) {
-    off->resize(nkeys);
-    unsigned long long at = 0;
-    for (int k = 0; k < nkeys; ++k) {
-        if (predg[k] > 7) return tz_fail(ctx, TZ_ERR_INVALID, "key frames: pred byte %d (entry %d) outside [0, 7]", predg[k], k);
-        (*off)[k] = at;
-        at += (unsigned long long)H * W * ((predg[k] & 4) ? 1 : 3);
-    }
-    *n = (size_t)at;
-    return TZ_OK;
-}
-
-static int keysg_upload(tz_ctx* ctx, const int* idx, const uint8_t* predg, const std::vector<unsigned long long>& off, int nkeys,
-                        const int** d_idx, const uint8_t** d_predg, const unsigned long long** d_off) {
-    void* d;
-    TZ_TRY(keys_upload(ctx, idx, predg, nkeys, d_idx, d_predg));
-    TZ_TRY(tz_pool_alloc(ctx, sizeof(unsigned long long) * nkeys, &d));
-    TZ_TRY(tz_upload(ctx, d, off.data(), sizeof(unsigned long long) * nkeys));
-    *d_off = (const unsigned long long*)d;
-    return TZ_OK;
-}
-
 static int keys_gray(tz_ctx* ctx, const int* idx, int nkeys, uint8_t* gray) {
-    const int* d_idx = nullptr;
-    const uint8_t* d_pred = nullptr;
+    KeysDev d;
     void* d_flags;
     std::vector<unsigned> flags(nkeys);
-    TZ_TRY(keys_upload(ctx, idx, nullptr, nkeys, &d_idx, &d_pred));
+    TZ_TRY(keys_upload(ctx, idx, nullptr, nullptr, nkeys, &d));
     TZ_TRY(tz_pool_alloc(ctx, sizeof(unsigned) * nkeys, &d_flags));
-    TZ_TRY(tzk_key_gray(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, nkeys, (unsigned*)d_flags));
+    TZ_TRY(tzk_key_gray(ctx, ctx->d_frames, ctx->H, ctx->W, d.idx, nkeys, (unsigned*)d_flags));
     TZ_TRY(tz_d2h(ctx, flags.data(), d_flags, sizeof(unsigned) * nkeys, ctx->stream));
     TZ_TRY(tz_stream_sync(ctx));
     for (int k = 0; k < nkeys; ++k) gray[k] = flags[k] ? 0 : 1;
@@ -3031,33 +2998,50 @@ extern "C" int tz_keys_gray(tz_ctx* ctx, const int* idx, int nkeys, uint8_t* gra
     tz_roctx_range roctx_("tz_keys_gray");
     if (!ctx || !gray) return TZ_ERR_INVALID;
     TZ_TRY(keys_resident(ctx, "tz_keys_gray"));
-    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys, nullptr));
+    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys));
     const int rc = keys_gray(ctx, idx, nkeys, gray);
     tz_pool_release_all(ctx);
     return rc;
 }
 
-static int keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* predg, const uint8_t* lengths, size_t* bytes) {
+static int keys_encode_dev(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const std::vector<unsigned long long>& off, size_t n,
+                           const uint8_t* lengths, size_t* bytes) {
+    KeysDev d;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
+    TZ_TRY(keys_upload(ctx, idx, pred, &off, nkeys, &d));
+    TZ_TRY(tzk_key_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d.idx, d.pred, d.off, nkeys, ctx->d_keysym));
+    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);   // (dist 0: plain TZH1 codes)
+}
+
+static int keys_encode(tz_ctx* ctx, const KeysFmt& f, const char* who, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths,
+                       size_t* bytes) {
+    if (!ctx || !pred || !lengths || !bytes) return TZ_ERR_INVALID;
     std::vector<unsigned long long> off;
     size_t n;
-    TZ_TRY(keysg_layout(ctx, predg, nkeys, ctx->H, ctx->W, &off, &n));
-    const int* d_idx = nullptr;
-    const uint8_t* d_predg = nullptr;
-    const unsigned long long* d_off = nullptr;
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
-    TZ_TRY(keysg_upload(ctx, idx, predg, off, nkeys, &d_idx, &d_predg, &d_off));
-    TZ_TRY(tzk_keyg_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d_idx, d_predg, d_off, nkeys, ctx->d_keysym));
-    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);   // (dist 0: plain TZH1 codes)
+    TZ_TRY(keys_resident(ctx, who));
+    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys));
+    TZ_TRY(keys_layout(ctx, f, pred, nkeys, ctx->H, ctx->W, &off, &n));
+    const int rc = keys_encode_dev(ctx, idx, nkeys, pred, off, n, lengths, bytes);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+extern "C" int tz_keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths, size_t* bytes) {
+    tz_roctx_range roctx_("tz_keys_encode");
+    return keys_encode(ctx, FMT_TZK1, "tz_keys_encode", idx, nkeys, pred, lengths, bytes);
 }
 
 extern "C" int tz_keysg_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* predg, const uint8_t* lengths, size_t* bytes) {
     tz_roctx_range roctx_("tz_keysg_encode");
-    if (!ctx || !predg || !lengths || !bytes) return TZ_ERR_INVALID;
-    TZ_TRY(keys_resident(ctx, "tz_keysg_encode"));
-    TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys, nullptr));
-    const int rc = keysg_encode(ctx, idx, nkeys, predg, lengths, bytes);
-    tz_pool_release_all(ctx);
-    return rc;
+    return keys_encode(ctx, FMT_TZK2, "tz_keysg_encode", idx, nkeys, predg, lengths, bytes);
+}
+
+extern "C" int tz_keys_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    if (!ctx->d_keys || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the resident key-frame stream");
+    TZ_TRY(tz_d2h(ctx, out, ctx->d_keys + offset, count, ctx->stream));
+    return tz_stream_sync(ctx);
 }
 
 extern "C" int tz_keysg_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* out) {
@@ -3065,35 +3049,27 @@ extern "C" int tz_keysg_get(tz_ctx* ctx, size_t offset, size_t count, uint8_t* o
 }
 
 // symbols (device) -> the frames idx[k] of a stack at d_frames; the other frames of the stack are not touched
-static int keysg_unresidual(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* idx, const uint8_t* predg, int nkeys, uint8_t* d_frames) {
+static int keys_unresidual(tz_ctx* ctx, const KeysFmt& f, const int16_t* d_sym, int H, int W, const int* idx, const uint8_t* pred, int nkeys,
+                           uint8_t* d_frames) {
     std::vector<unsigned long long> off;
     size_t n;
-    TZ_TRY(keysg_layout(ctx, predg, nkeys, H, W, &off, &n));
-    std::vector<uint8_t> pred3(predg, predg + nkeys);
-    for (auto& p : pred3)
-        if (p & 4) p = 0;
-    const int* d_idx = nullptr;
-    const uint8_t* d_predg = nullptr;
-    const unsigned long long* d_off = nullptr;
-    void *d_pred3, *d_tmp;
-    TZ_TRY(keysg_upload(ctx, idx, predg, off, nkeys, &d_idx, &d_predg, &d_off));
-    TZ_TRY(tz_pool_alloc(ctx, nkeys, &d_pred3));
-    TZ_TRY(tz_upload(ctx, d_pred3, pred3.data(), nkeys));
-    TZ_TRY(tz_pool_alloc(ctx, n, &d_tmp));
-    return tzk_keyg_unresid(ctx, d_sym, H, W, d_idx, d_predg, (const uint8_t*)d_pred3, d_off, nkeys, (uint8_t*)d_tmp, d_frames);
+    TZ_TRY(keys_layout(ctx, f, pred, nkeys, H, W, &off, &n));
+    KeysDev d;
+    TZ_TRY(keys_upload(ctx, idx, pred, &off, nkeys, &d));
+    void* d_tmp = nullptr;   // the scratch plane of the GRAY frames' column pass, where a frame has one
+    if (std::any_of(pred, pred + nkeys, [](uint8_t p) { return (p & 6) == 6; })) TZ_TRY(tz_pool_alloc(ctx, n, &d_tmp));
+    return tzk_key_unresid(ctx, d_sym, H, W, d.idx, d.pred, d.off, nkeys, (uint8_t*)d_tmp, d_frames);
 }
 
-// One body for tz_keys_begin / tz_keysg_begin: the key list and the pred array are checked as the format says -- predictor
-// ids 0..3 (TZK1) or pred bytes 0..7, whose GRAY bits give the symbol count (TZK2) -- the rest is the same.
-static int keys_begin(tz_ctx* ctx, tz_ctx::tz_keys_kind kind, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* pred,
+static int keys_begin(tz_ctx* ctx, const KeysFmt& f, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* pred,
                       const uint8_t* lengths) {
     if (!ctx || !pred) return TZ_ERR_INVALID;
     if (nt < 1 || H < 1 || W < 1 || nt > kMaxFrames || H > 32767 || W > 32767)
         return tz_fail(ctx, TZ_ERR_INVALID, "bad sequence shape nt=%d H=%d W=%d (int16 trailer limits)", nt, H, W);
-    TZ_TRY(keys_check(ctx, nt, idx, nkeys, kind == tz_ctx::KEYS_TZK1 ? pred : nullptr));
+    TZ_TRY(keys_check(ctx, nt, idx, nkeys));
     std::vector<unsigned long long> off;
-    size_t n = (size_t)nkeys * H * W * 3, sw;
-    if (kind == tz_ctx::KEYS_TZK2) TZ_TRY(keysg_layout(ctx, pred, nkeys, H, W, &off, &n));
+    size_t n, sw;
+    TZ_TRY(keys_layout(ctx, f, pred, nkeys, H, W, &off, &n));
     TZ_TRY(huff_check_stream(ctx, bytes, n, TZ_HUFF_RUN, &sw));
     std::vector<uint16_t> dec;
     TZ_TRY(huff_tables(ctx, lengths, TZ_KEYS_A, 0, nullptr, &dec, 0));
@@ -3109,22 +3085,22 @@ static int keys_begin(tz_ctx* ctx, tz_ctx::tz_keys_kind kind, size_t bytes, int 
     ctx->keys_pred.assign(pred, pred + nkeys);
     ctx->keys_dec_tab.swap(dec);
     ctx->keys_n = n;
-    ctx->keys_kind = kind;
+    ctx->keys_kind = f.kind;
     TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));  // earlier work may still read the old stream
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
     return TZ_OK;
 }
 
-static int keys_put(tz_ctx* ctx, tz_ctx::tz_keys_kind kind, size_t offset, size_t count, const uint8_t* src) {
+static int keys_put(tz_ctx* ctx, const KeysFmt& f, size_t offset, size_t count, const uint8_t* src) {
     if (!ctx || !src) return TZ_ERR_INVALID;
-    if (!ctx->d_keys || ctx->keys_kind != kind || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
-        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged key-frame stream%s", kind == tz_ctx::KEYS_TZK2 ? " (TZK2)" : "");
+    if (!ctx->d_keys || ctx->keys_kind != f.kind || offset > ctx->keys_bytes || count > ctx->keys_bytes - offset)
+        return tz_fail(ctx, TZ_ERR_INVALID, "byte range outside the staged key-frame stream%s", f.put_note);
     TZ_TRY(tz_h2d(ctx, ctx->d_keys + offset, src, count, ctx->copy_stream));
     ctx->keys_put += count;
     return TZ_OK;
 }
 
-static int keys_decode_dev(tz_ctx* ctx) {
+static int keys_decode_dev(tz_ctx* ctx, const KeysFmt& f) {
     const int nt = ctx->keys_nt, H = ctx->keys_H, W = ctx->keys_W;
     size_t sw;
     TZ_TRY(huff_check_stream(ctx, ctx->keys_bytes, ctx->keys_n, TZ_HUFF_RUN, &sw));
@@ -3137,8 +3113,7 @@ static int keys_decode_dev(tz_ctx* ctx) {
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
     TZ_TRY(huff_decode_dev(ctx, ctx->d_keys, sw, ctx->keys_n, ctx->keys_dec_tab, TZ_KEYS_A, 0, 0, ctx->d_keysym));
     TZ_HIP(ctx, hipMemsetAsync(ctx->d_frames, 0, fb, ctx->stream));   // the frames that are no key frames (a fresh buffer holds anything)
-    TZ_TRY((ctx->keys_kind == tz_ctx::KEYS_TZK2 ? keysg_unresidual : keys_unresidual)(ctx, ctx->d_keysym, H, W, ctx->keys_idx.data(),
-                                                                                    ctx->keys_pred.data(), (int)ctx->keys_idx.size(), ctx->d_frames));
+    TZ_TRY(keys_unresidual(ctx, f, ctx->d_keysym, H, W, ctx->keys_idx.data(), ctx->keys_pred.data(), (int)ctx->keys_idx.size(), ctx->d_frames));
     TZ_HIP(ctx, hipEventRecord(ctx->ev_compute, ctx->stream));       // a later tz_frames_put waits for the frames written here
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_compute, 0));
     ctx->nt = nt;
@@ -3148,106 +3123,90 @@ static int keys_decode_dev(tz_ctx* ctx) {
     return TZ_OK;
 }
 
-static int keys_decode(tz_ctx* ctx, tz_ctx::tz_keys_kind kind, const char* who) {
+static int keys_decode(tz_ctx* ctx, const KeysFmt& f) {
     if (!ctx) return TZ_ERR_INVALID;
-    if (ctx->keys_kind != kind || !ctx->d_keys || !ctx->d_keysym)
-        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode needs a stream staged with %s_begin / %s_put", who, who, who);
+    if (ctx->keys_kind != f.kind || !ctx->d_keys || !ctx->d_keysym)
+        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode needs a stream staged with %s_begin / %s_put", f.who, f.who, f.who);
     if (ctx->keys_put != ctx->keys_bytes)
-        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode: %zu of the stream's %zu bytes were put", who, ctx->keys_put, ctx->keys_bytes);
-    const int rc = keys_decode_dev(ctx);
+        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode: %zu of the stream's %zu bytes were put", f.who, ctx->keys_put, ctx->keys_bytes);
+    const int rc = keys_decode_dev(ctx, f);
     tz_pool_release_all(ctx);
     return rc;
 }
 
 extern "C" int tz_keys_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* pred,
                              const uint8_t* lengths) {
-    return keys_begin(ctx, tz_ctx::KEYS_TZK1, bytes, nt, H, W, idx, nkeys, pred, lengths);
+    return keys_begin(ctx, FMT_TZK1, bytes, nt, H, W, idx, nkeys, pred, lengths);
 }
 
-extern "C" int tz_keys_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
-    return keys_put(ctx, tz_ctx::KEYS_TZK1, offset, count, src);
-}
+extern "C" int tz_keys_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) { return keys_put(ctx, FMT_TZK1, offset, count, src); }
 
 extern "C" int tz_keys_decode(tz_ctx* ctx) {
     tz_roctx_range roctx_("tz_keys_decode");
-    return keys_decode(ctx, tz_ctx::KEYS_TZK1, "tz_keys");
+    return keys_decode(ctx, FMT_TZK1);
 }
 
 extern "C" int tz_keysg_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* predg,
                               const uint8_t* lengths) {
-    return keys_begin(ctx, tz_ctx::KEYS_TZK2, bytes, nt, H, W, idx, nkeys, predg, lengths);
+    return keys_begin(ctx, FMT_TZK2, bytes, nt, H, W, idx, nkeys, predg, lengths);
 }
 
-extern "C" int tz_keysg_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) {
-    return keys_put(ctx, tz_ctx::KEYS_TZK2, offset, count, src);
-}
+extern "C" int tz_keysg_put(tz_ctx* ctx, size_t offset, size_t count, const uint8_t* src) { return keys_put(ctx, FMT_TZK2, offset, count, src); }
 
 extern "C" int tz_keysg_decode(tz_ctx* ctx) {
     tz_roctx_range roctx_("tz_keysg_decode");
-    return keys_decode(ctx, tz_ctx::KEYS_TZK2, "tz_keysg");
+    return keys_decode(ctx, FMT_TZK2);
 }
 
-// stand-alone forms on host or device arrays: frames (k, H, W, 3) <-> int16 symbols, k * H * W * 3 of them under pred[k] per
-// frame (TZK1), or those keysg_layout counts under predg[k] (TZK2)
+// stand-alone forms on host or device arrays: frames (k, H, W, 3) <-> the int16 symbols keys_layout counts under pred[k]
 static const char* const kKeySymAlign = "key frames: a device symbol array must be 2-byte aligned";
 
-static int keys_buf_check(tz_ctx* ctx, int k, int H, int W, std::vector<int>* idx) {
+// the k frames of a buffer form are their own key list; *n: their symbols
+static int keys_buf_layout(tz_ctx* ctx, const KeysFmt& f, int k, int H, int W, const uint8_t* pred, std::vector<int>* idx,
+                           std::vector<unsigned long long>* off, size_t* n) {
     if (k < 1 || H < 1 || W < 1 || k > kMaxFrames || H > 32767 || W > 32767)
         return tz_fail(ctx, TZ_ERR_INVALID, "bad key-frame stack k=%d H=%d W=%d", k, H, W);
     idx->resize(k);
     for (int i = 0; i < k; ++i) (*idx)[i] = i;
-    return TZ_OK;
+    return keys_layout(ctx, f, pred, k, H, W, off, n);
+}
+
+static int keys_residual_buf(tz_ctx* ctx, const KeysFmt& f, const uint8_t* frames, int k, int H, int W, const uint8_t* pred, int16_t* sym) {
+    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
+    std::vector<int> idx;
+    std::vector<unsigned long long> off;
+    size_t n;
+    TZ_TRY(keys_buf_layout(ctx, f, k, H, W, pred, &idx, &off, &n));
+    return buf_op(ctx, frames, (size_t)k * H * W * 3, 0, sym, n * 2, 1, kKeySymAlign, [&](const void* din, void* dout) {
+        KeysDev d;
+        TZ_TRY(keys_upload(ctx, idx.data(), pred, &off, k, &d));
+        return tzk_key_resid(ctx, (const uint8_t*)din, H, W, d.idx, d.pred, d.off, k, (int16_t*)dout);
+    });
+}
+
+static int keys_unresidual_buf(tz_ctx* ctx, const KeysFmt& f, const int16_t* sym, int k, int H, int W, const uint8_t* pred, uint8_t* frames) {
+    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
+    std::vector<int> idx;
+    std::vector<unsigned long long> off;
+    size_t n;
+    TZ_TRY(keys_buf_layout(ctx, f, k, H, W, pred, &idx, &off, &n));
+    return buf_op(ctx, sym, n * 2, 1, frames, (size_t)k * H * W * 3, 0, kKeySymAlign, [&](const void* din, void* dout) {
+        return keys_unresidual(ctx, f, (const int16_t*)din, H, W, idx.data(), pred, k, (uint8_t*)dout);
+    });
 }
 
 extern "C" int tz_keys_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* pred, int16_t* sym) {
-    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
-    std::vector<int> idx;
-    TZ_TRY(keys_buf_check(ctx, k, H, W, &idx));
-    TZ_TRY(keys_check(ctx, k, idx.data(), k, pred));
-    const size_t n = (size_t)k * H * W * 3;
-    return buf_op(ctx, frames, n, 0, sym, n * 2, 1, kKeySymAlign, [&](const void* din, void* dout) {
-        const int* d_idx = nullptr;
-        const uint8_t* d_pred = nullptr;
-        TZ_TRY(keys_upload(ctx, idx.data(), pred, k, &d_idx, &d_pred));
-        return tzk_key_resid(ctx, (const uint8_t*)din, H, W, d_idx, d_pred, k, (int16_t*)dout);
-    });
+    return keys_residual_buf(ctx, FMT_TZK1, frames, k, H, W, pred, sym);
 }
 
 extern "C" int tz_keys_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* pred, uint8_t* frames) {
-    if (!ctx || !frames || !pred || !sym) return TZ_ERR_INVALID;
-    std::vector<int> idx;
-    TZ_TRY(keys_buf_check(ctx, k, H, W, &idx));
-    TZ_TRY(keys_check(ctx, k, idx.data(), k, pred));
-    const size_t n = (size_t)k * H * W * 3;
-    return buf_op(ctx, sym, n * 2, 1, frames, n, 0, kKeySymAlign, [&](const void* din, void* dout) {
-        return keys_unresidual(ctx, (const int16_t*)din, H, W, idx.data(), pred, k, (uint8_t*)dout);
-    });
+    return keys_unresidual_buf(ctx, FMT_TZK1, sym, k, H, W, pred, frames);
 }
 
 extern "C" int tz_keysg_residual_buf(tz_ctx* ctx, const uint8_t* frames, int k, int H, int W, const uint8_t* predg, int16_t* sym) {
-    if (!ctx || !frames || !predg || !sym) return TZ_ERR_INVALID;
-    std::vector<int> idx;
-    std::vector<unsigned long long> off;
-    size_t n;
-    TZ_TRY(keys_buf_check(ctx, k, H, W, &idx));
-    TZ_TRY(keysg_layout(ctx, predg, k, H, W, &off, &n));
-    return buf_op(ctx, frames, (size_t)k * H * W * 3, 0, sym, n * 2, 1, kKeySymAlign, [&](const void* din, void* dout) {
-        const int* d_idx = nullptr;
-        const uint8_t* d_predg = nullptr;
-        const unsigned long long* d_off = nullptr;
-        TZ_TRY(keysg_upload(ctx, idx.data(), predg, off, k, &d_idx, &d_predg, &d_off));
-        return tzk_keyg_resid(ctx, (const uint8_t*)din, H, W, d_idx, d_predg, d_off, k, (int16_t*)dout);
-    });
+    return keys_residual_buf(ctx, FMT_TZK2, frames, k, H, W, predg, sym);
 }
 
 extern "C" int tz_keysg_unresidual_buf(tz_ctx* ctx, const int16_t* sym, int k, int H, int W, const uint8_t* predg, uint8_t* frames) {
-    if (!ctx || !frames || !predg || !sym) return TZ_ERR_INVALID;
-    std::vector<int> idx;
-    std::vector<unsigned long long> off;
-    size_t n;
-    TZ_TRY(keys_buf_check(ctx, k, H, W, &idx));
-    TZ_TRY(keysg_layout(ctx, predg, k, H, W, &off, &n));
-    return buf_op(ctx, sym, n * 2, 1, frames, (size_t)k * H * W * 3, 0, kKeySymAlign, [&](const void* din, void* dout) {
-        return keysg_unresidual(ctx, (const int16_t*)din, H, W, idx.data(), predg, k, (uint8_t*)dout);
-    });
+    return keys_unresidual_buf(ctx, FMT_TZK2, sym, k, H, W, predg, frames);
 }

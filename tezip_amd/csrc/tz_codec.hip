@@ -3920,6 +3920,11 @@ int tzk_huff_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run
 // neighbour a, 2: the upper neighbour b, 3: a + b - c with c the upper-left one, always of the same channel and 0 outside
 // the frame, everything mod 256 -- and the residuals of all key frames are coded by the k_huff_* kernels above as int16
 // symbols 0..255.  The inverses are prefix sums mod 256 along the rows (1), the columns (2) or both (3).
+// `--key-coder huffg` (format TZK2, tezip_amd/keycoderg.py) is the same with one more bit per key frame: a key frame whose
+// three channels are equal at every pixel is GRAY (bit 2, value 4, of its pred byte), contributes the H * W residuals of
+// channel 0 alone, and the inverse writes each sample to all three channels.  Frames therefore differ in size: frame k's symbols
+// start at off[k], the u64 exclusive prefix of the per-frame symbol counts the host passes in.  TZK1 = TZK2 with no GRAY bit
+// (off[k] = k * fe), so one residual kernel and one set of inverse kernels serve both.
 // A frame is fe = H * W3 bytes, W3 = 3 W; a thread takes a UNIT of it: unit 0 is the head in front of the first 16-byte
 // boundary of the frame's address (fewer than 16 samples, possibly none), unit u >= 1 the 16 samples from there on.
 struct KeyWin {
@@ -4027,120 +4032,6 @@ int tzk_key_hist(tz_ctx* ctx, const uint8_t* d_frames, int H, int W, const int* 
     return TZ_OK;
 }
 
-// Residuals of key frame idx[k] under predictor pred[k] as int16 symbols 0..255 at sym[k * fe ...]: what k_huff_size /
-// k_huff_enc code.  16-byte loads of the samples; 16-byte stores where the output's address allows them.
-__global__ __launch_bounds__(256) void k_key_resid(const uint8_t* __restrict__ frames, size_t fe, unsigned W3, const int* __restrict__ idx,
-                                                   const uint8_t* __restrict__ pred, int16_t* __restrict__ sym) {
-    const int key = blockIdx.y;
-    const uint8_t* f = frames + (size_t)idx[key] * fe;
-    int16_t* out = sym + (size_t)key * fe;
-    const unsigned p = pred[key];
-    const unsigned head = key_head(f, fe);
-    const size_t nunits = 1 + (fe - head + 15) / 16, stride = (size_t)gridDim.x * 256;
-    for (size_t u = (size_t)blockIdx.x * 256 + threadIdx.x; u < nunits; u += stride) {
-        size_t e;
-        int cnt;
-        key_unit(u, head, fe, &e, &cnt);
-        if (cnt <= 0) continue;
-        KeyWin w;
-        key_window(f, fe, W3, e, cnt, w);
-        short8 lo, hi;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const unsigned q = (p & 1u ? w.a[j] : 0u) + (p & 2u ? w.b[j] : 0u) - (p == 3u ? w.c[j] : 0u);
-            const short v = (short)((w.x[j] - q) & 255u);
-            if (j < 8) lo[j] = v;
-            else hi[j - 8] = v;
-        }
-        if (cnt == 16 && ((uintptr_t)(out + e) & 15) == 0) {
-            *(short8*)(out + e) = lo;
-            *(short8*)(out + e + 8) = hi;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                if (j < cnt) out[e + j] = j < 8 ? lo[j] : hi[j - 8];
-        }
-    }
-}
-
-int tzk_key_resid(tz_ctx* ctx, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, int16_t* d_sym) {
-    const size_t fe = (size_t)H * W * 3;
-    tz_prof_scope ps(ctx, TZP_HUFF);
-    hipLaunchKernelGGL(k_key_resid, key_grid(fe, nkeys), dim3(256), 0, ctx->stream, d_frames, fe, (unsigned)W * 3u, d_idx, d_pred, d_sym);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
-}
-
-// The inverse, first pass: one wave per (key frame, row) turns the row's symbols into bytes of frame idx[k] -- under
-// predictors 1 and 3 as the inclusive prefix sum mod 256 along the row, per channel: 64 columns at a time, a shuffle scan
-// over the lanes, the carry into the next 64 columns in a register.  Only the low byte of a symbol counts.
-__global__ __launch_bounds__(256) void k_key_unresid_row(const int16_t* __restrict__ sym, int H, int W, const int* __restrict__ idx,
-                                                         const uint8_t* __restrict__ pred, uint8_t* __restrict__ frames) {
-    const int key = blockIdx.y, y = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (y >= H) return;   // (wave-uniform)
-    const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3;
-    const int16_t* s = sym + (size_t)key * fe + (size_t)y * W3;
-    uint8_t* o = frames + (size_t)idx[key] * fe + (size_t)y * W3;
-    const bool scan = (pred[key] & 1u) != 0;
-    unsigned carry[3] = {0u, 0u, 0u};
-    for (int c0 = 0; c0 < W; c0 += 64) {
-        const int col = c0 + lane;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            unsigned v = col < W ? (unsigned)s[(size_t)col * 3 + ch] & 255u : 0u;
-            if (scan) {
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const unsigned t = __shfl_up(v, d, 64);
-                    if (lane >= d) v += t;
-                }
-                v += carry[ch];
-                carry[ch] = __shfl(v, 63, 64) & 255u;
-            }
-            if (col < W) o[(size_t)col * 3 + ch] = (uint8_t)v;
-        }
-    }
-}
-
-// Second pass, predictors 2 and 3: a thread per (key frame, sample of a row) walks down its column and replaces every byte
-// by the running sum mod 256; neighbouring threads touch neighbouring bytes.  Eight rows are loaded before they are summed.
-__global__ __launch_bounds__(256) void k_key_unresid_col(int H, int W, const int* __restrict__ idx, const uint8_t* __restrict__ pred,
-                                                         uint8_t* __restrict__ frames) {
-    const int key = blockIdx.y;
-    if (!(pred[key] & 2u)) return;   // (workgroup-uniform)
-    const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3, j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= W3) return;
-    uint8_t* o = frames + (size_t)idx[key] * fe + j;
-    unsigned acc = 0;
-    for (int y0 = 0; y0 < H; y0 += 8) {
-        unsigned v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = y0 + i < H ? o[(size_t)(y0 + i) * W3] : 0u;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            acc += v[i];
-            if (y0 + i < H) o[(size_t)(y0 + i) * W3] = (uint8_t)acc;
-        }
-    }
-}
-
-int tzk_key_unresid(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, uint8_t* d_frames) {
-    tz_prof_scope ps(ctx, TZP_HUFF);
-    hipLaunchKernelGGL(k_key_unresid_row, dim3((unsigned)((H + 3) / 4), (unsigned)nkeys), dim3(256), 0, ctx->stream, d_sym, H, W, d_idx, d_pred,
-                       d_frames);
-    TZ_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_key_unresid_col, dim3((unsigned)(((size_t)W * 3 + 255) / 256), (unsigned)nkeys), dim3(256), 0, ctx->stream, H, W, d_idx,
-                       d_pred, d_frames);
-    TZ_HIP(ctx, hipGetLastError());
-    return TZ_OK;
-}
-
-// ---------------------------------------------------------------------------- key-frame coder, gray frames once (TZK2)
-// Opt-in stage `--key-coder huffg` (format TZK2: DESIGN.md section 9, tezip_amd/keycoderg.py is the slow statement of it).
-// A key frame whose three channels are equal at every pixel is GRAY (bit 2 of its pred byte): it contributes the H * W
-// residuals of channel 0 alone, and the inverse writes each sample to all three channels.  Frames therefore differ in size:
-// frame k's symbols start at off[k], the u64 exclusive prefix of the per-frame symbol counts the host passes in.
-
 // flags[k] becomes non-zero iff key frame idx[k] has a pixel with unequal channels.  The frame is gray iff f[i] == f[i + 1] for
 // every byte index i with i % 3 != 2 (fe is a multiple of 3, so i + 1 < fe for those).  Unit 0 is the head in front of the first
 // 16-byte boundary, unit u >= 1 the 48 bytes from there on: three 16-byte loads, every byte compared with its successor through
@@ -4193,18 +4084,19 @@ int tzk_key_gray(tz_ctx* ctx, const uint8_t* d_frames, int H, int W, const int* 
     return TZ_OK;
 }
 
-// Residuals of key frame idx[k] under pred byte predg[k] at sym[off[k] ...].  GRAY: a thread per pixel reads channel 0 of the
-// pixel and of its three neighbours at stride 3 (a wave covers 192 contiguous bytes of a row) and writes one symbol, so a
-// wave stores 128 contiguous bytes.  Any other frame: k_key_resid's units, at the frame's own offset.
-__global__ __launch_bounds__(256) void k_keyg_resid(const uint8_t* __restrict__ frames, int H, int W, const int* __restrict__ idx,
-                                                    const uint8_t* __restrict__ predg, const unsigned long long* __restrict__ off,
-                                                    int16_t* __restrict__ sym) {
+// Residuals of key frame idx[k] under pred byte pred[k] as int16 symbols 0..255 at sym[off[k] ...]: what k_huff_size /
+// k_huff_enc code.  GRAY: a thread per pixel reads channel 0 of the pixel and of its three neighbours at stride 3 (a wave covers
+// 192 contiguous bytes of a row) and writes one symbol, so a wave stores 128 contiguous bytes.  Any other frame: a thread per
+// unit, 16-byte loads of the samples; 16-byte stores where the output's address allows them.
+__global__ __launch_bounds__(256) void k_key_resid(const uint8_t* __restrict__ frames, int H, int W, const int* __restrict__ idx,
+                                                   const uint8_t* __restrict__ pred, const unsigned long long* __restrict__ off,
+                                                   int16_t* __restrict__ sym) {
     const int key = blockIdx.y;
     const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3, stride = (size_t)gridDim.x * 256;
     const uint8_t* f = frames + (size_t)idx[key] * fe;
     int16_t* out = sym + off[key];
-    const unsigned p = predg[key] & 3u;
-    if (predg[key] & 4u) {   // (workgroup-uniform)
+    const unsigned p = pred[key] & 3u;
+    if (pred[key] & 4u) {   // (workgroup-uniform)
         const size_t np = (size_t)H * W;
         for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < np; q += stride) {
             const size_t y = q / (size_t)W, col = q - y * (size_t)W;
@@ -4244,10 +4136,10 @@ __global__ __launch_bounds__(256) void k_keyg_resid(const uint8_t* __restrict__ 
     }
 }
 
-int tzk_keyg_resid(tz_ctx* ctx, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_predg,
-                   const unsigned long long* d_off, int nkeys, int16_t* d_sym) {
+int tzk_key_resid(tz_ctx* ctx, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_pred,
+                  const unsigned long long* d_off, int nkeys, int16_t* d_sym) {
     tz_prof_scope ps(ctx, TZP_HUFF);
-    hipLaunchKernelGGL(k_keyg_resid, key_grid((size_t)H * W * 3, nkeys), dim3(256), 0, ctx->stream, d_frames, H, W, d_idx, d_predg, d_off, d_sym);
+    hipLaunchKernelGGL(k_key_resid, key_grid((size_t)H * W * 3, nkeys), dim3(256), 0, ctx->stream, d_frames, H, W, d_idx, d_pred, d_off, d_sym);
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
@@ -4275,17 +4167,30 @@ __device__ __forceinline__ void keyg_store3(unsigned v, int lane, int ncols, uin
     }
 }
 
-// The inverse, first pass: one wave per (key frame, row).  GRAY: the row's W symbols, scanned along the row under predictors 1
-// and 3 (k_key_unresid_row's shuffle scan, one channel), go replicated into the frame (keyg_store3) -- or, when a column
-// pass follows (predictors 2 and 3), as single bytes to tmp[off[k] + y * W + col], from where k_keyg_unresid_col finishes
-// them.  Any other frame: k_key_unresid_row's work at the frame's own offset.  Only the low byte of a symbol counts.
-__global__ __launch_bounds__(256) void k_keyg_unresid_row(const int16_t* __restrict__ sym, int H, int W, const int* __restrict__ idx,
-                                                          const uint8_t* __restrict__ predg, const unsigned long long* __restrict__ off,
-                                                          uint8_t* __restrict__ tmp, uint8_t* __restrict__ frames) {
+// One sample per lane, 64 neighbouring columns of a row: the inclusive prefix sum over the lanes plus *carry, what the columns
+// in front of them add up to; *carry becomes the last lane's sum mod 256.  Every lane of the wave must call this.
+__device__ __forceinline__ unsigned key_scan64(unsigned v, int lane, unsigned* carry) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned t = __shfl_up(v, d, 64);
+        if (lane >= d) v += t;
+    }
+    v += *carry;
+    *carry = __shfl(v, 63, 64) & 255u;
+    return v;
+}
+
+// The inverse, first pass: one wave per (key frame, row) turns the row's symbols into bytes of frame idx[k] -- under
+// predictors 1 and 3 as the inclusive prefix sum mod 256 along the row, per channel, 64 columns at a time (key_scan64).  GRAY:
+// the row's W sums go replicated into the frame (keyg_store3) -- or, when a column pass follows (predictors 2 and 3), as
+// single bytes to tmp[off[k] + y * W + col], from where k_key_unresid_colg finishes them.  Only the low byte of a symbol counts.
+__global__ __launch_bounds__(256) void k_key_unresid_row(const int16_t* __restrict__ sym, int H, int W, const int* __restrict__ idx,
+                                                         const uint8_t* __restrict__ pred, const unsigned long long* __restrict__ off,
+                                                         uint8_t* __restrict__ tmp, uint8_t* __restrict__ frames) {
     const int key = blockIdx.y, y = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (y >= H) return;   // (wave-uniform)
     const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3;
-    const unsigned pb = predg[key];
+    const unsigned pb = pred[key];
     const bool scan = (pb & 1u) != 0;
     uint8_t* o = frames + (size_t)idx[key] * fe + (size_t)y * W3;
     if (pb & 4u) {   // (workgroup-uniform)
@@ -4295,15 +4200,7 @@ __global__ __launch_bounds__(256) void k_keyg_unresid_row(const int16_t* __restr
         for (int c0 = 0; c0 < W; c0 += 64) {
             const int col = c0 + lane;
             unsigned v = col < W ? (unsigned)s[col] & 255u : 0u;
-            if (scan) {
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const unsigned u = __shfl_up(v, d, 64);
-                    if (lane >= d) v += u;
-                }
-                v += carry;
-                carry = __shfl(v, 63, 64) & 255u;
-            }
+            if (scan) v = key_scan64(v, lane, &carry);
             if (pb & 2u) {
                 if (col < W) t[col] = (uint8_t)v;
             } else {
@@ -4319,28 +4216,42 @@ __global__ __launch_bounds__(256) void k_keyg_unresid_row(const int16_t* __restr
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             unsigned v = col < W ? (unsigned)s[(size_t)col * 3 + ch] & 255u : 0u;
-            if (scan) {
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const unsigned u = __shfl_up(v, d, 64);
-                    if (lane >= d) v += u;
-                }
-                v += carry[ch];
-                carry[ch] = __shfl(v, 63, 64) & 255u;
-            }
+            if (scan) v = key_scan64(v, lane, &carry[ch]);
             if (col < W) o[(size_t)col * 3 + ch] = (uint8_t)v;
+        }
+    }
+}
+
+// Second pass, predictors 2 and 3 of a frame that is not GRAY: a thread per (key frame, sample of a row) walks down its column
+// and replaces every byte by the running sum mod 256; neighbouring threads touch neighbouring bytes.  Eight rows are loaded
+// before they are summed.
+__global__ __launch_bounds__(256) void k_key_unresid_col(int H, int W, const int* __restrict__ idx, const uint8_t* __restrict__ pred,
+                                                         uint8_t* __restrict__ frames) {
+    const int key = blockIdx.y;
+    if ((pred[key] & 6u) != 2u) return;   // (workgroup-uniform)
+    const size_t W3 = (size_t)W * 3, fe = (size_t)H * W3, j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= W3) return;
+    uint8_t* o = frames + (size_t)idx[key] * fe + j;
+    unsigned acc = 0;
+    for (int y0 = 0; y0 < H; y0 += 8) {
+        unsigned v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = y0 + i < H ? o[(size_t)(y0 + i) * W3] : 0u;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            acc += v[i];
+            if (y0 + i < H) o[(size_t)(y0 + i) * W3] = (uint8_t)acc;
         }
     }
 }
 
 // Second pass of a GRAY frame under predictors 2 and 3: a thread per (key frame, column) walks down its column of tmp, eight
 // rows loaded ahead, and every wave writes the running sums mod 256 of its 64 columns replicated into the frame (keyg_store3).
-// The other frames' column pass is k_key_unresid_col itself, given predictor ids in which the GRAY frames carry 0.
-__global__ __launch_bounds__(256) void k_keyg_unresid_col(int H, int W, const int* __restrict__ idx, const uint8_t* __restrict__ predg,
+__global__ __launch_bounds__(256) void k_key_unresid_colg(int H, int W, const int* __restrict__ idx, const uint8_t* __restrict__ pred,
                                                           const unsigned long long* __restrict__ off, const uint8_t* __restrict__ tmp,
                                                           uint8_t* __restrict__ frames) {
     const int key = blockIdx.y, lane = threadIdx.x & 63;
-    if ((predg[key] & 6u) != 6u) return;   // (workgroup-uniform)
+    if ((pred[key] & 6u) != 6u) return;   // (workgroup-uniform)
     const int c0 = (int)(blockIdx.x * 256 + (threadIdx.x & ~63u));   // the wave's first column
     if (c0 >= W) return;                   // (wave-uniform)
     const int col = c0 + lane, ncols = min(64, W - c0);
@@ -4360,18 +4271,21 @@ __global__ __launch_bounds__(256) void k_keyg_unresid_col(int H, int W, const in
     }
 }
 
-// d_pred3: the predictor ids with 0 for every GRAY frame (k_key_unresid_col skips those); d_tmp: one byte per symbol
-int tzk_keyg_unresid(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_predg, const uint8_t* d_pred3,
-                     const unsigned long long* d_off, int nkeys, uint8_t* d_tmp, uint8_t* d_frames) {
+// d_tmp: scratch of one byte per symbol for the GRAY frames' column pass, or NULL when no frame has (pred & 6) == 6 -- the host
+// knows the pred bytes -- and k_key_unresid_colg has nothing to do
+int tzk_key_unresid(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_pred, const unsigned long long* d_off,
+                    int nkeys, uint8_t* d_tmp, uint8_t* d_frames) {
     tz_prof_scope ps(ctx, TZP_HUFF);
-    hipLaunchKernelGGL(k_keyg_unresid_row, dim3((unsigned)((H + 3) / 4), (unsigned)nkeys), dim3(256), 0, ctx->stream, d_sym, H, W, d_idx, d_predg,
+    hipLaunchKernelGGL(k_key_unresid_row, dim3((unsigned)((H + 3) / 4), (unsigned)nkeys), dim3(256), 0, ctx->stream, d_sym, H, W, d_idx, d_pred,
                        d_off, d_tmp, d_frames);
     TZ_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_keyg_unresid_col, dim3((unsigned)((W + 255) / 256), (unsigned)nkeys), dim3(256), 0, ctx->stream, H, W, d_idx, d_predg,
-                       d_off, d_tmp, d_frames);
-    TZ_HIP(ctx, hipGetLastError());
+    if (d_tmp) {
+        hipLaunchKernelGGL(k_key_unresid_colg, dim3((unsigned)((W + 255) / 256), (unsigned)nkeys), dim3(256), 0, ctx->stream, H, W, d_idx, d_pred,
+                           d_off, d_tmp, d_frames);
+        TZ_HIP(ctx, hipGetLastError());
+    }
     hipLaunchKernelGGL(k_key_unresid_col, dim3((unsigned)(((size_t)W * 3 + 255) / 256), (unsigned)nkeys), dim3(256), 0, ctx->stream, H, W, d_idx,
-                       d_pred3, d_frames);
+                       d_pred, d_frames);
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }

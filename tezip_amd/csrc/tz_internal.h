@@ -34,7 +34,7 @@ enum tz_prof_class {
     TZP_CARRY,      // prefix carry of the inverse scan (k_undelta_carry, tz_decode_range)
     TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality; k_ssim, tz_encode_ssim / tz_ssim_frames)
     TZP_HUFF,       // opt-in Huffman coder: k_huff_count / k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec (and k_huffr_*),
-                    // and the key-frame coder in front of it: k_key_hist / k_key_resid / k_key_unresid_*
+                    // and the key-frame coders in front of it: k_key_hist / k_key_gray / k_key_resid / k_key_unresid_*
     TZP_DIGEST,     // per-frame digests TZD64 (k_digest: tz_frame_digests, tz_decoded_digests, tz_encode_digests)
     TZP_COUNT
 };
@@ -364,19 +364,17 @@ int tzk_huff_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, in
                  const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words, int dist);
 int tzk_huff_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
                  const uint16_t* d_dec_tab4096, int A, int base, size_t n, int16_t* out, int dist);
-// key-frame coder (TZK1).  d_frames: a stack of H x W x 3 frames of which frame d_idx[k] is key frame k;
-// d_pred[k] its predictor id 0..3; d_sym: nkeys * H * W * 3 int16 symbols 0..255, key after key.
+// key-frame coders (TZK1, and TZK2 = TZK1 with a GRAY bit: DESIGN.md section 9).  d_frames: a stack of H x W x 3 frames of which
+// frame d_idx[k] is key frame k; d_pred[k] its pred byte: predictor id 0..3, | 4 for a GRAY frame (TZK2 alone), which has H * W
+// symbols instead of H * W * 3; d_sym: the int16 symbols 0..255, key after key; d_off[k]: where frame k's symbols start in d_sym
+// (u64 exclusive prefix of the per-frame counts; k * H * W * 3 without a GRAY frame); d_flags[k] != 0: not gray; d_tmp: scratch of
+// one byte per symbol, or NULL when no frame has (d_pred[k] & 6) == 6
 int tzk_key_hist(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, int nkeys, unsigned* d_counts /* [nkeys][4][256] */);
-int tzk_key_resid(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, int16_t* d_sym);
-int tzk_key_unresid(tz_ctx*, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_pred, int nkeys, uint8_t* d_frames);
-// the same with gray key frames stored once (TZK2).  d_predg[k]: predictor id | 4 for a GRAY frame, which has H * W symbols;
-// d_off[k]: where frame k's symbols start in d_sym (u64 exclusive prefix of the per-frame counts); d_flags[k] != 0: not gray;
-// d_pred3: d_predg with 0 for every GRAY frame; d_tmp: scratch of one byte per symbol
 int tzk_key_gray(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, int nkeys, unsigned* d_flags);
-int tzk_keyg_resid(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_predg,
-                   const unsigned long long* d_off, int nkeys, int16_t* d_sym);
-int tzk_keyg_unresid(tz_ctx*, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_predg, const uint8_t* d_pred3,
-                     const unsigned long long* d_off, int nkeys, uint8_t* d_tmp, uint8_t* d_frames);
+int tzk_key_resid(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_idx, const uint8_t* d_pred, const unsigned long long* d_off,
+                  int nkeys, int16_t* d_sym);
+int tzk_key_unresid(tz_ctx*, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_pred, const unsigned long long* d_off,
+                    int nkeys, uint8_t* d_tmp, uint8_t* d_frames);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,
             double* h_sse);
 int tzk_sse_blocks(int Hp, int Wp);

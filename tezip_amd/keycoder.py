@@ -1,5 +1,5 @@
 """The GPU-coded key_frame.dat (`--key-coder huff`; NOT a reference format): container, validation and a plain numpy
-statement of what the kernels k_key_hist / k_key_resid / k_key_unresid (csrc/tz_codec.hip) and the Huffman kernels behind
+statement of what the kernels k_key_hist / k_key_resid / k_key_unresid_row / k_key_unresid_col (csrc/tz_codec.hip) and the Huffman kernels behind
 them write and read.  The slow functions here are the specification the kernels are tested against
 (tests/test_keycoder.py, tests/test_gpu_keycoder.py); the product calls only the container, `choose_predictors` and `parse`.
 DESIGN.md section 9 holds the format as prose.
@@ -62,7 +62,7 @@ def residual(frame, pred):
 
 def unresidual(sym, pred, H, W):
     """The inverse of residual: prefix sums mod 256 along the rows (1), the columns (2) or both (3) -> uint8 (H, W, 3).
-    Only the low byte of a symbol counts, as in k_key_unresid."""
+    Only the low byte of a symbol counts, as in k_key_unresid_row."""
     if not 0 <= int(pred) < NPRED:
         raise ValueError("key_frame.dat (huff): predictor id %d outside [0, 3]" % int(pred))
     r = (np.asarray(sym, np.int64).reshape(H, W, 3)) & 255

@@ -1,5 +1,5 @@
 """The GPU-coded key_frame.dat that stores a gray key frame once (`--key-coder huffg`; NOT a reference format): container,
-validation and a plain numpy statement of what the kernels k_key_gray / k_keyg_resid / k_keyg_unresid_* (csrc/tz_codec.hip)
+validation and a plain numpy statement of what the kernels k_key_gray / k_key_resid / k_key_unresid_* (csrc/tz_codec.hip)
 and the Huffman kernels behind them write and read.  The slow functions here are the specification the kernels are tested
 against (tests/test_keycoderg.py, tests/test_gpu_keycoderg.py); the product calls only the container, `pred_bytes`,
 `chosen_counts` and `parse`.  DESIGN.md section 9 holds the format as prose.
