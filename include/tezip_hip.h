@@ -335,6 +335,30 @@ int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t payload_len, con
 int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
                       int shuffled, tz_frame_quality* out);
 
+/* ---- the bound for a PSNR target (no reference counterpart; `tezip.py -c --target-psnr DB`; definition TZ-TPSNR-1 in DESIGN.md
+ * section 9 and tezip_amd/target.py) ------------------------------------------------------------------------------------------
+ * tz_bound_probe: one candidate bound.  On the context's ENCODER rollout (state rules and errors are tz_encode_quality's; an
+ * unknown mode, a NaN or a refused negative bound are TZ_ERR_INVALID as in tz_encode) out[f] is, field for field, what
+ * tz_encode(ctx, mode, b0, b1, ...) followed by tz_encode_quality would report for frame f.  The predictions do not depend on
+ * the bound, so one rollout serves any number of probes.  A probe forms the delta stack, sends a copy of it through the
+ * quantiser and compares the two against the originals in one pass (k_bound_err, profiling class "quality"): no spatial
+ * delta, histogram, table or payload is made and nothing but the records leaves the device.
+ *  out: nt records, host or device; complete on return.
+ * The quantiser is the three-channel one in every layout.  Under tz_set_delta_stride(ctx, 1) the records are unchanged (the
+ * spatial delta is lossless).  Under tz_set_payload_channels(ctx, 1) they describe the one-channel job, as tz_encode_quality
+ * does: that job stores channel 0's quantised delta alone and its decoder writes channel 0's reconstruction to all three
+ * channels, so the kernel takes channel 0's error for every channel of a pixel (the model's three output channels differ
+ * even on a gray source: the three-channel job's records are NOT the one-channel job's); a stack with colour is refused as
+ * tz_encode refuses it (TZ_ERR_INVALID).  Nothing of the context changes: a resident payload, its kind, predictions, frames
+ * and rollout state are as they were. */
+int tz_bound_probe(tz_ctx* ctx, int mode, double b0, double b1, tz_frame_quality* out);
+/* tz_bound_err: the kernel of tz_bound_probe alone, over any three unpadded stacks of nframes frames of frame_elems
+ * elements, host or device: per element e = clamp(orig + delta - qdelta, 0, 255) - orig, per frame sum e^2, max |e| and the
+ * count of e != 0.  nframes <= 0 or frame_elems == 0 does nothing.  Under tz_set_payload_channels(ctx, 1) it is the one-channel
+ * form: element i of a frame counts only where i % 3 == 0, three times (frame_elems % 3 != 0: TZ_ERR_INVALID). */
+int tz_bound_err(tz_ctx* ctx, const uint8_t* orig, const int16_t* delta, const int16_t* qdelta, int nframes,
+                 size_t frame_elems, tz_frame_quality* out);
+
 /* ---- per-frame digests (no reference counterpart; `tezip.py -c --digests`, `-u --verify`; format TZD64 version 1 in
  * DESIGN.md section 9, slow statement of it in tezip_amd/digest.py) ------------------------------------------------------
  * For a frame of n bytes x[0..n) in (H, W, 3) memory order, all arithmetic mod 2^64:

@@ -58,6 +58,8 @@ _SIGS = {
     "tz_decode_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tz_encode_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_encode_digests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_bound_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "tz_bound_err": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     "tz_frame_digests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     "tz_ssim_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tz_encode_ssim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -708,6 +710,29 @@ class Context:
         tb = None if table is None else np.ascontiguousarray(table, np.int16)
         self._ck(self.lib.tz_encode_quality(self.h, None if resident else _ptr(payload), n, _ptr(tb), tl, int(bool(shuffle)),
                                             out.ctypes.data))
+        return out
+
+    # ---- the bound for a PSNR target (definition TZ-TPSNR-1: tezip_amd/target.py)
+    def bound_probe(self, mode, bound):
+        """tz_bound_probe after rollout: the QUALITY_DTYPE records (nt entries) that encode(mode, bound) + encode_quality
+        would give, without a payload, in the payload layout in force (set_payload_channels(1): the one-channel job's, and
+        a stack with colour is refused as encode refuses it).  Nothing of the context changes."""
+        nt, h, w = self._shape
+        b0, b1 = _bounds(bound)
+        out = np.zeros(nt, QUALITY_DTYPE)
+        self._ck(self.lib.tz_bound_probe(self.h, MODES[mode], b0, b1, out.ctypes.data))
+        return out
+
+    def bound_err(self, orig, delta, qdelta, nframes, frame_elems):
+        """tz_bound_err: k_bound_err over three stacks of nframes x frame_elems elements (uint8, int16, int16; host arrays
+        or device tensors): QUALITY_DTYPE[nframes].  After set_payload_channels(1): the one-channel form (target.errors_of
+        with channels=1 on gray originals)."""
+        n = int(nframes) * int(frame_elems)
+        if not (_numel(orig) == _numel(delta) == _numel(qdelta) == n):
+            raise ValueError("stacks hold %d, %d and %d elements, expected %d" % (_numel(orig), _numel(delta), _numel(qdelta), n))
+        out = np.zeros(max(int(nframes), 0), QUALITY_DTYPE)
+        self._ck(self.lib.tz_bound_err(self.h, _ptr(orig), _ptr(delta), _ptr(qdelta), int(nframes), int(frame_elems),
+                                       out.ctypes.data))
         return out
 
     # ---- structural similarity (definition TZ-SSIM-1: tezip_amd/ssim.py)

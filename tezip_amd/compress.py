@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, quality, sdelta, sidecar, weights, zstd
+from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, quality, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -484,11 +484,13 @@ def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
 
 
 SSIM_NEEDS_REPORT = "--ssim extends the compression report: add --report"
+TARGET_NEEDS_ABS = "--target-psnr finds the abs bound itself: it takes the place of -m and -b"
+TARGET_NOT_SHARDED = "--target-psnr is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
 
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
-        SSIM=False):
+        SSIM=False, TARGET_PSNR=None):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -521,6 +523,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     SSIM (--ssim; NOT in the reference; with REPORT only): the report also carries the structural similarity of what the
     stored payload decodes to against the sources (definition TZ-SSIM-1: tezip_amd/ssim.py), from one tz_encode_ssim call on
     the same resident payload; a fourth line is printed.  Every other file is what it is without it.
+    TARGET_PSNR (--target-psnr; NOT in the reference; MODE "abs" and an empty BOUND_VALUE): the abs bound is found on the device
+    after the rollout (definition TZ-TPSNR-1: tezip_amd/target.py; at most 9 tz_bound_probe calls on the one rollout) and the job
+    goes on as `-m abs -b <found>`: every file is what that job writes, one line says what was found, and bound_search.json
+    (target, limit, the probes, the result) is written besides.  Works with every other flag above.  Single-GPU jobs only.
+    With VERBOSE the quantiser time printed as error_bound includes the probes'.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -537,6 +544,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if SSIM and not REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         print("ERROR:", SSIM_NEEDS_REPORT)
         sys.exit(2)
+    if TARGET_PSNR is not None:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
+        problem = (target.check_target(TARGET_PSNR) or (TARGET_NEEDS_ABS if MODE != "abs" or BOUND_VALUE else None)
+                   or (TARGET_NOT_SHARDED if tzdist.active() is not None else None))
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     if tzdist.active() is not None:
         if REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
             print("ERROR: --report is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU")
@@ -585,6 +598,14 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                         print("move key point")
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
             stages.mark("rollout", ctx)
+            if TARGET_PSNR is not None:   # one rollout serves every candidate: the predictions do not depend on the bound
+                # (a probe describes the job in the payload layout decide_gray left in force: the one-channel job's own SSE)
+                limit = target.sse_limit(TARGET_PSNR, nt * H * W * 3)
+                k, trace = target.search(lambda c: int(ctx.bound_probe("abs", [target.bound_of(c)])["sse"].sum()), limit)
+                search_doc = target.make(TARGET_PSNR, nt * H * W * 3, limit, trace, k)
+                BOUND_VALUE = [target.bound_of(k)]
+                print(target.stdout_line(search_doc))
+                stages.mark("bound search (device)")
             _, table, _ = ctx.encode(MODE, BOUND_VALUE, ENTROPY_RUN, payload="resident", shuffle=SHUFFLE)
             stages.mark("encode (payload resident)", ctx)
             if REPORT:   # stream-ordered before _stream_outputs fetches the payload; changes nothing it reads
@@ -628,6 +649,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 quality.write(OUTPUT_DIR, report)
                 for line in quality.stdout_lines(report):
                     print(line)
+            if TARGET_PSNR is not None:
+                target.write(OUTPUT_DIR, search_doc)
             if DIGESTS:  # last: every other file is what it is without the flag
                 digest.write(OUTPUT_DIR, digest.make(dig[0], dig[1], (H, W, 3)))
         finally:

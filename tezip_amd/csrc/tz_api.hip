@@ -2054,6 +2054,70 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
     return rc;
 }
 
+// One candidate bound of `-c --target-psnr` (TZ-TPSNR-1): the records tz_encode(mode, b0, b1) + tz_encode_quality would give,
+// from the delta stack, a quantised copy of it and k_bound_err -- no spatial delta, histogram, table or payload.  The mask
+// that zeroes a frame's delta (group_first) and the frames the quantiser skips (quant_skip) are the encoder's own; a frame
+// they leave with q == d reconstructs to its original, which is what the decoder's key bytes and C0 slots give.
+// Under a one-channel payload the job stores channel 0 alone and its decoder writes that reconstruction to all three
+// channels: tz_encode's refusal of a stack with colour comes first, and the kernel counts channel 0 three times.  (The
+// model's three output channels differ even on a gray source, so the three-channel records would be another job's.)
+extern "C" int tz_bound_probe(tz_ctx* ctx, int mode, double b0, double b1, tz_frame_quality* out) {
+    tz_roctx_range roctx_("tz_bound_probe");
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    TZ_TRY(encode_check(ctx, "tz_bound_probe", mode));
+    const int channels = layout_of(ctx).channels;
+    if (channels == 1) {
+        const int rc_gray = encode_all_gray(ctx);
+        tz_pool_release_all(ctx);
+        TZ_TRY(rc_gray);
+    }
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
+    const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe;
+    std::vector<tz_out> outs;
+    tz_out o;
+    void *d_mask = nullptr, *d_delta = nullptr, *d_q = nullptr;
+    int rc = tz_pool_alloc(ctx, nt, &d_mask);
+    if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, ctx->group_first.data(), nt);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N * 2, &d_delta);
+    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N * 2, &d_q);
+    if (rc == TZ_OK) rc = tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta);
+    if (rc == TZ_OK && hipMemcpyAsync(d_q, d_delta, N * 2, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        rc = tz_fail(ctx, TZ_ERR_HIP, "tz_bound_probe: copy of the delta stack failed");
+    if (rc == TZ_OK) rc = tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_quality) * nt, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    if (rc == TZ_OK) rc = tzk_bound_err(ctx, channels, ctx->d_frames, (const int16_t*)d_delta, (const int16_t*)d_q, nt, fe, (tz_frame_quality*)o.dev);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device records too: complete on return)
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
+// k_bound_err alone, on any three stacks (tests against tezip_amd/target.py errors_of), in the form the context's payload
+// channels select.
+extern "C" int tz_bound_err(tz_ctx* ctx, const uint8_t* orig, const int16_t* delta, const int16_t* qdelta, int nframes,
+                            size_t frame_elems, tz_frame_quality* out) {
+    tz_roctx_range roctx_("tz_bound_err");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (nframes <= 0 || frame_elems == 0) return TZ_OK;
+    if (!orig || !delta || !qdelta || !out) return TZ_ERR_INVALID;
+    const size_t n = (size_t)nframes * frame_elems;
+    std::vector<tz_out> outs;
+    tz_out o;
+    const void *d_o = nullptr, *d_d = nullptr, *d_q = nullptr;
+    int rc = tz_dev_in(ctx, orig, n, &d_o);
+    if (rc == TZ_OK) rc = tz_dev_in(ctx, delta, n * 2, &d_d);
+    if (rc == TZ_OK) rc = tz_dev_in(ctx, qdelta, n * 2, &d_q);
+    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_quality) * nframes, &o);
+    if (rc == TZ_OK) outs.push_back(o);
+    if (rc == TZ_OK) rc = tzk_bound_err(ctx, ctx->payload_channels, (const uint8_t*)d_o, (const int16_t*)d_d, (const int16_t*)d_q, nframes, frame_elems,
+                                         (tz_frame_quality*)o.dev);
+    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
+    tz_pool_release_all(ctx);
+    return rc;
+}
+
 // The records of `-c --digests`: k_digest of the decoded stack, and of the resident originals when asked for.
 extern "C" int tz_encode_digests(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
                                  int shuffled, unsigned long long* decoded, unsigned long long* original) {

@@ -2956,6 +2956,169 @@ int tzk_quality(tz_ctx* ctx, const uint8_t* orig, const uint8_t* dec, int nframe
     return TZ_OK;
 }
 
+// ------------------------------------------------------------------- error of a candidate bound
+// tz_bound_probe / tz_bound_err (TZ-TPSNR-1; slow statement in tezip_amd/target.py errors_of): what
+// tz_encode_quality would report for a quantised delta stack, without a decoded stack in memory.  Per element of the
+// unpadded stacks orig (uint8), d (the deltas of tzk_delta) and q (d behind the quantiser):
+//   xh = orig + d  (the integer prediction the decoder reconstructs from; a masked frame has d = q = 0, and there the
+//                   decoder's base is the key byte = orig, the same sum),  r = clamp(xh - q, 0, 255)  (k_recon),  e = r - orig
+// and per frame sum e^2, max |e| and #(e != 0): k_recon plus k_quality in one pass, 5 B read per element and nothing
+// written but the records.  Shaped like k_quality, whose records and flush it shares: a workgroup owns a contiguous run of
+// whole tiles (256 lanes x 8 elements: one 16-byte load of d and of q, one 8-byte load of orig), cut without regard to
+// frame boundaries; the next tile's loads are in flight while the current one is summed; where a tile crosses a frame's end
+// the workgroup flushes (qy_flush: shuffle, LDS, one set of relaxed agent-scope atomics per frame it touched).  Tiles start
+// at the first element `head` at which orig is 8-byte and d and q are 16-byte aligned; workgroup 0 adds the elements in
+// front of it one by one; stacks that share no such element take element loads throughout (VEC = false).  A lane's
+// loads are whole or, at the end of the run, element by element under `end`: nothing outside the stacks is read.
+// GRAY: the records of a one-channel payload (tz_set_payload_channels(1)), whose decoder reconstructs channel 0 and writes
+// the sample to all three channels (k_recon_gray) of a frame whose originals have three equal channels: the error of every
+// channel is channel 0's, so only the elements with index % 3 == 0 count (fe is a multiple of 3: a frame starts a pixel),
+// and their squares and their count go in three times.
+static constexpr int BE_TILE = 256 * 8;   // elements per workgroup and step
+
+// elements e .. e+7: orig packed 4 per word, d and q 2 per word; 0 in all three for those at or behind `end`
+struct BeRaw {
+    uint4 d, q;
+    uint2 o;
+};
+
+template <bool VEC>
+__device__ __forceinline__ BeRaw be_fetch(const uint8_t* __restrict__ orig, const int16_t* __restrict__ d, const int16_t* __restrict__ q,
+                                          size_t e, size_t end) {
+    BeRaw r;
+    if (VEC && e + 8 <= end) {
+        r.o = *(const uint2*)(orig + e);
+        r.d = *(const uint4*)(d + e);
+        r.q = *(const uint4*)(q + e);
+    } else {
+        unsigned ow[2] = {0, 0}, dw[4] = {0, 0, 0, 0}, qw[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (e + j < end) {
+                ow[j >> 2] |= (unsigned)orig[e + j] << (8 * (j & 3));
+                dw[j >> 1] |= (unsigned)(unsigned short)d[e + j] << (16 * (j & 1));
+                qw[j >> 1] |= (unsigned)(unsigned short)q[e + j] << (16 * (j & 1));
+            }
+        r.o = make_uint2(ow[0], ow[1]);
+        r.d = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+        r.q = make_uint4(qw[0], qw[1], qw[2], qw[3]);
+    }
+    return r;
+}
+
+// one element: |clamp(orig + d - q, 0, 255) - orig|
+__device__ __forceinline__ unsigned be_abs1(int o, int d, int q) {
+    int r = o + d - q;
+    r = r < 0 ? 0 : (r > 255 ? 255 : r);
+    const int e = r - o;
+    return (unsigned)(e < 0 ? -e : e);
+}
+
+// e: the stack index of the lane's first element (GRAY: elements of channels 1 and 2 give 0)
+template <bool GRAY>
+__device__ __forceinline__ void be_abserr(const BeRaw& r, size_t e, unsigned ad[8]) {
+    const unsigned ow[2] = {r.o.x, r.o.y}, dw[4] = {r.d.x, r.d.y, r.d.z, r.d.w}, qw[4] = {r.q.x, r.q.y, r.q.z, r.q.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        ad[j] = be_abs1((int)((ow[j >> 2] >> (8 * (j & 3))) & 0xffu), (int)(short)(dw[j >> 1] >> (16 * (j & 1))),
+                        (int)(short)(qw[j >> 1] >> (16 * (j & 1))));
+    if (GRAY) {
+        const unsigned c0 = (unsigned)(e % 3);   // channel of element e
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if ((c0 + j) % 3 != 0) ad[j] = 0;
+    }
+}
+
+// per_block: elements per workgroup, a multiple of BE_TILE; tiles start at `head`
+template <bool VEC, bool GRAY>
+__global__ __launch_bounds__(256) void k_bound_err(const uint8_t* __restrict__ orig, const int16_t* __restrict__ d,
+                                                   const int16_t* __restrict__ q, size_t n, size_t fe, unsigned head, size_t per_block,
+                                                   tz_frame_quality* __restrict__ out) {
+    __shared__ QyPart red[4];
+    constexpr unsigned WT = GRAY ? 3 : 1;           // how often an element that counts is counted
+    if (blockIdx.x == 0 && threadIdx.x < head) {   // in front of the first aligned element: one by one
+        const size_t i = threadIdx.x;
+        const unsigned a = (GRAY && i % 3 != 0) ? 0u : be_abs1((int)orig[i], (int)d[i], (int)q[i]);
+        if (a != 0) {
+            unsigned long long s = (unsigned long long)(a * a * WT);
+            unsigned m = a, c = WT;
+            qy_add(&s, &m, &c, out + i / fe);
+        }
+    }
+    const size_t b0 = head + (size_t)blockIdx.x * per_block;
+    if (b0 >= n) return;   // (workgroup-uniform)
+    const size_t b1 = min(n, b0 + per_block);
+    size_t f = b0 / fe;                          // the frame the running sums belong to
+    unsigned long long sse = 0;
+    unsigned mx = 0, cnt = 0;
+    BeRaw cur = be_fetch<VEC>(orig, d, q, b0 + (size_t)threadIdx.x * 8, min(b1, b0 + (size_t)BE_TILE));
+    for (size_t t = b0; t < b1; t += BE_TILE) {
+        const size_t tend = min(b1, t + (size_t)BE_TILE), e = t + (size_t)threadIdx.x * 8;
+        BeRaw nxt{};   // the next tile's loads are in flight while this one is summed
+        if (tend < b1) nxt = be_fetch<VEC>(orig, d, q, e + BE_TILE, min(b1, tend + (size_t)BE_TILE));
+        unsigned ad[8];
+        be_abserr<GRAY>(cur, e, ad);
+        cur = nxt;
+        for (size_t lo = t;;) {                  // segments [lo, lim) of the tile inside frame f
+            const size_t bnd = (f + 1) * fe, lim = min(bnd, tend);
+            unsigned s = 0, m = 0, c = 0;        // (8 x 255^2 fits)
+            if (lo == t && lim == tend) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    s += ad[j] * ad[j];
+                    m = max(m, ad[j]);
+                    c += ad[j] != 0;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const unsigned v = (e + j >= lo && e + j < lim) ? ad[j] : 0u;
+                    s += v * v;
+                    m = max(m, v);
+                    c += v != 0;
+                }
+            }
+            sse += s * WT;
+            mx = max(mx, m);
+            cnt += c * WT;
+            if (lim < bnd) break;                // frame f goes on behind this tile
+            qy_flush(sse, mx, cnt, red, out + f);
+            sse = 0;
+            mx = cnt = 0;
+            ++f;
+            lo = lim;
+            if (lo >= tend) break;
+        }
+    }
+    if (f * fe < n) qy_flush(sse, mx, cnt, red, out + f);
+}
+
+int tzk_bound_err(tz_ctx* ctx, int channels, const uint8_t* orig, const int16_t* d, const int16_t* q, int nframes, size_t fe,
+                  tz_frame_quality* d_out) {
+    if (nframes <= 0 || fe == 0) return TZ_OK;
+    if (channels == 1 && fe % 3) return tz_fail(ctx, TZ_ERR_INVALID, "frames of %zu elements: a one-channel payload describes whole pixels", fe);
+    const size_t n = (size_t)nframes * fe;
+    TZ_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(tz_frame_quality) * nframes, ctx->stream));
+    const unsigned h = (unsigned)((8 - ((uintptr_t)orig & 7)) & 7);   // the first element at which orig is 8-byte aligned
+    const bool vec = ((((uintptr_t)d + 2 * h) | ((uintptr_t)q + 2 * h)) & 15) == 0;
+    const unsigned head = vec ? (unsigned)std::min<size_t>(n, h) : 0u;
+    const size_t tiles = std::max<size_t>(1, (n - head + BE_TILE - 1) / BE_TILE);
+    size_t G = std::min<size_t>((size_t)grid_for(tiles, 1), tiles);
+    const size_t per_block = (tiles + G - 1) / G * BE_TILE;
+    G = std::max<size_t>(1, (n - head + per_block - 1) / per_block);   // (no workgroup without a tile)
+    tz_prof_scope ps(ctx, TZP_QUALITY);
+#define TZ_BE_LAUNCH(V, GR) \
+    hipLaunchKernelGGL((k_bound_err<V, GR>), dim3((unsigned)G), dim3(256), 0, ctx->stream, orig, d, q, n, fe, head, per_block, d_out)
+    if (vec && channels == 1) TZ_BE_LAUNCH(true, true);
+    else if (vec) TZ_BE_LAUNCH(true, false);
+    else if (channels == 1) TZ_BE_LAUNCH(false, true);
+    else TZ_BE_LAUNCH(false, false);
+#undef TZ_BE_LAUNCH
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // ------------------------------------------------------------------------------ frame digests
 // TZD64 version 1 (slow statement in tezip_amd/digest.py): per frame of an unpadded uint8 stack the
 // sum mod 2^64 over its bytes of mix(256 * i + x[i]), i the byte's position inside ITS frame and mix splitmix64's output

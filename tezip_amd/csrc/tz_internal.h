@@ -32,7 +32,8 @@ enum tz_prof_class {
     TZP_TABLE,      // HOST time: rank table + LUT from the downloaded histogram (compress.py:356-361)
     TZP_QSERIAL,    // not a time: `launches` counts the chains the quantiser sent through its serial fallback (k_q_serial)
     TZP_CARRY,      // prefix carry of the inverse scan (k_undelta_carry, tz_decode_range)
-    TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality; k_ssim, tz_encode_ssim / tz_ssim_frames)
+    TZP_QUALITY,    // reconstruction statistics of an encode (k_quality, tz_encode_quality; k_ssim, tz_encode_ssim / tz_ssim_frames;
+                    // k_bound_err, tz_bound_probe / tz_bound_err)
     TZP_HUFF,       // opt-in Huffman coder: k_huff_count / k_huff_size / k_huff_scan / k_huff_enc / k_huff_dec (and k_huffr_*),
                     // and the key-frame coders in front of it: k_key_hist / k_key_gray / k_key_resid / k_key_unresid_*
     TZP_DIGEST,     // per-frame digests TZD64 (k_digest: tz_frame_digests, tz_decoded_digests, tz_encode_digests)
@@ -336,6 +337,10 @@ int tzk_decode_tail(tz_ctx*, tz_layout, const int16_t* in, const int16_t* h_lut2
                     uint8_t* out);
 // per-frame (sse, max |dec - orig|, #changed) of two unpadded nframes x fe uint8 stacks; d_out (device) is cleared here
 int tzk_quality(tz_ctx*, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out);
+// the same records for what the quantised deltas q of the deltas d (tzk_delta's, int16, unpadded like orig) reconstruct to:
+// clamp(orig + d - q, 0, 255) against orig, with no decoded stack in memory (k_bound_err); d_out (device) is cleared here.
+// channels 1: what a one-channel payload decodes to -- channel 0's reconstruction in all three channels (fe % 3 == 0)
+int tzk_bound_err(tz_ctx*, int channels, const uint8_t* orig, const int16_t* d, const int16_t* q, int nframes, size_t fe, tz_frame_quality* d_out);
 // TZD64 digests of nframes frames of fe bytes (fe < 2^32, else TZ_ERR_INVALID before any launch); d_out: nframes words, cleared here
 int tzk_digest(tz_ctx*, const uint8_t* x, int nframes, size_t fe, unsigned long long* d_out);
 // TZ-SSIM-1 records of two unpadded nframes x H x W x 3 uint8 stacks (a frame of 2^32 bytes or more: TZ_ERR_INVALID before any

@@ -15,7 +15,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "tezip_amd"
 
-from . import compress, decompress, train  # noqa: E402
+from . import compress, decompress, target, train  # noqa: E402
 
 # (short, long, argparse keywords) -- tezip.py:88-99
 FLAG_TABLE = (
@@ -75,6 +75,11 @@ FLAG_TABLE = (
     # of the pixel in front (tezip_amd/sdelta.py; smaller on colour jobs, LARGER on a gray source stored with three channels: use
     # --gray there; the reference cannot read such a file, -u recognises it by the mark in its trailer)
     (None, "--sdelta", dict(type=str, choices=("flat", "channel"), default=None, dest="sdelta")),
+    # not in the reference: with -c, IN PLACE of -m and -b: the job is `-m abs -b E` with the E (a multiple of 0.5) that a
+    # bisection over the GPU's exact error sums finds for a sequence PSNR of at least DB (definition TZ-TPSNR-1 in
+    # tezip_amd/target.py: one rollout, at most 9 probes; a boundary, not necessarily the largest such bound).  Also writes
+    # bound_search.json (compress.run(TARGET_PSNR=...))
+    (None, "--target-psnr", dict(type=float, default=None, metavar="DB", dest="target_psnr")),
 )
 
 TEXT = {
@@ -224,6 +229,23 @@ def check_sdelta_flag(arg):
     return compress.check_sdelta(mode, int(os.environ.get("WORLD_SIZE", "1")) > 1)
 
 
+def check_target_flag(arg):
+    """--target-psnr is valid with -c of one single-GPU job, in place of -m and -b, without --sweep.  Returns None, or the
+    message of a refusal."""
+    db = getattr(arg, "target_psnr", None)
+    if db is None:
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--target-psnr is valid with -c (--compress) only"
+    if getattr(arg, "sweep", None) is not None:
+        return "--target-psnr cannot be combined with --sweep"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return compress.TARGET_NOT_SHARDED
+    if arg.mode is not None or arg.bound is not None:
+        return compress.TARGET_NEEDS_ABS
+    return target.check_target(db)
+
+
 def check_verify_flag(arg):
     """--verify is valid with -u only; `require` needs frame_digests.json in the directory and one GPU.  Returns None, or the
     message of a refusal."""
@@ -313,6 +335,10 @@ def _main(arg):
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_target_flag(arg)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # launched by torch.distributed.run: one rank per GPU
         from . import dist as tzdist
         tzdist.init_from_env()
@@ -335,7 +361,11 @@ def _main(arg):
             return decompress.run(model, src, dst, gpu, arg.verbose, frames=frames)
         return decompress.run(model, src, dst, gpu, arg.verbose)
     print("compress mode")
-    problem = check_compress(arg)
+    db = getattr(arg, "target_psnr", None)
+    if db is not None:   # the job is an `abs` job whose bound is still to be found: the same checks, and `abs` is printed
+        problem = check_compress(argparse.Namespace(**dict(vars(arg), mode=["abs"], bound=[0.0])))
+    else:
+        problem = check_compress(arg)
     if problem:
         return complain(problem)
     model, src, dst = arg.compress
@@ -345,6 +375,12 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if db is not None:   # (every other flag travels with it; the jobs without it are the calls below)
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), GRAY=bool(getattr(arg, "gray", False)),
+                            SDELTA=getattr(arg, "sdelta", None) or "flat", SSIM=bool(getattr(arg, "ssim", False)), TARGET_PSNR=db)
     if getattr(arg, "sdelta", None) == "channel":   # (flat is the job without the flag: the calls below)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
