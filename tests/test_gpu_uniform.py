@@ -28,18 +28,30 @@ pytestmark = pytest.mark.gpu
 
 DEFAULT = ((3, 48, 96, 192), None)
 OTHER = ((3, 32, 64), (3, 48, 32))      # R_stack_sizes != stack_sizes: 48-column A blocks (NT = 3), as tests/test_gpu_wino.py
+SATURATED_SIZE = 256                    # the smallest size of this file: its log reports uniform tiles for S4 and S16 there
 LOG_LINE = re.compile(r"uniform constants, level (\d+) (G0|C0|Ahat0) \((\d+)x(\d+)\): w (-?\d+), 16x16 tiles (\d+) uniform (\d+) non-uniform")
 
 
-def _spec(hp, wp, batch, bias, shape=DEFAULT):
-    """A job: `batch` windows, so many frames that the last call is a batch of one (whose taps the library holds)."""
-    return (shape, float(bias), hp, wp, batch, 3 if batch == 1 else batch + 1)
+def _spec(hp, wp, batch, bias, shape=DEFAULT, gain=1.0, seed=123):
+    """A job: `batch` windows, so many frames that the last call is a batch of one (whose taps the library holds).  `gain`
+    multiplies every weight array (tests/regimes.py: the saturated models)."""
+    return (shape, float(bias), hp, wp, batch, 3 if batch == 1 else batch + 1, float(gain), int(seed))
+
+
+def regime_spec(regime):
+    """A saturated model of tests/regimes.py at SATURATED_SIZE."""
+    import regimes
+    bias, gain = regimes.REGIMES[regime]
+    return _spec(SATURATED_SIZE, SATURATED_SIZE, 1, bias, gain=gain, seed=regimes.SEED)
 
 
 def _model(spec):
-    (stack, rstack), bias, hp, wp, _, n = spec
+    (stack, rstack), bias, hp, wp, _, n, gain, seed = spec
     cfg = PredNetConfig(stack_sizes=stack, R_stack_sizes=rstack)
-    w = cfg.init_weights(seed=123, bias_scale=bias)
+    w = cfg.init_weights(seed=seed, bias_scale=bias)
+    if gain != 1.0:
+        from regimes import scaled
+        w = scaled(w, gain)
     frames = np.random.default_rng(hp * 31 + wp).integers(0, 256, (n, hp, wp, 3)).astype(np.float32) / np.float32(255)
     return cfg, w, frames
 
@@ -96,7 +108,7 @@ def _oracle(spec):
     pred[-1], dbg = net.next(frames[-1], debug=True)
     ref = {"pred": pred}
     for l in range(cfg.nb_layers):
-        ref["e%d" % l], ref["r%d" % l] = dbg["e"][l], dbg["r"][l]
+        ref["e%d" % l], ref["r%d" % l], ref["c%d" % l] = dbg["e"][l], dbg["r"][l], dbg["c"][l]
     for v in ref.values():
         v.setflags(write=False)
     return ref
@@ -203,6 +215,30 @@ def test_split_gate_launches(epart, tmp_path, monkeypatch):
 def test_model_with_other_r_stack_sizes(tmp_path):
     spec = _spec(256, 256, 1, 0.1, OTHER)
     _check(spec, run_job(spec), tmp_path)
+
+
+@pytest.mark.parametrize("regime", ["S4", "S16"])
+def test_saturated_model_keeps_its_uniform_tiles(regime, tmp_path):
+    """The models of tests/regimes.py (every weight array times 4 / 16): G0 and C0 hold clipped gates and cell states past
+    tanh's polynomial branch, the per-frame values the clamp of Ahat_0.  k_uniform_ring compares bits, so it must measure
+    such constants as well as any: the default run, the run with per-pixel loads everywhere and the C oracle agree in every
+    BIT (a zero of the other sign would be a difference), and the log still reports shortcut tiles -- the substitute path
+    is what ran."""
+    from regimes import assert_same_bits
+    spec = regime_spec(regime)
+    cfg = _model(spec)[0]
+    got, err = _child(spec, tmp_path, "on", TEZIP_UNIFORM_LOG=1)
+    off = _check(spec, got, tmp_path)
+    want = _oracle(spec[:4] + (1,) + spec[5:])
+    for k in _names(cfg):
+        assert_same_bits(got[k], want[k], "%s against the C oracle: %s" % (regime, k))
+        assert_same_bits(got[k], off[k], "%s against TEZIP_UNIFORM=0: %s" % (regime, k))
+    assert (want["pred"] == 1.0).any() and (want["pred"] == 0.0).any()
+    rows = _log(err)
+    for key in sorted(rows):
+        print("level %d %s: %r" % (key + (rows[key],)))
+    assert sum(row["uniform"] for row in rows.values()) >= 1, rows
+    assert any(rows[(l, "G0")]["uniform"] >= 1 for l in range(cfg.nb_layers)), rows
 
 
 if __name__ == "__main__":   # the child process of _child: the job named on the command line, results into an .npz
