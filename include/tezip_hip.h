@@ -144,6 +144,11 @@ int tz_rollout_contract(tz_ctx* ctx);
  * of the launch `epoch_skew` launches ahead (never written when != 0) and give up after poll_limit polls (0 = built-in
  * 2^22), so that a test can see the failure path; (0, 0) restores normal operation. */
 int tz_scan_fault_inject(tz_ctx* ctx, unsigned epoch_skew, unsigned poll_limit);
+/* Diagnostic: the number of blocks of the context's device scratch pool that are handed out right now (TZ_ERR_INVALID without
+ * a context); *blocks (may be NULL) receives the number of blocks the pool holds.  Every entry point hands its blocks back
+ * on every path it leaves by, so between calls the answer is 0, and a pool that recycles does not grow from one job to the
+ * same job again.  Launches nothing. */
+int tz_pool_held(tz_ctx* ctx, int* blocks);
 /* Diagnostic: the device's own statement of the predictor's scalar functions (prednet.py:79-81,198-205: Keras
  * hard_sigmoid and tanh in the fixed arithmetic of DESIGN.md section 3) on n caller-chosen inputs, so that a test can
  * compare them bit for bit with the oracle's; recip_mismatches (may be NULL) receives the number of float32 values d in

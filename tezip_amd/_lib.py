@@ -44,6 +44,7 @@ _SIGS = {
     "tz_predict_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_set_conv_impl": (C.c_int, [C.c_void_p, C.c_int]),
     "tz_scan_fault_inject": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint]),
+    "tz_pool_held": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tz_set_contract": (C.c_int, [C.c_void_p, C.c_int]),
     "tz_get_contract": (C.c_int, [C.c_void_p]),
     "tz_rollout_contract": (C.c_int, [C.c_void_p]),
@@ -464,6 +465,14 @@ class Context:
     def scan_fault_inject(self, epoch_skew=0, poll_limit=0):
         """Diagnostic: make the inverse scan's bounded wait expire (see tz_scan_fault_inject); (0, 0) = normal."""
         self._ck(self.lib.tz_scan_fault_inject(self.h, int(epoch_skew), int(poll_limit)))
+
+    def pool_held(self):
+        """Diagnostic: (blocks of the device scratch pool handed out right now, blocks the pool holds); 0 between calls."""
+        blocks = C.c_int(0)
+        held = int(self.lib.tz_pool_held(self.h, C.byref(blocks)))
+        if held < 0:
+            self._ck(held)
+        return held, int(blocks.value)
 
     # ---- rollout + encode / decode
     @staticmethod

@@ -470,6 +470,15 @@ void tz_pool_release_all(tz_ctx* ctx) {
     for (auto& e : ctx->pool) e.second &= ~kPoolUsed;
 }
 
+// diagnostic: blocks of the scratch pool that are handed out right now (0 between calls), *blocks (may be NULL): all of them
+extern "C" int tz_pool_held(tz_ctx* ctx, int* blocks) {
+    if (!ctx) return TZ_ERR_INVALID;
+    int held = 0;
+    for (auto& e : ctx->pool) held += (e.second & kPoolUsed) != 0;
+    if (blocks) *blocks = (int)ctx->pool.size();
+    return held;
+}
+
 int tz_ensure(tz_ctx* ctx, void** buf, size_t* cap, size_t bytes) {
     if (*cap >= bytes && *buf) return TZ_OK;
     if (*buf) {
@@ -527,7 +536,7 @@ int tz_dev_out(tz_ctx* ctx, void* p, size_t bytes, tz_out* o) {
     return tz_pool_alloc(ctx, bytes, &o->dev);
 }
 
-int tz_dev_out_finish(tz_ctx* ctx, std::vector<tz_out>& outs) {
+int tz_call::finish() {
     bool any = false;
     for (auto& o : outs)
         if (o.host && o.bytes && !o.done) {
@@ -1136,6 +1145,123 @@ extern "C" int tz_payload_get(tz_ctx* ctx, size_t offset, size_t count, int16_t*
     return TZ_OK;
 }
 
+// SWP: window boundaries are known up front (compress.py:249: (idx-p) % w == 0), so all windows advance together.  The
+// prediction the reference makes and drops at a boundary (251-253) is only evaluated when the MSE log is wanted (-v prints
+// it, 245-247).  key, gfirst, c0_slots: what the warm-up left, completed here; mse: the log, when wanted.
+static int rollout_swp(tz_ctx* ctx, int window, bool want_mse, std::vector<int>& c0_slots, std::vector<uint8_t>& key,
+                       std::vector<uint8_t>& gfirst, std::vector<double>& mse) {
+    const int nt = ctx->nt, p = ctx->warm_up;
+    const size_t fe_pad = (size_t)ctx->Hp * ctx->Wp * 3;
+    std::vector<PredItem> items;
+    std::vector<int> dropped;
+    int key_idx = p + 1;
+    for (int idx = p + 1; idx < nt; ++idx) {
+        bool from_key = idx == key_idx;
+        if (from_key) key[idx - 1] = 1;
+        bool trig = (idx - p) % window == 0;
+        if (trig) gfirst[idx] = 1;
+        if (trig && !want_mse) {
+            c0_slots.push_back(idx);
+        } else {
+            items.push_back(PredItem{idx, from_key ? 1 : 0, idx - 1, idx - (key_idx - 1)});
+            if (trig && idx != nt - 1) dropped.push_back(idx);  // the last frame keeps it (260-262)
+        }
+        if (trig) {
+            if (idx == nt - 1) key[idx] = 1;  // compress.py:260-262
+            key_idx = idx + 1;
+        }
+    }
+    TZ_TRY(fill_c0(ctx, c0_slots));
+    TZ_TRY(run_schedule(ctx, items));
+    TZ_TRY(rollout_finish_upload(ctx));
+    if (!want_mse) return TZ_OK;
+    std::vector<double> sse(nt, 0.0);
+    TZ_TRY(tzk_sse(ctx, ctx->d_frames, ctx->d_pred, nt, ctx->H, ctx->W, ctx->Hp, ctx->Wp, sse.data()));
+    int k0 = p + 1;
+    double run = 0.0;
+    for (int idx = p + 1; idx < nt; ++idx) {
+        run = run + sse[idx];
+        mse[idx] = run / (double)((size_t)(idx - k0 + 1) * fe_pad);
+        if (gfirst[idx]) {
+            k0 = idx + 1;
+            run = 0.0;
+        }
+    }
+    return fill_c0(ctx, dropped);  // slot 0 of the next group holds C0 (258)
+}
+
+// DWP: boundaries depend on the window MSE of the padded frames (compress.py:245-249).  The decision is taken ON THE DEVICE
+// (k_sse_decide): it sums the frame's partial squared errors in the fixed order, compares the window mean with the
+// threshold, marks the key frame and writes the input selection of the next predictor step, so the host only queues
+// launches -- no round trip per frame -- and reads the key mask / MSE log once at the end.
+static int rollout_dwp(tz_call& call, double threshold, const std::vector<int>& c0_slots, std::vector<uint8_t>& key,
+                       std::vector<uint8_t>& gfirst, std::vector<double>& mse) {
+    tz_ctx* ctx = call.ctx;
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W, p = ctx->warm_up;
+    const size_t fe_pad = (size_t)ctx->Hp * ctx->Wp * 3;
+    TZ_TRY(fill_c0(ctx, c0_slots));
+    int Hp_, Wp_, maxB;
+    TZ_TRY(tz_model_dims(ctx, &Hp_, &Wp_, &maxB));
+    const int nblk = tzk_sse_blocks(ctx->Hp, ctx->Wp);
+    DwpState* d_state;
+    double *d_part, *d_mse;
+    uint8_t *d_key, *d_gf;
+    int *d_flag, *d_slot0;   // (d_slot0: one int 0 = "the prediction is the input of slot 0 of the next step")
+    unsigned* d_ticket;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_sched, &ctx->cap_sched, 3 * (size_t)maxB * sizeof(int)));
+    TZ_TRY(call.alloc(sizeof(DwpState), &d_state));
+    TZ_TRY(call.alloc(sizeof(double) * nblk, &d_part));
+    TZ_TRY(call.alloc(nt, &d_key));
+    TZ_TRY(call.alloc(nt, &d_gf));
+    TZ_TRY(call.alloc(sizeof(double) * nt, &d_mse));
+    TZ_TRY(call.alloc(sizeof(int) * nt, &d_flag));
+    TZ_TRY(call.alloc(256, &d_ticket));
+    TZ_TRY(call.alloc(256, &d_slot0));
+    TZ_TRY(tz_upload(ctx, d_key, key.data(), nt));
+    TZ_TRY(tz_upload(ctx, d_gf, gfirst.data(), nt));
+    hipError_t e = hipMemsetAsync(d_mse, 0, sizeof(double) * nt, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int) * nt, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_ticket, 0, 256, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_slot0, 0, 256, ctx->stream);
+    if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "DWP state: %s", hipGetErrorString(e));
+    const float* c0 = nullptr;
+    TZ_TRY(tz_model_c0_dev(ctx, &c0));
+    hipLaunchKernelGGL(k_dwp_init, dim3(1), dim3(1), 0, ctx->stream, d_state, p, nt, ctx->d_sched, maxB, d_key);
+    if (hipGetLastError() != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "k_dwp_init launch failed");
+    const int gx = (int)std::min<size_t>((fe_pad + 255) / 256, 1024);
+    bool prev_fused = false;
+    for (int idx = p + 1; idx < nt; ++idx) {
+        // the prediction kernel also writes the level-0 error maps of the NEXT step as if that step went on from this
+        // prediction (as in the static schedule); the next step's error unit then runs for a key-frame start only --
+        // which of the two it is, k_sse_decide says on the device
+        bool fused = false;
+        static const bool spec = !getenv("TEZIP_DWP_SPEC") || atoi(getenv("TEZIP_DWP_SPEC")) != 0;   // (0: measurements)
+        TZ_TRY(tz_model_predict_batch_dev(ctx, 1, ctx->d_sched, maxB, ctx->d_frames, H, W, ctx->d_pred, ctx->d_pred, 0,
+                                          spec ? (const int*)d_slot0 : nullptr, false, &fused, prev_fused));
+        prev_fused = fused;
+        {
+            tz_prof_scope ps(ctx, TZP_SSE);
+            hipLaunchKernelGGL(k_sse_decide, dim3(nblk), dim3(256), 0, ctx->stream, ctx->d_frames + (size_t)idx * H * W * 3,
+                               ctx->d_pred + (size_t)idx * fe_pad, H, W, ctx->Hp, ctx->Wp, nblk, d_part, d_ticket, d_state, idx, nt,
+                               (double)fe_pad, threshold, ctx->d_sched, maxB, d_key, d_gf, d_mse, d_flag);
+        }
+        if (hipGetLastError() != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "DWP launch failed");
+    }
+    // slot 0 of every group opened on the way holds C0 (258); the last frame keeps its prediction (260-262: k_sse_decide
+    // does not flag it)
+    if (nt > 1) {
+        static_assert(kMaxFrames <= 65535, "gridDim.y = nt");   // (rollout_setup refuses nt > kMaxFrames)
+        hipLaunchKernelGGL(k_bcast_frames_flagged, dim3(std::min(gx, 128), nt), dim3(256), 0, ctx->stream, c0, fe_pad, (const int*)d_flag, ctx->d_pred);
+        if (hipGetLastError() != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "DWP launch failed");
+    }
+    e = hipMemcpyAsync(key.data(), d_key, nt, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(gfirst.data(), d_gf, nt, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(mse.data(), d_mse, sizeof(double) * nt, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "DWP result download: %s", hipGetErrorString(e));
+    return TZ_OK;
+}
+
 extern "C" int tz_rollout(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window,
                           double threshold, uint8_t* key_mask, double* mse_log) {
     tz_roctx_range roctx_("tz_rollout");
@@ -1149,12 +1275,8 @@ extern "C" int tz_rollout(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int
     std::vector<int> first;  // SWP reads exactly the frames that start a window (compress.py:218-220)
     if (!dwp)
         for (int f = p; f < nt; f += window) first.push_back(f);
-    int rc = rollout_setup(ctx, frames, nt, H, W, warm_up, dwp ? nullptr : &first);
-    if (rc != TZ_OK) {
-        tz_pool_release_all(ctx);
-        return rc;
-    }
-    const bool want_mse = dwp || mse_log != nullptr;
+    tz_call call(ctx);
+    TZ_TRY(rollout_setup(ctx, frames, nt, H, W, warm_up, dwp ? nullptr : &first));
     std::vector<uint8_t> key(nt, 0), gfirst(nt, 0), qskip(nt, 0);
     std::vector<double> mse(nt, 0.0);
     std::vector<int> c0_slots;
@@ -1171,142 +1293,26 @@ extern "C" int tz_rollout(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int
     } else {
         c0_slots.push_back(0);
     }
-    const size_t fe_pad = (size_t)ctx->Hp * ctx->Wp * 3;
-    if (!dwp) {
-        // SWP: window boundaries are known up front (compress.py:249: (idx-p) % w == 0), so all
-        // windows advance together.  The prediction the reference makes and drops at a boundary
-        // (251-253) is only evaluated when the MSE log is wanted (-v prints it, 245-247).
-        std::vector<PredItem> items;
-        std::vector<int> dropped;
-        int key_idx = p + 1;
-        for (int idx = p + 1; idx < nt; ++idx) {
-            bool from_key = idx == key_idx;
-            if (from_key) key[idx - 1] = 1;
-            bool trig = (idx - p) % window == 0;
-            if (trig) gfirst[idx] = 1;
-            if (trig && !want_mse) {
-                c0_slots.push_back(idx);
-            } else {
-                items.push_back(PredItem{idx, from_key ? 1 : 0, idx - 1, idx - (key_idx - 1)});
-                if (trig && idx != nt - 1) dropped.push_back(idx);  // the last frame keeps it (260-262)
-            }
-            if (trig) {
-                if (idx == nt - 1) key[idx] = 1;  // compress.py:260-262
-                key_idx = idx + 1;
-            }
-        }
-        rc = fill_c0(ctx, c0_slots);
-        if (rc == TZ_OK) rc = run_schedule(ctx, items);
-        if (rc == TZ_OK) rc = rollout_finish_upload(ctx);
-        if (rc == TZ_OK && want_mse) {
-            std::vector<double> sse(nt, 0.0);
-            rc = tzk_sse(ctx, ctx->d_frames, ctx->d_pred, nt, H, W, ctx->Hp, ctx->Wp, sse.data());
-            int k0 = p + 1;
-            double run = 0.0;
-            for (int idx = p + 1; idx < nt && rc == TZ_OK; ++idx) {
-                run = run + sse[idx];
-                mse[idx] = run / (double)((size_t)(idx - k0 + 1) * fe_pad);
-                if (gfirst[idx]) {
-                    k0 = idx + 1;
-                    run = 0.0;
-                }
-            }
-            if (rc == TZ_OK) rc = fill_c0(ctx, dropped);  // slot 0 of the next group holds C0 (258)
-        }
-    } else {
-        // DWP: boundaries depend on the window MSE of the padded frames (compress.py:245-249).  The
-        // decision is taken ON THE DEVICE (k_dwp_decide): it sums the frame's partial squared errors
-        // in the fixed order, compares the window mean with the threshold, marks the key frame and
-        // writes the input selection of the next predictor step, so the host only queues launches
-        // -- no round trip per frame -- and reads the key mask / MSE log once at the end.
-        rc = fill_c0(ctx, c0_slots);
-        int Hp_, Wp_, maxB;
-        if (rc == TZ_OK) rc = tz_model_dims(ctx, &Hp_, &Wp_, &maxB);
-        const int nblk = tzk_sse_blocks(ctx->Hp, ctx->Wp);
-        void *d_state = nullptr, *d_part = nullptr, *d_key = nullptr, *d_gf = nullptr, *d_mse = nullptr, *d_flag = nullptr;
-        if (rc == TZ_OK) rc = tz_ensure(ctx, (void**)&ctx->d_sched, &ctx->cap_sched, 3 * (size_t)maxB * sizeof(int));
-        if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(DwpState), &d_state);
-        if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(double) * nblk, &d_part);
-        if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_key);
-        if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_gf);
-        if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(double) * nt, &d_mse);
-        if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(int) * nt, &d_flag);
-        void *d_ticket = nullptr, *d_slot0 = nullptr;   // (d_slot0: one int 0 = "the prediction is the input of slot 0 of the next step")
-        bool prev_fused = false;
-        if (rc == TZ_OK) rc = tz_pool_alloc(ctx, 256, &d_ticket);
-        if (rc == TZ_OK) rc = tz_pool_alloc(ctx, 256, &d_slot0);
-        if (rc == TZ_OK) rc = tz_upload(ctx, d_key, key.data(), nt);
-        if (rc == TZ_OK) rc = tz_upload(ctx, d_gf, gfirst.data(), nt);
-        if (rc == TZ_OK) {
-            hipError_t e = hipMemsetAsync(d_mse, 0, sizeof(double) * nt, ctx->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int) * nt, ctx->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(d_ticket, 0, 256, ctx->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(d_slot0, 0, 256, ctx->stream);
-            if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "DWP state: %s", hipGetErrorString(e));
-        }
-        const float* c0 = nullptr;
-        if (rc == TZ_OK) rc = tz_model_c0_dev(ctx, &c0);
-        if (rc == TZ_OK) {
-            hipLaunchKernelGGL(k_dwp_init, dim3(1), dim3(1), 0, ctx->stream, (DwpState*)d_state, p, nt, ctx->d_sched, maxB,
-                               (uint8_t*)d_key);
-            if (hipGetLastError() != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "k_dwp_init launch failed");
-        }
-        const int gx = (int)std::min<size_t>((fe_pad + 255) / 256, 1024);
-        for (int idx = p + 1; idx < nt && rc == TZ_OK; ++idx) {
-            // the prediction kernel also writes the level-0 error maps of the NEXT step as if that step went on from this
-            // prediction (as in the static schedule); the next step's error unit then runs for a key-frame start only --
-            // which of the two it is, k_sse_decide says on the device
-            bool fused = false;
-            static const bool spec = !getenv("TEZIP_DWP_SPEC") || atoi(getenv("TEZIP_DWP_SPEC")) != 0;   // (0: measurements)
-            rc = tz_model_predict_batch_dev(ctx, 1, ctx->d_sched, maxB, ctx->d_frames, H, W, ctx->d_pred, ctx->d_pred, 0,
-                                            spec ? (const int*)d_slot0 : nullptr, false, &fused, prev_fused);
-            prev_fused = fused;
-            if (rc != TZ_OK) break;
-            {
-                tz_prof_scope ps(ctx, TZP_SSE);
-                hipLaunchKernelGGL(k_sse_decide, dim3(nblk), dim3(256), 0, ctx->stream, ctx->d_frames + (size_t)idx * H * W * 3,
-                                   ctx->d_pred + (size_t)idx * fe_pad, H, W, ctx->Hp, ctx->Wp, nblk, (double*)d_part, (unsigned*)d_ticket,
-                                   (DwpState*)d_state, idx, nt, (double)fe_pad, threshold, ctx->d_sched, maxB, (uint8_t*)d_key,
-                                   (uint8_t*)d_gf, (double*)d_mse, (int*)d_flag);
-            }
-            if (hipGetLastError() != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "DWP launch failed");
-        }
-        // slot 0 of every group opened on the way holds C0 (258); the last frame keeps its prediction (260-262: k_sse_decide
-        // does not flag it)
-        if (rc == TZ_OK && nt > 1) {
-            static_assert(kMaxFrames <= 65535, "gridDim.y = nt");   // (rollout_setup refuses nt > kMaxFrames)
-            hipLaunchKernelGGL(k_bcast_frames_flagged, dim3(std::min(gx, 128), nt), dim3(256), 0, ctx->stream, c0, fe_pad, (const int*)d_flag, ctx->d_pred);
-            if (hipGetLastError() != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "DWP launch failed");
-        }
-        if (rc == TZ_OK) {
-            hipError_t e = hipMemcpyAsync(key.data(), d_key, nt, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(gfirst.data(), d_gf, nt, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(mse.data(), d_mse, sizeof(double) * nt, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "DWP result download: %s", hipGetErrorString(e));
-        }
-    }
-    for (int i = 0; i < nt; ++i)
-        if (gfirst[i]) qskip[i] = 1;
+    const int rc = dwp ? rollout_dwp(call, threshold, c0_slots, key, gfirst, mse)
+                       : rollout_swp(ctx, window, mse_log != nullptr, c0_slots, key, gfirst, mse);
     if (rc != TZ_OK) {  // nothing of a failed rollout may still read the caller's frames when we return
         (void)hipStreamSynchronize(ctx->copy_stream);
         ctx->pending_src = nullptr;
+        return rc;
     }
-    if (rc == TZ_OK) {
-        ctx->key_mask = key;
-        ctx->group_first = gfirst;
-        ctx->quant_skip = qskip;
-        set_rollout(ctx, tz_ctx::ROLLOUT_ENCODE, 0, nt);
-        ctx->pred_contract = tz_get_contract(ctx);
-        if (key_mask) memcpy(key_mask, key.data(), nt);
-        if (mse_log) memcpy(mse_log, mse.data(), sizeof(double) * nt);
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "rollout failed: %s", hipGetErrorString(e));
-    }
-    tz_pool_release_all(ctx);
-    return rc;
+    for (int i = 0; i < nt; ++i)
+        if (gfirst[i]) qskip[i] = 1;
+    ctx->key_mask = key;
+    ctx->group_first = gfirst;
+    ctx->quant_skip = qskip;
+    set_rollout(ctx, tz_ctx::ROLLOUT_ENCODE, 0, nt);
+    ctx->pred_contract = tz_get_contract(ctx);
+    if (key_mask) memcpy(key_mask, key.data(), nt);
+    if (mse_log) memcpy(mse_log, mse.data(), sizeof(double) * nt);
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "rollout failed: %s", hipGetErrorString(e));
+    return TZ_OK;
 }
-
 // decompress.py:138-186: the frames the decoder reconstructs from their key-frame bytes rather than from a prediction slot
 // -- frame 0 and every key frame from the warm_up-th on; the warm-up frames 1..warm_up-1 reconstruct from their C0 slot.
 // key: the key mask of an n-frame stack.  The decoder's rollouts leave this in ctx->key_mask; tz_encode_quality derives
@@ -1341,21 +1347,17 @@ static int discover_keys(tz_ctx* ctx, int nt, int H, int W, std::vector<int>* fl
 static int rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, int first, int count,
                           uint8_t* key_mask, bool range) {
     ctx->enc_kind = tz_ctx::ENC_NONE;
+    tz_call call(ctx);
     // (a range sizes its prediction stack once it knows its restart frame)
-    int rc = rollout_setup(ctx, key_frames, nt, H, W, warm_up, nullptr, first == 0 && count == nt ? nt : 1);
-    if (rc != TZ_OK) return rc;
+    TZ_TRY(rollout_setup(ctx, key_frames, nt, H, W, warm_up, nullptr, first == 0 && count == nt ? nt : 1));
     std::vector<int> flags(nt, 0);
-    rc = discover_keys(ctx, nt, H, W, &flags);
-    for (int i = 0; range && rc == TZ_OK && i <= warm_up; ++i)
-        if (i >= nt || !flags[i]) rc = tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", i);
+    TZ_TRY(discover_keys(ctx, nt, H, W, &flags));
+    for (int i = 0; range && i <= warm_up; ++i)
+        if (i >= nt || !flags[i]) return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", i);
     std::vector<uint8_t> mask(nt);
     for (int i = 0; i < nt; ++i) mask[i] = flags[i] ? 1 : 0;
     int r = 0;
-    if (rc == TZ_OK) rc = tz_range_restart(mask.data(), nt, warm_up, first, &r);
-    if (rc != TZ_OK) {
-        tz_pool_release_all(ctx);
-        return rc;
-    }
+    TZ_TRY(tz_range_restart(mask.data(), nt, warm_up, first, &r));
     // sub-stack [r, end): from a key frame r > warm_up with warm_up 0, or from frame 0 with the job's warm_up -- and then
     // reaching frame warm_up, which the key-interval walk starts from (the whole decode of warm_up == nt: all C0 copies)
     const int end = r == 0 ? std::min(nt, std::max(first + count, warm_up + 1)) : first + count;
@@ -1372,10 +1374,7 @@ static int rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H,
     int produced = warm_up;
     for (int k = warm_up; k + 1 < (int)kfc.size(); ++k)
         for (int pi = kfc[k]; pi < kfc[k + 1]; ++pi, ++produced) {
-            if (produced != pi) {
-                tz_pool_release_all(ctx);
-                return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", pi);
-            }
+            if (produced != pi) return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", pi);
             if (pi < r || pi >= end) continue;
             if (pi == kfc[k]) {
                 c0_slots.push_back(pi - r);  // slot content is never used for reconstruction
@@ -1383,28 +1382,19 @@ static int rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H,
                 items.push_back(PredItem{pi - r, pi == kfc[k] + 1 ? 1 : 0, pi - 1 - r, pi - kfc[k]});
             }
         }
-    if (produced != nt) {
-        tz_pool_release_all(ctx);
-        return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (%d of %d frames)", produced, nt);
-    }
+    if (produced != nt) return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (%d of %d frames)", produced, nt);
     const std::vector<uint8_t> recon_key = recon_key_mask(mask.data() + r, ns, sw);   // (frame 0 of it: 0, or the key frame r)
     const size_t fsz = (size_t)H * W * 3;
-    rc = tz_ensure(ctx, (void**)&ctx->d_pred, &ctx->cap_pred, (size_t)ns * ctx->Hp * ctx->Wp * 3 * 4);
-    if (rc == TZ_OK) rc = fill_c0(ctx, c0_slots);
-    if (rc == TZ_OK) rc = run_schedule(ctx, items, ctx->d_frames + (size_t)r * fsz);
-    if (rc == TZ_OK) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess)
-            rc = tz_fail(ctx, TZ_ERR_HIP, "%sdecode rollout failed: %s", range ? "range " : "", hipGetErrorString(e));
-    }
-    if (rc == TZ_OK) {
-        ctx->key_mask = recon_key;
-        set_rollout(ctx, tz_ctx::ROLLOUT_DECODE, r, end);
-        ctx->pred_contract = tz_get_contract(ctx);
-        if (key_mask) memcpy(key_mask, mask.data(), nt);
-    }
-    tz_pool_release_all(ctx);
-    return rc;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_pred, &ctx->cap_pred, (size_t)ns * ctx->Hp * ctx->Wp * 3 * 4));
+    TZ_TRY(fill_c0(ctx, c0_slots));
+    TZ_TRY(run_schedule(ctx, items, ctx->d_frames + (size_t)r * fsz));
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "%sdecode rollout failed: %s", range ? "range " : "", hipGetErrorString(e));
+    ctx->key_mask = recon_key;
+    set_rollout(ctx, tz_ctx::ROLLOUT_DECODE, r, end);
+    ctx->pred_contract = tz_get_contract(ctx);
+    if (key_mask) memcpy(key_mask, mask.data(), nt);
+    return TZ_OK;
 }
 
 extern "C" int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up,
@@ -1579,12 +1569,13 @@ static int encode_front(tz_ctx* ctx, tz_layout layout, int mode, double b0, doub
     return TZ_OK;
 }
 
-// compress.py:356-373 from the N symbols of encode_front to the payload `o`, which joins `outs` to leave.  carry (may be
+// compress.py:356-373 from the N symbols of encode_front to the payload `o`, which joins the call's outputs to leave.  carry (may be
 // NULL): the previous shard's last delta element, with which the first symbol of a tz_encode_begin is made again.  lut
 // (NULL: none): the rank remap, by remap_out (in place when o is d_sym itself); else the symbols are copied unless
 // they are already in o.  o_shuffled (may be NULL): the payload leaves from there, as the byte planes of o.
-static int encode_tail(tz_ctx* ctx, int16_t* d_sym, size_t N, const int16_t* carry, const int16_t* lut, tz_out* o,
-                       tz_out* o_shuffled, bool defer, std::vector<tz_out>& outs) {
+static int encode_tail(tz_call& call, int16_t* d_sym, size_t N, const int16_t* carry, const int16_t* lut, tz_out* o,
+                       tz_out* o_shuffled, bool defer) {
+    tz_ctx* ctx = call.ctx;
     if (carry) {   // sd = carry - x[0] instead of x[0] (compress.py:73-77 across the boundary)
         const int16_t sd = (int16_t)(*carry - ctx->enc_first);
         const int16_t y = ctx->enc_entropy ? (int16_t)(TZ_OFFSET - sd) : sd;
@@ -1600,8 +1591,8 @@ static int encode_tail(tz_ctx* ctx, int16_t* d_sym, size_t N, const int16_t* car
         TZ_TRY(tzk_shuffle(ctx, (const int16_t*)o->dev, N, (uint8_t*)o_shuffled->dev, 0));
         o = o_shuffled;
     }
-    outs.push_back(*o);
-    return tz_dev_out_finish(ctx, outs);
+    call.outs.push_back(*o);
+    return call.finish();
 }
 
 // ---- one-channel payload of a gray job (include/tezip_hip.h: tz_set_payload_channels)
@@ -1664,9 +1655,8 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
     const tz_layout layout = layout_of(ctx);
     if (layout.channels == 1) {
         if (delta_out) return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode: no delta_out with a one-channel payload");
-        const int rc_gray = encode_all_gray(ctx);
-        tz_pool_release_all(ctx);
-        TZ_TRY(rc_gray);
+        tz_call gray_check(ctx);   // (a scope of its own: the encode reuses its blocks)
+        TZ_TRY(encode_all_gray(ctx));
     }
     const size_t N = (size_t)ctx->nt * tz_frame_elems(layout, ctx->H, ctx->W);
     const bool shuffle = (entropy & 2) != 0;  // opt-in byte planes (not a reference format)
@@ -1679,66 +1669,58 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
         ctx->payload_len = N;
         payload = ctx->d_payload;
     }
-    std::vector<tz_out> outs;
-    tz_out o_pay, o_plain{nullptr, nullptr, N * 2}, o_delta;
+    tz_call call(ctx);
+    tz_out o_pay, o_plain{nullptr, nullptr, N * 2};
     tz_out* o = shuffle ? &o_plain : &o_pay;   // where the plain payload goes (scratch when it is shuffled into o_pay)
-    void *d_hist = nullptr, *d_sd = nullptr, *d_edge = nullptr;
     // a transfer of the call before may still be reading the staging buffer (and writing the caller's previous host
     // buffer): it has ~a rollout's time to finish, and must have before this call's remap writes the buffer again
-    int rc = TZ_OK;
     const bool defer = ctx->defer_payload && entropy && !shuffle && tz_ptr_kind(payload) == 1;
     if (ctx->payload_inflight) {
         if (defer) {
             hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->ev_payload, 0);
-            if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+            if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
         } else {
-            rc = tz_payload_settle(ctx);
+            TZ_TRY(tz_payload_settle(ctx));
         }
     }
-    if (rc == TZ_OK && defer) {
-        if (ctx->cap_payload_stage < N * 2) rc = tz_payload_settle(ctx);   // (growing frees the old buffer)
-        if (rc == TZ_OK) rc = tz_ensure(ctx, (void**)&ctx->d_payload_stage, &ctx->cap_payload_stage, N * 2);
+    if (defer) {
+        if (ctx->cap_payload_stage < N * 2) TZ_TRY(tz_payload_settle(ctx));   // (growing frees the old buffer)
+        TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload_stage, &ctx->cap_payload_stage, N * 2));
         o_pay = tz_out{payload, ctx->d_payload_stage, N * 2};
-    } else if (rc == TZ_OK) {
-        rc = tz_dev_out(ctx, payload, N * 2, &o_pay);
+    } else {
+        TZ_TRY(tz_dev_out(ctx, payload, N * 2, &o_pay));   // (joins the outputs last, in encode_tail)
     }
-    if (rc == TZ_OK && shuffle) rc = tz_pool_alloc(ctx, N * 2, &o_plain.dev);
-    if (rc == TZ_OK && delta_out) {
-        rc = tz_dev_out(ctx, delta_out, N * 2, &o_delta);
-        if (rc == TZ_OK) outs.push_back(o_delta);
+    if (shuffle) TZ_TRY(call.alloc(N * 2, &o_plain.dev));
+    int16_t *d_delta = nullptr, *d_edge = nullptr, *d_sd = nullptr;
+    unsigned long long* d_hist = nullptr;
+    if (delta_out) TZ_TRY(call.out(delta_out, N * 2, &d_delta));
+    TZ_TRY(call.alloc(16, &d_edge));
+    if (entropy) {
+        TZ_TRY(call.alloc(TZ_NBINS * sizeof(unsigned long long), &d_hist));
+        TZ_TRY(call.alloc(N * 2, &d_sd));
     }
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, 16, &d_edge);
-    if (rc == TZ_OK && entropy) {
-        rc = tz_pool_alloc(ctx, TZ_NBINS * sizeof(unsigned long long), &d_hist);
-        if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N * 2, &d_sd);
-    }
-    int16_t* d_sym = entropy ? (int16_t*)d_sd : (int16_t*)o->dev;   // without a table the symbols are the payload
-    if (rc == TZ_OK)
-        rc = encode_front(ctx, layout, mode, b0, b1, entropy, delta_out ? (int16_t*)o_delta.dev : nullptr, d_sym,
-                          (unsigned long long*)d_hist, (int16_t*)d_edge);
+    int16_t* d_sym = entropy ? d_sd : (int16_t*)o->dev;   // without a table the symbols are the payload
+    TZ_TRY(encode_front(ctx, layout, mode, b0, b1, entropy, d_delta, d_sym, d_hist, d_edge));
     std::vector<int16_t> lut;
-    if (rc == TZ_OK && !entropy) {
+    if (!entropy) {
         *table_len = -1;
-    } else if (rc == TZ_OK) {
+    } else {
         std::vector<unsigned long long> hist(TZ_NBINS, 0);
         hipError_t e = hipMemcpyAsync(hist.data(), d_hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "hist download: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "hist download: %s", hipGetErrorString(e));
         const auto t0 = std::chrono::steady_clock::now();
-        if (rc == TZ_OK) rc = tz_build_table(hist.data(), TZ_NBINS, table, table_len);  // 356-361
-        if (rc == TZ_OK) rc = build_enc_lut(ctx, table, *table_len, &lut);
+        TZ_TRY(tz_build_table(hist.data(), TZ_NBINS, table, table_len));  // 356-361
+        TZ_TRY(build_enc_lut(ctx, table, *table_len, &lut));
         if (ctx->prof_on) {
             ctx->prof[TZP_TABLE].total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             ctx->prof[TZP_TABLE].launches += 1;
         }
     }
-    if (rc == TZ_OK)
-        rc = encode_tail(ctx, d_sym, N, nullptr, entropy ? lut.data() : nullptr, o, shuffle ? &o_pay : nullptr, defer, outs);
-    if (rc == TZ_OK && to_resident) ctx->enc_kind = tz_ctx::ENC_PAYLOAD;   // (tz_encode_quality's payload == NULL)
-    tz_pool_release_all(ctx);
-    return rc;
+    TZ_TRY(encode_tail(call, d_sym, N, nullptr, entropy ? lut.data() : nullptr, o, shuffle ? &o_pay : nullptr, defer));
+    if (to_resident) ctx->enc_kind = tz_ctx::ENC_PAYLOAD;   // (tz_encode_quality's payload == NULL)
+    return TZ_OK;
 }
-
 // ---- tz_encode in two phases, for jobs whose frame windows are sharded over GPUs.  The spatial delta
 // runs over the WHOLE flattened stack (compress.py:339) and the rank table comes from the GLOBAL histogram
 // (compress.py:354-361): a shard runs encode_front into the context's resident payload buffer (begin), the ranks exchange
@@ -1754,25 +1736,21 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_payload, &ctx->cap_payload, N * 2));
     ctx->payload_len = N;
-    void *d_hist = nullptr, *d_edge = nullptr;
-    int rc = tz_pool_alloc(ctx, 16, &d_edge);
-    if (rc == TZ_OK && entropy) rc = tz_pool_alloc(ctx, TZ_NBINS * sizeof(unsigned long long), &d_hist);
-    if (rc == TZ_OK)
-        rc = encode_front(ctx, kFlat, mode, b0, b1, entropy ? 1 : 0, nullptr, ctx->d_payload, (unsigned long long*)d_hist, (int16_t*)d_edge);
-    if (rc == TZ_OK) {
-        hipError_t e = hipMemcpyAsync(edge, d_edge, 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && entropy)
-            e = hipMemcpyAsync(hist, d_hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "tz_encode_begin: %s", hipGetErrorString(e));
-    }
-    if (rc == TZ_OK) {
-        ctx->enc_kind = tz_ctx::ENC_SYMBOLS;
-        ctx->enc_entropy = entropy != 0;
-        ctx->enc_first = edge[0];
-    }
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    unsigned long long* d_hist = nullptr;
+    int16_t* d_edge = nullptr;
+    TZ_TRY(call.alloc(16, &d_edge));
+    if (entropy) TZ_TRY(call.alloc(TZ_NBINS * sizeof(unsigned long long), &d_hist));
+    TZ_TRY(encode_front(ctx, kFlat, mode, b0, b1, entropy ? 1 : 0, nullptr, ctx->d_payload, d_hist, d_edge));
+    hipError_t e = hipMemcpyAsync(edge, d_edge, 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && entropy)
+        e = hipMemcpyAsync(hist, d_hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "tz_encode_begin: %s", hipGetErrorString(e));
+    ctx->enc_kind = tz_ctx::ENC_SYMBOLS;
+    ctx->enc_entropy = entropy != 0;
+    ctx->enc_first = edge[0];
+    return TZ_OK;
 }
 
 extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const int16_t* table, int table_len,
@@ -1789,50 +1767,37 @@ extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const
         return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish: the resident symbols (%zu) are not those of the current rollout", N);
     }
     std::vector<int16_t> lut;
-    std::vector<tz_out> outs;
+    if (ctx->enc_entropy) TZ_TRY(build_enc_lut(ctx, table, table_len, &lut));
+    tz_call call(ctx);
     tz_out o{nullptr, ctx->d_payload};   // payload NULL: the symbols become the payload in place and stay resident
-    int rc = ctx->enc_entropy ? build_enc_lut(ctx, table, table_len, &lut) : TZ_OK;
-    if (rc == TZ_OK && payload) rc = tz_dev_out(ctx, payload, N * 2, &o);
-    if (rc == TZ_OK)
-        rc = encode_tail(ctx, ctx->d_payload, N, has_carry ? &carry : nullptr, ctx->enc_entropy ? lut.data() : nullptr, &o,
-                         nullptr, false, outs);
-    if (rc == TZ_OK) ctx->enc_kind = tz_ctx::ENC_NONE;
-    tz_pool_release_all(ctx);
-    return rc;
+    if (payload) TZ_TRY(tz_dev_out(ctx, payload, N * 2, &o));   // (joins the outputs in encode_tail)
+    TZ_TRY(encode_tail(call, ctx->d_payload, N, has_carry ? &carry : nullptr, ctx->enc_entropy ? lut.data() : nullptr, &o, nullptr, false));
+    ctx->enc_kind = tz_ctx::ENC_NONE;
+    return TZ_OK;
 }
 
 // Opt-in byte shuffle of an int16 stream and its inverse (stand-alone; tz_encode applies the
 // forward direction itself when bit 1 of `entropy` is set).
 extern "C" int tz_byte_shuffle(tz_ctx* ctx, const int16_t* in, size_t n, uint8_t* out) {
     if (!ctx || !in || !out) return TZ_ERR_INVALID;
-    const void* din;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in, n * 2, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_shuffle(ctx, (const int16_t*)din, n, (uint8_t*)o.dev, 0);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const int16_t* din;
+    uint8_t* dout;
+    TZ_TRY(call.in(in, n * 2, &din));
+    TZ_TRY(call.out(out, n * 2, &dout));
+    TZ_TRY(tzk_shuffle(ctx, (const int16_t*)din, n, (uint8_t*)dout, 0));
+    return call.finish();
 }
 
 extern "C" int tz_byte_unshuffle(tz_ctx* ctx, const uint8_t* in, size_t n, int16_t* out) {
     if (!ctx || !in || !out) return TZ_ERR_INVALID;
-    const void* din;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in, n * 2, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_shuffle(ctx, (const int16_t*)din, n, (uint8_t*)o.dev, 1);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const uint8_t* din;
+    int16_t* dout;
+    TZ_TRY(call.in(in, n * 2, &din));
+    TZ_TRY(call.out(out, n * 2, &dout));
+    TZ_TRY(tzk_shuffle(ctx, (const int16_t*)din, n, (uint8_t*)dout, 1));
+    return call.finish();
 }
 
 extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int16_t* delta_out) {
@@ -1840,14 +1805,11 @@ extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int1
     TZ_TRY(flat_only(ctx, "tz_encode_delta"));
     TZ_TRY(encode_check(ctx, "tz_encode_delta", mode));
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
-    std::vector<tz_out> outs;
-    tz_out o;
-    int rc = tz_dev_out(ctx, delta_out, N * 2, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = encode_front(ctx, kFlat, mode, b0, b1, 0, (int16_t*)o.dev, nullptr, nullptr, nullptr);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    int16_t* d_delta;
+    TZ_TRY(call.out(delta_out, N * 2, &d_delta));
+    TZ_TRY(encode_front(ctx, kFlat, mode, b0, b1, 0, d_delta, nullptr, nullptr, nullptr));
+    return call.finish();
 }
 
 extern "C" int tz_decode_delta(tz_ctx* ctx, const int16_t* delta, uint8_t* frames_out) {
@@ -1857,21 +1819,15 @@ extern "C" int tz_decode_delta(tz_ctx* ctx, const int16_t* delta, uint8_t* frame
     TZ_TRY(tz_check_pred_contract(ctx, "tz_decode_delta"));
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
     const size_t N = (size_t)nt * H * W * 3;
-    std::vector<tz_out> outs;
-    tz_out o;
-    const void* d_diff = nullptr;
-    void* d_mask = nullptr;
-    int rc = tz_dev_in(ctx, delta, N * 2, &d_diff);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, frames_out, N, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_mask);
-    if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, ctx->key_mask.data(), nt);
-    if (rc == TZ_OK)
-        rc = tzk_reconstruct(ctx, 3, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, (const int16_t*)d_diff, nt, H, W,
-                             ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const int16_t* d_diff;
+    uint8_t *d_out, *d_mask;
+    TZ_TRY(call.in(delta, N * 2, &d_diff));
+    TZ_TRY(call.out(frames_out, N, &d_out));
+    TZ_TRY(call.alloc(nt, &d_mask));
+    TZ_TRY(tz_upload(ctx, d_mask, ctx->key_mask.data(), nt));
+    TZ_TRY(tzk_reconstruct(ctx, 3, ctx->d_pred, ctx->d_frames, d_mask, d_diff, nt, H, W, ctx->Hp, ctx->Wp, d_out));
+    return call.finish();
 }
 
 // the `stride` decoded elements in front of payload[n0] (k_undelta_carry, k_undelta_carry_s3): enqueued, then read back
@@ -1908,11 +1864,10 @@ static int undelta_carry_seam(tz_ctx* ctx, int stride, const int16_t* payload, s
     if (!payload) TZ_TRY(staged_payload(ctx, n0, &payload));
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
-    const void* d_pay = nullptr;
-    int rc = tz_dev_in(ctx, payload, n0 * 2, &d_pay);
-    if (rc == TZ_OK) rc = undelta_carry(ctx, stride, (const int16_t*)d_pay, n0, table_len >= 0 ? lut.data() : nullptr, carry);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const int16_t* d_pay;
+    TZ_TRY(call.in(payload, n0 * 2, &d_pay));
+    return undelta_carry(ctx, stride, d_pay, n0, table_len >= 0 ? lut.data() : nullptr, carry);
 }
 
 extern "C" int tz_undelta_carry(tz_ctx* ctx, const int16_t* payload, size_t n0, const int16_t* table, int table_len,
@@ -1948,32 +1903,28 @@ static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, s
         TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_out, &ctx->cap_out, nr));
         frames_out = ctx->d_out;
     }
-    std::vector<tz_out> outs;
-    tz_out o;
-    const void* d_pay = nullptr;
-    void* d_mask = nullptr;
+    tz_call call(ctx);
+    const int16_t* d_pay;
+    uint8_t *d_out, *d_mask;
     int16_t carry[3] = {0, 0, 0};   // the layout.stride decoded elements in front of the range
-    int rc = tz_dev_in(ctx, payload, n0 * 2 + np * 2, &d_pay);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, frames_out, nr, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, count, &d_mask);
-    if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, ctx->key_mask.data() + (first - r), count);
+    TZ_TRY(call.in(payload, n0 * 2 + np * 2, &d_pay));
+    TZ_TRY(call.out(frames_out, nr, &d_out));
+    TZ_TRY(call.alloc(count, &d_mask));
+    TZ_TRY(tz_upload(ctx, d_mask, ctx->key_mask.data() + (first - r), count));
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    if (rc == TZ_OK && first > 0) rc = undelta_carry(ctx, layout.stride, (const int16_t*)d_pay, n0, h_lut, carry);
-    if (rc == TZ_OK)
-        rc = tzk_decode_tail(ctx, layout, (const int16_t*)d_pay + n0, h_lut, 1, first > 0 ? carry : nullptr,
-                             ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + (size_t)first * fe,
-                             (const uint8_t*)d_mask, count, H, W, ctx->Hp, ctx->Wp, (uint8_t*)o.dev);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && resident) {   // only a decode whose work is queued leaves frames to fetch
+    if (first > 0) TZ_TRY(undelta_carry(ctx, layout.stride, d_pay, n0, h_lut, carry));
+    TZ_TRY(tzk_decode_tail(ctx, layout, d_pay + n0, h_lut, 1, first > 0 ? carry : nullptr,
+                           ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + (size_t)first * fe, d_mask, count, H,
+                           W, ctx->Hp, ctx->Wp, d_out));
+    TZ_TRY(call.finish());
+    if (resident) {   // only a decode whose work is queued leaves frames to fetch
         ctx->have_decoded = true;
         ctx->dec_first = first;
         ctx->dec_count = count;
     }
-    tz_pool_release_all(ctx);
-    return rc;
+    return TZ_OK;
 }
 
 extern "C" int tz_decode(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
@@ -1996,10 +1947,11 @@ extern "C" int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t paylo
 // What the stored payload of an encode decodes to (include/tezip_hip.h: tz_encode_quality, tz_encode_digests): the decoder's
 // tail over the payload on the ENCODER's predictions and frames -- the reconstruct reads frames only where the mask says
 // "key", and there the encoder's originals are the bytes key_frame.dat stores -- into pool scratch (*d_dec, nt*H*W*3
-// bytes, queued on the context's stream).  Only scratch is written; the caller releases the pool.  One statement of
+// bytes, queued on the context's stream).  Only scratch is written, under the caller's scope.  One statement of
 // "decoded" for every entry point that describes it.
-static int encode_decoded(tz_ctx* ctx, const char* who, const int16_t* payload, size_t payload_len, const int16_t* table,
+static int encode_decoded(tz_call& call, const char* who, const int16_t* payload, size_t payload_len, const int16_t* table,
                           int table_len, int shuffled, const uint8_t** d_dec_out) {
+    tz_ctx* ctx = call.ctx;
     if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "%s needs the encoder rollout of a tz_rollout", who);
     TZ_TRY(tz_check_pred_contract(ctx, who));
     TZ_TRY(check_table(ctx, table, table_len));
@@ -2014,26 +1966,24 @@ static int encode_decoded(tz_ctx* ctx, const char* who, const int16_t* payload, 
     if (payload_len != N)
         return tz_fail(ctx, TZ_ERR_INVALID, "payload holds %zu elements, the encoded stack %zu", payload_len, N);
     if (shuffled && (N & 7)) return tz_fail(ctx, TZ_ERR_INVALID, "byte shuffle needs a multiple of 8 elements");
-    const void* d_pay = nullptr;
-    void *d_plain = nullptr, *d_mask = nullptr, *d_dec = nullptr;
-    int rc = tz_dev_in(ctx, payload, N * 2, &d_pay);
-    if (rc == TZ_OK && shuffled) {   // byte planes -> int16 in scratch (the caller's payload stays as it is)
-        rc = tz_pool_alloc(ctx, N * 2, &d_plain);
-        if (rc == TZ_OK) rc = tzk_shuffle(ctx, (const int16_t*)d_pay, N, (uint8_t*)d_plain, 1);
-        d_pay = d_plain;
+    const int16_t* d_pay;
+    uint8_t *d_plain, *d_mask, *d_dec;
+    TZ_TRY(call.in(payload, N * 2, &d_pay));
+    if (shuffled) {   // byte planes -> int16 in scratch (the caller's payload stays as it is)
+        TZ_TRY(call.alloc(N * 2, &d_plain));
+        TZ_TRY(tzk_shuffle(ctx, d_pay, N, d_plain, 1));
+        d_pay = (const int16_t*)d_plain;
     }
     const std::vector<uint8_t> recon = recon_key_mask(ctx->key_mask.data(), nt, ctx->warm_up);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nt, &d_mask);
-    if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, recon.data(), nt);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, (size_t)nt * fe, &d_dec);
+    TZ_TRY(call.alloc(nt, &d_mask));
+    TZ_TRY(tz_upload(ctx, d_mask, recon.data(), nt));
+    TZ_TRY(call.alloc((size_t)nt * fe, &d_dec));
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
-    const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    if (rc == TZ_OK)   // the launches of tz_decode
-        rc = tzk_decode_tail(ctx, layout, (const int16_t*)d_pay, h_lut, 1, nullptr, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt,
-                             H, W, ctx->Hp, ctx->Wp, (uint8_t*)d_dec);
-    *d_dec_out = (const uint8_t*)d_dec;
-    return rc;
+    *d_dec_out = d_dec;
+    // the launches of tz_decode
+    return tzk_decode_tail(ctx, layout, d_pay, table_len >= 0 ? lut.data() : nullptr, 1, nullptr, ctx->d_pred, ctx->d_frames, d_mask, nt, H, W,
+                           ctx->Hp, ctx->Wp, d_dec);
 }
 
 // The report of `-c --report`: k_quality of the decoded stack against the originals.
@@ -2041,17 +1991,14 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
                                  int shuffled, tz_frame_quality* out) {
     tz_roctx_range roctx_("tz_encode_quality");
     if (!ctx || !out) return TZ_ERR_INVALID;
-    std::vector<tz_out> outs;
-    tz_out o;
-    const uint8_t* d_dec = nullptr;
-    int rc = encode_decoded(ctx, "tz_encode_quality", payload, payload_len, table, table_len, shuffled, &d_dec);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_quality) * ctx->nt, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tzk_quality(ctx, ctx->d_frames, d_dec, ctx->nt, (size_t)ctx->H * ctx->W * 3, (tz_frame_quality*)o.dev);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device records too: complete on return)
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const uint8_t* d_dec;
+    tz_frame_quality* d_out;
+    TZ_TRY(encode_decoded(call, "tz_encode_quality", payload, payload_len, table, table_len, shuffled, &d_dec));
+    TZ_TRY(call.out(out, sizeof(tz_frame_quality) * ctx->nt, &d_out));
+    TZ_TRY(tzk_quality(ctx, ctx->d_frames, d_dec, ctx->nt, (size_t)ctx->H * ctx->W * 3, d_out));
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);   // (device records too: complete on return)
 }
 
 // One candidate bound of `-c --target-psnr` (TZ-TPSNR-1): the records tz_encode(mode, b0, b1) + tz_encode_quality would give,
@@ -2067,30 +2014,27 @@ extern "C" int tz_bound_probe(tz_ctx* ctx, int mode, double b0, double b1, tz_fr
     TZ_TRY(encode_check(ctx, "tz_bound_probe", mode));
     const int channels = layout_of(ctx).channels;
     if (channels == 1) {
-        const int rc_gray = encode_all_gray(ctx);
-        tz_pool_release_all(ctx);
-        TZ_TRY(rc_gray);
+        tz_call gray_check(ctx);   // (a scope of its own: the probe reuses its blocks)
+        TZ_TRY(encode_all_gray(ctx));
     }
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
     const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe;
-    std::vector<tz_out> outs;
-    tz_out o;
-    void *d_mask = nullptr, *d_delta = nullptr, *d_q = nullptr;
-    int rc = tz_pool_alloc(ctx, nt, &d_mask);
-    if (rc == TZ_OK) rc = tz_upload(ctx, d_mask, ctx->group_first.data(), nt);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N * 2, &d_delta);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, N * 2, &d_q);
-    if (rc == TZ_OK) rc = tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta);
-    if (rc == TZ_OK && hipMemcpyAsync(d_q, d_delta, N * 2, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-        rc = tz_fail(ctx, TZ_ERR_HIP, "tz_bound_probe: copy of the delta stack failed");
-    if (rc == TZ_OK) rc = tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_quality) * nt, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tzk_bound_err(ctx, channels, ctx->d_frames, (const int16_t*)d_delta, (const int16_t*)d_q, nt, fe, (tz_frame_quality*)o.dev);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device records too: complete on return)
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    uint8_t* d_mask;
+    int16_t *d_delta, *d_q;
+    tz_frame_quality* d_out;
+    TZ_TRY(call.alloc(nt, &d_mask));
+    TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
+    TZ_TRY(call.alloc(N * 2, &d_delta));
+    TZ_TRY(call.alloc(N * 2, &d_q));
+    TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, d_mask, nt, H, W, ctx->Hp, ctx->Wp, d_delta));
+    if (hipMemcpyAsync(d_q, d_delta, N * 2, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        return tz_fail(ctx, TZ_ERR_HIP, "tz_bound_probe: copy of the delta stack failed");
+    TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
+    TZ_TRY(call.out(out, sizeof(tz_frame_quality) * nt, &d_out));
+    TZ_TRY(tzk_bound_err(ctx, channels, ctx->d_frames, d_delta, d_q, nt, fe, d_out));
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);   // (device records too: complete on return)
 }
 
 // k_bound_err alone, on any three stacks (tests against tezip_amd/target.py errors_of), in the form the context's payload
@@ -2102,20 +2046,17 @@ extern "C" int tz_bound_err(tz_ctx* ctx, const uint8_t* orig, const int16_t* del
     if (nframes <= 0 || frame_elems == 0) return TZ_OK;
     if (!orig || !delta || !qdelta || !out) return TZ_ERR_INVALID;
     const size_t n = (size_t)nframes * frame_elems;
-    std::vector<tz_out> outs;
-    tz_out o;
-    const void *d_o = nullptr, *d_d = nullptr, *d_q = nullptr;
-    int rc = tz_dev_in(ctx, orig, n, &d_o);
-    if (rc == TZ_OK) rc = tz_dev_in(ctx, delta, n * 2, &d_d);
-    if (rc == TZ_OK) rc = tz_dev_in(ctx, qdelta, n * 2, &d_q);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_quality) * nframes, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tzk_bound_err(ctx, ctx->payload_channels, (const uint8_t*)d_o, (const int16_t*)d_d, (const int16_t*)d_q, nframes, frame_elems,
-                                         (tz_frame_quality*)o.dev);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const uint8_t* d_o;
+    const int16_t *d_d, *d_q;
+    tz_frame_quality* d_out;
+    TZ_TRY(call.in(orig, n, &d_o));
+    TZ_TRY(call.in(delta, n * 2, &d_d));
+    TZ_TRY(call.in(qdelta, n * 2, &d_q));
+    TZ_TRY(call.out(out, sizeof(tz_frame_quality) * nframes, &d_out));
+    TZ_TRY(tzk_bound_err(ctx, ctx->payload_channels, d_o, d_d, d_q, nframes, frame_elems, d_out));
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);
 }
 
 // The records of `-c --digests`: k_digest of the decoded stack, and of the resident originals when asked for.
@@ -2123,24 +2064,20 @@ extern "C" int tz_encode_digests(tz_ctx* ctx, const int16_t* payload, size_t pay
                                  int shuffled, unsigned long long* decoded, unsigned long long* original) {
     tz_roctx_range roctx_("tz_encode_digests");
     if (!ctx || !decoded) return TZ_ERR_INVALID;
-    std::vector<tz_out> outs;
-    tz_out o;
-    const uint8_t* d_dec = nullptr;
-    int rc = encode_decoded(ctx, "tz_encode_digests", payload, payload_len, table, table_len, shuffled, &d_dec);
+    tz_call call(ctx);
+    const uint8_t* d_dec;
+    unsigned long long* d_out;
+    TZ_TRY(encode_decoded(call, "tz_encode_digests", payload, payload_len, table, table_len, shuffled, &d_dec));
     const int nt = ctx->nt;
     const size_t fe = (size_t)ctx->H * ctx->W * 3;
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, decoded, sizeof(unsigned long long) * nt, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tzk_digest(ctx, d_dec, nt, fe, (unsigned long long*)o.dev);
-    if (rc == TZ_OK && original) {
-        rc = tz_dev_out(ctx, original, sizeof(unsigned long long) * nt, &o);
-        if (rc == TZ_OK) outs.push_back(o);
-        if (rc == TZ_OK) rc = tzk_digest(ctx, ctx->d_frames, nt, fe, (unsigned long long*)o.dev);
+    TZ_TRY(call.out(decoded, sizeof(unsigned long long) * nt, &d_out));
+    TZ_TRY(tzk_digest(ctx, d_dec, nt, fe, d_out));
+    if (original) {
+        TZ_TRY(call.out(original, sizeof(unsigned long long) * nt, &d_out));
+        TZ_TRY(tzk_digest(ctx, ctx->d_frames, nt, fe, d_out));
     }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device words too: complete on return)
-    tz_pool_release_all(ctx);
-    return rc;
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);   // (device words too: complete on return)
 }
 
 // The records of `-c --report --ssim`: k_ssim of the decoded stack against the originals.
@@ -2148,17 +2085,14 @@ extern "C" int tz_encode_ssim(tz_ctx* ctx, const int16_t* payload, size_t payloa
                               int shuffled, tz_frame_ssim* out) {
     tz_roctx_range roctx_("tz_encode_ssim");
     if (!ctx || !out) return TZ_ERR_INVALID;
-    std::vector<tz_out> outs;
-    tz_out o;
-    const uint8_t* d_dec = nullptr;
-    int rc = encode_decoded(ctx, "tz_encode_ssim", payload, payload_len, table, table_len, shuffled, &d_dec);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_ssim) * ctx->nt, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tzk_ssim(ctx, d_dec, ctx->d_frames, ctx->nt, ctx->H, ctx->W, (tz_frame_ssim*)o.dev);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);   // (device records too: complete on return)
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const uint8_t* d_dec;
+    tz_frame_ssim* d_out;
+    TZ_TRY(encode_decoded(call, "tz_encode_ssim", payload, payload_len, table, table_len, shuffled, &d_dec));
+    TZ_TRY(call.out(out, sizeof(tz_frame_ssim) * ctx->nt, &d_out));
+    TZ_TRY(tzk_ssim(ctx, d_dec, ctx->d_frames, ctx->nt, ctx->H, ctx->W, d_out));
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);   // (device records too: complete on return)
 }
 
 // TZ-SSIM-1 records of any two unpadded uint8 stacks (tests against tezip_amd/ssim.py).
@@ -2169,18 +2103,15 @@ extern "C" int tz_ssim_frames(tz_ctx* ctx, const uint8_t* a, const uint8_t* b, i
     const size_t fe = (size_t)H * W * 3;
     if (fe >> 32) return tz_fail(ctx, TZ_ERR_INVALID, "frames of %zu bytes: SSIM covers frames of fewer than 2^32", fe);
     if (nframes == 0) return TZ_OK;
-    std::vector<tz_out> outs;
-    tz_out o;
-    const void *d_a = nullptr, *d_b = nullptr;
-    int rc = tz_dev_in(ctx, a, (size_t)nframes * fe, &d_a);
-    if (rc == TZ_OK) rc = tz_dev_in(ctx, b, (size_t)nframes * fe, &d_b);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(tz_frame_ssim) * nframes, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tzk_ssim(ctx, (const uint8_t*)d_a, (const uint8_t*)d_b, nframes, H, W, (tz_frame_ssim*)o.dev);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const uint8_t *d_a, *d_b;
+    tz_frame_ssim* d_out;
+    TZ_TRY(call.in(a, (size_t)nframes * fe, &d_a));
+    TZ_TRY(call.in(b, (size_t)nframes * fe, &d_b));
+    TZ_TRY(call.out(out, sizeof(tz_frame_ssim) * nframes, &d_out));
+    TZ_TRY(tzk_ssim(ctx, d_a, d_b, nframes, H, W, d_out));
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);
 }
 
 // TZD64 digests of any unpadded uint8 stack (`-u --verify` on the whole-array path; tests against tezip_amd/digest.py).
@@ -2189,17 +2120,14 @@ extern "C" int tz_frame_digests(tz_ctx* ctx, const uint8_t* frames, int nframes,
     if (!ctx || nframes < 0 || (nframes > 0 && (!out || (!frames && frame_bytes)))) return TZ_ERR_INVALID;
     if (frame_bytes >> 32) return tz_fail(ctx, TZ_ERR_INVALID, "frames of %zu bytes: a digest covers fewer than 2^32", frame_bytes);
     if (nframes == 0) return TZ_OK;
-    std::vector<tz_out> outs;
-    tz_out o;
-    const void* d_in = nullptr;
-    int rc = tz_dev_in(ctx, frames, (size_t)nframes * frame_bytes, &d_in);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, sizeof(unsigned long long) * nframes, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tzk_digest(ctx, (const uint8_t*)d_in, nframes, frame_bytes, (unsigned long long*)o.dev);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const uint8_t* d_in;
+    unsigned long long* d_out;
+    TZ_TRY(call.in(frames, (size_t)nframes * frame_bytes, &d_in));
+    TZ_TRY(call.out(out, sizeof(unsigned long long) * nframes, &d_out));
+    TZ_TRY(tzk_digest(ctx, d_in, nframes, frame_bytes, d_out));
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);
 }
 
 // The same over the decoded frames a tz_decode / tz_decode_range with frames_out == NULL left in the context (`-u --verify`
@@ -2212,15 +2140,12 @@ extern "C" int tz_decoded_digests(tz_ctx* ctx, int first, int count, unsigned lo
         return tz_fail(ctx, TZ_ERR_INVALID, "frames [%d, %d + %d) outside the resident decoded stack", first, first, count);
     if (count == 0) return TZ_OK;
     const size_t fsz = (size_t)ctx->H * ctx->W * 3;
-    std::vector<tz_out> outs;
-    tz_out o;
-    int rc = tz_dev_out(ctx, out, sizeof(unsigned long long) * count, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    if (rc == TZ_OK) rc = tzk_digest(ctx, ctx->d_out + (size_t)(first - ctx->dec_first) * fsz, count, fsz, (unsigned long long*)o.dev);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    unsigned long long* d_out;
+    TZ_TRY(call.out(out, sizeof(unsigned long long) * count, &d_out));
+    TZ_TRY(tzk_digest(ctx, ctx->d_out + (size_t)(first - ctx->dec_first) * fsz, count, fsz, d_out));
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);
 }
 
 // ------------------------------------------------------------------ stand-alone operators
@@ -2231,22 +2156,18 @@ extern "C" int tz_delta_encode(tz_ctx* ctx, const float* pred, const uint8_t* or
     size_t N = (size_t)nframes * H * W * 3;
     std::vector<uint8_t> zm(nframes, 0);
     if (zero_mask) memcpy(zm.data(), zero_mask, nframes);
-    const void *dp, *dor;
-    void* dm;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp);
-    if (rc == TZ_OK) rc = tz_dev_in(ctx, orig, N, &dor);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nframes, &dm);
-    if (rc == TZ_OK && nframes) rc = tz_upload(ctx, dm, zm.data(), nframes);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, N * 2, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_delta(ctx, (const float*)dp, (const uint8_t*)dor, (const uint8_t*)dm, nframes, H, W, Hp, Wp, (int16_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const float* dp;
+    const uint8_t* dor;
+    uint8_t* dm;
+    int16_t* dout;
+    TZ_TRY(call.in(pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp));
+    TZ_TRY(call.in(orig, N, &dor));
+    TZ_TRY(call.alloc(nframes, &dm));
+    if (nframes) TZ_TRY(tz_upload(ctx, dm, zm.data(), nframes));
+    TZ_TRY(call.out(out, N * 2, &dout));
+    TZ_TRY(tzk_delta(ctx, dp, dor, dm, nframes, H, W, Hp, Wp, dout));
+    return call.finish();
 }
 
 extern "C" int tz_error_bound(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask, int nframes, int H,
@@ -2255,22 +2176,17 @@ extern "C" int tz_error_bound(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, c
     size_t N = (size_t)nframes * H * W * 3;
     std::vector<uint8_t> sk(nframes, 0);
     if (skip_mask) memcpy(sk.data(), skip_mask, nframes);
-    const void* dor;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, orig, N, &dor);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, diff, N * 2, &o);
-    if (rc == TZ_OK && o.host) {
-        hipError_t e = hipMemcpyAsync(o.dev, diff, N * 2, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "diff upload: %s", hipGetErrorString(e));
+    tz_call call(ctx);
+    const uint8_t* dor;
+    int16_t* ddiff;
+    TZ_TRY(call.in(orig, N, &dor));
+    TZ_TRY(call.out(diff, N * 2, &ddiff));
+    if (call.outs.back().host) {
+        hipError_t e = hipMemcpyAsync(ddiff, diff, N * 2, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "diff upload: %s", hipGetErrorString(e));
     }
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_error_bound(ctx, (const uint8_t*)dor, (int16_t*)o.dev, sk.data(), nframes, H, W, mode, b0, b1);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    TZ_TRY(tzk_error_bound(ctx, dor, ddiff, sk.data(), nframes, H, W, mode, b0, b1));
+    return call.finish();
 }
 
 // The seams.  Each operation has one body, which takes the layout (tz_internal.h); the exported names of the gray payload
@@ -2284,29 +2200,21 @@ static int check_stride(tz_ctx* ctx, const char* who, int stride) {
 // n_in elements at `in` -> n_out at `out` (gray: three interleaved channels in, channel 0's delta out)
 static int spatial_delta_seam(tz_ctx* ctx, tz_layout layout, const int16_t* in, size_t n_in, size_t n_out, const int16_t* carry,
                               int apply_offset, int16_t* out, unsigned long long* hist) {
-    const void* din;
-    tz_out o, oh;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in, n_in * 2, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n_out * 2, &o);
-    if (rc == TZ_OK) outs.push_back(o);
-    void* dh = nullptr;
-    if (rc == TZ_OK && hist) {
-        rc = tz_dev_out(ctx, hist, TZ_NBINS * sizeof(unsigned long long), &oh);
-        if (rc == TZ_OK) {
-            dh = oh.dev;
-            if (oh.host) {  // counts are ADDED to what the caller holds
-                hipError_t e = hipMemcpyAsync(dh, hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream);
-                if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "hist upload: %s", hipGetErrorString(e));
-            }
-            outs.push_back(oh);
+    tz_call call(ctx);
+    const int16_t* din;
+    int16_t* dout;
+    unsigned long long* dh = nullptr;
+    TZ_TRY(call.in(in, n_in * 2, &din));
+    TZ_TRY(call.out(out, n_out * 2, &dout));
+    if (hist) {
+        TZ_TRY(call.out(hist, TZ_NBINS * sizeof(unsigned long long), &dh));
+        if (call.outs.back().host) {  // counts are ADDED to what the caller holds
+            hipError_t e = hipMemcpyAsync(dh, hist, TZ_NBINS * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "hist upload: %s", hipGetErrorString(e));
         }
     }
-    if (rc == TZ_OK)
-        rc = tzk_spatial_delta(ctx, layout, (const int16_t*)din, n_out, carry, apply_offset, (int16_t*)o.dev, (unsigned long long*)dh, nullptr);
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    TZ_TRY(tzk_spatial_delta(ctx, layout, din, n_out, carry, apply_offset, dout, dh, nullptr));
+    return call.finish();
 }
 
 extern "C" int tz_spatial_delta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, int apply_offset,
@@ -2329,18 +2237,13 @@ extern "C" int tz_spatial_delta_stride(tz_ctx* ctx, const int16_t* in, size_t n,
 }
 
 static int lut_op(tz_ctx* ctx, const int16_t* in, size_t n, const std::vector<int16_t>& lut, int post, int16_t* out) {
-    const void* din;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in, n * 2, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_lut(ctx, (const int16_t*)din, n, lut.data(), post, (int16_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const int16_t* din;
+    int16_t* dout;
+    TZ_TRY(call.in(in, n * 2, &din));
+    TZ_TRY(call.out(out, n * 2, &dout));
+    TZ_TRY(tzk_lut(ctx, din, n, lut.data(), post, dout));
+    return call.finish();
 }
 
 extern "C" int tz_remap(tz_ctx* ctx, const int16_t* in, size_t n, const int16_t* table, int table_len, int16_t* out) {
@@ -2361,19 +2264,14 @@ extern "C" int tz_unmap(tz_ctx* ctx, const int16_t* in, size_t n, const int16_t*
 // (stride 3 ends with a synchronisation that reads the fault word of the scan's bounded poll; the flat seam leaves that to the
 // caller's next synchronising call -- an open difference)
 static int spatial_undelta_seam(tz_ctx* ctx, int stride, const int16_t* in, size_t n, const int16_t* carry, int16_t* out) {
-    const void* din;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in, n * 2, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, n * 2, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_undelta(ctx, stride, (const int16_t*)din, n, carry, nullptr, 0, (int16_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && stride == 3) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const int16_t* din;
+    int16_t* dout;
+    TZ_TRY(call.in(in, n * 2, &din));
+    TZ_TRY(call.out(out, n * 2, &dout));
+    TZ_TRY(tzk_undelta(ctx, stride, din, n, carry, nullptr, 0, dout));
+    TZ_TRY(call.finish());
+    return stride == 3 ? tz_stream_sync(ctx) : TZ_OK;
 }
 
 extern "C" int tz_spatial_undelta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, int16_t* out) {
@@ -2405,24 +2303,19 @@ static int reconstruct_seam(tz_ctx* ctx, int channels, const float* pred, const 
     size_t N = (size_t)nframes * H * W * 3;
     std::vector<uint8_t> km(nframes, 0);
     if (key_mask && key_frames) memcpy(km.data(), key_mask, nframes);
-    const void *dp, *dk = nullptr, *dd;
-    void* dm;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp);
-    if (rc == TZ_OK && key_frames) rc = tz_dev_in(ctx, key_frames, N, &dk);
-    if (rc == TZ_OK) rc = tz_dev_in(ctx, diff, N / 3 * channels * 2, &dd);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, nframes, &dm);
-    if (rc == TZ_OK && nframes) rc = tz_upload(ctx, dm, km.data(), nframes);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, N, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = tzk_reconstruct(ctx, channels, (const float*)dp, (const uint8_t*)dk, (const uint8_t*)dm, (const int16_t*)dd, nframes, H,
-                             W, Hp, Wp, (uint8_t*)o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const float* dp;
+    const uint8_t* dk = nullptr;
+    const int16_t* dd;
+    uint8_t *dm, *dout;
+    TZ_TRY(call.in(pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp));
+    if (key_frames) TZ_TRY(call.in(key_frames, N, &dk));
+    TZ_TRY(call.in(diff, N / 3 * channels * 2, &dd));
+    TZ_TRY(call.alloc(nframes, &dm));
+    if (nframes) TZ_TRY(tz_upload(ctx, dm, km.data(), nframes));
+    TZ_TRY(call.out(out, N, &dout));
+    TZ_TRY(tzk_reconstruct(ctx, channels, dp, dk, dm, dd, nframes, H, W, Hp, Wp, dout));
+    return call.finish();
 }
 
 extern "C" int tz_reconstruct(tz_ctx* ctx, const float* pred, const uint8_t* key_frames, const uint8_t* key_mask,
@@ -2438,12 +2331,12 @@ extern "C" int tz_reconstruct_gray(tz_ctx* ctx, const float* pred, const uint8_t
 extern "C" int tz_window_sse(tz_ctx* ctx, const uint8_t* orig, const float* pred, int nframes, int H, int W, double* sse) {
     if (!ctx || !orig || !pred || !sse || nframes < 0 || H < 1 || W < 1) return TZ_ERR_INVALID;
     int Hp = pad8(H), Wp = pad8(W);
-    const void *dor, *dp;
-    int rc = tz_dev_in(ctx, orig, (size_t)nframes * H * W * 3, &dor);
-    if (rc == TZ_OK) rc = tz_dev_in(ctx, pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp);
-    if (rc == TZ_OK) rc = tzk_sse(ctx, (const uint8_t*)dor, (const float*)dp, nframes, H, W, Hp, Wp, sse);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const uint8_t* dor;
+    const float* dp;
+    TZ_TRY(call.in(orig, (size_t)nframes * H * W * 3, &dor));
+    TZ_TRY(call.in(pred, (size_t)nframes * Hp * Wp * 3 * 4, &dp));
+    return tzk_sse(ctx, dor, dp, nframes, H, W, Hp, Wp, sse);
 }
 
 // --------------------------------------------------------------------------- Huffman coder
@@ -2655,13 +2548,12 @@ static int huff_counts_dev(tz_ctx* ctx, const char* who, int ntok, int rows, huf
     void *d_hist, *d_meta;
     std::vector<unsigned long long> h((size_t)rows * BINS);
     tz_huff_meta meta;
-    int rc = tz_pool_alloc(ctx, h.size() * sizeof(unsigned long long), &d_hist);
-    if (rc == TZ_OK) rc = tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta);
-    if (rc == TZ_OK) rc = launch(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta);
-    if (rc == TZ_OK) rc = tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream);
-    if (rc == TZ_OK) rc = tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream);
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
-    TZ_TRY(rc);
+    TZ_TRY(tz_pool_alloc(ctx, h.size() * sizeof(unsigned long long), &d_hist));
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(tz_huff_meta), &d_meta));
+    TZ_TRY(launch(ctx, d_in, n, (unsigned long long*)d_hist, (tz_huff_meta*)d_meta));
+    TZ_TRY(tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream));
+    TZ_TRY(tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
     // Row 0 alone gives the span.  Every value of a run is a literal at its first occurrence there, so the literals of a
     // tokenised row span the values; huffd's row 0 counts every element, and its other rows' literals span the same values.
     int lo = -1, hi = -1;
@@ -2685,25 +2577,25 @@ static int huff_counts_dev(tz_ctx* ctx, const char* who, int ntok, int rows, huf
 static int huff_counts(tz_ctx* ctx, const char* who, int ntok, int rows, huff_count_launch launch, const int16_t* in, size_t n,
                        unsigned long long* counts, int* A, int* base) {
     if (!ctx || !counts || !A || !base) return TZ_ERR_INVALID;
-    const void* din = ctx->d_payload;
-    int rc = TZ_OK;
-    if (in)
-        rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
-    else if (!ctx->d_payload || !ctx->payload_len)
-        return tz_fail(ctx, TZ_ERR_STATE, "%s_counts needs a resident payload (tz_encode with payload == NULL)", who);
-    else
+    tz_call call(ctx);
+    const int16_t* din = ctx->d_payload;
+    if (!in) {
+        if (!ctx->d_payload || !ctx->payload_len)
+            return tz_fail(ctx, TZ_ERR_STATE, "%s_counts needs a resident payload (tz_encode with payload == NULL)", who);
         n = ctx->payload_len;
-    if (rc == TZ_OK) rc = huff_counts_dev(ctx, who, ntok, rows, launch, (const int16_t*)din, n, counts, A, base);
-    tz_pool_release_all(ctx);
-    return rc;
+    } else if (n < 1 || n >= ((size_t)1 << 40)) {
+        return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    } else {
+        TZ_TRY(call.in(in, n * 2, &din));
+    }
+    return huff_counts_dev(ctx, who, ntok, rows, launch, din, n, counts, A, base);
 }
 
 static int huff_encode(tz_ctx* ctx, const HuffFmt& f, const uint8_t* lengths, int A, int base, size_t* bytes) {
     if (!ctx || !bytes) return TZ_ERR_INVALID;
     if (!ctx->d_payload || !ctx->payload_len) return tz_fail(ctx, TZ_ERR_STATE, "%s_encode needs a resident payload (tz_encode with payload == NULL)", f.who);
-    const int rc = huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes, f.dist, false);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    return huff_encode_dev(ctx, ctx->d_payload, ctx->payload_len, lengths, A, base, bytes, f.dist, false);
 }
 
 static int huff_begin(tz_ctx* ctx, const HuffFmt& f, size_t bytes, size_t n, const uint8_t* lengths, int A, int base, int R) {
@@ -2744,53 +2636,46 @@ static int huff_decode(tz_ctx* ctx, tz_ctx::tz_huff_kind kind, const char* who) 
     TZ_TRY(huff_check_stream(ctx, ctx->huff_bytes, ctx->huff_n, TZ_HUFF_RUN, &sw));
     TZ_HIP(ctx, hipEventRecord(ctx->ev_frames, ctx->copy_stream));   // the pieces of the puts
     TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_frames, 0));
-    const int rc = huff_decode_dev(ctx, ctx->d_huff, sw, ctx->huff_n, ctx->huff_dec_tab, ctx->huff_A, ctx->huff_base, ctx->huff_dist, ctx->d_payload);
-    if (rc == TZ_OK) ctx->payload_len = ctx->huff_n;   // exactly as if tz_payload_begin / tz_payload_put had staged them
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    TZ_TRY(huff_decode_dev(ctx, ctx->d_huff, sw, ctx->huff_n, ctx->huff_dec_tab, ctx->huff_A, ctx->huff_base, ctx->huff_dist, ctx->d_payload));
+    ctx->payload_len = ctx->huff_n;   // exactly as if tz_payload_begin / tz_payload_put had staged them
+    return TZ_OK;
 }
 
 static int huff_encode_buf(tz_ctx* ctx, const HuffFmt& f, const int16_t* in, size_t n, const uint8_t* lengths, int A, int base, uint8_t* out,
                            size_t capacity, size_t* bytes) {
     if (!ctx || !in || !out || !bytes) return TZ_ERR_INVALID;
-    const void* din = nullptr;
-    int rc = n >= 1 && n < ((size_t)1 << 40) ? tz_dev_in(ctx, in, n * 2, &din) : tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
-    if (rc == TZ_OK) rc = huff_encode_dev(ctx, (const int16_t*)din, n, lengths, A, base, bytes, f.dist, false);
-    if (rc == TZ_OK && *bytes > capacity) rc = tz_fail(ctx, TZ_ERR_INVALID, "huffman: the stream needs %zu bytes, the buffer holds %zu", *bytes, capacity);
-    if (rc == TZ_OK) {
-        if (tz_is_device_ptr(out)) {
-            hipError_t e = hipMemcpyAsync(out, ctx->d_huff, *bytes, hipMemcpyDeviceToDevice, ctx->stream);
-            if (e != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "stream copy: %s", hipGetErrorString(e));
-        } else {
-            rc = tz_d2h(ctx, out, ctx->d_huff, *bytes, ctx->stream);
-        }
+    if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    tz_call call(ctx);
+    const int16_t* din;
+    TZ_TRY(call.in(in, n * 2, &din));
+    TZ_TRY(huff_encode_dev(ctx, din, n, lengths, A, base, bytes, f.dist, false));
+    if (*bytes > capacity) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: the stream needs %zu bytes, the buffer holds %zu", *bytes, capacity);
+    if (tz_is_device_ptr(out)) {
+        hipError_t e = hipMemcpyAsync(out, ctx->d_huff, *bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "stream copy: %s", hipGetErrorString(e));
+    } else {
+        TZ_TRY(tz_d2h(ctx, out, ctx->d_huff, *bytes, ctx->stream));
     }
-    if (rc == TZ_OK) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
+    return tz_stream_sync(ctx);
 }
 
 // The stand-alone forms that turn one host or device array into another: `in` is made a device array, `out` one to be copied
-// back if it is none, run(device in, device out) launches, the copy back and the stream are awaited, the pool is released.
+// back if it is none, run(device in, device out) launches under the scope opened here, the copy back and the stream are awaited.
 // A device array whose address has a bit of in_mask / out_mask set is refused with `misaligned`.
 template <class F>
 static int buf_op(tz_ctx* ctx, const void* in, size_t in_bytes, unsigned in_mask, void* out, size_t out_bytes, unsigned out_mask,
                   const char* misaligned, F&& run) {
-    const void* din = nullptr;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, in, in_bytes, &din);
-    if (rc == TZ_OK && ((uintptr_t)din & in_mask)) rc = tz_fail(ctx, TZ_ERR_INVALID, "%s", misaligned);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, out_bytes, &o);
-    if (rc == TZ_OK && ((uintptr_t)o.dev & out_mask)) rc = tz_fail(ctx, TZ_ERR_INVALID, "%s", misaligned);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        rc = run(din, o.dev);
-    }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    if (rc == TZ_OK && !o.host) rc = tz_stream_sync(ctx);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    const void* din;
+    void* dout;
+    TZ_TRY(call.in(in, in_bytes, &din));
+    if ((uintptr_t)din & in_mask) return tz_fail(ctx, TZ_ERR_INVALID, "%s", misaligned);
+    TZ_TRY(call.out(out, out_bytes, &dout));
+    if ((uintptr_t)dout & out_mask) return tz_fail(ctx, TZ_ERR_INVALID, "%s", misaligned);
+    TZ_TRY(run(din, dout));
+    TZ_TRY(call.finish());
+    return call.outs.back().host ? TZ_OK : tz_stream_sync(ctx);
 }
 
 static int huff_decode_buf(tz_ctx* ctx, const HuffFmt& f, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base,
@@ -3024,25 +2909,20 @@ static int keys_resident(tz_ctx* ctx, const char* who) {
     return TZ_OK;
 }
 
-static int keys_counts(tz_ctx* ctx, const int* idx, int nkeys, unsigned* counts) {
-    KeysDev d;
-    void* d_counts;
-    const size_t cb = (size_t)nkeys * 4 * TZ_KEYS_A * sizeof(unsigned);
-    TZ_TRY(keys_upload(ctx, idx, nullptr, nullptr, nkeys, &d));
-    TZ_TRY(tz_pool_alloc(ctx, cb, &d_counts));
-    TZ_TRY(tzk_key_hist(ctx, ctx->d_frames, ctx->H, ctx->W, d.idx, nkeys, (unsigned*)d_counts));
-    TZ_TRY(tz_d2h(ctx, counts, d_counts, cb, ctx->stream));
-    return tz_stream_sync(ctx);
-}
-
 extern "C" int tz_keys_counts(tz_ctx* ctx, const int* idx, int nkeys, unsigned* counts) {
     tz_roctx_range roctx_("tz_keys_counts");
     if (!ctx || !counts) return TZ_ERR_INVALID;
     TZ_TRY(keys_resident(ctx, "tz_keys_counts"));
     TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys));
-    const int rc = keys_counts(ctx, idx, nkeys, counts);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    KeysDev d;
+    unsigned* d_counts;
+    const size_t cb = (size_t)nkeys * 4 * TZ_KEYS_A * sizeof(unsigned);
+    TZ_TRY(keys_upload(ctx, idx, nullptr, nullptr, nkeys, &d));
+    TZ_TRY(call.alloc(cb, &d_counts));
+    TZ_TRY(tzk_key_hist(ctx, ctx->d_frames, ctx->H, ctx->W, d.idx, nkeys, d_counts));
+    TZ_TRY(tz_d2h(ctx, counts, d_counts, cb, ctx->stream));
+    return tz_stream_sync(ctx);
 }
 
 static int keys_gray(tz_ctx* ctx, const int* idx, int nkeys, uint8_t* gray) {
@@ -3063,18 +2943,8 @@ extern "C" int tz_keys_gray(tz_ctx* ctx, const int* idx, int nkeys, uint8_t* gra
     if (!ctx || !gray) return TZ_ERR_INVALID;
     TZ_TRY(keys_resident(ctx, "tz_keys_gray"));
     TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys));
-    const int rc = keys_gray(ctx, idx, nkeys, gray);
-    tz_pool_release_all(ctx);
-    return rc;
-}
-
-static int keys_encode_dev(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const std::vector<unsigned long long>& off, size_t n,
-                           const uint8_t* lengths, size_t* bytes) {
-    KeysDev d;
-    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
-    TZ_TRY(keys_upload(ctx, idx, pred, &off, nkeys, &d));
-    TZ_TRY(tzk_key_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d.idx, d.pred, d.off, nkeys, ctx->d_keysym));
-    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);   // (dist 0: plain TZH1 codes)
+    tz_call call(ctx);
+    return keys_gray(ctx, idx, nkeys, gray);
 }
 
 static int keys_encode(tz_ctx* ctx, const KeysFmt& f, const char* who, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths,
@@ -3085,9 +2955,12 @@ static int keys_encode(tz_ctx* ctx, const KeysFmt& f, const char* who, const int
     TZ_TRY(keys_resident(ctx, who));
     TZ_TRY(keys_check(ctx, ctx->nt, idx, nkeys));
     TZ_TRY(keys_layout(ctx, f, pred, nkeys, ctx->H, ctx->W, &off, &n));
-    const int rc = keys_encode_dev(ctx, idx, nkeys, pred, off, n, lengths, bytes);
-    tz_pool_release_all(ctx);
-    return rc;
+    tz_call call(ctx);
+    KeysDev d;
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_keysym, &ctx->cap_keysym, n * 2));
+    TZ_TRY(keys_upload(ctx, idx, pred, &off, nkeys, &d));
+    TZ_TRY(tzk_key_resid(ctx, ctx->d_frames, ctx->H, ctx->W, d.idx, d.pred, d.off, nkeys, ctx->d_keysym));
+    return huff_encode_dev(ctx, ctx->d_keysym, n, lengths, TZ_KEYS_A, 0, bytes, 0, true);   // (dist 0: plain TZH1 codes)
 }
 
 extern "C" int tz_keys_encode(tz_ctx* ctx, const int* idx, int nkeys, const uint8_t* pred, const uint8_t* lengths, size_t* bytes) {
@@ -3164,7 +3037,13 @@ static int keys_put(tz_ctx* ctx, const KeysFmt& f, size_t offset, size_t count, 
     return TZ_OK;
 }
 
-static int keys_decode_dev(tz_ctx* ctx, const KeysFmt& f) {
+static int keys_decode(tz_ctx* ctx, const KeysFmt& f) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (ctx->keys_kind != f.kind || !ctx->d_keys || !ctx->d_keysym)
+        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode needs a stream staged with %s_begin / %s_put", f.who, f.who, f.who);
+    if (ctx->keys_put != ctx->keys_bytes)
+        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode: %zu of the stream's %zu bytes were put", f.who, ctx->keys_put, ctx->keys_bytes);
+    tz_call call(ctx);
     const int nt = ctx->keys_nt, H = ctx->keys_H, W = ctx->keys_W;
     size_t sw;
     TZ_TRY(huff_check_stream(ctx, ctx->keys_bytes, ctx->keys_n, TZ_HUFF_RUN, &sw));
@@ -3185,17 +3064,6 @@ static int keys_decode_dev(tz_ctx* ctx, const KeysFmt& f) {
     ctx->W = W;
     ctx->staged = true;
     return TZ_OK;
-}
-
-static int keys_decode(tz_ctx* ctx, const KeysFmt& f) {
-    if (!ctx) return TZ_ERR_INVALID;
-    if (ctx->keys_kind != f.kind || !ctx->d_keys || !ctx->d_keysym)
-        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode needs a stream staged with %s_begin / %s_put", f.who, f.who, f.who);
-    if (ctx->keys_put != ctx->keys_bytes)
-        return tz_fail(ctx, TZ_ERR_STATE, "%s_decode: %zu of the stream's %zu bytes were put", f.who, ctx->keys_put, ctx->keys_bytes);
-    const int rc = keys_decode_dev(ctx, f);
-    tz_pool_release_all(ctx);
-    return rc;
 }
 
 extern "C" int tz_keys_begin(tz_ctx* ctx, size_t bytes, int nt, int H, int W, const int* idx, int nkeys, const uint8_t* pred,

@@ -1,5 +1,6 @@
 // Internal declarations shared by the translation units of libtezip_hip.so (gfx950 only).
 #pragma once
+#include <assert.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -55,8 +56,9 @@ struct tz_ctx {
     bool own_stream = false;
     std::string last_error;
     // device scratch pool (staging of host-pointer arguments, temporaries): grown on demand and
-    // reused; the top bit of the size marks a block that is handed out until tz_pool_release_all
+    // reused; the top bit of the size marks a block that is handed out until the entry point's tz_call scope closes
     std::vector<std::pair<void*, size_t>> pool;
+    bool in_call = false;             // a tz_call scope is open (scopes do not nest)
     // model + rollout state
     tz_model* model = nullptr;
     int conv_impl = 1;                // tz_set_conv_impl: 1 = LDS-DMA kernels where they apply
@@ -241,8 +243,8 @@ static __device__ __forceinline__ double tz_sse_block(const uint8_t* __restrict_
 bool tz_is_device_ptr(const void* p);
 int tz_poison_byte();                                 // TEZIP_POISON diagnostic: 0x100 | byte, or 0
 int tz_poison(tz_ctx*, void* p, size_t bytes);        // fill a freshly handed-out device buffer when it is on
-int tz_pool_alloc(tz_ctx* ctx, size_t bytes, void** out);   // freed by tz_pool_release_all
-void tz_pool_release_all(tz_ctx* ctx);
+int tz_pool_alloc(tz_ctx* ctx, size_t bytes, void** out);   // handed out until the caller's tz_call scope closes
+void tz_pool_release_all(tz_ctx* ctx);                      // (~tz_call and tz_ctx_destroy alone)
 int tz_ensure(tz_ctx* ctx, void** buf, size_t* cap, size_t bytes);  // persistent buffer growth
 // Stream-ordered upload of a small host block to `dst` (device) through the pinned ring.
 int tz_upload(tz_ctx* ctx, void* dst, const void* src, size_t bytes);
@@ -258,7 +260,7 @@ int tz_h2d(tz_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s)
 int tz_d2h(tz_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s);
 // Input argument: returns a device pointer holding `bytes` of *p (staging if host).
 int tz_dev_in(tz_ctx* ctx, const void* p, size_t bytes, const void** dev);
-// Output argument: returns a device pointer to write; tz_dev_out_finish copies back if host.
+// Output argument: returns a device pointer to write; tz_call::finish copies back if host.
 struct tz_out {
     void* host = nullptr;
     void* dev = nullptr;
@@ -266,7 +268,47 @@ struct tz_out {
     bool done = false;  // already copied back (chunked hand-over on the copy stream)
 };
 int tz_dev_out(tz_ctx* ctx, void* p, size_t bytes, tz_out* o);
-int tz_dev_out_finish(tz_ctx* ctx, std::vector<tz_out>& outs);  // D2H copies + stream sync if any host
+
+// The scope of one entry point: opened once, behind the argument checks, it owns the outputs of the call
+// and hands every pool block back on whichever path the call leaves.  Helpers allocate from the pool under their caller's
+// scope and never release; a call that wants its blocks back half way closes a braced scope of its own first.
+struct tz_call {
+    tz_ctx* ctx;
+    std::vector<tz_out> outs;   // copied back by finish(), in this order
+    explicit tz_call(tz_ctx* c) : ctx(c) {
+        assert(!ctx->in_call);
+        ctx->in_call = true;
+    }
+    ~tz_call() {
+        tz_pool_release_all(ctx);
+        ctx->in_call = false;
+    }
+    tz_call(const tz_call&) = delete;
+    tz_call& operator=(const tz_call&) = delete;
+    template <class T>
+    int in(const T* p, size_t bytes, const T** dev) {   // tz_dev_in
+        const void* d = nullptr;
+        TZ_TRY(tz_dev_in(ctx, p, bytes, &d));
+        *dev = (const T*)d;
+        return TZ_OK;
+    }
+    template <class T>
+    int alloc(size_t bytes, T** p) {   // tz_pool_alloc
+        void* d = nullptr;
+        TZ_TRY(tz_pool_alloc(ctx, bytes, &d));
+        *p = (T*)d;
+        return TZ_OK;
+    }
+    template <class T>
+    int out(T* p, size_t bytes, T** dev) {   // tz_dev_out; the tz_out joins outs (outs.back())
+        tz_out o;
+        TZ_TRY(tz_dev_out(ctx, p, bytes, &o));
+        outs.push_back(o);
+        *dev = (T*)o.dev;
+        return TZ_OK;
+    }
+    int finish();   // D2H copies of the outputs not yet done + stream sync if any was a host pointer
+};
 
 // ---- profiling wrapper ------------------------------------------------------------------
 struct tz_prof_scope {

@@ -1277,24 +1277,18 @@ extern "C" int tz_predict_next(tz_ctx* ctx, const float* frames, int n, float* o
     tz_model* m = ctx->model;
     if (!m || !m->prepared) return tz_fail(ctx, TZ_ERR_STATE, "model not prepared");
     size_t fe = (size_t)m->Hp * m->Wp * m->stack[0];
-    const void* din;
-    tz_out o;
-    std::vector<tz_out> outs;
-    int rc = tz_dev_in(ctx, frames, fe * n * 4, &din);
-    if (rc == TZ_OK) rc = tz_dev_out(ctx, out, fe * n * 4, &o);
-    if (rc == TZ_OK) {
-        outs.push_back(o);
-        for (int b0 = 0; b0 < n && rc == TZ_OK; b0 += m->maxB) {
-            int nb = std::min(m->maxB, n - b0);
-            std::vector<int> isk(nb, 0), ii(nb), oi(nb);
-            for (int i = 0; i < nb; ++i) ii[i] = oi[i] = b0 + i;
-            rc = tz_model_predict_batch(ctx, nb, isk.data(), ii.data(), oi.data(), nullptr, 0, 0, (const float*)din,
-                                        (float*)o.dev);
-        }
+    tz_call call(ctx);
+    const float* din;
+    float* dout;
+    TZ_TRY(call.in(frames, fe * n * 4, &din));
+    TZ_TRY(call.out(out, fe * n * 4, &dout));
+    for (int b0 = 0; b0 < n; b0 += m->maxB) {
+        int nb = std::min(m->maxB, n - b0);
+        std::vector<int> isk(nb, 0), ii(nb), oi(nb);
+        for (int i = 0; i < nb; ++i) ii[i] = oi[i] = b0 + i;
+        TZ_TRY(tz_model_predict_batch(ctx, nb, isk.data(), ii.data(), oi.data(), nullptr, 0, 0, din, dout));
     }
-    if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
-    tz_pool_release_all(ctx);
-    return rc;
+    return call.finish();
 }
 
 // ---- activation probe (diagnostic): the device's TZ-PA1 scalar functions on caller-chosen inputs, and an exhaustive
@@ -1323,37 +1317,28 @@ __global__ __launch_bounds__(256) void k_recip_check(unsigned lo_bits, unsigned 
 extern "C" int tz_act_probe(tz_ctx* ctx, const float* x, size_t n, float* hard_sigmoid, float* tanh_out,
                             unsigned long long* recip_mismatches) {
     if (!ctx || (n && (!x || !hard_sigmoid || !tanh_out))) return TZ_ERR_INVALID;
-    int rc = TZ_OK;
+    tz_call call(ctx);
     if (n) {
-        const void* dx = nullptr;
-        std::vector<tz_out> outs;
-        tz_out o1, o2;
-        rc = tz_dev_in(ctx, x, n * 4, &dx);
-        if (rc == TZ_OK) rc = tz_dev_out(ctx, hard_sigmoid, n * 4, &o1);
-        if (rc == TZ_OK) outs.push_back(o1);
-        if (rc == TZ_OK) rc = tz_dev_out(ctx, tanh_out, n * 4, &o2);
-        if (rc == TZ_OK) outs.push_back(o2);
-        if (rc == TZ_OK) {
-            hipLaunchKernelGGL(k_act_probe, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
-                               (const float*)dx, n, (float*)o1.dev, (float*)o2.dev);
-            if (hipGetLastError() != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "k_act_probe launch failed");
-        }
-        if (rc == TZ_OK) rc = tz_dev_out_finish(ctx, outs);
+        const float* dx;
+        float *d_hs, *d_th;
+        TZ_TRY(call.in(x, n * 4, &dx));
+        TZ_TRY(call.out(hard_sigmoid, n * 4, &d_hs));
+        TZ_TRY(call.out(tanh_out, n * 4, &d_th));
+        hipLaunchKernelGGL(k_act_probe, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, ctx->stream, dx, n, d_hs,
+                           d_th);
+        if (hipGetLastError() != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "k_act_probe launch failed");
+        TZ_TRY(call.finish());
     }
-    if (rc == TZ_OK && recip_mismatches) {   // every float32 d in [4, 2^27]: tz_tanh reaches [4.49, 6.6e7]
-        void* d_bad = nullptr;
-        rc = tz_pool_alloc(ctx, 8, &d_bad);
-        if (rc == TZ_OK) {
-            TZ_HIP(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
-            hipLaunchKernelGGL(k_recip_check, dim3(4096), dim3(256), 0, ctx->stream, 0x40800000u, 0x4D000000u,
-                               (unsigned long long*)d_bad);
-            TZ_HIP(ctx, hipGetLastError());
-            TZ_HIP(ctx, hipMemcpyAsync(recip_mismatches, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-            TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
+    if (recip_mismatches) {   // every float32 d in [4, 2^27]: tz_tanh reaches [4.49, 6.6e7]
+        unsigned long long* d_bad;
+        TZ_TRY(call.alloc(8, &d_bad));
+        TZ_HIP(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(k_recip_check, dim3(4096), dim3(256), 0, ctx->stream, 0x40800000u, 0x4D000000u, d_bad);
+        TZ_HIP(ctx, hipGetLastError());
+        TZ_HIP(ctx, hipMemcpyAsync(recip_mismatches, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+        TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    tz_pool_release_all(ctx);
-    return rc;
+    return TZ_OK;
 }
 
 extern "C" int tz_predict_tap(tz_ctx* ctx, int kind, int level, float* out) {
