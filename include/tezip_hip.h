@@ -567,6 +567,48 @@ int tz_huffd_encode_buf(tz_ctx* ctx, const int16_t* in, size_t n, const uint8_t*
 int tz_huffd_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t bytes, size_t n, const uint8_t* lengths, int A, int base,
                         int R, int D, int16_t* out);
 
+/* ---- the bound for a compression-ratio target (no reference counterpart; `tezip.py -c --target-ratio R --coder huff|huffr|huffd`;
+ * definition TZ-TRATIO-1 in DESIGN.md section 9 and tezip_amd/ratetarget.py) ------------------------------------------------------
+ * With a GPU coder the size of entropy.dat is an exact function of integer counts.  tz_size_probe: one candidate bound.  On
+ * the context's ENCODER rollout (state rules, the refusal of a stack with colour under tz_set_payload_channels(ctx, 1) and
+ * the errors of a bound are tz_encode's) *out describes the stream that tz_encode(ctx, mode, b0, b1, entropy, NULL, ...),
+ * tz_<coder>_counts, the host's choice of the code (tz_huff_lengths / tz_huffr_lengths, tezip_amd/huffd.py: choose) and
+ * tz_<coder>_encode would leave, in the payload layout in force (flat, tz_set_payload_channels(ctx, 1),
+ * tz_set_delta_stride(ctx, 1)); a candidate that chain refuses (values that span more than TZ_NBINS symbols, a stream of 2^32
+ * words) is refused here with the same status and message.  A probe forms the delta stack, quantises it and reads the result
+ * twice: k_size_count forms every payload symbol on the fly, in front of the rank remap, and fills the plain histogram and the
+ * token histograms at match distance 1 and 3; the host builds the table, permutes the counts by it and derives the code;
+ * k_size_bits sums the bits per run of 256 and chunk of 64 runs under that code, rounds every chunk up to 32-bit words and
+ * returns their total.  No payload, remapped copy, index or bit stream is made, and nothing of the context changes: a
+ * resident payload, its kind, a resident stream, predictions, frames and rollout state are as they were.
+ *  entropy: 0 or 1 as tz_encode's (byte planes, bit 1, are TZ_ERR_INVALID); coder: 0 = huff, 1 = huffr, 2 = huffd.
+ *  out: host. */
+typedef struct {
+    unsigned long long n;             /* payload elements */
+    unsigned long long stream_words;  /* 32-bit words of the bit stream */
+    unsigned long long bytes;         /* index | bits: what tz_<coder>_encode reports in *bytes */
+    unsigned long long cost_bits[3];  /* stream bits in front of the chunks' padding at match distance 0 | 1 | 3 (huffd: the three
+                                         totals of its choice; huff: [0] alone, huffr: [2] alone, the others 0) */
+    int A, base;                      /* the literals of the code, as tz_<coder>_counts reports them */
+    int dist;                         /* the match distance of the stream: 0 (huff), 3 (huffr), huffd's choice */
+    int table_len;                    /* length of the rank table, -1 without one (entropy == 0) */
+} tz_size_record;                     /* 64 bytes */
+int tz_size_probe(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int coder, tz_size_record* out);
+/* The two kernels alone, over any int16 stack q of nq elements (host or device, 2-byte aligned) read as the quantised deltas of
+ * the layout (channels, stride): (3, 1) flat, (3, 3) the channel stride, (1, 1) one channel -- q then holds whole pixels (nq % 3
+ * == 0) and yields nq / 3 symbols.  Symbol i is the spatial delta of the layout (the first `stride` symbols: the element
+ * itself), then 1600 - it when apply_offset.  Bins: TZ_SIZE_BINS literal bins (bin = symbol + TZ_SIZE_BIAS), then T_0..T_7.
+ * tz_size_count_buf: counts (host) receives 3 rows of TZ_SIZE_BINS + 8 entries, match distance 0 | 1 | 3 as tz_huffd_counts';
+ * *bad: a symbol outside the bins.  tz_size_bits_buf: lens (host) holds TZ_SIZE_BINS + 8 code lengths by bin; *bits the sum
+ * of the stream's bits at the match distance dist (0, 1 or 3), *words the sum over the chunks of ceil(bits / 32), *bad: a
+ * symbol or token of length 0. */
+#define TZ_SIZE_BINS 4096
+#define TZ_SIZE_BIAS 1024
+int tz_size_count_buf(tz_ctx* ctx, const int16_t* q, size_t nq, int channels, int stride, int apply_offset,
+                      unsigned long long* counts /* [3][TZ_SIZE_BINS + 8] */, int* bad);
+int tz_size_bits_buf(tz_ctx* ctx, const int16_t* q, size_t nq, int channels, int stride, int apply_offset, const uint8_t* lens,
+                     int dist, unsigned long long* words, unsigned long long* bits, int* bad);
+
 /* ---- opt-in key-frame coder (`tezip.py -c --key-coder huff`, format TZK1 in DESIGN.md section 9, slow statement of it in
  * tezip_amd/keycoder.py; no reference counterpart: compress.py:271-278 hands a zero-except-keys stack to zstd) -----------------
  * Only the key frames are stored: each as the residuals mod 256 of one of four predictors over its own samples (0: none,

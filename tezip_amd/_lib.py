@@ -142,6 +142,10 @@ _SIGS = {
                                       C.c_void_p]),
     "tz_huffr_decode_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p]),
+    "tz_size_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    "tz_size_count_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "tz_size_bits_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                   C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_int)]),
     "tz_keys_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tz_keys_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
     "tz_keys_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
@@ -175,6 +179,11 @@ class FrameQuality(C.Structure):
 
 
 QUALITY_DTYPE = np.dtype([("sse", "<u8"), ("max_abs", "<u4"), ("n_changed", "<u4")])   # the same layout as a numpy record
+# tz_size_record (64 bytes): one candidate of tz_size_probe
+SIZE_DTYPE = np.dtype([("n", "<u8"), ("stream_words", "<u8"), ("bytes", "<u8"), ("cost_bits", "<u8", (3,)), ("A", "<i4"), ("base", "<i4"),
+                       ("dist", "<i4"), ("table_len", "<i4")])
+SIZE_CODERS = {"huff": 0, "huffr": 1, "huffd": 2}   # the `coder` argument of tz_size_probe
+SIZE_BINS, SIZE_BIAS = 4096, 1024                   # TZ_SIZE_BINS, TZ_SIZE_BIAS: the literal bins of the size seams
 
 _LIB = None
 
@@ -1066,6 +1075,36 @@ class Context:
 
     def huffd_decode_buf(self, stream, n, lengths, base, dist, run=256, out=None):
         return self._stream_decode_buf(self.lib.tz_huffd_decode_buf, stream, n, lengths, base, run, out, HUFFR_NTOK, dist)
+
+    # ---- the bound for a compression-ratio target (definition TZ-TRATIO-1: tezip_amd/ratetarget.py)
+    def size_probe(self, mode, bound, entropy=True, coder="huffd"):
+        """tz_size_probe after rollout: one SIZE_DTYPE record of the stream that encode(mode, bound, entropy, payload="resident"),
+        <coder>_counts, the choice of the code and <coder>_encode would leave, without a payload, in the payload layout in
+        force.  Nothing of the context changes."""
+        b0, b1 = _bounds(bound)
+        out = np.zeros(1, SIZE_DTYPE)
+        self._ck(self.lib.tz_size_probe(self.h, MODES[mode], b0, b1, int(bool(entropy)), SIZE_CODERS[coder], out.ctypes.data))
+        return out[0]
+
+    def size_count_buf(self, q, channels=3, stride=1, offset=True):
+        """tz_size_count_buf: k_size_count over the int16 stack q (host array or device tensor) read in the layout (channels,
+        stride) -> (uint64[3][SIZE_BINS + 8], bad): ratetarget.count_of."""
+        counts = np.zeros((3, SIZE_BINS + HUFFR_NTOK), np.uint64)
+        bad = C.c_int(0)
+        self._ck(self.lib.tz_size_count_buf(self.h, _ptr(q), _numel(q), int(channels), int(stride), int(bool(offset)), counts.ctypes.data,
+                                            C.byref(bad)))
+        return counts, bool(bad.value)
+
+    def size_bits_buf(self, q, lens, dist, channels=3, stride=1, offset=True):
+        """tz_size_bits_buf: k_size_bits over q under the SIZE_BINS + 8 code lengths `lens` (by bin, then the tokens) at the match
+        distance dist -> (words, bits, bad): ratetarget.bits_of."""
+        ln = np.ascontiguousarray(lens, np.uint8)
+        if ln.size != SIZE_BINS + HUFFR_NTOK:
+            raise ValueError("%d code lengths, %d + %d wanted" % (ln.size, SIZE_BINS, HUFFR_NTOK))
+        words, bits, bad = C.c_ulonglong(0), C.c_ulonglong(0), C.c_int(0)
+        self._ck(self.lib.tz_size_bits_buf(self.h, _ptr(q), _numel(q), int(channels), int(stride), int(bool(offset)), ln.ctypes.data,
+                                           int(dist), C.byref(words), C.byref(bits), C.byref(bad)))
+        return int(words.value), int(bits.value), bool(bad.value)
 
     # ---- operator seams
     def delta_encode(self, pred, orig, zero_mask=None, out=None):

@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, quality, sdelta, sidecar, target, weights, zstd
+from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, quality, ratetarget, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -387,14 +387,10 @@ def _huff_entropy_file(ctx, path, n, trailer, verbose, coder="huff"):
     return _write_coded(path, front, nbytes, ctx.huff_get, "huffman_coding" if verbose else None, t0)
 
 
-def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False,
-                    key_coder="zstd", channels=3, strided=False):
-    """key_frame.dat and entropy.dat (compress.py:271-278, 375-400) from the context-resident frames
-    and payload, piece by piece: nothing of size nt*H*W lives on the host.  channels: what the resident payload stores per
-    pixel (1: a gray job, tezip_amd/graypayload.py); key_frame.dat has three either way.  strided: the payload's spatial delta
-    ran at the channel stride (tezip_amd/sdelta.py): the trailer says so in the first entry of its shape."""
+def _key_output(ctx, out_dir, nt, H, W, key, pool, stages=None, verbose=False, key_coder="zstd"):
+    """key_frame.dat (compress.py:271-278) from the context-resident frames -> a future of its size.  Nothing of it depends on
+    the payload: _stream_outputs starts it in front of entropy.dat, a --target-ratio job in front of its search."""
     n_key = nt * H * W * 3
-    n = nt * H * W * channels
     key_idx = [int(i) for i in np.nonzero(key)[0]]
     zero = np.zeros((H, W, 3), np.uint8)
     if key_coder in ("huff", "huffg"):
@@ -431,6 +427,13 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
                 sc.write(ctx.frames_get(i, 1)[0] if i in is_key else zero)
             ksize = sc.close()
         kf = _Done(ksize)
+    return kf
+
+
+def _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages=None, coder="zstd", verbose=False, channels=3, strided=False):
+    """entropy.dat (compress.py:375-400) from the context-resident payload, piece by piece -> its size.  channels, strided: as
+    _stream_outputs'."""
+    n = nt * H * W * channels
     if table is not None:
         tail = np.concatenate([table.astype(np.int64), [len(table)]])
     else:
@@ -442,7 +445,7 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
         esize = _huff_entropy_file(ctx, os.path.join(out_dir, "entropy.dat"), n, trailer, verbose, coder)
         if stages:
             stages.add("huffman coding + fetch entropy.dat", time.perf_counter() - t_e)
-        return kf.result(), esize
+        return esize
     bufs = [np.empty(min(PAYLOAD_CHUNK, n), np.int16) for _ in range(2)]
     with open(os.path.join(out_dir, "entropy.dat"), mode='wb') as f:
         sc = zstd.StreamCompressor(f, n * 2 + trailer.nbytes, 9, zstd.default_threads())
@@ -454,6 +457,17 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
         esize = sc.close()
     if stages:
         stages.add("payload fetch + zstd-9 entropy.dat", time.perf_counter() - t_e)
+    return esize
+
+
+def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False,
+                    key_coder="zstd", channels=3, strided=False):
+    """key_frame.dat and entropy.dat (compress.py:271-278, 375-400) from the context-resident frames
+    and payload, piece by piece: nothing of size nt*H*W lives on the host.  channels: what the resident payload stores per
+    pixel (1: a gray job, tezip_amd/graypayload.py); key_frame.dat has three either way.  strided: the payload's spatial delta
+    ran at the channel stride (tezip_amd/sdelta.py): the trailer says so in the first entry of its shape."""
+    kf = _key_output(ctx, out_dir, nt, H, W, key, pool, stages, verbose, key_coder)
+    esize = _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages, coder, verbose, channels, strided)
     return kf.result(), esize
 
 
@@ -486,11 +500,23 @@ def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
 SSIM_NEEDS_REPORT = "--ssim extends the compression report: add --report"
 TARGET_NEEDS_ABS = "--target-psnr finds the abs bound itself: it takes the place of -m and -b"
 TARGET_NOT_SHARDED = "--target-psnr is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+RATIO_NEEDS_ABS = "--target-ratio finds the abs bound itself: it takes the place of -m, -b and --target-psnr"
+RATIO_NOT_SHARDED = "--target-ratio is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+RATIO_NEEDS_CODER = ("--target-ratio needs a coder whose file size is an exact function of counts (zstd's is not known without "
+                     "running zstd): add --coder huffd")
+RATIO_NO_SHUFFLE = "--target-ratio cannot be combined with --shuffle (byte planes are not Huffman-coded)"
+
+
+def check_ratio(ratio, mode, bound, target_psnr, coder, shuffle, sharded):
+    """The refusals of --target-ratio that tezip.py and a direct caller of run() share: None, or the message."""
+    return (ratetarget.check_target(ratio) or (RATIO_NEEDS_ABS if mode != "abs" or bound or target_psnr is not None else None)
+            or (RATIO_NOT_SHARDED if sharded else None) or (RATIO_NO_SHUFFLE if shuffle else None)
+            or (RATIO_NEEDS_CODER if coder not in ratetarget.CODERS else None))
 
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
-        SSIM=False, TARGET_PSNR=None):
+        SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -528,6 +554,14 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     goes on as `-m abs -b <found>`: every file is what that job writes, one line says what was found, and bound_search.json
     (target, limit, the probes, the result) is written besides.  Works with every other flag above.  Single-GPU jobs only.
     With VERBOSE the quantiser time printed as error_bound includes the probes'.
+    TARGET_RATIO (--target-ratio; NOT in the reference; MODE "abs", an empty BOUND_VALUE, no TARGET_PSNR, CODER "huff", "huffr" or
+    "huffd", no SHUFFLE): the abs bound is found on the device for "the files may take raw / TARGET_RATIO bytes" (definition
+    TZ-TRATIO-1: tezip_amd/ratetarget.py).  key_frame.dat is written in front of the search, whose budget it counts against; at
+    most 11 tz_size_probe calls on the one rollout give the exact size of every candidate's entropy.dat; the job goes on as
+    `-m abs -b <found>`: every file is what that job writes, one line says what was found, and bound_search.json (target,
+    budget, the probes, the result) is written besides.  A target that abs 255 misses: the message, bound_search.json with a
+    null result, no entropy.dat, exit status 4.  Works with every KEY_CODER, GRAY, SDELTA, REPORT, SSIM and DIGESTS.
+    Single-GPU jobs only.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -536,6 +570,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if not GPU_FLAG:
         print("ERROR: this build runs the compression path on an AMD MI355X only (no CPU path).")
         exit()
+    if TARGET_RATIO is not None:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
+        problem = check_ratio(TARGET_RATIO, MODE, BOUND_VALUE, TARGET_PSNR, CODER, SHUFFLE, tzdist.active() is not None)
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     problem = (check_coder(CODER, SHUFFLE, tzdist.active() is not None) or check_key_coder(KEY_CODER, tzdist.active() is not None)
                or check_gray(GRAY, tzdist.active() is not None) or check_sdelta(SDELTA, tzdist.active() is not None))
     if problem:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
@@ -606,6 +645,21 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 BOUND_VALUE = [target.bound_of(k)]
                 print(target.stdout_line(search_doc))
                 stages.mark("bound search (device)")
+            if TARGET_RATIO is not None:   # likewise; the budget counts the files that do not depend on the bound, so they come first
+                _key_output(ctx, OUTPUT_DIR, nt, H, W, key, pool, stages, VERBOSE, KEY_CODER).result()
+                fixed = sum(os.path.getsize(os.path.join(OUTPUT_DIR, f)) for f in ("filename.txt", "key_frame.dat"))
+                raw = nt * H * W * 3
+                limit = ratetarget.budget(raw, TARGET_RATIO)
+                k, trace = ratetarget.search(lambda c: ratetarget.file_bytes(
+                    ctx.size_probe("abs", [ratetarget.bound_of(c)], ENTROPY_RUN, CODER), CODER), fixed, limit)
+                search_doc = ratetarget.make(TARGET_RATIO, raw, limit, fixed, trace, k)
+                stages.mark("key_frame.dat + bound search (device)")
+                if k is None:
+                    print(ratetarget.unreachable_line(search_doc))
+                    ratetarget.write(OUTPUT_DIR, search_doc)
+                    sys.exit(ratetarget.EXIT_UNREACHABLE)
+                BOUND_VALUE = [ratetarget.bound_of(k)]
+                print(ratetarget.stdout_line(search_doc))
             _, table, _ = ctx.encode(MODE, BOUND_VALUE, ENTROPY_RUN, payload="resident", shuffle=SHUFFLE)
             stages.mark("encode (payload resident)", ctx)
             if REPORT:   # stream-ordered before _stream_outputs fetches the payload; changes nothing it reads
@@ -635,8 +689,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     # the spatial-delta kernel here (timed above), what is left is the host-side sort
                     print("table_create:{0}".format(prof["table_create"][0] / 1e3) + "[sec]")
                     print("replacing_based_on_frequency:{0}".format(prof["lut_remap"][0] / 1e3) + "[sec]")
-            _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
-                            coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided)
+            if TARGET_RATIO is not None:   # (key_frame.dat is there already)
+                _entropy_output(ctx, OUTPUT_DIR, nt, H, W, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, stages, coder=CODER,
+                                verbose=VERBOSE, channels=channels, strided=strided)
+            else:
+                _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
+                                coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided)
             doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),   # the contract the predictions were made under
                                 payload_channels=channels, sdelta="channel" if strided else "flat")
             if VERBOSE:
@@ -651,6 +709,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     print(line)
             if TARGET_PSNR is not None:
                 target.write(OUTPUT_DIR, search_doc)
+            if TARGET_RATIO is not None:
+                ratetarget.write(OUTPUT_DIR, search_doc)
             if DIGESTS:  # last: every other file is what it is without the flag
                 digest.write(OUTPUT_DIR, digest.make(dig[0], dig[1], (H, W, 3)))
         finally:

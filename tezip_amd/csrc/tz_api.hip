@@ -2832,6 +2832,201 @@ extern "C" int tz_huffd_decode_buf(tz_ctx* ctx, const uint8_t* stream, size_t by
     return huff_decode_buf(ctx, f, stream, bytes, n, lengths, A, base, R, out);
 }
 
+// --------------------------------------------------------------------------- the size of a candidate bound (TZ-TRATIO-1)
+// `-c --target-ratio` (NOT a reference feature; DESIGN.md section 9, tezip_amd/ratetarget.py): with a GPU coder the size of
+// entropy.dat is an exact function of integer counts, so a candidate bound costs a quantiser run and two reads of its output
+// (k_size_count, k_size_bits) -- no spatial delta stack, no remapped payload, no index, no bit stream.  Between the two kernels
+// the host does what the real job does between tz_encode, tz_<coder>_counts and tz_<coder>_encode, on counts: the rank table
+// from the plain histogram (tz_build_table), the counts permuted by it (the remap is a bijection on the symbols present, so
+// the token histograms of the remapped payload are these with the literals moved), A and base, the code lengths
+// (tz_huff_lengths / tz_huffr_lengths) and, for huffd, the distance by tezip_amd/huffd.py's rule.  Every refusal of that chain
+// is made here with its status and message.
+static_assert(TZ_SIZE_BINS == TZ_HUFF_COUNT_BINS && TZ_SIZE_BIAS == TZ_HUFF_COUNT_BIAS, "the seams' bins are k_huffd_count's");
+static constexpr int SZ_BINS = TZ_HUFF_COUNT_BINS + TZ_HUFFR_NTOK;
+static const char* const kSizeWho[3] = {"tz_huff", "tz_huffr", "tz_huffd"};
+
+// h: the three rows of k_size_count (unremapped symbols).  -> rec (all but stream_words and bytes) and lens, the LUT of k_size_bits
+static int size_code(tz_ctx* ctx, const unsigned long long* h, bool bad, size_t n, int entropy, int coder, tz_size_record* rec,
+                     std::vector<uint8_t>* lens) {
+    const char* who = kSizeWho[coder];
+    std::vector<int16_t> lut;
+    rec->table_len = -1;
+    if (entropy) {   // tz_encode: the table from the counts of the symbols inside [0, TZ_NBINS)
+        std::vector<unsigned long long> hist(TZ_NBINS);
+        for (int y = 0; y < TZ_NBINS; ++y) hist[y] = h[y + TZ_HUFF_COUNT_BIAS];
+        int16_t table[TZ_MAX_TABLE];
+        TZ_TRY(tz_build_table(hist.data(), TZ_NBINS, table, &rec->table_len));
+        TZ_TRY(build_enc_lut(ctx, table, rec->table_len, &lut));
+    }
+    const auto rank = [&](int v) { return entropy && v >= 0 && v <= TZ_NBINS ? (int)lut[v] : v; };   // k_lut
+    // the histograms of the remapped payload: literals moved to their ranks, tokens as they are
+    std::vector<unsigned long long> r(3 * (size_t)SZ_BINS, 0);
+    for (int d = 0; d < 3; ++d) {
+        for (int b = 0; b < TZ_HUFF_COUNT_BINS; ++b)
+            if (h[d * SZ_BINS + b]) {
+                const int rb = rank(b - TZ_HUFF_COUNT_BIAS) + TZ_HUFF_COUNT_BIAS;
+                if (rb < 0 || rb >= TZ_HUFF_COUNT_BINS) bad = true;
+                else r[d * SZ_BINS + rb] += h[d * SZ_BINS + b];
+            }
+        for (int k = 0; k < TZ_HUFFR_NTOK; ++k) r[d * SZ_BINS + TZ_HUFF_COUNT_BINS + k] = h[d * SZ_BINS + TZ_HUFF_COUNT_BINS + k];
+    }
+    int lo = -1, hi = -1;   // huff_counts_dev
+    for (int b = 0; b < TZ_HUFF_COUNT_BINS; ++b)
+        if (r[b]) {
+            if (lo < 0) lo = b;
+            hi = b;
+        }
+    if (bad || lo < 0 || hi - lo + 1 > TZ_NBINS)
+        return tz_fail(ctx, TZ_ERR_INVALID, "%s_counts: the payload's values span more than %d symbols", who, TZ_NBINS);
+    const int A = hi - lo + 1, base = lo - TZ_HUFF_COUNT_BIAS;
+    // the code of every distance the coder may name (huff: 0, huffr: 3, huffd: all three) and its cost
+    static const int kDist[3] = {0, 1, 3};
+    std::vector<uint8_t> len[3];
+    int best = -1;
+    for (int d = 0; d < 3; ++d) {
+        rec->cost_bits[d] = 0;
+        if (coder != 2 && d != (coder == 0 ? 0 : 2)) continue;
+        std::vector<unsigned long long> c(A + TZ_HUFFR_NTOK, 0);
+        for (int s = 0; s < A; ++s) c[s] = r[d * SZ_BINS + lo + s];
+        for (int k = 0; k < TZ_HUFFR_NTOK; ++k) c[A + k] = r[d * SZ_BINS + TZ_HUFF_COUNT_BINS + k];
+        len[d].assign(A + TZ_HUFFR_NTOK, 0);
+        if ((d == 0 ? tz_huff_lengths(c.data(), A, TZ_HUFF_L, len[d].data()) : tz_huffr_lengths(c.data(), A + TZ_HUFFR_NTOK, TZ_HUFF_L, len[d].data())) != TZ_OK)
+            return tz_fail(ctx, TZ_ERR_INVALID, "%s_lengths refused the counts of the candidate", who);
+        unsigned long long cost = 0;
+        for (int s = 0; s < A + TZ_HUFFR_NTOK; ++s) cost += c[s] * len[d][s];
+        for (int k = 0; k < TZ_HUFFR_NTOK; ++k) cost += c[A + k] * (unsigned long long)k;
+        rec->cost_bits[d] = cost;
+        if (best < 0 || cost < rec->cost_bits[best]) best = d;   // (a tie goes to the smaller distance)
+    }
+    rec->n = n;
+    rec->A = A;
+    rec->base = base;
+    rec->dist = kDist[best];
+    lens->assign(SZ_BINS, 0);
+    for (int b = 0; b < TZ_HUFF_COUNT_BINS; ++b) {
+        const int s = rank(b - TZ_HUFF_COUNT_BIAS) - base;
+        if (s >= 0 && s < A) (*lens)[b] = len[best][s];
+    }
+    for (int k = 0; k < TZ_HUFFR_NTOK; ++k) (*lens)[TZ_HUFF_COUNT_BINS + k] = len[best][A + k];
+    return TZ_OK;
+}
+
+// the two kernels and the host between them, on the n symbols the device stack d_q yields under `layout`
+static int size_run(tz_ctx* ctx, tz_layout layout, const int16_t* d_q, size_t n, int entropy, int coder, tz_size_record* rec) {
+    if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    unsigned long long* d_hist;
+    tz_huff_meta *d_meta, meta;
+    tz_size_meta *d_smeta, smeta;
+    uint8_t* d_lens;
+    std::vector<unsigned long long> h(3 * (size_t)SZ_BINS);
+    TZ_TRY(tz_pool_alloc(ctx, h.size() * sizeof(unsigned long long), (void**)&d_hist));
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(meta), (void**)&d_meta));
+    TZ_TRY(tzk_size_count(ctx, layout, d_q, n, entropy, d_hist, d_meta));
+    TZ_TRY(tz_d2h(ctx, h.data(), d_hist, h.size() * sizeof(unsigned long long), ctx->stream));
+    TZ_TRY(tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
+    std::vector<uint8_t> lens;
+    TZ_TRY(size_code(ctx, h.data(), meta.bad != 0, n, entropy, coder, rec, &lens));
+    TZ_TRY(tz_pool_alloc(ctx, lens.size(), (void**)&d_lens));
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(smeta), (void**)&d_smeta));
+    TZ_TRY(tz_upload(ctx, d_lens, lens.data(), lens.size()));
+    TZ_TRY(tzk_size_bits(ctx, layout, d_q, n, entropy, d_lens, rec->dist, d_smeta));
+    TZ_TRY(tz_d2h(ctx, &smeta, d_smeta, sizeof(smeta), ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
+    if (smeta.bad) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: the payload holds a value the code lengths give no code");
+    if (smeta.words >= (1ull << 32)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: a bit stream of %llu words does not fit the format", smeta.words);
+    const int di = rec->dist == 0 ? 0 : rec->dist == 1 ? 1 : 2;
+    if (smeta.bits != rec->cost_bits[di])
+        return tz_fail(ctx, TZ_ERR_HIP, "tz_size_probe: k_size_bits summed %llu bits, the counts of k_size_count give %llu", smeta.bits, rec->cost_bits[di]);
+    size_t nruns, nchunks, index_bytes;
+    huff_geometry(n, &nruns, &nchunks, &index_bytes);
+    rec->stream_words = smeta.words;
+    rec->bytes = index_bytes + smeta.words * 4;
+    return TZ_OK;
+}
+
+extern "C" int tz_size_probe(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int coder, tz_size_record* out) {
+    tz_roctx_range roctx_("tz_size_probe");
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    if (coder < 0 || coder > 2) return tz_fail(ctx, TZ_ERR_INVALID, "tz_size_probe: coder %d, 0 (huff), 1 (huffr) or 2 (huffd) wanted", coder);
+    if (entropy & ~1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_size_probe: byte planes are not Huffman-coded");
+    TZ_TRY(encode_check(ctx, "tz_size_probe", mode));
+    const tz_layout layout = layout_of(ctx);
+    if (layout.channels == 1) {
+        tz_call gray_check(ctx);   // (a scope of its own: the probe reuses its blocks)
+        TZ_TRY(encode_all_gray(ctx));
+    }
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
+    const size_t N = (size_t)nt * H * W * 3;
+    tz_call call(ctx);
+    uint8_t* d_mask;
+    int16_t* d_q;
+    TZ_TRY(call.alloc(nt, &d_mask));
+    TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
+    TZ_TRY(call.alloc(N * 2, &d_q));
+    // compress.py:292-319 as encode_front's general path runs them (the quantiser walks three channels in every layout)
+    TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, d_mask, nt, H, W, ctx->Hp, ctx->Wp, d_q));
+    TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
+    memset(out, 0, sizeof(*out));
+    return size_run(ctx, layout, d_q, (size_t)nt * tz_frame_elems(layout, H, W), entropy, coder, out);
+}
+
+// the layout of a seam: 3 channels at stride 1 (flat) or 3 (channel stride), 1 channel at stride 1 (gray: q holds whole pixels)
+static int size_seam_layout(tz_ctx* ctx, size_t nq, int channels, int stride, tz_layout* layout, size_t* n) {
+    if (!((channels == 3 && (stride == 1 || stride == 3)) || (channels == 1 && stride == 1)))
+        return tz_fail(ctx, TZ_ERR_INVALID, "size probe: no payload layout of %d channels at stride %d", channels, stride);
+    if (channels == 1 && nq % 3) return tz_fail(ctx, TZ_ERR_INVALID, "size probe: a one-channel payload describes whole pixels, not %zu elements", nq);
+    *layout = tz_layout{channels, stride};
+    *n = channels == 1 ? nq / 3 : nq;
+    return TZ_OK;
+}
+
+extern "C" int tz_size_count_buf(tz_ctx* ctx, const int16_t* q, size_t nq, int channels, int stride, int apply_offset,
+                                 unsigned long long* counts, int* bad) {
+    if (!ctx || !q || !counts || !bad) return TZ_ERR_INVALID;
+    tz_layout layout;
+    size_t n;
+    TZ_TRY(size_seam_layout(ctx, nq, channels, stride, &layout, &n));
+    if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    tz_call call(ctx);
+    const int16_t* d_q;
+    unsigned long long* d_hist;
+    tz_huff_meta *d_meta, meta;
+    TZ_TRY(call.in(q, nq * 2, &d_q));
+    TZ_TRY(call.alloc(3 * (size_t)SZ_BINS * sizeof(unsigned long long), &d_hist));
+    TZ_TRY(call.alloc(sizeof(meta), &d_meta));
+    TZ_TRY(tzk_size_count(ctx, layout, d_q, n, apply_offset ? 1 : 0, d_hist, d_meta));
+    TZ_TRY(tz_d2h(ctx, counts, d_hist, 3 * (size_t)SZ_BINS * sizeof(unsigned long long), ctx->stream));
+    TZ_TRY(tz_d2h(ctx, &meta, d_meta, sizeof(meta), ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
+    *bad = meta.bad != 0;
+    return TZ_OK;
+}
+
+extern "C" int tz_size_bits_buf(tz_ctx* ctx, const int16_t* q, size_t nq, int channels, int stride, int apply_offset, const uint8_t* lens,
+                                int dist, unsigned long long* words, unsigned long long* bits, int* bad) {
+    if (!ctx || !q || !lens || !words || !bits || !bad) return TZ_ERR_INVALID;
+    tz_layout layout;
+    size_t n;
+    TZ_TRY(size_seam_layout(ctx, nq, channels, stride, &layout, &n));
+    if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
+    tz_call call(ctx);
+    const int16_t* d_q;
+    uint8_t* d_lens;
+    tz_size_meta *d_smeta, smeta;
+    TZ_TRY(call.in(q, nq * 2, &d_q));
+    TZ_TRY(call.alloc(SZ_BINS, &d_lens));
+    TZ_TRY(call.alloc(sizeof(smeta), &d_smeta));
+    TZ_TRY(tz_upload(ctx, d_lens, lens, SZ_BINS));
+    TZ_TRY(tzk_size_bits(ctx, layout, d_q, n, apply_offset ? 1 : 0, d_lens, dist, d_smeta));
+    TZ_TRY(tz_d2h(ctx, &smeta, d_smeta, sizeof(smeta), ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));
+    *words = smeta.words;
+    *bits = smeta.bits;
+    *bad = smeta.bad != 0;
+    return TZ_OK;
+}
+
 // --------------------------------------------------------------------------- key-frame coders (TZK1, TZK2)
 // `--key-coder huff` (NOT a reference feature: compress.py:271-278 hands a zero-except-keys stack of the whole sequence to
 // zstd): the key frames alone, as predictor residuals under one TZH1 code (tezip_amd/keycoder.py, k_key_* in tz_codec.hip).

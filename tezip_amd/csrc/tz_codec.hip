@@ -4077,6 +4077,215 @@ int tzk_huff_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run
     return TZ_OK;
 }
 
+// ---------------------------------------------------------------------------- size of a candidate bound
+// tz_size_probe (`-c --target-ratio`, definition TZ-TRATIO-1: DESIGN.md section 9, slow statement in tezip_amd/ratetarget.py
+// count_of / bits_of): what the entropy coders would make of the quantised delta stack q, without a payload.  Both kernels
+// form the payload symbols on the fly -- the spatial delta of the layout (k_sdelta: flat, k_sdelta_gray: channel 0 alone,
+// k_sdelta_s3: the channel stride; the stream start has no element in front, sd = x), then 1600 - sd when apply_offset --
+// and stop in front of the rank remap: it is a bijection on the symbols present, so equality at a distance is the payload's
+// and the host permutes the literal counts.  Geometry and structure are k_huffd_count's: one lane per run of 256 symbols,
+// 16-byte loads, no match across a run start.
+enum { SZ_FLAT = 0, SZ_GRAY = 1, SZ_S3 = 2 };
+
+// Walks the run of `cnt` symbols at symbol r0 (a multiple of 256) of the n symbols q yields: f(j, s) once per symbol, j its
+// place in the run.  q holds n elements, 3 n under SZ_GRAY; VEC: q is 16-byte aligned.
+template <int LAY, bool VEC, class F>
+__device__ __forceinline__ void sz_walk(const int16_t* __restrict__ q, size_t n, size_t r0, int cnt, int apply_offset, F&& f) {
+    constexpr int STRIDE = LAY == SZ_S3 ? 3 : 1;
+    short p1 = 0, p2 = 0, p3 = 0;   // the elements one, two and three symbols in front
+    if (r0) {
+        if (LAY == SZ_GRAY) {
+            p1 = q[3 * (r0 - 1)];
+        } else {
+            p1 = q[r0 - 1];
+            if (LAY == SZ_S3) {
+                p2 = q[r0 - 2];
+                p3 = q[r0 - 3];
+            }
+        }
+    }
+    for (int j = 0; j < cnt; j += 8) {
+        short8 v;
+        if (LAY == SZ_GRAY) {   // 8 pixels = 24 elements, of which channel 0 is taken
+            const size_t e0 = 3 * (r0 + j);
+            const short8 a = hf_load8<VEC>(q, e0, 3 * n, (short)0), b = hf_load8<VEC>(q, e0 + 8, 3 * n, (short)0),
+                         c = hf_load8<VEC>(q, e0 + 16, 3 * n, (short)0);
+            v[0] = a[0], v[1] = a[3], v[2] = a[6], v[3] = b[1], v[4] = b[4], v[5] = b[7], v[6] = c[2], v[7] = c[5];
+        } else {
+            v = hf_load8<VEC>(q, r0 + j, n, (short)0);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const short cur = v[k], front = STRIDE == 3 ? p3 : p1;
+            const short sd = (r0 || j + k >= STRIDE) ? (short)(front - cur) : cur;
+            const short y = apply_offset ? (short)(TZ_OFFSET - sd) : sd;
+            if (j + k < cnt) f(j + k, (int)y);   // (uniform but for the last run)
+            p3 = p2;
+            p2 = p1;
+            p1 = cur;
+        }
+    }
+}
+
+// k_huffd_count over the symbols of sz_walk: hist[0] the plain histogram (the one the rank table is built from, bin = symbol +
+// TZ_HUFF_COUNT_BIAS), hist[1] and hist[2] the token histograms at match distance 1 and 3.  No payload is written.
+template <int LAY, bool VEC>
+__global__ __launch_bounds__(256) void k_size_count(const int16_t* __restrict__ q, size_t n, size_t nruns, int apply_offset,
+                                                    unsigned long long* __restrict__ hist, tz_huff_meta* __restrict__ meta) {
+    constexpr int BINS = TZ_HUFF_COUNT_BINS + HFR_NTOK;
+    __shared__ unsigned h[3 * BINS];
+    for (int k = threadIdx.x; k < 3 * BINS; k += 256) h[k] = 0;
+    __syncthreads();
+    bool bad = false;
+    for (size_t run = (size_t)blockIdx.x * 256 + threadIdx.x; run < nruns; run += (size_t)gridDim.x * 256) {
+        const size_t r0 = run * HF_R;
+        int h1 = 0, h2 = 0, h3 = 0, m1 = 0, m3 = 0;
+        sz_walk<LAY, VEC>(q, n, r0, (int)std::min((size_t)HF_R, n - r0), apply_offset, [&](int j, int s) {
+            const int b = s + TZ_HUFF_COUNT_BIAS, b1 = h1 + TZ_HUFF_COUNT_BIAS;
+            const bool ok = b >= 0 && b < TZ_HUFF_COUNT_BINS;
+            const bool match1 = j >= 1 && s == h1, match3 = j >= HFR_DIST && s == h3;
+            bad |= !ok;
+            if (match1) {
+                ++m1;
+            } else {
+                if (m1) {   // the stretch in front: its token, and its elements as plain literals
+                    atomicAdd(&h[BINS + TZ_HUFF_COUNT_BINS + (31 - __clz(m1))], 1u);
+                    if (b1 >= 0 && b1 < TZ_HUFF_COUNT_BINS) atomicAdd(&h[b1], (unsigned)m1);
+                    m1 = 0;
+                }
+                if (ok) {
+                    atomicAdd(&h[b], 1u);
+                    atomicAdd(&h[BINS + b], 1u);
+                }
+            }
+            if (match3) {
+                ++m3;
+            } else {
+                if (m3) atomicAdd(&h[2 * BINS + TZ_HUFF_COUNT_BINS + (31 - __clz(m3))], 1u);
+                m3 = 0;
+                if (ok) atomicAdd(&h[2 * BINS + b], 1u);
+            }
+            h3 = h2;
+            h2 = h1;
+            h1 = s;
+        });
+        const int b1 = h1 + TZ_HUFF_COUNT_BIAS;   // the stretches the run's end cuts
+        if (m1) {
+            atomicAdd(&h[BINS + TZ_HUFF_COUNT_BINS + (31 - __clz(m1))], 1u);
+            if (b1 >= 0 && b1 < TZ_HUFF_COUNT_BINS) atomicAdd(&h[b1], (unsigned)m1);
+        }
+        if (m3) atomicAdd(&h[2 * BINS + TZ_HUFF_COUNT_BINS + (31 - __clz(m3))], 1u);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < 3 * BINS; k += 256)
+        if (h[k]) atomicAdd(&hist[k], (unsigned long long)h[k]);
+    if (bad) atomicOr(&meta->bad, 1u);
+}
+
+// The size pass without an index: one wave per chunk, four chunks per workgroup, a lane sums the bits of its run under the
+// lengths in LDS -- len[bin] the code length of the symbol of that bin AFTER the rank remap (0: no code), then T_0..T_7 -- at
+// the match distance dist (0: every symbol a literal; 1 or 3: hfr_walk's tokens, length + raw bits).  Every chunk's sum is
+// rounded up to words and joins one 64-bit total; nothing else is written.
+template <int LAY, bool VEC>
+__global__ __launch_bounds__(256) void k_size_bits(const int16_t* __restrict__ q, size_t n, size_t nruns, size_t nchunks, int apply_offset,
+                                                   const uint8_t* __restrict__ lens, int dist, tz_size_meta* __restrict__ meta) {
+    __shared__ uint8_t len[TZ_HUFF_COUNT_BINS + HFR_NTOK];
+    for (int k = threadIdx.x; k < (TZ_HUFF_COUNT_BINS + HFR_NTOK) / 4; k += 256) ((unsigned*)len)[k] = ((const unsigned*)lens)[k];
+    __syncthreads();
+    const size_t chunk = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (chunk >= nchunks) return;
+    const int lane = threadIdx.x & 63;
+    const size_t run = chunk * HF_CR + lane, r0 = run * HF_R;
+    unsigned bits = 0;
+    bool bad = false;
+    if (run < nruns) {
+        int h1 = 0, h2 = 0, h3 = 0, m = 0;
+        const auto stretch = [&]() {
+            const int k = 31 - __clz(m);
+            const unsigned l = len[TZ_HUFF_COUNT_BINS + k];
+            bits += l + k;
+            bad |= l == 0;
+        };
+        sz_walk<LAY, VEC>(q, n, r0, (int)std::min((size_t)HF_R, n - r0), apply_offset, [&](int j, int s) {
+            const bool match = dist && j >= dist && s == (dist == 1 ? h1 : h3);
+            if (match) {
+                ++m;
+            } else {
+                if (m) stretch();
+                m = 0;
+                const unsigned b = (unsigned)(s + TZ_HUFF_COUNT_BIAS);
+                const unsigned l = b < (unsigned)TZ_HUFF_COUNT_BINS ? len[b] : 0u;
+                bits += l;
+                bad |= l == 0;
+            }
+            h3 = h2;
+            h2 = h1;
+            h1 = s;
+        });
+        if (m) stretch();   // the stretch the run's end cuts
+    }
+    unsigned tot = bits;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d, 64);
+    if (lane == 0) {
+        atomicAdd(&meta->words, (unsigned long long)((tot + 31u) >> 5));
+        atomicAdd(&meta->bits, (unsigned long long)tot);
+    }
+    if (bad) atomicOr(&meta->bad, 1u);
+}
+
+static int sz_layout(tz_ctx* ctx, tz_layout layout, const int16_t* q, int* lay) {
+    if ((uintptr_t)q & 1) return tz_fail(ctx, TZ_ERR_INVALID, "size probe: the delta stack must be 2-byte aligned");
+    if (layout.channels == 3 && layout.stride == 1) *lay = SZ_FLAT;
+    else if (layout.channels == 1 && layout.stride == 1) *lay = SZ_GRAY;
+    else if (layout.channels == 3 && layout.stride == 3) *lay = SZ_S3;
+    else return tz_fail(ctx, TZ_ERR_INVALID, "size probe: no payload layout of %d channels at stride %d", layout.channels, layout.stride);
+    return TZ_OK;
+}
+
+#define TZ_SIZE_LAUNCH(K, GRID, ...)                                                                                           \
+    do {                                                                                                                       \
+        const bool vec = !((uintptr_t)q & 15);                                                                                 \
+        const auto kern = lay == SZ_FLAT   ? (vec ? K<SZ_FLAT, true> : K<SZ_FLAT, false>)                                      \
+                          : lay == SZ_GRAY ? (vec ? K<SZ_GRAY, true> : K<SZ_GRAY, false>)                                      \
+                                           : (vec ? K<SZ_S3, true> : K<SZ_S3, false>);                                         \
+        hipLaunchKernelGGL(kern, GRID, dim3(256), 0, ctx->stream, __VA_ARGS__);                                                \
+    } while (0)
+
+// d_hist: 3 x (TZ_HUFF_COUNT_BINS + 8) counts, distance 0 | 1 | 3, of the n symbols q yields under the layout (cleared here)
+int tzk_size_count(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t n, int apply_offset, unsigned long long* d_hist,
+                   tz_huff_meta* d_meta) {
+    int lay;
+    TZ_TRY(sz_layout(ctx, layout, q, &lay));
+    const size_t nruns = (n + HF_R - 1) / HF_R;
+    TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, 3 * (TZ_HUFF_COUNT_BINS + HFR_NTOK) * sizeof(unsigned long long), ctx->stream));
+    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
+    if (n == 0) return TZ_OK;
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    const dim3 grid((unsigned)std::min((nruns + 255) / 256, (size_t)2048));
+    TZ_SIZE_LAUNCH(k_size_count, grid, q, n, nruns, apply_offset, d_hist, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// d_lens: TZ_HUFF_COUNT_BINS + 8 code lengths (by bin, then the tokens), 4-byte aligned; d_meta is cleared here
+int tzk_size_bits(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t n, int apply_offset, const uint8_t* d_lens, int dist,
+                  tz_size_meta* d_meta) {
+    int lay;
+    TZ_TRY(sz_layout(ctx, layout, q, &lay));
+    if (dist != 0 && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
+    if ((uintptr_t)d_lens & 3) return tz_fail(ctx, TZ_ERR_INVALID, "size probe: the code lengths must be 4-byte aligned");
+    const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
+    TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_size_meta), ctx->stream));
+    if (n == 0) return TZ_OK;
+    tz_prof_scope ps(ctx, TZP_HUFF);
+    const dim3 grid((unsigned)((nchunks + 3) / 4));
+    TZ_SIZE_LAUNCH(k_size_bits, grid, q, n, nruns, nchunks, apply_offset, d_lens, dist, d_meta);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+#undef TZ_SIZE_LAUNCH
+
 // ---------------------------------------------------------------------------- key-frame coder
 // Opt-in stage `--key-coder huff` (format TZK1: DESIGN.md section 9, tezip_amd/keycoder.py is the slow statement of it).
 // A key frame is turned into the residuals of one of four predictors over its own samples -- 0: none, 1: the left

@@ -411,6 +411,19 @@ int tzk_huff_enc(tz_ctx*, const int16_t* in, size_t n, const uint16_t* d_enc, in
                  const unsigned* d_chunk_off, unsigned* d_words, size_t stream_words, int dist);
 int tzk_huff_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bits, const unsigned* d_words, size_t stream_words,
                  const uint16_t* d_dec_tab4096, int A, int base, size_t n, int16_t* out, int dist);
+// The size of a candidate bound (tz_size_probe, TZ-TRATIO-1): both kernels form the payload symbols of `layout` from the
+// quantised delta stack q on the fly (n symbols: q holds n elements, 3 n under the one-channel layout; 2-byte aligned, 16 for
+// vector loads), in front of the rank remap.  tzk_size_count: tzk_huffd_count's three histograms of those symbols.
+// tzk_size_bits: the stream's size under d_lens -- TZ_HUFF_COUNT_BINS code lengths by bin (= symbol + TZ_HUFF_COUNT_BIAS; the
+// length of the symbol's rank, 0: no code), then the 8 token lengths -- at the match distance dist.
+struct tz_size_meta {            // device words k_size_bits leaves for the host
+    unsigned long long words;    // sum over the chunks of ceil(chunk bits / 32)
+    unsigned long long bits;     // sum of the chunk bits
+    unsigned bad;                // a symbol or a token without a code
+    unsigned pad;
+};
+int tzk_size_count(tz_ctx*, tz_layout, const int16_t* q, size_t n, int apply_offset, unsigned long long* d_hist3x4104, tz_huff_meta* d_meta);
+int tzk_size_bits(tz_ctx*, tz_layout, const int16_t* q, size_t n, int apply_offset, const uint8_t* d_lens, int dist, tz_size_meta* d_meta);
 // key-frame coders (TZK1, and TZK2 = TZK1 with a GRAY bit: DESIGN.md section 9).  d_frames: a stack of H x W x 3 frames of which
 // frame d_idx[k] is key frame k; d_pred[k] its pred byte: predictor id 0..3, | 4 for a GRAY frame (TZK2 alone), which has H * W
 // symbols instead of H * W * 3; d_sym: the int16 symbols 0..255, key after key; d_off[k]: where frame k's symbols start in d_sym

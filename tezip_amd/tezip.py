@@ -80,6 +80,12 @@ FLAG_TABLE = (
     # tezip_amd/target.py: one rollout, at most 9 probes; a boundary, not necessarily the largest such bound).  Also writes
     # bound_search.json (compress.run(TARGET_PSNR=...))
     (None, "--target-psnr", dict(type=float, default=None, metavar="DB", dest="target_psnr")),
+    # not in the reference: with -c and --coder huff / huffr / huffd, IN PLACE of -m and -b: the job is `-m abs -b E` with the E (a
+    # multiple of 0.5) at which the files first fit into 1/R of the frames' bytes, found by a bisection over the exact size the
+    # GPU computes for a candidate's entropy.dat without writing it (definition TZ-TRATIO-1 in tezip_amd/ratetarget.py: one
+    # rollout, at most 11 probes; a boundary, not necessarily the smallest such bound).  Also writes bound_search.json; a
+    # target that abs 255 misses ends the job with exit status 4 (compress.run(TARGET_RATIO=...))
+    (None, "--target-ratio", dict(type=float, default=None, metavar="R", dest="target_ratio")),
 )
 
 TEXT = {
@@ -246,6 +252,20 @@ def check_target_flag(arg):
     return target.check_target(db)
 
 
+def check_ratio_flag(arg):
+    """--target-ratio is valid with -c of one single-GPU job with a GPU coder, in place of -m, -b and --target-psnr, without
+    --sweep and --shuffle.  Returns None, or the message of a refusal."""
+    ratio = getattr(arg, "target_ratio", None)
+    if ratio is None:
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--target-ratio is valid with -c (--compress) only"
+    if getattr(arg, "sweep", None) is not None:
+        return "--target-ratio cannot be combined with --sweep"
+    return compress.check_ratio(ratio, "abs" if arg.mode is None else None, arg.bound, getattr(arg, "target_psnr", None),
+                                getattr(arg, "coder", "zstd"), arg.shuffle, int(os.environ.get("WORLD_SIZE", "1")) > 1)
+
+
 def check_verify_flag(arg):
     """--verify is valid with -u only; `require` needs frame_digests.json in the directory and one GPU.  Returns None, or the
     message of a refusal."""
@@ -301,6 +321,10 @@ def check_compress(arg):
 def _main(arg):
     frames, problem = check_frames_flag(arg)
     if problem:   # exit status 2, as decompress.adopt_contract's errors: nothing was written
+        print("ERROR:", problem)
+        sys.exit(2)
+    problem = check_ratio_flag(arg)
+    if problem:   # likewise (in front of the other flags' checks: a refusal of this job names the flag that defines it)
         print("ERROR:", problem)
         sys.exit(2)
     problem = check_report_flag(arg)
@@ -361,8 +385,8 @@ def _main(arg):
             return decompress.run(model, src, dst, gpu, arg.verbose, frames=frames)
         return decompress.run(model, src, dst, gpu, arg.verbose)
     print("compress mode")
-    db = getattr(arg, "target_psnr", None)
-    if db is not None:   # the job is an `abs` job whose bound is still to be found: the same checks, and `abs` is printed
+    db, ratio = getattr(arg, "target_psnr", None), getattr(arg, "target_ratio", None)
+    if db is not None or ratio is not None:   # the job is an `abs` job whose bound is still to be found: the same checks, and `abs` is printed
         problem = check_compress(argparse.Namespace(**dict(vars(arg), mode=["abs"], bound=[0.0])))
     else:
         problem = check_compress(arg)
@@ -375,6 +399,12 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if ratio is not None:   # (every other flag travels with it; the jobs without it are the calls below)
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), GRAY=bool(getattr(arg, "gray", False)),
+                            SDELTA=getattr(arg, "sdelta", None) or "flat", SSIM=bool(getattr(arg, "ssim", False)), TARGET_RATIO=ratio)
     if db is not None:   # (every other flag travels with it; the jobs without it are the calls below)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
