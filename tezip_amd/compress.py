@@ -471,17 +471,23 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
     return kf.result(), esize
 
 
-def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
+def _accept_job(src, model_shape, warm_up, shuffle, out_dir, levels=1):
     """The checks of a compression job, in this order, each refusal with its message and exit(): the frame size against
-    the model's, the number of frames, --shuffle's multiple of 8.  The accepted job then writes filename.txt into
-    out_dir (None: not this process): compress.py:133-136 writes it after the images are loaded, and a rejected job
-    must not leave a partial directory behind.  Returns the padded frame size."""
+    the model's and against its number of levels, the number of frames, --shuffle's multiple of 8.  The accepted job then
+    makes out_dir (None: not this process) and writes filename.txt into it: compress.py:133-136 writes it after the images
+    are loaded, and a rejected job leaves no directory behind.  Returns the padded frame size."""
     nt, H, W = src.nt, src.H, src.W
     hp, wp = padding_shape(H, W)
     if model_shape is not None and (model_shape[0] != hp or model_shape[1] != wp):
         print("ERROR:Image size is out of scope for this model.")
         print("Compatible sizes for this model are height", model_shape[0] - 7, "to", model_shape[0], "and width",
               model_shape[1] - 7, "to", model_shape[1])
+        exit()
+    # every level halves the frame: a model of more than four levels needs more than the padding to 8 gives
+    # (tz_model_prepare refuses such a size; said here in the reference's words, before anything is written)
+    if hp % (1 << (levels - 1)) or wp % (1 << (levels - 1)):
+        print("ERROR:Image size is out of scope for this model.")
+        print("A model of %d levels needs a padded size that divides by %d: %dx%d does not" % (levels, 1 << (levels - 1), hp, wp))
         exit()
     if nt < warm_up + 2:
         print("ERROR: need at least warm_up+2 images (%d given, warm_up %d)." % (nt, warm_up))
@@ -490,6 +496,8 @@ def _accept_job(src, model_shape, warm_up, shuffle, out_dir):
         print("ERROR: --shuffle needs nt*H*W*3 to be a multiple of 8 (%d x %d x %d x 3 is not)." % (nt, H, W))
         exit()
     if out_dir is not None:
+        if not os.path.exists(out_dir):
+            os.mkdir(out_dir)
         with open(os.path.join(out_dir, 'filename.txt'), 'w', encoding='UTF-8') as f:
             f.write(f"{int(src.is_rgb)}\n")
             for file_name in src.files:
@@ -598,8 +606,6 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             sys.exit(2)
         return _run_sharded(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE,
                             VERBOSE, ENTROPY_RUN, device, SHUFFLE, CODER)
-    if not os.path.exists(OUTPUT_DIR):
-        os.mkdir(OUTPUT_DIR)
     stages = _Stages()
     src = FrameSource(DATA_DIR)
     nt, H, W = src.nt, src.H, src.W
@@ -611,7 +617,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
         stages.mark("first window decoded")
         cfg, wts, model_shape = open_model(WEIGHTS_DIR)
         stages.mark("model directory read")
-        hp, wp = _accept_job(src, model_shape, PREPROCESS, SHUFFLE, OUTPUT_DIR)
+        hp, wp = _accept_job(src, model_shape, PREPROCESS, SHUFFLE, OUTPUT_DIR, cfg.nb_layers)
         nwin = 1 if WINDOW_SIZE is None else max(1, (nt - PREPROCESS + WINDOW_SIZE - 1) // WINDOW_SIZE)
         ctx = make_context(cfg, wts, hp, wp, min(nwin, 64), device)
         stages.mark("context + model prepare")
@@ -756,12 +762,10 @@ def _run_sharded(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THR
         sys.exit(2)
     job = tzdist.active()
     rank0 = job[0] == 0
-    if rank0 and not os.path.exists(OUTPUT_DIR):
-        os.mkdir(OUTPUT_DIR)
     src = FrameSource(DATA_DIR)          # lists, probes the first image (mode, size): same messages as load_images
     nt, H, W = src.nt, src.H, src.W
     cfg, wts, model_shape = open_model(WEIGHTS_DIR)
-    hp, wp = _accept_job(src, model_shape, PREPROCESS, SHUFFLE, OUTPUT_DIR if rank0 else None)
+    hp, wp = _accept_job(src, model_shape, PREPROCESS, SHUFFLE, OUTPUT_DIR if rank0 else None, cfg.nb_layers)
     if WINDOW_SIZE is None:
         if rank0:
             print("NOTE: DWP (-t) finds its windows sequentially and does not shard: running on rank 0 only.")
