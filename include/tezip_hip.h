@@ -419,6 +419,18 @@ int tz_ssim_frames(tz_ctx* ctx, const uint8_t* a, const uint8_t* b, int nframes,
 int tz_encode_ssim(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
                    int shuffled, tz_frame_ssim* out);
 
+/* ---- alignment of device buffers --------------------------------------------------------------
+ * Every buffer argument below may be a host or a device pointer.  A host array is copied through the context's pool and may
+ * lie anywhere.  A DEVICE buffer is handed to the kernels as it is and need only be aligned to its element type (1, 2 or 4
+ * bytes: uint8_t, int16_t, float): each kernel picks its vector form from the addresses it is given and gives the same bits
+ * in its element-wise form (DESIGN.md section 0 lists every wide access and the term that guards it).  The exceptions are
+ * the entry points whose kernels have no element-wise form and which therefore REFUSE a device buffer, input or output,
+ * that is off a 16-byte boundary: tz_spatial_delta (and tz_spatial_delta_stride with stride 1: "spatial_delta buffers must
+ * be 16-byte aligned"), tz_remap and tz_unmap ("remap buffers must be 16-byte aligned"), tz_byte_shuffle and
+ * tz_byte_unshuffle ("byte-shuffle buffers must be 16-byte aligned"); and tz_encode for a device `payload`, which the last
+ * of these stages writes (its message).  Each refuses with TZ_ERR_INVALID and that message before any launch that writes
+ * the buffer: nothing of it is written. */
+
 /* ---- operator seams, usable stand-alone (each mirrors one reference helper) -----------------
  * tz_delta_encode: compress.py:292-314.  pred: nframes padded f32 frames; orig: nframes
  * unpadded u8 frames; zero_mask[nframes] (host): 1 => that frame's delta is forced to 0. */

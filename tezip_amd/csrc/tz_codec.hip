@@ -22,7 +22,8 @@ typedef short short8 __attribute__((ext_vector_type(8)));
 
 // ------------------------------------------------------------------------------- delta
 // compress.py:292-314: d = (int)(pred_f32 * 255.0f) - orig ; frames flagged in zero_mask -> 0.
-// Fast path: frame needs no padding (H==Hp, W==Wp): pred, orig and out share one flat index.
+// Fast path: frame needs no padding (H==Hp, W==Wp): pred, orig and out share one flat index.  16-byte loads of pred, 8-byte
+// loads of orig, 16-byte stores: tzk_delta takes it only for buffers on those boundaries.
 __global__ __launch_bounds__(256) void k_delta_flat(const float4* __restrict__ pred, const uint2* __restrict__ orig,
                                                     const uint8_t* __restrict__ zero_mask, size_t n8,
                                                     unsigned frame_elems8, short8* __restrict__ out) {
@@ -67,7 +68,8 @@ int tzk_delta(tz_ctx* ctx, const float* pred, const uint8_t* orig, const uint8_t
     size_t n = (size_t)nframes * H * W * 3;
     if (n == 0) return TZ_OK;
     tz_prof_scope ps(ctx, TZP_DELTA);
-    if (H == Hp && W == Wp && ((size_t)H * W * 3) % 8 == 0) {
+    const bool aligned = ((((uintptr_t)pred | (uintptr_t)out) & 15) | ((uintptr_t)orig & 7)) == 0;
+    if (H == Hp && W == Wp && ((size_t)H * W * 3) % 8 == 0 && aligned) {
         size_t n8 = n / 8;
         hipLaunchKernelGGL(k_delta_flat, dim3(grid_for(n8, 256)), dim3(256), 0, ctx->stream, (const float4*)pred,
                            (const uint2*)orig, d_zero_mask, n8, (unsigned)((size_t)H * W * 3 / 8), (short8*)out);
@@ -226,6 +228,27 @@ __device__ __forceinline__ int q_delta(const QSrc& s, const uint8_t* __restrict_
     return (int)s.diff[e];
 }
 
+// the 12 bytes at stack offset `off` (4 pixels x 3 channels), packed 4 per word.  Aligned dword loads -- three where the
+// address is a multiple of 4, else four and a funnel shift -- wherever those dwords lie inside the stack [x, x + total); the
+// groups at the stack's two ends that they would leave take byte loads (volatile: twelve plain ones the compiler folds into ONE
+// 12-byte load at a byte address).  Nothing outside the stack is read, and what is wider than a byte lies on a dword boundary.
+__device__ __forceinline__ void ss_row12(const uint8_t* __restrict__ x, size_t off, size_t total, unsigned w[3]) {
+    const uintptr_t addr = (uintptr_t)x + off, m = addr & 3, p0 = addr - m;
+    if (p0 >= (uintptr_t)x && p0 + (m ? 16 : 12) <= (uintptr_t)x + total) {
+        const unsigned* p = (const unsigned*)(x + off - m);   // (= p0, as a pointer into x: a global load)
+        const unsigned d0 = p[0], d1 = p[1], d2 = p[2], d3 = m ? p[3] : 0u;
+        const unsigned sh = 8u * (unsigned)m;
+        w[0] = (unsigned)((((unsigned long long)d1 << 32) | d0) >> sh);
+        w[1] = (unsigned)((((unsigned long long)d2 << 32) | d1) >> sh);
+        w[2] = (unsigned)((((unsigned long long)d3 << 32) | d2) >> sh);
+    } else {
+        const volatile uint8_t* b = x + off;
+        w[0] = w[1] = w[2] = 0;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) w[j >> 2] |= (unsigned)b[j] << (8 * (j & 3));
+    }
+}
+
 // min/max of the original slab per (frame, channel): 12 bytes (4 interleaved RGB pixels) per
 // lane and iteration, QBB blocks per frame combined with integer atomics (mm[f][c] = {min, max}).
 static constexpr int QBB = 16;
@@ -235,17 +258,11 @@ __global__ __launch_bounds__(256) void k_q_minmax(const uint8_t* __restrict__ or
     if (skip[f]) return;
     const uint8_t* o = orig + (size_t)f * HW * 3;
     int mn[3] = {255, 255, 255}, mx[3] = {0, 0, 0};
-    const int ngroups = HW / 4;  // 4 pixels = 12 bytes = 3 aligned dwords (frame base is 4-byte aligned when HW*3 % 4 == 0)
-    const bool aligned = (((size_t)f * HW * 3) & 3) == 0 && (((uintptr_t)orig) & 3) == 0;
+    const int ngroups = HW / 4;  // 4 pixels = 12 bytes: 3 aligned dwords where the frame starts on a 4-byte boundary, else 4 and a shift
+    const size_t total = (size_t)gridDim.y * HW * 3;
     for (int g = blockIdx.x * 256 + threadIdx.x; g < ngroups; g += QBB * 256) {
         unsigned w[3];
-        if (aligned) {
-            const unsigned* p = (const unsigned*)(o + (size_t)g * 12);
-            w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
-        } else {
-            const uint8_t* p = o + (size_t)g * 12;
-            for (int k = 0; k < 3; ++k) w[k] = p[4 * k] | (p[4 * k + 1] << 8) | (p[4 * k + 2] << 16) | ((unsigned)p[4 * k + 3] << 24);
-        }
+        ss_row12(orig, (size_t)f * HW * 3 + (size_t)g * 12, total, w);
 #pragma unroll
         for (int b = 0; b < 12; ++b) {
             int v = (w[b >> 2] >> (8 * (b & 3))) & 0xff, c = b % 3;
@@ -1528,6 +1545,7 @@ int tzk_quant_sd_fused(tz_ctx* ctx, const float* pred, const uint8_t* orig, cons
     if (std::isnan(b0) || (mode == TZ_MODE_ABSREL && std::isnan(b1)))
         return tz_fail(ctx, TZ_ERR_INVALID, "error bound is NaN (the reference raises on a NaN tolerance)");
     if (H != Hp || W != Wp || ((size_t)H * W) % 8 || nframes <= 0 || (((uintptr_t)sym) & 15)) return TZ_OK;
+    if ((((uintptr_t)pred & 15) | ((uintptr_t)orig & 3)) != 0) return TZ_OK;   // k_q_fill_sym: 16-byte pred, 4-byte orig loads
     QFused fu{pred, d_zero_mask, apply_offset, sym, d_hist, d_edge};
     TZ_TRY(quant_run(ctx, orig, nullptr, &fu, h_skip, nframes, H, W, mode, b0, b1));
     *done = true;
@@ -1639,6 +1657,7 @@ int tzk_delta_sd_fused(tz_ctx* ctx, const float* pred, const uint8_t* orig, cons
     *done = false;
     size_t fe = (size_t)H * W * 3;
     if (H != Hp || W != Wp || fe % 8 || nframes <= 0) return TZ_OK;
+    if (((((uintptr_t)pred | (uintptr_t)out) & 15) | ((uintptr_t)orig & 7)) != 0) return TZ_OK;   // 16-byte pred / out, 8-byte orig accesses
     size_t n8 = fe * nframes / 8;
     tz_prof_scope ps(ctx, TZP_DELTA);
     if (d_hist)
@@ -1917,9 +1936,17 @@ __global__ __launch_bounds__(256) void k_unshuffle(const uint8_t* __restrict__ i
     const size_t n8 = n / 8, stride = (size_t)gridDim.x * blockDim.x;
     short8* out8 = (short8*)out;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
-        unsigned long long lo, hi;
-        memcpy(&lo, in + 8 * i, 8);       // the high plane starts at n, which need not be 8-aligned
-        memcpy(&hi, in + n + 8 * i, 8);
+        // `in` is 16-byte aligned (tzk_shuffle); the high plane starts at n, which need not be a multiple of 8: then its bytes
+        // come one by one (volatile: eight plain byte loads, or a memcpy, the compiler folds into ONE 8-byte load at a byte address)
+        const unsigned long long lo = *(const unsigned long long*)(in + 8 * i);
+        unsigned long long hi = 0;
+        if ((n & 7) == 0) {
+            hi = *(const unsigned long long*)(in + n + 8 * i);
+        } else {
+            const volatile uint8_t* b = (const volatile uint8_t*)(in + n + 8 * i);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) hi |= (unsigned long long)b[k] << (8 * k);
+        }
         short8 r;
 #pragma unroll
         for (int k = 0; k < 8; ++k) r[k] = (short)(((lo >> (8 * k)) & 0xFF) | (((hi >> (8 * k)) & 0xFF) << 8));
@@ -2610,7 +2637,7 @@ int tzk_undelta_carry(tz_ctx* ctx, int stride, const int16_t* in, size_t n0, con
 // (DESIGN.md §"Why reconstruct is integer"); key slots use the key byte as base.
 __global__ __launch_bounds__(256) void k_recon(const float* __restrict__ pred, const uint8_t* __restrict__ key,
                                                const uint8_t* __restrict__ key_mask, const int16_t* __restrict__ diff,
-                                               size_t n, int H, int W, int Hp, int Wp, uint8_t* __restrict__ out) {
+                                               size_t n, int H, int W, int Hp, int Wp, int out_dwords, uint8_t* __restrict__ out) {
     size_t stride = (size_t)gridDim.x * blockDim.x;
     size_t row = (size_t)W * 3, fe = (size_t)H * row, fp = (size_t)Hp * Wp * 3;
     size_t n4 = n / 4;
@@ -2631,7 +2658,7 @@ __global__ __launch_bounds__(256) void k_recon(const float* __restrict__ pred, c
             v = v < 0 ? 0 : (v > 255 ? 255 : v);
             packed |= (unsigned)v << (8 * k);
         }
-        if (cnt == 4) ((unsigned*)out)[q] = packed;
+        if (cnt == 4 && out_dwords) ((unsigned*)out)[q] = packed;   // (out_dwords: `out` is on a 4-byte boundary)
         else
             for (int k = 0; k < cnt; ++k) out[q * 4 + k] = (uint8_t)(packed >> (8 * k));
     }
@@ -2767,7 +2794,7 @@ int tzk_reconstruct(tz_ctx* ctx, int channels, const float* pred, const uint8_t*
                            Hp, Wp, (int)(((uintptr_t)out & 3) == 0), out);
     } else {
         hipLaunchKernelGGL(k_recon, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, ctx->stream, pred, key, d_key_mask, diff, n, H, W, Hp,
-                           Wp, out);
+                           Wp, (int)(((uintptr_t)out & 3) == 0), out);
     }
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
@@ -3248,25 +3275,6 @@ struct SsPart {
 };
 
 __device__ __forceinline__ long long ss_min(long long x, long long y) { return y < x ? y : x; }
-
-// the 12 bytes at stack offset `off` (one cell row: 4 pixels x 3 channels), packed 4 per word.  Aligned dword loads -- three
-// where the address is a multiple of 4, else four and a funnel shift -- wherever those dwords lie inside the stack
-// [x, x + total); the rows at the stack's two ends that they would leave take byte loads.  Nothing outside the stack is read.
-__device__ __forceinline__ void ss_row12(const uint8_t* __restrict__ x, size_t off, size_t total, unsigned w[3]) {
-    const uintptr_t addr = (uintptr_t)x + off, m = addr & 3, p0 = addr - m;
-    if (p0 >= (uintptr_t)x && p0 + (m ? 16 : 12) <= (uintptr_t)x + total) {
-        const unsigned* p = (const unsigned*)p0;
-        const unsigned d0 = p[0], d1 = p[1], d2 = p[2], d3 = m ? p[3] : 0u;
-        const unsigned sh = 8u * (unsigned)m;
-        w[0] = (unsigned)((((unsigned long long)d1 << 32) | d0) >> sh);
-        w[1] = (unsigned)((((unsigned long long)d2 << 32) | d1) >> sh);
-        w[2] = (unsigned)((((unsigned long long)d3 << 32) | d2) >> sh);
-    } else {
-        w[0] = w[1] = w[2] = 0;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) w[j >> 2] |= (unsigned)x[off + j] << (8 * (j & 3));
-    }
-}
 
 // Q of one window from its five moments (exact integers; every factor below 2^53 in magnitude, d1, d2 > 0)
 __device__ __forceinline__ long long ss_q(long long s1, long long s2, long long sa, long long sb, long long s12) {
