@@ -227,6 +227,26 @@ int tz_get_payload_channels(tz_ctx* ctx);
  *    mode 1 (whatever the channel count): one carry element is not the carry of a strided scan, sharded jobs are out of scope. */
 int tz_set_delta_stride(tz_ctx* ctx, int mode);
 int tz_get_delta_stride(tz_ctx* ctx);
+/* Opt-in: one abs tolerance per frame (no reference counterpart: compress.py takes one bound per job, but its error_bound runs
+ * per frame and channel, compress.py:316-319, so a frame's quantised delta depends on that frame's tolerance alone;
+ * `tezip.py -c --target-psnr DB --per-frame`, `-c -m abs --frame-bounds FILE`).
+ * bounds: n host doubles, bounds[f] = the abs tolerance of frame f.  NULL or n == 0 clears the setting.  A NaN, infinite or
+ * negative entry, or n < 0, is TZ_ERR_INVALID and leaves the setting as it was.  tz_get_frame_bounds returns n, 0 when none
+ * is set.  With nothing set every entry point launches exactly what it launches without these calls.  While bounds are set:
+ *  - tz_encode, tz_encode_delta, tz_bound_probe and tz_size_probe quantise frame f of the context's encoder rollout as
+ *    `abs bounds[f]` does: the quantised delta of frame f is bit for bit the one tz_encode_delta(ctx, TZ_MODE_ABS, bounds[f],
+ *    0, ...) leaves for frame f, and a bound of 0 leaves the frame's deltas untouched, as `abs 0` does.  Frames the encoder
+ *    never quantises (frame 0, warm-up and key frames) stay as they are whatever their entry says.
+ *  - mode must be TZ_MODE_ABS (b0 and b1 are not read) and n must equal the rollout's nt: else TZ_ERR_INVALID, with a
+ *    message that names the rule.
+ *  - tz_encode_begin and tz_encode_finish return TZ_ERR_UNSUPPORTED (sharded jobs take one bound).
+ *  - the stand-alone tz_error_bound is not affected; the decoder never sees a bound, so tz_decode, tz_encode_quality,
+ *    tz_encode_ssim and tz_encode_digests take the payload as any other.
+ * The payload is the one the unfused chain gives (tz_encode_delta, then the layout's spatial delta), whichever fused pass
+ * serves: the lossless one when every bound is 0 or an identity (E <= 0.499), else the fused lossy front with the per-frame
+ * tolerances (one small launch, k_q_frame_bound, fills the per-chain array that rel / absrel jobs fill from the data). */
+int tz_set_frame_bounds(tz_ctx* ctx, const double* bounds, int n);
+int tz_get_frame_bounds(tz_ctx* ctx);
 /* Streaming delivery: tz_encode with payload == NULL keeps the payload in the context; it is then
  * fetched in pieces of `count` int16 elements starting at `offset` (compress.py:375-400 appends and
  * compresses one monolithic array). */
@@ -446,6 +466,12 @@ int tz_delta_encode(tz_ctx* ctx, const float* pred, const uint8_t* orig, const u
  * such call with TZ_ERR_INVALID -- a deliberate superset of the reference's failure, both oracles do the same. */
 int tz_error_bound(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask,
                    int nframes, int H, int W, int mode, double b0, double b1);
+/* tz_error_bound_frames: the seam of tz_set_frame_bounds -- tz_error_bound in abs mode with one tolerance per frame.  orig and
+ * diff are host or device stacks as tz_error_bound's; bounds: nframes host doubles, finite and >= 0 (else TZ_ERR_INVALID and
+ * diff is untouched).  Frame f of diff ends as tz_error_bound(.., TZ_MODE_ABS, bounds[f], 0) leaves it, bit for bit; a bound
+ * of 0 and a skipped frame leave it untouched.  Independent of the context's own frame bounds. */
+int tz_error_bound_frames(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask,
+                          int nframes, int H, int W, const double* bounds);
 /* tz_spatial_delta: compress.py:73-77 (+ the 1600 offset of :348 when apply_offset).
  * has_carry: treat `carry` as the element preceding in[0] (shard boundary). hist (may be
  * NULL): TZ_NBINS uint64 counts of the output symbols are ADDED (compress.py:354). */

@@ -78,6 +78,9 @@ _SIGS = {
     "tz_get_payload_channels": (C.c_int, [C.c_void_p]),
     "tz_set_delta_stride": (C.c_int, [C.c_void_p, C.c_int]),
     "tz_get_delta_stride": (C.c_int, [C.c_void_p]),
+    "tz_set_frame_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "tz_get_frame_bounds": (C.c_int, [C.c_void_p]),
+    "tz_error_bound_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tz_spatial_delta_stride": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "tz_spatial_undelta_stride": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "tz_undelta_carry_stride": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -628,6 +631,19 @@ class Context:
     def get_delta_stride(self):
         return int(self.lib.tz_get_delta_stride(self.h))
 
+    def set_frame_bounds(self, bounds):
+        """tz_set_frame_bounds: one abs tolerance per frame of the encoder rollout (None or empty: clear).  While set, encode /
+        encode_delta / bound_probe / size_probe take mode "abs", ignore its bound and quantise frame f as abs bounds[f] does;
+        the sharded entry points refuse.  A NaN, infinite or negative entry raises and the setting stays as it was."""
+        if bounds is None or len(bounds) == 0:
+            self._ck(self.lib.tz_set_frame_bounds(self.h, None, 0))
+            return
+        b = np.ascontiguousarray(bounds, np.float64)
+        self._ck(self.lib.tz_set_frame_bounds(self.h, b.ctypes.data, int(b.size)))
+
+    def get_frame_bounds(self):
+        return int(self.lib.tz_get_frame_bounds(self.h))
+
     def set_payload_deferred(self, on=True):
         """tz_set_payload_deferred: encode(payload=<pinned host buffer>) returns with the device -> host transfer of
         the payload still running; payload_wait() completes it (it overlaps the next sequence's rollout)."""
@@ -1120,6 +1136,16 @@ class Context:
         b0, b1 = _bounds(bound)
         sk = None if skip_mask is None else np.ascontiguousarray(skip_mask, np.uint8)
         self._ck(self.lib.tz_error_bound(self.h, _ptr(orig), _ptr(diff), _ptr(sk), n, h, w, MODES[mode], b0, b1))
+        return diff
+
+    def error_bound_frames(self, orig, diff, bounds, skip_mask=None):
+        """tz_error_bound_frames: error_bound in abs mode with bounds[f] for frame f (the seam of set_frame_bounds)."""
+        n, h, w = orig.shape[:3]
+        b = np.ascontiguousarray(bounds, np.float64)
+        if b.size != n:
+            raise ValueError("%d bounds for %d frames" % (b.size, n))
+        sk = None if skip_mask is None else np.ascontiguousarray(skip_mask, np.uint8)
+        self._ck(self.lib.tz_error_bound_frames(self.h, _ptr(orig), _ptr(diff), _ptr(sk), n, h, w, b.ctypes.data))
         return diff
 
     def spatial_delta(self, x, offset, carry=None, hist=None, out=None):

@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, quality, ratetarget, sdelta, sidecar, target, weights, zstd
+from . import _lib, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, quality, ratetarget, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -524,7 +524,7 @@ def check_ratio(ratio, mode, bound, target_psnr, coder, shuffle, sharded):
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
-        SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None):
+        SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -570,6 +570,15 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     budget, the probes, the result) is written besides.  A target that abs 255 misses: the message, bound_search.json with a
     null result, no entropy.dat, exit status 4.  Works with every KEY_CODER, GRAY, SDELTA, REPORT, SSIM and DIGESTS.
     Single-GPU jobs only.
+    PER_FRAME (--per-frame; NOT in the reference; with TARGET_PSNR only): the target holds in EVERY frame that is not stored
+    exactly (definition TZ-TPSNR-F1: tezip_amd/frametarget.py): every such frame gets an abs bound of its own from a
+    bisection of its own, all of them driven by the same at most 9 tz_bound_probe calls, and the job runs under
+    tz_set_frame_bounds.  The files are those of the reference's format (the decoder never sees a bound); bound_search.json
+    lists the bounds.  Works with every flag TARGET_PSNR works with.  Single-GPU jobs only.
+    FRAME_BOUNDS (--frame-bounds; NOT in the reference; MODE "abs", an empty BOUND_VALUE, no target): the path of a JSON file (a
+    list of numbers or an object with a "frame_bounds" list, so that a per-frame search's bound_search.json replays) or a
+    sequence: one abs bound per image, finite and >= 0; entries at frame 0, warm-up and key frames are taken as 0.  The
+    job runs under tz_set_frame_bounds.  Single-GPU jobs only.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -597,6 +606,17 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
         if problem:
             print("ERROR:", problem)
             sys.exit(2)
+    frame_bounds = None
+    if PER_FRAME or FRAME_BOUNDS is not None:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
+        problem = frametarget.check(PER_FRAME, FRAME_BOUNDS, MODE, BOUND_VALUE, TARGET_PSNR, TARGET_RATIO, tzdist.active() is not None)
+        if not problem and FRAME_BOUNDS is not None:
+            try:
+                frame_bounds = frametarget.load(FRAME_BOUNDS)
+            except ValueError as e:
+                problem = str(e)
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     if tzdist.active() is not None:
         if REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
             print("ERROR: --report is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU")
@@ -609,6 +629,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     stages = _Stages()
     src = FrameSource(DATA_DIR)
     nt, H, W = src.nt, src.H, src.W
+    if frame_bounds is not None:   # known once the directory is listed: before the model, the context and the rollout
+        problem = frametarget.check_length(frame_bounds, nt, FRAME_BOUNDS)
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     per_chunk = max(1, min(WINDOW_SIZE or 16, 64))
     with ThreadPoolExecutor(max_workers=io_threads() + 1) as pool:
         chunks = src.chunks(per_chunk, pool)   # decoding starts with the first next(); model + HIP start-up overlap it
@@ -643,7 +668,25 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                         print("move key point")
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
             stages.mark("rollout", ctx)
-            if TARGET_PSNR is not None:   # one rollout serves every candidate: the predictions do not depend on the bound
+            if PER_FRAME:   # one rollout and one probe serve every frame's candidate: a frame's quantiser sees its own bound alone
+                fixed = frametarget.fixed_frames(key, PREPROCESS)
+                limit = target.sse_limit(TARGET_PSNR, H * W * 3)
+
+                def probe(cand):
+                    ctx.set_frame_bounds([target.bound_of(c) for c in cand])
+                    return ctx.bound_probe("abs", [0.0])["sse"]
+
+                ks, sse, trace = frametarget.search(probe, limit, fixed)
+                search_doc = frametarget.make(TARGET_PSNR, H * W * 3, limit, fixed, src.files, ks, sse, trace)
+                frame_bounds = search_doc["frame_bounds"]
+                print(frametarget.stdout_line(search_doc))
+                stages.mark("per-frame bound search (device)")
+            elif frame_bounds is not None:
+                frame_bounds = [0.0 if fx else b for fx, b in zip(frametarget.fixed_frames(key, PREPROCESS), frame_bounds)]
+                print(frametarget.explicit_line(frame_bounds))
+            if frame_bounds is not None:   # the job: abs, frame f under frame_bounds[f]
+                ctx.set_frame_bounds(frame_bounds)
+            elif TARGET_PSNR is not None:   # one rollout serves every candidate: the predictions do not depend on the bound
                 # (a probe describes the job in the payload layout decide_gray left in force: the one-channel job's own SSE)
                 limit = target.sse_limit(TARGET_PSNR, nt * H * W * 3)
                 k, trace = target.search(lambda c: int(ctx.bound_probe("abs", [target.bound_of(c)])["sse"].sum()), limit)
@@ -666,7 +709,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     sys.exit(ratetarget.EXIT_UNREACHABLE)
                 BOUND_VALUE = [ratetarget.bound_of(k)]
                 print(ratetarget.stdout_line(search_doc))
-            _, table, _ = ctx.encode(MODE, BOUND_VALUE, ENTROPY_RUN, payload="resident", shuffle=SHUFFLE)
+            # (under frame bounds the bound of encode() is not read)
+            _, table, _ = ctx.encode(MODE, BOUND_VALUE if frame_bounds is None else [0.0], ENTROPY_RUN, payload="resident", shuffle=SHUFFLE)
             stages.mark("encode (payload resident)", ctx)
             if REPORT:   # stream-ordered before _stream_outputs fetches the payload; changes nothing it reads
                 t0 = time.time()
@@ -710,10 +754,14 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 report = quality.summarize(stats, src.files, H, W, MODE, BOUND_VALUE, quality.file_sizes(OUTPUT_DIR),
                                            window=WINDOW_SIZE, threshold=THRESHOLD, warm_up=PREPROCESS,
                                            **({"ssim": ssim_rec} if SSIM else {}))
+                if frame_bounds is not None:
+                    report["frame_bounds"] = [float(b) for b in frame_bounds]
                 quality.write(OUTPUT_DIR, report)
                 for line in quality.stdout_lines(report):
                     print(line)
-            if TARGET_PSNR is not None:
+            if PER_FRAME:
+                frametarget.write(OUTPUT_DIR, search_doc)
+            elif TARGET_PSNR is not None:
                 target.write(OUTPUT_DIR, search_doc)
             if TARGET_RATIO is not None:
                 ratetarget.write(OUTPUT_DIR, search_doc)

@@ -1519,7 +1519,53 @@ static int encode_check(tz_ctx* ctx, const char* who, int mode) {
     if (!whole_stack(ctx, tz_ctx::ROLLOUT_ENCODE)) return tz_fail(ctx, TZ_ERR_STATE, "%s needs a tz_rollout first", who);
     TZ_TRY(tz_check_pred_contract(ctx, who));
     if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
+    if (!ctx->frame_bounds.empty()) {   // tz_set_frame_bounds: b0 and b1 are not read
+        if (mode != TZ_MODE_ABS)
+            return tz_fail(ctx, TZ_ERR_INVALID, "%s: frame bounds are set (tz_set_frame_bounds), the mode must be abs, not %d", who, mode);
+        if ((int)ctx->frame_bounds.size() != ctx->nt)
+            return tz_fail(ctx, TZ_ERR_INVALID, "%s: frame bounds are set for %d frames (tz_set_frame_bounds), the rollout has %d", who,
+                           (int)ctx->frame_bounds.size(), ctx->nt);
+    }
     return TZ_OK;
+}
+
+// ---- one abs bound per frame (include/tezip_hip.h: tz_set_frame_bounds)
+extern "C" int tz_set_frame_bounds(tz_ctx* ctx, const double* bounds, int n) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (n < 0) return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_frame_bounds: %d bounds", n);
+    if (!bounds || n == 0) {
+        ctx->frame_bounds.clear();
+        return TZ_OK;
+    }
+    for (int f = 0; f < n; ++f)
+        if (!std::isfinite(bounds[f]) || bounds[f] < 0.0)
+            return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_frame_bounds: bound %g of frame %d is not a finite number >= 0", bounds[f], f);
+    ctx->frame_bounds.assign(bounds, bounds + n);
+    return TZ_OK;
+}
+
+extern "C" int tz_get_frame_bounds(tz_ctx* ctx) { return ctx ? (int)ctx->frame_bounds.size() : TZ_ERR_INVALID; }
+
+// The sharded entry points quantise one shard's frames under one bound.
+static int no_frame_bounds(tz_ctx* ctx, const char* who) {
+    if (!ctx->frame_bounds.empty())
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve per-frame bounds (tz_set_frame_bounds): sharded jobs take one bound", who);
+    return TZ_OK;
+}
+
+// every frame's bound leaves its deltas as they are (0, or an identity by tz_quant_is_identity): the lossless job
+static bool frame_bounds_identity(const tz_ctx* ctx) {
+    for (double b : ctx->frame_bounds)
+        if (b != 0.0 && !tz_quant_is_identity(TZ_MODE_ABS, b, 0.0)) return false;
+    return true;
+}
+
+// compress.py:315-319 on the delta stack of the context's rollout, under the frame bounds when some are set (encode_check has
+// passed)
+static int quantise_rollout(tz_ctx* ctx, int16_t* d_q, int mode, double b0, double b1) {
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
+    if (ctx->frame_bounds.empty()) return tzk_error_bound(ctx, ctx->d_frames, d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1);
+    return tzk_quant_frames(ctx, ctx->d_frames, d_q, nullptr, ctx->quant_skip.data(), nt, H, W, ctx->frame_bounds.data(), nullptr);
 }
 
 // compress.py:292-355 on the context-resident rollout: delta, quantiser, spatial delta over the whole flattened stack
@@ -1542,12 +1588,19 @@ static int encode_front(tz_ctx* ctx, tz_layout layout, int mode, double b0, doub
         // the worst-case tolerance of the job cannot merge two different deltas (E <= 0.499: tz_quant_is_identity, with the
         // proof).  A caller that taps the delta stack still gets it through the general quantiser (the parity tests compare
         // the two).  The gray layout and the channel stride have no fused pass.
-        const bool lossless = b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0) || tz_quant_is_identity(mode, b0, b1);
+        // Frame bounds (tz_set_frame_bounds): the lossless job when every frame's bound is such a one, else the same lossy
+        // front with the per-frame tolerances.
+        const bool per_frame = !ctx->frame_bounds.empty();
+        const bool lossless = per_frame ? frame_bounds_identity(ctx)
+                                        : b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0) || tz_quant_is_identity(mode, b0, b1);
         bool fused = false;
         if (lossless)   // delta and spatial delta in one pass (compress.py:292-355)
             TZ_TRY(tzk_delta_sd_fused(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp,
                                       entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge, &fused));
-        else            // quantiser on pred / orig, fill fused with the spatial delta
+        else if (per_frame) {
+            const tz_quant_fused fu{ctx->d_pred, (const uint8_t*)d_mask, ctx->Hp, ctx->Wp, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge};
+            TZ_TRY(tzk_quant_frames(ctx, ctx->d_frames, nullptr, &fu, ctx->quant_skip.data(), nt, H, W, ctx->frame_bounds.data(), &fused));
+        } else          // quantiser on pred / orig, fill fused with the spatial delta
             TZ_TRY(tzk_quant_sd_fused(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, ctx->quant_skip.data(), nt, H, W,
                                       ctx->Hp, ctx->Wp, mode, b0, b1, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge,
                                       &fused));
@@ -1557,7 +1610,7 @@ static int encode_front(tz_ctx* ctx, tz_layout layout, int mode, double b0, doub
     // compress.py:292-314
     TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp, (int16_t*)d_delta));
     // compress.py:315-319 (under the gray layout the quantiser also walks channels 1 and 2, whose output is dropped)
-    TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, (int16_t*)d_delta, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
+    TZ_TRY(quantise_rollout(ctx, (int16_t*)d_delta, mode, b0, b1));
     if (!d_sym) return TZ_OK;
     // compress.py:339-355
     TZ_TRY(tzk_spatial_delta(ctx, layout, (const int16_t*)d_delta, (size_t)nt * tz_frame_elems(layout, H, W), nullptr, entropy ? 1 : 0,
@@ -1731,6 +1784,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
     tz_roctx_range roctx_("tz_encode_begin");
     if (!ctx || !edge || (entropy && !hist)) return TZ_ERR_INVALID;
     TZ_TRY(flat_only(ctx, "tz_encode_begin"));
+    TZ_TRY(no_frame_bounds(ctx, "tz_encode_begin"));
     TZ_TRY(encode_check(ctx, "tz_encode_begin", mode));
     ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload now receives a shard's symbols
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
@@ -1758,6 +1812,7 @@ extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const
     tz_roctx_range roctx_("tz_encode_finish");
     if (!ctx) return TZ_ERR_INVALID;
     TZ_TRY(flat_only(ctx, "tz_encode_finish"));
+    TZ_TRY(no_frame_bounds(ctx, "tz_encode_finish"));
     if (ctx->enc_kind != tz_ctx::ENC_SYMBOLS) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish needs a tz_encode_begin first");
     if (ctx->enc_entropy != (table_len >= 0) || (table_len > 0 && !table) || table_len > TZ_MAX_TABLE)
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode_finish: table does not match the entropy flag of tz_encode_begin");
@@ -2030,7 +2085,7 @@ extern "C" int tz_bound_probe(tz_ctx* ctx, int mode, double b0, double b1, tz_fr
     TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, d_mask, nt, H, W, ctx->Hp, ctx->Wp, d_delta));
     if (hipMemcpyAsync(d_q, d_delta, N * 2, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
         return tz_fail(ctx, TZ_ERR_HIP, "tz_bound_probe: copy of the delta stack failed");
-    TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
+    TZ_TRY(quantise_rollout(ctx, d_q, mode, b0, b1));
     TZ_TRY(call.out(out, sizeof(tz_frame_quality) * nt, &d_out));
     TZ_TRY(tzk_bound_err(ctx, channels, ctx->d_frames, d_delta, d_q, nt, fe, d_out));
     TZ_TRY(call.finish());
@@ -2186,6 +2241,29 @@ extern "C" int tz_error_bound(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, c
         if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "diff upload: %s", hipGetErrorString(e));
     }
     TZ_TRY(tzk_error_bound(ctx, dor, ddiff, sk.data(), nframes, H, W, mode, b0, b1));
+    return call.finish();
+}
+
+// tz_error_bound in abs mode with one tolerance per frame: the seam of tz_set_frame_bounds
+extern "C" int tz_error_bound_frames(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask, int nframes, int H,
+                                     int W, const double* bounds) {
+    if (!ctx || !orig || !diff || nframes < 0 || H < 1 || W < 1 || (nframes > 0 && !bounds)) return TZ_ERR_INVALID;
+    for (int f = 0; f < nframes; ++f)
+        if (!std::isfinite(bounds[f]) || bounds[f] < 0.0)
+            return tz_fail(ctx, TZ_ERR_INVALID, "tz_error_bound_frames: bound %g of frame %d is not a finite number >= 0", bounds[f], f);
+    size_t N = (size_t)nframes * H * W * 3;
+    std::vector<uint8_t> sk(nframes, 0);
+    if (skip_mask) memcpy(sk.data(), skip_mask, nframes);
+    tz_call call(ctx);
+    const uint8_t* dor;
+    int16_t* ddiff;
+    TZ_TRY(call.in(orig, N, &dor));
+    TZ_TRY(call.out(diff, N * 2, &ddiff));
+    if (call.outs.back().host) {
+        hipError_t e = hipMemcpyAsync(ddiff, diff, N * 2, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "diff upload: %s", hipGetErrorString(e));
+    }
+    TZ_TRY(tzk_quant_frames(ctx, dor, ddiff, nullptr, sk.data(), nframes, H, W, bounds, nullptr));
     return call.finish();
 }
 
@@ -2966,7 +3044,7 @@ extern "C" int tz_size_probe(tz_ctx* ctx, int mode, double b0, double b1, int en
     TZ_TRY(call.alloc(N * 2, &d_q));
     // compress.py:292-319 as encode_front's general path runs them (the quantiser walks three channels in every layout)
     TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, d_mask, nt, H, W, ctx->Hp, ctx->Wp, d_q));
-    TZ_TRY(tzk_error_bound(ctx, ctx->d_frames, d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1));
+    TZ_TRY(quantise_rollout(ctx, d_q, mode, b0, b1));
     memset(out, 0, sizeof(*out));
     return size_run(ctx, layout, d_q, (size_t)nt * tz_frame_elems(layout, H, W), entropy, coder, out);
 }

@@ -195,7 +195,8 @@ __device__ __forceinline__ void sdelta8(const uint4 V, unsigned prev16, bool app
 // --------------------------------------------------------------------------- quantiser
 // compress.py:23-70, one chain per (frame, channel) over H*W elements, row-major.
 // Stage 1 (k_q_minmax, k_q_bound): per-chain tolerance E for rel / absrel from max-min of the
-//                      ORIGINAL slab (compress.py:31-33,36-43).
+//                      ORIGINAL slab (compress.py:31-33,36-43).  Under one abs bound per frame (tzk_quant_frames) k_q_frame_bound
+//                      fills the same array from the frames' bounds instead.
 // Stage 2 (k_q_width, k_q_tiles, k_q_chain, k_q_bstitch, k_q_serial): exact parallel form of the greedy
 //                      interval-intersection segmentation (see the kernels).  Result: one bit per element (`spec`, a 64-bit
 //                      mask per 64-element chunk and chain) that says where a run starts, and the
@@ -308,6 +309,14 @@ __global__ void k_q_bound(const int* __restrict__ mm, const uint8_t* __restrict_
         e = a < r ? a : r;
     }
     E[i] = e;
+}
+
+// tolerance per chain from one abs bound per frame (tz_set_frame_bounds, tz_error_bound_frames): the frame's three chains
+// share it.  The walks then read it as they read k_q_bound's.
+__global__ void k_q_frame_bound(const double* __restrict__ fb, const uint8_t* __restrict__ skip, int nframes, double* __restrict__ E) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nframes * 3 || skip[i / 3]) return;
+    E[i] = fb[i / 3];
 }
 
 // Two forms of the exact greedy segmentation live here.
@@ -1401,8 +1410,11 @@ struct QFused {   // fused encode: symbols + histogram + edge elements instead o
     int16_t* d_edge;
 };
 
+// h_fb (may be NULL): nframes abs tolerances, one per frame, in place of (mode, b0, b1).  The walks run in their per-chain
+// form, the one rel / absrel run: k_q_frame_bound fills the array k_q_bound would fill, and a frame whose bound is 0 is
+// skipped, which is what `abs 0` does to it (compress.py:24).
 static int quant_run(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const QFused* fu, const uint8_t* h_skip, int nframes,
-                     int H, int W, int mode, double b0, double b1) {
+                     int H, int W, int mode, double b0, double b1, const double* h_fb = nullptr) {
     int HW = H * W;
     size_t fe = (size_t)HW * 3;
     int nblk = (HW + QFB - 1) / QFB;
@@ -1415,12 +1427,27 @@ static int quant_run(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const QFus
     TZ_TRY(tz_pool_alloc(ctx, (size_t)nframes * 3 * 2, &d_ftail));
     const int nch = (HW + 63) / 64;
     TZ_TRY(tz_pool_alloc(ctx, (size_t)nframes * 3 * nch * sizeof(unsigned long long), &d_spec));
+    std::vector<uint8_t> fb_skip;
+    void* d_fb = nullptr;
+    if (h_fb) {
+        fb_skip.assign(h_skip, h_skip + nframes);
+        for (int f = 0; f < nframes; ++f)
+            if (h_fb[f] == 0.0) fb_skip[f] = 1;
+        h_skip = fb_skip.data();
+        TZ_TRY(tz_pool_alloc(ctx, sizeof(double) * nframes, &d_fb));
+        TZ_TRY(tz_upload(ctx, d_fb, h_fb, sizeof(double) * nframes));
+        mode = TZ_MODE_REL;   // what makes every walk read Echain; no kernel below reads b0 or b1 in this mode
+        b0 = b1 = 0.0;
+    }
     TZ_TRY(tz_upload(ctx, d_skip, h_skip, nframes));
     QParams qp{mode, b0, b1};
     QSrc src{diff, fu ? fu->pred : nullptr};
     {
         tz_prof_scope ps(ctx, TZP_QUANT);
-        if (mode == TZ_MODE_REL || mode == TZ_MODE_ABSREL) {
+        if (h_fb) {
+            hipLaunchKernelGGL(k_q_frame_bound, dim3((3 * nframes + 63) / 64), dim3(64), 0, ctx->stream, (const double*)d_fb,
+                               (const uint8_t*)d_skip, nframes, (double*)d_E);
+        } else if (mode == TZ_MODE_REL || mode == TZ_MODE_ABSREL) {
             hipLaunchKernelGGL(k_q_mm_init, dim3((6 * nframes + 255) / 256), dim3(256), 0, ctx->stream, (int*)d_mm, 6 * nframes);
             hipLaunchKernelGGL(k_q_minmax, dim3(QBB, nframes), dim3(256), 0, ctx->stream, orig, (const uint8_t*)d_skip, HW,
                                (int*)d_mm);
@@ -1548,6 +1575,29 @@ int tzk_quant_sd_fused(tz_ctx* ctx, const float* pred, const uint8_t* orig, cons
     if ((((uintptr_t)pred & 15) | ((uintptr_t)orig & 3)) != 0) return TZ_OK;   // k_q_fill_sym: 16-byte pred, 4-byte orig loads
     QFused fu{pred, d_zero_mask, apply_offset, sym, d_hist, d_edge};
     TZ_TRY(quant_run(ctx, orig, nullptr, &fu, h_skip, nframes, H, W, mode, b0, b1));
+    *done = true;
+    return TZ_OK;
+}
+
+// `abs` with one tolerance per frame (tz_set_frame_bounds, tz_error_bound_frames): frame f is quantised as `abs h_bounds[f]`
+// quantises it, bit for bit -- the walks read the same E, from the per-chain array instead of the launch's parameters.
+// diff != NULL: the delta stack is quantised in place, as by tzk_error_bound.  diff == NULL: the fused lossy front on
+// pred / orig, as tzk_quant_sd_fused and under its conditions; *done says whether it ran.  The entries are finite and >= 0
+// (the setters check).
+int tzk_quant_frames(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const tz_quant_fused* fu, const uint8_t* h_skip, int nframes,
+                     int H, int W, const double* h_bounds, bool* done) {
+    if (done) *done = false;
+    if (nframes <= 0 || H <= 0 || W <= 0) return TZ_OK;
+    if (diff) {
+        bool any = false;
+        for (int f = 0; f < nframes; ++f) any = any || (h_bounds[f] != 0.0 && !h_skip[f]);
+        if (!any) return TZ_OK;   // every frame is left as it is
+        return quant_run(ctx, orig, diff, nullptr, h_skip, nframes, H, W, TZ_MODE_ABS, 0.0, 0.0, h_bounds);
+    }
+    if (H != fu->Hp || W != fu->Wp || ((size_t)H * W) % 8 || (((uintptr_t)fu->sym) & 15)) return TZ_OK;
+    if ((((uintptr_t)fu->pred & 15) | ((uintptr_t)orig & 3)) != 0) return TZ_OK;   // k_q_fill_sym: 16-byte pred, 4-byte orig loads
+    QFused q{fu->pred, fu->d_zero_mask, fu->apply_offset, fu->sym, fu->d_hist, fu->d_edge};
+    TZ_TRY(quant_run(ctx, orig, nullptr, &q, h_skip, nframes, H, W, TZ_MODE_ABS, 0.0, 0.0, h_bounds));
     *done = true;
     return TZ_OK;
 }

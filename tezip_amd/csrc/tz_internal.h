@@ -132,6 +132,7 @@ struct tz_ctx {
     unsigned* d_fault = nullptr;
     int decode_unfused = 0;                 // TEZIP_DECODE_UNFUSED=1: tz_decode as scan + reconstruct launches (cross-check)
     int payload_channels = 3;               // tz_set_payload_channels: 1 = the payload of a gray job holds channel 0 alone
+    std::vector<double> frame_bounds;       // tz_set_frame_bounds: one abs tolerance per frame of the encoder rollout (empty: none)
     int delta_stride_mode = 0;              // tz_set_delta_stride: 1 = the spatial delta of the payload runs at the channel stride
     unsigned long long* d_scan3_status = nullptr;   // strided inverse scan (k_scan3p): one 64-bit word per block, own epochs
     unsigned scan3_epoch = 0;
@@ -349,6 +350,18 @@ bool tz_quant_is_identity(int mode, double b0, double b1);   // error_bound leav
 int tzk_quant_sd_fused(tz_ctx*, const float* pred, const uint8_t* orig, const uint8_t* d_zero_mask, const uint8_t* h_skip,
                        int nframes, int H, int W, int Hp, int Wp, int mode, double b0, double b1, int apply_offset,
                        int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done);
+// `abs` with one tolerance per frame (h_bounds: nframes finite doubles >= 0): on a delta stack in place (diff), or -- diff NULL --
+// as the fused lossy front that `fu` describes, where its kernels apply (*done).
+struct tz_quant_fused {
+    const float* pred;
+    const uint8_t* d_zero_mask;
+    int Hp, Wp, apply_offset;
+    int16_t* sym;
+    unsigned long long* d_hist;
+    int16_t* d_edge;
+};
+int tzk_quant_frames(tz_ctx*, const uint8_t* orig, int16_t* diff, const tz_quant_fused* fu, const uint8_t* h_skip, int nframes,
+                     int H, int W, const double* h_bounds, bool* done);
 // The layout of the payload, stated once per layer: elements per pixel, and how far in front the element
 // lies that the spatial delta subtracts.  flat {3, 1} is the reference's; gray {1, 1} stores channel 0 alone
 // (tz_set_payload_channels(1)); channel stride {3, 3} takes the same channel of the pixel in front (tz_set_delta_stride(1)).

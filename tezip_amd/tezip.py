@@ -15,7 +15,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "tezip_amd"
 
-from . import compress, decompress, target, train  # noqa: E402
+from . import compress, decompress, frametarget, target, train  # noqa: E402
 
 # (short, long, argparse keywords) -- tezip.py:88-99
 FLAG_TABLE = (
@@ -86,6 +86,15 @@ FLAG_TABLE = (
     # rollout, at most 11 probes; a boundary, not necessarily the smallest such bound).  Also writes bound_search.json; a
     # target that abs 255 misses ends the job with exit status 4 (compress.run(TARGET_RATIO=...))
     (None, "--target-ratio", dict(type=float, default=None, metavar="R", dest="target_ratio")),
+    # not in the reference: with -c --target-psnr DB: the target holds in EVERY frame that is not stored exactly (frame 0, warm-up
+    # and key frames are).  Each such frame gets an abs bound of its own (a multiple of 0.5) from a bisection of its own, all
+    # driven by the same at most 9 probes (definition TZ-TPSNR-F1 in tezip_amd/frametarget.py; per frame a boundary, not
+    # necessarily the largest such bound).  The files are ordinary ones: -u needs no flag (compress.run(PER_FRAME=True))
+    (None, "--per-frame", dict(action="store_true", dest="per_frame")),
+    # not in the reference: with -c -m abs, IN PLACE of -b: one abs bound per image from a JSON file, a list of numbers or an
+    # object with a "frame_bounds" list (the bound_search.json of a --per-frame job replays); 0 keeps a frame lossless; entries
+    # at frames that are stored exactly are taken as 0 (compress.run(FRAME_BOUNDS=FILE))
+    (None, "--frame-bounds", dict(type=str, default=None, metavar="FILE", dest="frame_bounds")),
 )
 
 TEXT = {
@@ -266,6 +275,30 @@ def check_ratio_flag(arg):
                                 getattr(arg, "coder", "zstd"), arg.shuffle, int(os.environ.get("WORLD_SIZE", "1")) > 1)
 
 
+def check_frame_bounds_flags(arg):
+    """--per-frame goes with -c --target-psnr, --frame-bounds with -c -m abs in place of -b; both need one single-GPU job without
+    --sweep.  The file of --frame-bounds is read here (its length is checked once the images are listed).  Returns None, or the
+    message of a refusal."""
+    per_frame, path = bool(getattr(arg, "per_frame", False)), getattr(arg, "frame_bounds", None)
+    if not per_frame and path is None:
+        return None
+    flag = "--per-frame" if per_frame else "--frame-bounds"
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "%s is valid with -c (--compress) only (-u decodes such a job without a flag)" % flag
+    if getattr(arg, "sweep", None) is not None:
+        return "%s cannot be combined with --sweep" % flag
+    problem = frametarget.check(per_frame, path, "abs" if per_frame and arg.mode is None else (arg.mode[0] if arg.mode else None),
+                                arg.bound, getattr(arg, "target_psnr", None), getattr(arg, "target_ratio", None),
+                                int(os.environ.get("WORLD_SIZE", "1")) > 1)
+    if problem or path is None:
+        return problem
+    try:
+        frametarget.load(path)
+    except ValueError as e:
+        return str(e)
+    return None
+
+
 def check_verify_flag(arg):
     """--verify is valid with -u only; `require` needs frame_digests.json in the directory and one GPU.  Returns None, or the
     message of a refusal."""
@@ -321,6 +354,10 @@ def check_compress(arg):
 def _main(arg):
     frames, problem = check_frames_flag(arg)
     if problem:   # exit status 2, as decompress.adopt_contract's errors: nothing was written
+        print("ERROR:", problem)
+        sys.exit(2)
+    problem = check_frame_bounds_flags(arg)
+    if problem:   # likewise (in front of the other flags' checks: a refusal of this job names the flag that defines it)
         print("ERROR:", problem)
         sys.exit(2)
     problem = check_ratio_flag(arg)
@@ -386,7 +423,10 @@ def _main(arg):
         return decompress.run(model, src, dst, gpu, arg.verbose)
     print("compress mode")
     db, ratio = getattr(arg, "target_psnr", None), getattr(arg, "target_ratio", None)
-    if db is not None or ratio is not None:   # the job is an `abs` job whose bound is still to be found: the same checks, and `abs` is printed
+    per_frame, bounds_file = bool(getattr(arg, "per_frame", False)), getattr(arg, "frame_bounds", None)
+    if bounds_file is not None:   # an `abs` job whose bounds come from the file: the same checks with a bound in -b's place
+        problem = check_compress(argparse.Namespace(**dict(vars(arg), bound=[0.0])))
+    elif db is not None or ratio is not None:   # the job is an `abs` job whose bound is still to be found: the same checks, and `abs` is printed
         problem = check_compress(argparse.Namespace(**dict(vars(arg), mode=["abs"], bound=[0.0])))
     else:
         problem = check_compress(arg)
@@ -399,6 +439,13 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if per_frame or bounds_file is not None:   # (every other flag travels with it; the jobs without it are the calls below)
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), GRAY=bool(getattr(arg, "gray", False)),
+                            SDELTA=getattr(arg, "sdelta", None) or "flat", SSIM=bool(getattr(arg, "ssim", False)), TARGET_PSNR=db,
+                            PER_FRAME=per_frame, FRAME_BOUNDS=bounds_file)
     if ratio is not None:   # (every other flag travels with it; the jobs without it are the calls below)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
