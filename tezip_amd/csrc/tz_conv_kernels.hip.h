@@ -1607,6 +1607,22 @@ __global__ __launch_bounds__(256) void k_uniform_ring(const unsigned* __restrict
     if ((threadIdx.x & 63) == 0 && mine) atomicMax(ring, mine);
 }
 
+// Which 16-channel blocks of a [pixel][C] plane hold anything but zeros of either sign (tz_prednet.hip measure_dead): bit b
+// of *live is set when some pixel of the plane has a non-zero magnitude in one of the channels 16 b .. 16 b + 15.  Only the
+// first `nblocks` (<= 64) blocks are looked at.
+__global__ __launch_bounds__(256) void k_live_blocks(const unsigned* __restrict__ src, long long npx, int C, int nblocks,
+                                                     unsigned long long* __restrict__ live) {
+    const long long total = npx * C;
+    unsigned long long mine = 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(i % C) >> 4;
+        if (b < nblocks && (src[i] & 0x7fffffffu)) mine |= 1ull << b;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mine |= __shfl_xor(mine, o);
+    if ((threadIdx.x & 63) == 0 && mine) atomicOr(live, mine);
+}
+
 // level-0 error unit (prednet.py:274-277 with a = input frame, Ahat = Ahat_0(t0)):
 // input is either a key frame (uint8, unpadded; x = float32(k)/255, compress.py:138) or a
 // padded float32 frame of the prediction stack (compress.py:222).

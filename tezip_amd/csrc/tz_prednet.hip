@@ -22,6 +22,7 @@
 //
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 
 #include "tz_conv_kernels.hip.h"
 #include "tz_wino_kernels.hip.h"
@@ -40,6 +41,7 @@ struct PackedConv {
     const float* d_zero = nullptr;
     float* d_bias = nullptr;
     int nslots = 0, ncols = 0, NT = 1, ncb = 1;
+    int wino_finite = 0;      // pack_wino: leading 16-channel blocks of segs[0] whose transformed weights are all finite
     std::vector<Seg> segs;
 };
 
@@ -64,6 +66,9 @@ struct tz_model {
     int tring[3][TZ_MAX_LEVELS] = {{0}};   // ... outside this ring every 16 x 16 tile equals the reference tile (ConvArgs)
     const float* uni[3][TZ_MAX_LEVELS] = {{0}};
     int uniform_mask = 0;   // TEZIP_UNIFORM at prepare time: which consumers take the shortcut (UNI_USE_*), default all
+    // Leading 16-channel blocks of E_l that are +0 at every pixel of every frame (measure_dead, tz_model_prepare), and how
+    // many of them the k_wino launches of the level's gate convolution / of A_l leave out (0 where a skipped weight is not finite)
+    int dead[TZ_MAX_LEVELS] = {0}, dead_gate[TZ_MAX_LEVELS] = {0}, dead_a[TZ_MAX_LEVELS] = {0};
     float *E[TZ_MAX_LEVELS] = {0}, *R1[TZ_MAX_LEVELS] = {0};
     float* P[TZ_MAX_LEVELS] = {0};   // gate accumulators after the E_l part of the chain (split launches of small grids), or null
     int Pcap[TZ_MAX_LEVELS] = {0};   // ... how many batch slots P[l] holds (<= maxB: at most kPBytes per level)
@@ -252,6 +257,7 @@ static int pack_wino(tz_ctx* ctx, tz_model* m, const std::vector<Seg>& segs, con
     auto at = [&](int st, int cb, int set, int lane, int nt) -> float& {
         return I[((((size_t)cb * (S1 + S2) + st) * 16 + set) * 64 + lane) * 4 + nt];
     };
+    std::vector<char> finite((size_t)segs[0].C / 16, 1);   // per 16-channel block of segs[0]: every U of every column is finite
     for (int col = 0; col < ncols; ++col) {
         const ColSrc& cs = cols[col];
         if (cs.ch < 0) continue;
@@ -274,7 +280,10 @@ static int pack_wino(tz_ctx* ctx, tz_model* m, const std::vector<Seg>& segs, con
                 U[i][2] = 0.5f * (s_ - w[i][1]);
                 U[i][3] = w[i][2];
             }
-            for (int p = 0; p < 16; ++p) at(c / 4, cb, p, (c % 4) * 16 + j, nt) = U[p >> 2][p & 3];
+            for (int p = 0; p < 16; ++p) {
+                at(c / 4, cb, p, (c % 4) * 16 + j, nt) = U[p >> 2][p & 3];
+                if (!std::isfinite(U[p >> 2][p & 3])) finite[c / 16] = 0;
+            }
         }
         for (int c = 0; c < (S2 ? segs[1].C : 0); ++c)
             for (int cls = 0; cls < 4; ++cls)
@@ -292,6 +301,8 @@ static int pack_wino(tz_ctx* ctx, tz_model* m, const std::vector<Seg>& segs, con
                     at(S1 + c / 4, cb, 8 * (cls >> 1) + 2 * tp + (cls & 1), (c % 4) * 16 + j, nt) = v;
                 }
     }
+    pc->wino_finite = 0;
+    while (pc->wino_finite < (int)finite.size() && finite[pc->wino_finite]) ++pc->wino_finite;
     TZ_TRY(dmalloc(ctx, m, (void**)&pc->d_Wwino, I.size() * 4));
     TZ_HIP(ctx, hipMemcpy(pc->d_Wwino, I.data(), I.size() * 4, hipMemcpyHostToDevice));
     return TZ_OK;
@@ -387,10 +398,25 @@ static int launch_wino_ref_t(tz_ctx* ctx, const ConvArgs& a, int nbatch) {
     return TZ_OK;
 }
 
-static int launch_wino(tz_ctx* ctx, int NT, int epi, bool ups, const ConvArgs& a, int nbatch, bool nosame = false) {
+// `dead`: leading 16-channel blocks of the same-resolution source that are +0 at every pixel (measure_dead).  k_wino leaves
+// their stages out: it takes its same-resolution stage count from src[0].C and its patch pointer from src[0].p, and it
+// already walks a PART of a column block's stages (wino_first / wino_stride), so the skip is a later first stage, a source
+// pointer 16 dead floats further on and a shorter source; wino_stride stays the FULL stage count of a column block, so
+// that the weight pointer lands on the next block's first executed stage.  The first executed stage of an item is still the
+// mfma_first one: after the dead stages every chain would hold exactly the +0 it starts from.  The
+// NOSAME half of a split walks no same-resolution stage and k_wino_ref stays the unskipped cross-check: both ignore `dead`.
+static int launch_wino(tz_ctx* ctx, int NT, int epi, bool ups, const ConvArgs& a0, int nbatch, bool nosame = false, int dead = 0) {
     if (nosame) {   // the second launch of a split gate convolution (tz_model_predict_batch_dev, "E-part ahead")
-        if (NT == 4 && epi == EPI_LSTM && ups && ctx->conv_impl) return launch_wino_t<4, EPI_LSTM, true, true>(ctx, a, nbatch);
+        if (NT == 4 && epi == EPI_LSTM && ups && ctx->conv_impl) return launch_wino_t<4, EPI_LSTM, true, true>(ctx, a0, nbatch);
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "no split TZ-PA2 kernel for NT=%d epilogue=%d upsampled=%d", NT, epi, (int)ups);
+    }
+    ConvArgs a = a0;
+    if (ctx->conv_impl && dead > 0 && 16 * (dead + 1) <= a.src[0].C) {   // (at least one block of the source remains)
+        if (!a.wino_stride) a.wino_stride = (a.src[0].C + (ups ? a.src[1].C : 0)) >> 2;
+        a.wino_first += 4 * dead;
+        a.src[0].p += 16 * dead;
+        a.src[0].C -= 16 * dead;
+        a.src[0].cpt -= dead;
     }
     if (!ctx->conv_impl) {   // tz_set_conv_impl(0): the plain statement of the same chains
         if (NT == 4 && epi == EPI_LSTM) return ups ? launch_wino_ref_t<4, EPI_LSTM, true>(ctx, a, nbatch) : launch_wino_ref_t<4, EPI_LSTM, false>(ctx, a, nbatch);
@@ -480,7 +506,10 @@ static LatPlan lat_plan(const tz_ctx* ctx, int NT, int epi, bool ups, bool fullk
     return lp;
 }
 
-static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbatch) {
+// (wino_dead: dead leading blocks of the same-resolution source, for k_wino alone -- launch_wino.  The TZ-PA1 kernels below,
+// k_conv16 / k_convlat / k_conv16b / k_conv3x3, walk every block: their chains start from G0 or the bias, which may be -0, and
+// fmaf(+0, w, -0) = +0 is not what the chain held; level 0 has no 16-channel block to leave out)
+static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbatch, int wino_dead = 0) {
     tz_prof_scope ps(ctx, TZP_CONV);
     bool ups = false, fullk = true;
     for (int s = 0; s < a.nsrc; ++s) {
@@ -516,7 +545,7 @@ static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbat
     // (the contract fixes the arithmetic per convolution; k_wino_ref is its cross-check, tz_set_conv_impl(0))
     if (a.Wwino && effective_contract(ctx) == 2 && fullk && (epi == EPI_LSTM || epi == EPI_POOL_ERR || epi == EPI_RAW)) {
         ps.sub = TZP_WINO;
-        return launch_wino(ctx, NT, epi, ups, a, nbatch);
+        return launch_wino(ctx, NT, epi, ups, a, nbatch, false, wino_dead);
     }
     {
         const LatPlan lp = lat_plan(ctx, NT, epi, ups, fullk, a, nbatch);
@@ -718,6 +747,60 @@ static int measure_uniform(tz_ctx* ctx, tz_model* m) {
     return TZ_OK;
 }
 
+// Dead leading blocks of the error maps.  The same-resolution source of every k_wino launch is E_l = [relu(Ahat0_l - A_l),
+// relu(A_l - Ahat0_l)], the positive half first.  A_l is the output of a relu (x > 0 ? x : 0): +0, positive or +inf, never
+// NaN and never -0.  So where Ahat0_l is +-0 over the WHOLE plane for a channel, Ahat0_l - A_l is <= 0 or +-0 and that channel
+// of E_l is +0 at every pixel of every frame, for as long as the model stays prepared.  Nothing is assumed about the model:
+// k_live_blocks looks at the magnitude bits of every pixel of Ahat0_l, and dead[l] is the number of LEADING 16-channel blocks
+// (four k_wino stages, once round its ring) without a set bit that lie entirely inside the positive half, leaving at least one
+// block of the source.  Zero biases (Keras' default initialisation, the bench's model): the whole positive half at every level.
+// A model with biases: as a rule none.  Why k_wino may leave such stages out without changing a bit, and why only a prefix,
+// only under TZ-PA2 and only over finite weights (PackedConv::wino_finite): DESIGN.md section 5, tests/test_deadsrc_oracle.py.
+// TEZIP_DEADSRC=0 (read here, per prepare): never; TEZIP_DEADSRC_LOG=1: one line per level and convolution.
+static int measure_dead(tz_ctx* ctx, tz_model* m) {
+    const int L = m->L;
+    const char* env = getenv("TEZIP_DEADSRC");
+    const bool on = !env || atoi(env) != 0;
+    const bool log = getenv("TEZIP_DEADSRC_LOG") && atoi(getenv("TEZIP_DEADSRC_LOG"));
+    unsigned long long h_live[TZ_MAX_LEVELS] = {0};
+    for (int l = 0; l < TZ_MAX_LEVELS; ++l) m->dead[l] = m->dead_gate[l] = m->dead_a[l] = 0;
+    if (on) {
+        unsigned long long* d_live = nullptr;
+        TZ_TRY(dmalloc(ctx, m, (void**)&d_live, sizeof(h_live)));
+        TZ_HIP(ctx, hipMemsetAsync(d_live, 0, sizeof(h_live), ctx->stream));
+        for (int l = 1; l < L; ++l) {
+            const long long npx = (long long)(m->Hp >> l) * (m->Wp >> l);
+            const int nb = std::min(m->stack[l] / 16, 64);
+            if (nb < 1) continue;
+            hipLaunchKernelGGL(k_live_blocks, dim3((unsigned)std::min<long long>((npx * m->stack[l] + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                               (const unsigned*)m->Ahat0[l], npx, m->stack[l], nb, d_live + l);
+            TZ_HIP(ctx, hipGetLastError());
+        }
+        TZ_HIP(ctx, hipMemcpyAsync(h_live, d_live, sizeof(h_live), hipMemcpyDeviceToHost, ctx->stream));
+        TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    for (int l = 1; l < L; ++l) {
+        const int src_blocks = 2 * m->stack[l] / 16;   // blocks of E_l
+        int d = 0;
+        // inside the positive half (16 (d + 1) <= stack[l]), one of the blocks looked at, and a block of the source remains
+        while (on && 16 * (d + 1) <= m->stack[l] && d < 64 && d + 1 < src_blocks && !((h_live[l] >> d) & 1)) ++d;
+        m->dead[l] = d;
+        // a skipped stage multiplies +0 by its weights: that is +0 only where every one of them is finite
+        const PackedConv* pcs[2] = {&m->gate_t1[l], l < L - 1 ? &m->a_conv[l] : nullptr};
+        int* out[2] = {&m->dead_gate[l], &m->dead_a[l]};
+        static const char* const names[2] = {"gates", "A"};
+        for (int k = 0; k < 2; ++k) {
+            if (!pcs[k] || !pcs[k]->d_Wwino) continue;
+            *out[k] = pcs[k]->wino_finite >= d ? d : 0;
+            if (log)
+                fprintf(stderr, "[tezip] dead source, level %d %s: %d of %d leading positive-half blocks dead, %d skipped: %d of %d same-resolution stages%s\n",
+                        l, names[k], d, m->stack[l] / 16, *out[k], 4 * *out[k], 2 * m->stack[l] / 4,
+                        !on ? " (TEZIP_DEADSRC=0)" : (*out[k] < d ? " (a weight of those stages is not finite)" : ""));
+        }
+    }
+    return TZ_OK;
+}
+
 extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
     tz_roctx_range roctx_("tz_model_prepare");
     if (!ctx) return TZ_ERR_INVALID;
@@ -884,6 +967,7 @@ extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
         if (l >= 1) TZ_TRY(pack_wino(ctx, m, {Seg{0, 2 * m->stack[l], 0}}, plain_cols(m->a_k(l), m->a_b(l), 2 * m->stack[l], Cout), NT, &m->a_conv[l]));
     }
     TZ_TRY(measure_uniform(ctx, m));   // (synchronises the stream)
+    TZ_TRY(measure_dead(ctx, m));
     m->prepared = true;
     return TZ_OK;
 }
@@ -940,7 +1024,7 @@ static bool epart_levels(tz_ctx* ctx, tz_model* m, int n, bool* lv, double* idle
         const int s_e = (2 * m->stack[l]) / 4, s_u = l < L - 1 ? m->rstack[l + 1] / 4 : 0;
         const long long it[2] = {m->gate_t1[l].d_Wwino ? tiles * m->gate_t1[l].ncb : 0,
                                  l < L - 1 && m->a_conv[l].d_Wwino ? tiles * m->a_conv[l].ncb : 0};
-        const int st[2] = {s_e + s_u, s_e};
+        const int st[2] = {s_e - 4 * m->dead_gate[l] + s_u, s_e - 4 * m->dead_a[l]};   // the stages actually walked (measure_dead)
         for (int k = 0; k < 2; ++k) {
             if (!it[k]) continue;
             busy += (double)it[k] / ctx->num_cus * st[k];
@@ -1144,7 +1228,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_epart_src[l], 0));
         hipStream_t main_stream = ctx->stream;
         ctx->stream = ctx->stream2;       // (the launchers and their profiling scopes take the context's stream)
-        int rc = launch_conv(ctx, 4, EPI_RAW, ge, n);
+        int rc = launch_conv(ctx, 4, EPI_RAW, ge, n, m->dead_gate[l]);
         ctx->stream = main_stream;
         TZ_TRY(rc);
         TZ_HIP(ctx, hipEventRecord(ctx->ev_epart_done[l], ctx->stream2));
@@ -1190,7 +1274,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
                 continue;
             }
         }
-        TZ_TRY(launch_conv(ctx, pc.NT, EPI_POOL_ERR, a, n));
+        TZ_TRY(launch_conv(ctx, pc.NT, EPI_POOL_ERR, a, n, m->dead_a[l]));
         // The side launches go out behind the A convolution that writes the E of the HIGHEST split level (the A convolutions
         // below it fill the chip by themselves), the highest level first: its second half is the first one the critical path
         // will ask for.
@@ -1233,7 +1317,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
             TZ_TRY(launch_wino(ctx, 4, EPI_LSTM, true, a, n, true));
             continue;
         }
-        TZ_TRY(launch_conv(ctx, pc.NT, pc.NT == 4 ? EPI_LSTM : EPI_LSTM_PACKED, a, n));
+        TZ_TRY(launch_conv(ctx, pc.NT, pc.NT == 4 ? EPI_LSTM : EPI_LSTM_PACKED, a, n, m->dead_gate[l]));
     }
     {  // Ahat_0 at t1 = the prediction (prednet.py:268-271, 293-295)
         const PackedConv& pc = m->ahat0_t1;
