@@ -21,7 +21,9 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum { EPI_RAW = 0, EPI_RELU = 1, EPI_LSTM = 2, EPI_LSTM_PACKED = 3, EPI_POOL_ERR = 4 };
+// (EPI_LSTM3 / EPI_RAW3: k_wino only -- the LSTM update of a level whose start cell state is +0 everywhere, columns
+// [i | g | o] x 16, and the first half of such a gate convolution run as two launches)
+enum { EPI_RAW = 0, EPI_RELU = 1, EPI_LSTM = 2, EPI_LSTM_PACKED = 3, EPI_POOL_ERR = 4, EPI_LSTM3 = 5, EPI_RAW3 = 6 };
 
 struct ConvSrc {
     const float* p;
@@ -1609,14 +1611,15 @@ __global__ __launch_bounds__(256) void k_uniform_ring(const unsigned* __restrict
 
 // Which 16-channel blocks of a [pixel][C] plane hold anything but zeros of either sign (tz_prednet.hip measure_dead): bit b
 // of *live is set when some pixel of the plane has a non-zero magnitude in one of the channels 16 b .. 16 b + 15.  Only the
-// first `nblocks` (<= 64) blocks are looked at.
+// first `nblocks` (<= 64) blocks are looked at.  `mask`: the bits of a word that count -- 0x7fffffff: the magnitude (zeros of
+// either sign are dead); 0xffffffff: the whole word (only +0 is, measure_deadf).
 __global__ __launch_bounds__(256) void k_live_blocks(const unsigned* __restrict__ src, long long npx, int C, int nblocks,
-                                                     unsigned long long* __restrict__ live) {
+                                                     unsigned long long* __restrict__ live, unsigned mask = 0x7fffffffu) {
     const long long total = npx * C;
     unsigned long long mine = 0;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int b = (int)(i % C) >> 4;
-        if (b < nblocks && (src[i] & 0x7fffffffu)) mine |= 1ull << b;
+        if (b < nblocks && (src[i] & mask)) mine |= 1ull << b;
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) mine |= __shfl_xor(mine, o);

@@ -42,6 +42,7 @@ struct PackedConv {
     float* d_bias = nullptr;
     int nslots = 0, ncols = 0, NT = 1, ncb = 1;
     int wino_finite = 0;      // pack_wino: leading 16-channel blocks of segs[0] whose transformed weights are all finite
+    bool wino_all_finite = false;   // pack_wino: every value of the stage image, both sources and every column, is finite
     std::vector<Seg> segs;
 };
 
@@ -69,11 +70,15 @@ struct tz_model {
     // Leading 16-channel blocks of E_l that are +0 at every pixel of every frame (measure_dead, tz_model_prepare), and how
     // many of them the k_wino launches of the level's gate convolution / of A_l leave out (0 where a skipped weight is not finite)
     int dead[TZ_MAX_LEVELS] = {0}, dead_gate[TZ_MAX_LEVELS] = {0}, dead_a[TZ_MAX_LEVELS] = {0};
+    // Levels whose start cell state C0_l is +0 in every word (measure_deadf, tz_model_prepare): their k_wino gate launches,
+    // fused or split, take gate_nf[l], the stage image of the same convolution packed WITHOUT the forget-gate columns
+    bool deadf[TZ_MAX_LEVELS] = {false};
     float *E[TZ_MAX_LEVELS] = {0}, *R1[TZ_MAX_LEVELS] = {0};
     float* P[TZ_MAX_LEVELS] = {0};   // gate accumulators after the E_l part of the chain (split launches of small grids), or null
     int Pcap[TZ_MAX_LEVELS] = {0};   // ... how many batch slots P[l] holds (<= maxB: at most kPBytes per level)
     std::vector<signed char> epart_choice;   // [n]: "E-part ahead" for batches of n items: -1 not measured yet, 0 fused, 1 split
     PackedConv a_conv[TZ_MAX_LEVELS], gate_t1[TZ_MAX_LEVELS], ahat0_t1;
+    PackedConv gate_nf[TZ_MAX_LEVELS];   // d_Wwino only: column blocks [i | g | o] x 16 (pack_wino with NT = 3), levels >= 1
     float* d_zero = nullptr;  // zero page for LDS-DMA halo pixels
     int e0s = 0;              // floats per pixel of E[0]: 2*stack[0] rounded up to 8 (k_conv16b reads 16-byte quads)
     int* d_idx = nullptr;  // 3*maxB ints: is_key, in_idx, out_idx
@@ -258,6 +263,7 @@ static int pack_wino(tz_ctx* ctx, tz_model* m, const std::vector<Seg>& segs, con
         return I[((((size_t)cb * (S1 + S2) + st) * 16 + set) * 64 + lane) * 4 + nt];
     };
     std::vector<char> finite((size_t)segs[0].C / 16, 1);   // per 16-channel block of segs[0]: every U of every column is finite
+    bool ups_finite = true;                                // ... and every collapsed sum of segs[1]
     for (int col = 0; col < ncols; ++col) {
         const ColSrc& cs = cols[col];
         if (cs.ch < 0) continue;
@@ -299,10 +305,13 @@ static int pack_wino(tz_ctx* ctx, tz_model* m, const std::vector<Seg>& segs, con
                             first = false;
                         }
                     at(S1 + c / 4, cb, 8 * (cls >> 1) + 2 * tp + (cls & 1), (c % 4) * 16 + j, nt) = v;
+                    if (!std::isfinite(v)) ups_finite = false;
                 }
     }
     pc->wino_finite = 0;
     while (pc->wino_finite < (int)finite.size() && finite[pc->wino_finite]) ++pc->wino_finite;
+    // (a non-finite weight of either source leaves a non-finite value in the image: every tap is a term of some U or collapsed sum)
+    pc->wino_all_finite = ups_finite && pc->wino_finite == (int)finite.size();
     TZ_TRY(dmalloc(ctx, m, (void**)&pc->d_Wwino, I.size() * 4));
     TZ_HIP(ctx, hipMemcpy(pc->d_Wwino, I.data(), I.size() * 4, hipMemcpyHostToDevice));
     return TZ_OK;
@@ -405,8 +414,19 @@ static int launch_wino_ref_t(tz_ctx* ctx, const ConvArgs& a, int nbatch) {
 // that the weight pointer lands on the next block's first executed stage.  The first executed stage of an item is still the
 // mfma_first one: after the dead stages every chain would hold exactly the +0 it starts from.  The
 // NOSAME half of a split walks no same-resolution stage and k_wino_ref stays the unskipped cross-check: both ignore `dead`.
-static int launch_wino(tz_ctx* ctx, int NT, int epi, bool ups, const ConvArgs& a0, int nbatch, bool nosame = false, int dead = 0) {
+// `wino3`: the stage image of a gate convolution without its forget-gate columns (measure_deadf), or null.  k_wino then runs
+// three column tiles with the EPI_LSTM3 epilogue over it; everything else of the launch -- start values, biases (64 columns a
+// block), the dead-source prefix, ipw / ncb -- is the four-gate launch's.  The halves of a split gate convolution take it
+// too (EPI_RAW3, then EPI_LSTM3 from rows of 3 R columns in P_l).  k_wino_ref stays the four-gate cross-check.
+static int launch_wino(tz_ctx* ctx, int NT, int epi, bool ups, const ConvArgs& a0, int nbatch, bool nosame = false, int dead = 0,
+                       const float* wino3 = nullptr) {
     if (nosame) {   // the second launch of a split gate convolution (tz_model_predict_batch_dev, "E-part ahead")
+        if (NT == 4 && epi == EPI_LSTM && ups && ctx->conv_impl && wino3) {   // (its start values: rows of 3 R columns, per item)
+            ConvArgs a = a0;
+            a.Wwino = wino3;
+            a.ncols = 3 * a.Cout;
+            return launch_wino_t<3, EPI_LSTM3, true, true>(ctx, a, nbatch);
+        }
         if (NT == 4 && epi == EPI_LSTM && ups && ctx->conv_impl) return launch_wino_t<4, EPI_LSTM, true, true>(ctx, a0, nbatch);
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "no split TZ-PA2 kernel for NT=%d epilogue=%d upsampled=%d", NT, epi, (int)ups);
     }
@@ -424,6 +444,14 @@ static int launch_wino(tz_ctx* ctx, int NT, int epi, bool ups, const ConvArgs& a
         if (epi == EPI_POOL_ERR && !ups) return NT == 4 ? launch_wino_ref_t<4, EPI_POOL_ERR, false>(ctx, a, nbatch) : launch_wino_ref_t<3, EPI_POOL_ERR, false>(ctx, a, nbatch);
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "no TZ-PA2 reference kernel for NT=%d epilogue=%d upsampled=%d", NT, epi, (int)ups);
     }
+    if (NT == 4 && epi == EPI_LSTM && wino3) {
+        a.Wwino = wino3;
+        return ups ? launch_wino_t<3, EPI_LSTM3, true>(ctx, a, nbatch) : launch_wino_t<3, EPI_LSTM3, false>(ctx, a, nbatch);
+    }
+    if (NT == 4 && epi == EPI_RAW && wino3 && !ups) {   // the first half of a split: rows of 3 R columns out
+        a.Wwino = wino3;
+        return launch_wino_t<3, EPI_RAW3, false>(ctx, a, nbatch);
+    }
     if (NT == 4 && epi == EPI_LSTM) return ups ? launch_wino_t<4, EPI_LSTM, true>(ctx, a, nbatch) : launch_wino_t<4, EPI_LSTM, false>(ctx, a, nbatch);
     if (NT == 4 && epi == EPI_RAW) return ups ? launch_wino_t<4, EPI_RAW, true>(ctx, a, nbatch) : launch_wino_t<4, EPI_RAW, false>(ctx, a, nbatch);
     if (epi == EPI_POOL_ERR && !ups) return NT == 4 ? launch_wino_t<4, EPI_POOL_ERR, false>(ctx, a, nbatch) : launch_wino_t<3, EPI_POOL_ERR, false>(ctx, a, nbatch);
@@ -437,6 +465,7 @@ static constexpr long long TZ_PA2_MIN_PIXELS = 256 * 256;
 static constexpr size_t kPBytes = (size_t)160 << 20;      // P[l]: at most this much per level (tz_model_prepare)
 static constexpr double kEpartMinIdle = 0.06;   // "E-part ahead": below this idle share of a step's k_wino launches the split is not even tried
 static constexpr int kEpartSteps = 3;             // ... steps back to back per timed sample of its measurement
+static constexpr int kEpartSamples = 4;           // ... timed samples per form (the best one counts), behind one untimed
 static constexpr float kEpartMinGain = 0.98f;   // ... and it is kept only where it measures at least 2 % faster than the fused step
 static int effective_contract(const tz_ctx* ctx) {
     if (ctx->contract) return ctx->contract;
@@ -509,7 +538,8 @@ static LatPlan lat_plan(const tz_ctx* ctx, int NT, int epi, bool ups, bool fullk
 // (wino_dead: dead leading blocks of the same-resolution source, for k_wino alone -- launch_wino.  The TZ-PA1 kernels below,
 // k_conv16 / k_convlat / k_conv16b / k_conv3x3, walk every block: their chains start from G0 or the bias, which may be -0, and
 // fmaf(+0, w, -0) = +0 is not what the chain held; level 0 has no 16-channel block to leave out)
-static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbatch, int wino_dead = 0) {
+// (wino3: launch_wino)
+static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbatch, int wino_dead = 0, const float* wino3 = nullptr) {
     tz_prof_scope ps(ctx, TZP_CONV);
     bool ups = false, fullk = true;
     for (int s = 0; s < a.nsrc; ++s) {
@@ -545,7 +575,7 @@ static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbat
     // (the contract fixes the arithmetic per convolution; k_wino_ref is its cross-check, tz_set_conv_impl(0))
     if (a.Wwino && effective_contract(ctx) == 2 && fullk && (epi == EPI_LSTM || epi == EPI_POOL_ERR || epi == EPI_RAW)) {
         ps.sub = TZP_WINO;
-        return launch_wino(ctx, NT, epi, ups, a, nbatch, false, wino_dead);
+        return launch_wino(ctx, NT, epi, ups, a, nbatch, false, wino_dead, wino3);
     }
     {
         const LatPlan lp = lat_plan(ctx, NT, epi, ups, fullk, a, nbatch);
@@ -801,6 +831,68 @@ static int measure_dead(tz_ctx* ctx, tz_model* m) {
     return TZ_OK;
 }
 
+// Dead forget gates.  The LSTM update of a gate convolution is c = f * c_prev + i * g as a multiplication, a multiplication
+// and an addition, and in this predictor c_prev is the per-model constant C0_l.  Where EVERY 32-bit word of the plane C0_l is
+// 0x00000000 (+0; -0 does not count), f * c_prev is +0 for every f that is not NaN -- a hard sigmoid is in [0, 1] or NaN --
+// and c = (+0) + i * g: the forget gate's pre-activation reaches no result.  Nothing is assumed about the model: k_live_blocks
+// ORs the whole words of the plane, border included.  deadf[l] then lets the k_wino gate launches of the level take the
+// stage image without the f columns (gate_nf[l], three column tiles instead of four, EPI_LSTM3).  Zero biases (Keras' default
+// initialisation, the bench's model): every level.  A model with biases: none.  Only where the convolution has a k_wino form
+// and every weight of it -- all four gates, both sources -- is finite: with a non-finite weight f could be NaN and the
+// four-gate form is kept (a NaN that comes from an OVERFLOWED activation times a finite weight is not reproduced: DESIGN.md
+// section 5).  Both halves of a split gate convolution ("E-part ahead") take the same image (P_l then holds 3 R columns per
+// pixel); k_wino_ref, the TZ-PA1 kernels and level 0 keep all four gates.  TEZIP_DEADF=0 (read here, per prepare): never; TEZIP_DEADF_LOG=1: one line per level >= 1.
+static int measure_deadf(tz_ctx* ctx, tz_model* m) {
+    const int L = m->L;
+    const char* env = getenv("TEZIP_DEADF");
+    const bool on = !env || atoi(env) != 0;
+    const bool log = getenv("TEZIP_DEADF_LOG") && atoi(getenv("TEZIP_DEADF_LOG"));
+    unsigned long long h_live[TZ_MAX_LEVELS] = {0};
+    for (int l = 0; l < TZ_MAX_LEVELS; ++l) m->deadf[l] = false;
+    if (!on && !log) return TZ_OK;
+    {
+        unsigned long long* d_live = nullptr;
+        TZ_TRY(dmalloc(ctx, m, (void**)&d_live, sizeof(h_live)));
+        TZ_HIP(ctx, hipMemsetAsync(d_live, 0, sizeof(h_live), ctx->stream));
+        for (int l = 1; l < L; ++l) {
+            // (the plane as one block of single-channel "pixels": bit 0 = some word of it has a bit set)
+            const long long nwords = (long long)(m->Hp >> l) * (m->Wp >> l) * m->rstack[l];
+            hipLaunchKernelGGL(k_live_blocks, dim3((unsigned)std::min<long long>((nwords + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                               (const unsigned*)m->C0[l], nwords, 1, 1, d_live + l, 0xffffffffu);
+            TZ_HIP(ctx, hipGetLastError());
+        }
+        TZ_HIP(ctx, hipMemcpyAsync(h_live, d_live, sizeof(h_live), hipMemcpyDeviceToHost, ctx->stream));
+        TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    for (int l = 1; l < L; ++l) {
+        const bool zero = !(h_live[l] & 1);
+        const bool form = m->gate_t1[l].d_Wwino && m->gate_t1[l].NT == 4;
+        const bool finite = form && m->gate_t1[l].wino_all_finite;
+        m->deadf[l] = on && zero && form && finite;
+        if (m->deadf[l]) {
+            // the same convolution packed once more without the forget gate: column blocks [i | g | o] x 16, NT = 3 -- the same
+            // transformed and collapsed weights, the same stage order, the same [column block][stage] stream (only for a level
+            // that takes it: a model with biases pays the scan above and nothing else)
+            std::vector<ColSrc> cols, cols3;
+            int NT;
+            TZ_TRY(gate_cols(ctx, m, l, &cols, &NT));
+            for (size_t c = 0; c < cols.size(); ++c)
+                if ((c % 64) / 16 != 1) cols3.push_back(cols[c]);
+            TZ_TRY(pack_wino(ctx, m, m->gate_t1[l].segs, cols3, 3, &m->gate_nf[l]));
+            m->deadf[l] = m->gate_nf[l].d_Wwino != nullptr;
+        }
+        if (log)
+            fprintf(stderr, "[tezip] dead forget gate, level %d: C0 +0 everywhere: %s, forget-gate columns left out: %s%s\n", l, zero ? "yes" : "no",
+                    m->deadf[l] ? "yes" : "no",
+                    m->deadf[l] ? " (3 of 4 column tiles in every k_wino gate launch, fused or split)"
+                    : !zero     ? ""
+                    : !on       ? " (TEZIP_DEADF=0)"
+                    : !form     ? " (no k_wino form)"
+                                : " (a weight of the convolution is not finite)");
+    }
+    return TZ_OK;
+}
+
 extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
     tz_roctx_range roctx_("tz_model_prepare");
     if (!ctx) return TZ_ERR_INVALID;
@@ -968,6 +1060,7 @@ extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
     }
     TZ_TRY(measure_uniform(ctx, m));   // (synchronises the stream)
     TZ_TRY(measure_dead(ctx, m));
+    TZ_TRY(measure_deadf(ctx, m));
     m->prepared = true;
     return TZ_OK;
 }
@@ -1025,10 +1118,12 @@ static bool epart_levels(tz_ctx* ctx, tz_model* m, int n, bool* lv, double* idle
         const long long it[2] = {m->gate_t1[l].d_Wwino ? tiles * m->gate_t1[l].ncb : 0,
                                  l < L - 1 && m->a_conv[l].d_Wwino ? tiles * m->a_conv[l].ncb : 0};
         const int st[2] = {s_e - 4 * m->dead_gate[l] + s_u, s_e - 4 * m->dead_a[l]};   // the stages actually walked (measure_dead)
+        // ... and their length: a gate stage without the forget gate multiplies three column tiles instead of four (measure_deadf)
+        const double len[2] = {m->deadf[l] ? 0.75 : 1.0, 1.0};
         for (int k = 0; k < 2; ++k) {
             if (!it[k]) continue;
-            busy += (double)it[k] / ctx->num_cus * st[k];
-            span += (double)((it[k] + ctx->num_cus - 1) / ctx->num_cus) * st[k];
+            busy += (double)it[k] / ctx->num_cus * st[k] * len[k];
+            span += (double)((it[k] + ctx->num_cus - 1) / ctx->num_cus) * st[k] * len[k];
         }
     }
     if (span > 0.0) *idle = 1.0 - busy / span;
@@ -1051,9 +1146,12 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
 // side workgroups land on CUs the critical path is about to ask for depends on how every launch's last round falls, and on
 // the command processor's handling of stream priorities, which HIP does not promise).  So the first call for a batch size
 // n of a prepared model MEASURES: the same step -- a pure function of its inputs when the level-0 error maps are formed
-// here (skip_err0 off) -- runs fused and split, one untimed and two timed samples of three back-to-back steps each, HIP events on the compute stream,
+// here (skip_err0 off) -- runs fused and split, one untimed and four timed samples of three back-to-back steps each, HIP events on the compute stream,
 // and the split is kept for that n where it is at least 2 % faster.  Both forms give the same bits (tests/test_gpu_epart.py),
-// so the outcome of the measurement never shows in the results; it costs eighteen extra steps once per (prepare, n).
+// so the outcome of the measurement never shows in the results; it costs thirty extra steps once per (prepare, n).  (Four timed
+// samples since the forget gate can be left out, measure_deadf: two were enough while the split led by 7-8 % on the small frames of
+// the tests; with both forms a seventh faster it leads by 5-6 %, and one disturbed pair of samples in a fresh process put a batch
+// size on the other side of the 2 % line -- the best of four has to be disturbed four times.)
 // TEZIP_EPART=0 / 1 still forbid / force it.  Not tried at all where the idle share is under 6 % (every such case measured
 // slower) or no level can split.
 static int epart_measure(tz_ctx* ctx, int n, const int* d_idx, int stride, const uint8_t* d_frames_u8, int H, int W,
@@ -1072,7 +1170,7 @@ static int epart_measure(tz_ctx* ctx, int n, const int* d_idx, int stride, const
     ctx->prof_on = false;                        // (the measurement's launches are not the caller's)
     float best[2] = {1e30f, 1e30f};
     int rc = TZ_OK;
-    for (int rep = 0; rep < 3 && rc == TZ_OK; ++rep)
+    for (int rep = 0; rep < 1 + kEpartSamples && rc == TZ_OK; ++rep)
         for (int mode = 0; mode < 2 && rc == TZ_OK; ++mode) {
             bool dummy;
             hipError_t e = hipEventRecord(ctx->ev_cal[0], ctx->stream);
@@ -1207,6 +1305,9 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         double idle;
         epart_levels(ctx, m, n, epart, &idle);
     }
+    // a level without its forget gate (measure_deadf): the stage image its k_wino launches take, and the columns per pixel of P_l
+    auto wino3 = [&](int l) -> const float* { return m->deadf[l] ? m->gate_nf[l].d_Wwino : nullptr; };
+    auto pcols = [&](int l) { return m->deadf[l] ? 3 * m->rstack[l] : m->gate_t1[l].ncols; };
     auto epart_launch = [&](int l) -> int {   // the launch over E_l, on stream2, behind the A convolution that wrote E_l
         if (!ctx->ev_epart_src[l]) {
             TZ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_epart_src[l], hipEventDisableTiming));
@@ -1221,14 +1322,14 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         ge.aux = ge.auxf = nullptr;
         ge.aux_u = nullptr;
         ge.aux_ring = ge.aux_tring = -1;
-        ge.out0_nstride = npx(l) * ge.ncols;
+        ge.out0_nstride = npx(l) * pcols(l);
         ge.out0 = m->P[l] + slot0 * ge.out0_nstride;
         ge.ipw = 1;   // short workgroups: a CU a side workgroup holds is one the critical path may be waiting for
         TZ_HIP(ctx, hipEventRecord(ctx->ev_epart_src[l], ctx->stream));
         TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_epart_src[l], 0));
         hipStream_t main_stream = ctx->stream;
         ctx->stream = ctx->stream2;       // (the launchers and their profiling scopes take the context's stream)
-        int rc = launch_conv(ctx, 4, EPI_RAW, ge, n, m->dead_gate[l]);
+        int rc = launch_conv(ctx, 4, EPI_RAW, ge, n, m->dead_gate[l], wino3(l));
         ctx->stream = main_stream;
         TZ_TRY(rc);
         TZ_HIP(ctx, hipEventRecord(ctx->ev_epart_done[l], ctx->stream2));
@@ -1306,7 +1407,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         if (epart[l]) {   // the chains go on from P_l over the upsampled source
             a.wino_stride = (a.src[0].C + a.src[1].C) >> 2;
             a.wino_first = a.src[0].C >> 2;
-            a.init_nstride = npx(l) * a.ncols;
+            a.init_nstride = npx(l) * pcols(l);
             a.init = m->P[l] + slot0 * a.init_nstride;
             a.initf = nullptr;
             a.init_u = nullptr;   // (start values per item; the cell state may still be uniform)
@@ -1314,10 +1415,10 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
             TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_epart_done[l], 0));
             tz_prof_scope ps(ctx, TZP_CONV);
             ps.sub = TZP_WINO;
-            TZ_TRY(launch_wino(ctx, 4, EPI_LSTM, true, a, n, true));
+            TZ_TRY(launch_wino(ctx, 4, EPI_LSTM, true, a, n, true, 0, wino3(l)));
             continue;
         }
-        TZ_TRY(launch_conv(ctx, pc.NT, pc.NT == 4 ? EPI_LSTM : EPI_LSTM_PACKED, a, n, m->dead_gate[l]));
+        TZ_TRY(launch_conv(ctx, pc.NT, pc.NT == 4 ? EPI_LSTM : EPI_LSTM_PACKED, a, n, m->dead_gate[l], wino3(l)));
     }
     {  // Ahat_0 at t1 = the prediction (prednet.py:268-271, 293-295)
         const PackedConv& pc = m->ahat0_t1;

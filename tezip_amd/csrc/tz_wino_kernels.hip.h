@@ -119,6 +119,13 @@ __device__ __forceinline__ float fadd(float a, float b) {
     asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// (+0) + x as an instruction of its own: nothing folds it away (it is not the identity: (+0) + (-0) = +0), and x arrives
+// rounded, so nothing fuses the multiplication in front of it into it either
+__device__ __forceinline__ float fadd_zero(float x) {
+    float r;
+    asm("v_add_f32 %0, 0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
 // every wave issues 3 LDS-DMA instructions per stage: "my pieces of all but the N youngest stages have landed"
 template <int N>
 __device__ __forceinline__ void wait_vm_stages() {
@@ -173,7 +180,12 @@ __device__ unsigned long long tzw_stamps[8][4096][16];   // [0..6] real time at 
 #else
 #define TZW_STAMP(K)
 #endif
-// EPI: EPI_LSTM (NT = 4: columns [i | f | g | o] x 16 channels), EPI_POOL_ERR (NT = 3 or 4), EPI_RAW (NT = 4).
+// EPI: EPI_LSTM (NT = 4: columns [i | f | g | o] x 16 channels), EPI_POOL_ERR (NT = 3 or 4), EPI_RAW (NT = 4),
+// EPI_LSTM3 (NT = 3: columns [i | g | o] x 16 of a stage image packed without the forget gate -- a level whose start cell
+// state is +0 at every pixel, tz_prednet.hip measure_deadf: c = f * (+0) + i * g = (+0) + i * g for every non-NaN f, so the f
+// columns are neither multiplied nor transformed; start values and biases stay 64 columns per block, column tile t of
+// the kernel = gate column 16 (t + (t > 0)) of them), EPI_RAW3 (NT = 3: the first half of a split over that image: start values
+// as EPI_LSTM3, rows of 3 Cout columns out; the second half <3, EPI_LSTM3, true, NOSAME> starts from those rows, a.ncols = 3 Cout).
 // src[0]: the same-resolution source (multiple of 16 channels); src[1] (UPS): the half-resolution source.
 // A gate convolution can also run as TWO launches (round 5, tz_prednet.hip "E-part ahead"; launches that cannot fill the
 // chip): <4, EPI_RAW, false> over the same-resolution source alone, which leaves every output's chain as it stands behind
@@ -183,6 +195,15 @@ __device__ unsigned long long tzw_stamps[8][4096][16];   // [0..6] real time at 
 template <int NT, int EPI, bool UPS, bool NOSAME = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_wino(const ConvArgs a) {
     static_assert(!NOSAME || UPS, "a launch without the same-resolution phase walks the upsampled source");
+    static_assert((EPI != EPI_LSTM3 && EPI != EPI_RAW3) || NT == 3, "three gates");
+    static_assert(EPI != EPI_LSTM || NT == 4, "four gates");
+    static_assert(EPI != EPI_RAW3 || !UPS, "the first half of a split walks the same-resolution source");
+    // columns of a block in the start values / biases, and where column tile t of this kernel sits among them: a three-gate
+    // launch that starts from G0 / the bias reads the four-gate rows; the second half of a split starts from what the first
+    // half wrote, 48 columns a block
+    constexpr bool G3 = (EPI == EPI_LSTM3 && !NOSAME) || EPI == EPI_RAW3;
+    constexpr int CBW = G3 ? 64 : 16 * NT;
+#define TZW_COLT(t) (G3 ? 16 * ((t) + ((t) > 0)) : 16 * (t))
     using namespace tzw;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -478,20 +499,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     // every workgroup of the launch then reads the same block
                     const bool rep = tile_uniform(a.init, a.init_tring, ty0, tx0, a.H, a.W);
                     const int yr = rep ? y - ty0 + ref_tile_origin(a.H) : y, xr = rep ? x0 - tx0 + ref_tile_origin(a.W) : x0;
-                    const float* ip = initn + (unsigned)((yr * a.W + xr) * a.ncols + cb * (16 * NT) + r);
+                    const float* ip = initn + (unsigned)((yr * a.W + xr) * a.ncols + cb * CBW + r);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float* ie = ip + (unsigned)(2 * e * a.ncols);
 #pragma unroll
                         for (int t = 0; t < NT; ++t) {
-                            in0[t][e] = ie[16 * t];
-                            in1[t][e] = ie[a.ncols + 16 * t];
+                            in0[t][e] = ie[TZW_COLT(t)];
+                            in1[t][e] = ie[a.ncols + TZW_COLT(t)];
                         }
                     }
                 } else {
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
-                        const int col = cb * (16 * NT) + 16 * t + r;
+                        const int col = cb * CBW + TZW_COLT(t) + r;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int x = x0 + 2 * e;
@@ -506,7 +527,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const float* bu = uni_init && !(TZW_ABL & 64) ? a.init_u : a.bias;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
-                    const float b = bu[cb * (16 * NT) + 16 * t + r];
+                    const float b = bu[cb * CBW + TZW_COLT(t) + r];
                     in0[t] = in1[t] = (f32x4){b, b, b, b};
                 }
             }
@@ -521,8 +542,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
             // into their accumulation registers HERE, two wait states ahead of any MFMA that takes them as C (the asm MFMAs get
             // no hazard handling: a v_accvgpr_write sunk to right in front of the first stage would be read too early)
-            static_assert(!NOSAME || NT == 4, "the split launch exists for gate convolutions");
-            asm volatile("" : "+a"(Y[0][0]), "+a"(Y[0][1]), "+a"(Y[0][2]), "+a"(Y[0][3]), "+a"(Y[1][0]), "+a"(Y[1][1]), "+a"(Y[1][2]), "+a"(Y[1][3]));
+            static_assert(!NOSAME || EPI == EPI_LSTM || EPI == EPI_LSTM3, "the split launch exists for gate convolutions");
+            if (NT == 4) asm volatile("" : "+a"(Y[0][0]), "+a"(Y[0][1]), "+a"(Y[0][2]), "+a"(Y[0][3]), "+a"(Y[1][0]), "+a"(Y[1][1]), "+a"(Y[1][2]), "+a"(Y[1][3]));
+            else asm volatile("" : "+a"(Y[0][0]), "+a"(Y[0][1]), "+a"(Y[0][2]), "+a"(Y[1][0]), "+a"(Y[1][1]), "+a"(Y[1][2]));
             asm volatile("s_nop 1" ::: "memory");
         } else
 #pragma unroll
@@ -629,11 +651,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef TZW_ISSUE_P
 #undef TZW_ISSUE_HERE
 #undef TZW_WAIT
+#undef TZW_COLT
 
     // ---- epilogues.  This wave's outputs: pixel row a = ph of its 16 tiles, columns b = 0, 1: Y[b][column tile][e],
     // accumulator row 4 g + e = tile (tyl = g, txl = e)
     const int oy = ty0 + 8 * (mt >> 1) + 2 * g + ph + per_item;
-    if (EPI == EPI_RAW) {
+    if (EPI == EPI_RAW || EPI == EPI_RAW3) {
+        // (EPI_RAW3: the rows written are 3 Cout wide -- [i | g | o] x 16 per block --, the rows of the start values 4 Cout = a.ncols)
+        const int ocols = EPI == EPI_RAW3 ? 3 * a.Cout : a.ncols;
         float* on = a.out0 + (long long)n * a.out0_nstride;
 #pragma unroll
         for (int b = 0; b < 2; ++b)
@@ -642,12 +667,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const int x = tx0 + 8 * (mt & 1) + 2 * e + b;
                 if (oy < a.H && x < a.W) {
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) on[((long long)oy * a.W + x) * a.ncols + cb * (16 * NT) + 16 * t + r] = Y[b][t][e];
+                    for (int t = 0; t < NT; ++t) on[((long long)oy * a.W + x) * ocols + cb * (16 * NT) + 16 * t + r] = Y[b][t][e];
                 }
             }
-    } else if (EPI == EPI_LSTM) {
+    } else if (EPI == EPI_LSTM || EPI == EPI_LSTM3) {
         // columns of this block: [i | f | g | o] x 16 channels of channel group cb (prednet.py:255-259):
         // c = f * c_prev + i * g ; r = o * tanh(c)
+        // EPI_LSTM3: [i | g | o], c_prev = +0 everywhere: f * (+0) = +0 for every non-NaN f, so c = (+0) + i * g -- a real
+        // float32 addition (it turns i * g = -0 into +0, as the four-gate form does), no cell state is loaded
+        constexpr bool F3 = EPI == EPI_LSTM3;
+        constexpr int TG = F3 ? 1 : 2 % NT, TO = F3 ? 2 : 3 % NT;   // column tiles of gates g and o
         const int ch = cb * 16 + r, R = a.Cout;
         float* o0 = a.out0 + (long long)n * a.out0_nstride;
         float* o1 = a.out1 ? a.out1 + (long long)n * a.out1_nstride : nullptr;
@@ -661,7 +690,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             char* p0 = (char*)o0;
             char* p1 = (char*)o1;
             float cpv[2][4];
-            if (tile_uniform(a.aux_u, a.aux_ring, ty0, tx0, a.H, a.W) && !(TZW_ABL & 256)) {
+            if (F3) {
+                // (no cell state to load)
+            } else if (tile_uniform(a.aux_u, a.aux_ring, ty0, tx0, a.H, a.W) && !(TZW_ABL & 256)) {
                 // (uniform) away from the border of the plane the cell state is one value per channel: one load
                 const float cu = a.aux_u[ch];
 #pragma unroll
@@ -687,12 +718,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float gi = tz_hard_sigmoid(Y[b][0][e]);
-                    const float gf = tz_hard_sigmoid(Y[b][1 % NT][e]);
-                    const float gg = tz_tanh(Y[b][2 % NT][e]);
-                    const float go = tz_hard_sigmoid(Y[b][3 % NT][e]);
-                    const float t1 = gf * cpv[b][e];
+                    const float gg = tz_tanh(Y[b][TG][e]);
+                    const float go = tz_hard_sigmoid(Y[b][TO][e]);
                     const float t2 = gi * gg;
-                    const float c = t1 + t2;
+                    float c;
+                    if (F3) {
+                        c = fadd_zero(t2);
+                    } else {
+                        const float gf = tz_hard_sigmoid(Y[b][1 % NT][e]);
+                        const float t1 = gf * cpv[b][e];
+                        c = t1 + t2;
+                    }
                     const float rr = go * tz_tanh(c);
                     *(float*)(p0 + (size_t)(2 * e + b) * R * 4 + voff) = rr;
                     if (o1) *(float*)(p1 + (size_t)(2 * e + b) * R * 4 + voff) = c;
@@ -711,7 +747,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 // (Asking for these ahead of the output transform through asm loads -- to hide their round trip -- is NOT
                 // safe: the compiler is free to reuse an asm load's destination register before the data lands, and did:
                 // the late write then hit an address register, a memory fault in the bench.  Plain loads, at their use.)
-                cp[b][e] = a.aux && !(TZW_ABL & 256) ? a.aux[pix[b][e] * R + ch] : 0.0f;
+                cp[b][e] = !F3 && a.aux && !(TZW_ABL & 256) ? a.aux[pix[b][e] * R + ch] : 0.0f;
             }
 #ifdef TZW_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -729,12 +765,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     continue;
                 }
                 const float gi = tz_hard_sigmoid(Y[b][0][e]);
-                const float gf = tz_hard_sigmoid(Y[b][1 % NT][e]);
-                const float gg = tz_tanh(Y[b][2 % NT][e]);
-                const float go = tz_hard_sigmoid(Y[b][3 % NT][e]);
-                const float t1 = gf * cp[b][e];
+                const float gg = tz_tanh(Y[b][TG][e]);
+                const float go = tz_hard_sigmoid(Y[b][TO][e]);
                 const float t2 = gi * gg;
-                const float c = t1 + t2;
+                float c;
+                if (F3) {
+                    c = fadd_zero(t2);
+                } else {
+                    const float gf = tz_hard_sigmoid(Y[b][1 % NT][e]);
+                    const float t1 = gf * cp[b][e];
+                    c = t1 + t2;
+                }
                 const float rr = go * tz_tanh(c);
                 if (ok[b][e]) {
                     o0[pix[b][e] * R + ch] = rr;
