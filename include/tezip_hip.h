@@ -247,6 +247,33 @@ int tz_get_delta_stride(tz_ctx* ctx);
  * tolerances (one small launch, k_q_frame_bound, fills the per-chain array that rel / absrel jobs fill from the data). */
 int tz_set_frame_bounds(tz_ctx* ctx, const double* bounds, int n);
 int tz_get_frame_bounds(tz_ctx* ctx);
+/* Opt-in: the quantiser of a lossy job (no reference counterpart: compress.py:23-70 is the only one the reference has, a greedy
+ * walk that merges runs of neighbouring deltas which fit into one 2E window; `tezip.py -c --quant lattice`, DESIGN.md section 9,
+ * slow statement in tezip_amd/lattice.py).  q: 0 (the default: every entry point launches exactly what it launches without this
+ * call) = that greedy walk; 1 = the lattice quantiser, definition TZ-QL1: for a delta d in [-255, 255] and the tolerance e, the
+ * float64 the greedy walk forms (abs |b0|; rel (max - min of the slab) * b0; absrel the smaller of the two; pwrel orig * b0 per
+ * element; under tz_set_frame_bounds bounds[f])
+ *     E = min(255, floor(e))      s = 2E + 1      q = clamp(sign(d) * ((|d| + E) div s) * s, -255, 255)
+ * so that |q - d| <= E <= e (the clamp projects onto an interval that contains d), |q| <= 255 (the spatial delta stays in
+ * [-510, 510]: TZ_NBINS and TZ_MAX_TABLE hold), e < 1 is the identity and E = 255 maps everything to 0.  A pure function of one
+ * delta and one tolerance: no walk, no stitch, no serial fallback.  Anything else is TZ_ERR_INVALID.  tz_get_quantiser returns
+ * the value in force.  A change drops a resident payload.  Under 1:
+ *  - tz_encode (payload == NULL, the deferred hand-over, the shuffle bit and delta_out included), tz_encode_delta,
+ *    tz_bound_probe and tz_size_probe quantise by TZ-QL1 and honour tz_set_frame_bounds, tz_set_payload_channels and
+ *    tz_set_delta_stride as under 0.  Frame 0, warm-up frames and key frames are not quantised, as under 0; an unknown mode, a
+ *    NaN and a negative rel / pwrel tolerance are refused where they are refused under 0.
+ *  - a job whose worst-case tolerance is below 1 (abs |b0|; rel / pwrel 255 b0; absrel the smaller of |b0| and 255 b1; every
+ *    frame bound) is the lossless job, byte for byte, and takes the lossless kernels.
+ *  - where the lossless one-pass front applies (unpadded frames of whole 16-byte groups, no delta_out) tz_encode runs ONE pass
+ *    over predictions and originals in every layout (k_lattice_sd: delta, TZ-QL1, the layout's spatial delta, offset,
+ *    histogram); elsewhere the delta stack is quantised in place (k_lattice) between the kernels of the unfused chain.  The
+ *    payload is the same.
+ *  - tz_encode_begin and tz_encode_finish return TZ_ERR_UNSUPPORTED (sharded jobs are out of scope).
+ *  - the payload carries the quantised deltas themselves, not lattice indices: the decoder never sees a bound, so tz_decode,
+ *    tz_decode_range, tz_encode_quality, tz_encode_ssim and tz_encode_digests take the payload as any other, and with the
+ *    default formats so does the reference's decoder. */
+int tz_set_quantiser(tz_ctx* ctx, int q);
+int tz_get_quantiser(tz_ctx* ctx);
 /* Streaming delivery: tz_encode with payload == NULL keeps the payload in the context; it is then
  * fetched in pieces of `count` int16 elements starting at `offset` (compress.py:375-400 appends and
  * compresses one monolithic array). */
@@ -472,6 +499,16 @@ int tz_error_bound(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_
  * of 0 and a skipped frame leave it untouched.  Independent of the context's own frame bounds. */
 int tz_error_bound_frames(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask,
                           int nframes, int H, int W, const double* bounds);
+/* tz_lattice_bound: the lattice quantiser TZ-QL1 (tz_set_quantiser) per frame and channel, in place, with the argument rules of
+ * tz_error_bound: orig and diff host or device stacks, skip_mask[nframes] (host, may be NULL), the same refusals of an unknown
+ * mode, of a NaN and of a negative rel / pwrel / absrel tolerance; b0 == 0 (and absrel with b1 == 0) leaves diff as it is.
+ * Defined for every int16 delta (the error bound holds for those in [-255, 255]).  tz_lattice_bound_frames: the twin of
+ * tz_error_bound_frames, abs with bounds[f] for frame f (finite and >= 0, else TZ_ERR_INVALID and diff is untouched).  Both are
+ * independent of the context's own quantiser and frame bounds. */
+int tz_lattice_bound(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask,
+                     int nframes, int H, int W, int mode, double b0, double b1);
+int tz_lattice_bound_frames(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask,
+                            int nframes, int H, int W, const double* bounds);
 /* tz_spatial_delta: compress.py:73-77 (+ the 1600 offset of :348 when apply_offset).
  * has_carry: treat `carry` as the element preceding in[0] (shard boundary). hist (may be
  * NULL): TZ_NBINS uint64 counts of the output symbols are ADDED (compress.py:354). */

@@ -27,6 +27,7 @@ TZ_NBINS = 2111
 HUFFR_NTOK = 8          # TZ_HUFFR_NTOK: repeat tokens behind the literals of a tz_huffr_* code
 TZ_MAX_TABLE = 1021
 MODES = {"abs": 0, "rel": 1, "absrel": 2, "pwrel": 3}
+QUANTISERS = ("greedy", "lattice")   # tz_set_quantiser: 0 = compress.py:23-70, 1 = TZ-QL1 (tezip_amd/lattice.py)
 
 _SIGS = {
     "tz_version": (C.c_int, []),
@@ -81,6 +82,11 @@ _SIGS = {
     "tz_set_frame_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "tz_get_frame_bounds": (C.c_int, [C.c_void_p]),
     "tz_error_bound_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_set_quantiser": (C.c_int, [C.c_void_p, C.c_int]),
+    "tz_get_quantiser": (C.c_int, [C.c_void_p]),
+    "tz_lattice_bound": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_double, C.c_double]),
+    "tz_lattice_bound_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tz_spatial_delta_stride": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "tz_spatial_undelta_stride": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "tz_undelta_carry_stride": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -644,6 +650,15 @@ class Context:
     def get_frame_bounds(self):
         return int(self.lib.tz_get_frame_bounds(self.h))
 
+    def set_quantiser(self, quant):
+        """tz_set_quantiser: "greedy" / 0 (the default) = the reference's quantiser, "lattice" / 1 = the lattice quantiser
+        TZ-QL1 (tezip_amd/lattice.py) in encode / encode_delta / bound_probe / size_probe."""
+        q = QUANTISERS.index(quant) if isinstance(quant, str) else int(quant)
+        self._ck(self.lib.tz_set_quantiser(self.h, q))
+
+    def get_quantiser(self):
+        return int(self.lib.tz_get_quantiser(self.h))
+
     def set_payload_deferred(self, on=True):
         """tz_set_payload_deferred: encode(payload=<pinned host buffer>) returns with the device -> host transfer of
         the payload still running; payload_wait() completes it (it overlaps the next sequence's rollout)."""
@@ -1146,6 +1161,24 @@ class Context:
             raise ValueError("%d bounds for %d frames" % (b.size, n))
         sk = None if skip_mask is None else np.ascontiguousarray(skip_mask, np.uint8)
         self._ck(self.lib.tz_error_bound_frames(self.h, _ptr(orig), _ptr(diff), _ptr(sk), n, h, w, b.ctypes.data))
+        return diff
+
+    def lattice_bound(self, orig, diff, mode, bound, skip_mask=None):
+        """tz_lattice_bound: the lattice quantiser TZ-QL1 per frame and channel, in place (error_bound's arguments)."""
+        n, h, w = orig.shape[:3]
+        b0, b1 = _bounds(bound)
+        sk = None if skip_mask is None else np.ascontiguousarray(skip_mask, np.uint8)
+        self._ck(self.lib.tz_lattice_bound(self.h, _ptr(orig), _ptr(diff), _ptr(sk), n, h, w, MODES[mode], b0, b1))
+        return diff
+
+    def lattice_bound_frames(self, orig, diff, bounds, skip_mask=None):
+        """tz_lattice_bound_frames: lattice_bound in abs mode with bounds[f] for frame f."""
+        n, h, w = orig.shape[:3]
+        b = np.ascontiguousarray(bounds, np.float64)
+        if b.size != n:
+            raise ValueError("%d bounds for %d frames" % (b.size, n))
+        sk = None if skip_mask is None else np.ascontiguousarray(skip_mask, np.uint8)
+        self._ck(self.lib.tz_lattice_bound_frames(self.h, _ptr(orig), _ptr(diff), _ptr(sk), n, h, w, b.ctypes.data))
         return diff
 
     def spatial_delta(self, x, offset, carry=None, hist=None, out=None):

@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, quality, ratetarget, sdelta, sidecar, target, weights, zstd
+from . import _lib, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, quality, ratetarget, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -258,6 +258,18 @@ def check_gray(gray, sharded=False):
     """The refusal of --gray that a direct caller of run() can meet (tezip.py knows the others): None, or the message."""
     if gray and sharded:
         return "--gray is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+    return None
+
+
+QUANT_NOT_SHARDED = "--quant lattice is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+
+
+def check_quant(quant, sharded=False):
+    """The refusals of --quant that a direct caller of run() can meet (tezip.py knows the others): None, or the message."""
+    if quant not in lattice.QUANTS:
+        return "--quant takes one of %s, got %r" % (", ".join(lattice.QUANTS), quant)
+    if quant == "lattice" and sharded:
+        return QUANT_NOT_SHARDED
     return None
 
 
@@ -524,7 +536,7 @@ def check_ratio(ratio, mode, bound, target_psnr, coder, shuffle, sharded):
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
-        SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None):
+        SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None, QUANT="greedy"):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -579,6 +591,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     list of numbers or an object with a "frame_bounds" list, so that a per-frame search's bound_search.json replays) or a
     sequence: one abs bound per image, finite and >= 0; entries at frame 0, warm-up and key frames are taken as 0.  The
     job runs under tz_set_frame_bounds.  Single-GPU jobs only.
+    QUANT (--quant; NOT in the reference): "greedy" (the default: every file, line and launch is what it is without it) is
+    the reference's quantiser (compress.py:23-70); "lattice" quantises every delta on its own by definition TZ-QL1
+    (tezip_amd/lattice.py) under the same tolerance: one line says so, tezip_amd.json and bound_search.json record it, and the
+    files are ordinary ones -- the payload holds the quantised deltas themselves, `-u` needs no flag and does not read the
+    record.  Smaller than greedy on data that is not smooth, LARGER on sparse frames at loose bounds (README).  The probes of
+    TARGET_PSNR, PER_FRAME and TARGET_RATIO quantise the same way.  Works with every flag above.  Single-GPU jobs only.
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -599,6 +617,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
         sys.exit(2)
     if SSIM and not REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         print("ERROR:", SSIM_NEEDS_REPORT)
+        sys.exit(2)
+    problem = check_quant(QUANT, tzdist.active() is not None)
+    if problem:   # likewise
+        print("ERROR:", problem)
         sys.exit(2)
     if TARGET_PSNR is not None:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         problem = (target.check_target(TARGET_PSNR) or (TARGET_NEEDS_ABS if MODE != "abs" or BOUND_VALUE else None)
@@ -657,6 +679,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 channels = decide_gray(ctx, nt, src.files)
                 stages.mark("gray check (device)")
             strided = SDELTA == "channel" and decide_sdelta(ctx, channels)
+            if QUANT == "lattice":   # the probes of the searches below and the job itself quantise by TZ-QL1
+                ctx.set_quantiser("lattice")
+                print(lattice.STDOUT_LINE)
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
@@ -704,6 +729,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 search_doc = ratetarget.make(TARGET_RATIO, raw, limit, fixed, trace, k)
                 stages.mark("key_frame.dat + bound search (device)")
                 if k is None:
+                    if QUANT == "lattice":
+                        search_doc["quant"] = "lattice"
                     print(ratetarget.unreachable_line(search_doc))
                     ratetarget.write(OUTPUT_DIR, search_doc)
                     sys.exit(ratetarget.EXIT_UNREACHABLE)
@@ -745,8 +772,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             else:
                 _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
                                 coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided)
-            doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),   # the contract the predictions were made under
-                                payload_channels=channels, sdelta="channel" if strided else "flat")
+            if QUANT == "lattice":
+                doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
+                                    payload_channels=channels, sdelta="channel" if strided else "flat", quant="lattice")
+            else:
+                doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),   # the contract the predictions were made under
+                                    payload_channels=channels, sdelta="channel" if strided else "flat")
             if VERBOSE:
                 print("arithmetic contract:", doc["arithmetic_contract"])
             stages.mark("key_frame.dat + entropy.dat")
@@ -759,6 +790,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 quality.write(OUTPUT_DIR, report)
                 for line in quality.stdout_lines(report):
                     print(line)
+            if QUANT == "lattice" and (TARGET_PSNR is not None or TARGET_RATIO is not None):
+                search_doc["quant"] = "lattice"
             if PER_FRAME:
                 frametarget.write(OUTPUT_DIR, search_doc)
             elif TARGET_PSNR is not None:

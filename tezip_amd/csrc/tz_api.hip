@@ -1556,14 +1556,35 @@ static int no_frame_bounds(tz_ctx* ctx, const char* who) {
 // every frame's bound leaves its deltas as they are (0, or an identity by tz_quant_is_identity): the lossless job
 static bool frame_bounds_identity(const tz_ctx* ctx) {
     for (double b : ctx->frame_bounds)
-        if (b != 0.0 && !tz_quant_is_identity(TZ_MODE_ABS, b, 0.0)) return false;
+        if (b != 0.0 && !(ctx->quantiser == 1 ? tz_lattice_is_identity(TZ_MODE_ABS, b, 0.0) : tz_quant_is_identity(TZ_MODE_ABS, b, 0.0))) return false;
     return true;
+}
+
+// ---- the quantiser of a lossy job (include/tezip_hip.h: tz_set_quantiser)
+extern "C" int tz_set_quantiser(tz_ctx* ctx, int q) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (q != 0 && q != 1) return tz_fail(ctx, TZ_ERR_INVALID, "quantiser must be 0 (greedy) or 1 (lattice, TZ-QL1), not %d", q);
+    if (q != ctx->quantiser) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made by the other quantiser
+    ctx->quantiser = q;
+    return TZ_OK;
+}
+
+extern "C" int tz_get_quantiser(tz_ctx* ctx) { return ctx ? ctx->quantiser : TZ_ERR_INVALID; }
+
+// The sharded entry points run the reference's quantiser.
+static int greedy_only(tz_ctx* ctx, const char* who) {
+    if (ctx->quantiser != 0)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve the lattice quantiser (tz_set_quantiser(1)): sharded jobs are out of scope", who);
+    return TZ_OK;
 }
 
 // compress.py:315-319 on the delta stack of the context's rollout, under the frame bounds when some are set (encode_check has
 // passed)
 static int quantise_rollout(tz_ctx* ctx, int16_t* d_q, int mode, double b0, double b1) {
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
+    if (ctx->quantiser == 1)   // TZ-QL1 (tz_set_quantiser): one pass over the stack in place
+        return tzk_lattice(ctx, ctx->d_frames, d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1,
+                           ctx->frame_bounds.empty() ? nullptr : ctx->frame_bounds.data());
     if (ctx->frame_bounds.empty()) return tzk_error_bound(ctx, ctx->d_frames, d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1);
     return tzk_quant_frames(ctx, ctx->d_frames, d_q, nullptr, ctx->quant_skip.data(), nt, H, W, ctx->frame_bounds.data(), nullptr);
 }
@@ -1583,7 +1604,22 @@ static int encode_front(tz_ctx* ctx, tz_layout layout, int mode, double b0, doub
     TZ_TRY(tz_pool_alloc(ctx, nt, &d_mask));
     TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
     if (entropy) TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, TZ_NBINS * sizeof(unsigned long long), ctx->stream));
-    if (flat && !d_delta_tap) {   // nobody asked for the delta stack: one of the two fused passes, where its kernel applies
+    if (ctx->quantiser == 1 && d_sym && !d_delta_tap) {
+        // TZ-QL1 (tz_set_quantiser): a job whose worst-case tolerance is below 1 is the lossless job and takes its kernels (the
+        // flat one-pass front below, or the unfused chain, whose quantiser step then launches nothing); every other job has
+        // one fused pass in EVERY layout -- the quantised value is a function of one delta and one tolerance.
+        const bool per_frame = !ctx->frame_bounds.empty();
+        const bool lossless = per_frame ? frame_bounds_identity(ctx) : tz_lattice_is_identity(mode, b0, b1);
+        bool fused = false;
+        if (!lossless)
+            TZ_TRY(tzk_lattice_sd_fused(ctx, layout, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, ctx->quant_skip.data(), nt, H, W,
+                                        ctx->Hp, ctx->Wp, mode, b0, b1, per_frame ? ctx->frame_bounds.data() : nullptr, entropy ? 1 : 0,
+                                        d_sym, entropy ? d_hist : nullptr, d_edge, &fused));
+        else if (flat)
+            TZ_TRY(tzk_delta_sd_fused(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp,
+                                      entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge, &fused));
+        if (fused) return TZ_OK;
+    } else if (flat && !d_delta_tap) {   // nobody asked for the delta stack: one of the two fused passes, where its kernel applies
         // error_bound returns its input untouched in these cases (compress.py:24,35), and COMPUTES its input back wherever
         // the worst-case tolerance of the job cannot merge two different deltas (E <= 0.499: tz_quant_is_identity, with the
         // proof).  A caller that taps the delta stack still gets it through the general quantiser (the parity tests compare
@@ -1785,6 +1821,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
     if (!ctx || !edge || (entropy && !hist)) return TZ_ERR_INVALID;
     TZ_TRY(flat_only(ctx, "tz_encode_begin"));
     TZ_TRY(no_frame_bounds(ctx, "tz_encode_begin"));
+    TZ_TRY(greedy_only(ctx, "tz_encode_begin"));
     TZ_TRY(encode_check(ctx, "tz_encode_begin", mode));
     ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload now receives a shard's symbols
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
@@ -1813,6 +1850,7 @@ extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const
     if (!ctx) return TZ_ERR_INVALID;
     TZ_TRY(flat_only(ctx, "tz_encode_finish"));
     TZ_TRY(no_frame_bounds(ctx, "tz_encode_finish"));
+    TZ_TRY(greedy_only(ctx, "tz_encode_finish"));
     if (ctx->enc_kind != tz_ctx::ENC_SYMBOLS) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish needs a tz_encode_begin first");
     if (ctx->enc_entropy != (table_len >= 0) || (table_len > 0 && !table) || table_len > TZ_MAX_TABLE)
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode_finish: table does not match the entropy flag of tz_encode_begin");
@@ -2265,6 +2303,41 @@ extern "C" int tz_error_bound_frames(tz_ctx* ctx, const uint8_t* orig, int16_t* 
     }
     TZ_TRY(tzk_quant_frames(ctx, dor, ddiff, nullptr, sk.data(), nframes, H, W, bounds, nullptr));
     return call.finish();
+}
+
+// The lattice quantiser TZ-QL1 on any stack, in place: tz_error_bound's arguments and refusals (bounds NULL), or
+// tz_error_bound_frames' (one abs tolerance per frame).  Independent of the context's quantiser and frame bounds.
+static int lattice_seam(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask, int nframes, int H, int W, int mode,
+                        double b0, double b1, const double* bounds) {
+    size_t N = (size_t)nframes * H * W * 3;
+    std::vector<uint8_t> sk(nframes, 0);
+    if (skip_mask) memcpy(sk.data(), skip_mask, nframes);
+    tz_call call(ctx);
+    const uint8_t* dor;
+    int16_t* ddiff;
+    TZ_TRY(call.in(orig, N, &dor));
+    TZ_TRY(call.out(diff, N * 2, &ddiff));
+    if (call.outs.back().host) {
+        hipError_t e = hipMemcpyAsync(ddiff, diff, N * 2, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "diff upload: %s", hipGetErrorString(e));
+    }
+    TZ_TRY(tzk_lattice(ctx, dor, ddiff, sk.data(), nframes, H, W, mode, b0, b1, bounds));
+    return call.finish();
+}
+
+extern "C" int tz_lattice_bound(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask, int nframes, int H,
+                                int W, int mode, double b0, double b1) {
+    if (!ctx || !orig || !diff || nframes < 0 || H < 1 || W < 1) return TZ_ERR_INVALID;
+    return lattice_seam(ctx, orig, diff, skip_mask, nframes, H, W, mode, b0, b1, nullptr);
+}
+
+extern "C" int tz_lattice_bound_frames(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* skip_mask, int nframes, int H,
+                                       int W, const double* bounds) {
+    if (!ctx || !orig || !diff || nframes < 0 || H < 1 || W < 1 || (nframes > 0 && !bounds)) return TZ_ERR_INVALID;
+    for (int f = 0; f < nframes; ++f)
+        if (!std::isfinite(bounds[f]) || bounds[f] < 0.0)
+            return tz_fail(ctx, TZ_ERR_INVALID, "tz_lattice_bound_frames: bound %g of frame %d is not a finite number >= 0", bounds[f], f);
+    return lattice_seam(ctx, orig, diff, skip_mask, nframes, H, W, TZ_MODE_ABS, 0.0, 0.0, bounds);
 }
 
 // The seams.  Each operation has one body, which takes the layout (tz_internal.h); the exported names of the gray payload

@@ -1910,6 +1910,320 @@ int tzk_spatial_delta(tz_ctx* ctx, tz_layout layout, const int16_t* in, size_t n
     return TZ_OK;
 }
 
+// --------------------------------------------------------------------- lattice quantiser (TZ-QL1)
+// Not in the reference (include/tezip_hip.h: tz_set_quantiser; slow statement: tezip_amd/lattice.py).  For a delta d and the
+// tolerance e of its chain -- the float64 the greedy walk above forms, from the same launches (k_q_minmax / k_q_bound,
+// k_q_frame_bound's rule) --
+//     E = min(255, floor(e)),  s = 2E + 1,  q = clamp(sign(d) * ((|d| + E) div s) * s, -255, 255),  E == 0: q = d.
+// A pure function of one delta and one tolerance: no walk, no stitch, no fallback.  Per chain the host side of the launch is
+// LatP {E, M}, M = floor(2^32 / s) + 1: (a * M) >> 32 == a div s exactly while a * s < 2^32, and a = |d| + E <= 33023,
+// s <= 511 for every int16 d.  pwrel has a tolerance per element (orig * b0 in fp64): E is formed in the lane and the division
+// is the compiler's; LatP.E then only says whether the frame is quantised at all.
+struct LatP {
+    int E;        // 0: the chain is left as it is (a skipped frame, or e < 1)
+    unsigned M;
+};
+
+__global__ void k_lat_params(const double* __restrict__ Echain, const uint8_t* __restrict__ skip, int nframes, int pw,
+                             LatP* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nframes * 3) return;
+    LatP p{0, 0u};
+    if (!skip[i / 3]) {
+        if (pw) {
+            p.E = 1;
+        } else {
+            const double e = Echain[i];                          // >= 0 (a NaN, 0 * inf, counts as 0)
+            const int E = e >= 255.0 ? 255 : (e >= 1.0 ? (int)e : 0);
+            p.E = E;
+            p.M = E ? (unsigned)(0x100000000ull / (unsigned)(2 * E + 1)) + 1u : 0u;
+        }
+    }
+    out[i] = p;
+}
+
+template <bool PW>
+__device__ __forceinline__ int lat_apply(int d, unsigned o, const LatP p, double b0) {
+    const unsigned ad = (unsigned)(d < 0 ? -d : d);
+    unsigned E, k;
+    if (PW) {
+        const double e = o ? (double)o * b0 : 0.0;               // (0 * inf is no tolerance)
+        E = e >= 255.0 ? 255u : (e >= 1.0 ? (unsigned)e : 0u);
+        if (!p.E) E = 0u;
+        k = (ad + E) / (2u * E + 1u);
+    } else {
+        E = (unsigned)p.E;
+        k = __umulhi(ad + E, p.M);
+    }
+    const int m = (int)min(k * (2u * E + 1u), 255u);
+    return E ? (d < 0 ? -m : m) : d;
+}
+
+// the three chains of frame f, rotated so that r[j] belongs to the element j places behind one of channel c0
+__device__ __forceinline__ void lat_chains(const LatP* __restrict__ P, size_t f, unsigned c0, LatP r[3]) {
+    const LatP a = P[3 * f], b = P[3 * f + 1], c = P[3 * f + 2];
+    r[0] = c0 == 0 ? a : (c0 == 1 ? b : c);
+    r[1] = c0 == 0 ? b : (c0 == 1 ? c : a);
+    r[2] = c0 == 0 ? c : (c0 == 1 ? a : b);
+}
+
+// Stand-alone / unfused form: an int16 delta stack in place (tz_lattice_bound, and tz_encode where the fused front below does
+// not apply).  diff need only be 2-byte aligned: `head` elements in front of the first 16-byte boundary and the n - head - 8 n8
+// behind the vector groups go one by one; a group of 8 that straddles a frame boundary takes its chains element by element.
+template <bool PW>
+__device__ __forceinline__ void lattice1(int16_t* __restrict__ diff, const uint8_t* __restrict__ orig, const LatP* __restrict__ P,
+                                         double b0, size_t fe, size_t e) {
+    const size_t f = e / fe;
+    const unsigned c = (unsigned)((e - f * fe) % 3);
+    diff[e] = (int16_t)lat_apply<PW>(diff[e], PW ? orig[e] : 0u, P[3 * f + c], b0);
+}
+
+template <bool PW>
+__global__ __launch_bounds__(256) void k_lattice(int16_t* __restrict__ diff, const uint8_t* __restrict__ orig, const LatP* __restrict__ P,
+                                                 double b0, size_t n, size_t fe, size_t head, size_t n8) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint4* v8 = (uint4*)(diff + head);   // 16-byte aligned when n8 > 0 (tzk_lattice)
+    for (size_t i = t0; i < n8; i += stride) {
+        const size_t e0 = head + 8 * i, f = e0 / fe, r0 = e0 - f * fe;
+        if (r0 + 8 > fe) {   // the group straddles a frame boundary
+            for (int k = 0; k < 8; ++k) lattice1<PW>(diff, orig, P, b0, fe, e0 + k);
+            continue;
+        }
+        LatP r[3];
+        lat_chains(P, f, (unsigned)(r0 % 3), r);
+        const uint4 v = v8[i];
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+        unsigned q[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int lo = lat_apply<PW>((int)(short)(w[j] & 0xFFFFu), PW ? orig[e0 + 2 * j] : 0u, r[(2 * j) % 3], b0);
+            const int hi = lat_apply<PW>((int)w[j] >> 16, PW ? orig[e0 + 2 * j + 1] : 0u, r[(2 * j + 1) % 3], b0);
+            q[j] = ((unsigned)lo & 0xFFFFu) | ((unsigned)hi << 16);
+        }
+        v8[i] = make_uint4(q[0], q[1], q[2], q[3]);
+    }
+    const size_t v_end = head + 8 * n8, nscalar = head + (n - v_end);
+    for (size_t j = t0; j < nscalar; j += stride) lattice1<PW>(diff, orig, P, b0, fe, j < head ? j : v_end + (j - head));
+}
+
+// what tzk_error_bound refuses, refused in its words
+static int lattice_check(tz_ctx* ctx, int mode, double b0, double b1) {
+    if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
+    if ((mode == TZ_MODE_PWREL || mode == TZ_MODE_REL) && b0 < 0.0)
+        return tz_fail(ctx, TZ_ERR_INVALID, "%s bound must be >= 0 (the reference raises on a negative one)", mode == TZ_MODE_REL ? "rel" : "pwrel");
+    if (mode == TZ_MODE_ABSREL && b1 < 0.0)
+        return tz_fail(ctx, TZ_ERR_INVALID, "the rel bound of absrel must be >= 0 (the reference raises on a negative one)");
+    if (std::isnan(b0) || (mode == TZ_MODE_ABSREL && std::isnan(b1)))
+        return tz_fail(ctx, TZ_ERR_INVALID, "error bound is NaN (the reference raises on a NaN tolerance)");
+    return TZ_OK;
+}
+
+bool tz_lattice_is_identity(int mode, double b0, double b1) {
+    if (std::isnan(b0) || (mode == TZ_MODE_ABSREL && std::isnan(b1))) return false;   // (the general path and its refusal)
+    double worst;
+    if (mode == TZ_MODE_ABS) worst = fabs(b0);
+    else if (mode == TZ_MODE_REL || mode == TZ_MODE_PWREL) worst = 255.0 * b0;        // (rounding is monotone: range * b0 <= 255 b0)
+    else if (mode == TZ_MODE_ABSREL) worst = std::min(fabs(b0), 255.0 * b1);
+    else return false;
+    return worst >= 0.0 && worst < 1.0;
+}
+
+// LatP per chain on the device: the tolerances as quant_run's first stage forms them (the same kernels for rel / absrel), then
+// k_lat_params.  h_fb (may be NULL): one abs tolerance per frame in place of (mode, b0, b1).
+static int lattice_params(tz_ctx* ctx, const uint8_t* orig, const uint8_t* h_skip, int nframes, int HW, int mode, double b0, double b1,
+                          const double* h_fb, const LatP** out) {
+    void *d_skip, *d_E, *d_lp;
+    TZ_TRY(tz_pool_alloc(ctx, nframes, &d_skip));
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(double) * 3 * nframes, &d_E));
+    TZ_TRY(tz_pool_alloc(ctx, sizeof(LatP) * 3 * nframes, &d_lp));
+    TZ_TRY(tz_upload(ctx, d_skip, h_skip, nframes));
+    tz_prof_scope ps(ctx, TZP_QUANT);
+    if (!h_fb && (mode == TZ_MODE_REL || mode == TZ_MODE_ABSREL)) {
+        void* d_mm;
+        TZ_TRY(tz_pool_alloc(ctx, sizeof(int) * 6 * nframes, &d_mm));
+        QParams qp{mode, b0, b1};
+        hipLaunchKernelGGL(k_q_mm_init, dim3((6 * nframes + 255) / 256), dim3(256), 0, ctx->stream, (int*)d_mm, 6 * nframes);
+        hipLaunchKernelGGL(k_q_minmax, dim3(QBB, nframes), dim3(256), 0, ctx->stream, orig, (const uint8_t*)d_skip, HW, (int*)d_mm);
+        hipLaunchKernelGGL(k_q_bound, dim3((3 * nframes + 63) / 64), dim3(64), 0, ctx->stream, (const int*)d_mm, (const uint8_t*)d_skip, qp,
+                           nframes, (double*)d_E);
+    } else {
+        std::vector<double> e(3 * (size_t)nframes);
+        for (int i = 0; i < 3 * nframes; ++i) e[i] = h_fb ? h_fb[i / 3] : fabs(b0);   // (pwrel: not read)
+        TZ_TRY(tz_upload(ctx, d_E, e.data(), sizeof(double) * e.size()));
+    }
+    hipLaunchKernelGGL(k_lat_params, dim3((3 * nframes + 63) / 64), dim3(64), 0, ctx->stream, (const double*)d_E, (const uint8_t*)d_skip,
+                       nframes, !h_fb && mode == TZ_MODE_PWREL ? 1 : 0, (LatP*)d_lp);
+    TZ_HIP(ctx, hipGetLastError());
+    *out = (const LatP*)d_lp;
+    return TZ_OK;
+}
+
+int tzk_lattice(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* h_skip, int nframes, int H, int W, int mode, double b0,
+                double b1, const double* h_bounds) {
+    if (!h_bounds) {
+        TZ_TRY(lattice_check(ctx, mode, b0, b1));
+        if (b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0)) return TZ_OK;   // no tolerance: nothing changes
+        if (tz_lattice_is_identity(mode, b0, b1)) return TZ_OK;                 // every chain has E == 0
+    }
+    if (nframes <= 0 || H <= 0 || W <= 0) return TZ_OK;
+    if (h_bounds) {
+        bool any = false;
+        for (int f = 0; f < nframes; ++f) any = any || (h_bounds[f] >= 1.0 && !h_skip[f]);
+        if (!any) return TZ_OK;   // every frame is left as it is
+    }
+    if ((uintptr_t)diff & 1) return tz_fail(ctx, TZ_ERR_INVALID, "lattice_bound: the delta stack must be 2-byte aligned");
+    const size_t fe = (size_t)H * W * 3, n = fe * nframes;
+    const LatP* d_lp;
+    TZ_TRY(lattice_params(ctx, orig, h_skip, nframes, H * W, mode, b0, b1, h_bounds, &d_lp));
+    size_t head = std::min(n, (size_t)((16 - ((uintptr_t)diff & 15)) & 15) / 2), n8 = (n - head) / 8;
+    if (n8 == 0) head = n;
+    const bool pw = !h_bounds && mode == TZ_MODE_PWREL;
+    const size_t items = std::max(n8, head + (n - head - 8 * n8));
+    tz_prof_scope ps(ctx, TZP_QUANT);
+    if (pw) hipLaunchKernelGGL(k_lattice<true>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, diff, orig, d_lp, b0, n, fe, head, n8);
+    else hipLaunchKernelGGL(k_lattice<false>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, diff, orig, d_lp, b0, n, fe, head, n8);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// The fused lattice front: k_delta_sd_fused with TZ-QL1 between the delta and the spatial delta, in every payload layout.  A lane
+// makes 8 symbols: flat and channel stride from 8 consecutive elements (two 16-byte loads of pred, one 8-byte load of orig),
+// gray from channel 0 of 8 pixels (six and three loads; channels 1 and 2 share their cache lines and are not looked at).  The
+// elements in front of a lane's first -- one, or three at the channel stride -- are made again from pred / orig and quantised
+// with THEIR chain's tolerance (the last frame's at a frame start).  Histogram: HistLds / HistAcc above.
+static constexpr int LAT_FLAT = 0, LAT_GRAY = 1, LAT_S3 = 2;
+
+template <int LAY, bool HIST, bool PW>
+__global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_lattice_sd(const float4* __restrict__ pred, const uint2* __restrict__ orig,
+                                                                        const uint8_t* __restrict__ zero_mask, const LatP* __restrict__ P,
+                                                                        double b0, size_t n8, unsigned frame_items, int apply_offset,
+                                                                        uint4* __restrict__ out, unsigned long long* __restrict__ hist,
+                                                                        int16_t* __restrict__ edge) {
+    __shared__ unsigned hraw[HIST ? HL_WORDS : 1];
+    HistLds& hl = *(HistLds*)hraw;
+    constexpr bool do_hist = HIST;
+    if (do_hist) hist_clear(hl);
+    const int centre = apply_offset ? TZ_OFFSET : 0;
+    HistAcc acc;
+    const float* predf = (const float*)pred;
+    const uint8_t* origb = (const uint8_t*)orig;
+    constexpr int ES = LAY == LAT_GRAY ? 3 : 1;        // input elements per symbol
+    constexpr int NPREV = LAY == LAT_S3 ? 3 : 1;       // elements in front of the lane's first that its symbols need
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
+        const size_t f = i / frame_items;
+        const bool fstart = i - f * frame_items == 0;
+        const bool zero = zero_mask[f] != 0;
+        int d[8];
+        unsigned ob[8];
+        if (LAY == LAT_GRAY) {
+            const float4 p0 = pred[6 * i], p1 = pred[6 * i + 1], p2 = pred[6 * i + 2], p3 = pred[6 * i + 3], p4 = pred[6 * i + 4],
+                         p5 = pred[6 * i + 5];
+            const uint2 o0 = orig[3 * i], o1 = orig[3 * i + 1], o2 = orig[3 * i + 2];
+            const float pv[8] = {p0.x, p0.w, p1.z, p2.y, p3.x, p3.w, p4.z, p5.y};     // elements 0, 3, .. 21 of the 24
+            const unsigned w[6] = {o0.x, o0.y, o1.x, o1.y, o2.x, o2.y};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                ob[k] = (w[(3 * k) >> 2] >> (8 * ((3 * k) & 3))) & 0xffu;
+                d[k] = (int)(pv[k] * 255.0f) - (int)ob[k];
+            }
+        } else {
+            const float4 p0 = pred[2 * i], p1 = pred[2 * i + 1];
+            const uint2 o = orig[i];
+            const float pv[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                ob[k] = ((k < 4 ? o.x : o.y) >> (8 * (k & 3))) & 0xffu;
+                d[k] = (int)(pv[k] * 255.0f) - (int)ob[k];
+            }
+        }
+        LatP r[3];
+        if (LAY == LAT_GRAY) r[0] = r[1] = r[2] = P[3 * f];
+        else lat_chains(P, f, (unsigned)(((i % 3) * 2) % 3), r);   // (a frame holds a multiple of 3 elements: channel of 8 i = 8 i mod 3)
+        int q[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) q[k] = lat_apply<PW>(zero ? 0 : d[k], ob[k], r[LAY == LAT_GRAY ? 0 : k % 3], b0);
+        int pq[3] = {0, 0, 0};
+        if (i) {
+            const size_t pf = fstart ? f - 1 : f;
+            const bool pzero = zero_mask[pf] != 0;
+#pragma unroll
+            for (int j = 0; j < NPREV; ++j) {
+                const size_t e = (size_t)8 * ES * i - (size_t)ES * (NPREV - j);
+                const int c = LAY == LAT_GRAY ? 0 : (LAY == LAT_FLAT ? 2 : j);      // at a frame start the elements in front are ..., 1, 2
+                const LatP lp = fstart ? P[3 * pf + c] : r[c];
+                const unsigned o = origb[e];
+                pq[j] = lat_apply<PW>(pzero ? 0 : (int)(predf[e] * 255.0f) - (int)o, o, lp, b0);
+            }
+        }
+        unsigned V[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) V[j] = ((unsigned)q[2 * j] & 0xFFFFu) | ((unsigned)q[2 * j + 1] << 16);
+        unsigned Y[4];
+        if (LAY == LAT_S3) {
+            // w = (e[-4], e[-3]), (e[-2], e[-1]); at the stream start out[k] = x[k] for k < 3, i.e. the elements in front are "2 x[k]"
+            const uint2 w = i ? make_uint2((unsigned)pq[0] << 16, ((unsigned)pq[1] & 0xFFFFu) | ((unsigned)pq[2] << 16))
+                              : make_uint2(V[0] << 17, ((V[0] >> 15) & 0xFFFEu) | (V[1] << 17));
+            const unsigned P0 = __builtin_amdgcn_alignbit(w.y, w.x, 16), P1 = __builtin_amdgcn_alignbit(V[0], w.y, 16),
+                           P2 = __builtin_amdgcn_alignbit(V[1], V[0], 16), P3 = __builtin_amdgcn_alignbit(V[2], V[1], 16);
+            Y[0] = pk_sub(P0, V[0]);
+            Y[1] = pk_sub(P1, V[1]);
+            Y[2] = pk_sub(P2, V[2]);
+            Y[3] = pk_sub(P3, V[3]);
+            if (apply_offset) {
+                const unsigned C = ((unsigned)TZ_OFFSET << 16) | (unsigned)TZ_OFFSET;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) Y[j] = pk_sub(C, Y[j]);
+            }
+        } else {
+            const unsigned pv = i ? ((unsigned)pq[0] & 0xFFFFu) : ((V[0] << 1) & 0xFFFFu);   // stream start: sd[0] = x[0]
+            sdelta8(make_uint4(V[0], V[1], V[2], V[3]), pv, apply_offset != 0, Y);
+        }
+        out[i] = make_uint4(Y[0], Y[1], Y[2], Y[3]);
+        if (do_hist) hist_add8(hl, acc, Y, centre);
+        if (LAY != LAT_S3 && edge) {   // first / last element of the quantised stack (channel 0's under the gray layout)
+            if (i == 0) edge[0] = (int16_t)q[0];
+            if (i == n8 - 1) edge[1] = (int16_t)q[7];
+        }
+    }
+    if (do_hist) hist_flush(hl, acc, centre, hist);
+}
+
+int tzk_lattice_sd_fused(tz_ctx* ctx, tz_layout layout, const float* pred, const uint8_t* orig, const uint8_t* d_zero_mask,
+                         const uint8_t* h_skip, int nframes, int H, int W, int Hp, int Wp, int mode, double b0, double b1,
+                         const double* h_bounds, int apply_offset, int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done) {
+    *done = false;
+    if (!h_bounds) TZ_TRY(lattice_check(ctx, mode, b0, b1));
+    const int lay = layout.channels == 1 ? LAT_GRAY : (layout.stride == 3 ? LAT_S3 : LAT_FLAT);
+    const size_t fsym = tz_frame_elems(layout, H, W);   // symbols of a frame
+    if (H != Hp || W != Wp || fsym % 8 || nframes <= 0) return TZ_OK;
+    if (((((uintptr_t)pred | (uintptr_t)sym) & 15) | ((uintptr_t)orig & 7)) != 0) return TZ_OK;   // 16-byte pred / sym, 8-byte orig accesses
+    const LatP* d_lp;
+    TZ_TRY(lattice_params(ctx, orig, h_skip, nframes, H * W, mode, b0, b1, h_bounds, &d_lp));
+    const size_t n8 = fsym * nframes / 8;
+    const bool pw = !h_bounds && mode == TZ_MODE_PWREL;
+    tz_prof_scope ps(ctx, TZP_DELTA);
+    const dim3 grid(d_hist ? std::min(HB_GRID, grid_for(n8, HB_THREADS)) : grid_for(n8, 256)), block(d_hist ? HB_THREADS : 256);
+#define TZ_LAT_LAUNCH(L, HV, PWV)                                                                                                 \
+    hipLaunchKernelGGL((k_lattice_sd<L, HV, PWV>), grid, block, 0, ctx->stream, (const float4*)pred, (const uint2*)orig, d_zero_mask, \
+                       d_lp, b0, n8, (unsigned)(fsym / 8), apply_offset, (uint4*)sym, d_hist, d_edge)
+#define TZ_LAT_LAYOUT(L)                            \
+    do {                                            \
+        if (d_hist && pw) TZ_LAT_LAUNCH(L, true, true);        \
+        else if (d_hist) TZ_LAT_LAUNCH(L, true, false);        \
+        else if (pw) TZ_LAT_LAUNCH(L, false, true);            \
+        else TZ_LAT_LAUNCH(L, false, false);                   \
+    } while (0)
+    if (lay == LAT_FLAT) TZ_LAT_LAYOUT(LAT_FLAT);
+    else if (lay == LAT_GRAY) TZ_LAT_LAYOUT(LAT_GRAY);
+    else TZ_LAT_LAYOUT(LAT_S3);
+#undef TZ_LAT_LAYOUT
+#undef TZ_LAT_LAUNCH
+    TZ_HIP(ctx, hipGetLastError());
+    *done = true;
+    return TZ_OK;
+}
+
 // ----------------------------------------------------------------------- rank remap / unmap
 // compress.py:84-90 and decompress.py:31-36 are T sequential `where` passes (O(N*T)); here
 // one pass through a 2112-entry LUT held in LDS.  Values outside [0, 2112) pass through

@@ -134,6 +134,7 @@ struct tz_ctx {
     int payload_channels = 3;               // tz_set_payload_channels: 1 = the payload of a gray job holds channel 0 alone
     std::vector<double> frame_bounds;       // tz_set_frame_bounds: one abs tolerance per frame of the encoder rollout (empty: none)
     int delta_stride_mode = 0;              // tz_set_delta_stride: 1 = the spatial delta of the payload runs at the channel stride
+    int quantiser = 0;                      // tz_set_quantiser: 0 = the reference's greedy walk, 1 = the lattice quantiser TZ-QL1
     unsigned long long* d_scan3_status = nullptr;   // strided inverse scan (k_scan3p): one 64-bit word per block, own epochs
     unsigned scan3_epoch = 0;
     // opt-in Huffman coder (tz_huff_*): the coded stream (index | bits) of the resident payload, or the stream a decoder
@@ -375,6 +376,19 @@ static inline size_t tz_frame_elems(tz_layout l, int H, int W) { return (size_t)
 // and the counts ADDED to d_hist (may be NULL).  Flat wants 16-byte aligned buffers, the other two 2-byte aligned ones.
 int tzk_spatial_delta(tz_ctx*, tz_layout, const int16_t* in, size_t n, const int16_t* carry, int apply_offset, int16_t* out,
                       unsigned long long* d_hist, int16_t* d_edge);
+// The lattice quantiser TZ-QL1 (include/tezip_hip.h: tz_set_quantiser).  (mode, b0, b1) as tzk_error_bound's
+// and refused as there; h_bounds (may be NULL): nframes abs tolerances, finite and >= 0, in their place.
+// tzk_lattice: the int16 delta stack diff (any 2-byte alignment) is quantised in place; frames with h_skip[f] stay as they are.
+// tzk_lattice_sd_fused: the fused front -- delta, TZ-QL1, the layout's spatial delta, 1600 offset and histogram in one pass over
+// pred / orig, where its kernel applies (unpadded frames of whole 16-byte groups on 16-byte boundaries: *done).  d_zero_mask as
+// tzk_delta's; d_edge (may be NULL) receives the first and the last element of the quantised stack (channel 0's under the gray
+// layout, nothing under the channel stride).
+int tzk_lattice(tz_ctx*, const uint8_t* orig, int16_t* diff, const uint8_t* h_skip, int nframes, int H, int W, int mode, double b0,
+                double b1, const double* h_bounds);
+int tzk_lattice_sd_fused(tz_ctx*, tz_layout, const float* pred, const uint8_t* orig, const uint8_t* d_zero_mask, const uint8_t* h_skip,
+                         int nframes, int H, int W, int Hp, int Wp, int mode, double b0, double b1, const double* h_bounds,
+                         int apply_offset, int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done);
+bool tz_lattice_is_identity(int mode, double b0, double b1);   // the worst-case tolerance of the job is below 1: q == d everywhere
 int tzk_lut(tz_ctx*, const int16_t* in, size_t n, const int16_t* h_lut2112, int post_offset, int16_t* out);
 // forward: int16[n] -> low-byte plane | high-byte plane (2n bytes); inverse: planes (passed as `in`) -> int16[n] at `out`
 int tzk_shuffle(tz_ctx*, const int16_t* in, size_t n, uint8_t* out, int inverse);

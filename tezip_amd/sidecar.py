@@ -19,6 +19,10 @@ states the same and is authoritative: a sidecar that contradicts it is an error.
 three-channel payload, tezip_amd/sdelta.py); every other job has no such key.  The trailer of entropy.dat states the same (mark
 4 or 5) and is authoritative: a sidecar that contradicts it is an error.
 
+`quant` = "lattice" (optional): the job's deltas were quantised by the lattice quantiser TZ-QL1 (`-c --quant lattice`,
+tezip_amd/lattice.py); every other job has no such key.  Informational: the payload holds the quantised deltas themselves, a
+decoder never sees a bound, and `-u` does not read the key.
+
 `stack` = [frames, height, width, warm_up] (round 6, optional): the reference stores these in the LAST seven
 values of entropy.dat (compress.py:390-394), so a decoder learns it only when the whole payload is decompressed; with
 it here the decoder runs its rollout WHILE entropy.dat is being decompressed (decompress._run_streaming) and checks the
@@ -55,7 +59,7 @@ def requested_contract():
     return int(v) if v in ("1", "2") else None
 
 
-def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta="flat"):
+def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta="flat", quant="greedy"):
     from . import _lib
     if contract not in (1, 2):
         raise ValueError("contract must be 1 or 2, not %r" % (contract,))
@@ -68,6 +72,8 @@ def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta
         doc["payload_channels"] = 1
     if sdelta == "channel":     # a --sdelta channel job with a three-channel payload; every other job has no such key
         doc["sdelta"] = "channel"
+    if quant == "lattice":      # a --quant lattice job; every other job has no such key
+        doc["quant"] = "lattice"
     with open(os.path.join(out_dir, NAME), "w", encoding="UTF-8") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")

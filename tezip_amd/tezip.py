@@ -95,6 +95,12 @@ FLAG_TABLE = (
     # object with a "frame_bounds" list (the bound_search.json of a --per-frame job replays); 0 keeps a frame lossless; entries
     # at frames that are stored exactly are taken as 0 (compress.run(FRAME_BOUNDS=FILE))
     (None, "--frame-bounds", dict(type=str, default=None, metavar="FILE", dest="frame_bounds")),
+    # not in the reference: with -c, the quantiser of a lossy job.  greedy (also when the flag is absent) = the reference's
+    # error_bound, which merges runs of neighbouring deltas; lattice = every delta on its own to the nearest multiple of
+    # 2 floor(E) + 1 under the same tolerance E (definition TZ-QL1 in tezip_amd/lattice.py; smaller on data that is not smooth,
+    # LARGER on sparse frames at loose bounds, and at tight bounds about 2 dB less PSNR for the same worst-case error: README).
+    # The files are ordinary ones: -u needs no flag (compress.run(QUANT=...))
+    (None, "--quant", dict(type=str, choices=("greedy", "lattice"), default=None, dest="quant")),
 )
 
 TEXT = {
@@ -242,6 +248,19 @@ def check_sdelta_flag(arg):
     if mode == "channel" and getattr(arg, "sweep", None) is not None:
         return "--sdelta channel cannot be combined with --sweep"
     return compress.check_sdelta(mode, int(os.environ.get("WORLD_SIZE", "1")) > 1)
+
+
+def check_quant_flag(arg):
+    """--quant is valid with -c only; `lattice` needs one single-GPU job without --sweep.  Returns None, or the message of a
+    refusal."""
+    quant = getattr(arg, "quant", None)
+    if quant is None:
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return "--quant is valid with -c (--compress) only (-u decodes such a job without a flag)"
+    if quant == "lattice" and getattr(arg, "sweep", None) is not None:
+        return "--quant lattice cannot be combined with --sweep"
+    return compress.check_quant(quant, int(os.environ.get("WORLD_SIZE", "1")) > 1)
 
 
 def check_target_flag(arg):
@@ -400,6 +419,10 @@ def _main(arg):
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_quant_flag(arg)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # launched by torch.distributed.run: one rank per GPU
         from . import dist as tzdist
         tzdist.init_from_env()
@@ -439,6 +462,15 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if getattr(arg, "quant", None) == "lattice":   # (greedy is the job without the flag: the calls below; every other flag travels with it)
+        searched = db is not None or ratio is not None or bounds_file is not None
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs" if searched else arg.mode[0],
+                            [] if searched else arg.bound, gpu, arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle,
+                            REPORT=bool(getattr(arg, "report", False)), CODER=getattr(arg, "coder", "zstd"),
+                            KEY_CODER=getattr(arg, "key_coder", "zstd"), DIGESTS=bool(getattr(arg, "digests", False)),
+                            GRAY=bool(getattr(arg, "gray", False)), SDELTA=getattr(arg, "sdelta", None) or "flat",
+                            SSIM=bool(getattr(arg, "ssim", False)), TARGET_PSNR=db, TARGET_RATIO=ratio, PER_FRAME=per_frame,
+                            FRAME_BOUNDS=bounds_file, QUANT="lattice")
     if per_frame or bounds_file is not None:   # (every other flag travels with it; the jobs without it are the calls below)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
