@@ -227,6 +227,34 @@ int tz_get_payload_channels(tz_ctx* ctx);
  *    mode 1 (whatever the channel count): one carry element is not the carry of a strided scan, sharded jobs are out of scope. */
 int tz_set_delta_stride(tz_ctx* ctx, int mode);
 int tz_get_delta_stride(tz_ctx* ctx);
+/* Opt-in 2-D spatial delta of the payload, definition TZ-SD2 (no reference counterpart; `tezip.py -c --sdelta plane`, format in
+ * DESIGN.md section 9, slow statement in tezip_amd/sdelta.py encode_plane / decode_plane).  on: 0 (the default: every entry point
+ * launches exactly what it launches without this call) or 1; anything else is TZ_ERR_INVALID.  A change drops a resident payload.
+ * tz_set_delta_plane(1) while tz_set_delta_stride(1) is in force is TZ_ERR_INVALID, and so is tz_set_delta_stride(1) while
+ * tz_set_delta_plane(1) is.  With q[f, y, x, c] the quantised delta stack, C = tz_get_payload_channels() and every neighbour
+ * outside the frame taken as 0, per frame and channel
+ *     sd = wrap9(q[y, x-1] + q[y-1, x] - q[y-1, x-1] - q[y, x]),   wrap9(v) = ((v + 256) mod 512) - 256  in [-256, 255]
+ * and the symbol is 1600 - sd in [1345, 1856]: TZ_NBINS and TZ_MAX_TABLE hold.  The inverse is q = wrap9(S), S the inclusive 2-D
+ * prefix sum of -sd over the frame and channel.  Every frame is coded on its own.  On one channel this is NOT the flat delta.
+ * Under 1:
+ *  - tz_encode (payload == NULL, the deferred hand-over, the shuffle bit, delta_out with three channels, tz_set_frame_bounds and
+ *    both quantisers) yields the plane payload, by the unfused chain in every mode: delta, quantiser, k_sdelta_plane with the
+ *    histogram, remap.  tz_encode_delta and tz_bound_probe do not depend on the spatial delta and serve as ever.
+ *  - tz_decode, tz_decode_range, tz_encode_quality, tz_encode_ssim and tz_encode_digests take such a payload and yield what they
+ *    yield without the call from the flat payload of the same job; tz_decode_range with first > 0 computes no carry and reads
+ *    nothing in front of the range.
+ *  - tz_encode_begin, tz_encode_finish, tz_decode_delta, tz_undelta_carry, tz_undelta_carry_stride and tz_size_probe return
+ *    TZ_ERR_UNSUPPORTED with a message that names tz_set_delta_plane. */
+int tz_set_delta_plane(tz_ctx* ctx, int on);
+int tz_get_delta_plane(tz_ctx* ctx);
+/* The seams of TZ-SD2, whatever the context's setting: nframes x H x W x channels int16 elements (channels 3 or 1), host or
+ * device buffers at any 2-byte alignment.  tz_spatial_delta_plane: out = sd, or 1600 - sd when apply_offset; the counts of out
+ * are ADDED to hist (TZ_NBINS words, may be NULL).  tz_spatial_undelta_plane: the inverse; table_len -1: `in` holds sd as
+ * stored, else the ranks of the symbols 1600 - sd under `table` (tz_decode's reading of a payload). */
+int tz_spatial_delta_plane(tz_ctx* ctx, const int16_t* in, int nframes, int H, int W, int channels, int apply_offset, int16_t* out,
+                           unsigned long long* hist);
+int tz_spatial_undelta_plane(tz_ctx* ctx, const int16_t* in, int nframes, int H, int W, int channels, const int16_t* table,
+                             int table_len, int16_t* out);
 /* Opt-in: one abs tolerance per frame (no reference counterpart: compress.py takes one bound per job, but its error_bound runs
  * per frame and channel, compress.py:316-319, so a frame's quantised delta depends on that frame's tolerance alone;
  * `tezip.py -c --target-psnr DB --per-frame`, `-c -m abs --frame-bounds FILE`).

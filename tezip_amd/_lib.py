@@ -79,6 +79,10 @@ _SIGS = {
     "tz_get_payload_channels": (C.c_int, [C.c_void_p]),
     "tz_set_delta_stride": (C.c_int, [C.c_void_p, C.c_int]),
     "tz_get_delta_stride": (C.c_int, [C.c_void_p]),
+    "tz_set_delta_plane": (C.c_int, [C.c_void_p, C.c_int]),
+    "tz_get_delta_plane": (C.c_int, [C.c_void_p]),
+    "tz_spatial_delta_plane": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tz_spatial_undelta_plane": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "tz_set_frame_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "tz_get_frame_bounds": (C.c_int, [C.c_void_p]),
     "tz_error_bound_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -636,6 +640,15 @@ class Context:
 
     def get_delta_stride(self):
         return int(self.lib.tz_get_delta_stride(self.h))
+
+    def set_delta_plane(self, on):
+        """tz_set_delta_plane: 0 (the default) or 1 = the spatial delta of the payload is the 2-D one, TZ-SD2
+        (tezip_amd/sdelta.py encode_plane): encode / decode / decode_range / encode_quality / encode_ssim / encode_digests work
+        on the plane payload, a range decode takes no carry; the sharded entry points, the carries and size_probe refuse."""
+        self._ck(self.lib.tz_set_delta_plane(self.h, int(on)))
+
+    def get_delta_plane(self):
+        return int(self.lib.tz_get_delta_plane(self.h))
 
     def set_frame_bounds(self, bounds):
         """tz_set_frame_bounds: one abs tolerance per frame of the encoder rollout (None or empty: clear).  While set, encode /
@@ -1244,6 +1257,26 @@ class Context:
             out = np.empty(n, np.int16)
         cy = None if carry is None else _carry(carry, stride)
         self._ck(self.lib.tz_spatial_undelta_stride(self.h, _ptr(x), n, int(stride), _ptr(cy), _ptr(out)))
+        return out
+
+    def spatial_delta_plane(self, x, shape, offset, hist=None, out=None):
+        """tz_spatial_delta_plane: TZ-SD2 (tezip_amd/sdelta.py encode_plane) of the int16 stack x of `shape` = (nt, H, W, C),
+        host or device."""
+        nt, h, w, c = (int(v) for v in shape)
+        if out is None:
+            out = np.empty(nt * h * w * c, np.int16)
+        self._ck(self.lib.tz_spatial_delta_plane(self.h, _ptr(x), nt, h, w, c, int(offset), _ptr(out), _ptr(hist)))
+        return out
+
+    def spatial_undelta_plane(self, x, shape, table=None, out=None):
+        """tz_spatial_undelta_plane: the inverse; table None: x holds the spatial delta as stored, else ranks under the table
+        (with the 1600 offset)."""
+        nt, h, w, c = (int(v) for v in shape)
+        if out is None:
+            out = np.empty(nt * h * w * c, np.int16)
+        tl = -1 if table is None else len(table)
+        tb = None if table is None else np.ascontiguousarray(table, np.int16)
+        self._ck(self.lib.tz_spatial_undelta_plane(self.h, _ptr(x), nt, h, w, c, _ptr(tb), tl, _ptr(out)))
         return out
 
     def undelta_carry_stride(self, payload, n0, stride, table=None, staged=False):

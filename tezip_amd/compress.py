@@ -277,9 +277,13 @@ def check_sdelta(mode, sharded=False):
     """The refusals of --sdelta that a direct caller of run() can meet (tezip.py knows the others): None, or the message."""
     if mode not in sdelta.MODES:
         return "--sdelta takes one of %s, got %r" % (", ".join(sdelta.MODES), mode)
-    if mode == "channel" and sharded:
-        return "--sdelta channel is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU"
+    if mode in ("channel", "plane") and sharded:
+        return "--sdelta %s is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU" % mode
     return None
+
+
+PLANE_NO_RATIO = ("--sdelta plane cannot be combined with --target-ratio: the size probe's kernels form flat and channel-stride "
+                  "symbols only, so it cannot size a plane payload")
 
 
 def decide_sdelta(ctx, channels):
@@ -291,6 +295,14 @@ def decide_sdelta(ctx, channels):
         return True
     print("sdelta: channel equals flat on a one-channel payload")
     return False
+
+
+def decide_plane(ctx):
+    """--sdelta plane: the context is set to the 2-D spatial delta TZ-SD2, whatever the payload's channel count (on one channel
+    plane is NOT the flat delta)."""
+    ctx.set_delta_plane(1)
+    print("sdelta: plane (TZ-SD2)")
+    return True
 
 
 def decide_gray(ctx, nt, files):
@@ -442,15 +454,16 @@ def _key_output(ctx, out_dir, nt, H, W, key, pool, stages=None, verbose=False, k
     return kf
 
 
-def _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages=None, coder="zstd", verbose=False, channels=3, strided=False):
-    """entropy.dat (compress.py:375-400) from the context-resident payload, piece by piece -> its size.  channels, strided: as
-    _stream_outputs'."""
+def _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages=None, coder="zstd", verbose=False, channels=3, strided=False,
+                    plane=False):
+    """entropy.dat (compress.py:375-400) from the context-resident payload, piece by piece -> its size.  channels, strided,
+    plane: as _stream_outputs'."""
     n = nt * H * W * channels
     if table is not None:
         tail = np.concatenate([table.astype(np.int64), [len(table)]])
     else:
         tail = np.array([-1], dtype=np.int64)
-    one = sdelta.mark(shuffled) if strided else (SHUFFLE_MARK if shuffled else 1)
+    one = sdelta.mark(shuffled, plane) if strided or plane else (SHUFFLE_MARK if shuffled else 1)
     trailer = np.concatenate([tail, [one, nt, H, W, channels], [warm_up]]).astype(np.int16)
     t_e = time.perf_counter()
     if coder in ("huff", "huffr", "huffd"):
@@ -473,13 +486,14 @@ def _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages=Non
 
 
 def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False,
-                    key_coder="zstd", channels=3, strided=False):
+                    key_coder="zstd", channels=3, strided=False, plane=False):
     """key_frame.dat and entropy.dat (compress.py:271-278, 375-400) from the context-resident frames
     and payload, piece by piece: nothing of size nt*H*W lives on the host.  channels: what the resident payload stores per
     pixel (1: a gray job, tezip_amd/graypayload.py); key_frame.dat has three either way.  strided: the payload's spatial delta
-    ran at the channel stride (tezip_amd/sdelta.py): the trailer says so in the first entry of its shape."""
+    ran at the channel stride, plane: it is the 2-D one, TZ-SD2 (tezip_amd/sdelta.py): the trailer says so in the first entry of
+    its shape."""
     kf = _key_output(ctx, out_dir, nt, H, W, key, pool, stages, verbose, key_coder)
-    esize = _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages, coder, verbose, channels, strided)
+    esize = _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages, coder, verbose, channels, strided, plane)
     return kf.result(), esize
 
 
@@ -562,6 +576,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     with colour writes exactly the files it writes without the flag.  Works with every CODER, KEY_CODER, SHUFFLE, REPORT and
     DIGESTS.  Single-GPU jobs only.
     SDELTA (--sdelta; NOT in the reference): "flat" (the default: every file, line and launch is what it is without it) or
+    "plane": the spatial delta of the payload is the 2-D one, TZ-SD2 (left + up - upleft per frame and channel, wrapped to nine
+    bits; tezip_amd/sdelta.py): mark 8 in the trailer, 9 with byte planes, with three channels or one; not with TARGET_RATIO; or
     "channel": the spatial delta of a three-channel payload is taken at the channel stride (tezip_amd/sdelta.py); only the
     lossless back half of the coder changes, so the job decodes to exactly the images it decodes to without it.  `-u`
     recognises the stream by the mark in its trailer.  On a one-channel payload (GRAY on an all-gray job) the stride is 1 and
@@ -614,6 +630,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                or check_gray(GRAY, tzdist.active() is not None) or check_sdelta(SDELTA, tzdist.active() is not None))
     if problem:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         print("ERROR:", problem)
+        sys.exit(2)
+    if SDELTA == "plane" and TARGET_RATIO is not None:   # likewise
+        print("ERROR:", PLANE_NO_RATIO)
         sys.exit(2)
     if SSIM and not REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         print("ERROR:", SSIM_NEEDS_REPORT)
@@ -679,6 +698,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 channels = decide_gray(ctx, nt, src.files)
                 stages.mark("gray check (device)")
             strided = SDELTA == "channel" and decide_sdelta(ctx, channels)
+            plane = SDELTA == "plane" and decide_plane(ctx)
+            sd_mode = "plane" if plane else ("channel" if strided else "flat")
             if QUANT == "lattice":   # the probes of the searches below and the job itself quantise by TZ-QL1
                 ctx.set_quantiser("lattice")
                 print(lattice.STDOUT_LINE)
@@ -768,16 +789,16 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     print("replacing_based_on_frequency:{0}".format(prof["lut_remap"][0] / 1e3) + "[sec]")
             if TARGET_RATIO is not None:   # (key_frame.dat is there already)
                 _entropy_output(ctx, OUTPUT_DIR, nt, H, W, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, stages, coder=CODER,
-                                verbose=VERBOSE, channels=channels, strided=strided)
+                                verbose=VERBOSE, channels=channels, strided=strided, plane=plane)
             else:
                 _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
-                                coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided)
+                                coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided, plane=plane)
             if QUANT == "lattice":
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
-                                    payload_channels=channels, sdelta="channel" if strided else "flat", quant="lattice")
+                                    payload_channels=channels, sdelta=sd_mode, quant="lattice")
             else:
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),   # the contract the predictions were made under
-                                    payload_channels=channels, sdelta="channel" if strided else "flat")
+                                    payload_channels=channels, sdelta=sd_mode)
             if VERBOSE:
                 print("arithmetic contract:", doc["arithmetic_contract"])
             stages.mark("key_frame.dat + entropy.dat")

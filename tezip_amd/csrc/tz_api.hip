@@ -1599,7 +1599,7 @@ static int encode_front(tz_ctx* ctx, tz_layout layout, int mode, double b0, doub
                         unsigned long long* d_hist, int16_t* d_edge) {
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
     const size_t N = (size_t)nt * H * W * 3;
-    const bool flat = layout.channels == 3 && layout.stride == 1;
+    const bool flat = layout.channels == 3 && layout.stride == 1 && !layout.plane_h;   // (plane: the unfused chain in every mode)
     void *d_mask = nullptr, *d_delta = d_delta_tap;
     TZ_TRY(tz_pool_alloc(ctx, nt, &d_mask));
     TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
@@ -1699,6 +1699,8 @@ extern "C" int tz_get_payload_channels(tz_ctx* ctx) { return ctx ? ctx->payload_
 extern "C" int tz_set_delta_stride(tz_ctx* ctx, int mode) {
     if (!ctx) return TZ_ERR_INVALID;
     if (mode != 0 && mode != 1) return tz_fail(ctx, TZ_ERR_INVALID, "delta stride mode must be 0 (flat) or 1 (channel), not %d", mode);
+    if (mode == 1 && ctx->delta_plane)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_delta_stride(1) while tz_set_delta_plane(1) is in force: a payload has one spatial delta");
     if (mode != ctx->delta_stride_mode) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under the other stride
     ctx->delta_stride_mode = mode;
     return TZ_OK;
@@ -1706,20 +1708,49 @@ extern "C" int tz_set_delta_stride(tz_ctx* ctx, int mode) {
 
 extern "C" int tz_get_delta_stride(tz_ctx* ctx) { return ctx ? ctx->delta_stride_mode : TZ_ERR_INVALID; }
 
-// the layout in force (tz_internal.h): mode 1 on a one-channel payload is the flat delta
-static constexpr tz_layout kFlat = {3, 1};
+// ---- 2-D spatial delta of the payload, TZ-SD2 (include/tezip_hip.h: tz_set_delta_plane)
+extern "C" int tz_set_delta_plane(tz_ctx* ctx, int on) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (on != 0 && on != 1) return tz_fail(ctx, TZ_ERR_INVALID, "delta plane must be 0 (off) or 1 (TZ-SD2), not %d", on);
+    if (on == 1 && ctx->delta_stride_mode == 1)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_delta_plane(1) while tz_set_delta_stride(1) is in force: a payload has one spatial delta");
+    if (on != ctx->delta_plane) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under the other predictor
+    ctx->delta_plane = on;
+    return TZ_OK;
+}
+
+extern "C" int tz_get_delta_plane(tz_ctx* ctx) { return ctx ? ctx->delta_plane : TZ_ERR_INVALID; }
+
+// the layout in force (tz_internal.h): mode 1 on a one-channel payload is the flat delta; plane fills the frame's rows and
+// columns from the context (with plane off the layout is what it was: every launcher chooses what it chose)
+static const tz_layout kFlat = {3, 1};
 static tz_layout layout_of(const tz_ctx* ctx) {
-    return {ctx->payload_channels, ctx->delta_stride_mode == 1 && ctx->payload_channels == 3 ? 3 : 1};
+    tz_layout l = {ctx->payload_channels, ctx->delta_stride_mode == 1 && ctx->payload_channels == 3 ? 3 : 1};
+    if (ctx->delta_plane) {
+        l.plane_h = ctx->H;
+        l.plane_w = ctx->W;
+    }
+    return l;
+}
+
+// The entry points that serve no plane payload: sharded jobs, carries (a plane frame is coded on its own) and the size probe
+// (its kernels form flat and strided symbols only).
+static int no_plane(tz_ctx* ctx, const char* who) {
+    if (ctx->delta_plane)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve the 2-D spatial delta (tz_set_delta_plane(1)): sharded jobs, carries and the size probe are out of its scope", who);
+    return TZ_OK;
 }
 
 // The entry points of the sharded encoder / decoder serve the flat layout alone: not a one-channel payload, and one carry
 // element is not the carry of a strided scan.  (tz_undelta_carry serves a gray payload: its carry is one element.)
-static int flat_only(tz_ctx* ctx, const char* who, bool serves_gray = false) {
+// (tz_encode_delta serves a plane job: the quantised delta stack does not depend on the spatial delta.)
+static int flat_only(tz_ctx* ctx, const char* who, bool serves_gray = false, bool serves_plane = false) {
     if (ctx->payload_channels == 1 && !serves_gray)
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve a one-channel payload (tz_set_payload_channels(1)): sharded gray jobs are not supported", who);
     if (ctx->delta_stride_mode == 1)
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve the channel-stride spatial delta (tz_set_delta_stride(1)): sharded jobs and one-element carries are flat only", who);
-    return TZ_OK;
+    if (serves_plane) return TZ_OK;
+    return no_plane(ctx, who);
 }
 
 static int keys_gray(tz_ctx* ctx, const int* idx, int nkeys, uint8_t* gray);   // (k_key_gray: with the key-frame coders below)
@@ -1895,7 +1926,7 @@ extern "C" int tz_byte_unshuffle(tz_ctx* ctx, const uint8_t* in, size_t n, int16
 
 extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int16_t* delta_out) {
     if (!ctx || !delta_out) return TZ_ERR_INVALID;
-    TZ_TRY(flat_only(ctx, "tz_encode_delta"));
+    TZ_TRY(flat_only(ctx, "tz_encode_delta", false, true));
     TZ_TRY(encode_check(ctx, "tz_encode_delta", mode));
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
     tz_call call(ctx);
@@ -2007,8 +2038,9 @@ static int decode_frames(tz_ctx* ctx, const char* who, const int16_t* payload, s
     std::vector<int16_t> lut;
     if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
     const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
-    if (first > 0) TZ_TRY(undelta_carry(ctx, layout.stride, d_pay, n0, h_lut, carry));
-    TZ_TRY(tzk_decode_tail(ctx, layout, d_pay + n0, h_lut, 1, first > 0 ? carry : nullptr,
+    const bool has_carry = first > 0 && !layout.plane_h;   // (a plane frame is coded on its own)
+    if (has_carry) TZ_TRY(undelta_carry(ctx, layout.stride, d_pay, n0, h_lut, carry));
+    TZ_TRY(tzk_decode_tail(ctx, layout, d_pay + n0, h_lut, 1, has_carry ? carry : nullptr,
                            ctx->d_pred + (size_t)(first - r) * ctx->Hp * ctx->Wp * 3, ctx->d_frames + (size_t)first * fe, d_mask, count, H,
                            W, ctx->Hp, ctx->Wp, d_out));
     TZ_TRY(call.finish());
@@ -2348,9 +2380,9 @@ static int check_stride(tz_ctx* ctx, const char* who, int stride) {
     return TZ_OK;
 }
 
-// n_in elements at `in` -> n_out at `out` (gray: three interleaved channels in, channel 0's delta out)
-static int spatial_delta_seam(tz_ctx* ctx, tz_layout layout, const int16_t* in, size_t n_in, size_t n_out, const int16_t* carry,
-                              int apply_offset, int16_t* out, unsigned long long* hist) {
+// n_in elements at `in` -> n_out at `out`, by launch(din, dout, dh) on the device buffers
+template <class Launch>
+static int delta_seam(tz_ctx* ctx, const int16_t* in, size_t n_in, size_t n_out, int16_t* out, unsigned long long* hist, Launch launch) {
     tz_call call(ctx);
     const int16_t* din;
     int16_t* dout;
@@ -2364,8 +2396,16 @@ static int spatial_delta_seam(tz_ctx* ctx, tz_layout layout, const int16_t* in, 
             if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "hist upload: %s", hipGetErrorString(e));
         }
     }
-    TZ_TRY(tzk_spatial_delta(ctx, layout, din, n_out, carry, apply_offset, dout, dh, nullptr));
+    TZ_TRY(launch(din, dout, dh));
     return call.finish();
+}
+
+// (gray: three interleaved channels in, channel 0's delta out)
+static int spatial_delta_seam(tz_ctx* ctx, tz_layout layout, const int16_t* in, size_t n_in, size_t n_out, const int16_t* carry,
+                              int apply_offset, int16_t* out, unsigned long long* hist) {
+    return delta_seam(ctx, in, n_in, n_out, out, hist, [&](const int16_t* din, int16_t* dout, unsigned long long* dh) {
+        return tzk_spatial_delta(ctx, layout, din, n_out, carry, apply_offset, dout, dh, nullptr);
+    });
 }
 
 extern "C" int tz_spatial_delta(tz_ctx* ctx, const int16_t* in, size_t n, int has_carry, int16_t carry, int apply_offset,
@@ -2385,6 +2425,42 @@ extern "C" int tz_spatial_delta_stride(tz_ctx* ctx, const int16_t* in, size_t n,
     if (!ctx || !in || !out) return TZ_ERR_INVALID;
     TZ_TRY(check_stride(ctx, "tz_spatial_delta_stride", stride));
     return spatial_delta_seam(ctx, {3, stride}, in, n, n, carry, apply_offset, out, hist);
+}
+
+// The seams of TZ-SD2 (tezip_amd/sdelta.py encode_plane / decode_plane) on nframes x H x W x channels elements, channels 3 or 1,
+// whatever the context's own setting.
+static int check_plane_dims(tz_ctx* ctx, const char* who, int nframes, int H, int W, int channels) {
+    if (nframes < 0 || H < 1 || W < 1 || (channels != 1 && channels != 3) || (size_t)H * W > 0x0FFFFFFFull)
+        return tz_fail(ctx, TZ_ERR_INVALID, "%s: %d frames of %d x %d with %d channels (channels: 3 or 1)", who, nframes, H, W, channels);
+    return TZ_OK;
+}
+
+extern "C" int tz_spatial_delta_plane(tz_ctx* ctx, const int16_t* in, int nframes, int H, int W, int channels, int apply_offset,
+                                      int16_t* out, unsigned long long* hist) {
+    if (!ctx || !in || !out) return TZ_ERR_INVALID;
+    TZ_TRY(check_plane_dims(ctx, "tz_spatial_delta_plane", nframes, H, W, channels));
+    const size_t n = (size_t)nframes * H * W * channels;
+    return delta_seam(ctx, in, n, n, out, hist, [&](const int16_t* din, int16_t* dout, unsigned long long* dh) {
+        return tzk_sdelta_plane(ctx, din, channels, nframes, H, W, channels, apply_offset, dout, dh);
+    });
+}
+
+// table_len -1: `in` holds the spatial delta as stored; else ranks under the table, with the 1600 offset (tz_decode's reading)
+extern "C" int tz_spatial_undelta_plane(tz_ctx* ctx, const int16_t* in, int nframes, int H, int W, int channels, const int16_t* table,
+                                        int table_len, int16_t* out) {
+    if (!ctx || !in || !out) return TZ_ERR_INVALID;
+    TZ_TRY(check_plane_dims(ctx, "tz_spatial_undelta_plane", nframes, H, W, channels));
+    TZ_TRY(check_table(ctx, table, table_len));
+    const size_t n = (size_t)nframes * H * W * channels;
+    std::vector<int16_t> lut;
+    if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
+    tz_call call(ctx);
+    const int16_t* din;
+    int16_t* dout;
+    TZ_TRY(call.in(in, n * 2, &din));
+    TZ_TRY(call.out(out, n * 2, &dout));
+    TZ_TRY(tzk_unplane(ctx, din, nframes, H, W, channels, table_len >= 0 ? lut.data() : nullptr, 1, dout));
+    return call.finish();
 }
 
 static int lut_op(tz_ctx* ctx, const int16_t* in, size_t n, const std::vector<int16_t>& lut, int post, int16_t* out) {
@@ -2441,6 +2517,7 @@ extern "C" int tz_undelta_carry_stride(tz_ctx* ctx, const int16_t* payload, size
     tz_roctx_range roctx_("tz_undelta_carry_stride");
     if (!ctx || !carry_out) return TZ_ERR_INVALID;
     TZ_TRY(check_stride(ctx, "tz_undelta_carry_stride", stride));
+    TZ_TRY(no_plane(ctx, "tz_undelta_carry_stride"));
     if (n0 == 0 || n0 % (size_t)stride)
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_undelta_carry_stride: n0 = %zu is not a positive multiple of the stride %d", n0, stride);
     return undelta_carry_seam(ctx, stride, payload, n0, table, table_len, carry_out);
@@ -3101,6 +3178,7 @@ extern "C" int tz_size_probe(tz_ctx* ctx, int mode, double b0, double b1, int en
     if (!ctx || !out) return TZ_ERR_INVALID;
     if (coder < 0 || coder > 2) return tz_fail(ctx, TZ_ERR_INVALID, "tz_size_probe: coder %d, 0 (huff), 1 (huffr) or 2 (huffd) wanted", coder);
     if (entropy & ~1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_size_probe: byte planes are not Huffman-coded");
+    TZ_TRY(no_plane(ctx, "tz_size_probe"));
     TZ_TRY(encode_check(ctx, "tz_size_probe", mode));
     const tz_layout layout = layout_of(ctx);
     if (layout.channels == 1) {

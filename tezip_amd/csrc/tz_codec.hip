@@ -1865,11 +1865,125 @@ __global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_sdelta_s3(const int
     if (HIST) hist_flush(hl, acc, centre, hist);
 }
 
+// ------------------------------------------------- 2-D spatial delta of the payload (TZ-SD2, tz_set_delta_plane(1))
+// Not in the reference (tezip_amd/sdelta.py encode_plane).  Per frame and channel of the (frame, y, x, C) stack, every
+// neighbour outside the frame taken as 0:
+//     sd = wrap9(q[y, x-1] + q[y-1, x] - q[y-1, x-1] - q[y, x]),   wrap9(v) = ((v + 256) mod 512) - 256
+// then 1600 - sd and the histogram as k_sdelta.  Elementwise: the element, the C elements in front, and the same two places in
+// the row above; nothing is read across a frame boundary.  Vector route (n8 > 0: CIN == C, a row is whole 16-byte groups on
+// 16-byte boundaries): a lane takes 8 elements of a row and the 8 above them as 16-byte loads, the elements in front of either
+// from one more 8-byte load, and forms (left - cur) - (upleft - up) in packed int16 arithmetic.  Any other W, alignment or
+// channel count goes one element at a time; CIN = 3 with C = 1 reads channel 0 of the interleaved three-channel stack.
+__device__ __forceinline__ unsigned pk_wrap9(unsigned x) {   // two int16 lanes
+    return pk_sub(pk_sub(x, 0xFF00FF00u) & 0x01FF01FFu, 0x01000100u);
+}
+
+// P = the eight elements C places in front of the group v at p; no front (the row starts here): zeros
+template <int C>
+__device__ __forceinline__ void plane_front8(const int16_t* __restrict__ p, bool has_front, const uint4 v, unsigned* P) {
+    const uint2 w = has_front ? *(const uint2*)(p - 4) : make_uint2(0u, 0u);   // (e[-4], e[-3]), (e[-2], e[-1])
+    if (C == 3) {
+        P[0] = __builtin_amdgcn_alignbit(w.y, w.x, 16);
+        P[1] = __builtin_amdgcn_alignbit(v.x, w.y, 16);
+        P[2] = __builtin_amdgcn_alignbit(v.y, v.x, 16);
+        P[3] = __builtin_amdgcn_alignbit(v.z, v.y, 16);
+    } else {
+        P[0] = __builtin_amdgcn_alignbit(v.x, w.y, 16);
+        P[1] = __builtin_amdgcn_alignbit(v.y, v.x, 16);
+        P[2] = __builtin_amdgcn_alignbit(v.z, v.y, 16);
+        P[3] = __builtin_amdgcn_alignbit(v.w, v.z, 16);
+    }
+}
+
+template <bool HIST, int CIN, int C>
+__global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_sdelta_plane(const int16_t* __restrict__ in, size_t n, size_t n8, int H, int W,
+                                                      int apply_offset, int16_t* __restrict__ out,
+                                                      unsigned long long* __restrict__ hist) {
+    __shared__ unsigned hraw[HIST ? HL_WORDS : 1];
+    HistLds& hl = *(HistLds*)hraw;
+    if (HIST) hist_clear(hl);
+    const int centre = apply_offset ? TZ_OFFSET : 0;
+    HistAcc acc;
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (CIN == C && n8) {
+        const size_t rw = (size_t)W * C, rw8 = rw / 8;   // elements, groups of a row
+        for (size_t i = t0; i < n8; i += stride) {
+            const size_t row = i / rw8;
+            const bool front = i != row * rw8, top = row % (size_t)H == 0;
+            const int16_t* p = in + 8 * i;
+            const uint4 v = *(const uint4*)p;
+            uint4 u = make_uint4(0u, 0u, 0u, 0u);
+            unsigned Pc[4], Pu[4] = {0u, 0u, 0u, 0u};
+            plane_front8<C>(p, front, v, Pc);
+            if (!top) {
+                u = *(const uint4*)(p - rw);
+                plane_front8<C>(p - rw, front, u, Pu);
+            }
+            unsigned Y[4] = {pk_wrap9(pk_sub(pk_sub(Pc[0], v.x), pk_sub(Pu[0], u.x))), pk_wrap9(pk_sub(pk_sub(Pc[1], v.y), pk_sub(Pu[1], u.y))),
+                             pk_wrap9(pk_sub(pk_sub(Pc[2], v.z), pk_sub(Pu[2], u.z))), pk_wrap9(pk_sub(pk_sub(Pc[3], v.w), pk_sub(Pu[3], u.w)))};
+            if (apply_offset) {
+                const unsigned K = ((unsigned)TZ_OFFSET << 16) | (unsigned)TZ_OFFSET;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) Y[j] = pk_sub(K, Y[j]);
+            }
+            *(uint4*)(out + 8 * i) = make_uint4(Y[0], Y[1], Y[2], Y[3]);
+            if (HIST) hist_add8(hl, acc, Y, centre);
+        }
+    } else {
+        for (size_t j = t0; j < n; j += stride) {
+            const size_t pix = j / C, row = pix / (size_t)W;
+            const int c = (int)(j - pix * C);
+            const bool left = pix != row * (size_t)W, top = row % (size_t)H == 0;
+            const int16_t* p = in + pix * CIN + c;
+            const int cur = p[0], l = left ? (int)p[-CIN] : 0, up = top ? 0 : (int)p[-(ptrdiff_t)W * CIN],
+                      ul = (left && !top) ? (int)p[-((ptrdiff_t)W + 1) * CIN] : 0;
+            const int sd = ((l + up - ul - cur + 256) & 511) - 256;
+            const short y = (short)(apply_offset ? TZ_OFFSET - sd : sd);
+            out[j] = y;
+            if (HIST && y >= 0 && y < TZ_NBINS) atomicAdd(&hl.w[HL_FULL + y], 1u);
+        }
+    }
+    if (HIST) hist_flush(hl, acc, centre, hist);
+}
+
+// in: nframes x H x W x cin elements (cin == C, or 3 with C = 1: channel 0 is taken) -> nframes x H x W x C at out; the counts
+// are ADDED to d_hist (may be NULL).  Buffers at any 2-byte alignment.
+int tzk_sdelta_plane(tz_ctx* ctx, const int16_t* in, int cin, int nframes, int H, int W, int C, int apply_offset, int16_t* out,
+                     unsigned long long* d_hist) {
+    if (nframes < 0 || H < 1 || W < 1 || (C != 1 && C != 3) || (cin != C && cin != 3))
+        return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_plane: %d frames of %d x %d with %d of %d channels", nframes, H, W, C, cin);
+    const size_t n = (size_t)nframes * H * W * C;
+    if (n == 0) return TZ_OK;
+    const uintptr_t both = (uintptr_t)in | (uintptr_t)out;
+    if (both & 1) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_plane buffers must be 2-byte aligned");
+    const size_t n8 = (cin == C && ((size_t)W * C) % 8 == 0 && (both & 15) == 0) ? n / 8 : 0;
+    const size_t items = n8 ? n8 : n;
+    tz_prof_scope ps(ctx, TZP_SDELTA);
+    const dim3 grid(d_hist ? std::min(HB_GRID, grid_for(items, HB_THREADS)) : grid_for(items, 256)), block(d_hist ? HB_THREADS : 256);
+#define TZ_PLANE_LAUNCH(CI, CO)                                                                                                  \
+    do {                                                                                                                         \
+        if (d_hist) hipLaunchKernelGGL((k_sdelta_plane<true, CI, CO>), grid, block, 0, ctx->stream, in, n, n8, H, W, apply_offset, out, d_hist);  \
+        else hipLaunchKernelGGL((k_sdelta_plane<false, CI, CO>), grid, block, 0, ctx->stream, in, n, n8, H, W, apply_offset, out, d_hist);        \
+    } while (0)
+    if (C == 3) TZ_PLANE_LAUNCH(3, 3);
+    else if (cin == 1) TZ_PLANE_LAUNCH(1, 1);
+    else TZ_PLANE_LAUNCH(3, 1);
+#undef TZ_PLANE_LAUNCH
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // The spatial delta of every layout (tz_internal.h): k_sdelta (flat), k_sdelta_gray or k_sdelta_s3, each with its own alignment
-// rule and its own cut into vector groups and single elements; one grid rule over the resulting work items.
+// rule and its own cut into vector groups and single elements; one grid rule over the resulting work items.  The plane layout
+// goes to tzk_sdelta_plane above.
 int tzk_spatial_delta(tz_ctx* ctx, tz_layout layout, const int16_t* in, size_t n, const int16_t* carry, int apply_offset, int16_t* out,
                       unsigned long long* d_hist, int16_t* d_edge) {
     if (n == 0) return TZ_OK;
+    if (layout.plane_h) {   // TZ-SD2: whole frames, no carry; a one-channel payload reads channel 0 of the three, as the gray front
+        const size_t fe = tz_frame_elems(layout, layout.plane_h, layout.plane_w);
+        if (carry || n % fe) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_plane takes whole frames and no carry");
+        return tzk_sdelta_plane(ctx, in, 3, (int)(n / fe), layout.plane_h, layout.plane_w, layout.channels, apply_offset, out, d_hist);
+    }
     const bool gray = layout.channels == 1, s3 = layout.stride == 3;
     const uintptr_t both = (uintptr_t)in | (uintptr_t)out;
     if (gray && (both & 1)) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_delta_gray buffers must be 2-byte aligned");
@@ -2194,6 +2308,7 @@ int tzk_lattice_sd_fused(tz_ctx* ctx, tz_layout layout, const float* pred, const
                          const double* h_bounds, int apply_offset, int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done) {
     *done = false;
     if (!h_bounds) TZ_TRY(lattice_check(ctx, mode, b0, b1));
+    if (layout.plane_h) return TZ_OK;   // TZ-SD2 has no fused front
     const int lay = layout.channels == 1 ? LAT_GRAY : (layout.stride == 3 ? LAT_S3 : LAT_FLAT);
     const size_t fsym = tz_frame_elems(layout, H, W);   // symbols of a frame
     if (H != Hp || W != Wp || fsym % 8 || nframes <= 0) return TZ_OK;
@@ -3028,39 +3143,43 @@ __global__ __launch_bounds__(256) void k_recon(const float* __restrict__ pred, c
     }
 }
 
+// Group i (8 elements) of an unpadded three-channel stack: its 8 key bytes or 8 truncated predictions, minus the deltas d, clamped.
+__device__ __forceinline__ uint2 recon8_flat(const float4* __restrict__ pred, const uint2* __restrict__ key, bool is_key, size_t i,
+                                             const short8 d) {
+    int base[8];
+    if (is_key) {
+        uint2 k = key[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            base[j] = (k.x >> (8 * j)) & 0xff;
+            base[4 + j] = (k.y >> (8 * j)) & 0xff;
+        }
+    } else {
+        float4 p0 = pred[2 * i], p1 = pred[2 * i + 1];
+        base[0] = (int)(p0.x * 255.0f); base[1] = (int)(p0.y * 255.0f);
+        base[2] = (int)(p0.z * 255.0f); base[3] = (int)(p0.w * 255.0f);
+        base[4] = (int)(p1.x * 255.0f); base[5] = (int)(p1.y * 255.0f);
+        base[6] = (int)(p1.z * 255.0f); base[7] = (int)(p1.w * 255.0f);
+    }
+    unsigned lo = 0, hi = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int a = base[j] - (int)d[j], b = base[4 + j] - (int)d[4 + j];
+        a = a < 0 ? 0 : (a > 255 ? 255 : a);
+        b = b < 0 ? 0 : (b > 255 ? 255 : b);
+        lo |= (unsigned)a << (8 * j);
+        hi |= (unsigned)b << (8 * j);
+    }
+    return make_uint2(lo, hi);
+}
+
 // Fast path: unpadded frames, 8 elements per lane (2x16 B pred, 16 B diff, 8 B key, 8 B out).
 __global__ __launch_bounds__(256) void k_recon_flat(const float4* __restrict__ pred, const uint2* __restrict__ key,
                                                     const uint8_t* __restrict__ key_mask, const short8* __restrict__ diff,
                                                     size_t n8, unsigned frame_elems8, uint2* __restrict__ out) {
     size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
-        short8 d = diff[i];
-        int base[8];
-        if (key_mask[i / frame_elems8]) {
-            uint2 k = key[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                base[j] = (k.x >> (8 * j)) & 0xff;
-                base[4 + j] = (k.y >> (8 * j)) & 0xff;
-            }
-        } else {
-            float4 p0 = pred[2 * i], p1 = pred[2 * i + 1];
-            base[0] = (int)(p0.x * 255.0f); base[1] = (int)(p0.y * 255.0f);
-            base[2] = (int)(p0.z * 255.0f); base[3] = (int)(p0.w * 255.0f);
-            base[4] = (int)(p1.x * 255.0f); base[5] = (int)(p1.y * 255.0f);
-            base[6] = (int)(p1.z * 255.0f); base[7] = (int)(p1.w * 255.0f);
-        }
-        unsigned lo = 0, hi = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int a = base[j] - (int)d[j], b = base[4 + j] - (int)d[4 + j];
-            a = a < 0 ? 0 : (a > 255 ? 255 : a);
-            b = b < 0 ? 0 : (b > 255 ? 255 : b);
-            lo |= (unsigned)a << (8 * j);
-            hi |= (unsigned)b << (8 * j);
-        }
-        out[i] = make_uint2(lo, hi);
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride)
+        out[i] = recon8_flat(pred, key, key_mask[i / frame_elems8] != 0, i, diff[i]);
 }
 
 // ---------------------------------------------------------- reconstruct from a one-channel payload (gray job)
@@ -3103,42 +3222,47 @@ __global__ __launch_bounds__(256) void k_recon_gray(const float* __restrict__ pr
     }
 }
 
+// Pixel group i (8 pixels) of an unpadded stack under a one-channel payload: channel 0's key byte or truncated prediction minus
+// the delta, clamped, to all three channels.
+__device__ __forceinline__ void recon8_gray(const float4* __restrict__ pred, const uint2* __restrict__ key, bool is_key, size_t i,
+                                            const short8 d, uint2* __restrict__ out) {
+    int base[8];
+    if (is_key) {
+        const uint2 k0 = key[3 * i], k1 = key[3 * i + 1], k2 = key[3 * i + 2];
+        // channel 0 of pixel k is byte 3 k of the 24
+        base[0] = k0.x & 0xff;          base[1] = k0.x >> 24;
+        base[2] = (k0.y >> 16) & 0xff;  base[3] = (k1.x >> 8) & 0xff;
+        base[4] = k1.y & 0xff;          base[5] = k1.y >> 24;
+        base[6] = (k2.x >> 16) & 0xff;  base[7] = (k2.y >> 8) & 0xff;
+    } else {
+        // channel 0 of pixel k is float 3 k of the 24
+        const float4 p0 = pred[6 * i], p1 = pred[6 * i + 1], p2 = pred[6 * i + 2], p3 = pred[6 * i + 3], p4 = pred[6 * i + 4],
+                     p5 = pred[6 * i + 5];
+        base[0] = (int)(p0.x * 255.0f); base[1] = (int)(p0.w * 255.0f);
+        base[2] = (int)(p1.z * 255.0f); base[3] = (int)(p2.y * 255.0f);
+        base[4] = (int)(p3.x * 255.0f); base[5] = (int)(p3.w * 255.0f);
+        base[6] = (int)(p4.z * 255.0f); base[7] = (int)(p5.y * 255.0f);
+    }
+    unsigned v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int a = base[j] - (int)d[j];
+        v[j] = (unsigned)(a < 0 ? 0 : (a > 255 ? 255 : a));
+    }
+    // bytes v0 v0 v0 v1 | v1 v1 v2 v2 | v2 v3 v3 v3, twice
+    out[3 * i] = make_uint2(v[0] * 0x010101u | (v[1] << 24), v[1] * 0x0101u | (v[2] * 0x0101u << 16));
+    out[3 * i + 1] = make_uint2(v[2] | (v[3] * 0x010101u << 8), v[4] * 0x010101u | (v[5] << 24));
+    out[3 * i + 2] = make_uint2(v[5] * 0x0101u | (v[6] * 0x0101u << 16), v[6] | (v[7] * 0x010101u << 8));
+}
+
 // Flat form: unpadded frames of a multiple of 8 pixels, 8 pixels per lane: 16 B of deltas, the 96 B of prediction (or the
 // 24 B of key bytes) that hold their channel 0, 24 B out as three aligned 8-byte stores.
 __global__ __launch_bounds__(256) void k_recon_gray_flat(const float4* __restrict__ pred, const uint2* __restrict__ key,
                                                          const uint8_t* __restrict__ key_mask, const short8* __restrict__ diff,
                                                          size_t n8, unsigned frame_pix8, uint2* __restrict__ out) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
-        const short8 d = diff[i];
-        int base[8];
-        if (key_mask[i / frame_pix8]) {
-            const uint2 k0 = key[3 * i], k1 = key[3 * i + 1], k2 = key[3 * i + 2];
-            // channel 0 of pixel k is byte 3 k of the 24
-            base[0] = k0.x & 0xff;          base[1] = k0.x >> 24;
-            base[2] = (k0.y >> 16) & 0xff;  base[3] = (k1.x >> 8) & 0xff;
-            base[4] = k1.y & 0xff;          base[5] = k1.y >> 24;
-            base[6] = (k2.x >> 16) & 0xff;  base[7] = (k2.y >> 8) & 0xff;
-        } else {
-            // channel 0 of pixel k is float 3 k of the 24
-            const float4 p0 = pred[6 * i], p1 = pred[6 * i + 1], p2 = pred[6 * i + 2], p3 = pred[6 * i + 3], p4 = pred[6 * i + 4],
-                         p5 = pred[6 * i + 5];
-            base[0] = (int)(p0.x * 255.0f); base[1] = (int)(p0.w * 255.0f);
-            base[2] = (int)(p1.z * 255.0f); base[3] = (int)(p2.y * 255.0f);
-            base[4] = (int)(p3.x * 255.0f); base[5] = (int)(p3.w * 255.0f);
-            base[6] = (int)(p4.z * 255.0f); base[7] = (int)(p5.y * 255.0f);
-        }
-        unsigned v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int a = base[j] - (int)d[j];
-            v[j] = (unsigned)(a < 0 ? 0 : (a > 255 ? 255 : a));
-        }
-        // bytes v0 v0 v0 v1 | v1 v1 v2 v2 | v2 v3 v3 v3, twice
-        out[3 * i] = make_uint2(v[0] * 0x010101u | (v[1] << 24), v[1] * 0x0101u | (v[2] * 0x0101u << 16));
-        out[3 * i + 1] = make_uint2(v[2] | (v[3] * 0x010101u << 8), v[4] * 0x010101u | (v[5] << 24));
-        out[3 * i + 2] = make_uint2(v[5] * 0x0101u | (v[6] * 0x0101u << 16), v[6] | (v[7] * 0x010101u << 8));
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride)
+        recon8_gray(pred, key, key_mask[i / frame_pix8] != 0, i, diff[i], out);
 }
 
 // k_recon* over a diff stack of three elements per pixel, k_recon_gray* over one (channels = 1): the flat form where the frames
@@ -3164,24 +3288,263 @@ int tzk_reconstruct(tz_ctx* ctx, int channels, const float* pred, const uint8_t*
     return TZ_OK;
 }
 
+// ------------------------------------------------- inverse of the 2-D spatial delta (TZ-SD2, tz_set_delta_plane(1))
+// q = wrap9(S), S[y, x] the inclusive 2-D prefix sum of -sd over the frame and channel (tezip_amd/sdelta.py decode_plane).  The
+// sum is separable -- down the columns, then along the rows -- and sums are taken mod 2^16 (512 divides 65536).  Two launches;
+// neither waits on another workgroup: no status words, no polling.
+// Pass one, k_unplane_cols<LUT, V>: a frame is H rows of W*C independent columns.  Lanes lie along the row (V columns each:
+// 4 as one 8-byte access where a row is whole 8-byte groups on 8-byte boundaries, else 1), the decoder LUT is applied on load,
+// the value negated, and each lane walks down with running sums, several rows' loads in flight.  The four waves of a workgroup
+// take four row bands of one column strip (one band while H <= UNPLANE_BAND_ROWS): they sum their bands, exchange the sums
+// through LDS behind ONE barrier, then walk again and store.
+// Pass two, k_unplane_rows<C>: a wave owns whole rows and walks one in wave-tiles of UNPLANE_ROW_TILE elements: per-thread sums
+// by class mod C (relative to the thread's first element, rotated into row classes by rot3 as k_scan3p does), a wave shuffle
+// scan, a running row carry in registers; then wrap9.  A lane reads its 8 elements before it writes them and a row's tiles are
+// walked in order by one wave, so the pass runs IN PLACE on pass one's output.  RECON (the decoder's tail on unpadded frames whose
+// rows are whole 16-byte groups on 16-byte boundaries): the lane goes straight on to decompress.py:252-256,269 with its 8 deltas
+// -- the group's key bytes or truncated predictions, clamp, uint8 out; with C = 1 the sample goes to all three channels
+// (recon8_flat / recon8_gray, the bodies of k_recon_flat / k_recon_gray_flat) -- and no delta stack is written.
+// Pass one carries the LUT because it is the pass that reads the payload; pass two carries wrap9 and RECON because it is the last
+// one, and because it leaves the frame in row order, which is the order of pred, key and out: rows last, a lane's 8 deltas are
+// 8 neighbouring bytes of the frame, columns last they would be 8 rows apart.
+static constexpr int UNPLANE_BAND_ROWS = 32;                  // fewest rows of a band of k_unplane_cols
+static constexpr int UNPLANE_ROW_EPT = 8;                     // elements per lane of k_unplane_rows
+static constexpr int UNPLANE_ROW_TILE = 64 * UNPLANE_ROW_EPT; // elements of its wave-tile
+
+template <bool LUT>
+__device__ __forceinline__ unsigned unplane_sym(int x, const int16_t* sl, int post_offset) {
+    if (LUT) return (unsigned)((x >= 0 && x <= TZ_NBINS) ? (int)sl[x] : (int)(short)(post_offset ? TZ_OFFSET - x : x));
+    return (unsigned)x;
+}
+
+template <int V>
+__device__ __forceinline__ void unplane_load(const int16_t* p, int* x) {
+    if (V == 4) {
+        const uint2 w = *(const uint2*)p;
+        x[0] = (int)(short)(w.x & 0xFFFFu);
+        x[1] = (int)w.x >> 16;
+        x[2] = (int)(short)(w.y & 0xFFFFu);
+        x[3] = (int)w.y >> 16;
+    } else {
+        x[0] = p[0];
+    }
+}
+
+template <bool LUT, int V>
+__global__ __launch_bounds__(256) void k_unplane_cols(const int16_t* __restrict__ in, int nframes, int H, int RW, int band_rows,
+                                                      const int16_t* __restrict__ lut, int post_offset, int16_t* __restrict__ out) {
+    __shared__ int16_t sl[LUT ? TZ_NBINS + 1 : 1];
+    __shared__ unsigned bsum[2][4][64 * V];
+    if (LUT) {
+        for (int k = threadIdx.x; k < TZ_NBINS + 1; k += 256) sl[k] = lut[k];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int col = (blockIdx.x * 64 + lane) * V;
+    const bool active = col < RW;   // (V == 4: RW is a multiple of 4, so are the lane's columns)
+    const bool multi = band_rows < H;   // uniform for the launch
+    const int y0 = multi ? min(H, wv * band_rows) : (wv == 0 ? 0 : H), y1 = multi ? min(H, y0 + band_rows) : (wv == 0 ? H : H);
+    int it = 0;
+    for (int f = blockIdx.y; f < nframes; f += gridDim.y, ++it) {
+        const size_t fbase = (size_t)f * H * RW + col;
+        unsigned acc[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k] = 0u;
+        if (multi) {
+            if (active && wv < 3) {   // (nobody needs the last band's sum)
+#pragma unroll 4
+                for (int y = y0; y < y1; ++y) {
+                    int x[V];
+                    unplane_load<V>(in + fbase + (size_t)y * RW, x);
+#pragma unroll
+                    for (int k = 0; k < V; ++k) acc[k] -= unplane_sym<LUT>(x[k], sl, post_offset);
+                }
+            }
+            unsigned(*bs)[64 * V] = bsum[it & 1];   // (two sets: the next frame's sums never meet a late reader of this one's)
+#pragma unroll
+            for (int k = 0; k < V; ++k) bs[wv][lane * V + k] = acc[k];
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                acc[k] = 0u;
+                for (int w = 0; w < 3; ++w)
+                    if (w < wv) acc[k] += bs[w][lane * V + k];
+            }
+        }
+        if (!active) continue;
+#pragma unroll 4
+        for (int y = y0; y < y1; ++y) {
+            int x[V];
+            unplane_load<V>(in + fbase + (size_t)y * RW, x);
+#pragma unroll
+            for (int k = 0; k < V; ++k) acc[k] -= unplane_sym<LUT>(x[k], sl, post_offset);
+            int16_t* o = out + fbase + (size_t)y * RW;
+            if (V == 4) *(uint2*)o = make_uint2((acc[0] & 0xFFFFu) | (acc[1] << 16), (acc[2] & 0xFFFFu) | (acc[3] << 16));
+            else o[0] = (int16_t)(uint16_t)acc[0];
+        }
+    }
+}
+
+__device__ __forceinline__ short unplane_wrap9(unsigned s) { return (short)((int)((s + 256u) & 511u) - 256); }
+
+struct PlaneRecon {
+    const float4* pred;       // [frame][H*W*3] floats
+    const uint8_t* key;       // key-frame stack (bytes of non-key slots unused)
+    const uint8_t* key_mask;  // [frame]
+    int H;                    // rows of a frame
+    uint8_t* out;
+};
+
+// in and out may be the same buffer (RECON: out is not written, vec is set and RW is a multiple of 8)
+template <int C, bool RECON>
+__global__ __launch_bounds__(256) void k_unplane_rows(const int16_t* in, size_t nrows, int RW, int vec, int16_t* out, const PlaneRecon rc) {
+    const int lane = threadIdx.x & 63;
+    const size_t nwaves = (size_t)gridDim.x * 4;
+    for (size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < nrows; row += nwaves) {
+        const int16_t* src = in + row * (size_t)RW;
+        int16_t* dst = out + row * (size_t)RW;
+        unsigned run[3] = {0u, 0u, 0u};   // per row class: the sum of everything in front of the next tile
+        for (int tb = 0; tb < RW; tb += UNPLANE_ROW_TILE) {   // uniform for the wave
+            const int base = tb + lane * UNPLANE_ROW_EPT;
+            const bool whole = vec && base + UNPLANE_ROW_EPT <= RW;
+            int v[UNPLANE_ROW_EPT];
+            if (whole) {
+                const short8 a = *(const short8*)(src + base);
+#pragma unroll
+                for (int k = 0; k < UNPLANE_ROW_EPT; ++k) v[k] = a[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < UNPLANE_ROW_EPT; ++k) v[k] = base + k < RW ? (int)src[base + k] : 0;
+            }
+            short res[UNPLANE_ROW_EPT];
+            if (C == 3) {
+                unsigned a[3] = {0u, 0u, 0u}, q0, q1, q2;
+#pragma unroll
+                for (int k = 0; k < UNPLANE_ROW_EPT; ++k) a[k % 3] += (unsigned)v[k];
+                const unsigned r = (unsigned)(base % 3), rinv = (3u - r) % 3u;
+                rot3(r, a[0], a[1], a[2], q0, q1, q2);
+                const unsigned i0 = wave_scan_incl(q0), i1 = wave_scan_incl(q1), i2 = wave_scan_incl(q2);
+                unsigned p[3];   // by relative class: the sums in front of the thread's elements
+                rot3(rinv, i0 - q0 + run[0], i1 - q1 + run[1], i2 - q2 + run[2], p[0], p[1], p[2]);
+                run[0] += __shfl(i0, 63);
+                run[1] += __shfl(i1, 63);
+                run[2] += __shfl(i2, 63);
+#pragma unroll
+                for (int k = 0; k < UNPLANE_ROW_EPT; ++k) {
+                    p[k % 3] += (unsigned)v[k];
+                    res[k] = unplane_wrap9(p[k % 3]);
+                }
+            } else {
+                unsigned q = 0u;
+#pragma unroll
+                for (int k = 0; k < UNPLANE_ROW_EPT; ++k) q += (unsigned)v[k];
+                const unsigned incl = wave_scan_incl(q);
+                unsigned pre = incl - q + run[0];
+                run[0] += __shfl(incl, 63);
+#pragma unroll
+                for (int k = 0; k < UNPLANE_ROW_EPT; ++k) {
+                    pre += (unsigned)v[k];
+                    res[k] = unplane_wrap9(pre);
+                }
+            }
+            if (RECON) {
+                if (whole) {   // (a lane's group lies in the row or behind it)
+                    short8 d;
+#pragma unroll
+                    for (int k = 0; k < UNPLANE_ROW_EPT; ++k) d[k] = res[k];
+                    const size_t i = (row * (size_t)RW + (size_t)base) / 8;   // the group (C = 1: the pixel group) in the stack
+                    const bool is_key = rc.key_mask[row / (size_t)rc.H] != 0;
+                    if (C == 3) ((uint2*)rc.out)[i] = recon8_flat(rc.pred, (const uint2*)rc.key, is_key, i, d);
+                    else recon8_gray(rc.pred, (const uint2*)rc.key, is_key, i, d, (uint2*)rc.out);
+                }
+            } else if (whole) {
+                short8 o;
+#pragma unroll
+                for (int k = 0; k < UNPLANE_ROW_EPT; ++k) o[k] = res[k];
+                *(short8*)(dst + base) = o;
+            } else {
+#pragma unroll
+                for (int k = 0; k < UNPLANE_ROW_EPT; ++k)
+                    if (base + k < RW) dst[base + k] = res[k];
+            }
+        }
+    }
+}
+
+// nframes x H x W x C elements at `in` -> the delta stack at `out` (any 2-byte alignment; h_lut2112 NULL = symbols as stored).
+// recon (may be NULL; the caller has checked k_unplane_rows<.., true>'s conditions): `out` is scratch for pass one, and pass two
+// writes the frames to recon->out.
+static int unplane_launch(tz_ctx* ctx, const int16_t* in, int nframes, int H, int W, int C, const int16_t* h_lut2112, int post_offset,
+                          int16_t* out, const PlaneRecon* recon) {
+    if (nframes < 0 || H < 1 || W < 1 || (C != 1 && C != 3) || (size_t)W * C > 0x3FFFFFFFull)
+        return tz_fail(ctx, TZ_ERR_INVALID, "spatial_undelta_plane: %d frames of %d x %d x %d", nframes, H, W, C);
+    if (nframes == 0) return TZ_OK;
+    const uintptr_t both = (uintptr_t)in | (uintptr_t)out;
+    if (both & 1) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_undelta_plane buffers must be 2-byte aligned");
+    const int RW = W * C;
+    void* d_lut;
+    TZ_TRY(upload_dec_lut(ctx, h_lut2112, &d_lut));
+    tz_prof_scope ps(ctx, TZP_SCAN);
+    const int band_rows = std::max(UNPLANE_BAND_ROWS, (H + 3) / 4);
+    const bool v4 = RW % 4 == 0 && (both & 7) == 0;
+    const dim3 grid((unsigned)((RW + (v4 ? 256 : 64) - 1) / (v4 ? 256 : 64)), (unsigned)std::min(nframes, 65535));
+#define TZ_UNPLANE_COLS(L, V) \
+    hipLaunchKernelGGL((k_unplane_cols<L, V>), grid, dim3(256), 0, ctx->stream, in, nframes, H, RW, band_rows, (const int16_t*)d_lut, post_offset, out)
+    if (h_lut2112 && v4) TZ_UNPLANE_COLS(true, 4);
+    else if (h_lut2112) TZ_UNPLANE_COLS(true, 1);
+    else if (v4) TZ_UNPLANE_COLS(false, 4);
+    else TZ_UNPLANE_COLS(false, 1);
+#undef TZ_UNPLANE_COLS
+    TZ_HIP(ctx, hipGetLastError());
+    const size_t nrows = (size_t)nframes * H;
+    const int vec = RW % 8 == 0 && ((uintptr_t)out & 15) == 0;
+    const dim3 rgrid((unsigned)std::min<size_t>((nrows + 3) / 4, (size_t)kCUs * kBlocksPerCU));
+    const PlaneRecon rc = recon ? *recon : PlaneRecon{};
+#define TZ_UNPLANE_ROWS(CV, R) hipLaunchKernelGGL((k_unplane_rows<CV, R>), rgrid, dim3(256), 0, ctx->stream, (const int16_t*)out, nrows, RW, vec, out, rc)
+    if (recon && !vec) return tz_fail(ctx, TZ_ERR_INVALID, "spatial_undelta_plane: the fused reconstruct needs rows of whole 16-byte groups");
+    if (C == 3 && recon) TZ_UNPLANE_ROWS(3, true);
+    else if (C == 3) TZ_UNPLANE_ROWS(3, false);
+    else if (recon) TZ_UNPLANE_ROWS(1, true);
+    else TZ_UNPLANE_ROWS(1, false);
+#undef TZ_UNPLANE_ROWS
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+int tzk_unplane(tz_ctx* ctx, const int16_t* in, int nframes, int H, int W, int C, const int16_t* h_lut2112, int post_offset, int16_t* out) {
+    return unplane_launch(ctx, in, nframes, H, W, C, h_lut2112, post_offset, out, nullptr);
+}
+
 // the decoder's tail over frames [first, first + nframes) of a stream (tz_decode, tz_decode_range, tz_encode_quality): `in`,
 // pred, key and d_key_mask point at the range's first frame and `carry` holds the layout.stride decoded elements in front of it (NULL
 // at the stream start).  One launch (inverse remap when there is a table, inverse spatial delta, reconstruct) where the
 // layout allows it: unpadded frames of a multiple of 16 elements, 16-byte aligned buffers, and no TEZIP_DECODE_UNFUSED.
-// Else, and for the gray and the channel-stride layout always, a scan into a temporary and k_recon* / k_recon_gray*.
+// Else, and for the gray and the channel-stride layout always, a scan into a temporary and k_recon* / k_recon_gray*.  The plane
+// layout (TZ-SD2): k_unplane_cols into a temporary, then k_unplane_rows -- with the reconstruct fused where the frames allow it.
 int tzk_decode_tail(tz_ctx* ctx, tz_layout layout, const int16_t* in, const int16_t* h_lut2112, int post_offset, const int16_t* carry,
                     const float* pred, const uint8_t* key, const uint8_t* d_key_mask, int nframes, int H, int W, int Hp, int Wp,
                     uint8_t* out) {
     const size_t fe = tz_frame_elems(layout, H, W), n = (size_t)nframes * fe;
     if (n == 0) return TZ_OK;
-    if (layout.channels == 3 && layout.stride == 1 && H == Hp && W == Wp && fe % SCAN_EPT == 0 && key && !ctx->decode_unfused &&
+    if (layout.channels == 3 && layout.stride == 1 && !layout.plane_h && H == Hp && W == Wp && fe % SCAN_EPT == 0 && key && !ctx->decode_unfused &&
         ((((uintptr_t)in | (uintptr_t)pred | (uintptr_t)key | (uintptr_t)out) & 15) == 0)) {
         const ScanRecon rc = {(const float4*)pred, key, d_key_mask, (unsigned long long)fe, out};
         return scan_launch(ctx, in, n, carry != nullptr, carry ? carry[0] : (int16_t)0, h_lut2112, post_offset, nullptr, &rc);
     }
     void* d_diff;
     TZ_TRY(tz_pool_alloc(ctx, n * 2, &d_diff));
-    TZ_TRY(tzk_undelta(ctx, layout.stride, in, n, carry, h_lut2112, post_offset, (int16_t*)d_diff));
+    if (layout.plane_h) {   // TZ-SD2: every frame on its own, no carry
+        if (carry) return tz_fail(ctx, TZ_ERR_INVALID, "the plane payload takes no carry");
+        // unpadded frames whose rows are whole 16-byte groups, aligned buffers, no TEZIP_DECODE_UNFUSED: pass two reconstructs
+        if (H == Hp && W == Wp && ((size_t)W * layout.channels) % 8 == 0 && key && !ctx->decode_unfused &&
+            ((((uintptr_t)d_diff | (uintptr_t)pred) & 15) | (((uintptr_t)key | (uintptr_t)out) & 7)) == 0) {
+            const PlaneRecon rc = {(const float4*)pred, key, d_key_mask, H, out};
+            return unplane_launch(ctx, in, nframes, H, W, layout.channels, h_lut2112, post_offset, (int16_t*)d_diff, &rc);
+        }
+        TZ_TRY(tzk_unplane(ctx, in, nframes, H, W, layout.channels, h_lut2112, post_offset, (int16_t*)d_diff));
+    } else {
+        TZ_TRY(tzk_undelta(ctx, layout.stride, in, n, carry, h_lut2112, post_offset, (int16_t*)d_diff));
+    }
     return tzk_reconstruct(ctx, layout.channels, pred, key, d_key_mask, (const int16_t*)d_diff, nframes, H, W, Hp, Wp, out);
 }
 

@@ -134,6 +134,7 @@ struct tz_ctx {
     int payload_channels = 3;               // tz_set_payload_channels: 1 = the payload of a gray job holds channel 0 alone
     std::vector<double> frame_bounds;       // tz_set_frame_bounds: one abs tolerance per frame of the encoder rollout (empty: none)
     int delta_stride_mode = 0;              // tz_set_delta_stride: 1 = the spatial delta of the payload runs at the channel stride
+    int delta_plane = 0;                    // tz_set_delta_plane: 1 = the spatial delta of the payload is the 2-D one, TZ-SD2
     int quantiser = 0;                      // tz_set_quantiser: 0 = the reference's greedy walk, 1 = the lattice quantiser TZ-QL1
     unsigned long long* d_scan3_status = nullptr;   // strided inverse scan (k_scan3p): one 64-bit word per block, own epochs
     unsigned scan3_epoch = 0;
@@ -365,10 +366,14 @@ int tzk_quant_frames(tz_ctx*, const uint8_t* orig, int16_t* diff, const tz_quant
                      int H, int W, const double* h_bounds, bool* done);
 // The layout of the payload, stated once per layer: elements per pixel, and how far in front the element
 // lies that the spatial delta subtracts.  flat {3, 1} is the reference's; gray {1, 1} stores channel 0 alone
-// (tz_set_payload_channels(1)); channel stride {3, 3} takes the same channel of the pixel in front (tz_set_delta_stride(1)).
+// (tz_set_payload_channels(1)); channel stride {3, 3} takes the same channel of the pixel in front (tz_set_delta_stride(1));
+// plane {3 or 1, 1, H, W} predicts from the pixel in front and the row above within a frame (tz_set_delta_plane(1)).
 // A carry is `stride` HOST elements, the ones in front of the first element, or NULL at the stream start.
+// plane_h, plane_w (0: not plane): the frame's rows and columns when the spatial delta is the 2-D one, TZ-SD2
+// (tz_set_delta_plane(1)); stride is then 1 and no carry exists -- every frame is coded on its own.
 struct tz_layout {
     int channels, stride;
+    int plane_h = 0, plane_w = 0;
 };
 static inline size_t tz_frame_elems(tz_layout l, int H, int W) { return (size_t)H * W * l.channels; }   // payload elements of a frame
 // in -> n elements at out.  flat, channel stride: in holds n elements; gray: the interleaved three-channel stack of n pixels, of
@@ -389,6 +394,11 @@ int tzk_lattice_sd_fused(tz_ctx*, tz_layout, const float* pred, const uint8_t* o
                          int nframes, int H, int W, int Hp, int Wp, int mode, double b0, double b1, const double* h_bounds,
                          int apply_offset, int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done);
 bool tz_lattice_is_identity(int mode, double b0, double b1);   // the worst-case tolerance of the job is below 1: q == d everywhere
+// TZ-SD2 (k_sdelta_plane; k_unplane_cols + k_unplane_rows) on nframes x H x W x C elements at any 2-byte alignment.  in of
+// tzk_sdelta_plane holds cin elements per pixel: cin == C, or 3 with C = 1 (channel 0 is taken).  tzk_unplane may run in place.
+int tzk_sdelta_plane(tz_ctx*, const int16_t* in, int cin, int nframes, int H, int W, int C, int apply_offset, int16_t* out,
+                     unsigned long long* d_hist);
+int tzk_unplane(tz_ctx*, const int16_t* in, int nframes, int H, int W, int C, const int16_t* h_lut2112, int post_offset, int16_t* out);
 int tzk_lut(tz_ctx*, const int16_t* in, size_t n, const int16_t* h_lut2112, int post_offset, int16_t* out);
 // forward: int16[n] -> low-byte plane | high-byte plane (2n bytes); inverse: planes (passed as `in`) -> int16[n] at `out`
 int tzk_shuffle(tz_ctx*, const int16_t* in, size_t n, uint8_t* out, int inverse);

@@ -39,10 +39,13 @@ def check_stream(shape, warm_up, payload_len, key_len):
     # C: the channels the PAYLOAD stores per pixel -- 3, or 1 for this build's opt-in payload of a gray job (--gray,
     # tezip_amd/graypayload.py); the frames and key_frame.dat have three channels either way
     # one: 1 in the reference, SHUFFLE_MARK for byte planes; sdelta.MARK / MARK_SHUFFLE (4 / 5) say the same of a payload whose
-    # spatial delta ran at the channel stride (--sdelta channel, tezip_amd/sdelta.py), which has three channels.  3 means nothing
-    if one not in (1, SHUFFLE_MARK) + sdelta.MARKS or C not in (1, 3) or (one in sdelta.MARKS and C != 3) or nt < 1 or H < 1 or W < 1:
-        raise ValueError("entropy.dat: unsupported stack shape %r (expected (1, nt, H, W, 3), (1, nt, H, W, 1) for a gray job or "
-                         "(4, nt, H, W, 3) for a channel-stride payload)" % (tuple(shape),))
+    # spatial delta ran at the channel stride (--sdelta channel, tezip_amd/sdelta.py), which has three channels;
+    # sdelta.MARK_PLANE / MARK_PLANE_SHUFFLE (8 / 9) of a payload under the 2-D spatial delta TZ-SD2 (--sdelta plane), which has
+    # three channels or one.  3, 6 and 7 mean nothing
+    if (one not in (1, SHUFFLE_MARK) + sdelta.MARKS + sdelta.PLANE_MARKS or C not in (1, 3) or (one in sdelta.MARKS and C != 3)
+            or nt < 1 or H < 1 or W < 1):
+        raise ValueError("entropy.dat: unsupported stack shape %r (expected (1, nt, H, W, 3), (1, nt, H, W, 1) for a gray job, "
+                         "(4, nt, H, W, 3) for a channel-stride payload or (8, nt, H, W, 3 or 1) for a plane payload)" % (tuple(shape),))
     n = nt * H * W * C
     if payload_len != n:
         raise ValueError("entropy.dat: payload holds %d elements, the trailer says %d (truncated or corrupt file)"
@@ -65,12 +68,21 @@ def check_channels(data_dir, C):
 def check_sdelta(data_dir, one):
     """The stride of the payload's spatial delta that entropy.dat's trailer states (mark 4 / 5: channel) against tezip_amd.json,
     which records "channel" and says nothing for flat.  The trailer is authoritative; a sidecar that contradicts it belongs to
-    another stream.  Returns the mode for tz_set_delta_stride."""
-    have = "channel" if sdelta.is_strided(one) else "flat"
+    another stream.  Marks 8 / 9 (plane, TZ-SD2) likewise against "plane".  Returns the mode for set_sdelta: 0 flat, 1 channel,
+    2 plane."""
+    have = sdelta.mode_of(one)
     want = sidecar.sdelta_of(sidecar.read(data_dir))
     if want is not None and want != have:
         raise ValueError("tezip_amd.json describes the payload's spatial delta as %s, entropy.dat's trailer as %s" % (want, have))
-    return 1 if have == "channel" else 0
+    return sdelta.MODES.index(have)
+
+
+def set_sdelta(ctx, mode):
+    """check_sdelta's mode on the context: tz_set_delta_stride for flat and channel, tz_set_delta_plane for plane."""
+    if mode == 2:
+        ctx.set_delta_plane(1)
+    else:
+        ctx.set_delta_stride(mode)
 
 
 TAIL_ELEMS = _lib.TZ_NBINS + 8  # the longest trailer: table (<= 2111 symbols) + T + shape(5) + warm_up
@@ -398,7 +410,7 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
                 rollout(nt, warm_up)
         check_channels(DATA_DIR, C)
         ctx.set_payload_channels(C)         # 1: the one-channel payload of a gray job; the frames keep three channels
-        ctx.set_delta_stride(check_sdelta(DATA_DIR, one))   # 1: the payload's spatial delta ran at the channel stride
+        set_sdelta(ctx, check_sdelta(DATA_DIR, one))   # 1: the payload's spatial delta ran at the channel stride, 2: plane
         if records is not None:
             check_records(records, nt, H, W)
         stages.mark("rollout (decoder)", ctx)
@@ -557,7 +569,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
         sys.exit(2)
     stride_mode = check_sdelta(DATA_DIR, shape[0])
     if stride_mode and job is not None:
-        print("ERROR: a channel-stride payload (--sdelta channel) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU")
+        print("ERROR: a %s payload (--sdelta %s) cannot be decoded by a sharded job (WORLD_SIZE > 1): run it on one GPU"
+              % (("channel-stride", "channel") if stride_mode == 1 else ("plane", "plane")))
         sys.exit(2)
     key_frames = None if keys is not None else np.frombuffer(key_bytes, dtype=np.uint8).reshape(nt, H, W, 3)
     hp, wp = padding_shape(H, W)
@@ -584,7 +597,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
         if contract:
             ctx.set_contract(contract)
         ctx.set_payload_channels(C)
-        ctx.set_delta_stride(stride_mode)
+        set_sdelta(ctx, stride_mode)
         if sdelta.is_shuffled(shape[0]):  # this build's opt-in byte planes -> the int16 payload
             payload = ctx.byte_unshuffle(np.ascontiguousarray(payload).view(np.uint8))
         if job:

@@ -14,6 +14,19 @@ neighbour of a sample is another CHANNEL of the same pixel.  Here the neighbour 
             for a payload of three channels: with one channel (--gray on an all-gray job) S = 1, which IS the flat delta,
             and the stream is the --gray stream
 
+The 2-D spatial delta, definition TZ-SD2 (`-c --sdelta plane`, tz_set_delta_plane(1); kernels k_sdelta_plane, k_unplane_cols,
+k_unplane_rows), is stated here too.  q[f, y, x, c] is the quantised delta stack, values in [-255, 255], C the payload's
+channels (3, or 1 under --gray on an all-gray job); per frame and channel, every neighbour outside the frame taken as 0:
+
+  encode    sd = wrap9(q[y, x-1] + q[y-1, x] - q[y-1, x-1] - q[y, x]), wrap9(v) = ((v + 256) mod 512) - 256 in [-256, 255];
+            then 1600 - sd in [1345, 1856] (512 symbols: TZ_NBINS and every coder's alphabet hold) and the rank as above
+  decode    q = wrap9(S), S the inclusive 2-D prefix sum of -sd over the frame and channel (mod 2^16 suffices: 512 | 65536)
+  trailer   mark = 8 (MARK_PLANE), or 9 (MARK_PLANE_SHUFFLE) with byte planes; the last entry of the shape may be 3 or 1 -- on
+            one channel plane is NOT the flat delta, so a --gray plane stream is marked.  3, 6 and 7 stay refused
+  example   the 2 x 2 one-channel frame [[255, -255], [-255, 255]] -> sd [[-255, -2], [-2, 4]], symbols [[1855, 1602], [1602, 1596]]
+
+Every frame is coded on its own, so a range decode needs no carry.
+
 Only the lossless back half of the coder changes: a job decodes to exactly the images it decodes to without the flag.
 
   python -m tezip_amd.sdelta FILE.npy [STRIDE]    sizes of an int16 array under the flat and the strided delta (zstd-9)
@@ -24,10 +37,15 @@ OFFSET = 1600      # compress.py:348
 MARK = 4           # first entry of the trailer's stack shape: channel-stride payload
 MARK_SHUFFLE = 5   # ... stored as byte planes (--shuffle)
 MARKS = (MARK, MARK_SHUFFLE)
-MODES = ("flat", "channel")
+MARK_PLANE = 8          # ... 2-D plane payload TZ-SD2 (encode_plane below); the last entry of the shape may be 3 or 1
+MARK_PLANE_SHUFFLE = 9  # ... stored as byte planes (--shuffle)
+PLANE_MARKS = (MARK_PLANE, MARK_PLANE_SHUFFLE)
+MODES = ("flat", "channel", "plane")
 
 
-def mark(shuffled):
+def mark(shuffled, plane=False):
+    if plane:
+        return MARK_PLANE_SHUFFLE if shuffled else MARK_PLANE
     return MARK_SHUFFLE if shuffled else MARK
 
 
@@ -36,9 +54,19 @@ def is_strided(one):
     return int(one) in MARKS
 
 
+def is_plane(one):
+    """Whether the first entry of a trailer's stack shape says the 2-D plane delta TZ-SD2."""
+    return int(one) in PLANE_MARKS
+
+
 def is_shuffled(one):
-    """Whether the first entry of a trailer's stack shape says byte planes (2: flat, 5: channel stride)."""
-    return int(one) in (2, MARK_SHUFFLE)
+    """Whether the first entry of a trailer's stack shape says byte planes (2: flat, 5: channel stride, 9: plane)."""
+    return int(one) in (2, MARK_SHUFFLE, MARK_PLANE_SHUFFLE)
+
+
+def mode_of(one):
+    """The --sdelta mode the first entry of a trailer's stack shape states."""
+    return "plane" if is_plane(one) else ("channel" if is_strided(one) else "flat")
 
 
 def _carry(carry, stride):
@@ -89,6 +117,42 @@ def carry_of(stack, n0, stride):
     return np.asarray(stack, np.int16).reshape(-1)[n0 - stride:n0].copy()
 
 
+def wrap9(v):
+    """((v + 256) mod 512) - 256, in [-256, 255]."""
+    return ((np.asarray(v, np.int64) + 256) % 512) - 256
+
+
+def encode_plane(stack4d, apply_offset):
+    """TZ-SD2: the (nt, H, W, C) int16 quantised delta stack q, values in [-255, 255] -> the flattened int16
+    sd = wrap9(q[y, x-1] + q[y-1, x] - q[y-1, x-1] - q[y, x]) per frame and channel, every neighbour outside the frame 0;
+    1600 - sd on top when apply_offset.  Every frame is coded on its own."""
+    q = np.asarray(stack4d, np.int16)
+    if q.ndim != 4:
+        raise ValueError("encode_plane takes the (nt, H, W, C) stack, not %d dimensions" % q.ndim)
+    q = q.astype(np.int64)
+    if q.size and (q.min() < -255 or q.max() > 255):
+        raise ValueError("encode_plane takes deltas in [-255, 255]")
+    p = np.zeros_like(q)
+    p[:, :, 1:] += q[:, :, :-1]
+    p[:, 1:, :] += q[:, :-1, :]
+    p[:, 1:, 1:] -= q[:, :-1, :-1]
+    sd = wrap9(p - q)
+    if apply_offset:
+        sd = OFFSET - sd
+    return sd.astype(np.int16).reshape(-1)
+
+
+def decode_plane(delta, shape, apply_offset):
+    """The inverse of encode_plane -> the flattened stack of `shape` = (nt, H, W, C): q = wrap9(S), S the inclusive 2-D prefix
+    sum of -sd over the frame and channel (sums may be taken mod 2^16: 512 divides 65536)."""
+    nt, H, W, C = (int(v) for v in shape)
+    s = np.asarray(delta, np.int16).reshape(nt, H, W, C).astype(np.int64)
+    if apply_offset:
+        s = OFFSET - s
+    S = np.cumsum(np.cumsum(-s, axis=1), axis=2)
+    return wrap9(S).astype(np.int16).reshape(-1)
+
+
 def build_table(symbols):
     """compress.py:352-361: the symbols present, by count descending, equal counts by ascending symbol."""
     counts = np.bincount(np.asarray(symbols).reshape(-1).astype(np.int64))
@@ -110,20 +174,23 @@ def unmap(ranks, table):
     return t[np.asarray(ranks).astype(np.int64)]
 
 
-def payload_from_delta(delta_stack, entropy, stride=3):
-    """The (nt, H, W, C) int16 quantised delta stack -> (payload int16[nt*H*W*C], table | None)."""
+def payload_from_delta(delta_stack, entropy, stride=3, plane=False):
+    """The (nt, H, W, C) int16 quantised delta stack -> (payload int16[nt*H*W*C], table | None).  plane: TZ-SD2 in place of
+    the delta at `stride`."""
+    enc = (lambda off: encode_plane(delta_stack, off)) if plane else (lambda off: encode(delta_stack, stride, off))
     if not entropy:
-        return encode(delta_stack, stride, False), None
-    y = encode(delta_stack, stride, True)
+        return enc(False), None
+    y = enc(True)
     table = build_table(y)
     return remap(y, table), table
 
 
-def delta_from_payload(payload, table, stride=3):
-    """The inverse of payload_from_delta -> the flattened delta stack."""
+def delta_from_payload(payload, table, stride=3, plane_shape=None):
+    """The inverse of payload_from_delta -> the flattened delta stack.  plane_shape: the (nt, H, W, C) of a TZ-SD2 payload."""
+    dec = (lambda s, off: decode_plane(s, plane_shape, off)) if plane_shape is not None else (lambda s, off: decode(s, stride, off))
     if table is None:
-        return decode(payload, stride, False)
-    return decode(unmap(payload, table), stride, True)
+        return dec(payload, False)
+    return dec(unmap(payload, table), True)
 
 
 def main(argv=None):

@@ -16,8 +16,9 @@ are all gray, tezip_amd/graypayload.py); a job with the three-channel payload ha
 states the same and is authoritative: a sidecar that contradicts it is an error.
 
 `sdelta` = "channel" (optional): the spatial delta of the payload was taken at the channel stride (`-c --sdelta channel` on a
-three-channel payload, tezip_amd/sdelta.py); every other job has no such key.  The trailer of entropy.dat states the same (mark
-4 or 5) and is authoritative: a sidecar that contradicts it is an error.
+three-channel payload, tezip_amd/sdelta.py), or "plane": it is the 2-D one, TZ-SD2 (`-c --sdelta plane`, three channels or one);
+every other job has no such key.  The trailer of entropy.dat states the same (mark 4 or 5, 8 or 9) and is authoritative: a sidecar
+that contradicts it is an error.
 
 `quant` = "lattice" (optional): the job's deltas were quantised by the lattice quantiser TZ-QL1 (`-c --quant lattice`,
 tezip_amd/lattice.py); every other job has no such key.  Informational: the payload holds the quantised deltas themselves, a
@@ -70,8 +71,8 @@ def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta
         doc["stack"] = [int(v) for v in stack]
     if payload_channels == 1:   # a --gray job; every other job has no such key
         doc["payload_channels"] = 1
-    if sdelta == "channel":     # a --sdelta channel job with a three-channel payload; every other job has no such key
-        doc["sdelta"] = "channel"
+    if sdelta in ("channel", "plane"):   # a --sdelta channel job with a three-channel payload, or a --sdelta plane job; every
+        doc["sdelta"] = sdelta           # other job has no such key
     if quant == "lattice":      # a --quant lattice job; every other job has no such key
         doc["quant"] = "lattice"
     with open(os.path.join(out_dir, NAME), "w", encoding="UTF-8") as f:
@@ -118,13 +119,14 @@ def channels_of(doc):
 
 
 def sdelta_of(doc):
-    """The stride mode of the payload's spatial delta the sidecar states: "channel" for a --sdelta channel job
-    (tezip_amd/sdelta.py), "flat" for a sidecar without the key, None without a sidecar.  Anything else is a damaged file."""
+    """The mode of the payload's spatial delta the sidecar states: "channel" for a --sdelta channel job, "plane" for a --sdelta
+    plane job (tezip_amd/sdelta.py), "flat" for a sidecar without the key, None without a sidecar.  Anything else is a damaged
+    file."""
     if doc is None:
         return None
     mode = doc.get("sdelta", "flat")
-    if mode not in ("flat", "channel") or ("sdelta" in doc and mode != "channel"):
-        raise SidecarMismatch("%s states sdelta %r (\"channel\" is the only value ever written)" % (NAME, mode))
+    if mode not in ("flat", "channel", "plane") or ("sdelta" in doc and mode == "flat"):
+        raise SidecarMismatch("%s states sdelta %r (\"channel\" and \"plane\" are the only values ever written)" % (NAME, mode))
     return mode
 
 

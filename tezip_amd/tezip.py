@@ -73,8 +73,11 @@ FLAG_TABLE = (
     # not in the reference: with -c, the stride of the payload's spatial delta.  flat (also when the flag is absent) = the
     # reference's finding_difference, whose neighbour of a sample is another channel of the same pixel; channel = the same channel
     # of the pixel in front (tezip_amd/sdelta.py; smaller on colour jobs, LARGER on a gray source stored with three channels: use
-    # --gray there; the reference cannot read such a file, -u recognises it by the mark in its trailer)
-    (None, "--sdelta", dict(type=str, choices=("flat", "channel"), default=None, dest="sdelta")),
+    # --gray there; the reference cannot read such a file, -u recognises it by the mark in its trailer); plane = the 2-D predictor
+    # left + up - upleft per frame and channel, TZ-SD2 (smaller on smooth colour data lossless and under --quant lattice, LARGER
+    # under the greedy quantiser from abs 6 on and on sparse or gray sources: README; not with --sweep, --target-ratio or a
+    # sharded job)
+    (None, "--sdelta", dict(type=str, choices=("flat", "channel", "plane"), default=None, dest="sdelta")),
     # not in the reference: with -c, IN PLACE of -m and -b: the job is `-m abs -b E` with the E (a multiple of 0.5) that a
     # bisection over the GPU's exact error sums finds for a sequence PSNR of at least DB (definition TZ-TPSNR-1 in
     # tezip_amd/target.py: one rollout, at most 9 probes; a boundary, not necessarily the largest such bound).  Also writes
@@ -238,15 +241,17 @@ def check_gray_flag(arg):
 
 
 def check_sdelta_flag(arg):
-    """--sdelta is valid with -c only; `channel` needs one single-GPU job without --sweep.  Returns None, or the message of a
-    refusal."""
+    """--sdelta is valid with -c only; `channel` and `plane` need one single-GPU job without --sweep, `plane` one without
+    --target-ratio.  Returns None, or the message of a refusal."""
     mode = getattr(arg, "sdelta", None)
     if mode is None:
         return None
     if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
         return "--sdelta is valid with -c (--compress) only (-u recognises a channel-stride payload by itself)"
-    if mode == "channel" and getattr(arg, "sweep", None) is not None:
-        return "--sdelta channel cannot be combined with --sweep"
+    if mode in ("channel", "plane") and getattr(arg, "sweep", None) is not None:
+        return "--sdelta %s cannot be combined with --sweep" % mode
+    if mode == "plane" and getattr(arg, "target_ratio", None) is not None:
+        return compress.PLANE_NO_RATIO
     return compress.check_sdelta(mode, int(os.environ.get("WORLD_SIZE", "1")) > 1)
 
 
@@ -490,12 +495,12 @@ def _main(arg):
                             CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
                             DIGESTS=bool(getattr(arg, "digests", False)), GRAY=bool(getattr(arg, "gray", False)),
                             SDELTA=getattr(arg, "sdelta", None) or "flat", SSIM=bool(getattr(arg, "ssim", False)), TARGET_PSNR=db)
-    if getattr(arg, "sdelta", None) == "channel":   # (flat is the job without the flag: the calls below)
+    if getattr(arg, "sdelta", None) in ("channel", "plane"):   # (flat is the job without the flag: the calls below)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
                             CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
                             DIGESTS=bool(getattr(arg, "digests", False)), GRAY=bool(getattr(arg, "gray", False)),
-                            SSIM=bool(getattr(arg, "ssim", False)), SDELTA="channel")
+                            SSIM=bool(getattr(arg, "ssim", False)), SDELTA=arg.sdelta)
     if getattr(arg, "ssim", False):
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=True,
