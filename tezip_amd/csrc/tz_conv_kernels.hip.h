@@ -40,7 +40,8 @@ struct ConvArgs {
     int H, W, tiles_x, tiles_y, ncb;
     const float* Wp;    // [weight slots * 16][ncols], slot order = the K-loop order (see pack_conv)
     const float* Wimg;  // the same weights in LDS image order for k_conv16 (see pack_conv), or null
-    const float* Wblk;  // block-step image for k_conv16b (see pack_block_image), or null
+    const float* Wblk;  // block-step image for k_conv16b (see pack_conv), or null
+    const float* Wblk0; // k_conv16b: block 0 without the k-step of E_0's positive half (pack_block0_dead), or null: walk both
     const float* Wlat;  // per-wave fragment image for k_convlat: [slot][column block][4 column tiles][lane][k-step], or null
     const float* Wwino; // TZ-PA2 stage image for k_wino: [column block][stage][16 weight sets][lane][4 column tiles], or null
     int ipw;            // k_wino: column blocks a workgroup does one after the other (divides ncb)
@@ -1304,12 +1305,17 @@ __global__ __launch_bounds__(256) void k_convlat_pair(const ConvArgs a, const Co
 // channels needs -- its patch and the weights of ALL its taps (and parity classes) -- is one
 // LDS-DMA batch: one barrier pair per block, 32-108 MFMAs per wave between them, the next
 // block's batch in flight meanwhile.  Same tiles, fmaf-chain order and epilogues as k_conv16.
-//   block 0: the same-resolution source, stored 8 floats per pixel (6 real channels + 2 zeros):
+//   block 0: the same-resolution source E_0, stored 8 floats per pixel, one half per quad (k_err0: [e+ (3) 0 | e- (3) 0]):
 //            2 quad planes = 11 pieces, 9 taps x 2 k-steps;
+//            DEAD0 (the positive half is +0 at every pixel of every frame and its weights are finite, measured at
+//            prepare time: tz_prednet.hip measure_dead): the first k-step of every tap is left out -- quad plane 1 alone
+//            = 6 pieces, 9 taps x 1 k-step, weights from the compact image Wblk0.  Every tap still ends in the pad term
+//            fmaf(+0, +0, acc) of that quad, which is what makes the two forms equal bit for bit;
 //   blocks 1..: 16 channels of the upsampled source: 7 pieces, 4 taps x 4 classes x 4 k-steps.
 // Weight image per block: [tap][(class)][k-step][lane][NTI], NTI = 1 float per lane for one
-// column tile (ds_read_b32), 4 otherwise (ds_read_b128).
+// column tile (ds_read_b32), 4 otherwise (ds_read_b128); Wblk0: [tap][lane][NTI].
 static constexpr int E8_PIECES = 11;
+static constexpr int E4_PIECES = 6;   // ONE quad plane of the same patch (336 slots x 16 bytes = 5.25 KB): DEAD0 below
 
 __device__ __forceinline__ void wait_vm_n(int n) {  // wave-uniform n: leave the n youngest operations in flight
     switch (n) {
@@ -1330,18 +1336,22 @@ template <int NT>
 struct C16b {
     static constexpr int NTI = NT == 1 ? 1 : 4;
     static constexpr int W8 = (18 * 64 * NTI * 4 + 1023) / 1024;  // weight pieces of block 0
+    static constexpr int W8D = (9 * 64 * NTI * 4 + 1023) / 1024;  // ... of its second k-steps alone (DEAD0)
     static constexpr int WU = 16 * NTI;                           // ... of an upsampled block
-    static constexpr int bufp(bool ups) {
-        return !ups ? E8_PIECES + W8 : (E8_PIECES + W8 > U16_PIECES + WU ? E8_PIECES + W8 : U16_PIECES + WU);
+    static constexpr int bufp(bool ups, bool dead0) {
+        const int b0 = dead0 ? E4_PIECES + W8D : E8_PIECES + W8;
+        return !ups ? b0 : (b0 > U16_PIECES + WU ? b0 : U16_PIECES + WU);
     }
 };
 
-template <int NT, int EPI, bool UPS>
+template <int NT, int EPI, bool UPS, bool DEAD0 = false>
 __global__ __launch_bounds__(NTHR, 6) void k_conv16b(const ConvArgs a) {
     constexpr int MAP = EPI == EPI_POOL_ERR ? MAP_POOL : (UPS ? MAP_PARITY : MAP_LINEAR);
-    constexpr int NTI = C16b<NT>::NTI, W8 = C16b<NT>::W8, WU = C16b<NT>::WU, BUFP = C16b<NT>::bufp(UPS);
+    constexpr int NTI = C16b<NT>::NTI, W8 = C16b<NT>::W8, WU = C16b<NT>::WU, BUFP = C16b<NT>::bufp(UPS, DEAD0);
+    constexpr int P0 = DEAD0 ? E4_PIECES : E8_PIECES, W0 = DEAD0 ? C16b<NT>::W8D : W8;   // patch / weight pieces of block 0
+    constexpr int KS0 = DEAD0 ? 1 : 2;                                                   // ... and its k-steps per tap
     constexpr int NBUF = UPS ? 2 : 1;
-    static_assert((U16_PIECES + WU + 7) / 8 <= 9 && (E8_PIECES + W8 + 7) / 8 <= 9, "wait_vm_n covers at most 9 DMAs per wave in flight");
+    static_assert((U16_PIECES + WU + 7) / 8 <= 9 && (P0 + W0 + 7) / 8 <= 9, "wait_vm_n covers at most 9 DMAs per wave in flight");
     constexpr int SCRATCH = EPI == EPI_LSTM_PACKED ? 8 * 32 * 17 : 0;  // epilogue scratch (re-uses the buffers)
     __shared__ __attribute__((aligned(16))) float smem[NBUF * BUFP * 256 > SCRATCH ? NBUF * BUFP * 256 : SCRATCH];
 
@@ -1361,8 +1371,8 @@ __global__ __launch_bounds__(NTHR, 6) void k_conv16b(const ConvArgs a) {
         float* dst = smem + buf * BUFP * 256;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        const int P = b == 0 ? E8_PIECES : U16_PIECES, T = P + (b == 0 ? W8 : WU);
-        const float* wsrc = b == 0 ? a.Wblk + (long long)cb * W8 * 256
+        const int P = b == 0 ? P0 : U16_PIECES, T = P + (b == 0 ? W0 : WU);
+        const float* wsrc = b == 0 ? (DEAD0 ? a.Wblk0 : a.Wblk) + (long long)cb * W0 * 256
                                    : a.Wblk + ((long long)a.ncb * W8 + ((long long)(b - 1) * a.ncb + cb) * WU) * 256;
         int cnt = 0;
         for (int piece = wv; piece < T; piece += 8, ++cnt) {
@@ -1370,7 +1380,8 @@ __global__ __launch_bounds__(NTHR, 6) void k_conv16b(const ConvArgs a) {
                 glds16(wsrc + (piece - P) * 256 + ln * 4, dst + piece * 256);
             } else if (b == 0) {
                 const ConvSrc& s = a.src[0];
-                const int i = piece * 64 + ln, q = i / NP16, slot = i - q * NP16;
+                // (DEAD0: the image holds quad plane 1 alone, at the place of plane 0)
+                const int i = piece * 64 + ln, q = DEAD0 ? 1 : i / NP16, slot = DEAD0 ? i : i - q * NP16;
                 const int y = slot / PW, xs = slot - y * PW;
                 const int x = MAP == MAP_PARITY ? (xs < PW / 2 ? 2 * xs : 2 * (xs - PW / 2) + 1) : xs;
                 const int yy = ty0 - 1 + y, xx = tx0 - 1 + x;
@@ -1443,23 +1454,23 @@ __global__ __launch_bounds__(NTHR, 6) void k_conv16b(const ConvArgs a) {
     };
 
     __builtin_amdgcn_s_setprio(1);
-    // ---- block 0: 9 taps x 2 k-steps of the 8-wide same-resolution source
+    // ---- block 0: 9 taps x 2 k-steps of the 8-wide same-resolution source (DEAD0: x the second k-step)
     wait_vm_n(inflight);
     wg_barrier();
     {
         const float* pa = smem;
-        const float* wb = smem + E8_PIECES * 256 + lane * NTI;
+        const float* wb = smem + P0 * 256 + lane * NTI;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int dy = tap / 3, dx = tap % 3;
             const int xo = MAP == MAP_PARITY ? (dx == 1 ? ((wcls & 1) ? 1 - PW / 2 : PW / 2) : (dx >> 1)) : dx;
             const int toff = 4 * (dy * PW + xo);
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
+            for (int kk = 0; kk < KS0; ++kk) {
                 float fa[MT];
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) fa[mt] = pa[abase[mt] + toff + kk * 4 * NP16];
-                mfma_step(fa, wb + (tap * 2 + kk) * 64 * NTI);
+                mfma_step(fa, wb + (tap * KS0 + kk) * 64 * NTI);
             }
         }
     }
@@ -1549,8 +1560,8 @@ __global__ __launch_bounds__(256) void k_conv_small(const ConvArgs a) {
                     d2[c] = v[c] - h;
                 }
                 float* e = a.e0_out + (long long)slot * a.e0_nstride + pix * 8;
-                *(float4*)e = make_float4(tz_relu(d1[0]), tz_relu(d1[1]), tz_relu(d1[2]), tz_relu(d2[0]));
-                *(float4*)(e + 4) = make_float4(tz_relu(d2[1]), tz_relu(d2[2]), 0.0f, 0.0f);
+                *(float4*)e = make_float4(tz_relu(d1[0]), tz_relu(d1[1]), tz_relu(d1[2]), 0.0f);   // (one half per quad: k_err0)
+                *(float4*)(e + 4) = make_float4(tz_relu(d2[0]), tz_relu(d2[1]), tz_relu(d2[2]), 0.0f);
             }
         }
     }
@@ -1629,6 +1640,10 @@ __global__ __launch_bounds__(256) void k_live_blocks(const unsigned* __restrict_
 // level-0 error unit (prednet.py:274-277 with a = input frame, Ahat = Ahat_0(t0)):
 // input is either a key frame (uint8, unpadded; x = float32(k)/255, compress.py:138) or a
 // padded float32 frame of the prediction stack (compress.py:222).
+// Layout of e_0 at Cs == 8 floats per pixel (C <= 4), ONE HALF PER QUAD: [relu(Ahat - a) (C), 0.. | relu(a - Ahat) (C), 0..]
+// -- floats [0, C) the positive half, [4, 4 + C) the negative one, the rest zeros -- so that a k-step of k_conv16b's block 0
+// holds one half only (it leaves the positive one out where that is +0 for the model, tz_prednet.hip measure_dead); wider
+// maps (Cs > 8) keep [positive (C) | negative (C) | zeros].
 __global__ __launch_bounds__(256) void k_err0(const uint8_t* __restrict__ frames_u8, int H, int W,
                                               const float* __restrict__ in_stack, const int* __restrict__ is_key,
                                               const int* __restrict__ in_idx, const float* __restrict__ ahat0, int Hp,
@@ -1657,8 +1672,21 @@ __global__ __launch_bounds__(256) void k_err0(const uint8_t* __restrict__ frames
                 d1[c] = h - av[c];
                 d2[c] = av[c] - h;
             }
-            *(float4*)o = make_float4(tz_relu(d1[0]), tz_relu(d1[1]), tz_relu(d1[2]), tz_relu(d2[0]));
-            *(float4*)(o + 4) = make_float4(tz_relu(d2[1]), tz_relu(d2[2]), 0.0f, 0.0f);
+            *(float4*)o = make_float4(tz_relu(d1[0]), tz_relu(d1[1]), tz_relu(d1[2]), 0.0f);
+            *(float4*)(o + 4) = make_float4(tz_relu(d2[0]), tz_relu(d2[1]), tz_relu(d2[2]), 0.0f);
+            continue;
+        }
+        if (Cs == 8) {  // C <= 4: one half per quad, as above
+            for (int c = 0; c < 8; ++c) o[c] = 0.0f;
+            for (int c = 0; c < C; ++c) {
+                float av = 0.0f;
+                if (!key) av = in_stack[(fi * npx + p) * C + c];
+                else if (y < H && x < W) av = (float)frames_u8[(fi * H * W + (long long)y * W + x) * C + c] / 255.0f;
+                float h = ahat0[p * C + c];
+                float d1 = h - av, d2 = av - h;
+                o[c] = tz_relu(d1);
+                o[4 + c] = tz_relu(d2);
+            }
             continue;
         }
         for (int c = 0; c < C; ++c) {

@@ -31,11 +31,21 @@
 struct Seg {
     int row_off, C;
     int up;  // 1: half-resolution source read through a x2 nearest upsample (collapsed taps)
+    // E_0 stored one half per quad (k_err0, e0s == 8): channels per half.  Channel c of the segment then sits at float
+    // c (c < half) or 4 + c - half of a pixel, and the packed weights have their rows there, zero rows at the pads.  0: dense
+    int half = 0;
+    int row(int c) const { return half && c >= half ? 4 + c - half : c; }
 };
 struct PackedConv {
     float* d_W = nullptr;
     float* d_Wimg = nullptr;  // LDS image order for k_conv16 (every source a multiple of 16 channels), else null
     float* d_Wblk = nullptr;  // block-step image for k_conv16b (first source <= 8 channels at stride 8), else null
+    // k_conv16b over E_0 stored one half per quad (Seg::half): block 0 of the image without the k-step of the positive half,
+    // packed only where measure_dead finds that half dead; whether every weight that multiplies it is finite; and the host
+    // copy of block 0's slots of d_W that the compact image is packed from
+    float* d_Wblk0 = nullptr;
+    bool pos_finite = false;
+    std::vector<float> h_W0;
     float* d_Wlat = nullptr;  // per-wave fragment image for k_convlat (same condition as d_Wimg), else null
     float* d_Wwino = nullptr; // TZ-PA2 stage image for k_wino (pack_wino), else null
     const float* d_zero = nullptr;
@@ -70,6 +80,10 @@ struct tz_model {
     // Leading 16-channel blocks of E_l that are +0 at every pixel of every frame (measure_dead, tz_model_prepare), and how
     // many of them the k_wino launches of the level's gate convolution / of A_l leave out (0 where a skipped weight is not finite)
     int dead[TZ_MAX_LEVELS] = {0}, dead_gate[TZ_MAX_LEVELS] = {0}, dead_a[TZ_MAX_LEVELS] = {0};
+    // Level 0 (measure_dead): the positive half of E_0 is +0 at every pixel of every frame.  The k_conv16b convolutions that
+    // leave its k-step out are the ones that carry PackedConv::d_Wblk0
+    bool dead0 = false;
+    bool dead0_hold = false;   // tz_predict_next: the caller's frames hold a sign bit, x >= +0 is not given: walk every k-step
     // Levels whose start cell state C0_l is +0 in every word (measure_deadf, tz_model_prepare): their k_wino gate launches,
     // fused or split, take gate_nf[l], the stage image of the same convolution packed WITHOUT the forget-gate columns
     bool deadf[TZ_MAX_LEVELS] = {false};
@@ -134,6 +148,7 @@ static int pack_conv(tz_ctx* ctx, tz_model* m, const std::vector<Seg>& segs, con
     for (auto& s : segs) nslots += (s.up ? 16 : 9) * ((s.C + 15) / 16);
     std::vector<float> W((size_t)std::max(nslots, 1) * 16 * ncols, 0.0f), B(ncols, 0.0f);
     int slot = 0;
+    bool pos_finite = true;   // every weight that multiplies the positive half of an E_0 stored one half per quad
     auto put = [&](const Seg& s, int c0, const int* kys, int nky, const int* kxs, int nkx) {
         for (int kc = 0; kc < 16 && c0 + kc < s.C; ++kc)
             for (int col = 0; col < ncols; ++col) {
@@ -147,7 +162,8 @@ static int pack_conv(tz_ctx* ctx, tz_model* m, const std::vector<Seg>& segs, con
                         v = first ? w : v + w;
                         first = false;
                     }
-                W[((size_t)slot * 16 + kc) * ncols + col] = v;
+                W[((size_t)slot * 16 + s.row(c0 + kc) - c0) * ncols + col] = v;
+                if (s.half && c0 + kc < s.half && !std::isfinite(v)) pos_finite = false;
             }
         ++slot;
     };
@@ -208,7 +224,8 @@ static int pack_conv(tz_ctx* ctx, tz_model* m, const std::vector<Seg>& segs, con
         TZ_HIP(ctx, hipMemcpy(pc->d_Wlat, I.data(), I.size() * 4, hipMemcpyHostToDevice));
     }
     // k_conv16b's image: block 0 = the <= 8-channel same-resolution source [cb][tap][k-step 0..1][lane][NTI]
-    // (padded to whole 1 KB pieces), then per 16-channel block of the upsampled source
+    // (padded to whole 1 KB pieces; the rows of W are the floats of a pixel as stored, so for E_0 one half per quad k-step 0
+    // holds the positive half and k-step 1 the negative one, each behind a zero pad row), then per 16-channel block of the upsampled source
     // [block][cb][tap][class][k-step][lane][NTI]
     const bool blk_ok = !segs.empty() && !segs[0].up && segs[0].C <= 8 && (NT == 1 || NT >= 3) &&
                         (segs.size() == 1 || (segs.size() == 2 && segs[1].up && segs[1].C % 16 == 0));
@@ -239,7 +256,30 @@ static int pack_conv(tz_ctx* ctx, tz_model* m, const std::vector<Seg>& segs, con
         TZ_TRY(dmalloc(ctx, m, (void**)&pc->d_Wblk, I.size() * 4));
         TZ_HIP(ctx, hipMemcpy(pc->d_Wblk, I.data(), I.size() * 4, hipMemcpyHostToDevice));
         pc->d_zero = m->d_zero;
+        if (segs[0].half) {   // what pack_block0_dead needs, should measure_dead ask for it
+            pc->pos_finite = pos_finite;
+            pc->h_W0.assign(W.begin(), W.begin() + (size_t)9 * 16 * ncols);
+        }
     }
+    return TZ_OK;
+}
+
+// k_conv16b's block 0 once more for a convolution whose E_0 (one half per quad) has a dead positive half: the k-step of the
+// negative half alone, [cb][tap][lane][NTI] padded to whole 1 KB pieces per column block -- rows 4..7 of each tap's slot, the
+// same values as k-step 1 of d_Wblk.  Called by measure_dead, only for a model that takes the skip.
+static int pack_block0_dead(tz_ctx* ctx, tz_model* m, PackedConv* pc) {
+    if (pc->h_W0.empty() || !pc->d_Wblk) return TZ_OK;
+    const int NT = pc->NT, ncb = pc->ncb, ncols = pc->ncols, NTI = NT == 1 ? 1 : 4;
+    const int W8D = (9 * 64 * NTI * 4 + 1023) / 1024;
+    std::vector<float> I((size_t)ncb * W8D * 256, 0.0f);
+    for (int cb = 0; cb < ncb; ++cb)
+        for (int tap = 0; tap < 9; ++tap)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int nt = 0; nt < std::min(NT, NTI); ++nt)
+                    I[(size_t)cb * W8D * 256 + ((size_t)tap * 64 + lane) * NTI + nt] =
+                        pc->h_W0[((size_t)tap * 16 + 4 + (lane >> 4)) * ncols + cb * NT * 16 + nt * 16 + (lane & 15)];
+    TZ_TRY(dmalloc(ctx, m, (void**)&pc->d_Wblk0, I.size() * 4));
+    TZ_HIP(ctx, hipMemcpy(pc->d_Wblk0, I.data(), I.size() * 4, hipMemcpyHostToDevice));
     return TZ_OK;
 }
 
@@ -536,8 +576,14 @@ static LatPlan lat_plan(const tz_ctx* ctx, int NT, int epi, bool ups, bool fullk
 }
 
 // (wino_dead: dead leading blocks of the same-resolution source, for k_wino alone -- launch_wino.  The TZ-PA1 kernels below,
-// k_conv16 / k_convlat / k_conv16b / k_conv3x3, walk every block: their chains start from G0 or the bias, which may be -0, and
-// fmaf(+0, w, -0) = +0 is not what the chain held; level 0 has no 16-channel block to leave out)
+// k_conv16 / k_convlat / k_conv3x3, walk every block: their chains start from G0 or the bias, which may be -0, and
+// fmaf(+0, w, -0) = +0 is not what the chain held.)
+// Level 0 leaves a dead half out in k_conv16b instead, by the k-step: E_0 is stored one half per quad with a zero pad behind
+// each (k_err0), every tap is two k-steps, and every tap ENDS in the pad term fmaf(+0, +0, acc), which already turns a -0
+// accumulator into +0 -- so where the positive half is +0 at every pixel and its weights are finite, the first k-step of a tap
+// changes no bit behind the tap, whatever the chain started from (tests/test_dead0_oracle.py).  The
+// convolutions measure_dead found so carry the compact block-0 image (ConvArgs::Wblk0) and run k_conv16b<.., DEAD0>: the same
+// launch with 9 k-steps instead of 18 in block 0.  k_conv3x3 (tz_set_conv_impl(0)) walks all 8 floats: the unskipped cross-check.
 // (wino3: launch_wino)
 static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbatch, int wino_dead = 0, const float* wino3 = nullptr) {
     tz_prof_scope ps(ctx, TZP_CONV);
@@ -563,7 +609,8 @@ static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbat
 #define TZ_CASE16B(nt, e, u)                                                                                    \
     if (NT == nt && epi == e && ups == u) {                                                                     \
         ps.sub = TZP_CONV16B;                                                                                   \
-        hipLaunchKernelGGL((k_conv16b<nt, e, u>), dim3(blocks), dim3(NTHR), 0, ctx->stream, a);                 \
+        if (a.Wblk0) hipLaunchKernelGGL((k_conv16b<nt, e, u, true>), dim3(blocks), dim3(NTHR), 0, ctx->stream, a); \
+        else hipLaunchKernelGGL((k_conv16b<nt, e, u>), dim3(blocks), dim3(NTHR), 0, ctx->stream, a);            \
         TZ_HIP(ctx, hipGetLastError());                                                                         \
         return TZ_OK;                                                                                           \
     }
@@ -630,7 +677,8 @@ static void fill_srcs(ConvArgs& a, const PackedConv& pc, const float* const* ptr
     for (int s = 0; s < a.nsrc; ++s) {
         a.src[s].p = ptrs[s];
         a.src[s].nstride = nstrides[s];
-        a.src[s].C = pc.segs[s].C;
+        // (E_0 one half per quad: the kernels see the 8 floats of a pixel as 8 channels, the pads with zero weight rows)
+        a.src[s].C = pc.segs[s].half ? 8 : pc.segs[s].C;
         a.src[s].pstride = s == 0 && pstride0 ? pstride0 : pc.segs[s].C;
         a.src[s].up = pc.segs[s].up;
         a.src[s].cpt = (pc.segs[s].C + 15) / 16;
@@ -638,6 +686,7 @@ static void fill_srcs(ConvArgs& a, const PackedConv& pc, const float* const* ptr
     a.Wp = pc.d_W;
     a.Wimg = pc.d_Wimg;
     a.Wblk = pc.d_Wblk;
+    a.Wblk0 = pc.d_Wblk0;
     a.Wlat = pc.d_Wlat;
     a.Wwino = pc.d_Wwino;
     a.zero = pc.d_zero;
@@ -794,11 +843,22 @@ static int measure_dead(tz_ctx* ctx, tz_model* m) {
     const bool log = getenv("TEZIP_DEADSRC_LOG") && atoi(getenv("TEZIP_DEADSRC_LOG"));
     unsigned long long h_live[TZ_MAX_LEVELS] = {0};
     for (int l = 0; l < TZ_MAX_LEVELS; ++l) m->dead[l] = m->dead_gate[l] = m->dead_a[l] = 0;
-    if (on) {
+    const char* env0 = getenv("TEZIP_DEAD0");
+    const bool on0 = !env0 || atoi(env0) != 0;
+    const bool log0 = getenv("TEZIP_DEAD0_LOG") && atoi(getenv("TEZIP_DEAD0_LOG"));
+    const bool half0 = m->e0s == 8;   // E_0 is stored one half per quad: the only layout with a k-step to leave out
+    m->dead0 = false;
+    if (on || ((on0 || log0) && half0)) {
         unsigned long long* d_live = nullptr;
         TZ_TRY(dmalloc(ctx, m, (void**)&d_live, sizeof(h_live)));
         TZ_HIP(ctx, hipMemsetAsync(d_live, 0, sizeof(h_live), ctx->stream));
-        for (int l = 1; l < L; ++l) {
+        if ((on0 || log0) && half0) {   // level 0: the whole plane Ahat0_0, border included, as ONE block of stack[0] channels
+            const long long npx = (long long)m->Hp * m->Wp;
+            hipLaunchKernelGGL(k_live_blocks, dim3((unsigned)std::min<long long>((npx * m->stack[0] + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                               (const unsigned*)m->Ahat0[0], npx, m->stack[0], 1, d_live);
+            TZ_HIP(ctx, hipGetLastError());
+        }
+        for (int l = 1; on && l < L; ++l) {
             const long long npx = (long long)(m->Hp >> l) * (m->Wp >> l);
             const int nb = std::min(m->stack[l] / 16, 64);
             if (nb < 1) continue;
@@ -826,6 +886,33 @@ static int measure_dead(tz_ctx* ctx, tz_model* m) {
                 fprintf(stderr, "[tezip] dead source, level %d %s: %d of %d leading positive-half blocks dead, %d skipped: %d of %d same-resolution stages%s\n",
                         l, names[k], d, m->stack[l] / 16, *out[k], 4 * *out[k], 2 * m->stack[l] / 4,
                         !on ? " (TEZIP_DEADSRC=0)" : (*out[k] < d ? " (a weight of those stages is not finite)" : ""));
+        }
+    }
+    // Level 0.  E_0 = [relu(Ahat0_0 - x), relu(x - Ahat0_0)] with x a frame: a key frame (u8 / 255) or a prediction
+    // (min(relu(.), 1), and relu(NaN) = 0), so x >= +0 and never NaN (tz_predict_next, whose frames are the caller's, looks:
+    // dead0_hold).  Where Ahat0_0 is +-0 over the whole plane the positive half is then +0 at every pixel of every frame.
+    // It sits in a quad of its own (k_err0), so the k_conv16b convolutions over E_0 -- A_0 and the level-0 gates -- can leave
+    // out the k-step that multiplies it, each where every weight of those rows is finite (0 x inf is a NaN the chain must keep).
+    // Why that changes no bit although the chains may start from -0: launch_conv, DESIGN.md section 5.
+    // TEZIP_DEAD0=0 (read here, per prepare): never; TEZIP_DEAD0_LOG=1: one line per convolution.
+    if (half0 && (on0 || log0)) {
+        const bool zero = !(h_live[0] & 1);
+        m->dead0 = zero;
+        PackedConv* pcs[2] = {L > 1 ? &m->a_conv[0] : nullptr, &m->gate_t1[0]};
+        static const char* const names[2] = {"A", "gates"};
+        for (int k = 0; k < 2; ++k) {
+            if (!pcs[k]) continue;
+            // (launch_conv's TZ_CASE16B: every A_0 shape; the gates where they are one packed column tile, R_0 <= 4)
+            const bool form = pcs[k]->d_Wblk && !pcs[k]->h_W0.empty() && (k == 0 || pcs[k]->NT == 1), finite = pcs[k]->pos_finite;
+            if (on0 && zero && form && finite) TZ_TRY(pack_block0_dead(ctx, m, pcs[k]));
+            if (log0)
+                fprintf(stderr, "[tezip] dead level 0, %s: positive half of E_0 +0 everywhere: %s, its k-step left out: %s%s\n", names[k],
+                        zero ? "yes" : "no", pcs[k]->d_Wblk0 ? "yes" : "no",
+                        pcs[k]->d_Wblk0 ? " (9 of 18 k-steps in block 0 of k_conv16b)"
+                        : !zero         ? ""
+                        : !on0          ? " (TEZIP_DEAD0=0)"
+                        : !form         ? " (no k_conv16b form)"
+                                        : " (a weight of those rows is not finite)");
         }
     }
     return TZ_OK;
@@ -1029,7 +1116,8 @@ extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
         set_geom(a, hl(l), wl(l));
         a.out0 = m->G0[l];
         TZ_TRY(launch_conv(ctx, NT, EPI_RAW, a, 1));
-        std::vector<Seg> segs = {Seg{m->rstack[l], 2 * m->stack[l], 0}};
+        const int half = l == 0 && m->e0s == 8 ? m->stack[0] : 0;   // E_0 one half per quad (k_err0)
+        std::vector<Seg> segs = {Seg{m->rstack[l], 2 * m->stack[l], 0, half}};
         if (l < L - 1) segs.push_back(Seg{m->rstack[l] + 2 * m->stack[l], m->rstack[l + 1], 1});
         TZ_TRY(pack_conv(ctx, m, segs, cols, NT, &m->gate_t1[l]));
         if (l >= 1) TZ_TRY(pack_wino(ctx, m, segs, cols, NT, &m->gate_t1[l]));   // TZ-PA2 form of the same convolution
@@ -1054,7 +1142,8 @@ extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
     // ---- A convs (prednet.py:290)
     for (int l = 0; l < L - 1; ++l) {
         int Cout = m->stack[l + 1], NT = plain_nt(Cout);
-        TZ_TRY(pack_conv(ctx, m, {Seg{0, 2 * m->stack[l], 0}}, plain_cols(m->a_k(l), m->a_b(l), 2 * m->stack[l], Cout), NT,
+        const int half = l == 0 && m->e0s == 8 ? m->stack[0] : 0;   // E_0 one half per quad (k_err0)
+        TZ_TRY(pack_conv(ctx, m, {Seg{0, 2 * m->stack[l], 0, half}}, plain_cols(m->a_k(l), m->a_b(l), 2 * m->stack[l], Cout), NT,
                          &m->a_conv[l]));
         if (l >= 1) TZ_TRY(pack_wino(ctx, m, {Seg{0, 2 * m->stack[l], 0}}, plain_cols(m->a_k(l), m->a_b(l), 2 * m->stack[l], Cout), NT, &m->a_conv[l]));
     }
@@ -1263,6 +1352,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         long long ns[2] = {npx(l) * ec, l < L - 1 ? npx(l + 1) * m->rstack[l + 1] : 0};
         const float* ptrs[2] = {m->E[l] + slot0 * ns[0], l < L - 1 ? m->R1[l + 1] + slot0 * ns[1] : nullptr};
         fill_srcs(a, pc, ptrs, ns, ec);
+        if (m->dead0_hold) a.Wblk0 = nullptr;
         set_geom(a, hl(l), wl(l));
         a.init = m->G0[l];
         a.initf = m->G0f[l];
@@ -1284,6 +1374,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         long long ns[2] = {npx(l) * ec, 0};
         const float* ptrs[2] = {m->E[l] + slot0 * ns[0], nullptr};
         fill_srcs(a, pc, ptrs, ns, ec);
+        if (m->dead0_hold) a.Wblk0 = nullptr;
         set_geom(a, hl(l), wl(l));
         a.Cout = m->stack[l + 1];
         a.aux = m->Ahat0[l + 1];
@@ -1467,6 +1558,24 @@ extern "C" int tz_predict_next(tz_ctx* ctx, const float* frames, int n, float* o
     float* dout;
     TZ_TRY(call.in(frames, fe * n * 4, &din));
     TZ_TRY(call.out(out, fe * n * 4, &dout));
+    // These frames are the caller's, not key frames or predictions: a negative value makes the positive half of E_0 live, so
+    // the level-0 skip (measure_dead) holds off for the call unless no word of them has its sign bit set.
+    struct Hold {
+        tz_model* m;
+        ~Hold() { m->dead0_hold = false; }
+    } hold{m};
+    if (m->dead0 && n > 0) {
+        unsigned long long* d_neg;
+        unsigned long long neg = 0;
+        TZ_TRY(call.alloc(8, &d_neg));
+        TZ_HIP(ctx, hipMemsetAsync(d_neg, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(k_live_blocks, dim3((unsigned)std::min<size_t>((fe * n + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                           (const unsigned*)din, (long long)(fe * n), 1, 1, d_neg, 0x80000000u);
+        TZ_HIP(ctx, hipGetLastError());
+        TZ_HIP(ctx, hipMemcpyAsync(&neg, d_neg, 8, hipMemcpyDeviceToHost, ctx->stream));
+        TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        m->dead0_hold = neg != 0;
+    }
     for (int b0 = 0; b0 < n; b0 += m->maxB) {
         int nb = std::min(m->maxB, n - b0);
         std::vector<int> isk(nb, 0), ii(nb), oi(nb);
@@ -1535,7 +1644,14 @@ extern "C" int tz_predict_tap(tz_ctx* ctx, int kind, int level, float* out) {
     const float* src = kind == 0 ? m->E[level] : m->R1[level];
     const size_t ch = kind == 0 ? 2 * m->stack[level] : m->rstack[level];
     const size_t sch = kind == 0 && level == 0 ? m->e0s : ch;  // E[0] is stored with a pixel stride of 8 floats
-    TZ_HIP(ctx, hipMemcpy2DAsync(out, ch * 4, src, sch * 4, ch * 4, npx, hipMemcpyDefault, ctx->stream));
+    if (kind == 0 && level == 0 && m->e0s == 8) {
+        // ... one half per quad (k_err0); the caller gets the 2 * stack[0] channels in their order, positive half first
+        const size_t hb = (size_t)m->stack[0] * 4;
+        TZ_HIP(ctx, hipMemcpy2DAsync(out, ch * 4, src, sch * 4, hb, npx, hipMemcpyDefault, ctx->stream));
+        TZ_HIP(ctx, hipMemcpy2DAsync((char*)out + hb, ch * 4, src + 4, sch * 4, hb, npx, hipMemcpyDefault, ctx->stream));
+    } else {
+        TZ_HIP(ctx, hipMemcpy2DAsync(out, ch * 4, src, sch * 4, ch * 4, npx, hipMemcpyDefault, ctx->stream));
+    }
     TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TZ_OK;
 }
