@@ -83,6 +83,11 @@ struct ConvArgs {
     const float* aux_u;
     int init_ring, aux_ring;
     int init_tring, aux_tring;
+    // EPI_POOL_ERR / k_conv_small's e0_out: Ahat0 of the level written is +-0 over the whole plane (tz_prednet.hip
+    // measure_dead), so e = [relu(Ahat0 - a) | relu(a - Ahat0)] with a >= +0 is [+0 | a] bit for bit.
+    // The LDS-DMA kernels then load no Ahat0, subtract nothing and store the live half alone; the dead half keeps the +0 that
+    // tz_model_prepare filled it with.  k_conv3x3 / k_conv16 / k_convlat / k_wino_ref ignore this: the unskipped cross-checks.
+    int dead_half;
 };
 
 // the reference tile of a plane: the 16 x 16 tile that holds the centre pixel
@@ -147,7 +152,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 // Fused epilogues on the accumulator tiles of one wave (shared by both convolution kernels):
 // acc[mt][nt], element r <-> GEMM row (lane>>4)*4 + r of M-tile mt, column lane&15 of N-tile nt.
-template <int NT, int EPI, int MAP>
+// DH (EPI_POOL_ERR, k_conv16b alone): ConvArgs::dead_half -- no Ahat0 is loaded, nothing subtracted, the live half alone stored
+template <int NT, int EPI, int MAP, bool DH = false>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[MT][NT], int n, int cb, int ty0, int tx0,
                                               int wv, int lane, float* scratch) {
     constexpr int NTC = NT * 16;
@@ -302,7 +308,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[MT
             for (int nt = 0; nt < NT; ++nt) {
                 const int ch = col0 + nt * 16;
                 ok[mt][nt] = okp && ch < C;
-                h[mt][nt] = a.aux[ok[mt][nt] ? pp[mt] * C + ch : 0];
+                h[mt][nt] = DH ? 0.0f : a.aux[ok[mt][nt] ? pp[mt] * C + ch : 0];
             }
         }
 #pragma unroll
@@ -315,6 +321,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[MT
                 for (int r = 1; r < 4; ++r) {
                     float t = tz_relu(acc[mt][nt][r]);
                     if (t > m) m = t;
+                }
+                if (DH) {   // m >= +0, Ahat0 = +-0: e = [+0 | m], and the +0 is there already
+                    if (ok[mt][nt]) o[pp[mt] * 2 * C + C + ch] = m;
+                    continue;
                 }
                 float d1 = h[mt][nt] - m, d2 = m - h[mt][nt];
                 if (ok[mt][nt]) {
@@ -1503,7 +1513,8 @@ __global__ __launch_bounds__(NTHR, 6) void k_conv16b(const ConvArgs a) {
     }
     __builtin_amdgcn_s_setprio(0);
     if (EPI == EPI_LSTM_PACKED) wg_barrier();  // the staging buffers become the epilogue's scratch
-    conv_epilogue<NT, EPI, MAP>(a, acc, n, cb, ty0, tx0, wv, lane, smem);
+    if (EPI == EPI_POOL_ERR && a.dead_half) conv_epilogue<NT, EPI, MAP, true>(a, acc, n, cb, ty0, tx0, wv, lane, smem);   // (uniform)
+    else conv_epilogue<NT, EPI, MAP>(a, acc, n, cb, ty0, tx0, wv, lane, smem);
 }
 
 // Level-0 prediction Ahat_0 = min(relu(conv3x3(r_0)), 1) (prednet.py:268-271) with CIN, COUT <= 4:
@@ -1551,7 +1562,11 @@ __global__ __launch_bounds__(256) void k_conv_small(const ConvArgs a) {
         }
         if (COUT == 3 && a.e0_out) {   // the next step's level-0 error unit, same arithmetic as k_err0
             const int slot = a.e0_slot[n];
-            if (slot >= 0) {
+            if (slot >= 0 && a.dead_half) {
+                // (uniform) Ahat0_0 = +-0 and v >= +0: e_0 = [+0 | v] bit for bit; the positive quad holds its +0 already
+                float* e = a.e0_out + (long long)slot * a.e0_nstride + pix * 8;
+                *(float4*)(e + 4) = make_float4(v[0], v[1], v[2], 0.0f);
+            } else if (slot >= 0) {
                 float d1[3], d2[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {

@@ -87,6 +87,12 @@ struct tz_model {
     // Levels whose start cell state C0_l is +0 in every word (measure_deadf, tz_model_prepare): their k_wino gate launches,
     // fused or split, take gate_nf[l], the stage image of the same convolution packed WITHOUT the forget-gate columns
     bool deadf[TZ_MAX_LEVELS] = {false};
+    // Levels whose Ahat0_l is +-0 over the whole plane (measure_dead): the positive half of E_l is +0 in every frame and the
+    // negative half is the level's A itself, so the LDS-DMA writers of E_l store the live half alone (ConvArgs::dead_half);
+    // the dead half keeps the +0 tz_model_prepare filled it with.  e0_dirty: a tz_predict_next call whose frames held a sign
+    // bit (dead0_hold) has put something else into E_0's positive half; level 0 then stores both halves from there on.
+    bool deadhalf[TZ_MAX_LEVELS] = {false};
+    bool e0_dirty = false;
     float *E[TZ_MAX_LEVELS] = {0}, *R1[TZ_MAX_LEVELS] = {0};
     float* P[TZ_MAX_LEVELS] = {0};   // gate accumulators after the E_l part of the chain (split launches of small grids), or null
     int Pcap[TZ_MAX_LEVELS] = {0};   // ... how many batch slots P[l] holds (<= maxB: at most kPBytes per level)
@@ -848,17 +854,23 @@ static int measure_dead(tz_ctx* ctx, tz_model* m) {
     const bool log0 = getenv("TEZIP_DEAD0_LOG") && atoi(getenv("TEZIP_DEAD0_LOG"));
     const bool half0 = m->e0s == 8;   // E_0 is stored one half per quad: the only layout with a k-step to leave out
     m->dead0 = false;
-    if (on || ((on0 || log0) && half0)) {
+    // TEZIP_DEADHALF=0 (read here, per prepare): the writers of E_l store both halves everywhere; TEZIP_DEADHALF_LOG=1: one line per level.
+    const char* envh = getenv("TEZIP_DEADHALF");
+    const bool onh = !envh || atoi(envh) != 0;
+    const bool logh = getenv("TEZIP_DEADHALF_LOG") && atoi(getenv("TEZIP_DEADHALF_LOG"));
+    for (int l = 0; l < TZ_MAX_LEVELS; ++l) m->deadhalf[l] = false;
+    m->e0_dirty = false;
+    if (on || onh || ((on0 || log0) && half0)) {
         unsigned long long* d_live = nullptr;
         TZ_TRY(dmalloc(ctx, m, (void**)&d_live, sizeof(h_live)));
         TZ_HIP(ctx, hipMemsetAsync(d_live, 0, sizeof(h_live), ctx->stream));
-        if ((on0 || log0) && half0) {   // level 0: the whole plane Ahat0_0, border included, as ONE block of stack[0] channels
+        if ((on0 || log0 || onh) && half0) {   // level 0: the whole plane Ahat0_0, border included, as ONE block of stack[0] channels
             const long long npx = (long long)m->Hp * m->Wp;
             hipLaunchKernelGGL(k_live_blocks, dim3((unsigned)std::min<long long>((npx * m->stack[0] + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
                                (const unsigned*)m->Ahat0[0], npx, m->stack[0], 1, d_live);
             TZ_HIP(ctx, hipGetLastError());
         }
-        for (int l = 1; on && l < L; ++l) {
+        for (int l = 1; (on || onh) && l < L; ++l) {
             const long long npx = (long long)(m->Hp >> l) * (m->Wp >> l);
             const int nb = std::min(m->stack[l] / 16, 64);
             if (nb < 1) continue;
@@ -887,6 +899,17 @@ static int measure_dead(tz_ctx* ctx, tz_model* m) {
                         l, names[k], d, m->stack[l] / 16, *out[k], 4 * *out[k], 2 * m->stack[l] / 4,
                         !on ? " (TEZIP_DEADSRC=0)" : (*out[k] < d ? " (a weight of those stages is not finite)" : ""));
         }
+    }
+    // Dead halves.  Where Ahat0_l is +-0 over the WHOLE plane (every 16-channel block looked at, none live) the error unit
+    // e = [relu(Ahat0 - a) | relu(a - Ahat0)] over a >= +0 (a pooled relu, or a clipped prediction at level 0: never NaN, never
+    // -0) is [+0 | a] bit for bit, and the LDS-DMA writers of E_l store a alone (ConvArgs::dead_half).
+    for (int l = 0; l < L; ++l) {
+        const bool whole = l == 0 ? half0 : (m->stack[l] % 16 == 0 && m->stack[l] / 16 <= 64);
+        const unsigned long long blocks = l == 0 ? 1ull : (m->stack[l] / 16 >= 64 ? ~0ull : (1ull << (m->stack[l] / 16)) - 1);
+        m->deadhalf[l] = onh && whole && !(h_live[l] & blocks);
+        if (logh)
+            fprintf(stderr, "[tezip] dead half, level %d: Ahat0 +-0 over the whole plane: %s%s\n", l, m->deadhalf[l] ? "yes" : "no",
+                    m->deadhalf[l] ? " (its writers store the live half alone)" : !onh ? " (TEZIP_DEADHALF=0)" : "");
     }
     // Level 0.  E_0 = [relu(Ahat0_0 - x), relu(x - Ahat0_0)] with x a frame: a key frame (u8 / 255) or a prediction
     // (min(relu(.), 1), and relu(NaN) = 0), so x >= +0 and never NaN (tz_predict_next, whose frames are the caller's, looks:
@@ -1042,6 +1065,14 @@ extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
         TZ_TRY(dmalloc(ctx, m, (void**)&m->Ahat0[l], npx * m->stack[l] * 4));
         const int ec = l == 0 ? (m->e0s = (2 * m->stack[0] + 7) / 8 * 8) : 2 * m->stack[l];
         TZ_TRY(dmalloc(ctx, m, (void**)&m->E[l], (size_t)max_batch * npx * ec * 4));
+        // Every slot starts as +0: where a half of E_l is dead for the model (tz_model::deadhalf) its LDS-DMA writers store
+        // the live half alone, and the unskipped readers (k_wino_ref, k_conv3x3, TEZIP_DEADSRC=0, TEZIP_DEAD0=0) must find
+        // +0 where nothing was stored.  Writers of E_l, all of which put +0 into a dead half or leave it alone:
+        //   E_0: k_err0 (both halves: relu((+-0) - x) = +0 for x >= +0; a tz_predict_next call with a sign bit in its frames
+        //        sets e0_dirty and level 0 stores both halves from then on), k_conv_small's e0_out (the live quad alone);
+        //   E_l, l >= 1: the POOL_ERR epilogues of A_{l-1} -- k_conv16b and k_wino (the live half alone), k_conv3x3,
+        //        k_conv16, k_convlat, k_convlat_pair and k_wino_ref (both halves, the dead one computed as +0).
+        TZ_HIP(ctx, hipMemsetAsync(m->E[l], 0, (size_t)max_batch * npx * ec * 4, ctx->stream));
         TZ_TRY(dmalloc(ctx, m, (void**)&m->R1[l], (size_t)max_batch * npx * R * 4));
         // split gate launches (small grids only, see tz_model_predict_batch_dev): [item][pixel][4R] accumulators
         // (also the hand-over buffer of a gate convolution that runs as two k_wino launches: "E-part ahead" below).
@@ -1381,6 +1412,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         a.init_tring = a.aux_tring = -1;
         a.out0_nstride = npx(l + 1) * 2 * m->stack[l + 1];
         a.out0 = m->E[l + 1] + slot0 * a.out0_nstride;
+        a.dead_half = m->deadhalf[l + 1];
     };
     // "E-part ahead" (round 5): a gate convolution under TZ-PA2 is two phases in ONE chain per output -- the same-resolution
     // source E_l, then the upsampled R_{l+1} -- and only the second one sits on the step's critical path
@@ -1530,6 +1562,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
             a.e0_out = m->E[0] + slot0 * a.e0_nstride;   // (the table's slot numbers are positions in the next batch)
             a.e0_ahat = m->Ahat0[0];
             a.e0_slot = d_next_slot;
+            a.dead_half = m->deadhalf[0] && !m->dead0_hold && !m->e0_dirty;
             if (fused_next) *fused_next = true;
         }
         TZ_TRY(launch_conv(ctx, pc.NT, EPI_RELU, a, n));
@@ -1564,7 +1597,7 @@ extern "C" int tz_predict_next(tz_ctx* ctx, const float* frames, int n, float* o
         tz_model* m;
         ~Hold() { m->dead0_hold = false; }
     } hold{m};
-    if (m->dead0 && n > 0) {
+    if ((m->dead0 || m->deadhalf[0]) && n > 0) {
         unsigned long long* d_neg;
         unsigned long long neg = 0;
         TZ_TRY(call.alloc(8, &d_neg));
@@ -1575,6 +1608,7 @@ extern "C" int tz_predict_next(tz_ctx* ctx, const float* frames, int n, float* o
         TZ_HIP(ctx, hipMemcpyAsync(&neg, d_neg, 8, hipMemcpyDeviceToHost, ctx->stream));
         TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
         m->dead0_hold = neg != 0;
+        if (neg) m->e0_dirty = true;   // (k_err0 is about to put non-zero values into E_0's positive half)
     }
     for (int b0 = 0; b0 < n; b0 += m->maxB) {
         int nb = std::min(m->maxB, n - b0);

@@ -787,6 +787,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // prednet.py:289-291 then 274-277 of the next level: A = maxpool2x2(relu(conv)) -- the pooling window IS the tile --,
         // e = [relu(Ahat0 - A), relu(A - Ahat0)] at the pooled resolution.  The wave holds one row of every window; the
         // partner the other: wave ph = 0 finishes column tiles 0, 1, wave ph = 1 the rest
+        // (ConvArgs::dead_half: Ahat0 is +-0 over the plane -- no load of it, no subtraction, the live half A alone stored)
         const int H2 = a.H >> 1, W2 = a.W >> 1, C = a.Cout;
         float* o = a.out0 + (long long)n * a.out0_nstride;
         f32x4 m[NT];
@@ -822,6 +823,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const int t = (ph == 0 ? 0 : 2) + k;
                 const f32x4 mine = ph == 0 ? m[k] : m[(2 + k) % NT], other = k == 0 ? q0 : q1;
                 const unsigned hoff = 4u * (pix * (unsigned)C + colw + 16u * t), ooff = 4u * (pix * 2u * (unsigned)C + colw + 16u * t);
+                if (a.dead_half) {   // (uniform) Ahat0 = +-0 over the plane and mm >= +0: e = [+0 | mm], the +0 is there already
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float mm = other[e] > mine[e] ? other[e] : mine[e];
+                        *(float*)(po + (size_t)e * C * 8 + (size_t)C * 4 + ooff) = mm;
+                    }
+                    continue;
+                }
                 float hv[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) hv[e] = *(const float*)(ph_ + (size_t)e * C * 4 + hoff);
@@ -845,8 +854,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const int xp = (tx0 >> 1) + 4 * (mt & 1) + e;
                 const bool okp = yp < H2 && xp < W2 && ch < C;
                 const long long pp = okp ? (long long)yp * W2 + xp : 0;
-                const float h = a.aux[okp ? pp * C + ch : 0];
                 const float mm = other[e] > mine[e] ? other[e] : mine[e];
+                if (a.dead_half) {   // (uniform)
+                    if (okp) o[pp * 2 * C + C + ch] = mm;
+                    continue;
+                }
+                const float h = a.aux[okp ? pp * C + ch : 0];
                 const float d1 = h - mm, d2 = mm - h;
                 if (okp) {
                     o[pp * 2 * C + ch] = tz_relu(d1);
