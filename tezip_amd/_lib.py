@@ -159,6 +159,11 @@ _SIGS = {
     "tz_size_count_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "tz_size_bits_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                    C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_int)]),
+    "tz_sdelta_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    "tz_size_count_plane_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.POINTER(C.c_int)]),
+    "tz_size_bits_plane_buf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                         C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_int)]),
     "tz_keys_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tz_keys_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
     "tz_keys_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
@@ -1148,6 +1153,41 @@ class Context:
         words, bits, bad = C.c_ulonglong(0), C.c_ulonglong(0), C.c_int(0)
         self._ck(self.lib.tz_size_bits_buf(self.h, _ptr(q), _numel(q), int(channels), int(stride), int(bool(offset)), ln.ctypes.data,
                                            int(dist), C.byref(words), C.byref(bits), C.byref(bad)))
+        return int(words.value), int(bits.value), bool(bad.value)
+
+    # ---- the payload's spatial delta by exact size (definition TZ-SDA1: tezip_amd/sdauto.py)
+    def sdelta_probe(self, mode, bound, entropy=True, coder="huffd"):
+        """tz_sdelta_probe after rollout: three SIZE_DTYPE records, the streams of the job under the flat (one channel: channel 0
+        alone), channel-stride and plane payloads, from ONE quantiser run; n == 0: the layout is no candidate.  The context's
+        own delta_stride / delta_plane are neither read nor changed."""
+        b0, b1 = _bounds(bound)
+        out = np.zeros(3, SIZE_DTYPE)
+        self._ck(self.lib.tz_sdelta_probe(self.h, MODES[mode], b0, b1, int(bool(entropy)), SIZE_CODERS[coder], out.ctypes.data))
+        return out
+
+    def size_count_plane_buf(self, q, shape, channels=3, offset=True):
+        """tz_size_count_plane_buf: k_size_count over the plane symbols (TZ-SD2) of the int16 stack q of `shape` = (nt, H, W) pixels
+        of 3 elements, channels 3 or 1 (channel 0 alone) -> (uint64[3][SIZE_BINS + 8], bad): sdauto.count_of_plane."""
+        nt, h, w = (int(v) for v in shape)
+        if _numel(q) != nt * h * w * 3:
+            raise ValueError("q holds %d elements, %d x %d x %d x 3 wanted" % (_numel(q), nt, h, w))
+        counts = np.zeros((3, SIZE_BINS + HUFFR_NTOK), np.uint64)
+        bad = C.c_int(0)
+        self._ck(self.lib.tz_size_count_plane_buf(self.h, _ptr(q), nt, h, w, int(channels), int(bool(offset)), counts.ctypes.data,
+                                                  C.byref(bad)))
+        return counts, bool(bad.value)
+
+    def size_bits_plane_buf(self, q, shape, lens, dist, channels=3, offset=True):
+        """tz_size_bits_plane_buf: k_size_bits over the plane symbols of q -> (words, bits, bad): sdauto.bits_of_plane."""
+        nt, h, w = (int(v) for v in shape)
+        if _numel(q) != nt * h * w * 3:
+            raise ValueError("q holds %d elements, %d x %d x %d x 3 wanted" % (_numel(q), nt, h, w))
+        ln = np.ascontiguousarray(lens, np.uint8)
+        if ln.size != SIZE_BINS + HUFFR_NTOK:
+            raise ValueError("%d code lengths, %d + %d wanted" % (ln.size, SIZE_BINS, HUFFR_NTOK))
+        words, bits, bad = C.c_ulonglong(0), C.c_ulonglong(0), C.c_int(0)
+        self._ck(self.lib.tz_size_bits_plane_buf(self.h, _ptr(q), nt, h, w, int(channels), int(bool(offset)), ln.ctypes.data, int(dist),
+                                                 C.byref(words), C.byref(bits), C.byref(bad)))
         return int(words.value), int(bits.value), bool(bad.value)
 
     # ---- operator seams

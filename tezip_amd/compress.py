@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, quality, ratetarget, sdelta, sidecar, target, weights, zstd
+from . import _lib, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -275,8 +275,10 @@ def check_quant(quant, sharded=False):
 
 def check_sdelta(mode, sharded=False):
     """The refusals of --sdelta that a direct caller of run() can meet (tezip.py knows the others): None, or the message."""
+    if mode == sdauto.MODE:   # (its own refusals: sdauto.check)
+        return None
     if mode not in sdelta.MODES:
-        return "--sdelta takes one of %s, got %r" % (", ".join(sdelta.MODES), mode)
+        return "--sdelta takes one of %s, got %r" % (", ".join(sdelta.MODES + (sdauto.MODE,)), mode)
     if mode in ("channel", "plane") and sharded:
         return "--sdelta %s is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU" % mode
     return None
@@ -303,6 +305,16 @@ def decide_plane(ctx):
     ctx.set_delta_plane(1)
     print("sdelta: plane (TZ-SD2)")
     return True
+
+
+def decide_auto(ctx, channels, mode, bound, entropy, coder):
+    """--sdelta auto once the bound is known (definition TZ-SDA1, tezip_amd/sdauto.py): one quantiser run sizes the job's
+    entropy.dat under every layout the payload has (tz_sdelta_probe), the smallest is taken, and the context is set as
+    `--sdelta <chosen>` sets it -- the setters only drop a resident payload, so they may follow the rollout.
+    -> (strided, plane)."""
+    chosen, sizes = sdauto.choose(ctx.sdelta_probe(mode, bound, entropy, coder), coder)
+    print(sdauto.stdout_line(chosen, sizes))
+    return chosen == "channel" and decide_sdelta(ctx, channels), chosen == "plane" and decide_plane(ctx)
 
 
 def decide_gray(ctx, nt, files):
@@ -578,6 +590,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     SDELTA (--sdelta; NOT in the reference): "flat" (the default: every file, line and launch is what it is without it) or
     "plane": the spatial delta of the payload is the 2-D one, TZ-SD2 (left + up - upleft per frame and channel, wrapped to nine
     bits; tezip_amd/sdelta.py): mark 8 in the trailer, 9 with byte planes, with three channels or one; not with TARGET_RATIO; or
+    "auto" (CODER "huff", "huffr" or "huffd", no SHUFFLE, no TARGET_RATIO; definition TZ-SDA1, tezip_amd/sdauto.py): once the bound
+    is known, one tz_sdelta_probe on the rollout gives the exact size of entropy.dat under every layout the payload has, and the
+    job goes on as the SDELTA of the smallest (a tie: the earlier of flat, channel, plane): every file is that job's; or
     "channel": the spatial delta of a three-channel payload is taken at the channel stride (tezip_amd/sdelta.py); only the
     lossless back half of the coder changes, so the job decodes to exactly the images it decodes to without it.  `-u`
     recognises the stream by the mark in its trailer.  On a one-channel payload (GRAY on an all-gray job) the stride is 1 and
@@ -634,6 +649,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if SDELTA == "plane" and TARGET_RATIO is not None:   # likewise
         print("ERROR:", PLANE_NO_RATIO)
         sys.exit(2)
+    if SDELTA == sdauto.MODE:   # likewise
+        problem = sdauto.check(CODER, SHUFFLE, tzdist.active() is not None, TARGET_RATIO)
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     if SSIM and not REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         print("ERROR:", SSIM_NEEDS_REPORT)
         sys.exit(2)
@@ -757,6 +777,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     sys.exit(ratetarget.EXIT_UNREACHABLE)
                 BOUND_VALUE = [ratetarget.bound_of(k)]
                 print(ratetarget.stdout_line(search_doc))
+            if SDELTA == sdauto.MODE:   # the bound is known: size the layouts on the one rollout, then go on as the chosen job
+                strided, plane = decide_auto(ctx, channels, MODE, BOUND_VALUE if frame_bounds is None else [0.0], ENTROPY_RUN, CODER)
+                sd_mode = "plane" if plane else ("channel" if strided else "flat")
+                stages.mark("sdelta probe (device)")
             # (under frame bounds the bound of encode() is not read)
             _, table, _ = ctx.encode(MODE, BOUND_VALUE if frame_bounds is None else [0.0], ENTROPY_RUN, payload="resident", shuffle=SHUFFLE)
             stages.mark("encode (payload resident)", ctx)

@@ -1733,8 +1733,8 @@ static tz_layout layout_of(const tz_ctx* ctx) {
     return l;
 }
 
-// The entry points that serve no plane payload: sharded jobs, carries (a plane frame is coded on its own) and the size probe
-// (its kernels form flat and strided symbols only).
+// The entry points that serve no plane payload: sharded jobs, carries (a plane frame is coded on its own) and tz_size_probe
+// (tz_sdelta_probe sizes the plane payload, next to the other two, whatever the setting).
 static int no_plane(tz_ctx* ctx, const char* who) {
     if (ctx->delta_plane)
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve the 2-D spatial delta (tz_set_delta_plane(1)): sharded jobs, carries and the size probe are out of its scope", who);
@@ -3200,6 +3200,44 @@ extern "C" int tz_size_probe(tz_ctx* ctx, int mode, double b0, double b1, int en
     return size_run(ctx, layout, d_q, (size_t)nt * tz_frame_elems(layout, H, W), entropy, coder, out);
 }
 
+// `-c --sdelta auto` (NOT a reference feature; definition TZ-SDA1: DESIGN.md section 9, tezip_amd/sdauto.py): the quantised
+// deltas do not depend on the payload's spatial delta, so ONE delta + quantiser run serves the three layouts, and each costs
+// the two reads of size_run -- flat (or channel 0 alone), the channel stride, the 2-D plane TZ-SD2.  out[0..2] in that order;
+// n == 0: no candidate (the channel stride on a one-channel payload IS the flat delta).  The context's own spatial delta
+// (tz_set_delta_stride / tz_set_delta_plane) is neither read nor changed.
+extern "C" int tz_sdelta_probe(tz_ctx* ctx, int mode, double b0, double b1, int entropy, int coder, tz_size_record* out) {
+    tz_roctx_range roctx_("tz_sdelta_probe");
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    if (coder < 0 || coder > 2) return tz_fail(ctx, TZ_ERR_INVALID, "tz_sdelta_probe: coder %d, 0 (huff), 1 (huffr) or 2 (huffd) wanted", coder);
+    if (entropy & ~1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_sdelta_probe: byte planes are not Huffman-coded");
+    TZ_TRY(encode_check(ctx, "tz_sdelta_probe", mode));
+    const int channels = ctx->payload_channels;
+    if (channels == 1) {
+        tz_call gray_check(ctx);   // (a scope of its own: the probe reuses its blocks)
+        TZ_TRY(encode_all_gray(ctx));
+    }
+    const int nt = ctx->nt, H = ctx->H, W = ctx->W;
+    const size_t N = (size_t)nt * H * W * 3;
+    tz_call call(ctx);
+    uint8_t* d_mask;
+    int16_t* d_q;
+    TZ_TRY(call.alloc(nt, &d_mask));
+    TZ_TRY(tz_upload(ctx, d_mask, ctx->group_first.data(), nt));
+    TZ_TRY(call.alloc(N * 2, &d_q));
+    TZ_TRY(tzk_delta(ctx, ctx->d_pred, ctx->d_frames, d_mask, nt, H, W, ctx->Hp, ctx->Wp, d_q));
+    TZ_TRY(quantise_rollout(ctx, d_q, mode, b0, b1));
+    memset(out, 0, 3 * sizeof(*out));
+    tz_layout plane = {channels, 1};
+    plane.plane_h = H;
+    plane.plane_w = W;
+    const tz_layout cand[3] = {tz_layout{channels, 1}, tz_layout{3, 3}, plane};
+    for (int i = 0; i < 3; ++i) {
+        if (i == 1 && channels == 1) continue;
+        TZ_TRY(size_run(ctx, cand[i], d_q, (size_t)nt * tz_frame_elems(cand[i], H, W), entropy, coder, &out[i]));
+    }
+    return TZ_OK;
+}
+
 // the layout of a seam: 3 channels at stride 1 (flat) or 3 (channel stride), 1 channel at stride 1 (gray: q holds whole pixels)
 static int size_seam_layout(tz_ctx* ctx, size_t nq, int channels, int stride, tz_layout* layout, size_t* n) {
     if (!((channels == 3 && (stride == 1 || stride == 3)) || (channels == 1 && stride == 1)))
@@ -3210,12 +3248,51 @@ static int size_seam_layout(tz_ctx* ctx, size_t nq, int channels, int stride, tz
     return TZ_OK;
 }
 
+// the layout of a plane seam: nframes x H x W pixels, 3 channels, or channel 0 alone of q's whole pixels; q holds *nq elements
+static int size_seam_plane(tz_ctx* ctx, const char* who, int nframes, int H, int W, int channels, tz_layout* layout, size_t* n, size_t* nq) {
+    TZ_TRY(check_plane_dims(ctx, who, nframes, H, W, channels));
+    *layout = tz_layout{channels, 1};
+    layout->plane_h = H;
+    layout->plane_w = W;
+    *n = (size_t)nframes * tz_frame_elems(*layout, H, W);
+    *nq = (size_t)nframes * H * W * 3;
+    return TZ_OK;
+}
+
+static int size_count_seam(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t nq, size_t n, int apply_offset, unsigned long long* counts,
+                           int* bad);
+static int size_bits_seam(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t nq, size_t n, int apply_offset, const uint8_t* lens, int dist,
+                          unsigned long long* words, unsigned long long* bits, int* bad);
+
+extern "C" int tz_size_count_plane_buf(tz_ctx* ctx, const int16_t* q, int nframes, int H, int W, int channels, int apply_offset,
+                                       unsigned long long* counts, int* bad) {
+    if (!ctx || !q || !counts || !bad) return TZ_ERR_INVALID;
+    tz_layout layout;
+    size_t n, nq;
+    TZ_TRY(size_seam_plane(ctx, "tz_size_count_plane_buf", nframes, H, W, channels, &layout, &n, &nq));
+    return size_count_seam(ctx, layout, q, nq, n, apply_offset, counts, bad);
+}
+
+extern "C" int tz_size_bits_plane_buf(tz_ctx* ctx, const int16_t* q, int nframes, int H, int W, int channels, int apply_offset,
+                                      const uint8_t* lens, int dist, unsigned long long* words, unsigned long long* bits, int* bad) {
+    if (!ctx || !q || !lens || !words || !bits || !bad) return TZ_ERR_INVALID;
+    tz_layout layout;
+    size_t n, nq;
+    TZ_TRY(size_seam_plane(ctx, "tz_size_bits_plane_buf", nframes, H, W, channels, &layout, &n, &nq));
+    return size_bits_seam(ctx, layout, q, nq, n, apply_offset, lens, dist, words, bits, bad);
+}
+
 extern "C" int tz_size_count_buf(tz_ctx* ctx, const int16_t* q, size_t nq, int channels, int stride, int apply_offset,
                                  unsigned long long* counts, int* bad) {
     if (!ctx || !q || !counts || !bad) return TZ_ERR_INVALID;
     tz_layout layout;
     size_t n;
     TZ_TRY(size_seam_layout(ctx, nq, channels, stride, &layout, &n));
+    return size_count_seam(ctx, layout, q, nq, n, apply_offset, counts, bad);
+}
+
+static int size_count_seam(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t nq, size_t n, int apply_offset, unsigned long long* counts,
+                           int* bad) {
     if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
     tz_call call(ctx);
     const int16_t* d_q;
@@ -3238,6 +3315,11 @@ extern "C" int tz_size_bits_buf(tz_ctx* ctx, const int16_t* q, size_t nq, int ch
     tz_layout layout;
     size_t n;
     TZ_TRY(size_seam_layout(ctx, nq, channels, stride, &layout, &n));
+    return size_bits_seam(ctx, layout, q, nq, n, apply_offset, lens, dist, words, bits, bad);
+}
+
+static int size_bits_seam(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t nq, size_t n, int apply_offset, const uint8_t* lens, int dist,
+                          unsigned long long* words, unsigned long long* bits, int* bad) {
     if (n < 1 || n >= ((size_t)1 << 40)) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: %zu elements outside [1, 2^40)", n);
     tz_call call(ctx);
     const int16_t* d_q;

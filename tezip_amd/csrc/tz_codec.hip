@@ -4820,7 +4820,15 @@ int tzk_huff_dec(tz_ctx* ctx, const unsigned* d_chunk_off, const uint16_t* d_run
 // and stop in front of the rank remap: it is a bijection on the symbols present, so equality at a distance is the payload's
 // and the host permutes the literal counts.  Geometry and structure are k_huffd_count's: one lane per run of 256 symbols,
 // 16-byte loads, no match across a run start.
-enum { SZ_FLAT = 0, SZ_GRAY = 1, SZ_S3 = 2 };
+// Two more layouts form the symbols of the 2-D spatial delta TZ-SD2 (k_sdelta_plane; tz_sdelta_probe, `-c --sdelta auto`,
+// definition TZ-SDA1): SZ_P3 three channels, SZ_P1 channel 0 alone of q's whole pixels.  They walk in the overload of sz_walk
+// that takes the frame, which the kernels pass on as their last argument; the three layouts above pass nothing, and their
+// instructions are what they were.
+enum { SZ_FLAT = 0, SZ_GRAY = 1, SZ_S3 = 2, SZ_P3 = 3, SZ_P1 = 4 };
+template <bool VECU>
+struct sz_frame {   // the frame of the plane layouts: rows and columns (H * W * 3 < 2^32); VECU: the row above loads 16 bytes
+    int H, W;
+};
 
 // Walks the run of `cnt` symbols at symbol r0 (a multiple of 256) of the n symbols q yields: f(j, s) once per symbol, j its
 // place in the run.  q holds n elements, 3 n under SZ_GRAY; VEC: q is 16-byte aligned.
@@ -4862,11 +4870,82 @@ __device__ __forceinline__ void sz_walk(const int16_t* __restrict__ q, size_t n,
     }
 }
 
+// 8 consecutive symbols from symbol s0 of the plane layouts (SZ_P1: channel 0 of 8 pixels); VEC: the first is 16-byte aligned
+template <int LAY, bool VEC>
+__device__ __forceinline__ short8 sz_load8(const int16_t* __restrict__ q, size_t s0, size_t n) {
+    if (LAY == SZ_P1) {
+        const short8 a = hf_load8<VEC>(q, 3 * s0, 3 * n, (short)0), b = hf_load8<VEC>(q, 3 * s0 + 8, 3 * n, (short)0),
+                     c = hf_load8<VEC>(q, 3 * s0 + 16, 3 * n, (short)0);
+        short8 v;
+        v[0] = a[0], v[1] = a[3], v[2] = a[6], v[3] = b[1], v[4] = b[4], v[5] = b[7], v[6] = c[2], v[7] = c[5];
+        return v;
+    }
+    return hf_load8<VEC>(q, s0, n, (short)0);
+}
+
+// sz_walk for the plane layouts (the overload that takes the frame): symbol i <-> (f, y, x, c) is
+// wrap9(q[y, x-1] + q[y-1, x] - q[y-1, x-1] - q[y, x]), every neighbour outside the frame 0 (tezip_amd/sdelta.py encode_plane
+// at index i; x below counts symbols, so it runs over pixel and channel), then 1600 - sd when apply_offset.  A run starts
+// anywhere in a row and may cross rows and frames: the place of its first symbol comes from one division by the frame and one
+// by the row, and a counter pair follows from there.  The row above is a second load stream one row of symbols back -- in
+// the flattened stack that is so across a row's end too -- VECU: it is 16-byte aligned (q is, and a row is whole 16-byte
+// groups).  No index in front of q is formed: a group that starts inside row 0 of frame 0 loads element by element, and what
+// a load brings from the frame in front (y == 0) or the row's far end (x == 0) is never used.
+template <int LAY, bool VEC, bool VECU, class F>
+__device__ __forceinline__ void sz_walk(const int16_t* __restrict__ q, size_t n, size_t r0, int cnt, int apply_offset, sz_frame<VECU> g,
+                                        F&& f) {
+    constexpr int C = LAY == SZ_P3 ? 3 : 1;    // symbols per pixel
+    constexpr int QE = LAY == SZ_P3 ? 1 : 3;   // elements of q per symbol
+    const unsigned rs = (unsigned)g.W * C, fs = rs * (unsigned)g.H;   // symbols of a row and of a frame
+    const unsigned rem = (unsigned)(r0 % fs);
+    unsigned y = rem / rs, x = rem - y * rs;   // the row in the frame, the symbol in the row
+    short p1 = 0, p2 = 0, p3 = 0, u1 = 0, u2 = 0, u3 = 0;   // one, two and three symbols in front: this row, the row above
+    if (x >= 1) {   // (x >= k: symbol r0 - k is in this row, and with y > 0 symbol r0 - k - rs in the row above, same frame)
+        p1 = q[QE * (r0 - 1)];
+        if (y) u1 = q[QE * (r0 - 1 - rs)];
+    }
+    if (C == 3 && x >= 2) {
+        p2 = q[r0 - 2];
+        if (y) u2 = q[r0 - 2 - rs];
+    }
+    if (C == 3 && x >= 3) {
+        p3 = q[r0 - 3];
+        if (y) u3 = q[r0 - 3 - rs];
+    }
+    for (int j = 0; j < cnt; j += 8) {
+        const size_t s0 = r0 + j;
+        const short8 v = sz_load8<LAY, VEC>(q, s0, n);
+        short8 u;
+        if (s0 >= rs) {
+            u = sz_load8<LAY, VECU>(q, s0 - rs, n);
+        } else {   // the group starts inside row 0 of frame 0
+#pragma unroll
+            for (int k = 0; k < 8; ++k) u[k] = (s0 + k >= rs && s0 + k - rs < n) ? q[QE * (s0 + k - rs)] : (short)0;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const bool left = x >= (unsigned)C, up = y > 0;
+            const int cur = v[k], a = left ? (int)(C == 3 ? p3 : p1) : 0, b = up ? (int)u[k] : 0,
+                      c = left && up ? (int)(C == 3 ? u3 : u1) : 0;   // left, up, upleft
+            const int sd = ((a + b - c - cur + 256) & 511) - 256;
+            const int s = apply_offset ? TZ_OFFSET - sd : sd;
+            if (j + k < cnt) f(j + k, s);   // (uniform but for the last run)
+            p3 = p2, p2 = p1, p1 = v[k];
+            u3 = u2, u2 = u1, u1 = u[k];
+            if (++x == rs) {
+                x = 0;
+                if (++y == (unsigned)g.H) y = 0;
+            }
+        }
+    }
+}
+
 // k_huffd_count over the symbols of sz_walk: hist[0] the plain histogram (the one the rank table is built from, bin = symbol +
 // TZ_HUFF_COUNT_BIAS), hist[1] and hist[2] the token histograms at match distance 1 and 3.  No payload is written.
-template <int LAY, bool VEC>
+// (g: nothing, or the sz_frame of the plane layouts)
+template <int LAY, bool VEC, class... G>
 __global__ __launch_bounds__(256) void k_size_count(const int16_t* __restrict__ q, size_t n, size_t nruns, int apply_offset,
-                                                    unsigned long long* __restrict__ hist, tz_huff_meta* __restrict__ meta) {
+                                                    unsigned long long* __restrict__ hist, tz_huff_meta* __restrict__ meta, G... g) {
     constexpr int BINS = TZ_HUFF_COUNT_BINS + HFR_NTOK;
     __shared__ unsigned h[3 * BINS];
     for (int k = threadIdx.x; k < 3 * BINS; k += 256) h[k] = 0;
@@ -4875,7 +4954,7 @@ __global__ __launch_bounds__(256) void k_size_count(const int16_t* __restrict__ 
     for (size_t run = (size_t)blockIdx.x * 256 + threadIdx.x; run < nruns; run += (size_t)gridDim.x * 256) {
         const size_t r0 = run * HF_R;
         int h1 = 0, h2 = 0, h3 = 0, m1 = 0, m3 = 0;
-        sz_walk<LAY, VEC>(q, n, r0, (int)std::min((size_t)HF_R, n - r0), apply_offset, [&](int j, int s) {
+        sz_walk<LAY, VEC>(q, n, r0, (int)std::min((size_t)HF_R, n - r0), apply_offset, g..., [&](int j, int s) {
             const int b = s + TZ_HUFF_COUNT_BIAS, b1 = h1 + TZ_HUFF_COUNT_BIAS;
             const bool ok = b >= 0 && b < TZ_HUFF_COUNT_BINS;
             const bool match1 = j >= 1 && s == h1, match3 = j >= HFR_DIST && s == h3;
@@ -4921,9 +5000,9 @@ __global__ __launch_bounds__(256) void k_size_count(const int16_t* __restrict__ 
 // lengths in LDS -- len[bin] the code length of the symbol of that bin AFTER the rank remap (0: no code), then T_0..T_7 -- at
 // the match distance dist (0: every symbol a literal; 1 or 3: hfr_walk's tokens, length + raw bits).  Every chunk's sum is
 // rounded up to words and joins one 64-bit total; nothing else is written.
-template <int LAY, bool VEC>
+template <int LAY, bool VEC, class... G>
 __global__ __launch_bounds__(256) void k_size_bits(const int16_t* __restrict__ q, size_t n, size_t nruns, size_t nchunks, int apply_offset,
-                                                   const uint8_t* __restrict__ lens, int dist, tz_size_meta* __restrict__ meta) {
+                                                   const uint8_t* __restrict__ lens, int dist, tz_size_meta* __restrict__ meta, G... g) {
     __shared__ uint8_t len[TZ_HUFF_COUNT_BINS + HFR_NTOK];
     for (int k = threadIdx.x; k < (TZ_HUFF_COUNT_BINS + HFR_NTOK) / 4; k += 256) ((unsigned*)len)[k] = ((const unsigned*)lens)[k];
     __syncthreads();
@@ -4941,7 +5020,7 @@ __global__ __launch_bounds__(256) void k_size_bits(const int16_t* __restrict__ q
             bits += l + k;
             bad |= l == 0;
         };
-        sz_walk<LAY, VEC>(q, n, r0, (int)std::min((size_t)HF_R, n - r0), apply_offset, [&](int j, int s) {
+        sz_walk<LAY, VEC>(q, n, r0, (int)std::min((size_t)HF_R, n - r0), apply_offset, g..., [&](int j, int s) {
             const bool match = dist && j >= dist && s == (dist == 1 ? h1 : h3);
             if (match) {
                 ++m;
@@ -4969,8 +5048,17 @@ __global__ __launch_bounds__(256) void k_size_bits(const int16_t* __restrict__ q
     if (bad) atomicOr(&meta->bad, 1u);
 }
 
-static int sz_layout(tz_ctx* ctx, tz_layout layout, const int16_t* q, int* lay) {
+static int sz_layout(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t n, int* lay) {
     if ((uintptr_t)q & 1) return tz_fail(ctx, TZ_ERR_INVALID, "size probe: the delta stack must be 2-byte aligned");
+    if (layout.plane_h || layout.plane_w) {   // TZ-SD2: whole frames of plane_h x plane_w, three channels or channel 0 alone
+        const size_t fs = tz_frame_elems(layout, layout.plane_h, layout.plane_w);
+        if (layout.plane_h < 1 || layout.plane_w < 1 || (size_t)layout.plane_h * layout.plane_w > 0x0FFFFFFFull || layout.stride != 1 ||
+            (layout.channels != 3 && layout.channels != 1) || n % fs)
+            return tz_fail(ctx, TZ_ERR_INVALID, "size probe: no plane layout of %zu symbols in frames of %d x %d x %d", n, layout.plane_h,
+                           layout.plane_w, layout.channels);
+        *lay = layout.channels == 3 ? SZ_P3 : SZ_P1;
+        return TZ_OK;
+    }
     if (layout.channels == 3 && layout.stride == 1) *lay = SZ_FLAT;
     else if (layout.channels == 1 && layout.stride == 1) *lay = SZ_GRAY;
     else if (layout.channels == 3 && layout.stride == 3) *lay = SZ_S3;
@@ -4986,19 +5074,36 @@ static int sz_layout(tz_ctx* ctx, tz_layout layout, const int16_t* q, int* lay) 
                                            : (vec ? K<SZ_S3, true> : K<SZ_S3, false>);                                         \
         hipLaunchKernelGGL(kern, GRID, dim3(256), 0, ctx->stream, __VA_ARGS__);                                                \
     } while (0)
+// (the plane kernels: the row above is a 16-byte stream when q is one and a row of q, 3 W elements, is whole 16-byte groups)
+#define TZ_SIZE_LAUNCH_PLANE(K, GRID, ...)                                                                                     \
+    do {                                                                                                                       \
+        const bool vec = !((uintptr_t)q & 15), vecu = vec && layout.plane_w % 8 == 0;                                          \
+        const int H = layout.plane_h, W = layout.plane_w;                                                                      \
+        if (vecu) {                                                                                                            \
+            const auto kern = lay == SZ_P3 ? K<SZ_P3, true, sz_frame<true>> : K<SZ_P1, true, sz_frame<true>>;                  \
+            hipLaunchKernelGGL(kern, GRID, dim3(256), 0, ctx->stream, __VA_ARGS__, sz_frame<true>{H, W});                      \
+        } else {                                                                                                               \
+            const auto kern = lay == SZ_P3 ? (vec ? K<SZ_P3, true, sz_frame<false>> : K<SZ_P3, false, sz_frame<false>>)        \
+                                           : (vec ? K<SZ_P1, true, sz_frame<false>> : K<SZ_P1, false, sz_frame<false>>);       \
+            hipLaunchKernelGGL(kern, GRID, dim3(256), 0, ctx->stream, __VA_ARGS__, sz_frame<false>{H, W});                     \
+        }                                                                                                                      \
+    } while (0)
 
 // d_hist: 3 x (TZ_HUFF_COUNT_BINS + 8) counts, distance 0 | 1 | 3, of the n symbols q yields under the layout (cleared here)
 int tzk_size_count(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t n, int apply_offset, unsigned long long* d_hist,
                    tz_huff_meta* d_meta) {
     int lay;
-    TZ_TRY(sz_layout(ctx, layout, q, &lay));
+    TZ_TRY(sz_layout(ctx, layout, q, n, &lay));
     const size_t nruns = (n + HF_R - 1) / HF_R;
     TZ_HIP(ctx, hipMemsetAsync(d_hist, 0, 3 * (TZ_HUFF_COUNT_BINS + HFR_NTOK) * sizeof(unsigned long long), ctx->stream));
     TZ_HIP(ctx, hipMemsetAsync(d_meta, 0, sizeof(tz_huff_meta), ctx->stream));
     if (n == 0) return TZ_OK;
     tz_prof_scope ps(ctx, TZP_HUFF);
     const dim3 grid((unsigned)std::min((nruns + 255) / 256, (size_t)2048));
-    TZ_SIZE_LAUNCH(k_size_count, grid, q, n, nruns, apply_offset, d_hist, d_meta);
+    if (lay == SZ_P3 || lay == SZ_P1)
+        TZ_SIZE_LAUNCH_PLANE(k_size_count, grid, q, n, nruns, apply_offset, d_hist, d_meta);
+    else
+        TZ_SIZE_LAUNCH(k_size_count, grid, q, n, nruns, apply_offset, d_hist, d_meta);
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
@@ -5007,7 +5112,7 @@ int tzk_size_count(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t n, in
 int tzk_size_bits(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t n, int apply_offset, const uint8_t* d_lens, int dist,
                   tz_size_meta* d_meta) {
     int lay;
-    TZ_TRY(sz_layout(ctx, layout, q, &lay));
+    TZ_TRY(sz_layout(ctx, layout, q, n, &lay));
     if (dist != 0 && dist != 1 && dist != HFR_DIST) return tz_fail(ctx, TZ_ERR_INVALID, "huffman: match distance %d, the kernels know 1 and 3", dist);
     if ((uintptr_t)d_lens & 3) return tz_fail(ctx, TZ_ERR_INVALID, "size probe: the code lengths must be 4-byte aligned");
     const size_t nruns = (n + HF_R - 1) / HF_R, nchunks = (nruns + HF_CR - 1) / HF_CR;
@@ -5015,11 +5120,15 @@ int tzk_size_bits(tz_ctx* ctx, tz_layout layout, const int16_t* q, size_t n, int
     if (n == 0) return TZ_OK;
     tz_prof_scope ps(ctx, TZP_HUFF);
     const dim3 grid((unsigned)((nchunks + 3) / 4));
-    TZ_SIZE_LAUNCH(k_size_bits, grid, q, n, nruns, nchunks, apply_offset, d_lens, dist, d_meta);
+    if (lay == SZ_P3 || lay == SZ_P1)
+        TZ_SIZE_LAUNCH_PLANE(k_size_bits, grid, q, n, nruns, nchunks, apply_offset, d_lens, dist, d_meta);
+    else
+        TZ_SIZE_LAUNCH(k_size_bits, grid, q, n, nruns, nchunks, apply_offset, d_lens, dist, d_meta);
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
 #undef TZ_SIZE_LAUNCH
+#undef TZ_SIZE_LAUNCH_PLANE
 
 // ---------------------------------------------------------------------------- key-frame coder
 // Opt-in stage `--key-coder huff` (format TZK1: DESIGN.md section 9, tezip_amd/keycoder.py is the slow statement of it).

@@ -450,7 +450,8 @@ int tzk_huff_dec(tz_ctx*, const unsigned* d_chunk_off, const uint16_t* d_run_bit
                  const uint16_t* d_dec_tab4096, int A, int base, size_t n, int16_t* out, int dist);
 // The size of a candidate bound (tz_size_probe, TZ-TRATIO-1): both kernels form the payload symbols of `layout` from the
 // quantised delta stack q on the fly (n symbols: q holds n elements, 3 n under the one-channel layout; 2-byte aligned, 16 for
-// vector loads), in front of the rank remap.  tzk_size_count: tzk_huffd_count's three histograms of those symbols.
+// vector loads), in front of the rank remap.  A layout with plane_h, plane_w (tz_sdelta_probe, TZ-SDA1: stride 1, n whole frames)
+// yields the symbols of TZ-SD2, three channels or channel 0 alone of q's whole pixels.  tzk_size_count: tzk_huffd_count's three histograms of those symbols.
 // tzk_size_bits: the stream's size under d_lens -- TZ_HUFF_COUNT_BINS code lengths by bin (= symbol + TZ_HUFF_COUNT_BIAS; the
 // length of the symbol's rank, 0: no code), then the 8 token lengths -- at the match distance dist.
 struct tz_size_meta {            // device words k_size_bits leaves for the host

@@ -154,7 +154,12 @@ def _log2(m):
 def count_of(q, channels=3, stride=1, offset=True):
     """k_size_count: (uint64[3][BINS + 8], bad) -- row i at the match distance huffd.DISTS[i]: the literals by bin = symbol +
     BIAS, then T_0..T_7; bad: a symbol outside the bins (it is counted nowhere)."""
-    sym = symbols_of(q, channels, stride, offset).astype(np.int64)
+    return count_of_symbols(symbols_of(q, channels, stride, offset))
+
+
+def count_of_symbols(symbols):
+    """count_of over ready-made payload symbols (in front of the rank remap), whatever spatial delta formed them."""
+    sym = np.asarray(symbols).reshape(-1).astype(np.int64)
     b = sym + BIAS
     inside = (b >= 0) & (b < BINS)
     out = np.zeros((len(huffd.DISTS), BINS + NTOK), np.uint64)
@@ -168,7 +173,12 @@ def count_of(q, channels=3, stride=1, offset=True):
 def bits_of(q, lens, dist, channels=3, stride=1, offset=True):
     """k_size_bits: (words, bits, bad) under lens (BINS + 8 code lengths: by bin, then the tokens) at the match distance dist --
     bits per run of 256, per chunk of 64 runs, every chunk rounded up to 32-bit words; bad: a literal or token of length 0."""
-    sym = symbols_of(q, channels, stride, offset).astype(np.int64)
+    return bits_of_symbols(symbols_of(q, channels, stride, offset), lens, dist)
+
+
+def bits_of_symbols(symbols, lens, dist):
+    """bits_of over ready-made payload symbols (in front of the rank remap), whatever spatial delta formed them."""
+    sym = np.asarray(symbols).reshape(-1).astype(np.int64)
     ln = np.asarray(lens, np.int64).reshape(-1)
     if ln.size != BINS + NTOK:
         raise ValueError("%d code lengths, %d + %d wanted" % (ln.size, BINS, NTOK))

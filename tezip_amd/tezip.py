@@ -15,7 +15,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "tezip_amd"
 
-from . import compress, decompress, frametarget, target, train  # noqa: E402
+from . import compress, decompress, frametarget, sdauto, target, train  # noqa: E402
 
 # (short, long, argparse keywords) -- tezip.py:88-99
 FLAG_TABLE = (
@@ -76,8 +76,10 @@ FLAG_TABLE = (
     # --gray there; the reference cannot read such a file, -u recognises it by the mark in its trailer); plane = the 2-D predictor
     # left + up - upleft per frame and channel, TZ-SD2 (smaller on smooth colour data lossless and under --quant lattice, LARGER
     # under the greedy quantiser from abs 6 on and on sparse or gray sources: README; not with --sweep, --target-ratio or a
-    # sharded job)
-    (None, "--sdelta", dict(type=str, choices=("flat", "channel", "plane"), default=None, dest="sdelta")),
+    # sharded job); auto (with --coder huff / huffr / huffd) = the one of the three under which this job's entropy.dat is
+    # smallest, known exactly from one more pass over the quantised deltas (definition TZ-SDA1 in tezip_amd/sdauto.py; every file
+    # is what `--sdelta <chosen>` writes; not with --shuffle, --sweep, --target-ratio or a sharded job)
+    (None, "--sdelta", dict(type=str, choices=("flat", "channel", "plane", "auto"), default=None, dest="sdelta")),
     # not in the reference: with -c, IN PLACE of -m and -b: the job is `-m abs -b E` with the E (a multiple of 0.5) that a
     # bisection over the GPU's exact error sums finds for a sequence PSNR of at least DB (definition TZ-TPSNR-1 in
     # tezip_amd/target.py: one rollout, at most 9 probes; a boundary, not necessarily the largest such bound).  Also writes
@@ -241,13 +243,18 @@ def check_gray_flag(arg):
 
 
 def check_sdelta_flag(arg):
-    """--sdelta is valid with -c only; `channel` and `plane` need one single-GPU job without --sweep, `plane` one without
-    --target-ratio.  Returns None, or the message of a refusal."""
+    """--sdelta is valid with -c only; `channel`, `plane` and `auto` need one single-GPU job without --sweep, `plane` and `auto`
+    one without --target-ratio, `auto` a GPU coder and no --shuffle.  Returns None, or the message of a refusal."""
     mode = getattr(arg, "sdelta", None)
     if mode is None:
         return None
     if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
         return "--sdelta is valid with -c (--compress) only (-u recognises a channel-stride payload by itself)"
+    if mode == sdauto.MODE:   # the size of the job's own entropy.dat decides: a GPU coder, one job, one GPU, a given bound
+        if getattr(arg, "sweep", None) is not None:
+            return "--sdelta auto cannot be combined with --sweep: run the job you want with -w or -t"
+        return sdauto.check(getattr(arg, "coder", "zstd"), arg.shuffle, int(os.environ.get("WORLD_SIZE", "1")) > 1,
+                            getattr(arg, "target_ratio", None))
     if mode in ("channel", "plane") and getattr(arg, "sweep", None) is not None:
         return "--sdelta %s cannot be combined with --sweep" % mode
     if mode == "plane" and getattr(arg, "target_ratio", None) is not None:
@@ -495,7 +502,7 @@ def _main(arg):
                             CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
                             DIGESTS=bool(getattr(arg, "digests", False)), GRAY=bool(getattr(arg, "gray", False)),
                             SDELTA=getattr(arg, "sdelta", None) or "flat", SSIM=bool(getattr(arg, "ssim", False)), TARGET_PSNR=db)
-    if getattr(arg, "sdelta", None) in ("channel", "plane"):   # (flat is the job without the flag: the calls below)
+    if getattr(arg, "sdelta", None) in ("channel", "plane", "auto"):   # (flat is the job without the flag: the calls below)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
                             CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
