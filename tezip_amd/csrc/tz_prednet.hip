@@ -48,6 +48,7 @@ struct PackedConv {
     std::vector<float> h_W0;
     float* d_Wlat = nullptr;  // per-wave fragment image for k_convlat (same condition as d_Wimg), else null
     float* d_Wwino = nullptr; // TZ-PA2 stage image for k_wino (pack_wino), else null
+    float* d_Wwino2 = nullptr; // the same image packed dense for k_wino2 (choose_wino_forms: three-tile convolutions that take the two-quad stage), else null
     const float* d_zero = nullptr;
     float* d_bias = nullptr;
     int nslots = 0, ncols = 0, NT = 1, ncb = 1;
@@ -410,8 +411,14 @@ static void launch_conv16_t(tz_ctx* ctx, const ConvArgs& a, int nbatch) {
     hipLaunchKernelGGL((k_conv16<NT, EPI, UPS>), dim3(blocks), dim3(NTHR), 0, ctx->stream, a);
 }
 
-template <int NT, int EPI, bool UPS, bool NOSAME = false>
+// (TWOQ: the launch takes k_wino2, the two-quad stage over the dense image a0.Wwino -- launch_wino decides)
+template <int NT, int EPI, bool UPS, bool NOSAME = false, bool TWOQ = false>
 static int launch_wino_t(tz_ctx* ctx, const ConvArgs& a0, int nbatch) {
+    static_assert(!TWOQ || NT == 3, "k_wino2 is the three-tile form");
+    const void* kernel;
+    int lds;
+    if constexpr (TWOQ) kernel = (const void*)k_wino2<EPI, UPS, NOSAME>, lds = tzw::LDS2_BYTES;
+    else kernel = (const void*)k_wino<NT, EPI, UPS, NOSAME>, lds = tzw::LDS_BYTES;
     // (per instantiation and device: the attribute belongs to the function on a device, not to a context; a process that
     // opens contexts on several devices sets it on each)
     // (contexts of several threads may launch at once: the flag is atomic and is set only AFTER the attribute is, so a thread
@@ -420,7 +427,7 @@ static int launch_wino_t(tz_ctx* ctx, const ConvArgs& a0, int nbatch) {
     static std::atomic<bool> attr_set[64];
     const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 63;
     if (dev == 63 || !attr_set[dev].load(std::memory_order_acquire)) {
-        TZ_HIP(ctx, hipFuncSetAttribute((const void*)k_wino<NT, EPI, UPS, NOSAME>, hipFuncAttributeMaxDynamicSharedMemorySize, tzw::LDS_BYTES));
+        TZ_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_set[dev].store(true, std::memory_order_release);
     }
     // Column blocks per workgroup (one workgroup occupies a CU): the divisor of ncb with the shortest launch in items --
@@ -439,7 +446,8 @@ static int launch_wino_t(tz_ctx* ctx, const ConvArgs& a0, int nbatch) {
     if (a0.ipw > 0 && a.ncb % a0.ipw == 0) a.ipw = a0.ipw;                         // (the caller knows better: side launches want short workgroups)
     if (ctx->wino_ipw > 0 && a.ncb % ctx->wino_ipw == 0) a.ipw = ctx->wino_ipw;   // (TEZIP_WINO_IPW: measurements)
     const int blocks = (a.ncb / a.ipw) * tiles;
-    hipLaunchKernelGGL((k_wino<NT, EPI, UPS, NOSAME>), dim3(blocks), dim3(512), tzw::LDS_BYTES, ctx->stream, a);
+    if constexpr (TWOQ) hipLaunchKernelGGL((k_wino2<EPI, UPS, NOSAME>), dim3(blocks), dim3(512), tzw::LDS2_BYTES, ctx->stream, a);
+    else hipLaunchKernelGGL((k_wino<NT, EPI, UPS, NOSAME>), dim3(blocks), dim3(512), tzw::LDS_BYTES, ctx->stream, a);
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
@@ -464,13 +472,26 @@ static int launch_wino_ref_t(tz_ctx* ctx, const ConvArgs& a, int nbatch) {
 // three column tiles with the EPI_LSTM3 epilogue over it; everything else of the launch -- start values, biases (64 columns a
 // block), the dead-source prefix, ipw / ncb -- is the four-gate launch's.  The halves of a split gate convolution take it
 // too (EPI_RAW3, then EPI_LSTM3 from rows of 3 R columns in P_l).  k_wino_ref stays the four-gate cross-check.
+// A three-tile launch takes k_wino2 -- a stage of two channel quads over the dense image `dense` (choose_wino_forms) -- where
+// the walk fits its ring of three double slots: the executed stages of either source a multiple of 6, so that every phase
+// and every item starts in slot 0, and the first stage and the stages per column block even, so that the walk starts and
+// stays on whole double stages of the image.  Otherwise it takes k_wino with the arguments it has.
+static bool wino2q_walk(int s_same, int s_up, int first, int stride) {
+    return s_same + s_up > 0 && s_same % 6 == 0 && s_up % 6 == 0 && first % 2 == 0 && stride % 2 == 0;
+}
+
+// `wino3q`: the dense image of `wino3` -- or, without a `wino3`, of the convolution's own three-tile image a0.Wwino --, or null.
 static int launch_wino(tz_ctx* ctx, int NT, int epi, bool ups, const ConvArgs& a0, int nbatch, bool nosame = false, int dead = 0,
-                       const float* wino3 = nullptr) {
+                       const float* wino3 = nullptr, const float* wino3q = nullptr) {
     if (nosame) {   // the second launch of a split gate convolution (tz_model_predict_batch_dev, "E-part ahead")
         if (NT == 4 && epi == EPI_LSTM && ups && ctx->conv_impl && wino3) {   // (its start values: rows of 3 R columns, per item)
             ConvArgs a = a0;
             a.Wwino = wino3;
             a.ncols = 3 * a.Cout;
+            if (wino3q && wino2q_walk(0, a.src[1].C >> 2, a.wino_first, a.wino_stride)) {
+                a.Wwino = wino3q;
+                return launch_wino_t<3, EPI_LSTM3, true, true, true>(ctx, a, nbatch);
+            }
             return launch_wino_t<3, EPI_LSTM3, true, true>(ctx, a, nbatch);
         }
         if (NT == 4 && epi == EPI_LSTM && ups && ctx->conv_impl) return launch_wino_t<4, EPI_LSTM, true, true>(ctx, a0, nbatch);
@@ -490,16 +511,30 @@ static int launch_wino(tz_ctx* ctx, int NT, int epi, bool ups, const ConvArgs& a
         if (epi == EPI_POOL_ERR && !ups) return NT == 4 ? launch_wino_ref_t<4, EPI_POOL_ERR, false>(ctx, a, nbatch) : launch_wino_ref_t<3, EPI_POOL_ERR, false>(ctx, a, nbatch);
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "no TZ-PA2 reference kernel for NT=%d epilogue=%d upsampled=%d", NT, epi, (int)ups);
     }
+    // (the walk as the kernel will see it: behind the dead prefix, the part of the column block's stages this launch covers)
+    const bool walk2q = wino2q_walk(a.src[0].C >> 2, ups ? a.src[1].C >> 2 : 0, a.wino_first, a.wino_stride);
     if (NT == 4 && epi == EPI_LSTM && wino3) {
         a.Wwino = wino3;
+        if (wino3q && walk2q) {
+            a.Wwino = wino3q;
+            return ups ? launch_wino_t<3, EPI_LSTM3, true, false, true>(ctx, a, nbatch) : launch_wino_t<3, EPI_LSTM3, false, false, true>(ctx, a, nbatch);
+        }
         return ups ? launch_wino_t<3, EPI_LSTM3, true>(ctx, a, nbatch) : launch_wino_t<3, EPI_LSTM3, false>(ctx, a, nbatch);
     }
     if (NT == 4 && epi == EPI_RAW && wino3 && !ups) {   // the first half of a split: rows of 3 R columns out
         a.Wwino = wino3;
+        if (wino3q && walk2q) {
+            a.Wwino = wino3q;
+            return launch_wino_t<3, EPI_RAW3, false, false, true>(ctx, a, nbatch);
+        }
         return launch_wino_t<3, EPI_RAW3, false>(ctx, a, nbatch);
     }
     if (NT == 4 && epi == EPI_LSTM) return ups ? launch_wino_t<4, EPI_LSTM, true>(ctx, a, nbatch) : launch_wino_t<4, EPI_LSTM, false>(ctx, a, nbatch);
     if (NT == 4 && epi == EPI_RAW) return ups ? launch_wino_t<4, EPI_RAW, true>(ctx, a, nbatch) : launch_wino_t<4, EPI_RAW, false>(ctx, a, nbatch);
+    if (epi == EPI_POOL_ERR && !ups && NT == 3 && wino3q && walk2q) {
+        a.Wwino = wino3q;
+        return launch_wino_t<3, EPI_POOL_ERR, false, false, true>(ctx, a, nbatch);
+    }
     if (epi == EPI_POOL_ERR && !ups) return NT == 4 ? launch_wino_t<4, EPI_POOL_ERR, false>(ctx, a, nbatch) : launch_wino_t<3, EPI_POOL_ERR, false>(ctx, a, nbatch);
     return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "no TZ-PA2 kernel for NT=%d epilogue=%d upsampled=%d", NT, epi, (int)ups);
 }
@@ -590,8 +625,9 @@ static LatPlan lat_plan(const tz_ctx* ctx, int NT, int epi, bool ups, bool fullk
 // changes no bit behind the tap, whatever the chain started from (tests/test_dead0_oracle.py).  The
 // convolutions measure_dead found so carry the compact block-0 image (ConvArgs::Wblk0) and run k_conv16b<.., DEAD0>: the same
 // launch with 9 k-steps instead of 18 in block 0.  k_conv3x3 (tz_set_conv_impl(0)) walks all 8 floats: the unskipped cross-check.
-// (wino3: launch_wino)
-static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbatch, int wino_dead = 0, const float* wino3 = nullptr) {
+// (wino3, wino3q: launch_wino)
+static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbatch, int wino_dead = 0, const float* wino3 = nullptr,
+                       const float* wino3q = nullptr) {
     tz_prof_scope ps(ctx, TZP_CONV);
     bool ups = false, fullk = true;
     for (int s = 0; s < a.nsrc; ++s) {
@@ -628,7 +664,7 @@ static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbat
     // (the contract fixes the arithmetic per convolution; k_wino_ref is its cross-check, tz_set_conv_impl(0))
     if (a.Wwino && effective_contract(ctx) == 2 && fullk && (epi == EPI_LSTM || epi == EPI_POOL_ERR || epi == EPI_RAW)) {
         ps.sub = TZP_WINO;
-        return launch_wino(ctx, NT, epi, ups, a, nbatch, false, wino_dead, wino3);
+        return launch_wino(ctx, NT, epi, ups, a, nbatch, false, wino_dead, wino3, wino3q);
     }
     {
         const LatPlan lp = lat_plan(ctx, NT, epi, ups, fullk, a, nbatch);
@@ -1003,6 +1039,48 @@ static int measure_deadf(tz_ctx* ctx, tz_model* m) {
     return TZ_OK;
 }
 
+// Which k_wino convolutions take the two-quad stage (k_wino2, tz_wino_kernels.hip.h): the three-tile ones -- a gate convolution
+// without its forget gate (measure_deadf), an A convolution of 48 k columns -- whose executed stages, behind the dead prefix
+// (measure_dead), are a multiple of 6 per source (wino2q_walk; the halves of a split gate convolution then qualify too: their
+// first stage and stride are multiples of 4).  Those get the dense image next to the one k_wino and k_wino_ref read; a launch
+// that finds none takes k_wino.  The bench's model: every gate convolution and A_1 (12 + 24, 24 + 48, 48 and 12 stages); a
+// model with biases: A_1 at most.  TEZIP_WINO2Q=0 (read here, per prepare): none; TEZIP_WINO2Q_LOG=1: one line per convolution.
+static int choose_wino_forms(tz_ctx* ctx, tz_model* m) {
+    const char* env = getenv("TEZIP_WINO2Q");
+    const bool on = !env || atoi(env) != 0;
+    const bool log = getenv("TEZIP_WINO2Q_LOG") && atoi(getenv("TEZIP_WINO2Q_LOG"));
+    for (int l = 1; l < m->L; ++l)
+        for (int k = 0; k < 2; ++k) {   // the gate convolution of level l, then A_l
+            if (k == 1 && l == m->L - 1) continue;
+            PackedConv& pc = k == 0 ? (m->deadf[l] ? m->gate_nf[l] : m->gate_t1[l]) : m->a_conv[l];
+            pc.d_Wwino2 = nullptr;
+            if (!pc.d_Wwino) continue;   // not a k_wino convolution
+            const int s_full = (2 * m->stack[l]) / 4, s_up = k == 0 && l < m->L - 1 ? m->rstack[l + 1] / 4 : 0;
+            const int dead = k == 0 ? m->dead_gate[l] : m->dead_a[l];
+            const int s_same = dead > 0 && 16 * (dead + 1) <= 2 * m->stack[l] ? s_full - 4 * dead : s_full;   // (launch_wino)
+            const bool three = k == 0 ? m->deadf[l] : pc.NT == 3;
+            const bool walk = wino2q_walk(s_same, s_up, s_full - s_same, s_full + s_up);
+            if (on && three && walk) {
+                // (column blocks: gate_nf carries an image only -- pack_wino sets no ncb --; without the forget gate a block is
+                // 48 of 3 R columns where it was 64 of 4 R: as many blocks as gate_t1 has)
+                const long long nquads = (long long)(k == 0 ? m->gate_t1[l].ncb : pc.ncb) * (s_full + s_up);
+                TZ_TRY(dmalloc(ctx, m, (void**)&pc.d_Wwino2, (size_t)nquads * 3072 * 4));
+                hipLaunchKernelGGL(k_dense_stages, dim3((unsigned)std::min<long long>((nquads * 3072 + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                                   pc.d_Wwino, pc.d_Wwino2, nquads);
+                TZ_HIP(ctx, hipGetLastError());
+            }
+            if (log)
+                fprintf(stderr, "[tezip] k_wino stage, level %d %s: %d + %d stages, %s: %s\n", l, k == 0 ? "gates" : "A", s_same, s_up,
+                        three ? "three column tiles" : "four column tiles",
+                        pc.d_Wwino2 ? "two-quad (k_wino2)"
+                        : !three    ? "one-quad"
+                        : !on       ? "one-quad (TEZIP_WINO2Q=0)"
+                                    : "one-quad (stages not a multiple of 6)");
+        }
+    TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TZ_OK;
+}
+
 extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
     tz_roctx_range roctx_("tz_model_prepare");
     if (!ctx) return TZ_ERR_INVALID;
@@ -1181,6 +1259,7 @@ extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
     TZ_TRY(measure_uniform(ctx, m));   // (synchronises the stream)
     TZ_TRY(measure_dead(ctx, m));
     TZ_TRY(measure_deadf(ctx, m));
+    TZ_TRY(choose_wino_forms(ctx, m));
     m->prepared = true;
     return TZ_OK;
 }
@@ -1430,6 +1509,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
     }
     // a level without its forget gate (measure_deadf): the stage image its k_wino launches take, and the columns per pixel of P_l
     auto wino3 = [&](int l) -> const float* { return m->deadf[l] ? m->gate_nf[l].d_Wwino : nullptr; };
+    auto wino3q = [&](int l) -> const float* { return m->deadf[l] ? m->gate_nf[l].d_Wwino2 : nullptr; };   // (its dense image where k_wino2 takes it)
     auto pcols = [&](int l) { return m->deadf[l] ? 3 * m->rstack[l] : m->gate_t1[l].ncols; };
     auto epart_launch = [&](int l) -> int {   // the launch over E_l, on stream2, behind the A convolution that wrote E_l
         if (!ctx->ev_epart_src[l]) {
@@ -1452,7 +1532,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_epart_src[l], 0));
         hipStream_t main_stream = ctx->stream;
         ctx->stream = ctx->stream2;       // (the launchers and their profiling scopes take the context's stream)
-        int rc = launch_conv(ctx, 4, EPI_RAW, ge, n, m->dead_gate[l], wino3(l));
+        int rc = launch_conv(ctx, 4, EPI_RAW, ge, n, m->dead_gate[l], wino3(l), wino3q(l));
         ctx->stream = main_stream;
         TZ_TRY(rc);
         TZ_HIP(ctx, hipEventRecord(ctx->ev_epart_done[l], ctx->stream2));
@@ -1498,7 +1578,7 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
                 continue;
             }
         }
-        TZ_TRY(launch_conv(ctx, pc.NT, EPI_POOL_ERR, a, n, m->dead_a[l]));
+        TZ_TRY(launch_conv(ctx, pc.NT, EPI_POOL_ERR, a, n, m->dead_a[l], nullptr, pc.d_Wwino2));
         // The side launches go out behind the A convolution that writes the E of the HIGHEST split level (the A convolutions
         // below it fill the chip by themselves), the highest level first: its second half is the first one the critical path
         // will ask for.
@@ -1538,10 +1618,10 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
             TZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_epart_done[l], 0));
             tz_prof_scope ps(ctx, TZP_CONV);
             ps.sub = TZP_WINO;
-            TZ_TRY(launch_wino(ctx, 4, EPI_LSTM, true, a, n, true, 0, wino3(l)));
+            TZ_TRY(launch_wino(ctx, 4, EPI_LSTM, true, a, n, true, 0, wino3(l), wino3q(l)));
             continue;
         }
-        TZ_TRY(launch_conv(ctx, pc.NT, pc.NT == 4 ? EPI_LSTM : EPI_LSTM_PACKED, a, n, m->dead_gate[l], wino3(l)));
+        TZ_TRY(launch_conv(ctx, pc.NT, pc.NT == 4 ? EPI_LSTM : EPI_LSTM_PACKED, a, n, m->dead_gate[l], wino3(l), wino3q(l)));
     }
     {  // Ahat_0 at t1 = the prediction (prednet.py:268-271, 293-295)
         const PackedConv& pc = m->ahat0_t1;

@@ -198,65 +198,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     static_assert((EPI != EPI_LSTM3 && EPI != EPI_RAW3) || NT == 3, "three gates");
     static_assert(EPI != EPI_LSTM || NT == 4, "four gates");
     static_assert(EPI != EPI_RAW3 || !UPS, "the first half of a split walks the same-resolution source");
-    // columns of a block in the start values / biases, and where column tile t of this kernel sits among them: a three-gate
-    // launch that starts from G0 / the bias reads the four-gate rows; the second half of a split starts from what the first
-    // half wrote, 48 columns a block
-    constexpr bool G3 = (EPI == EPI_LSTM3 && !NOSAME) || EPI == EPI_RAW3;
-    constexpr int CBW = G3 ? 64 : 16 * NT;
-#define TZW_COLT(t) (G3 ? 16 * ((t) + ((t) > 0)) : 16 * (t))
-    using namespace tzw;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int mt = wv & 3, ph = wv >> 2;
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    // a workgroup walks over `ipw` column blocks of ITS tile one after the other (items): geometry, zero fill and the first
-    // DMA round trip happen once, the stream of stages runs on across the items (the first stages of the next item are
-    // issued under the last ones of the current)
-    const int ipw = a.ipw, ncbg = a.ncb / ipw;
-    const int cb0 = (bid % ncbg) * ipw;
-    bid /= ncbg;
-    const int ntiles = a.tiles_x * a.tiles_y;
-    const int tile = bid % ntiles, n = bid / ntiles;
-    const int ty0 = (tile / a.tiles_x) * 16, tx0 = (tile % a.tiles_x) * 16;
-    const int g = lane >> 4, r = lane & 15;
-#ifdef TZW_STAMPS
-    int stamp_id = blockIdx.x * a.ipw;   // one record per item
-#endif
-    TZW_STAMP(0)
-#ifdef TZW_STAMPS
-    if (tid == 0 && stamp_id < 4096) {   // where this workgroup runs: (XCC, SE, SH, CU) -- slot 7
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
-        for (int q = 0; q < a.ipw && stamp_id + q < 4096; ++q) tzw_stamps[(a.ncb & 3) | (EPI == EPI_LSTM ? 4 : 0)][stamp_id + q][7] = ((unsigned long long)(xcc & 15) << 32) | hw;
-    }
-#endif
-    const unsigned sbase = lds_addr(smem);
-    const int S1 = NOSAME ? 0 : a.src[0].C >> 2;          // stages of the same-resolution source
-    const int S = S1 + (UPS ? a.src[1].C >> 2 : 0);       // ... and of the upsampled one
-    const int SI = a.wino_stride ? a.wino_stride : S;     // stages per column block in the image (a launch may walk a part)
-
-    // ---- DMA geometry, once per workgroup.  Same-resolution plane: piece wv = slots 41 wv ..; slot = row * 18 + column
-    // with the columns stored evens first.  Half-resolution plane: piece wv = slots 13 wv .., slot = row * 10 + column.
-    unsigned poff, uoff = 0;
-    unsigned long long pmask, umask = 0;
-    {
-        const int slot = wv * PP + lane;
-        const int py = slot / WPW, xs = slot - py * WPW;
-        const int px = xs < WPW / 2 ? 2 * xs : 2 * (xs - WPW / 2) + 1;
-        const int yy = ty0 - 1 + py, xx = tx0 - 1 + px;
-        const bool ok = lane < PP && slot < WPW * WPW && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-        poff = ok ? 4u * (unsigned)((yy * a.W + xx) * a.src[0].pstride) : 0u;
-        pmask = __ballot(ok);
-    }
-    if (UPS) {
-        const int slot = wv * UP + lane;
-        const int Y = slot / WLW, X = slot - Y * WLW;
-        const int ly = (ty0 >> 1) - 1 + Y, lx = (tx0 >> 1) - 1 + X;
-        const bool ok = lane < UP && slot < WLW * WLW && ly >= 0 && ly < (a.H >> 1) && lx >= 0 && lx < (a.W >> 1);
-        uoff = ok ? 4u * (unsigned)((ly * (a.W >> 1) + lx) * a.src[1].pstride) : 0u;
-        umask = __ballot(ok);
-    }
-    const unsigned lane16 = lane * 16;
+    // (the four sections this kernel shares with k_wino2, which differs in its stage loops alone, are the text of the
+    // tz_wino_*.inc.h files: the same object code here as when they stood in this body)
+#define TZW_XOFF (NS * SLOT)   // the exchange areas sit behind the ring
+#include "tz_wino_geometry.inc.h"
     // ---- the DMA stream.  Stage si goes into ring slot si mod 4: 2 KB of weights + one patch piece per wave = 3 DMA
     // instructions.  The stage loops are unrolled once per ring slot, so every LDS address below is a constant; the global
     // addresses are running scalar pointers (the first form recomputed them from the stage number: ~40 scalar instructions
@@ -313,58 +258,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     unsigned adA[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) adA[k] = sbase + (unsigned)k * SLOT + abase;
-    auto read_d = [&](unsigned ad, f32x2 (&d)[3][2]) {
-        read_rows<0>(ad, d);
-        read_rows<1>(ad, d);
-        read_rows<2>(ad, d);
-    };
-    // B^T d B for the wave's two transform rows (same association as the oracle): columns first, then rows
-    auto transform = [&](const f32x2 (&d)[3][2], float (&V)[8]) {
-#if TZW_PK
-        // 10 packed instructions instead of 20: per row T1 = (t0, t3) = (d0, d1) - (d2, d3), T2 = (t1, t2) = (d1 + d2, d2 - d1);
-        // then the rows the same way on the pairs
-        f32x2 T1[3], T2[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            T1[k] = pk_sub(d[k][0], d[k][1]);
-            T2[k] = pk_cross(d[k][0], d[k][1]);
-        }
-        f32x2 a03, a12, b03, b12;   // (V[.][0], V[.][3]), (V[.][1], V[.][2]) of the wave's two transform rows
-        if (ph == 0) {   // rows 0, 1, 2 of the patch: V[0] = t0 - t2, V[1] = t1 + t2
-            a03 = pk_sub(T1[0], T1[2]);
-            a12 = pk_sub(T2[0], T2[2]);
-            b03 = pk_add(T1[1], T1[2]);
-            b12 = pk_add(T2[1], T2[2]);
-        } else {         // rows 1, 2, 3: V[2] = t2 - t1, V[3] = t1 - t3
-            a03 = pk_sub(T1[1], T1[0]);
-            a12 = pk_sub(T2[1], T2[0]);
-            b03 = pk_sub(T1[0], T1[2]);
-            b12 = pk_sub(T2[0], T2[2]);
-        }
-        V[0] = a03[0]; V[3] = a03[1]; V[1] = a12[0]; V[2] = a12[1];
-        V[4] = b03[0]; V[7] = b03[1]; V[5] = b12[0]; V[6] = b12[1];
-        return;
-#endif
-        float t[3][4];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float d0 = d[k][0][0], d2 = TZW_PK ? d[k][1][0] : d[k][0][1], d1 = TZW_PK ? d[k][0][1] : d[k][1][0], d3 = d[k][1][1];
-            t[k][0] = fsub(d0, d2);
-            t[k][1] = fadd(d1, d2);
-            t[k][2] = fsub(d2, d1);
-            t[k][3] = fsub(d1, d3);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (ph == 0) {   // rows 0, 1, 2 of the patch: V[0] = t0 - t2, V[1] = t1 + t2
-                V[j] = fsub(t[0][j], t[2][j]);
-                V[4 + j] = fadd(t[1][j], t[2][j]);
-            } else {         // rows 1, 2, 3: V[2] = t2 - t1, V[3] = t1 - t3
-                V[j] = fsub(t[1][j], t[0][j]);
-                V[4 + j] = fsub(t[0][j], t[2][j]);
-            }
-        }
-    };
+#include "tz_wino_transform.inc.h"
 
     // stages 0 and 1 landed for everyone (from the second item on the last stage of the item before has seen to that)
     if (nlead == LEAD) wait_vm_stages<LEAD - 2>();
@@ -476,105 +370,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     TZW_STAMP(2)
 
-    // ---- output transform, oracle order, one column tile per round (everything of a round dies with it: the first form
-    // computed all row sums ahead and the compiler parked them in AGPRs -- 1100 vector instructions per wave with the matrix
-    // pipes idle; this one has ~450).
-    //   y[0][b] = ((init + Z[0][b]) + Z[1][b]) + Z[2][b] belongs to the wave with rows 0, 1 and needs Z[2] of its partner;
-    //   y[1][b] = ((init + Z[1][b]) - Z[2][b]) - Z[3][b] belongs to the wave with rows 2, 3 and needs Z[1]:
-    // exchanged through LDS, two areas of 16 KB in turn, so that one barrier a round is enough (a wave that writes area
-    // t & 1 again in round t + 2 has passed the barrier of round t + 1, behind which nobody reads round t's data any more)
-    f32x4 Y[2][4];
-    {
-        // accumulator start of this wave's outputs: row a = ph of the tiles, columns b = 0, 1; register e <-> tile (g, e)
-        f32x4 in0[NT], in1[NT];
-        {
-            const int y = ty0 + 8 * (mt >> 1) + 2 * g + ph + per_item, x0 = tx0 + 8 * (mt & 1);
-            // (uniform) away from the border of the plane G0 is one value per column (ConvArgs::init_u): NT loads and a
-            // splat, the bias branch below, instead of 8 NT scattered ones
-            const bool uni_init = tile_uniform(a.init_u, a.init_ring, ty0, tx0, a.H, a.W);
-            if (a.init && !uni_init && !(TZW_ABL & 64)) {
-                const float* initn = a.init + (long long)n * a.init_nstride;   // (0 for the per-model G0; a split launch's start values are per item)
-                if (ty0 + 16 <= a.H && tx0 + 16 <= a.W) {   // (uniform) the whole tile inside the image: one lane offset, uniform steps
-                    // (uniform) where G0 repeats tile by tile the reference tile stands in for this one (ConvArgs::init_tring):
-                    // every workgroup of the launch then reads the same block
-                    const bool rep = tile_uniform(a.init, a.init_tring, ty0, tx0, a.H, a.W);
-                    const int yr = rep ? y - ty0 + ref_tile_origin(a.H) : y, xr = rep ? x0 - tx0 + ref_tile_origin(a.W) : x0;
-                    const float* ip = initn + (unsigned)((yr * a.W + xr) * a.ncols + cb * CBW + r);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float* ie = ip + (unsigned)(2 * e * a.ncols);
-#pragma unroll
-                        for (int t = 0; t < NT; ++t) {
-                            in0[t][e] = ie[TZW_COLT(t)];
-                            in1[t][e] = ie[a.ncols + TZW_COLT(t)];
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        const int col = cb * CBW + TZW_COLT(t) + r;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int x = x0 + 2 * e;
-                            const bool ok = y < a.H && x < a.W;   // (W even wherever tiles are cut: x + 1 < W too)
-                            const float* ip = initn + ((long long)(ok ? y * a.W + x : 0)) * a.ncols + col;
-                            in0[t][e] = ip[0];
-                            in1[t][e] = ip[x + 1 < a.W && ok ? a.ncols : 0];
-                        }
-                    }
-                }
-            } else {
-                const float* bu = uni_init && !(TZW_ABL & 64) ? a.init_u : a.bias;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const float b = bu[cb * CBW + TZW_COLT(t) + r];
-                    in0[t] = in1[t] = (f32x4){b, b, b, b};
-                }
-            }
-        }
-        f32x4* xo = (f32x4*)(smem + NS * SLOT) + (wv * 2) * 64 + lane;
-        const f32x4* xi = (const f32x4*)(smem + NS * SLOT) + ((wv ^ 4) * 2) * 64 + lane;
-        if (NOSAME) {   // the chains as the launch over the same-resolution source left them
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                Y[0][t] = in0[t];
-                Y[1][t] = in1[t];
-            }
-            // into their accumulation registers HERE, two wait states ahead of any MFMA that takes them as C (the asm MFMAs get
-            // no hazard handling: a v_accvgpr_write sunk to right in front of the first stage would be read too early)
-            static_assert(!NOSAME || EPI == EPI_LSTM || EPI == EPI_LSTM3, "the split launch exists for gate convolutions");
-            if (NT == 4) asm volatile("" : "+a"(Y[0][0]), "+a"(Y[0][1]), "+a"(Y[0][2]), "+a"(Y[0][3]), "+a"(Y[1][0]), "+a"(Y[1][1]), "+a"(Y[1][2]), "+a"(Y[1][3]));
-            else asm volatile("" : "+a"(Y[0][0]), "+a"(Y[0][1]), "+a"(Y[0][2]), "+a"(Y[1][0]), "+a"(Y[1][1]), "+a"(Y[1][2]));
-            asm volatile("s_nop 1" ::: "memory");
-        } else
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            constexpr int XA = XBYTES / 2 / 16;   // (f32x4 units) the second area
-            const int xa = (t & 1) * XA;
-            // (the accumulators of this round are read HERE: hoisted, they and the start values went through ~300 register
-            // moves between VGPRs and AGPRs)
-            asm volatile("" : "+a"(D[0][t]), "+a"(D[1][t]), "+a"(D[2][t]), "+a"(D[3][t]), "+a"(D[4][t]), "+a"(D[5][t]), "+a"(D[6][t]), "+a"(D[7][t]));
-            // row sums of the wave's two transform rows
-            const f32x4 za0 = (D[0][t] + D[1][t]) + D[2][t], za1 = (D[1][t] - D[2][t]) - D[3][t];
-            const f32x4 zb0 = (D[4][t] + D[5][t]) + D[6][t], zb1 = (D[5][t] - D[6][t]) - D[7][t];
-            if (ph == 0) {   // (uniform)
-                xo[xa] = zb0;
-                xo[xa + 64] = zb1;
-            } else {
-                xo[xa] = za0;
-                xo[xa + 64] = za1;
-            }
-            if (!(TZW_ABL & 128)) __syncthreads();
-            const f32x4 p0 = xi[xa], p1 = xi[xa + 64];
-            if (ph == 0) {
-                Y[0][t] = ((in0[t] + za0) + zb0) + p0;
-                Y[1][t] = ((in1[t] + za1) + zb1) + p1;
-            } else {
-                Y[0][t] = ((in0[t] + p0) - za0) - zb0;
-                Y[1][t] = ((in1[t] + p1) - za1) - zb1;
-            }
-        }
-    }
+#include "tz_wino_output.inc.h"
 
     TZW_STAMP(3)
     // ---- the upsampled source: every output's chain goes on with its collapsed taps.  Stage = one channel quad; the
@@ -653,221 +449,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef TZW_WAIT
 #undef TZW_COLT
 
-    // ---- epilogues.  This wave's outputs: pixel row a = ph of its 16 tiles, columns b = 0, 1: Y[b][column tile][e],
-    // accumulator row 4 g + e = tile (tyl = g, txl = e)
-    const int oy = ty0 + 8 * (mt >> 1) + 2 * g + ph + per_item;
-    if (EPI == EPI_RAW || EPI == EPI_RAW3) {
-        // (EPI_RAW3: the rows written are 3 Cout wide -- [i | g | o] x 16 per block --, the rows of the start values 4 Cout = a.ncols)
-        const int ocols = EPI == EPI_RAW3 ? 3 * a.Cout : a.ncols;
-        float* on = a.out0 + (long long)n * a.out0_nstride;
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int x = tx0 + 8 * (mt & 1) + 2 * e + b;
-                if (oy < a.H && x < a.W) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) on[((long long)oy * a.W + x) * ocols + cb * (16 * NT) + 16 * t + r] = Y[b][t][e];
-                }
-            }
-    } else if (EPI == EPI_LSTM || EPI == EPI_LSTM3) {
-        // columns of this block: [i | f | g | o] x 16 channels of channel group cb (prednet.py:255-259):
-        // c = f * c_prev + i * g ; r = o * tanh(c)
-        // EPI_LSTM3: [i | g | o], c_prev = +0 everywhere: f * (+0) = +0 for every non-NaN f, so c = (+0) + i * g -- a real
-        // float32 addition (it turns i * g = -0 into +0, as the four-gate form does), no cell state is loaded
-        constexpr bool F3 = EPI == EPI_LSTM3;
-        constexpr int TG = F3 ? 1 : 2 % NT, TO = F3 ? 2 : 3 % NT;   // column tiles of gates g and o
-        const int ch = cb * 16 + r, R = a.Cout;
-        float* o0 = a.out0 + (long long)n * a.out0_nstride;
-        float* o1 = a.out1 ? a.out1 + (long long)n * a.out1_nstride : nullptr;
-        if (ty0 + 16 <= a.H && tx0 + 16 <= a.W && !(TZW_ABL & 512)) {
-            // (uniform) the whole tile inside the image: ONE lane offset for the eight outputs of a lane, the steps between
-            // them uniform -- scalar base + 32-bit lane offset addressing, no per-output predicates (the general form below
-            // spends ~25 instructions per output on 64-bit addresses and exec masks; in a serial section, with the matrix
-            // pipes idle, instructions are what costs)
-            const unsigned voff = 4u * (unsigned)((oy * a.W + tx0 + 8 * (mt & 1)) * R + ch);
-            const char* pc = (const char*)a.aux;
-            char* p0 = (char*)o0;
-            char* p1 = (char*)o1;
-            float cpv[2][4];
-            if (F3) {
-                // (no cell state to load)
-            } else if (tile_uniform(a.aux_u, a.aux_ring, ty0, tx0, a.H, a.W) && !(TZW_ABL & 256)) {
-                // (uniform) away from the border of the plane the cell state is one value per channel: one load
-                const float cu = a.aux_u[ch];
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) cpv[b][e] = cu;
-            } else {
-                // (uniform) where the cell state repeats tile by tile: the reference tile's values (ConvArgs::aux_tring)
-                const unsigned roff = 4u * (unsigned)(((ref_tile_origin(a.H) - ty0) * a.W + ref_tile_origin(a.W) - tx0) * R);
-                const unsigned coff = tile_uniform(a.aux, a.aux_tring, ty0, tx0, a.H, a.W) ? voff + roff : voff;
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        cpv[b][e] = a.aux && !(TZW_ABL & 256) ? *(const float*)(pc + (size_t)(2 * e + b) * R * 4 + coff) : 0.0f;
-            }
-#ifdef TZW_STAMPS
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            TZW_STAMP(6)
-#endif
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float gi = tz_hard_sigmoid(Y[b][0][e]);
-                    const float gg = tz_tanh(Y[b][TG][e]);
-                    const float go = tz_hard_sigmoid(Y[b][TO][e]);
-                    const float t2 = gi * gg;
-                    float c;
-                    if (F3) {
-                        c = fadd_zero(t2);
-                    } else {
-                        const float gf = tz_hard_sigmoid(Y[b][1 % NT][e]);
-                        const float t1 = gf * cpv[b][e];
-                        c = t1 + t2;
-                    }
-                    const float rr = go * tz_tanh(c);
-                    *(float*)(p0 + (size_t)(2 * e + b) * R * 4 + voff) = rr;
-                    if (o1) *(float*)(p1 + (size_t)(2 * e + b) * R * 4 + voff) = c;
-                }
-        } else {
-        long long pix[2][4];
-        bool ok[2][4];
-        float cp[2][4];
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int x = tx0 + 8 * (mt & 1) + 2 * e + b;
-                ok[b][e] = oy < a.H && x < a.W;
-                pix[b][e] = ok[b][e] ? (long long)oy * a.W + x : 0;
-                // (Asking for these ahead of the output transform through asm loads -- to hide their round trip -- is NOT
-                // safe: the compiler is free to reuse an asm load's destination register before the data lands, and did:
-                // the late write then hit an address register, a memory fault in the bench.  Plain loads, at their use.)
-                cp[b][e] = !F3 && a.aux && !(TZW_ABL & 256) ? a.aux[pix[b][e] * R + ch] : 0.0f;
-            }
-#ifdef TZW_STAMPS
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        TZW_STAMP(6)
-#endif
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (TZW_ABL & 512) {
-                    if (ok[b][e]) {
-                        o0[pix[b][e] * R + ch] = Y[b][0][e] + Y[b][1 % NT][e] + cp[b][e];
-                        if (o1) o1[pix[b][e] * R + ch] = Y[b][2 % NT][e] + Y[b][3 % NT][e];
-                    }
-                    continue;
-                }
-                const float gi = tz_hard_sigmoid(Y[b][0][e]);
-                const float gg = tz_tanh(Y[b][TG][e]);
-                const float go = tz_hard_sigmoid(Y[b][TO][e]);
-                const float t2 = gi * gg;
-                float c;
-                if (F3) {
-                    c = fadd_zero(t2);
-                } else {
-                    const float gf = tz_hard_sigmoid(Y[b][1 % NT][e]);
-                    const float t1 = gf * cp[b][e];
-                    c = t1 + t2;
-                }
-                const float rr = go * tz_tanh(c);
-                if (ok[b][e]) {
-                    o0[pix[b][e] * R + ch] = rr;
-                    if (o1) o1[pix[b][e] * R + ch] = c;
-                }
-            }
-        }
-    } else if (EPI == EPI_POOL_ERR) {
-        // prednet.py:289-291 then 274-277 of the next level: A = maxpool2x2(relu(conv)) -- the pooling window IS the tile --,
-        // e = [relu(Ahat0 - A), relu(A - Ahat0)] at the pooled resolution.  The wave holds one row of every window; the
-        // partner the other: wave ph = 0 finishes column tiles 0, 1, wave ph = 1 the rest
-        // (ConvArgs::dead_half: Ahat0 is +-0 over the plane -- no load of it, no subtraction, the live half A alone stored)
-        const int H2 = a.H >> 1, W2 = a.W >> 1, C = a.Cout;
-        float* o = a.out0 + (long long)n * a.out0_nstride;
-        f32x4 m[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float v0 = tz_relu(Y[0][t][e]), v1 = tz_relu(Y[1][t][e]);
-                m[t][e] = v1 > v0 ? v1 : v0;
-            }
-        // (the exchange area the last round of the output transform did NOT use: a partner may still be reading that one)
-        constexpr int XP = (NT & 1) * (XBYTES / 2 / 16);
-        f32x4* xo = (f32x4*)(smem + NS * SLOT) + XP + (wv * 2) * 64 + lane;
-        const f32x4* xi = (const f32x4*)(smem + NS * SLOT) + XP + ((wv ^ 4) * 2) * 64 + lane;
-        // (no run-time indices into m[]: it has to stay in registers)
-        xo[0] = ph == 0 ? m[2] : m[0];                       // the column tiles the partner finishes
-        xo[64] = ph == 0 ? m[NT - 1] : m[1];                 // (NT = 3: the second one of wave 0 is not used)
-        __syncthreads();
-        const f32x4 q0 = xi[0], q1 = xi[64];
-        const int yp = (ty0 >> 1) + 4 * (mt >> 1) + g + per_item;
-        if (ty0 + 16 <= a.H && tx0 + 16 <= a.W && (cb + 1) * (16 * NT) <= C && !(TZW_ABL & 512)) {
-            // (uniform) the whole tile inside the image and the whole column block inside the stack: ONE lane offset per
-            // array for the outputs of a lane, uniform steps between them -- scalar base + 32-bit lane offset addressing, no
-            // per-output predicates (what the LSTM epilogue got in round 4; the general form below spends ~25 instructions
-            // per output on 64-bit addresses and exec masks, in a serial section with the matrix pipes idle)
-            const unsigned pix = (unsigned)(yp * W2 + (tx0 >> 1) + 4 * (mt & 1));
-            const unsigned colw = (unsigned)(cb * (16 * NT) + r);
-            const char* ph_ = (const char*)a.aux;
-            char* po = (char*)o;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (ph == 1 && 2 + k >= NT) break;
-                const int t = (ph == 0 ? 0 : 2) + k;
-                const f32x4 mine = ph == 0 ? m[k] : m[(2 + k) % NT], other = k == 0 ? q0 : q1;
-                const unsigned hoff = 4u * (pix * (unsigned)C + colw + 16u * t), ooff = 4u * (pix * 2u * (unsigned)C + colw + 16u * t);
-                if (a.dead_half) {   // (uniform) Ahat0 = +-0 over the plane and mm >= +0: e = [+0 | mm], the +0 is there already
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float mm = other[e] > mine[e] ? other[e] : mine[e];
-                        *(float*)(po + (size_t)e * C * 8 + (size_t)C * 4 + ooff) = mm;
-                    }
-                    continue;
-                }
-                float hv[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) hv[e] = *(const float*)(ph_ + (size_t)e * C * 4 + hoff);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float mm = other[e] > mine[e] ? other[e] : mine[e];
-                    const float d1 = hv[e] - mm, d2 = mm - hv[e];
-                    *(float*)(po + (size_t)e * C * 8 + ooff) = tz_relu(d1);
-                    *(float*)(po + (size_t)e * C * 8 + (size_t)C * 4 + ooff) = tz_relu(d2);
-                }
-            }
-        } else
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            if (ph == 1 && 2 + k >= NT) break;               // wave 1 finishes column tiles 2 .. NT - 1, wave 0 tiles 0, 1
-            const int t = (ph == 0 ? 0 : 2) + k;
-            const f32x4 mine = ph == 0 ? m[k] : m[(2 + k) % NT], other = k == 0 ? q0 : q1;
-            const int ch = cb * (16 * NT) + 16 * t + r;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int xp = (tx0 >> 1) + 4 * (mt & 1) + e;
-                const bool okp = yp < H2 && xp < W2 && ch < C;
-                const long long pp = okp ? (long long)yp * W2 + xp : 0;
-                const float mm = other[e] > mine[e] ? other[e] : mine[e];
-                if (a.dead_half) {   // (uniform)
-                    if (okp) o[pp * 2 * C + C + ch] = mm;
-                    continue;
-                }
-                const float h = a.aux[okp ? pp * C + ch : 0];
-                const float d1 = h - mm, d2 = mm - h;
-                if (okp) {
-                    o[pp * 2 * C + ch] = tz_relu(d1);
-                    o[pp * 2 * C + C + ch] = tz_relu(d2);
-                }
-            }
-        }
-    }
+#include "tz_wino_epilogue.inc.h"
+#undef TZW_XOFF
 #ifdef TZW_STAMPS
     TZW_STAMP(5)
     if (more) {
@@ -876,6 +459,287 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 #endif
     }   // items
+}
+
+// k_wino2: the three-tile forms of k_wino (NT = 3) with a stage of TWO consecutive channel quads.  A stage carries a fixed
+// cost -- the barrier, the counted vmcnt wait, the DMA issue burst, the loop bookkeeping -- that does not shrink with the number
+// of column tiles; here it is paid once per 48 MFMAs of a wave instead of once per 24.  Everything outside the stage loops is
+// k_wino's text (the tz_wino_*.inc.h sections); every chain is still one fmaf chain over the channels in ascending order
+// (within a stage all of quad q is multiplied before quad q + 1), so the bits are k_wino's.
+//   Stage image (tz_prednet.hip choose_wino_forms): per channel quad 12 KB, [ph][read 6][lane][4]: fragment v = 3 p + t (position p of the wave's 8,
+//   column tile t) sits in read v >> 2, slot v & 3 -- no fourth column tile is stored, DMA'd or read.  A double stage = 24 KB.
+//   Ring: 3 double slots [weights 24 KB | two same-resolution planes | two half-resolution planes] = 38,400 bytes each, the DMA
+//   stream 2 double stages ahead; the stage loops are unrolled once per slot (every LDS address a constant), so the executed
+//   stages of either source are a multiple of 6 quads and wino_first / wino_stride are even (launch_wino checks).
+//   Per wave and double stage: 48 MFMAs, 12 ds_read_b128 of weights in one continuous stream (register k of 6 is read again
+//   right behind the last position that multiplies from it), the patch reads and B^T d B of the next double stage (one quad
+//   under each half), 5 LDS-DMA instructions (3 KB of weights, two patch pieces) behind the first position, one vmcnt wait,
+//   one barrier.
+// Ordering (cdna_hip_programming.md: read a staged buffer one phase AFTER the wait that retires it), stage n in slot n mod 3:
+//   RAW  stage n + 2 is issued during stage n by every wave and is the youngest thing the wave has in flight at the tail of
+//        stage n, where it waits vmcnt(0) in front of the barrier; the first reads of slot (n + 2) mod 3 -- the patch reads
+//        of stage n + 1, and the weight reads behind its second half -- come behind that barrier.
+//   WAR  slot (n + 2) mod 3 = (n - 1) mod 3 was last read for stage n - 1: its planes during stage n - 2, its weights by the
+//        reads issued up to the first half of stage n - 1, all of them consumed -- so returned -- by MFMAs of stage n - 1,
+//        in front of that stage's barrier.  The DMA into it is issued behind that barrier by every wave.
+//   The lgkmcnt immediates are counts of younger reads in the in-order LDS queue (NA = patch reads of a half: 6 or 3):
+//        position 0: 5, 1: 4, 2: 4 + NA, 4: 5 + NA, 5: 4 + NA, 6: 3 (the patch reads are done too); 3 and 7 need no new register.
+namespace tzw {
+static constexpr int NS2 = 3;                                   // double slots of the ring, the stream 2 double stages ahead
+static constexpr int W3BYTES = 12 * 1024;                       // dense weights of a channel quad
+static constexpr int DWBYTES = 2 * W3BYTES;
+static constexpr int DSLOT = DWBYTES + 2 * P1BYTES + 2 * P2BYTES;   // 38,400
+static constexpr int LDS2_BYTES = NS2 * DSLOT + XBYTES;             // 147,968
+static_assert(LDS2_BYTES <= 160 * 1024, "LDS of a CU");
+static_assert(DSLOT + DWBYTES <= 65536, "the 16-bit immediate of ds_read_b128 reaches slot 1's weights from slot 0's base");
+}  // namespace tzw
+
+template <int EPI, bool UPS, bool NOSAME = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_wino2(const ConvArgs a) {
+    constexpr int NT = 3;
+    static_assert(!NOSAME || UPS, "a launch without the same-resolution phase walks the upsampled source");
+    static_assert(EPI == EPI_LSTM3 || EPI == EPI_RAW3 || EPI == EPI_POOL_ERR, "the three-tile forms");
+    static_assert(EPI != EPI_RAW3 || !UPS, "the first half of a split walks the same-resolution source");
+    static_assert(EPI != EPI_POOL_ERR || !UPS, "A convolutions have one source");
+#define TZW_XOFF (NS2 * DSLOT)
+#include "tz_wino_geometry.inc.h"
+    // ---- the DMA stream.  Double stage n (quads 2 n, 2 n + 1 of the walk) goes into ring slot n mod 3.  The dense image is one
+    // stream of 3072 floats a quad: wave wv moves floats [768 wv, 768 wv + 768) of a double stage's 6144 with three
+    // instructions, then its piece of the two quads' patch planes: 5 LDS-DMA instructions per wave and double stage.
+    const float* wp = a.Wwino + ((long long)cb0 * SI + a.wino_first) * 3072 + 768 * wv;   // weights of the next double stage to issue
+    const float* xp0 = a.src[0].p + (long long)n * a.src[0].nstride;                   // ... its first quad of the same-resolution source
+    const float* xp1 = UPS ? a.src[1].p + (long long)n * a.src[1].nstride : nullptr;   // ... of the upsampled one
+    int si = 0;                                                                        // ... its first quad's number
+    const unsigned wvw = (unsigned)wv * 3072, wvp = DWBYTES + (unsigned)wv * (PP * 16), wvu = DWBYTES + 2 * P1BYTES + (unsigned)wv * (UP * 16);
+#define TZW2_ISSUE_TO(KI)                                                                                                   \
+    {                                                                                                                       \
+        const unsigned so = sbase + (unsigned)(KI) * DSLOT;                                                                 \
+        dma_lanes(wp, lane16, so + wvw);                                                                                    \
+        dma_lanes(wp + 256, lane16, so + wvw + 1024);                                                                       \
+        dma_lanes(wp + 512, lane16, so + wvw + 2048);                                                                       \
+        if (!UPS || si < S1) {   /* (S1 is even: both quads of a double stage are of one source) */                         \
+            dma_gather(xp0, poff, pmask, so + wvp);                                                                         \
+            dma_gather(xp0 + 4, poff, pmask, so + wvp + P1BYTES);                                                           \
+            xp0 += 8;                                                                                                       \
+        } else {                                                                                                            \
+            dma_gather(xp1, uoff, umask, so + wvu);                                                                         \
+            dma_gather(xp1 + 4, uoff, umask, so + wvu + P2BYTES);                                                           \
+            xp1 += 8;                                                                                                       \
+        }                                                                                                                   \
+        wp += 2 * 3072;                                                                                                     \
+        si += 2;                                                                                                            \
+        if (si == S) {   /* on to the next item: the next column block's first executed quad, the sources from the start */ \
+            si = 0;                                                                                                         \
+            wp += (SI - S) * 3072;                                                                                          \
+            xp0 -= 4 * S1;                                                                                                  \
+            if (UPS) xp1 -= 4 * (S - S1);                                                                                   \
+        }                                                                                                                   \
+    }
+    // zero the patch areas once: the slots of out-of-image pixels are never written by the DMA
+    const bool interior = ty0 >= 2 && tx0 >= 2 && ty0 + 18 <= a.H && tx0 + 18 <= a.W;
+    if (!interior)
+    for (int i = tid; i < NS2 * ((DSLOT - DWBYTES) / 16); i += 512) {
+        const int sl = i / ((DSLOT - DWBYTES) / 16), o = i - sl * ((DSLOT - DWBYTES) / 16);
+        *(f32x4*)(smem + sl * DSLOT + DWBYTES + o * 16) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    __syncthreads();
+    TZW2_ISSUE_TO(0)   // (S >= 6: at least three double stages)
+    TZW2_ISSUE_TO(1)
+
+    // A address of this lane: tile r = (tyl, txl) of quadrant mt, channel g of the quad, first of the wave's three rows
+    const int tyl = r >> 2, txl = r & 3;
+    const unsigned abase = DWBYTES + (unsigned)(((8 * (mt >> 1) + 2 * tyl + ph) * WPW + 4 * (mt & 1) + txl) * 16 + 4 * g);
+    const unsigned ubase = DWBYTES + 2 * P1BYTES + (unsigned)(((4 * (mt >> 1) + tyl + ph) * WLW + 4 * (mt & 1) + txl) * 16 + 4 * g);
+    // weights: the wave's six reads of a quad sit at ph * 6 KB; slots 0, 1 are read from wbL, slot 2 from wbH
+    const unsigned wbL = sbase + (unsigned)ph * (W3BYTES / 2) + lane16, wbH = wbL + 2 * DSLOT;
+    unsigned adA[NS2][2];   // patch planes per slot and half (ds_read2 immediates are 8 bits)
+#pragma unroll
+    for (int k = 0; k < NS2; ++k) {
+        adA[k][0] = sbase + (unsigned)k * DSLOT + abase;
+        adA[k][1] = adA[k][0] + P1BYTES;
+    }
+#include "tz_wino_transform.inc.h"
+
+    // double stages 0 and 1 landed for everyone (from the second item on the last stage of the item before has seen to that)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll 1
+    for (int it = 0; it < ipw; ++it) {
+    const int cb = cb0 + it;
+    const bool more = it + 1 < ipw;   // (uniform) the DMA stream runs on into another item
+    int per_item = 0;                 // (see k_wino: keeps the pixel offsets of the serial sections out of the stage loops)
+    asm volatile("" : "+s"(per_item));
+    f32x4 D[8][NT];   // (first written by the first quad of the item: mfma_first)
+    // B^T d B of the quads in flight, three sets in rotation: a stage multiplies (first half, second half) = (X, Y), (Z, X), (Y, Z)
+    // and computes the next stage's into the set that is free -- period 3, as the ring
+    float VX[8], VY[8], VZ[8];
+    f32x4 B[6];
+    int s = 0;   // quads done; the ring slot of a double stage is its position in the unrolled loop body
+#define TZW2_WAIT(R, N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(B[R]) : : "memory")
+#define TZW2_MM(F, ACC, P, AV)                                                                                              \
+        _Pragma("unroll") for (int t = 0; t < NT; ++t) F(ACC[t], AV, B[(3 * (P) + t) >> 2][(3 * (P) + t) & 3]);
+#define TZW2_ISSUE_HERE(K) if (s + 4 < S || more) TZW2_ISSUE_TO(((K) + 2) % NS2)
+    // every wave issued the 5 LDS-DMA instructions of the stage two ahead (if there is one) in front of this: they are the
+    // youngest it has in flight, and the next stage reads that slot
+#define TZW2_STAGE_TAIL                                                                                                     \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                    \
+        __builtin_amdgcn_s_barrier();                                                                                       \
+        s += 2;
+    // where slot K's weights are read from: base register and immediate
+#define TZW2_WB(K) (((K) & 2) ? wbH : wbL)
+#define TZW2_WO(K) (((K) & 1) * DSLOT)
+    // one half of a same-resolution double stage: quad VC from the six registers, the next reads of each register from
+    // (WR, WRO), the next stage's patch plane ADN transformed into VN
+#define TZW2_HALF1(F, VC, VN, ADN, WR, WRO, ISSUE)                                                                          \
+    {                                                                                                                       \
+        f32x2 d[3][2];                                                                                                      \
+        TZW2_WAIT(0, 5);  TZW2_MM(F, D[0], 0, VC[0])                                                                        \
+        ISSUE                                                                                                               \
+        TZW2_WAIT(1, 4);  TZW2_MM(F, D[1], 1, VC[1]) B[0] = lds_read16<(WRO)>(WR);                                          \
+        read_d(ADN, d);                                                                                                     \
+        TZW2_WAIT(2, 10); TZW2_MM(F, D[2], 2, VC[2]) B[1] = lds_read16<(WRO) + 1024>(WR);                                   \
+                          TZW2_MM(F, D[3], 3, VC[3]) B[2] = lds_read16<(WRO) + 2048>(WR);                                   \
+        TZW2_WAIT(3, 11); TZW2_MM(F, D[4], 4, VC[4])                                                                        \
+        TZW2_WAIT(4, 10); TZW2_MM(F, D[5], 5, VC[5]) B[3] = lds_read16<(WRO) + 3072>(WR);                                   \
+        TZW2_WAIT(5, 3);  TZW2_MM(F, D[6], 6, VC[6]) B[4] = lds_read16<(WRO) + 4096>(WR);                                   \
+        /* the patch reads have arrived (they are older than the three reads that wait left outstanding); the transform is */ \
+        /* done HERE, not sunk to its first use right in front of an asm MFMA                                              */ \
+        TZW_TIED(d);                                                                                                        \
+        transform(d, VN);                                                                                                   \
+        TZW_TIE8(VN);                                                                                                       \
+                          TZW2_MM(F, D[7], 7, VC[7]) B[5] = lds_read16<(WRO) + 5120>(WR);                                   \
+    }
+#define TZW2_STAGE1(K, VA, VB, VNA, VNB, F)                                                                                 \
+    {                                                                                                                       \
+        constexpr int KN = ((K) + 1) % NS2;                                                                                 \
+        TZW2_HALF1(F, VA, VNA, adA[KN][0], TZW2_WB(K), TZW2_WO(K) + W3BYTES, TZW2_ISSUE_HERE(K))                            \
+        TZW2_HALF1(mfma_acc, VB, VNB, adA[KN][1], TZW2_WB(KN), TZW2_WO(KN), )                                               \
+        TZW2_STAGE_TAIL                                                                                                     \
+    }
+    if (!NOSAME) {
+        {
+            f32x2 d[3][2], e[3][2];
+            read_d(adA[0][0], d);
+            read_d(adA[0][1], e);
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]), "+v"(d[2][0]), "+v"(d[2][1]), "+v"(e[0][0]), "+v"(e[0][1]),
+                           "+v"(e[1][0]), "+v"(e[1][1]), "+v"(e[2][0]), "+v"(e[2][1])
+                         :
+                         : "memory");
+            transform(d, VX);
+            transform(e, VY);
+            TZW_TIE8(VX);
+            TZW_TIE8(VY);
+        }
+        // the weight reads run as one continuous stream across the halves and the stage boundaries
+        B[0] = lds_read16<0>(wbL);
+        B[1] = lds_read16<1024>(wbL);
+        B[2] = lds_read16<2048>(wbL);
+        B[3] = lds_read16<3072>(wbL);
+        B[4] = lds_read16<4096>(wbL);
+        B[5] = lds_read16<5120>(wbL);
+        // the first three double stages of an item: its first quad starts the chains
+        TZW2_STAGE1(0, VX, VY, VZ, VX, mfma_first)
+        TZW2_STAGE1(1, VZ, VX, VY, VZ, mfma_acc)
+        TZW2_STAGE1(2, VY, VZ, VX, VY, mfma_acc)
+#pragma unroll 1
+        while (s < S1) {   // six quads = once round the ring
+            TZW2_STAGE1(0, VX, VY, VZ, VX, mfma_acc)
+            TZW2_STAGE1(1, VZ, VX, VY, VZ, mfma_acc)
+            TZW2_STAGE1(2, VY, VZ, VX, VY, mfma_acc)
+        }
+        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // the last MFMAs have written their accumulators
+    }
+
+#include "tz_wino_output.inc.h"
+
+    // ---- the upsampled source, as in k_wino: a quad = 4 classes x 4 taps of collapsed weights, the wave's 8 sets in consumption
+    // order lp = 2 tap + b, A fragments = the 2 x 3 half-resolution pixels around the tile, three sets in rotation
+    if (UPS) {
+        unsigned udA[NS2][2];
+#pragma unroll
+        for (int k = 0; k < NS2; ++k) {
+            udA[k][0] = sbase + (unsigned)k * DSLOT + ubase;
+            udA[k][1] = udA[k][0] + P2BYTES;
+        }
+        auto read_u = [&](unsigned ad, f32x2 (&u)[3]) {
+            u[0] = lds_read2<0, 4>(ad);             // (row 0, columns 0, 1)
+            u[1] = lds_read2<8, WLW * 4>(ad);        // (row 0, column 2), (row 1, column 0)
+            u[2] = lds_read2<WLW * 4 + 4, WLW * 4 + 8>(ad);   // (row 1, columns 1, 2)
+        };
+        f32x2 AX[3], AY[3], AZ[3];
+        {
+            read_u(udA[0][0], AX);   // (S1 is a multiple of 6: the first double stage of this phase sits in slot 0)
+            read_u(udA[0][1], AY);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(AX[0]), "+v"(AX[1]), "+v"(AX[2]), "+v"(AY[0]), "+v"(AY[1]), "+v"(AY[2]) : : "memory");
+            // (the weight stream was drained by that wait: restart it)
+            B[0] = lds_read16<0>(wbL);
+            B[1] = lds_read16<1024>(wbL);
+            B[2] = lds_read16<2048>(wbL);
+            B[3] = lds_read16<3072>(wbL);
+            B[4] = lds_read16<4096>(wbL);
+            B[5] = lds_read16<5120>(wbL);
+        }
+        // lp = 2 tap + b: tap = (tpy, tpx) -> A[3 tpy + b + tpx]  (A[q] = fragment pair q >> 1, half q & 1)
+#define TZW2_HALF2(AC, AN, ADN, WR, WRO, ISSUE)                                                                             \
+    {                                                                                                                       \
+        TZW2_WAIT(0, 5); TZW2_MM(mfma_acc, Y[0], 0, AC[0][0])                                                               \
+        ISSUE                                                                                                               \
+        TZW2_WAIT(1, 4); TZW2_MM(mfma_acc, Y[1], 1, AC[0][1]) B[0] = lds_read16<(WRO)>(WR);                                 \
+        read_u(ADN, AN);                                                                                                    \
+        TZW2_WAIT(2, 7); TZW2_MM(mfma_acc, Y[0], 2, AC[0][1]) B[1] = lds_read16<(WRO) + 1024>(WR);                          \
+                         TZW2_MM(mfma_acc, Y[1], 3, AC[1][0]) B[2] = lds_read16<(WRO) + 2048>(WR);                          \
+        TZW2_WAIT(3, 8); TZW2_MM(mfma_acc, Y[0], 4, AC[1][1])                                                               \
+        TZW2_WAIT(4, 7); TZW2_MM(mfma_acc, Y[1], 5, AC[2][0]) B[3] = lds_read16<(WRO) + 3072>(WR);                          \
+        TZW2_WAIT(5, 3); TZW2_MM(mfma_acc, Y[0], 6, AC[2][0]) B[4] = lds_read16<(WRO) + 4096>(WR);                          \
+        /* the patch reads have arrived (they are older than the three reads that wait left outstanding) */                 \
+        TZW_TIEU(AN);                                                                                                       \
+                         TZW2_MM(mfma_acc, Y[1], 7, AC[2][1]) B[5] = lds_read16<(WRO) + 5120>(WR);                          \
+    }
+#define TZW2_STAGE2(K, AA, AB, ANA, ANB)                                                                                    \
+    {                                                                                                                       \
+        constexpr int KN = ((K) + 1) % NS2;                                                                                 \
+        TZW2_HALF2(AA, ANA, udA[KN][0], TZW2_WB(K), TZW2_WO(K) + W3BYTES, TZW2_ISSUE_HERE(K))                               \
+        TZW2_HALF2(AB, ANB, udA[KN][1], TZW2_WB(KN), TZW2_WO(KN), )                                                         \
+        TZW2_STAGE_TAIL                                                                                                     \
+    }
+#pragma unroll 1
+        while (s < S) {
+            TZW2_STAGE2(0, AX, AY, AZ, AX)
+            TZW2_STAGE2(1, AZ, AX, AY, AZ)
+            TZW2_STAGE2(2, AY, AZ, AX, AY)
+        }
+        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the reads issued for a stage past the end
+#undef TZW2_STAGE2
+#undef TZW2_HALF2
+#undef TZW2_STAGE1
+#undef TZW2_HALF1
+#undef TZW2_WO
+#undef TZW2_WB
+#undef TZW2_STAGE_TAIL
+#undef TZW2_ISSUE_HERE
+#undef TZW2_MM
+#undef TZW2_WAIT
+#undef TZW2_ISSUE_TO
+#undef TZW_COLT
+
+#include "tz_wino_epilogue.inc.h"
+#undef TZW_XOFF
+    }   // items
+}
+
+// The dense image of k_wino2 from the three-tile image of pack_wino, quad by quad: [set 16][lane][4 column tiles, the fourth
+// zero] -> [ph][read 6][lane][4], fragment v = 3 p + t of set 8 ph + p in read v >> 2, slot v & 3.  A permutation of the values
+// k_wino and k_wino_ref read: a packing error cannot hide between them and k_wino2 (tests/test_gpu_wino2q.py).
+__global__ __launch_bounds__(256) void k_dense_stages(const float* __restrict__ src, float* __restrict__ dst, long long nquads) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nquads * 3072; i += (long long)gridDim.x * blockDim.x) {
+        const long long q = i / 3072;
+        const int rem = (int)(i - q * 3072);
+        const int ph = rem / 1536, rd = (rem % 1536) >> 8, lane = (rem & 255) >> 2, v = 4 * rd + (rem & 3);
+        dst[i] = src[((q * 16 + 8 * ph + v / 3) * 64 + lane) * 4 + v % 3];
+    }
 }
 
 // k_wino_ref: the same TZ-PA2 convolutions (and epilogues) as k_wino, written the plain way -- one thread per (tile, column
