@@ -10,7 +10,9 @@ Streams: work on device buffers is enqueued on the context's stream and is compl
 context on a torch stream (`s = torch.cuda.Stream(); Context(dev, stream=s.cuda_stream)` and run
 the torch side under `torch.cuda.stream(s)`) or synchronise both sides explicitly (bench.py and
 tezip_amd.dist.HipEngine do the latter).  torch's DEFAULT stream has the handle 0, which the C ABI
-reads as "make your own stream": such a context does not share anything with torch."""
+reads as "make your own stream": such a context does not share anything with torch.  A process that hands the library torch's
+streams or tensors imports torch BEFORE the first Context is made (bench.py does): the library then binds to the HIP runtime torch has
+loaded; the other way round the process holds two runtimes, and torch's finds no device."""
 import ctypes as C
 import os
 import threading

@@ -967,6 +967,7 @@ static int run_schedule(tz_ctx* ctx, std::vector<PredItem>& items, const uint8_t
     // chains one group's launch could fill the CUs the other's draining launch leaves idle.  Measured in round 3
     // (bit-identical, all GPU tests green with it on): 62.5 -> 65.4 ms per cfg3 step -- two half-sized launches
     // lose more to their own ramps than the overlap returns -- so it is OFF by default and kept as a switch.
+    // (tests/test_gpu_two_groups.py runs it against the one-group rollout and the C oracle; TEZIP_SPLIT_LOG=1 says that it ran.)
     // Per-launch event timing needs launches that run alone: profiling keeps one stream in any case.
     const bool split = ctx->split_rollout && ctx->stream2 && maxB >= 2 && !ctx->prof_on;
     const int capA = split ? (maxB + 1) / 2 : maxB, capB = maxB - capA;
@@ -1035,6 +1036,8 @@ static int run_schedule(tz_ctx* ctx, std::vector<PredItem>& items, const uint8_t
             all_fed[g].push_back(fed ? 1 : 0);
         }
     }
+    if (split && getenv("TEZIP_SPLIT_LOG"))
+        fprintf(stderr, "[tezip] two-group rollout: caps %d + %d, batches %zu + %zu\n", capA, capB, counts[0].size(), counts[1].size());
     TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_sched, &ctx->cap_sched, table.size() * sizeof(int)));
     TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // an earlier rollout may still read the old table
     TZ_HIP(ctx, hipMemcpy(ctx->d_sched, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice));
