@@ -37,6 +37,13 @@ typedef struct {
     unsigned n_changed;       /* samples with decoded != original */
 } tz_frame_quality;
 
+/* tz_map_check / tz_encode_map_check: one record per frame (16 bytes), definition TZ-BM1 below */
+typedef struct {
+    unsigned long long violations;   /* samples with |decoded - original| > M[pixel] */
+    unsigned max_excess;             /* max over the frame of max(|decoded - original| - M[pixel], 0) */
+    unsigned reserved;               /* 0 */
+} tz_map_record;
+
 /* tz_ssim_frames / tz_encode_ssim: one record per frame (24 bytes), definition TZ-SSIM-1 below */
 typedef struct {
     long long sum_q32;        /* sum of Q over the frame's windows; frame SSIM = sum_q32 / (windows * 2^32) */
@@ -276,6 +283,52 @@ int tz_spatial_undelta_plane(tz_ctx* ctx, const int16_t* in, int nframes, int H,
  * tolerances (one small launch, k_q_frame_bound, fills the per-chain array that rel / absrel jobs fill from the data). */
 int tz_set_frame_bounds(tz_ctx* ctx, const double* bounds, int n);
 int tz_get_frame_bounds(tz_ctx* ctx);
+/* Opt-in: one abs tolerance per PIXEL, definition TZ-BM1 (no reference counterpart: compress.py takes one bound per job;
+ * `tezip.py -c -m abs --bound-map FILE`; DESIGN.md section 9, slow statement in tezip_amd/boundmap.py).
+ * map: H x W host bytes, row-major, of the source frames' own (unpadded) size: map[y * W + x] is the abs tolerance, an integer
+ * 0..255, of all three channels of pixel (y, x) in every frame the encoder quantises.  NULL clears the setting.  H < 1 or W < 1
+ * with a map is TZ_ERR_INVALID.  The map is copied to the device in this call and stays resident: H * W bytes, shared by all
+ * frames and channels -- no per-frame or per-channel copy of it is ever made.  tz_get_bound_map returns 1 and the size, or 0.
+ * With no map set every entry point launches exactly what it launches without these calls.  A change drops a resident payload.
+ *   Greedy quantiser (tz_set_quantiser 0): per quantised frame and channel the chain of H * W deltas in row-major order is
+ *   walked as compress.py:55-67 walks it, with E_i = (double)map[i], Du = d + E_i, Dl = d - E_i: the reference's pwrel walk
+ *   with the tolerance vector replaced by the map (error_bound(map, diff, "pwrel", (1.0,)) is it, bit for bit).
+ *   Lattice quantiser (tz_set_quantiser 1): TZ-QL1 with e = map[p] per sample.
+ * Under both |q - d| <= map[p] at every sample (a run's value lies in [l, u], a subset of every member's [d - E, d + E]; the ends
+ * are integers, so the truncation of (u + l) / 2 stays inside), hence |decoded - original| <= map[p]; a pixel with map 0 is
+ * restored exactly; a map that is k everywhere gives byte for byte the job `abs k`; a map of zeros gives the lossless job.
+ * While a map is set:
+ *  - tz_encode (payload == NULL, the deferred hand-over, the shuffle bit and delta_out included), tz_encode_delta,
+ *    tz_bound_probe and tz_sdelta_probe quantise by TZ-BM1 under the context's quantiser and honour tz_set_payload_channels,
+ *    tz_set_delta_stride and tz_set_delta_plane.  Frame 0, warm-up and key frames are stored exactly, as ever.
+ *  - mode must be TZ_MODE_ABS (b0 and b1 are not read) and the map's size must be the rollout's H, W: else TZ_ERR_INVALID with
+ *    a message that names the rule.
+ *  - tz_set_frame_bounds is TZ_ERR_INVALID and leaves both settings as they were; tz_set_bound_map while frame bounds are set is
+ *    refused the same way.
+ *  - tz_encode_begin, tz_encode_finish and tz_size_probe return TZ_ERR_UNSUPPORTED.
+ *  - a map whose maximum is 0 is the lossless job byte for byte and takes the lossless kernels.
+ *  - the greedy walk is the per-element one in float64 (the Q_TOL_MAP instantiations of k_q_tiles, k_q_bstitch and k_q_serial),
+ *    with the direct-from-predictions front where uniform abs jobs have it; the lattice runs k_lattice_sd / k_lattice with the
+ *    same source.  The decoder never sees a bound: tz_decode, tz_decode_range, tz_encode_quality, tz_encode_ssim and
+ *    tz_encode_digests take the payload as any other, and with the default formats so does the reference's decoder. */
+int tz_set_bound_map(tz_ctx* ctx, const uint8_t* map, int H, int W);
+int tz_get_bound_map(tz_ctx* ctx, int* H, int* W);
+/* The seams of TZ-BM1, independent of the context's settings: the int16 stack diff (nframes x H x W x 3, ANY values; host or
+ * device at any alignment) is quantised in place under `map` (H x W bytes, host or device at any alignment); frames with
+ * skip_mask[f] != 0 (host, may be NULL) stay as they are.  No originals are needed.  tz_error_bound_map: the greedy walk;
+ * tz_lattice_bound_map: TZ-QL1 (diff 2-byte aligned). */
+int tz_error_bound_map(tz_ctx* ctx, int16_t* diff, const uint8_t* skip_mask, int nframes, int H, int W, const uint8_t* map);
+int tz_lattice_bound_map(tz_ctx* ctx, int16_t* diff, const uint8_t* skip_mask, int nframes, int H, int W, const uint8_t* map);
+/* tz_map_check: the check kernel of TZ-BM1 over any two unpadded uint8 stacks of nframes x H x W x 3 (host or device) and a map
+ * of H x W bytes (host or device): out[f] (host or device, complete on return) = the number of samples of frame f with
+ * |decoded - orig| > map[pixel] and the largest excess.  Exact integers.  nframes <= 0 does nothing.
+ * tz_encode_map_check: the front of tz_encode_quality (the decoder's tail over the stored payload with the encoder's own
+ * predictions; its arguments, state rules and errors), then that kernel against the originals under the context's map
+ * (TZ_ERR_STATE when none is set).  Nothing of the context changes. */
+int tz_map_check(tz_ctx* ctx, const uint8_t* orig, const uint8_t* decoded, const uint8_t* map, int nframes, int H, int W,
+                 tz_map_record* out);
+int tz_encode_map_check(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len, int shuffled,
+                        tz_map_record* out);
 /* Opt-in: the quantiser of a lossy job (no reference counterpart: compress.py:23-70 is the only one the reference has, a greedy
  * walk that merges runs of neighbouring deltas which fit into one 2E window; `tezip.py -c --quant lattice`, DESIGN.md section 9,
  * slow statement in tezip_amd/lattice.py).  q: 0 (the default: every entry point launches exactly what it launches without this

@@ -88,6 +88,12 @@ _SIGS = {
     "tz_set_frame_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "tz_get_frame_bounds": (C.c_int, [C.c_void_p]),
     "tz_error_bound_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_set_bound_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "tz_get_bound_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tz_error_bound_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_lattice_bound_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_map_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_encode_map_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tz_set_quantiser": (C.c_int, [C.c_void_p, C.c_int]),
     "tz_get_quantiser": (C.c_int, [C.c_void_p]),
     "tz_lattice_bound": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -199,6 +205,8 @@ class FrameQuality(C.Structure):
 
 
 QUALITY_DTYPE = np.dtype([("sse", "<u8"), ("max_abs", "<u4"), ("n_changed", "<u4")])   # the same layout as a numpy record
+# tz_map_record (16 bytes): one frame of tz_map_check / tz_encode_map_check
+MAP_DTYPE = np.dtype([("violations", "<u8"), ("max_excess", "<u4"), ("reserved", "<u4")])
 # tz_size_record (64 bytes): one candidate of tz_size_probe
 SIZE_DTYPE = np.dtype([("n", "<u8"), ("stream_words", "<u8"), ("bytes", "<u8"), ("cost_bits", "<u8", (3,)), ("A", "<i4"), ("base", "<i4"),
                        ("dist", "<i4"), ("table_len", "<i4")])
@@ -669,6 +677,50 @@ class Context:
 
     def get_frame_bounds(self):
         return int(self.lib.tz_get_frame_bounds(self.h))
+
+    def set_bound_map(self, bmap):
+        """tz_set_bound_map: an H x W uint8 map of abs tolerances, one per pixel, for every frame the encoder quantises
+        (TZ-BM1, tezip_amd/boundmap.py; None: clear).  While set, encode / encode_delta / bound_probe / sdelta_probe take mode
+        "abs", ignore its bound and hold every sample to its pixel's entry; frame bounds, the sharded entry points and
+        size_probe refuse."""
+        if bmap is None:
+            self._ck(self.lib.tz_set_bound_map(self.h, None, 0, 0))
+            return
+        m = np.ascontiguousarray(bmap)
+        if m.dtype != np.uint8 or m.ndim != 2:
+            raise ValueError("a bound map is a 2-D uint8 array, not %s%s" % (m.dtype, m.shape))
+        self._ck(self.lib.tz_set_bound_map(self.h, m.ctypes.data, int(m.shape[0]), int(m.shape[1])))
+
+    def get_bound_map(self):
+        """tz_get_bound_map: (H, W) of the map in force, or None."""
+        h, w = C.c_int(0), C.c_int(0)
+        return (h.value, w.value) if self.lib.tz_get_bound_map(self.h, C.byref(h), C.byref(w)) == 1 else None
+
+    def encode_map_check(self, payload="resident", table=None, shuffle=False):
+        """tz_encode_map_check after set_bound_map + rollout + encode, arguments as encode_quality's: per frame (violations,
+        max_excess) of what the payload decodes to against the originals under the map, as MAP_DTYPE[nt]."""
+        nt, h, w = self._shape
+        n = nt * h * w * self.channels
+        resident = isinstance(payload, str) and payload == "resident"
+        if not resident and _numel(payload) != n:
+            raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
+        out = np.zeros(nt, MAP_DTYPE)
+        tl = -1 if table is None else len(table)
+        tb = None if table is None else np.ascontiguousarray(table, np.int16)
+        self._ck(self.lib.tz_encode_map_check(self.h, None if resident else _ptr(payload), n, _ptr(tb), tl, int(bool(shuffle)),
+                                              out.ctypes.data))
+        return out
+
+    def map_check(self, orig, decoded, bmap, shape):
+        """tz_map_check: k_map_check over two uint8 stacks of shape = (nframes, H, W) x 3 and an H x W map (host arrays or
+        device tensors): MAP_DTYPE[nframes] (boundmap.check)."""
+        n, h, w = (int(v) for v in shape)
+        if not (_numel(orig) == _numel(decoded) == n * h * w * 3) or _numel(bmap) != h * w:
+            raise ValueError("stacks of %d and %d elements and a map of %d, %d x %d x %d x 3 and %d x %d wanted"
+                             % (_numel(orig), _numel(decoded), _numel(bmap), n, h, w, h, w))
+        out = np.zeros(max(n, 0), MAP_DTYPE)
+        self._ck(self.lib.tz_map_check(self.h, _ptr(orig), _ptr(decoded), _ptr(bmap), n, h, w, out.ctypes.data))
+        return out
 
     def set_quantiser(self, quant):
         """tz_set_quantiser: "greedy" / 0 (the default) = the reference's quantiser, "lattice" / 1 = the lattice quantiser
@@ -1234,6 +1286,25 @@ class Context:
             raise ValueError("%d bounds for %d frames" % (b.size, n))
         sk = None if skip_mask is None else np.ascontiguousarray(skip_mask, np.uint8)
         self._ck(self.lib.tz_lattice_bound_frames(self.h, _ptr(orig), _ptr(diff), _ptr(sk), n, h, w, b.ctypes.data))
+        return diff
+
+    def error_bound_map(self, diff, bmap, shape, skip_mask=None):
+        """tz_error_bound_map: the greedy walk under the H x W uint8 map bmap (TZ-BM1), in place on the int16 stack diff of
+        shape = (nframes, H, W) x 3; no originals.  Host arrays or device tensors at any alignment."""
+        n, h, w = (int(v) for v in shape)
+        if _numel(diff) != n * h * w * 3 or _numel(bmap) != h * w:
+            raise ValueError("diff holds %d elements and the map %d, %d x %d x %d x 3 and %d x %d wanted" % (_numel(diff), _numel(bmap), n, h, w, h, w))
+        sk = None if skip_mask is None else np.ascontiguousarray(skip_mask, np.uint8)
+        self._ck(self.lib.tz_error_bound_map(self.h, _ptr(diff), _ptr(sk), n, h, w, _ptr(bmap)))
+        return diff
+
+    def lattice_bound_map(self, diff, bmap, shape, skip_mask=None):
+        """tz_lattice_bound_map: TZ-QL1 with e = bmap[pixel], arguments as error_bound_map's."""
+        n, h, w = (int(v) for v in shape)
+        if _numel(diff) != n * h * w * 3 or _numel(bmap) != h * w:
+            raise ValueError("diff holds %d elements and the map %d, %d x %d x %d x 3 and %d x %d wanted" % (_numel(diff), _numel(bmap), n, h, w, h, w))
+        sk = None if skip_mask is None else np.ascontiguousarray(skip_mask, np.uint8)
+        self._ck(self.lib.tz_lattice_bound_map(self.h, _ptr(diff), _ptr(sk), n, h, w, _ptr(bmap)))
         return diff
 
     def spatial_delta(self, x, offset, carry=None, hist=None, out=None):

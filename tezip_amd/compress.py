@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
+from . import _lib, boundmap, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -562,7 +562,7 @@ def check_ratio(ratio, mode, bound, target_psnr, coder, shuffle, sharded):
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
-        SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None, QUANT="greedy"):
+        SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None, QUANT="greedy", BOUND_MAP=None):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -629,6 +629,15 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     record.  Smaller than greedy on data that is not smooth, LARGER on sparse frames at loose bounds (README).  The probes of
     TARGET_PSNR, PER_FRAME and TARGET_RATIO quantise the same way.  Works with every flag above.  Single-GPU jobs only.
 
+    BOUND_MAP (--bound-map; NOT in the reference; MODE "abs", an empty BOUND_VALUE, no target, no FRAME_BOUNDS): the path of a map
+    of the images' own size (a .npy with a 2-D uint8 array, or an image with one channel or three equal ones) or such an array:
+    one abs bound per pixel, for all three channels in every frame the encoder quantises (definition TZ-BM1:
+    tezip_amd/boundmap.py).  The job runs under tz_set_bound_map.  The files are ordinary ones (the decoder never sees a bound);
+    one line describes the map, tezip_amd.json records its maximum and its exact pixels (`-u` does not read them), and with
+    REPORT quality.json carries the violations per frame (0, or a bug) from tz_encode_map_check on the resident payload: any
+    violation is one ERROR line per frame and exit status 3.  Works with every QUANT, CODER, KEY_CODER, SHUFFLE, GRAY, SDELTA,
+    REPORT, SSIM and DIGESTS.  Single-GPU jobs only.
+
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
     does not grow with the number of frames.  Under torch.distributed.run the windows are sharded
@@ -678,6 +687,20 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
         if problem:
             print("ERROR:", problem)
             sys.exit(2)
+    bound_map = None
+    if BOUND_MAP is not None:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
+        problem = boundmap.check_flags(BOUND_MAP, MODE, BOUND_VALUE, TARGET_PSNR, TARGET_RATIO, PER_FRAME, FRAME_BOUNDS,
+                                       tzdist.active() is not None)
+        if not problem:
+            try:
+                bound_map = boundmap.load(BOUND_MAP) if isinstance(BOUND_MAP, (str, os.PathLike)) else np.ascontiguousarray(BOUND_MAP)
+                if bound_map.dtype != np.uint8 or bound_map.ndim != 2:
+                    raise ValueError("bound map BOUND_MAP is a %s array of shape %s: a map is a 2-D uint8 array" % (bound_map.dtype, bound_map.shape))
+            except ValueError as e:
+                problem = str(e)
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     if tzdist.active() is not None:
         if REPORT:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
             print("ERROR: --report is not available for a sharded job (WORLD_SIZE > 1): run it on one GPU")
@@ -692,6 +715,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     nt, H, W = src.nt, src.H, src.W
     if frame_bounds is not None:   # known once the directory is listed: before the model, the context and the rollout
         problem = frametarget.check_length(frame_bounds, nt, FRAME_BOUNDS)
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
+    if bound_map is not None:   # likewise
+        problem = boundmap.check_size(bound_map, H, W, BOUND_MAP if isinstance(BOUND_MAP, (str, os.PathLike)) else "BOUND_MAP")
         if problem:
             print("ERROR:", problem)
             sys.exit(2)
@@ -750,6 +778,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             elif frame_bounds is not None:
                 frame_bounds = [0.0 if fx else b for fx, b in zip(frametarget.fixed_frames(key, PREPROCESS), frame_bounds)]
                 print(frametarget.explicit_line(frame_bounds))
+            if bound_map is not None:   # the job: abs, pixel p under bound_map[p] in every frame (BOUND_VALUE is not read)
+                ctx.set_bound_map(bound_map)
+                print(boundmap.stdout_line(bound_map))
+                BOUND_VALUE = [0.0]
             if frame_bounds is not None:   # the job: abs, frame f under frame_bounds[f]
                 ctx.set_frame_bounds(frame_bounds)
             elif TARGET_PSNR is not None:   # one rollout serves every candidate: the predictions do not depend on the bound
@@ -790,6 +822,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 if VERBOSE:
                     print("quality:{0}".format(time.time() - t0) + "[sec]")
                 stages.mark("quality report (device)")
+                if bound_map is not None:   # likewise: the decoded stack against the originals under the map
+                    map_rec = ctx.encode_map_check("resident", table if ENTROPY_RUN else None, shuffle=SHUFFLE)
+                    stages.mark("bound map check (device)")
                 if SSIM:   # likewise, on the same resident payload
                     t0 = time.time()
                     ssim_rec = ctx.encode_ssim("resident", table if ENTROPY_RUN else None, shuffle=SHUFFLE)
@@ -817,7 +852,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             else:
                 _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
                                 coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided, plane=plane)
-            if QUANT == "lattice":
+            if bound_map is not None:
+                doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
+                                    payload_channels=channels, sdelta=sd_mode, quant=QUANT, bound_map=boundmap.stats(bound_map))
+            elif QUANT == "lattice":
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
                                     payload_channels=channels, sdelta=sd_mode, quant="lattice")
             else:
@@ -827,14 +865,27 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 print("arithmetic contract:", doc["arithmetic_contract"])
             stages.mark("key_frame.dat + entropy.dat")
             if REPORT:   # the three files exist: the ratio is known
-                report = quality.summarize(stats, src.files, H, W, MODE, BOUND_VALUE, quality.file_sizes(OUTPUT_DIR),
+                report = quality.summarize(stats, src.files, H, W, MODE, [] if bound_map is not None else BOUND_VALUE, quality.file_sizes(OUTPUT_DIR),
                                            window=WINDOW_SIZE, threshold=THRESHOLD, warm_up=PREPROCESS,
                                            **({"ssim": ssim_rec} if SSIM else {}))
                 if frame_bounds is not None:
                     report["frame_bounds"] = [float(b) for b in frame_bounds]
+                if bound_map is not None:
+                    report["bound_map"] = {"file": os.fspath(BOUND_MAP) if isinstance(BOUND_MAP, (str, os.PathLike)) else None,
+                                           "max": int(bound_map.max()), "violations": int(map_rec["violations"].sum()),
+                                           "max_excess": int(map_rec["max_excess"].max()) if nt else 0}
+                    for entry, r in zip(report["per_frame"], map_rec):
+                        entry["violations"] = int(r["violations"])
                 quality.write(OUTPUT_DIR, report)
                 for line in quality.stdout_lines(report):
                     print(line)
+                if bound_map is not None:
+                    broken = [i for i in range(nt) if map_rec["violations"][i]]
+                    for i in broken:   # a bug, not a property of the data
+                        print(boundmap.broken_line(i, src.files[i], int(map_rec["violations"][i])))
+                    if broken:
+                        sys.exit(boundmap.EXIT_BROKEN)
+                    print(boundmap.HELD_LINE)
             if QUANT == "lattice" and (TARGET_PSNR is not None or TARGET_RATIO is not None):
                 search_doc["quant"] = "lattice"
             if PER_FRAME:

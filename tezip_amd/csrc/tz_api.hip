@@ -219,6 +219,7 @@ extern "C" int tz_ctx_destroy(tz_ctx* ctx) {
     if (ctx->d_pred) (void)hipFree(ctx->d_pred);
     if (ctx->d_sched) (void)hipFree(ctx->d_sched);
     if (ctx->d_payload) (void)hipFree(ctx->d_payload);
+    if (ctx->d_bound_map) (void)hipFree(ctx->d_bound_map);
     if (ctx->d_payload_stage) (void)hipFree(ctx->d_payload_stage);
     if (ctx->ev_payload) (void)hipEventDestroy(ctx->ev_payload);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
@@ -1529,6 +1530,13 @@ static int encode_check(tz_ctx* ctx, const char* who, int mode) {
             return tz_fail(ctx, TZ_ERR_INVALID, "%s: frame bounds are set for %d frames (tz_set_frame_bounds), the rollout has %d", who,
                            (int)ctx->frame_bounds.size(), ctx->nt);
     }
+    if (ctx->map_h) {   // tz_set_bound_map: b0 and b1 are not read
+        if (mode != TZ_MODE_ABS)
+            return tz_fail(ctx, TZ_ERR_INVALID, "%s: a bound map is set (tz_set_bound_map), the mode must be abs, not %d", who, mode);
+        if (ctx->map_h != ctx->H || ctx->map_w != ctx->W)
+            return tz_fail(ctx, TZ_ERR_INVALID, "%s: the bound map is %d x %d (tz_set_bound_map), the rollout's frames are %d x %d: a map has the frames' own size",
+                           who, ctx->map_h, ctx->map_w, ctx->H, ctx->W);
+    }
     return TZ_OK;
 }
 
@@ -1536,6 +1544,8 @@ static int encode_check(tz_ctx* ctx, const char* who, int mode) {
 extern "C" int tz_set_frame_bounds(tz_ctx* ctx, const double* bounds, int n) {
     if (!ctx) return TZ_ERR_INVALID;
     if (n < 0) return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_frame_bounds: %d bounds", n);
+    if (ctx->map_h && bounds && n > 0)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_frame_bounds while a bound map is set (tz_set_bound_map): a job takes one of the two");
     if (!bounds || n == 0) {
         ctx->frame_bounds.clear();
         return TZ_OK;
@@ -1548,6 +1558,53 @@ extern "C" int tz_set_frame_bounds(tz_ctx* ctx, const double* bounds, int n) {
 }
 
 extern "C" int tz_get_frame_bounds(tz_ctx* ctx) { return ctx ? (int)ctx->frame_bounds.size() : TZ_ERR_INVALID; }
+
+// ---- one abs bound per pixel, TZ-BM1 (include/tezip_hip.h: tz_set_bound_map)
+extern "C" int tz_set_bound_map(tz_ctx* ctx, const uint8_t* map, int H, int W) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (!map) {
+        if (ctx->map_h) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under the map
+        ctx->map_h = ctx->map_w = ctx->map_max = 0;
+        return TZ_OK;
+    }
+    if (H < 1 || W < 1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_bound_map: a map of %d x %d", H, W);
+    if (!ctx->frame_bounds.empty())
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_bound_map while frame bounds are set (tz_set_frame_bounds): a job takes one of the two");
+    const size_t n = (size_t)H * W;
+    if (!ctx->d_bound_map || (size_t)ctx->map_h * ctx->map_w < n) {   // the one copy: H * W bytes for every frame and channel
+        uint8_t* d = nullptr;
+        TZ_HIP(ctx, hipMalloc((void**)&d, n));
+        if (ctx->d_bound_map) {
+            TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (a launch may still read the old map)
+            (void)hipFree(ctx->d_bound_map);
+        }
+        ctx->d_bound_map = d;
+        ctx->map_h = ctx->map_w = ctx->map_max = 0;
+    }
+    TZ_TRY(tz_h2d(ctx, ctx->d_bound_map, map, n, ctx->stream));
+    TZ_TRY(tz_stream_sync(ctx));   // (the caller's buffer is free on return)
+    int mx = 0;
+    for (size_t i = 0; i < n; ++i) mx = std::max(mx, (int)map[i]);
+    ctx->map_h = H;
+    ctx->map_w = W;
+    ctx->map_max = mx;
+    ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under another tolerance
+    return TZ_OK;
+}
+
+extern "C" int tz_get_bound_map(tz_ctx* ctx, int* H, int* W) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (H) *H = ctx->map_h;
+    if (W) *W = ctx->map_w;
+    return ctx->map_h ? 1 : 0;
+}
+
+// The sharded entry points and the size probe take one bound per job.
+static int no_bound_map(tz_ctx* ctx, const char* who) {
+    if (ctx->map_h)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "%s does not serve a bound map (tz_set_bound_map): sharded jobs and the size probe take one bound", who);
+    return TZ_OK;
+}
 
 // The sharded entry points quantise one shard's frames under one bound.
 static int no_frame_bounds(tz_ctx* ctx, const char* who) {
@@ -1585,6 +1642,12 @@ static int greedy_only(tz_ctx* ctx, const char* who) {
 // passed)
 static int quantise_rollout(tz_ctx* ctx, int16_t* d_q, int mode, double b0, double b1) {
     const int nt = ctx->nt, H = ctx->H, W = ctx->W;
+    if (ctx->map_h) {   // TZ-BM1 (tz_set_bound_map): a map of zeros leaves every delta as it is
+        if (ctx->map_max == 0) return TZ_OK;
+        if (ctx->quantiser == 1)
+            return tzk_lattice(ctx, ctx->d_frames, d_q, ctx->quant_skip.data(), nt, H, W, TZ_MODE_ABS, 0.0, 0.0, nullptr, ctx->d_bound_map);
+        return tzk_quant_map(ctx, ctx->d_frames, d_q, nullptr, ctx->quant_skip.data(), nt, H, W, ctx->d_bound_map, nullptr);
+    }
     if (ctx->quantiser == 1)   // TZ-QL1 (tz_set_quantiser): one pass over the stack in place
         return tzk_lattice(ctx, ctx->d_frames, d_q, ctx->quant_skip.data(), nt, H, W, mode, b0, b1,
                            ctx->frame_bounds.empty() ? nullptr : ctx->frame_bounds.data());
@@ -1611,13 +1674,14 @@ static int encode_front(tz_ctx* ctx, tz_layout layout, int mode, double b0, doub
         // TZ-QL1 (tz_set_quantiser): a job whose worst-case tolerance is below 1 is the lossless job and takes its kernels (the
         // flat one-pass front below, or the unfused chain, whose quantiser step then launches nothing); every other job has
         // one fused pass in EVERY layout -- the quantised value is a function of one delta and one tolerance.
-        const bool per_frame = !ctx->frame_bounds.empty();
-        const bool lossless = per_frame ? frame_bounds_identity(ctx) : tz_lattice_is_identity(mode, b0, b1);
+        // Under a bound map (tz_set_bound_map) the same pass takes e from the map; a map of zeros is the lossless job.
+        const bool per_frame = !ctx->frame_bounds.empty(), mapped = ctx->map_h != 0;
+        const bool lossless = mapped ? ctx->map_max == 0 : (per_frame ? frame_bounds_identity(ctx) : tz_lattice_is_identity(mode, b0, b1));
         bool fused = false;
         if (!lossless)
             TZ_TRY(tzk_lattice_sd_fused(ctx, layout, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, ctx->quant_skip.data(), nt, H, W,
                                         ctx->Hp, ctx->Wp, mode, b0, b1, per_frame ? ctx->frame_bounds.data() : nullptr, entropy ? 1 : 0,
-                                        d_sym, entropy ? d_hist : nullptr, d_edge, &fused));
+                                        d_sym, entropy ? d_hist : nullptr, d_edge, &fused, mapped ? ctx->d_bound_map : nullptr));
         else if (flat)
             TZ_TRY(tzk_delta_sd_fused(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp,
                                       entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge, &fused));
@@ -1629,14 +1693,20 @@ static int encode_front(tz_ctx* ctx, tz_layout layout, int mode, double b0, doub
         // the two).  The gray layout and the channel stride have no fused pass.
         // Frame bounds (tz_set_frame_bounds): the lossless job when every frame's bound is such a one, else the same lossy
         // front with the per-frame tolerances.
-        const bool per_frame = !ctx->frame_bounds.empty();
-        const bool lossless = per_frame ? frame_bounds_identity(ctx)
-                                        : b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0) || tz_quant_is_identity(mode, b0, b1);
+        // A bound map (tz_set_bound_map): the lossless job when the map is zero everywhere, else the same lossy front with the
+        // map as the walks' tolerance source.
+        const bool per_frame = !ctx->frame_bounds.empty(), mapped = ctx->map_h != 0;
+        const bool lossless = mapped      ? ctx->map_max == 0
+                              : per_frame ? frame_bounds_identity(ctx)
+                                          : b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0) || tz_quant_is_identity(mode, b0, b1);
         bool fused = false;
         if (lossless)   // delta and spatial delta in one pass (compress.py:292-355)
             TZ_TRY(tzk_delta_sd_fused(ctx, ctx->d_pred, ctx->d_frames, (const uint8_t*)d_mask, nt, H, W, ctx->Hp, ctx->Wp,
                                       entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge, &fused));
-        else if (per_frame) {
+        else if (mapped) {
+            const tz_quant_fused fu{ctx->d_pred, (const uint8_t*)d_mask, ctx->Hp, ctx->Wp, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge};
+            TZ_TRY(tzk_quant_map(ctx, ctx->d_frames, nullptr, &fu, ctx->quant_skip.data(), nt, H, W, ctx->d_bound_map, &fused));
+        } else if (per_frame) {
             const tz_quant_fused fu{ctx->d_pred, (const uint8_t*)d_mask, ctx->Hp, ctx->Wp, entropy ? 1 : 0, d_sym, entropy ? d_hist : nullptr, d_edge};
             TZ_TRY(tzk_quant_frames(ctx, ctx->d_frames, nullptr, &fu, ctx->quant_skip.data(), nt, H, W, ctx->frame_bounds.data(), &fused));
         } else          // quantiser on pred / orig, fill fused with the spatial delta
@@ -1855,6 +1925,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
     if (!ctx || !edge || (entropy && !hist)) return TZ_ERR_INVALID;
     TZ_TRY(flat_only(ctx, "tz_encode_begin"));
     TZ_TRY(no_frame_bounds(ctx, "tz_encode_begin"));
+    TZ_TRY(no_bound_map(ctx, "tz_encode_begin"));
     TZ_TRY(greedy_only(ctx, "tz_encode_begin"));
     TZ_TRY(encode_check(ctx, "tz_encode_begin", mode));
     ctx->enc_kind = tz_ctx::ENC_NONE;   // d_payload now receives a shard's symbols
@@ -1884,6 +1955,7 @@ extern "C" int tz_encode_finish(tz_ctx* ctx, int has_carry, int16_t carry, const
     if (!ctx) return TZ_ERR_INVALID;
     TZ_TRY(flat_only(ctx, "tz_encode_finish"));
     TZ_TRY(no_frame_bounds(ctx, "tz_encode_finish"));
+    TZ_TRY(no_bound_map(ctx, "tz_encode_finish"));
     TZ_TRY(greedy_only(ctx, "tz_encode_finish"));
     if (ctx->enc_kind != tz_ctx::ENC_SYMBOLS) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_finish needs a tz_encode_begin first");
     if (ctx->enc_entropy != (table_len >= 0) || (table_len > 0 && !table) || table_len > TZ_MAX_TABLE)
@@ -2127,6 +2199,46 @@ extern "C" int tz_encode_quality(tz_ctx* ctx, const int16_t* payload, size_t pay
     TZ_TRY(tzk_quality(ctx, ctx->d_frames, d_dec, ctx->nt, (size_t)ctx->H * ctx->W * 3, d_out));
     TZ_TRY(call.finish());
     return tz_stream_sync(ctx);   // (device records too: complete on return)
+}
+
+// The bound-map line of `-c --bound-map --report`: k_map_check of the decoded stack against the originals under the context's map.
+extern "C" int tz_encode_map_check(tz_ctx* ctx, const int16_t* payload, size_t payload_len, const int16_t* table, int table_len,
+                                   int shuffled, tz_map_record* out) {
+    tz_roctx_range roctx_("tz_encode_map_check");
+    if (!ctx || !out) return TZ_ERR_INVALID;
+    if (!ctx->map_h) return tz_fail(ctx, TZ_ERR_STATE, "tz_encode_map_check needs a bound map (tz_set_bound_map)");
+    if (ctx->map_h != ctx->H || ctx->map_w != ctx->W)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode_map_check: the bound map is %d x %d, the rollout's frames are %d x %d: a map has the frames' own size",
+                       ctx->map_h, ctx->map_w, ctx->H, ctx->W);
+    tz_call call(ctx);
+    const uint8_t* d_dec;
+    tz_map_record* d_out;
+    TZ_TRY(encode_decoded(call, "tz_encode_map_check", payload, payload_len, table, table_len, shuffled, &d_dec));
+    TZ_TRY(call.out(out, sizeof(tz_map_record) * ctx->nt, &d_out));
+    TZ_TRY(tzk_map_check(ctx, ctx->d_frames, d_dec, ctx->d_bound_map, ctx->nt, ctx->H, ctx->W, d_out));
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);   // (device records too: complete on return)
+}
+
+// k_map_check alone, on any two stacks and any map (tests against tezip_amd/boundmap.py check).
+extern "C" int tz_map_check(tz_ctx* ctx, const uint8_t* orig, const uint8_t* decoded, const uint8_t* map, int nframes, int H, int W,
+                            tz_map_record* out) {
+    tz_roctx_range roctx_("tz_map_check");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (nframes <= 0) return TZ_OK;
+    if (!orig || !decoded || !map || !out) return TZ_ERR_INVALID;
+    if (H < 1 || W < 1) return tz_fail(ctx, TZ_ERR_INVALID, "frames of %d x %d", H, W);
+    const size_t n = (size_t)nframes * H * W * 3;
+    tz_call call(ctx);
+    const uint8_t *d_o, *d_d, *d_m;
+    tz_map_record* d_out;
+    TZ_TRY(call.in(orig, n, &d_o));
+    TZ_TRY(call.in(decoded, n, &d_d));
+    TZ_TRY(call.in(map, (size_t)H * W, &d_m));
+    TZ_TRY(call.out(out, sizeof(tz_map_record) * nframes, &d_out));
+    TZ_TRY(tzk_map_check(ctx, d_o, d_d, d_m, nframes, H, W, d_out));
+    TZ_TRY(call.finish());
+    return tz_stream_sync(ctx);
 }
 
 // One candidate bound of `-c --target-psnr` (TZ-TPSNR-1): the records tz_encode(mode, b0, b1) + tz_encode_quality would give,
@@ -2373,6 +2485,36 @@ extern "C" int tz_lattice_bound_frames(tz_ctx* ctx, const uint8_t* orig, int16_t
         if (!std::isfinite(bounds[f]) || bounds[f] < 0.0)
             return tz_fail(ctx, TZ_ERR_INVALID, "tz_lattice_bound_frames: bound %g of frame %d is not a finite number >= 0", bounds[f], f);
     return lattice_seam(ctx, orig, diff, skip_mask, nframes, H, W, TZ_MODE_ABS, 0.0, 0.0, bounds);
+}
+
+// The seams of TZ-BM1 (tz_set_bound_map): any int16 stack in place under any H x W map, by the greedy walk (lattice == false) or
+// TZ-QL1.  No originals.  Independent of the context's settings.
+static int bound_map_seam(tz_ctx* ctx, bool lattice, int16_t* diff, const uint8_t* skip_mask, int nframes, int H, int W, const uint8_t* map) {
+    if (!ctx || !diff || !map || nframes < 0 || H < 1 || W < 1) return TZ_ERR_INVALID;
+    if (nframes == 0) return TZ_OK;
+    size_t N = (size_t)nframes * H * W * 3;
+    std::vector<uint8_t> sk(nframes, 0);
+    if (skip_mask) memcpy(sk.data(), skip_mask, nframes);
+    tz_call call(ctx);
+    const uint8_t* dmap;
+    int16_t* ddiff;
+    TZ_TRY(call.in(map, (size_t)H * W, &dmap));
+    TZ_TRY(call.out(diff, N * 2, &ddiff));
+    if (call.outs.back().host) {
+        hipError_t e = hipMemcpyAsync(ddiff, diff, N * 2, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return tz_fail(ctx, TZ_ERR_HIP, "diff upload: %s", hipGetErrorString(e));
+    }
+    if (lattice) TZ_TRY(tzk_lattice(ctx, nullptr, ddiff, sk.data(), nframes, H, W, TZ_MODE_ABS, 0.0, 0.0, nullptr, dmap));
+    else TZ_TRY(tzk_quant_map(ctx, nullptr, ddiff, nullptr, sk.data(), nframes, H, W, dmap, nullptr));
+    return call.finish();
+}
+
+extern "C" int tz_error_bound_map(tz_ctx* ctx, int16_t* diff, const uint8_t* skip_mask, int nframes, int H, int W, const uint8_t* map) {
+    return bound_map_seam(ctx, false, diff, skip_mask, nframes, H, W, map);
+}
+
+extern "C" int tz_lattice_bound_map(tz_ctx* ctx, int16_t* diff, const uint8_t* skip_mask, int nframes, int H, int W, const uint8_t* map) {
+    return bound_map_seam(ctx, true, diff, skip_mask, nframes, H, W, map);
 }
 
 // The seams.  Each operation has one body, which takes the layout (tz_internal.h); the exported names of the gray payload
@@ -3182,6 +3324,7 @@ extern "C" int tz_size_probe(tz_ctx* ctx, int mode, double b0, double b1, int en
     if (coder < 0 || coder > 2) return tz_fail(ctx, TZ_ERR_INVALID, "tz_size_probe: coder %d, 0 (huff), 1 (huffr) or 2 (huffd) wanted", coder);
     if (entropy & ~1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_size_probe: byte planes are not Huffman-coded");
     TZ_TRY(no_plane(ctx, "tz_size_probe"));
+    TZ_TRY(no_bound_map(ctx, "tz_size_probe"));
     TZ_TRY(encode_check(ctx, "tz_size_probe", mode));
     const tz_layout layout = layout_of(ctx);
     if (layout.channels == 1) {

@@ -375,10 +375,21 @@ __device__ __forceinline__ int q_pack(int mn, int mx) { return (mn & 0xFFFF) | (
 __device__ __forceinline__ int q_lo(int p) { return (int)(short)(p & 0xFFFF); }
 __device__ __forceinline__ int q_hi(int p) { return p >> 16; }
 
+// Where a walk takes its tolerance from (the PW template value of q_chunk and k_q_tiles, of lat_apply and its kernels):
+//   Q_TOL_CHAIN  one E per chain (abs, rel, absrel, frame bounds): the integer walk
+//   Q_TOL_ORIG   E = orig * b0 per element (pwrel): the double walk
+//   Q_TOL_MAP    E = M[pixel] per element, M an H x W uint8 map shared by every frame and channel (TZ-BM1, tz_set_bound_map):
+//                the double walk; the map itself is the only tolerance storage, `orig` is read for the deltas alone (FP)
+// The kernels' argument lists are what they were without the map (one argument more moves the hidden ones, and with them an
+// offset in every existing instantiation's instruction stream): under Q_TOL_MAP the map travels in the slot of an argument that
+// source never reads -- `Echain` in the walks (q_tol_map), `orig` in k_lattice, the eight bytes of `b0` in k_lattice_sd (lat_tol_map).
+static constexpr int Q_TOL_CHAIN = 0, Q_TOL_ORIG = 1, Q_TOL_MAP = 2;
+__device__ __forceinline__ const uint8_t* q_tol_map(const double* Echain) { return (const uint8_t*)Echain; }
+
 // fe0 = element index of the frame's first sample in the whole stack (f * HW * 3)
-template <bool PW, bool FP>
+template <int PW, bool FP>
 __device__ __forceinline__ QChunk q_chunk(const QSrc& src, const uint8_t* __restrict__ orig, size_t fe0, int c, int ch, int HW,
-                                          const QParams& qp, double E, int lane) {
+                                          const QParams& qp, double E, int lane, const uint8_t* __restrict__ tolmap = nullptr) {
     const int idx = ch * 64 + lane;
     unsigned long long M = 1ull << lane;
     int pos = lane + 1;
@@ -424,7 +435,7 @@ __device__ __forceinline__ QChunk q_chunk(const QSrc& src, const uint8_t* __rest
         double du = inf, dl = -inf;
         if (idx < HW) {
             const size_t e = fe0 + (size_t)idx * 3 + c;
-            const double tol = (double)orig[e] * qp.b0;
+            const double tol = PW == Q_TOL_MAP ? (double)tolmap[idx] : (double)orig[e] * qp.b0;
             const double df = (double)q_delta<FP>(src, orig, e);
             du = df + tol;
             dl = df - tol;
@@ -573,7 +584,7 @@ struct QRunD {
     int hd;
 };
 
-template <bool PW, bool FP>
+template <int PW, bool FP>
 __global__ __launch_bounds__(192) void k_q_tiles(QSrc src, const uint8_t* __restrict__ orig, const uint8_t* __restrict__ skip,
                                                  int HW, int ntiles, QParams qp, const double* __restrict__ Echain,
                                                  const QWidth* __restrict__ width, int16_t* __restrict__ tmp,
@@ -583,20 +594,22 @@ __global__ __launch_bounds__(192) void k_q_tiles(QSrc src, const uint8_t* __rest
     const int c = threadIdx.x >> 6, lane = threadIdx.x & 63;   // one wave per channel of the same pixels (they share cache lines)
     const int f = blockIdx.x / ntiles, tile = blockIdx.x % ntiles;
     if (skip[f]) return;
+    const uint8_t* const tolmap = PW == Q_TOL_MAP ? q_tol_map(Echain) : nullptr;
     const int chain = f * 3 + c;
     const size_t fe0 = (size_t)f * HW * 3;
     int16_t* t = tmp + fe0;
     const int nch = (HW + 63) >> 6;
     const int e0 = tile * QT_TILE;                              // first element of the tile in the chain
     short* ls = (short*)lds_raw + c * 64 * QT_S16;              // !PW: int16 deltas
-    unsigned* lw = (unsigned*)lds_raw + c * 64 * QT_S32;        //  PW: delta | orig << 16
+    unsigned* lw = (unsigned*)lds_raw + c * 64 * QT_S32;        //  PW: delta | orig << 16 (Q_TOL_MAP: delta | M[pixel] << 16)
     // ---- stage the tile transposed: row r = the 64 elements of chunk r (lane r walks it).
     // Frames of whole 4-pixel groups: the block's three waves load the tile TOGETHER -- a thread takes 4 pixels =
     // 12 consecutive samples (three 16-byte loads of the prediction + 12 original bytes, or 24 bytes of the delta
     // stack), forms the deltas and deals them to the three channel planes.  (A wave per channel fetching its own
     // samples with a stride of three touched every cache line three times, 2-byte / 4-byte accesses: 141 of the
     // first version's 280 us.)
-    const bool grouped = (HW & 3) == 0 && (((uintptr_t)src.pred & 15) | ((uintptr_t)src.diff & 7) | ((uintptr_t)orig & 3) | ((uintptr_t)tmp & 7)) == 0;
+    const bool grouped = (HW & 3) == 0 && (((uintptr_t)src.pred & 15) | ((uintptr_t)src.diff & 7) | ((uintptr_t)orig & 3) | ((uintptr_t)tmp & 7)) == 0 &&
+                         (PW != Q_TOL_MAP || ((uintptr_t)tolmap & 3) == 0);   // (the map: a thread's four pixels as one 4-byte load)
     // The integer walk below rests on k_q_width's table, which covers deltas in [-255, 255] -- everything compress.py:292-314
     // can produce.  The stand-alone tz_error_bound takes ANY int16 stack: a tile that holds a value outside that range
     // (`wide`) evaluates the double test of compress.py:60 itself at every step instead.
@@ -606,11 +619,13 @@ __global__ __launch_bounds__(192) void k_q_tiles(QSrc src, const uint8_t* __rest
         for (int g = threadIdx.x; g < QT_TILE / 4; g += 192) {
             const int p0 = g * 4;
             int d[12], o[12];
+            unsigned mw = 0;   // Q_TOL_MAP: the tolerances of the thread's four pixels
 #pragma unroll
             for (int k = 0; k < 12; ++k) d[k] = o[k] = 0;
             if (p0 < npix) {
                 const size_t e = fe0 + (size_t)(e0 + p0) * 3;
-                if (FP || PW) {
+                if (PW == Q_TOL_MAP) mw = *(const unsigned*)(tolmap + e0 + p0);
+                if (FP || PW == Q_TOL_ORIG) {
                     const uint3 ob = *(const uint3*)(orig + e);
                     const unsigned ow[3] = {ob.x, ob.y, ob.z};
 #pragma unroll
@@ -639,7 +654,8 @@ __global__ __launch_bounds__(192) void k_q_tiles(QSrc src, const uint8_t* __rest
                 if (PW) {
                     unsigned* w = (unsigned*)lds_raw + cc * 64 * QT_S32 + row * QT_S32 + col;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) w[i] = ((unsigned)d[3 * i + cc] & 0xFFFFu) | ((unsigned)o[3 * i + cc] << 16);
+                    for (int i = 0; i < 4; ++i)
+                        w[i] = ((unsigned)d[3 * i + cc] & 0xFFFFu) | ((PW == Q_TOL_MAP ? (mw >> (8 * i)) & 0xFFu : (unsigned)o[3 * i + cc]) << 16);
                 } else {
                     unsigned* w = (unsigned*)((short*)lds_raw + cc * 64 * QT_S16 + row * QT_S16 + col);   // 4-byte aligned: 132 r + 2 col
                     w[0] = ((unsigned)d[cc] & 0xFFFFu) | ((unsigned)d[3 + cc] << 16);
@@ -657,7 +673,8 @@ __global__ __launch_bounds__(192) void k_q_tiles(QSrc src, const uint8_t* __rest
             if (idx < HW) {
                 const size_t e = fe0 + (size_t)idx * 3 + c;
                 d = q_delta<FP>(src, orig, e);
-                if (PW) o = orig[e];
+                if (PW == Q_TOL_ORIG) o = orig[e];
+                if (PW == Q_TOL_MAP) o = tolmap[idx];
                 if (!FP && !PW) wide |= (unsigned)(d + 255) > 510u;
             }
             if (PW) lw[r * QT_S32 + lane] = ((unsigned)d & 0xFFFFu) | ((unsigned)o << 16);
@@ -699,7 +716,8 @@ __global__ __launch_bounds__(192) void k_q_tiles(QSrc src, const uint8_t* __rest
     auto val_i = [&](int mn, int mx) { return (int)((((double)mn + E) + ((double)mx - E)) / 2); };
     auto elem_d = [&](int tt, double& du, double& dl) {
         const unsigned w = lw[lane * QT_S32 + tt];
-        const double df = (double)(int)(short)(w & 0xFFFFu), tol = (double)(int)(w >> 16) * qp.b0;
+        const double df = (double)(int)(short)(w & 0xFFFFu);
+        const double tol = PW == Q_TOL_MAP ? (double)(int)(w >> 16) : (double)(int)(w >> 16) * qp.b0;
         du = df + tol;
         dl = df - tol;
     };
@@ -1013,7 +1031,7 @@ __global__ __launch_bounds__(64) void k_q_chain(const uint8_t* __restrict__ skip
 
 // The run entering tile T walked into the tile until it meets the tile's own chain (see k_q_tiles); a tile that is
 // crossed without that marks the chain for k_q_serial.
-template <bool FP>
+template <bool FP, bool MAP>
 __global__ __launch_bounds__(64) void k_q_bstitch(QSrc src, const uint8_t* __restrict__ orig, const uint8_t* __restrict__ skip,
                                                 int HW, int ntiles, QParams qp, const double* __restrict__ Echain,
                                                 int16_t* __restrict__ tmp, unsigned long long* __restrict__ spec,
@@ -1032,15 +1050,17 @@ __global__ __launch_bounds__(64) void k_q_bstitch(QSrc src, const uint8_t* __res
         return;
     }
     double E = 0.0;
-    if (qp.mode == TZ_MODE_ABS) E = fabs(qp.b0);
+    if (MAP) E = 0.0;   // (per element, from the map)
+    else if (qp.mode == TZ_MODE_ABS) E = fabs(qp.b0);
     else if (qp.mode != TZ_MODE_PWREL) E = Echain[chain];
     const QState st = tile_in[(size_t)chain * ntiles + T];
     double u = st.u, l = st.l;
     int chead = st.head;
     bool merged = false;
     for (int ch = c0; ch < c1 && !merged; ++ch) {
-        const QChunk q = qp.mode == TZ_MODE_PWREL ? q_chunk<true, FP>(src, orig, fe0, c, ch, HW, qp, E, lane)
-                                                  : q_chunk<false, FP>(src, orig, fe0, c, ch, HW, qp, E, lane);
+        const QChunk q = MAP ? q_chunk<Q_TOL_MAP, FP>(src, orig, fe0, c, ch, HW, qp, E, lane, q_tol_map(Echain))
+                         : qp.mode == TZ_MODE_PWREL ? q_chunk<Q_TOL_ORIG, FP>(src, orig, fe0, c, ch, HW, qp, E, lane)
+                                                    : q_chunk<Q_TOL_CHAIN, FP>(src, orig, fe0, c, ch, HW, qp, E, lane);
         const unsigned long long S = sp[ch];
         const double eu = u < q.pu ? u : q.pu, el = l > q.pl ? l : q.pl;
         const unsigned long long brk = __ballot(eu - el < 0.0);
@@ -1082,7 +1102,7 @@ __global__ __launch_bounds__(64) void k_q_bstitch(QSrc src, const uint8_t* __res
 // Exact serial walk of a whole chain (one wave, chunk after chunk: the algorithm of round 1), for the chains
 // k_q_bstitch marked: the true chain crossed a whole 4096-element tile out of step with the tile's speculative chain
 // (regular ramps do that).  Rewrites every mask word and run value of the chain.
-template <bool FP>
+template <bool FP, bool MAP>
 __global__ __launch_bounds__(64) void k_q_serial(QSrc src, const uint8_t* __restrict__ orig, const uint8_t* __restrict__ skip, int HW,
                                                QParams qp, const double* __restrict__ Echain, int16_t* __restrict__ tmp,
                                                unsigned long long* __restrict__ spec, const int* __restrict__ bad) {
@@ -1093,13 +1113,15 @@ __global__ __launch_bounds__(64) void k_q_serial(QSrc src, const uint8_t* __rest
     const int nch = (HW + 63) >> 6;
     unsigned long long* sp = spec + (size_t)chain * nch;
     double E = 0.0;
-    if (qp.mode == TZ_MODE_ABS) E = fabs(qp.b0);
+    if (MAP) E = 0.0;   // (per element, from the map)
+    else if (qp.mode == TZ_MODE_ABS) E = fabs(qp.b0);
     else if (qp.mode != TZ_MODE_PWREL) E = Echain[chain];
     double u = __builtin_huge_val(), l = -__builtin_huge_val();
     int chead = 0;
     for (int ch = 0; ch < nch; ++ch) {
-        const QChunk q = qp.mode == TZ_MODE_PWREL ? q_chunk<true, FP>(src, orig, fe0, c, ch, HW, qp, E, lane)
-                                                  : q_chunk<false, FP>(src, orig, fe0, c, ch, HW, qp, E, lane);
+        const QChunk q = MAP ? q_chunk<Q_TOL_MAP, FP>(src, orig, fe0, c, ch, HW, qp, E, lane, q_tol_map(Echain))
+                         : qp.mode == TZ_MODE_PWREL ? q_chunk<Q_TOL_ORIG, FP>(src, orig, fe0, c, ch, HW, qp, E, lane)
+                                                    : q_chunk<Q_TOL_CHAIN, FP>(src, orig, fe0, c, ch, HW, qp, E, lane);
         const unsigned long long first = ch == 0 ? 1ull : 0ull;
         const double eu = u < q.pu ? u : q.pu, el = l > q.pl ? l : q.pl;
         const unsigned long long brk = __ballot(eu - el < 0.0);
@@ -1413,8 +1435,11 @@ struct QFused {   // fused encode: symbols + histogram + edge elements instead o
 // h_fb (may be NULL): nframes abs tolerances, one per frame, in place of (mode, b0, b1).  The walks run in their per-chain
 // form, the one rel / absrel run: k_q_frame_bound fills the array k_q_bound would fill, and a frame whose bound is 0 is
 // skipped, which is what `abs 0` does to it (compress.py:24).
+// d_map (may be NULL; device, H * W bytes): the bound map of TZ-BM1 in place of (mode, b0, b1) -- the per-element walks with the map as
+// their tolerance source (Q_TOL_MAP).  Every scratch block below is what a pwrel job allocates: nothing of the map's is expanded
+// per frame or channel.  orig may then be NULL unless `fu` forms the deltas from it.
 static int quant_run(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const QFused* fu, const uint8_t* h_skip, int nframes,
-                     int H, int W, int mode, double b0, double b1, const double* h_fb = nullptr) {
+                     int H, int W, int mode, double b0, double b1, const double* h_fb = nullptr, const uint8_t* d_map = nullptr) {
     int HW = H * W;
     size_t fe = (size_t)HW * 3;
     int nblk = (HW + QFB - 1) / QFB;
@@ -1439,9 +1464,14 @@ static int quant_run(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const QFus
         mode = TZ_MODE_REL;   // what makes every walk read Echain; no kernel below reads b0 or b1 in this mode
         b0 = b1 = 0.0;
     }
+    if (d_map) {
+        mode = TZ_MODE_PWREL;   // what makes every walk per element; no kernel below reads b0 or b1 under Q_TOL_MAP
+        b0 = b1 = 0.0;
+    }
     TZ_TRY(tz_upload(ctx, d_skip, h_skip, nframes));
     QParams qp{mode, b0, b1};
     QSrc src{diff, fu ? fu->pred : nullptr};
+    if (d_map) d_E = (void*)d_map;   // (q_tol_map: the walks' Echain slot carries the map; the pool block is handed back with the call)
     {
         tz_prof_scope ps(ctx, TZP_QUANT);
         if (h_fb) {
@@ -1472,28 +1502,29 @@ static int quant_run(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const QFus
     hipLaunchKernelGGL((k_q_tiles<PWV, FPV>), dim3(nframes * ntiles), dim3(192), 0, ctx->stream, src, orig, (const uint8_t*)d_skip, HW, \
                        ntiles, qp, (const double*)d_E, (const QWidth*)d_width, (int16_t*)d_tmp, (unsigned long long*)d_spec,         \
                        (QState*)d_tout, (double2*)d_tagg)
-            if (pw && fu) TZ_Q_TILES(true, true);
-            else if (pw) TZ_Q_TILES(true, false);
-            else if (fu) TZ_Q_TILES(false, true);
-            else TZ_Q_TILES(false, false);
+            if (d_map && fu) TZ_Q_TILES(Q_TOL_MAP, true);
+            else if (d_map) TZ_Q_TILES(Q_TOL_MAP, false);
+            else if (pw && fu) TZ_Q_TILES(Q_TOL_ORIG, true);
+            else if (pw) TZ_Q_TILES(Q_TOL_ORIG, false);
+            else if (fu) TZ_Q_TILES(Q_TOL_CHAIN, true);
+            else TZ_Q_TILES(Q_TOL_CHAIN, false);
 #undef TZ_Q_TILES
             hipLaunchKernelGGL(k_q_chain, dim3(nchains), dim3(64), 0, ctx->stream, (const uint8_t*)d_skip, HW, ntiles,
                                (const QState*)d_tout, (const double2*)d_tagg, (QState*)d_tin, (uint8_t*)d_swal, (int16_t*)d_tmp);
             if (ntiles > 1) {
-                if (fu)
-                    hipLaunchKernelGGL(k_q_bstitch<true>, dim3(nchains * (ntiles - 1)), dim3(64), 0, ctx->stream, src, orig,
-                                       (const uint8_t*)d_skip, HW, ntiles, qp, (const double*)d_E, (int16_t*)d_tmp,
-                                       (unsigned long long*)d_spec, (const QState*)d_tin, (const uint8_t*)d_swal, (int*)d_bad);
-                else
-                    hipLaunchKernelGGL(k_q_bstitch<false>, dim3(nchains * (ntiles - 1)), dim3(64), 0, ctx->stream, src, orig,
-                                       (const uint8_t*)d_skip, HW, ntiles, qp, (const double*)d_E, (int16_t*)d_tmp,
-                                       (unsigned long long*)d_spec, (const QState*)d_tin, (const uint8_t*)d_swal, (int*)d_bad);
-                if (fu)
-                    hipLaunchKernelGGL(k_q_serial<true>, dim3(nchains), dim3(64), 0, ctx->stream, src, orig, (const uint8_t*)d_skip, HW, qp,
-                                       (const double*)d_E, (int16_t*)d_tmp, (unsigned long long*)d_spec, (const int*)d_bad);
-                else
-                    hipLaunchKernelGGL(k_q_serial<false>, dim3(nchains), dim3(64), 0, ctx->stream, src, orig, (const uint8_t*)d_skip, HW, qp,
-                                       (const double*)d_E, (int16_t*)d_tmp, (unsigned long long*)d_spec, (const int*)d_bad);
+#define TZ_Q_STITCH(FPV, MAPV)                                                                                                  \
+    do {                                                                                                                        \
+        hipLaunchKernelGGL((k_q_bstitch<FPV, MAPV>), dim3(nchains * (ntiles - 1)), dim3(64), 0, ctx->stream, src, orig,          \
+                           (const uint8_t*)d_skip, HW, ntiles, qp, (const double*)d_E, (int16_t*)d_tmp,                         \
+                           (unsigned long long*)d_spec, (const QState*)d_tin, (const uint8_t*)d_swal, (int*)d_bad);             \
+        hipLaunchKernelGGL((k_q_serial<FPV, MAPV>), dim3(nchains), dim3(64), 0, ctx->stream, src, orig, (const uint8_t*)d_skip,  \
+                           HW, qp, (const double*)d_E, (int16_t*)d_tmp, (unsigned long long*)d_spec, (const int*)d_bad);        \
+    } while (0)
+                if (fu && d_map) TZ_Q_STITCH(true, true);
+                else if (fu) TZ_Q_STITCH(true, false);
+                else if (d_map) TZ_Q_STITCH(false, true);
+                else TZ_Q_STITCH(false, false);
+#undef TZ_Q_STITCH
                 if (ctx->prof_on) {   // how many chains took the fallback (a test asserts that its ramps really do)
                     std::vector<int> hb(nchains, 0);
                     TZ_HIP(ctx, hipMemcpyAsync(hb.data(), d_bad, sizeof(int) * nchains, hipMemcpyDeviceToHost, ctx->stream));
@@ -1598,6 +1629,23 @@ int tzk_quant_frames(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const tz_q
     if ((((uintptr_t)fu->pred & 15) | ((uintptr_t)orig & 3)) != 0) return TZ_OK;   // k_q_fill_sym: 16-byte pred, 4-byte orig loads
     QFused q{fu->pred, fu->d_zero_mask, fu->apply_offset, fu->sym, fu->d_hist, fu->d_edge};
     TZ_TRY(quant_run(ctx, orig, nullptr, &q, h_skip, nframes, H, W, TZ_MODE_ABS, 0.0, 0.0, h_bounds));
+    *done = true;
+    return TZ_OK;
+}
+
+// The bound map TZ-BM1 (tz_set_bound_map, tz_error_bound_map): every sample of pixel p is quantised under the abs tolerance
+// d_map[p] (device, H * W bytes), by the reference's pwrel walk with the map in place of orig * b0.  diff != NULL: the delta
+// stack is quantised in place (orig is not read).  diff == NULL: the fused lossy front on pred / orig, as tzk_quant_sd_fused and
+// under its conditions; *done says whether it ran.
+int tzk_quant_map(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const tz_quant_fused* fu, const uint8_t* h_skip, int nframes, int H,
+                  int W, const uint8_t* d_map, bool* done) {
+    if (done) *done = false;
+    if (nframes <= 0 || H <= 0 || W <= 0) return TZ_OK;
+    if (diff) return quant_run(ctx, orig, diff, nullptr, h_skip, nframes, H, W, TZ_MODE_ABS, 0.0, 0.0, nullptr, d_map);
+    if (H != fu->Hp || W != fu->Wp || ((size_t)H * W) % 8 || (((uintptr_t)fu->sym) & 15)) return TZ_OK;
+    if ((((uintptr_t)fu->pred & 15) | ((uintptr_t)orig & 3)) != 0) return TZ_OK;   // k_q_fill_sym: 16-byte pred, 4-byte orig loads
+    QFused q{fu->pred, fu->d_zero_mask, fu->apply_offset, fu->sym, fu->d_hist, fu->d_edge};
+    TZ_TRY(quant_run(ctx, orig, nullptr, &q, h_skip, nframes, H, W, TZ_MODE_ABS, 0.0, 0.0, nullptr, d_map));
     *done = true;
     return TZ_OK;
 }
@@ -2056,11 +2104,16 @@ __global__ void k_lat_params(const double* __restrict__ Echain, const uint8_t* _
     out[i] = p;
 }
 
-template <bool PW>
+// PW: the tolerance source (Q_TOL_*).  o: the original sample under Q_TOL_ORIG, the map byte M[pixel] under Q_TOL_MAP (TZ-BM1:
+// e = M[p] is an integer in [0, 255], so E = e)
+template <int PW>
 __device__ __forceinline__ int lat_apply(int d, unsigned o, const LatP p, double b0) {
     const unsigned ad = (unsigned)(d < 0 ? -d : d);
     unsigned E, k;
-    if (PW) {
+    if (PW == Q_TOL_MAP) {
+        E = p.E ? o : 0u;
+        k = (ad + E) / (2u * E + 1u);
+    } else if (PW) {
         const double e = o ? (double)o * b0 : 0.0;               // (0 * inf is no tolerance)
         E = e >= 255.0 ? 255u : (e >= 1.0 ? (unsigned)e : 0u);
         if (!p.E) E = 0u;
@@ -2084,15 +2137,16 @@ __device__ __forceinline__ void lat_chains(const LatP* __restrict__ P, size_t f,
 // Stand-alone / unfused form: an int16 delta stack in place (tz_lattice_bound, and tz_encode where the fused front below does
 // not apply).  diff need only be 2-byte aligned: `head` elements in front of the first 16-byte boundary and the n - head - 8 n8
 // behind the vector groups go one by one; a group of 8 that straddles a frame boundary takes its chains element by element.
-template <bool PW>
+// Q_TOL_MAP: `orig` is the bound map, one byte per pixel of a frame (the deltas are there already: no original is read)
+template <int PW>
 __device__ __forceinline__ void lattice1(int16_t* __restrict__ diff, const uint8_t* __restrict__ orig, const LatP* __restrict__ P,
                                          double b0, size_t fe, size_t e) {
     const size_t f = e / fe;
     const unsigned c = (unsigned)((e - f * fe) % 3);
-    diff[e] = (int16_t)lat_apply<PW>(diff[e], PW ? orig[e] : 0u, P[3 * f + c], b0);
+    diff[e] = (int16_t)lat_apply<PW>(diff[e], PW == Q_TOL_MAP ? orig[(e - f * fe) / 3] : (PW ? orig[e] : 0u), P[3 * f + c], b0);
 }
 
-template <bool PW>
+template <int PW>
 __global__ __launch_bounds__(256) void k_lattice(int16_t* __restrict__ diff, const uint8_t* __restrict__ orig, const LatP* __restrict__ P,
                                                  double b0, size_t n, size_t fe, size_t head, size_t n8) {
     const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2110,8 +2164,10 @@ __global__ __launch_bounds__(256) void k_lattice(int16_t* __restrict__ diff, con
         unsigned q[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int lo = lat_apply<PW>((int)(short)(w[j] & 0xFFFFu), PW ? orig[e0 + 2 * j] : 0u, r[(2 * j) % 3], b0);
-            const int hi = lat_apply<PW>((int)w[j] >> 16, PW ? orig[e0 + 2 * j + 1] : 0u, r[(2 * j + 1) % 3], b0);
+            const int lo = lat_apply<PW>((int)(short)(w[j] & 0xFFFFu), PW == Q_TOL_MAP ? orig[(r0 + 2 * j) / 3] : (PW ? orig[e0 + 2 * j] : 0u),
+                                         r[(2 * j) % 3], b0);
+            const int hi = lat_apply<PW>((int)w[j] >> 16, PW == Q_TOL_MAP ? orig[(r0 + 2 * j + 1) / 3] : (PW ? orig[e0 + 2 * j + 1] : 0u),
+                                         r[(2 * j + 1) % 3], b0);
             q[j] = ((unsigned)lo & 0xFFFFu) | ((unsigned)hi << 16);
         }
         v8[i] = make_uint4(q[0], q[1], q[2], q[3]);
@@ -2172,9 +2228,15 @@ static int lattice_params(tz_ctx* ctx, const uint8_t* orig, const uint8_t* h_ski
     return TZ_OK;
 }
 
+// d_map (may be NULL; device, H * W bytes): the bound map of TZ-BM1 in place of (mode, b0, b1) and h_bounds; orig is then not read
 int tzk_lattice(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* h_skip, int nframes, int H, int W, int mode, double b0,
-                double b1, const double* h_bounds) {
-    if (!h_bounds) {
+                double b1, const double* h_bounds, const uint8_t* d_map) {
+    if (d_map) {
+        h_bounds = nullptr;
+        mode = TZ_MODE_PWREL;   // (lattice_params: LatP.E only says whether the frame is quantised)
+        b0 = 1.0;
+        b1 = 0.0;
+    } else if (!h_bounds) {
         TZ_TRY(lattice_check(ctx, mode, b0, b1));
         if (b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0)) return TZ_OK;   // no tolerance: nothing changes
         if (tz_lattice_is_identity(mode, b0, b1)) return TZ_OK;                 // every chain has E == 0
@@ -2194,7 +2256,9 @@ int tzk_lattice(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* 
     const bool pw = !h_bounds && mode == TZ_MODE_PWREL;
     const size_t items = std::max(n8, head + (n - head - 8 * n8));
     tz_prof_scope ps(ctx, TZP_QUANT);
-    if (pw) hipLaunchKernelGGL(k_lattice<true>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, diff, orig, d_lp, b0, n, fe, head, n8);
+    // (true = Q_TOL_ORIG, false = Q_TOL_CHAIN; under Q_TOL_MAP the map goes in the orig slot)
+    if (d_map) hipLaunchKernelGGL(k_lattice<Q_TOL_MAP>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, diff, d_map, d_lp, b0, n, fe, head, n8);
+    else if (pw) hipLaunchKernelGGL(k_lattice<true>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, diff, orig, d_lp, b0, n, fe, head, n8);
     else hipLaunchKernelGGL(k_lattice<false>, dim3(grid_for(items, 256)), dim3(256), 0, ctx->stream, diff, orig, d_lp, b0, n, fe, head, n8);
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
@@ -2207,12 +2271,23 @@ int tzk_lattice(tz_ctx* ctx, const uint8_t* orig, int16_t* diff, const uint8_t* 
 // with THEIR chain's tolerance (the last frame's at a frame start).  Histogram: HistLds / HistAcc above.
 static constexpr int LAT_FLAT = 0, LAT_GRAY = 1, LAT_S3 = 2;
 
-template <int LAY, bool HIST, bool PW>
+// Q_TOL_MAP: the tolerance of an element is the byte of its pixel in the map (H x W, shared by all frames and channels: cached),
+// which travels as the eight bytes of b0 (lat_tol_arg on the host): that source reads no b0.
+__device__ __forceinline__ const uint8_t* lat_tol_map(double b0) { return (const uint8_t*)(uintptr_t)__double_as_longlong(b0); }
+static double lat_tol_arg(const uint8_t* d_map) {
+    double v;
+    static_assert(sizeof(v) == sizeof(d_map), "a device pointer fills the argument's eight bytes");
+    memcpy(&v, &d_map, sizeof(v));
+    return v;
+}
+
+template <int LAY, bool HIST, int PW>
 __global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_lattice_sd(const float4* __restrict__ pred, const uint2* __restrict__ orig,
                                                                         const uint8_t* __restrict__ zero_mask, const LatP* __restrict__ P,
                                                                         double b0, size_t n8, unsigned frame_items, int apply_offset,
                                                                         uint4* __restrict__ out, unsigned long long* __restrict__ hist,
                                                                         int16_t* __restrict__ edge) {
+    const uint8_t* const tol = PW == Q_TOL_MAP ? lat_tol_map(b0) : nullptr;
     __shared__ unsigned hraw[HIST ? HL_WORDS : 1];
     HistLds& hl = *(HistLds*)hraw;
     constexpr bool do_hist = HIST;
@@ -2255,6 +2330,11 @@ __global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_lattice_sd(const fl
         if (LAY == LAT_GRAY) r[0] = r[1] = r[2] = P[3 * f];
         else lat_chains(P, f, (unsigned)(((i % 3) * 2) % 3), r);   // (a frame holds a multiple of 3 elements: channel of 8 i = 8 i mod 3)
         int q[8];
+        if (PW == Q_TOL_MAP) {   // the lane's 8 symbols start at element 8 ES (i - f frame_items) of frame f
+            const unsigned fi = (unsigned)(i - f * frame_items) * 8u;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) ob[k] = tol[LAY == LAT_GRAY ? fi + k : (fi + k) / 3u];
+        }
 #pragma unroll
         for (int k = 0; k < 8; ++k) q[k] = lat_apply<PW>(zero ? 0 : d[k], ob[k], r[LAY == LAT_GRAY ? 0 : k % 3], b0);
         int pq[3] = {0, 0, 0};
@@ -2267,7 +2347,9 @@ __global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_lattice_sd(const fl
                 const int c = LAY == LAT_GRAY ? 0 : (LAY == LAT_FLAT ? 2 : j);      // at a frame start the elements in front are ..., 1, 2
                 const LatP lp = fstart ? P[3 * pf + c] : r[c];
                 const unsigned o = origb[e];
-                pq[j] = lat_apply<PW>(pzero ? 0 : (int)(predf[e] * 255.0f) - (int)o, o, lp, b0);
+                // (the pixel of e within ITS frame pf: a frame holds 8 ES frame_items elements, three per pixel)
+                const unsigned t = PW == Q_TOL_MAP ? tol[(e - pf * ((size_t)8 * ES * frame_items)) / 3] : o;
+                pq[j] = lat_apply<PW>(pzero ? 0 : (int)(predf[e] * 255.0f) - (int)o, t, lp, b0);
             }
         }
         unsigned V[4];
@@ -2305,8 +2387,15 @@ __global__ __launch_bounds__(HIST ? HB_THREADS : 256) void k_lattice_sd(const fl
 
 int tzk_lattice_sd_fused(tz_ctx* ctx, tz_layout layout, const float* pred, const uint8_t* orig, const uint8_t* d_zero_mask,
                          const uint8_t* h_skip, int nframes, int H, int W, int Hp, int Wp, int mode, double b0, double b1,
-                         const double* h_bounds, int apply_offset, int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done) {
+                         const double* h_bounds, int apply_offset, int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done,
+                         const uint8_t* d_map) {
     *done = false;
+    if (d_map) {
+        h_bounds = nullptr;
+        mode = TZ_MODE_PWREL;   // (lattice_params: LatP.E only says whether the frame is quantised)
+        b0 = 1.0;
+        b1 = 0.0;
+    }
     if (!h_bounds) TZ_TRY(lattice_check(ctx, mode, b0, b1));
     if (layout.plane_h) return TZ_OK;   // TZ-SD2 has no fused front
     const int lay = layout.channels == 1 ? LAT_GRAY : (layout.stride == 3 ? LAT_S3 : LAT_FLAT);
@@ -2317,6 +2406,7 @@ int tzk_lattice_sd_fused(tz_ctx* ctx, tz_layout layout, const float* pred, const
     TZ_TRY(lattice_params(ctx, orig, h_skip, nframes, H * W, mode, b0, b1, h_bounds, &d_lp));
     const size_t n8 = fsym * nframes / 8;
     const bool pw = !h_bounds && mode == TZ_MODE_PWREL;
+    if (d_map) b0 = lat_tol_arg(d_map);
     tz_prof_scope ps(ctx, TZP_DELTA);
     const dim3 grid(d_hist ? std::min(HB_GRID, grid_for(n8, HB_THREADS)) : grid_for(n8, 256)), block(d_hist ? HB_THREADS : 256);
 #define TZ_LAT_LAUNCH(L, HV, PWV)                                                                                                 \
@@ -2324,10 +2414,12 @@ int tzk_lattice_sd_fused(tz_ctx* ctx, tz_layout layout, const float* pred, const
                        d_lp, b0, n8, (unsigned)(fsym / 8), apply_offset, (uint4*)sym, d_hist, d_edge)
 #define TZ_LAT_LAYOUT(L)                            \
     do {                                            \
-        if (d_hist && pw) TZ_LAT_LAUNCH(L, true, true);        \
-        else if (d_hist) TZ_LAT_LAUNCH(L, true, false);        \
-        else if (pw) TZ_LAT_LAUNCH(L, false, true);            \
-        else TZ_LAT_LAUNCH(L, false, false);                   \
+        if (d_hist && d_map) TZ_LAT_LAUNCH(L, true, Q_TOL_MAP);       \
+        else if (d_map) TZ_LAT_LAUNCH(L, false, Q_TOL_MAP);           \
+        else if (d_hist && pw) TZ_LAT_LAUNCH(L, true, Q_TOL_ORIG);    \
+        else if (d_hist) TZ_LAT_LAUNCH(L, true, Q_TOL_CHAIN);         \
+        else if (pw) TZ_LAT_LAUNCH(L, false, Q_TOL_ORIG);             \
+        else TZ_LAT_LAUNCH(L, false, Q_TOL_CHAIN);                    \
     } while (0)
     if (lay == LAT_FLAT) TZ_LAT_LAYOUT(LAT_FLAT);
     else if (lay == LAT_GRAY) TZ_LAT_LAYOUT(LAT_GRAY);
@@ -3706,6 +3798,66 @@ int tzk_quality(tz_ctx* ctx, const uint8_t* orig, const uint8_t* dec, int nframe
         hipLaunchKernelGGL(k_quality<true>, dim3((unsigned)G), dim3(256), 0, ctx->stream, orig, dec, n, fe, head, per_block, d_out);
     else
         hipLaunchKernelGGL(k_quality<false>, dim3((unsigned)G), dim3(256), 0, ctx->stream, orig, dec, n, fe, head, per_block, d_out);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+// ------------------------------------------------------------------- bound-map check (TZ-BM1)
+// tz_map_check / tz_encode_map_check (slow statement: tezip_amd/boundmap.py check): per frame of two unpadded uint8 stacks the
+// number of samples with |dec - orig| > M[pixel] and the largest max(|dec - orig| - M[pixel], 0).  A workgroup owns a run of
+// pixels of ONE frame (grid.y), a thread a pixel at a time: 7 B read per pixel, the map's byte from cache.  Exact integers per
+// thread, per wave, per workgroup, then one atomic pair per workgroup that found something, as k_quality.
+__global__ __launch_bounds__(256) void k_map_check(const uint8_t* __restrict__ orig, const uint8_t* __restrict__ dec,
+                                                   const uint8_t* __restrict__ map, size_t HW, tz_map_record* __restrict__ out) {
+    __shared__ unsigned long long red_n[4];
+    __shared__ unsigned red_x[4];
+    const size_t f = blockIdx.y, fe0 = f * HW * 3;
+    unsigned long long nv = 0;
+    unsigned mx = 0;
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < HW; p += (size_t)gridDim.x * 256) {
+        const int m = map[p];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int d = (int)dec[fe0 + 3 * p + c] - (int)orig[fe0 + 3 * p + c];
+            const int x = (d < 0 ? -d : d) - m;
+            nv += x > 0;
+            mx = max(mx, (unsigned)max(x, 0));
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        nv += __shfl_xor(nv, off, 64);
+        mx = max(mx, (unsigned)__shfl_xor((int)mx, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red_n[threadIdx.x >> 6] = nv;
+        red_x[threadIdx.x >> 6] = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        nv = red_n[0] + red_n[1] + red_n[2] + red_n[3];
+        mx = max(max(red_x[0], red_x[1]), max(red_x[2], red_x[3]));
+        if (nv != 0) {   // (nothing found: the record stays as cleared)
+            __hip_atomic_fetch_add(&out[f].violations, nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_max(&out[f].max_excess, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+int tzk_map_check(tz_ctx* ctx, const uint8_t* orig, const uint8_t* dec, const uint8_t* d_map, int nframes, int H, int W,
+                  tz_map_record* d_out) {
+    if (nframes <= 0 || H <= 0 || W <= 0) return TZ_OK;
+    const size_t HW = (size_t)H * W;
+    TZ_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(tz_map_record) * nframes, ctx->stream));
+    // enough workgroups per frame to fill the chip over the whole stack, none without a pixel
+    const size_t want = std::max<size_t>(1, (size_t)(4 * kCUs + nframes - 1) / nframes);
+    const unsigned gx = (unsigned)std::min(want, (HW + 255) / 256);
+    tz_prof_scope ps(ctx, TZP_QUALITY);
+    for (int f0 = 0; f0 < nframes; f0 += 65535) {   // (grid.y holds 65535 frames)
+        const int nf = std::min(65535, nframes - f0);
+        hipLaunchKernelGGL(k_map_check, dim3(gx, (unsigned)nf), dim3(256), 0, ctx->stream, orig + (size_t)f0 * HW * 3,
+                           dec + (size_t)f0 * HW * 3, d_map, HW, d_out + f0);
+    }
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }

@@ -133,6 +133,10 @@ struct tz_ctx {
     int decode_unfused = 0;                 // TEZIP_DECODE_UNFUSED=1: tz_decode as scan + reconstruct launches (cross-check)
     int payload_channels = 3;               // tz_set_payload_channels: 1 = the payload of a gray job holds channel 0 alone
     std::vector<double> frame_bounds;       // tz_set_frame_bounds: one abs tolerance per frame of the encoder rollout (empty: none)
+    // tz_set_bound_map (TZ-BM1): the H x W uint8 map of abs tolerances, resident on the device from the call that set it
+    // (map_h == 0: none); map_max = its largest entry (0: the lossless job)
+    uint8_t* d_bound_map = nullptr;
+    int map_h = 0, map_w = 0, map_max = 0;
     int delta_stride_mode = 0;              // tz_set_delta_stride: 1 = the spatial delta of the payload runs at the channel stride
     int delta_plane = 0;                    // tz_set_delta_plane: 1 = the spatial delta of the payload is the 2-D one, TZ-SD2
     int quantiser = 0;                      // tz_set_quantiser: 0 = the reference's greedy walk, 1 = the lattice quantiser TZ-QL1
@@ -364,6 +368,10 @@ struct tz_quant_fused {
 };
 int tzk_quant_frames(tz_ctx*, const uint8_t* orig, int16_t* diff, const tz_quant_fused* fu, const uint8_t* h_skip, int nframes,
                      int H, int W, const double* h_bounds, bool* done);
+// the greedy walk under the bound map d_map (TZ-BM1; device, H * W bytes), in the two forms of tzk_quant_frames; orig is read only
+// by the fused front
+int tzk_quant_map(tz_ctx*, const uint8_t* orig, int16_t* diff, const tz_quant_fused* fu, const uint8_t* h_skip, int nframes, int H,
+                  int W, const uint8_t* d_map, bool* done);
 // The layout of the payload, stated once per layer: elements per pixel, and how far in front the element
 // lies that the spatial delta subtracts.  flat {3, 1} is the reference's; gray {1, 1} stores channel 0 alone
 // (tz_set_payload_channels(1)); channel stride {3, 3} takes the same channel of the pixel in front (tz_set_delta_stride(1));
@@ -388,11 +396,13 @@ int tzk_spatial_delta(tz_ctx*, tz_layout, const int16_t* in, size_t n, const int
 // pred / orig, where its kernel applies (unpadded frames of whole 16-byte groups on 16-byte boundaries: *done).  d_zero_mask as
 // tzk_delta's; d_edge (may be NULL) receives the first and the last element of the quantised stack (channel 0's under the gray
 // layout, nothing under the channel stride).
+// d_map (may be NULL; device, H * W bytes): the bound map of TZ-BM1 in place of (mode, b0, b1) and h_bounds -- e = d_map[pixel].
 int tzk_lattice(tz_ctx*, const uint8_t* orig, int16_t* diff, const uint8_t* h_skip, int nframes, int H, int W, int mode, double b0,
-                double b1, const double* h_bounds);
+                double b1, const double* h_bounds, const uint8_t* d_map = nullptr);
 int tzk_lattice_sd_fused(tz_ctx*, tz_layout, const float* pred, const uint8_t* orig, const uint8_t* d_zero_mask, const uint8_t* h_skip,
                          int nframes, int H, int W, int Hp, int Wp, int mode, double b0, double b1, const double* h_bounds,
-                         int apply_offset, int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done);
+                         int apply_offset, int16_t* sym, unsigned long long* d_hist, int16_t* d_edge, bool* done,
+                         const uint8_t* d_map = nullptr);
 bool tz_lattice_is_identity(int mode, double b0, double b1);   // the worst-case tolerance of the job is below 1: q == d everywhere
 // TZ-SD2 (k_sdelta_plane; k_unplane_cols + k_unplane_rows) on nframes x H x W x C elements at any 2-byte alignment.  in of
 // tzk_sdelta_plane holds cin elements per pixel: cin == C, or 3 with C = 1 (channel 0 is taken).  tzk_unplane may run in place.
@@ -416,6 +426,9 @@ int tzk_decode_tail(tz_ctx*, tz_layout, const int16_t* in, const int16_t* h_lut2
                     uint8_t* out);
 // per-frame (sse, max |dec - orig|, #changed) of two unpadded nframes x fe uint8 stacks; d_out (device) is cleared here
 int tzk_quality(tz_ctx*, const uint8_t* orig, const uint8_t* dec, int nframes, size_t fe, tz_frame_quality* d_out);
+// per-frame (#samples with |dec - orig| > d_map[pixel], largest excess) of two unpadded nframes x H x W x 3 uint8 stacks under the
+// H x W bound map d_map (device); d_out (device) is cleared here
+int tzk_map_check(tz_ctx*, const uint8_t* orig, const uint8_t* dec, const uint8_t* d_map, int nframes, int H, int W, tz_map_record* d_out);
 // the same records for what the quantised deltas q of the deltas d (tzk_delta's, int16, unpadded like orig) reconstruct to:
 // clamp(orig + d - q, 0, 255) against orig, with no decoded stack in memory (k_bound_err); d_out (device) is cleared here.
 // channels 1: what a one-channel payload decodes to -- channel 0's reconstruction in all three channels (fe % 3 == 0)

@@ -60,7 +60,7 @@ def requested_contract():
     return int(v) if v in ("1", "2") else None
 
 
-def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta="flat", quant="greedy"):
+def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta="flat", quant="greedy", bound_map=None):
     from . import _lib
     if contract not in (1, 2):
         raise ValueError("contract must be 1 or 2, not %r" % (contract,))
@@ -75,6 +75,8 @@ def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta
         doc["sdelta"] = sdelta           # other job has no such key
     if quant == "lattice":      # a --quant lattice job; every other job has no such key
         doc["quant"] = "lattice"
+    if bound_map is not None:   # a --bound-map job: {"max", "exact_pixels"}, informational (`-u` does not read it); else no such key
+        doc["bound_map"] = {"max": int(bound_map["max"]), "exact_pixels": int(bound_map["exact_pixels"])}
     with open(os.path.join(out_dir, NAME), "w", encoding="UTF-8") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")

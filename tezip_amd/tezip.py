@@ -15,7 +15,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "tezip_amd"
 
-from . import compress, decompress, frametarget, sdauto, target, train  # noqa: E402
+from . import boundmap, compress, decompress, frametarget, sdauto, target, train  # noqa: E402
 
 # (short, long, argparse keywords) -- tezip.py:88-99
 FLAG_TABLE = (
@@ -100,6 +100,10 @@ FLAG_TABLE = (
     # object with a "frame_bounds" list (the bound_search.json of a --per-frame job replays); 0 keeps a frame lossless; entries
     # at frames that are stored exactly are taken as 0 (compress.run(FRAME_BOUNDS=FILE))
     (None, "--frame-bounds", dict(type=str, default=None, metavar="FILE", dest="frame_bounds")),
+    # not in the reference: with -c -m abs, IN PLACE of -b: one abs bound per PIXEL from a map of the images' own size -- a .npy
+    # holding a 2-D uint8 array, or an image with one channel (or three equal ones); 0 keeps a pixel exact in every frame
+    # (definition TZ-BM1 in tezip_amd/boundmap.py).  The files are ordinary ones: -u needs no flag (compress.run(BOUND_MAP=FILE))
+    (None, "--bound-map", dict(type=str, default=None, metavar="FILE", dest="bound_map")),
     # not in the reference: with -c, the quantiser of a lossy job.  greedy (also when the flag is absent) = the reference's
     # error_bound, which merges runs of neighbouring deltas; lattice = every delta on its own to the nearest multiple of
     # 2 floor(E) + 1 under the same tolerance E (definition TZ-QL1 in tezip_amd/lattice.py; smaller on data that is not smooth,
@@ -330,6 +334,28 @@ def check_frame_bounds_flags(arg):
     return None
 
 
+def check_bound_map_flag(arg):
+    """--bound-map goes with -c -m abs in place of -b and of every way to find a bound; one single-GPU job without --sweep.  The
+    file is read here (its size is checked once the images are listed).  Returns None, or the message of a refusal."""
+    path = getattr(arg, "bound_map", None)
+    if path is None:
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return boundmap.NEEDS_COMPRESS
+    if getattr(arg, "sweep", None) is not None:
+        return boundmap.NO_SWEEP
+    problem = boundmap.check_flags(path, arg.mode[0] if arg.mode else None, arg.bound, getattr(arg, "target_psnr", None),
+                                   getattr(arg, "target_ratio", None), bool(getattr(arg, "per_frame", False)),
+                                   getattr(arg, "frame_bounds", None), int(os.environ.get("WORLD_SIZE", "1")) > 1)
+    if problem:
+        return problem
+    try:
+        boundmap.load(path)
+    except ValueError as e:
+        return str(e)
+    return None
+
+
 def check_verify_flag(arg):
     """--verify is valid with -u only; `require` needs frame_digests.json in the directory and one GPU.  Returns None, or the
     message of a refusal."""
@@ -385,6 +411,10 @@ def check_compress(arg):
 def _main(arg):
     frames, problem = check_frames_flag(arg)
     if problem:   # exit status 2, as decompress.adopt_contract's errors: nothing was written
+        print("ERROR:", problem)
+        sys.exit(2)
+    problem = check_bound_map_flag(arg)
+    if problem:   # likewise (in front of the other flags' checks: a refusal of this job names the flag that defines it)
         print("ERROR:", problem)
         sys.exit(2)
     problem = check_frame_bounds_flags(arg)
@@ -459,7 +489,8 @@ def _main(arg):
     print("compress mode")
     db, ratio = getattr(arg, "target_psnr", None), getattr(arg, "target_ratio", None)
     per_frame, bounds_file = bool(getattr(arg, "per_frame", False)), getattr(arg, "frame_bounds", None)
-    if bounds_file is not None:   # an `abs` job whose bounds come from the file: the same checks with a bound in -b's place
+    map_file = getattr(arg, "bound_map", None)
+    if bounds_file is not None or map_file is not None:   # an `abs` job whose bounds come from the file: the same checks with a bound in -b's place
         problem = check_compress(argparse.Namespace(**dict(vars(arg), bound=[0.0])))
     elif db is not None or ratio is not None:   # the job is an `abs` job whose bound is still to be found: the same checks, and `abs` is printed
         problem = check_compress(argparse.Namespace(**dict(vars(arg), mode=["abs"], bound=[0.0])))
@@ -474,6 +505,13 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if map_file is not None:   # (every other flag travels with it; the jobs without it are the calls below)
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
+                            arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), GRAY=bool(getattr(arg, "gray", False)),
+                            SDELTA=getattr(arg, "sdelta", None) or "flat", SSIM=bool(getattr(arg, "ssim", False)),
+                            QUANT=getattr(arg, "quant", None) or "greedy", BOUND_MAP=map_file)
     if getattr(arg, "quant", None) == "lattice":   # (greedy is the job without the flag: the calls below; every other flag travels with it)
         searched = db is not None or ratio is not None or bounds_file is not None
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs" if searched else arg.mode[0],
