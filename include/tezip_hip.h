@@ -187,6 +187,43 @@ int tz_rollout_decode(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int
                       uint8_t* key_mask);
 /* Copy out the prediction stack of the last rollout: nt*Hp*Wp*3 float32. */
 int tz_get_predictions(tz_ctx* ctx, float* out);
+/* ---- closed-loop prediction, definition TZ-CL1 (no reference counterpart: inside a window compress.py:230 feeds the predictor
+ * its own last prediction, so a w-frame window ends on a (w-1)-step extrapolation; `tezip.py -c --loop closed`, DESIGN.md
+ * section 9, slow statement in tezip_amd/closedloop.py).  The decoder holds the decoded frame t-1 when it predicts frame t; fed
+ * THAT frame, every prediction is a one-step prediction, and encoder and decoder stay in lock-step because both feed the same
+ * decoded bytes.
+ *   key mask, groups   exactly those of tz_rollout with the same warm_up and window > 0 (a trigger on frame nt-1 makes it a key
+ *                      frame).  Frame 0, warm-up frames and key frames are stored exactly: their decoded frame is the original.
+ *   non-key frame t, in order inside its window:
+ *                      in     = dec[t-1] / 255 as a float32 divide, zero outside H x W (how a key frame is fed)
+ *                      pred_t = next(in)
+ *                      x      = trunc(f32(pred_t * 255)) cropped to H x W        d = x - orig_t
+ *                      q_t    = d where the job's quantiser is the identity (tz_encode's rule), else TZ-QL1 with E = min(255, floor(|b0|))
+ *                      dec[t] = clamp(x - q_t, 0, 255)                            (what tz_decode computes)
+ *   stored stack       what tz_encode(mode, b0, b1) makes of the final predictions: q is a pure function of (pred_t, orig_t, bound),
+ *                      so the unchanged back half reproduces the loop's q under every layout, coder and report.
+ * tz_rollout_closed: frames, nt, H, W, warm_up, key_mask as tz_rollout (frames == NULL: the staged stack); window > 0.
+ *   Lossless (b0 == 0, or an identity by tz_encode's rule under the quantiser in force): the decoded frame is the original, so all
+ *   predictions are independent -- one schedule of "predict from a u8 frame" items over the frame stack, in full batches.
+ *   Lossy: step s predicts frame k + s of every window that still has one, then k_cl_step forms d, q and dec for exactly those
+ *   frames into a u8 stack the next step reads.  Needs tz_set_quantiser(1) and TZ_MODE_ABS: the greedy walk and the rel bounds
+ *   are no function of one sample (TZ_ERR_UNSUPPORTED; also for window == 0, per-frame bounds, a bound map and a one-channel payload).
+ *   It leaves the context as tz_rollout does (prediction stack, key mask, contract stamp) and STAMPS the loop: tz_rollout_loop
+ *   returns 1 (0 after any other rollout, TZ_ERR_STATE without one).  On a stamped rollout tz_encode, tz_encode_begin, tz_encode_delta,
+ *   tz_bound_probe, tz_size_probe and tz_sdelta_probe return TZ_ERR_STATE, with a message that names the loop's parameters, when
+ *   called with another mode, bound or quantiser, under tz_set_frame_bounds or tz_set_bound_map, or with
+ *   tz_set_payload_channels(ctx, 1): the predictions serve the loop's job alone.
+ * tz_rollout_decode_closed: key_frames / key discovery as tz_rollout_decode; payload (host, device, or NULL = the payload staged
+ *   with tz_payload_begin / tz_payload_put), payload_len == nt*H*W*3, table / table_len as tz_decode.  The payload becomes q by the
+ *   inverse remap and inverse spatial delta of the layout in force (flat, tz_set_delta_stride, tz_set_delta_plane; byte planes are
+ *   undone by the caller as for tz_decode); then the same loop runs with k_cl_recon (dec = clamp(x - q, 0, 255)) on each step's
+ *   frames, reading dec[t-1] from its own output.  The decoded stack stays resident for tz_decoded_get / tz_decoded_digests.
+ *   A one-channel payload is TZ_ERR_UNSUPPORTED. */
+int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, int mode, double b0,
+                      double b1, uint8_t* key_mask);
+int tz_rollout_loop(tz_ctx* ctx);
+int tz_rollout_decode_closed(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, const int16_t* payload,
+                             size_t payload_len, const int16_t* table, int table_len, uint8_t* key_mask);
 
 /* ---- encoder back half on the context-resident rollout (compress.py:289-373) ---------------
  * payload: nt*H*W*3 int16 = rank(1600 - sd) when bit 0 of `entropy` is set, else sd.

@@ -55,6 +55,11 @@ _SIGS = {
     "tz_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                              C.c_void_p, C.c_void_p]),
     "tz_rollout_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tz_rollout_closed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                    C.c_void_p]),
+    "tz_rollout_loop": (C.c_int, [C.c_void_p]),
+    "tz_rollout_decode_closed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.c_int, C.c_void_p]),
     "tz_range_restart": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "tz_rollout_decode_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p]),
@@ -579,6 +584,48 @@ class Context:
         key = np.zeros(nt, np.uint8)
         self._ck(self.lib.tz_rollout_decode(self.h, None if key_frames is None else _ptr(key_frames, np.uint8), nt, h, w,
                                             warm_up, key.ctypes.data))
+        self._shape = (nt, h, w)
+        return key.astype(bool)
+
+    def rollout_closed(self, frames, warm_up, window, mode="abs", bound=(0.0,)):
+        """tz_rollout_closed (TZ-CL1, tezip_amd/closedloop.py): the rollout of the job (mode, bound) under the quantiser in force
+        with the DECODED frame fed back; frames as for rollout.  Returns the key mask."""
+        if frames is None:
+            nt, h, w = self._staged
+        else:
+            self._check_stack(frames, "frames")
+            nt, h, w = frames.shape[:3]
+        b0, b1 = _bounds(bound)
+        key = np.zeros(nt, np.uint8)
+        self._ck(self.lib.tz_rollout_closed(self.h, None if frames is None else _ptr(frames, np.uint8), nt, h, w, warm_up, int(window or 0),
+                                            MODES[mode], b0, b1, key.ctypes.data))
+        self._shape = (nt, h, w)
+        return key.astype(bool)
+
+    def rollout_loop(self):
+        """tz_rollout_loop: 1 when the resident predictions are a closed loop's, 0 after any other rollout."""
+        rc = int(self.lib.tz_rollout_loop(self.h))
+        if rc < 0:
+            self._ck(rc)
+        return rc
+
+    def rollout_decode_closed(self, key_frames, warm_up, payload, table):
+        """tz_rollout_decode_closed: the decoder of a closed-loop stream.  key_frames as for rollout_decode; payload None: the
+        pieces staged with payload_begin / payload_put.  The decoded frames stay in the context (decoded_get); returns the
+        key mask."""
+        if key_frames is None:
+            nt, h, w = self._staged
+        else:
+            self._check_stack(key_frames, "key_frames")
+            nt, h, w = key_frames.shape[:3]
+        n = nt * h * w * 3
+        if payload is not None and _numel(payload) != n:
+            raise ValueError("payload holds %d elements, expected %d" % (_numel(payload), n))
+        tl = -1 if table is None else len(table)
+        tb = None if table is None else np.ascontiguousarray(table, np.int16)
+        key = np.zeros(nt, np.uint8)
+        self._ck(self.lib.tz_rollout_decode_closed(self.h, None if key_frames is None else _ptr(key_frames, np.uint8), nt, h, w, warm_up,
+                                                   None if payload is None else _ptr(payload), n, _ptr(tb), tl, key.ctypes.data))
         self._shape = (nt, h, w)
         return key.astype(bool)
 

@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, boundmap, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
+from . import _lib, boundmap, closedloop, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -467,15 +467,17 @@ def _key_output(ctx, out_dir, nt, H, W, key, pool, stages=None, verbose=False, k
 
 
 def _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages=None, coder="zstd", verbose=False, channels=3, strided=False,
-                    plane=False):
+                    plane=False, closed=False):
     """entropy.dat (compress.py:375-400) from the context-resident payload, piece by piece -> its size.  channels, strided,
-    plane: as _stream_outputs'."""
+    plane, closed: as _stream_outputs'."""
     n = nt * H * W * channels
     if table is not None:
         tail = np.concatenate([table.astype(np.int64), [len(table)]])
     else:
         tail = np.array([-1], dtype=np.int64)
     one = sdelta.mark(shuffled, plane) if strided or plane else (SHUFFLE_MARK if shuffled else 1)
+    if closed:
+        one += closedloop.MARK_CLOSED
     trailer = np.concatenate([tail, [one, nt, H, W, channels], [warm_up]]).astype(np.int16)
     t_e = time.perf_counter()
     if coder in ("huff", "huffr", "huffd"):
@@ -498,14 +500,14 @@ def _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages=Non
 
 
 def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool, stages=None, coder="zstd", verbose=False,
-                    key_coder="zstd", channels=3, strided=False, plane=False):
+                    key_coder="zstd", channels=3, strided=False, plane=False, closed=False):
     """key_frame.dat and entropy.dat (compress.py:271-278, 375-400) from the context-resident frames
     and payload, piece by piece: nothing of size nt*H*W lives on the host.  channels: what the resident payload stores per
     pixel (1: a gray job, tezip_amd/graypayload.py); key_frame.dat has three either way.  strided: the payload's spatial delta
     ran at the channel stride, plane: it is the 2-D one, TZ-SD2 (tezip_amd/sdelta.py): the trailer says so in the first entry of
-    its shape."""
+    its shape.  closed: the job ran closed-loop prediction TZ-CL1 (tezip_amd/closedloop.py): that entry is 16 larger."""
     kf = _key_output(ctx, out_dir, nt, H, W, key, pool, stages, verbose, key_coder)
-    esize = _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages, coder, verbose, channels, strided, plane)
+    esize = _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages, coder, verbose, channels, strided, plane, closed)
     return kf.result(), esize
 
 
@@ -562,7 +564,8 @@ def check_ratio(ratio, mode, bound, target_psnr, coder, shuffle, sharded):
 
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
-        SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None, QUANT="greedy", BOUND_MAP=None):
+        SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None, QUANT="greedy", BOUND_MAP=None,
+        LOOP="open"):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -638,6 +641,15 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     violation is one ERROR line per frame and exit status 3.  Works with every QUANT, CODER, KEY_CODER, SHUFFLE, GRAY, SDELTA,
     REPORT, SSIM and DIGESTS.  Single-GPU jobs only.
 
+    LOOP (--loop; NOT in the reference): "open" (the default: every file, line and launch is what it is without it) feeds the
+    predictor its own last prediction inside a window (compress.py:230); "closed" feeds it the DECODED frame in front, definition
+    TZ-CL1 (tezip_amd/closedloop.py): the rollout is tz_rollout_closed under the job's mode, bound and quantiser, every prediction
+    is a one-step prediction, and the unchanged back half stores the loop's quantised deltas.  One line says so, tezip_amd.json
+    records it, and the first entry of the trailer's shape is 16 larger; `-u` recognises the stream by that mark.  WINDOW_SIZE
+    only (no THRESHOLD), MODE "abs", lossless or with QUANT "lattice"; not with GRAY, TARGET_PSNR, TARGET_RATIO, PER_FRAME,
+    FRAME_BOUNDS or BOUND_MAP (a target's probes assume predictions that do not depend on the bound).  Works with every SDELTA,
+    CODER, KEY_CODER, SHUFFLE, REPORT, SSIM and DIGESTS.  VERBOSE prints no per-step MSE lines.  Single-GPU jobs only.
+
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
     does not grow with the number of frames.  Under torch.distributed.run the windows are sharded
@@ -670,6 +682,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    problem = closedloop.check_flags(LOOP, MODE, BOUND_VALUE, QUANT, THRESHOLD, False, tzdist.active() is not None, GRAY, TARGET_PSNR,
+                                     TARGET_RATIO, PER_FRAME, FRAME_BOUNDS, BOUND_MAP)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
+    closed = LOOP == "closed"
     if TARGET_PSNR is not None:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         problem = (target.check_target(TARGET_PSNR) or (TARGET_NEEDS_ABS if MODE != "abs" or BOUND_VALUE else None)
                    or (TARGET_NOT_SHARDED if tzdist.active() is not None else None))
@@ -754,9 +772,13 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
-            key, mse = ctx.rollout(None, PREPROCESS, WINDOW_SIZE, THRESHOLD, want_mse=bool(VERBOSE))
+            if closed:   # TZ-CL1: the decoded frame is fed back, under the job's own bound and quantiser (no window MSE exists)
+                print(closedloop.STDOUT_LINE)
+                key = ctx.rollout_closed(None, PREPROCESS, WINDOW_SIZE, MODE, BOUND_VALUE)
+            else:
+                key, mse = ctx.rollout(None, PREPROCESS, WINDOW_SIZE, THRESHOLD, want_mse=bool(VERBOSE))
             if VERBOSE:
-                for i in range(PREPROCESS + 1, nt):
+                for i in range(PREPROCESS + 1, nt) if not closed else ():
                     print("MSE:", mse[i])
                     if key[i] and i > PREPROCESS:
                         print("move key point")
@@ -851,8 +873,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                                 verbose=VERBOSE, channels=channels, strided=strided, plane=plane)
             else:
                 _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
-                                coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided, plane=plane)
-            if bound_map is not None:
+                                coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided, plane=plane,
+                                **({"closed": True} if closed else {}))
+            if closed:
+                doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
+                                    payload_channels=channels, sdelta=sd_mode, quant=QUANT, loop="closed")
+            elif bound_map is not None:
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
                                     payload_channels=channels, sdelta=sd_mode, quant=QUANT, bound_map=boundmap.stats(bound_map))
             elif QUANT == "lattice":

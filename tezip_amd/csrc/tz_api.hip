@@ -684,6 +684,7 @@ constexpr int kMaxFrames = 32767;
 
 static void set_rollout(tz_ctx* ctx, tz_ctx::tz_rollout_kind kind, int pred_first, int pred_end) {
     ctx->rollout_kind = kind;
+    ctx->loop_closed = 0;   // (tz_rollout_closed stamps its loop behind this)
     ctx->pred_first = pred_first;
     ctx->pred_end = pred_end;
 }
@@ -1540,6 +1541,28 @@ static int encode_check(tz_ctx* ctx, const char* who, int mode) {
     return TZ_OK;
 }
 
+// TZ-CL1: the predictions of a closed loop (tz_rollout_closed) depend on what its job decodes to, so they serve that job alone:
+// the loop's mode, bound and quantiser, one bound for every sample and the three-channel payload.
+static int loop_check(tz_ctx* ctx, const char* who, int mode, double b0, double b1) {
+    if (!ctx->loop_closed) return TZ_OK;
+    const bool same = mode == ctx->loop_mode && b0 == ctx->loop_b0 && (mode != TZ_MODE_ABSREL || b1 == ctx->loop_b1) &&
+                      ctx->quantiser == ctx->loop_quantiser;
+    if (same && ctx->frame_bounds.empty() && !ctx->map_h && ctx->payload_channels == 3) return TZ_OK;
+    return tz_fail(ctx, TZ_ERR_STATE,
+                   "%s: the resident predictions are those of a closed loop (tz_rollout_closed) run with mode %d, bound %.17g (%.17g) and "
+                   "quantiser %d; they serve that job alone, not mode %d, bound %.17g (%.17g), quantiser %d%s%s%s",
+                   who, ctx->loop_mode, ctx->loop_b0, ctx->loop_b1, ctx->loop_quantiser, mode, b0, b1, ctx->quantiser,
+                   ctx->frame_bounds.empty() ? "" : ", frame bounds (tz_set_frame_bounds)", ctx->map_h ? ", a bound map (tz_set_bound_map)" : "",
+                   ctx->payload_channels == 3 ? "" : ", a one-channel payload (tz_set_payload_channels)");
+}
+
+// encode_check with the bound: what tz_encode and the probes check (the loop's rule comes first: it concerns the setters, whose own
+// refusals would otherwise hide it; tz_encode_begin, tz_encode_delta and tz_size_probe call loop_check ahead of their layout checks)
+static int encode_check(tz_ctx* ctx, const char* who, int mode, double b0, double b1) {
+    TZ_TRY(loop_check(ctx, who, mode, b0, b1));
+    return encode_check(ctx, who, mode);
+}
+
 // ---- one abs bound per frame (include/tezip_hip.h: tz_set_frame_bounds)
 extern "C" int tz_set_frame_bounds(tz_ctx* ctx, const double* bounds, int n) {
     if (!ctx) return TZ_ERR_INVALID;
@@ -1844,7 +1867,7 @@ extern "C" int tz_encode(tz_ctx* ctx, int mode, double b0, double b1, int entrop
                          int* table_len, int16_t* delta_out) {
     tz_roctx_range roctx_("tz_encode");
     if (!ctx || !table_len || ((entropy & 1) && !table)) return TZ_ERR_INVALID;
-    TZ_TRY(encode_check(ctx, "tz_encode", mode));
+    TZ_TRY(encode_check(ctx, "tz_encode", mode, b0, b1));
     const tz_layout layout = layout_of(ctx);
     if (layout.channels == 1) {
         if (delta_out) return tz_fail(ctx, TZ_ERR_INVALID, "tz_encode: no delta_out with a one-channel payload");
@@ -1923,6 +1946,7 @@ extern "C" int tz_encode_begin(tz_ctx* ctx, int mode, double b0, double b1, int 
                                int16_t* edge) {
     tz_roctx_range roctx_("tz_encode_begin");
     if (!ctx || !edge || (entropy && !hist)) return TZ_ERR_INVALID;
+    TZ_TRY(loop_check(ctx, "tz_encode_begin", mode, b0, b1));
     TZ_TRY(flat_only(ctx, "tz_encode_begin"));
     TZ_TRY(no_frame_bounds(ctx, "tz_encode_begin"));
     TZ_TRY(no_bound_map(ctx, "tz_encode_begin"));
@@ -2001,6 +2025,7 @@ extern "C" int tz_byte_unshuffle(tz_ctx* ctx, const uint8_t* in, size_t n, int16
 
 extern "C" int tz_encode_delta(tz_ctx* ctx, int mode, double b0, double b1, int16_t* delta_out) {
     if (!ctx || !delta_out) return TZ_ERR_INVALID;
+    TZ_TRY(loop_check(ctx, "tz_encode_delta", mode, b0, b1));
     TZ_TRY(flat_only(ctx, "tz_encode_delta", false, true));
     TZ_TRY(encode_check(ctx, "tz_encode_delta", mode));
     const size_t N = (size_t)ctx->nt * ctx->H * ctx->W * 3;
@@ -2144,6 +2169,190 @@ extern "C" int tz_decode_range(tz_ctx* ctx, const int16_t* payload, size_t paylo
     return decode_frames(ctx, "tz_decode_range", payload, payload_len, table, table_len, first, count, frames_out);
 }
 
+// ---- closed-loop prediction, definition TZ-CL1 (include/tezip_hip.h: tz_rollout_closed; slow statement in
+// tezip_amd/closedloop.py).  The steps of a closed loop: step s holds the frames k + s of every key interval [k, next key) that
+// still has one, so that step s reads what step s - 1 decoded (or the key frame itself).  key: the key mask of the sequence
+// (frame 0 is a key frame).  Every frame of a step is an item "predict from the u8 frame in front" of run_schedule.
+static std::vector<std::vector<int>> closed_steps(const std::vector<uint8_t>& key) {
+    std::vector<std::vector<int>> steps;
+    for (int t = 0, s = 0; t < (int)key.size(); ++t) {
+        s = key[t] ? 0 : s + 1;
+        if (!s) continue;
+        if ((int)steps.size() < s) steps.resize(s);
+        steps[s - 1].push_back(t);
+    }
+    return steps;
+}
+
+// one schedule over the frames `list`, each predicted from frame - 1 of the u8 stack `src`
+static int closed_predict(tz_ctx* ctx, const std::vector<int>& list, const uint8_t* src) {
+    std::vector<PredItem> items;
+    for (int t : list) items.push_back(PredItem{t, 1, t - 1, 1});
+    return run_schedule(ctx, items, src);
+}
+
+// the steps' frame lists, one after the other, on the device
+static int closed_lists(tz_call& call, const std::vector<std::vector<int>>& steps, const int** d_lists) {
+    std::vector<int> all;
+    for (const auto& st : steps) all.insert(all.end(), st.begin(), st.end());
+    int* d = nullptr;
+    TZ_TRY(call.alloc(std::max<size_t>(all.size(), 1) * sizeof(int), &d));
+    if (!all.empty()) TZ_TRY(tz_upload(call.ctx, d, all.data(), all.size() * sizeof(int)));
+    *d_lists = d;
+    return TZ_OK;
+}
+
+extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, int mode, double b0,
+                                 double b1, uint8_t* key_mask) {
+    tz_roctx_range roctx_("tz_rollout_closed");
+    if (!ctx) return TZ_ERR_INVALID;
+    ctx->enc_kind = tz_ctx::ENC_NONE;
+    if (window < 0) return tz_fail(ctx, TZ_ERR_INVALID, "window must be >= 0");
+    if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
+    if (std::isnan(b0) || (mode == TZ_MODE_ABSREL && std::isnan(b1)))
+        return tz_fail(ctx, TZ_ERR_INVALID, "error bound is NaN (the reference raises on a NaN tolerance)");
+    if (window == 0)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: the closed loop serves fixed windows (window > 0), not the threshold rule");
+    if (nt < warm_up + 2)
+        return tz_fail(ctx, TZ_ERR_INVALID, "need at least warm_up+2 frames (nt=%d, warm_up=%d)", nt, warm_up);
+    // what the loop feeds back: the original where the job's quantiser leaves every delta as it is, else TZ-QL1 under one abs bound
+    const bool lossless = b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0) ||
+                          (ctx->quantiser == 1 ? tz_lattice_is_identity(mode, b0, b1) : tz_quant_is_identity(mode, b0, b1));
+    if (!lossless && ctx->quantiser != 1)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: a lossy closed loop needs the lattice quantiser (tz_set_quantiser(1)): the greedy walk is no function of one sample");
+    if (!lossless && mode != TZ_MODE_ABS)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: a lossy closed loop takes mode abs, not %d: rel bounds depend on whole frames", mode);
+    if (ctx->payload_channels != 3 || !ctx->frame_bounds.empty() || ctx->map_h)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: the closed loop takes one bound and a three-channel payload (no tz_set_payload_channels(1), tz_set_frame_bounds or tz_set_bound_map)");
+    const int p = warm_up;
+    tz_call call(ctx);
+    TZ_TRY(rollout_setup(ctx, frames, nt, H, W, warm_up));   // (the whole stack goes up ahead: every frame is read by a step)
+    // key mask and groups of the open-loop SWP job (rollout_swp; compress.py:188-220, 249-262)
+    std::vector<uint8_t> key(nt, 0), gfirst(nt, 0), qskip(nt, 0);
+    std::vector<int> c0_slots;
+    for (int i = 0; i < p; ++i) {
+        key[i] = 1;
+        qskip[i] = 1;
+        c0_slots.push_back(i);
+    }
+    gfirst[0] = 1;
+    if (p > 0) gfirst[p] = 1;
+    c0_slots.push_back(p > 0 ? p : 0);
+    key[p] = 1;   // (nt >= p + 2: frame p + 1 starts from frame p)
+    for (int idx = p + 1; idx < nt; ++idx)
+        if ((idx - p) % window == 0) {
+            gfirst[idx] = 1;
+            key[idx] = 1;   // the frame the next window starts from, or the last frame (compress.py:260-262)
+            c0_slots.push_back(idx);
+        }
+    for (int i = 0; i < nt; ++i)
+        if (gfirst[i]) qskip[i] = 1;
+    int rc = fill_c0(ctx, c0_slots);
+    const std::vector<std::vector<int>> steps = closed_steps(key);
+    if (rc == TZ_OK && lossless) {   // the decoded frame is the original: every prediction is independent of every other
+        std::vector<int> all;
+        for (const auto& st : steps) all.insert(all.end(), st.begin(), st.end());
+        rc = closed_predict(ctx, all, ctx->d_frames);
+    } else if (rc == TZ_OK) {
+        const size_t fb = (size_t)nt * H * W * 3;
+        const int E = fabs(b0) >= 255.0 ? 255 : (int)fabs(b0);
+        uint8_t* d_dec = nullptr;
+        const int* d_lists = nullptr;
+        rc = call.alloc(fb, &d_dec);
+        if (rc == TZ_OK) rc = closed_lists(call, steps, &d_lists);
+        if (rc == TZ_OK && hipMemcpyAsync(d_dec, ctx->d_frames, fb, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)   // the key frames
+            rc = tz_fail(ctx, TZ_ERR_HIP, "tz_rollout_closed: copy of the frame stack failed");
+        size_t at = 0;
+        for (size_t s = 0; s < steps.size() && rc == TZ_OK; at += steps[s].size(), ++s) {
+            rc = closed_predict(ctx, steps[s], d_dec);
+            if (rc == TZ_OK)
+                rc = tzk_cl_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp, E);
+        }
+    }
+    if (rc == TZ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "closed-loop rollout failed");
+    if (rc != TZ_OK) {  // nothing of a failed rollout may still read the caller's frames when we return
+        (void)hipStreamSynchronize(ctx->copy_stream);
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    ctx->key_mask = key;
+    ctx->group_first = gfirst;
+    ctx->quant_skip = qskip;
+    set_rollout(ctx, tz_ctx::ROLLOUT_ENCODE, 0, nt);
+    ctx->pred_contract = tz_get_contract(ctx);
+    ctx->loop_closed = 1;
+    ctx->loop_mode = mode;
+    ctx->loop_b0 = b0;
+    ctx->loop_b1 = b1;
+    ctx->loop_quantiser = ctx->quantiser;
+    if (key_mask) memcpy(key_mask, key.data(), nt);
+    return TZ_OK;
+}
+
+extern "C" int tz_rollout_loop(tz_ctx* ctx) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (ctx->rollout_kind == tz_ctx::ROLLOUT_NONE) return tz_fail(ctx, TZ_ERR_STATE, "no rollout in this context");
+    return ctx->loop_closed;
+}
+
+extern "C" int tz_rollout_decode_closed(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, const int16_t* payload,
+                                        size_t payload_len, const int16_t* table, int table_len, uint8_t* key_mask) {
+    tz_roctx_range roctx_("tz_rollout_decode_closed");
+    if (!ctx) return TZ_ERR_INVALID;
+    if (ctx->payload_channels != 3)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_decode_closed does not serve a one-channel payload (tz_set_payload_channels(1))");
+    TZ_TRY(check_table(ctx, table, table_len));
+    ctx->have_decoded = false;
+    tz_call call(ctx);
+    TZ_TRY(rollout_setup(ctx, key_frames, nt, H, W, warm_up));
+    ctx->enc_kind = tz_ctx::ENC_NONE;
+    const size_t fe = (size_t)H * W * 3, N = (size_t)nt * fe;
+    if (!payload) TZ_TRY(staged_payload(ctx, N, &payload));   // (a rollout leaves the staged payload alone)
+    if (payload_len != N)
+        return tz_fail(ctx, TZ_ERR_INVALID, "payload holds %zu elements, the key-frame stack implies %zu", payload_len, N);
+    std::vector<int> flags(nt, 0);
+    TZ_TRY(discover_keys(ctx, nt, H, W, &flags));
+    std::vector<uint8_t> key(nt);
+    for (int i = 0; i < nt; ++i) key[i] = flags[i] ? 1 : 0;
+    for (int i = 0; i <= warm_up; ++i)   // decompress.py:138-179: frames 0 .. warm_up are key frames
+        if (i >= nt || !key[i]) return tz_fail(ctx, TZ_ERR_INVALID, "key frames do not cover the sequence (frame %d)", i);
+    // q: the quantised delta stack, by the layout's inverse remap and inverse spatial delta -- no prediction is needed for it
+    const tz_layout layout = layout_of(ctx);
+    const int16_t* d_pay;
+    int16_t* d_q;
+    const int* d_lists = nullptr;
+    TZ_TRY(call.in(payload, N * 2, &d_pay));
+    TZ_TRY(call.alloc(N * 2, &d_q));
+    std::vector<int16_t> lut;
+    if (table_len >= 0) build_dec_lut(table, table_len, 1, &lut);
+    const int16_t* h_lut = table_len >= 0 ? lut.data() : nullptr;
+    if (layout.plane_h) TZ_TRY(tzk_unplane(ctx, d_pay, nt, H, W, 3, h_lut, 1, d_q));
+    else TZ_TRY(tzk_undelta(ctx, layout.stride, d_pay, N, nullptr, h_lut, 1, d_q));
+    // the decoded stack starts as the key stack: key frames are stored exactly, every other frame is written by its step
+    TZ_TRY(tz_ensure(ctx, (void**)&ctx->d_out, &ctx->cap_out, N));
+    TZ_HIP(ctx, hipMemcpyAsync(ctx->d_out, ctx->d_frames, N, hipMemcpyDeviceToDevice, ctx->stream));
+    std::vector<int> c0_slots;
+    for (int i = 0; i < nt; ++i)
+        if (key[i]) c0_slots.push_back(i);   // (a key slot is never read for reconstruction)
+    TZ_TRY(fill_c0(ctx, c0_slots));
+    const std::vector<std::vector<int>> steps = closed_steps(key);
+    TZ_TRY(closed_lists(call, steps, &d_lists));
+    size_t at = 0;
+    for (size_t s = 0; s < steps.size(); at += steps[s].size(), ++s) {
+        TZ_TRY(closed_predict(ctx, steps[s], ctx->d_out));
+        TZ_TRY(tzk_cl_recon(ctx, ctx->d_pred, d_q, ctx->d_out, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp));
+    }
+    TZ_TRY(tz_stream_sync(ctx));
+    ctx->key_mask = recon_key_mask(key.data(), nt, warm_up);
+    set_rollout(ctx, tz_ctx::ROLLOUT_DECODE, 0, nt);
+    ctx->pred_contract = tz_get_contract(ctx);
+    ctx->have_decoded = true;
+    ctx->dec_first = 0;
+    ctx->dec_count = nt;
+    if (key_mask) memcpy(key_mask, key.data(), nt);
+    return TZ_OK;
+}
+
 // What the stored payload of an encode decodes to (include/tezip_hip.h: tz_encode_quality, tz_encode_digests): the decoder's
 // tail over the payload on the ENCODER's predictions and frames -- the reconstruct reads frames only where the mask says
 // "key", and there the encoder's originals are the bytes key_frame.dat stores -- into pool scratch (*d_dec, nt*H*W*3
@@ -2251,7 +2460,7 @@ extern "C" int tz_map_check(tz_ctx* ctx, const uint8_t* orig, const uint8_t* dec
 extern "C" int tz_bound_probe(tz_ctx* ctx, int mode, double b0, double b1, tz_frame_quality* out) {
     tz_roctx_range roctx_("tz_bound_probe");
     if (!ctx || !out) return TZ_ERR_INVALID;
-    TZ_TRY(encode_check(ctx, "tz_bound_probe", mode));
+    TZ_TRY(encode_check(ctx, "tz_bound_probe", mode, b0, b1));
     const int channels = layout_of(ctx).channels;
     if (channels == 1) {
         tz_call gray_check(ctx);   // (a scope of its own: the probe reuses its blocks)
@@ -3323,9 +3532,10 @@ extern "C" int tz_size_probe(tz_ctx* ctx, int mode, double b0, double b1, int en
     if (!ctx || !out) return TZ_ERR_INVALID;
     if (coder < 0 || coder > 2) return tz_fail(ctx, TZ_ERR_INVALID, "tz_size_probe: coder %d, 0 (huff), 1 (huffr) or 2 (huffd) wanted", coder);
     if (entropy & ~1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_size_probe: byte planes are not Huffman-coded");
+    TZ_TRY(loop_check(ctx, "tz_size_probe", mode, b0, b1));
     TZ_TRY(no_plane(ctx, "tz_size_probe"));
     TZ_TRY(no_bound_map(ctx, "tz_size_probe"));
-    TZ_TRY(encode_check(ctx, "tz_size_probe", mode));
+    TZ_TRY(encode_check(ctx, "tz_size_probe", mode, b0, b1));
     const tz_layout layout = layout_of(ctx);
     if (layout.channels == 1) {
         tz_call gray_check(ctx);   // (a scope of its own: the probe reuses its blocks)
@@ -3356,7 +3566,7 @@ extern "C" int tz_sdelta_probe(tz_ctx* ctx, int mode, double b0, double b1, int 
     if (!ctx || !out) return TZ_ERR_INVALID;
     if (coder < 0 || coder > 2) return tz_fail(ctx, TZ_ERR_INVALID, "tz_sdelta_probe: coder %d, 0 (huff), 1 (huffr) or 2 (huffd) wanted", coder);
     if (entropy & ~1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_sdelta_probe: byte planes are not Huffman-coded");
-    TZ_TRY(encode_check(ctx, "tz_sdelta_probe", mode));
+    TZ_TRY(encode_check(ctx, "tz_sdelta_probe", mode, b0, b1));
     const int channels = ctx->payload_channels;
     if (channels == 1) {
         tz_call gray_check(ctx);   // (a scope of its own: the probe reuses its blocks)

@@ -5657,3 +5657,140 @@ int tzk_key_unresid(tz_ctx* ctx, const int16_t* d_sym, int H, int W, const int* 
     TZ_HIP(ctx, hipGetLastError());
     return TZ_OK;
 }
+
+// ------------------------------------------------------------------------ closed-loop prediction (TZ-CL1)
+// tz_rollout_closed / tz_rollout_decode_closed (include/tezip_hip.h; slow statement in
+// tezip_amd/closedloop.py): between two predictor steps the frames the step predicted are DECODED, and the decoded bytes are what
+// the next step is fed.  Per sample, with x = (int)(pred * 255.0f) the truncated prediction (compress.py:307,311) cropped to H x W:
+//   k_cl_step  (encoder)  d = x - orig, q = TZ-QL1(d, E) as lat_apply forms it for a uniform abs tolerance, dec = clamp(x - q, 0, 255)
+//   k_cl_recon (decoder)  dec = clamp(x - q, 0, 255) with q read from the int16 stack the payload decodes to (k_recon's arithmetic)
+// blockIdx.y walks `list`, the sequence indices of the step's frames; pred is the padded stack (pitch Wp * 3), orig / q / dec the
+// unpadded ones.  A lane makes 16 samples: one 16-byte load of orig (two of q), one 16-byte store of dec, and the 16 predictions
+// as four 16-byte loads where the frame is unpadded (FLAT) or one by one across the crop.  vec == 0 (a stack off the 16-byte
+// boundary): every sample goes one by one; else the `head` samples in front of the frame's first 16-byte boundary and the tail
+// behind the last whole group do.
+__device__ __forceinline__ unsigned cl_sample(float p, int o, int E) {
+    const int x = (int)(p * 255.0f), d = x - o;
+    const unsigned ad = (unsigned)(d < 0 ? -d : d), s = 2u * (unsigned)E + 1u;
+    const int m = (int)min((ad + (unsigned)E) / s * s, 255u);
+    const int q = E ? (d < 0 ? -m : m) : d;
+    const int v = x - q;
+    return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+__device__ __forceinline__ unsigned cl_recon_sample(float p, int q) {
+    const int v = (int)(p * 255.0f) - q;
+    return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// the prediction of sample r of an unpadded frame (row = W * 3 samples a row, pitch = Wp * 3)
+__device__ __forceinline__ float cl_pred(const float* __restrict__ pf, size_t r, unsigned row, unsigned pitch) {
+    const size_t y = r / row;
+    return pf[y * pitch + (r - y * row)];
+}
+
+template <bool RECON, bool FLAT>
+__device__ __forceinline__ void cl_frames(const float* __restrict__ pred, const uint8_t* __restrict__ orig, const int16_t* __restrict__ qs,
+                                          uint8_t* __restrict__ dec, const int* __restrict__ list, int H, int W, int Hp, int Wp, int E, int vec) {
+    const size_t f = (size_t)list[blockIdx.y];
+    const unsigned row = (unsigned)W * 3u, pitch = (unsigned)Wp * 3u;
+    const size_t fe = (size_t)H * row, base = f * fe;
+    const float* pf = pred + f * (size_t)Hp * pitch;
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    size_t head = vec ? min(fe, (size_t)((16u - (unsigned)(base & 15)) & 15u)) : fe;
+    const size_t n16 = (fe - head) / 16;
+    for (size_t g = t0; g < n16; g += stride) {
+        const size_t r0 = head + 16 * g;
+        float p[16];
+        if (FLAT) {   // (an unpadded frame is whole groups of 64 samples: head == 0 and r0 is a multiple of 16)
+            const float4* p4 = (const float4*)(pf + r0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4 v = p4[j];
+                p[4 * j] = v.x; p[4 * j + 1] = v.y; p[4 * j + 2] = v.z; p[4 * j + 3] = v.w;
+            }
+        } else {
+            size_t y = r0 / row;
+            unsigned xc = (unsigned)(r0 - y * row);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                p[j] = pf[y * pitch + xc];
+                if (++xc == row) {
+                    xc = 0;
+                    ++y;
+                }
+            }
+        }
+        unsigned b[16];
+        if (RECON) {
+            const uint4* q4 = (const uint4*)(qs + base + r0);
+            const uint4 a = q4[0], c = q4[1];
+            const unsigned w[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                b[2 * j] = cl_recon_sample(p[2 * j], (int)(short)(w[j] & 0xFFFFu));
+                b[2 * j + 1] = cl_recon_sample(p[2 * j + 1], (int)w[j] >> 16);
+            }
+        } else {
+            const uint4 o = *(const uint4*)(orig + base + r0);
+            const unsigned w[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+            for (int j = 0; j < 16; ++j) b[j] = cl_sample(p[j], (int)((w[j >> 2] >> (8 * (j & 3))) & 0xFFu), E);
+        }
+        uint4 out;
+        out.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        out.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+        out.z = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+        out.w = b[12] | (b[13] << 8) | (b[14] << 16) | (b[15] << 24);
+        *(uint4*)(dec + base + r0) = out;
+    }
+    const size_t v_end = head + 16 * n16, nscalar = head + (fe - v_end);
+    for (size_t j = t0; j < nscalar; j += stride) {
+        const size_t r = j < head ? j : v_end + (j - head);
+        const float p = cl_pred(pf, r, row, pitch);
+        dec[base + r] = (uint8_t)(RECON ? cl_recon_sample(p, (int)qs[base + r]) : cl_sample(p, (int)orig[base + r], E));
+    }
+}
+
+template <bool FLAT>
+__global__ __launch_bounds__(256) void k_cl_step(const float* __restrict__ pred, const uint8_t* __restrict__ orig, uint8_t* __restrict__ dec,
+                                                 const int* __restrict__ list, int H, int W, int Hp, int Wp, int E, int vec) {
+    cl_frames<false, FLAT>(pred, orig, nullptr, dec, list, H, W, Hp, Wp, E, vec);
+}
+
+template <bool FLAT>
+__global__ __launch_bounds__(256) void k_cl_recon(const float* __restrict__ pred, const int16_t* __restrict__ qs, uint8_t* __restrict__ dec,
+                                                  const int* __restrict__ list, int H, int W, int Hp, int Wp, int vec) {
+    cl_frames<true, FLAT>(pred, nullptr, qs, dec, list, H, W, Hp, Wp, 0, vec);
+}
+
+// d_list: nlist sequence indices (device); every stack is the whole sequence's.  orig (step) or q (recon) is NULL for the other form.
+static int cl_launch(tz_ctx* ctx, const float* pred, const uint8_t* orig, const int16_t* q, uint8_t* dec, const int* d_list, int nlist,
+                     int H, int W, int Hp, int Wp, int E) {
+    if (nlist <= 0) return TZ_OK;
+    const bool recon = q != nullptr;
+    const size_t fe = (size_t)H * W * 3;
+    const int vec = ((((uintptr_t)dec | (uintptr_t)(recon ? (const void*)q : (const void*)orig) | (uintptr_t)pred) & 15) == 0) ? 1 : 0;
+    const bool flat = vec && H == Hp && W == Wp;
+    const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>((fe / 16 + 255) / 256, 64));   // (times nlist frames)
+    const dim3 grid(gx, (unsigned)nlist);
+    tz_prof_scope ps(ctx, recon ? TZP_RECON : TZP_QUANT);
+    if (recon) {
+        if (flat) hipLaunchKernelGGL(k_cl_recon<true>, grid, dim3(256), 0, ctx->stream, pred, q, dec, d_list, H, W, Hp, Wp, vec);
+        else hipLaunchKernelGGL(k_cl_recon<false>, grid, dim3(256), 0, ctx->stream, pred, q, dec, d_list, H, W, Hp, Wp, vec);
+    } else {
+        if (flat) hipLaunchKernelGGL(k_cl_step<true>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, d_list, H, W, Hp, Wp, E, vec);
+        else hipLaunchKernelGGL(k_cl_step<false>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, d_list, H, W, Hp, Wp, E, vec);
+    }
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+int tzk_cl_step(tz_ctx* ctx, const float* pred, const uint8_t* orig, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp,
+                int E) {
+    return cl_launch(ctx, pred, orig, nullptr, dec, d_list, nlist, H, W, Hp, Wp, E);
+}
+
+int tzk_cl_recon(tz_ctx* ctx, const float* pred, const int16_t* q, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp) {
+    return cl_launch(ctx, pred, nullptr, q, dec, d_list, nlist, H, W, Hp, Wp, 0);
+}

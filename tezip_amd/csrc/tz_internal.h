@@ -84,6 +84,11 @@ struct tz_ctx {
     int pred_first = 0, pred_end = 0;
     int pred_contract = 0;            // the arithmetic contract that produced the resident prediction stack (stamped by
                                       // tz_rollout / tz_rollout_decode*; tz_encode* / tz_decode* refuse a flip in between)
+    // tz_rollout_closed (TZ-CL1): the resident predictions are those of a closed loop that fed back what (mode, b0, b1, quantiser)
+    // decodes to -- the only job whose quantised deltas they serve (every rollout clears the stamp, tz_rollout_closed sets it)
+    int loop_closed = 0;
+    int loop_mode = 0, loop_quantiser = 0;
+    double loop_b0 = 0.0, loop_b1 = 0.0;
     // pinned staging ring for small host->device uploads (index arrays, masks, LUTs): the copy
     // out of it is truly asynchronous and the memory outlives the caller's locals
     uint8_t* ring = nullptr;
@@ -486,6 +491,12 @@ int tzk_key_resid(tz_ctx*, const uint8_t* d_frames, int H, int W, const int* d_i
                   int nkeys, int16_t* d_sym);
 int tzk_key_unresid(tz_ctx*, const int16_t* d_sym, int H, int W, const int* d_idx, const uint8_t* d_pred, const unsigned long long* d_off,
                     int nkeys, uint8_t* d_tmp, uint8_t* d_frames);
+// closed-loop prediction TZ-CL1: the frames d_list[0 .. nlist) (device, sequence indices) of the padded prediction stack pred and of
+// the unpadded whole-sequence stacks.  tzk_cl_step: dec = clamp(x - TZ-QL1(x - orig, E), 0, 255), x the truncated prediction
+// (E = 0: dec = the clamped original's own value, x - (x - orig)); tzk_cl_recon: dec = clamp(x - q, 0, 255).
+int tzk_cl_step(tz_ctx*, const float* pred, const uint8_t* orig, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp,
+                int E);
+int tzk_cl_recon(tz_ctx*, const float* pred, const int16_t* q, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,
             double* h_sse);
 int tzk_sse_blocks(int Hp, int Wp);

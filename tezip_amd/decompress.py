@@ -9,7 +9,7 @@ import time
 
 import numpy as np
 
-from . import _lib, digest, huff, huffd, huffr, keycoder, keycoderg, sidecar, zstd
+from . import _lib, closedloop, digest, huff, huffd, huffr, keycoder, keycoderg, sidecar, zstd
 from . import dist as tzdist
 from . import sdelta
 from .compress import SHUFFLE_MARK, make_context, open_model
@@ -41,7 +41,11 @@ def check_stream(shape, warm_up, payload_len, key_len):
     # one: 1 in the reference, SHUFFLE_MARK for byte planes; sdelta.MARK / MARK_SHUFFLE (4 / 5) say the same of a payload whose
     # spatial delta ran at the channel stride (--sdelta channel, tezip_amd/sdelta.py), which has three channels;
     # sdelta.MARK_PLANE / MARK_PLANE_SHUFFLE (8 / 9) of a payload under the 2-D spatial delta TZ-SD2 (--sdelta plane), which has
-    # three channels or one.  3, 6 and 7 mean nothing
+    # three channels or one.  3, 6 and 7 mean nothing.  Each of the six plus 16 (17, 18, 20, 21, 24, 25): the same layout of a
+    # closed-loop job (--loop closed, tezip_amd/closedloop.py), which has three channels
+    if closedloop.is_closed(one) and C != 3:
+        raise ValueError("entropy.dat: a closed-loop stream (mark %d) has a three-channel payload, the trailer says %d" % (one, C))
+    one = closedloop.open_mark(one)
     if (one not in (1, SHUFFLE_MARK) + sdelta.MARKS + sdelta.PLANE_MARKS or C not in (1, 3) or (one in sdelta.MARKS and C != 3)
             or nt < 1 or H < 1 or W < 1):
         raise ValueError("entropy.dat: unsupported stack shape %r (expected (1, nt, H, W, 3), (1, nt, H, W, 1) for a gray job, "
@@ -75,6 +79,24 @@ def check_sdelta(data_dir, one):
     if want is not None and want != have:
         raise ValueError("tezip_amd.json describes the payload's spatial delta as %s, entropy.dat's trailer as %s" % (want, have))
     return sdelta.MODES.index(have)
+
+
+def check_loop(data_dir, one):
+    """The prediction loop that entropy.dat's trailer states (the open-loop mark plus 16: closed, TZ-CL1) against tezip_amd.json,
+    which records "closed" and says nothing for open.  The trailer is authoritative; a sidecar that contradicts it belongs to
+    another stream.  Returns whether the stream is a closed-loop one."""
+    have = "closed" if closedloop.is_closed(one) else "open"
+    want = sidecar.loop_of(sidecar.read(data_dir))
+    if want is not None and want != have:
+        raise ValueError("tezip_amd.json describes the prediction loop as %s, entropy.dat's trailer as %s" % (want, have))
+    return have == "closed"
+
+
+def refuse_closed_range(frames):
+    """A frame range of a closed-loop stream: exit status 2 (the error class of adopt_contract: nothing was written)."""
+    if frames is not None:
+        print("ERROR:", closedloop.NO_FRAMES)
+        sys.exit(2)
 
 
 def set_sdelta(ctx, mode):
@@ -325,6 +347,10 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
 
+        # a closed-loop stream (TZ-CL1, tezip_amd/closedloop.py) has no rollout ahead of its payload: every step of
+        # tz_rollout_decode_closed reads the quantised deltas.  The sidecar says so up front; the trailer's mark has the last word
+        sidecar_closed = sidecar.loop_of(sidecar.read(DATA_DIR)) == "closed"
+
         with open(paths["entropy.dat"], "rb") as f:
             ent_head = f.read(64)
         fmt = coded_format(ent_head)
@@ -335,6 +361,10 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             coded = fmt.parse(np.fromfile(paths["entropy.dat"], np.uint8), key_len)
             table, warm_up = coded.table, coded.warm_up
             one, nt, H, W, C = coded.shape
+            closed = check_loop(DATA_DIR, one)
+            one = closedloop.open_mark(one)
+            if closed:
+                refuse_closed_range(frames)
             if stack is not None and key_len == stack[0] * stack[1] * stack[2] * 3 and len(file_names) == stack[0] \
                     and (nt, H, W, warm_up) != tuple(stack):
                 raise ValueError("tezip_amd.json describes the stack as %r (frames, height, width, warm-up), entropy.dat's trailer as %r"
@@ -345,8 +375,9 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             begin, put, expand = coded_calls(ctx, coded)
             begin(coded.body.size, coded.n, coded.lengths, coded.base, run=coded.run)
             per = stage_keys(nt, H, W, hp, wp)
-            rollout(nt, warm_up)
-            stages.mark("rollout (decoder) queued")
+            if not closed:
+                rollout(nt, warm_up)
+                stages.mark("rollout (decoder) queued")
             piece = PUT_PIECE
             for off in range(0, coded.body.size, piece):
                 put(off, coded.body[off: off + piece])                  # pageable: the piece is free again on return
@@ -364,7 +395,7 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             early = None
             if stack is not None and key_len == stack[0] * stack[1] * stack[2] * 3 and len(file_names) == stack[0]:
                 hp_e, wp_e = padding_shape(stack[1], stack[2])
-                if model_shape is None or (model_shape[0] == hp_e and model_shape[1] == wp_e):
+                if (model_shape is None or (model_shape[0] == hp_e and model_shape[1] == wp_e)) and not sidecar_closed:
                     early = stack
             pre = _Prefetch(paths["entropy.dat"])      # entropy.dat is being decompressed from here on
             try:
@@ -396,6 +427,10 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             table = None if tlen == -1 else np.ascontiguousarray(tail[tail.size - 7 - tlen: tail.size - 7])
             payload_len = total - 7 - max(tlen, 0)
             check_stream(shape, warm_up, payload_len, key_len)
+            closed = check_loop(DATA_DIR, shape[0])   # (a rollout that ran early on a closed-loop stream: the sidecar is another stream's)
+            if closed:
+                refuse_closed_range(frames)
+            shape = (closedloop.open_mark(shape[0]),) + shape[1:]
             if sdelta.is_shuffled(shape[0]):
                 return False
             one, nt, H, W, C = shape
@@ -407,7 +442,8 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             if early is None:
                 hp, wp = checks(nt, H, W)
                 per = stage_keys(nt, H, W, hp, wp)
-                rollout(nt, warm_up)
+                if not closed:
+                    rollout(nt, warm_up)
         check_channels(DATA_DIR, C)
         ctx.set_payload_channels(C)         # 1: the one-channel payload of a gray job; the frames keep three channels
         set_sdelta(ctx, check_sdelta(DATA_DIR, one))   # 1: the payload's spatial delta ran at the channel stride, 2: plane
@@ -415,7 +451,15 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             check_records(records, nt, H, W)
         stages.mark("rollout (decoder)", ctx)
         lo, hi = frames or (0, nt)
-        ctx.decode_range(None, table, lo, hi - lo, out="resident")
+        if closed:   # the staged payload becomes the quantised deltas, then predict and reconstruct step by step
+            if VERBOSE:
+                ctx.prof_enable(True)
+            t0 = time.time()
+            ctx.rollout_decode_closed(None, warm_up, None, table)
+            if VERBOSE:
+                print("predict:{0}".format(time.time() - t0) + "[sec]")
+        else:
+            ctx.decode_range(None, table, lo, hi - lo, out="resident")
         stages.mark("decode tail (frames resident)", ctx)
         if records is not None:
             verify_frames(records, ctx.decoded_digests(lo, hi - lo), lo, file_names)
@@ -562,6 +606,13 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
     else:
         payload, table, shape, warm_up = parse_stream(read("entropy.dat"))
         check_stream(shape, warm_up, payload.size, key_len)
+    closed = check_loop(DATA_DIR, shape[0])
+    shape = (closedloop.open_mark(shape[0]),) + tuple(shape[1:])
+    if closed and job is not None:
+        print("ERROR:", closedloop.NO_SHARDED_DECODE)
+        sys.exit(2)
+    if closed:
+        refuse_closed_range(frames)
     _, nt, H, W, C = shape
     check_channels(DATA_DIR, C)
     if C == 1 and job is not None:
@@ -612,17 +663,23 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
             first, end = frames or (0, nt)
             if keys is not None:    # the same C calls as the streaming path; the stack stays on the device
                 stage_coded_keys(ctx, keys, (nt, H, W))
-                ctx.rollout_decode_range(None, warm_up, first, end - first)
-            else:
-                ctx.rollout_decode_range(np.ascontiguousarray(key_frames), warm_up, first, end - first)
-            if VERBOSE:
-                print("predict:{0}".format(time.time() - t0) + "[sec]")
+            kf = None if keys is not None else np.ascontiguousarray(key_frames)
+            if not closed:   # (tz_rollout_decode_closed reads the payload in every step: it runs once that is staged)
+                ctx.rollout_decode_range(kf, warm_up, first, end - first)
+                if VERBOSE:
+                    print("predict:{0}".format(time.time() - t0) + "[sec]")
             if coded is not None:
                 begin, put, expand = coded_calls(ctx, coded)
                 begin(coded.body.size, coded.n, coded.lengths, coded.base, run=coded.run)
                 put(0, np.ascontiguousarray(coded.body))
                 expand()
-            frames = ctx.decode_range(None if coded is not None else np.ascontiguousarray(payload), tb, first, end - first)
+            if closed:
+                ctx.rollout_decode_closed(kf, warm_up, None if coded is not None else np.ascontiguousarray(payload), tb)
+                if VERBOSE:
+                    print("predict:{0}".format(time.time() - t0) + "[sec]")
+                frames = ctx.decoded_get(0, nt)
+            else:
+                frames = ctx.decode_range(None if coded is not None else np.ascontiguousarray(payload), tb, first, end - first)
             if VERBOSE:
                 prof = ctx.prof_get()
                 if table is not None:

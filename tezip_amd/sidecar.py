@@ -24,6 +24,10 @@ that contradicts it is an error.
 tezip_amd/lattice.py); every other job has no such key.  Informational: the payload holds the quantised deltas themselves, a
 decoder never sees a bound, and `-u` does not read the key.
 
+`loop` = "closed" (optional): the job ran closed-loop prediction TZ-CL1 (`-c --loop closed`, tezip_amd/closedloop.py); every other
+job has no such key.  The mark in entropy.dat's trailer is authoritative (the open-loop mark plus 16); a sidecar that contradicts
+it is an error.  A decoder that reads "closed" here does not queue its rollout ahead of the payload: the loop needs it.
+
 `stack` = [frames, height, width, warm_up] (round 6, optional): the reference stores these in the LAST seven
 values of entropy.dat (compress.py:390-394), so a decoder learns it only when the whole payload is decompressed; with
 it here the decoder runs its rollout WHILE entropy.dat is being decompressed (decompress._run_streaming) and checks the
@@ -60,7 +64,7 @@ def requested_contract():
     return int(v) if v in ("1", "2") else None
 
 
-def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta="flat", quant="greedy", bound_map=None):
+def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta="flat", quant="greedy", bound_map=None, loop="open"):
     from . import _lib
     if contract not in (1, 2):
         raise ValueError("contract must be 1 or 2, not %r" % (contract,))
@@ -77,6 +81,8 @@ def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta
         doc["quant"] = "lattice"
     if bound_map is not None:   # a --bound-map job: {"max", "exact_pixels"}, informational (`-u` does not read it); else no such key
         doc["bound_map"] = {"max": int(bound_map["max"]), "exact_pixels": int(bound_map["exact_pixels"])}
+    if loop == "closed":        # a --loop closed job (tezip_amd/closedloop.py); every other job has no such key
+        doc["loop"] = "closed"
     with open(os.path.join(out_dir, NAME), "w", encoding="UTF-8") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
@@ -130,6 +136,17 @@ def sdelta_of(doc):
     if mode not in ("flat", "channel", "plane") or ("sdelta" in doc and mode == "flat"):
         raise SidecarMismatch("%s states sdelta %r (\"channel\" and \"plane\" are the only values ever written)" % (NAME, mode))
     return mode
+
+
+def loop_of(doc):
+    """The prediction loop the sidecar states: "closed" for a --loop closed job (tezip_amd/closedloop.py), "open" for a sidecar
+    without the key, None without a sidecar.  Anything else is a damaged file."""
+    if doc is None:
+        return None
+    loop = doc.get("loop", "open")
+    if loop not in ("open", "closed") or ("loop" in doc and loop == "open"):
+        raise SidecarMismatch("%s states loop %r (\"closed\" is the only value ever written)" % (NAME, loop))
+    return loop
 
 
 def resolve(doc, wts=None):

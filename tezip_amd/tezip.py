@@ -15,7 +15,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "tezip_amd"
 
-from . import boundmap, compress, decompress, frametarget, sdauto, target, train  # noqa: E402
+from . import boundmap, closedloop, compress, decompress, frametarget, sdauto, target, train  # noqa: E402
 
 # (short, long, argparse keywords) -- tezip.py:88-99
 FLAG_TABLE = (
@@ -110,6 +110,12 @@ FLAG_TABLE = (
     # LARGER on sparse frames at loose bounds, and at tight bounds about 2 dB less PSNR for the same worst-case error: README).
     # The files are ordinary ones: -u needs no flag (compress.run(QUANT=...))
     (None, "--quant", dict(type=str, choices=("greedy", "lattice"), default=None, dest="quant")),
+    # not in the reference: with -c, what the predictor is fed inside a window.  open (also when the flag is absent) = its own last
+    # prediction (compress.py:230); closed = the DECODED frame in front, which the decoder holds anyway: every prediction is a
+    # one-step prediction (definition TZ-CL1 in tezip_amd/closedloop.py; smaller files with a trained model, README).  With -w and
+    # -m abs, lossless or with --quant lattice; not with -t, --sweep, --gray, a target, --per-frame, --frame-bounds, --bound-map
+    # or a sharded job.  -u recognises the stream by the mark in its trailer (compress.run(LOOP=...))
+    (None, "--loop", dict(type=str, choices=("open", "closed"), default=None, dest="loop")),
 )
 
 TEXT = {
@@ -279,6 +285,22 @@ def check_quant_flag(arg):
     return compress.check_quant(quant, int(os.environ.get("WORLD_SIZE", "1")) > 1)
 
 
+def check_loop_flag(arg):
+    """--loop is valid with -c only; `closed` needs one single-GPU SWP job under one abs bound (lossless, or --quant lattice).
+    Returns None, or the message of a refusal."""
+    loop = getattr(arg, "loop", None)
+    if loop is None:
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return closedloop.NEEDS_COMPRESS
+    return closedloop.check_flags(loop, arg.mode[0] if arg.mode else None, arg.bound or [], getattr(arg, "quant", None),
+                                  arg.threshold[0] if arg.threshold is not None else None, getattr(arg, "sweep", None) is not None,
+                                  int(os.environ.get("WORLD_SIZE", "1")) > 1, bool(getattr(arg, "gray", False)),
+                                  getattr(arg, "target_psnr", None), getattr(arg, "target_ratio", None),
+                                  bool(getattr(arg, "per_frame", False)), getattr(arg, "frame_bounds", None),
+                                  getattr(arg, "bound_map", None))
+
+
 def check_target_flag(arg):
     """--target-psnr is valid with -c of one single-GPU job, in place of -m and -b, without --sweep.  Returns None, or the
     message of a refusal."""
@@ -413,6 +435,10 @@ def _main(arg):
     if problem:   # exit status 2, as decompress.adopt_contract's errors: nothing was written
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_loop_flag(arg)
+    if problem:   # likewise (in front of the other flags' checks: a refusal of this job names the flag that defines it)
+        print("ERROR:", problem)
+        sys.exit(2)
     problem = check_bound_map_flag(arg)
     if problem:   # likewise (in front of the other flags' checks: a refusal of this job names the flag that defines it)
         print("ERROR:", problem)
@@ -505,6 +531,12 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if getattr(arg, "loop", None) == "closed":   # (open is the job without the flag: the calls below; every other flag travels with it)
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu, arg.verbose,
+                            arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), SDELTA=getattr(arg, "sdelta", None) or "flat",
+                            SSIM=bool(getattr(arg, "ssim", False)), QUANT=getattr(arg, "quant", None) or "greedy", LOOP="closed")
     if map_file is not None:   # (every other flag travels with it; the jobs without it are the calls below)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
