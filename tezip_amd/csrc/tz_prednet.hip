@@ -26,6 +26,7 @@
 
 #include "tz_conv_kernels.hip.h"
 #include "tz_wino_kernels.hip.h"
+#include "tz_l0_kernels.hip.h"
 
 // ------------------------------------------------------------------------------- host side
 struct Seg {
@@ -94,6 +95,10 @@ struct tz_model {
     // bit (dead0_hold) has put something else into E_0's positive half; level 0 then stores both halves from there on.
     bool deadhalf[TZ_MAX_LEVELS] = {false};
     bool e0_dirty = false;
+    // Level 0 on the vector ALU (tz_l0_kernels.hip.h; choose_l0_forms, tz_model_prepare): the level-0 gate convolution takes
+    // k_l0_gates -- and deadf0: without its forget-gate columns (C0_0 is +0 in every word, every gate weight finite)
+    bool l0valu_g = false, deadf0 = false;
+    float* l0_wg = nullptr;   // k_l0_gates: the weights of up(R_1) as [class][16-channel block][collapsed tap][channel][12 columns]
     float *E[TZ_MAX_LEVELS] = {0}, *R1[TZ_MAX_LEVELS] = {0};
     float* P[TZ_MAX_LEVELS] = {0};   // gate accumulators after the E_l part of the chain (split launches of small grids), or null
     int Pcap[TZ_MAX_LEVELS] = {0};   // ... how many batch slots P[l] holds (<= maxB: at most kPBytes per level)
@@ -646,6 +651,18 @@ static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbat
         TZ_HIP(ctx, hipGetLastError());
         return TZ_OK;
     }
+    // Level 0 of the reference shape on the vector ALU (choose_l0_forms): the same chains as k_conv16b<.., DEAD0>, and like it
+    // only while Wblk0 says that the positive half of E_0 is left out (a call that holds the skip off takes k_conv16b).
+    // (Counted with k_conv16b, as the level-0 convolutions: the same launches of a step, whichever kernel takes them.)
+    if (const tz_model* m = ctx->model; m && ctx->conv_impl && a.nsrc > 0 && a.src[0].pstride == 8) {
+        if (m->l0valu_g && a.Wblk0 && epi == EPI_LSTM_PACKED && ups && a.nsrc == 2 && a.init && a.Wp == m->gate_t1[0].d_W) {
+            ps.sub = TZP_CONV16B;
+            const int blocks = ((a.W + tzl0::GT - 1) / tzl0::GT) * ((a.H + tzl0::GT - 1) / tzl0::GT) * nbatch;
+            hipLaunchKernelGGL((k_l0_gates<true, 5>), dim3(blocks), dim3(256), 0, ctx->stream, a, m->l0_wg);
+            TZ_HIP(ctx, hipGetLastError());
+            return TZ_OK;
+        }
+    }
     if (a.Wblk && a.nsrc > 0 && !a.src[0].up && a.src[0].pstride == 8 && ctx->conv_impl) {
         const int blocks = a.ncb * a.tiles_x * a.tiles_y * nbatch;
 #define TZ_CASE16B(nt, e, u)                                                                                    \
@@ -1039,6 +1056,75 @@ static int measure_deadf(tz_ctx* ctx, tz_model* m) {
     return TZ_OK;
 }
 
+// Level 0 on the vector ALU.  Where the model has the reference shape at level 0 -- the shape k_conv_small's fused error
+// unit asks for: 3 image channels, R_0 = 3, E_0 one half per quad, and an R_1 of whole 16-channel blocks -- the level-0 gate
+// convolution takes k_l0_gates (tz_l0_kernels.hip.h): the same fmaf chains as k_conv16b, pad terms included, from the same
+// packed weights (PackedConv::d_W), the dead positive half (measure_dead) left out alike.  A_0 keeps k_conv16b: built the
+// same way it was not faster (EXPERIMENTS.md).
+// k_l0_gates also leaves the forget gate out where measure_deadf's conditions hold at level 0: C0_0 is +0 in every word, so
+// f * c_prev = +0 for every f a hard sigmoid returns and c = (+0) + i g, and every weight of the convolution is finite, so no
+// chain of f could have been NaN (limits: DESIGN.md section 5, the EPI_LSTM3 row).  k_conv16b keeps four gates.  Taken only
+// where BOTH skips apply (the bench's zero-bias model): with anything live k_conv16b measured faster.
+// TEZIP_L0VALU=0 (read here, per prepare): k_conv16b; TEZIP_L0VALU_LOG=1: one line per level-0 convolution.
+static int choose_l0_forms(tz_ctx* ctx, tz_model* m) {
+    const char* env = getenv("TEZIP_L0VALU");
+    const bool on = !env || atoi(env) != 0;
+    const bool log = getenv("TEZIP_L0VALU_LOG") && atoi(getenv("TEZIP_L0VALU_LOG"));
+    m->l0valu_g = m->deadf0 = false;
+    m->l0_wg = nullptr;
+    const bool shape = m->L > 1 && m->stack[0] == 3 && m->rstack[0] == 3 && m->e0s == 8 && m->rstack[1] % 16 == 0;
+    const PackedConv& pg = m->gate_t1[0];
+    // (k_l0_gates reads the 16-column rows [i | f | g | o] x 3 of pack_conv)
+    const bool form_g = shape && pg.d_Wblk && pg.NT == 1 && pg.ncols == 16 && pg.segs.size() == 2;
+    bool zero = false, finite = false;
+    if (on && form_g) {
+        unsigned long long h_live = 0, *d_live = nullptr;
+        TZ_TRY(dmalloc(ctx, m, (void**)&d_live, sizeof(h_live)));
+        TZ_HIP(ctx, hipMemsetAsync(d_live, 0, sizeof(h_live), ctx->stream));
+        const long long nwords = (long long)m->Hp * m->Wp * m->rstack[0];
+        hipLaunchKernelGGL(k_live_blocks, dim3((unsigned)std::min<long long>((nwords + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                           (const unsigned*)m->C0[0], nwords, 1, 1, d_live, 0xffffffffu);
+        TZ_HIP(ctx, hipGetLastError());
+        TZ_HIP(ctx, hipMemcpyAsync(&h_live, d_live, sizeof(h_live), hipMemcpyDeviceToHost, ctx->stream));
+        TZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        zero = !(h_live & 1);
+        std::vector<float> W((size_t)pg.nslots * 16 * pg.ncols);
+        TZ_HIP(ctx, hipMemcpy(W.data(), pg.d_W, W.size() * 4, hipMemcpyDeviceToHost));
+        finite = true;
+        for (float v : W) finite = finite && std::isfinite(v);
+        // the rows of the upsampled source once more, class-major: slot 9 + 16 b + 4 tp + cls of pack_conv, columns 0..11
+        // (the same float32 values; 24 floats of padding behind the last row: the kernel requests one step ahead)
+        const int nub = pg.segs[1].C / 16;
+        std::vector<float> G((size_t)4 * nub * 64 * 12 + 24, 0.0f);
+        for (int cls = 0; cls < 4; ++cls)
+            for (int b = 0; b < nub; ++b)
+                for (int tp = 0; tp < 4; ++tp)
+                    for (int ch = 0; ch < 16; ++ch)
+                        for (int c = 0; c < 12; ++c)
+                            G[((((size_t)cls * nub + b) * 4 + tp) * 16 + ch) * 12 + c] = W[((size_t)(9 + 16 * b + 4 * tp + cls) * 16 + ch) * pg.ncols + c];
+        TZ_TRY(dmalloc(ctx, m, (void**)&m->l0_wg, G.size() * 4));
+        TZ_HIP(ctx, hipMemcpy(m->l0_wg, G.data(), G.size() * 4, hipMemcpyHostToDevice));
+        const char* envf = getenv("TEZIP_DEADF");
+        m->deadf0 = zero && finite && (!envf || atoi(envf) != 0);
+        // Only the form with everything dead left out is taken: with both halves of E_0 and four gates (bias_scale 0.1, the
+        // trained model) k_l0_gates<false, 6> cost 4.34 ms of a 40.4 ms step where k_conv16b costs 3.56 (EXPERIMENTS.md); the
+        // forms in between were not measured and keep k_conv16b too.
+        m->l0valu_g = m->deadf0 && pg.d_Wblk0 != nullptr;
+    }
+    if (log) {
+        fprintf(stderr, "[tezip] level 0 A: k_conv16b (its vector-ALU form was not faster: EXPERIMENTS.md)\n");
+        fprintf(stderr, "[tezip] level 0 gates: %s%s\n", m->l0valu_g ? "k_l0_gates (vector ALU)" : "k_conv16b",
+                m->l0valu_g   ? ", forget-gate columns left out: yes (9 of 12 gate columns)"
+                : !on         ? " (TEZIP_L0VALU=0)"
+                : !form_g     ? " (not the reference shape)"
+                : !pg.d_Wblk0 ? " (the positive half of E_0 is walked: k_conv16b is the faster form)"
+                : !zero       ? " (the forget gate is needed: k_conv16b is the faster form)"
+                : !finite     ? " (a weight of the convolution is not finite: the forget gate is needed)"
+                              : " (TEZIP_DEADF=0: the forget gate is kept)");
+    }
+    return TZ_OK;
+}
+
 // Which k_wino convolutions take the two-quad stage (k_wino2, tz_wino_kernels.hip.h): the three-tile ones -- a gate convolution
 // without its forget gate (measure_deadf), an A convolution of 48 k columns -- whose executed stages, behind the dead prefix
 // (measure_dead), are a multiple of 6 per source (wino2q_walk; the halves of a split gate convolution then qualify too: their
@@ -1259,6 +1345,7 @@ extern "C" int tz_model_prepare(tz_ctx* ctx, int Hp, int Wp, int max_batch) {
     TZ_TRY(measure_uniform(ctx, m));   // (synchronises the stream)
     TZ_TRY(measure_dead(ctx, m));
     TZ_TRY(measure_deadf(ctx, m));
+    TZ_TRY(choose_l0_forms(ctx, m));
     TZ_TRY(choose_wino_forms(ctx, m));
     m->prepared = true;
     return TZ_OK;
