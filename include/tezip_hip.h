@@ -224,6 +224,27 @@ int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, 
 int tz_rollout_loop(tz_ctx* ctx);
 int tz_rollout_decode_closed(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, const int16_t* payload,
                              size_t payload_len, const int16_t* table, int table_len, uint8_t* key_mask);
+/* ---- per-tile choice between the network and the frame in front, definition TZ-PS1 (no reference counterpart;
+ * `tezip.py -c --loop closed --pred select`, DESIGN.md section 9, slow statement in tezip_amd/predselect.py).  In a closed loop both
+ * sides hold dec[t-1] when frame t is predicted: a second predictor.  TZ-PS1 is TZ-CL1 except for the value x of a non-key frame:
+ *   tiles       16 x 16 pixels over the unpadded frame, TH = ceil(H/16) by TW = ceil(W/16), all three channels; edge tiles own the
+ *               samples inside the frame
+ *   mode        m = 1 iff sum |Q(dec[t-1] - orig_t)| < sum |Q(x_net - orig_t)| over the tile, Q the loop's quantiser, integers; a
+ *               tie goes to the network; key frames have mode 0
+ *   x           m ? dec[t-1] : x_net;  q = Q(x - orig);  dec[t] = clamp(x - q, 0, 255).  The network is always fed dec[t-1].
+ *   predictions a chosen tile is written into the prediction stack as (v + 0.5f) / 255.0f (1.0f for v = 255), which truncates back
+ *               to v: tz_encode, the probes, tz_encode_quality, tz_encode_ssim and tz_encode_digests work on it unchanged.
+ * tz_set_pred_select(ctx, on): on = 0 (the default) or 1.  Under 0 tz_rollout_closed and tz_rollout_decode_closed make exactly the
+ *   launches they make without this call.  The open-loop entry points ignore the setting.  The setting a closed loop ran under is
+ *   part of its stamp: tz_encode and the other calls listed at tz_rollout_closed return TZ_ERR_STATE under the other setting.
+ * tz_pred_modes(ctx, out, cap): after a tz_rollout_closed under selection, the nt*TH*TW mode bytes (0 / 1): frame-major, row-major
+ *   tiles, 0 at key frames.  TZ_ERR_STATE when the resident rollout is not such a rollout, TZ_ERR_INVALID for cap < nt*TH*TW.
+ * tz_put_pred_modes(ctx, modes, n): the modes of the stream, ahead of a tz_rollout_decode_closed under selection (host memory; the
+ *   context keeps a copy).  TZ_ERR_INVALID for a byte above 1, and from the rollout for n != nt*TH*TW or a set byte in a key frame. */
+int tz_set_pred_select(tz_ctx* ctx, int on);
+int tz_get_pred_select(tz_ctx* ctx);
+int tz_pred_modes(tz_ctx* ctx, uint8_t* out, size_t cap);
+int tz_put_pred_modes(tz_ctx* ctx, const uint8_t* modes, size_t n);
 
 /* ---- encoder back half on the context-resident rollout (compress.py:289-373) ---------------
  * payload: nt*H*W*3 int16 = rank(1600 - sd) when bit 0 of `entropy` is set, else sd.

@@ -60,6 +60,10 @@ _SIGS = {
     "tz_rollout_loop": (C.c_int, [C.c_void_p]),
     "tz_rollout_decode_closed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.c_int, C.c_void_p]),
+    "tz_set_pred_select": (C.c_int, [C.c_void_p, C.c_int]),
+    "tz_get_pred_select": (C.c_int, [C.c_void_p]),
+    "tz_pred_modes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "tz_put_pred_modes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "tz_range_restart": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "tz_rollout_decode_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p]),
@@ -628,6 +632,26 @@ class Context:
                                                    None if payload is None else _ptr(payload), n, _ptr(tb), tl, key.ctypes.data))
         self._shape = (nt, h, w)
         return key.astype(bool)
+
+    def set_pred_select(self, on):
+        """tz_set_pred_select (TZ-PS1, tezip_amd/predselect.py): rollout_closed / rollout_decode_closed choose per 16 x 16 tile
+        between the network's prediction and the decoded frame in front.  Off by default."""
+        self._ck(self.lib.tz_set_pred_select(self.h, int(bool(on))))
+
+    def get_pred_select(self):
+        return int(self.lib.tz_get_pred_select(self.h))
+
+    def pred_modes(self):
+        """tz_pred_modes: the modes of the resident rollout_closed under selection, uint8 (nt, ceil(H/16), ceil(W/16))."""
+        nt, h, w = self._shape
+        out = np.zeros((nt, (h + 15) // 16, (w + 15) // 16), np.uint8)
+        self._ck(self.lib.tz_pred_modes(self.h, out.ctypes.data, out.size))
+        return out
+
+    def put_pred_modes(self, modes):
+        """tz_put_pred_modes: the stored modes of a stream, ahead of rollout_decode_closed under selection."""
+        m = np.ascontiguousarray(modes, np.uint8)
+        self._ck(self.lib.tz_put_pred_modes(self.h, m.ctypes.data, m.size))
 
     def rollout_decode_range(self, key_frames, warm_up, first, count):
         """tz_rollout_decode for frames [first, first + count) only; key_frames as for rollout_decode.  Returns the key mask

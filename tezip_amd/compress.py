@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, boundmap, closedloop, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
+from . import _lib, boundmap, closedloop, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, predselect, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -476,8 +476,8 @@ def _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages=Non
     else:
         tail = np.array([-1], dtype=np.int64)
     one = sdelta.mark(shuffled, plane) if strided or plane else (SHUFFLE_MARK if shuffled else 1)
-    if closed:
-        one += closedloop.MARK_CLOSED
+    if closed:   # (2: closed-loop prediction with per-tile selection TZ-PS1, tezip_amd/predselect.py: 32 more)
+        one += closedloop.MARK_CLOSED + (predselect.MARK_SELECT if closed == 2 else 0)
     trailer = np.concatenate([tail, [one, nt, H, W, channels], [warm_up]]).astype(np.int16)
     t_e = time.perf_counter()
     if coder in ("huff", "huffr", "huffd"):
@@ -505,7 +505,8 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
     and payload, piece by piece: nothing of size nt*H*W lives on the host.  channels: what the resident payload stores per
     pixel (1: a gray job, tezip_amd/graypayload.py); key_frame.dat has three either way.  strided: the payload's spatial delta
     ran at the channel stride, plane: it is the 2-D one, TZ-SD2 (tezip_amd/sdelta.py): the trailer says so in the first entry of
-    its shape.  closed: the job ran closed-loop prediction TZ-CL1 (tezip_amd/closedloop.py): that entry is 16 larger."""
+    its shape.  closed: the job ran closed-loop prediction TZ-CL1 (tezip_amd/closedloop.py): that entry is 16 larger; closed == 2:
+    with per-tile selection TZ-PS1 (tezip_amd/predselect.py): 48 larger."""
     kf = _key_output(ctx, out_dir, nt, H, W, key, pool, stages, verbose, key_coder)
     esize = _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages, coder, verbose, channels, strided, plane, closed)
     return kf.result(), esize
@@ -565,7 +566,7 @@ def check_ratio(ratio, mode, bound, target_psnr, coder, shuffle, sharded):
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
         SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None, QUANT="greedy", BOUND_MAP=None,
-        LOOP="open"):
+        LOOP="open", PRED="net"):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -650,6 +651,13 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     FRAME_BOUNDS or BOUND_MAP (a target's probes assume predictions that do not depend on the bound).  Works with every SDELTA,
     CODER, KEY_CODER, SHUFFLE, REPORT, SSIM and DIGESTS.  VERBOSE prints no per-step MSE lines.  Single-GPU jobs only.
 
+    PRED (--pred; NOT in the reference): "net" (the default: every file, line and launch is what it is without it) or, with LOOP
+    "closed", "select": every 16 x 16 tile of a predicted frame takes whichever of the network's prediction and the decoded frame
+    in front leaves the smaller quantised residual, definition TZ-PS1 (tezip_amd/predselect.py).  One line says how many tiles
+    took the frame in front, a fifth file pred_modes.dat holds one bit per tile, tezip_amd.json records it, and the first entry of
+    the trailer's shape is 48 larger than the open-loop mark; `-u` recognises the stream by that mark.  REPORT counts the file in
+    `ratio:` and adds "pred_select" to quality.json.  Everything LOOP "closed" refuses stays refused.
+
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
     does not grow with the number of frames.  Under torch.distributed.run the windows are sharded
@@ -687,7 +695,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    problem = predselect.check_flags(PRED, LOOP)
+    if problem:   # likewise
+        print("ERROR:", problem)
+        sys.exit(2)
     closed = LOOP == "closed"
+    select = PRED == "select"
     if TARGET_PSNR is not None:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         problem = (target.check_target(TARGET_PSNR) or (TARGET_NEEDS_ABS if MODE != "abs" or BOUND_VALUE else None)
                    or (TARGET_NOT_SHARDED if tzdist.active() is not None else None))
@@ -774,7 +787,12 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             t0 = time.time()
             if closed:   # TZ-CL1: the decoded frame is fed back, under the job's own bound and quantiser (no window MSE exists)
                 print(closedloop.STDOUT_LINE)
+                if select:   # TZ-PS1: per tile, the network or the decoded frame in front
+                    ctx.set_pred_select(True)
                 key = ctx.rollout_closed(None, PREPROCESS, WINDOW_SIZE, MODE, BOUND_VALUE)
+                if select:
+                    modes = ctx.pred_modes()
+                    print(predselect.stdout_line(modes[~key]))
             else:
                 key, mse = ctx.rollout(None, PREPROCESS, WINDOW_SIZE, THRESHOLD, want_mse=bool(VERBOSE))
             if VERBOSE:
@@ -874,10 +892,13 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             else:
                 _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
                                 coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided, plane=plane,
-                                **({"closed": True} if closed else {}))
+                                **({"closed": 2 if select else True} if closed else {}))
+            if select:
+                modes_size = predselect.write(OUTPUT_DIR, modes)
             if closed:
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
-                                    payload_channels=channels, sdelta=sd_mode, quant=QUANT, loop="closed")
+                                    payload_channels=channels, sdelta=sd_mode, quant=QUANT, loop="closed",
+                                    **({"pred": "select"} if select else {}))
             elif bound_map is not None:
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
                                     payload_channels=channels, sdelta=sd_mode, quant=QUANT, bound_map=boundmap.stats(bound_map))
@@ -894,6 +915,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 report = quality.summarize(stats, src.files, H, W, MODE, [] if bound_map is not None else BOUND_VALUE, quality.file_sizes(OUTPUT_DIR),
                                            window=WINDOW_SIZE, threshold=THRESHOLD, warm_up=PREPROCESS,
                                            **({"ssim": ssim_rec} if SSIM else {}))
+                if select:   # pred_modes.dat is part of the stream
+                    report["stored_bytes"] += modes_size
+                    report["ratio"] = float(report["raw_bytes"]) / float(report["stored_bytes"])
+                    report["pred_select"] = {"tiles": int(modes[~key].size), "prev_tiles": int(np.count_nonzero(modes))}
                 if frame_bounds is not None:
                     report["frame_bounds"] = [float(b) for b in frame_bounds]
                 if bound_map is not None:

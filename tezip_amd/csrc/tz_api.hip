@@ -685,6 +685,8 @@ constexpr int kMaxFrames = 32767;
 static void set_rollout(tz_ctx* ctx, tz_ctx::tz_rollout_kind kind, int pred_first, int pred_end) {
     ctx->rollout_kind = kind;
     ctx->loop_closed = 0;   // (tz_rollout_closed stamps its loop behind this)
+    ctx->loop_select = 0;
+    ctx->pred_modes.clear();
     ctx->pred_first = pred_first;
     ctx->pred_end = pred_end;
 }
@@ -1545,6 +1547,11 @@ static int encode_check(tz_ctx* ctx, const char* who, int mode) {
 // the loop's mode, bound and quantiser, one bound for every sample and the three-channel payload.
 static int loop_check(tz_ctx* ctx, const char* who, int mode, double b0, double b1) {
     if (!ctx->loop_closed) return TZ_OK;
+    if (ctx->loop_select != ctx->pred_select)   // TZ-PS1: chosen tiles are expressed in the predictions, or they are not
+        return tz_fail(ctx, TZ_ERR_STATE,
+                       "%s: the resident predictions are those of a closed loop (tz_rollout_closed) run %s per-tile selection "
+                       "(tz_set_pred_select(%d)); they serve that kind of job alone, the setting is now %d",
+                       who, ctx->loop_select ? "with" : "without", ctx->loop_select, ctx->pred_select);
     const bool same = mode == ctx->loop_mode && b0 == ctx->loop_b0 && (mode != TZ_MODE_ABSREL || b1 == ctx->loop_b1) &&
                       ctx->quantiser == ctx->loop_quantiser;
     if (same && ctx->frame_bounds.empty() && !ctx->map_h && ctx->payload_channels == 3) return TZ_OK;
@@ -2202,6 +2209,48 @@ static int closed_lists(tz_call& call, const std::vector<std::vector<int>>& step
     return TZ_OK;
 }
 
+// ---- per-tile choice of the prediction, definition TZ-PS1 (include/tezip_hip.h: tz_set_pred_select; slow statement in
+// tezip_amd/predselect.py): the mode bytes of a sequence, nt * ceil(H / 16) * ceil(W / 16), frame-major, row-major tiles
+static size_t select_count(int nt, int H, int W) { return (size_t)nt * ((H + 15) / 16) * ((W + 15) / 16); }
+
+// the mode bytes on the device: zero (the encoder's kernels write the tiles of the frames they choose for), or a decoder's
+static int select_modes(tz_call& call, size_t n, const uint8_t* host, uint8_t** d_modes) {
+    TZ_TRY(call.alloc(std::max<size_t>(n, 1), d_modes));
+    if (host) return tz_upload(call.ctx, *d_modes, host, n);
+    if (hipMemsetAsync(*d_modes, 0, n, call.ctx->stream) != hipSuccess) return tz_fail(call.ctx, TZ_ERR_HIP, "clearing the mode bytes failed");
+    return TZ_OK;
+}
+
+extern "C" int tz_set_pred_select(tz_ctx* ctx, int on) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (on != 0 && on != 1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_pred_select takes 0 or 1, not %d", on);
+    if (on != ctx->pred_select) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under the other setting
+    ctx->pred_select = on;
+    return TZ_OK;
+}
+
+extern "C" int tz_get_pred_select(tz_ctx* ctx) { return ctx ? ctx->pred_select : TZ_ERR_INVALID; }
+
+extern "C" int tz_pred_modes(tz_ctx* ctx, uint8_t* out, size_t cap) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (!ctx->loop_closed || !ctx->loop_select)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_pred_modes: the resident rollout is no tz_rollout_closed under tz_set_pred_select(1)");
+    const size_t n = ctx->pred_modes.size();
+    if (!out || cap < n) return tz_fail(ctx, TZ_ERR_INVALID, "tz_pred_modes: room for %zu mode bytes, the rollout has %zu", out ? cap : (size_t)0, n);
+    memcpy(out, ctx->pred_modes.data(), n);
+    return TZ_OK;
+}
+
+extern "C" int tz_put_pred_modes(tz_ctx* ctx, const uint8_t* modes, size_t n) {
+    if (!ctx) return TZ_ERR_INVALID;
+    ctx->put_modes.clear();
+    if (!modes || !n) return tz_fail(ctx, TZ_ERR_INVALID, "tz_put_pred_modes: no mode bytes");
+    for (size_t i = 0; i < n; ++i)
+        if (modes[i] > 1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_put_pred_modes: mode byte %zu is %d, 0 or 1 wanted", i, (int)modes[i]);
+    ctx->put_modes.assign(modes, modes + n);
+    return TZ_OK;
+}
+
 extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, int mode, double b0,
                                  double b1, uint8_t* key_mask) {
     tz_roctx_range roctx_("tz_rollout_closed");
@@ -2225,6 +2274,9 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
     if (ctx->payload_channels != 3 || !ctx->frame_bounds.empty() || ctx->map_h)
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: the closed loop takes one bound and a three-channel payload (no tz_set_payload_channels(1), tz_set_frame_bounds or tz_set_bound_map)");
     const int p = warm_up;
+    const bool select = ctx->pred_select != 0;
+    const size_t nmodes = select_count(nt, H, W);
+    uint8_t* d_modes = nullptr;
     tz_call call(ctx);
     TZ_TRY(rollout_setup(ctx, frames, nt, H, W, warm_up));   // (the whole stack goes up ahead: every frame is read by a step)
     // key mask and groups of the open-loop SWP job (rollout_swp; compress.py:188-220, 249-262)
@@ -2253,6 +2305,12 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
         std::vector<int> all;
         for (const auto& st : steps) all.insert(all.end(), st.begin(), st.end());
         rc = closed_predict(ctx, all, ctx->d_frames);
+        if (rc == TZ_OK && select) {   // TZ-PS1: one launch over all of them (the frame in front is the original)
+            const int* d_all = nullptr;
+            rc = closed_lists(call, steps, &d_all);
+            if (rc == TZ_OK) rc = select_modes(call, nmodes, nullptr, &d_modes);
+            if (rc == TZ_OK) rc = tzk_ps_select(ctx, ctx->d_pred, ctx->d_frames, d_modes, d_all, (int)all.size(), H, W, ctx->Hp, ctx->Wp);
+        }
     } else if (rc == TZ_OK) {
         const size_t fb = (size_t)nt * H * W * 3;
         const int E = fabs(b0) >= 255.0 ? 255 : (int)fabs(b0);
@@ -2260,15 +2318,20 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
         const int* d_lists = nullptr;
         rc = call.alloc(fb, &d_dec);
         if (rc == TZ_OK) rc = closed_lists(call, steps, &d_lists);
+        if (rc == TZ_OK && select) rc = select_modes(call, nmodes, nullptr, &d_modes);
         if (rc == TZ_OK && hipMemcpyAsync(d_dec, ctx->d_frames, fb, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)   // the key frames
             rc = tz_fail(ctx, TZ_ERR_HIP, "tz_rollout_closed: copy of the frame stack failed");
         size_t at = 0;
         for (size_t s = 0; s < steps.size() && rc == TZ_OK; at += steps[s].size(), ++s) {
             rc = closed_predict(ctx, steps[s], d_dec);
-            if (rc == TZ_OK)
+            if (rc == TZ_OK && select)   // TZ-PS1 in the step's place: the mode bytes, the chosen tiles in the predictions, dec[t]
+                rc = tzk_ps_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_modes, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp, E);
+            else if (rc == TZ_OK)
                 rc = tzk_cl_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp, E);
         }
     }
+    std::vector<uint8_t> modes(select ? nmodes : 0);
+    if (rc == TZ_OK && select) rc = tz_d2h(ctx, modes.data(), d_modes, nmodes, ctx->stream);
     if (rc == TZ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "closed-loop rollout failed");
     if (rc != TZ_OK) {  // nothing of a failed rollout may still read the caller's frames when we return
         (void)hipStreamSynchronize(ctx->copy_stream);
@@ -2285,6 +2348,8 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
     ctx->loop_b0 = b0;
     ctx->loop_b1 = b1;
     ctx->loop_quantiser = ctx->quantiser;
+    ctx->loop_select = select ? 1 : 0;
+    ctx->pred_modes.swap(modes);
     if (key_mask) memcpy(key_mask, key.data(), nt);
     return TZ_OK;
 }
@@ -2302,6 +2367,10 @@ extern "C" int tz_rollout_decode_closed(tz_ctx* ctx, const uint8_t* key_frames, 
     if (ctx->payload_channels != 3)
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_decode_closed does not serve a one-channel payload (tz_set_payload_channels(1))");
     TZ_TRY(check_table(ctx, table, table_len));
+    const bool select = ctx->pred_select != 0;
+    if (select && nt > 0 && H > 0 && W > 0 && ctx->put_modes.size() != select_count(nt, H, W))
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_decode_closed under tz_set_pred_select(1): %zu mode bytes were put (tz_put_pred_modes), "
+                       "the stack has %zu tiles", ctx->put_modes.size(), select_count(nt, H, W));
     ctx->have_decoded = false;
     tz_call call(ctx);
     TZ_TRY(rollout_setup(ctx, key_frames, nt, H, W, warm_up));
@@ -2337,10 +2406,19 @@ extern "C" int tz_rollout_decode_closed(tz_ctx* ctx, const uint8_t* key_frames, 
     TZ_TRY(fill_c0(ctx, c0_slots));
     const std::vector<std::vector<int>> steps = closed_steps(key);
     TZ_TRY(closed_lists(call, steps, &d_lists));
+    uint8_t* d_modes = nullptr;
+    if (select) {   // TZ-PS1: the stored modes, now that the keys are known
+        const size_t per = select_count(1, H, W);
+        for (int i = 0; i < nt; ++i)
+            if (key[i] && std::any_of(ctx->put_modes.begin() + i * per, ctx->put_modes.begin() + (i + 1) * per, [](uint8_t m) { return m != 0; }))
+                return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_decode_closed: a mode byte of key frame %d is set (key frames are stored exactly)", i);
+        TZ_TRY(select_modes(call, ctx->put_modes.size(), ctx->put_modes.data(), &d_modes));
+    }
     size_t at = 0;
     for (size_t s = 0; s < steps.size(); at += steps[s].size(), ++s) {
         TZ_TRY(closed_predict(ctx, steps[s], ctx->d_out));
-        TZ_TRY(tzk_cl_recon(ctx, ctx->d_pred, d_q, ctx->d_out, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp));
+        if (select) TZ_TRY(tzk_ps_recon(ctx, ctx->d_pred, d_q, ctx->d_out, d_modes, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp));
+        else TZ_TRY(tzk_cl_recon(ctx, ctx->d_pred, d_q, ctx->d_out, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp));
     }
     TZ_TRY(tz_stream_sync(ctx));
     ctx->key_mask = recon_key_mask(key.data(), nt, warm_up);

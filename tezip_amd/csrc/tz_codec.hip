@@ -5794,3 +5794,220 @@ int tzk_cl_step(tz_ctx* ctx, const float* pred, const uint8_t* orig, uint8_t* de
 int tzk_cl_recon(tz_ctx* ctx, const float* pred, const int16_t* q, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp) {
     return cl_launch(ctx, pred, nullptr, q, dec, d_list, nlist, H, W, Hp, Wp, 0);
 }
+
+// ------------------------------------------------------------------------ per-tile choice of the prediction (TZ-PS1)
+// tz_set_pred_select (include/tezip_hip.h; slow statement in tezip_amd/predselect.py): in a closed loop every
+// 16 x 16 tile of a predicted frame takes whichever of x_net = (int)(pred * 255.0f) and x_prev = dec[t-1] leaves the smaller
+// sum |Q(x - orig)| over its samples inside H x W (a tie goes to the network), one mode byte per tile says which, and a tile that
+// took the frame in front is EXPRESSED in the prediction stack so that the back half, which forms x from that stack, needs no change:
+//   pv(v) = (v + 0.5f) / 255.0f for v < 255, 1.0f for v = 255:  (int)(pv(v) * 255.0f) == v for all 256 values in float32 with the
+//   correctly rounded divide this library is built with (tests/test_predselect.py walks them; the unguarded formula gives a value
+//   above 1.0 at v = 255 alone).  Samples of the padded stack outside H x W stay as the network left them.
+//   k_ps_select (lossless encoder)     prev = orig[t-1], Q the identity (E = 0): mode byte, patched pred; nothing else is written
+//   k_ps_step   (lossy encoder)        prev = dec[t-1], Q = TZ-QL1(E) as cl_sample forms it: mode byte, patched pred and dec[t]
+//   k_ps_recon  (decoder)              the mode byte picks x: dec[t] = clamp(x - q, 0, 255), patched pred; nothing to reduce
+// Mapping: a workgroup of 256 lanes owns a strip of PS_STRIP = 4 tiles of one tile row, 16 rows of 64 pixels.  A lane holds 4
+// pixels = 12 samples of one row (three 16-byte loads of pred, whose pitch and x0 * 3 floats are 16-byte multiples for any shape;
+// three 4-byte loads of each u8 stack where W is a multiple of 4 and the stacks sit on 4-byte boundaries, VEC, else byte by byte
+// with the crop checked per sample), 16 consecutive lanes cover 768 contiguous bytes of a pred row, a wave covers 4 rows, the 4 waves
+// the 16 rows.  The lanes of a tile inside a wave are 4 neighbours in each of 4 rows: lane bits 0, 1, 4, 5, summed with four
+// __shfl_xor; the four waves' partial sums meet in LDS (two buffers by the trip's parity: one barrier a trip).  blockIdx.y walks
+// `list`, blockIdx.x the strips of a frame in a grid-stride loop (at most PS_GRID workgroups a frame).
+enum { PS_SELECT = 0, PS_STEP = 1, PS_RECON = 2 };
+constexpr int PS_TILE = 16, PS_STRIP = 4, PS_GRID = 64;
+
+__device__ __forceinline__ int ps_quant(int d, int E) {   // (cl_sample's q)
+    const unsigned ad = (unsigned)(d < 0 ? -d : d), s = 2u * (unsigned)E + 1u;
+    const int m = (int)min((ad + (unsigned)E) / s * s, 255u);
+    return E ? (d < 0 ? -m : m) : d;
+}
+
+__device__ __forceinline__ float ps_pv(unsigned v) { return v == 255u ? 1.0f : ((float)v + 0.5f) / 255.0f; }
+
+template <int KIND, bool VEC>
+__device__ __forceinline__ void ps_strips(float* pred, const uint8_t* orig, const uint8_t* prev, const int16_t* __restrict__ qs, uint8_t* dec,
+                                          uint8_t* modes, const int* __restrict__ list, int H, int W, int Hp, int Wp, int TH, int TW, int E) {
+    __shared__ unsigned s_cost[2][4][PS_STRIP][2];
+    const int f = list[blockIdx.y];
+    const unsigned row = (unsigned)W * 3u, pitch = (unsigned)Wp * 3u;
+    const size_t fe = (size_t)H * row;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tis = (lane >> 2) & 3;                       // the lane's tile inside the strip
+    const int SW = (TW + PS_STRIP - 1) / PS_STRIP, nstrips = TH * SW;
+    int par = 0;
+    for (int s = blockIdx.x; s < nstrips; s += gridDim.x, par ^= 1) {
+        const int ty = s / SW, sx = s - ty * SW;
+        const int tx = sx * PS_STRIP + tis;
+        const int y = ty * PS_TILE + wave * 4 + (lane >> 4), x0 = sx * (PS_STRIP * PS_TILE) + (lane & 15) * 4;
+        const bool active = y < H && x0 < W;
+        const int ns = active ? min(4, W - x0) * 3 : 0;     // the lane's samples inside the frame (VEC: 12 or 0)
+        float* pf = pred + (size_t)f * Hp * pitch + (size_t)y * pitch + (size_t)x0 * 3;
+        const size_t at = (size_t)f * fe + (size_t)y * row + (size_t)x0 * 3;     // in the unpadded stacks
+        int xn[12], o[12], v[12];
+#pragma unroll
+        for (int j = 0; j < 12; ++j) xn[j] = o[j] = v[j] = 0;
+        if (active) {
+            const float4 a = ((const float4*)pf)[0], b = ((const float4*)pf)[1], c = ((const float4*)pf)[2];
+            const float p[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+            for (int j = 0; j < 12; ++j) xn[j] = (int)(p[j] * 255.0f);
+            if (VEC) {
+                const unsigned* pw = (const unsigned*)(prev + at - fe);
+                const unsigned w0[3] = {pw[0], pw[1], pw[2]};
+#pragma unroll
+                for (int j = 0; j < 12; ++j) v[j] = (int)((w0[j >> 2] >> (8 * (j & 3))) & 0xFFu);
+                if (KIND != PS_RECON) {
+                    const unsigned* ow = (const unsigned*)(orig + at);
+                    const unsigned w1[3] = {ow[0], ow[1], ow[2]};
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) o[j] = (int)((w1[j >> 2] >> (8 * (j & 3))) & 0xFFu);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 12; ++j)
+                    if (j < ns) {
+                        v[j] = (int)prev[at - fe + j];
+                        if (KIND != PS_RECON) o[j] = (int)orig[at + j];
+                    }
+            }
+        }
+        bool m;
+        if (KIND == PS_RECON) {
+            m = active && modes[((size_t)f * TH + ty) * TW + tx] != 0;     // (an active lane's tile is inside the frame)
+        } else {
+            unsigned cn = 0, cp = 0;
+#pragma unroll
+            for (int j = 0; j < 12; ++j)
+                if (j < ns) {
+                    const int qn = ps_quant(xn[j] - o[j], E), qp = ps_quant(v[j] - o[j], E);
+                    cn += (unsigned)(qn < 0 ? -qn : qn);
+                    cp += (unsigned)(qp < 0 ? -qp : qp);
+                }
+            cn += (unsigned)__shfl_xor((int)cn, 1);  cp += (unsigned)__shfl_xor((int)cp, 1);
+            cn += (unsigned)__shfl_xor((int)cn, 2);  cp += (unsigned)__shfl_xor((int)cp, 2);
+            cn += (unsigned)__shfl_xor((int)cn, 16); cp += (unsigned)__shfl_xor((int)cp, 16);
+            cn += (unsigned)__shfl_xor((int)cn, 32); cp += (unsigned)__shfl_xor((int)cp, 32);
+            if ((lane & 0x33) == 0) {
+                s_cost[par][wave][tis][0] = cn;
+                s_cost[par][wave][tis][1] = cp;
+            }
+            __syncthreads();
+            cn = s_cost[par][0][tis][0] + s_cost[par][1][tis][0] + s_cost[par][2][tis][0] + s_cost[par][3][tis][0];
+            cp = s_cost[par][0][tis][1] + s_cost[par][1][tis][1] + s_cost[par][2][tis][1] + s_cost[par][3][tis][1];
+            m = cp < cn;                                    // a tie goes to the network
+            if (wave == 0 && (lane & 0x33) == 0 && tx < TW) modes[((size_t)f * TH + ty) * TW + tx] = m ? 1 : 0;
+        }
+        if (!active) continue;
+        if (KIND != PS_SELECT) {
+            unsigned b[12];
+            if (KIND == PS_RECON) {
+                int q[12];
+                if (VEC) {
+                    const uint2* q2 = (const uint2*)(qs + at);
+                    const uint2 q0 = q2[0], q1 = q2[1], q3 = q2[2];
+                    const unsigned w2[6] = {q0.x, q0.y, q1.x, q1.y, q3.x, q3.y};
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) {
+                        q[2 * j] = (int)(short)(w2[j] & 0xFFFFu);
+                        q[2 * j + 1] = (int)w2[j] >> 16;
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) q[j] = j < ns ? (int)qs[at + j] : 0;
+                }
+#pragma unroll
+                for (int j = 0; j < 12; ++j) {
+                    const int r = (m ? v[j] : xn[j]) - q[j];
+                    b[j] = (unsigned)(r < 0 ? 0 : (r > 255 ? 255 : r));
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 12; ++j) {
+                    const int x = m ? v[j] : xn[j], r = x - ps_quant(x - o[j], E);
+                    b[j] = (unsigned)(r < 0 ? 0 : (r > 255 ? 255 : r));
+                }
+            }
+            if (VEC) {
+                unsigned* dw = (unsigned*)(dec + at);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) dw[j] = b[4 * j] | (b[4 * j + 1] << 8) | (b[4 * j + 2] << 16) | (b[4 * j + 3] << 24);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 12; ++j)
+                    if (j < ns) dec[at + j] = (uint8_t)b[j];
+            }
+        }
+        if (m) {   // the chosen tile in the prediction stack: pv of the frame in front, inside H x W only
+            if (VEC) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    ((float4*)pf)[j] = make_float4(ps_pv((unsigned)v[4 * j]), ps_pv((unsigned)v[4 * j + 1]), ps_pv((unsigned)v[4 * j + 2]),
+                                                   ps_pv((unsigned)v[4 * j + 3]));
+            } else {
+#pragma unroll
+                for (int j = 0; j < 12; ++j)
+                    if (j < ns) pf[j] = ps_pv((unsigned)v[j]);
+            }
+        }
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_ps_select(float* pred, const uint8_t* orig, uint8_t* modes, const int* __restrict__ list, int H, int W,
+                                                   int Hp, int Wp, int TH, int TW) {
+    ps_strips<PS_SELECT, VEC>(pred, orig, orig, nullptr, nullptr, modes, list, H, W, Hp, Wp, TH, TW, 0);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_ps_step(float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, const int* __restrict__ list,
+                                                 int H, int W, int Hp, int Wp, int TH, int TW, int E) {
+    ps_strips<PS_STEP, VEC>(pred, orig, dec, nullptr, dec, modes, list, H, W, Hp, Wp, TH, TW, E);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_ps_recon(float* pred, const int16_t* __restrict__ qs, uint8_t* dec, const uint8_t* modes,
+                                                  const int* __restrict__ list, int H, int W, int Hp, int Wp, int TH, int TW) {
+    ps_strips<PS_RECON, VEC>(pred, nullptr, dec, qs, dec, const_cast<uint8_t*>(modes), list, H, W, Hp, Wp, TH, TW, 0);
+}
+
+int tzk_ps_grid(int H, int W) {
+    const int TH = (H + PS_TILE - 1) / PS_TILE, TW = (W + PS_TILE - 1) / PS_TILE;
+    return std::min(TH * ((TW + PS_STRIP - 1) / PS_STRIP), (int)PS_GRID);
+}
+
+// d_list: nlist sequence indices (device); every stack is the whole sequence's; modes: nt * TH * TW bytes (device).
+static int ps_launch(tz_ctx* ctx, int kind, float* pred, const uint8_t* orig, const int16_t* q, uint8_t* dec, uint8_t* modes, const int* d_list,
+                     int nlist, int H, int W, int Hp, int Wp, int E) {
+    if (nlist <= 0) return TZ_OK;
+    const int TH = (H + PS_TILE - 1) / PS_TILE, TW = (W + PS_TILE - 1) / PS_TILE;
+    const bool vec = W % 4 == 0 && (((uintptr_t)orig | (uintptr_t)dec) & 3) == 0 && ((uintptr_t)q & 7) == 0;
+    if ((uintptr_t)pred & 15) return tz_fail(ctx, TZ_ERR_INVALID, "the prediction stack is off the 16-byte boundary");
+    const dim3 grid((unsigned)tzk_ps_grid(H, W), (unsigned)nlist);
+    tz_prof_scope ps(ctx, kind == PS_RECON ? TZP_RECON : TZP_QUANT);
+    if (kind == PS_SELECT) {
+        if (vec) hipLaunchKernelGGL(k_ps_select<true>, grid, dim3(256), 0, ctx->stream, pred, orig, modes, d_list, H, W, Hp, Wp, TH, TW);
+        else hipLaunchKernelGGL(k_ps_select<false>, grid, dim3(256), 0, ctx->stream, pred, orig, modes, d_list, H, W, Hp, Wp, TH, TW);
+    } else if (kind == PS_STEP) {
+        if (vec) hipLaunchKernelGGL(k_ps_step<true>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, modes, d_list, H, W, Hp, Wp, TH, TW, E);
+        else hipLaunchKernelGGL(k_ps_step<false>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, modes, d_list, H, W, Hp, Wp, TH, TW, E);
+    } else {
+        if (vec) hipLaunchKernelGGL(k_ps_recon<true>, grid, dim3(256), 0, ctx->stream, pred, q, dec, (const uint8_t*)modes, d_list, H, W, Hp, Wp, TH, TW);
+        else hipLaunchKernelGGL(k_ps_recon<false>, grid, dim3(256), 0, ctx->stream, pred, q, dec, (const uint8_t*)modes, d_list, H, W, Hp, Wp, TH, TW);
+    }
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+int tzk_ps_select(tz_ctx* ctx, float* pred, const uint8_t* orig, uint8_t* modes, const int* d_list, int nlist, int H, int W, int Hp, int Wp) {
+    return ps_launch(ctx, PS_SELECT, pred, orig, nullptr, nullptr, modes, d_list, nlist, H, W, Hp, Wp, 0);
+}
+
+int tzk_ps_step(tz_ctx* ctx, float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, const int* d_list, int nlist, int H, int W, int Hp,
+                int Wp, int E) {
+    return ps_launch(ctx, PS_STEP, pred, orig, nullptr, dec, modes, d_list, nlist, H, W, Hp, Wp, E);
+}
+
+int tzk_ps_recon(tz_ctx* ctx, float* pred, const int16_t* q, uint8_t* dec, const uint8_t* modes, const int* d_list, int nlist, int H, int W,
+                 int Hp, int Wp) {
+    return ps_launch(ctx, PS_RECON, pred, nullptr, q, dec, const_cast<uint8_t*>(modes), d_list, nlist, H, W, Hp, Wp, 0);
+}

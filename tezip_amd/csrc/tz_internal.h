@@ -89,6 +89,11 @@ struct tz_ctx {
     int loop_closed = 0;
     int loop_mode = 0, loop_quantiser = 0;
     double loop_b0 = 0.0, loop_b1 = 0.0;
+    // tz_set_pred_select (TZ-PS1): the setting; whether the stamped loop ran under it (part of the stamp: predictions with chosen
+    // tiles expressed in them serve a select job alone, and the other way round); the modes of that loop (nt * TH * TW bytes,
+    // tz_pred_modes), and the modes a decoder was given (tz_put_pred_modes) for its next tz_rollout_decode_closed
+    int pred_select = 0, loop_select = 0;
+    std::vector<uint8_t> pred_modes, put_modes;
     // pinned staging ring for small host->device uploads (index arrays, masks, LUTs): the copy
     // out of it is truly asynchronous and the memory outlives the caller's locals
     uint8_t* ring = nullptr;
@@ -497,6 +502,18 @@ int tzk_key_unresid(tz_ctx*, const int16_t* d_sym, int H, int W, const int* d_id
 int tzk_cl_step(tz_ctx*, const float* pred, const uint8_t* orig, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp,
                 int E);
 int tzk_cl_recon(tz_ctx*, const float* pred, const int16_t* q, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp);
+// per-tile choice of the prediction TZ-PS1 (tezip_amd/predselect.py) on the same frames and stacks; modes: nt * ceil(H/16) * ceil(W/16)
+// bytes on the device, frame-major.  Per 16 x 16 tile, x_prev = the frame in front (orig[t-1] for tzk_ps_select, dec[t-1] for the
+// others) replaces x_net = the truncated prediction iff it leaves the smaller sum |Q(x - orig)| (TZ-QL1 with E, the identity for
+// E = 0); a chosen tile is written into pred as (v + 0.5f) / 255.0f (1.0f for v = 255), which truncates back to v.
+// tzk_ps_select: the mode bytes and the patched pred (lossless: dec is the original); tzk_ps_step: also dec[t] as tzk_cl_step;
+// tzk_ps_recon: the mode bytes are read, dec[t] as tzk_cl_recon.  tzk_ps_grid: the workgroups a frame's launch starts (grid.x).
+int tzk_ps_select(tz_ctx*, float* pred, const uint8_t* orig, uint8_t* modes, const int* d_list, int nlist, int H, int W, int Hp, int Wp);
+int tzk_ps_step(tz_ctx*, float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, const int* d_list, int nlist, int H, int W, int Hp,
+                int Wp, int E);
+int tzk_ps_recon(tz_ctx*, float* pred, const int16_t* q, uint8_t* dec, const uint8_t* modes, const int* d_list, int nlist, int H, int W,
+                 int Hp, int Wp);
+int tzk_ps_grid(int H, int W);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,
             double* h_sse);
 int tzk_sse_blocks(int Hp, int Wp);

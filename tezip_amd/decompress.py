@@ -9,7 +9,7 @@ import time
 
 import numpy as np
 
-from . import _lib, closedloop, digest, huff, huffd, huffr, keycoder, keycoderg, sidecar, zstd
+from . import _lib, closedloop, digest, huff, huffd, huffr, keycoder, keycoderg, predselect, sidecar, zstd
 from . import dist as tzdist
 from . import sdelta
 from .compress import SHUFFLE_MARK, make_context, open_model
@@ -43,9 +43,10 @@ def check_stream(shape, warm_up, payload_len, key_len):
     # sdelta.MARK_PLANE / MARK_PLANE_SHUFFLE (8 / 9) of a payload under the 2-D spatial delta TZ-SD2 (--sdelta plane), which has
     # three channels or one.  3, 6 and 7 mean nothing.  Each of the six plus 16 (17, 18, 20, 21, 24, 25): the same layout of a
     # closed-loop job (--loop closed, tezip_amd/closedloop.py), which has three channels
-    if closedloop.is_closed(one) and C != 3:
+    # Each of those plus 32 (49, 50, 52, 53, 56, 57): a closed-loop job with per-tile selection (--pred select, tezip_amd/predselect.py)
+    if closedloop.is_closed(predselect.closed_mark(one)) and C != 3:
         raise ValueError("entropy.dat: a closed-loop stream (mark %d) has a three-channel payload, the trailer says %d" % (one, C))
-    one = closedloop.open_mark(one)
+    one = closedloop.open_mark(predselect.closed_mark(one))
     if (one not in (1, SHUFFLE_MARK) + sdelta.MARKS + sdelta.PLANE_MARKS or C not in (1, 3) or (one in sdelta.MARKS and C != 3)
             or nt < 1 or H < 1 or W < 1):
         raise ValueError("entropy.dat: unsupported stack shape %r (expected (1, nt, H, W, 3), (1, nt, H, W, 1) for a gray job, "
@@ -90,6 +91,37 @@ def check_loop(data_dir, one):
     if want is not None and want != have:
         raise ValueError("tezip_amd.json describes the prediction loop as %s, entropy.dat's trailer as %s" % (want, have))
     return have == "closed"
+
+
+def early_pred_modes(data_dir):
+    """pred_modes.dat of a stream whose sidecar states per-tile selection (TZ-PS1, tezip_amd/predselect.py) and the stack, read
+    and validated against that stack before a GPU is touched -> the modes, or None when the sidecar says nothing of it (the
+    trailer's mark decides then, in check_pred).  ValueError for a missing or malformed file."""
+    doc = sidecar.read(data_dir)
+    stack = sidecar.stack_of(doc)
+    if sidecar.pred_of(doc) != "select" or stack is None:
+        return None
+    return predselect.read(data_dir, stack[0], stack[1], stack[2])
+
+
+def check_pred(data_dir, one, nt, H, W):
+    """What entropy.dat's trailer states about per-tile selection (the closed-loop mark plus 32) against tezip_amd.json, which
+    records "select" and says nothing otherwise.  The trailer is authoritative; a sidecar that contradicts it belongs to another
+    stream.  Returns the modes of pred_modes.dat, validated against the trailer's stack, or None for a stream without selection."""
+    have = "select" if predselect.is_select(one) else "net"
+    want = sidecar.pred_of(sidecar.read(data_dir))
+    if want is not None and want != have:
+        raise ValueError("tezip_amd.json describes the prediction as %s, entropy.dat's trailer as %s" % (want, have))
+    return predselect.read(data_dir, nt, H, W) if have == "select" else None
+
+
+def pred_modes_or_exit(data_dir, one, nt, H, W):
+    """check_pred with a refusal as one ERROR line and exit status 2 (the error class of adopt_contract: nothing was written)."""
+    try:
+        return check_pred(data_dir, one, nt, H, W)
+    except ValueError as e:
+        print("ERROR:", e)
+        sys.exit(2)
 
 
 def refuse_closed_range(frames):
@@ -361,6 +393,8 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             coded = fmt.parse(np.fromfile(paths["entropy.dat"], np.uint8), key_len)
             table, warm_up = coded.table, coded.warm_up
             one, nt, H, W, C = coded.shape
+            modes = pred_modes_or_exit(DATA_DIR, one, nt, H, W)
+            one = predselect.closed_mark(one)
             closed = check_loop(DATA_DIR, one)
             one = closedloop.open_mark(one)
             if closed:
@@ -427,6 +461,8 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             table = None if tlen == -1 else np.ascontiguousarray(tail[tail.size - 7 - tlen: tail.size - 7])
             payload_len = total - 7 - max(tlen, 0)
             check_stream(shape, warm_up, payload_len, key_len)
+            modes = pred_modes_or_exit(DATA_DIR, *shape[:4])
+            shape = (predselect.closed_mark(shape[0]),) + shape[1:]
             closed = check_loop(DATA_DIR, shape[0])   # (a rollout that ran early on a closed-loop stream: the sidecar is another stream's)
             if closed:
                 refuse_closed_range(frames)
@@ -455,6 +491,9 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
+            if modes is not None:   # TZ-PS1: the stored modes pick every tile's prediction
+                ctx.set_pred_select(True)
+                ctx.put_pred_modes(modes)
             ctx.rollout_decode_closed(None, warm_up, None, table)
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
@@ -558,6 +597,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
 
     cfg, wts, model_shape = open_model(WEIGHTS_DIR)
     contract = adopt_contract(DATA_DIR, wts, VERBOSE)
+    try:   # a stream with per-tile selection (tezip_amd/predselect.py): its fifth file is read and validated before a GPU is touched
+        early_pred_modes(DATA_DIR)
+    except ValueError as e:
+        print("ERROR:", e)
+        sys.exit(2)
     if job is None and not os.environ.get("TEZIP_NO_STREAMING"):
         # (the sidecar passed adopt_contract: it is readable or absent)
         stack = None if os.environ.get("TEZIP_NO_EARLY_ROLLOUT") else sidecar.stack_of(sidecar.read(DATA_DIR))
@@ -606,6 +650,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
     else:
         payload, table, shape, warm_up = parse_stream(read("entropy.dat"))
         check_stream(shape, warm_up, payload.size, key_len)
+    modes = pred_modes_or_exit(DATA_DIR, *shape[:4])
+    shape = (predselect.closed_mark(shape[0]),) + tuple(shape[1:])
     closed = check_loop(DATA_DIR, shape[0])
     shape = (closedloop.open_mark(shape[0]),) + tuple(shape[1:])
     if closed and job is not None:
@@ -673,6 +719,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
                 begin(coded.body.size, coded.n, coded.lengths, coded.base, run=coded.run)
                 put(0, np.ascontiguousarray(coded.body))
                 expand()
+            if closed and modes is not None:   # TZ-PS1: the stored modes pick every tile's prediction
+                ctx.set_pred_select(True)
+                ctx.put_pred_modes(modes)
             if closed:
                 ctx.rollout_decode_closed(kf, warm_up, None if coded is not None else np.ascontiguousarray(payload), tb)
                 if VERBOSE:

@@ -317,8 +317,11 @@ def parse_of(fmt, p, check, data, key_len=None):
     # one: 1, 4 = the spatial delta of a three-channel payload at the channel stride, or 8 = the 2-D spatial delta TZ-SD2 of a payload
     # of three channels or one (tezip_amd/sdelta.py); byte planes (2, 5, 9) are never Huffman-coded
     # each plus 16 (17, 20, 24): the same layout of a closed-loop job (tezip_amd/closedloop.py), which has three channels
+    # each plus 48 (49, 52, 56): a closed-loop job with per-tile selection (tezip_amd/predselect.py)
     if one in (17, 20, 24) and C == 3:
         one -= 16
+    elif one in (49, 52, 56) and C == 3:
+        one -= 48
     if one not in (1, 4, 8) or C not in (1, 3) or (one == 4 and C != 3) or nt < 1 or H < 1 or W < 1:
         raise ValueError("%s: unsupported stack shape %r (expected (1, nt, H, W, 3), (1, nt, H, W, 1) for a gray job, "
                          "(4, nt, H, W, 3) for a channel-stride payload or (8, nt, H, W, 3 or 1) for a plane payload; 16 more for a closed-loop job)" % (what, tuple(p.shape)))

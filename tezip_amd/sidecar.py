@@ -28,6 +28,10 @@ decoder never sees a bound, and `-u` does not read the key.
 job has no such key.  The mark in entropy.dat's trailer is authoritative (the open-loop mark plus 16); a sidecar that contradicts
 it is an error.  A decoder that reads "closed" here does not queue its rollout ahead of the payload: the loop needs it.
 
+`pred` = "select" (optional): the job chose per 16 x 16 tile between the network and the decoded frame in front, TZ-PS1
+(`-c --loop closed --pred select`, tezip_amd/predselect.py); every other job has no such key.  The mark in entropy.dat's trailer is
+authoritative (the closed-loop mark plus 32); a sidecar that contradicts it is an error.
+
 `stack` = [frames, height, width, warm_up] (round 6, optional): the reference stores these in the LAST seven
 values of entropy.dat (compress.py:390-394), so a decoder learns it only when the whole payload is decompressed; with
 it here the decoder runs its rollout WHILE entropy.dat is being decompressed (decompress._run_streaming) and checks the
@@ -64,7 +68,8 @@ def requested_contract():
     return int(v) if v in ("1", "2") else None
 
 
-def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta="flat", quant="greedy", bound_map=None, loop="open"):
+def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta="flat", quant="greedy", bound_map=None, loop="open",
+          pred="net"):
     from . import _lib
     if contract not in (1, 2):
         raise ValueError("contract must be 1 or 2, not %r" % (contract,))
@@ -83,6 +88,8 @@ def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta
         doc["bound_map"] = {"max": int(bound_map["max"]), "exact_pixels": int(bound_map["exact_pixels"])}
     if loop == "closed":        # a --loop closed job (tezip_amd/closedloop.py); every other job has no such key
         doc["loop"] = "closed"
+    if pred == "select":        # a --pred select job (tezip_amd/predselect.py); every other job has no such key
+        doc["pred"] = "select"
     with open(os.path.join(out_dir, NAME), "w", encoding="UTF-8") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
@@ -147,6 +154,17 @@ def loop_of(doc):
     if loop not in ("open", "closed") or ("loop" in doc and loop == "open"):
         raise SidecarMismatch("%s states loop %r (\"closed\" is the only value ever written)" % (NAME, loop))
     return loop
+
+
+def pred_of(doc):
+    """What the sidecar states about per-tile selection: "select" for a --pred select job (tezip_amd/predselect.py), "net" for a
+    sidecar without the key, None without a sidecar.  Anything else is a damaged file."""
+    if doc is None:
+        return None
+    pred = doc.get("pred", "net")
+    if pred not in ("net", "select") or ("pred" in doc and pred == "net"):
+        raise SidecarMismatch("%s states pred %r (\"select\" is the only value ever written)" % (NAME, pred))
+    return pred
 
 
 def resolve(doc, wts=None):

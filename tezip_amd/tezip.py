@@ -15,7 +15,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "tezip_amd"
 
-from . import boundmap, closedloop, compress, decompress, frametarget, sdauto, target, train  # noqa: E402
+from . import boundmap, closedloop, compress, decompress, frametarget, predselect, sdauto, target, train  # noqa: E402
 
 # (short, long, argparse keywords) -- tezip.py:88-99
 FLAG_TABLE = (
@@ -116,6 +116,12 @@ FLAG_TABLE = (
     # -m abs, lossless or with --quant lattice; not with -t, --sweep, --gray, a target, --per-frame, --frame-bounds, --bound-map
     # or a sharded job.  -u recognises the stream by the mark in its trailer (compress.run(LOOP=...))
     (None, "--loop", dict(type=str, choices=("open", "closed"), default=None, dest="loop")),
+    # not in the reference: with -c --loop closed, what a 16 x 16 tile of a predicted frame is predicted from.  net (also when the
+    # flag is absent) = the network, today's job byte for byte; select = whichever of the network and the decoded frame in front
+    # leaves the smaller quantised residual, one bit per tile in a fifth file pred_modes.dat (definition TZ-PS1 in
+    # tezip_amd/predselect.py; in a lossless job no tile's residual grows in L1 norm, which promises nothing about bytes: README).
+    # -u recognises the stream by the mark in its trailer (compress.run(PRED=...))
+    (None, "--pred", dict(type=str, choices=("net", "select"), default=None, dest="pred")),
 )
 
 TEXT = {
@@ -301,6 +307,16 @@ def check_loop_flag(arg):
                                   getattr(arg, "bound_map", None))
 
 
+def check_pred_flag(arg):
+    """--pred is valid with -c only; `select` needs --loop closed.  Returns None, or the message of a refusal."""
+    pred = getattr(arg, "pred", None)
+    if pred is None:
+        return None
+    if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
+        return predselect.NEEDS_COMPRESS
+    return predselect.check_flags(pred, getattr(arg, "loop", None) or "open")
+
+
 def check_target_flag(arg):
     """--target-psnr is valid with -c of one single-GPU job, in place of -m and -b, without --sweep.  Returns None, or the
     message of a refusal."""
@@ -439,6 +455,10 @@ def _main(arg):
     if problem:   # likewise (in front of the other flags' checks: a refusal of this job names the flag that defines it)
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_pred_flag(arg)
+    if problem:   # likewise (behind --loop's check: everything the closed loop refuses stays refused in its own words)
+        print("ERROR:", problem)
+        sys.exit(2)
     problem = check_bound_map_flag(arg)
     if problem:   # likewise (in front of the other flags' checks: a refusal of this job names the flag that defines it)
         print("ERROR:", problem)
@@ -536,7 +556,8 @@ def _main(arg):
                             arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
                             CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
                             DIGESTS=bool(getattr(arg, "digests", False)), SDELTA=getattr(arg, "sdelta", None) or "flat",
-                            SSIM=bool(getattr(arg, "ssim", False)), QUANT=getattr(arg, "quant", None) or "greedy", LOOP="closed")
+                            SSIM=bool(getattr(arg, "ssim", False)), QUANT=getattr(arg, "quant", None) or "greedy", LOOP="closed",
+                            **({"PRED": "select"} if getattr(arg, "pred", None) == "select" else {}))
     if map_file is not None:   # (every other flag travels with it; the jobs without it are the calls below)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
