@@ -1517,66 +1517,131 @@ __global__ __launch_bounds__(NTHR, 6) void k_conv16b(const ConvArgs a) {
     else conv_epilogue<NT, EPI, MAP>(a, acc, n, cb, ty0, tx0, wv, lane, smem);
 }
 
-// Level-0 prediction Ahat_0 = min(relu(conv3x3(r_0)), 1) (prednet.py:268-271) with CIN, COUT <= 4:
+// Level-0 prediction Ahat_0 = min(relu(conv3x3(r_0)), 1) (prednet.py:268-271), 3 channels in, 3 out:
 // 81 fmaf per pixel do not need the matrix cores (the MFMA kernel pads K and N to 16 and spends
-// its time in 9 barrier-separated staging steps: 55 us per launch at 512^2 x 4).  One thread per
-// pixel, 18x18 halo tile in LDS, weights by scalar loads.  Same chain as the MFMA kernel and the
+// its time in 9 barrier-separated staging steps: 55 us per launch at 512^2 x 4).  Same chain as the MFMA kernel and the
 // oracle: acc = bias; for tap (ky, kx) ascending; for ci ascending: acc = fmaf(x, w, acc), where a
 // tap outside the image multiplies a stored zero.
+// The kernel moves 45 bytes a pixel and computes next to nothing, so it is built around 16-byte accesses and has no LDS and
+// no barrier: a thread owns four neighbouring pixels of a row -- 48 bytes of prediction out, four quads of E_0 -- and loads
+// its own 3 x 6 pixel window of R_0 as five aligned quads a row (the neighbours' quads come from L1 / L2: a halo patch
+// staged in LDS, its halo columns loaded by edge threads, was not distinguishable in time and is the longer text, EXPERIMENTS.md).  A workgroup is a tile of CS_TH x CS_TW pixels.  W is a multiple of 4
+// (tz_model_prepare: of 8), so a group of four lies inside the image or outside it and starts on a 16-byte boundary of its
+// frame.  Weights, bias and the batch item's table entries are scalar loads.
+static constexpr int CS_TW = 64, CS_TH = 16;          // 256 threads x 4 pixels
+static constexpr int CS_G = CS_TW / 4;                // groups of four pixels in a row of the tile
+__host__ __device__ __forceinline__ int conv_small_tiles(int H, int W) { return ((W + CS_TW - 1) / CS_TW) * ((H + CS_TH - 1) / CS_TH); }
+
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256) void k_conv_small(const ConvArgs a) {
-    __shared__ float tile[PPIX * CIN];
+    static_assert(CIN == 3 && COUT == 3, "the one shape launch_conv sends here");
+    typedef const __attribute__((address_space(4))) float* cfloat;   // per-model constants and per-call tables: scalar loads
+    typedef const __attribute__((address_space(4))) int* cint;
     const int tid = threadIdx.x;
-    const int ntiles = a.tiles_x * a.tiles_y;
+    const int tsx = (a.W + CS_TW - 1) / CS_TW, ntiles = conv_small_tiles(a.H, a.W);
     const int tileid = blockIdx.x % ntiles, n = blockIdx.x / ntiles;
-    const int ty0 = (tileid / a.tiles_x) * 16, tx0 = (tileid % a.tiles_x) * 16;
+    const int ty0 = (tileid / tsx) * CS_TH, tx0 = (tileid % tsx) * CS_TW;
     const float* base = a.src[0].p + (long long)n * a.src[0].nstride;
-    for (int i = tid; i < PPIX * CIN; i += 256) {
-        const int pp = i / CIN, ci = i - pp * CIN;
-        const int yy = ty0 - 1 + pp / PW, xx = tx0 - 1 + pp % PW;
-        tile[i] = (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) ? base[((long long)yy * a.W + xx) * CIN + ci] : 0.0f;
-    }
-    __syncthreads();
-    const int py = tid >> 4, px = tid & 15;
-    float acc[COUT];
+    const int py = tid / CS_G, g = tid % CS_G;
+    const int y = ty0 + py, x = tx0 + 4 * g;
+    if (y >= a.H || x >= a.W) return;
+    // The window of a row: five quads, floats 3 x - 4 .. 3 x + 15 of the image row -- pixel x - 1 + m, channel ci at float
+    // k = 1 + 3 m + ci.  The first quad is not loaded at the left edge, the last not at the right edge, none of a row
+    // outside the image: those stay zero.
+    f32x4 xr[3][5];
 #pragma unroll
-    for (int co = 0; co < COUT; ++co) acc[co] = a.bias[co];
+    for (int ky = 0; ky < 3; ++ky) {
+        const int yy = y - 1 + ky;
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        const float* x = tile + ((py + tap / 3) * PW + px + tap % 3) * CIN;
+        for (int q = 0; q < 5; ++q) xr[ky][q] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        if (yy >= 0 && yy < a.H) {
+            const f32x4* r = (const f32x4*)(base + ((long long)yy * a.W + x) * 3);
+            if (x > 0) xr[ky][0] = r[-1];
 #pragma unroll
-        for (int ci = 0; ci < CIN; ++ci)
-#pragma unroll
-            for (int co = 0; co < COUT; ++co) acc[co] = __builtin_fmaf(x[ci], a.Wp[(tap * 16 + ci) * a.ncols + co], acc[co]);
-    }
-    const int y = ty0 + py, xq = tx0 + px;
-    if (y < a.H && xq < a.W) {
-        const long long pix = (long long)y * a.W + xq;
-        float* o = a.out0 + (long long)(a.out_idx ? a.out_idx[n] : n) * a.out0_nstride + pix * COUT;
-        float v[COUT];
-#pragma unroll
-        for (int co = 0; co < COUT; ++co) {
-            v[co] = tz_relu(acc[co]);
-            if (a.clip1 && v[co] > 1.0f) v[co] = 1.0f;
-            o[co] = v[co];
+            for (int q = 1; q < 4; ++q) xr[ky][q] = r[q - 1];
+            if (x + 4 < a.W) xr[ky][4] = r[3];
         }
-        if (COUT == 3 && a.e0_out) {   // the next step's level-0 error unit, same arithmetic as k_err0
-            const int slot = a.e0_slot[n];
+    }
+    const cfloat bias = (cfloat)(unsigned long long)a.bias;
+    float acc[4][3];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int co = 0; co < 3; ++co) acc[p][co] = bias[co];
+    // A row of taps at a time, 27 weights: all 81 do not fit the scalar registers, and left alone the compiler requests them
+    // all in front of the first multiply-add.  So the address of the next row passes through an empty asm together with the
+    // accumulators behind the first tap of this row: its weights are requested there, no earlier.  Rows of 16 columns:
+    // pack_conv pads Cout = 3 to one tile.
+    unsigned long long wnext = (unsigned long long)a.Wp;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const cfloat wp = (cfloat)wnext;
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+#pragma unroll
+            for (int ci = 0; ci < 3; ++ci) {
+#pragma unroll
+                for (int co = 0; co < 3; ++co) {
+                    const float w = wp[(kx * 16 + ci) * 16 + co];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const int k = 1 + 3 * (p + kx) + ci;
+                        acc[p][co] = __builtin_fmaf(xr[ky][k >> 2][k & 3], w, acc[p][co]);
+                    }
+                }
+            }
+            if (kx == 0 && ky < 2) {
+                wnext = (unsigned long long)(a.Wp + (ky + 1) * 3 * 16 * 16);
+                asm volatile("" : "+s"(wnext), "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[1][2]),
+                             "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[2][2]), "+v"(acc[3][0]), "+v"(acc[3][1]), "+v"(acc[3][2]));
+            }
+        }
+    }
+    {
+        const long long pix = (long long)y * a.W + x;
+        const int frame = a.out_idx ? ((cint)(unsigned long long)a.out_idx)[n] : n;
+        float* o = a.out0 + (long long)frame * a.out0_nstride + pix * 3;
+        float v[4][3];
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int co = 0; co < 3; ++co) {
+                v[p][co] = tz_relu(acc[p][co]);
+                if (a.clip1 && v[p][co] > 1.0f) v[p][co] = 1.0f;
+            }
+        if (((unsigned long long)o & 15) == 0) {   // (uniform: pix is a multiple of 4) the caller's stack may start anywhere
+            f32x4* o4 = (f32x4*)o;
+            o4[0] = (f32x4){v[0][0], v[0][1], v[0][2], v[1][0]};
+            o4[1] = (f32x4){v[1][1], v[1][2], v[2][0], v[2][1]};
+            o4[2] = (f32x4){v[2][2], v[3][0], v[3][1], v[3][2]};
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int co = 0; co < 3; ++co) o[p * 3 + co] = v[p][co];
+        }
+        if (a.e0_out) {   // the next step's level-0 error unit, same arithmetic as k_err0
+            const int slot = ((cint)(unsigned long long)a.e0_slot)[n];
+            float* e = a.e0_out + (long long)(slot >= 0 ? slot : 0) * a.e0_nstride + pix * 8;
             if (slot >= 0 && a.dead_half) {
                 // (uniform) Ahat0_0 = +-0 and v >= +0: e_0 = [+0 | v] bit for bit; the positive quad holds its +0 already
-                float* e = a.e0_out + (long long)slot * a.e0_nstride + pix * 8;
-                *(float4*)(e + 4) = make_float4(v[0], v[1], v[2], 0.0f);
-            } else if (slot >= 0) {
-                float d1[3], d2[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float h = a.e0_ahat[pix * 3 + c];
-                    d1[c] = h - v[c];
-                    d2[c] = v[c] - h;
+                for (int p = 0; p < 4; ++p) *(f32x4*)(e + 8 * p + 4) = (f32x4){v[p][0], v[p][1], v[p][2], 0.0f};
+            } else if (slot >= 0) {
+                const f32x4* h4 = (const f32x4*)(a.e0_ahat + pix * 3);
+                const f32x4 h[3] = {h4[0], h4[1], h4[2]};
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    float d1[3], d2[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float hv = h[(3 * p + c) >> 2][(3 * p + c) & 3];
+                        d1[c] = hv - v[p][c];
+                        d2[c] = v[p][c] - hv;
+                    }
+                    *(f32x4*)(e + 8 * p) = (f32x4){tz_relu(d1[0]), tz_relu(d1[1]), tz_relu(d1[2]), 0.0f};   // (one half per quad: k_err0)
+                    *(f32x4*)(e + 8 * p + 4) = (f32x4){tz_relu(d2[0]), tz_relu(d2[1]), tz_relu(d2[2]), 0.0f};
                 }
-                float* e = a.e0_out + (long long)slot * a.e0_nstride + pix * 8;
-                *(float4*)e = make_float4(tz_relu(d1[0]), tz_relu(d1[1]), tz_relu(d1[2]), 0.0f);   // (one half per quad: k_err0)
-                *(float4*)(e + 4) = make_float4(tz_relu(d2[0]), tz_relu(d2[1]), tz_relu(d2[2]), 0.0f);
             }
         }
     }

@@ -59,9 +59,9 @@ struct PackedConv {
 };
 
 enum { UNI_G0 = 0, UNI_C0 = 1, UNI_AHAT0 = 2 };
-// bits of TEZIP_UNIFORM (measurements: one part at a time; 0 = the per-pixel loads everywhere): k_wino's start values, its cell state
-// and whether tiles that only REPEAT (the reference tile) take theirs
-enum { UNI_USE_WINO_INIT = 1, UNI_USE_WINO_CELL = 2, UNI_USE_TILES = 4, UNI_USE_ALL = 7 };
+// bits of TEZIP_UNIFORM (measurements: one part at a time; 0 = the per-pixel loads everywhere): k_wino's start values, its cell state,
+// whether tiles that only REPEAT (the reference tile) take theirs, and k_l0_gates' start values
+enum { UNI_USE_WINO_INIT = 1, UNI_USE_WINO_CELL = 2, UNI_USE_TILES = 4, UNI_USE_L0_INIT = 8, UNI_USE_ALL = 15 };
 
 struct tz_model {
     int L = 0;
@@ -645,9 +645,9 @@ static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbat
         fullk = fullk && hs * ws * a.src[s].pstride * 4 < (1LL << 32);
     }
     ps.sub = TZP_CONV_GEN;
-    if (epi == EPI_RELU && a.nsrc == 1 && !ups && a.src[0].C == 3 && a.Cout == 3 && ctx->conv_impl) {
+    if (epi == EPI_RELU && a.nsrc == 1 && !ups && a.src[0].C == 3 && a.Cout == 3 && a.ncols == 16 && ctx->conv_impl) {
         ps.sub = TZP_CONV_SMALL;
-        hipLaunchKernelGGL((k_conv_small<3, 3>), dim3(a.tiles_x * a.tiles_y * nbatch), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL((k_conv_small<3, 3>), dim3(conv_small_tiles(a.H, a.W) * nbatch), dim3(256), 0, ctx->stream, a);
         TZ_HIP(ctx, hipGetLastError());
         return TZ_OK;
     }
@@ -655,10 +655,10 @@ static int launch_conv(tz_ctx* ctx, int NT, int epi, const ConvArgs& a, int nbat
     // only while Wblk0 says that the positive half of E_0 is left out (a call that holds the skip off takes k_conv16b).
     // (Counted with k_conv16b, as the level-0 convolutions: the same launches of a step, whichever kernel takes them.)
     if (const tz_model* m = ctx->model; m && ctx->conv_impl && a.nsrc > 0 && a.src[0].pstride == 8) {
-        if (m->l0valu_g && a.Wblk0 && epi == EPI_LSTM_PACKED && ups && a.nsrc == 2 && a.init && a.Wp == m->gate_t1[0].d_W) {
+        if (m->l0valu_g && a.Wblk0 && epi == EPI_LSTM_PACKED && ups && a.nsrc == 2 && a.init && a.ncols == tzl0::NCOLS && a.Wp == m->gate_t1[0].d_W) {
             ps.sub = TZP_CONV16B;
             const int blocks = ((a.W + tzl0::GT - 1) / tzl0::GT) * ((a.H + tzl0::GT - 1) / tzl0::GT) * nbatch;
-            hipLaunchKernelGGL((k_l0_gates<true, 5>), dim3(blocks), dim3(256), 0, ctx->stream, a, m->l0_wg);
+            hipLaunchKernelGGL(k_l0_gates, dim3(blocks), dim3(256), 0, ctx->stream, a, m->l0_wg);
             TZ_HIP(ctx, hipGetLastError());
             return TZ_OK;
         }
@@ -820,8 +820,9 @@ extern "C" int tz_model_load(tz_ctx* ctx, int nb_layers, const int* stack_sizes,
 //   * tring: outside it every 16 x 16 tile equals the REFERENCE tile (the one that holds the centre pixel), which covers any
 //     such period up to 16.  k_wino reads the reference tile in place of a tile inside (ConvArgs::init_tring / aux_tring):
 //     as many loads, all workgroups of a launch from one block.  Valid only if the reference tile itself lies inside.
-// Ahat0_l and level 0 are measured and logged as well; their consumers (the pool / error epilogues, k_conv16b) keep the
-// per-pixel loads: the shortcut measured nothing there (profiles/uniform_constants_2026-10-18.md).
+// Ahat0_l and level 0 are measured and logged as well.  k_l0_gates takes G0_0's row on the 32 x 32 tiles inside its ring
+// (tile32_uniform; a consumer bit of its own, UNI_USE_L0_INIT); the other consumers (the pool / error epilogues, k_conv16b)
+// keep the per-pixel loads: the shortcut measured nothing there (profiles/uniform_constants_2026-10-18.md).
 // TEZIP_UNIFORM (read here, per prepare): 0 = never, else a mask of UNI_USE_*; TEZIP_UNIFORM_LOG=1: one line per level and array.
 static bool tile_inside(int w, int y0, int x0, int H, int W) {   // (tile_uniform of the kernels)
     return w >= 0 && y0 >= w && y0 + 16 <= H - w && x0 >= w && x0 + 16 <= W - w;
@@ -1075,7 +1076,7 @@ static int choose_l0_forms(tz_ctx* ctx, tz_model* m) {
     const bool shape = m->L > 1 && m->stack[0] == 3 && m->rstack[0] == 3 && m->e0s == 8 && m->rstack[1] % 16 == 0;
     const PackedConv& pg = m->gate_t1[0];
     // (k_l0_gates reads the 16-column rows [i | f | g | o] x 3 of pack_conv)
-    const bool form_g = shape && pg.d_Wblk && pg.NT == 1 && pg.ncols == 16 && pg.segs.size() == 2;
+    const bool form_g = shape && pg.d_Wblk && pg.NT == 1 && pg.ncols == tzl0::NCOLS && pg.segs.size() == 2;
     bool zero = false, finite = false;
     if (on && form_g) {
         unsigned long long h_live = 0, *d_live = nullptr;
@@ -1106,9 +1107,9 @@ static int choose_l0_forms(tz_ctx* ctx, tz_model* m) {
         TZ_HIP(ctx, hipMemcpy(m->l0_wg, G.data(), G.size() * 4, hipMemcpyHostToDevice));
         const char* envf = getenv("TEZIP_DEADF");
         m->deadf0 = zero && finite && (!envf || atoi(envf) != 0);
-        // Only the form with everything dead left out is taken: with both halves of E_0 and four gates (bias_scale 0.1, the
-        // trained model) k_l0_gates<false, 6> cost 4.34 ms of a 40.4 ms step where k_conv16b costs 3.56 (EXPERIMENTS.md); the
-        // forms in between were not measured and keep k_conv16b too.
+        // Only the form with everything dead left out exists: with both halves of E_0 and four gates (bias_scale 0.1, the
+        // trained model) a 12-column, two-quad form of k_l0_gates cost 4.34 ms of a 40.4 ms step where k_conv16b costs 3.56
+        // (EXPERIMENTS.md); the forms in between were not measured.  All of them keep k_conv16b.
         m->l0valu_g = m->deadf0 && pg.d_Wblk0 != nullptr;
     }
     if (log) {
@@ -1559,9 +1560,9 @@ static int predict_batch_impl(tz_ctx* ctx, int n, const int* d_idx, int stride, 
         a.auxf = m->C0f[l];
         a.out0_nstride = npx(l) * m->rstack[l];
         a.out0 = m->R1[l] + slot0 * a.out0_nstride;
-        // (k_wino only, levels >= 1: at level 0 and in the pool / error epilogues the shortcut measured nothing,
-        // profiles/uniform_constants_2026-10-18.md)
-        set_uniform(a.init_u, a.init_ring, a.init_tring, UNI_G0, l, l >= 1 ? UNI_USE_WINO_INIT : 0);
+        // (k_wino at levels >= 1 and k_l0_gates' start values at level 0: in k_conv16b and in the pool / error epilogues the
+        // shortcut measured nothing, profiles/uniform_constants_2026-10-18.md; k_conv16b does not look at init_u)
+        set_uniform(a.init_u, a.init_ring, a.init_tring, UNI_G0, l, l >= 1 ? UNI_USE_WINO_INIT : UNI_USE_L0_INIT);
         set_uniform(a.aux_u, a.aux_ring, a.aux_tring, UNI_C0, l, l >= 1 ? UNI_USE_WINO_CELL : 0);
     };
     auto aconv_args = [&](int l, ConvArgs& a) {
