@@ -245,6 +245,26 @@ int tz_set_pred_select(tz_ctx* ctx, int on);
 int tz_get_pred_select(tz_ctx* ctx);
 int tz_pred_modes(tz_ctx* ctx, uint8_t* out, size_t cap);
 int tz_put_pred_modes(tz_ctx* ctx, const uint8_t* modes, size_t n);
+/* ---- motion-compensated tiles, definition TZ-PM1 (no reference counterpart; `tezip.py -c --loop closed --pred motion`, DESIGN.md
+ * section 9, slow statement in tezip_amd/predmotion.py).  TZ-PS1 with another second candidate: the frame in front DISPLACED per tile,
+ *   ref(y, x, c) = dec[t-1][clamp(y + dy, 0, H-1), clamp(x + dx, 0, W-1), c],  -7 <= dy, dx <= 7 (the edge is replicated)
+ *   search      on raw u8 values: SAD(dy, dx) = sum |ref - orig_t| over the tile's samples inside the frame; the tile's vector has
+ *               the smallest SAD * 4096 + (|dy| + |dx|) * 256 + (dy + 7) * 16 + (dx + 7) of all 225
+ *   mode        m = 1 iff sum |Q(ref - orig_t)| < sum |Q(x_net - orig_t)| at that vector; a tie goes to the network.  Tiles of mode 0
+ *               and of key frames have the vector (0, 0).  x, q, dec[t], the feedback and the patched predictions as in TZ-PS1 with
+ *               ref in dec[t-1]'s place.
+ * tz_set_pred_motion(ctx, r): r = 0 (the default, off) or 7.  It excludes tz_set_pred_select(ctx, 1) and the other way round
+ *   (TZ_ERR_INVALID).  Under 0 every launch is what it is without this call.  The setting is part of the closed loop's stamp like
+ *   tz_set_pred_select's.  tz_pred_modes and tz_put_pred_modes serve a motion rollout too.
+ * tz_pred_vectors(ctx, out, cap): after a tz_rollout_closed under motion, 2*nt*TH*TW int8, (dy, dx) per tile in the order of the
+ *   mode bytes.  TZ_ERR_STATE when the resident rollout is not such a rollout, TZ_ERR_INVALID for cap < 2*nt*TH*TW.
+ * tz_put_pred_vectors(ctx, vectors, n): the vectors of the stream, next to tz_put_pred_modes, ahead of a tz_rollout_decode_closed
+ *   under motion (host memory; the context keeps a copy).  TZ_ERR_INVALID for a component outside -7 .. 7, and from the rollout for
+ *   n != 2*nt*TH*TW or a non-zero vector on a tile of mode 0 (a key frame's tiles among them). */
+int tz_set_pred_motion(tz_ctx* ctx, int r);
+int tz_get_pred_motion(tz_ctx* ctx);
+int tz_pred_vectors(tz_ctx* ctx, int8_t* out, size_t cap);
+int tz_put_pred_vectors(tz_ctx* ctx, const int8_t* vectors, size_t n);
 
 /* ---- encoder back half on the context-resident rollout (compress.py:289-373) ---------------
  * payload: nt*H*W*3 int16 = rank(1600 - sd) when bit 0 of `entropy` is set, else sd.

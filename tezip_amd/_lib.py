@@ -64,6 +64,10 @@ _SIGS = {
     "tz_get_pred_select": (C.c_int, [C.c_void_p]),
     "tz_pred_modes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "tz_put_pred_modes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "tz_set_pred_motion": (C.c_int, [C.c_void_p, C.c_int]),
+    "tz_get_pred_motion": (C.c_int, [C.c_void_p]),
+    "tz_pred_vectors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "tz_put_pred_vectors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "tz_range_restart": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "tz_rollout_decode_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p]),
@@ -652,6 +656,27 @@ class Context:
         """tz_put_pred_modes: the stored modes of a stream, ahead of rollout_decode_closed under selection."""
         m = np.ascontiguousarray(modes, np.uint8)
         self._ck(self.lib.tz_put_pred_modes(self.h, m.ctypes.data, m.size))
+
+    def set_pred_motion(self, r):
+        """tz_set_pred_motion (TZ-PM1, tezip_amd/predmotion.py): rollout_closed / rollout_decode_closed choose per 16 x 16 tile
+        between the network's prediction and the decoded frame in front displaced by a vector of up to r = 7 pixels.  0 (the
+        default): off.  Excludes set_pred_select(True)."""
+        self._ck(self.lib.tz_set_pred_motion(self.h, int(r)))
+
+    def get_pred_motion(self):
+        return int(self.lib.tz_get_pred_motion(self.h))
+
+    def pred_vectors(self):
+        """tz_pred_vectors: the vectors of the resident rollout_closed under motion, int8 (nt, ceil(H/16), ceil(W/16), 2) of (dy, dx)."""
+        nt, h, w = self._shape
+        out = np.zeros((nt, (h + 15) // 16, (w + 15) // 16, 2), np.int8)
+        self._ck(self.lib.tz_pred_vectors(self.h, out.ctypes.data, out.size))
+        return out
+
+    def put_pred_vectors(self, vectors):
+        """tz_put_pred_vectors: the stored vectors of a stream, next to put_pred_modes, ahead of rollout_decode_closed under motion."""
+        v = np.ascontiguousarray(vectors, np.int8)
+        self._ck(self.lib.tz_put_pred_vectors(self.h, v.ctypes.data, v.size))
 
     def rollout_decode_range(self, key_frames, warm_up, first, count):
         """tz_rollout_decode for frames [first, first + count) only; key_frames as for rollout_decode.  Returns the key mask

@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, boundmap, closedloop, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, predselect, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
+from . import _lib, boundmap, closedloop, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, predmotion, predselect, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -476,8 +476,9 @@ def _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages=Non
     else:
         tail = np.array([-1], dtype=np.int64)
     one = sdelta.mark(shuffled, plane) if strided or plane else (SHUFFLE_MARK if shuffled else 1)
-    if closed:   # (2: closed-loop prediction with per-tile selection TZ-PS1, tezip_amd/predselect.py: 32 more)
-        one += closedloop.MARK_CLOSED + (predselect.MARK_SELECT if closed == 2 else 0)
+    if closed:   # (2: closed-loop prediction with per-tile selection TZ-PS1, tezip_amd/predselect.py: 32 more; 3: with
+        # motion-compensated tiles TZ-PM1, tezip_amd/predmotion.py: 64 more)
+        one += closedloop.MARK_CLOSED + (predselect.MARK_SELECT if closed == 2 else predmotion.MARK_MOTION if closed == 3 else 0)
     trailer = np.concatenate([tail, [one, nt, H, W, channels], [warm_up]]).astype(np.int16)
     t_e = time.perf_counter()
     if coder in ("huff", "huffr", "huffd"):
@@ -506,7 +507,8 @@ def _stream_outputs(ctx, out_dir, nt, H, W, key, table, warm_up, shuffled, pool,
     pixel (1: a gray job, tezip_amd/graypayload.py); key_frame.dat has three either way.  strided: the payload's spatial delta
     ran at the channel stride, plane: it is the 2-D one, TZ-SD2 (tezip_amd/sdelta.py): the trailer says so in the first entry of
     its shape.  closed: the job ran closed-loop prediction TZ-CL1 (tezip_amd/closedloop.py): that entry is 16 larger; closed == 2:
-    with per-tile selection TZ-PS1 (tezip_amd/predselect.py): 48 larger."""
+    with per-tile selection TZ-PS1 (tezip_amd/predselect.py): 48 larger; closed == 3: with motion-compensated tiles TZ-PM1
+    (tezip_amd/predmotion.py): 80 larger."""
     kf = _key_output(ctx, out_dir, nt, H, W, key, pool, stages, verbose, key_coder)
     esize = _entropy_output(ctx, out_dir, nt, H, W, table, warm_up, shuffled, stages, coder, verbose, channels, strided, plane, closed)
     return kf.result(), esize
@@ -656,7 +658,10 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     in front leaves the smaller quantised residual, definition TZ-PS1 (tezip_amd/predselect.py).  One line says how many tiles
     took the frame in front, a fifth file pred_modes.dat holds one bit per tile, tezip_amd.json records it, and the first entry of
     the trailer's shape is 48 larger than the open-loop mark; `-u` recognises the stream by that mark.  REPORT counts the file in
-    `ratio:` and adds "pred_select" to quality.json.  Everything LOOP "closed" refuses stays refused.
+    `ratio:` and adds "pred_select" to quality.json.  Everything LOOP "closed" refuses stays refused.  Or "motion": the frame in
+    front is displaced per tile by a vector of up to 7 pixels found by a full search, definition TZ-PM1 (tezip_amd/predmotion.py);
+    the line also counts the displaced tiles, pred_modes.dat (format TZP2) also holds one byte per chosen tile, the mark is 80
+    larger than the open-loop one and quality.json gains "pred_motion".
 
     One process: the images stream through a ring of window buffers into HBM while the model loads,
     and key_frame.dat / entropy.dat are written from context-resident data in pieces, so host memory
@@ -695,12 +700,13 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
-    problem = predselect.check_flags(PRED, LOOP)
+    problem = predmotion.check_flags(PRED, LOOP)
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
     closed = LOOP == "closed"
     select = PRED == "select"
+    motion = PRED == "motion"
     if TARGET_PSNR is not None:   # (tezip.py refuses this before any GPU is touched; a caller of run() gets the same answer)
         problem = (target.check_target(TARGET_PSNR) or (TARGET_NEEDS_ABS if MODE != "abs" or BOUND_VALUE else None)
                    or (TARGET_NOT_SHARDED if tzdist.active() is not None else None))
@@ -789,10 +795,15 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 print(closedloop.STDOUT_LINE)
                 if select:   # TZ-PS1: per tile, the network or the decoded frame in front
                     ctx.set_pred_select(True)
+                elif motion:   # TZ-PM1: per tile, the network or the decoded frame in front displaced by the tile's vector
+                    ctx.set_pred_motion(predmotion.RADIUS)
                 key = ctx.rollout_closed(None, PREPROCESS, WINDOW_SIZE, MODE, BOUND_VALUE)
                 if select:
                     modes = ctx.pred_modes()
                     print(predselect.stdout_line(modes[~key]))
+                elif motion:
+                    modes, vectors = ctx.pred_modes(), ctx.pred_vectors()
+                    print(predmotion.stdout_line(modes[~key], vectors[~key]))
             else:
                 key, mse = ctx.rollout(None, PREPROCESS, WINDOW_SIZE, THRESHOLD, want_mse=bool(VERBOSE))
             if VERBOSE:
@@ -892,13 +903,15 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             else:
                 _stream_outputs(ctx, OUTPUT_DIR, nt, H, W, key, table if ENTROPY_RUN else None, PREPROCESS, SHUFFLE, pool, stages,
                                 coder=CODER, verbose=VERBOSE, key_coder=KEY_CODER, channels=channels, strided=strided, plane=plane,
-                                **({"closed": 2 if select else True} if closed else {}))
+                                **({"closed": 3 if motion else 2 if select else True} if closed else {}))
             if select:
                 modes_size = predselect.write(OUTPUT_DIR, modes)
+            elif motion:
+                modes_size = predmotion.write(OUTPUT_DIR, modes, vectors)
             if closed:
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
                                     payload_channels=channels, sdelta=sd_mode, quant=QUANT, loop="closed",
-                                    **({"pred": "select"} if select else {}))
+                                    **({"pred": "select"} if select else {"pred": "motion"} if motion else {}))
             elif bound_map is not None:
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
                                     payload_channels=channels, sdelta=sd_mode, quant=QUANT, bound_map=boundmap.stats(bound_map))
@@ -919,6 +932,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     report["stored_bytes"] += modes_size
                     report["ratio"] = float(report["raw_bytes"]) / float(report["stored_bytes"])
                     report["pred_select"] = {"tiles": int(modes[~key].size), "prev_tiles": int(np.count_nonzero(modes))}
+                elif motion:   # likewise
+                    report["stored_bytes"] += modes_size
+                    report["ratio"] = float(report["raw_bytes"]) / float(report["stored_bytes"])
+                    report["pred_motion"] = {"tiles": int(modes[~key].size), "prev_tiles": int(np.count_nonzero(modes)),
+                                             "displaced_tiles": int(np.count_nonzero(vectors.any(axis=-1)))}
                 if frame_bounds is not None:
                     report["frame_bounds"] = [float(b) for b in frame_bounds]
                 if bound_map is not None:

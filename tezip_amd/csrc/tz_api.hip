@@ -686,7 +686,9 @@ static void set_rollout(tz_ctx* ctx, tz_ctx::tz_rollout_kind kind, int pred_firs
     ctx->rollout_kind = kind;
     ctx->loop_closed = 0;   // (tz_rollout_closed stamps its loop behind this)
     ctx->loop_select = 0;
+    ctx->loop_motion = 0;
     ctx->pred_modes.clear();
+    ctx->pred_vectors.clear();
     ctx->pred_first = pred_first;
     ctx->pred_end = pred_end;
 }
@@ -1552,6 +1554,11 @@ static int loop_check(tz_ctx* ctx, const char* who, int mode, double b0, double 
                        "%s: the resident predictions are those of a closed loop (tz_rollout_closed) run %s per-tile selection "
                        "(tz_set_pred_select(%d)); they serve that kind of job alone, the setting is now %d",
                        who, ctx->loop_select ? "with" : "without", ctx->loop_select, ctx->pred_select);
+    if (ctx->loop_motion != ctx->pred_motion)   // TZ-PM1: likewise
+        return tz_fail(ctx, TZ_ERR_STATE,
+                       "%s: the resident predictions are those of a closed loop (tz_rollout_closed) run %s motion-compensated tiles "
+                       "(tz_set_pred_motion(%d)); they serve that kind of job alone, the setting is now %d",
+                       who, ctx->loop_motion ? "with" : "without", ctx->loop_motion, ctx->pred_motion);
     const bool same = mode == ctx->loop_mode && b0 == ctx->loop_b0 && (mode != TZ_MODE_ABSREL || b1 == ctx->loop_b1) &&
                       ctx->quantiser == ctx->loop_quantiser;
     if (same && ctx->frame_bounds.empty() && !ctx->map_h && ctx->payload_channels == 3) return TZ_OK;
@@ -2224,6 +2231,8 @@ static int select_modes(tz_call& call, size_t n, const uint8_t* host, uint8_t** 
 extern "C" int tz_set_pred_select(tz_ctx* ctx, int on) {
     if (!ctx) return TZ_ERR_INVALID;
     if (on != 0 && on != 1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_pred_select takes 0 or 1, not %d", on);
+    if (on && ctx->pred_motion)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_pred_select(1) while tz_set_pred_motion(%d) is in force: a tile has one second candidate", ctx->pred_motion);
     if (on != ctx->pred_select) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under the other setting
     ctx->pred_select = on;
     return TZ_OK;
@@ -2233,7 +2242,9 @@ extern "C" int tz_get_pred_select(tz_ctx* ctx) { return ctx ? ctx->pred_select :
 
 extern "C" int tz_pred_modes(tz_ctx* ctx, uint8_t* out, size_t cap) {
     if (!ctx) return TZ_ERR_INVALID;
-    if (!ctx->loop_closed || !ctx->loop_select)
+    if ((!ctx->loop_closed || !ctx->loop_motion) && ctx->pred_motion)   // (asked for under motion: say so; else the message as it was)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_pred_modes: the resident rollout is no tz_rollout_closed under tz_set_pred_motion(7)");
+    if (!ctx->loop_closed || (!ctx->loop_select && !ctx->loop_motion))
         return tz_fail(ctx, TZ_ERR_STATE, "tz_pred_modes: the resident rollout is no tz_rollout_closed under tz_set_pred_select(1)");
     const size_t n = ctx->pred_modes.size();
     if (!out || cap < n) return tz_fail(ctx, TZ_ERR_INVALID, "tz_pred_modes: room for %zu mode bytes, the rollout has %zu", out ? cap : (size_t)0, n);
@@ -2248,6 +2259,48 @@ extern "C" int tz_put_pred_modes(tz_ctx* ctx, const uint8_t* modes, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (modes[i] > 1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_put_pred_modes: mode byte %zu is %d, 0 or 1 wanted", i, (int)modes[i]);
     ctx->put_modes.assign(modes, modes + n);
+    return TZ_OK;
+}
+
+// ---- motion-compensated tiles, definition TZ-PM1 (include/tezip_hip.h: tz_set_pred_motion; slow statement in
+// tezip_amd/predmotion.py): TZ-PS1's mode bytes plus one vector (dy, dx) per tile, 2 * select_count int8
+static int motion_vectors(tz_call& call, size_t n, const int8_t* host, int8_t** d_vecs) {
+    TZ_TRY(call.alloc(std::max<size_t>(n, 1), d_vecs));
+    if (host) return tz_upload(call.ctx, *d_vecs, host, n);
+    if (hipMemsetAsync(*d_vecs, 0, n, call.ctx->stream) != hipSuccess) return tz_fail(call.ctx, TZ_ERR_HIP, "clearing the vectors failed");
+    return TZ_OK;
+}
+
+extern "C" int tz_set_pred_motion(tz_ctx* ctx, int r) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (r != 0 && r != 7) return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_pred_motion takes 0 (off) or the search radius 7, not %d", r);
+    if (r && ctx->pred_select)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_pred_motion(%d) while tz_set_pred_select(1) is in force: a tile has one second candidate", r);
+    if (r != ctx->pred_motion) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under the other setting
+    ctx->pred_motion = r;
+    return TZ_OK;
+}
+
+extern "C" int tz_get_pred_motion(tz_ctx* ctx) { return ctx ? ctx->pred_motion : TZ_ERR_INVALID; }
+
+extern "C" int tz_pred_vectors(tz_ctx* ctx, int8_t* out, size_t cap) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (!ctx->loop_closed || !ctx->loop_motion)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_pred_vectors: the resident rollout is no tz_rollout_closed under tz_set_pred_motion(7)");
+    const size_t n = ctx->pred_vectors.size();
+    if (!out || cap < n) return tz_fail(ctx, TZ_ERR_INVALID, "tz_pred_vectors: room for %zu vector components, the rollout has %zu", out ? cap : (size_t)0, n);
+    memcpy(out, ctx->pred_vectors.data(), n);
+    return TZ_OK;
+}
+
+extern "C" int tz_put_pred_vectors(tz_ctx* ctx, const int8_t* vectors, size_t n) {
+    if (!ctx) return TZ_ERR_INVALID;
+    ctx->put_vectors.clear();
+    if (!vectors || !n) return tz_fail(ctx, TZ_ERR_INVALID, "tz_put_pred_vectors: no vectors");
+    for (size_t i = 0; i < n; ++i)
+        if (vectors[i] < -7 || vectors[i] > 7)
+            return tz_fail(ctx, TZ_ERR_INVALID, "tz_put_pred_vectors: component %zu is %d, -7 .. 7 wanted", i, (int)vectors[i]);
+    ctx->put_vectors.assign(vectors, vectors + n);
     return TZ_OK;
 }
 
@@ -2274,9 +2327,10 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
     if (ctx->payload_channels != 3 || !ctx->frame_bounds.empty() || ctx->map_h)
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: the closed loop takes one bound and a three-channel payload (no tz_set_payload_channels(1), tz_set_frame_bounds or tz_set_bound_map)");
     const int p = warm_up;
-    const bool select = ctx->pred_select != 0;
+    const bool select = ctx->pred_select != 0, motion = ctx->pred_motion != 0;
     const size_t nmodes = select_count(nt, H, W);
     uint8_t* d_modes = nullptr;
+    int8_t* d_vecs = nullptr;
     tz_call call(ctx);
     TZ_TRY(rollout_setup(ctx, frames, nt, H, W, warm_up));   // (the whole stack goes up ahead: every frame is read by a step)
     // key mask and groups of the open-loop SWP job (rollout_swp; compress.py:188-220, 249-262)
@@ -2310,6 +2364,12 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
             rc = closed_lists(call, steps, &d_all);
             if (rc == TZ_OK) rc = select_modes(call, nmodes, nullptr, &d_modes);
             if (rc == TZ_OK) rc = tzk_ps_select(ctx, ctx->d_pred, ctx->d_frames, d_modes, d_all, (int)all.size(), H, W, ctx->Hp, ctx->Wp);
+        } else if (rc == TZ_OK && motion) {   // TZ-PM1: likewise, with the search
+            const int* d_all = nullptr;
+            rc = closed_lists(call, steps, &d_all);
+            if (rc == TZ_OK) rc = select_modes(call, nmodes, nullptr, &d_modes);
+            if (rc == TZ_OK) rc = motion_vectors(call, 2 * nmodes, nullptr, &d_vecs);
+            if (rc == TZ_OK) rc = tzk_pm_select(ctx, ctx->d_pred, ctx->d_frames, d_modes, d_vecs, d_all, (int)all.size(), H, W, ctx->Hp, ctx->Wp);
         }
     } else if (rc == TZ_OK) {
         const size_t fb = (size_t)nt * H * W * 3;
@@ -2318,7 +2378,8 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
         const int* d_lists = nullptr;
         rc = call.alloc(fb, &d_dec);
         if (rc == TZ_OK) rc = closed_lists(call, steps, &d_lists);
-        if (rc == TZ_OK && select) rc = select_modes(call, nmodes, nullptr, &d_modes);
+        if (rc == TZ_OK && (select || motion)) rc = select_modes(call, nmodes, nullptr, &d_modes);
+        if (rc == TZ_OK && motion) rc = motion_vectors(call, 2 * nmodes, nullptr, &d_vecs);
         if (rc == TZ_OK && hipMemcpyAsync(d_dec, ctx->d_frames, fb, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)   // the key frames
             rc = tz_fail(ctx, TZ_ERR_HIP, "tz_rollout_closed: copy of the frame stack failed");
         size_t at = 0;
@@ -2326,12 +2387,16 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
             rc = closed_predict(ctx, steps[s], d_dec);
             if (rc == TZ_OK && select)   // TZ-PS1 in the step's place: the mode bytes, the chosen tiles in the predictions, dec[t]
                 rc = tzk_ps_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_modes, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp, E);
+            else if (rc == TZ_OK && motion)   // TZ-PM1 in the step's place: also the vectors
+                rc = tzk_pm_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_modes, d_vecs, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp, E);
             else if (rc == TZ_OK)
                 rc = tzk_cl_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp, E);
         }
     }
-    std::vector<uint8_t> modes(select ? nmodes : 0);
-    if (rc == TZ_OK && select) rc = tz_d2h(ctx, modes.data(), d_modes, nmodes, ctx->stream);
+    std::vector<uint8_t> modes(select || motion ? nmodes : 0);
+    std::vector<int8_t> vectors(motion ? 2 * nmodes : 0);
+    if (rc == TZ_OK && (select || motion)) rc = tz_d2h(ctx, modes.data(), d_modes, nmodes, ctx->stream);
+    if (rc == TZ_OK && motion) rc = tz_d2h(ctx, vectors.data(), d_vecs, 2 * nmodes, ctx->stream);
     if (rc == TZ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "closed-loop rollout failed");
     if (rc != TZ_OK) {  // nothing of a failed rollout may still read the caller's frames when we return
         (void)hipStreamSynchronize(ctx->copy_stream);
@@ -2349,7 +2414,9 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
     ctx->loop_b1 = b1;
     ctx->loop_quantiser = ctx->quantiser;
     ctx->loop_select = select ? 1 : 0;
+    ctx->loop_motion = motion ? ctx->pred_motion : 0;
     ctx->pred_modes.swap(modes);
+    ctx->pred_vectors.swap(vectors);
     if (key_mask) memcpy(key_mask, key.data(), nt);
     return TZ_OK;
 }
@@ -2367,10 +2434,16 @@ extern "C" int tz_rollout_decode_closed(tz_ctx* ctx, const uint8_t* key_frames, 
     if (ctx->payload_channels != 3)
         return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_decode_closed does not serve a one-channel payload (tz_set_payload_channels(1))");
     TZ_TRY(check_table(ctx, table, table_len));
-    const bool select = ctx->pred_select != 0;
+    const bool select = ctx->pred_select != 0, motion = ctx->pred_motion != 0;
     if (select && nt > 0 && H > 0 && W > 0 && ctx->put_modes.size() != select_count(nt, H, W))
         return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_decode_closed under tz_set_pred_select(1): %zu mode bytes were put (tz_put_pred_modes), "
                        "the stack has %zu tiles", ctx->put_modes.size(), select_count(nt, H, W));
+    if (motion && nt > 0 && H > 0 && W > 0 && ctx->put_modes.size() != select_count(nt, H, W))
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_decode_closed under tz_set_pred_motion(%d): %zu mode bytes were put (tz_put_pred_modes), "
+                       "the stack has %zu tiles", ctx->pred_motion, ctx->put_modes.size(), select_count(nt, H, W));
+    if (motion && nt > 0 && H > 0 && W > 0 && ctx->put_vectors.size() != 2 * select_count(nt, H, W))
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_decode_closed under tz_set_pred_motion(%d): %zu vector components were put "
+                       "(tz_put_pred_vectors), the stack has %zu tiles of two", ctx->pred_motion, ctx->put_vectors.size(), select_count(nt, H, W));
     ctx->have_decoded = false;
     tz_call call(ctx);
     TZ_TRY(rollout_setup(ctx, key_frames, nt, H, W, warm_up));
@@ -2407,7 +2480,19 @@ extern "C" int tz_rollout_decode_closed(tz_ctx* ctx, const uint8_t* key_frames, 
     const std::vector<std::vector<int>> steps = closed_steps(key);
     TZ_TRY(closed_lists(call, steps, &d_lists));
     uint8_t* d_modes = nullptr;
-    if (select) {   // TZ-PS1: the stored modes, now that the keys are known
+    int8_t* d_vecs = nullptr;
+    if (motion) {   // TZ-PM1: a vector belongs to a tile of mode 1, and a key frame has none
+        const size_t per = select_count(1, H, W);
+        for (int i = 0; i < nt; ++i)
+            if (key[i] && std::any_of(ctx->put_vectors.begin() + 2 * i * per, ctx->put_vectors.begin() + 2 * (i + 1) * per, [](int8_t v) { return v != 0; }))
+                return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_decode_closed: a vector of key frame %d is non-zero (key frames are stored exactly)", i);
+        for (size_t i = 0; i < ctx->put_modes.size(); ++i)
+            if (!ctx->put_modes[i] && (ctx->put_vectors[2 * i] || ctx->put_vectors[2 * i + 1]))
+                return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_decode_closed: tile %zu has mode 0 and the vector (%d, %d): only a tile taken from "
+                               "the frame in front is displaced", i, (int)ctx->put_vectors[2 * i], (int)ctx->put_vectors[2 * i + 1]);
+        TZ_TRY(motion_vectors(call, ctx->put_vectors.size(), ctx->put_vectors.data(), &d_vecs));
+    }
+    if (select || motion) {   // TZ-PS1: the stored modes, now that the keys are known
         const size_t per = select_count(1, H, W);
         for (int i = 0; i < nt; ++i)
             if (key[i] && std::any_of(ctx->put_modes.begin() + i * per, ctx->put_modes.begin() + (i + 1) * per, [](uint8_t m) { return m != 0; }))
@@ -2417,7 +2502,8 @@ extern "C" int tz_rollout_decode_closed(tz_ctx* ctx, const uint8_t* key_frames, 
     size_t at = 0;
     for (size_t s = 0; s < steps.size(); at += steps[s].size(), ++s) {
         TZ_TRY(closed_predict(ctx, steps[s], ctx->d_out));
-        if (select) TZ_TRY(tzk_ps_recon(ctx, ctx->d_pred, d_q, ctx->d_out, d_modes, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp));
+        if (motion) TZ_TRY(tzk_pm_recon(ctx, ctx->d_pred, d_q, ctx->d_out, d_modes, d_vecs, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp));
+        else if (select) TZ_TRY(tzk_ps_recon(ctx, ctx->d_pred, d_q, ctx->d_out, d_modes, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp));
         else TZ_TRY(tzk_cl_recon(ctx, ctx->d_pred, d_q, ctx->d_out, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp));
     }
     TZ_TRY(tz_stream_sync(ctx));

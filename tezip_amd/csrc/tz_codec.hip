@@ -6011,3 +6011,227 @@ int tzk_ps_recon(tz_ctx* ctx, float* pred, const int16_t* q, uint8_t* dec, const
                  int Hp, int Wp) {
     return ps_launch(ctx, PS_RECON, pred, nullptr, q, dec, const_cast<uint8_t*>(modes), d_list, nlist, H, W, Hp, Wp, 0);
 }
+
+// ------------------------------------------------------------------------ motion-compensated tiles (TZ-PM1)
+// tz_set_pred_motion (include/tezip_hip.h; slow statement in tezip_amd/predmotion.py): TZ-PS1's tiles and
+// modes, but the second candidate is the frame in front DISPLACED by a vector (dy, dx), -7 <= dy, dx <= 7, found per tile:
+//   ref(y, x, c) = prev[clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1), c];  SAD(dy, dx) = sum |ref - orig| over the tile's
+//   samples inside H x W (raw u8 values: the search does not depend on the quantiser);  the vector is the one with the smallest
+//   key = SAD * 4096 + (|dy| + |dx|) * 256 + (dy + 7) * 16 + (dx + 7) (below 2^30; no two vectors share a key, so the minimum does
+//   not depend on the order of the reduction);  mode 1 iff sum |Q(ref - orig)| < sum |Q(x_net - orig)|, a tie goes to the network.
+// A chosen tile is expressed in the prediction stack as ps_pv(ref); a tile of mode 0 has vector (0, 0).
+//   k_pm_select (lossless encoder)     prev = orig[t-1], Q the identity: mode byte, vector, patched pred
+//   k_pm_step   (lossy encoder)        prev = dec[t-1], Q = TZ-QL1(E): mode byte, vector, patched pred and dec[t]
+//   k_pm_recon  (decoder)              mode byte and vector pick x (a gather, no search): dec[t] = clamp(x - q, 0, 255), patched pred
+// Mapping: a workgroup of 256 lanes owns one tile; blockIdx.y walks `list`, blockIdx.x the tiles of a frame in a grid-stride loop
+// (at most PM_GRID workgroups a frame).  The encoders stage the tile of orig (16 rows of 12 words, samples outside the frame as 0)
+// and the 30 x 30 pixel window of prev around it (30 rows of 90 bytes in a pitch of 23 words, coordinates clamped WHILE staging:
+// the search has no bounds logic) in LDS.  Lanes 0 .. 224 own one vector each: per tile row 12 words of the window at byte
+// offset (dx + 7) * 3, each formed from two aligned LDS words by v_alignbyte_b32, against the 12 words of orig with v_sad_u8; a
+// ragged tile limits the rows and the words and masks the last word.  The minimum key is taken per wave by __shfl_xor and over
+// the waves by an LDS atomic.  Then lane (row, pixel) forms its three samples of x_net and of ref (from the LDS window), the two
+// costs are summed as in ps_strips, and lane 0 writes mode and vector.  One path serves every W and alignment: the u8 stacks are
+// read and written byte by byte (the window's left edge, (x0 - 7) * 3 bytes, is on no word boundary anyway).
+enum { PM_SELECT = 0, PM_STEP = 1 };
+constexpr int PM_R = 7, PM_WIN = PS_TILE + 2 * PM_R, PM_ROWW = 23, PM_GRID = 128;
+
+template <int KIND>
+__device__ __forceinline__ void pm_tiles(float* pred, const uint8_t* __restrict__ orig, const uint8_t* prev, uint8_t* dec, uint8_t* modes,
+                                         int8_t* vecs, const int* __restrict__ list, int H, int W, int Hp, int Wp, int TH, int TW, int E) {
+    __shared__ unsigned s_o[PS_TILE * 12];
+    __shared__ unsigned s_r[PM_WIN * PM_ROWW];
+    __shared__ unsigned s_key;
+    __shared__ unsigned s_cost[4][2];
+    const int f = list[blockIdx.y];
+    const unsigned row = (unsigned)W * 3u, pitch = (unsigned)Wp * 3u;
+    const size_t fe = (size_t)H * row;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int ly = tid >> 4, lx = tid & 15;               // the lane's pixel inside the tile
+    const uint8_t* pframe = prev + (size_t)(f - 1) * fe;  // (a predicted frame has a frame in front: frame 0 is a key frame)
+    uint8_t* ob = (uint8_t*)s_o;
+    uint8_t* rb = (uint8_t*)s_r;
+    for (int t = blockIdx.x; t < TH * TW; t += gridDim.x) {
+        const int ty = t / TW, tx = t - ty * TW;
+        const int y0 = ty * PS_TILE, x0 = tx * PS_TILE;
+        const int nrows = min(PS_TILE, H - y0), nbytes = min(PS_TILE, W - x0) * 3;   // what the tile owns
+        const int nwords = (nbytes + 3) >> 2;
+        const unsigned lastmask = (nbytes & 3) ? (1u << (8 * (nbytes & 3))) - 1u : 0xFFFFFFFFu;
+        const int y = y0 + ly, x = x0 + lx;
+        const bool active = y < H && x < W;
+        const size_t at = active ? (size_t)f * fe + (size_t)y * row + (size_t)x * 3 : 0;   // (formed inside the frame only)
+        int o[3] = {0, 0, 0};
+        if (active) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = (int)orig[at + c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ob[ly * 48 + lx * 3 + c] = (uint8_t)o[c];
+        for (int i = tid; i < PM_WIN * PM_ROWW * 4; i += 256) {
+            const int r = i / (PM_ROWW * 4), b = i - r * (PM_ROWW * 4);
+            const int px = b / 3, c = b - px * 3;
+            const int yy = min(max(y0 - PM_R + r, 0), H - 1), xx = min(max(x0 - PM_R + px, 0), W - 1);
+            rb[i] = b < PM_WIN * 3 ? pframe[(size_t)yy * row + (size_t)xx * 3 + c] : (uint8_t)0;
+        }
+        if (tid == 0) s_key = 0xFFFFFFFFu;
+        __syncthreads();
+        unsigned key = 0xFFFFFFFFu;                         // (idle lanes)
+        if (tid < (2 * PM_R + 1) * (2 * PM_R + 1)) {
+            const int vy = tid / (2 * PM_R + 1), vx = tid - vy * (2 * PM_R + 1);
+            const int dy = vy - PM_R, dx = vx - PM_R;
+            const int off = vx * 3, wb = off >> 2;
+            const unsigned sh = (unsigned)(off & 3);
+            unsigned sad = 0;
+            for (int r = 0; r < nrows; ++r) {
+                const unsigned* rw = s_r + (r + vy) * PM_ROWW + wb;   // window row r + dy + 7
+                const unsigned* ow = s_o + r * 12;
+                unsigned lo = rw[0];
+                for (int j = 0; j < nwords; ++j) {
+                    const unsigned hi = rw[j + 1];                    // (at most word 10 + 12 = 22 of the row's 23)
+                    unsigned wv = __builtin_amdgcn_alignbyte(hi, lo, sh);
+                    if (j == nwords - 1) wv &= lastmask;
+                    sad = __builtin_amdgcn_sad_u8(wv, ow[j], sad);
+                    lo = hi;
+                }
+            }
+            key = sad * 4096u + (unsigned)((dy < 0 ? -dy : dy) + (dx < 0 ? -dx : dx)) * 256u + (unsigned)vy * 16u + (unsigned)vx;
+        }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) key = min(key, (unsigned)__shfl_xor((int)key, d));
+        if (lane == 0) atomicMin(&s_key, key);
+        __syncthreads();
+        key = s_key;
+        const int vy = (int)((key >> 4) & 15u), vx = (int)(key & 15u);
+        int xn[3] = {0, 0, 0}, v[3] = {0, 0, 0};
+        float* pf = active ? pred + (size_t)f * Hp * pitch + (size_t)y * pitch + (size_t)x * 3 : pred;
+        unsigned cn = 0, cp = 0;
+        if (active) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                xn[c] = (int)(pf[c] * 255.0f);
+                v[c] = (int)rb[(ly + vy) * (PM_ROWW * 4) + (lx + vx) * 3 + c];
+                const int qn = ps_quant(xn[c] - o[c], E), qp = ps_quant(v[c] - o[c], E);
+                cn += (unsigned)(qn < 0 ? -qn : qn);
+                cp += (unsigned)(qp < 0 ? -qp : qp);
+            }
+        }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            cn += (unsigned)__shfl_xor((int)cn, d);
+            cp += (unsigned)__shfl_xor((int)cp, d);
+        }
+        if (lane == 0) {
+            s_cost[wave][0] = cn;
+            s_cost[wave][1] = cp;
+        }
+        __syncthreads();
+        cn = s_cost[0][0] + s_cost[1][0] + s_cost[2][0] + s_cost[3][0];
+        cp = s_cost[0][1] + s_cost[1][1] + s_cost[2][1] + s_cost[3][1];
+        const bool m = cp < cn;                             // a tie goes to the network
+        if (tid == 0) {
+            const size_t ti = ((size_t)f * TH + ty) * TW + tx;
+            modes[ti] = m ? 1 : 0;
+            vecs[2 * ti] = (int8_t)(m ? vy - PM_R : 0);
+            vecs[2 * ti + 1] = (int8_t)(m ? vx - PM_R : 0);
+        }
+        if (active) {
+            if (KIND == PM_STEP) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int xv = m ? v[c] : xn[c], r = xv - ps_quant(xv - o[c], E);
+                    dec[at + c] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
+                }
+            }
+            if (m) {   // the chosen tile in the prediction stack: pv of the displaced frame in front, inside H x W only
+#pragma unroll
+                for (int c = 0; c < 3; ++c) pf[c] = ps_pv((unsigned)v[c]);
+            }
+        }
+        __syncthreads();                                    // the next trip stages into the same LDS
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pm_select(float* pred, const uint8_t* orig, uint8_t* modes, int8_t* vecs, const int* __restrict__ list,
+                                                   int H, int W, int Hp, int Wp, int TH, int TW) {
+    pm_tiles<PM_SELECT>(pred, orig, orig, nullptr, modes, vecs, list, H, W, Hp, Wp, TH, TW, 0);
+}
+
+__global__ __launch_bounds__(256) void k_pm_step(float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, int8_t* vecs,
+                                                 const int* __restrict__ list, int H, int W, int Hp, int Wp, int TH, int TW, int E) {
+    pm_tiles<PM_STEP>(pred, orig, dec, dec, modes, vecs, list, H, W, Hp, Wp, TH, TW, E);
+}
+
+// the decoder: lane (row, pixel) of a tile's workgroup gathers its three displaced samples of dec[t-1] where the mode byte is set
+__global__ __launch_bounds__(256) void k_pm_recon(float* pred, const int16_t* __restrict__ qs, uint8_t* dec, const uint8_t* __restrict__ modes,
+                                                  const int8_t* __restrict__ vecs, const int* __restrict__ list, int H, int W, int Hp, int Wp,
+                                                  int TH, int TW) {
+    const int f = list[blockIdx.y];
+    const unsigned row = (unsigned)W * 3u, pitch = (unsigned)Wp * 3u;
+    const size_t fe = (size_t)H * row;
+    const int ly = threadIdx.x >> 4, lx = threadIdx.x & 15;
+    for (int t = blockIdx.x; t < TH * TW; t += gridDim.x) {
+        const int ty = t / TW, tx = t - ty * TW;
+        const int y = ty * PS_TILE + ly, x = tx * PS_TILE + lx;
+        if (y >= H || x >= W) continue;
+        const size_t ti = ((size_t)f * TH + ty) * TW + tx;
+        const bool m = modes[ti] != 0;
+        const size_t at = (size_t)f * fe + (size_t)y * row + (size_t)x * 3;
+        float* pf = pred + (size_t)f * Hp * pitch + (size_t)y * pitch + (size_t)x * 3;
+        int xv[3];
+        if (m) {
+            const int yy = min(max(y + (int)vecs[2 * ti], 0), H - 1), xx = min(max(x + (int)vecs[2 * ti + 1], 0), W - 1);
+            const uint8_t* src = dec + (size_t)(f - 1) * fe + (size_t)yy * row + (size_t)xx * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                xv[c] = (int)src[c];
+                pf[c] = ps_pv((unsigned)xv[c]);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) xv[c] = (int)(pf[c] * 255.0f);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int r = xv[c] - (int)qs[at + c];
+            dec[at + c] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
+        }
+    }
+}
+
+int tzk_pm_grid(int H, int W) {
+    const int TH = (H + PS_TILE - 1) / PS_TILE, TW = (W + PS_TILE - 1) / PS_TILE;
+    return std::min(TH * TW, (int)PM_GRID);
+}
+
+// d_list: nlist sequence indices (device); every stack is the whole sequence's; modes: nt * TH * TW bytes, vecs: twice that (device).
+int tzk_pm_select(tz_ctx* ctx, float* pred, const uint8_t* orig, uint8_t* modes, int8_t* vecs, const int* d_list, int nlist, int H, int W,
+                  int Hp, int Wp) {
+    if (nlist <= 0) return TZ_OK;
+    const int TH = (H + PS_TILE - 1) / PS_TILE, TW = (W + PS_TILE - 1) / PS_TILE;
+    tz_prof_scope ps(ctx, TZP_QUANT);
+    hipLaunchKernelGGL(k_pm_select, dim3((unsigned)tzk_pm_grid(H, W), (unsigned)nlist), dim3(256), 0, ctx->stream, pred, orig, modes, vecs, d_list,
+                       H, W, Hp, Wp, TH, TW);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+int tzk_pm_step(tz_ctx* ctx, float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, int8_t* vecs, const int* d_list, int nlist, int H,
+                int W, int Hp, int Wp, int E) {
+    if (nlist <= 0) return TZ_OK;
+    const int TH = (H + PS_TILE - 1) / PS_TILE, TW = (W + PS_TILE - 1) / PS_TILE;
+    tz_prof_scope ps(ctx, TZP_QUANT);
+    hipLaunchKernelGGL(k_pm_step, dim3((unsigned)tzk_pm_grid(H, W), (unsigned)nlist), dim3(256), 0, ctx->stream, pred, orig, dec, modes, vecs,
+                       d_list, H, W, Hp, Wp, TH, TW, E);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+int tzk_pm_recon(tz_ctx* ctx, float* pred, const int16_t* q, uint8_t* dec, const uint8_t* modes, const int8_t* vecs, const int* d_list,
+                 int nlist, int H, int W, int Hp, int Wp) {
+    if (nlist <= 0) return TZ_OK;
+    const int TH = (H + PS_TILE - 1) / PS_TILE, TW = (W + PS_TILE - 1) / PS_TILE;
+    tz_prof_scope ps(ctx, TZP_RECON);
+    hipLaunchKernelGGL(k_pm_recon, dim3((unsigned)tzk_pm_grid(H, W), (unsigned)nlist), dim3(256), 0, ctx->stream, pred, q, dec, modes, vecs,
+                       d_list, H, W, Hp, Wp, TH, TW);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}

@@ -94,6 +94,10 @@ struct tz_ctx {
     // tz_pred_modes), and the modes a decoder was given (tz_put_pred_modes) for its next tz_rollout_decode_closed
     int pred_select = 0, loop_select = 0;
     std::vector<uint8_t> pred_modes, put_modes;
+    // tz_set_pred_motion (TZ-PM1): the search radius (0: off, 7), the radius the stamped loop ran under (part of the stamp like
+    // loop_select), its vectors (2 * nt * TH * TW int8 (dy, dx), tz_pred_vectors) and a decoder's (tz_put_pred_vectors)
+    int pred_motion = 0, loop_motion = 0;
+    std::vector<int8_t> pred_vectors, put_vectors;
     // pinned staging ring for small host->device uploads (index arrays, masks, LUTs): the copy
     // out of it is truly asynchronous and the memory outlives the caller's locals
     uint8_t* ring = nullptr;
@@ -514,6 +518,17 @@ int tzk_ps_step(tz_ctx*, float* pred, const uint8_t* orig, uint8_t* dec, uint8_t
 int tzk_ps_recon(tz_ctx*, float* pred, const int16_t* q, uint8_t* dec, const uint8_t* modes, const int* d_list, int nlist, int H, int W,
                  int Hp, int Wp);
 int tzk_ps_grid(int H, int W);
+// motion-compensated tiles TZ-PM1 (tezip_amd/predmotion.py): as the three above, but the second candidate is the frame in front
+// displaced by the tile's vector, -7 <= dy, dx <= 7 with clamped coordinates, found by a full search on raw u8 values (smallest
+// SAD * 4096 + (|dy| + |dx|) * 256 + (dy + 7) * 16 + (dx + 7)).  vecs: 2 * nt * TH * TW int8 (dy, dx) on the device, (0, 0) where
+// the mode byte is 0; the encoders write them, tzk_pm_recon reads them.  tzk_pm_grid: the workgroups a frame's launch starts.
+int tzk_pm_select(tz_ctx*, float* pred, const uint8_t* orig, uint8_t* modes, int8_t* vecs, const int* d_list, int nlist, int H, int W, int Hp,
+                  int Wp);
+int tzk_pm_step(tz_ctx*, float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, int8_t* vecs, const int* d_list, int nlist, int H,
+                int W, int Hp, int Wp, int E);
+int tzk_pm_recon(tz_ctx*, float* pred, const int16_t* q, uint8_t* dec, const uint8_t* modes, const int8_t* vecs, const int* d_list, int nlist,
+                 int H, int W, int Hp, int Wp);
+int tzk_pm_grid(int H, int W);
 int tzk_sse(tz_ctx*, const uint8_t* orig, const float* pred, int nframes, int H, int W, int Hp, int Wp,
             double* h_sse);
 int tzk_sse_blocks(int Hp, int Wp);

@@ -9,7 +9,7 @@ import time
 
 import numpy as np
 
-from . import _lib, closedloop, digest, huff, huffd, huffr, keycoder, keycoderg, predselect, sidecar, zstd
+from . import _lib, closedloop, digest, huff, huffd, huffr, keycoder, keycoderg, predmotion, predselect, sidecar, zstd
 from . import dist as tzdist
 from . import sdelta
 from .compress import SHUFFLE_MARK, make_context, open_model
@@ -96,32 +96,62 @@ def check_loop(data_dir, one):
 def early_pred_modes(data_dir):
     """pred_modes.dat of a stream whose sidecar states per-tile selection (TZ-PS1, tezip_amd/predselect.py) and the stack, read
     and validated against that stack before a GPU is touched -> the modes, or None when the sidecar says nothing of it (the
-    trailer's mark decides then, in check_pred).  ValueError for a missing or malformed file."""
+    trailer's mark decides then, in stream_pred).  ValueError for a missing or malformed file.  A sidecar that states
+    motion-compensated tiles (TZ-PM1, tezip_amd/predmotion.py): likewise with that definition's format TZP2."""
     doc = sidecar.read(data_dir)
     stack = sidecar.stack_of(doc)
-    if sidecar.pred_of(doc) != "select" or stack is None:
+    pred = sidecar.pred_of(doc)
+    if pred not in ("select", "motion") or stack is None:
         return None
+    if pred == "motion":
+        return predmotion.read(data_dir, stack[0], stack[1], stack[2])[0]
     return predselect.read(data_dir, stack[0], stack[1], stack[2])
 
 
-def check_pred(data_dir, one, nt, H, W):
-    """What entropy.dat's trailer states about per-tile selection (the closed-loop mark plus 32) against tezip_amd.json, which
-    records "select" and says nothing otherwise.  The trailer is authoritative; a sidecar that contradicts it belongs to another
-    stream.  Returns the modes of pred_modes.dat, validated against the trailer's stack, or None for a stream without selection."""
-    have = "select" if predselect.is_select(one) else "net"
+def stream_pred(data_dir, one, nt, H, W):
+    """What entropy.dat's trailer states about the prediction of a tile -- the closed-loop mark plus 32: per-tile selection
+    (TZ-PS1), plus 64: motion-compensated tiles (TZ-PM1, tezip_amd/predmotion.py) -- against tezip_amd.json, which records "select"
+    or "motion" and says nothing otherwise.  The trailer is authoritative; a sidecar that contradicts it belongs to another
+    stream.  Returns (kind, modes, vectors): kind "net", "select" or "motion"; the modes of pred_modes.dat, validated against the
+    trailer's stack, None for "net"; the vectors for "motion" alone, else None."""
+    have = predmotion.pred_of_mark(one)
     want = sidecar.pred_of(sidecar.read(data_dir))
     if want is not None and want != have:
         raise ValueError("tezip_amd.json describes the prediction as %s, entropy.dat's trailer as %s" % (want, have))
-    return predselect.read(data_dir, nt, H, W) if have == "select" else None
+    if have == "motion":
+        return (have,) + tuple(predmotion.read(data_dir, nt, H, W))
+    return have, (predselect.read(data_dir, nt, H, W) if have == "select" else None), None
 
 
-def pred_modes_or_exit(data_dir, one, nt, H, W):
-    """check_pred with a refusal as one ERROR line and exit status 2 (the error class of adopt_contract: nothing was written)."""
+def check_pred(data_dir, one, nt, H, W):
+    """stream_pred's modes alone: None for a stream whose tiles all come from the network."""
+    return stream_pred(data_dir, one, nt, H, W)[1]
+
+
+def stream_pred_or_exit(data_dir, one, nt, H, W):
+    """stream_pred with a refusal as one ERROR line and exit status 2 (the error class of adopt_contract: nothing was written)."""
     try:
-        return check_pred(data_dir, one, nt, H, W)
+        return stream_pred(data_dir, one, nt, H, W)
     except ValueError as e:
         print("ERROR:", e)
         sys.exit(2)
+
+
+def pred_modes_or_exit(data_dir, one, nt, H, W):
+    """stream_pred_or_exit's modes alone."""
+    return stream_pred_or_exit(data_dir, one, nt, H, W)[1]
+
+
+def put_pred(ctx, kind, modes, vectors):
+    """What stream_pred returned, in front of ctx.rollout_decode_closed: nothing for "net", TZ-PS1's modes for "select", TZ-PM1's
+    modes and vectors for "motion"."""
+    if kind == "motion":
+        ctx.set_pred_motion(predmotion.RADIUS)
+        ctx.put_pred_modes(modes)
+        ctx.put_pred_vectors(vectors)
+    elif kind == "select":
+        ctx.set_pred_select(True)
+        ctx.put_pred_modes(modes)
 
 
 def refuse_closed_range(frames):
@@ -393,8 +423,8 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             coded = fmt.parse(np.fromfile(paths["entropy.dat"], np.uint8), key_len)
             table, warm_up = coded.table, coded.warm_up
             one, nt, H, W, C = coded.shape
-            modes = pred_modes_or_exit(DATA_DIR, one, nt, H, W)
-            one = predselect.closed_mark(one)
+            tile_pred = stream_pred_or_exit(DATA_DIR, one, nt, H, W)
+            one = predmotion.closed_mark(one)
             closed = check_loop(DATA_DIR, one)
             one = closedloop.open_mark(one)
             if closed:
@@ -460,9 +490,9 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
                 raise ValueError("corrupt table length %d" % tlen)
             table = None if tlen == -1 else np.ascontiguousarray(tail[tail.size - 7 - tlen: tail.size - 7])
             payload_len = total - 7 - max(tlen, 0)
-            check_stream(shape, warm_up, payload_len, key_len)
-            modes = pred_modes_or_exit(DATA_DIR, *shape[:4])
-            shape = (predselect.closed_mark(shape[0]),) + shape[1:]
+            check_stream((predmotion.select_mark(shape[0]),) + shape[1:], warm_up, payload_len, key_len)   # (a motion mark: as its layout's select mark)
+            tile_pred = stream_pred_or_exit(DATA_DIR, *shape[:4])
+            shape = (predmotion.closed_mark(shape[0]),) + shape[1:]
             closed = check_loop(DATA_DIR, shape[0])   # (a rollout that ran early on a closed-loop stream: the sidecar is another stream's)
             if closed:
                 refuse_closed_range(frames)
@@ -491,9 +521,7 @@ def _run_streaming(DATA_DIR, OUTPUT_DIR, file_names, isRGB, cfg, wts, model_shap
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
-            if modes is not None:   # TZ-PS1: the stored modes pick every tile's prediction
-                ctx.set_pred_select(True)
-                ctx.put_pred_modes(modes)
+            put_pred(ctx, *tile_pred)   # TZ-PS1 / TZ-PM1: the stored modes (and vectors) pick every tile's prediction
             ctx.rollout_decode_closed(None, warm_up, None, table)
             if VERBOSE:
                 print("predict:{0}".format(time.time() - t0) + "[sec]")
@@ -649,9 +677,9 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
         payload, table, shape, warm_up = None, coded.table, coded.shape, coded.warm_up
     else:
         payload, table, shape, warm_up = parse_stream(read("entropy.dat"))
-        check_stream(shape, warm_up, payload.size, key_len)
-    modes = pred_modes_or_exit(DATA_DIR, *shape[:4])
-    shape = (predselect.closed_mark(shape[0]),) + tuple(shape[1:])
+        check_stream((predmotion.select_mark(shape[0]),) + tuple(shape[1:]), warm_up, payload.size, key_len)   # (a motion mark: as its layout's select mark)
+    tile_pred = stream_pred_or_exit(DATA_DIR, *shape[:4])
+    shape = (predmotion.closed_mark(shape[0]),) + tuple(shape[1:])
     closed = check_loop(DATA_DIR, shape[0])
     shape = (closedloop.open_mark(shape[0]),) + tuple(shape[1:])
     if closed and job is not None:
@@ -719,9 +747,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, GPU_FLAG, VERBOSE, device=0, frames=N
                 begin(coded.body.size, coded.n, coded.lengths, coded.base, run=coded.run)
                 put(0, np.ascontiguousarray(coded.body))
                 expand()
-            if closed and modes is not None:   # TZ-PS1: the stored modes pick every tile's prediction
-                ctx.set_pred_select(True)
-                ctx.put_pred_modes(modes)
+            if closed:   # TZ-PS1 / TZ-PM1: the stored modes (and vectors) pick every tile's prediction
+                put_pred(ctx, *tile_pred)
             if closed:
                 ctx.rollout_decode_closed(kf, warm_up, None if coded is not None else np.ascontiguousarray(payload), tb)
                 if VERBOSE:

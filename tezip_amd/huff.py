@@ -322,6 +322,8 @@ def parse_of(fmt, p, check, data, key_len=None):
         one -= 16
     elif one in (49, 52, 56) and C == 3:
         one -= 48
+    elif one in (81, 84, 88) and C == 3:   # each plus 80: a closed-loop job with motion-compensated tiles (tezip_amd/predmotion.py)
+        one -= 80
     if one not in (1, 4, 8) or C not in (1, 3) or (one == 4 and C != 3) or nt < 1 or H < 1 or W < 1:
         raise ValueError("%s: unsupported stack shape %r (expected (1, nt, H, W, 3), (1, nt, H, W, 1) for a gray job, "
                          "(4, nt, H, W, 3) for a channel-stride payload or (8, nt, H, W, 3 or 1) for a plane payload; 16 more for a closed-loop job)" % (what, tuple(p.shape)))

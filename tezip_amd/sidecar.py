@@ -30,7 +30,8 @@ it is an error.  A decoder that reads "closed" here does not queue its rollout a
 
 `pred` = "select" (optional): the job chose per 16 x 16 tile between the network and the decoded frame in front, TZ-PS1
 (`-c --loop closed --pred select`, tezip_amd/predselect.py); every other job has no such key.  The mark in entropy.dat's trailer is
-authoritative (the closed-loop mark plus 32); a sidecar that contradicts it is an error.
+authoritative (the closed-loop mark plus 32); a sidecar that contradicts it is an error.  `pred` = "motion": the frame in front was
+displaced per tile, TZ-PM1 (`--pred motion`, tezip_amd/predmotion.py); the mark is the closed-loop mark plus 64.
 
 `stack` = [frames, height, width, warm_up] (round 6, optional): the reference stores these in the LAST seven
 values of entropy.dat (compress.py:390-394), so a decoder learns it only when the whole payload is decompressed; with
@@ -88,8 +89,8 @@ def write(out_dir, contract, wts, hp, wp, stack=None, payload_channels=3, sdelta
         doc["bound_map"] = {"max": int(bound_map["max"]), "exact_pixels": int(bound_map["exact_pixels"])}
     if loop == "closed":        # a --loop closed job (tezip_amd/closedloop.py); every other job has no such key
         doc["loop"] = "closed"
-    if pred == "select":        # a --pred select job (tezip_amd/predselect.py); every other job has no such key
-        doc["pred"] = "select"
+    if pred in ("select", "motion"):   # a --pred select job (tezip_amd/predselect.py) or a --pred motion job (tezip_amd/predmotion.py);
+        doc["pred"] = pred             # every other job has no such key
     with open(os.path.join(out_dir, NAME), "w", encoding="UTF-8") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
@@ -157,13 +158,14 @@ def loop_of(doc):
 
 
 def pred_of(doc):
-    """What the sidecar states about per-tile selection: "select" for a --pred select job (tezip_amd/predselect.py), "net" for a
-    sidecar without the key, None without a sidecar.  Anything else is a damaged file."""
+    """What the sidecar states about per-tile selection: "select" for a --pred select job (tezip_amd/predselect.py), "motion" for a
+    --pred motion job (tezip_amd/predmotion.py), "net" for a sidecar without the key, None without a sidecar.  Anything else is a
+    damaged file."""
     if doc is None:
         return None
     pred = doc.get("pred", "net")
-    if pred not in ("net", "select") or ("pred" in doc and pred == "net"):
-        raise SidecarMismatch("%s states pred %r (\"select\" is the only value ever written)" % (NAME, pred))
+    if pred not in ("net", "select", "motion") or ("pred" in doc and pred == "net"):
+        raise SidecarMismatch("%s states pred %r (\"select\" and \"motion\" are the only values ever written)" % (NAME, pred))
     return pred
 
 

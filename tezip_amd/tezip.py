@@ -15,7 +15,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "tezip_amd"
 
-from . import boundmap, closedloop, compress, decompress, frametarget, predselect, sdauto, target, train  # noqa: E402
+from . import boundmap, closedloop, compress, decompress, frametarget, predmotion, predselect, sdauto, target, train  # noqa: E402
 
 # (short, long, argparse keywords) -- tezip.py:88-99
 FLAG_TABLE = (
@@ -120,8 +120,10 @@ FLAG_TABLE = (
     # flag is absent) = the network, today's job byte for byte; select = whichever of the network and the decoded frame in front
     # leaves the smaller quantised residual, one bit per tile in a fifth file pred_modes.dat (definition TZ-PS1 in
     # tezip_amd/predselect.py; in a lossless job no tile's residual grows in L1 norm, which promises nothing about bytes: README).
+    # motion = select with the frame in front displaced per tile by a vector of up to 7 pixels found by a full search; the file also
+    # holds one byte per chosen tile (definition TZ-PM1 in tezip_amd/predmotion.py).
     # -u recognises the stream by the mark in its trailer (compress.run(PRED=...))
-    (None, "--pred", dict(type=str, choices=("net", "select"), default=None, dest="pred")),
+    (None, "--pred", dict(type=str, choices=("net", "select", "motion"), default=None, dest="pred")),
 )
 
 TEXT = {
@@ -308,13 +310,13 @@ def check_loop_flag(arg):
 
 
 def check_pred_flag(arg):
-    """--pred is valid with -c only; `select` needs --loop closed.  Returns None, or the message of a refusal."""
+    """--pred is valid with -c only; `select` and `motion` need --loop closed.  Returns None, or the message of a refusal."""
     pred = getattr(arg, "pred", None)
     if pred is None:
         return None
     if arg.compress is None or arg.uncompress is not None or arg.learn is not None:
         return predselect.NEEDS_COMPRESS
-    return predselect.check_flags(pred, getattr(arg, "loop", None) or "open")
+    return predmotion.check_flags(pred, getattr(arg, "loop", None) or "open")
 
 
 def check_target_flag(arg):
@@ -557,7 +559,7 @@ def _main(arg):
                             CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
                             DIGESTS=bool(getattr(arg, "digests", False)), SDELTA=getattr(arg, "sdelta", None) or "flat",
                             SSIM=bool(getattr(arg, "ssim", False)), QUANT=getattr(arg, "quant", None) or "greedy", LOOP="closed",
-                            **({"PRED": "select"} if getattr(arg, "pred", None) == "select" else {}))
+                            **({"PRED": arg.pred} if getattr(arg, "pred", None) in ("select", "motion") else {}))
     if map_file is not None:   # (every other flag travels with it; the jobs without it are the calls below)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu,
                             arg.verbose, arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
