@@ -224,6 +224,34 @@ int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, 
 int tz_rollout_loop(tz_ctx* ctx);
 int tz_rollout_decode_closed(tz_ctx* ctx, const uint8_t* key_frames, int nt, int H, int W, int warm_up, const int16_t* payload,
                              size_t payload_len, const int16_t* table, int table_len, uint8_t* key_mask);
+/* ---- the closed loop under one abs bound per frame, definition TZ-CLF1 (no reference counterpart; slow
+ * statement in tezip_amd/closedframes.py).  TZ-CL1 except for the tolerance of a non-key frame t: q = Q_{E_t}(d) with
+ * E_t = min(255, floor(b_t)), TZ-QL1's quantiser.  When the loop stands at frame t, pred_t is fixed (it depends on dec[t-1] alone),
+ * so b_t can be GIVEN, or FOUND there: sse_t(k) = sum (clamp(x - Q_{k/2}(x - orig_t), 0, 255) - orig_t)^2 over the frame's H*W*3
+ * samples; lo = 0, hi = 511, mid = (lo + hi) / 2, pass <=> sse_t(mid) <= sse_limit, at most 9 rounds; k_t = lo, b_t = k_t / 2.
+ * Per searched frame: sse_t(k_t) <= sse_limit, and k_t == 510 or sse_t(k_t + 1) > sse_limit -- a boundary, not the largest passing
+ * bound, and greedy in time: sse_t is taken given the dec[t-1] the earlier frames' results produced.
+ * tz_rollout_closed_frames: frames, nt, H, W, warm_up, window, key_mask as tz_rollout_closed.  Exactly one of bounds (nt finite
+ *   numbers >= 0; entries at frame 0, warm-up and key frames are taken as 0) and sse_limit > 0 (TZ_ERR_INVALID otherwise, and for a
+ *   bound that is negative or not finite).  TZ_ERR_UNSUPPORTED, naming the setter, unless: tz_set_quantiser(1), a three-channel
+ *   payload, no tz_set_bound_map, no tz_set_frame_bounds in force, no tz_set_pred_select / tz_set_pred_motion, window > 0.
+ *   Per step: the predictor; for a search 9 launches of k_clf_probe (one bisection round each for every frame of the step, the
+ *   sums kept on the device); k_clf_step, which decodes the step's frames under their own E.  No host wait inside the loop; one
+ *   copy-back behind it.  Given bounds whose E are all 0 run the lossless closed job's one schedule.
+ *   It stamps the loop as tz_rollout_closed does (tz_rollout_loop returns 1), and the stamp carries the bounds (0 at fixed frames):
+ *   tz_encode, tz_encode_begin, tz_encode_delta, tz_bound_probe, tz_size_probe and tz_sdelta_probe return TZ_ERR_STATE unless the
+ *   mode is TZ_MODE_ABS, the quantiser the lattice and tz_set_frame_bounds holds exactly those bounds (b0 / b1 are not read).  The
+ *   unchanged back half then forms the loop's q again, and the stream is an ordinary closed-loop stream: tz_rollout_decode_closed
+ *   decodes it.
+ * tz_loop_frame_bounds(ctx, bounds, sse, cap): the stamp's nt bounds and, after a search, sse_t(k_t) (0 at fixed frames, at k_t = 0
+ *   and after given bounds); either pointer may be NULL.  Returns nt.  TZ_ERR_INVALID for cap < nt.
+ * tz_loop_search_trace(ctx, sse, cap): the search's 9*nt sums, round-major (sse[r*nt + f]); 2^64-1 where round r did not run for
+ *   frame f (a fixed frame, or an interval that had closed).  Returns 9*nt.
+ *   Both: TZ_ERR_STATE when the resident rollout is of another kind (the trace also after given bounds). */
+int tz_rollout_closed_frames(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, const double* bounds,
+                             unsigned long long sse_limit, uint8_t* key_mask);
+int tz_loop_frame_bounds(tz_ctx* ctx, double* bounds, unsigned long long* sse, int cap);
+int tz_loop_search_trace(tz_ctx* ctx, unsigned long long* sse, int cap);
 /* ---- per-tile choice between the network and the frame in front, definition TZ-PS1 (no reference counterpart;
  * `tezip.py -c --loop closed --pred select`, DESIGN.md section 9, slow statement in tezip_amd/predselect.py).  In a closed loop both
  * sides hold dec[t-1] when frame t is predicted: a second predictor.  TZ-PS1 is TZ-CL1 except for the value x of a non-key frame:

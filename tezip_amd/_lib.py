@@ -58,6 +58,10 @@ _SIGS = {
     "tz_rollout_closed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                     C.c_void_p]),
     "tz_rollout_loop": (C.c_int, [C.c_void_p]),
+    "tz_rollout_closed_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_ulonglong,
+                                           C.c_void_p]),
+    "tz_loop_frame_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "tz_loop_search_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "tz_rollout_decode_closed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.c_int, C.c_void_p]),
     "tz_set_pred_select": (C.c_int, [C.c_void_p, C.c_int]),
@@ -609,6 +613,46 @@ class Context:
                                             MODES[mode], b0, b1, key.ctypes.data))
         self._shape = (nt, h, w)
         return key.astype(bool)
+
+    def rollout_closed_frames(self, frames, warm_up, window, bounds=None, sse_limit=0):
+        """tz_rollout_closed_frames (TZ-CLF1, tezip_amd/closedframes.py): the closed loop under one abs bound per frame -- `bounds`
+        (nt numbers), or found inside the loop so that every frame's sse stays <= `sse_limit` (> 0); exactly one of the two.  Needs
+        the lattice quantiser; frames as for rollout.  Returns the key mask; loop_frame_bounds() has the bounds of the job, which
+        runs under set_frame_bounds of exactly those."""
+        if frames is None:
+            nt, h, w = self._staged
+        else:
+            self._check_stack(frames, "frames")
+            nt, h, w = frames.shape[:3]
+        b = None
+        if bounds is not None:
+            b = np.ascontiguousarray(bounds, np.float64)
+            if b.shape != (nt,):
+                raise ValueError("%d bounds for %d frames" % (b.size, nt))
+        key = np.zeros(nt, np.uint8)
+        self._ck(self.lib.tz_rollout_closed_frames(self.h, None if frames is None else _ptr(frames, np.uint8), nt, h, w, warm_up,
+                                                   int(window or 0), None if b is None else b.ctypes.data, int(sse_limit), key.ctypes.data))
+        self._shape = (nt, h, w)
+        return key.astype(bool)
+
+    def loop_frame_bounds(self):
+        """tz_loop_frame_bounds: (bounds float64[nt], sse uint64[nt]) of the resident rollout_closed_frames; sse is zero after
+        given bounds."""
+        nt = self._shape[0]
+        bounds, sse = np.zeros(nt, np.float64), np.zeros(nt, np.uint64)
+        rc = int(self.lib.tz_loop_frame_bounds(self.h, bounds.ctypes.data, sse.ctypes.data, nt))
+        if rc < 0:
+            self._ck(rc)
+        return bounds, sse
+
+    def loop_search_trace(self):
+        """tz_loop_search_trace: uint64 (9, nt), the sse of every bisection round and frame; 2**64 - 1 where a round did not run."""
+        nt = self._shape[0]
+        out = np.zeros((9, nt), np.uint64)
+        rc = int(self.lib.tz_loop_search_trace(self.h, out.ctypes.data, out.size))
+        if rc < 0:
+            self._ck(rc)
+        return out
 
     def rollout_loop(self):
         """tz_rollout_loop: 1 when the resident predictions are a closed loop's, 0 after any other rollout."""

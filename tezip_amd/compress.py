@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, boundmap, closedloop, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, predmotion, predselect, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
+from . import _lib, boundmap, closedframes, closedloop, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, predmotion, predselect, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -568,7 +568,7 @@ def check_ratio(ratio, mode, bound, target_psnr, coder, shuffle, sharded):
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
         SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None, QUANT="greedy", BOUND_MAP=None,
-        LOOP="open", PRED="net"):
+        LOOP="open", PRED="net", LOOP_PSNR=None, LOOP_BOUNDS=None):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -653,6 +653,13 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     FRAME_BOUNDS or BOUND_MAP (a target's probes assume predictions that do not depend on the bound).  Works with every SDELTA,
     CODER, KEY_CODER, SHUFFLE, REPORT, SSIM and DIGESTS.  VERBOSE prints no per-step MSE lines.  Single-GPU jobs only.
 
+    LOOP_PSNR (--loop-psnr; NOT in the reference; LOOP "closed", QUANT "lattice", MODE "abs", an empty BOUND_VALUE): a PSNR in dB
+    that every frame not stored exactly must reach, definition TZ-CLF1 (tezip_amd/closedframes.py): the ONE closed-loop rollout
+    (tz_rollout_closed_frames) finds every frame's abs bound when the loop stands at that frame, by a bisection that stays on the
+    device.  One line says so, bound_search.json holds the search, and the job then runs under tz_set_frame_bounds with the bounds
+    found; `-u` takes no flag.  LOOP_BOUNDS (--loop-bounds): the bounds given instead -- a path or a sequence as FRAME_BOUNDS
+    takes them (a bound_search.json replays).  Not with PRED "select" / "motion", nor with anything LOOP "closed" refuses.
+
     PRED (--pred; NOT in the reference): "net" (the default: every file, line and launch is what it is without it) or, with LOOP
     "closed", "select": every 16 x 16 tile of a predicted frame takes whichever of the network's prediction and the decoded frame
     in front leaves the smaller quantised residual, definition TZ-PS1 (tezip_amd/predselect.py).  One line says how many tiles
@@ -695,6 +702,20 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    loop_frames = LOOP_PSNR is not None or LOOP_BOUNDS is not None
+    loop_bounds = None
+    if loop_frames:   # likewise (in front of --loop's check: a refusal of this job names the flag that defines it)
+        problem = closedframes.check_flags(LOOP_PSNR, LOOP_BOUNDS, LOOP, QUANT, None if LOOP_PSNR is not None and MODE == "abs" else MODE,
+                                           BOUND_VALUE, PRED, True, False, tzdist.active() is not None, GRAY, THRESHOLD, TARGET_PSNR,
+                                           TARGET_RATIO, PER_FRAME, FRAME_BOUNDS, BOUND_MAP)
+        if not problem and LOOP_BOUNDS is not None:
+            try:
+                loop_bounds = closedframes.load(LOOP_BOUNDS)
+            except ValueError as e:
+                problem = str(e)
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     problem = closedloop.check_flags(LOOP, MODE, BOUND_VALUE, QUANT, THRESHOLD, False, tzdist.active() is not None, GRAY, TARGET_PSNR,
                                      TARGET_RATIO, PER_FRAME, FRAME_BOUNDS, BOUND_MAP)
     if problem:   # likewise
@@ -755,6 +776,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
         if problem:
             print("ERROR:", problem)
             sys.exit(2)
+    if loop_bounds is not None:   # likewise
+        problem = closedframes.check_length(loop_bounds, nt, LOOP_BOUNDS)
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     if bound_map is not None:   # likewise
         problem = boundmap.check_size(bound_map, H, W, BOUND_MAP if isinstance(BOUND_MAP, (str, os.PathLike)) else "BOUND_MAP")
         if problem:
@@ -791,7 +817,23 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             if VERBOSE:
                 ctx.prof_enable(True)
             t0 = time.time()
-            if closed:   # TZ-CL1: the decoded frame is fed back, under the job's own bound and quantiser (no window MSE exists)
+            if closed and loop_frames:   # TZ-CLF1: TZ-CL1 under one abs bound per frame, given or found inside the one rollout
+                print(closedloop.STDOUT_LINE)
+                if LOOP_PSNR is not None:
+                    limit = target.sse_limit(LOOP_PSNR, H * W * 3)
+                    key = (ctx.rollout_closed_frames(None, PREPROCESS, WINDOW_SIZE, sse_limit=limit) if limit > 0 else
+                           ctx.rollout_closed_frames(None, PREPROCESS, WINDOW_SIZE, bounds=[0.0] * nt))   # (the lossless job: no probe)
+                    found, found_sse = ctx.loop_frame_bounds()
+                    search_doc = closedframes.make(LOOP_PSNR, H * W * 3, limit, frametarget.fixed_frames(key, PREPROCESS), src.files, found,
+                                                   found_sse, ctx.loop_search_trace() if limit > 0 else [])
+                    search_doc["quant"] = "lattice"
+                    frame_bounds = search_doc["frame_bounds"]
+                    print(closedframes.stdout_line(search_doc))
+                else:
+                    key = ctx.rollout_closed_frames(None, PREPROCESS, WINDOW_SIZE, bounds=loop_bounds)
+                    frame_bounds = [float(b) for b in ctx.loop_frame_bounds()[0]]   # (0 at the frames stored exactly)
+                    print(closedframes.explicit_line(frame_bounds))
+            elif closed:   # TZ-CL1: the decoded frame is fed back, under the job's own bound and quantiser (no window MSE exists)
                 print(closedloop.STDOUT_LINE)
                 if select:   # TZ-PS1: per tile, the network or the decoded frame in front
                     ctx.set_pred_select(True)
@@ -826,7 +868,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 frame_bounds = search_doc["frame_bounds"]
                 print(frametarget.stdout_line(search_doc))
                 stages.mark("per-frame bound search (device)")
-            elif frame_bounds is not None:
+            elif frame_bounds is not None and not loop_frames:
                 frame_bounds = [0.0 if fx else b for fx, b in zip(frametarget.fixed_frames(key, PREPROCESS), frame_bounds)]
                 print(frametarget.explicit_line(frame_bounds))
             if bound_map is not None:   # the job: abs, pixel p under bound_map[p] in every frame (BOUND_VALUE is not read)
@@ -959,6 +1001,8 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                 search_doc["quant"] = "lattice"
             if PER_FRAME:
                 frametarget.write(OUTPUT_DIR, search_doc)
+            elif LOOP_PSNR is not None:
+                closedframes.write(OUTPUT_DIR, search_doc)
             elif TARGET_PSNR is not None:
                 target.write(OUTPUT_DIR, search_doc)
             if TARGET_RATIO is not None:

@@ -687,6 +687,7 @@ static void set_rollout(tz_ctx* ctx, tz_ctx::tz_rollout_kind kind, int pred_firs
     ctx->loop_closed = 0;   // (tz_rollout_closed stamps its loop behind this)
     ctx->loop_select = 0;
     ctx->loop_motion = 0;
+    ctx->loop_frames = 0;   // (tz_rollout_closed_frames likewise)
     ctx->pred_modes.clear();
     ctx->pred_vectors.clear();
     ctx->pred_first = pred_first;
@@ -1559,6 +1560,18 @@ static int loop_check(tz_ctx* ctx, const char* who, int mode, double b0, double 
                        "%s: the resident predictions are those of a closed loop (tz_rollout_closed) run %s motion-compensated tiles "
                        "(tz_set_pred_motion(%d)); they serve that kind of job alone, the setting is now %d",
                        who, ctx->loop_motion ? "with" : "without", ctx->loop_motion, ctx->pred_motion);
+    if (ctx->loop_frames) {   // TZ-CLF1: every frame was decoded under its own bound; the job is the one under exactly those bounds
+        if (mode == TZ_MODE_ABS && ctx->quantiser == 1 && ctx->frame_bounds == ctx->loop_bounds && !ctx->map_h && ctx->payload_channels == 3)
+            return TZ_OK;
+        return tz_fail(ctx, TZ_ERR_STATE,
+                       "%s: the resident predictions are those of a closed loop run under one abs bound per frame "
+                       "(tz_rollout_closed_frames); they serve the abs job of the lattice quantiser (tz_set_quantiser(1)) under "
+                       "tz_set_frame_bounds with exactly those %d bounds (tz_loop_frame_bounds) alone, not mode %d, quantiser %d, %s%s%s",
+                       who, (int)ctx->loop_bounds.size(), mode, ctx->quantiser,
+                       ctx->frame_bounds.empty() ? "no frame bounds" : (ctx->frame_bounds == ctx->loop_bounds ? "those bounds" : "other frame bounds"),
+                       ctx->map_h ? ", a bound map (tz_set_bound_map)" : "",
+                       ctx->payload_channels == 3 ? "" : ", a one-channel payload (tz_set_payload_channels)");
+    }
     const bool same = mode == ctx->loop_mode && b0 == ctx->loop_b0 && (mode != TZ_MODE_ABSREL || b1 == ctx->loop_b1) &&
                       ctx->quantiser == ctx->loop_quantiser;
     if (same && ctx->frame_bounds.empty() && !ctx->map_h && ctx->payload_channels == 3) return TZ_OK;
@@ -2419,6 +2432,177 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
     ctx->pred_vectors.swap(vectors);
     if (key_mask) memcpy(key_mask, key.data(), nt);
     return TZ_OK;
+}
+
+// ---- the closed loop under one abs bound per frame, definition TZ-CLF1 (include/tezip_hip.h: tz_rollout_closed_frames; slow
+// statement in tezip_amd/closedframes.py).  When the loop stands at frame t, pred_t is fixed, so every candidate bound of frame t
+// is priced by a pass over (pred_t, orig_t) alone: the search costs TZ_CLF_ROUNDS small launches a step and no host wait.
+extern "C" int tz_rollout_closed_frames(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, const double* bounds,
+                                        unsigned long long sse_limit, uint8_t* key_mask) {
+    tz_roctx_range roctx_("tz_rollout_closed_frames");
+    if (!ctx) return TZ_ERR_INVALID;
+    ctx->enc_kind = tz_ctx::ENC_NONE;
+    if (window < 0) return tz_fail(ctx, TZ_ERR_INVALID, "window must be >= 0");
+    if ((bounds != nullptr) == (sse_limit > 0))
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_closed_frames takes either the bounds or an sse limit > 0 to search them under, not %s",
+                       bounds ? "both" : "neither");
+    if (window == 0)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_frames: the closed loop serves fixed windows (window > 0), not the threshold rule");
+    if (nt < warm_up + 2 || warm_up < 0)
+        return tz_fail(ctx, TZ_ERR_INVALID, "need at least warm_up+2 frames (nt=%d, warm_up=%d)", nt, warm_up);
+    if (bounds)
+        for (int f = 0; f < nt; ++f)
+            if (!std::isfinite(bounds[f]) || bounds[f] < 0.0)
+                return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_closed_frames: bound %g of frame %d is not a finite number >= 0", bounds[f], f);
+    if (ctx->quantiser != 1)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_frames needs the lattice quantiser (tz_set_quantiser(1)): the greedy walk is no function of one sample");
+    if (ctx->payload_channels != 3)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_frames: the loop decodes three channels (no tz_set_payload_channels(1))");
+    if (ctx->map_h) return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_frames does not serve a bound map (tz_set_bound_map)");
+    if (!ctx->frame_bounds.empty())
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_frames takes its bounds itself: clear tz_set_frame_bounds first, and set it to tz_loop_frame_bounds' answer for the job");
+    if (ctx->pred_select)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_frames does not serve per-tile selection (tz_set_pred_select)");
+    if (ctx->pred_motion)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_frames does not serve motion-compensated tiles (tz_set_pred_motion)");
+    const int p = warm_up;
+    tz_call call(ctx);
+    TZ_TRY(rollout_setup(ctx, frames, nt, H, W, warm_up));
+    // key mask and groups: tz_rollout_closed's
+    std::vector<uint8_t> key(nt, 0), gfirst(nt, 0), qskip(nt, 0);
+    std::vector<int> c0_slots;
+    for (int i = 0; i < p; ++i) {
+        key[i] = 1;
+        qskip[i] = 1;
+        c0_slots.push_back(i);
+    }
+    gfirst[0] = 1;
+    if (p > 0) gfirst[p] = 1;
+    c0_slots.push_back(p > 0 ? p : 0);
+    key[p] = 1;
+    for (int idx = p + 1; idx < nt; ++idx)
+        if ((idx - p) % window == 0) {
+            gfirst[idx] = 1;
+            key[idx] = 1;
+            c0_slots.push_back(idx);
+        }
+    for (int i = 0; i < nt; ++i)
+        if (gfirst[i]) qskip[i] = 1;
+    // the bounds of the stamp (0 at the frames stored exactly) and their radii E = min(255, floor(b))
+    std::vector<double> norm(nt, 0.0);
+    std::vector<int> radius(nt, 0);
+    bool lossless = bounds != nullptr;
+    for (int f = 0; f < nt && bounds; ++f) {
+        if (key[f]) continue;
+        norm[f] = bounds[f];
+        radius[f] = bounds[f] >= 255.0 ? 255 : (int)bounds[f];
+        if (radius[f]) lossless = false;
+    }
+    std::vector<unsigned long long> fsse(nt, 0ull), trace;
+    std::vector<int> ks(nt, 0);
+    int rc = fill_c0(ctx, c0_slots);
+    const std::vector<std::vector<int>> steps = closed_steps(key);
+    if (rc == TZ_OK && lossless) {   // every E is 0: the lossless closed job, one schedule
+        std::vector<int> all;
+        for (const auto& st : steps) all.insert(all.end(), st.begin(), st.end());
+        rc = closed_predict(ctx, all, ctx->d_frames);
+    } else if (rc == TZ_OK) {
+        const size_t fb = (size_t)nt * H * W * 3, ntrace = (size_t)TZ_CLF_ROUNDS * nt;
+        uint8_t* d_dec = nullptr;
+        const int* d_lists = nullptr;
+        int *d_radius = nullptr, *d_k = nullptr;
+        unsigned long long *d_sse = nullptr, *d_fsse = nullptr;
+        rc = call.alloc(fb, &d_dec);
+        if (rc == TZ_OK) rc = closed_lists(call, steps, &d_lists);
+        if (rc == TZ_OK && bounds) {
+            rc = call.alloc((size_t)nt * sizeof(int), &d_radius);
+            if (rc == TZ_OK) rc = tz_upload(ctx, d_radius, radius.data(), (size_t)nt * sizeof(int));
+        } else if (rc == TZ_OK) {
+            rc = call.alloc(ntrace * sizeof(unsigned long long), &d_sse);
+            if (rc == TZ_OK) rc = call.alloc((size_t)nt * sizeof(unsigned long long), &d_fsse);
+            if (rc == TZ_OK) rc = call.alloc((size_t)nt * sizeof(int), &d_k);
+            if (rc == TZ_OK && (hipMemsetAsync(d_sse, 0, ntrace * sizeof(unsigned long long), ctx->stream) != hipSuccess ||
+                                hipMemsetAsync(d_fsse, 0, (size_t)nt * sizeof(unsigned long long), ctx->stream) != hipSuccess ||
+                                hipMemsetAsync(d_k, 0, (size_t)nt * sizeof(int), ctx->stream) != hipSuccess))
+                rc = tz_fail(ctx, TZ_ERR_HIP, "tz_rollout_closed_frames: clearing the search's sums failed");
+        }
+        if (rc == TZ_OK && hipMemcpyAsync(d_dec, ctx->d_frames, fb, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)   // the key frames
+            rc = tz_fail(ctx, TZ_ERR_HIP, "tz_rollout_closed_frames: copy of the frame stack failed");
+        size_t at = 0;
+        for (size_t s = 0; s < steps.size() && rc == TZ_OK; at += steps[s].size(), ++s) {
+            const int n = (int)steps[s].size();
+            rc = closed_predict(ctx, steps[s], d_dec);
+            for (int r = 0; r < TZ_CLF_ROUNDS && rc == TZ_OK && !bounds; ++r)
+                rc = tzk_clf_probe(ctx, ctx->d_pred, ctx->d_frames, d_lists + at, n, H, W, ctx->Hp, ctx->Wp, r, d_sse, nt, sse_limit);
+            if (rc == TZ_OK)
+                rc = tzk_clf_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_lists + at, n, H, W, ctx->Hp, ctx->Wp, d_radius, d_sse, nt, sse_limit,
+                                  d_k, d_fsse);
+        }
+        if (rc == TZ_OK && !bounds) {   // one copy-back behind the loop: k, sse(k) and the rounds' sums
+            trace.resize(ntrace);
+            rc = tz_d2h(ctx, ks.data(), d_k, (size_t)nt * sizeof(int), ctx->stream);
+            if (rc == TZ_OK) rc = tz_d2h(ctx, fsse.data(), d_fsse, (size_t)nt * sizeof(unsigned long long), ctx->stream);
+            if (rc == TZ_OK) rc = tz_d2h(ctx, trace.data(), d_sse, ntrace * sizeof(unsigned long long), ctx->stream);
+        }
+    }
+    if (rc == TZ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = tz_fail(ctx, TZ_ERR_HIP, "closed-loop rollout failed");
+    if (rc != TZ_OK) {  // nothing of a failed rollout may still read the caller's frames when we return
+        (void)hipStreamSynchronize(ctx->copy_stream);
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    if (!bounds) {   // the bounds found, and ~0 in the rounds that did not run for a frame (the device array starts from zeros)
+        for (int f = 0; f < nt; ++f) {
+            norm[f] = key[f] ? 0.0 : ks[f] / 2.0;
+            int lo = 0, hi = key[f] ? 1 : 511;
+            for (int r = 0; r < TZ_CLF_ROUNDS; ++r) {
+                unsigned long long& v = trace[(size_t)r * nt + f];
+                if (hi - lo <= 1) {
+                    v = ~0ull;
+                    continue;
+                }
+                const int mid = (lo + hi) / 2;
+                if (v <= sse_limit) lo = mid;
+                else hi = mid;
+            }
+        }
+    }
+    ctx->key_mask = key;
+    ctx->group_first = gfirst;
+    ctx->quant_skip = qskip;
+    set_rollout(ctx, tz_ctx::ROLLOUT_ENCODE, 0, nt);
+    ctx->pred_contract = tz_get_contract(ctx);
+    ctx->loop_closed = 1;
+    ctx->loop_mode = TZ_MODE_ABS;
+    ctx->loop_b0 = ctx->loop_b1 = 0.0;
+    ctx->loop_quantiser = 1;
+    ctx->loop_frames = 1;
+    ctx->loop_bounds.swap(norm);
+    ctx->loop_frame_sse.swap(fsse);
+    ctx->loop_trace.swap(trace);
+    if (key_mask) memcpy(key_mask, key.data(), nt);
+    return TZ_OK;
+}
+
+extern "C" int tz_loop_frame_bounds(tz_ctx* ctx, double* bounds, unsigned long long* sse, int cap) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (ctx->rollout_kind != tz_ctx::ROLLOUT_ENCODE || !ctx->loop_closed || !ctx->loop_frames)
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_loop_frame_bounds: the resident rollout is no tz_rollout_closed_frames");
+    const int nt = (int)ctx->loop_bounds.size();
+    if ((bounds || sse) && cap < nt) return tz_fail(ctx, TZ_ERR_INVALID, "tz_loop_frame_bounds: room for %d frames, the rollout has %d", cap, nt);
+    if (bounds) memcpy(bounds, ctx->loop_bounds.data(), (size_t)nt * sizeof(double));
+    if (sse) memcpy(sse, ctx->loop_frame_sse.data(), (size_t)nt * sizeof(unsigned long long));
+    return nt;
+}
+
+extern "C" int tz_loop_search_trace(tz_ctx* ctx, unsigned long long* sse, int cap) {
+    if (!ctx) return TZ_ERR_INVALID;
+    if (ctx->rollout_kind != tz_ctx::ROLLOUT_ENCODE || !ctx->loop_closed || !ctx->loop_frames || ctx->loop_trace.empty())
+        return tz_fail(ctx, TZ_ERR_STATE, "tz_loop_search_trace: the resident rollout is no tz_rollout_closed_frames that searched its bounds");
+    const int n = (int)ctx->loop_trace.size();
+    if (sse && cap < n) return tz_fail(ctx, TZ_ERR_INVALID, "tz_loop_search_trace: room for %d sums, the search has %d", cap, n);
+    if (sse) memcpy(sse, ctx->loop_trace.data(), (size_t)n * sizeof(unsigned long long));
+    return n;
 }
 
 extern "C" int tz_rollout_loop(tz_ctx* ctx) {

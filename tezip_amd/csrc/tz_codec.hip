@@ -5795,6 +5795,161 @@ int tzk_cl_recon(tz_ctx* ctx, const float* pred, const int16_t* q, uint8_t* dec,
     return cl_launch(ctx, pred, nullptr, q, dec, d_list, nlist, H, W, Hp, Wp, 0);
 }
 
+// ------------------------------------------------------------------------ closed loop, one abs bound per frame (TZ-CLF1)
+// tz_rollout_closed_frames (include/tezip_hip.h; slow statement in tezip_amd/closedframes.py): TZ-CL1 with
+// the radius E of a frame's own bound, given (E[nt]) or found while the loop stands at the frame: when a step's predictions
+// exist, every candidate k of the bisection lo = 0, hi = 511, mid = (lo + hi) / 2, pass <=> sse(mid) <= limit is priced by one
+// pass over (pred, orig) -- sse(k) = sum (clamp(x - Q_{k >> 1}(x - orig), 0, 255) - orig)^2, an exact integer.
+//   k_clf_probe  round r for every frame of the step: a workgroup replays rounds 0 .. r - 1 of its frame from sse[round][frame]
+//                (uniform scalar work), leaves at once when the interval has closed, else adds its samples' squared errors under
+//                E = mid >> 1 to sse[r][frame].  Integer sums: no order shows.  Round r + 1 is the next launch; nothing else
+//                synchronises.
+//   k_clf_step   k_cl_step with the frame's E: E[frame], or lo >> 1 of the replay of all CLF_ROUNDS rounds, in which case one
+//                lane per frame also leaves k = lo and sse(k) (0 for k = 0, which is never probed).
+// Sample mapping, FLAT and vec as cl_frames.
+constexpr int CLF_ROUNDS = TZ_CLF_ROUNDS;
+constexpr int CLF_K_END = 511;   // candidates k = 0 .. 510
+static_assert((1 << CLF_ROUNDS) >= CLF_K_END, "the interval [0, 511) closes within the rounds");
+
+struct clf_interval {
+    int lo, hi;
+    unsigned long long sse_lo;
+};
+
+// the bisection of frame f after `rounds` rounds (those behind a closed interval did not run and are not read)
+__device__ __forceinline__ clf_interval clf_replay(const unsigned long long* __restrict__ sse, int nt, size_t f, int rounds,
+                                                   unsigned long long limit) {
+    clf_interval s{0, CLF_K_END, 0ull};
+    for (int i = 0; i < rounds && s.hi - s.lo > 1; ++i) {
+        const int mid = (s.lo + s.hi) >> 1;
+        const unsigned long long v = sse[(size_t)i * nt + f];
+        if (v <= limit) {
+            s.lo = mid;
+            s.sse_lo = v;
+        } else {
+            s.hi = mid;
+        }
+    }
+    return s;
+}
+
+__device__ __forceinline__ unsigned clf_err2(float p, int o, int E) {
+    const int e = (int)cl_sample(p, o, E) - o;
+    return (unsigned)(e * e);
+}
+
+template <bool FLAT>
+__global__ __launch_bounds__(256) void k_clf_probe(const float* __restrict__ pred, const uint8_t* __restrict__ orig, const int* __restrict__ list,
+                                                   int H, int W, int Hp, int Wp, int vec, int round, unsigned long long* __restrict__ sse,
+                                                   int nt, unsigned long long limit) {
+    const size_t f = (size_t)list[blockIdx.y];
+    const clf_interval s = clf_replay(sse, nt, f, round, limit);
+    if (s.hi - s.lo <= 1) return;   // (uniform: the whole workgroup leaves)
+    const int E = ((s.lo + s.hi) >> 1) >> 1;
+    const unsigned row = (unsigned)W * 3u, pitch = (unsigned)Wp * 3u;
+    const size_t fe = (size_t)H * row, base = f * fe;
+    const float* pf = pred + f * (size_t)Hp * pitch;
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t head = vec ? min(fe, (size_t)((16u - (unsigned)(base & 15)) & 15u)) : fe;
+    const size_t n16 = (fe - head) / 16;
+    // a group's 16 squared errors are summed in 32 bits, everything wider in 64: no bound on the frame size is needed
+    static_assert(16ull * 65025ull < (1ull << 32), "16 squared errors of at most 255^2 fit 32 bits");
+    unsigned long long acc = 0;
+    for (size_t g = t0; g < n16; g += stride) {
+        const size_t r0 = head + 16 * g;
+        float p[16];
+        if (FLAT) {
+            const float4* p4 = (const float4*)(pf + r0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4 v = p4[j];
+                p[4 * j] = v.x; p[4 * j + 1] = v.y; p[4 * j + 2] = v.z; p[4 * j + 3] = v.w;
+            }
+        } else {
+            size_t y = r0 / row;
+            unsigned xc = (unsigned)(r0 - y * row);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                p[j] = pf[y * pitch + xc];
+                if (++xc == row) {
+                    xc = 0;
+                    ++y;
+                }
+            }
+        }
+        const uint4 o = *(const uint4*)(orig + base + r0);
+        const unsigned w[4] = {o.x, o.y, o.z, o.w};
+        unsigned part = 0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) part += clf_err2(p[j], (int)((w[j >> 2] >> (8 * (j & 3))) & 0xFFu), E);
+        acc += part;
+    }
+    const size_t v_end = head + 16 * n16, nscalar = head + (fe - v_end);
+    for (size_t j = t0; j < nscalar; j += stride) {
+        const size_t r = j < head ? j : v_end + (j - head);
+        acc += clf_err2(cl_pred(pf, r, row, pitch), (int)orig[base + r], E);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(&sse[(size_t)round * nt + f], acc);   // one 64-bit vector atomic a wave
+}
+
+template <bool FLAT>
+__global__ __launch_bounds__(256) void k_clf_step(const float* __restrict__ pred, const uint8_t* __restrict__ orig, uint8_t* __restrict__ dec,
+                                                  const int* __restrict__ list, int H, int W, int Hp, int Wp, int vec,
+                                                  const int* __restrict__ radius, const unsigned long long* __restrict__ sse, int nt,
+                                                  unsigned long long limit, int* __restrict__ k_out, unsigned long long* __restrict__ sse_out) {
+    const size_t f = (size_t)list[blockIdx.y];
+    int E;
+    if (radius) {
+        E = radius[f];
+    } else {
+        const clf_interval s = clf_replay(sse, nt, f, CLF_ROUNDS, limit);
+        E = s.lo >> 1;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            k_out[f] = s.lo;
+            sse_out[f] = s.sse_lo;
+        }
+    }
+    cl_frames<false, FLAT>(pred, orig, nullptr, dec, list, H, W, Hp, Wp, E, vec);
+}
+
+static dim3 clf_grid(int nlist, int H, int W) {   // (cl_launch's)
+    const size_t fe = (size_t)H * W * 3;
+    return dim3((unsigned)std::max<size_t>(1, std::min<size_t>((fe / 16 + 255) / 256, 64)), (unsigned)nlist);
+}
+
+int tzk_clf_probe(tz_ctx* ctx, const float* pred, const uint8_t* orig, const int* d_list, int nlist, int H, int W, int Hp, int Wp, int round,
+                  unsigned long long* d_sse, int nt, unsigned long long limit) {
+    if (nlist <= 0) return TZ_OK;
+    if (round < 0 || round >= CLF_ROUNDS) return tz_fail(ctx, TZ_ERR_INVALID, "tzk_clf_probe: round %d", round);
+    const int vec = ((((uintptr_t)orig | (uintptr_t)pred) & 15) == 0) ? 1 : 0;
+    const dim3 grid = clf_grid(nlist, H, W);
+    tz_prof_scope ps(ctx, TZP_QUANT);
+    if (vec && H == Hp && W == Wp)
+        hipLaunchKernelGGL(k_clf_probe<true>, grid, dim3(256), 0, ctx->stream, pred, orig, d_list, H, W, Hp, Wp, vec, round, d_sse, nt, limit);
+    else
+        hipLaunchKernelGGL(k_clf_probe<false>, grid, dim3(256), 0, ctx->stream, pred, orig, d_list, H, W, Hp, Wp, vec, round, d_sse, nt, limit);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
+int tzk_clf_step(tz_ctx* ctx, const float* pred, const uint8_t* orig, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp,
+                 const int* d_radius, const unsigned long long* d_sse, int nt, unsigned long long limit, int* d_k, unsigned long long* d_sse_out) {
+    if (nlist <= 0) return TZ_OK;
+    const int vec = ((((uintptr_t)dec | (uintptr_t)orig | (uintptr_t)pred) & 15) == 0) ? 1 : 0;
+    const dim3 grid = clf_grid(nlist, H, W);
+    tz_prof_scope ps(ctx, TZP_QUANT);
+    if (vec && H == Hp && W == Wp)
+        hipLaunchKernelGGL(k_clf_step<true>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, d_list, H, W, Hp, Wp, vec, d_radius, d_sse, nt,
+                           limit, d_k, d_sse_out);
+    else
+        hipLaunchKernelGGL(k_clf_step<false>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, d_list, H, W, Hp, Wp, vec, d_radius, d_sse, nt,
+                           limit, d_k, d_sse_out);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // ------------------------------------------------------------------------ per-tile choice of the prediction (TZ-PS1)
 // tz_set_pred_select (include/tezip_hip.h; slow statement in tezip_amd/predselect.py): in a closed loop every
 // 16 x 16 tile of a predicted frame takes whichever of x_net = (int)(pred * 255.0f) and x_prev = dec[t-1] leaves the smaller

@@ -89,6 +89,12 @@ struct tz_ctx {
     int loop_closed = 0;
     int loop_mode = 0, loop_quantiser = 0;
     double loop_b0 = 0.0, loop_b1 = 0.0;
+    // tz_rollout_closed_frames (TZ-CLF1): the stamped loop ran under one abs bound per frame -- loop_bounds, 0 at fixed frames,
+    // which tz_set_frame_bounds must hold for the rollout to serve a job; loop_frame_sse: sse(k) of a searched frame (0: given
+    // bounds); loop_trace: the search's TZ_CLF_ROUNDS * nt sums, round-major, ~0 where a round did not run (empty: given bounds)
+    int loop_frames = 0;
+    std::vector<double> loop_bounds;
+    std::vector<unsigned long long> loop_frame_sse, loop_trace;
     // tz_set_pred_select (TZ-PS1): the setting; whether the stamped loop ran under it (part of the stamp: predictions with chosen
     // tiles expressed in them serve a select job alone, and the other way round); the modes of that loop (nt * TH * TW bytes,
     // tz_pred_modes), and the modes a decoder was given (tz_put_pred_modes) for its next tz_rollout_decode_closed
@@ -506,6 +512,15 @@ int tzk_key_unresid(tz_ctx*, const int16_t* d_sym, int H, int W, const int* d_id
 int tzk_cl_step(tz_ctx*, const float* pred, const uint8_t* orig, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp,
                 int E);
 int tzk_cl_recon(tz_ctx*, const float* pred, const int16_t* q, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp);
+// TZ-CLF1 (tz_rollout_closed_frames): the closed loop under one abs bound per frame.  d_sse: TZ_CLF_ROUNDS * nt sums, round-major,
+// zeroed once per rollout.  tzk_clf_probe: round `round` of the bisection against `limit` for the nlist frames of a step (a frame
+// whose interval has closed is left alone).  tzk_clf_step: tzk_cl_step with E = d_radius[frame], or (d_radius NULL) with the result
+// of the frame's TZ_CLF_ROUNDS rounds, which also leaves k in d_k[frame] and sse(k) in d_sse_out[frame].
+constexpr int TZ_CLF_ROUNDS = 9;
+int tzk_clf_probe(tz_ctx*, const float* pred, const uint8_t* orig, const int* d_list, int nlist, int H, int W, int Hp, int Wp, int round,
+                  unsigned long long* d_sse, int nt, unsigned long long limit);
+int tzk_clf_step(tz_ctx*, const float* pred, const uint8_t* orig, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp,
+                 const int* d_radius, const unsigned long long* d_sse, int nt, unsigned long long limit, int* d_k, unsigned long long* d_sse_out);
 // per-tile choice of the prediction TZ-PS1 (tezip_amd/predselect.py) on the same frames and stacks; modes: nt * ceil(H/16) * ceil(W/16)
 // bytes on the device, frame-major.  Per 16 x 16 tile, x_prev = the frame in front (orig[t-1] for tzk_ps_select, dec[t-1] for the
 // others) replaces x_net = the truncated prediction iff it leaves the smaller sum |Q(x - orig)| (TZ-QL1 with E, the identity for

@@ -149,12 +149,13 @@ def _entries(seq, where):
     return out
 
 
-def load(spec):
+def load(spec, flag="--frame-bounds", name="FRAME_BOUNDS"):
     """spec: the path of a JSON file -- a list of numbers, or an object with a "frame_bounds" list (the bound_search.json of a
-    per-frame search replays) -- or a sequence of numbers.  -> the list of floats.  ValueError names the file and the index."""
+    per-frame search replays) -- or a sequence of numbers.  -> the list of floats.  ValueError names the file and the index.
+    flag, name: what the messages call the command-line flag and compress.run's argument (--loop-bounds reads the same files)."""
     if isinstance(spec, (str, bytes, os.PathLike)):
         path = os.fspath(spec)
-        where = "--frame-bounds %s" % path
+        where = "%s %s" % (flag, path)
         try:
             with open(path, "r", encoding="UTF-8") as f:
                 doc = json.load(f)
@@ -170,18 +171,18 @@ def load(spec):
     try:
         seq = [v.item() if hasattr(v, "item") else v for v in spec]
     except TypeError:
-        raise ValueError("FRAME_BOUNDS: a path or a sequence of numbers is wanted, got %r" % (spec,)) from None
-    return _entries(seq, "FRAME_BOUNDS")
+        raise ValueError("%s: a path or a sequence of numbers is wanted, got %r" % (name, spec)) from None
+    return _entries(seq, name)
 
 
-def where_of(spec):
-    return "--frame-bounds %s" % os.fspath(spec) if isinstance(spec, (str, bytes, os.PathLike)) else "FRAME_BOUNDS"
+def where_of(spec, flag="--frame-bounds", name="FRAME_BOUNDS"):
+    return "%s %s" % (flag, os.fspath(spec)) if isinstance(spec, (str, bytes, os.PathLike)) else name
 
 
-def check_length(bounds, nt, spec):
+def check_length(bounds, nt, spec, flag="--frame-bounds", name="FRAME_BOUNDS"):
     """None, or the refusal of a list that does not have one entry per image."""
     if len(bounds) != int(nt):
-        return "%s: %d bounds for %d images" % (where_of(spec), len(bounds), int(nt))
+        return "%s: %d bounds for %d images" % (where_of(spec, flag, name), len(bounds), int(nt))
     return None
 
 

@@ -15,7 +15,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "tezip_amd"
 
-from . import boundmap, closedloop, compress, decompress, frametarget, predmotion, predselect, sdauto, target, train  # noqa: E402
+from . import boundmap, closedframes, closedloop, compress, decompress, frametarget, predmotion, predselect, sdauto, target, train  # noqa: E402
 
 # (short, long, argparse keywords) -- tezip.py:88-99
 FLAG_TABLE = (
@@ -124,6 +124,15 @@ FLAG_TABLE = (
     # holds one byte per chosen tile (definition TZ-PM1 in tezip_amd/predmotion.py).
     # -u recognises the stream by the mark in its trailer (compress.run(PRED=...))
     (None, "--pred", dict(type=str, choices=("net", "select", "motion"), default=None, dest="pred")),
+    # not in the reference: with -c --loop closed --quant lattice, IN PLACE of -m and -b: every frame that is not stored exactly
+    # reaches DB dB.  The ONE closed-loop rollout finds each frame's abs bound (a multiple of 0.5) when the loop stands at that
+    # frame, where its prediction no longer depends on anything undecided (definition TZ-CLF1 in tezip_amd/closedframes.py; per
+    # frame a boundary, greedy in time).  bound_search.json holds the search; -u needs no flag (compress.run(LOOP_PSNR=DB))
+    (None, "--loop-psnr", dict(type=float, default=None, metavar="DB", dest="loop_psnr")),
+    # not in the reference: with -c --loop closed --quant lattice -m abs, IN PLACE of -b: one abs bound per image for the closed
+    # loop, from a JSON file as --frame-bounds reads it (the bound_search.json of a --loop-psnr job replays); entries at frames that
+    # are stored exactly are taken as 0 (compress.run(LOOP_BOUNDS=FILE))
+    (None, "--loop-bounds", dict(type=str, default=None, metavar="FILE", dest="loop_bounds")),
 )
 
 TEXT = {
@@ -309,6 +318,28 @@ def check_loop_flag(arg):
                                   getattr(arg, "bound_map", None))
 
 
+def check_closedframes_flags(arg):
+    """--loop-psnr and --loop-bounds go with -c --loop closed --quant lattice of one single-GPU job, in place of -b (and of -m for
+    --loop-psnr).  The file of --loop-bounds is read here (its length is checked once the images are listed).  Returns None, or
+    the message of a refusal."""
+    db, path = getattr(arg, "loop_psnr", None), getattr(arg, "loop_bounds", None)
+    if db is None and path is None:
+        return None
+    problem = closedframes.check_flags(
+        db, path, getattr(arg, "loop", None), getattr(arg, "quant", None), arg.mode[0] if arg.mode else None, arg.bound or [],
+        getattr(arg, "pred", None), arg.compress is not None and arg.uncompress is None and arg.learn is None,
+        getattr(arg, "sweep", None) is not None, int(os.environ.get("WORLD_SIZE", "1")) > 1, bool(getattr(arg, "gray", False)),
+        arg.threshold[0] if arg.threshold is not None else None, getattr(arg, "target_psnr", None), getattr(arg, "target_ratio", None),
+        bool(getattr(arg, "per_frame", False)), getattr(arg, "frame_bounds", None), getattr(arg, "bound_map", None))
+    if problem or path is None:
+        return problem
+    try:
+        closedframes.load(path)
+    except ValueError as e:
+        return str(e)
+    return None
+
+
 def check_pred_flag(arg):
     """--pred is valid with -c only; `select` and `motion` need --loop closed.  Returns None, or the message of a refusal."""
     pred = getattr(arg, "pred", None)
@@ -453,6 +484,10 @@ def _main(arg):
     if problem:   # exit status 2, as decompress.adopt_contract's errors: nothing was written
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_closedframes_flags(arg)
+    if problem:   # likewise (in front of --loop's check: a refusal of this job names the flag that defines it)
+        print("ERROR:", problem)
+        sys.exit(2)
     problem = check_loop_flag(arg)
     if problem:   # likewise (in front of the other flags' checks: a refusal of this job names the flag that defines it)
         print("ERROR:", problem)
@@ -538,7 +573,12 @@ def _main(arg):
     db, ratio = getattr(arg, "target_psnr", None), getattr(arg, "target_ratio", None)
     per_frame, bounds_file = bool(getattr(arg, "per_frame", False)), getattr(arg, "frame_bounds", None)
     map_file = getattr(arg, "bound_map", None)
-    if bounds_file is not None or map_file is not None:   # an `abs` job whose bounds come from the file: the same checks with a bound in -b's place
+    loop_db, loop_file = getattr(arg, "loop_psnr", None), getattr(arg, "loop_bounds", None)
+    if loop_db is not None:   # an `abs` job whose bounds the closed loop finds: the same checks, and `abs` is printed
+        problem = check_compress(argparse.Namespace(**dict(vars(arg), mode=["abs"], bound=[0.0])))
+    elif loop_file is not None:   # an `abs` job whose bounds come from the file
+        problem = check_compress(argparse.Namespace(**dict(vars(arg), bound=[0.0])))
+    elif bounds_file is not None or map_file is not None:   # an `abs` job whose bounds come from the file: the same checks with a bound in -b's place
         problem = check_compress(argparse.Namespace(**dict(vars(arg), bound=[0.0])))
     elif db is not None or ratio is not None:   # the job is an `abs` job whose bound is still to be found: the same checks, and `abs` is printed
         problem = check_compress(argparse.Namespace(**dict(vars(arg), mode=["abs"], bound=[0.0])))
@@ -553,6 +593,13 @@ def _main(arg):
                          arg.no_entropy)
     window = arg.window[0] if arg.window is not None else None
     threshold = arg.threshold[0] if arg.threshold is not None else None
+    if loop_db is not None or loop_file is not None:   # TZ-CLF1 (every other flag travels with it; the jobs without it are the calls below)
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu, arg.verbose,
+                            arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), SDELTA=getattr(arg, "sdelta", None) or "flat",
+                            SSIM=bool(getattr(arg, "ssim", False)), QUANT="lattice", LOOP="closed",
+                            **({"LOOP_PSNR": loop_db} if loop_db is not None else {"LOOP_BOUNDS": loop_file}))
     if getattr(arg, "loop", None) == "closed":   # (open is the job without the flag: the calls below; every other flag travels with it)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu, arg.verbose,
                             arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
