@@ -252,6 +252,25 @@ int tz_rollout_closed_frames(tz_ctx* ctx, const uint8_t* frames, int nt, int H, 
                              unsigned long long sse_limit, uint8_t* key_mask);
 int tz_loop_frame_bounds(tz_ctx* ctx, double* bounds, unsigned long long* sse, int cap);
 int tz_loop_search_trace(tz_ctx* ctx, unsigned long long* sse, int cap);
+/* ---- the closed loop under one abs bound per pixel, definition TZ-CLM1 (no reference counterpart; `tezip.py -c --loop closed --quant
+ * lattice -m abs --loop-map FILE`; slow statement in tezip_amd/closedmap.py).  TZ-CL1 except for the quantiser
+ * of a non-key frame: q = Q_{M[p]}(d), TZ-QL1 with E = M[p] of the bound map in force (tz_set_bound_map), the same E for the three
+ * channels of a pixel in every frame; dec = clamp(x - q, 0, 255) is fed to the next step.  |dec - orig| <= M[p] at every sample, a
+ * pixel with M = 0 is restored exactly, a map that is k everywhere gives tz_rollout_closed's job under abs k byte for byte.
+ * tz_rollout_closed_map: frames, nt, H, W, warm_up, window, key_mask as tz_rollout_closed (frames NULL: the staged stack).
+ *   TZ_ERR_STATE without a bound map in force, TZ_ERR_INVALID when its size is not H x W (both name tz_set_bound_map).
+ *   TZ_ERR_UNSUPPORTED, naming the setter, unless: tz_set_quantiser(1), a three-channel payload, no tz_set_frame_bounds in force, no
+ *   tz_set_pred_motion, window > 0.  Under tz_set_pred_select(1) it runs TZ-PS1 with that Q (cost_c = sum |Q_{M[p]}(x_c - orig)|),
+ *   and tz_pred_modes delivers the modes as after tz_rollout_closed.  A map of zeros takes the lossless closed job's one schedule.
+ *   Per step: the predictor, then k_clm_step (or k_psm_step), which reads the context's own H*W-byte map; no host wait inside the loop.
+ *   It stamps the loop as tz_rollout_closed does (tz_rollout_loop returns 1), and the stamp carries the map's bytes: tz_encode,
+ *   tz_encode_begin, tz_encode_delta, tz_bound_probe, tz_size_probe and tz_sdelta_probe return TZ_ERR_STATE, naming
+ *   tz_rollout_closed_map, unless the mode is TZ_MODE_ABS, the quantiser the lattice and the map in force holds exactly those bytes
+ *   (b0 / b1 are not read; setting an equal map again is fine).  The unchanged back half then forms the loop's q again
+ *   (tz_encode_begin and tz_size_probe go on to refuse any bound map, as ever), tz_encode_map_check and the quality, SSIM and digest
+ *   entries work on the payload, and the stream is an ordinary closed-loop stream: tz_rollout_decode_closed decodes it and never
+ *   sees a bound.  tz_rollout_closed under a map stays TZ_ERR_UNSUPPORTED. */
+int tz_rollout_closed_map(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, uint8_t* key_mask);
 /* ---- per-tile choice between the network and the frame in front, definition TZ-PS1 (no reference counterpart;
  * `tezip.py -c --loop closed --pred select`, DESIGN.md section 9, slow statement in tezip_amd/predselect.py).  In a closed loop both
  * sides hold dec[t-1] when frame t is predicted: a second predictor.  TZ-PS1 is TZ-CL1 except for the value x of a non-key frame:

@@ -60,6 +60,7 @@ _SIGS = {
     "tz_rollout_loop": (C.c_int, [C.c_void_p]),
     "tz_rollout_closed_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_ulonglong,
                                            C.c_void_p]),
+    "tz_rollout_closed_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tz_loop_frame_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "tz_loop_search_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "tz_rollout_decode_closed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
@@ -632,6 +633,21 @@ class Context:
         key = np.zeros(nt, np.uint8)
         self._ck(self.lib.tz_rollout_closed_frames(self.h, None if frames is None else _ptr(frames, np.uint8), nt, h, w, warm_up,
                                                    int(window or 0), None if b is None else b.ctypes.data, int(sse_limit), key.ctypes.data))
+        self._shape = (nt, h, w)
+        return key.astype(bool)
+
+    def rollout_closed_map(self, frames, warm_up, window):
+        """tz_rollout_closed_map (TZ-CLM1, tezip_amd/closedmap.py): the closed loop under the bound map in force (set_bound_map), one
+        abs bound per pixel; with set_pred_select(True) the per-tile selection under that map.  Needs the lattice quantiser; frames
+        as for rollout.  Returns the key mask; the job runs under the same map: encode("abs", [0.0], ...)."""
+        if frames is None:
+            nt, h, w = self._staged
+        else:
+            self._check_stack(frames, "frames")
+            nt, h, w = frames.shape[:3]
+        key = np.zeros(nt, np.uint8)
+        self._ck(self.lib.tz_rollout_closed_map(self.h, None if frames is None else _ptr(frames, np.uint8), nt, h, w, warm_up,
+                                                int(window or 0), key.ctypes.data))
         self._shape = (nt, h, w)
         return key.astype(bool)
 

@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib, boundmap, closedframes, closedloop, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, predmotion, predselect, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
+from . import _lib, boundmap, closedframes, closedloop, closedmap, digest, frametarget, huff, huffd, huffr, keycoder, keycoderg, lattice, predmotion, predselect, quality, ratetarget, sdauto, sdelta, sidecar, target, weights, zstd
 from . import dist as tzdist
 from .data_utils import padding_shape
 
@@ -568,7 +568,7 @@ def check_ratio(ratio, mode, bound, target_psnr, coder, shuffle, sharded):
 def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, MODE, BOUND_VALUE, GPU_FLAG, VERBOSE,
         ENTROPY_RUN, device=0, SHUFFLE=False, REPORT=False, CODER="zstd", KEY_CODER="zstd", DIGESTS=False, GRAY=False, SDELTA="flat",
         SSIM=False, TARGET_PSNR=None, TARGET_RATIO=None, PER_FRAME=False, FRAME_BOUNDS=None, QUANT="greedy", BOUND_MAP=None,
-        LOOP="open", PRED="net", LOOP_PSNR=None, LOOP_BOUNDS=None):
+        LOOP="open", PRED="net", LOOP_PSNR=None, LOOP_BOUNDS=None, LOOP_MAP=None):
     """SHUFFLE (--shuffle; NOT in the reference): store the payload as byte planes.  Off by default:
     a shuffled entropy.dat is flagged in its trailer and is not readable by the reference.
     REPORT (--report; NOT in the reference): also write quality.json -- per frame and for the sequence the error the
@@ -660,6 +660,14 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     found; `-u` takes no flag.  LOOP_BOUNDS (--loop-bounds): the bounds given instead -- a path or a sequence as FRAME_BOUNDS
     takes them (a bound_search.json replays).  Not with PRED "select" / "motion", nor with anything LOOP "closed" refuses.
 
+    LOOP_MAP (--loop-map; NOT in the reference; LOOP "closed", QUANT "lattice", MODE "abs", an empty BOUND_VALUE): one abs bound per
+    pixel for the closed loop, definition TZ-CLM1 (tezip_amd/closedmap.py) -- a path as BOUND_MAP takes it, or a 2-D uint8 array of
+    the images' own size.  The closed-loop rollout (tz_rollout_closed_map) decodes every pixel under its own tolerance, with PRED
+    "select" the tiles are chosen under the map, and the job then runs under tz_set_bound_map with that map; `-u` takes no flag.
+    tezip_amd.json is the closed job's plus BOUND_MAP's informational "bound_map"; with REPORT quality.json gains BOUND_MAP's
+    object and the per-frame violations.  Not with PRED "motion", BOUND_MAP, LOOP_PSNR or LOOP_BOUNDS, nor with anything LOOP
+    "closed" refuses.
+
     PRED (--pred; NOT in the reference): "net" (the default: every file, line and launch is what it is without it) or, with LOOP
     "closed", "select": every 16 x 16 tile of a predicted frame takes whichever of the network's prediction and the decoded frame
     in front leaves the smaller quantised residual, definition TZ-PS1 (tezip_amd/predselect.py).  One line says how many tiles
@@ -702,6 +710,18 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
     if problem:   # likewise
         print("ERROR:", problem)
         sys.exit(2)
+    loop_map = None
+    if LOOP_MAP is not None:   # likewise (in front of every other check: a refusal of this job names the flag that defines it)
+        problem = closedmap.check_flags(LOOP_MAP, LOOP, QUANT, MODE, BOUND_VALUE, PRED, True, False, tzdist.active() is not None, GRAY,
+                                        THRESHOLD, TARGET_PSNR, TARGET_RATIO, PER_FRAME, FRAME_BOUNDS, BOUND_MAP, LOOP_PSNR, LOOP_BOUNDS)
+        if not problem:
+            try:
+                loop_map = closedmap.load(LOOP_MAP)
+            except ValueError as e:
+                problem = str(e)
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     loop_frames = LOOP_PSNR is not None or LOOP_BOUNDS is not None
     loop_bounds = None
     if loop_frames:   # likewise (in front of --loop's check: a refusal of this job names the flag that defines it)
@@ -781,6 +801,11 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
         if problem:
             print("ERROR:", problem)
             sys.exit(2)
+    if loop_map is not None:   # likewise
+        problem = closedmap.check_size(loop_map, H, W, LOOP_MAP if isinstance(LOOP_MAP, (str, os.PathLike)) else "LOOP_MAP")
+        if problem:
+            print("ERROR:", problem)
+            sys.exit(2)
     if bound_map is not None:   # likewise
         problem = boundmap.check_size(bound_map, H, W, BOUND_MAP if isinstance(BOUND_MAP, (str, os.PathLike)) else "BOUND_MAP")
         if problem:
@@ -833,6 +858,17 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
                     key = ctx.rollout_closed_frames(None, PREPROCESS, WINDOW_SIZE, bounds=loop_bounds)
                     frame_bounds = [float(b) for b in ctx.loop_frame_bounds()[0]]   # (0 at the frames stored exactly)
                     print(closedframes.explicit_line(frame_bounds))
+            elif closed and loop_map is not None:   # TZ-CLM1: TZ-CL1 under one abs bound per pixel; the job below runs under the same map
+                print(closedloop.STDOUT_LINE)
+                ctx.set_bound_map(loop_map)
+                print(closedmap.stdout_line(loop_map))
+                if select:
+                    ctx.set_pred_select(True)
+                key = ctx.rollout_closed_map(None, PREPROCESS, WINDOW_SIZE)
+                if select:
+                    modes = ctx.pred_modes()
+                    print(predselect.stdout_line(modes[~key]))
+                bound_map, BOUND_MAP, BOUND_VALUE = loop_map, LOOP_MAP, [0.0]   # (what the report and the sidecar say about a map)
             elif closed:   # TZ-CL1: the decoded frame is fed back, under the job's own bound and quantiser (no window MSE exists)
                 print(closedloop.STDOUT_LINE)
                 if select:   # TZ-PS1: per tile, the network or the decoded frame in front
@@ -871,7 +907,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             elif frame_bounds is not None and not loop_frames:
                 frame_bounds = [0.0 if fx else b for fx, b in zip(frametarget.fixed_frames(key, PREPROCESS), frame_bounds)]
                 print(frametarget.explicit_line(frame_bounds))
-            if bound_map is not None:   # the job: abs, pixel p under bound_map[p] in every frame (BOUND_VALUE is not read)
+            if bound_map is not None and loop_map is None:   # the job: abs, pixel p under bound_map[p] in every frame (BOUND_VALUE is not read)
                 ctx.set_bound_map(bound_map)
                 print(boundmap.stdout_line(bound_map))
                 BOUND_VALUE = [0.0]
@@ -953,6 +989,7 @@ def run(WEIGHTS_DIR, DATA_DIR, OUTPUT_DIR, PREPROCESS, WINDOW_SIZE, THRESHOLD, M
             if closed:
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),
                                     payload_channels=channels, sdelta=sd_mode, quant=QUANT, loop="closed",
+                                    **({"bound_map": boundmap.stats(loop_map)} if loop_map is not None else {}),
                                     **({"pred": "select"} if select else {"pred": "motion"} if motion else {}))
             elif bound_map is not None:
                 doc = sidecar.write(OUTPUT_DIR, ctx.rollout_contract(), wts, hp, wp, (nt, H, W, PREPROCESS),

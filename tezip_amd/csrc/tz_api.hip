@@ -688,6 +688,7 @@ static void set_rollout(tz_ctx* ctx, tz_ctx::tz_rollout_kind kind, int pred_firs
     ctx->loop_select = 0;
     ctx->loop_motion = 0;
     ctx->loop_frames = 0;   // (tz_rollout_closed_frames likewise)
+    ctx->loop_map = 0;      // (tz_rollout_closed_map likewise)
     ctx->pred_modes.clear();
     ctx->pred_vectors.clear();
     ctx->pred_first = pred_first;
@@ -1560,6 +1561,18 @@ static int loop_check(tz_ctx* ctx, const char* who, int mode, double b0, double 
                        "%s: the resident predictions are those of a closed loop (tz_rollout_closed) run %s motion-compensated tiles "
                        "(tz_set_pred_motion(%d)); they serve that kind of job alone, the setting is now %d",
                        who, ctx->loop_motion ? "with" : "without", ctx->loop_motion, ctx->pred_motion);
+    if (ctx->loop_map) {   // TZ-CLM1: every pixel was decoded under its own bound; the job is the one under exactly that map
+        const bool same_map = ctx->map_h == ctx->loop_map_h && ctx->map_w == ctx->loop_map_w && ctx->map_host == ctx->loop_map_bytes;
+        if (mode == TZ_MODE_ABS && ctx->quantiser == 1 && same_map && ctx->frame_bounds.empty() && ctx->payload_channels == 3) return TZ_OK;
+        return tz_fail(ctx, TZ_ERR_STATE,
+                       "%s: the resident predictions are those of a closed loop run under one abs bound per pixel "
+                       "(tz_rollout_closed_map); they serve the abs job of the lattice quantiser (tz_set_quantiser(1)) under "
+                       "tz_set_bound_map with exactly that %d x %d map alone, not mode %d, quantiser %d, %s%s%s",
+                       who, ctx->loop_map_h, ctx->loop_map_w, mode, ctx->quantiser,
+                       !ctx->map_h ? "no bound map" : (same_map ? "that map" : "another bound map"),
+                       ctx->frame_bounds.empty() ? "" : ", frame bounds (tz_set_frame_bounds)",
+                       ctx->payload_channels == 3 ? "" : ", a one-channel payload (tz_set_payload_channels)");
+    }
     if (ctx->loop_frames) {   // TZ-CLF1: every frame was decoded under its own bound; the job is the one under exactly those bounds
         if (mode == TZ_MODE_ABS && ctx->quantiser == 1 && ctx->frame_bounds == ctx->loop_bounds && !ctx->map_h && ctx->payload_channels == 3)
             return TZ_OK;
@@ -1615,6 +1628,7 @@ extern "C" int tz_set_bound_map(tz_ctx* ctx, const uint8_t* map, int H, int W) {
     if (!map) {
         if (ctx->map_h) ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under the map
         ctx->map_h = ctx->map_w = ctx->map_max = 0;
+        ctx->map_host.clear();
         return TZ_OK;
     }
     if (H < 1 || W < 1) return tz_fail(ctx, TZ_ERR_INVALID, "tz_set_bound_map: a map of %d x %d", H, W);
@@ -1638,6 +1652,7 @@ extern "C" int tz_set_bound_map(tz_ctx* ctx, const uint8_t* map, int H, int W) {
     ctx->map_h = H;
     ctx->map_w = W;
     ctx->map_max = mx;
+    ctx->map_host.assign(map, map + n);   // (what a tz_rollout_closed_map stamps its loop with)
     ctx->enc_kind = tz_ctx::ENC_NONE;   // a resident payload was made under another tolerance
     return TZ_OK;
 }
@@ -2317,28 +2332,10 @@ extern "C" int tz_put_pred_vectors(tz_ctx* ctx, const int8_t* vectors, size_t n)
     return TZ_OK;
 }
 
-extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, int mode, double b0,
-                                 double b1, uint8_t* key_mask) {
-    tz_roctx_range roctx_("tz_rollout_closed");
-    if (!ctx) return TZ_ERR_INVALID;
-    ctx->enc_kind = tz_ctx::ENC_NONE;
-    if (window < 0) return tz_fail(ctx, TZ_ERR_INVALID, "window must be >= 0");
-    if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
-    if (std::isnan(b0) || (mode == TZ_MODE_ABSREL && std::isnan(b1)))
-        return tz_fail(ctx, TZ_ERR_INVALID, "error bound is NaN (the reference raises on a NaN tolerance)");
-    if (window == 0)
-        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: the closed loop serves fixed windows (window > 0), not the threshold rule");
-    if (nt < warm_up + 2)
-        return tz_fail(ctx, TZ_ERR_INVALID, "need at least warm_up+2 frames (nt=%d, warm_up=%d)", nt, warm_up);
-    // what the loop feeds back: the original where the job's quantiser leaves every delta as it is, else TZ-QL1 under one abs bound
-    const bool lossless = b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0) ||
-                          (ctx->quantiser == 1 ? tz_lattice_is_identity(mode, b0, b1) : tz_quant_is_identity(mode, b0, b1));
-    if (!lossless && ctx->quantiser != 1)
-        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: a lossy closed loop needs the lattice quantiser (tz_set_quantiser(1)): the greedy walk is no function of one sample");
-    if (!lossless && mode != TZ_MODE_ABS)
-        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: a lossy closed loop takes mode abs, not %d: rel bounds depend on whole frames", mode);
-    if (ctx->payload_channels != 3 || !ctx->frame_bounds.empty() || ctx->map_h)
-        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: the closed loop takes one bound and a three-channel payload (no tz_set_payload_channels(1), tz_set_frame_bounds or tz_set_bound_map)");
+// The loop of tz_rollout_closed and tz_rollout_closed_map behind their checks: the key mask and groups, the lossless job's one
+// schedule or the steps, each decoded under E (d_map NULL) or under d_map[pixel], and the stamp both share.
+static int closed_rollout(tz_ctx* ctx, const char* who, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, bool lossless, int E,
+                          const uint8_t* d_map, uint8_t* key_mask) {
     const int p = warm_up;
     const bool select = ctx->pred_select != 0, motion = ctx->pred_motion != 0;
     const size_t nmodes = select_count(nt, H, W);
@@ -2386,7 +2383,6 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
         }
     } else if (rc == TZ_OK) {
         const size_t fb = (size_t)nt * H * W * 3;
-        const int E = fabs(b0) >= 255.0 ? 255 : (int)fabs(b0);
         uint8_t* d_dec = nullptr;
         const int* d_lists = nullptr;
         rc = call.alloc(fb, &d_dec);
@@ -2394,11 +2390,15 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
         if (rc == TZ_OK && (select || motion)) rc = select_modes(call, nmodes, nullptr, &d_modes);
         if (rc == TZ_OK && motion) rc = motion_vectors(call, 2 * nmodes, nullptr, &d_vecs);
         if (rc == TZ_OK && hipMemcpyAsync(d_dec, ctx->d_frames, fb, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)   // the key frames
-            rc = tz_fail(ctx, TZ_ERR_HIP, "tz_rollout_closed: copy of the frame stack failed");
+            rc = tz_fail(ctx, TZ_ERR_HIP, "%s: copy of the frame stack failed", who);
         size_t at = 0;
         for (size_t s = 0; s < steps.size() && rc == TZ_OK; at += steps[s].size(), ++s) {
             rc = closed_predict(ctx, steps[s], d_dec);
-            if (rc == TZ_OK && select)   // TZ-PS1 in the step's place: the mode bytes, the chosen tiles in the predictions, dec[t]
+            if (rc == TZ_OK && d_map && select)   // TZ-CLM1: the same two kernels' places, Q under the map
+                rc = tzk_psm_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_modes, d_map, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp);
+            else if (rc == TZ_OK && d_map)
+                rc = tzk_clm_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_map, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp);
+            else if (rc == TZ_OK && select)   // TZ-PS1 in the step's place: the mode bytes, the chosen tiles in the predictions, dec[t]
                 rc = tzk_ps_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_modes, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp, E);
             else if (rc == TZ_OK && motion)   // TZ-PM1 in the step's place: also the vectors
                 rc = tzk_pm_step(ctx, ctx->d_pred, ctx->d_frames, d_dec, d_modes, d_vecs, d_lists + at, (int)steps[s].size(), H, W, ctx->Hp, ctx->Wp, E);
@@ -2421,16 +2421,79 @@ extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int
     ctx->quant_skip = qskip;
     set_rollout(ctx, tz_ctx::ROLLOUT_ENCODE, 0, nt);
     ctx->pred_contract = tz_get_contract(ctx);
-    ctx->loop_closed = 1;
-    ctx->loop_mode = mode;
-    ctx->loop_b0 = b0;
-    ctx->loop_b1 = b1;
-    ctx->loop_quantiser = ctx->quantiser;
+    ctx->loop_closed = 1;   // (the caller adds what the loop ran under)
     ctx->loop_select = select ? 1 : 0;
     ctx->loop_motion = motion ? ctx->pred_motion : 0;
     ctx->pred_modes.swap(modes);
     ctx->pred_vectors.swap(vectors);
     if (key_mask) memcpy(key_mask, key.data(), nt);
+    return TZ_OK;
+}
+
+extern "C" int tz_rollout_closed(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, int mode, double b0,
+                                 double b1, uint8_t* key_mask) {
+    tz_roctx_range roctx_("tz_rollout_closed");
+    if (!ctx) return TZ_ERR_INVALID;
+    ctx->enc_kind = tz_ctx::ENC_NONE;
+    if (window < 0) return tz_fail(ctx, TZ_ERR_INVALID, "window must be >= 0");
+    if (mode < 0 || mode > 3) return tz_fail(ctx, TZ_ERR_INVALID, "unknown error-bound mode %d", mode);
+    if (std::isnan(b0) || (mode == TZ_MODE_ABSREL && std::isnan(b1)))
+        return tz_fail(ctx, TZ_ERR_INVALID, "error bound is NaN (the reference raises on a NaN tolerance)");
+    if (window == 0)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: the closed loop serves fixed windows (window > 0), not the threshold rule");
+    if (nt < warm_up + 2)
+        return tz_fail(ctx, TZ_ERR_INVALID, "need at least warm_up+2 frames (nt=%d, warm_up=%d)", nt, warm_up);
+    // what the loop feeds back: the original where the job's quantiser leaves every delta as it is, else TZ-QL1 under one abs bound
+    const bool lossless = b0 == 0.0 || (mode == TZ_MODE_ABSREL && b1 == 0.0) ||
+                          (ctx->quantiser == 1 ? tz_lattice_is_identity(mode, b0, b1) : tz_quant_is_identity(mode, b0, b1));
+    if (!lossless && ctx->quantiser != 1)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: a lossy closed loop needs the lattice quantiser (tz_set_quantiser(1)): the greedy walk is no function of one sample");
+    if (!lossless && mode != TZ_MODE_ABS)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: a lossy closed loop takes mode abs, not %d: rel bounds depend on whole frames", mode);
+    if (ctx->payload_channels != 3 || !ctx->frame_bounds.empty() || ctx->map_h)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed: the closed loop takes one bound and a three-channel payload (no tz_set_payload_channels(1), tz_set_frame_bounds or tz_set_bound_map)");
+    TZ_TRY(closed_rollout(ctx, "tz_rollout_closed", frames, nt, H, W, warm_up, window, lossless, fabs(b0) >= 255.0 ? 255 : (int)fabs(b0), nullptr,
+                          key_mask));
+    ctx->loop_mode = mode;
+    ctx->loop_b0 = b0;
+    ctx->loop_b1 = b1;
+    ctx->loop_quantiser = ctx->quantiser;
+    return TZ_OK;
+}
+
+// ---- the closed loop under one abs bound per pixel, definition TZ-CLM1 (include/tezip_hip.h: tz_rollout_closed_map; slow statement
+// in tezip_amd/closedmap.py): tz_rollout_closed's loop with E = map[pixel] of the bound map in force.  TZ-BM1 under the lattice
+// quantiser is a pure function of one delta and one tolerance, which is all the loop needs.
+extern "C" int tz_rollout_closed_map(tz_ctx* ctx, const uint8_t* frames, int nt, int H, int W, int warm_up, int window, uint8_t* key_mask) {
+    tz_roctx_range roctx_("tz_rollout_closed_map");
+    if (!ctx) return TZ_ERR_INVALID;
+    ctx->enc_kind = tz_ctx::ENC_NONE;
+    if (window < 0) return tz_fail(ctx, TZ_ERR_INVALID, "window must be >= 0");
+    if (window == 0)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_map: the closed loop serves fixed windows (window > 0), not the threshold rule");
+    if (nt < warm_up + 2 || warm_up < 0)
+        return tz_fail(ctx, TZ_ERR_INVALID, "need at least warm_up+2 frames (nt=%d, warm_up=%d)", nt, warm_up);
+    if (ctx->quantiser != 1)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_map needs the lattice quantiser (tz_set_quantiser(1)): the greedy walk is no function of one sample");
+    if (ctx->payload_channels != 3)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_map: the loop decodes three channels (no tz_set_payload_channels(1))");
+    if (!ctx->frame_bounds.empty())
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_map takes one bound per pixel, not one per frame as well: clear tz_set_frame_bounds first");
+    if (ctx->pred_motion)
+        return tz_fail(ctx, TZ_ERR_UNSUPPORTED, "tz_rollout_closed_map does not serve motion-compensated tiles (tz_set_pred_motion): tz_set_pred_select is served");
+    // (behind the setters' refusals: frame bounds exclude a map at the setters, so "no map" would hide what is in the way)
+    if (!ctx->map_h) return tz_fail(ctx, TZ_ERR_STATE, "tz_rollout_closed_map needs a bound map in force (tz_set_bound_map)");
+    if (ctx->map_h != H || ctx->map_w != W)
+        return tz_fail(ctx, TZ_ERR_INVALID, "tz_rollout_closed_map: the bound map is %d x %d (tz_set_bound_map), the frames are %d x %d: a map has the frames' own size",
+                       ctx->map_h, ctx->map_w, H, W);
+    TZ_TRY(closed_rollout(ctx, "tz_rollout_closed_map", frames, nt, H, W, warm_up, window, ctx->map_max == 0, 0, ctx->d_bound_map, key_mask));
+    ctx->loop_mode = TZ_MODE_ABS;
+    ctx->loop_b0 = ctx->loop_b1 = 0.0;
+    ctx->loop_quantiser = 1;
+    ctx->loop_map = 1;
+    ctx->loop_map_h = ctx->map_h;
+    ctx->loop_map_w = ctx->map_w;
+    ctx->loop_map_bytes = ctx->map_host;
     return TZ_OK;
 }
 

@@ -5950,6 +5950,110 @@ int tzk_clf_step(tz_ctx* ctx, const float* pred, const uint8_t* orig, uint8_t* d
     return TZ_OK;
 }
 
+// ------------------------------------------------------------------------ closed loop, one abs bound per pixel (TZ-CLM1)
+// tz_rollout_closed_map (include/tezip_hip.h; slow statement in tezip_amd/closedmap.py): TZ-CL1 with the
+// radius E = map[pixel] of the context's own H * W byte map (tz_set_bound_map), shared by every frame and channel and read through
+// the cache.  k_clm_step takes k_cl_step's place.  A lane owns WHOLE pixels, so that its tolerances are one aligned load:
+//   CLM_FLAT  (stacks on 16-byte boundaries, an unpadded frame: H * W is a multiple of 64)  group g = pixels 16 g .. 16 g + 15 of
+//             the frame: one 16-byte load of the map, three of orig, twelve of pred, three 16-byte stores of dec
+//   CLM_ROWS  (stacks on 16-byte boundaries, a padded frame whose W is a multiple of 16)  the same group inside one row of the
+//             crop: pixel (y, x0) with y = g / (W / 16), x0 = 16 (g % (W / 16)); every address stays a 16-byte multiple
+//   CLM_SCALAR (a stack off its boundary, or a W that does not divide)  one pixel a lane and trip, byte by byte
+// The division (|d| + E) div (2 E + 1) has a divisor that varies per pixel: one v_rcp_f32 per pixel, shared by its three channels,
+// and trunc((f32(|d| + E) + 0.5f) * r) per sample -- exact for every numerator and E the quantiser meets, whatever the last bit of
+// r (closedmap.div_shortcut; tests/test_closedmap.py walks all 511 x 256 pairs with r one ulp either way).
+enum { CLM_SCALAR = 0, CLM_FLAT = 1, CLM_ROWS = 2 };
+
+__device__ __forceinline__ float clm_rcp(unsigned E) { return __builtin_amdgcn_rcpf((float)(2u * E + 1u)); }
+
+__device__ __forceinline__ int clm_quant(int d, unsigned E, float r) {   // (ps_quant's q with the pixel's E)
+    const unsigned ad = (unsigned)(d < 0 ? -d : d), s = 2u * E + 1u;
+    const unsigned k = (unsigned)(((float)(ad + E) + 0.5f) * r);
+    const int m = (int)min(k * s, 255u);
+    return E ? (d < 0 ? -m : m) : d;
+}
+
+__device__ __forceinline__ unsigned clm_sample(float p, int o, unsigned E, float r) {
+    const int x = (int)(p * 255.0f), v = x - clm_quant(x - o, E, r);
+    return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+template <int FORM>
+__global__ __launch_bounds__(256) void k_clm_step(const float* __restrict__ pred, const uint8_t* __restrict__ orig, uint8_t* __restrict__ dec,
+                                                  const uint8_t* __restrict__ map, const int* __restrict__ list, int H, int W, int Hp, int Wp) {
+    const size_t f = (size_t)list[blockIdx.y];
+    const size_t npix = (size_t)H * W, base = f * npix * 3;
+    const float* pf = pred + f * (size_t)Hp * Wp * 3;
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (FORM == CLM_SCALAR) {
+        for (size_t i = t0; i < npix; i += stride) {
+            const size_t y = i / (size_t)W, x = i - y * (size_t)W;
+            const float* pp = pf + (y * Wp + x) * 3;
+            const unsigned E = map[i];
+            const float r = clm_rcp(E);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dec[base + 3 * i + c] = (uint8_t)clm_sample(pp[c], (int)orig[base + 3 * i + c], E, r);
+        }
+        return;
+    }
+    const size_t rowg = (size_t)W / 16;                                          // (CLM_ROWS: groups a row)
+    const size_t ngroups = FORM == CLM_FLAT ? npix / 16 : (size_t)H * rowg;
+    for (size_t g = t0; g < ngroups; g += stride) {
+        size_t pix, pat;                                                         // first pixel in the unpadded stacks / in pred
+        if (FORM == CLM_FLAT) {
+            pix = pat = 16 * g;
+        } else {
+            const size_t y = g / rowg, x0 = 16 * (g - y * rowg);
+            pix = y * W + x0;
+            pat = y * Wp + x0;
+        }
+        const uint4 m4 = *(const uint4*)(map + pix);
+        const unsigned mw[4] = {m4.x, m4.y, m4.z, m4.w};
+        const uint4* o4 = (const uint4*)(orig + base + 3 * pix);
+        const float4* p4 = (const float4*)(pf + 3 * pat);
+        uint4* d4 = (uint4*)(dec + base + 3 * pix);
+#pragma unroll
+        for (int h = 0; h < 3; ++h) {                                            // 16 samples = pixels 5 1/3 h .. of the group
+            const uint4 o = o4[h];
+            const unsigned ow[4] = {o.x, o.y, o.z, o.w};
+            float p[16];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4 v = p4[4 * h + j];
+                p[4 * j] = v.x; p[4 * j + 1] = v.y; p[4 * j + 2] = v.z; p[4 * j + 3] = v.w;
+            }
+            unsigned b[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int px = (16 * h + j) / 3;                                 // (a constant after unrolling)
+                const unsigned E = (mw[px >> 2] >> (8 * (px & 3))) & 0xFFu;
+                b[j] = clm_sample(p[j], (int)((ow[j >> 2] >> (8 * (j & 3))) & 0xFFu), E, clm_rcp(E));   // (one rcp a pixel after CSE)
+            }
+            uint4 out;
+            out.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+            out.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+            out.z = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+            out.w = b[12] | (b[13] << 8) | (b[14] << 16) | (b[15] << 24);
+            d4[h] = out;
+        }
+    }
+}
+
+// d_map: the H * W byte map (device).  FLAT / vec are chosen as cl_launch chooses them; the grid is cl_launch's.
+int tzk_clm_step(tz_ctx* ctx, const float* pred, const uint8_t* orig, uint8_t* dec, const uint8_t* d_map, const int* d_list, int nlist, int H,
+                 int W, int Hp, int Wp) {
+    if (nlist <= 0) return TZ_OK;
+    const bool vec = (((uintptr_t)dec | (uintptr_t)orig | (uintptr_t)pred | (uintptr_t)d_map) & 15) == 0;
+    const int form = vec && H == Hp && W == Wp ? CLM_FLAT : (vec && W % 16 == 0 ? CLM_ROWS : CLM_SCALAR);
+    const dim3 grid = clf_grid(nlist, H, W);
+    tz_prof_scope ps(ctx, TZP_QUANT);
+    if (form == CLM_FLAT) hipLaunchKernelGGL(k_clm_step<CLM_FLAT>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, d_map, d_list, H, W, Hp, Wp);
+    else if (form == CLM_ROWS) hipLaunchKernelGGL(k_clm_step<CLM_ROWS>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, d_map, d_list, H, W, Hp, Wp);
+    else hipLaunchKernelGGL(k_clm_step<CLM_SCALAR>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, d_map, d_list, H, W, Hp, Wp);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
+}
+
 // ------------------------------------------------------------------------ per-tile choice of the prediction (TZ-PS1)
 // tz_set_pred_select (include/tezip_hip.h; slow statement in tezip_amd/predselect.py): in a closed loop every
 // 16 x 16 tile of a predicted frame takes whichever of x_net = (int)(pred * 255.0f) and x_prev = dec[t-1] leaves the smaller
@@ -5979,9 +6083,13 @@ __device__ __forceinline__ int ps_quant(int d, int E) {   // (cl_sample's q)
 
 __device__ __forceinline__ float ps_pv(unsigned v) { return v == 255u ? 1.0f : ((float)v + 0.5f) / 255.0f; }
 
-template <int KIND, bool VEC>
+// MAP (TZ-CLM1, tz_rollout_closed_map): Q takes the pixel's own E = map[y * W + x] in place of the uniform one -- the lane's four
+// tolerances are one 4-byte load where VEC holds, else byte by byte with the crop check -- and divides by clm_quant's reciprocal,
+// one per pixel.  Without MAP the map is never read and the instruction stream is what it was.
+template <int KIND, bool VEC, bool MAP = false>
 __device__ __forceinline__ void ps_strips(float* pred, const uint8_t* orig, const uint8_t* prev, const int16_t* __restrict__ qs, uint8_t* dec,
-                                          uint8_t* modes, const int* __restrict__ list, int H, int W, int Hp, int Wp, int TH, int TW, int E) {
+                                          uint8_t* modes, const int* __restrict__ list, int H, int W, int Hp, int Wp, int TH, int TW, int E,
+                                          const uint8_t* __restrict__ map = nullptr) {
     __shared__ unsigned s_cost[2][4][PS_STRIP][2];
     const int f = list[blockIdx.y];
     const unsigned row = (unsigned)W * 3u, pitch = (unsigned)Wp * 3u;
@@ -6001,11 +6109,27 @@ __device__ __forceinline__ void ps_strips(float* pred, const uint8_t* orig, cons
         int xn[12], o[12], v[12];
 #pragma unroll
         for (int j = 0; j < 12; ++j) xn[j] = o[j] = v[j] = 0;
+        unsigned pe[4] = {0u, 0u, 0u, 0u};                   // MAP: the tolerances of the lane's pixels and 1 / (2 E + 1)
+        float pr[4] = {1.0f, 1.0f, 1.0f, 1.0f};
         if (active) {
             const float4 a = ((const float4*)pf)[0], b = ((const float4*)pf)[1], c = ((const float4*)pf)[2];
             const float p[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
 #pragma unroll
             for (int j = 0; j < 12; ++j) xn[j] = (int)(p[j] * 255.0f);
+            if (MAP) {
+                const size_t mat = (size_t)y * W + x0;
+                if (VEC) {
+                    const unsigned mw = *(const unsigned*)(map + mat);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) pe[i] = (mw >> (8 * i)) & 0xFFu;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (3 * i < ns) pe[i] = map[mat + i];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pr[i] = clm_rcp(pe[i]);
+            }
             if (VEC) {
                 const unsigned* pw = (const unsigned*)(prev + at - fe);
                 const unsigned w0[3] = {pw[0], pw[1], pw[2]};
@@ -6034,7 +6158,8 @@ __device__ __forceinline__ void ps_strips(float* pred, const uint8_t* orig, cons
 #pragma unroll
             for (int j = 0; j < 12; ++j)
                 if (j < ns) {
-                    const int qn = ps_quant(xn[j] - o[j], E), qp = ps_quant(v[j] - o[j], E);
+                    const int qn = MAP ? clm_quant(xn[j] - o[j], pe[j / 3], pr[j / 3]) : ps_quant(xn[j] - o[j], E);
+                    const int qp = MAP ? clm_quant(v[j] - o[j], pe[j / 3], pr[j / 3]) : ps_quant(v[j] - o[j], E);
                     cn += (unsigned)(qn < 0 ? -qn : qn);
                     cp += (unsigned)(qp < 0 ? -qp : qp);
                 }
@@ -6078,7 +6203,7 @@ __device__ __forceinline__ void ps_strips(float* pred, const uint8_t* orig, cons
             } else {
 #pragma unroll
                 for (int j = 0; j < 12; ++j) {
-                    const int x = m ? v[j] : xn[j], r = x - ps_quant(x - o[j], E);
+                    const int x = m ? v[j] : xn[j], r = x - (MAP ? clm_quant(x - o[j], pe[j / 3], pr[j / 3]) : ps_quant(x - o[j], E));
                     b[j] = (unsigned)(r < 0 ? 0 : (r > 255 ? 255 : r));
                 }
             }
@@ -6125,6 +6250,14 @@ __global__ __launch_bounds__(256) void k_ps_recon(float* pred, const int16_t* __
     ps_strips<PS_RECON, VEC>(pred, nullptr, dec, qs, dec, const_cast<uint8_t*>(modes), list, H, W, Hp, Wp, TH, TW, 0);
 }
 
+// TZ-CLM1: k_ps_step with Q under the map.  A map that is zero in some region only is still lossy and comes here; the all-zero map
+// is the lossless job and takes k_ps_select as it is, so k_ps_select has no map form: nothing would launch it.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_psm_step(float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, const uint8_t* __restrict__ map,
+                                                  const int* __restrict__ list, int H, int W, int Hp, int Wp, int TH, int TW) {
+    ps_strips<PS_STEP, VEC, true>(pred, orig, dec, nullptr, dec, modes, list, H, W, Hp, Wp, TH, TW, 0, map);
+}
+
 int tzk_ps_grid(int H, int W) {
     const int TH = (H + PS_TILE - 1) / PS_TILE, TW = (W + PS_TILE - 1) / PS_TILE;
     return std::min(TH * ((TW + PS_STRIP - 1) / PS_STRIP), (int)PS_GRID);
@@ -6160,6 +6293,20 @@ int tzk_ps_select(tz_ctx* ctx, float* pred, const uint8_t* orig, uint8_t* modes,
 int tzk_ps_step(tz_ctx* ctx, float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, const int* d_list, int nlist, int H, int W, int Hp,
                 int Wp, int E) {
     return ps_launch(ctx, PS_STEP, pred, orig, nullptr, dec, modes, d_list, nlist, H, W, Hp, Wp, E);
+}
+
+int tzk_psm_step(tz_ctx* ctx, float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, const uint8_t* d_map, const int* d_list, int nlist,
+                 int H, int W, int Hp, int Wp) {
+    if (nlist <= 0) return TZ_OK;
+    const int TH = (H + PS_TILE - 1) / PS_TILE, TW = (W + PS_TILE - 1) / PS_TILE;
+    const bool vec = W % 4 == 0 && (((uintptr_t)orig | (uintptr_t)dec | (uintptr_t)d_map) & 3) == 0;   // (ps_launch's rule, and the map's words)
+    if ((uintptr_t)pred & 15) return tz_fail(ctx, TZ_ERR_INVALID, "the prediction stack is off the 16-byte boundary");
+    const dim3 grid((unsigned)tzk_ps_grid(H, W), (unsigned)nlist);
+    tz_prof_scope ps(ctx, TZP_QUANT);
+    if (vec) hipLaunchKernelGGL(k_psm_step<true>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, modes, d_map, d_list, H, W, Hp, Wp, TH, TW);
+    else hipLaunchKernelGGL(k_psm_step<false>, grid, dim3(256), 0, ctx->stream, pred, orig, dec, modes, d_map, d_list, H, W, Hp, Wp, TH, TW);
+    TZ_HIP(ctx, hipGetLastError());
+    return TZ_OK;
 }
 
 int tzk_ps_recon(tz_ctx* ctx, float* pred, const int16_t* q, uint8_t* dec, const uint8_t* modes, const int* d_list, int nlist, int H, int W,

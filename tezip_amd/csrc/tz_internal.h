@@ -94,6 +94,10 @@ struct tz_ctx {
     // bounds); loop_trace: the search's TZ_CLF_ROUNDS * nt sums, round-major, ~0 where a round did not run (empty: given bounds)
     int loop_frames = 0;
     std::vector<double> loop_bounds;
+    // tz_rollout_closed_map (TZ-CLM1): the stamped loop ran under the bound map loop_map_bytes of loop_map_h x loop_map_w (a copy of
+    // the bytes: setting an equal map again still serves the job); map_host: the bytes of the map in force
+    int loop_map = 0, loop_map_h = 0, loop_map_w = 0;
+    std::vector<uint8_t> loop_map_bytes, map_host;
     std::vector<unsigned long long> loop_frame_sse, loop_trace;
     // tz_set_pred_select (TZ-PS1): the setting; whether the stamped loop ran under it (part of the stamp: predictions with chosen
     // tiles expressed in them serve a select job alone, and the other way round); the modes of that loop (nt * TH * TW bytes,
@@ -521,6 +525,11 @@ int tzk_clf_probe(tz_ctx*, const float* pred, const uint8_t* orig, const int* d_
                   unsigned long long* d_sse, int nt, unsigned long long limit);
 int tzk_clf_step(tz_ctx*, const float* pred, const uint8_t* orig, uint8_t* dec, const int* d_list, int nlist, int H, int W, int Hp, int Wp,
                  const int* d_radius, const unsigned long long* d_sse, int nt, unsigned long long limit, int* d_k, unsigned long long* d_sse_out);
+// TZ-CLM1 (tz_rollout_closed_map): tzk_cl_step / tzk_ps_step with E = d_map[pixel], the H * W byte bound map on the device
+int tzk_clm_step(tz_ctx*, const float* pred, const uint8_t* orig, uint8_t* dec, const uint8_t* d_map, const int* d_list, int nlist, int H,
+                 int W, int Hp, int Wp);
+int tzk_psm_step(tz_ctx*, float* pred, const uint8_t* orig, uint8_t* dec, uint8_t* modes, const uint8_t* d_map, const int* d_list, int nlist,
+                 int H, int W, int Hp, int Wp);
 // per-tile choice of the prediction TZ-PS1 (tezip_amd/predselect.py) on the same frames and stacks; modes: nt * ceil(H/16) * ceil(W/16)
 // bytes on the device, frame-major.  Per 16 x 16 tile, x_prev = the frame in front (orig[t-1] for tzk_ps_select, dec[t-1] for the
 // others) replaces x_net = the truncated prediction iff it leaves the smaller sum |Q(x - orig)| (TZ-QL1 with E, the identity for

@@ -15,7 +15,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "tezip_amd"
 
-from . import boundmap, closedframes, closedloop, compress, decompress, frametarget, predmotion, predselect, sdauto, target, train  # noqa: E402
+from . import boundmap, closedframes, closedloop, closedmap, compress, decompress, frametarget, predmotion, predselect, sdauto, target, train  # noqa: E402
 
 # (short, long, argparse keywords) -- tezip.py:88-99
 FLAG_TABLE = (
@@ -133,6 +133,11 @@ FLAG_TABLE = (
     # loop, from a JSON file as --frame-bounds reads it (the bound_search.json of a --loop-psnr job replays); entries at frames that
     # are stored exactly are taken as 0 (compress.run(LOOP_BOUNDS=FILE))
     (None, "--loop-bounds", dict(type=str, default=None, metavar="FILE", dest="loop_bounds")),
+    # not in the reference: with -c --loop closed --quant lattice -m abs, IN PLACE of -b: one abs bound per pixel for the closed
+    # loop, from what --bound-map reads (a .npy holding a 2-D uint8 array, or a single-channel image of the images' own size); with
+    # --pred select the tiles are chosen under that map (definition TZ-CLM1 in tezip_amd/closedmap.py).  -u needs no flag
+    # (compress.run(LOOP_MAP=FILE))
+    (None, "--loop-map", dict(type=str, default=None, metavar="FILE", dest="loop_map")),
 )
 
 TEXT = {
@@ -340,6 +345,28 @@ def check_closedframes_flags(arg):
     return None
 
 
+def check_closedmap_flag(arg):
+    """--loop-map goes with -c --loop closed --quant lattice -m abs of one single-GPU job, in place of -b.  The file is read here
+    (its size is checked once the images are listed).  Returns None, or the message of a refusal."""
+    path = getattr(arg, "loop_map", None)
+    if path is None:
+        return None
+    problem = closedmap.check_flags(
+        path, getattr(arg, "loop", None), getattr(arg, "quant", None), arg.mode[0] if arg.mode else None, arg.bound or [],
+        getattr(arg, "pred", None), arg.compress is not None and arg.uncompress is None and arg.learn is None,
+        getattr(arg, "sweep", None) is not None, int(os.environ.get("WORLD_SIZE", "1")) > 1, bool(getattr(arg, "gray", False)),
+        arg.threshold[0] if arg.threshold is not None else None, getattr(arg, "target_psnr", None), getattr(arg, "target_ratio", None),
+        bool(getattr(arg, "per_frame", False)), getattr(arg, "frame_bounds", None), getattr(arg, "bound_map", None),
+        getattr(arg, "loop_psnr", None), getattr(arg, "loop_bounds", None))
+    if problem:
+        return problem
+    try:
+        closedmap.load(path)
+    except ValueError as e:
+        return str(e)
+    return None
+
+
 def check_pred_flag(arg):
     """--pred is valid with -c only; `select` and `motion` need --loop closed.  Returns None, or the message of a refusal."""
     pred = getattr(arg, "pred", None)
@@ -484,6 +511,10 @@ def _main(arg):
     if problem:   # exit status 2, as decompress.adopt_contract's errors: nothing was written
         print("ERROR:", problem)
         sys.exit(2)
+    problem = check_closedmap_flag(arg)
+    if problem:   # likewise (in front of every other check: a refusal of this job names the flag that defines it)
+        print("ERROR:", problem)
+        sys.exit(2)
     problem = check_closedframes_flags(arg)
     if problem:   # likewise (in front of --loop's check: a refusal of this job names the flag that defines it)
         print("ERROR:", problem)
@@ -576,7 +607,7 @@ def _main(arg):
     loop_db, loop_file = getattr(arg, "loop_psnr", None), getattr(arg, "loop_bounds", None)
     if loop_db is not None:   # an `abs` job whose bounds the closed loop finds: the same checks, and `abs` is printed
         problem = check_compress(argparse.Namespace(**dict(vars(arg), mode=["abs"], bound=[0.0])))
-    elif loop_file is not None:   # an `abs` job whose bounds come from the file
+    elif loop_file is not None or getattr(arg, "loop_map", None) is not None:   # an `abs` job whose bounds come from the file
         problem = check_compress(argparse.Namespace(**dict(vars(arg), bound=[0.0])))
     elif bounds_file is not None or map_file is not None:   # an `abs` job whose bounds come from the file: the same checks with a bound in -b's place
         problem = check_compress(argparse.Namespace(**dict(vars(arg), bound=[0.0])))
@@ -600,6 +631,13 @@ def _main(arg):
                             DIGESTS=bool(getattr(arg, "digests", False)), SDELTA=getattr(arg, "sdelta", None) or "flat",
                             SSIM=bool(getattr(arg, "ssim", False)), QUANT="lattice", LOOP="closed",
                             **({"LOOP_PSNR": loop_db} if loop_db is not None else {"LOOP_BOUNDS": loop_file}))
+    if getattr(arg, "loop_map", None) is not None:   # TZ-CLM1 (likewise)
+        return compress.run(model, src, dst, arg.preprocess[0], window, threshold, "abs", [], gpu, arg.verbose,
+                            arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
+                            CODER=getattr(arg, "coder", "zstd"), KEY_CODER=getattr(arg, "key_coder", "zstd"),
+                            DIGESTS=bool(getattr(arg, "digests", False)), SDELTA=getattr(arg, "sdelta", None) or "flat",
+                            SSIM=bool(getattr(arg, "ssim", False)), QUANT="lattice", LOOP="closed", LOOP_MAP=arg.loop_map,
+                            **({"PRED": "select"} if getattr(arg, "pred", None) == "select" else {}))
     if getattr(arg, "loop", None) == "closed":   # (open is the job without the flag: the calls below; every other flag travels with it)
         return compress.run(model, src, dst, arg.preprocess[0], window, threshold, arg.mode[0], arg.bound, gpu, arg.verbose,
                             arg.no_entropy, SHUFFLE=arg.shuffle, REPORT=bool(getattr(arg, "report", False)),
